@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — env-steps/sec of the batched ShipEnv hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set-up, burn-in, device conditioning, W warm-up steps, ONE timed region of exactly
+K steps (`ms_per_step` = its wall time / K), the outputs of its last step under DIR with --dump-outputs, and the JSON line.
+--full adds everything else, as measured before it existed: five timed repeats of K steps (value = the median), the device-copy
+roofline, the one-launch-per-step path, `other_configs`, configs[4] at --gpus 8 and `cpu_baseline`; fields a plain run does not
+measure are null.  The inputs (map bank, Philox actions, burn-in) depend on the arguments only, so two builds can be compared
+output for output with --dump-outputs.
 
 One process per GPU.  With N > 1 and no torch.distributed environment (RANK unset) this process is only a
 LAUNCHER: it touches no GPU, starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child
@@ -18,7 +25,7 @@ loop consumes, train/random.py:14-27; SURVEY.md 8d: "obs/reward/done materialise
 233 B per env-step of outputs physically reach HBM instead of being rewritten in place inside the 256 MiB Infinity
 Cache; done envs are auto-reset in-kernel.  Workload at N=1: BASELINE.json configs[2] — 65 536 parallel envs, 1 ship,
 8-beam lidar, default 600x600 map bank (64 maps), SPEED 10 — the configuration the ">= 10 M env-steps/s on one
-MI355X" target is quoted on.  With --gpus 8 rank 0 also times BASELINE configs[4] (131 072 envs per rank x 8 =
+MI355X" target is quoted on.  With --gpus 8 --full rank 0 also times BASELINE configs[4] (131 072 envs per rank x 8 =
 1 048 576 envs, 10 beams) as `other_configs.c5_full` (all ranks step, MAX over ranks).
 
 TEST-ONLY overrides (tests/test_sharding_gpu.py; never set by the driver): SSG_BENCH_SHARE_DEVICE=1 puts every rank
@@ -29,11 +36,13 @@ Timing: the timed env is reset and stepped `--burn-in-steps` (default 1 000, `bu
 its episodes are no longer phase-locked; then an untimed, time-based device conditioning (`--precondition-ms`, default 300: the same K-step rollout on a SCRATCH env and
 scratch buffers, bracketed by synchronize exactly like a timed repeat and repeated until the time is up, reported as
 `preconditioning_ms`; every trajectory buffer set is written once beforehand), then W untimed warm-up steps, then the K-step
-rollout is timed `--repeats` (default 5) times (`repeats_min_ms` / `repeats_median_ms` / `repeats_max_ms`; the shader clock the
+rollout is timed `--repeats` (default 1; 5 with --full) times (`repeats_min_ms` / `repeats_median_ms` / `repeats_max_ms`; the shader clock the
 step kernel recorded during each repeat in `repeats_shader_clock_ghz`: no probe kernel runs between repeats), every repeat
 bracketed by barrier + torch.cuda.synchronize() on both sides (a rank's interval runs from the opening barrier + synchronize
 to its own closing synchronize; the closing barrier follows) and reduced with MAX over ranks; `value` is the
-MEDIAN repeat, all repeats are listed in `repeats_ms`.
+MEDIAN repeat, all repeats are listed in `repeats_ms`.  A trajectory buffer set holds at most
+TRAJ_RING_BYTES: a longer repeat streams through the sets in pieces of whole launches, and past ACT_RING_BYTES of actions
+step g takes the action row g % rows (both only at K far beyond a few thousand steps of 65 536 envs).
 
 Rank 0 prints ONE JSON line (see the driver contract) with extra objects:
   roofline      — `achieved` / `frac`: algorithmic HBM bytes per launch (675 B/env-step at S=1, nb=8,
@@ -44,13 +53,13 @@ Rank 0 prints ONE JSON line (see the driver contract) with extra objects:
                   that stored profile and reported only when the profile was taken on this very kernel source
                   (sha256 of csrc/ + include/ recorded in the profile == the tree's); otherwise they are null.
                   `bound` is what those counters say binds the kernel, not a label.
-  other_configs — informational (N=1 only, outside the timed region): BASELINE configs[1] (4 096 envs, 10 beams),
+  other_configs — informational (--full, N=1 only, outside the timed region): BASELINE configs[1] (4 096 envs, 10 beams),
                   configs[3] (65 536 envs x 4 ships), the per-GPU share of configs[4], configs[2] with a brand-new world
                   per episode (map_mode="fresh_device"), and the one-launch-per-step (policy-in-the-loop) path.
   config.ranks  — per rank: device, HIP ordinal, the RCCL world size it saw, its env range and the HSA / HIP / NCCL / RCCL /
                   rendezvous environment it ran under (a rank that cannot join the job prints the same to stderr, exit 4).
   cpu_baseline  — the CPU oracle ("port": our C restatement of the reference path, NOT pymunk) timed on this box's
-                  host cores on a bounded sample of the same workload (rank 0, N=1 only).
+                  host cores on a bounded sample of the same workload (--full, rank 0, N=1 only).
 """
 import argparse
 import json
@@ -70,6 +79,7 @@ ENVS_PER_GPU = 65536
 N_BEAMS = 8
 VALU_ISSUE_PEAK = 1024 * 2.4e9 / 4.0  # 256 CUs x 4 SIMDs, one FP64 wave64 VALU instruction per 4 cycles at 2.4 GHz
 TRAJ_RING_BYTES = 48 << 30            # at most this much HBM for the bench's trajectory buffers
+ACT_RING_BYTES = 32 << 30             # at most this much HBM for the pre-generated actions of the warm-up + timed steps
 N_MAPS = int(os.environ.get("SSG_BENCH_MAPS", "64"))  # BASELINE workload: 64; override only for experiments
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E, /opt/skills/guides/MI355X_MICROARCH.md
 
@@ -434,10 +444,10 @@ def launch_clock(vec, buf_row):
             "ssg_debug_launch_clock")
 
 
-def bracketed_rollout(vec, a, out, use_dist):
-    """ONE repeat: exactly a.shape[0] trajectory-mode steps bracketed by barrier + synchronize on both sides.  Returns (wall
-    seconds of this rank, HIP-event ms).  The device conditioning runs this very function on a scratch env, so the timed repeats
-    continue the launch / wait pattern the GPU is already in."""
+def bracketed_rollout(vec, pieces, use_dist):
+    """ONE repeat: the trajectory-mode steps of `pieces` ((actions [k, N], buffer set) pairs, back to back, no wait in between)
+    bracketed by barrier + synchronize on both sides.  Returns (wall seconds of this rank, HIP-event ms).  The device conditioning
+    runs this very function on a scratch env, so the timed repeats continue the launch / wait pattern the GPU is already in."""
     import torch
     import torch.distributed as dist
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -447,7 +457,8 @@ def bracketed_rollout(vec, a, out, use_dist):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     ev0.record()
-    vec.rollout_tensor(a, trajectory=True, out=out)  # exactly K steps: ceil(K / steps_per_launch) launches of the step kernel
+    for a, out in pieces:  # a.shape[0] steps each: ceil(a.shape[0] / steps_per_launch) launches of the step kernel
+        vec.rollout_tensor(a, trajectory=True, out=out)
     ev1.record()
     torch.cuda.synchronize()
     t1 = time.perf_counter()  # this rank's K steps are complete; the job's time is the MAX over ranks (below), so the
@@ -475,7 +486,7 @@ def precondition(pvec, pacts, pouts, min_ms, use_dist, dev):
     rounds = 0
     while True:  # chunks of 16 bracketed rollouts until EVERY rank has run for min_ms (the ranks' barriers must pair up)
         for _ in range(16):
-            bracketed_rollout(pvec, pacts, pouts[rounds % len(pouts)], use_dist)  # (rotating over as many sets as the repeats do)
+            bracketed_rollout(pvec, [(pacts, pouts[rounds % len(pouts)])], use_dist)  # (rotating over as many sets as the repeats do)
             rounds += 1
         more = (time.perf_counter() - t0) * 1e3 < min_ms
         if use_dist:
@@ -487,23 +498,48 @@ def precondition(pvec, pacts, pouts, min_ms, use_dist, dev):
     return (time.perf_counter() - t0) * 1e3, rounds
 
 
-def timed_rollouts(vec, K, W, R, use_dist, dev, precondition_ms=0.0, pvec=None, burn_in=0):
+def timed_rollouts(vec, K, W, R, use_dist, dev, precondition_ms=0.0, pvec=None, burn_in=0, keep_last=False):
     """Device conditioning (untimed, scratch env and buffers), W untimed warm-up steps, then R timed repeats of exactly K
     trajectory-mode steps, each bracketed by barrier + synchronize on both sides; returns (wall seconds per repeat, MAX over ranks;
-    HIP-event ms per repeat; buffer sets; the shader clock GHz the step kernel itself recorded in every repeat; preconditioning info)."""
+    HIP-event ms per repeat; buffer sets; steps per buffer set; the shader clock GHz the step kernel itself recorded in every
+    repeat; preconditioning info; with keep_last, the outputs of the last timed step as host arrays (obs, reward, done, flags))."""
     import torch
     import torch.distributed as dist
-    acts = vec.random_actions(12345, 0, W + K * R)  # int32 [W + R*K, n], generated on device before any timed region
-    per_set = traj_bytes_per_step(vec.num_envs, vec.states_history) * K
-    n_bufs = max(1, min(R, int(TRAJ_RING_BYTES // per_set)))
-    bufs = traj_buffers(vec, K, n_bufs)  # distinct slots per repeat: a repeat never rewrites lines still in the Infinity Cache
+    n = vec.num_envs
+    per_step = traj_bytes_per_step(n, vec.states_history)
+    # steps per buffer set: all K while a set of K steps fits TRAJ_RING_BYTES, otherwise as many whole launches as fit; a longer
+    # repeat then streams through the sets in pieces of that many steps (every step's outputs still land in HBM)
+    cap, spl = max(1, TRAJ_RING_BYTES // per_step), steps_per_launch_cfg()
+    S = K if K <= cap else max(min(cap, spl), cap // spl * spl)
+    n_pieces = (K + S - 1) // S
+    # the conditioning and the warm-up write as many sets as five repeats rotate over whatever R is, so that a single timed repeat
+    # meets the cache and memory state the first of five would
+    n_rot = max(1, min(max(R, 5) * n_pieces, int(TRAJ_RING_BYTES // (per_step * S))))
+    n_bufs = min(n_rot, R * n_pieces)
+    # int32 action rows, generated on device before any timed region: row g is step g of the warm-up + timed steps, all of them
+    # while they fit ACT_RING_BYTES; past that the rows are a ring and step g takes row g % A
+    total = W + K * R
+    A = total if total * 4 * n <= ACT_RING_BYTES else max(S, ACT_RING_BYTES // (4 * n) // S * S)
+    acts = vec.random_actions(12345, 0, A)
+
+    def pieces(g, m, b, sets):
+        """(action rows, buffer set) pieces of at most S steps for steps g .. g + m - 1, sets rotating from piece number b."""
+        out = []
+        while m > 0:
+            r0 = g % A
+            k = min(m, S, A - r0)
+            out.append((acts[r0: r0 + k], sets[b % len(sets)]))
+            g, m, b = g + k, m - k, b + 1
+        return out
+
+    bufs = traj_buffers(vec, S, n_bufs)  # distinct slots per repeat: a repeat never rewrites lines still in the Infinity Cache
     for set_ in bufs:                     # pre-touch: no repeat is the first writer of its buffer set's pages,
         for t in set_:                    # nor the first call that hands this set to rollout_tensor (its checked slow path)
             t.zero_()
         vec.rollout_tensor(acts[:1], trajectory=True, out=set_)  # (before the reset below: the env starts over afterwards)
     wbuf = bufs[0]
-    if n_bufs > 1:  # the warm-up steps get a set of their own: no repeat finds lines of ITS set still in the Infinity Cache
-        wbuf = traj_buffers(vec, K, 1)[0]
+    if n_rot > 1:  # the warm-up steps get a set of their own: no repeat finds lines of ITS set still in the Infinity Cache
+        wbuf = traj_buffers(vec, S, 1)[0]
         for t in wbuf:
             t.zero_()
         vec.rollout_tensor(acts[:1], trajectory=True, out=wbuf)
@@ -525,34 +561,58 @@ def timed_rollouts(vec, K, W, R, use_dist, dev, precondition_ms=0.0, pvec=None, 
         vec.rollout_tensor(vec.random_actions(777, b0, min(200, burn_in - b0)))
     pre = {"preconditioning_ms": 0.0, "preconditioning_launches": 0}
     if precondition_ms > 0 and pvec is not None:
-        pacts = pvec.random_actions(4321, 0, K)
-        pouts = traj_buffers(pvec, K, n_bufs) if n_bufs > 1 else [bufs[0]]  # (a 30 GB set is not allocated twice)
+        pacts = pvec.random_actions(4321, 0, S)
+        pouts = traj_buffers(pvec, S, n_rot) if n_rot > 1 else [bufs[0]]  # (a 30 GB set is not allocated twice)
         for set_ in pouts:
             for t in set_:
                 t.zero_()
         ms, nl = precondition(pvec, pacts, pouts, precondition_ms, use_dist, dev)
         pre = {"preconditioning_ms": ms, "preconditioning_launches": nl,
                "preconditioning": "%d rollouts of %d steps of the same kernel on a scratch env and scratch trajectory buffers, each "
-                                  "bracketed by synchronize like a timed repeat, untimed, before the warm-up steps" % (nl, K)}
-    # warm-up: the same kernel in the same output mode, bracketed like a repeat (chunks of <= K steps into a set of their own)
-    for w0 in range(0, W, K):
-        bracketed_rollout(vec, acts[w0: min(W, w0 + K)], wbuf, use_dist)
+                                  "bracketed by synchronize like a timed repeat, untimed, before the warm-up steps" % (nl, S)}
+    # warm-up: the same kernel in the same output mode, bracketed like a repeat (chunks of <= S steps into a set of their own)
+    for p in pieces(0, W, 0, [wbuf]):
+        bracketed_rollout(vec, [p], use_dist)
+    plan = [pieces(W + r * K, K, r * n_pieces, bufs) for r in range(R)]
     walls, evs = [], []
     for r in range(R):
         launch_clock(vec, clk[r])
-        w, e = bracketed_rollout(vec, acts[W + r * K: W + (r + 1) * K], bufs[r % n_bufs], use_dist)
+        w, e = bracketed_rollout(vec, plan[r], use_dist)
         walls.append(w); evs.append(e)
     gc.enable()
     launch_clock(vec, None)
+    last = None
+    if keep_last:  # what a caller of the timed path receives for its last step: that step's row of each trajectory tensor
+        a, out = plan[-1][-1]
+        last = tuple(t[a.shape[0] - 1].cpu().numpy() for t in out)
     ch = clk.cpu().double()
     clocks = [float(ch[r, 0] / max(float(ch[r, 1]), 1.0)) * 0.1 for r in range(R)]
     if use_dist:
         t = torch.tensor(walls, dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)  # the slowest rank defines the job's time, repeat by repeat
         walls = [float(v) for v in t.tolist()]
-    del bufs, acts, wbuf
+    del bufs, acts, wbuf, plan
     torch.cuda.empty_cache()
-    return walls, evs, n_bufs, clocks, pre
+    return walls, evs, n_bufs, S, clocks, pre, last
+
+
+def dump_outputs(d, last, limit_bytes=64 << 20):
+    """--dump-outputs: the last timed step's (obs [N, D], reward [N], done [N], flags [N]) as DIR/<name>.npy — obs and reward in
+    float64 as computed, done and flags (uint8) as float32.  Above `limit_bytes` in all: a fixed, seeded sample of the envs, the same
+    rows of every array, their env indices in env_index.npy."""
+    import numpy as np
+    obs, rew, done, flags = last
+    arrs = {"obs": obs.astype(np.float64), "reward": rew.astype(np.float64), "done": done.astype(np.float32),
+            "flags": flags.astype(np.float32)}
+    n = obs.shape[0]
+    per_env = sum(a.nbytes for a in arrs.values()) / n
+    if per_env * n > limit_bytes:
+        idx = np.sort(np.random.default_rng(0).choice(n, int(limit_bytes // (per_env + 8)), replace=False))
+        arrs = {k: v[idx] for k, v in arrs.items()}
+        arrs["env_index"] = idx.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrs.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(v))
 
 
 def main():
@@ -560,7 +620,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
-    ap.add_argument("--repeats", type=int, default=5, help="timed repeats of the K-step rollout; value = the median")
+    ap.add_argument("--repeats", type=int, default=None, help="timed repeats of the K-step rollout; value = the median "
+                    "(default 1: exactly K timed steps; 5 with --full)")
     ap.add_argument("--envs-per-gpu", type=int, default=ENVS_PER_GPU)
     ap.add_argument("--precondition-ms", type=float, default=300.0,
                     help="untimed device conditioning before the warm-up steps: the same kernel on a scratch env and scratch buffers "
@@ -573,13 +634,22 @@ def main():
     ap.add_argument("--no-single-step", action="store_true", help="skip the informational one-launch-per-step timing")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the informational C2 / C4 timings")
     ap.add_argument("--c5-full", action="store_true", help="also time BASELINE configs[4]'s per-rank share (131 072 envs, 10 beams) "
-                    "on every rank and report other_configs.c5_full (automatic when --gpus 8)")
+                    "on every rank and report other_configs.c5_full (automatic with --gpus 8 --full)")
     ap.add_argument("--dry-launch", action="store_true", help="with --gpus N > 1: print the N-rank child command line and its "
                     "communication environment as one JSON line and exit without starting anything")
     ap.add_argument("--workload", choices=("c3", "c4"), default="c3",
                     help="c3 (default, the BASELINE metric's config): 1 ship, 8 beams; c4: BASELINE configs[3], 4 ships "
                          "(traffic + dynamic goals + contact solver), 10 beams — informational, not the headline line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: five timed repeats, the device-copy roofline, the "
+                         "one-launch-per-step path, other_configs, c5_full at --gpus 8 and the CPU baseline (each --no-* flag still "
+                         "skips its part)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them returned (obs, reward, done, flags of every env; "
+                         "rank 0) to DIR/<name>.npy as float64 / float32")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     if args.gpus < 1 or args.steps < 1 or args.warmup < 0 or args.repeats < 1:
         ap.error("--gpus/--steps/--repeats must be >= 1 and --warmup >= 0")
 
@@ -653,15 +723,19 @@ def main():
         sharding.broadcast_bank(vec, src=0)  # RCCL broadcast of the map bank over xGMI; the only collective on the path
 
     K, W, R = args.steps, args.warmup, args.repeats
-    # the device-copy calibration runs BEFORE the timed region (it also brings the GPU out of its idle clocks; it is not a
-    # step of the hot path and touches none of its buffers)
-    copy_gbps = measured_copy_gbps(dev) if rank == 0 else None
+    # the device-copy calibration (--full) runs BEFORE the timed region (it is not a step of the hot path and touches none of its
+    # buffers; the device conditioning below brings the GPU out of its idle clocks either way)
+    copy_gbps = measured_copy_gbps(dev) if rank == 0 and args.full else None
     # scratch env for the untimed device conditioning: same kernel instantiation, same bank, its own state and buffers
     pvec = None
     if args.precondition_ms > 0:
         pvec = ShipVecEnv(n, device=dev, map_mode="bank", n_maps=N_MAPS, map_seed=1000, n_beams=n_beams, env_id_base=rank * n,
                           n_ships=4 if c4 else 1)
-    walls, evs, n_bufs, clocks, pre = timed_rollouts(vec, K, W, R, use_dist, dev, args.precondition_ms, pvec, max(0, args.burn_in_steps))
+    walls, evs, n_bufs, set_steps, clocks, pre, last = timed_rollouts(vec, K, W, R, use_dist, dev, args.precondition_ms, pvec,
+                                                                      max(0, args.burn_in_steps),
+                                                                      keep_last=bool(args.dump_outputs) and rank == 0)
+    if last is not None:
+        dump_outputs(args.dump_outputs, last)
     if pvec is not None:
         pvec.close()
         del pvec
@@ -677,9 +751,9 @@ def main():
         ranks_info = gathered
 
     # BASELINE configs[4] — 1 048 576 envs over 8 GPUs (131 072 per rank, 10 beams): timed by every rank when the job is that
-    # size (or on request), reported by rank 0 next to the headline
+    # size and --full is given (or on request), reported by rank 0 next to the headline
     c5_full = None
-    if (world == 8 or args.c5_full) and not c4:
+    if ((world == 8 and args.full) or args.c5_full) and not c4:
         vec5 = ShipVecEnv(131072, device=dev, map_mode="bank", n_maps=N_MAPS, map_seed=1000, n_beams=10, env_id_base=rank * 131072)
         if use_dist:
             sharding.broadcast_bank(vec5, src=0)
@@ -754,8 +828,9 @@ def main():
                                    ("BASELINE configs[2]: 65536 parallel envs per GPU, 1 ship, 8-beam lidar, 64-map "
                                     "bank (600x600, SPEED 10), random Philox actions, auto-reset in-kernel"),
                        "outputs": "trajectory: every step's obs/reward/done/flags kept in HBM as [K, N, ...] tensors "
-                                  "(ssg_rollout_traj), %d B per env-step, %d buffer set(s) of %.2f GB rotated over the repeats"
-                                  % (traj_bytes_per_step(1, vec.states_history), n_bufs, traj_bytes_per_step(n, vec.states_history) * K / 1e9),
+                                  "(ssg_rollout_traj), %d B per env-step, %d buffer set(s) of %.2f GB rotated over the repeats%s"
+                                  % (traj_bytes_per_step(1, vec.states_history), n_bufs, traj_bytes_per_step(n, vec.states_history) * set_steps / 1e9,
+                                     "" if set_steps == K else " in pieces of %d steps" % set_steps),
                        "envs_per_gpu": n, "total_envs": n * world, "n_beams": n_beams, "history": 2,
                        "parallelism": "env-sharded x%d, one process per GPU (RCCL world size %d), no data-path "
                                       "collective" % (world, world),
@@ -793,7 +868,7 @@ def main():
                               "us_per_step_in_launch": launch_s * 1e6 / steps_in_launch}, **roof_pmc),
         }
         other = {}
-        if world == 1 and not args.no_single_step:
+        if world == 1 and args.full and not args.no_single_step:
             # the policy-in-the-loop path: one ssg_step launch per step; median of 7 repeats of `ks` back-to-back steps
             # (500 whatever --steps says: every repeat starts from an idle, synchronized GPU and pays ~80 us for it once —
             # 0.8 us per step over 100 steps, 0.16 over 500; a trainer's stream of steps has no such restarts)
@@ -815,7 +890,7 @@ def main():
             out["single_step_launch_us_repeats"] = reps
         else:
             out["single_step_launch_us"] = None
-        if world == 1 and not args.no_other_configs and not c4:
+        if world == 1 and args.full and not args.no_other_configs and not c4:
             try:
                 other["c2_4096_envs_10_beams"] = side_config(dev, 4096, 10, 1, 1000, 200, single_step=True)
                 # BASELINE configs[3].  Bank mode (the benchmark workload of SURVEY 8d: envs share the 64 records): cpSpaceStep of the
@@ -869,7 +944,7 @@ def main():
         if c5_full is not None:
             other["c5_full"] = c5_full
         out["other_configs"] = other or None
-        if world == 1 and not args.no_cpu_baseline and not c4:
+        if world == 1 and args.full and not args.no_cpu_baseline and not c4:
             out["cpu_baseline"] = cpu_baseline(vec)
         else:
             out["cpu_baseline"] = None

@@ -75,3 +75,31 @@ def test_failing_rank_prints_its_comm_env():
     p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "5", "--warmup", "1"], capture_output=True,
                        text=True, timeout=600, env=_env())
     assert p.returncode != 0 and "comm env of the ranks" in p.stderr and "HSA_ENABLE_IPC_MODE_LEGACY" in p.stderr
+
+
+def test_dump_outputs_writes_float_arrays_within_the_cap(tmp_path):
+    """--dump-outputs' writer: obs / reward as float64, done / flags as float32, every env while the cap allows; past it the same
+    fixed, seeded sample of env rows in every array, with their indices."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(1)
+    n, D = 1000, 28
+    last = (rng.random((n, D)), rng.random(n), (rng.random(n) < 0.1).astype(np.uint8), rng.integers(0, 4, n).astype(np.uint8))
+    names = ("obs", "reward", "done", "flags")
+    bench.dump_outputs(str(tmp_path / "all"), last)
+    got = [np.load(tmp_path / "all" / (k + ".npy")) for k in names]
+    assert [g.dtype for g in got] == [np.float64, np.float64, np.float32, np.float32]
+    for g, v in zip(got, last):
+        np.testing.assert_array_equal(g, v)
+    assert sorted(os.listdir(tmp_path / "all")) == sorted(k + ".npy" for k in names)
+    limit = 100 * (8 * D + 8 + 4 + 4)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), last, limit_bytes=limit)
+    idx = np.load(tmp_path / "s1" / "env_index.npy")
+    assert idx.dtype == np.float64 and 0 < len(idx) < n and np.all(np.diff(idx) > 0)
+    sample = {k: np.load(tmp_path / "s1" / (k + ".npy")) for k in names}
+    assert sum(a.nbytes for a in sample.values()) + idx.nbytes <= limit
+    for k, v in zip(names, last):
+        np.testing.assert_array_equal(sample[k], v[idx.astype(np.int64)])
+        np.testing.assert_array_equal(sample[k], np.load(tmp_path / "s2" / (k + ".npy")))

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 export SSG_LIB_PATH=$ROOT/ship_sim_gym_amd/libshipsim_abl.so
 for A in ${ABLS:-0 1 2 8 0x10 0x20 0x40 0x80}; do
   rm -rf /tmp/ablpmc
-  SSG_ABLATE=$A rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES --output-format csv -d /tmp/ablpmc -- python3 $ROOT/bench.py --steps 1000 --warmup 100 --no-cpu-baseline --no-single-step --no-other-configs > /tmp/ablpmc.log 2>&1
+  SSG_ABLATE=$A rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES --output-format csv -d /tmp/ablpmc -- python3 $ROOT/bench.py --full --steps 1000 --warmup 100 --no-cpu-baseline --no-single-step --no-other-configs > /tmp/ablpmc.log 2>&1
   python3 - <<PY
 import csv,glob,collections
 acc=collections.defaultdict(list)

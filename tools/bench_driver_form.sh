@@ -5,9 +5,9 @@ set -u
 tag=${1:-driver_form}; n=${2:-3}
 out=gpurun_out/$tag; mkdir -p $out
 for i in $(seq 1 $n); do
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline > $out/line_$i.json 2> $out/err_$i.txt
+  python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline > $out/line_$i.json 2> $out/err_$i.txt
 done
-python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline --precondition-ms 0 > $out/line_nocond.json 2> $out/err_nocond.txt
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline --precondition-ms 0 > $out/line_nocond.json 2> $out/err_nocond.txt
 python3 - <<PY
 import json,glob
 for f in sorted(glob.glob("$out/line_*.json")):

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 export SSG_LIB_PATH=$ROOT/ship_sim_gym_amd/libshipsim_abl.so
 for A in ${@:-0 0x80}; do
   rm -rf /tmp/c4abl
-  SSG_ABLATE=$A rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/c4abl -- python3 $ROOT/bench.py --workload c4 --steps 300 --warmup 50 --no-cpu-baseline > /tmp/c4abl.log 2>&1
+  SSG_ABLATE=$A rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/c4abl -- python3 $ROOT/bench.py --full --workload c4 --steps 300 --warmup 50 --no-cpu-baseline > /tmp/c4abl.log 2>&1
   echo "ablate=$A"
   python3 - <<PY
 import csv,glob

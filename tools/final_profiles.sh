@@ -15,9 +15,9 @@ K=300 bash tools/c4_kernel_times.sh product > gpurun_out/prof_c4_$R/kernel_times
 find gpurun_out/prof_c4_$R gpurun_out/prof_${R}h -name "*.csv" -size +3M -delete
 OUT=gpurun_out/${R}final; mkdir -p $OUT
 for i in 1 2 3; do
-  timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_line_driver_form_$i.json 2> $OUT/bench_driver_$i.err; echo "bench driver form $i rc=$?"
+  timeout 900 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_line_driver_form_$i.json 2> $OUT/bench_driver_$i.err; echo "bench driver form $i rc=$?"
 done
-timeout 1500 python3 bench.py > $OUT/bench_line.json 2> $OUT/bench_line.err; echo "bench default rc=$?"
+timeout 1500 python3 bench.py --full > $OUT/bench_line.json 2> $OUT/bench_line.err; echo "bench default rc=$?"
 timeout 2400 python3 tools/soak_parity.py ${SOAK:-} > $OUT/soak_parity.txt 2>&1; echo "soak rc=$?"
 tail -n 12 $OUT/soak_parity.txt
 tail -40 gpurun_out/prof_${R}h.log
