@@ -23,14 +23,16 @@
 extern "C" {
 #endif
 
-#define SSG_ABI_VERSION 8 /* 2: ssg_config.n_ships, SSG_F_TRAFFIC / SSG_F_GOAL_BODIES (config 4); 3: ssg_init_state;
+#define SSG_ABI_VERSION 9 /* 2: ssg_config.n_ships, SSG_F_TRAFFIC / SSG_F_GOAL_BODIES (config 4); 3: ssg_init_state;
                              4: map record without dtMin/dtMax (SSG_MAP_STRIDE 145, SSG_PLANE_DOUBLES 5);
                              5: ssg_config.map_ring, ssg_refill_worlds (a brand-new world per episode, generated on the device);
                              6: ssg_rollout_traj (every step of a fused rollout lands in its own slot of a trajectory buffer);
                              7: SSG_FLAG_DYN_MEMO_OFF, SSG_F_DYN_MEMO_STATS (config 4: the memo table of the full cpSpaceStep lives
                                 in the state blob, which grows by ~30 MB);
                              8: ssg_set_terminal_obs (the RLlib flow without a reset launch), ssg_step_host / ssg_wait_host (a numpy-protocol step in one
-                                call), ssg_debug_launch_clock, ssg_debug_clock_probe */
+                                call), ssg_debug_launch_clock, ssg_debug_clock_probe;
+                             9: ssg_policy, ssg_policy_act, ssg_rollout_policy (the policy forward + action sampling of a rollout step on
+                                the device: rollouts with the policy in the loop, driven from C) */
 
 typedef enum ssg_status {
     SSG_OK = 0,
@@ -374,6 +376,69 @@ int ssg_debug_launch_clock(ssg_handle *h, uint64_t *dev_buf);
  * ticks.  (A probe wide enough to load every CU pulls the chip into its power-limited clocks and slows whatever is timed right
  * after it: bench.py uses ssg_debug_launch_clock for the timed repeats instead.) */
 int ssg_debug_clock_probe(uint64_t *dev_out, int n_blocks, int iters, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * The policy in the loop (ABI 9)
+ * An MLP actor-critic evaluated on the device for every env of a handle, with the action sampled there too: what the reference's
+ * runner does around each env.step (train/stable_baselines/ppo.py:84-100) and what train/ppo_torch.py does with a dozen PyTorch
+ * kernels per rollout step.  f32 parameters, f64 observations in.
+ *
+ * Packed parameter layout (dev_params, f32, 4-byte aligned, no padding), with D = obs_dim, H = hidden, A = n_actions; W is nn.Linear's
+ * own [out][in] row-major order, so the buffer is torch.cat([p.flatten() for p in net.parameters()]) of
+ * Sequential(Linear(D, H), act[, Linear(H, H), act]) followed by the heads Linear(H, A) and Linear(H, 1):
+ *   [0 .. H*D)                  W0  [H][D]
+ *   [H*D .. H*D + H)            b0  [H]
+ *   then, with n_hidden_layers = 2:
+ *   [o1 .. o1 + H*H)            W1  [H][H]          o1 = H*D + H
+ *   [o1 + H*H .. o1 + H*H + H)  b1  [H]
+ *   then, at oh = H*D + H (+ H*H + H with 2 layers):
+ *   [oh .. oh + A*H)            Wpi [A][H]
+ *   [oh + A*H .. + A)           bpi [A]
+ *   [oh + A*H + A .. + H)       Wv  [1][H]
+ *   [oh + A*H + A + H]          bv  [1]
+ *   total: H*D + H + (n_hidden_layers - 1)*(H*H + H) + A*H + A + H + 1 floats.
+ * Forward, per env e: x[d] = (float)(obs[e][d] / obs_scale[d]) (f64 division, then one rounding to f32); every dense output is an
+ * fmaf chain from its bias over k = 0, 1, ... in order, followed by tanh / ReLU on the hidden layers; logits = the pi head, value = the
+ * v head.  Sampling (f32): m = max(logits), lse = m + log(sum exp(l - m)), logp_all = l - lse, cdf = cumsum(exp(logp_all)),
+ * act = #{j < A-1 : u > cdf[j]}, logp = logp_all[act].  An env's outputs depend on its own observation row, the parameters and its
+ * own u only (bitwise: not on n_envs, sharding or the launch that computed them).
+ * ------------------------------------------------------------------------------------------------- */
+#define SSG_POLICY_MAX_HIDDEN 128
+#define SSG_POLICY_TANH 0
+#define SSG_POLICY_RELU 1
+typedef struct ssg_policy {
+    uint32_t struct_size;        /* sizeof(ssg_policy) */
+    int32_t obs_dim;             /* == history*(6+n_beams) of the handle */
+    int32_t hidden;              /* 16..SSG_POLICY_MAX_HIDDEN, multiple of 16 */
+    int32_t n_hidden_layers;     /* 1 or 2 */
+    int32_t n_actions;           /* 2..4 (ssg_step accepts actions 0..3; the reference's action space is Discrete(3), ship_env.py:19) */
+    int32_t activation;          /* SSG_POLICY_TANH | SSG_POLICY_RELU */
+    const float *dev_params;     /* packed f32, layout above */
+    const double *dev_obs_scale; /* f64[obs_dim]: x = (float)(obs / scale) */
+} ssg_policy;
+
+/* Replaces: the policy half of one rollout step of the reference's runner inside model.learn (train/stable_baselines/ppo.py:84-100:
+ * one policy forward + action sampling per env.step over the SubprocVecEnv of :122-123).  For every env e of the handle, on the
+ * observation rows dev_obs (f64[n_envs][D]): dev_actions[e] (i32, ready for ssg_step), dev_logp[e], dev_value[e] (f32) and, with
+ * dev_x != NULL, the normalised row dev_x[e][0..D) (f32).  u = dev_uniform[e] (f32[n_envs]) when given; otherwise Philox4x32-10 with
+ * counter (env_lo, env_hi, step_lo, step_hi) over the GLOBAL env id env_id_base + e and key = seed (ssg_fill_actions' stream), output
+ * word 1: u = (w1 >> 8) * 2^-24.  One launch on `stream`.  SSG_ERR_BAD_ARG (nothing launched) for a bad policy record or a NULL
+ * required pointer. */
+int ssg_policy_act(ssg_handle *h, const ssg_policy *pol, const double *dev_obs, const float *dev_uniform /* nullable */, uint64_t seed,
+                   int64_t step, int32_t *dev_actions, float *dev_logp, float *dev_value, float *dev_x /* nullable */, void *stream);
+
+/* Replaces: the whole rollout loop of that runner (train/stable_baselines/ppo.py:84-100, one policy forward + env.step per step over
+ * the SubprocVecEnv of :122-123), K steps enqueued from C on `stream`: step k = ssg_policy_act for step step0 + k (uniforms row k of
+ * dev_uniform_KN, or Philox as above) writing its row of act / logp / value / x, then ssg_step with that row of actions, which rewrites
+ * dev_obs in place and writes its row of reward / done / flags.  Row k of every [K][...] buffer starts step_stride_envs envs after row
+ * k-1 (>= n_envs, as in ssg_rollout_traj).  dev_last_value (nullable): the value of the observation after step K-1 (the bootstrap
+ * value of PPO's GAE), one more value-only forward.  Every handle ssg_step serves is served (history 1..8, n_ships = 4, map_ring), with
+ * the same launches ssg_step issues.  SSG_ERR_BAD_ARG (nothing launched) for a bad policy record, NULL required pointers, K < 1 or a
+ * stride < n_envs. */
+int ssg_rollout_policy(ssg_handle *h, const ssg_policy *pol, int K, const float *dev_uniform_KN /* nullable */, uint64_t seed,
+                       int64_t step0, double *dev_obs, int32_t *dev_act_KN, float *dev_logp_KN, float *dev_value_KN,
+                       float *dev_x_KND /* nullable */, double *dev_reward_KN, uint8_t *dev_done_KN, uint8_t *dev_flags_KN /* nullable */,
+                       float *dev_last_value /* nullable */, int64_t step_stride_envs, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Host-side geometry (what pymunk's cffi exposed at reset time); no GPU needed.

@@ -10,12 +10,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SSG_LIB_PATH: development override (tools/build_variant.sh builds diagnostic variants next to the product library)
 LIB_PATH = os.environ.get("SSG_LIB_PATH") or os.path.join(_HERE, "libshipsim.so")
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 MAX_BEAMS, MAX_GOALS, MAX_HULL, SHIP_VERTS, N_TRAFFIC = 16, 6, 12, 5, 3
 MAP_STRIDE = 145
 MAP_OFF_COUNTS, MAP_OFF_AABB, MAP_OFF_GOALS, MAP_OFF_SPAWN_GOAL, MAP_OFF_PLANES, PLANE_DOUBLES = 0, 2, 10, 22, 24, 5
 FLAG_AUTO_RESET, FLAG_FIX_COLLISION_REWARD, FLAG_BANK_IN_GLOBAL, FLAG_EXACT_LIDAR, FLAG_DYN_MEMO_OFF = 0x1, 0x2, 0x4, 0x8, 0x10
 EV_COLLIDING, EV_GOAL_REACHED, EV_OUT_OF_BOUNDS, EV_MAX_STEPS, EV_NO_GOALS_LEFT = 0x1, 0x2, 0x4, 0x8, 0x10
+POLICY_MAX_HIDDEN, POLICY_TANH, POLICY_RELU = 128, 0, 1
 (F_X, F_Y, F_VX, F_VY, F_ANGLE, F_W, F_CUM_REWARD, F_LIDAR, F_RUDDER, F_STEP_COUNT, F_MAP_ID, F_GOAL_MASK,
  F_STATS, F_TRAFFIC, F_GOAL_BODIES, F_DYN_FLAGS, F_EPISODES, F_DYN_MEMO_STATS) = range(18)
 
@@ -27,6 +28,7 @@ EXPORTS = (
     "ssg_host_build_map", "ssg_host_segment_query", "ssg_debug_copy8", "ssg_generate_bank", "ssg_render", "ssg_dyn_invalidate",
     "ssg_init_state", "ssg_refill_worlds", "ssg_debug_launch_geometry", "ssg_rollout_traj", "ssg_debug_dyn_counters", "ssg_debug_kernel_times",
     "ssg_debug_clock_probe", "ssg_debug_launch_clock", "ssg_set_terminal_obs", "ssg_step_host", "ssg_wait_host",
+    "ssg_policy_act", "ssg_rollout_policy",
 )
 
 
@@ -47,6 +49,14 @@ class Config(C.Structure):
         ("thrust_px0", C.c_double), ("thrust_py0", C.c_double),
         ("rudder_step", C.c_int32), ("rudder_max", C.c_int32),
         ("n_ships", C.c_int32), ("map_ring", C.c_int32),
+    ]
+
+
+class Policy(C.Structure):
+    """ssg_policy (ABI 9): an MLP actor-critic the device evaluates for every env (layout of dev_params: include/shipsim.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("obs_dim", C.c_int32), ("hidden", C.c_int32), ("n_hidden_layers", C.c_int32),
+        ("n_actions", C.c_int32), ("activation", C.c_int32), ("dev_params", C.c_void_p), ("dev_obs_scale", C.c_void_p),
     ]
 
 
@@ -100,6 +110,9 @@ def lib():
     L.ssg_set_terminal_obs.argtypes = [vp, vp]
     L.ssg_step_host.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_int, vp]
     L.ssg_wait_host.argtypes = [vp, C.c_int]
+    L.ssg_policy_act.argtypes = [vp, C.POINTER(Policy), vp, vp, C.c_uint64, C.c_int64, vp, vp, vp, vp, vp]
+    L.ssg_rollout_policy.argtypes = [vp, C.POINTER(Policy), C.c_int, vp, C.c_uint64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                     C.c_int64, vp]
     L.ssg_render.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, vp]
     L.ssg_dyn_invalidate.argtypes = [vp, vp, vp]
     L.ssg_host_convex_hull.argtypes = [C.c_int, dp, dp, ip]

@@ -52,6 +52,7 @@ struct ssg_handle {
     static constexpr int kHostSlots = 8;
     hipEvent_t host_ev[kHostSlots] = {};
     bool host_ev_made[kHostSlots] = {};
+    bool policy_prepared = false; // ssg_policy_act / ssg_rollout_policy: the policy kernel's dynamic-LDS limit is set
     std::string err;
 };
 
@@ -958,6 +959,95 @@ int ssg_rollout_traj(ssg_handle *h, const int32_t *dev_actions, int K, double *d
         hipError_t e = ssg::launch_step(h->dev, h->block, h->lds, h->lds_bytes, dev_actions + (size_t)k * h->cfg.n_envs, kk,
                                         obs_at(k), rew_at(k), done_at(k), flags_at(k), traj, static_cast<hipStream_t>(stream));
         if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("step launch: ") + hipGetErrorString(e));
+    }
+    return SSG_OK;
+}
+
+// ABI 9: the policy in the loop.  Everything a call could refuse is refused here, before anything is enqueued.
+static int check_policy(ssg_handle *h, const ssg_policy *pol, const char *what)
+{
+    const std::string w(what);
+    if (!pol) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL policy");
+    if (pol->struct_size != sizeof(ssg_policy)) return fail(h, SSG_ERR_BAD_ARG, w + ": ssg_policy.struct_size != sizeof(ssg_policy)");
+    const int D = h->cfg.history * (6 + h->cfg.n_beams);
+    if (pol->obs_dim != D) {
+        char buf[160];
+        std::snprintf(buf, sizeof buf, ": obs_dim %d differs from the handle's history*(6+n_beams) = %d", pol->obs_dim, D);
+        return fail(h, SSG_ERR_BAD_ARG, w + buf);
+    }
+    if (pol->hidden < 16 || pol->hidden > SSG_POLICY_MAX_HIDDEN || pol->hidden % 16 != 0)
+        return fail(h, SSG_ERR_BAD_ARG, w + ": hidden must be a multiple of 16 in 16..SSG_POLICY_MAX_HIDDEN");
+    if (pol->n_hidden_layers < 1 || pol->n_hidden_layers > 2) return fail(h, SSG_ERR_BAD_ARG, w + ": n_hidden_layers must be 1 or 2");
+    if (pol->n_actions < 2 || pol->n_actions > 4) return fail(h, SSG_ERR_BAD_ARG, w + ": n_actions must be in 2..4 (ssg_step accepts actions 0..3)");
+    if (pol->activation != SSG_POLICY_TANH && pol->activation != SSG_POLICY_RELU)
+        return fail(h, SSG_ERR_BAD_ARG, w + ": activation must be SSG_POLICY_TANH or SSG_POLICY_RELU");
+    if (!pol->dev_params || !pol->dev_obs_scale) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_params or dev_obs_scale");
+    return SSG_OK;
+}
+
+static int prepare_policy(ssg_handle *h)
+{
+    if (h->policy_prepared) return SSG_OK;
+    hipError_t e = ssg::prepare_policy();
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("prepare_policy: ") + hipGetErrorString(e));
+    h->policy_prepared = true;
+    return SSG_OK;
+}
+
+int ssg_policy_act(ssg_handle *h, const ssg_policy *pol, const double *dev_obs, const float *dev_uniform, uint64_t seed, int64_t step,
+                   int32_t *dev_actions, float *dev_logp, float *dev_value, float *dev_x, void *stream)
+{
+    int rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    rc = check_policy(h, pol, "ssg_policy_act");
+    if (rc != SSG_OK) return rc;
+    if (!dev_obs || !dev_actions || !dev_logp || !dev_value)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_policy_act: NULL dev_obs, dev_actions, dev_logp or dev_value");
+    rc = prepare_policy(h);
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_policy_act(*pol, h->cfg.n_envs, h->cfg.env_id_base, dev_obs, dev_uniform, seed, step, dev_actions, dev_logp,
+                                          dev_value, dev_x, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("policy launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+int ssg_rollout_policy(ssg_handle *h, const ssg_policy *pol, int K, const float *dev_uniform_KN, uint64_t seed, int64_t step0,
+                       double *dev_obs, int32_t *dev_act_KN, float *dev_logp_KN, float *dev_value_KN, float *dev_x_KND,
+                       double *dev_reward_KN, uint8_t *dev_done_KN, uint8_t *dev_flags_KN, float *dev_last_value,
+                       int64_t step_stride_envs, void *stream)
+{
+    int rc = check_ready(h, true);
+    if (rc != SSG_OK) return rc;
+    rc = check_policy(h, pol, "ssg_rollout_policy");
+    if (rc != SSG_OK) return rc;
+    if (!dev_obs || !dev_act_KN || !dev_logp_KN || !dev_value_KN || !dev_reward_KN || !dev_done_KN)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_rollout_policy: NULL dev_obs, act, logp, value, reward or done buffer");
+    if (K < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_rollout_policy: K < 1");
+    if (step_stride_envs < (int64_t)h->cfg.n_envs) return fail(h, SSG_ERR_BAD_ARG, "ssg_rollout_policy: step_stride_envs < n_envs (steps would overlap)");
+    // what the per-step ssg_step would refuse, refused before the first policy launch
+    if (h->cfg.map_ring > 0 && !h->ring_ready) return fail(h, SSG_ERR_NOT_BOUND, "map_ring mode: call ssg_refill_worlds first");
+    rc = refuse_capture(h, stream, "ssg_rollout_policy");
+    if (rc != SSG_OK) return rc;
+    rc = prepare(h);
+    if (rc == SSG_OK) rc = prepare_policy(h);
+    if (rc != SSG_OK) return rc;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t S = (size_t)step_stride_envs, D = (size_t)pol->obs_dim;
+    for (int k = 0; k < K; ++k) {
+        const size_t r = (size_t)k * S;
+        hipError_t e = ssg::launch_policy_act(*pol, h->cfg.n_envs, h->cfg.env_id_base, dev_obs, dev_uniform_KN ? dev_uniform_KN + r : nullptr,
+                                              seed, step0 + k, dev_act_KN + r, dev_logp_KN + r, dev_value_KN + r,
+                                              dev_x_KND ? dev_x_KND + r * D : nullptr, st);
+        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("policy launch: ") + hipGetErrorString(e));
+        // (ssg_step as it stands: the same launches, frame shifts, dyn kernels and ring refills as a caller's own step)
+        rc = ssg_rollout_traj(h, dev_act_KN + r, 1, dev_obs, dev_reward_KN + r, dev_done_KN + r, dev_flags_KN ? dev_flags_KN + r : nullptr, 0,
+                              stream);
+        if (rc != SSG_OK) return rc;
+    }
+    if (dev_last_value) { // the value of the observation after the last step (PPO's bootstrap): a value-only forward
+        hipError_t e = ssg::launch_policy_act(*pol, h->cfg.n_envs, h->cfg.env_id_base, dev_obs, nullptr, seed, step0 + K, nullptr, nullptr,
+                                              dev_last_value, nullptr, st);
+        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("policy launch: ") + hipGetErrorString(e));
     }
     return SSG_OK;
 }

@@ -201,8 +201,27 @@ hipError_t launch_refill_worlds(const DevCfg &c, uint64_t seed, double width_fra
                                 double *bank, double *raw, hipStream_t stream);
 hipError_t launch_fill_actions(uint64_t seed, uint64_t step0, int K, long long env_base, int n, int32_t *out,
                                hipStream_t stream);
+// the policy kernel (shipsim_policy.hip): ssg_policy_act on n envs; act / logp NULL = value only (no sampling), x NULL = no x rows
+size_t policy_lds_bytes(const ssg_policy &p);
+hipError_t prepare_policy(); // (the dynamic-LDS limit of the kernel: up to 79 KB per workgroup at obs_dim 176, hidden 128)
+hipError_t launch_policy_act(const ssg_policy &p, int n, long long env_base, const double *obs, const float *uniform, uint64_t seed,
+                             int64_t step, int32_t *act, float *logp, float *value, float *x, hipStream_t stream);
 
 #ifdef __HIPCC__
+// One round of Philox4x32-10 (counter ctr, key key).  The counter-based streams of the library — fill_actions_kernel's actions
+// (shipsim_kernels.hip) and the policy kernel's uniforms (shipsim_policy.hip) — both key it with the seed and count with
+// (env_lo, env_hi, step_lo, step_hi) over the GLOBAL env id.
+__device__ __forceinline__ void philox_round(uint32_t (&ctr)[4], const uint32_t (&key)[2])
+{
+    const uint64_t p0 = (uint64_t)0xD2511F53u * ctr[0];
+    const uint64_t p1 = (uint64_t)0xCD9E8D57u * ctr[2];
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ ctr[1] ^ key[0];
+    const uint32_t n1 = (uint32_t)p1;
+    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ ctr[3] ^ key[1];
+    const uint32_t n3 = (uint32_t)p0;
+    ctr[0] = n0; ctr[1] = n1; ctr[2] = n2; ctr[3] = n3;
+}
+
 // ShipEnv.reset / ShipGame.reset of ONE env (ship_env.py:171-184, game.py:260-277): the player's columns, the goal mask, the
 // observation rows (deque([-1]*n), then the spawn frame).  Shared by reset_kernel and, for config 4, the kernel that also rebuilds
 // the env's traffic ships and goal bodies in the same launch (shipsim_dynamics.hip).  Returns the bank record the env is reset onto.

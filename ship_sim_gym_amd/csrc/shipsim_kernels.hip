@@ -2181,18 +2181,8 @@ __global__ void clock_probe_kernel(unsigned long long *__restrict__ out, int ite
 
 // ---------------------------------------------------------------------------------------------------------
 // counter-based action stream: Philox4x32-10, counter = (env_lo, env_hi, step_lo, step_hi), key = seed
+// (philox_round lives in shipsim_internal.h: the policy kernel draws its uniforms from the same stream)
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox_round(uint32_t (&ctr)[4], const uint32_t (&key)[2])
-{
-    const uint64_t p0 = (uint64_t)0xD2511F53u * ctr[0];
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * ctr[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ ctr[1] ^ key[0];
-    const uint32_t n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ ctr[3] ^ key[1];
-    const uint32_t n3 = (uint32_t)p0;
-    ctr[0] = n0; ctr[1] = n1; ctr[2] = n2; ctr[3] = n3;
-}
-
 __global__ void fill_actions_kernel(uint64_t seed, uint64_t step0, int K, long long env_base, int n,
                                     int32_t *__restrict__ out)
 {

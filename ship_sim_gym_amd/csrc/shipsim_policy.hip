@@ -1,0 +1,224 @@
+// shipsim_policy.hip — the policy half of a rollout step on the device: ssg_policy_act / ssg_rollout_policy (include/shipsim.h).
+//
+// What the reference's runner does around every env.step (train/stable_baselines/ppo.py:84-100: one policy forward per step) and what
+// train/ppo_torch.py's Shard.step() does in a dozen PyTorch kernels: normalise the f64 observation, an MLP actor-critic in f32, inverse-CDF
+// sampling of the action, the rollout-buffer values.  One launch per step, one lane per env.
+//
+// Shape.  One wave (64 lanes = 64 envs) per workgroup.  The activations of one layer live in LDS as rows of 65 floats (one column per
+// lane, +1 of padding), which each lane reads back as its own column.  The weights are the same for every lane: 16 output rows at a
+// time are staged into an LDS tile and read with broadcast ds_read_b128 (all lanes, one address: 4 weights per read).  A dense layer
+// keeps 16 accumulators; per 4 inputs it issues 4 activation reads and 16 weight reads, then 64 fmaf.  (Reading the weights with
+// scalar loads instead serialised on the scalar cache's latency: 120 us per launch at 65 536 envs.)  The MFMA alternative
+// (v_mfma_f32_16x16x4_f32, exact f32 like the VALU) needs envs x outputs tiles through LDS; not built here.
+//
+// Numerics (the determinism contract).  x = (float)(obs / scale) with an f64 division, exactly torch's (obs / scale).float().  Every
+// dense output is one fmaf chain that starts at the bias and adds W[j][k] * in[k] in increasing k; tanhf / expf / logf are the device
+// library's.  An env's outputs depend on its own observation row, the parameters and its own uniform only: not on n_envs, the
+// workgroup geometry, env_id_base (except through the Philox counter, which is the GLOBAL env id) or on whether the launch comes from
+// ssg_policy_act or ssg_rollout_policy.
+#include <cstdint>
+
+#include "shipsim_internal.h"
+
+namespace ssg {
+namespace {
+
+constexpr int kPolWave = 64;   // envs per workgroup (one wave)
+constexpr int kPolStride = 65; // LDS floats per activation row: one per lane, +1 so that the obs pass's stores spread over the banks
+
+__device__ __forceinline__ float activate(float v, int kind) { return kind == SSG_POLICY_RELU ? fmaxf(v, 0.0f) : tanhf(v); }
+
+// Stage `rows` rows of a row-major [rows][K] weight block into the workgroup's weight tile (row stride K4 = K rounded up to 4, the
+// padding zeroed), read linearly from global memory (coalesced).  The caller brackets it with barriers.
+__device__ __forceinline__ void stage_rows(const float *__restrict__ W, int rows, int K, int K4, float *wt, int lane)
+{
+    for (int i = lane; i < rows * K; i += kPolWave) {
+        const int r = i / K, c = i - r * K;
+        wt[r * K4 + c] = W[i];
+    }
+    for (int i = lane; i < rows * (K4 - K); i += kPolWave) {
+        const int r = i / (K4 - K), c = K + i - r * (K4 - K);
+        wt[r * K4 + c] = 0.0f;
+    }
+}
+
+// out[j] = activate(b[j] + sum_k W[j][k] * in[k]) for j < M (M a multiple of 16), W row-major [M][K]; in / out: LDS rows, this lane's
+// column (in has K4 rows, those past K zero).  16 output rows at a time are staged in the weight tile; per 4 inputs a lane reads its
+// 4 activations and, for each of the 16 outputs, the 4 weights as ONE broadcast ds_read_b128 (every lane reads the same address).
+__device__ __forceinline__ void dense(const float *__restrict__ W, const float *__restrict__ b, int K, int M, int kind,
+                                      const float *in, float *out, float *wt, int lane)
+{
+    const int K4 = (K + 3) & ~3;
+    for (int j0 = 0; j0 < M; j0 += 16) {
+        __syncthreads(); // (the previous tile's readers are done)
+        stage_rows(W + (size_t)j0 * K, 16, K, K4, wt, lane);
+        __syncthreads();
+        float acc[16];
+#pragma unroll
+        for (int jj = 0; jj < 16; ++jj) acc[jj] = b[j0 + jj];
+        for (int k = 0; k < K4; k += 4) {
+            float v[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) v[t] = in[(k + t) * kPolStride + lane];
+            // all 16 reads first, then the fmaf in t-major order: 16 independent chains between two dependent steps (each
+            // accumulator still adds k, k+1, k+2, k+3 in order)
+            float4 w[16];
+#pragma unroll
+            for (int jj = 0; jj < 16; ++jj) w[jj] = *reinterpret_cast<const float4 *>(wt + jj * K4 + k);
+#pragma unroll
+            for (int jj = 0; jj < 16; ++jj) acc[jj] = fmaf(w[jj].x, v[0], acc[jj]);
+#pragma unroll
+            for (int jj = 0; jj < 16; ++jj) acc[jj] = fmaf(w[jj].y, v[1], acc[jj]);
+#pragma unroll
+            for (int jj = 0; jj < 16; ++jj) acc[jj] = fmaf(w[jj].z, v[2], acc[jj]);
+#pragma unroll
+            for (int jj = 0; jj < 16; ++jj) acc[jj] = fmaf(w[jj].w, v[3], acc[jj]);
+        }
+#pragma unroll
+        for (int jj = 0; jj < 16; ++jj) out[(j0 + jj) * kPolStride + lane] = activate(acc[jj], kind);
+    }
+}
+
+// (waves_per_eu(1, 2): lets the scheduler keep all 16 weight reads of a step in flight — 113 VGPRs — instead of two at a time)
+__global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1, 2))) policy_act_kernel(const ssg_policy p, const float *__restrict__ params, const double *__restrict__ scale,
+                                                              int n, long long env_base, const double *__restrict__ obs,
+                                                              const float *__restrict__ uniform, uint64_t seed, int64_t step,
+                                                              int32_t *__restrict__ act_out, float *__restrict__ logp_out,
+                                                              float *__restrict__ value_out, float *__restrict__ x_out)
+{
+    extern __shared__ float4 lds4[];
+    const int lane = threadIdx.x;
+    const int e0 = blockIdx.x * kPolWave;
+    const int ne = (n - e0 < kPolWave) ? n - e0 : kPolWave; // tail workgroup: lanes >= ne store nothing
+    const int D = p.obs_dim, H = p.hidden, A = p.n_actions;
+    const int R4 = ((D > H ? D : H) + 3) & ~3;                // rows of bufA, and the weight tile's widest row
+    float *wt = reinterpret_cast<float *>(lds4);              // weight tile: 16 rows x R4 (16-byte aligned rows of 4k floats)
+    float *bufA = wt + 16 * R4;                               // x (rows D..R4 zero), then the second hidden layer
+    float *bufB = bufA + R4 * kPolStride;                     // the first hidden layer
+
+    // 1. x = (float)(obs / scale).  The workgroup's ne observation rows are ONE contiguous block of ne*D doubles: read it linearly
+    // (coalesced), and write the x rows (same linear index, f32) the same way; element i is (env i / D, feature i % D), tracked
+    // incrementally (64 = qd * D + rd).
+    {
+        const double *src = obs + (size_t)e0 * D;
+        float *xdst = x_out ? x_out + (size_t)e0 * D : nullptr;
+        const int total = ne * D, qd = kPolWave / D, rd = kPolWave % D;
+        int d = lane % D, el = lane / D;
+        for (int i = lane; i < total; i += kPolWave) {
+            const float xv = (float)(src[i] / scale[d]);
+            bufA[d * kPolStride + el] = xv;
+            if (xdst) xdst[i] = xv;
+            d += rd;
+            el += qd;
+            if (d >= D) { d -= D; ++el; }
+        }
+        for (int r = D; r < R4; ++r) bufA[r * kPolStride + lane] = 0.0f; // (padding rows: 0 * weight 0, never a NaN)
+    }
+    // (the first dense tile's barrier orders these stores before any lane reads another lane's column: after it every lane reads and
+    // writes its own activation column only)
+
+    // 2. the body: Linear(D, H) + act [+ Linear(H, H) + act]
+    const float *P = params;
+    dense(P, P + H * D, D, H, p.activation, bufA, bufB, wt, lane);
+    P += H * D + H;
+    const float *h = bufB;
+    if (p.n_hidden_layers == 2) {
+        dense(P, P + H * H, H, H, p.activation, bufB, bufA, wt, lane);
+        P += H * H + H;
+        h = bufA;
+    }
+
+    // 3. the heads: Wpi [A][H], bpi [A], Wv [1][H], bv [1]
+    // (staged like a dense tile: rows 0..A-1 = Wpi, row 4 = Wv; H is a multiple of 16, so no padding)
+    const float *Wpi = P, *bpi = P + A * H, *Wv = bpi + A, *bv = Wv + H;
+    __syncthreads();
+    stage_rows(Wpi, A, H, H, wt, lane);
+    stage_rows(Wv, 1, H, H, wt + 4 * H, lane);
+    __syncthreads();
+    float lg[4], v = bv[0];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) lg[j] = j < A ? bpi[j] : 0.0f;
+    for (int k = 0; k < H; k += 4) {
+        float hv[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) hv[t] = h[(k + t) * kPolStride + lane];
+        float4 w[5];
+#pragma unroll
+        for (int j = 0; j < 5; ++j) w[j] = *reinterpret_cast<const float4 *>(wt + j * H + k); // (rows A..3 unused: never summed)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const float hx = hv[t];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (j < A) lg[j] = fmaf(t == 0 ? w[j].x : t == 1 ? w[j].y : t == 2 ? w[j].z : w[j].w, hx, lg[j]);
+            v = fmaf(t == 0 ? w[4].x : t == 1 ? w[4].y : t == 2 ? w[4].z : w[4].w, hx, v);
+        }
+    }
+    if (lane >= ne) return;
+    const int e = e0 + lane;
+    if (value_out) value_out[e] = v;
+    if (!act_out) return; // (the bootstrap forward of ssg_rollout_policy: value only)
+
+    // 4. inverse-CDF sampling, the formula order of ppo_torch's Shard.step(): log_softmax, cumsum(exp), count(u > cdf[j]) over j < A-1
+    float m = lg[0];
+#pragma unroll
+    for (int j = 1; j < 4; ++j)
+        if (j < A) m = fmaxf(m, lg[j]);
+    float s = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j < A) s += expf(lg[j] - m);
+    const float lse = m + logf(s);
+    float u;
+    if (uniform) {
+        u = uniform[e];
+    } else { // Philox4x32-10, counter (global env, step), key = seed: fill_actions_kernel's stream, output word 1
+        const uint64_t env = (uint64_t)(env_base + e), st = (uint64_t)step;
+        uint32_t ctr[4] = {(uint32_t)env, (uint32_t)(env >> 32), (uint32_t)st, (uint32_t)(st >> 32)};
+        uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+#pragma unroll
+        for (int r = 0; r < 10; ++r) {
+            if (r) { key[0] += 0x9E3779B9u; key[1] += 0xBB67AE85u; }
+            philox_round(ctr, key);
+        }
+        u = (float)(ctr[1] >> 8) * 0x1p-24f;
+    }
+    float cdf = 0.0f, lp = lg[0] - lse;
+    int a = 0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        if (j + 1 < A) {
+            cdf += expf(lg[j] - lse);
+            a += u > cdf ? 1 : 0;
+        }
+    }
+#pragma unroll
+    for (int j = 1; j < 4; ++j)
+        if (a == j) lp = lg[j] - lse;
+    act_out[e] = a;
+    logp_out[e] = lp;
+}
+
+} // namespace
+
+size_t policy_lds_bytes(const ssg_policy &p)
+{
+    const size_t R4 = (size_t)(((p.obs_dim > p.hidden ? p.obs_dim : p.hidden) + 3) & ~3);
+    return (16 * R4 + (R4 + (size_t)p.hidden) * kPolStride) * sizeof(float);
+}
+
+hipError_t prepare_policy()
+{
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(policy_act_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+}
+
+hipError_t launch_policy_act(const ssg_policy &p, int n, long long env_base, const double *obs, const float *uniform, uint64_t seed,
+                             int64_t step, int32_t *act, float *logp, float *value, float *x, hipStream_t stream)
+{
+    const unsigned grid = (unsigned)((n + kPolWave - 1) / kPolWave);
+    hipLaunchKernelGGL(policy_act_kernel, dim3(grid), dim3(kPolWave), policy_lds_bytes(p), stream, p, p.dev_params, p.dev_obs_scale, n, env_base,
+                       obs, uniform, seed, step, act, logp, value, x);
+    return hipGetLastError();
+}
+
+} // namespace ssg

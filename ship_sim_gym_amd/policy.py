@@ -1,0 +1,144 @@
+"""NativePolicy — an MLP actor-critic the device evaluates inside the rollout (ssg_policy_act / ssg_rollout_policy, ABI 9).
+
+The reference's runner does one policy forward + action sampling per ``env.step`` (train/stable_baselines/ppo.py:84-100); a
+GPU-resident trainer does the same with a dozen PyTorch kernels per step.  ``NativePolicy`` hands the parameters of such a network
+to the library as ONE packed f32 device buffer — ``torch.cat([p.flatten() for p in net.parameters()])`` of an ActorCritic shaped
+like train/ppo_torch.py's: ``body = Sequential(Linear, Tanh|ReLU[, Linear, Tanh|ReLU])``, heads ``pi`` (n_actions) and ``v`` (1) —
+plus the f64 observation scale.  ``refresh()`` re-packs it in place (same address) after an optimiser step.
+
+``ShipVecEnv.policy_act`` / ``ShipVecEnv.rollout_policy`` run it.  ``forward_reference`` is a plain torch restatement for tests.
+"""
+import ctypes as C
+
+from . import _native as N
+
+ACTIVATIONS = {"tanh": N.POLICY_TANH, "relu": N.POLICY_RELU}
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def packed_offsets(obs_dim, hidden, n_hidden_layers, n_actions):
+    """{name: (offset, shape)} of every tensor inside the packed buffer (include/shipsim.h, ssg_policy), and the total length."""
+    D, H, A = int(obs_dim), int(hidden), int(n_actions)
+    shapes = [("W0", (H, D)), ("b0", (H,))]
+    if n_hidden_layers == 2:
+        shapes += [("W1", (H, H)), ("b1", (H,))]
+    shapes += [("Wpi", (A, H)), ("bpi", (A,)), ("Wv", (1, H)), ("bv", (1,))]
+    out, o = {}, 0
+    for name, shp in shapes:
+        out[name] = (o, shp)
+        n = 1
+        for s in shp:
+            n *= s
+        o += n
+    return out, o
+
+
+class NativePolicy(object):
+    """layers: [(W0, b0)] or [(W0, b0), (W1, b1)] with W [out][in] (nn.Linear's order); pi, v: (W, b) of the heads; obs_scale: f64
+    [obs_dim] (or a number) — the device computes x = (float)(obs / obs_scale) as train/ppo_torch.py's normalise() does."""
+
+    def __init__(self, layers, pi, v, obs_scale, activation="tanh"):
+        torch = _torch()
+        if activation not in ACTIVATIONS:
+            raise ValueError("activation must be 'tanh' or 'relu' (got %r)" % (activation,))
+        layers = [tuple(l) for l in layers]
+        if len(layers) not in (1, 2):
+            raise ValueError("NativePolicy: 1 or 2 hidden layers (got %d)" % len(layers))
+        W0 = layers[0][0]
+        if W0.dim() != 2:
+            raise ValueError("NativePolicy: weights must be [out][in] matrices")
+        H, D = int(W0.shape[0]), int(W0.shape[1])
+        if H < 16 or H > N.POLICY_MAX_HIDDEN or H % 16:
+            raise ValueError("NativePolicy: hidden width must be a multiple of 16 in 16..%d (got %d)" % (N.POLICY_MAX_HIDDEN, H))
+        A = int(pi[0].shape[0])
+        if A < 2 or A > 4:
+            raise ValueError("NativePolicy: n_actions must be in 2..4 (ssg_step accepts actions 0..3; got %d)" % A)
+        want = [((H, D), (H,))] + [((H, H), (H,))] * (len(layers) - 1) + [((A, H), (A,)), ((1, H), (1,))]
+        for (W, b), (ws, bs) in zip(layers + [tuple(pi), tuple(v)], want):
+            if tuple(W.shape) != ws or tuple(b.shape) != bs:
+                raise ValueError("NativePolicy: a (W, b) pair has shapes %s, %s where %s, %s belong" % (tuple(W.shape), tuple(b.shape), ws, bs))
+            if W.dtype != torch.float32 or b.dtype != torch.float32 or W.device != W0.device or b.device != W0.device:
+                raise ValueError("NativePolicy: every parameter must be float32 on one device")
+        self.obs_dim, self.hidden, self.n_hidden_layers, self.n_actions = D, H, len(layers), A
+        self.activation = activation
+        self.device = W0.device
+        self._sources = [t for pair in layers + [tuple(pi), tuple(v)] for t in pair]
+        self.offsets, total = packed_offsets(D, H, len(layers), A)
+        with torch.no_grad():
+            self.params = torch.empty(total, dtype=torch.float32, device=self.device)
+            self.refresh()
+            if not torch.is_tensor(obs_scale):
+                obs_scale = torch.full((D,), float(obs_scale), dtype=torch.float64)
+            obs_scale = obs_scale.detach().to(device=self.device, dtype=torch.float64).reshape(-1).contiguous()
+        if obs_scale.numel() != D:
+            raise ValueError("NativePolicy: obs_scale has %d entries, obs_dim is %d" % (obs_scale.numel(), D))
+        self.obs_scale = obs_scale
+
+    @classmethod
+    def from_actor_critic(cls, net, obs_scale):
+        """A NativePolicy over the parameters OF `net` (refresh() picks up their new values after an optimiser step).  `net` must be
+        shaped like train/ppo_torch.py's ActorCritic; anything else raises ValueError."""
+        nn = _torch().nn
+        body, pi, v = getattr(net, "body", None), getattr(net, "pi", None), getattr(net, "v", None)
+        if not isinstance(body, nn.Sequential) or not isinstance(pi, nn.Linear) or not isinstance(v, nn.Linear):
+            raise ValueError("from_actor_critic: expected a module with body = nn.Sequential, pi = nn.Linear, v = nn.Linear")
+        mods = list(body)
+        if len(mods) not in (2, 4):
+            raise ValueError("from_actor_critic: body must be Linear, act[, Linear, act] (1 or 2 hidden layers; got %d modules)" % len(mods))
+        acts = {nn.Tanh: "tanh", nn.ReLU: "relu"}
+        kinds = set()
+        layers = []
+        for lin, act in zip(mods[0::2], mods[1::2]):
+            if not isinstance(lin, nn.Linear) or type(act) not in acts or lin.bias is None:
+                raise ValueError("from_actor_critic: body must alternate nn.Linear (with bias) and nn.Tanh / nn.ReLU (got %s, %s)"
+                                 % (type(lin).__name__, type(act).__name__))
+            kinds.add(acts[type(act)])
+            layers.append((lin.weight, lin.bias))
+        if len(kinds) != 1:
+            raise ValueError("from_actor_critic: every hidden layer must use the same activation")
+        if pi.bias is None or v.bias is None or v.out_features != 1:
+            raise ValueError("from_actor_critic: heads must be nn.Linear with bias, v with one output")
+        return cls(layers, (pi.weight, pi.bias), (v.weight, v.bias), obs_scale, activation=kinds.pop())
+
+    def refresh(self):
+        """Re-pack the parameters into the same device buffer (one torch.cat): call after every optimiser step."""
+        torch = _torch()
+        with torch.no_grad():
+            torch.cat([t.detach().reshape(-1) for t in self._sources], out=self.params)
+        return self.params
+
+    def to_native(self):
+        """The ssg_policy record (pointers into this object's tensors: keep the policy alive while the library uses it)."""
+        p = N.Policy()
+        p.struct_size = C.sizeof(N.Policy)
+        p.obs_dim, p.hidden, p.n_hidden_layers, p.n_actions = self.obs_dim, self.hidden, self.n_hidden_layers, self.n_actions
+        p.activation = ACTIVATIONS[self.activation]
+        p.dev_params, p.dev_obs_scale = self.params.data_ptr(), self.obs_scale.data_ptr()
+        return p
+
+    def unpack(self):
+        """{name: tensor view} of the packed buffer, by the header's offsets."""
+        return {k: self.params[o: o + _numel(s)].view(*s) for k, (o, s) in self.offsets.items()}
+
+    def forward_reference(self, obs):
+        """Plain torch restatement: (x f32 [N, D], logits [N, A], value [N]) for f64 observations [N, D]."""
+        torch = _torch()
+        t = self.unpack()
+        act = torch.tanh if self.activation == "tanh" else torch.relu
+        with torch.no_grad():
+            x = (obs / self.obs_scale.to(obs.device)).float()
+            h = act(x @ t["W0"].T + t["b0"])
+            if self.n_hidden_layers == 2:
+                h = act(h @ t["W1"].T + t["b1"])
+            return x, h @ t["Wpi"].T + t["bpi"], (h @ t["Wv"].T + t["bv"]).squeeze(-1)
+
+
+def _numel(shape):
+    n = 1
+    for s in shape:
+        n *= s
+    return n

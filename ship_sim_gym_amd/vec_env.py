@@ -582,6 +582,81 @@ class ShipVecEnv(*_BASES):
         shapes only), so this is never needed to free memory; it exists for callers that recycle addresses deliberately."""
         self.__dict__.pop("_traj_plans", None)
 
+    # ------------------------------------------------------------------------------------------------
+    # the policy in the loop on the device (ABI 9: ssg_policy_act / ssg_rollout_policy; ship_sim_gym_amd/policy.py)
+    # ------------------------------------------------------------------------------------------------
+    def _check_policy(self, policy, what):
+        if self.map_mode == "fresh":
+            raise ValueError("%s: map_mode='fresh' draws every new world on the host at each done; use 'bank' or 'fresh_device'" % what)
+        if self.rllib:
+            raise ValueError("%s: the rllib flow is a numpy protocol (reset_at per done env); construct the env with rllib=False" % what)
+        if not self.auto_reset:
+            raise ValueError("%s: needs auto_reset=True (a done env is reset inside the step)" % what)
+        if policy.obs_dim != self.states_history:
+            raise ValueError("%s: the policy's obs_dim %d differs from the env's %d" % (what, policy.obs_dim, self.states_history))
+        if policy.params.device != self.device or policy.obs_scale.device != self.device:
+            raise ValueError("%s: the policy lives on %s, the env on %s" % (what, policy.params.device, self.device))
+
+    def _f32_rows(self, t, shape, what):
+        torch = _torch()
+        if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous() or t.dim() != len(shape) or t.shape[0] < shape[0] \
+                or tuple(t.shape[1:]) != tuple(shape[1:]):
+            raise ValueError("%s: expected a contiguous float32 tensor %s on %s (got %s %s on %s)"
+                             % (what, tuple(shape), self.device, t.dtype, tuple(t.shape), t.device))
+        return C.c_void_p(t.data_ptr())
+
+    def policy_act(self, policy, seed=0, step=0, uniforms=None, x_out=None):
+        """The policy forward + inverse-CDF sampling on the env's current `obs` (ssg_policy_act): returns (act int32 [N], logp [N],
+        value [N], x [N, D] float32) device tensors.  uniforms: float32 [N] (e.g. torch.rand) or None = Philox keyed by (seed, step,
+        global env id).  x_out: a float32 [N, D] tensor to write the normalised observations into."""
+        torch = _torch()
+        self._check_policy(policy, "policy_act")
+        n, D = self.num_envs, self.states_history
+        up = self._f32_rows(uniforms, (n,), "policy_act uniforms") if uniforms is not None else None
+        with torch.cuda.device(self.device):
+            act = torch.empty(n, dtype=torch.int32, device=self.device)
+            logp = torch.empty(n, dtype=torch.float32, device=self.device)
+            val = torch.empty(n, dtype=torch.float32, device=self.device)
+            x = x_out if x_out is not None else torch.empty((n, D), dtype=torch.float32, device=self.device)
+            xp = self._f32_rows(x, (n, D), "policy_act x_out")
+            pol = policy.to_native()
+            N.check(N.lib().ssg_policy_act(self._h, C.byref(pol), C.c_void_p(self.obs.data_ptr()), up, int(seed), int(step),
+                                           C.c_void_p(act.data_ptr()), C.c_void_p(logp.data_ptr()), C.c_void_p(val.data_ptr()), xp,
+                                           self._stream()), self._h, "ssg_policy_act")
+        return act, logp, val, x
+
+    def rollout_policy(self, policy, K, seed=0, step0=0, uniforms=None, out=None):
+        """K rollout steps with the policy in the loop, enqueued from C on the current stream (ssg_rollout_policy): step k runs the
+        policy on the env's current obs, then ssg_step with the sampled actions.  Returns a dict of device tensors — obs f32 [K, N, D]
+        (the normalised observation each step's action was drawn from), act i32 / logp f32 / val f32 / rew f64 / done u8 / flags u8
+        [K, N], last_val f32 [N] (the value of the observation after the last step).  uniforms: float32 [K, N] or None = Philox keyed
+        by (seed, step0 + k, global env id).  out: such a dict, preallocated (first dimension >= K), to write into.  Leaves `obs`
+        holding the observation after the last step, like K step_tensor calls."""
+        torch = _torch()
+        self._check_policy(policy, "rollout_policy")
+        K, n, D = int(K), self.num_envs, self.states_history
+        if K < 1:
+            raise ValueError("rollout_policy: K must be >= 1")
+        up = self._f32_rows(uniforms, (K, n), "rollout_policy uniforms") if uniforms is not None else None
+        specs = {"obs": ((K, n, D), torch.float32), "act": ((K, n), torch.int32), "logp": ((K, n), torch.float32),
+                 "val": ((K, n), torch.float32), "rew": ((K, n), torch.float64), "done": ((K, n), torch.uint8),
+                 "flags": ((K, n), torch.uint8), "last_val": ((n,), torch.float32)}
+        with torch.cuda.device(self.device):
+            if out is None:
+                out = {k: torch.empty(s, dtype=dt, device=self.device) for k, (s, dt) in specs.items()}
+            for k, (s, dt) in specs.items():
+                t = out[k]
+                if (t.dtype != dt or t.device != self.device or not t.is_contiguous() or t.dim() != len(s) or t.shape[0] < s[0]
+                        or tuple(t.shape[1:]) != tuple(s[1:])):
+                    raise ValueError("rollout_policy: out[%r] must be a contiguous %s tensor %s on %s (got %s %s on %s)"
+                                     % (k, dt, s, self.device, t.dtype, tuple(t.shape), t.device))
+            pol = policy.to_native()
+            p = {k: C.c_void_p(out[k].data_ptr()) for k in specs}
+            N.check(N.lib().ssg_rollout_policy(self._h, C.byref(pol), K, up, int(seed), int(step0), C.c_void_p(self.obs.data_ptr()),
+                                               p["act"], p["logp"], p["val"], p["obs"], p["rew"], p["done"], p["flags"], p["last_val"],
+                                               n, self._stream()), self._h, "ssg_rollout_policy")
+        return {k: (v[:K] if k != "last_val" else v) for k, v in out.items()}
+
     def random_actions(self, seed, step0, K):
         """int32 [K, N] Philox action stream keyed by (seed, step, global env id), generated on the device."""
         torch = _torch()

@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""Rollout step with the policy in the loop: train/ppo_torch.py's `graph` mode (policy in PyTorch, the whole step one HIP graph)
+against its `native` mode (ssg_rollout_policy: policy kernel + ssg_step per step, enqueued from C), in one process.
+
+For each env count (65 536 and 4 096; default env: 10 beams, history 2 -> D = 32; ActorCritic hidden 64, 2 layers, 3 actions): both
+modes are set up on their own envs and warmed up, then whole rollouts (horizon 64, ppo_torch.rollout() — the same uniforms draw and
+buffer conversions the trainer does) are timed with HIP events that end in a synchronize, 5 repeats alternating the two modes;
+the median per mode in us per rollout step.  The policy kernel's own time: HIP events around 50 back-to-back ssg_policy_act launches
+on preallocated buffers (a launch-bound upper bound where the kernel is shorter than the host call; `rocprofv3 --kernel-trace --stats`
+gives the kernel alone, see tools/README.md).  One JSON line on stdout.
+
+    python tools/policy_rollout_timing.py [--envs 65536,4096] [--horizon 64] [--repeats 5]
+"""
+import argparse
+import ctypes as C
+import importlib.util
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from ship_sim_gym_amd import _native as N  # noqa: E402
+
+
+def _ppo():
+    spec = importlib.util.spec_from_file_location("ppo_torch", os.path.join(ROOT, "train", "ppo_torch.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def _timed(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3  # us
+
+
+def measure(mod, n, horizon, repeats, dev):
+    torch.manual_seed(0)
+    probe = mod.ShipVecEnv(1, mod.GameConfig, mod.EnvConfig, device=dev, n_maps=1)
+    D, A = probe.states_history, probe.action_space.n
+    probe.close()
+    net = mod.ActorCritic(D, A).to(dev)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    # graph mode, set up as train() does: reset, one eager warm-up step, reset, capture
+    g_shards = mod.make_shards(n, "graph", net, dev, horizon)
+    sh = g_shards[0]
+    sh.env.reset_tensor()
+    sh.step()
+    sh.env.reset_tensor()
+    sh.t.zero_()
+    torch.cuda.synchronize()
+    sh.capture(torch.cuda.Stream(device=dev))
+    torch.cuda.synchronize()
+    # native mode
+    n_shards = mod.make_shards(n, "native", net, dev, horizon)
+    n_shards[0].env.reset_tensor()
+    policy = mod.NativePolicy.from_actor_critic(net, n_shards[0].scale)
+    run = {"graph": lambda: mod.rollout(g_shards, horizon, "graph", gen),
+           "native": lambda: mod.rollout(n_shards, horizon, "native", gen, policy)}
+    for m in ("graph", "native", "graph", "native"):  # warm-up: two rollouts each
+        run[m]()
+    torch.cuda.synchronize()
+    times = {"graph": [], "native": []}
+    for _ in range(repeats):
+        for m in ("graph", "native"):
+            times[m].append(_timed(run[m]) / horizon)
+    # the policy kernel alone: back-to-back launches on preallocated buffers
+    env = n_shards[0].env
+    bufs = [torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, device=dev), torch.empty(n, device=dev),
+            torch.empty((n, D), device=dev)]
+    pol = policy.to_native()
+    L, h, st = N.lib(), env._h, env._stream()
+    obs, act, logp, val, x = (C.c_void_p(t.data_ptr()) for t in [env.obs] + bufs)
+
+    def launches(k):
+        for i in range(k):
+            N.check(L.ssg_policy_act(h, C.byref(pol), obs, None, 1, i, act, logp, val, x, st), h, "ssg_policy_act")
+    launches(5)
+    torch.cuda.synchronize()
+    kernel_us = statistics.median(_timed(lambda: launches(50)) / 50 for _ in range(repeats))
+    for s in g_shards + n_shards:
+        s.graph = None
+        s.env.close()
+    g = statistics.median(times["graph"])
+    nat = statistics.median(times["native"])
+    return {"envs": n, "obs_dim": D, "hidden": 64, "layers": 2, "n_actions": A, "horizon": horizon,
+            "graph_us_per_step": round(g, 2), "native_us_per_step": round(nat, 2), "speedup": round(g / nat, 2),
+            "native_env_steps_per_s": round(n / nat * 1e6), "policy_act_us": round(kernel_us, 2),
+            "repeats_us": {k: [round(t, 2) for t in v] for k, v in times.items()}}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", default="65536,4096")
+    ap.add_argument("--horizon", type=int, default=64)
+    ap.add_argument("--repeats", type=int, default=5)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "needs the MI355X"
+    mod = _ppo()
+    dev = "cuda:0"
+    res = [measure(mod, int(n), a.horizon, a.repeats, dev) for n in a.envs.split(",")]
+    print(json.dumps({"tool": "policy_rollout_timing", "device": torch.cuda.get_device_name(0), "results": res}))
+
+
+if __name__ == "__main__":
+    main()

@@ -4,9 +4,9 @@ device tensors — the role SubprocVecEnv + PPO2 play in the reference's train/s
 stable-baselines (absent from this image).  The env side is the only point: observations, rewards and dones never
 leave the GPU; the policy is a small MLP in fp32.
 
-    python train/ppo_torch.py --envs 4096 --updates 20 [--mode eager|graph|pingpong]
+    python train/ppo_torch.py --envs 4096 --updates 20 [--mode eager|graph|pingpong|native]
 
-Three ways to run the rollout loop (the reference's `model.learn` -> runner.run(): one `env.step(actions)` per policy
+Four ways to run the rollout loop (the reference's `model.learn` -> runner.run(): one `env.step(actions)` per policy
 forward, train/stable_baselines/ppo.py:84-100,122-123) — same arithmetic, same results bit for bit:
 
 * ``eager``    — every rollout step launches the policy forward, the action sampling, ``ssg_step`` and the buffer writes one
@@ -15,7 +15,12 @@ forward, train/stable_baselines/ppo.py:84-100,122-123) — same arithmetic, same
                  (a 1-ship handle on a shared bank launches with constant arguments, include/shipsim.h) and replayed per step:
                  one host call per rollout step;
 * ``pingpong`` — the batch is split into two halves (two ShipVecEnv shards, global env ids and so results unchanged), each
-                 with its own graph on its own stream: half A's env step runs while half B's policy forward does.
+                 with its own graph on its own stream: half A's env step runs while half B's policy forward does;
+* ``native``   — the policy forward + sampling run on the device inside the library (ship_sim_gym_amd/policy.py, ABI 9): the
+                 whole rollout is ONE ``env.rollout_policy`` call that enqueues {policy kernel, ``ssg_step``} per step from C, then the
+                 buffers' dtype conversions once per rollout; ``policy.refresh()`` re-packs the parameters after each PPO update.
+                 Same uniforms, same formulas; the MLP's f32 sums are the kernel's own fmaf chains, so logp / value agree with the
+                 PyTorch modes to rounding and an action differs only where a uniform lies within rounding of a CDF boundary.
 
 The sampling noise of a whole rollout is drawn in one call before it (uniforms [horizon, envs], inverse-CDF sampling inside
 the step), so a captured step holds no random-number generator state and replays exactly what the eager loop computes.
@@ -34,6 +39,7 @@ import torch.nn as nn
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ship_gym.config import EnvConfig, GameConfig  # noqa: E402  (the reference's import lines, via the alias package)
 from ship_sim_gym_amd.vec_env import ShipVecEnv  # noqa: E402
+from ship_sim_gym_amd.policy import NativePolicy  # noqa: E402
 
 
 class ActorCritic(nn.Module):
@@ -130,9 +136,16 @@ def make_shards(envs, mode, net, device, horizon, n_maps=64, env_kw=None):
     return shards
 
 
-def rollout(shards, horizon, mode, gen):
-    """`horizon` policy-in-the-loop steps of every shard; returns the rollout buffers concatenated over the shards (env axis)."""
+def rollout(shards, horizon, mode, gen, policy=None):
+    """`horizon` policy-in-the-loop steps of every shard; returns the rollout buffers concatenated over the shards (env axis).
+    mode "native" (one shard, `policy` = its NativePolicy) also returns "last_val", the device's bootstrap value."""
     full = torch.rand((horizon, sum(sh.n for sh in shards)), generator=gen, device=shards[0].noise.device)
+    if mode == "native":
+        sh = shards[0]
+        o = sh.env.rollout_policy(policy, horizon, uniforms=full, out=getattr(sh, "native_out", None))
+        sh.native_out = o
+        return {"obs": o["obs"], "act": o["act"].long(), "logp": o["logp"], "val": o["val"], "rew": o["rew"].float(),
+                "done": o["done"].float(), "last_val": o["last_val"]}
     base = 0
     for sh in shards:  # (one draw for the whole batch, split by env: a split batch samples with the unsplit batch's uniforms)
         sh.noise.copy_(full[:, base: base + sh.n])
@@ -161,7 +174,7 @@ def rollout(shards, horizon, mode, gen):
 
 def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, gamma=0.99, lam=0.95, clip=0.2,
           device="cuda:0", seed=0, log=print, mode="eager", return_details=False, env_kw=None):
-    assert mode in ("eager", "graph", "pingpong")
+    assert mode in ("eager", "graph", "pingpong", "native")
     torch.manual_seed(seed)
     dev = torch.device(device)
     gen = torch.Generator(device=dev)
@@ -174,7 +187,8 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
     shards = make_shards(envs, mode, net, device, horizon, env_kw=env_kw)
     for sh in shards:
         sh.env.reset_tensor()
-    if mode != "eager":
+    policy = NativePolicy.from_actor_critic(net, shards[0].scale) if mode == "native" else None
+    if mode in ("graph", "pingpong"):
         # one eager warm-up step per shard OUTSIDE the capture (prepares the library's kernels and hipBLASLt's workspaces), then the
         # envs start over; the capture itself runs nothing
         for sh in shards:
@@ -190,13 +204,17 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
     for u in range(updates):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        b = rollout(shards, horizon, mode, gen)
+        b = rollout(shards, horizon, mode, gen, policy)
         torch.cuda.synchronize()
         t_roll += time.perf_counter() - t0
+        native_last_val = b.pop("last_val", None)
         if return_details is True:
             snapshots.append({k: v.clone() for k, v in b.items()})
-        with torch.no_grad():
-            last_val = torch.cat([net(normalise(sh.env.obs, sh.scale))[1] for sh in shards])
+        if native_last_val is not None:
+            last_val = native_last_val
+        else:
+            with torch.no_grad():
+                last_val = torch.cat([net(normalise(sh.env.obs, sh.scale))[1] for sh in shards])
         adv = torch.zeros(envs, device=dev)
         advs, rets = [None] * horizon, [None] * horizon
         nxt = last_val
@@ -219,6 +237,8 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
                 pg = -torch.min(ratio * b_adv[mb], torch.clamp(ratio, 1 - clip, 1 + clip) * b_adv[mb]).mean()
                 loss = pg + 0.5 * (val - b_ret[mb]).pow(2).mean() - 0.01 * dist.entropy().mean()
                 opt.zero_grad(); loss.backward(); opt.step()
+        if policy is not None:
+            policy.refresh()
         st = {k: sum(sh.env.stats()[k] for sh in shards) for k in ("sum_return", "episodes", "goals_hit")}
         mean_ret = st["sum_return"] / max(st["episodes"], 1)
         goals_per_ep = st["goals_hit"] / max(st["episodes"], 1)
@@ -240,11 +260,15 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
     return (history, details) if return_details else history
 
 
-if __name__ == "__main__":
+def make_arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--updates", type=int, default=20)
     ap.add_argument("--horizon", type=int, default=64)
-    ap.add_argument("--mode", choices=("eager", "graph", "pingpong"), default="graph")
-    a = ap.parse_args()
+    ap.add_argument("--mode", choices=("eager", "graph", "pingpong", "native"), default="graph")
+    return ap
+
+
+if __name__ == "__main__":
+    a = make_arg_parser().parse_args()
     train(envs=a.envs, updates=a.updates, horizon=a.horizon, mode=a.mode)
