@@ -32,7 +32,9 @@ extern "C" {
                              8: ssg_set_terminal_obs (the RLlib flow without a reset launch), ssg_step_host / ssg_wait_host (a numpy-protocol step in one
                                 call), ssg_debug_launch_clock, ssg_debug_clock_probe;
                              9: ssg_policy, ssg_policy_act, ssg_rollout_policy (the policy forward + action sampling of a rollout step on
-                                the device: rollouts with the policy in the loop, driven from C) */
+                                the device: rollouts with the policy in the loop, driven from C); extended, additively and without a
+                                version change: ssg_ppo_hparams, ssg_ppo_workspace_nbytes, ssg_ppo_gae, ssg_ppo_grad, ssg_ppo_adam,
+                                ssg_ppo_update (GAE and the PPO update of that policy on the device) */
 
 typedef enum ssg_status {
     SSG_OK = 0,
@@ -439,6 +441,83 @@ int ssg_rollout_policy(ssg_handle *h, const ssg_policy *pol, int K, const float 
                        int64_t step0, double *dev_obs, int32_t *dev_act_KN, float *dev_logp_KN, float *dev_value_KN,
                        float *dev_x_KND /* nullable */, double *dev_reward_KN, uint8_t *dev_done_KN, uint8_t *dev_flags_KN /* nullable */,
                        float *dev_last_value /* nullable */, int64_t step_stride_envs, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * The PPO update on the device (additions to ABI 9)
+ * What the reference's PPO2 does after every rollout inside model.learn (train/stable_baselines/ppo.py:90), and what
+ * train/ppo_torch.py does in eager PyTorch: GAE over the rollout buffers of ssg_rollout_policy, the advantage mean / unbiased std,
+ * then epochs x minibatches of {forward, clipped PPO loss, backward, Adam} on the packed parameters of an ssg_policy.
+ *
+ * Samples.  A rollout of K steps x N envs is K*N samples in [K][N] order: sample i = t*N + e.  The gradient entry points read
+ * x f32 [K*N][obs_dim] (the normalised observations ssg_rollout_policy writes), act i32, logp f32 (of the acting policy), and
+ * adv / ret f32 from ssg_ppo_gae, each [K*N], through a minibatch of int64 sample indices.
+ *
+ * Loss, per minibatch of M samples (p = softmax(logits), r = exp(log p[act] - logp_old), A = (adv - mean) / (std + adv_eps) with the
+ * mean / unbiased std that ssg_ppo_gae left in the workspace):
+ *   loss = -mean(min(r*A, clamp(r, 1-clip, 1+clip)*A)) + vf_coef*mean((v - ret)^2) - ent_coef*mean(entropy(p))
+ * Its gradient follows autograd's conventions: min passes half the gradient to each side on a tie, clamp passes it inside
+ * [1-clip, 1+clip] inclusive, tanh' = 1 - y*y, ReLU'(0) = 0.  Sums over samples run in a fixed order (per workgroup tile, then the
+ * workgroups' partials in order): a gradient is bitwise reproducible for a given M.  No floating-point atomics.
+ *
+ * Adam: torch.optim.Adam's default (foreach) formula, step t = 1, 2, ...:  m = lerp(m, g, 1-beta1);  v = beta2*v + (1-beta2)*g*g;
+ *   p -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps).  dev_adam_mv: f32 [2*P] (m, then v; zero before step 1),
+ * P = the packed length.  The Adam entry points write pol->dev_params in place: the next ssg_rollout_policy sees the new weights.
+ *
+ * Workspace: caller-owned device memory of ssg_ppo_workspace_nbytes bytes (256-byte aligned), shared by the calls of one update:
+ * ssg_ppo_gae leaves the advantage statistics in it, which the gradient entry points read on the device (no host round trip).
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct ssg_ppo_hparams {
+    uint32_t struct_size; /* sizeof(ssg_ppo_hparams) */
+    double gamma;         /* GAE discount (rounded to f32 where the reference trainer multiplies a tensor by it) */
+    double lam;           /* GAE lambda (gamma*lam formed in double, then rounded to f32) */
+    double clip;          /* PPO clip range, > 0 */
+    double vf_coef;       /* value-loss coefficient (train/ppo_torch.py: 0.5) */
+    double ent_coef;      /* entropy coefficient (0.01) */
+    double lr;            /* Adam learning rate (3e-4) */
+    double beta1, beta2;  /* Adam betas (0.9, 0.999) */
+    double eps;           /* Adam eps (1e-8) */
+    double adv_eps;       /* advantage normalisation: (adv - mean) / (std + adv_eps) (1e-8) */
+} ssg_ppo_hparams;
+
+/* Replaces nothing (memory binding): the workspace size for a policy shaped like *pol, rollouts of up to n_samples = K*N samples
+ * and minibatches of up to max_minibatch samples.  SSG_ERR_BAD_ARG for a bad record or sizes < 1. */
+int ssg_ppo_workspace_nbytes(const ssg_policy *pol, int64_t n_samples, int64_t max_minibatch, size_t *nbytes);
+
+/* Replaces: the advantage / return computation of PPO2's runner before the update behind model.learn
+ * (train/stable_baselines/ppo.py:90; train/ppo_torch.py's GAE loop).  One lane per env walks t = K-1 .. 0 with exactly the
+ * reference trainer's f32 operations: nonterm = 1 - done; delta = (rew + (gamma*nxt)*nonterm) - val;
+ * adv = delta + (gamma*lam)*nonterm*adv; ret = adv + val; nxt = val (nxt starts at dev_last_value).  Rows of every [K][N] buffer are
+ * N apart.  Also leaves mean(adv) and std(adv) (unbiased) in the workspace.  Two launches on `stream`.  SSG_ERR_BAD_ARG (nothing
+ * launched) for NULL pointers, K < 1, N < 1, K*N < 2 or a workspace too small. */
+int ssg_ppo_gae(ssg_handle *h, const ssg_ppo_hparams *hp, int K, int N, const double *dev_reward_KN, const uint8_t *dev_done_KN,
+                const float *dev_value_KN, const float *dev_last_value, float *dev_adv_KN, float *dev_ret_KN, void *dev_workspace,
+                size_t workspace_nbytes, void *stream);
+
+/* Replaces: one minibatch of PPO2's update behind model.learn (train/stable_baselines/ppo.py:90) without the optimiser step: the
+ * gradient of the loss above over the samples dev_idx[0 .. M) (int64, each in [0, n_samples)) of a rollout of n_samples, written to
+ * dev_grad (f32 [P], the packed layout of ssg_policy).  dev_stats (nullable): f32[4] = the minibatch means of the pg loss, (v - ret)^2,
+ * the entropy and the clip fraction (|r - 1| > clip).  Needs ssg_ppo_gae's statistics in the workspace.  Two launches on `stream`.
+ * SSG_ERR_BAD_ARG (nothing launched) for a bad record, NULL pointers, M < 1 or a workspace too small. */
+int ssg_ppo_grad(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, int64_t n_samples, const float *dev_x,
+                 const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret, const int64_t *dev_idx,
+                 int64_t M, float *dev_grad, float *dev_stats /* nullable */, void *dev_workspace, size_t workspace_nbytes, void *stream);
+
+/* Replaces: the optimiser step of that update (PPO2's Adam, train/stable_baselines/ppo.py:90; torch.optim.Adam.step in
+ * train/ppo_torch.py): Adam step `step` (>= 1) with the gradient dev_grad (f32 [P]) on pol->dev_params, moments in dev_adam_mv.
+ * One launch on `stream`.  SSG_ERR_BAD_ARG (nothing launched) for a bad record, NULL pointers or step < 1. */
+int ssg_ppo_adam(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, const float *dev_grad, float *dev_adam_mv,
+                 int64_t step, void *stream);
+
+/* Replaces: the whole update behind model.learn (train/stable_baselines/ppo.py:90: noptepochs x nminibatches of gradient + Adam),
+ * enqueued from C on `stream`: for epoch e and minibatch b, the samples dev_perm[e*n_samples + b*C .. + C) (C = ceil(n_samples /
+ * minibatches), the last chunk shorter: torch.chunk's split, so as many chunks as it makes), then {gradient, Adam step step0 + 1 + j}
+ * for the j-th minibatch, two launches each.  dev_stats (nullable): f32 [epochs*chunks][4], ssg_ppo_grad's stats per minibatch.
+ * Needs ssg_ppo_gae's statistics in the workspace.  SSG_ERR_BAD_ARG (nothing launched) for a bad record, NULL pointers,
+ * epochs < 1, minibatches < 1, step0 < 0 or a workspace too small. */
+int ssg_ppo_update(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, int64_t n_samples, const float *dev_x,
+                   const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret, const int64_t *dev_perm,
+                   int epochs, int minibatches, float *dev_adam_mv, int64_t step0, float *dev_stats /* nullable */,
+                   void *dev_workspace, size_t workspace_nbytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Host-side geometry (what pymunk's cffi exposed at reset time); no GPU needed.

@@ -29,6 +29,7 @@ EXPORTS = (
     "ssg_init_state", "ssg_refill_worlds", "ssg_debug_launch_geometry", "ssg_rollout_traj", "ssg_debug_dyn_counters", "ssg_debug_kernel_times",
     "ssg_debug_clock_probe", "ssg_debug_launch_clock", "ssg_set_terminal_obs", "ssg_step_host", "ssg_wait_host",
     "ssg_policy_act", "ssg_rollout_policy",
+    "ssg_ppo_workspace_nbytes", "ssg_ppo_gae", "ssg_ppo_grad", "ssg_ppo_adam", "ssg_ppo_update",
 )
 
 
@@ -57,6 +58,15 @@ class Policy(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("obs_dim", C.c_int32), ("hidden", C.c_int32), ("n_hidden_layers", C.c_int32),
         ("n_actions", C.c_int32), ("activation", C.c_int32), ("dev_params", C.c_void_p), ("dev_obs_scale", C.c_void_p),
+    ]
+
+
+class PpoHparams(C.Structure):
+    """ssg_ppo_hparams (ABI 9 addition): GAE, loss and Adam hyper-parameters of the device's PPO update."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("gamma", C.c_double), ("lam", C.c_double), ("clip", C.c_double), ("vf_coef", C.c_double),
+        ("ent_coef", C.c_double), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+        ("adv_eps", C.c_double),
     ]
 
 
@@ -113,6 +123,13 @@ def lib():
     L.ssg_policy_act.argtypes = [vp, C.POINTER(Policy), vp, vp, C.c_uint64, C.c_int64, vp, vp, vp, vp, vp]
     L.ssg_rollout_policy.argtypes = [vp, C.POINTER(Policy), C.c_int, vp, C.c_uint64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                      C.c_int64, vp]
+    L.ssg_ppo_workspace_nbytes.argtypes = [C.POINTER(Policy), C.c_int64, C.c_int64, szp]
+    L.ssg_ppo_gae.argtypes = [vp, C.POINTER(PpoHparams), C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.ssg_ppo_grad.argtypes = [vp, C.POINTER(Policy), C.POINTER(PpoHparams), C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp,
+                               C.c_size_t, vp]
+    L.ssg_ppo_adam.argtypes = [vp, C.POINTER(Policy), C.POINTER(PpoHparams), vp, vp, C.c_int64, vp]
+    L.ssg_ppo_update.argtypes = [vp, C.POINTER(Policy), C.POINTER(PpoHparams), C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp,
+                                 C.c_int64, vp, vp, C.c_size_t, vp]
     L.ssg_render.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, vp]
     L.ssg_dyn_invalidate.argtypes = [vp, vp, vp]
     L.ssg_host_convex_hull.argtypes = [C.c_int, dp, dp, ip]

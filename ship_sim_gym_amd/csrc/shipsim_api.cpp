@@ -53,6 +53,7 @@ struct ssg_handle {
     hipEvent_t host_ev[kHostSlots] = {};
     bool host_ev_made[kHostSlots] = {};
     bool policy_prepared = false; // ssg_policy_act / ssg_rollout_policy: the policy kernel's dynamic-LDS limit is set
+    bool ppo_prepared = false;    // ssg_ppo_grad / ssg_ppo_update: the gradient kernel's dynamic-LDS limit is set
     std::string err;
 };
 
@@ -1048,6 +1049,159 @@ int ssg_rollout_policy(ssg_handle *h, const ssg_policy *pol, int K, const float 
         hipError_t e = ssg::launch_policy_act(*pol, h->cfg.n_envs, h->cfg.env_id_base, dev_obs, nullptr, seed, step0 + K, nullptr, nullptr,
                                               dev_last_value, nullptr, st);
         if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("policy launch: ") + hipGetErrorString(e));
+    }
+    return SSG_OK;
+}
+
+// ABI 9 additions: GAE and the PPO update.  As above, everything a call could refuse is refused before anything is enqueued.
+static int check_policy_shape(const ssg_policy *pol)
+{
+    return pol && pol->struct_size == sizeof(ssg_policy) && pol->obs_dim >= 1 && pol->obs_dim <= SSG_MAX_HISTORY * (6 + SSG_MAX_BEAMS) &&
+           pol->hidden >= 16 && pol->hidden <= SSG_POLICY_MAX_HIDDEN && pol->hidden % 16 == 0 && pol->n_hidden_layers >= 1 &&
+           pol->n_hidden_layers <= 2 && pol->n_actions >= 2 && pol->n_actions <= 4 &&
+           (pol->activation == SSG_POLICY_TANH || pol->activation == SSG_POLICY_RELU);
+}
+
+static int check_hparams(ssg_handle *h, const ssg_ppo_hparams *hp, const char *what)
+{
+    const std::string w(what);
+    if (!hp) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL hparams");
+    if (hp->struct_size != sizeof(ssg_ppo_hparams)) return fail(h, SSG_ERR_BAD_ARG, w + ": ssg_ppo_hparams.struct_size != sizeof(ssg_ppo_hparams)");
+    const double v[] = {hp->gamma, hp->lam, hp->clip, hp->vf_coef, hp->ent_coef, hp->lr, hp->beta1, hp->beta2, hp->eps, hp->adv_eps};
+    for (double x : v)
+        if (!std::isfinite(x)) return fail(h, SSG_ERR_BAD_ARG, w + ": a hyper-parameter is not finite");
+    if (!(hp->clip > 0.0)) return fail(h, SSG_ERR_BAD_ARG, w + ": clip must be > 0");
+    if (!(hp->beta1 >= 0.0 && hp->beta1 < 1.0 && hp->beta2 >= 0.0 && hp->beta2 < 1.0)) return fail(h, SSG_ERR_BAD_ARG, w + ": betas must be in [0, 1)");
+    return SSG_OK;
+}
+
+static size_t ppo_need_gae(long long N) { return ssg::kPpoSlotsOff + (size_t)ssg::ppo_gae_blocks(N) * 16; }
+static size_t ppo_need_grad(const ssg_policy &p, long long M)
+{
+    return ssg::kPpoSlotsOff + (size_t)ssg::ppo_grid(M) * (size_t)(ssg::ppo_packed_len(p) + 4) * sizeof(float);
+}
+
+static int check_workspace(ssg_handle *h, const void *ws, size_t nbytes, size_t need, const char *what)
+{
+    const std::string w(what);
+    if (!ws) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL workspace");
+    if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) return fail(h, SSG_ERR_BAD_ARG, w + ": the workspace must be 256-byte aligned");
+    if (nbytes < need) {
+        char buf[200];
+        std::snprintf(buf, sizeof buf, ": workspace of %zu bytes, this call needs %zu (ssg_ppo_workspace_nbytes)", nbytes, need);
+        return fail(h, SSG_ERR_BAD_ARG, w + buf);
+    }
+    return SSG_OK;
+}
+
+static int prepare_ppo(ssg_handle *h)
+{
+    if (h->ppo_prepared) return SSG_OK;
+    hipError_t e = ssg::prepare_ppo();
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("prepare_ppo: ") + hipGetErrorString(e));
+    h->ppo_prepared = true;
+    return SSG_OK;
+}
+
+int ssg_ppo_workspace_nbytes(const ssg_policy *pol, int64_t n_samples, int64_t max_minibatch, size_t *nbytes)
+{
+    if (!nbytes || !check_policy_shape(pol) || n_samples < 1 || max_minibatch < 1)
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_ppo_workspace_nbytes: bad policy record, NULL nbytes or a size < 1");
+    *nbytes = std::max(ppo_need_gae(n_samples), ppo_need_grad(*pol, max_minibatch));
+    return SSG_OK;
+}
+
+int ssg_ppo_gae(ssg_handle *h, const ssg_ppo_hparams *hp, int K, int N, const double *dev_reward_KN, const uint8_t *dev_done_KN,
+                const float *dev_value_KN, const float *dev_last_value, float *dev_adv_KN, float *dev_ret_KN, void *dev_workspace,
+                size_t workspace_nbytes, void *stream)
+{
+    int rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    rc = check_hparams(h, hp, "ssg_ppo_gae");
+    if (rc != SSG_OK) return rc;
+    if (!dev_reward_KN || !dev_done_KN || !dev_value_KN || !dev_last_value || !dev_adv_KN || !dev_ret_KN)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_gae: NULL reward, done, value, last value, adv or ret buffer");
+    if (K < 1 || N < 1 || (long long)K * N < 2) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_gae: K and N must be >= 1 and K*N >= 2");
+    rc = check_workspace(h, dev_workspace, workspace_nbytes, ppo_need_gae(N), "ssg_ppo_gae");
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_ppo_gae(*hp, K, N, dev_reward_KN, dev_done_KN, dev_value_KN, dev_last_value, dev_adv_KN, dev_ret_KN,
+                                       dev_workspace, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("gae launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+static int check_batch(ssg_handle *h, int64_t n_samples, const float *x, const int32_t *act, const float *logp, const float *adv,
+                       const float *ret, const void *idx, const char *what)
+{
+    if (!x || !act || !logp || !adv || !ret || !idx)
+        return fail(h, SSG_ERR_BAD_ARG, std::string(what) + ": NULL x, act, logp, adv, ret or index buffer");
+    if (n_samples < 1) return fail(h, SSG_ERR_BAD_ARG, std::string(what) + ": n_samples < 1");
+    return SSG_OK;
+}
+
+int ssg_ppo_grad(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, int64_t n_samples, const float *dev_x,
+                 const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret, const int64_t *dev_idx,
+                 int64_t M, float *dev_grad, float *dev_stats, void *dev_workspace, size_t workspace_nbytes, void *stream)
+{
+    int rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    rc = check_policy(h, pol, "ssg_ppo_grad");
+    if (rc == SSG_OK) rc = check_hparams(h, hp, "ssg_ppo_grad");
+    if (rc == SSG_OK) rc = check_batch(h, n_samples, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_idx, "ssg_ppo_grad");
+    if (rc != SSG_OK) return rc;
+    if (!dev_grad) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_grad: NULL dev_grad");
+    if (M < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_grad: M < 1");
+    rc = check_workspace(h, dev_workspace, workspace_nbytes, ppo_need_grad(*pol, M), "ssg_ppo_grad");
+    if (rc == SSG_OK) rc = prepare_ppo(h);
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_ppo_grad(*pol, *hp, n_samples, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_idx, M, dev_workspace,
+                                        dev_grad, dev_stats, nullptr, 0, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("ppo grad launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+int ssg_ppo_adam(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, const float *dev_grad, float *dev_adam_mv,
+                 int64_t step, void *stream)
+{
+    int rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    rc = check_policy(h, pol, "ssg_ppo_adam");
+    if (rc == SSG_OK) rc = check_hparams(h, hp, "ssg_ppo_adam");
+    if (rc != SSG_OK) return rc;
+    if (!dev_grad || !dev_adam_mv) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_adam: NULL dev_grad or dev_adam_mv");
+    if (step < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_adam: step must be >= 1");
+    hipError_t e = ssg::launch_ppo_adam(*pol, *hp, dev_grad, dev_adam_mv, step, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("adam launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+int ssg_ppo_update(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, int64_t n_samples, const float *dev_x,
+                   const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret, const int64_t *dev_perm,
+                   int epochs, int minibatches, float *dev_adam_mv, int64_t step0, float *dev_stats, void *dev_workspace,
+                   size_t workspace_nbytes, void *stream)
+{
+    int rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    rc = check_policy(h, pol, "ssg_ppo_update");
+    if (rc == SSG_OK) rc = check_hparams(h, hp, "ssg_ppo_update");
+    if (rc == SSG_OK) rc = check_batch(h, n_samples, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_perm, "ssg_ppo_update");
+    if (rc != SSG_OK) return rc;
+    if (!dev_adam_mv) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_update: NULL dev_adam_mv");
+    if (epochs < 1 || minibatches < 1 || step0 < 0) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_update: epochs < 1, minibatches < 1 or step0 < 0");
+    const long long n = n_samples, C = (n + minibatches - 1) / minibatches; // torch.chunk: chunks of ceil(n / minibatches)
+    rc = check_workspace(h, dev_workspace, workspace_nbytes, ppo_need_grad(*pol, C), "ssg_ppo_update");
+    if (rc == SSG_OK) rc = prepare_ppo(h);
+    if (rc != SSG_OK) return rc;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    int64_t step = step0, j = 0;
+    for (int ep = 0; ep < epochs; ++ep) {
+        for (long long b0 = 0; b0 < n; b0 += C, ++j) {
+            const long long M = std::min(C, n - b0);
+            hipError_t e = ssg::launch_ppo_grad(*pol, *hp, n_samples, dev_x, dev_act, dev_logp, dev_adv, dev_ret,
+                                                dev_perm + (size_t)ep * (size_t)n + (size_t)b0, M, dev_workspace, nullptr,
+                                                dev_stats ? dev_stats + 4 * j : nullptr, dev_adam_mv, ++step, st);
+            if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("ppo update launch: ") + hipGetErrorString(e));
+        }
     }
     return SSG_OK;
 }

@@ -206,6 +206,24 @@ size_t policy_lds_bytes(const ssg_policy &p);
 hipError_t prepare_policy(); // (the dynamic-LDS limit of the kernel: up to 79 KB per workgroup at obs_dim 176, hidden 128)
 hipError_t launch_policy_act(const ssg_policy &p, int n, long long env_base, const double *obs, const float *uniform, uint64_t seed,
                              int64_t step, int32_t *act, float *logp, float *value, float *x, hipStream_t stream);
+// GAE and the PPO update (shipsim_ppo.hip).  Workspace: f32[4] advantage statistics at kPpoStatsOff (mean, std + adv_eps, its
+// inverse), then from kPpoSlotsOff the gradient kernel's per-workgroup slots [grid][P + 4] — or, during ssg_ppo_gae, its f64 partials.
+constexpr size_t kPpoStatsOff = 0, kPpoSlotsOff = 256;
+constexpr int kPpoMaxGrid = 512; // gradient workgroups at most (the slots a minibatch's partial gradients are summed over)
+inline int ppo_gae_blocks(long long N) { return (int)((N + 255) / 256); }
+int ppo_packed_len(const ssg_policy &p);
+int ppo_grid(long long M); // gradient workgroups for a minibatch of M samples
+size_t ppo_grad_lds_bytes(const ssg_policy &p);
+hipError_t prepare_ppo(); // (the dynamic-LDS limit of the gradient kernel: up to 151 KB at obs_dim 176, hidden 128, 2 layers)
+hipError_t launch_ppo_gae(const ssg_ppo_hparams &hp, int K, int N, const double *rew, const uint8_t *done, const float *val,
+                          const float *last_val, float *adv, float *ret, void *ws, hipStream_t stream);
+// the gradient of one minibatch into the workspace's slots, then their sum: into grad_out (nullable) and, with adam_mv, Adam step
+// `step` on p.dev_params; stats_out (nullable): the minibatch's loss means
+hipError_t launch_ppo_grad(const ssg_policy &p, const ssg_ppo_hparams &hp, long long n_samples, const float *x, const int32_t *act,
+                           const float *logp, const float *adv, const float *ret, const int64_t *idx, long long M, void *ws,
+                           float *grad_out, float *stats_out, float *adam_mv, int64_t step, hipStream_t stream);
+hipError_t launch_ppo_adam(const ssg_policy &p, const ssg_ppo_hparams &hp, const float *grad, float *adam_mv, int64_t step,
+                           hipStream_t stream);
 
 #ifdef __HIPCC__
 // One round of Philox4x32-10 (counter ctr, key key).  The counter-based streams of the library — fill_actions_kernel's actions

@@ -1,0 +1,520 @@
+// shipsim_ppo.hip — GAE and the PPO update on the device: ssg_ppo_gae / ssg_ppo_grad / ssg_ppo_adam / ssg_ppo_update (include/shipsim.h).
+//
+// What the reference's PPO2 does after every rollout inside model.learn (train/stable_baselines/ppo.py:90) and what train/ppo_torch.py
+// does in eager PyTorch: GAE, advantage normalisation, then per minibatch the MLP forward, the clipped PPO loss, its backward and Adam.
+//
+// GAE.  One lane per env walks t = K-1 .. 0 over coalesced [K][N] rows with the trainer's f32 operations in its order (bitwise equal),
+// and sums adv / adv^2 in f64 per workgroup; a one-workgroup kernel adds those partials in a fixed order into mean, std + adv_eps and
+// its inverse, which the gradient kernel reads from the workspace.
+//
+// Gradient.  A workgroup (4 waves) takes tiles of 64 samples: the gathered inputs, every layer's activations and the backward deltas
+// of a tile live in LDS as [sample][feature] rows (stride +1 float against bank conflicts).  The three matrix products per layer —
+// forward Z = In·Wᵀ, backward dIn = dZ·W and the weight gradient dW = dZᵀ·In (a contraction over the tile's samples) — run on
+// v_mfma_f32_16x16x4_f32 (exact f32: a k-ordered fmaf chain), one 16x16 output tile per wave at a time; the forward and dIn products
+// read their B operand (the weights) from global memory (L2-resident) and keep 4 row-tile accumulators per weight fragment.  The heads
+// (A <= 4 logits and the value) and the per-sample loss run on the VALU, one lane per sample.  A workgroup accumulates its tiles'
+// weight gradients in its own slot of the caller's workspace (read-modify-write by the lane that owns the entry, so in tile order),
+// its bias / head gradients and loss sums in registers; a second kernel adds the slots in workgroup order and, for an update, applies
+// Adam to the packed parameters in place.  Deterministic for a given M (the grid depends on M only); no floating-point atomics.
+#include <cmath>
+#include <cstdint>
+
+#include "shipsim_internal.h"
+
+namespace ssg {
+namespace {
+
+constexpr int kTile = 64;     // samples per tile
+constexpr int kPpoBlock = 256; // threads of the gradient kernel (4 waves)
+
+typedef float f4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float activate(float v, int kind) { return kind == SSG_POLICY_RELU ? fmaxf(v, 0.0f) : tanhf(v); }
+// autograd's derivative from the stored output: tanh' = 1 - y*y; ReLU' = (y > 0)
+__device__ __forceinline__ float dactivate(float y, int kind) { return kind == SSG_POLICY_RELU ? (y > 0.0f ? 1.0f : 0.0f) : 1.0f - y * y; }
+
+__device__ __forceinline__ f4 mfma4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// GAE
+// ------------------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) ppo_gae_kernel(int K, int N, const double *__restrict__ rew, const uint8_t *__restrict__ done,
+                                                      const float *__restrict__ val, const float *__restrict__ last_val,
+                                                      float *__restrict__ adv_out, float *__restrict__ ret_out, float gf, float glf,
+                                                      double2 *__restrict__ part)
+{
+    __shared__ double rs[256], rq[256];
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    double s = 0.0, q = 0.0;
+    if (e < N) {
+        float nxt = last_val[e], adv = 0.0f;
+        for (int t = K - 1; t >= 0; --t) {
+            const size_t i = (size_t)t * N + e;
+            const float nonterm = 1.0f - (float)done[i], v = val[i];
+            const float delta = ((float)rew[i] + (gf * nxt) * nonterm) - v;
+            adv = delta + (glf * nonterm) * adv;
+            adv_out[i] = adv;
+            ret_out[i] = adv + v;
+            nxt = v;
+            s += (double)adv;
+            q += (double)adv * (double)adv;
+        }
+    }
+    rs[threadIdx.x] = s;
+    rq[threadIdx.x] = q;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            rs[threadIdx.x] += rs[threadIdx.x + w];
+            rq[threadIdx.x] += rq[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = make_double2(rs[0], rq[0]);
+}
+
+// stats[0] = mean, stats[1] = std + adv_eps (unbiased std, as torch's .std()), stats[2] = 1 / stats[1]
+__global__ void __launch_bounds__(256) ppo_gae_stats_kernel(const double2 *__restrict__ part, int nblocks, double n, float adv_eps,
+                                                            float *__restrict__ stats)
+{
+    __shared__ double rs[256], rq[256];
+    double s = 0.0, q = 0.0;
+    for (int b = threadIdx.x; b < nblocks; b += 256) {
+        s += part[b].x;
+        q += part[b].y;
+    }
+    rs[threadIdx.x] = s;
+    rq[threadIdx.x] = q;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            rs[threadIdx.x] += rs[threadIdx.x + w];
+            rq[threadIdx.x] += rq[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double mean = rs[0] / n;
+        double var = (rq[0] - rs[0] * mean) / (n - 1.0);
+        if (var < 0.0) var = 0.0;
+        const float stdp = (float)sqrt(var) + adv_eps;
+        stats[0] = (float)mean;
+        stats[1] = stdp;
+        stats[2] = 1.0f / stdp;
+        stats[3] = 0.0f;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// the minibatch gradient
+// ------------------------------------------------------------------------------------------------------------------------------
+struct GradArgs {
+    int D, H, L, A, kind;
+    const float *params;
+    const float *x;
+    const int32_t *act;
+    const float *logp, *adv, *ret;
+    const int64_t *idx;
+    long long M, n_samples;
+    const float *stats; // mean, std + adv_eps (ssg_ppo_gae)
+    float *slots;       // [grid][P + 4]
+    int P;
+    float lo, hi, clip, vf, ent, invM;
+};
+
+// out[s][col] = act(bias[col] + sum_k in[s][k] * W[col][k]) for the tile's 64 rows; W global row-major [NT*16][K]; K4 = K rounded up
+// to 4 (in's columns K..K4 are zero).  Wave `wave` takes output column tiles wave, wave+4, ...; per k-step one weight fragment
+// feeds the 4 row tiles.
+__device__ __forceinline__ void mm_forward(const float *__restrict__ W, const float *__restrict__ bias, int K, int K4, int NT,
+                                           const float *in, int sin, float *out, int sout, int kind, int wave, int lane)
+{
+    const int r16 = lane & 15, kq = lane >> 4;
+    for (int ct = wave; ct < NT; ct += 4) {
+        const int col = ct * 16 + r16;
+        const float *wrow = W + (size_t)col * K;
+        f4 acc[4];
+#pragma unroll
+        for (int rt = 0; rt < 4; ++rt) acc[rt] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int k0 = 0; k0 < K4; k0 += 4) {
+            const int k = k0 + kq;
+            const float b = k < K ? wrow[k] : 0.0f;
+#pragma unroll
+            for (int rt = 0; rt < 4; ++rt) acc[rt] = mfma4(in[(rt * 16 + r16) * sin + k], b, acc[rt]);
+        }
+        const float bb = bias[col];
+#pragma unroll
+        for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) out[(rt * 16 + kq * 4 + r) * sout + col] = activate(acc[rt][r] + bb, kind);
+    }
+}
+
+// out[s][col] = (sum_j dz[s][j] * W[j][col]) * act'(y[s][col]): the delta of the layer below, W global row-major [H][H].
+__device__ __forceinline__ void mm_backward(const float *__restrict__ W, int H, const float *dz, const float *y, float *out, int sh,
+                                            int kind, int wave, int lane)
+{
+    const int r16 = lane & 15, kq = lane >> 4, NT = H / 16;
+    for (int ct = wave; ct < NT; ct += 4) {
+        const int col = ct * 16 + r16;
+        f4 acc[4];
+#pragma unroll
+        for (int rt = 0; rt < 4; ++rt) acc[rt] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int j0 = 0; j0 < H; j0 += 4) {
+            const float b = W[(size_t)(j0 + kq) * H + col];
+#pragma unroll
+            for (int rt = 0; rt < 4; ++rt) acc[rt] = mfma4(dz[(rt * 16 + r16) * sh + j0 + kq], b, acc[rt]);
+        }
+#pragma unroll
+        for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = rt * 16 + kq * 4 + r;
+                out[row * sh + col] = acc[rt][r] * dactivate(y[row * sh + col], kind);
+            }
+    }
+}
+
+// g[j][k] (+)= sum_s dz[s][j] * in[s][k] over the tile's 64 samples, j < NTj*16, k < Kcols (g row-major, row stride Kcols; in's
+// columns up to NTk*16 exist, those past Kcols are zero and not stored).  first: this workgroup's first tile (store, not add).
+__device__ __forceinline__ void mm_wgrad(const float *dz, int sdz, const float *in, int sin, int NTj, int NTk, int Kcols, float *g,
+                                         bool first, int wave, int lane)
+{
+    const int r16 = lane & 15, kq = lane >> 4;
+    for (int t = wave; t < NTj * NTk; t += 4) {
+        const int jt = t / NTk, kt = t - jt * NTk;
+        const int col = kt * 16 + r16;
+        f4 acc = f4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int s0 = 0; s0 < kTile; s0 += 4) {
+            const int s = s0 + kq;
+            acc = mfma4(dz[s * sdz + jt * 16 + r16], in[s * sin + col], acc);
+        }
+        if (col < Kcols) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float *dst = g + (size_t)(jt * 16 + kq * 4 + r) * Kcols + col;
+                *dst = first ? acc[r] : *dst + acc[r];
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kPpoBlock) ppo_grad_kernel(const GradArgs a)
+{
+    extern __shared__ float4 lds4[];
+    float *lds = reinterpret_cast<float *>(lds4);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int D = a.D, H = a.H, A = a.A, kind = a.kind, NT = H / 16;
+    const int DT = (D + 15) / 16, D4 = (D + 3) & ~3;
+    const int SX = DT * 16 + 1, SH = H + 1;
+    // LDS: X [64][SX] | HB0 [64][SH] | HB1 [64][SH] (2 layers) | DZ [64][SH] | WH [5][H] | DLOG [64][4] | DV [64] | sample scalars
+    float *X = lds;
+    float *HB0 = X + kTile * SX;
+    float *HB1 = HB0 + kTile * SH;
+    float *DZ = HB1 + (a.L == 2 ? kTile * SH : 0);
+    float *WH = DZ + kTile * SH;
+    float *DLOG = WH + 5 * H;
+    float *DV = DLOG + kTile * 4;
+    float *SLOGP = DV + kTile, *SADV = SLOGP + kTile, *SRET = SADV + kTile, *RED = SRET + kTile;
+    int *SACT = reinterpret_cast<int *>(RED + kTile * 4);
+    long long *SIDX = reinterpret_cast<long long *>(SACT + kTile); // (8-byte aligned: every region above is a multiple of 2 floats)
+
+    // packed offsets (include/shipsim.h)
+    const float *P = a.params;
+    const float *W0 = P, *b0 = P + H * D;
+    const float *W1 = b0 + H, *b1 = W1 + H * H;
+    const float *Wpi = a.L == 2 ? b1 + H : b0 + H;
+    const float *bpi = Wpi + A * H, *Wv = bpi + A, *bv = Wv + H;
+    float *g = a.slots + (size_t)blockIdx.x * (a.P + 4);
+    float *gW0 = g, *gb0 = g + H * D, *gW1 = gb0 + H, *gb1 = gW1 + H * H;
+    float *gWpi = g + (Wpi - P), *gbpi = g + (bpi - P), *gWv = g + (Wv - P), *gbv = g + (bv - P);
+
+    for (int i = tid; i < kTile * SX; i += kPpoBlock) X[i] = 0.0f; // (the padding columns stay zero)
+    for (int i = tid; i < 5 * H; i += kPpoBlock) {
+        const int j = i / H, k = i - j * H;
+        WH[i] = j < A ? Wpi[j * H + k] : (j == 4 ? Wv[k] : 0.0f);
+    }
+    const float mean = a.stats[0], stdp = a.stats[1];
+    const float *HL = a.L == 2 ? HB1 : HB0; // the last hidden layer
+    float accb0 = 0.0f, accb1 = 0.0f, accW[4] = {0.0f, 0.0f, 0.0f, 0.0f}, accWv = 0.0f, accbh = 0.0f;
+    float st_pg = 0.0f, st_vl = 0.0f, st_en = 0.0f, st_cf = 0.0f;
+    const long long ntiles = (a.M + kTile - 1) / kTile;
+    bool first = true;
+    for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        // 1. the tile's sample scalars, then its x rows (a row outside [0, n_samples) is a zero, gradient-free sample)
+        if (tid < kTile) {
+            const long long i = tile * kTile + tid;
+            long long j = i < a.M ? a.idx[i] : -1;
+            if (j >= a.n_samples) j = -1;
+            SIDX[tid] = j;
+            if (j >= 0) {
+                SACT[tid] = a.act[j];
+                SLOGP[tid] = a.logp[j];
+                SADV[tid] = (a.adv[j] - mean) / stdp;
+                SRET[tid] = a.ret[j];
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < kTile * D; i += kPpoBlock) {
+            const int s = i / D, d = i - s * D;
+            const long long j = SIDX[s];
+            X[s * SX + d] = j >= 0 ? a.x[(size_t)j * D + d] : 0.0f;
+        }
+        __syncthreads();
+        // 2. forward body
+        mm_forward(W0, b0, D, D4, NT, X, SX, HB0, SH, kind, wave, lane);
+        __syncthreads();
+        if (a.L == 2) {
+            mm_forward(W1, b1, H, H, NT, HB0, SH, HB1, SH, kind, wave, lane);
+            __syncthreads();
+        }
+        // 3. heads, loss and its gradient wrt the logits and the value: one lane per sample
+        if (tid < kTile) {
+            const int s = tid;
+            float lg[4], v = 0.0f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) lg[j] = 0.0f;
+            const float *h = HL + s * SH;
+            for (int k = 0; k < H; ++k) {
+                const float hk = h[k];
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < A) lg[j] = fmaf(WH[j * H + k], hk, lg[j]);
+                v = fmaf(WH[4 * H + k], hk, v);
+            }
+            float dl[4] = {0.0f, 0.0f, 0.0f, 0.0f}, dv = 0.0f;
+            if (SIDX[s] >= 0) {
+                v += bv[0];
+                float m = -INFINITY;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < A) {
+                        lg[j] += bpi[j];
+                        m = fmaxf(m, lg[j]);
+                    }
+                float se = 0.0f;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < A) se += expf(lg[j] - m);
+                const float lse = m + logf(se);
+                float lp[4], p[4], ent = 0.0f, lpa = 0.0f;
+                const int act = SACT[s];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    lp[j] = j < A ? lg[j] - lse : 0.0f;
+                    p[j] = j < A ? expf(lp[j]) : 0.0f;
+                    ent -= p[j] * lp[j];
+                    if (j == act) lpa = lp[j];
+                }
+                const float ratio = expf(lpa - SLOGP[s]), An = SADV[s];
+                const float s1 = ratio * An, s2 = fminf(fmaxf(ratio, a.lo), a.hi) * An;
+                const float gmin = -a.invM; // d loss / d min(s1, s2)
+                const float g1 = s1 < s2 ? gmin : (s1 == s2 ? 0.5f * gmin : 0.0f);
+                const float g2 = s2 < s1 ? gmin : (s1 == s2 ? 0.5f * gmin : 0.0f);
+                const bool inside = ratio >= a.lo && ratio <= a.hi;
+                const float gr = g1 * An + (inside ? g2 * An : 0.0f);
+                const float glpa = gr * ratio, gent = -a.ent * a.invM;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < A) dl[j] = glpa * ((j == act ? 1.0f : 0.0f) - p[j]) + gent * (-p[j] * (lp[j] + ent));
+                const float err = v - SRET[s];
+                dv = a.vf * 2.0f * err * a.invM;
+                st_pg += -fminf(s1, s2);
+                st_vl += err * err;
+                st_en += ent;
+                st_cf += fabsf(ratio - 1.0f) > a.clip ? 1.0f : 0.0f;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) DLOG[s * 4 + j] = dl[j];
+            DV[s] = dv;
+        }
+        __syncthreads();
+        // 4. the heads' backward: the last hidden layer's delta, and the heads' own gradients (registers, one column per lane)
+        for (int i = tid; i < kTile * H; i += kPpoBlock) {
+            const int s = i / H, k = i - s * H;
+            float d = DV[s] * WH[4 * H + k];
+            for (int j = 0; j < A; ++j) d = fmaf(DLOG[s * 4 + j], WH[j * H + k], d);
+            DZ[s * SH + k] = d * dactivate(HL[s * SH + k], kind);
+        }
+        if (tid < H) {
+            for (int s = 0; s < kTile; ++s) {
+                const float hk = HL[s * SH + tid];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) accW[j] = fmaf(DLOG[s * 4 + j], hk, accW[j]);
+                accWv = fmaf(DV[s], hk, accWv);
+            }
+        } else if (tid >= 128 && tid <= 128 + A) {
+            const int j = tid - 128;
+            for (int s = 0; s < kTile; ++s) accbh += j < A ? DLOG[s * 4 + j] : DV[s];
+        }
+        __syncthreads();
+        // 5. the second hidden layer: dW1 = dZᵀ·HB0, db1, and the first layer's delta into HB1 (dead by now)
+        const float *DZ0 = DZ;
+        if (a.L == 2) {
+            mm_wgrad(DZ, SH, HB0, SH, NT, NT, H, gW1, first, wave, lane);
+            mm_backward(W1, H, DZ, HB0, HB1, SH, kind, wave, lane);
+            if (tid >= 128 && tid < 128 + H)
+                for (int s = 0; s < kTile; ++s) accb1 += DZ[s * SH + tid - 128];
+            __syncthreads();
+            DZ0 = HB1;
+        }
+        // 6. the first layer: dW0 = dZ0ᵀ·X, db0
+        mm_wgrad(DZ0, SH, X, SX, NT, DT, D, gW0, first, wave, lane);
+        if (tid < H)
+            for (int s = 0; s < kTile; ++s) accb0 += DZ0[s * SH + tid];
+        __syncthreads();
+        first = false;
+    }
+    // the register-held sums into the slot
+    if (tid < H) {
+        gb0[tid] = accb0;
+        for (int j = 0; j < A; ++j) gWpi[j * H + tid] = accW[j];
+        gWv[tid] = accWv;
+    }
+    if (a.L == 2 && tid >= 128 && tid < 128 + H) gb1[tid - 128] = accb1;
+    if (tid >= 128 && tid <= 128 + A) (tid - 128 < A ? gbpi[tid - 128] : gbv[0]) = accbh;
+    if (tid < kTile) {
+        RED[tid * 4 + 0] = st_pg;
+        RED[tid * 4 + 1] = st_vl;
+        RED[tid * 4 + 2] = st_en;
+        RED[tid * 4 + 3] = st_cf;
+    }
+    __syncthreads();
+    if (tid < 4) {
+        float s = 0.0f;
+        for (int i = 0; i < kTile; ++i) s += RED[i * 4 + tid];
+        g[a.P + tid] = s;
+    }
+}
+
+// grad[p] = sum over the slots in order; entries P..P+3 (when nstats) are the loss sums -> stats = sum / M.  With params: Adam, torch's
+// foreach formula: m = lerp(m, g, 1-b1); v = v*b2 + (1-b2)*g*g; p += step_size * m / (sqrt(v) / sqrt(bc2) + eps), step_size = -lr/bc1.
+struct AdamArgs {
+    float w1, beta2, w2, bc2_sqrt, eps, step_size;
+};
+
+__global__ void __launch_bounds__(256) ppo_reduce_kernel(const float *__restrict__ slots, int G, int P, int stride, float fM,
+                                                         float *__restrict__ grad_out, float *__restrict__ stats_out,
+                                                         float *__restrict__ params, float *__restrict__ mv, const AdamArgs ad)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= stride) return;
+    float s = 0.0f;
+    for (int gi = 0; gi < G; ++gi) s += slots[(size_t)gi * stride + p];
+    if (p >= P) {
+        if (stats_out) stats_out[p - P] = s / fM;
+        return;
+    }
+    if (grad_out) grad_out[p] = s;
+    if (params) {
+        float m = mv[p], v = mv[P + p];
+        m = m + ad.w1 * (s - m);
+        v = v * ad.beta2;
+        v = v + ad.w2 * (s * s);
+        mv[p] = m;
+        mv[P + p] = v;
+        const float den = sqrtf(v) / ad.bc2_sqrt + ad.eps;
+        params[p] = params[p] + ad.step_size * (m / den);
+    }
+}
+
+AdamArgs adam_args(const ssg_ppo_hparams &hp, int64_t step)
+{
+    const double bc1 = 1.0 - std::pow(hp.beta1, (double)step), bc2 = 1.0 - std::pow(hp.beta2, (double)step);
+    AdamArgs ad;
+    ad.w1 = (float)(1.0 - hp.beta1);
+    ad.beta2 = (float)hp.beta2;
+    ad.w2 = (float)(1.0 - hp.beta2);
+    ad.bc2_sqrt = (float)std::sqrt(bc2);
+    ad.eps = (float)hp.eps;
+    ad.step_size = (float)(-(hp.lr / bc1));
+    return ad;
+}
+
+} // namespace
+
+int ppo_packed_len(const ssg_policy &p)
+{
+    const int D = p.obs_dim, H = p.hidden, A = p.n_actions;
+    return H * D + H + (p.n_hidden_layers - 1) * (H * H + H) + A * H + A + H + 1;
+}
+
+int ppo_grid(long long M)
+{
+    const long long t = (M + kTile - 1) / kTile;
+    return (int)(t < kPpoMaxGrid ? t : kPpoMaxGrid);
+}
+
+size_t ppo_grad_lds_bytes(const ssg_policy &p)
+{
+    const size_t D = (size_t)p.obs_dim, H = (size_t)p.hidden;
+    const size_t SX = (D + 15) / 16 * 16 + 1, SH = H + 1;
+    const size_t floats = kTile * SX + kTile * SH * (size_t)(p.n_hidden_layers + 1) + 5 * H + kTile * 4 + kTile + 4 * kTile + kTile * 4;
+    return floats * sizeof(float) + kTile * sizeof(int) + kTile * sizeof(long long) + 8;
+}
+
+hipError_t prepare_ppo()
+{
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(ppo_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+}
+
+hipError_t launch_ppo_gae(const ssg_ppo_hparams &hp, int K, int N, const double *rew, const uint8_t *done, const float *val,
+                          const float *last_val, float *adv, float *ret, void *ws, hipStream_t stream)
+{
+    const int nb = ppo_gae_blocks(N);
+    float *stats = reinterpret_cast<float *>(static_cast<char *>(ws) + kPpoStatsOff);
+    double2 *part = reinterpret_cast<double2 *>(static_cast<char *>(ws) + kPpoSlotsOff);
+    // torch rounds a Python scalar to f32 when it multiplies an f32 tensor; gamma * lam is formed in double first
+    hipLaunchKernelGGL(ppo_gae_kernel, dim3(nb), dim3(256), 0, stream, K, N, rew, done, val, last_val, adv, ret, (float)hp.gamma,
+                       (float)(hp.gamma * hp.lam), part);
+    hipLaunchKernelGGL(ppo_gae_stats_kernel, dim3(1), dim3(256), 0, stream, (const double2 *)part, nb, (double)K * (double)N,
+                       (float)hp.adv_eps, stats);
+    return hipGetLastError();
+}
+
+hipError_t launch_ppo_grad(const ssg_policy &p, const ssg_ppo_hparams &hp, long long n_samples, const float *x, const int32_t *act,
+                           const float *logp, const float *adv, const float *ret, const int64_t *idx, long long M, void *ws,
+                           float *grad_out, float *stats_out, float *adam_mv, int64_t step, hipStream_t stream)
+{
+    GradArgs a;
+    a.D = p.obs_dim;
+    a.H = p.hidden;
+    a.L = p.n_hidden_layers;
+    a.A = p.n_actions;
+    a.kind = p.activation;
+    a.params = p.dev_params;
+    a.x = x;
+    a.act = act;
+    a.logp = logp;
+    a.adv = adv;
+    a.ret = ret;
+    a.idx = idx;
+    a.M = M;
+    a.n_samples = n_samples;
+    a.stats = reinterpret_cast<const float *>(static_cast<const char *>(ws) + kPpoStatsOff);
+    a.slots = reinterpret_cast<float *>(static_cast<char *>(ws) + kPpoSlotsOff);
+    a.P = ppo_packed_len(p);
+    a.lo = (float)(1.0 - hp.clip);
+    a.hi = (float)(1.0 + hp.clip);
+    a.clip = (float)hp.clip;
+    a.vf = (float)hp.vf_coef;
+    a.ent = (float)hp.ent_coef;
+    a.invM = 1.0f / (float)M;
+    const int G = ppo_grid(M);
+    hipLaunchKernelGGL(ppo_grad_kernel, dim3(G), dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a);
+    const int stride = a.P + 4;
+    const AdamArgs ad = adam_mv ? adam_args(hp, step) : AdamArgs{};
+    hipLaunchKernelGGL(ppo_reduce_kernel, dim3((stride + 255) / 256), dim3(256), 0, stream, (const float *)a.slots, G, a.P, stride,
+                       (float)M, grad_out, stats_out, adam_mv ? const_cast<float *>(p.dev_params) : nullptr, adam_mv, ad);
+    return hipGetLastError();
+}
+
+hipError_t launch_ppo_adam(const ssg_policy &p, const ssg_ppo_hparams &hp, const float *grad, float *adam_mv, int64_t step,
+                           hipStream_t stream)
+{
+    const int P = ppo_packed_len(p);
+    hipLaunchKernelGGL(ppo_reduce_kernel, dim3((P + 255) / 256), dim3(256), 0, stream, grad, 1, P, P, 1.0f, nullptr, nullptr,
+                       const_cast<float *>(p.dev_params), adam_mv, adam_args(hp, step));
+    return hipGetLastError();
+}
+
+} // namespace ssg

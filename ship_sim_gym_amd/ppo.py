@@ -1,0 +1,168 @@
+"""NativePPO — GAE and the PPO update of a NativePolicy on the device (ssg_ppo_gae / ssg_ppo_grad / ssg_ppo_adam / ssg_ppo_update).
+
+The reference's PPO2 runs GAE and noptepochs x nminibatches of {loss, backward, Adam} after every rollout inside model.learn
+(train/stable_baselines/ppo.py:90); train/ppo_torch.py does the same in eager PyTorch.  ``NativePPO`` does it on the packed parameter
+buffer of a ``NativePolicy``: Adam writes ``policy.params`` in place, so the next ``rollout_policy`` acts with the new weights (do NOT
+call ``policy.refresh()`` afterwards: that would copy the module's stale parameters back).  ``load_into(net)`` copies them into the
+``nn.Module`` (checkpoints).  It owns the Adam moments and the workspace.
+
+A batch is the dict ``ShipVecEnv.rollout_policy`` returns (obs f32 [K, N, D], act i32, logp / val f32, rew f64, done u8 [K, N], last_val
+f32 [N]); ``gae`` adds "adv" and "ret" (f32 [K, N]) to it.  Sample i of the flattened batch is (t, e) = divmod(i, N).
+"""
+import ctypes as C
+
+from . import _native as N
+
+
+def _torch():
+    import torch
+    return torch
+
+
+class NativePPO(object):
+    """Defaults: train/ppo_torch.py's (Adam lr 3e-4, betas (0.9, 0.999), eps 1e-8; clip 0.2; loss pg + 0.5*vf - 0.01*entropy)."""
+
+    def __init__(self, policy, env, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, clip=0.2, vf_coef=0.5, ent_coef=0.01, adv_eps=1e-8):
+        torch = _torch()
+        self.policy, self.env = policy, env
+        if env.states_history != policy.obs_dim:
+            raise ValueError("NativePPO: the env's observation width %d differs from the policy's obs_dim %d" % (env.states_history, policy.obs_dim))
+        hp = N.PpoHparams()
+        hp.struct_size = C.sizeof(N.PpoHparams)
+        hp.gamma, hp.lam, hp.clip, hp.vf_coef, hp.ent_coef = 0.99, 0.95, float(clip), float(vf_coef), float(ent_coef)
+        hp.lr, hp.beta1, hp.beta2, hp.eps, hp.adv_eps = float(lr), float(betas[0]), float(betas[1]), float(eps), float(adv_eps)
+        self.hp = hp
+        self.n_params = policy.params.numel()
+        self.adam_mv = torch.zeros(2 * self.n_params, dtype=torch.float32, device=policy.device)  # m, then v
+        self.step = 0  # Adam steps taken
+        self.workspace = torch.zeros(0, dtype=torch.uint8, device=policy.device)
+
+    # ------------------------------------------------------------------------------------------------
+    def _ws(self, n_samples, max_minibatch):
+        """The workspace, grown to serve n_samples and minibatches of max_minibatch (its first 16 bytes — the advantage
+        statistics ssg_ppo_gae left — are kept when it grows)."""
+        torch = _torch()
+        need = C.c_size_t()
+        pol = self.policy.to_native()
+        N.check(N.lib().ssg_ppo_workspace_nbytes(C.byref(pol), int(n_samples), int(max_minibatch), C.byref(need)), None,
+                "ssg_ppo_workspace_nbytes")
+        if self.workspace.numel() < need.value:
+            ws = torch.zeros(need.value + 256, dtype=torch.uint8, device=self.policy.device)
+            if self.workspace.numel():
+                ws[:16].copy_(self.workspace[:16])
+            self.workspace = ws
+        return self.workspace
+
+    def _ws_ptr(self):
+        # (torch's allocations are 256-byte aligned; the header requires it)
+        return C.c_void_p(self.workspace.data_ptr()), self.workspace.numel()
+
+    def _stream(self):
+        return C.c_void_p(_torch().cuda.current_stream(self.policy.device).cuda_stream)
+
+    def _flat(self, batch, key, dtype):
+        t = batch[key]
+        if t.dtype != dtype or t.device != self.policy.device or not t.is_contiguous():
+            raise ValueError("NativePPO: batch[%r] must be a contiguous %s tensor on %s (got %s on %s)" % (key, dtype, self.policy.device, t.dtype, t.device))
+        return t
+
+    def _samples(self, batch):
+        torch = _torch()
+        x = self._flat(batch, "obs", torch.float32)
+        n = x.numel() // self.policy.obs_dim
+        ptrs = [C.c_void_p(self._flat(batch, k, dt).data_ptr()) for k, dt in
+                (("obs", torch.float32), ("act", torch.int32), ("logp", torch.float32), ("adv", torch.float32), ("ret", torch.float32))]
+        for k in ("act", "logp", "adv", "ret"):
+            if batch[k].numel() != n:
+                raise ValueError("NativePPO: batch[%r] has %d entries, the batch %d samples" % (k, batch[k].numel(), n))
+        return n, ptrs
+
+    # ------------------------------------------------------------------------------------------------
+    def gae(self, batch, gamma=0.99, lam=0.95):
+        """GAE over the rollout batch (train/ppo_torch.py's loop, bitwise): returns (adv, ret) f32 [K, N] and stores them in the batch
+        as "adv" / "ret".  Also leaves the advantage mean / std on the device for the update (adv_stats())."""
+        torch = _torch()
+        rew, done, val, last = (self._flat(batch, "rew", torch.float64), self._flat(batch, "done", torch.uint8),
+                                self._flat(batch, "val", torch.float32), self._flat(batch, "last_val", torch.float32))
+        K, n_env = int(rew.shape[0]), int(rew.shape[1])
+        if tuple(done.shape) != (K, n_env) or tuple(val.shape) != (K, n_env) or tuple(last.shape) != (n_env,):
+            raise ValueError("NativePPO.gae: rew / done / val must be [K, N] and last_val [N]")
+        self.hp.gamma, self.hp.lam = float(gamma), float(lam)
+        self._ws(K * n_env, 1)
+        adv = torch.empty((K, n_env), dtype=torch.float32, device=self.policy.device)
+        ret = torch.empty_like(adv)
+        ws, nb = self._ws_ptr()
+        h = self.env._h
+        with torch.cuda.device(self.policy.device):
+            N.check(N.lib().ssg_ppo_gae(h, C.byref(self.hp), K, n_env, C.c_void_p(rew.data_ptr()), C.c_void_p(done.data_ptr()),
+                                        C.c_void_p(val.data_ptr()), C.c_void_p(last.data_ptr()), C.c_void_p(adv.data_ptr()),
+                                        C.c_void_p(ret.data_ptr()), ws, nb, self._stream()), h, "ssg_ppo_gae")
+        batch["adv"], batch["ret"] = adv, ret
+        return adv, ret
+
+    def adv_stats(self):
+        """f32 [3] device view: the advantage mean, std + adv_eps and its inverse, as the last gae() left them."""
+        return self.workspace[:16].view(_torch().float32)[:3]
+
+    def grad(self, batch, idx, stats=False):
+        """The gradient (f32 [P], the packed layout) of the PPO loss over the samples idx (int64) of a batch gae() has seen; with
+        stats=True also the minibatch means (pg loss, (v - ret)^2, entropy, clip fraction) as f32 [4]."""
+        torch = _torch()
+        n, p = self._samples(batch)
+        idx = idx.to(device=self.policy.device, dtype=torch.int64).contiguous()
+        M = idx.numel()
+        self._ws(n, M)
+        g = torch.empty(self.n_params, dtype=torch.float32, device=self.policy.device)
+        st = torch.empty(4, dtype=torch.float32, device=self.policy.device) if stats else None
+        ws, nb = self._ws_ptr()
+        pol, h = self.policy.to_native(), self.env._h
+        with torch.cuda.device(self.policy.device):
+            N.check(N.lib().ssg_ppo_grad(h, C.byref(pol), C.byref(self.hp), n, *p, C.c_void_p(idx.data_ptr()), M, C.c_void_p(g.data_ptr()),
+                                         C.c_void_p(st.data_ptr()) if stats else None, ws, nb, self._stream()), h, "ssg_ppo_grad")
+        return (g, st) if stats else g
+
+    def adam_step(self, grad):
+        """One Adam step with a given gradient (f32 [P]) on policy.params, in place."""
+        torch = _torch()
+        grad = grad.to(device=self.policy.device, dtype=torch.float32).contiguous()
+        if grad.numel() != self.n_params:
+            raise ValueError("NativePPO.adam_step: gradient of %d entries, the policy has %d" % (grad.numel(), self.n_params))
+        pol, h = self.policy.to_native(), self.env._h
+        with torch.cuda.device(self.policy.device):
+            N.check(N.lib().ssg_ppo_adam(h, C.byref(pol), C.byref(self.hp), C.c_void_p(grad.data_ptr()), C.c_void_p(self.adam_mv.data_ptr()),
+                                         self.step + 1, self._stream()), h, "ssg_ppo_adam")
+        self.step += 1
+
+    def update(self, batch, perm, epochs, minibatches, stats=False):
+        """epochs x minibatches of {gradient, Adam} from ONE library call: the minibatches are perm[e].chunk(minibatches) (perm: int64
+        [epochs, K*N], e.g. torch.randperm rows).  stats=True returns f32 [epochs * chunks, 4] (grad()'s stats per minibatch)."""
+        torch = _torch()
+        n, p = self._samples(batch)
+        perm = perm.to(device=self.policy.device, dtype=torch.int64).contiguous()
+        if tuple(perm.shape) != (int(epochs), n):
+            raise ValueError("NativePPO.update: perm must be int64 [epochs, %d] (got %s)" % (n, tuple(perm.shape)))
+        chunk = -(-n // int(minibatches))
+        n_chunks = -(-n // chunk)
+        self._ws(n, chunk)
+        st = torch.empty((int(epochs) * n_chunks, 4), dtype=torch.float32, device=self.policy.device) if stats else None
+        ws, nb = self._ws_ptr()
+        pol, h = self.policy.to_native(), self.env._h
+        with torch.cuda.device(self.policy.device):
+            N.check(N.lib().ssg_ppo_update(h, C.byref(pol), C.byref(self.hp), n, *p, C.c_void_p(perm.data_ptr()), int(epochs),
+                                           int(minibatches), C.c_void_p(self.adam_mv.data_ptr()), self.step,
+                                           C.c_void_p(st.data_ptr()) if stats else None, ws, nb, self._stream()), h, "ssg_ppo_update")
+        self.step += int(epochs) * n_chunks
+        return st
+
+    def load_into(self, net):
+        """Copy the packed parameters into `net` (shaped like the policy: its parameters in torch.cat order)."""
+        torch = _torch()
+        params = list(net.parameters())
+        if sum(q.numel() for q in params) != self.n_params:
+            raise ValueError("NativePPO.load_into: the module has %d parameters, the policy %d" % (sum(q.numel() for q in params), self.n_params))
+        o = 0
+        with torch.no_grad():
+            for q in params:
+                q.copy_(self.policy.params[o: o + q.numel()].view_as(q))
+                o += q.numel()
+        return net

@@ -1,0 +1,275 @@
+"""GPU checks of GAE and the PPO update on the device (ship_sim_gym_amd/ppo.py, ssg_ppo_*): GAE bitwise against train/ppo_torch.py's
+loop, the minibatch gradient against an f64 autograd reference, Adam against torch.optim.Adam, a whole update against the f64
+reference of the same update (and run to run bitwise), and ppo_torch's --update native."""
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    import torch
+    assert torch.cuda.is_available(), "gpu tests need a HIP device"
+    return torch
+
+
+def _vec(n):
+    from ship_sim_gym_amd.vec_env import ShipVecEnv
+    return ShipVecEnv(n, n_maps=64)
+
+
+def _policy(torch, D, H=64, layers=2, act="tanh", A=3, seed=0):
+    from ship_sim_gym_amd.policy import NativePolicy
+    nn = torch.nn
+    g = torch.Generator().manual_seed(seed)
+    mods = [nn.Linear(D, H), nn.Tanh() if act == "tanh" else nn.ReLU()]
+    if layers == 2:
+        mods += [nn.Linear(H, H), nn.Tanh() if act == "tanh" else nn.ReLU()]
+    net = nn.Module()
+    net.body, net.pi, net.v = nn.Sequential(*mods), nn.Linear(H, A), nn.Linear(H, 1)
+    with torch.no_grad():
+        for p in net.parameters():
+            p.copy_(torch.rand(p.shape, generator=g) * 2 - 1).mul_(1.5 / p.shape[-1] ** 0.5)
+    net = net.to("cuda:0")
+    return net, NativePolicy.from_actor_critic(net, torch.full((D,), 600.0, dtype=torch.float64, device="cuda:0"))
+
+
+def _rollout(torch, env, pol, K, seed=1):
+    env.reset_tensor()
+    return dict(env.rollout_policy(pol, K, seed=seed))
+
+
+def _torch_gae(torch, b, gamma=0.99, lam=0.95):
+    """train/ppo_torch.py's GAE loop, restated on the native rollout's buffers (rew / done as ppo_torch converts them)."""
+    rew, done, val = b["rew"].float(), b["done"].float(), b["val"]
+    K, n = rew.shape
+    adv = torch.zeros(n, device=rew.device)
+    advs, rets = [None] * K, [None] * K
+    nxt = b["last_val"]
+    for t in reversed(range(K)):
+        nonterm = 1.0 - done[t]
+        delta = rew[t] + gamma * nxt * nonterm - val[t]
+        adv = delta + gamma * lam * nonterm * adv
+        advs[t], rets[t] = adv, adv + val[t]
+        nxt = val[t]
+    return torch.stack(advs), torch.stack(rets)
+
+
+@pytest.mark.parametrize("n,K", [(1000, 16), (4097, 8), (512, 1)])
+def test_gae_is_bitwise_the_trainers_loop(torch_cuda, n, K):
+    torch = torch_cuda
+    from ship_sim_gym_amd.ppo import NativePPO
+    env = _vec(n)
+    _, pol = _policy(torch, env.states_history)
+    b = _rollout(torch, env, pol, K)
+    # real dones, plus forced ones so that every K sees terminations mid-rollout
+    g = torch.Generator(device="cuda:0").manual_seed(n + K)
+    b["done"] = (b["done"] | (torch.rand(b["done"].shape, generator=g, device="cuda:0") < 0.05)).to(torch.uint8).contiguous()
+    assert int(b["done"].sum()) > 0
+    ppo = NativePPO(pol, env)
+    adv, ret = ppo.gae(b, 0.99, 0.95)
+    ref_adv, ref_ret = _torch_gae(torch, b)
+    assert torch.equal(adv, ref_adv) and torch.equal(ret, ref_ret)
+    flat = ref_adv.reshape(-1)
+    ref_norm = (flat - flat.mean()) / (flat.std() + 1e-8)
+    st = ppo.adv_stats()
+    mine = (adv.reshape(-1) - st[0]) / st[1]
+    assert float((mine - ref_norm).abs().max()) <= 1e-5
+    env.close()
+
+
+def _unpack(p, offsets):
+    return {k: p[o: o + int(np.prod(s))].view(*s) for k, (o, s) in offsets.items()}
+
+
+def _loss(torch, p, offsets, L, act, x, a, logp_old, advn, ret, clip=0.2):
+    """ppo_torch's minibatch loss on packed parameters p (any dtype); returns (loss, pg, (v-ret)^2 mean, entropy mean, clip fraction)."""
+    t = _unpack(p, offsets)
+    f = torch.tanh if act == "tanh" else torch.relu
+    h = f(x @ t["W0"].T + t["b0"])
+    if L == 2:
+        h = f(h @ t["W1"].T + t["b1"])
+    logits, v = h @ t["Wpi"].T + t["bpi"], (h @ t["Wv"].T + t["bv"]).squeeze(-1)
+    dist = torch.distributions.Categorical(logits=logits)
+    ratio = torch.exp(dist.log_prob(a) - logp_old)
+    pg = -torch.min(ratio * advn, torch.clamp(ratio, 1 - clip, 1 + clip) * advn).mean()
+    vl = (v - ret).pow(2).mean()
+    ent = dist.entropy().mean()
+    cf = ((ratio - 1).abs() > clip).to(x.dtype).mean()
+    return pg + 0.5 * vl - 0.01 * ent, pg, vl, ent, cf
+
+
+def _ref_grad(torch, pol, b, idx, advn, dtype):
+    x = b["obs"].reshape(-1, pol.obs_dim)[idx].to(dtype)
+    a = b["act"].reshape(-1)[idx].long()
+    lo, an, rt = b["logp"].reshape(-1)[idx].to(dtype), advn[idx].to(dtype), b["ret"].reshape(-1)[idx].to(dtype)
+    p = pol.params.detach().to(dtype).clone().requires_grad_(True)
+    out = _loss(torch, p, pol.offsets, pol.n_hidden_layers, pol.activation, x, a, lo, an, rt)
+    out[0].backward()
+    return p.grad.detach(), [float(o.detach()) for o in out[1:]]
+
+
+def _check_per_tensor(torch, pol, mine, ref64, ref32, what):
+    for k, (o, s) in pol.offsets.items():
+        n = int(np.prod(s))
+        g64 = ref64[o: o + n].double()
+        e_mine = float((mine[o: o + n].double() - g64).abs().max())
+        e_t32 = float((ref32[o: o + n].double() - g64).abs().max())
+        bound = 4 * e_t32 + 1e-6 * float(g64.abs().max())
+        assert e_mine <= bound, (what, k, e_mine, e_t32, bound)
+
+
+def _batch_for(torch, H, L, act, A, n=4096, K=10, seed=0):
+    from ship_sim_gym_amd.ppo import NativePPO
+    env = _vec(n)
+    _, pol = _policy(torch, env.states_history, H, L, act, A, seed=seed)
+    b = _rollout(torch, env, pol, K, seed=seed + 7)
+    ppo = NativePPO(pol, env)
+    ppo.gae(b)
+    # logp of an older policy: ratios clipped on both sides, and (where |log r| is small) ties of min() inside the clip range
+    g = torch.Generator(device="cuda:0").manual_seed(seed)
+    b["logp"] = (b["logp"] + (torch.rand(b["logp"].shape, generator=g, device="cuda:0") - 0.5) * 0.8).contiguous()
+    st = ppo.adv_stats()
+    advn = (b["adv"].reshape(-1) - st[0]) / st[1]
+    return env, pol, ppo, b, advn
+
+
+@pytest.mark.parametrize("H,L,act,A", [(16, 1, "relu", 2), (64, 2, "tanh", 3), (128, 2, "relu", 4), (128, 1, "tanh", 3),
+                                       (64, 1, "relu", 4), (16, 2, "tanh", 4)])
+def test_grad_matches_f64_autograd(torch_cuda, H, L, act, A):
+    torch = torch_cuda
+    env, pol, ppo, b, advn = _batch_for(torch, H, L, act, A, seed=H + L + A)
+    n = b["act"].numel()
+    g = torch.Generator(device="cuda:0").manual_seed(5)
+    perm = torch.randperm(n, device="cuda:0", generator=g)
+    sizes = [3000, n] if (H, L) == (64, 2) else [3000]
+    for M in sizes:
+        idx = perm[:M]
+        mine, st = ppo.grad(b, idx, stats=True)
+        again = ppo.grad(b, idx)
+        assert torch.equal(mine, again)                      # bitwise run to run
+        r64, terms64 = _ref_grad(torch, pol, b, idx, advn, torch.float64)
+        r32, terms32 = _ref_grad(torch, pol, b, idx, advn, torch.float32)
+        _check_per_tensor(torch, pol, mine, r64, r32, (H, L, act, A, M))
+        ratio_inside = terms64[3] < 1.0
+        assert ratio_inside and terms64[3] > 0.0, terms64      # clipped samples exist, and so do ties inside the range
+        for got, want in zip(st.tolist(), terms32):
+            assert abs(got - want) <= 1e-5 * abs(want) + 1e-6, (st.tolist(), terms32)
+    env.close()
+
+
+def test_clipped_on_both_sides_and_ties(torch_cuda):
+    """The default network's batch has ratios below 1-clip, above 1+clip, and inside (min() ties)."""
+    torch = torch_cuda
+    env, pol, ppo, b, advn = _batch_for(torch, 64, 2, "tanh", 3)
+    with torch.no_grad():
+        x = b["obs"].reshape(-1, pol.obs_dim)
+        t = _unpack(pol.params, pol.offsets)
+        h = torch.tanh(torch.tanh(x @ t["W0"].T + t["b0"]) @ t["W1"].T + t["b1"])
+        lp = torch.log_softmax(h @ t["Wpi"].T + t["bpi"], -1).gather(-1, b["act"].reshape(-1, 1).long()).squeeze(-1)
+        r = torch.exp(lp - b["logp"].reshape(-1))
+    assert int((r < 0.8).sum()) > 0 and int((r > 1.2).sum()) > 0 and int(((r >= 0.8) & (r <= 1.2)).sum()) > 0
+    env.close()
+
+
+def test_adam_matches_torch_optim(torch_cuda):
+    torch = torch_cuda
+    from ship_sim_gym_amd.ppo import NativePPO
+    env = _vec(64)
+    _, pol = _policy(torch, env.states_history)
+    ppo = NativePPO(pol, env, lr=3e-4)
+    ref = pol.params.detach().clone().requires_grad_(True)
+    opt = torch.optim.Adam([ref], lr=3e-4)
+    g = torch.Generator(device="cuda:0").manual_seed(3)
+    for _ in range(10):
+        grad = torch.randn(ref.shape, generator=g, device="cuda:0") * 0.1
+        ppo.adam_step(grad)
+        ref.grad = grad.clone()
+        opt.step()
+    torch.testing.assert_close(pol.params, ref.detach(), rtol=1e-6, atol=1e-7)
+    env.close()
+
+
+def _ref_update(torch, pol, b, advn, perm, epochs, minibatches, dtype):
+    p = pol.params.detach().to(dtype).clone().requires_grad_(True)
+    opt = torch.optim.Adam([p], lr=3e-4)
+    x = b["obs"].reshape(-1, pol.obs_dim).to(dtype)
+    a, lo = b["act"].reshape(-1).long(), b["logp"].reshape(-1).to(dtype)
+    an, rt = advn.to(dtype), b["ret"].reshape(-1).to(dtype)
+    for e in range(epochs):
+        for mb in perm[e].chunk(minibatches):
+            loss = _loss(torch, p, pol.offsets, pol.n_hidden_layers, pol.activation, x[mb], a[mb], lo[mb], an[mb], rt[mb])[0]
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+    return p.detach()
+
+
+def test_whole_update_against_f64_and_run_to_run(torch_cuda):
+    torch = torch_cuda
+    from ship_sim_gym_amd.ppo import NativePPO
+    env, pol, ppo, b, advn = _batch_for(torch, 64, 2, "tanh", 3, n=2048, K=8)
+    n = b["act"].numel()
+    g = torch.Generator(device="cuda:0").manual_seed(11)
+    perm = torch.stack([torch.randperm(n, device="cuda:0", generator=g) for _ in range(2)])
+    p0 = pol.params.detach().clone()
+    r64 = _ref_update(torch, pol, b, advn, perm, 2, 4, torch.float64)
+    r32 = _ref_update(torch, pol, b, advn, perm, 2, 4, torch.float32)
+    st = ppo.update(b, perm, 2, 4, stats=True)
+    assert st.shape == (8, 4) and bool(torch.isfinite(st).all())
+    first = pol.params.detach().clone()
+    _check_per_tensor(torch, pol, first, r64, r32, "update")
+    # again from the same start: bitwise the same parameters
+    stats = ppo.adv_stats().clone()
+    pol.params.copy_(p0)
+    ppo2 = NativePPO(pol, env)
+    ppo2._ws(n, -(-n // 4))
+    ppo2.workspace[:12].view(torch.float32).copy_(stats)
+    ppo2.update(b, perm, 2, 4)
+    assert torch.equal(pol.params, first)
+    env.close()
+
+
+def _ppo_mod():
+    spec = importlib.util.spec_from_file_location("ppo_torch_update_gpu", os.path.join(ROOT, "train", "ppo_torch.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_trainer_native_update(torch_cuda):
+    torch = torch_cuda
+    mod = _ppo_mod()
+    hist, det = mod.train(envs=4096, updates=3, horizon=32, log=lambda s: None, mode="native", update="native", return_details=True)
+    assert len(hist) == 3 and all(np.isfinite(h[1]) and np.isfinite(h[3]) for h in hist)
+    assert det["update_seconds"] > 0 and all(bool(torch.isfinite(p).all()) for p in det["params"])
+    # the first update sees the same first rollout and the same minibatches in both update paths
+    _, nat = mod.train(envs=4096, updates=1, horizon=32, log=lambda s: None, mode="native", update="native", return_details=True)
+    _, ref = mod.train(envs=4096, updates=1, horizon=32, log=lambda s: None, mode="native", update="torch", return_details=True)
+    for a, b in zip(nat["snapshots"][0].values(), ref["snapshots"][0].values()):
+        assert torch.equal(a, b)
+    torch.manual_seed(0)  # train()'s own start: the seed, the probe env, then the module (its initial parameters)
+    probe = mod.ShipVecEnv(1, mod.GameConfig, mod.EnvConfig, device="cuda:0", n_maps=1)
+    D, A = probe.states_history, probe.action_space.n
+    probe.close()
+    net0 = mod.ActorCritic(D, A)
+    for pn, pr, p0 in zip(nat["params"], ref["params"], net0.parameters()):
+        dn, dr = pn.cpu() - p0.detach(), pr.cpu() - p0.detach()
+        assert float((dn - dr).norm()) <= 0.02 * float(dr.norm()) + 1e-7, (float((dn - dr).norm()), float(dr.norm()))
+    # load_into round-trips the packed buffer into a module
+    from ship_sim_gym_amd.ppo import NativePPO
+    from ship_sim_gym_amd.policy import NativePolicy
+    env = _vec(64)
+    net, pol = _policy(torch, env.states_history)
+    ppo = NativePPO(pol, env)
+    ppo.adam_step(torch.ones(pol.params.numel(), device="cuda:0"))
+    other, _ = _policy(torch, env.states_history, seed=9)
+    ppo.load_into(other)
+    assert torch.equal(NativePolicy.from_actor_critic(other, 600.0).params, pol.params)
+    env.close()

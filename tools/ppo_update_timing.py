@@ -1,0 +1,140 @@
+#!/usr/bin/env python3
+"""GAE + PPO update after one rollout: train/ppo_torch.py's torch update (the GAE loop, autograd, torch.optim.Adam) against the native
+one (NativePPO: ssg_ppo_gae + ssg_ppo_update, ship_sim_gym_amd/ppo.py), in one process, on the same native rollout batch.
+
+For each (envs, horizon) — default 65 536 x 32 and 4 096 x 64; default env (D = 32), ActorCritic hidden 64, 2 layers, 3 actions;
+2 epochs x 4 minibatches — one rollout_policy batch is collected, then each path runs 2 warm-up updates and `--repeats` timed ones
+(alternating), each bracketed by a synchronize and timed with HIP events; the median per path in ms per update.  Both paths start
+every update from the same parameters' values (their own copies) and draw their permutations from generators seeded alike.  One JSON
+line on stdout.  The kernels alone: `rocprofv3 --kernel-trace --stats -- python tools/ppo_update_timing.py --only native` (tools/README.md).
+
+    python tools/ppo_update_timing.py [--configs 65536x32,4096x64] [--repeats 7] [--only torch|native]
+"""
+import argparse
+import importlib.util
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+
+def _ppo():
+    spec = importlib.util.spec_from_file_location("ppo_torch", os.path.join(ROOT, "train", "ppo_torch.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def _timed(fn):
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1)  # ms
+
+
+def torch_update(net, opt, b, horizon, envs, D, epochs, minibatches, gen, gamma=0.99, lam=0.95, clip=0.2):
+    """train/ppo_torch.py's update, as it runs after a native rollout (rew / done converted as rollout() does)."""
+    dev = b["obs"].device
+    rew, done, val = b["rew"].float(), b["done"].float(), b["val"]
+    adv = torch.zeros(envs, device=dev)
+    advs, rets = [None] * horizon, [None] * horizon
+    nxt = b["last_val"]
+    for t in reversed(range(horizon)):
+        nonterm = 1.0 - done[t]
+        delta = rew[t] + gamma * nxt * nonterm - val[t]
+        adv = delta + gamma * lam * nonterm * adv
+        advs[t], rets[t] = adv, adv + val[t]
+        nxt = val[t]
+    b_obs, b_act = b["obs"].reshape(horizon * envs, D), b["act"].long().reshape(-1)
+    b_logp, b_adv, b_ret = b["logp"].reshape(-1), torch.cat(advs), torch.cat(rets)
+    b_adv = (b_adv - b_adv.mean()) / (b_adv.std() + 1e-8)
+    n = b_obs.shape[0]
+    for _ in range(epochs):
+        perm = torch.randperm(n, device=dev, generator=gen)
+        for mb in perm.chunk(minibatches):
+            logits, v = net(b_obs[mb])
+            dist = torch.distributions.Categorical(logits=logits)
+            ratio = torch.exp(dist.log_prob(b_act[mb]) - b_logp[mb])
+            pg = -torch.min(ratio * b_adv[mb], torch.clamp(ratio, 1 - clip, 1 + clip) * b_adv[mb]).mean()
+            loss = pg + 0.5 * (v - b_ret[mb]).pow(2).mean() - 0.01 * dist.entropy().mean()
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+
+
+def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4):
+    from ship_sim_gym_amd.policy import NativePolicy
+    from ship_sim_gym_amd.ppo import NativePPO
+    torch.manual_seed(0)
+    env = mod.ShipVecEnv(envs, mod.GameConfig, mod.EnvConfig, device=dev, n_maps=64)
+    D, A = env.states_history, env.action_space.n
+    net = mod.ActorCritic(D, A).to(dev)
+    scale = torch.full((D,), float(max(env.bounds)), dtype=torch.float64, device=dev)
+    env.reset_tensor()
+    pol_roll = NativePolicy.from_actor_critic(net, scale)
+    b = dict(env.rollout_policy(pol_roll, horizon, seed=1))
+    p0 = [p.detach().clone() for p in net.parameters()]
+    # the torch path trains `net`; the native path a second module's packed parameters
+    net_n = mod.ActorCritic(D, A).to(dev)
+    pol = NativePolicy.from_actor_critic(net_n, scale)
+    opt = torch.optim.Adam(net.parameters(), lr=3e-4)
+    ppo = NativePPO(pol, env)
+    g_t, g_n = torch.Generator(device=dev), torch.Generator(device=dev)
+    g_t.manual_seed(1)
+    g_n.manual_seed(1)
+    n = horizon * envs
+
+    def run_torch():
+        with torch.no_grad():
+            for p, q in zip(net.parameters(), p0):
+                p.copy_(q)
+        torch_update(net, opt, b, horizon, envs, D, epochs, minibatches, g_t)
+
+    def run_native():
+        with torch.no_grad():
+            for p, q in zip(net_n.parameters(), p0):
+                p.copy_(q)
+        pol.refresh()
+        nb = dict(b)
+        ppo.gae(nb)
+        ppo.update(nb, torch.stack([torch.randperm(n, device=dev, generator=g_n) for _ in range(epochs)]), epochs, minibatches)
+
+    paths = [(k, f) for k, f in (("torch", run_torch), ("native", run_native)) if only in (None, k)]
+    times = {k: [] for k, _ in paths}
+    for _ in range(2):
+        for k, f in paths:
+            _timed(f)
+    for _ in range(repeats):
+        for k, f in paths:
+            times[k].append(_timed(f))
+    env.close()
+    out = {"envs": envs, "horizon": horizon, "epochs": epochs, "minibatches": minibatches, "samples_per_minibatch": -(-n // minibatches)}
+    for k, v in times.items():
+        out[k + "_ms_per_update"] = statistics.median(v)
+        out[k + "_ms_all"] = [round(x, 3) for x in v]
+    if "torch" in times and "native" in times:
+        out["speedup"] = out["torch_ms_per_update"] / out["native_ms_per_update"]
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", default="65536x32,4096x64")
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--only", choices=("torch", "native"), default=None)
+    a = ap.parse_args()
+    mod = _ppo()
+    res = [measure(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.repeats, a.only, "cuda:0") for c in a.configs.split(",")]
+    print(json.dumps({"ppo_update_timing": res}))
+
+
+if __name__ == "__main__":
+    main()

@@ -4,7 +4,7 @@ device tensors — the role SubprocVecEnv + PPO2 play in the reference's train/s
 stable-baselines (absent from this image).  The env side is the only point: observations, rewards and dones never
 leave the GPU; the policy is a small MLP in fp32.
 
-    python train/ppo_torch.py --envs 4096 --updates 20 [--mode eager|graph|pingpong|native]
+    python train/ppo_torch.py --envs 4096 --updates 20 [--mode eager|graph|pingpong|native] [--update torch|native]
 
 Four ways to run the rollout loop (the reference's `model.learn` -> runner.run(): one `env.step(actions)` per policy
 forward, train/stable_baselines/ppo.py:84-100,122-123) — same arithmetic, same results bit for bit:
@@ -21,6 +21,14 @@ forward, train/stable_baselines/ppo.py:84-100,122-123) — same arithmetic, same
                  buffers' dtype conversions once per rollout; ``policy.refresh()`` re-packs the parameters after each PPO update.
                  Same uniforms, same formulas; the MLP's f32 sums are the kernel's own fmaf chains, so logp / value agree with the
                  PyTorch modes to rounding and an action differs only where a uniform lies within rounding of a CDF boundary.
+
+Two ways to run the update after each rollout (GAE, advantage normalisation, epochs x minibatches of loss + backward + Adam):
+
+* ``torch``  — eager PyTorch: the GAE loop below, autograd and torch.optim.Adam on the module (the default);
+* ``native`` — (``--mode native`` only) ship_sim_gym_amd/ppo.py's NativePPO: GAE and the whole update on the device from two library
+               calls, on the packed parameters the native rollout reads (no refresh); the minibatches are the same randperm chunks,
+               drawn from the same generator.  Same loss, same conventions; the parameters agree with the torch update's to f32
+               rounding (the module is loaded from the packed buffer at the end, NativePPO.load_into).
 
 The sampling noise of a whole rollout is drawn in one call before it (uniforms [horizon, envs], inverse-CDF sampling inside
 the step), so a captured step holds no random-number generator state and replays exactly what the eager loop computes.
@@ -40,6 +48,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ship_gym.config import EnvConfig, GameConfig  # noqa: E402  (the reference's import lines, via the alias package)
 from ship_sim_gym_amd.vec_env import ShipVecEnv  # noqa: E402
 from ship_sim_gym_amd.policy import NativePolicy  # noqa: E402
+from ship_sim_gym_amd.ppo import NativePPO  # noqa: E402
 
 
 class ActorCritic(nn.Module):
@@ -173,8 +182,12 @@ def rollout(shards, horizon, mode, gen, policy=None):
 
 
 def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, gamma=0.99, lam=0.95, clip=0.2,
-          device="cuda:0", seed=0, log=print, mode="eager", return_details=False, env_kw=None):
+          device="cuda:0", seed=0, log=print, mode="eager", return_details=False, env_kw=None, update="torch"):
     assert mode in ("eager", "graph", "pingpong", "native")
+    if update not in ("torch", "native"):
+        raise ValueError("update must be 'torch' or 'native' (got %r)" % (update,))
+    if update == "native" and mode != "native":
+        raise ValueError("update='native' runs on the native policy's packed parameters: it needs mode='native' (got mode=%r)" % (mode,))
     torch.manual_seed(seed)
     dev = torch.device(device)
     gen = torch.Generator(device=dev)
@@ -188,6 +201,7 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
     for sh in shards:
         sh.env.reset_tensor()
     policy = NativePolicy.from_actor_critic(net, shards[0].scale) if mode == "native" else None
+    ppo = NativePPO(policy, shards[0].env, lr=lr, clip=clip) if update == "native" else None
     if mode in ("graph", "pingpong"):
         # one eager warm-up step per shard OUTSIDE the capture (prepares the library's kernels and hipBLASLt's workspaces), then the
         # envs start over; the capture itself runs nothing
@@ -199,7 +213,7 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         for sh in shards:
             sh.capture(torch.cuda.Stream(device=dev))
         torch.cuda.synchronize()
-    history, t_roll, t_all0 = [], 0.0, time.perf_counter()
+    history, t_roll, t_upd, t_all0 = [], 0.0, 0.0, time.perf_counter()
     snapshots = []
     for u in range(updates):
         torch.cuda.synchronize()
@@ -210,35 +224,44 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         native_last_val = b.pop("last_val", None)
         if return_details is True:
             snapshots.append({k: v.clone() for k, v in b.items()})
-        if native_last_val is not None:
-            last_val = native_last_val
+        t1 = time.perf_counter()
+        if ppo is not None:  # GAE + the whole update on the device, on the rollout's own buffers (the same randperm draws)
+            nb = dict(shards[0].native_out)
+            ppo.gae(nb, gamma, lam)
+            n = horizon * envs
+            ppo.update(nb, torch.stack([torch.randperm(n, device=dev, generator=gen) for _ in range(epochs)]), epochs, minibatches)
         else:
-            with torch.no_grad():
-                last_val = torch.cat([net(normalise(sh.env.obs, sh.scale))[1] for sh in shards])
-        adv = torch.zeros(envs, device=dev)
-        advs, rets = [None] * horizon, [None] * horizon
-        nxt = last_val
-        for t in reversed(range(horizon)):           # GAE; a done env's next obs belongs to a fresh episode (auto-reset)
-            nonterm = 1.0 - b["done"][t]
-            delta = b["rew"][t] + gamma * nxt * nonterm - b["val"][t]
-            adv = delta + gamma * lam * nonterm * adv
-            advs[t], rets[t] = adv, adv + b["val"][t]
-            nxt = b["val"][t]
-        b_obs, b_act = b["obs"].reshape(horizon * envs, D), b["act"].reshape(-1)
-        b_logp, b_adv, b_ret = b["logp"].reshape(-1), torch.cat(advs), torch.cat(rets)
-        b_adv = (b_adv - b_adv.mean()) / (b_adv.std() + 1e-8)
-        n = b_obs.shape[0]
-        for _ in range(epochs):
-            perm = torch.randperm(n, device=dev, generator=gen)
-            for mb in perm.chunk(minibatches):
-                logits, val = net(b_obs[mb])
-                dist = torch.distributions.Categorical(logits=logits)
-                ratio = torch.exp(dist.log_prob(b_act[mb]) - b_logp[mb])
-                pg = -torch.min(ratio * b_adv[mb], torch.clamp(ratio, 1 - clip, 1 + clip) * b_adv[mb]).mean()
-                loss = pg + 0.5 * (val - b_ret[mb]).pow(2).mean() - 0.01 * dist.entropy().mean()
-                opt.zero_grad(); loss.backward(); opt.step()
-        if policy is not None:
-            policy.refresh()
+            if native_last_val is not None:
+                last_val = native_last_val
+            else:
+                with torch.no_grad():
+                    last_val = torch.cat([net(normalise(sh.env.obs, sh.scale))[1] for sh in shards])
+            adv = torch.zeros(envs, device=dev)
+            advs, rets = [None] * horizon, [None] * horizon
+            nxt = last_val
+            for t in reversed(range(horizon)):           # GAE; a done env's next obs belongs to a fresh episode (auto-reset)
+                nonterm = 1.0 - b["done"][t]
+                delta = b["rew"][t] + gamma * nxt * nonterm - b["val"][t]
+                adv = delta + gamma * lam * nonterm * adv
+                advs[t], rets[t] = adv, adv + b["val"][t]
+                nxt = b["val"][t]
+            b_obs, b_act = b["obs"].reshape(horizon * envs, D), b["act"].reshape(-1)
+            b_logp, b_adv, b_ret = b["logp"].reshape(-1), torch.cat(advs), torch.cat(rets)
+            b_adv = (b_adv - b_adv.mean()) / (b_adv.std() + 1e-8)
+            n = b_obs.shape[0]
+            for _ in range(epochs):
+                perm = torch.randperm(n, device=dev, generator=gen)
+                for mb in perm.chunk(minibatches):
+                    logits, val = net(b_obs[mb])
+                    dist = torch.distributions.Categorical(logits=logits)
+                    ratio = torch.exp(dist.log_prob(b_act[mb]) - b_logp[mb])
+                    pg = -torch.min(ratio * b_adv[mb], torch.clamp(ratio, 1 - clip, 1 + clip) * b_adv[mb]).mean()
+                    loss = pg + 0.5 * (val - b_ret[mb]).pow(2).mean() - 0.01 * dist.entropy().mean()
+                    opt.zero_grad(); loss.backward(); opt.step()
+            if policy is not None:
+                policy.refresh()
+        torch.cuda.synchronize()
+        t_upd += time.perf_counter() - t1
         st = {k: sum(sh.env.stats()[k] for sh in shards) for k in ("sum_return", "episodes", "goals_hit")}
         mean_ret = st["sum_return"] / max(st["episodes"], 1)
         goals_per_ep = st["goals_hit"] / max(st["episodes"], 1)
@@ -247,11 +270,13 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
             u, st["episodes"], mean_ret, goals_per_ep, history[-1][3]))
     torch.cuda.synchronize()
     t_all = time.perf_counter() - t_all0
+    if ppo is not None:
+        ppo.load_into(net)  # the module gets the device-trained parameters (details["params"], checkpoints)
     steps = envs * horizon * updates
     log("rollout (%s): %.1f M env-steps/s with the policy in the loop; whole training loop (rollout + PPO update): %.1f M env-steps/s" % (
         mode, steps / max(t_roll, 1e-9) / 1e6, steps / max(t_all, 1e-9) / 1e6))
     details = {"mode": mode, "rollout_env_steps_per_s": steps / max(t_roll, 1e-9), "training_env_steps_per_s": steps / max(t_all, 1e-9),
-               "rollout_us_per_step": t_roll * 1e6 / (horizon * updates), "rollout_seconds": t_roll, "total_seconds": t_all,
+               "rollout_us_per_step": t_roll * 1e6 / (horizon * updates), "rollout_seconds": t_roll, "update_seconds": t_upd, "total_seconds": t_all,
                "snapshots": snapshots, "final_state": [env_columns(sh.env) for sh in shards] if return_details is True else None,
                "params": [p.detach().clone() for p in net.parameters()] if return_details is True else None}
     for sh in shards:
@@ -266,9 +291,20 @@ def make_arg_parser():
     ap.add_argument("--updates", type=int, default=20)
     ap.add_argument("--horizon", type=int, default=64)
     ap.add_argument("--mode", choices=("eager", "graph", "pingpong", "native"), default="graph")
+    ap.add_argument("--update", choices=("torch", "native"), default="torch",
+                    help="where GAE and the PPO update run: eager PyTorch, or on the device (needs --mode native)")
     return ap
 
 
+def parse_args(argv=None):
+    """make_arg_parser().parse_args, refusing --update native without --mode native."""
+    ap = make_arg_parser()
+    a = ap.parse_args(argv)
+    if a.update == "native" and a.mode != "native":
+        ap.error("--update native needs --mode native (the update runs on the native policy's packed parameters)")
+    return a
+
+
 if __name__ == "__main__":
-    a = make_arg_parser().parse_args()
-    train(envs=a.envs, updates=a.updates, horizon=a.horizon, mode=a.mode)
+    a = parse_args()
+    train(envs=a.envs, updates=a.updates, horizon=a.horizon, mode=a.mode, update=a.update)
