@@ -457,10 +457,12 @@ int ssg_rollout_policy(ssg_handle *h, const ssg_policy *pol, int K, const float 
  *   loss = -mean(min(r*A, clamp(r, 1-clip, 1+clip)*A)) + vf_coef*mean((v - ret)^2) - ent_coef*mean(entropy(p))
  * Its gradient follows autograd's conventions: min passes half the gradient to each side on a tie, clamp passes it inside
  * [1-clip, 1+clip] inclusive, tanh' = 1 - y*y, ReLU'(0) = 0.  Sums over samples run in a fixed order (per workgroup tile, then the
- * workgroups' partials in order): a gradient is bitwise reproducible for a given M.  No floating-point atomics.
+ * workgroups' partials; the bias sums and the partials as pairwise trees): a gradient is bitwise reproducible for a given M.  No
+ * floating-point atomics.
  *
  * Adam: torch.optim.Adam's default (foreach) formula, step t = 1, 2, ...:  m = lerp(m, g, 1-beta1);  v = beta2*v + (1-beta2)*g*g;
- *   p -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps).  dev_adam_mv: f32 [2*P] (m, then v; zero before step 1),
+ *   p -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps).  lerp is torch's, with both of its branches (w = 1-beta1
+ *   in f32):  m + w*(g - m) when |w| < 0.5;  g - (g - m)*(1 - w) otherwise (beta1 <= 0.5; 1 - w formed in f32), so beta1 = 0 gives m = g.  dev_adam_mv: f32 [2*P] (m, then v; zero before step 1),
  * P = the packed length.  The Adam entry points write pol->dev_params in place: the next ssg_rollout_policy sees the new weights.
  *
  * Workspace: caller-owned device memory of ssg_ppo_workspace_nbytes bytes (256-byte aligned), shared by the calls of one update:

@@ -14,7 +14,7 @@
 // read their B operand (the weights) from global memory (L2-resident) and keep 4 row-tile accumulators per weight fragment.  The heads
 // (A <= 4 logits and the value) and the per-sample loss run on the VALU, one lane per sample.  A workgroup accumulates its tiles'
 // weight gradients in its own slot of the caller's workspace (read-modify-write by the lane that owns the entry, so in tile order),
-// its bias / head gradients and loss sums in registers; a second kernel adds the slots in workgroup order and, for an update, applies
+// its bias / head gradients and loss sums in registers; a second kernel adds the slots (a fixed tree) and, for an update, applies
 // Adam to the packed parameters in place.  Deterministic for a given M (the grid depends on M only); no floating-point atomics.
 #include <cmath>
 #include <cstdint>
@@ -34,6 +34,27 @@ __device__ __forceinline__ float activate(float v, int kind) { return kind == SS
 __device__ __forceinline__ float dactivate(float y, int kind) { return kind == SSG_POLICY_RELU ? (y > 0.0f ? 1.0f : 0.0f) : 1.0f - y * y; }
 
 __device__ __forceinline__ f4 mfma4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+// x[0] + ... + x[N-1] as a pairwise tree (N a power of 2; x is overwritten).  Long f32 sums of the gradient run as trees, as torch's
+// reductions do: a 64- or 512-term chain loses several times torch's accuracy on cancelling or repeated terms.
+template <int N> __device__ __forceinline__ float tree_sum(float *x)
+{
+#pragma unroll
+    for (int w = N / 2; w > 0; w >>= 1)
+#pragma unroll
+        for (int i = 0; i < w; ++i) x[i] = x[i] + x[i + w];
+    return x[0];
+}
+
+// sum over the tile's 64 samples of v[s * stride]: 8 interleaved partial sums, then a tree
+__device__ __forceinline__ float tile_sum(const float *v, int stride)
+{
+    float t[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    for (int s = 0; s < kTile; s += 8)
+#pragma unroll
+        for (int r = 0; r < 8; ++r) t[r] += v[(s + r) * stride];
+    return tree_sum<8>(t);
+}
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // GAE
@@ -344,7 +365,7 @@ __global__ void __launch_bounds__(kPpoBlock) ppo_grad_kernel(const GradArgs a)
             }
         } else if (tid >= 128 && tid <= 128 + A) {
             const int j = tid - 128;
-            for (int s = 0; s < kTile; ++s) accbh += j < A ? DLOG[s * 4 + j] : DV[s];
+            accbh += j < A ? tile_sum(DLOG + j, 4) : tile_sum(DV, 1);
         }
         __syncthreads();
         // 5. the second hidden layer: dW1 = dZᵀ·HB0, db1, and the first layer's delta into HB1 (dead by now)
@@ -352,15 +373,13 @@ __global__ void __launch_bounds__(kPpoBlock) ppo_grad_kernel(const GradArgs a)
         if (a.L == 2) {
             mm_wgrad(DZ, SH, HB0, SH, NT, NT, H, gW1, first, wave, lane);
             mm_backward(W1, H, DZ, HB0, HB1, SH, kind, wave, lane);
-            if (tid >= 128 && tid < 128 + H)
-                for (int s = 0; s < kTile; ++s) accb1 += DZ[s * SH + tid - 128];
+            if (tid >= 128 && tid < 128 + H) accb1 += tile_sum(DZ + tid - 128, SH);
             __syncthreads();
             DZ0 = HB1;
         }
         // 6. the first layer: dW0 = dZ0ᵀ·X, db0
         mm_wgrad(DZ0, SH, X, SX, NT, DT, D, gW0, first, wave, lane);
-        if (tid < H)
-            for (int s = 0; s < kTile; ++s) accb0 += DZ0[s * SH + tid];
+        if (tid < H) accb0 += tile_sum(DZ0 + tid, SH);
         __syncthreads();
         first = false;
     }
@@ -386,10 +405,12 @@ __global__ void __launch_bounds__(kPpoBlock) ppo_grad_kernel(const GradArgs a)
     }
 }
 
-// grad[p] = sum over the slots in order; entries P..P+3 (when nstats) are the loss sums -> stats = sum / M.  With params: Adam, torch's
+// grad[p] = sum over the slots (a fixed order); entries P..P+3 (when nstats) are the loss sums -> stats = sum / M.  With params: Adam, torch's
 // foreach formula: m = lerp(m, g, 1-b1); v = v*b2 + (1-b2)*g*g; p += step_size * m / (sqrt(v) / sqrt(bc2) + eps), step_size = -lr/bc1.
+// torch's lerp (ATen/native/Lerp.h) has two branches: m + w*(g - m) for |w| < 0.5, g - (g - m)*(1 - w) otherwise (b1 <= 0.5), with
+// 1 - w formed in f32; with b1 = 0 the second gives m = g exactly.
 struct AdamArgs {
-    float w1, beta2, w2, bc2_sqrt, eps, step_size;
+    float w1, one_minus_w1, beta2, w2, bc2_sqrt, eps, step_size;
 };
 
 __global__ void __launch_bounds__(256) ppo_reduce_kernel(const float *__restrict__ slots, int G, int P, int stride, float fM,
@@ -398,8 +419,22 @@ __global__ void __launch_bounds__(256) ppo_reduce_kernel(const float *__restrict
 {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= stride) return;
-    float s = 0.0f;
-    for (int gi = 0; gi < G; ++gi) s += slots[(size_t)gi * stride + p];
+    float s = 0.0f; // the slots in order, 64 at a time as a tree of 4 trees of 16 (the missing ones are zeros)
+#pragma unroll 1
+    for (int b0 = 0; b0 < G; b0 += 64) {
+        float u[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float w[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int gi = b0 + i * 16 + j;
+                w[j] = gi < G ? slots[(size_t)gi * stride + p] : 0.0f;
+            }
+            u[i] = tree_sum<16>(w);
+        }
+        s += tree_sum<4>(u);
+    }
     if (p >= P) {
         if (stats_out) stats_out[p - P] = s / fM;
         return;
@@ -407,7 +442,7 @@ __global__ void __launch_bounds__(256) ppo_reduce_kernel(const float *__restrict
     if (grad_out) grad_out[p] = s;
     if (params) {
         float m = mv[p], v = mv[P + p];
-        m = m + ad.w1 * (s - m);
+        m = fabsf(ad.w1) < 0.5f ? m + ad.w1 * (s - m) : s - (s - m) * ad.one_minus_w1;
         v = v * ad.beta2;
         v = v + ad.w2 * (s * s);
         mv[p] = m;
@@ -422,6 +457,7 @@ AdamArgs adam_args(const ssg_ppo_hparams &hp, int64_t step)
     const double bc1 = 1.0 - std::pow(hp.beta1, (double)step), bc2 = 1.0 - std::pow(hp.beta2, (double)step);
     AdamArgs ad;
     ad.w1 = (float)(1.0 - hp.beta1);
+    ad.one_minus_w1 = 1.0f - ad.w1;
     ad.beta2 = (float)hp.beta2;
     ad.w2 = (float)(1.0 - hp.beta2);
     ad.bc2_sqrt = (float)std::sqrt(bc2);

@@ -19,6 +19,13 @@ def _torch():
     return torch
 
 
+def chunk_split(n, minibatches):
+    """(chunk length, number of chunks) of torch.chunk over n samples into `minibatches` parts, as ssg_ppo_update splits a perm row:
+    chunks of ceil(n / minibatches), the last one shorter, so as many chunks as that makes (which can be fewer than minibatches)."""
+    chunk = -(-int(n) // int(minibatches))
+    return chunk, -(-int(n) // chunk)
+
+
 class NativePPO(object):
     """Defaults: train/ppo_torch.py's (Adam lr 3e-4, betas (0.9, 0.999), eps 1e-8; clip 0.2; loss pg + 0.5*vf - 0.01*entropy)."""
 
@@ -141,8 +148,7 @@ class NativePPO(object):
         perm = perm.to(device=self.policy.device, dtype=torch.int64).contiguous()
         if tuple(perm.shape) != (int(epochs), n):
             raise ValueError("NativePPO.update: perm must be int64 [epochs, %d] (got %s)" % (n, tuple(perm.shape)))
-        chunk = -(-n // int(minibatches))
-        n_chunks = -(-n // chunk)
+        chunk, n_chunks = chunk_split(n, minibatches)
         self._ws(n, chunk)
         st = torch.empty((int(epochs) * n_chunks, 4), dtype=torch.float32, device=self.policy.device) if stats else None
         ws, nb = self._ws_ptr()

@@ -9,6 +9,8 @@ import os
 import numpy as np
 import pytest
 
+from helpers import actor_critic_policy as _policy, assert_same_rollout as _assert_same, stepwise_rollout as _stepwise
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,22 +35,6 @@ def _env_config(history):
     class E(EnvConfig):
         HISTORY_SIZE = history
     return E
-
-
-def _policy(torch, D, H=64, layers=2, act="tanh", A=3, seed=0, device="cuda:0"):
-    from ship_sim_gym_amd.policy import NativePolicy
-    nn = torch.nn
-    g = torch.Generator().manual_seed(seed)
-    mods = [nn.Linear(D, H), nn.Tanh() if act == "tanh" else nn.ReLU()]
-    if layers == 2:
-        mods += [nn.Linear(H, H), nn.Tanh() if act == "tanh" else nn.ReLU()]
-    net = nn.Module()
-    net.body, net.pi, net.v = nn.Sequential(*mods), nn.Linear(H, A), nn.Linear(H, 1)
-    with torch.no_grad():
-        for p in net.parameters():
-            p.copy_(torch.rand(p.shape, generator=g) * 2 - 1).mul_(1.5 / p.shape[-1] ** 0.5)
-    net = net.to(device)
-    return net, NativePolicy.from_actor_critic(net, torch.full((D,), 600.0, dtype=torch.float64, device=device))
 
 
 def _torch_sample(torch, logits, u):
@@ -153,24 +139,6 @@ def test_philox_uniforms_are_the_documented_stream(torch_cuda):
             seen |= set(a0.tolist())
         assert seen == {0, 1, 2, 3}
         env.close()
-
-
-def _stepwise(env, pol, K, seed, step0, uniforms=None):
-    torch = __import__("torch")
-    rows = {k: [] for k in ("obs", "act", "logp", "val", "rew", "done", "flags")}
-    for k in range(K):
-        a, lp, v, x = env.policy_act(pol, seed=seed, step=step0 + k, uniforms=None if uniforms is None else uniforms[k])
-        rows["obs"].append(x); rows["act"].append(a); rows["logp"].append(lp); rows["val"].append(v)
-        _, r, d, f = env.step_tensor(a)
-        rows["rew"].append(r.clone()); rows["done"].append(d.clone()); rows["flags"].append(f.clone())
-    out = {k: torch.stack(v) for k, v in rows.items()}
-    out["last_val"] = env.policy_act(pol, seed=seed, step=step0 + K)[2]
-    return out
-
-
-def _assert_same(torch, a, b, what):
-    for k in ("obs", "act", "logp", "val", "rew", "done", "flags", "last_val"):
-        assert a[k].dtype == b[k].dtype and torch.equal(a[k], b[k]), (what, k)
 
 
 def test_fused_rollout_equals_stepwise_loop(torch_cuda):

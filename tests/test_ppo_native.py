@@ -104,3 +104,18 @@ def test_trainer_offers_native_update_only_with_native_mode():
             mod.train(envs=64, updates=1, mode=m, update="native", device="cpu")
     with pytest.raises(ValueError):
         mod.train(envs=64, updates=1, mode="native", update="adam", device="cpu")
+
+
+def test_update_chunks_are_torch_chunks():
+    """NativePPO.update's chunk count (its stats rows and its Adam step advance, epochs x chunks) is torch.chunk's, also where
+    torch.chunk makes fewer chunks than asked (n = 10 into 6 gives 5)."""
+    import torch
+    from ship_sim_gym_amd.ppo import chunk_split
+    for n in range(1, 301):
+        r = torch.arange(n)
+        for m in range(1, 41):
+            chunks = r.chunk(m)
+            chunk, n_chunks = chunk_split(n, m)
+            assert n_chunks == len(chunks) and chunk == len(chunks[0]), (n, m)
+            assert [len(c) for c in chunks] == [min(chunk, n - i * chunk) for i in range(n_chunks)], (n, m)
+    assert chunk_split(10, 6) == (2, 5)

@@ -7,6 +7,9 @@ import os
 import numpy as np
 import pytest
 
+from helpers import actor_critic_policy as _policy, check_per_tensor as _check_per_tensor, ppo_loss as _loss, torch_gae as _torch_gae, \
+    unpack as _unpack
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,41 +27,9 @@ def _vec(n):
     return ShipVecEnv(n, n_maps=64)
 
 
-def _policy(torch, D, H=64, layers=2, act="tanh", A=3, seed=0):
-    from ship_sim_gym_amd.policy import NativePolicy
-    nn = torch.nn
-    g = torch.Generator().manual_seed(seed)
-    mods = [nn.Linear(D, H), nn.Tanh() if act == "tanh" else nn.ReLU()]
-    if layers == 2:
-        mods += [nn.Linear(H, H), nn.Tanh() if act == "tanh" else nn.ReLU()]
-    net = nn.Module()
-    net.body, net.pi, net.v = nn.Sequential(*mods), nn.Linear(H, A), nn.Linear(H, 1)
-    with torch.no_grad():
-        for p in net.parameters():
-            p.copy_(torch.rand(p.shape, generator=g) * 2 - 1).mul_(1.5 / p.shape[-1] ** 0.5)
-    net = net.to("cuda:0")
-    return net, NativePolicy.from_actor_critic(net, torch.full((D,), 600.0, dtype=torch.float64, device="cuda:0"))
-
-
 def _rollout(torch, env, pol, K, seed=1):
     env.reset_tensor()
     return dict(env.rollout_policy(pol, K, seed=seed))
-
-
-def _torch_gae(torch, b, gamma=0.99, lam=0.95):
-    """train/ppo_torch.py's GAE loop, restated on the native rollout's buffers (rew / done as ppo_torch converts them)."""
-    rew, done, val = b["rew"].float(), b["done"].float(), b["val"]
-    K, n = rew.shape
-    adv = torch.zeros(n, device=rew.device)
-    advs, rets = [None] * K, [None] * K
-    nxt = b["last_val"]
-    for t in reversed(range(K)):
-        nonterm = 1.0 - done[t]
-        delta = rew[t] + gamma * nxt * nonterm - val[t]
-        adv = delta + gamma * lam * nonterm * adv
-        advs[t], rets[t] = adv, adv + val[t]
-        nxt = val[t]
-    return torch.stack(advs), torch.stack(rets)
 
 
 @pytest.mark.parametrize("n,K", [(1000, 16), (4097, 8), (512, 1)])
@@ -84,27 +55,6 @@ def test_gae_is_bitwise_the_trainers_loop(torch_cuda, n, K):
     env.close()
 
 
-def _unpack(p, offsets):
-    return {k: p[o: o + int(np.prod(s))].view(*s) for k, (o, s) in offsets.items()}
-
-
-def _loss(torch, p, offsets, L, act, x, a, logp_old, advn, ret, clip=0.2):
-    """ppo_torch's minibatch loss on packed parameters p (any dtype); returns (loss, pg, (v-ret)^2 mean, entropy mean, clip fraction)."""
-    t = _unpack(p, offsets)
-    f = torch.tanh if act == "tanh" else torch.relu
-    h = f(x @ t["W0"].T + t["b0"])
-    if L == 2:
-        h = f(h @ t["W1"].T + t["b1"])
-    logits, v = h @ t["Wpi"].T + t["bpi"], (h @ t["Wv"].T + t["bv"]).squeeze(-1)
-    dist = torch.distributions.Categorical(logits=logits)
-    ratio = torch.exp(dist.log_prob(a) - logp_old)
-    pg = -torch.min(ratio * advn, torch.clamp(ratio, 1 - clip, 1 + clip) * advn).mean()
-    vl = (v - ret).pow(2).mean()
-    ent = dist.entropy().mean()
-    cf = ((ratio - 1).abs() > clip).to(x.dtype).mean()
-    return pg + 0.5 * vl - 0.01 * ent, pg, vl, ent, cf
-
-
 def _ref_grad(torch, pol, b, idx, advn, dtype):
     x = b["obs"].reshape(-1, pol.obs_dim)[idx].to(dtype)
     a = b["act"].reshape(-1)[idx].long()
@@ -113,16 +63,6 @@ def _ref_grad(torch, pol, b, idx, advn, dtype):
     out = _loss(torch, p, pol.offsets, pol.n_hidden_layers, pol.activation, x, a, lo, an, rt)
     out[0].backward()
     return p.grad.detach(), [float(o.detach()) for o in out[1:]]
-
-
-def _check_per_tensor(torch, pol, mine, ref64, ref32, what):
-    for k, (o, s) in pol.offsets.items():
-        n = int(np.prod(s))
-        g64 = ref64[o: o + n].double()
-        e_mine = float((mine[o: o + n].double() - g64).abs().max())
-        e_t32 = float((ref32[o: o + n].double() - g64).abs().max())
-        bound = 4 * e_t32 + 1e-6 * float(g64.abs().max())
-        assert e_mine <= bound, (what, k, e_mine, e_t32, bound)
 
 
 def _batch_for(torch, H, L, act, A, n=4096, K=10, seed=0):
