@@ -65,10 +65,13 @@ typedef enum ssg_status {
 #define SSG_FLAG_DYN_MEMO_OFF      0x10u /* config 4, development / measurement aid: never look a cpSpaceStep up in the memo table
                                            (see SSG_F_DYN_MEMO_STATS): every queued env walks the full narrowphase / solver chain.
                                            Results are bit for bit the same either way. */
-#define SSG_FLAG_EXACT_LIDAR       0x8u /* lidar: intersect every hull plane with every beam exactly as
-                                           cpPolyShapeSegmentQuery does (one division per plane and beam) instead of
-                                           the default one-division-per-beam evaluation of the same predicate; the two
-                                           differ only for rays within rounding of a hull vertex.  Validation aid. */
+#define SSG_FLAG_EXACT_LIDAR       0x8u /* lidar: intersect every hull plane with every beam in cpPolyShapeSegmentQuery's
+                                           order of operations (one division per plane and beam, plain IEEE products and
+                                           sums, no fused multiply-add) instead of the default one-division-per-beam
+                                           evaluation of the same predicate.  Not bitwise the reference: the beam end comes
+                                           from the angle-sum identity (~1e-13 from cos / sin of the beam's angle).  The two
+                                           paths differ only for rays within rounding of a decision boundary of the query
+                                           (a hull vertex, an edge's end, an origin on a plane).  Validation aid. */
 
 /*
  * Map bank record: SSG_MAP_STRIDE doubles per map, built on the host by ssg_host_build_map().

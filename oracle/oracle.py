@@ -93,6 +93,7 @@ def lib():
         L.ora_circle_segment_query.argtypes = [V2, C.c_double, V2, V2, C.c_double, C.POINTER(SegInfo)]
         L.ora_world_set_ship.argtypes = [C.c_void_p, C.POINTER(Body)]
         L.ora_world_get_ship.argtypes = [C.c_void_p, C.POINTER(Body)]
+        L.ora_world_place_ship.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
         L.ora_world_space_step.argtypes = [C.c_void_p]
         L.ora_polys_collide.restype = C.c_int
         L.ora_polys_collide.argtypes = [C.POINTER(Poly), C.POINTER(Poly)]
@@ -200,6 +201,15 @@ class World:
         """Install bank hulls (for goal_x_range during goal generation) without goals."""
         return self.reset(left, right, np.zeros((self.cfg.n_goals, 2)))
 
+    def place_player(self, x, y, angle):
+        """The player at rest at pose (x, y, angle); see Batch.place_player."""
+        lib().ora_world_place_ship(self._p, float(x), float(y), float(angle))
+
+    def lidar_origin(self):
+        """LiDAR.query's origin for the current pose: position + half the shape's cached AABB extents (models.py:51-53)."""
+        pk = self.peek()
+        return pk["x"] + (pk["bb_r"] - pk["bb_l"]) / 2, pk["y"] + (pk["bb_t"] - pk["bb_b"]) / 2
+
     def goal_x_range(self, y):
         lo, hi = C.c_double(), C.c_double()
         ok = lib().ora_goal_x_range(self._p, float(y), C.byref(lo), C.byref(hi))
@@ -297,6 +307,11 @@ class Batch:
     def poke_traffic(self, i, k, x, y, angle=0.0, vx=0.0, vy=0.0, w=0.0):
         lib().ora_world_poke_traffic(lib().ora_world_at(self._p, int(i)), int(k),
                                      _dp(np.array([x, y, angle, vx, vy, w], dtype=np.float64)))
+
+    def place_player(self, i, x, y, angle):
+        """Put env i's player at rest at pose (x, y, angle) (rot = (cos, sin), shape planes and AABB refreshed), as a test writes
+        the SSG_F_X, F_Y, F_ANGLE columns and zeroes F_VX, F_VY, F_W."""
+        lib().ora_world_place_ship(lib().ora_world_at(self._p, int(i)), float(x), float(y), float(angle))
 
     def poke_player(self, i, x, y, vx=0.0, vy=0.0):
         """Move env i's player body (position, velocity; angle and spin kept) as a test writes the SSG_F_X.. columns."""

@@ -584,6 +584,19 @@ void ora_world_step(ora_world *w, int action, double *obs_out, double *reward, u
  * reference's own Python runs on the oracle's full cpSpaceStep (contact solver included) ---- */
 void ora_world_set_ship(ora_world *w, const ora_body *b) { w->ship = *b; }
 void ora_world_get_ship(const ora_world *w, ora_body *b) { *b = w->ship; }
+/* Put the player at rest at pose (x, y, a), as a caller that writes the SSG_F_X / F_Y / F_ANGLE columns (and zero velocities)
+ * of the HIP state does; the shape's world planes and AABB follow, which the next LiDAR.query takes its origin from (the HIP
+ * path rebuilds them from the pose every step) */
+void ora_world_place_ship(ora_world *w, double x, double y, double a)
+{
+    ora_body *b = &w->ship;
+    b->p = V(x, y);
+    b->v = V(0, 0);
+    b->a = a;
+    b->w = 0.0;
+    b->rot = V(cos(a), sin(a));
+    ora_poly_update(&w->ship_shape, b->p, b->rot);
+}
 /* ShipGame.update's `self.space.step(dt)` alone: cpSpaceStep with the begin-callbacks' effects (colliding, goal_reached, the
  * goal list), without the action, the lidar and the ShipEnv bookkeeping around it */
 void ora_world_space_step(ora_world *w)

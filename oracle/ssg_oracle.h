@@ -169,6 +169,7 @@ int ora_circle_segment_query(ora_v2 center, double r1, ora_v2 a, ora_v2 b, doubl
 /* hooks of the traffic-capable pymunk stand-in (tests/golden/shims): shadow world in, cpSpaceStep, everything back out */
 void ora_world_set_ship(ora_world *w, const ora_body *b);
 void ora_world_get_ship(const ora_world *w, ora_body *b);
+void ora_world_place_ship(ora_world *w, double x, double y, double a);
 void ora_world_space_step(ora_world *w);
 
 /* ---- world ---- */

@@ -331,7 +331,9 @@ constexpr unsigned long long kLidarMiss = ~0ull; // result key of a beam no hull
 // wavefronts.  A worker lane pulls the pose of the env it serves with ds_bpermute, rebuilds the beam and runs
 // cpShapeSegmentQuery(shape, a=(cx,cy), b=(ex,ey), r=0) against one hull:
 //   EXACT = true : cpPolyShapeSegmentQuery literally — every plane is intersected (one division per plane),
-//                  accepted when the crossing lies inside the edge's extent, later planes overwrite.
+//                  accepted when the crossing lies inside the edge's extent, later planes overwrite; plain IEEE
+//                  products and sums as Chipmunk's (seg_mad), no fused multiply-add.  Its beam end still comes from
+//                  beam_end's angle-sum identity, so it is not bitwise the reference's either.
 //   EXACT = false: the same predicate with one division per beam: among the planes the beam crosses front-to-back
 //                  within its length (d >= 0 and d <= den, i.e. 0 <= t <= 1) only the one with the largest t can
 //                  be the entry edge of a convex polygon, so only that plane gets the exact t = d/den, lerp and
@@ -343,6 +345,11 @@ constexpr unsigned long long kLidarMiss = ~0ull; // result key of a beam no hull
 // hull planes fetched ahead of their arithmetic, per loop trip: 4 from LDS; 8 when the record is gathered from L2 / HBM (every
 // trip is then a dependent ~1 k-cycle round trip on the lidar role's chain, and 99.4 % of the bank hulls have <= 8 planes)
 template <bool LDS_BANK> struct PlaneChunk { static constexpr int n = LDS_BANK ? 4 : 8; };
+
+// a * b + c in the lidar's segment query: one fused multiply-add on the default path (obs_fma), the plain IEEE product and sum
+// Chipmunk's cpvdot / cpvcross / cpvlerp evaluate on the EXACT path
+template <bool EXACT>
+__device__ __forceinline__ double seg_mad(double a, double b, double c) { return EXACT ? a * b + c : obs_fma(a, b, c); }
 
 template <bool LDS_BANK, bool EXACT>
 __device__ __forceinline__ void lidar_pass(const DevCfg &c, const int n_items, const unsigned short *queue,
@@ -392,8 +399,8 @@ __device__ __forceinline__ void lidar_pass(const DevCfg &c, const int n_items, c
                     const int jp = (j == 0) ? cnt - 1 : j - 1;
                     const int qp = pb + SSG_PLANE_DOUBLES * ((jp >= 0 && jp < SSG_MAX_HULL) ? jp : 0);
                     const double ux = bank_at<LDS_BANK>(c, qp + 0), uy = bank_at<LDS_BANK>(c, qp + 1);
-                    pdtmin[u] = obs_fma(pnx[u], uy, -(pny[u] * ux));
-                    pdtmax[u] = obs_fma(pnx[u], pv0y[u], -(pny[u] * pv0x[u]));
+                    pdtmin[u] = seg_mad<EXACT>(pnx[u], uy, -(pny[u] * ux));
+                    pdtmax[u] = seg_mad<EXACT>(pnx[u], pv0y[u], -(pny[u] * pv0x[u]));
                 }
             }
 #pragma unroll
@@ -401,7 +408,7 @@ __device__ __forceinline__ void lidar_pass(const DevCfg &c, const int n_items, c
                 const int j = j0 + u;
                 const bool valid = act & (j < cnt);
                 const double nx = pnx[u], ny = pny[u], v0n = pv0n[u];
-                const double an = obs_fma(wcx, nx, wcy * ny);
+                const double an = seg_mad<EXACT>(wcx, nx, wcy * ny);
                 const double d = an - v0n;
                 if (EXACT) {
                     outside = outside | (valid & ((nx * (wcx - pv0x[u]) + ny * (wcy - pv0y[u])) > 0.0));
@@ -413,13 +420,13 @@ __device__ __forceinline__ void lidar_pass(const DevCfg &c, const int n_items, c
                     maybe = maybe | (valid & !(d < -kSignEps));
                 }
                 const bool front = valid & !(d < 0.0);
-                const double bn = obs_fma(ex, nx, ey * ny);
+                const double bn = seg_mad<EXACT>(ex, nx, ey * ny);
                 const double den = dmax(an - bn, DBL_MIN);
                 if (EXACT) {
                     const double t = d / den;
                     const double omt = 1.0 - t;
-                    const double qx = obs_fma(ex, t, wcx * omt), qy = obs_fma(ey, t, wcy * omt); // cpvlerp(a,b,t)
-                    const double dtv = obs_fma(nx, qy, -(ny * qx));                  // cpvcross(n, point)
+                    const double qx = seg_mad<EXACT>(ex, t, wcx * omt), qy = seg_mad<EXACT>(ey, t, wcy * omt); // cpvlerp(a,b,t)
+                    const double dtv = seg_mad<EXACT>(nx, qy, -(ny * qx));           // cpvcross(n, point)
                     const bool acc = front & !((t < 0.0) | (1.0 < t)) & (pdtmin[u] <= dtv) & (dtv <= pdtmax[u]);
                     ok = ok | acc;
                     ptx = acc ? qx : ptx;
@@ -472,7 +479,7 @@ __device__ __forceinline__ void lidar_pass(const DevCfg &c, const int n_items, c
         if constexpr (EXACT) {
             const double px = outside ? ptx : ex, py = outside ? pty : ey;
             const double dx = px - wcx, dy = py - wcy;
-            dist = sqrt(obs_fma(dx, dx, dy * dy)); // Vec2d.get_distance, literally
+            dist = sqrt(dx * dx + dy * dy); // Vec2d.get_distance, literally
         } else {
             // |cpvlerp(a, b, t) - a| = t |b - a| = t x the beam's length (the far end itself when the origin is inside the hull):
             // the reading without the point difference and the square root (~20 wave-instructions per pass); it differs from the
