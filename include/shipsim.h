@@ -172,6 +172,17 @@ typedef enum ssg_field {
                            player pushes nothing) — so the first env to step a state stores (state -> next state) in a table
                            inside the state blob and later envs in that state copy the result after comparing the COMPLETE
                            state word for word: a memoised step writes exactly the bits a computed one writes. */
+    /* The cached arbiters of the config-4 space (cpSpace.cachedArbiters), n_ships == 4 only, inspection only.  One row per
+       PAIR ID p, the shape pair in the canonical collide order of the dyn kernel (k, j: traffic ships 0..2, s: bank hull 0/1,
+       g, h: goals 0..5):  p = 2k + s (ship k, bank s) [0, 6) | 6 + j + k - 1 (ships j < k) [6, 9) | 9 + 2g + s (goal g, bank s)
+       [9, 21) | 21 + 3g + k (goal g, ship k) [21, 39) | 39 + g(g - 1)/2 + h (goals h < g) [39, 54).  The solver's list holds
+       every pair that has contacts in a step, in that collide order (at most 54).  A row is meaningful only while bit p of
+       the live mask is set.  The arbiters of a goal the player reached leave with it at the env's next full step. */
+    SSG_F_DYN_LIVE,     /* u64: bit p = pair p has a cached arbiter */
+    SSG_F_DYN_ARB_META, /* u32 x 54: pair p = column p: state (1 first contact, 2 normal, 4 cached) | age << 3 (steps since it was
+                           last touched, < 3) | contact count << 5 */
+    SSG_F_DYN_ARB_HASH, /* u32 x 9 (the polygon pairs p < 9): contact hash 0 | contact hash 1 << 16 (0 when one contact) */
+    SSG_F_DYN_ARB_IMPULSE, /* f64 x 4*54: pair p = columns 4p..4p+3: jnAcc of contact 0, 1, jtAcc of contact 0, 1 */
     SSG_F_COUNT
 } ssg_field;
 

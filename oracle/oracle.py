@@ -15,6 +15,8 @@ _LIB_PATH = os.path.join(_HERE, "_build", "libssg_oracle.so")
 MAX_VERTS, MAX_GOALS, MAX_BEAMS, MAX_HISTORY = 16, 8, 32, 8
 PEEK_LEN = 19
 PEEK_DYN_LEN = 6 * 3 + 4 * 5 + 2
+N_SLOTS, CENSUS_LIST, CENSUS_ARB = 11, 64, 11                      # ssg_oracle.h ORA_N_SLOTS / ORA_CENSUS_*
+CENSUS_LEN = 8 + 4 * CENSUS_LIST + CENSUS_ARB * N_SLOTS * (N_SLOTS - 1) // 2
 PEEK_FIELDS = ("x", "y", "vx", "vy", "angle", "w", "rudder", "step_count", "n_goals_alive", "colliding",
                "goal_reached", "map_id", "cumulative_reward", "alive_mask", "episodes", "bb_l", "bb_b", "bb_r",
                "bb_t")
@@ -109,6 +111,8 @@ def lib():
         L.ora_world_peek.argtypes = [C.c_void_p, dp]
         L.ora_world_peek_dyn.argtypes = [C.c_void_p, dp]
         L.ora_world_poke_traffic.argtypes = [C.c_void_p, C.c_int, dp]
+        L.ora_world_poke_goal.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double]
+        L.ora_world_census.argtypes = [C.c_void_p, dp]
         L.ora_collide_poly_poly.restype = C.c_int
         L.ora_collide_poly_poly.argtypes = [C.POINTER(Poly), C.POINTER(Poly), C.c_int, C.c_int, C.POINTER(V2),
                                             C.POINTER(V2), C.POINTER(V2), C.POINTER(C.c_uint32), dp]
@@ -233,6 +237,31 @@ class World:
     def poke_traffic(self, k, x, y, angle=0.0, vx=0.0, vy=0.0, w=0.0):
         lib().ora_world_poke_traffic(self._p, int(k), _dp(np.array([x, y, angle, vx, vy, w], dtype=np.float64)))
 
+    def poke_goal(self, g, x, y, vx=0.0, vy=0.0):
+        lib().ora_world_poke_goal(self._p, int(g), float(x), float(y), float(vx), float(vy))
+
+    def census(self):
+        return _census(self._p)
+
+
+def _census(p):
+    """Arbiter census after a step (ora_world_census): {'list': [(slot a, slot b, count, state)] in solver order, 'arbs':
+    {(i, j): (state, age, count, a, b, hashes, jnAcc, jtAcc)} for every slot pair i < j in cachedArbiters (state != NONE),
+    'epa_hull', 'gjk_cap', 'epa_cap', 'c2c_zero'}.  Slots: 0, 1 banks, 2..6 goals, 7 the player, 8..10 traffic."""
+    o = np.empty(CENSUS_LEN)
+    lib().ora_world_census(p, _dp(o))
+    n = int(o[0])
+    lst = [tuple(int(v) for v in o[8 + 4 * i: 12 + 4 * i]) for i in range(n)]
+    arbs, r = {}, 8 + 4 * CENSUS_LIST
+    for i in range(N_SLOTS):
+        for j in range(i + 1, N_SLOTS):
+            v = o[r: r + CENSUS_ARB]
+            r += CENSUS_ARB
+            if int(v[0]) != 0:
+                arbs[(i, j)] = {"state": int(v[0]), "age": int(v[1]), "count": int(v[2]), "a": int(v[3]), "b": int(v[4]),
+                                "hash": (int(v[5]), int(v[6])), "jn": (v[7], v[8]), "jt": (v[9], v[10])}
+    return {"list": lst, "arbs": arbs, "epa_hull": int(o[1]), "gjk_cap": int(o[2]), "epa_cap": int(o[3]), "c2c_zero": int(o[4])}
+
 
 def _peek_dyn(p):
     """config 4 bodies: {'traffic': [3][x,y,angle,vx,vy,w], 'goals': [5][x,y,vx,vy], 'in_space': mask, 'arbiters': n}"""
@@ -307,6 +336,14 @@ class Batch:
     def poke_traffic(self, i, k, x, y, angle=0.0, vx=0.0, vy=0.0, w=0.0):
         lib().ora_world_poke_traffic(lib().ora_world_at(self._p, int(i)), int(k),
                                      _dp(np.array([x, y, angle, vx, vy, w], dtype=np.float64)))
+
+    def poke_goal(self, i, g, x, y, vx=0.0, vy=0.0):
+        """Move env i's goal body g (a goal still in the space) as a test writes its 8 F_GOAL_BODIES columns: x, y, vx, vy,
+        then v_bias, w and w_bias zero.  The player sees the new position from the next step on, as on the HIP path."""
+        lib().ora_world_poke_goal(lib().ora_world_at(self._p, int(i)), int(g), float(x), float(y), float(vx), float(vy))
+
+    def census(self, i):
+        return _census(lib().ora_world_at(self._p, int(i)))
 
     def place_player(self, i, x, y, angle):
         """Put env i's player at rest at pose (x, y, angle) (rot = (cos, sin), shape planes and AABB refreshed), as a test writes

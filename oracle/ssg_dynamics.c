@@ -42,6 +42,10 @@
 
 static double collision_bias(void) { return pow(1.0 - 0.1, 60.0); } /* cpSpace default collisionBias */
 
+/* inspection only (ora_world_census): what the narrowphase of the current step met, per thread (the batch steps worlds on
+ * OpenMP threads); reset and read by ora_dyn_collide_solve.  Nothing reads it back into the arithmetic. */
+static _Thread_local struct { int epa_hull, gjk_cap, epa_cap, c2c_zero; } census_acc;
+
 static const double SHIP_TEMPLATE[5][2] = {{0, 0}, {0, 10}, {5, 15}, {10, 10}, {10, 0}}; /* models.py:6 */
 /* add_default_traffic game.py:284-286: (x, y, width, height) */
 static const double TRAFFIC[ORA_N_TRAFFIC][4] = {{100, 200, 1, 1}, {300, 200, 1.5, 2}, {400, 350, 1, 3}};
@@ -156,6 +160,7 @@ static closest_pts epa(const shape_ref *s1, const shape_ref *s2, mink_pt v0, min
     mink_pt hull[MAX_EPA_ITERATIONS + 4], hull2[MAX_EPA_ITERATIONS + 4];
     int count = 3;
     hull[0] = v0; hull[1] = v1; hull[2] = v2;
+    if (census_acc.epa_hull < count) census_acc.epa_hull = count;
     for (int iteration = 1;; iteration++) {
         int mini = 0;
         double min_dist = INFINITY;
@@ -178,7 +183,9 @@ static closest_pts epa(const shape_ref *s1, const shape_ref *s2, mink_pt v0, min
             }
             memcpy(hull, hull2, sizeof(mink_pt) * (size_t)count2);
             count = count2;
+            if (census_acc.epa_hull < count) census_acc.epa_hull = count;
         } else {
+            if (area2x > 0.0) census_acc.epa_cap++;
             return closest_new(e0, e1);
         }
     }
@@ -209,7 +216,7 @@ static closest_pts gjk(const shape_ref *s1, const shape_ref *s2, uint32_t *id)
     closest_pts out;
     int iteration = 1;
     for (;;) {
-        if (iteration > MAX_GJK_ITERATIONS) { out = closest_new(v0, v1); break; }
+        if (iteration > MAX_GJK_ITERATIONS) { census_acc.gjk_cap++; out = closest_new(v0, v1); break; }
         ora_v2 delta = vsub(v1.ab, v0.ab);
         if (vcross(delta, vadd(v0.ab, v1.ab)) > 0.0) {
             mink_pt tmp = v0; v0 = v1; v1 = tmp; /* origin is behind the axis: flip, same iteration */
@@ -318,6 +325,7 @@ static void circle_to_circle(const shape_ref *c1, const shape_ref *c2, collision
     double distsq = vlengthsq(delta);
     if (distsq < mindist * mindist) {
         double dist = sqrt(distsq);
+        if (dist == 0.0) census_acc.c2c_zero++;
         ora_v2 n = info->n = (dist ? vmult(delta, 1.0 / dist) : V(1.0, 0.0));
         info->p1[0] = vadd(c1->tc, vmult(n, c1->r));
         info->p2[0] = vadd(c2->tc, vmult(n, -c2->r));
@@ -619,6 +627,7 @@ void ora_dyn_collide_solve(ora_world *w, int reached_mask)
     /* (3) collide — ORDER assumption (file header) */
     ora_arbiter *list[64];
     int n_list = 0;
+    memset(&census_acc, 0, sizeof(census_acc));
     for (int g = 0; g < c->n_goals; g++) {
         if (!(d->goal_in_space >> g & 1)) continue;
         int sg = ORA_SLOT_GOAL0 + g;
@@ -639,6 +648,9 @@ void ora_dyn_collide_solve(ora_world *w, int reached_mask)
         for (int j = 0; j < k; j++)
             if (collide_pair(w, ORA_SLOT_TRAFFIC0 + j, st)) list[n_list++] = arb_at(w, ORA_SLOT_TRAFFIC0 + j, st);
     }
+    for (int i = 0; i < n_list; i++) { d->last_list[i][0] = list[i]->a; d->last_list[i][1] = list[i]->b; }
+    d->last_epa_hull = census_acc.epa_hull; d->last_gjk_cap = census_acc.gjk_cap;
+    d->last_epa_cap = census_acc.epa_cap; d->last_c2c_zero = census_acc.c2c_zero;
     /* cpSpaceArbiterSetFilter: separated arbiters become "cached", and are dropped after 3 stamps */
     for (int i = 0; i < ORA_N_SLOTS; i++)
         for (int j = i + 1; j < ORA_N_SLOTS; j++) {
@@ -699,4 +711,35 @@ void ora_world_poke_traffic(ora_world *w, int k, const double *v6)
     b->v = V(v6[3], v6[4]); b->w = v6[5];
     b->v_bias = V(0, 0); b->w_bias = 0.0;
     ora_poly_update(&w->dyn.tshape[k], b->p, b->rot);
+}
+
+/* test hook: move goal g's body.  A circle's shape cache is its body position, read where it is collided; the player's view of
+ * the goals (goal_p) is refreshed from the bodies by the next ora_dyn_integrate, before the player's goal tests (space_step). */
+void ora_world_poke_goal(ora_world *w, int g, double x, double y, double vx, double vy)
+{
+    ora_body *b = &w->dyn.gbody[g];
+    b->p = V(x, y); b->v = V(vx, vy);
+    b->v_bias = V(0, 0); b->w = 0.0; b->w_bias = 0.0;
+}
+
+void ora_world_census(const ora_world *w, double *o)
+{
+    const ora_dyn *d = &w->dyn;
+    memset(o, 0, sizeof(double) * ORA_CENSUS_LEN);
+    o[0] = d->last_arbiters; o[1] = d->last_epa_hull; o[2] = d->last_gjk_cap; o[3] = d->last_epa_cap; o[4] = d->last_c2c_zero;
+    for (int i = 0; i < d->last_arbiters && i < ORA_CENSUS_LIST; i++) {
+        const int a = d->last_list[i][0], b = d->last_list[i][1];
+        const ora_arbiter *arb = a < b ? &d->arb[a][b] : &d->arb[b][a];
+        double *r = o + 8 + 4 * i;
+        r[0] = a; r[1] = b; r[2] = arb->count; r[3] = arb->state;
+    }
+    double *r = o + 8 + 4 * ORA_CENSUS_LIST;
+    for (int i = 0; i < ORA_N_SLOTS; i++)
+        for (int j = i + 1; j < ORA_N_SLOTS; j++, r += ORA_CENSUS_ARB) {
+            const ora_arbiter *arb = &d->arb[i][j];
+            r[0] = arb->state; r[1] = d->stamp - arb->stamp; r[2] = arb->count; r[3] = arb->a; r[4] = arb->b;
+            for (int k = 0; k < 2; k++) {
+                r[5 + k] = arb->con[k].hash; r[7 + k] = arb->con[k].jnAcc; r[9 + k] = arb->con[k].jtAcc;
+            }
+        }
 }

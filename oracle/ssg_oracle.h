@@ -116,6 +116,9 @@ typedef struct {
     ora_body gbody[ORA_MAX_GOALS];      /* goal circle bodies, by original goal index */
     int goal_in_space;                  /* bit g: goal g's body/shape still in the space */
     int last_arbiters;                  /* solver list length of the last step (inspection) */
+    int last_list[64][2];               /* ... and its arbiters in list order: shape slots a, b in cpCollide's order (inspection) */
+    int last_epa_hull, last_gjk_cap, last_epa_cap, last_c2c_zero; /* last step: largest EPA hull, GJK / EPA queries that hit
+                                                                     their iteration cap, CircleToCircle calls with dist == 0 */
     ora_body static_body;               /* the banks' body: all zero (cpBodyNewStatic at the origin) */
     ora_arbiter arb[ORA_N_SLOTS][ORA_N_SLOTS]; /* cachedArbiters keyed by (lower slot, higher slot) */
     uint32_t pair_id[ORA_N_SLOTS][ORA_N_SLOTS]; /* ORA_VAR_GJK_WARM only: cpCollisionID of the broadphase pair */
@@ -193,6 +196,17 @@ ora_world *ora_world_at(ora_world *ws, int i);
 void ora_world_peek_dyn(const ora_world *w, double *out);
 /* ---- config 4 internals (ssg_dynamics.c), called by ora_world_reset / space_step ---- */
 void ora_world_poke_traffic(ora_world *w, int k, const double *v6 /* x,y,angle,vx,vy,w */);
+/* test hook: goal g's body at (x, y) with velocity (vx, vy), v_bias / w / w_bias zeroed (mirrors writing its 8 SSG_F_GOAL_BODIES
+ * columns); only for a goal still in the space */
+void ora_world_poke_goal(ora_world *w, int g, double x, double y, double vx, double vy);
+/* arbiter census after a step (inspection only): [0] solver list length, [1] largest EPA hull, [2] GJK cap hits, [3] EPA cap
+ * hits, [4] CircleToCircle calls with dist == 0, [5..7] 0; then ORA_CENSUS_LIST entries (slot a, slot b, contact count, state)
+ * in list order; then one record of ORA_CENSUS_ARB values per slot pair i < j (row-major over i, j): state, age (stamp
+ * difference), count, slot a, slot b, hash[2], jnAcc[2], jtAcc[2] */
+#define ORA_CENSUS_LIST 64
+#define ORA_CENSUS_ARB 11
+#define ORA_CENSUS_LEN (8 + 4 * ORA_CENSUS_LIST + ORA_CENSUS_ARB * ORA_N_SLOTS * (ORA_N_SLOTS - 1) / 2)
+void ora_world_census(const ora_world *w, double *out);
 void ora_dyn_reset(ora_world *w);
 void ora_dyn_integrate(ora_world *w);
 void ora_dyn_collide_solve(ora_world *w, int reached_mask);

@@ -18,7 +18,9 @@ FLAG_AUTO_RESET, FLAG_FIX_COLLISION_REWARD, FLAG_BANK_IN_GLOBAL, FLAG_EXACT_LIDA
 EV_COLLIDING, EV_GOAL_REACHED, EV_OUT_OF_BOUNDS, EV_MAX_STEPS, EV_NO_GOALS_LEFT = 0x1, 0x2, 0x4, 0x8, 0x10
 POLICY_MAX_HIDDEN, POLICY_TANH, POLICY_RELU = 128, 0, 1
 (F_X, F_Y, F_VX, F_VY, F_ANGLE, F_W, F_CUM_REWARD, F_LIDAR, F_RUDDER, F_STEP_COUNT, F_MAP_ID, F_GOAL_MASK,
- F_STATS, F_TRAFFIC, F_GOAL_BODIES, F_DYN_FLAGS, F_EPISODES, F_DYN_MEMO_STATS) = range(18)
+ F_STATS, F_TRAFFIC, F_GOAL_BODIES, F_DYN_FLAGS, F_EPISODES, F_DYN_MEMO_STATS,
+ F_DYN_LIVE, F_DYN_ARB_META, F_DYN_ARB_HASH, F_DYN_ARB_IMPULSE) = range(22)
+DYN_PAIRS, DYN_POLY_PAIRS = 54, 9  # arbiter rows of F_DYN_ARB_* (pair ids: include/shipsim.h)
 
 # every symbol include/shipsim.h declares (checked by tests/test_abi.py against the header text)
 EXPORTS = (

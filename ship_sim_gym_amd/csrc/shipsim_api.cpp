@@ -622,6 +622,12 @@ int ssg_state_field(const ssg_handle *h, int field, size_t *offset, int *elem_si
         off = h->off_dyn_memo_stats; es = 8; nc = ssg::kMemoStatSlots * ssg::kMemoStatWords;
         *offset = off; *elem_size = es; *n_columns = nc; *column_stride_bytes = 8;
         return SSG_OK;
+    } else if (field == SSG_F_DYN_LIVE || field == SSG_F_DYN_ARB_META || field == SSG_F_DYN_ARB_HASH || field == SSG_F_DYN_ARB_IMPULSE) {
+        if (h->cfg.n_ships <= 1) return SSG_ERR_BAD_ARG;
+        if (field == SSG_F_DYN_LIVE) { off = h->off_dyn_live; es = 8; nc = 1; }
+        else if (field == SSG_F_DYN_ARB_META) { off = h->off_dyn_u32 + (size_t)ssg::DU_META * np * 4; es = 4; nc = ssg::kDynPairs; }
+        else if (field == SSG_F_DYN_ARB_HASH) { off = h->off_dyn_u32 + (size_t)ssg::DU_HASH * np * 4; es = 4; nc = ssg::kPolyPairs; }
+        else { off = h->off_dyn_f64 + (size_t)ssg::DC_ARB * np * 8; es = 8; nc = 4 * ssg::kDynPairs; }
     } else if (field == SSG_F_STATS) {
         // kStatsSlots rows of 4 int64 counters; sum over rows: [0] sum_return*100 [1] sum_length [2] episodes [3] goals
         off = h->off_stats; es = 8; nc = 4 * ssg::kStatsSlots;

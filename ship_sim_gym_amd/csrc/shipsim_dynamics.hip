@@ -67,7 +67,7 @@ constexpr int kIter = 10;          // cpSpace iterations
 constexpr int kPersist = 3;        // collisionPersistence
 constexpr int kMaxGjk = 30, kMaxEpa = 30;
 constexpr int kLdsArb = 2;         // arbiter records per env held in LDS; further ones (rare: 98.8 % of the queued envs have <= 2) go to scratch
-constexpr int kMaxActive = 8;      // arbiters on one env's solver list
+constexpr int kMaxActive = kDynPairs; // arbiters on one env's solver list: every colliding pair, as cpSpaceStep solves them all
 enum { ST_NONE = 0, ST_FIRST = 1, ST_NORMAL = 2, ST_IGNORE = 3, ST_CACHED = 4 };
 
 // ---- per-lane LDS columns ----------------------------------------------------------------------------------
@@ -849,7 +849,7 @@ __global__ __launch_bounds__(64) void dyn_step_kernel(const DevCfg c, const DynC
     // L2 / HBM round trip in the middle of the collide phase — 8 k cycles of a wave's chain with two arbiters.
     constexpr int kPre = 4;
     static_assert(kPre == kMemoArbIn, "the memo key holds exactly the cached arbiters that are prefetched here");
-    static_assert(kMaxActive <= kMemoArbOut, "the memo value has one slot per arbiter the solver's list can hold");
+    static_assert(kMemoArbOut < kMaxActive, "a solver list longer than the memo value's kMemoArbOut slots is computed, never stored");
     int ppid[kPre];
     unsigned pmeta[kPre], phh[kPre];
     double pacc[kPre][4];
@@ -1833,7 +1833,7 @@ __global__ __launch_bounds__(64) void dyn_step_kernel(const DevCfg c, const DynC
     bool memo_ins = false;
     if constexpr (MEMO) {
         asm volatile("" : "+v"(memo_old)); // (first use of the CAS's answer: not before this point)
-        memo_ins = memo_try & (memo_old == 0ull) & (memo_n_aged <= kMemoAged); // (a claimed entry that is not filled stays unusable: rare)
+        memo_ins = memo_try & (memo_old == 0ull) & (memo_n_aged <= kMemoAged) & (n_act <= kMemoArbOut); // (a claimed entry that is not filled stays unusable: rare)
         if (memo_ins) {
             key_visit([&](int i, u64 w0, u64 w1) { memo_ent[ME_KEY + i] = w0; memo_ent[ME_KEY + i + 1] = w1; }, memo_incl, memo_n_live);
 #pragma unroll

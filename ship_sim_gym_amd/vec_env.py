@@ -391,6 +391,8 @@ class ShipVecEnv(*_BASES):
         N.check(N.lib().ssg_state_field(self._h, fid, C.byref(off), C.byref(es), C.byref(nc), C.byref(stride)), self._h,
                 "ssg_state_field")
         dt = {8: torch.float64, 4: torch.int32, 1: torch.uint8}[es.value]
+        if fid == N.F_DYN_LIVE:
+            dt = torch.int64                  # (a 64-bit mask)
         if fid == N.F_STATS:
             return self.state[off.value: off.value + 8 * nc.value].view(torch.int64).view(-1, 4)
         if fid == N.F_DYN_MEMO_STATS:

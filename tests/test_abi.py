@@ -236,6 +236,19 @@ def test_create_limits_and_config4_blob_layout(native):
     assert L.ssg_state_field(h4, native.F_DYN_MEMO_STATS, C.byref(off), C.byref(es), C.byref(nc), C.byref(st)) == 0
     assert es.value == 8 and nc.value == 256 * 16 and off.value % 256 == 0 and off.value + 8 * nc.value < n4.value
     assert L.ssg_state_field(h1, native.F_DYN_MEMO_STATS, C.byref(off), C.byref(es), C.byref(nc), C.byref(st)) < 0   # 1-ship handles have none
+    # the cached-arbiter view: live mask, 54 meta rows, 9 hash rows, 4 x 54 impulse rows, each inside the blob, config 4 only
+    np_ = (1024 + 255) // 256 * 256
+    spans = []
+    for fid, want_es, want_nc in ((native.F_DYN_LIVE, 8, 1), (native.F_DYN_ARB_META, 4, native.DYN_PAIRS),
+                                  (native.F_DYN_ARB_HASH, 4, native.DYN_POLY_PAIRS), (native.F_DYN_ARB_IMPULSE, 8, 4 * native.DYN_PAIRS)):
+        assert L.ssg_state_field(h4, fid, C.byref(off), C.byref(es), C.byref(nc), C.byref(st)) == 0, fid
+        assert (es.value, nc.value) == (want_es, want_nc), fid
+        assert st.value >= np_ * es.value and off.value + nc.value * st.value <= n4.value, fid
+        spans.append((off.value, off.value + nc.value * st.value))
+        assert L.ssg_state_field(h1, fid, C.byref(off), C.byref(es), C.byref(nc), C.byref(st)) < 0, fid
+    spans.sort()
+    assert all(a1 <= b0 for (_, a1), (b0, _) in zip(spans, spans[1:])), spans          # four disjoint regions
+    assert L.ssg_state_field(h4, native.F_DYN_ARB_IMPULSE + 1, C.byref(off), C.byref(es), C.byref(nc), C.byref(st)) < 0
     a, b = C.c_uint64(7), C.c_uint64(7)
     assert L.ssg_debug_dyn_counters(h4, C.byref(a), C.byref(b)) == 0 and (a.value, b.value) == (0, 0)
     L.ssg_destroy(h1); L.ssg_destroy(h4)

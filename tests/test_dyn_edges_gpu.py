@@ -1,0 +1,184 @@
+"""Config 4's full cpSpaceStep (dyn_step_kernel) at its edges, against the oracle, on all four kernel instantiations.
+
+One handle holds every scene of tests/dyn_scenes.py (piles of 0 .. 44 arbiters, signed gaps of every pair type, deep and
+coincident shapes, ties, arbiter ageing and warm starts, goal removal, memo twins), one per env.  The scenes' bodies are written
+through field() (and into the oracle worlds), then every env steps K times with auto-reset.  Per step: reward, done and the
+event flags bit-exact; observations within 1e-9; traffic and goal bodies within 1e-8; the cached-arbiter set with each arbiter's
+state, age, contact count and hashes exact, its accumulated impulses within 1e-8 relative.  The four layouts (a bank of <= 64
+records and one of > 64, memo on and off) give identical bits for every env up to its first done.
+"""
+import collections
+
+import numpy as np
+import pytest
+
+import dyn_scenes as DS
+
+pytestmark = pytest.mark.gpu
+
+K = 40
+LAYOUTS = ((len(DS.RECORDS), True), (len(DS.RECORDS), False), (72, True), (72, False))
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    import torch
+    assert torch.cuda.is_available(), "gpu tests need a HIP device"
+    return torch
+
+
+def _fingerprint(parts, mult):
+    """[n] u64 per env: the bits of every column in `parts` ([n, m] arrays), mixed (wrapping integer dot product)."""
+    bits = np.concatenate([np.ascontiguousarray(p).reshape(len(p), -1).view(np.uint64) if p.dtype.itemsize == 8 else
+                           p.reshape(len(p), -1).astype(np.uint64) for p in parts], axis=1)
+    return bits @ mult[:bits.shape[1]]
+
+
+def _gpu_run(torch, N, O, scenes, n_records, memo, ref):
+    from ship_sim_gym_amd import worldgen
+    from ship_sim_gym_amd.vec_env import ShipVecEnv
+    polys, goals = DS.bank_arrays(n_records)
+    bank = np.stack([worldgen.build_record(p[0], p[1], g, DS.PLAYER) for p, g in zip(polys, goals)])
+    n = len(scenes)
+    vec = ShipVecEnv(n, bank=bank, n_ships=4, dyn_memo=memo, auto_reset=True)
+    dev = vec.device
+    obs0 = vec.reset_tensor(map_ids=torch.tensor([s.rec for s in scenes], dtype=torch.int32, device=dev)).cpu().numpy()
+    np.testing.assert_array_equal(obs0, ref["obs0"])
+    act = torch.full((n,), DS.ACTION, dtype=torch.int32, device=dev)
+    T, G = vec.field(N.F_TRAFFIC), vec.field(N.F_GOAL_BODIES)
+    mult = np.random.RandomState(5).randint(1, 2 ** 62, size=4096, dtype=np.int64).astype(np.uint64) | np.uint64(1)
+    out = {"fp": [], "bad": [], "hits": [], "checked": 0}
+    for k in range(K):
+        poked = ref["poked"][k]
+        if poked.any():
+            idx = np.nonzero(poked)[0]
+            t = T.cpu().numpy().copy(); g = G.cpu().numpy().copy()
+            gm = vec.field(N.F_GOAL_MASK).cpu().numpy()
+            for e in idx:
+                s = scenes[e]
+                ships, gls = [(sh, go) for st, sh, go in s.pokes if st == k][0]
+                for j in range(3):
+                    t[9 * j: 9 * j + 6, e] = ships[j]; t[9 * j + 6: 9 * j + 9, e] = 0.0
+                for j in range(5):
+                    if gm[e] >> j & 1:
+                        g[8 * j: 8 * j + 4, e] = gls[j]; g[8 * j + 4: 8 * j + 8, e] = 0.0
+            T.copy_(torch.from_numpy(t).to(dev)); G.copy_(torch.from_numpy(g).to(dev))
+            # (masked: only the poked envs' columns changed, and the memo keeps its entries — an unmasked wake starts a new
+            # generation of the table, as for a blob that may have been restored)
+            vec.wake_dynamics(torch.from_numpy(poked.astype(np.uint8)).to(dev))
+        h0 = int(vec.field(N.F_DYN_MEMO_STATS)[:, 0].sum()) if memo else 0
+        o, r, d, fl = [x.cpu().numpy().copy() for x in vec.step_tensor(act)]
+        out["hits"].append((int(vec.field(N.F_DYN_MEMO_STATS)[:, 0].sum()) - h0) if memo else 0)
+        t = vec.field(N.F_TRAFFIC).cpu().numpy().T.copy()                       # [n, 27]
+        g = vec.field(N.F_GOAL_BODIES).cpu().numpy().T.copy()                   # [n, 48]
+        gm = vec.field(N.F_GOAL_MASK).cpu().numpy()
+        gone = DS.goal_pair_mask(gm)
+        live = vec.field(N.F_DYN_LIVE).cpu().numpy().view(np.uint64) & ~gone
+        meta = vec.field(N.F_DYN_ARB_META).cpu().numpy().T.view(np.uint32).copy()
+        hh = vec.field(N.F_DYN_ARB_HASH).cpu().numpy().T.view(np.uint32).copy()
+        acc = vec.field(N.F_DYN_ARB_IMPULSE).cpu().numpy().T.reshape(n, 54, 4).copy()
+        on = ((live[:, None] >> np.arange(54, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
+        meta[~on] = 0; hh[~on[:, :9]] = 0; acc[~on] = 0.0
+        for j in range(5):
+            g[(gm >> j & 1) == 0, 8 * j: 8 * j + 8] = 0.0
+        out["fp"].append(_fingerprint([o, r[:, None], d[:, None].astype(np.float64), fl.reshape(n, -1).astype(np.float64), t, g,
+                                       live[:, None], meta, hh, acc], mult))
+        # ---- against the oracle
+        where = "n_records=%d memo=%d step %d" % (n_records, memo, k)
+        rd = ref["done"][k]
+        np.testing.assert_array_equal(d.astype(np.uint8), rd, err_msg="done: " + where)
+        np.testing.assert_array_equal(r, ref["rew"][k], err_msg="reward: " + where)
+        keep = rd == 0
+        pk = ref["peek"][k]
+        np.testing.assert_array_equal(((fl & N.EV_COLLIDING) != 0)[keep], pk[keep, 9] != 0, err_msg="colliding: " + where)
+        np.testing.assert_array_equal(((fl & N.EV_GOAL_REACHED) != 0)[keep], pk[keep, 10] != 0, err_msg="goal: " + where)
+        err = np.abs(o - ref["obs"][k]).max(axis=1)
+        # bodies and arbiters: not for envs reset in this step (their columns lag the reset by one step)
+        tr = np.stack([x["traffic"] for x in ref["dyn"][k]])                   # [n, 3, 6]
+        go = np.stack([x["goals"] for x in ref["dyn"][k]])                     # [n, 5, 4]
+        terr = np.abs(t.reshape(n, 3, 9)[:, :, :6] - tr).reshape(n, -1).max(axis=1)
+        alive_g = ((gm[:, None] >> np.arange(5)[None, :]) & 1).astype(bool)
+        gerr = np.where(alive_g[:, :, None], np.abs(g.reshape(n, 6, 8)[:, :5, :4] - go), 0.0).reshape(n, -1).max(axis=1)
+        o_live, o_meta, o_hh, o_acc = ref["rows"][k]
+        aerr = np.abs(acc - o_acc)
+        arel = (aerr <= 1e-8 * np.abs(o_acc) + 1e-12).all(axis=(1, 2))
+        for e in np.nonzero(~keep | True)[0]:
+            s = scenes[e]
+            probs = []
+            if err[e] > 1e-9:
+                probs.append("obs %.3g" % err[e])
+            if keep[e]:
+                if terr[e] > 1e-8 or gerr[e] > 1e-8:
+                    probs.append("bodies %.3g %.3g" % (terr[e], gerr[e]))
+                if live[e] != o_live[e]:
+                    probs.append("live %x != %x" % (int(live[e]), int(o_live[e])))
+                elif (meta[e] != o_meta[e]).any() or (hh[e] != o_hh[e]).any():
+                    p = int(np.nonzero((meta[e] != o_meta[e]) | np.r_[hh[e] != o_hh[e], np.zeros(45, bool)])[0][0])
+                    probs.append("pair %d meta %x != %x" % (p, meta[e, p], o_meta[e, p]))
+                elif not arel[e]:
+                    probs.append("impulses %.3g" % aerr[e].max())
+            if probs:
+                out["bad"].append((k, e, s.family, s.tag, probs))
+        out["checked"] += int(keep.sum())
+    vec.close()
+    return out
+
+
+def test_dyn_step_at_its_edges(torch_cuda, oracle, native):
+    torch, O, N = torch_cuda, oracle, native
+    from helpers import oracle_cfg
+    scenes = DS.build_scenes(O)
+    n = len(scenes)
+    fam = collections.Counter(s.family for s in scenes)
+    assert set(fam) == set(DS.FAMILIES)
+    refs, first = {}, None
+    report = ["scenes per family: " + " ".join("%s %d" % (f, fam[f]) for f in DS.FAMILIES)]
+    for n_records, memo in LAYOUTS:
+        if n_records not in refs:
+            from ship_sim_gym_amd.vec_env import ShipVecEnv
+            probe = ShipVecEnv(8, n_maps=4, n_ships=4)  # (the oracle config of a 4-ship handle with the default beams / history)
+            cfg = oracle_cfg(O, probe)
+            probe.close()
+            ref = DS.run_oracle(O, scenes, n_records, K, cfg=cfg)
+            ref["rows"] = [DS.census_rows(c) for c in ref["census"]]
+            refs[n_records] = ref
+        ref = refs[n_records]
+        g = _gpu_run(torch, N, O, scenes, n_records, memo, ref)
+        where = "n_records=%d memo=%d" % (n_records, memo)
+        if g["bad"]:
+            by = collections.Counter((f, k) for k, _, f, _, _ in g["bad"])
+            print(where, "MISMATCHES", len(g["bad"]), sorted(by.items())[:20])
+            for b in g["bad"][:25]:
+                print("  ", b)
+        assert not g["bad"], (where, len(g["bad"]), g["bad"][:8])
+        print(where, "ok: %d env-steps checked, memo hits per step %s" % (g["checked"], g["hits"][:4]), flush=True)
+        if memo:
+            assert sum(g["hits"]) > 0, where
+            # the twins: poked one launch after their originals, from a parked state with no arbiters, so their whole memo key
+            # is the original's of the launch before; an original whose step is memoisable (list <= 8 arbiters) stored it — unless
+            # another lane of launch 0 claimed the same free table slot first (the CAS of the memo's claim: a cache miss, a few
+            # per launch of ~1 000 storing lanes in 16 384 slots), so nearly all, not all, of them are answered
+            c0 = ref["census"][0]
+            twins = [s for s in scenes if s.family == "dup" and len(c0[scenes.index(s.twin)]["list"]) <= 8]
+            assert len(twins) >= 40 and g["hits"][1] >= 0.8 * len(twins), (where, g["hits"][:3], len(twins))
+        # every layout: the same bits for every env up to its first done
+        done = np.stack(ref["done"])
+        first_done = np.where(done.any(axis=0), done.argmax(axis=0), K)
+        fp = np.stack(g["fp"])
+        if first is None:
+            first = (fp, first_done)
+        else:
+            upto = np.arange(K)[:, None] <= np.minimum(first_done, first[1])[None, :]
+            diff = (fp != first[0]) & upto
+            assert not diff.any(), (where, "differs from the first layout", [(int(k), int(e), scenes[e].tag) for k, e in zip(*np.nonzero(diff))][:8])
+    # coverage, from the oracle census (the small bank)
+    cen = refs[len(DS.RECORDS)]["census"]
+    lens = collections.Counter(len(c["list"]) for step in cen for c in step)
+    assert all(lens[m] > 0 for m in range(10)) and max(lens) > 12, sorted(lens.items())
+    assert max(c["epa_hull"] for step in cen for c in step) > 7
+    assert sum(c["c2c_zero"] for step in cen for c in step) > 0
+    ages = collections.Counter(a["age"] for step in cen for c in step for a in c["arbs"].values() if a["state"] == 4)
+    assert ages[1] > 0 and ages[2] > 0, ages
+    report.append("solver-list lengths (env-steps): " + " ".join("%d:%d" % kv for kv in sorted(lens.items())))
+    report.append("largest EPA hull %d, cached arbiters by age %s" % (max(c["epa_hull"] for step in cen for c in step), dict(ages)))
+    print("\n".join(report))
