@@ -34,7 +34,8 @@ extern "C" {
                              9: ssg_policy, ssg_policy_act, ssg_rollout_policy (the policy forward + action sampling of a rollout step on
                                 the device: rollouts with the policy in the loop, driven from C); extended, additively and without a
                                 version change: ssg_ppo_hparams, ssg_ppo_workspace_nbytes, ssg_ppo_gae, ssg_ppo_grad, ssg_ppo_adam,
-                                ssg_ppo_update (GAE and the PPO update of that policy on the device) */
+                                ssg_ppo_update (GAE and the PPO update of that policy on the device); ssg_population and the ssg_pop_*
+                                entry points (a population of such policies sharing every launch: batched PPO for PBT) */
 
 typedef enum ssg_status {
     SSG_OK = 0,
@@ -534,6 +535,112 @@ int ssg_ppo_update(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *
                    const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret, const int64_t *dev_perm,
                    int epochs, int minibatches, float *dev_adam_mv, int64_t step0, float *dev_stats /* nullable */,
                    void *dev_workspace, size_t workspace_nbytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * A population of policies on one handle (additions to ABI 9)
+ * Both reference trainers train populations: train/rllib/pbt.py:29-74 runs 120 PPO trials under PopulationBasedTraining,
+ * train/stable_baselines/ppo.py:118-137 three PPO2 models, one per learning rate.  Here P members share every launch of the rollout,
+ * of GAE and of the update, and each member's results are bit for bit what the single-policy entry points above compute for that
+ * member alone (the same device code behind a member dimension of the grid).
+ *
+ * Members.  All members share one architecture and one observation scale; dev_params is f32 [P][L] (L = the packed length of
+ * ssg_policy), and row m is a valid packed buffer of its own: an ssg_policy with dev_params = row m is member m.  The handle's envs
+ * are split into P equal contiguous slices by local env index: member m owns envs [m*n, (m+1)*n), n = n_envs / P (n_envs % P != 0 is
+ * SSG_ERR_BAD_ARG; n itself is unconstrained: every member has its own tail workgroup).  Env e runs under member e / n; its Philox
+ * counter stays the global env id env_id_base + e.
+ *
+ * Samples.  The rollout buffers are the [K][N] buffers of ssg_rollout_policy, N = n_envs.  Member m's sample i = t*n + e (e < n) is
+ * row t*N + m*n + e of them; dev_perm is int64 [P][epochs][K*n] of such member-local indices.
+ *
+ * Hyper-parameters are per member (a host array of P ssg_ppo_hparams); epochs and minibatches are common to the population.  The f32
+ * constants the kernels use (1 -+ clip, the coefficients, gamma, gamma*lam, adv_eps, and per Adam step 1-beta1, beta2, 1-beta2,
+ * sqrt(1-beta2^t), eps, -lr/(1-beta1^t)) are derived on the host, in double, exactly as the single-policy entry points derive them, by
+ * ssg_pop_pack_hparams into a caller buffer of SSG_POP_TABLE_FLOATS floats; the caller uploads it and passes the device copy
+ * (dev_table) to ssg_pop_gae / ssg_pop_update.  (The library owns no device memory; the host arrays are free once a call returns.)
+ *
+ * Workspace: ssg_pop_workspace_nbytes bytes, 256-byte aligned; ssg_pop_gae leaves f32 [P][4] advantage statistics (mean, std + adv_eps,
+ * its inverse, 0) at its start, per member over that member's K*n samples, which ssg_pop_update reads.  dev_adam_mv: f32 [P][2L].
+ * Out of scope: per-member epochs / minibatch sizes / batch sizes (they change launch shapes), a KL penalty, populations spanning
+ * handles or GPUs, per-member architectures.
+ * ------------------------------------------------------------------------------------------------- */
+#define SSG_POP_MAX_MEMBERS 256
+#define SSG_POP_TABLE_FLOATS(n_members, n_steps) ((size_t)(n_members) * 8u * (size_t)(1 + (n_steps)))
+typedef struct ssg_population {
+    uint32_t struct_size;        /* sizeof(ssg_population) */
+    int32_t n_members;           /* P: 1..SSG_POP_MAX_MEMBERS, a divisor of the handle's n_envs */
+    int32_t obs_dim;             /* the shape, as in ssg_policy */
+    int32_t hidden;
+    int32_t n_hidden_layers;
+    int32_t n_actions;
+    int32_t activation;
+    int32_t reserved;            /* 0 */
+    float *dev_params;           /* f32 [P][L]: row m = member m's packed parameters */
+    const double *dev_obs_scale; /* f64[obs_dim], common to the population */
+} ssg_population;
+
+/* Replaces: the policy half of one rollout step of EVERY trial of the reference's population (train/rllib/pbt.py:47-74: 120 PPO trials,
+ * each with its own sampler; train/stable_baselines/ppo.py:84-100 per model).  ssg_policy_act with env e evaluated under the parameters
+ * of member e / n: same buffers, same uniforms / Philox keying, ONE launch for the whole population.  SSG_ERR_BAD_ARG (nothing
+ * launched) for a bad record, n_members out of range or not a divisor of n_envs, or a NULL required pointer. */
+int ssg_pop_act(ssg_handle *h, const ssg_population *pop, const double *dev_obs, const float *dev_uniform /* nullable */, uint64_t seed,
+                int64_t step, int32_t *dev_actions, float *dev_logp, float *dev_value, float *dev_x /* nullable */, void *stream);
+
+/* Replaces: the rollout loops of that population (train/rllib/pbt.py:47-74; train/stable_baselines/ppo.py:118-137: three models on the
+ * same vector env, :84-100 per step).  ssg_rollout_policy with env e under member e / n: the same buffers, strides, uniforms, Philox
+ * keying, dev_last_value and per-step launch sequence (one policy launch per step for the whole population, then ssg_step); every
+ * handle ssg_rollout_policy serves is served.  Refusals as ssg_rollout_policy, plus those of ssg_pop_act. */
+int ssg_pop_rollout(ssg_handle *h, const ssg_population *pop, int K, const float *dev_uniform_KN /* nullable */, uint64_t seed,
+                    int64_t step0, double *dev_obs, int32_t *dev_act_KN, float *dev_logp_KN, float *dev_value_KN,
+                    float *dev_x_KND /* nullable */, double *dev_reward_KN, uint8_t *dev_done_KN, uint8_t *dev_flags_KN /* nullable */,
+                    float *dev_last_value /* nullable */, int64_t step_stride_envs, void *stream);
+
+/* Replaces nothing (host only; no reference counterpart: ray hands every trial its own config dict, train/rllib/pbt.py:56-70).  Fills
+ * out[0 .. SSG_POP_TABLE_FLOATS(n_members, n_steps)) with the members' f32 constants: 8 per member for GAE and the loss, then for Adam
+ * steps step0 + 1 .. step0 + n_steps 8 per member and step (n_steps = 0: no Adam rows, enough for ssg_pop_gae).  SSG_ERR_BAD_ARG for
+ * NULL pointers, n_members out of range, n_steps < 0, step0 < 0, out_floats too small or a bad ssg_ppo_hparams record. */
+int ssg_pop_pack_hparams(int n_members, const ssg_ppo_hparams *hparams, int64_t step0, int n_steps, float *out, size_t out_floats);
+
+/* Replaces nothing (memory binding; no reference counterpart): the workspace size for a population shaped like *pop, rollouts of up to
+ * samples_per_member = K*n samples per member and minibatches of up to max_minibatch samples per member.  SSG_ERR_BAD_ARG for a bad
+ * record, n_members out of range or sizes < 1. */
+int ssg_pop_workspace_nbytes(const ssg_population *pop, int64_t samples_per_member, int64_t max_minibatch, size_t *nbytes);
+
+/* Replaces: the advantage computation of every trial (train/rllib/pbt.py:47-74, with `lambda` among the mutated hyper-parameters,
+ * :36; train/stable_baselines/ppo.py:90 per model).  ssg_ppo_gae per member with that member's gamma / lam (dev_table) over its
+ * columns of the [K][N] buffers (N = the handle's n_envs); the advantage mean / unbiased std are per member, with partial sums laid
+ * out per member exactly as a single run over n envs lays them out (256-env blocks counted from the member's first env, the same
+ * final reduction).  Two launches.  SSG_ERR_BAD_ARG (nothing launched) for a bad record, NULL pointers, K < 1, K*n < 2 or a workspace
+ * too small. */
+int ssg_pop_gae(ssg_handle *h, const ssg_population *pop, const float *dev_table, int K, const double *dev_reward_KN,
+                const uint8_t *dev_done_KN, const float *dev_value_KN, const float *dev_last_value, float *dev_adv_KN, float *dev_ret_KN,
+                void *dev_workspace, size_t workspace_nbytes, void *stream);
+
+/* Replaces: the SGD phase of every trial (train/rllib/pbt.py:47-74: num_sgd_iter x minibatches per trial, with lr and clip_param
+ * mutated per trial, :36-38; train/stable_baselines/ppo.py:118-137: one model.learn per learning rate).  ssg_ppo_update for all members
+ * at once: epochs x chunks steps (C = ceil(K*n / minibatches), torch.chunk's split) of {gradient of every member, reduce + Adam of every
+ * member}, two launches per step with grid = (the single-policy grid for the chunk length, P).  dev_table: the device copy of
+ * ssg_pop_pack_hparams' output for table_steps >= epochs*chunks Adam steps (its step0 is the population's Adam step count before this
+ * call).  dev_stats (nullable): f32 [P][epochs*chunks][4].  Needs ssg_pop_gae's statistics in the workspace.  No floating-point
+ * atomics; member m's parameters, moments and stats are bitwise those of ssg_ppo_update on its slice.  SSG_ERR_BAD_ARG (nothing
+ * launched) for a bad record, NULL pointers, K < 1, epochs < 1, minibatches < 1, table_steps too small or a workspace too small. */
+int ssg_pop_update(ssg_handle *h, const ssg_population *pop, const float *dev_table, int table_steps, int K, const float *dev_x,
+                   const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret, const int64_t *dev_perm,
+                   int epochs, int minibatches, float *dev_adam_mv, float *dev_stats /* nullable */, void *dev_workspace,
+                   size_t workspace_nbytes, void *stream);
+
+/* Replaces: PopulationBasedTraining's exploit step (train/rllib/pbt.py:29-43: a bottom-quantile trial restores a top-quantile trial's
+ * checkpoint), on the device: member m takes the parameter row AND the Adam moments of member src[m] (host array int32 [P];
+ * src[m] == m keeps).  Validated on the host: every index in range and no source itself a destination (src[src[m]] == src[m]), so the
+ * copy does not depend on its order; otherwise SSG_ERR_BAD_ARG and nothing is launched.  One launch; src is free when the call returns. */
+int ssg_pop_exploit(ssg_handle *h, const ssg_population *pop, const int32_t *src, float *dev_adam_mv, void *stream);
+
+/* Replaces: the per-trial episode_reward_mean PopulationBasedTraining ranks trials by (train/rllib/pbt.py:31, reward_attr) —
+ * SSG_F_STATS is per handle and cannot be split by member.  One lane per env walks t = 0 .. K-1 over dev_reward_KN / dev_done_KN
+ * ([K][N] rows of a rollout) with caller-owned carry columns (dev_carry_return f64 [N], dev_carry_length i32 [N]; zero after a reset),
+ * so an episode that spans rollouts is counted once, at its end; at a done step it adds llrint(100 * return), the length and 1 to the
+ * member's row of dev_out (int64 [P][3], accumulated: the caller zeroes it).  Integer sums: order-free and exact.  One launch. */
+int ssg_pop_episode_stats(ssg_handle *h, int n_members, int K, const double *dev_reward_KN, const uint8_t *dev_done_KN,
+                          double *dev_carry_return, int32_t *dev_carry_length, int64_t *dev_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Host-side geometry (what pymunk's cffi exposed at reset time); no GPU needed.

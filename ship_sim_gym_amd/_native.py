@@ -17,6 +17,14 @@ MAP_OFF_COUNTS, MAP_OFF_AABB, MAP_OFF_GOALS, MAP_OFF_SPAWN_GOAL, MAP_OFF_PLANES,
 FLAG_AUTO_RESET, FLAG_FIX_COLLISION_REWARD, FLAG_BANK_IN_GLOBAL, FLAG_EXACT_LIDAR, FLAG_DYN_MEMO_OFF = 0x1, 0x2, 0x4, 0x8, 0x10
 EV_COLLIDING, EV_GOAL_REACHED, EV_OUT_OF_BOUNDS, EV_MAX_STEPS, EV_NO_GOALS_LEFT = 0x1, 0x2, 0x4, 0x8, 0x10
 POLICY_MAX_HIDDEN, POLICY_TANH, POLICY_RELU = 128, 0, 1
+POP_MAX_MEMBERS = 256
+
+
+def pop_table_floats(n_members, n_steps):
+    """SSG_POP_TABLE_FLOATS: the floats ssg_pop_pack_hparams writes for n_members members and n_steps Adam steps."""
+    return int(n_members) * 8 * (1 + int(n_steps))
+
+
 (F_X, F_Y, F_VX, F_VY, F_ANGLE, F_W, F_CUM_REWARD, F_LIDAR, F_RUDDER, F_STEP_COUNT, F_MAP_ID, F_GOAL_MASK,
  F_STATS, F_TRAFFIC, F_GOAL_BODIES, F_DYN_FLAGS, F_EPISODES, F_DYN_MEMO_STATS,
  F_DYN_LIVE, F_DYN_ARB_META, F_DYN_ARB_HASH, F_DYN_ARB_IMPULSE) = range(22)
@@ -32,6 +40,8 @@ EXPORTS = (
     "ssg_debug_clock_probe", "ssg_debug_launch_clock", "ssg_set_terminal_obs", "ssg_step_host", "ssg_wait_host",
     "ssg_policy_act", "ssg_rollout_policy",
     "ssg_ppo_workspace_nbytes", "ssg_ppo_gae", "ssg_ppo_grad", "ssg_ppo_adam", "ssg_ppo_update",
+    "ssg_pop_act", "ssg_pop_rollout", "ssg_pop_pack_hparams", "ssg_pop_workspace_nbytes", "ssg_pop_gae", "ssg_pop_update",
+    "ssg_pop_exploit", "ssg_pop_episode_stats",
 )
 
 
@@ -69,6 +79,15 @@ class PpoHparams(C.Structure):
         ("struct_size", C.c_uint32), ("gamma", C.c_double), ("lam", C.c_double), ("clip", C.c_double), ("vf_coef", C.c_double),
         ("ent_coef", C.c_double), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
         ("adv_eps", C.c_double),
+    ]
+
+
+class Population(C.Structure):
+    """ssg_population (ABI 9 addition): P policies of one shape on one handle; dev_params is f32 [P][L], row m = member m."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_members", C.c_int32), ("obs_dim", C.c_int32), ("hidden", C.c_int32),
+        ("n_hidden_layers", C.c_int32), ("n_actions", C.c_int32), ("activation", C.c_int32), ("reserved", C.c_int32),
+        ("dev_params", C.c_void_p), ("dev_obs_scale", C.c_void_p),
     ]
 
 
@@ -132,6 +151,15 @@ def lib():
     L.ssg_ppo_adam.argtypes = [vp, C.POINTER(Policy), C.POINTER(PpoHparams), vp, vp, C.c_int64, vp]
     L.ssg_ppo_update.argtypes = [vp, C.POINTER(Policy), C.POINTER(PpoHparams), C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp,
                                  C.c_int64, vp, vp, C.c_size_t, vp]
+    pp, hp = C.POINTER(Population), C.POINTER(PpoHparams)
+    L.ssg_pop_act.argtypes = [vp, pp, vp, vp, C.c_uint64, C.c_int64, vp, vp, vp, vp, vp]
+    L.ssg_pop_rollout.argtypes = [vp, pp, C.c_int, vp, C.c_uint64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64, vp]
+    L.ssg_pop_pack_hparams.argtypes = [C.c_int, hp, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_size_t]
+    L.ssg_pop_workspace_nbytes.argtypes = [pp, C.c_int64, C.c_int64, szp]
+    L.ssg_pop_gae.argtypes = [vp, pp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.ssg_pop_update.argtypes = [vp, pp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_size_t, vp]
+    L.ssg_pop_exploit.argtypes = [vp, pp, i32p, vp, vp]
+    L.ssg_pop_episode_stats.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     L.ssg_render.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, vp]
     L.ssg_dyn_invalidate.argtypes = [vp, vp, vp]
     L.ssg_host_convex_hull.argtypes = [C.c_int, dp, dp, ip]

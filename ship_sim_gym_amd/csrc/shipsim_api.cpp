@@ -1212,6 +1212,235 @@ int ssg_ppo_update(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *
     return SSG_OK;
 }
 
+// ABI 9 additions: a population of policies on one handle.  Order of the refusals: no handle (BAD_ARG), no state blob (NOT_BOUND), then
+// everything the host can judge about the arguments (BAD_ARG), and only then the device (check_ready) — nothing is enqueued before all
+// of it passed.
+static int pop_bound(ssg_handle *h)
+{
+    if (!h) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop: NULL handle");
+    if (!h->state) return fail(h, SSG_ERR_NOT_BOUND, "no state blob bound: call ssg_bind_state first");
+    return SSG_OK;
+}
+
+static ssg_policy pop_policy(const ssg_population &pop)
+{
+    ssg_policy p;
+    p.struct_size = sizeof(ssg_policy);
+    p.obs_dim = pop.obs_dim;
+    p.hidden = pop.hidden;
+    p.n_hidden_layers = pop.n_hidden_layers;
+    p.n_actions = pop.n_actions;
+    p.activation = pop.activation;
+    p.dev_params = pop.dev_params;
+    p.dev_obs_scale = pop.dev_obs_scale;
+    return p;
+}
+
+static bool pop_shape_ok(const ssg_population *pop)
+{
+    if (!pop || pop->struct_size != sizeof(ssg_population)) return false;
+    if (pop->n_members < 1 || pop->n_members > SSG_POP_MAX_MEMBERS) return false;
+    const ssg_policy p = pop_policy(*pop);
+    return check_policy_shape(&p) != 0;
+}
+
+// the record against the handle: shape, member count, pointers
+static int check_population(ssg_handle *h, const ssg_population *pop, const char *what)
+{
+    const std::string w(what);
+    if (!pop) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL population");
+    if (pop->struct_size != sizeof(ssg_population)) return fail(h, SSG_ERR_BAD_ARG, w + ": ssg_population.struct_size != sizeof(ssg_population)");
+    if (pop->n_members < 1 || pop->n_members > SSG_POP_MAX_MEMBERS) return fail(h, SSG_ERR_BAD_ARG, w + ": n_members must be in 1..SSG_POP_MAX_MEMBERS");
+    if (h->cfg.n_envs % pop->n_members != 0) {
+        char buf[160];
+        std::snprintf(buf, sizeof buf, ": the handle's %d envs do not split into %d equal member slices", h->cfg.n_envs, pop->n_members);
+        return fail(h, SSG_ERR_BAD_ARG, w + buf);
+    }
+    const ssg_policy p = pop_policy(*pop);
+    return check_policy(h, &p, what);
+}
+
+int ssg_pop_act(ssg_handle *h, const ssg_population *pop, const double *dev_obs, const float *dev_uniform, uint64_t seed, int64_t step,
+                int32_t *dev_actions, float *dev_logp, float *dev_value, float *dev_x, void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_act");
+    if (rc != SSG_OK) return rc;
+    if (!dev_obs || !dev_actions || !dev_logp || !dev_value)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_act: NULL dev_obs, dev_actions, dev_logp or dev_value");
+    rc = check_ready(h, false);
+    if (rc == SSG_OK) rc = prepare_policy(h);
+    if (rc != SSG_OK) return rc;
+    const int P = pop->n_members;
+    hipError_t e = ssg::launch_policy_pop(pop_policy(*pop), P, h->cfg.n_envs / P, h->cfg.env_id_base, dev_obs, dev_uniform, seed, step,
+                                          dev_actions, dev_logp, dev_value, dev_x, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population policy launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+int ssg_pop_rollout(ssg_handle *h, const ssg_population *pop, int K, const float *dev_uniform_KN, uint64_t seed, int64_t step0,
+                    double *dev_obs, int32_t *dev_act_KN, float *dev_logp_KN, float *dev_value_KN, float *dev_x_KND,
+                    double *dev_reward_KN, uint8_t *dev_done_KN, uint8_t *dev_flags_KN, float *dev_last_value, int64_t step_stride_envs,
+                    void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_rollout");
+    if (rc != SSG_OK) return rc;
+    if (!dev_obs || !dev_act_KN || !dev_logp_KN || !dev_value_KN || !dev_reward_KN || !dev_done_KN)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_rollout: NULL dev_obs, act, logp, value, reward or done buffer");
+    if (K < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_rollout: K < 1");
+    if (step_stride_envs < (int64_t)h->cfg.n_envs) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_rollout: step_stride_envs < n_envs (steps would overlap)");
+    rc = check_ready(h, true);
+    if (rc != SSG_OK) return rc;
+    if (h->cfg.map_ring > 0 && !h->ring_ready) return fail(h, SSG_ERR_NOT_BOUND, "map_ring mode: call ssg_refill_worlds first");
+    rc = refuse_capture(h, stream, "ssg_pop_rollout");
+    if (rc != SSG_OK) return rc;
+    rc = prepare(h);
+    if (rc == SSG_OK) rc = prepare_policy(h);
+    if (rc != SSG_OK) return rc;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const ssg_policy pol = pop_policy(*pop);
+    const int P = pop->n_members, n = h->cfg.n_envs / P;
+    const size_t S = (size_t)step_stride_envs, D = (size_t)pol.obs_dim;
+    for (int k = 0; k < K; ++k) { // ssg_rollout_policy's sequence: one policy launch for the whole population, then the step
+        const size_t r = (size_t)k * S;
+        hipError_t e = ssg::launch_policy_pop(pol, P, n, h->cfg.env_id_base, dev_obs, dev_uniform_KN ? dev_uniform_KN + r : nullptr, seed,
+                                              step0 + k, dev_act_KN + r, dev_logp_KN + r, dev_value_KN + r,
+                                              dev_x_KND ? dev_x_KND + r * D : nullptr, st);
+        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population policy launch: ") + hipGetErrorString(e));
+        rc = ssg_rollout_traj(h, dev_act_KN + r, 1, dev_obs, dev_reward_KN + r, dev_done_KN + r, dev_flags_KN ? dev_flags_KN + r : nullptr, 0,
+                              stream);
+        if (rc != SSG_OK) return rc;
+    }
+    if (dev_last_value) {
+        hipError_t e = ssg::launch_policy_pop(pol, P, n, h->cfg.env_id_base, dev_obs, nullptr, seed, step0 + K, nullptr, nullptr,
+                                              dev_last_value, nullptr, st);
+        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population policy launch: ") + hipGetErrorString(e));
+    }
+    return SSG_OK;
+}
+
+int ssg_pop_pack_hparams(int n_members, const ssg_ppo_hparams *hparams, int64_t step0, int n_steps, float *out, size_t out_floats)
+{
+    if (!hparams || !out || n_members < 1 || n_members > SSG_POP_MAX_MEMBERS || n_steps < 0 || step0 < 0)
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_hparams: NULL pointer, n_members out of range, n_steps < 0 or step0 < 0");
+    if (out_floats < SSG_POP_TABLE_FLOATS(n_members, n_steps))
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_hparams: out_floats < SSG_POP_TABLE_FLOATS(n_members, n_steps)");
+    for (int m = 0; m < n_members; ++m) {
+        const int rc = check_hparams(nullptr, hparams + m, "ssg_pop_pack_hparams");
+        if (rc != SSG_OK) return rc;
+    }
+    ssg::pop_pack(n_members, hparams, step0, n_steps, out);
+    return SSG_OK;
+}
+
+static size_t pop_need_gae(int P, long long n) { return ssg::kPopSlotsOff + (size_t)P * (size_t)ssg::ppo_gae_blocks(n) * 16; }
+static size_t pop_need_grad(const ssg_policy &p, int P, long long M)
+{
+    return ssg::kPopSlotsOff + (size_t)P * (size_t)ssg::ppo_grid(M) * (size_t)(ssg::ppo_packed_len(p) + 4) * sizeof(float);
+}
+
+int ssg_pop_workspace_nbytes(const ssg_population *pop, int64_t samples_per_member, int64_t max_minibatch, size_t *nbytes)
+{
+    if (!nbytes || !pop_shape_ok(pop) || samples_per_member < 1 || max_minibatch < 1)
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_workspace_nbytes: bad population record, n_members out of range, NULL nbytes or a size < 1");
+    *nbytes = std::max(pop_need_gae(pop->n_members, samples_per_member), pop_need_grad(pop_policy(*pop), pop->n_members, max_minibatch));
+    return SSG_OK;
+}
+
+int ssg_pop_gae(ssg_handle *h, const ssg_population *pop, const float *dev_table, int K, const double *dev_reward_KN,
+                const uint8_t *dev_done_KN, const float *dev_value_KN, const float *dev_last_value, float *dev_adv_KN, float *dev_ret_KN,
+                void *dev_workspace, size_t workspace_nbytes, void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_gae");
+    if (rc != SSG_OK) return rc;
+    if (!dev_table || !dev_reward_KN || !dev_done_KN || !dev_value_KN || !dev_last_value || !dev_adv_KN || !dev_ret_KN)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_gae: NULL table, reward, done, value, last value, adv or ret buffer");
+    const int P = pop->n_members, N = h->cfg.n_envs, n = N / P;
+    if (K < 1 || (long long)K * n < 2) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_gae: K must be >= 1 and K * (n_envs / n_members) >= 2");
+    rc = check_workspace(h, dev_workspace, workspace_nbytes, pop_need_gae(P, n), "ssg_pop_gae");
+    if (rc == SSG_OK) rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_pop_gae(P, K, N, dev_table, dev_reward_KN, dev_done_KN, dev_value_KN, dev_last_value, dev_adv_KN, dev_ret_KN,
+                                       dev_workspace, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population gae launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+int ssg_pop_update(ssg_handle *h, const ssg_population *pop, const float *dev_table, int table_steps, int K, const float *dev_x,
+                   const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret, const int64_t *dev_perm,
+                   int epochs, int minibatches, float *dev_adam_mv, float *dev_stats, void *dev_workspace, size_t workspace_nbytes,
+                   void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_update");
+    if (rc != SSG_OK) return rc;
+    if (K < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update: K < 1");
+    const int P = pop->n_members, N = h->cfg.n_envs;
+    const long long n = (long long)K * (N / P); // samples per member
+    rc = check_batch(h, n, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_perm, "ssg_pop_update");
+    if (rc != SSG_OK) return rc;
+    if (!dev_table || !dev_adam_mv) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update: NULL dev_table or dev_adam_mv");
+    if (epochs < 1 || minibatches < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update: epochs < 1 or minibatches < 1");
+    const long long C = (n + minibatches - 1) / minibatches, chunks = (n + C - 1) / C; // torch.chunk
+    if ((long long)table_steps < (long long)epochs * chunks)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update: the table holds fewer Adam steps than epochs * chunks");
+    const ssg_policy pol = pop_policy(*pop);
+    rc = check_workspace(h, dev_workspace, workspace_nbytes, pop_need_grad(pol, P, C), "ssg_pop_update");
+    if (rc == SSG_OK) rc = check_ready(h, false);
+    if (rc == SSG_OK) rc = prepare_ppo(h);
+    if (rc != SSG_OK) return rc;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    long long j = 0;
+    for (int ep = 0; ep < epochs; ++ep) {
+        for (long long b0 = 0; b0 < n; b0 += C, ++j) {
+            const long long M = std::min(C, n - b0);
+            hipError_t e = ssg::launch_pop_grad(pol, P, K, N, dev_table, dev_table + (size_t)(1 + j) * (size_t)P * ssg::kPopTableRow, dev_x,
+                                                dev_act, dev_logp, dev_adv, dev_ret, dev_perm + (size_t)ep * (size_t)n + (size_t)b0,
+                                                (long long)epochs * n, M, dev_workspace, dev_stats ? dev_stats + 4 * j : nullptr,
+                                                4 * (long long)epochs * chunks, dev_adam_mv, st);
+            if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population update launch: ") + hipGetErrorString(e));
+        }
+    }
+    return SSG_OK;
+}
+
+int ssg_pop_exploit(ssg_handle *h, const ssg_population *pop, const int32_t *src, float *dev_adam_mv, void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_exploit");
+    if (rc != SSG_OK) return rc;
+    if (!src || !dev_adam_mv) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_exploit: NULL src or dev_adam_mv");
+    const int P = pop->n_members;
+    for (int m = 0; m < P; ++m)
+        if (src[m] < 0 || src[m] >= P) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_exploit: a source index is out of range");
+    for (int m = 0; m < P; ++m)
+        if (src[src[m]] != src[m]) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_exploit: a source is itself a destination (chained copy)");
+    rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_pop_exploit(pop_policy(*pop), P, src, dev_adam_mv, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population exploit launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+int ssg_pop_episode_stats(ssg_handle *h, int n_members, int K, const double *dev_reward_KN, const uint8_t *dev_done_KN,
+                          double *dev_carry_return, int32_t *dev_carry_length, int64_t *dev_out, void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc != SSG_OK) return rc;
+    if (n_members < 1 || n_members > SSG_POP_MAX_MEMBERS || h->cfg.n_envs % n_members != 0)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_episode_stats: n_members must be in 1..SSG_POP_MAX_MEMBERS and divide the handle's n_envs");
+    if (K < 1 || !dev_reward_KN || !dev_done_KN || !dev_carry_return || !dev_carry_length || !dev_out)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_episode_stats: K < 1 or a NULL buffer");
+    rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_pop_episode_stats(n_members, K, h->cfg.n_envs, dev_reward_KN, dev_done_KN, dev_carry_return,
+                                                 dev_carry_length, dev_out, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population episode stats launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
 int ssg_fill_actions(ssg_handle *h, uint64_t seed, uint64_t step0, int K, int32_t *dev_actions, void *stream)
 {
     if (!h || !dev_actions || K < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_fill_actions: bad argument");

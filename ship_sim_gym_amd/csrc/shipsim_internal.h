@@ -224,6 +224,28 @@ hipError_t launch_ppo_grad(const ssg_policy &p, const ssg_ppo_hparams &hp, long 
                            float *grad_out, float *stats_out, float *adam_mv, int64_t step, hipStream_t stream);
 hipError_t launch_ppo_adam(const ssg_policy &p, const ssg_ppo_hparams &hp, const float *grad, float *adam_mv, int64_t step,
                            hipStream_t stream);
+// A population of `members` policies on one handle (ssg_pop_*): p is the shared shape with dev_params = f32 [members][L]; member m owns
+// the n = N / members envs [m*n, (m+1)*n).  Workspace: f32 [members][4] advantage statistics at kPpoStatsOff (room for
+// SSG_POP_MAX_MEMBERS rows), then from kPopSlotsOff the gradient slots [members][grid][L + 4] — or, during ssg_pop_gae, the f64
+// partials [members][ppo_gae_blocks(n)].  table: the device copy of what pop_pack wrote, kPopTableRow floats per member (loss / GAE
+// constants), then per Adam step kPopTableRow floats per member.
+constexpr size_t kPopSlotsOff = 4096;
+constexpr int kPopTableRow = 8;
+static_assert(SSG_POP_MAX_MEMBERS * 16 <= kPopSlotsOff, "the members' advantage statistics fit in front of the slots");
+hipError_t launch_policy_pop(const ssg_policy &p, int members, int n, long long env_base, const double *obs, const float *uniform,
+                             uint64_t seed, int64_t step, int32_t *act, float *logp, float *value, float *x, hipStream_t stream);
+void pop_pack(int members, const ssg_ppo_hparams *hp, int64_t step0, int n_steps, float *out); // host only
+hipError_t launch_pop_gae(int members, int K, int N, const float *table, const double *rew, const uint8_t *done, const float *val,
+                          const float *last_val, float *adv, float *ret, void *ws, hipStream_t stream);
+// one minibatch of every member: the gradients (member m's indices at idx + m*idx_stride, member-local), then reduce + Adam with the
+// step's table rows adam_row; stats_out (nullable): member m's row at stats_out + m*stats_stride
+hipError_t launch_pop_grad(const ssg_policy &p, int members, long long K, long long N, const float *table, const float *adam_row,
+                           const float *x, const int32_t *act, const float *logp, const float *adv, const float *ret,
+                           const int64_t *idx, long long idx_stride, long long M, void *ws, float *stats_out, long long stats_stride,
+                           float *adam_mv, hipStream_t stream);
+hipError_t launch_pop_exploit(const ssg_policy &p, int members, const int32_t *src, float *adam_mv, hipStream_t stream);
+hipError_t launch_pop_episode_stats(int members, int K, int N, const double *rew, const uint8_t *done, double *carry_ret,
+                                    int32_t *carry_len, int64_t *out, hipStream_t stream);
 
 #ifdef __HIPCC__
 // One round of Philox4x32-10 (counter ctr, key key).  The counter-based streams of the library — fill_actions_kernel's actions

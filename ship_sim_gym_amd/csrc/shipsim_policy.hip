@@ -80,13 +80,30 @@ __device__ __forceinline__ void dense(const float *__restrict__ W, const float *
 }
 
 // (waves_per_eu(1, 2): lets the scheduler keep all 16 weight reads of a step in flight — 113 VGPRs — instead of two at a time)
+//
+// POP = false: ssg_policy_act's launch, n envs under one parameter buffer (plen unused).  POP = true: a population in one launch, grid
+// (workgroups of n envs, members): member m = blockIdx.y owns the n envs [m*n, (m+1)*n) of every buffer and the parameter row
+// params + m*plen, with a tail workgroup of its own, so an env's outputs are bit for bit those of the POP = false launch on that slice
+// with that row (the same code below).  The Philox counter stays the global env id: env_base + m*n + e.
+template <bool POP>
 __global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1, 2))) policy_act_kernel(const ssg_policy p, const float *__restrict__ params, const double *__restrict__ scale,
                                                               int n, long long env_base, const double *__restrict__ obs,
                                                               const float *__restrict__ uniform, uint64_t seed, int64_t step,
                                                               int32_t *__restrict__ act_out, float *__restrict__ logp_out,
-                                                              float *__restrict__ value_out, float *__restrict__ x_out)
+                                                              float *__restrict__ value_out, float *__restrict__ x_out, int plen)
 {
     extern __shared__ float4 lds4[];
+    if (POP) { // the member's slice of every buffer
+        const size_t m0 = (size_t)blockIdx.y * (size_t)n, D = (size_t)p.obs_dim;
+        params += (size_t)blockIdx.y * (size_t)plen;
+        env_base += (long long)m0;
+        obs += m0 * D;
+        if (uniform) uniform += m0;
+        if (act_out) act_out += m0;
+        if (logp_out) logp_out += m0;
+        if (value_out) value_out += m0;
+        if (x_out) x_out += m0 * D;
+    }
     const int lane = threadIdx.x;
     const int e0 = blockIdx.x * kPolWave;
     const int ne = (n - e0 < kPolWave) ? n - e0 : kPolWave; // tail workgroup: lanes >= ne store nothing
@@ -209,15 +226,26 @@ size_t policy_lds_bytes(const ssg_policy &p)
 
 hipError_t prepare_policy()
 {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(policy_act_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(policy_act_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(policy_act_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
 hipError_t launch_policy_act(const ssg_policy &p, int n, long long env_base, const double *obs, const float *uniform, uint64_t seed,
                              int64_t step, int32_t *act, float *logp, float *value, float *x, hipStream_t stream)
 {
     const unsigned grid = (unsigned)((n + kPolWave - 1) / kPolWave);
-    hipLaunchKernelGGL(policy_act_kernel, dim3(grid), dim3(kPolWave), policy_lds_bytes(p), stream, p, p.dev_params, p.dev_obs_scale, n, env_base,
-                       obs, uniform, seed, step, act, logp, value, x);
+    hipLaunchKernelGGL(policy_act_kernel<false>, dim3(grid), dim3(kPolWave), policy_lds_bytes(p), stream, p, p.dev_params, p.dev_obs_scale, n, env_base,
+                       obs, uniform, seed, step, act, logp, value, x, 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_pop(const ssg_policy &p, int members, int n, long long env_base, const double *obs, const float *uniform,
+                             uint64_t seed, int64_t step, int32_t *act, float *logp, float *value, float *x, hipStream_t stream)
+{
+    const unsigned grid = (unsigned)((n + kPolWave - 1) / kPolWave);
+    hipLaunchKernelGGL(policy_act_kernel<true>, dim3(grid, (unsigned)members), dim3(kPolWave), policy_lds_bytes(p), stream, p, p.dev_params,
+                       p.dev_obs_scale, n, env_base, obs, uniform, seed, step, act, logp, value, x, ppo_packed_len(p));
     return hipGetLastError();
 }
 

@@ -59,15 +59,15 @@ __device__ __forceinline__ float tile_sum(const float *v, int stride)
 // ------------------------------------------------------------------------------------------------------------------------------
 // GAE
 // ------------------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) ppo_gae_kernel(int K, int N, const double *__restrict__ rew, const uint8_t *__restrict__ done,
-                                                      const float *__restrict__ val, const float *__restrict__ last_val,
-                                                      float *__restrict__ adv_out, float *__restrict__ ret_out, float gf, float glf,
-                                                      double2 *__restrict__ part)
+// The walk of workgroup blockIdx.x's 256 envs out of n, over [K] rows that are N apart (the body of both GAE kernels; every pointer
+// is the first env's of the batch the workgroup belongs to, rs / rq its 2 x 256 doubles of LDS).
+__device__ __forceinline__ void gae_body(int K, int N, int n, const double *__restrict__ rew, const uint8_t *__restrict__ done,
+                                         const float *__restrict__ val, const float *__restrict__ last_val, float *__restrict__ adv_out,
+                                         float *__restrict__ ret_out, float gf, float glf, double2 *__restrict__ part, double *rs, double *rq)
 {
-    __shared__ double rs[256], rq[256];
     const int e = blockIdx.x * 256 + threadIdx.x;
     double s = 0.0, q = 0.0;
-    if (e < N) {
+    if (e < n) {
         float nxt = last_val[e], adv = 0.0f;
         for (int t = K - 1; t >= 0; --t) {
             const size_t i = (size_t)t * N + e;
@@ -94,11 +94,37 @@ __global__ void __launch_bounds__(256) ppo_gae_kernel(int K, int N, const double
     if (threadIdx.x == 0) part[blockIdx.x] = make_double2(rs[0], rq[0]);
 }
 
-// stats[0] = mean, stats[1] = std + adv_eps (unbiased std, as torch's .std()), stats[2] = 1 / stats[1]
-__global__ void __launch_bounds__(256) ppo_gae_stats_kernel(const double2 *__restrict__ part, int nblocks, double n, float adv_eps,
-                                                            float *__restrict__ stats)
+__global__ void __launch_bounds__(256) ppo_gae_kernel(int K, int N, const double *__restrict__ rew, const uint8_t *__restrict__ done,
+                                                      const float *__restrict__ val, const float *__restrict__ last_val,
+                                                      float *__restrict__ adv_out, float *__restrict__ ret_out, float gf, float glf,
+                                                      double2 *__restrict__ part)
 {
     __shared__ double rs[256], rq[256];
+    gae_body(K, N, N, rew, done, val, last_val, adv_out, ret_out, gf, glf, part, rs, rq);
+}
+
+// The per-member constants of a population (ssg_pop_pack_hparams derives them on the host, in double, exactly as launch_ppo_gae,
+// launch_ppo_grad and adam_args do for one policy): kPopTableRow floats per member — lo, hi, clip, vf, ent, adv_eps, gamma, gamma*lam —
+// then per Adam step kPopTableRow floats per member: AdamArgs' seven fields.
+enum { PT_LO = 0, PT_HI, PT_CLIP, PT_VF, PT_ENT, PT_ADV_EPS, PT_GF, PT_GLF };
+
+// GAE of a population: member m = blockIdx.y owns columns [m*n, (m+1)*n) of the [K][N] buffers, walks them with its own gamma /
+// lambda, and lays its partial sums out as a run over n envs does (256-env blocks from the member's first env: part[m*nb + block]).
+__global__ void __launch_bounds__(256) pop_gae_kernel(int K, int N, int n, int nb, const double *__restrict__ rew,
+                                                      const uint8_t *__restrict__ done, const float *__restrict__ val,
+                                                      const float *__restrict__ last_val, float *__restrict__ adv_out,
+                                                      float *__restrict__ ret_out, const float *__restrict__ table, double2 *__restrict__ part)
+{
+    __shared__ double rs[256], rq[256];
+    const size_t m = blockIdx.y, e0 = m * (size_t)n;
+    gae_body(K, N, n, rew + e0, done + e0, val + e0, last_val + e0, adv_out + e0, ret_out + e0, table[m * kPopTableRow + PT_GF],
+             table[m * kPopTableRow + PT_GLF], part + m * (size_t)nb, rs, rq);
+}
+
+// stats[0] = mean, stats[1] = std + adv_eps (unbiased std, as torch's .std()), stats[2] = 1 / stats[1]
+__device__ __forceinline__ void gae_stats_body(const double2 *__restrict__ part, int nblocks, double n, float adv_eps,
+                                               float *__restrict__ stats, double *rs, double *rq)
+{
     double s = 0.0, q = 0.0;
     for (int b = threadIdx.x; b < nblocks; b += 256) {
         s += part[b].x;
@@ -124,6 +150,22 @@ __global__ void __launch_bounds__(256) ppo_gae_stats_kernel(const double2 *__res
         stats[2] = 1.0f / stdp;
         stats[3] = 0.0f;
     }
+}
+
+__global__ void __launch_bounds__(256) ppo_gae_stats_kernel(const double2 *__restrict__ part, int nblocks, double n, float adv_eps,
+                                                            float *__restrict__ stats)
+{
+    __shared__ double rs[256], rq[256];
+    gae_stats_body(part, nblocks, n, adv_eps, stats, rs, rq);
+}
+
+// one workgroup per member: the member's nblocks partials in the single run's order, into stats[m][4]
+__global__ void __launch_bounds__(256) pop_gae_stats_kernel(const double2 *__restrict__ part, int nblocks, double n,
+                                                            const float *__restrict__ table, float *__restrict__ stats)
+{
+    __shared__ double rs[256], rq[256];
+    const size_t m = blockIdx.x;
+    gae_stats_body(part + m * (size_t)nblocks, nblocks, n, table[m * kPopTableRow + PT_ADV_EPS], stats + m * 4, rs, rq);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -219,10 +261,35 @@ __device__ __forceinline__ void mm_wgrad(const float *dz, int sdz, const float *
     }
 }
 
-__global__ void __launch_bounds__(kPpoBlock) ppo_grad_kernel(const GradArgs a)
+// What a population's launch adds to GradArgs (whose params / idx / stats / slots are then member 0's and whose lo .. ent are unused).
+struct PopGradArgs {
+    long long n, N;       // envs per member, envs of the batch: member m's sample i = t*n + e is row t*N + m*n + e of the [K][N] buffers
+    long long idx_stride; // int64 entries between two members' index rows
+    const float *table;   // [members][kPopTableRow]
+};
+
+// POP = false: ssg_ppo_grad's launch (pa unused).  POP = true: the minibatch gradient of every member in one launch, grid
+// (ppo_grid(M), members): member m = blockIdx.y reads parameter row m, its own index row (member-local indices), its advantage
+// statistics (stats + 4m) and loss constants (table row m), and owns the slots [m*grid, (m+1)*grid) — what the POP = false launch
+// computes for that member alone, tile for tile (the same code below).
+template <bool POP> __global__ void __launch_bounds__(kPpoBlock) ppo_grad_kernel(const GradArgs a_, const PopGradArgs pa)
 {
     extern __shared__ float4 lds4[];
     float *lds = reinterpret_cast<float *>(lds4);
+    GradArgs a = a_;
+    if (POP) {
+        const size_t m = blockIdx.y;
+        a.params += m * (size_t)a.P;
+        a.idx += m * (size_t)pa.idx_stride;
+        a.stats += m * 4;
+        a.slots += m * (size_t)gridDim.x * (size_t)(a.P + 4);
+        const float *row = pa.table + m * kPopTableRow;
+        a.lo = row[PT_LO];
+        a.hi = row[PT_HI];
+        a.clip = row[PT_CLIP];
+        a.vf = row[PT_VF];
+        a.ent = row[PT_ENT];
+    }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int D = a.D, H = a.H, A = a.A, kind = a.kind, NT = H / 16;
     const int DT = (D + 15) / 16, D4 = (D + 3) & ~3;
@@ -266,6 +333,10 @@ __global__ void __launch_bounds__(kPpoBlock) ppo_grad_kernel(const GradArgs a)
             const long long i = tile * kTile + tid;
             long long j = i < a.M ? a.idx[i] : -1;
             if (j >= a.n_samples) j = -1;
+            if (POP && j >= 0) {
+                const long long t = j / pa.n;
+                j = t * pa.N + (long long)blockIdx.y * pa.n + (j - t * pa.n);
+            }
             SIDX[tid] = j;
             if (j >= 0) {
                 SACT[tid] = a.act[j];
@@ -413,10 +484,32 @@ struct AdamArgs {
     float w1, one_minus_w1, beta2, w2, bc2_sqrt, eps, step_size;
 };
 
+// POP = false: the launch of ssg_ppo_grad / ssg_ppo_adam / ssg_ppo_update (stats_stride, adam unused).  POP = true: reduce + Adam of
+// every member in one launch, grid (ceil(stride / 256), members): member m = blockIdx.y sums its own G slots, writes its stats row
+// (stats_out + m*stats_stride, nullable) and steps parameter row m / moments row m with ITS Adam constants of this step (adam row m:
+// the host's doubles, rounded as adam_args rounds them).
+template <bool POP>
 __global__ void __launch_bounds__(256) ppo_reduce_kernel(const float *__restrict__ slots, int G, int P, int stride, float fM,
                                                          float *__restrict__ grad_out, float *__restrict__ stats_out,
-                                                         float *__restrict__ params, float *__restrict__ mv, const AdamArgs ad)
+                                                         float *__restrict__ params, float *__restrict__ mv, const AdamArgs ad_,
+                                                         long long stats_stride, const float *__restrict__ adam)
 {
+    AdamArgs ad = ad_;
+    if (POP) {
+        const size_t m = blockIdx.y;
+        const float *row = adam + m * kPopTableRow;
+        ad.w1 = row[0];
+        ad.one_minus_w1 = row[1];
+        ad.beta2 = row[2];
+        ad.w2 = row[3];
+        ad.bc2_sqrt = row[4];
+        ad.eps = row[5];
+        ad.step_size = row[6];
+        slots += m * (size_t)G * (size_t)stride;
+        if (stats_out) stats_out += m * (size_t)stats_stride;
+        params += m * (size_t)P;
+        mv += m * 2 * (size_t)P;
+    }
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= stride) return;
     float s = 0.0f; // the slots in order, 64 at a time as a tree of 4 trees of 16 (the missing ones are zeros)
@@ -450,6 +543,65 @@ __global__ void __launch_bounds__(256) ppo_reduce_kernel(const float *__restrict
         const float den = sqrtf(v) / ad.bc2_sqrt + ad.eps;
         params[p] = params[p] + ad.step_size * (m / den);
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// the PBT exploit copy and the per-member episode statistics
+// ------------------------------------------------------------------------------------------------------------------------------
+struct PopSrc {
+    uint8_t src[SSG_POP_MAX_MEMBERS]; // by value in the kernel arguments: the caller's host array is free when the call returns
+};
+
+// grid (ceil(3L / 256), members): member m with src[m] != m takes the parameter row and both moment rows of src[m].  The host
+// refused a source that is itself a destination, so no row is read and written in one launch.
+__global__ void __launch_bounds__(256) pop_exploit_kernel(const PopSrc s, int L, float *__restrict__ params, float *__restrict__ mv)
+{
+    const int m = blockIdx.y, from = s.src[m];
+    if (from == m) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < L) params[(size_t)m * L + i] = params[(size_t)from * L + i];
+    else if (i < 3 * L) mv[(size_t)m * 2 * L + (i - L)] = mv[(size_t)from * 2 * L + (i - L)];
+}
+
+// grid (ceil(n / 256), members): one lane per env walks t = 0 .. K-1 with the env's carried return / length; an episode is counted at
+// its done step as the step kernel counts it (llrint(100 * cum): cum is a sum of {1, -1, -0.01} terms).  Integer sums per workgroup,
+// then three integer atomics per workgroup on the member's triple: order-free and exact.
+__global__ void __launch_bounds__(256) pop_episode_stats_kernel(int K, int N, int n, const double *__restrict__ rew,
+                                                                const uint8_t *__restrict__ done, double *__restrict__ carry_ret,
+                                                                int32_t *__restrict__ carry_len, unsigned long long *__restrict__ out)
+{
+    __shared__ long long red[3][256];
+    const int el = blockIdx.x * 256 + threadIdx.x;
+    long long s_ret = 0, s_len = 0, s_eps = 0;
+    if (el < n) {
+        const size_t e = (size_t)blockIdx.y * (size_t)n + (size_t)el;
+        double cum = carry_ret[e];
+        int len = carry_len[e];
+        for (int t = 0; t < K; ++t) {
+            const size_t i = (size_t)t * N + e;
+            cum += rew[i];
+            len += 1;
+            if (done[i]) {
+                s_ret += (long long)llrint(cum * 100.0);
+                s_len += len;
+                s_eps += 1;
+                cum = 0.0;
+                len = 0;
+            }
+        }
+        carry_ret[e] = cum;
+        carry_len[e] = len;
+    }
+    red[0][threadIdx.x] = s_ret;
+    red[1][threadIdx.x] = s_len;
+    red[2][threadIdx.x] = s_eps;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w)
+            for (int c = 0; c < 3; ++c) red[c][threadIdx.x] += red[c][threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x < 3 && red[2][0] != 0) atomicAdd(out + (size_t)blockIdx.y * 3 + threadIdx.x, (unsigned long long)red[threadIdx.x][0]);
 }
 
 AdamArgs adam_args(const ssg_ppo_hparams &hp, int64_t step)
@@ -490,7 +642,9 @@ size_t ppo_grad_lds_bytes(const ssg_policy &p)
 
 hipError_t prepare_ppo()
 {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(ppo_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ppo_grad_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(ppo_grad_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
 hipError_t launch_ppo_gae(const ssg_ppo_hparams &hp, int K, int N, const double *rew, const uint8_t *done, const float *val,
@@ -536,11 +690,12 @@ hipError_t launch_ppo_grad(const ssg_policy &p, const ssg_ppo_hparams &hp, long 
     a.ent = (float)hp.ent_coef;
     a.invM = 1.0f / (float)M;
     const int G = ppo_grid(M);
-    hipLaunchKernelGGL(ppo_grad_kernel, dim3(G), dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a);
+    hipLaunchKernelGGL(ppo_grad_kernel<false>, dim3(G), dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a, PopGradArgs{});
     const int stride = a.P + 4;
     const AdamArgs ad = adam_mv ? adam_args(hp, step) : AdamArgs{};
-    hipLaunchKernelGGL(ppo_reduce_kernel, dim3((stride + 255) / 256), dim3(256), 0, stream, (const float *)a.slots, G, a.P, stride,
-                       (float)M, grad_out, stats_out, adam_mv ? const_cast<float *>(p.dev_params) : nullptr, adam_mv, ad);
+    hipLaunchKernelGGL(ppo_reduce_kernel<false>, dim3((stride + 255) / 256), dim3(256), 0, stream, (const float *)a.slots, G, a.P, stride,
+                       (float)M, grad_out, stats_out, adam_mv ? const_cast<float *>(p.dev_params) : nullptr, adam_mv, ad, 0ll,
+                       (const float *)nullptr);
     return hipGetLastError();
 }
 
@@ -548,8 +703,108 @@ hipError_t launch_ppo_adam(const ssg_policy &p, const ssg_ppo_hparams &hp, const
                            hipStream_t stream)
 {
     const int P = ppo_packed_len(p);
-    hipLaunchKernelGGL(ppo_reduce_kernel, dim3((P + 255) / 256), dim3(256), 0, stream, grad, 1, P, P, 1.0f, nullptr, nullptr,
-                       const_cast<float *>(p.dev_params), adam_mv, adam_args(hp, step));
+    hipLaunchKernelGGL(ppo_reduce_kernel<false>, dim3((P + 255) / 256), dim3(256), 0, stream, grad, 1, P, P, 1.0f, (float *)nullptr,
+                       (float *)nullptr, const_cast<float *>(p.dev_params), adam_mv, adam_args(hp, step), 0ll, (const float *)nullptr);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// the population launchers
+// ------------------------------------------------------------------------------------------------------------------------------
+void pop_pack(int members, const ssg_ppo_hparams *hp, int64_t step0, int n_steps, float *out)
+{
+    for (int m = 0; m < members; ++m) { // launch_ppo_gae's and launch_ppo_grad's roundings
+        float *row = out + (size_t)m * kPopTableRow;
+        row[PT_LO] = (float)(1.0 - hp[m].clip);
+        row[PT_HI] = (float)(1.0 + hp[m].clip);
+        row[PT_CLIP] = (float)hp[m].clip;
+        row[PT_VF] = (float)hp[m].vf_coef;
+        row[PT_ENT] = (float)hp[m].ent_coef;
+        row[PT_ADV_EPS] = (float)hp[m].adv_eps;
+        row[PT_GF] = (float)hp[m].gamma;
+        row[PT_GLF] = (float)(hp[m].gamma * hp[m].lam);
+    }
+    for (int j = 0; j < n_steps; ++j)
+        for (int m = 0; m < members; ++m) {
+            const AdamArgs ad = adam_args(hp[m], step0 + 1 + j);
+            float *row = out + ((size_t)(1 + j) * members + m) * kPopTableRow;
+            row[0] = ad.w1;
+            row[1] = ad.one_minus_w1;
+            row[2] = ad.beta2;
+            row[3] = ad.w2;
+            row[4] = ad.bc2_sqrt;
+            row[5] = ad.eps;
+            row[6] = ad.step_size;
+            row[7] = 0.0f;
+        }
+}
+
+hipError_t launch_pop_gae(int members, int K, int N, const float *table, const double *rew, const uint8_t *done, const float *val,
+                          const float *last_val, float *adv, float *ret, void *ws, hipStream_t stream)
+{
+    const int n = N / members, nb = ppo_gae_blocks(n);
+    float *stats = reinterpret_cast<float *>(static_cast<char *>(ws) + kPpoStatsOff);
+    double2 *part = reinterpret_cast<double2 *>(static_cast<char *>(ws) + kPopSlotsOff);
+    hipLaunchKernelGGL(pop_gae_kernel, dim3(nb, members), dim3(256), 0, stream, K, N, n, nb, rew, done, val, last_val, adv, ret, table, part);
+    hipLaunchKernelGGL(pop_gae_stats_kernel, dim3(members), dim3(256), 0, stream, (const double2 *)part, nb, (double)K * (double)n, table, stats);
+    return hipGetLastError();
+}
+
+hipError_t launch_pop_grad(const ssg_policy &p, int members, long long K, long long N, const float *table, const float *adam_row,
+                           const float *x, const int32_t *act, const float *logp, const float *adv, const float *ret,
+                           const int64_t *idx, long long idx_stride, long long M, void *ws, float *stats_out, long long stats_stride,
+                           float *adam_mv, hipStream_t stream)
+{
+    PopGradArgs pa;
+    GradArgs a;
+    a.D = p.obs_dim;
+    a.H = p.hidden;
+    a.L = p.n_hidden_layers;
+    a.A = p.n_actions;
+    a.kind = p.activation;
+    a.params = p.dev_params;
+    a.x = x;
+    a.act = act;
+    a.logp = logp;
+    a.adv = adv;
+    a.ret = ret;
+    a.idx = idx;
+    a.M = M;
+    pa.n = N / members;
+    pa.N = N;
+    a.n_samples = K * pa.n;
+    a.stats = reinterpret_cast<const float *>(static_cast<const char *>(ws) + kPpoStatsOff);
+    a.slots = reinterpret_cast<float *>(static_cast<char *>(ws) + kPopSlotsOff);
+    a.P = ppo_packed_len(p);
+    a.lo = a.hi = a.clip = a.vf = a.ent = 0.0f; // (per member: the table)
+    a.invM = 1.0f / (float)M;
+    pa.idx_stride = idx_stride;
+    pa.table = table;
+    const int G = ppo_grid(M);
+    hipLaunchKernelGGL(ppo_grad_kernel<true>, dim3(G, members), dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a, pa);
+    const int stride = a.P + 4;
+    hipLaunchKernelGGL(ppo_reduce_kernel<true>, dim3((stride + 255) / 256, members), dim3(256), 0, stream, (const float *)a.slots, G, a.P,
+                       stride, (float)M, (float *)nullptr, stats_out, const_cast<float *>(p.dev_params), adam_mv, AdamArgs{}, stats_stride,
+                       adam_row);
+    return hipGetLastError();
+}
+
+hipError_t launch_pop_exploit(const ssg_policy &p, int members, const int32_t *src, float *adam_mv, hipStream_t stream)
+{
+    PopSrc s;
+    for (int m = 0; m < SSG_POP_MAX_MEMBERS; ++m) s.src[m] = (uint8_t)(m < members ? src[m] : m);
+    const int L = ppo_packed_len(p);
+    hipLaunchKernelGGL(pop_exploit_kernel, dim3((3 * L + 255) / 256, members), dim3(256), 0, stream, s, L, const_cast<float *>(p.dev_params),
+                       adam_mv);
+    return hipGetLastError();
+}
+
+hipError_t launch_pop_episode_stats(int members, int K, int N, const double *rew, const uint8_t *done, double *carry_ret,
+                                    int32_t *carry_len, int64_t *out, hipStream_t stream)
+{
+    const int n = N / members;
+    hipLaunchKernelGGL(pop_episode_stats_kernel, dim3((n + 255) / 256, members), dim3(256), 0, stream, K, N, n, rew, done, carry_ret,
+                       carry_len, reinterpret_cast<unsigned long long *>(out));
     return hipGetLastError();
 }
 

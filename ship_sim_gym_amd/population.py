@@ -1,0 +1,382 @@
+"""A population of policies trained on one handle: NativePopulation, PopulationPPO and PBTScheduler (the ssg_pop_* entry points).
+
+Both reference trainers train populations: train/rllib/pbt.py runs 120 PPO trials under ray's PopulationBasedTraining (:29-43 the
+scheduler, :47-74 the experiment) and train/stable_baselines/ppo.py:118-137 three PPO2 models, one per learning rate.  A member of such a
+population is a small batch, and at small batches the device waits on launches; here the P members share every launch — one policy
+launch per rollout step, two launches for GAE, two per minibatch of the update — and each member's results are bit for bit what
+``NativePolicy`` / ``NativePPO`` compute for that member alone on its own shard of the envs.
+
+The handle's envs are split into P equal contiguous slices: member m owns envs [m*n, (m+1)*n), n = num_envs / P.  ``params`` is f32
+[P, L]; row m is a packed buffer of its own, and ``member(m)`` is a ``NativePolicy`` that shares it.  Hyper-parameters are per member
+(plain Python lists on ``PopulationPPO`` that a scheduler may rewrite between updates); epochs, minibatches and the batch size are common
+to the population (they shape the launches), there is no KL penalty (``NativePPO`` has none either), and a population lives on one
+handle with one architecture.
+
+``PBTScheduler`` is host-only (``random`` with its own seeded generator, no torch): ray 0.6's PopulationBasedTraining as the reference
+configures it, with the interval counted in updates instead of seconds of wall time.
+"""
+import ctypes as C
+import math
+import random
+
+from . import _native as N
+from .policy import ACTIVATIONS, NativePolicy
+from .ppo import chunk_split
+
+
+def _torch():
+    import torch
+    return torch
+
+
+class NativePopulation(object):
+    """members: P ``NativePolicy`` objects of one shape, activation and device (their parameters are copied into row m of ``params`` and
+    each member is re-pointed at its row).  obs_scale: f64 [obs_dim] common to the population (default: member 0's)."""
+
+    def __init__(self, members, obs_scale=None):
+        torch = _torch()
+        members = list(members)
+        if not 1 <= len(members) <= N.POP_MAX_MEMBERS:
+            raise ValueError("NativePopulation: 1..%d members (got %d)" % (N.POP_MAX_MEMBERS, len(members)))
+        first = members[0]
+        shape = (first.obs_dim, first.hidden, first.n_hidden_layers, first.n_actions, first.activation, first.device)
+        for m, pol in enumerate(members):
+            if (pol.obs_dim, pol.hidden, pol.n_hidden_layers, pol.n_actions, pol.activation, pol.device) != shape:
+                raise ValueError("NativePopulation: member %d differs from member 0 in shape, activation or device" % m)
+        self.obs_dim, self.hidden, self.n_hidden_layers, self.n_actions, self.activation, self.device = shape
+        self.offsets, self.n_params = first.offsets, first.params.numel()
+        if obs_scale is None:
+            obs_scale = first.obs_scale
+        elif not torch.is_tensor(obs_scale):
+            obs_scale = torch.full((self.obs_dim,), float(obs_scale), dtype=torch.float64)
+        obs_scale = obs_scale.detach().to(device=self.device, dtype=torch.float64).reshape(-1).contiguous()
+        if obs_scale.numel() != self.obs_dim:
+            raise ValueError("NativePopulation: obs_scale has %d entries, obs_dim is %d" % (obs_scale.numel(), self.obs_dim))
+        self.obs_scale = obs_scale
+        with torch.no_grad():
+            self.params = torch.stack([pol.params for pol in members]).contiguous()
+        self._members = members
+        for m, pol in enumerate(members):  # a member IS its row from now on
+            pol.params = self.params[m]
+            pol.obs_scale = self.obs_scale
+
+    @classmethod
+    def from_actor_critics(cls, nets, obs_scale):
+        """A population over the parameters OF `nets` (modules shaped like train/ppo_torch.py's ActorCritic, all alike)."""
+        return cls([NativePolicy.from_actor_critic(net, obs_scale) for net in nets])
+
+    @classmethod
+    def from_layers(cls, members, obs_scale, activation="tanh"):
+        """members: per member a (layers, pi, v) triple of (W, b) tensors, as NativePolicy's constructor takes them."""
+        return cls([NativePolicy(layers, pi, v, obs_scale, activation=activation) for layers, pi, v in members])
+
+    def __len__(self):
+        return len(self._members)
+
+    def member(self, m):
+        """Member m as a NativePolicy whose ``params`` is row m of this population's (a view: nothing is copied)."""
+        return self._members[m]
+
+    def refresh(self):
+        """Re-pack every member's source tensors into its row (after an optimiser step on the modules)."""
+        for pol in self._members:
+            pol.refresh()
+        return self.params
+
+    def load_into(self, nets):
+        """Copy row m into nets[m] (modules shaped like the members), for checkpoints."""
+        torch = _torch()
+        nets = list(nets)
+        if len(nets) != len(self):
+            raise ValueError("NativePopulation.load_into: %d modules for %d members" % (len(nets), len(self)))
+        with torch.no_grad():
+            for m, net in enumerate(nets):
+                params = list(net.parameters())
+                if sum(q.numel() for q in params) != self.n_params:
+                    raise ValueError("NativePopulation.load_into: module %d has %d parameters, a member %d"
+                                     % (m, sum(q.numel() for q in params), self.n_params))
+                o = 0
+                for q in params:
+                    q.copy_(self.params[m, o: o + q.numel()].view_as(q))
+                    o += q.numel()
+        return nets
+
+    def to_native(self):
+        """The ssg_population record (pointers into this object's tensors: keep it alive while the library uses it)."""
+        p = N.Population()
+        p.struct_size = C.sizeof(N.Population)
+        p.n_members = len(self)
+        p.obs_dim, p.hidden, p.n_hidden_layers, p.n_actions = self.obs_dim, self.hidden, self.n_hidden_layers, self.n_actions
+        p.activation = ACTIVATIONS[self.activation]
+        p.dev_params, p.dev_obs_scale = self.params.data_ptr(), self.obs_scale.data_ptr()
+        return p
+
+
+HPARAM_KEYS = ("gamma", "lam", "clip", "vf_coef", "ent_coef", "lr", "beta1", "beta2", "eps", "adv_eps")
+
+
+class PopulationPPO(object):
+    """GAE and the PPO update of every member of a NativePopulation in shared launches (ssg_pop_gae / ssg_pop_update), the PBT exploit
+    copy (ssg_pop_exploit) and per-member episode statistics (ssg_pop_episode_stats).  Owns the Adam moments [P, 2L], the workspace and
+    the episode carry columns.  Every hyper-parameter is a list of P floats (``self.lr[m] = ...``); defaults: NativePPO's."""
+
+    def __init__(self, population, env, gamma=0.99, lam=0.95, clip=0.2, vf_coef=0.5, ent_coef=0.01, lr=3e-4, beta1=0.9, beta2=0.999,
+                 eps=1e-8, adv_eps=1e-8):
+        torch = _torch()
+        self.population, self.env = population, env
+        P = len(population)
+        if env.states_history != population.obs_dim:
+            raise ValueError("PopulationPPO: the env's observation width %d differs from the population's obs_dim %d"
+                             % (env.states_history, population.obs_dim))
+        if env.num_envs % P:
+            raise ValueError("PopulationPPO: %d envs do not split into %d equal member slices" % (env.num_envs, P))
+        given = dict(gamma=gamma, lam=lam, clip=clip, vf_coef=vf_coef, ent_coef=ent_coef, lr=lr, beta1=beta1, beta2=beta2, eps=eps,
+                     adv_eps=adv_eps)
+        for k in HPARAM_KEYS:
+            v = given[k]
+            v = [float(x) for x in v] if isinstance(v, (list, tuple)) else [float(v)] * P
+            if len(v) != P:
+                raise ValueError("PopulationPPO: %s has %d entries for %d members" % (k, len(v), P))
+            setattr(self, k, v)
+        self.n_members, self.n_params, self.envs_per_member = P, population.n_params, env.num_envs // P
+        dev = population.device
+        self.adam_mv = torch.zeros((P, 2 * self.n_params), dtype=torch.float32, device=dev)  # per member: m, then v
+        self.step = 0  # Adam steps taken (common to the population: every update steps every member)
+        self.workspace = torch.zeros(0, dtype=torch.uint8, device=dev)
+        self.carry_return = torch.zeros(env.num_envs, dtype=torch.float64, device=dev)
+        self.carry_length = torch.zeros(env.num_envs, dtype=torch.int32, device=dev)
+
+    # ------------------------------------------------------------------------------------------------
+    def hparams(self):
+        """The members' hyper-parameters as a ctypes array of P ssg_ppo_hparams."""
+        arr = (N.PpoHparams * self.n_members)()
+        for m in range(self.n_members):
+            arr[m].struct_size = C.sizeof(N.PpoHparams)
+            for k in HPARAM_KEYS:
+                setattr(arr[m], k, float(getattr(self, k)[m]))
+        return arr
+
+    def _table(self, n_steps):
+        """The members' f32 constants for GAE, the loss and Adam steps self.step + 1 .. + n_steps, derived by the library on the host
+        in double (ssg_pop_pack_hparams) and uploaded: a fresh device tensor per call, so the lists may change right after."""
+        torch = _torch()
+        n = N.pop_table_floats(self.n_members, n_steps)
+        buf = (C.c_float * n)()
+        N.check(N.lib().ssg_pop_pack_hparams(self.n_members, self.hparams(), int(self.step), int(n_steps), buf, n), None,
+                "ssg_pop_pack_hparams")
+        return torch.tensor(list(buf), dtype=torch.float32).to(self.population.device)
+
+    def _ws(self, samples_per_member, max_minibatch):
+        """The workspace, grown to serve the sizes (its head — the members' advantage statistics — is kept when it grows)."""
+        torch = _torch()
+        need = C.c_size_t()
+        pop = self.population.to_native()
+        N.check(N.lib().ssg_pop_workspace_nbytes(C.byref(pop), int(samples_per_member), int(max_minibatch), C.byref(need)), None,
+                "ssg_pop_workspace_nbytes")
+        if self.workspace.numel() < need.value:
+            ws = torch.zeros(need.value + 256, dtype=torch.uint8, device=self.population.device)
+            if self.workspace.numel():
+                ws[:16 * self.n_members].copy_(self.workspace[:16 * self.n_members])
+            self.workspace = ws
+        return self.workspace
+
+    def _stream(self):
+        return C.c_void_p(_torch().cuda.current_stream(self.population.device).cuda_stream)
+
+    def _flat(self, batch, key, dtype, shape):
+        t = batch[key]
+        dev = self.population.device
+        if t.dtype != dtype or t.device != dev or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+            raise ValueError("PopulationPPO: batch[%r] must be a contiguous %s tensor %s on %s (got %s %s on %s)"
+                             % (key, dtype, tuple(shape), dev, t.dtype, tuple(t.shape), t.device))
+        return C.c_void_p(t.data_ptr())
+
+    def _KN(self, batch):
+        rew = batch["rew"]
+        if rew.dim() != 2 or int(rew.shape[1]) != self.env.num_envs:
+            raise ValueError("PopulationPPO: batch['rew'] must be [K, %d] (the handle's envs)" % self.env.num_envs)
+        return int(rew.shape[0]), self.env.num_envs
+
+    # ------------------------------------------------------------------------------------------------
+    def gae(self, batch):
+        """GAE of every member over its columns of the rollout batch (``rollout_population``'s dict) with its own gamma / lam: returns
+        (adv, ret) f32 [K, N], stored in the batch as "adv" / "ret"; leaves the per-member advantage statistics for update()."""
+        torch = _torch()
+        K, n_env = self._KN(batch)
+        dev = self.population.device
+        p = [self._flat(batch, "rew", torch.float64, (K, n_env)), self._flat(batch, "done", torch.uint8, (K, n_env)),
+             self._flat(batch, "val", torch.float32, (K, n_env)), self._flat(batch, "last_val", torch.float32, (n_env,))]
+        self._ws(K * self.envs_per_member, 1)
+        adv = torch.empty((K, n_env), dtype=torch.float32, device=dev)
+        ret = torch.empty_like(adv)
+        pop, h = self.population.to_native(), self.env._h
+        with torch.cuda.device(dev):
+            table = self._table(0)
+            N.check(N.lib().ssg_pop_gae(h, C.byref(pop), C.c_void_p(table.data_ptr()), K, *p, C.c_void_p(adv.data_ptr()),
+                                        C.c_void_p(ret.data_ptr()), C.c_void_p(self.workspace.data_ptr()), self.workspace.numel(),
+                                        self._stream()), h, "ssg_pop_gae")
+        batch["adv"], batch["ret"] = adv, ret
+        return adv, ret
+
+    def adv_stats(self):
+        """f32 [P, 3] device view: per member the advantage mean, std + adv_eps and its inverse, as the last gae() left them."""
+        return self.workspace[:16 * self.n_members].view(_torch().float32).view(self.n_members, 4)[:, :3]
+
+    def update(self, batch, perm, epochs, minibatches, stats=False):
+        """epochs x chunks of {gradient, Adam} for every member from ONE library call.  perm: int64 [P, epochs, K*n] — member m's
+        minibatches are perm[m, e].chunk(minibatches), indices into ITS samples (i = t*n + e).  stats=True returns f32
+        [P, epochs * chunks, 4] (the minibatch means of the pg loss, (v - ret)^2, the entropy and the clip fraction)."""
+        torch = _torch()
+        K, n_env = self._KN(batch)
+        P, dev, D = self.n_members, self.population.device, self.population.obs_dim
+        n = K * self.envs_per_member
+        p = [self._flat(batch, "obs", torch.float32, (K, n_env, D)), self._flat(batch, "act", torch.int32, (K, n_env)),
+             self._flat(batch, "logp", torch.float32, (K, n_env)), self._flat(batch, "adv", torch.float32, (K, n_env)),
+             self._flat(batch, "ret", torch.float32, (K, n_env))]
+        perm = perm.to(device=dev, dtype=torch.int64).contiguous()
+        if tuple(perm.shape) != (P, int(epochs), n):
+            raise ValueError("PopulationPPO.update: perm must be int64 [%d, %d, %d] (got %s)" % (P, int(epochs), n, tuple(perm.shape)))
+        chunk, n_chunks = chunk_split(n, minibatches)
+        steps = int(epochs) * n_chunks
+        self._ws(n, chunk)
+        st = torch.empty((P, steps, 4), dtype=torch.float32, device=dev) if stats else None
+        pop, h = self.population.to_native(), self.env._h
+        with torch.cuda.device(dev):
+            table = self._table(steps)
+            N.check(N.lib().ssg_pop_update(h, C.byref(pop), C.c_void_p(table.data_ptr()), steps, K, *p, C.c_void_p(perm.data_ptr()),
+                                           int(epochs), int(minibatches), C.c_void_p(self.adam_mv.data_ptr()),
+                                           C.c_void_p(st.data_ptr()) if stats else None, C.c_void_p(self.workspace.data_ptr()),
+                                           self.workspace.numel(), self._stream()), h, "ssg_pop_update")
+        self.step += steps
+        return st
+
+    def exploit(self, src):
+        """PBT's exploit on the device: member m takes the parameters and Adam moments of member src[m] (src[m] == m keeps).  A source
+        must not itself be a destination.  Hyper-parameters are the scheduler's business (PBTScheduler returns the new lists)."""
+        torch = _torch()
+        src = [int(s) for s in src]
+        if len(src) != self.n_members:
+            raise ValueError("PopulationPPO.exploit: src has %d entries for %d members" % (len(src), self.n_members))
+        arr = (C.c_int32 * len(src))(*src)
+        pop, h = self.population.to_native(), self.env._h
+        with torch.cuda.device(self.population.device):
+            N.check(N.lib().ssg_pop_exploit(h, C.byref(pop), arr, C.c_void_p(self.adam_mv.data_ptr()), self._stream()), h,
+                    "ssg_pop_exploit")
+
+    def reset_episode_carry(self):
+        """Forget the running episodes (call after an env reset)."""
+        self.carry_return.zero_()
+        self.carry_length.zero_()
+
+    def episode_stats(self, batch):
+        """int64 [P, 3] device tensor: per member (100 * sum of returns, sum of lengths, episodes) of the episodes that ENDED in this
+        rollout batch; episodes spanning batches are carried and counted once, at their end."""
+        torch = _torch()
+        K, n_env = self._KN(batch)
+        dev = self.population.device
+        rew, done = self._flat(batch, "rew", torch.float64, (K, n_env)), self._flat(batch, "done", torch.uint8, (K, n_env))
+        out = torch.zeros((self.n_members, 3), dtype=torch.int64, device=dev)
+        h = self.env._h
+        with torch.cuda.device(dev):
+            N.check(N.lib().ssg_pop_episode_stats(h, self.n_members, K, rew, done, C.c_void_p(self.carry_return.data_ptr()),
+                                                  C.c_void_p(self.carry_length.data_ptr()), C.c_void_p(out.data_ptr()), self._stream()),
+                    h, "ssg_pop_episode_stats")
+        return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# the scheduler (host only)
+# ------------------------------------------------------------------------------------------------------------------------------------
+LR_CHOICES = [1e-3, 5e-4, 1e-4, 5e-5, 1e-5]
+
+
+def reference_mutations():
+    """The three of the reference's six mutated hyper-parameters (train/rllib/pbt.py:34-41) that can vary per member here: a callable
+    draws a fresh value from the generator it is handed; a list is a set of choices.  (num_sgd_iter, sgd_minibatch_size and
+    train_batch_size shape the launches and stay common to the population.)"""
+    return {
+        "lambda": lambda rng: rng.uniform(0.9, 1.0),
+        "clip_param": lambda rng: rng.uniform(0.01, 0.5),
+        "lr": list(LR_CHOICES),
+    }
+
+
+class PBTScheduler(object):
+    """ray 0.6's PopulationBasedTraining as train/rllib/pbt.py:29-43 configures it, for a population that trains in lockstep.
+
+    Every `perturbation_interval` UPDATES (the reference counts 600 s of wall time; a lockstep population has no per-trial clock) the
+    members are ranked by score.  Each member of the bottom quantile (ceil(P * quantile_fraction), at most P // 2) picks a random member of the
+    top quantile as its source and takes that member's hyper-parameters, then explores: for each mutated key, with probability
+    `resample_probability` the value is redrawn from the key's generator / list; otherwise a continuous value is multiplied by 1.2 or
+    0.8 and a list-valued one steps to the neighbouring entry (staying at an end of the list, as ray clamps it; a value that is not in
+    the list is redrawn).  As in ray, a perturbed continuous value is not clamped to the generator's range.
+    """
+
+    def __init__(self, n_members, seed=0, perturbation_interval=1, quantile_fraction=0.25, resample_probability=0.33, mutations=None):
+        if n_members < 1:
+            raise ValueError("PBTScheduler: n_members must be >= 1")
+        if perturbation_interval < 1:
+            raise ValueError("PBTScheduler: perturbation_interval must be >= 1 (updates)")
+        if not 0.0 <= quantile_fraction <= 0.5:
+            raise ValueError("PBTScheduler: quantile_fraction must be in [0, 0.5]")
+        self.n_members, self.interval = int(n_members), int(perturbation_interval)
+        self.quantile_fraction, self.resample_probability = float(quantile_fraction), float(resample_probability)
+        self.mutations = reference_mutations() if mutations is None else dict(mutations)
+        self.rng = random.Random(seed)
+
+    def due(self, update):
+        """True after update number `update` (1, 2, ...) when a perturbation is due."""
+        return update > 0 and update % self.interval == 0
+
+    def quantiles(self, scores):
+        """(bottom, top): member indices of the lowest / highest scoring quantile (ties broken by index; disjoint)."""
+        order = sorted(range(self.n_members), key=lambda m: (scores[m], m))
+        if len(order) <= 1:
+            return [], []
+        k = int(math.ceil(len(order) * self.quantile_fraction))
+        k = min(k, len(order) // 2)
+        return (order[:k], order[-k:]) if k else ([], [])
+
+    def explore(self, values):
+        """One member's new {key: value} from its source's values; returns (new values, [(key, kind, old, new)])."""
+        new, log = dict(values), []
+        for key, dist in self.mutations.items():
+            old = values[key]
+            if isinstance(dist, list):
+                if self.rng.random() < self.resample_probability or old not in dist:
+                    new[key], kind = self.rng.choice(dist), "resample"
+                elif self.rng.random() > 0.5:
+                    new[key], kind = dist[max(0, dist.index(old) - 1)], "perturb"
+                else:
+                    new[key], kind = dist[min(len(dist) - 1, dist.index(old) + 1)], "perturb"
+            else:
+                if self.rng.random() < self.resample_probability:
+                    new[key], kind = dist(self.rng), "resample"
+                elif self.rng.random() > 0.5:
+                    new[key], kind = old * 1.2, "perturb"
+                else:
+                    new[key], kind = old * 0.8, "perturb"
+            log.append((key, kind, old, new[key]))
+        return new, log
+
+    def perturb(self, scores, hparams):
+        """scores: P numbers (higher is better); hparams: {key: list of P values} holding at least the mutated keys.  Returns
+        (src, new_hparams, events): src[m] = the member whose weights m takes (m itself = keep), for ``PopulationPPO.exploit``; the new
+        lists (copies; only destinations change); events = [{"member", "source", "mutations": [(key, kind, old, new)]}]."""
+        if len(scores) != self.n_members:
+            raise ValueError("PBTScheduler.perturb: %d scores for %d members" % (len(scores), self.n_members))
+        for key in self.mutations:
+            if key not in hparams or len(hparams[key]) != self.n_members:
+                raise ValueError("PBTScheduler.perturb: hparams[%r] must list %d values" % (key, self.n_members))
+        bottom, top = self.quantiles(scores)
+        src = list(range(self.n_members))
+        new = {k: list(v) for k, v in hparams.items()}
+        events = []
+        for m in bottom:
+            s = self.rng.choice(top)
+            values, log = self.explore({k: hparams[k][s] for k in self.mutations})
+            src[m] = s
+            for k in hparams:  # the source's whole configuration, then the explored keys
+                new[k][m] = values[k] if k in values else hparams[k][s]
+            events.append({"member": m, "source": s, "mutations": log})
+        return src, new, events

@@ -636,27 +636,78 @@ class ShipVecEnv(*_BASES):
         holding the observation after the last step, like K step_tensor calls."""
         torch = _torch()
         self._check_policy(policy, "rollout_policy")
-        K, n, D = int(K), self.num_envs, self.states_history
+        K, n = int(K), self.num_envs
         if K < 1:
             raise ValueError("rollout_policy: K must be >= 1")
         up = self._f32_rows(uniforms, (K, n), "rollout_policy uniforms") if uniforms is not None else None
-        specs = {"obs": ((K, n, D), torch.float32), "act": ((K, n), torch.int32), "logp": ((K, n), torch.float32),
-                 "val": ((K, n), torch.float32), "rew": ((K, n), torch.float64), "done": ((K, n), torch.uint8),
-                 "flags": ((K, n), torch.uint8), "last_val": ((n,), torch.float32)}
         with torch.cuda.device(self.device):
-            if out is None:
-                out = {k: torch.empty(s, dtype=dt, device=self.device) for k, (s, dt) in specs.items()}
-            for k, (s, dt) in specs.items():
-                t = out[k]
-                if (t.dtype != dt or t.device != self.device or not t.is_contiguous() or t.dim() != len(s) or t.shape[0] < s[0]
-                        or tuple(t.shape[1:]) != tuple(s[1:])):
-                    raise ValueError("rollout_policy: out[%r] must be a contiguous %s tensor %s on %s (got %s %s on %s)"
-                                     % (k, dt, s, self.device, t.dtype, tuple(t.shape), t.device))
+            out, p = self._rollout_buffers(K, out, "rollout_policy")
             pol = policy.to_native()
-            p = {k: C.c_void_p(out[k].data_ptr()) for k in specs}
             N.check(N.lib().ssg_rollout_policy(self._h, C.byref(pol), K, up, int(seed), int(step0), C.c_void_p(self.obs.data_ptr()),
                                                p["act"], p["logp"], p["val"], p["obs"], p["rew"], p["done"], p["flags"], p["last_val"],
                                                n, self._stream()), self._h, "ssg_rollout_policy")
+        return {k: (v[:K] if k != "last_val" else v) for k, v in out.items()}
+
+    def _rollout_buffers(self, K, out, what):
+        """The out-dict of a policy-in-the-loop rollout of K steps (allocated, or the caller's checked) and its tensors' C pointers."""
+        torch = _torch()
+        n, D = self.num_envs, self.states_history
+        specs = {"obs": ((K, n, D), torch.float32), "act": ((K, n), torch.int32), "logp": ((K, n), torch.float32),
+                 "val": ((K, n), torch.float32), "rew": ((K, n), torch.float64), "done": ((K, n), torch.uint8),
+                 "flags": ((K, n), torch.uint8), "last_val": ((n,), torch.float32)}
+        if out is None:
+            out = {k: torch.empty(s, dtype=dt, device=self.device) for k, (s, dt) in specs.items()}
+        for k, (s, dt) in specs.items():
+            t = out[k]
+            if (t.dtype != dt or t.device != self.device or not t.is_contiguous() or t.dim() != len(s) or t.shape[0] < s[0]
+                    or tuple(t.shape[1:]) != tuple(s[1:])):
+                raise ValueError("%s: out[%r] must be a contiguous %s tensor %s on %s (got %s %s on %s)"
+                                 % (what, k, dt, s, self.device, t.dtype, tuple(t.shape), t.device))
+        return out, {k: C.c_void_p(out[k].data_ptr()) for k in specs}
+
+    # ------------------------------------------------------------------------------------------------
+    # a population of policies on this handle (ssg_pop_act / ssg_pop_rollout; ship_sim_gym_amd/population.py)
+    # ------------------------------------------------------------------------------------------------
+    def _check_population(self, population, what):
+        self._check_policy(population, what)
+        if self.num_envs % len(population):
+            raise ValueError("%s: %d envs do not split into %d equal member slices" % (what, self.num_envs, len(population)))
+
+    def population_act(self, population, seed=0, step=0, uniforms=None, x_out=None):
+        """policy_act with env e evaluated under member e // (N / P) of a NativePopulation (ssg_pop_act, one launch): returns (act
+        int32 [N], logp [N], value [N], x [N, D] float32) device tensors.  uniforms / x_out / Philox keying as policy_act."""
+        torch = _torch()
+        self._check_population(population, "population_act")
+        n, D = self.num_envs, self.states_history
+        up = self._f32_rows(uniforms, (n,), "population_act uniforms") if uniforms is not None else None
+        with torch.cuda.device(self.device):
+            act = torch.empty(n, dtype=torch.int32, device=self.device)
+            logp = torch.empty(n, dtype=torch.float32, device=self.device)
+            val = torch.empty(n, dtype=torch.float32, device=self.device)
+            x = x_out if x_out is not None else torch.empty((n, D), dtype=torch.float32, device=self.device)
+            xp = self._f32_rows(x, (n, D), "population_act x_out")
+            pop = population.to_native()
+            N.check(N.lib().ssg_pop_act(self._h, C.byref(pop), C.c_void_p(self.obs.data_ptr()), up, int(seed), int(step),
+                                        C.c_void_p(act.data_ptr()), C.c_void_p(logp.data_ptr()), C.c_void_p(val.data_ptr()), xp,
+                                        self._stream()), self._h, "ssg_pop_act")
+        return act, logp, val, x
+
+    def rollout_population(self, population, K, seed=0, step0=0, uniforms=None, out=None):
+        """rollout_policy with env e acting under member e // (N / P) of a NativePopulation (ssg_pop_rollout: one policy launch per step
+        for the whole population, then ssg_step).  Same out-dict, uniforms, Philox keying and `out` as rollout_policy; member m's
+        columns are [m*n, (m+1)*n), n = N / P."""
+        torch = _torch()
+        self._check_population(population, "rollout_population")
+        K, n = int(K), self.num_envs
+        if K < 1:
+            raise ValueError("rollout_population: K must be >= 1")
+        up = self._f32_rows(uniforms, (K, n), "rollout_population uniforms") if uniforms is not None else None
+        with torch.cuda.device(self.device):
+            out, p = self._rollout_buffers(K, out, "rollout_population")
+            pop = population.to_native()
+            N.check(N.lib().ssg_pop_rollout(self._h, C.byref(pop), K, up, int(seed), int(step0), C.c_void_p(self.obs.data_ptr()),
+                                            p["act"], p["logp"], p["val"], p["obs"], p["rew"], p["done"], p["flags"], p["last_val"],
+                                            n, self._stream()), self._h, "ssg_pop_rollout")
         return {k: (v[:K] if k != "last_val" else v) for k, v in out.items()}
 
     def random_actions(self, seed, step0, K):

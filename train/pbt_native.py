@@ -1,0 +1,133 @@
+#!/usr/bin/env python3
+"""Population-based training of PPO on the MI355X batched env, entirely on the device: the counterpart of the reference's
+train/rllib/pbt.py (:29-43 the scheduler, :47-74 the experiment) that runs without ray — train/rllib_pbt.py is that script with its env
+line changed and needs ray; this one needs only the library.
+
+    python train/pbt_native.py --members 16 --envs-per-member 512 --updates 40 --horizon 32 --perturb-every 5 --seed 0
+    python train/pbt_native.py --lrs 1e-3,1e-4,1e-5 --no-pbt        # the learning-rate sweep of train/stable_baselines/ppo.py:118-137
+
+One ShipVecEnv of members x envs-per-member envs; member m owns the contiguous slice [m*n, (m+1)*n).  Every update is one
+``rollout_population`` (one policy launch per step for the whole population), then ``PopulationPPO.gae`` and ``.update`` (two launches
+per minibatch for the whole population), with per-member lambda / clip / learning rate.  Same game configuration as the reference's PBT
+(FPS 1000, SPEED 30, DEBUG off, BOUNDS 1000x1000), same initial lambda 0.95, clip 0.2, lr 5e-4, same scheduler semantics
+(ship_sim_gym_amd/population.py's PBTScheduler: bottom quarter exploits a random top-quarter member, resample probability 0.33, x1.2 /
+x0.8 or a neighbouring list entry otherwise) ranked by episode_reward_mean.
+
+What differs from the reference, on purpose:
+* --perturb-every counts UPDATES, not seconds of wall time (the reference perturbs every 600 s of a trial's own clock; a population
+  that trains in lockstep has no per-trial clock, and a count makes runs reproducible);
+* of the six mutated hyper-parameters only lambda, clip_param and lr vary per member: num_sgd_iter, sgd_minibatch_size and
+  train_batch_size shape the launches and are common to the population (--epochs, --minibatches, --horizon);
+* no kl_coeff (the device's PPO loss has no KL penalty), one handle on one GPU, one architecture.
+
+Logged per update: every member's episode_reward_mean (over the episodes that ended since the last perturbation); per perturbation:
+each exploit (member <- source) and each mutation (key, resample / perturb, old -> new).
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+INITIAL = {"lambda": 0.95, "clip_param": 0.2, "lr": 5e-4}  # train/rllib/pbt.py:60-62
+
+
+def make_arg_parser():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--members", type=int, default=16, help="population size (the reference: 120 samples)")
+    ap.add_argument("--envs-per-member", type=int, default=512)
+    ap.add_argument("--updates", type=int, default=40)
+    ap.add_argument("--horizon", type=int, default=32, help="rollout steps per update (common to the population)")
+    ap.add_argument("--perturb-every", type=int, default=5, help="perturbation interval in UPDATES (the reference: 600 s of wall time)")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--epochs", type=int, default=2)
+    ap.add_argument("--minibatches", type=int, default=4)
+    ap.add_argument("--lrs", default=None, help="comma-separated learning rates, one member each (overrides --members)")
+    ap.add_argument("--no-pbt", dest="pbt", action="store_false", help="no exploit / explore: a plain sweep")
+    ap.add_argument("--device", default="cuda:0")
+    return ap
+
+
+def parse_args(argv=None):
+    ap = make_arg_parser()
+    a = ap.parse_args(argv)
+    a.lrs = [float(x) for x in a.lrs.split(",")] if a.lrs else None
+    if a.lrs is not None:
+        a.members = len(a.lrs)
+    if a.members < 1 or a.envs_per_member < 1 or a.updates < 1 or a.horizon < 1 or a.perturb_every < 1:
+        ap.error("--members, --envs-per-member, --updates, --horizon and --perturb-every must be >= 1")
+    return a
+
+
+def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every=5, seed=0, epochs=2, minibatches=4, lrs=None,
+          pbt=True, device="cuda:0", log=print, return_details=False):
+    import torch
+    from ship_gym.config import EnvConfig, GameConfig
+    from ship_sim_gym_amd.population import NativePopulation, PBTScheduler, PopulationPPO
+    from ship_sim_gym_amd.vec_env import ShipVecEnv
+    from train.ppo_torch import ActorCritic
+    from train.rllib_ppo import game_configuration
+
+    P, n = int(members), int(envs_per_member)
+    if lrs is not None and len(lrs) != P:
+        raise ValueError("train: %d learning rates for %d members" % (len(lrs), P))
+    torch.manual_seed(seed)
+    dev = torch.device(device)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(seed + 1)
+    saved = {k: getattr(GameConfig, k) for k in ("FPS", "SPEED", "DEBUG", "BOUNDS")}
+    try:  # (game_configuration writes the GameConfig class, as the reference's does; the env reads it once, here)
+        env = ShipVecEnv(P * n, game_configuration(speed=30, fps=1000, debug=False), EnvConfig, device=device, n_maps=64)
+    finally:
+        for k, v in saved.items():
+            setattr(GameConfig, k, v)
+    D, A = env.states_history, env.action_space.n
+    nets = [ActorCritic(D, A).to(dev) for _ in range(P)]
+    scale = torch.full((D,), float(max(env.bounds)), dtype=torch.float64, device=dev)
+    pop = NativePopulation.from_actor_critics(nets, scale)
+    ppo = PopulationPPO(pop, env, lam=INITIAL["lambda"], clip=INITIAL["clip_param"], lr=list(lrs) if lrs is not None else INITIAL["lr"])
+    sched = PBTScheduler(P, seed=seed, perturbation_interval=perturb_every)
+    env.reset_tensor()
+    window = torch.zeros((P, 3), dtype=torch.int64, device=dev)  # episodes since the last perturbation
+    scores = [float("-inf")] * P
+    samples = horizon * n
+    out, history, exploits = None, [], []
+    for u in range(1, updates + 1):
+        uniforms = torch.rand((horizon, P * n), generator=gen, device=dev)
+        batch = env.rollout_population(pop, horizon, uniforms=uniforms, out=out)
+        out = {k: v for k, v in batch.items() if k not in ("adv", "ret")}
+        window += ppo.episode_stats(batch)
+        ppo.gae(batch)
+        perm = torch.rand((P, epochs, samples), generator=gen, device=dev).argsort(dim=-1)
+        ppo.update(batch, perm, epochs, minibatches)
+        w = window.cpu().tolist()
+        scores = [w[m][0] / 100.0 / w[m][2] if w[m][2] else scores[m] for m in range(P)]
+        history.append(list(scores))
+        log("update %d  episode_reward_mean %s" % (u, " ".join("%d:%.3f" % (m, s) for m, s in enumerate(scores))))
+        if pbt and sched.due(u):
+            src, new, events = sched.perturb(scores, {"lambda": ppo.lam, "clip_param": ppo.clip, "lr": ppo.lr})
+            ppo.exploit(src)
+            ppo.lam, ppo.clip, ppo.lr = new["lambda"], new["clip_param"], new["lr"]
+            for ev in events:
+                log("update %d  exploit: member %d <- member %d" % (u, ev["member"], ev["source"]))
+                for key, kind, old, val in ev["mutations"]:
+                    log("update %d  mutation: member %d %s %s %.6g -> %.6g" % (u, ev["member"], key, kind, old, val))
+                scores[ev["member"]] = scores[ev["source"]]
+            exploits += events
+            window.zero_()
+    torch.cuda.synchronize(dev)
+    pop.load_into(nets)
+    details = {"params": pop.params.detach().clone(), "exploits": exploits, "nets": nets,
+               "hparams": {"lambda": list(ppo.lam), "clip_param": list(ppo.clip), "lr": list(ppo.lr)}}
+    env.close()
+    return (history, details) if return_details else history
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    train(members=a.members, envs_per_member=a.envs_per_member, updates=a.updates, horizon=a.horizon, perturb_every=a.perturb_every,
+          seed=a.seed, epochs=a.epochs, minibatches=a.minibatches, lrs=a.lrs, pbt=a.pbt, device=a.device)
+
+
+if __name__ == "__main__":
+    main()

@@ -4,7 +4,9 @@ train/rllib/pbt.py (:14-72) with the env-construction line changed as in train/r
 per rollout worker instead of one `ShipEnv` per worker).  Same game configuration (FPS 1000, SPEED 30, BOUNDS 1000x1000),
 same scheduler (perturb every 600 s of training time on episode_reward_mean, resample 0.33, the six mutated
 hyper-parameters with the reference's ranges), same experiment (120 samples, kl_coeff 1.0, lambda 0.95, clip 0.2, lr 5e-4,
-randomly drawn num_sgd_iter / minibatch / train batch).  ray is not part of this image: imports are guarded."""
+randomly drawn num_sgd_iter / minibatch / train batch).  ray is not part of this image: imports are guarded, and this script stops at
+`import ray`.  train/pbt_native.py is the version that runs here: the same population-based training with every member's rollout, GAE
+and update on the device (ship_sim_gym_amd/population.py), no ray needed."""
 import argparse
 import os
 import random
