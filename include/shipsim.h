@@ -317,7 +317,13 @@ int ssg_fill_actions(ssg_handle *h, uint64_t seed, uint64_t step0, int K, int32_
  * seed-compatible with the reference's Mersenne-Twister draws: a separate mode for refreshing the bank without the
  * host.  dev_raw (nullable): per map 48 + 3*n_goals doubles = the raw 2x12 polygon vertices, then per goal (y, the
  * uniform draw u, the fallback x), so a test can rebuild every record on the host and compare bit for bit.
- * Call ssg_set_map_bank afterwards (or pass the already-installed bank pointer to refresh it in place). */
+ * Call ssg_set_map_bank afterwards (or pass the already-installed bank pointer to refresh it in place).
+ * width_frac in (0, 1].  THE LAW of the draws is the reference's for width_frac * width >= 6.85: a bank vertex's x is
+ * the half-normal x_max - |gauss(0, 50)| cut at the strip's inner edge, which is what gen_river_poly's redrawn two-sided
+ * gauss(x_max, 50) comes to as long as its 1000-try cap is out of reach (at that bound a vertex reaches the cap with
+ * probability (1 - q)^999 = 1e-12, q = Phi(width_frac * width / 100) - 1/2).  BELOW that bound the device's law is NOT
+ * the reference's: a device try passes with 2q, so it reaches the cap with (1 - 2q)^999 only, and a vertex kept at the
+ * cap is folded (never above x_max) where the reference's is not.  Nothing is refused there. */
 int ssg_generate_bank(ssg_handle *h, uint64_t seed, double width_frac, double *dev_bank, int n_maps, double *dev_raw,
                       void *stream);
 
@@ -329,7 +335,9 @@ int ssg_generate_bank(ssg_handle *h, uint64_t seed, double width_frac, double *d
  * rings and fixes seed / width_frac for the automatic refills ssg_reset / ssg_step / ssg_rollout issue afterwards).
  * dev_raw (nullable): [n_envs * R][48 + 3*n_goals] doubles, row e*R + slot receives the raw polygons and goal draws of the
  * world generated into that slot by THIS call (rows of slots not regenerated are left untouched), so a test can rebuild
- * the records on the host and compare bit for bit.  NOT seed-compatible with the reference's Mersenne-Twister draws. */
+ * the records on the host and compare bit for bit.  NOT seed-compatible with the reference's Mersenne-Twister draws.
+ * width_frac in (0, 1]; as for ssg_generate_bank, below width_frac * width = 6.85 (where a vertex reaches the reference's
+ * 1000-try cap with probability above 1e-12) the device's law of the bank vertices is NOT the reference's. */
 int ssg_refill_worlds(ssg_handle *h, uint64_t seed, double width_frac, double *dev_raw, void *stream);
 
 /* Config 4 only; no reference counterpart (writing `ship.body.position` on a pymunk body, game.py:117-131, needs no
