@@ -545,6 +545,75 @@ int ssg_ppo_update(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *
                    void *dev_workspace, size_t workspace_nbytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The extended PPO update (additions to ABI 9): value clipping, a KL penalty, gradient-norm clipping
+ * What the reference trainers' own PPO adds to the loss above.  train/stable_baselines/ppo.py builds PPO2 with its defaults: the value
+ * loss clipped around the rollout's value prediction (cliprange) and the gradients through clip_by_global_norm(0.5);
+ * train/rllib/pbt.py:55-62 sets kl_coeff = 1.0: RLlib's PPO adds kl_coeff * KL(old || new), adapts the coefficient after every update
+ * against kl_target and clips the value loss (vf_clip_param).  Every term is opt-in; with all of them off the _ext entry points compute
+ * bit for bit what the plain ones compute.
+ *
+ * Loss, per minibatch of M samples, with the symbols above (v_old = the rollout's value, logp_old = the acting policy's whole
+ * log-distribution from ssg_ppo_dist, p_old = exp(logp_old)):
+ *   loss = pg + vf_coef*mean(VL) - ent_coef*mean(entropy(p)) + kl_coef*mean(KL)
+ *   KL = sum_{j<A} p_old[j] * (logp_old[j] - logp[j])
+ *   VL = (v - ret)^2                                                              when vf_clip <= 0
+ *      = max((v - ret)^2, (v_old + clamp(v - v_old, -vf_clip, vf_clip) - ret)^2)   otherwise
+ * (PPO2's factor 0.5 on the value loss is the caller's vf_coef.)  The gradient follows autograd: max passes the gradient to the larger
+ * side and half to each on a tie, clamp passes it inside [-vf_clip, vf_clip] inclusive, and the KL term's gradient with respect to
+ * logit j is p[j]*sum(p_old) - p_old[j].  A KL coefficient of 0 is "no KL term" (mean(KL) is then reported as 0).
+ *
+ * Gradient-norm clipping (max_grad_norm > 0): a minibatch takes three launches instead of two — the gradient kernel; the slot
+ * reduction into a gradient vector in the workspace plus per-workgroup sums of squares (f64, a fixed tree); a launch in which every
+ * workgroup adds those partials in index order and forms in f32 norm = (float)sqrt(sum), coef = min(1, max_grad_norm / (norm + 1e-6f))
+ * (torch.nn.utils.clip_grad_norm_), then Adam on g * coef.
+ *
+ * The coefficient's adaptation (kl_target > 0; RLlib's update_kl): the last launch of an _ext update takes the f32 mean of mean(KL)
+ * over the last epoch's minibatches (a running f32 sum in chunk order, kept in the workspace, divided by the number of chunks) and
+ * multiplies *dev_kl_coef by 1.5 when that mean is above 2*kl_target, by 0.5 when it is below 0.5*kl_target.
+ *
+ * Stats rows of the _ext entry points are f32[8]: [0..3] as above with [1] = mean(VL), [4] mean(KL), [5] the global gradient norm
+ * before clipping (0 when max_grad_norm is off), [6] the KL coefficient the minibatch used, [7] 0.  No floating-point atomics; a
+ * gradient stays bitwise reproducible for a given M.  The workspace is ssg_ppo_workspace_nbytes' / ssg_pop_workspace_nbytes', which
+ * cover the _ext calls.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct ssg_ppo_ext {
+    uint32_t struct_size;       /* sizeof(ssg_ppo_ext) */
+    double vf_clip;             /* value clip range; <= 0 = off */
+    double max_grad_norm;       /* global gradient-norm clip; <= 0 = off */
+    double kl_target;           /* <= 0 = the coefficient is never adapted */
+    float *dev_kl_coef;         /* f32[1] on the device; NULL = no KL term */
+    const float *dev_logp_all;  /* f32 [n_samples][4] (ssg_ppo_dist); required when dev_kl_coef is given */
+    const float *dev_value_old; /* f32 [n_samples] (the rollout's dev_value_KN); required when vf_clip > 0 */
+} ssg_ppo_ext;
+
+/* Replaces: the old policy's action distribution that RLlib's PPO keeps in its sample batch for the KL term (train/rllib/pbt.py:55-62,
+ * kl_coeff) — the rollout stores only logp[act].  The policy forward of ssg_policy_act over the stored normalised rows dev_x (f32
+ * [n_samples][obs_dim], what ssg_rollout_policy wrote): dev_logp_all[i][j] = logit_j - lse for j < n_actions, 0 for the columns up to 4.
+ * The same device code as the acting forward: called with the pre-update parameters, dev_logp_all[i][act[i]] is the rollout's logp[i]
+ * bit for bit.  One launch.  SSG_ERR_BAD_ARG (nothing launched) for a bad record, NULL pointers or n_samples outside 1..2^31-1. */
+int ssg_ppo_dist(ssg_handle *h, const ssg_policy *pol, int64_t n_samples, const float *dev_x, float *dev_logp_all, void *stream);
+
+/* Replaces: one minibatch of the reference trainers' update without the optimiser step, with their loss terms
+ * (train/stable_baselines/ppo.py:90; train/rllib/pbt.py:47-74).  ssg_ppo_grad with the extended loss; dev_grad is the UNCLIPPED
+ * gradient, dev_stats (nullable) f32[8] with the norm in [5] when max_grad_norm > 0 (three launches then, two otherwise).  The
+ * coefficient is not adapted.  Refusals as ssg_ppo_grad, plus a bad ssg_ppo_ext record or a missing pointer that a switched-on term
+ * needs: SSG_ERR_BAD_ARG, nothing launched. */
+int ssg_ppo_grad_ext(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, const ssg_ppo_ext *ext, int64_t n_samples,
+                     const float *dev_x, const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret,
+                     const int64_t *dev_idx, int64_t M, float *dev_grad, float *dev_stats /* nullable */, void *dev_workspace,
+                     size_t workspace_nbytes, void *stream);
+
+/* Replaces: the whole update of those trainers (PPO2's noptepochs x nminibatches with clipped value loss and clip_by_global_norm,
+ * train/stable_baselines/ppo.py:90; RLlib's SGD phase with the KL penalty and update_kl, train/rllib/pbt.py:47-74).  ssg_ppo_update
+ * with the extended loss: per minibatch two launches, three with max_grad_norm > 0, and with kl_target > 0 and a coefficient one
+ * more launch at the end (the adaptation).  dev_stats (nullable): f32 [epochs*chunks][8].  Refusals as ssg_ppo_update and
+ * ssg_ppo_grad_ext. */
+int ssg_ppo_update_ext(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, const ssg_ppo_ext *ext, int64_t n_samples,
+                       const float *dev_x, const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret,
+                       const int64_t *dev_perm, int epochs, int minibatches, float *dev_adam_mv, int64_t step0,
+                       float *dev_stats /* nullable */, void *dev_workspace, size_t workspace_nbytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * A population of policies on one handle (additions to ABI 9)
  * Both reference trainers train populations: train/rllib/pbt.py:29-74 runs 120 PPO trials under PopulationBasedTraining,
  * train/stable_baselines/ppo.py:118-137 three PPO2 models, one per learning rate.  Here P members share every launch of the rollout,
@@ -568,8 +637,9 @@ int ssg_ppo_update(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *
  *
  * Workspace: ssg_pop_workspace_nbytes bytes, 256-byte aligned; ssg_pop_gae leaves f32 [P][4] advantage statistics (mean, std + adv_eps,
  * its inverse, 0) at its start, per member over that member's K*n samples, which ssg_pop_update reads.  dev_adam_mv: f32 [P][2L].
- * Out of scope: per-member epochs / minibatch sizes / batch sizes (they change launch shapes), a KL penalty, populations spanning
- * handles or GPUs, per-member architectures.
+ * The extended loss terms are per member too (ssg_pop_update_ext below).  Out of scope: per-member epochs / minibatch sizes / batch
+ * sizes (they change launch shapes), PPO2's per-minibatch advantage normalisation, populations spanning handles or GPUs, per-member
+ * architectures.
  * ------------------------------------------------------------------------------------------------- */
 #define SSG_POP_MAX_MEMBERS 256
 #define SSG_POP_TABLE_FLOATS(n_members, n_steps) ((size_t)(n_members) * 8u * (size_t)(1 + (n_steps)))
@@ -635,6 +705,37 @@ int ssg_pop_update(ssg_handle *h, const ssg_population *pop, const float *dev_ta
                    const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret, const int64_t *dev_perm,
                    int epochs, int minibatches, float *dev_adam_mv, float *dev_stats /* nullable */, void *dev_workspace,
                    size_t workspace_nbytes, void *stream);
+
+/* The extended update for a population.  The per-member constants are read on the device, like dev_table: dev_ext is f32
+ * [P][4] = per member vf_clip, max_grad_norm, kl_target, 0 (the caller rounds them from double); an entry <= 0 switches that term off
+ * for that member.  What changes the launch sequence or needs a buffer the host must know, so flags says it: */
+#define SSG_POP_EXT_GRAD_CLIP 0x1u /* some member has max_grad_norm > 0: the three-launch sequence runs for the population */
+#define SSG_POP_EXT_VF_CLIP 0x2u   /* some member has vf_clip > 0: dev_value_old is required */
+typedef struct ssg_pop_ext {
+    uint32_t struct_size;       /* sizeof(ssg_pop_ext) */
+    uint32_t flags;             /* SSG_POP_EXT_* */
+    const float *dev_ext;       /* f32 [P][4] */
+    float *dev_kl_coef;         /* f32 [P]; NULL = no KL term for anyone (a member's 0 = none for that member) */
+    const float *dev_logp_all;  /* f32 [K][N][4] (ssg_pop_dist); required when dev_kl_coef is given */
+    const float *dev_value_old; /* f32 [K][N]; required with SSG_POP_EXT_VF_CLIP */
+} ssg_pop_ext;
+
+/* Replaces: the old action distributions every RLlib trial keeps for its KL term (train/rllib/pbt.py:47-74).  ssg_ppo_dist for a
+ * population over the [K][N] rows of dev_x: row t*N + m*n + e runs under parameter row m.  One launch for all members.
+ * SSG_ERR_BAD_ARG (nothing launched) for a bad record, NULL pointers or K outside 1..65535. */
+int ssg_pop_dist(ssg_handle *h, const ssg_population *pop, int K, const float *dev_x, float *dev_logp_all, void *stream);
+
+/* Replaces: the SGD phase of every trial with RLlib's loss (train/rllib/pbt.py:47-74, kl_coeff = 1.0 at :55-62) or PPO2's
+ * (train/stable_baselines/ppo.py:118-137).  ssg_pop_update with the extended loss per member.  With SSG_POP_EXT_GRAD_CLIP every
+ * minibatch takes three launches; members with max_grad_norm <= 0 then get coef = 1.0f, which is exact.  The last launch adapts the
+ * coefficients of the members whose kl_target is > 0 (when dev_kl_coef is given).  dev_stats (nullable): f32 [P][epochs*chunks][8].
+ * Member m's parameters, moments, stats rows and coefficient are bitwise those of ssg_ppo_update_ext on its slice alone with its
+ * constants (of ssg_ppo_update when all its terms are off).  Refusals as ssg_pop_update, plus a bad ssg_pop_ext record or a missing
+ * pointer that a switched-on term needs. */
+int ssg_pop_update_ext(ssg_handle *h, const ssg_population *pop, const ssg_pop_ext *ext, const float *dev_table, int table_steps, int K,
+                       const float *dev_x, const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret,
+                       const int64_t *dev_perm, int epochs, int minibatches, float *dev_adam_mv, float *dev_stats /* nullable */,
+                       void *dev_workspace, size_t workspace_nbytes, void *stream);
 
 /* Replaces: PopulationBasedTraining's exploit step (train/rllib/pbt.py:29-43: a bottom-quantile trial restores a top-quantile trial's
  * checkpoint), on the device: member m takes the parameter row AND the Adam moments of member src[m] (host array int32 [P];

@@ -18,6 +18,8 @@ FLAG_AUTO_RESET, FLAG_FIX_COLLISION_REWARD, FLAG_BANK_IN_GLOBAL, FLAG_EXACT_LIDA
 EV_COLLIDING, EV_GOAL_REACHED, EV_OUT_OF_BOUNDS, EV_MAX_STEPS, EV_NO_GOALS_LEFT = 0x1, 0x2, 0x4, 0x8, 0x10
 POLICY_MAX_HIDDEN, POLICY_TANH, POLICY_RELU = 128, 0, 1
 POP_MAX_MEMBERS = 256
+POP_EXT_GRAD_CLIP, POP_EXT_VF_CLIP = 0x1, 0x2
+PPO_EXT_STATS = 8  # stats columns of the _ext entry points
 
 
 def pop_table_floats(n_members, n_steps):
@@ -42,6 +44,7 @@ EXPORTS = (
     "ssg_ppo_workspace_nbytes", "ssg_ppo_gae", "ssg_ppo_grad", "ssg_ppo_adam", "ssg_ppo_update",
     "ssg_pop_act", "ssg_pop_rollout", "ssg_pop_pack_hparams", "ssg_pop_workspace_nbytes", "ssg_pop_gae", "ssg_pop_update",
     "ssg_pop_exploit", "ssg_pop_episode_stats",
+    "ssg_ppo_dist", "ssg_ppo_grad_ext", "ssg_ppo_update_ext", "ssg_pop_dist", "ssg_pop_update_ext",
 )
 
 
@@ -88,6 +91,22 @@ class Population(C.Structure):
         ("struct_size", C.c_uint32), ("n_members", C.c_int32), ("obs_dim", C.c_int32), ("hidden", C.c_int32),
         ("n_hidden_layers", C.c_int32), ("n_actions", C.c_int32), ("activation", C.c_int32), ("reserved", C.c_int32),
         ("dev_params", C.c_void_p), ("dev_obs_scale", C.c_void_p),
+    ]
+
+
+class PpoExt(C.Structure):
+    """ssg_ppo_ext (ABI 9 addition): the value clip, gradient-norm clip and KL penalty of the extended PPO update."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("vf_clip", C.c_double), ("max_grad_norm", C.c_double), ("kl_target", C.c_double),
+        ("dev_kl_coef", C.c_void_p), ("dev_logp_all", C.c_void_p), ("dev_value_old", C.c_void_p),
+    ]
+
+
+class PopExt(C.Structure):
+    """ssg_pop_ext (ABI 9 addition): the extended update's per-member constants (dev_ext f32 [P][4]) and buffers."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("flags", C.c_uint32), ("dev_ext", C.c_void_p), ("dev_kl_coef", C.c_void_p),
+        ("dev_logp_all", C.c_void_p), ("dev_value_old", C.c_void_p),
     ]
 
 
@@ -160,6 +179,13 @@ def lib():
     L.ssg_pop_update.argtypes = [vp, pp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_size_t, vp]
     L.ssg_pop_exploit.argtypes = [vp, pp, i32p, vp, vp]
     L.ssg_pop_episode_stats.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
+    xp, qp = C.POINTER(PpoExt), C.POINTER(PopExt)
+    L.ssg_ppo_dist.argtypes = [vp, C.POINTER(Policy), C.c_int64, vp, vp, vp]
+    L.ssg_ppo_grad_ext.argtypes = [vp, C.POINTER(Policy), hp, xp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, C.c_size_t, vp]
+    L.ssg_ppo_update_ext.argtypes = [vp, C.POINTER(Policy), hp, xp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int64, vp,
+                                     vp, C.c_size_t, vp]
+    L.ssg_pop_dist.argtypes = [vp, pp, C.c_int, vp, vp, vp]
+    L.ssg_pop_update_ext.argtypes = [vp, pp, qp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_size_t, vp]
     L.ssg_render.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, vp]
     L.ssg_dyn_invalidate.argtypes = [vp, vp, vp]
     L.ssg_host_convex_hull.argtypes = [C.c_int, dp, dp, ip]

@@ -1087,6 +1087,12 @@ static size_t ppo_need_grad(const ssg_policy &p, long long M)
     return ssg::kPpoSlotsOff + (size_t)ssg::ppo_grid(M) * (size_t)(ssg::ppo_packed_len(p) + 4) * sizeof(float);
 }
 
+// the extended update's workspace (slots of P + kExtStats floats behind the clip sequence's vector, partials and the KL sum)
+static size_t ppo_need_grad_ext(const ssg_policy &p, long long M)
+{
+    return ssg::ppo_ext_layout(ssg::kPpoSlotsOff, 1, ssg::ppo_grid(M), ssg::ppo_packed_len(p)).end;
+}
+
 static int check_workspace(ssg_handle *h, const void *ws, size_t nbytes, size_t need, const char *what)
 {
     const std::string w(what);
@@ -1113,7 +1119,7 @@ int ssg_ppo_workspace_nbytes(const ssg_policy *pol, int64_t n_samples, int64_t m
 {
     if (!nbytes || !check_policy_shape(pol) || n_samples < 1 || max_minibatch < 1)
         return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_ppo_workspace_nbytes: bad policy record, NULL nbytes or a size < 1");
-    *nbytes = std::max(ppo_need_gae(n_samples), ppo_need_grad(*pol, max_minibatch));
+    *nbytes = std::max(ppo_need_gae(n_samples), std::max(ppo_need_grad(*pol, max_minibatch), ppo_need_grad_ext(*pol, max_minibatch)));
     return SSG_OK;
 }
 
@@ -1260,6 +1266,110 @@ static int check_population(ssg_handle *h, const ssg_population *pop, const char
     return check_policy(h, &p, what);
 }
 
+// ABI 9 additions: the extended update.  Order of the refusals as for a population: no handle (BAD_ARG), no state blob (NOT_BOUND),
+// everything the host can judge (BAD_ARG), and only then the device.
+static int check_ext(ssg_handle *h, const ssg_ppo_ext *ext, const char *what)
+{
+    const std::string w(what);
+    if (!ext) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL ssg_ppo_ext");
+    if (ext->struct_size != sizeof(ssg_ppo_ext)) return fail(h, SSG_ERR_BAD_ARG, w + ": ssg_ppo_ext.struct_size != sizeof(ssg_ppo_ext)");
+    if (!std::isfinite(ext->vf_clip) || !std::isfinite(ext->max_grad_norm) || !std::isfinite(ext->kl_target))
+        return fail(h, SSG_ERR_BAD_ARG, w + ": vf_clip, max_grad_norm or kl_target is not finite");
+    if (ext->dev_kl_coef && !ext->dev_logp_all) return fail(h, SSG_ERR_BAD_ARG, w + ": dev_kl_coef without dev_logp_all (ssg_ppo_dist)");
+    if (ext->vf_clip > 0.0 && !ext->dev_value_old) return fail(h, SSG_ERR_BAD_ARG, w + ": vf_clip > 0 without dev_value_old");
+    return SSG_OK;
+}
+
+static ssg::PpoExtLaunch ext_launch(const ssg_ppo_ext &ext)
+{
+    ssg::PpoExtLaunch e;
+    e.kl_coef = ext.dev_kl_coef;
+    e.logp_all = ext.dev_kl_coef ? ext.dev_logp_all : nullptr;
+    e.vf_clip = ext.vf_clip > 0.0 ? (float)ext.vf_clip : 0.0f;
+    e.value_old = ext.vf_clip > 0.0 ? ext.dev_value_old : nullptr;
+    e.max_grad_norm = ext.max_grad_norm > 0.0 ? (float)ext.max_grad_norm : 0.0f;
+    e.clip_seq = ext.max_grad_norm > 0.0;
+    e.pop_ext = nullptr;
+    e.first_chunk = true;
+    return e;
+}
+
+int ssg_ppo_dist(ssg_handle *h, const ssg_policy *pol, int64_t n_samples, const float *dev_x, float *dev_logp_all, void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc == SSG_OK) rc = check_policy(h, pol, "ssg_ppo_dist");
+    if (rc != SSG_OK) return rc;
+    if (!dev_x || !dev_logp_all) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_dist: NULL dev_x or dev_logp_all");
+    if (n_samples < 1 || n_samples > 0x7fffffffll) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_dist: n_samples must be in 1..2^31-1");
+    rc = check_ready(h, false);
+    if (rc == SSG_OK) rc = prepare_policy(h);
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_policy_dist(*pol, 1, (int)n_samples, n_samples, 1, dev_x, dev_logp_all, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("policy dist launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+int ssg_ppo_grad_ext(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, const ssg_ppo_ext *ext, int64_t n_samples,
+                     const float *dev_x, const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret,
+                     const int64_t *dev_idx, int64_t M, float *dev_grad, float *dev_stats, void *dev_workspace, size_t workspace_nbytes,
+                     void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc == SSG_OK) rc = check_policy(h, pol, "ssg_ppo_grad_ext");
+    if (rc == SSG_OK) rc = check_hparams(h, hp, "ssg_ppo_grad_ext");
+    if (rc == SSG_OK) rc = check_ext(h, ext, "ssg_ppo_grad_ext");
+    if (rc == SSG_OK) rc = check_batch(h, n_samples, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_idx, "ssg_ppo_grad_ext");
+    if (rc != SSG_OK) return rc;
+    if (!dev_grad) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_grad_ext: NULL dev_grad");
+    if (M < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_grad_ext: M < 1");
+    rc = check_workspace(h, dev_workspace, workspace_nbytes, ppo_need_grad_ext(*pol, M), "ssg_ppo_grad_ext");
+    if (rc == SSG_OK) rc = check_ready(h, false);
+    if (rc == SSG_OK) rc = prepare_ppo(h);
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_ppo_grad_ext(*pol, *hp, ext_launch(*ext), n_samples, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_idx, M,
+                                            dev_workspace, dev_grad, dev_stats, nullptr, 0, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("ppo grad_ext launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+int ssg_ppo_update_ext(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, const ssg_ppo_ext *ext, int64_t n_samples,
+                       const float *dev_x, const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret,
+                       const int64_t *dev_perm, int epochs, int minibatches, float *dev_adam_mv, int64_t step0, float *dev_stats,
+                       void *dev_workspace, size_t workspace_nbytes, void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc == SSG_OK) rc = check_policy(h, pol, "ssg_ppo_update_ext");
+    if (rc == SSG_OK) rc = check_hparams(h, hp, "ssg_ppo_update_ext");
+    if (rc == SSG_OK) rc = check_ext(h, ext, "ssg_ppo_update_ext");
+    if (rc == SSG_OK) rc = check_batch(h, n_samples, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_perm, "ssg_ppo_update_ext");
+    if (rc != SSG_OK) return rc;
+    if (!dev_adam_mv) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_update_ext: NULL dev_adam_mv");
+    if (epochs < 1 || minibatches < 1 || step0 < 0) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_update_ext: epochs < 1, minibatches < 1 or step0 < 0");
+    const long long n = n_samples, C = (n + minibatches - 1) / minibatches, chunks = (n + C - 1) / C; // torch.chunk
+    rc = check_workspace(h, dev_workspace, workspace_nbytes, ppo_need_grad_ext(*pol, C), "ssg_ppo_update_ext");
+    if (rc == SSG_OK) rc = check_ready(h, false);
+    if (rc == SSG_OK) rc = prepare_ppo(h);
+    if (rc != SSG_OK) return rc;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    ssg::PpoExtLaunch el = ext_launch(*ext);
+    int64_t step = step0, j = 0;
+    for (int ep = 0; ep < epochs; ++ep) {
+        for (long long b0 = 0; b0 < n; b0 += C, ++j) {
+            const long long M = std::min(C, n - b0);
+            el.first_chunk = b0 == 0;
+            hipError_t e = ssg::launch_ppo_grad_ext(*pol, *hp, el, n_samples, dev_x, dev_act, dev_logp, dev_adv, dev_ret,
+                                                    dev_perm + (size_t)ep * (size_t)n + (size_t)b0, M, dev_workspace, nullptr,
+                                                    dev_stats ? dev_stats + ssg::kExtStats * j : nullptr, dev_adam_mv, ++step, st);
+            if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("ppo update_ext launch: ") + hipGetErrorString(e));
+        }
+    }
+    if (ext->kl_target > 0.0 && ext->dev_kl_coef) {
+        hipError_t e = ssg::launch_kl_adapt(1, el, (float)ext->kl_target, ssg::ppo_packed_len(*pol), chunks, dev_workspace, ssg::kPpoSlotsOff, st);
+        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("kl adapt launch: ") + hipGetErrorString(e));
+    }
+    return SSG_OK;
+}
+
 int ssg_pop_act(ssg_handle *h, const ssg_population *pop, const double *dev_obs, const float *dev_uniform, uint64_t seed, int64_t step,
                 int32_t *dev_actions, float *dev_logp, float *dev_value, float *dev_x, void *stream)
 {
@@ -1340,11 +1450,18 @@ static size_t pop_need_grad(const ssg_policy &p, int P, long long M)
     return ssg::kPopSlotsOff + (size_t)P * (size_t)ssg::ppo_grid(M) * (size_t)(ssg::ppo_packed_len(p) + 4) * sizeof(float);
 }
 
+static size_t pop_need_grad_ext(const ssg_policy &p, int P, long long M)
+{
+    return ssg::ppo_ext_layout(ssg::kPopSlotsOff, P, ssg::ppo_grid(M), ssg::ppo_packed_len(p)).end;
+}
+
 int ssg_pop_workspace_nbytes(const ssg_population *pop, int64_t samples_per_member, int64_t max_minibatch, size_t *nbytes)
 {
     if (!nbytes || !pop_shape_ok(pop) || samples_per_member < 1 || max_minibatch < 1)
         return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_workspace_nbytes: bad population record, n_members out of range, NULL nbytes or a size < 1");
-    *nbytes = std::max(pop_need_gae(pop->n_members, samples_per_member), pop_need_grad(pop_policy(*pop), pop->n_members, max_minibatch));
+    *nbytes = std::max(pop_need_gae(pop->n_members, samples_per_member),
+                       std::max(pop_need_grad(pop_policy(*pop), pop->n_members, max_minibatch),
+                                pop_need_grad_ext(pop_policy(*pop), pop->n_members, max_minibatch)));
     return SSG_OK;
 }
 
@@ -1402,6 +1519,81 @@ int ssg_pop_update(ssg_handle *h, const ssg_population *pop, const float *dev_ta
                                                 4 * (long long)epochs * chunks, dev_adam_mv, st);
             if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population update launch: ") + hipGetErrorString(e));
         }
+    }
+    return SSG_OK;
+}
+
+int ssg_pop_dist(ssg_handle *h, const ssg_population *pop, int K, const float *dev_x, float *dev_logp_all, void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_dist");
+    if (rc != SSG_OK) return rc;
+    if (!dev_x || !dev_logp_all) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_dist: NULL dev_x or dev_logp_all");
+    if (K < 1 || K > 65535) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_dist: K must be in 1..65535");
+    rc = check_ready(h, false);
+    if (rc == SSG_OK) rc = prepare_policy(h);
+    if (rc != SSG_OK) return rc;
+    const int P = pop->n_members, N = h->cfg.n_envs;
+    hipError_t e = ssg::launch_policy_dist(pop_policy(*pop), P, N / P, N, K, dev_x, dev_logp_all, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population dist launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+int ssg_pop_update_ext(ssg_handle *h, const ssg_population *pop, const ssg_pop_ext *ext, const float *dev_table, int table_steps, int K,
+                       const float *dev_x, const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret,
+                       const int64_t *dev_perm, int epochs, int minibatches, float *dev_adam_mv, float *dev_stats, void *dev_workspace,
+                       size_t workspace_nbytes, void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_update_ext");
+    if (rc != SSG_OK) return rc;
+    if (!ext) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: NULL ssg_pop_ext");
+    if (ext->struct_size != sizeof(ssg_pop_ext)) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: ssg_pop_ext.struct_size != sizeof(ssg_pop_ext)");
+    if (ext->flags & ~(SSG_POP_EXT_GRAD_CLIP | SSG_POP_EXT_VF_CLIP)) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: unknown ssg_pop_ext.flags bits");
+    if (!ext->dev_ext) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: NULL dev_ext");
+    if (ext->dev_kl_coef && !ext->dev_logp_all) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: dev_kl_coef without dev_logp_all (ssg_pop_dist)");
+    if ((ext->flags & SSG_POP_EXT_VF_CLIP) && !ext->dev_value_old)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: SSG_POP_EXT_VF_CLIP without dev_value_old");
+    if (K < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: K < 1");
+    const int P = pop->n_members, N = h->cfg.n_envs;
+    const long long n = (long long)K * (N / P); // samples per member
+    rc = check_batch(h, n, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_perm, "ssg_pop_update_ext");
+    if (rc != SSG_OK) return rc;
+    if (!dev_table || !dev_adam_mv) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: NULL dev_table or dev_adam_mv");
+    if (epochs < 1 || minibatches < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: epochs < 1 or minibatches < 1");
+    const long long C = (n + minibatches - 1) / minibatches, chunks = (n + C - 1) / C; // torch.chunk
+    if ((long long)table_steps < (long long)epochs * chunks)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: the table holds fewer Adam steps than epochs * chunks");
+    const ssg_policy pol = pop_policy(*pop);
+    rc = check_workspace(h, dev_workspace, workspace_nbytes, pop_need_grad_ext(pol, P, C), "ssg_pop_update_ext");
+    if (rc == SSG_OK) rc = check_ready(h, false);
+    if (rc == SSG_OK) rc = prepare_ppo(h);
+    if (rc != SSG_OK) return rc;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    ssg::PpoExtLaunch el;
+    el.kl_coef = ext->dev_kl_coef;
+    el.logp_all = ext->dev_kl_coef ? ext->dev_logp_all : nullptr;
+    el.value_old = (ext->flags & SSG_POP_EXT_VF_CLIP) ? ext->dev_value_old : nullptr;
+    el.pop_ext = ext->dev_ext;
+    el.vf_clip = el.max_grad_norm = 0.0f; // (per member: dev_ext)
+    el.clip_seq = (ext->flags & SSG_POP_EXT_GRAD_CLIP) != 0;
+    el.first_chunk = true;
+    long long j = 0;
+    for (int ep = 0; ep < epochs; ++ep) {
+        for (long long b0 = 0; b0 < n; b0 += C, ++j) {
+            const long long M = std::min(C, n - b0);
+            el.first_chunk = b0 == 0;
+            hipError_t e = ssg::launch_pop_grad_ext(pol, P, K, N, dev_table, dev_table + (size_t)(1 + j) * (size_t)P * ssg::kPopTableRow, el,
+                                                    dev_x, dev_act, dev_logp, dev_adv, dev_ret,
+                                                    dev_perm + (size_t)ep * (size_t)n + (size_t)b0, (long long)epochs * n, M, dev_workspace,
+                                                    dev_stats ? dev_stats + ssg::kExtStats * j : nullptr,
+                                                    ssg::kExtStats * (long long)epochs * chunks, dev_adam_mv, st);
+            if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population update_ext launch: ") + hipGetErrorString(e));
+        }
+    }
+    if (ext->dev_kl_coef) {
+        hipError_t e = ssg::launch_kl_adapt(P, el, 0.0f, ssg::ppo_packed_len(pol), chunks, dev_workspace, ssg::kPopSlotsOff, st);
+        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population kl adapt launch: ") + hipGetErrorString(e));
     }
     return SSG_OK;
 }

@@ -244,6 +244,51 @@ hipError_t launch_pop_grad(const ssg_policy &p, int members, long long K, long l
                            const int64_t *idx, long long idx_stride, long long M, void *ws, float *stats_out, long long stats_stride,
                            float *adam_mv, hipStream_t stream);
 hipError_t launch_pop_exploit(const ssg_policy &p, int members, const int32_t *src, float *adam_mv, hipStream_t stream);
+// The extended update (ssg_ppo_grad_ext / ssg_ppo_update_ext / ssg_pop_update_ext): value clip, KL penalty, gradient-norm clip.
+// From the plain path's slot offset the workspace holds the running sum of the epoch's mean(KL) (f32 [members]), the gradient vector of
+// the clip sequence (f32 [members][P]), its per-workgroup sums of squares (f64 [members][nb]), then the slots [grid][P + kExtStats].
+constexpr int kExtStats = 8;  // loss sums per slot and stats columns per minibatch
+constexpr int kPopExtRow = 4; // ssg_pop_ext.dev_ext: vf_clip, max_grad_norm, kl_target, 0 per member
+struct PpoExtLayout {
+    size_t slots, gvec, part, klacc, end;
+    int nb; // workgroups of the reduction: ceil((P + kExtStats) / 256)
+};
+inline PpoExtLayout ppo_ext_layout(size_t slots_off, int members, int G, int P)
+{
+    const size_t m = (size_t)members, a = 255;
+    PpoExtLayout l;
+    l.nb = (P + kExtStats + 255) / 256;
+    // (the fixed-size parts first: their places do not move with the minibatch length; every part is `members` times one policy's,
+    // each rounded up to 256 bytes, so a population's workspace stays P times a single policy's)
+    l.klacc = slots_off;
+    l.gvec = l.klacc + m * 256;
+    l.part = l.gvec + m * (((size_t)P * sizeof(float) + a) & ~a);
+    l.slots = l.part + m * (((size_t)l.nb * sizeof(double) + a) & ~a);
+    l.end = l.slots + m * (size_t)G * (size_t)(P + kExtStats) * sizeof(float);
+    return l;
+}
+struct PpoExtLaunch {
+    const float *logp_all, *value_old; // device; NULL where the term that reads them is off for everyone
+    float *kl_coef;                    // device f32 [members]; NULL = no KL term
+    const float *pop_ext;              // a population's f32 [members][kPopExtRow]; NULL for one policy
+    float vf_clip, max_grad_norm;      // one policy's constants (a population reads pop_ext)
+    bool clip_seq;                     // three launches per minibatch: gradient, reduction + sums of squares, clip + Adam
+    bool first_chunk;                  // the minibatch is the first of its epoch (restarts the running KL sum)
+};
+size_t ppo_grad_ext_lds_bytes(const ssg_policy &p);
+// as launch_ppo_grad / launch_pop_grad, with stats rows of kExtStats floats
+hipError_t launch_ppo_grad_ext(const ssg_policy &p, const ssg_ppo_hparams &hp, const PpoExtLaunch &ext, long long n_samples, const float *x,
+                               const int32_t *act, const float *logp, const float *adv, const float *ret, const int64_t *idx, long long M,
+                               void *ws, float *grad_out, float *stats_out, float *adam_mv, int64_t step, hipStream_t stream);
+hipError_t launch_pop_grad_ext(const ssg_policy &p, int members, long long K, long long N, const float *table, const float *adam_row,
+                               const PpoExtLaunch &ext, const float *x, const int32_t *act, const float *logp, const float *adv,
+                               const float *ret, const int64_t *idx, long long idx_stride, long long M, void *ws, float *stats_out,
+                               long long stats_stride, float *adam_mv, hipStream_t stream);
+// RLlib's update_kl on every member's coefficient from the last epoch's `chunks` minibatches 
+hipError_t launch_kl_adapt(int members, const PpoExtLaunch &ext, float kl_target, int P, long long chunks, void *ws, size_t slots_off,
+                           hipStream_t stream);
+// the acting policy's log-distribution over stored x rows (shipsim_policy.hip): rows t*N + m*n + e, t < K, e < n, under parameter row m
+hipError_t launch_policy_dist(const ssg_policy &p, int members, int n, long long N, int K, const float *x, float *logp_all, hipStream_t stream);
 hipError_t launch_pop_episode_stats(int members, int K, int N, const double *rew, const uint8_t *done, double *carry_ret,
                                     int32_t *carry_len, int64_t *out, hipStream_t stream);
 

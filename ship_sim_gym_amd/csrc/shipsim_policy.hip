@@ -79,6 +79,51 @@ __device__ __forceinline__ void dense(const float *__restrict__ W, const float *
     }
 }
 
+// The heads over the last hidden layer h (this lane's column): P points at Wpi [A][H], bpi [A], Wv [1][H], bv [1].  Staged like a
+// dense tile (rows 0..A-1 = Wpi, row 4 = Wv; H is a multiple of 16, so no padding); lg[j] for j >= A stays 0.
+__device__ __forceinline__ void heads(const float *__restrict__ P, int H, int A, const float *h, float *wt, int lane, float (&lg)[4], float *v_out)
+{
+    const float *Wpi = P, *bpi = P + A * H, *Wv = bpi + A, *bv = Wv + H;
+    __syncthreads();
+    stage_rows(Wpi, A, H, H, wt, lane);
+    stage_rows(Wv, 1, H, H, wt + 4 * H, lane);
+    __syncthreads();
+    float v = bv[0];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) lg[j] = j < A ? bpi[j] : 0.0f;
+    for (int k = 0; k < H; k += 4) {
+        float hv[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) hv[t] = h[(k + t) * kPolStride + lane];
+        float4 w[5];
+#pragma unroll
+        for (int j = 0; j < 5; ++j) w[j] = *reinterpret_cast<const float4 *>(wt + j * H + k); // (rows A..3 unused: never summed)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const float hx = hv[t];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (j < A) lg[j] = fmaf(t == 0 ? w[j].x : t == 1 ? w[j].y : t == 2 ? w[j].z : w[j].w, hx, lg[j]);
+            v = fmaf(t == 0 ? w[4].x : t == 1 ? w[4].y : t == 2 ? w[4].z : w[4].w, hx, v);
+        }
+    }
+    *v_out = v;
+}
+
+// log(sum_j exp(lg[j])) over j < A, the formula order of ppo_torch's log_softmax
+__device__ __forceinline__ float log_sum_exp(const float (&lg)[4], int A)
+{
+    float m = lg[0];
+#pragma unroll
+    for (int j = 1; j < 4; ++j)
+        if (j < A) m = fmaxf(m, lg[j]);
+    float s = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j < A) s += expf(lg[j] - m);
+    return m + logf(s);
+}
+
 // (waves_per_eu(1, 2): lets the scheduler keep all 16 weight reads of a step in flight — 113 VGPRs — instead of two at a time)
 //
 // POP = false: ssg_policy_act's launch, n envs under one parameter buffer (plen unused).  POP = true: a population in one launch, grid
@@ -145,47 +190,16 @@ __global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1
         h = bufA;
     }
 
-    // 3. the heads: Wpi [A][H], bpi [A], Wv [1][H], bv [1]
-    // (staged like a dense tile: rows 0..A-1 = Wpi, row 4 = Wv; H is a multiple of 16, so no padding)
-    const float *Wpi = P, *bpi = P + A * H, *Wv = bpi + A, *bv = Wv + H;
-    __syncthreads();
-    stage_rows(Wpi, A, H, H, wt, lane);
-    stage_rows(Wv, 1, H, H, wt + 4 * H, lane);
-    __syncthreads();
-    float lg[4], v = bv[0];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) lg[j] = j < A ? bpi[j] : 0.0f;
-    for (int k = 0; k < H; k += 4) {
-        float hv[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) hv[t] = h[(k + t) * kPolStride + lane];
-        float4 w[5];
-#pragma unroll
-        for (int j = 0; j < 5; ++j) w[j] = *reinterpret_cast<const float4 *>(wt + j * H + k); // (rows A..3 unused: never summed)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const float hx = hv[t];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (j < A) lg[j] = fmaf(t == 0 ? w[j].x : t == 1 ? w[j].y : t == 2 ? w[j].z : w[j].w, hx, lg[j]);
-            v = fmaf(t == 0 ? w[4].x : t == 1 ? w[4].y : t == 2 ? w[4].z : w[4].w, hx, v);
-        }
-    }
+    // 3. the heads
+    float lg[4], v;
+    heads(P, H, A, h, wt, lane, lg, &v);
     if (lane >= ne) return;
     const int e = e0 + lane;
     if (value_out) value_out[e] = v;
     if (!act_out) return; // (the bootstrap forward of ssg_rollout_policy: value only)
 
     // 4. inverse-CDF sampling, the formula order of ppo_torch's Shard.step(): log_softmax, cumsum(exp), count(u > cdf[j]) over j < A-1
-    float m = lg[0];
-#pragma unroll
-    for (int j = 1; j < 4; ++j)
-        if (j < A) m = fmaxf(m, lg[j]);
-    float s = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (j < A) s += expf(lg[j] - m);
-    const float lse = m + logf(s);
+    const float lse = log_sum_exp(lg, A);
     float u;
     if (uniform) {
         u = uniform[e];
@@ -216,6 +230,64 @@ __global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1
     logp_out[e] = lp;
 }
 
+// The acting policy's whole log-distribution over STORED x rows (ssg_ppo_dist / ssg_pop_dist): policy_act_kernel's forward from its
+// step 2 on — the same dense, heads and log_sum_exp — so that logp_all[i][act[i]] is the rollout's logp[i] bit for bit.  Grid
+// (workgroups of n rows, members, K): the workgroup's rows start at row blockIdx.z*N + blockIdx.y*n and run under parameter row
+// blockIdx.y (one policy: members = 1, K = 1, n = the number of rows).  logp_all[i][j] = logit_j - lse for j < A, 0 for j >= A.
+__global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1, 2))) policy_dist_kernel(const ssg_policy p, const float *__restrict__ params, int n, long long N,
+                                                               const float *__restrict__ x, float *__restrict__ logp_all, int plen)
+{
+    extern __shared__ float4 lds4[];
+    const int lane = threadIdx.x;
+    const int e0 = blockIdx.x * kPolWave;
+    const int ne = (n - e0 < kPolWave) ? n - e0 : kPolWave;
+    const int D = p.obs_dim, H = p.hidden, A = p.n_actions;
+    const size_t row0 = (size_t)blockIdx.z * (size_t)N + (size_t)blockIdx.y * (size_t)n + (size_t)e0;
+    params += (size_t)blockIdx.y * (size_t)plen;
+    const int R4 = ((D > H ? D : H) + 3) & ~3;
+    float *wt = reinterpret_cast<float *>(lds4);
+    float *bufA = wt + 16 * R4;
+    float *bufB = bufA + R4 * kPolStride;
+    {
+        const float *src = x + row0 * D;
+        const int total = ne * D, qd = kPolWave / D, rd = kPolWave % D;
+        int d = lane % D, el = lane / D;
+        for (int i = lane; i < total; i += kPolWave) {
+            bufA[d * kPolStride + el] = src[i];
+            d += rd;
+            el += qd;
+            if (d >= D) { d -= D; ++el; }
+        }
+        // (a tail workgroup's lanes >= ne compute on zeros and store nothing)
+        if (lane >= ne)
+            for (int r = 0; r < D; ++r) bufA[r * kPolStride + lane] = 0.0f;
+        for (int r = D; r < R4; ++r) bufA[r * kPolStride + lane] = 0.0f;
+    }
+    const float *P = params;
+    dense(P, P + H * D, D, H, p.activation, bufA, bufB, wt, lane);
+    P += H * D + H;
+    const float *h = bufB;
+    if (p.n_hidden_layers == 2) {
+        dense(P, P + H * H, H, H, p.activation, bufB, bufA, wt, lane);
+        P += H * H + H;
+        h = bufA;
+    }
+    float lg[4], v;
+    heads(P, H, A, h, wt, lane, lg, &v);
+    if (lane >= ne) return;
+    const float lse = log_sum_exp(lg, A);
+    float4 out;
+    out.x = lg[0] - lse;
+    out.y = 1 < A ? lg[1] - lse : 0.0f;
+    out.z = 2 < A ? lg[2] - lse : 0.0f;
+    out.w = 3 < A ? lg[3] - lse : 0.0f;
+    float *dst = logp_all + (row0 + (size_t)lane) * 4;
+    dst[0] = out.x;
+    dst[1] = out.y;
+    dst[2] = out.z;
+    dst[3] = out.w;
+}
+
 } // namespace
 
 size_t policy_lds_bytes(const ssg_policy &p)
@@ -228,7 +300,9 @@ hipError_t prepare_policy()
 {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(policy_act_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(policy_act_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(policy_act_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(policy_dist_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
 hipError_t launch_policy_act(const ssg_policy &p, int n, long long env_base, const double *obs, const float *uniform, uint64_t seed,
@@ -246,6 +320,14 @@ hipError_t launch_policy_pop(const ssg_policy &p, int members, int n, long long 
     const unsigned grid = (unsigned)((n + kPolWave - 1) / kPolWave);
     hipLaunchKernelGGL(policy_act_kernel<true>, dim3(grid, (unsigned)members), dim3(kPolWave), policy_lds_bytes(p), stream, p, p.dev_params,
                        p.dev_obs_scale, n, env_base, obs, uniform, seed, step, act, logp, value, x, ppo_packed_len(p));
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_dist(const ssg_policy &p, int members, int n, long long N, int K, const float *x, float *logp_all, hipStream_t stream)
+{
+    const unsigned grid = (unsigned)((n + kPolWave - 1) / kPolWave);
+    hipLaunchKernelGGL(policy_dist_kernel, dim3(grid, (unsigned)members, (unsigned)K), dim3(kPolWave), policy_lds_bytes(p), stream, p, p.dev_params,
+                       n, N, x, logp_all, ppo_packed_len(p));
     return hipGetLastError();
 }
 

@@ -268,21 +268,40 @@ struct PopGradArgs {
     const float *table;   // [members][kPopTableRow]
 };
 
+// What the extended loss (ssg_ppo_grad_ext / ssg_ppo_update_ext / ssg_pop_update_ext) adds to GradArgs.  A term is off for a member
+// whose constant is <= 0 (or whose pointer is NULL): its samples then take exactly the operations of the plain loss.
+struct ExtGradArgs {
+    const float *logp_all; // f32 [rows][4]: the acting policy's log-distribution (ssg_ppo_dist); read where the KL term is on
+    const float *v_old;    // f32 [rows]: the rollout's value prediction; read where the value clip is on
+    const float *kl_coef;  // device f32 [members] (one policy: [1]); NULL = no KL term
+    const float *pop_ext;  // POP: f32 [members][kPopExtRow] = vf_clip, max_grad_norm, kl_target, 0
+    float vf_clip;         // one policy: the value clip range (<= 0 = off)
+};
+
 // POP = false: ssg_ppo_grad's launch (pa unused).  POP = true: the minibatch gradient of every member in one launch, grid
 // (ppo_grid(M), members): member m = blockIdx.y reads parameter row m, its own index row (member-local indices), its advantage
 // statistics (stats + 4m) and loss constants (table row m), and owns the slots [m*grid, (m+1)*grid) — what the POP = false launch
 // computes for that member alone, tile for tile (the same code below).
-template <bool POP> __global__ void __launch_bounds__(kPpoBlock) ppo_grad_kernel(const GradArgs a_, const PopGradArgs pa)
+// EXT = false: the loss of ssg_ppo_grad (ea unused), slots of P + 4 floats.  EXT = true: plus the value clip and the KL penalty,
+// slots of P + kExtStats floats (the loss sums pg, VL, entropy, clip fraction, KL, then zeros).
+template <bool POP, bool EXT> __device__ __forceinline__ void ppo_grad_body(const GradArgs &a_, const PopGradArgs &pa, const ExtGradArgs &ea)
 {
     extern __shared__ float4 lds4[];
     float *lds = reinterpret_cast<float *>(lds4);
     GradArgs a = a_;
+    const int SS = a_.P + (EXT ? kExtStats : 4); // floats per slot
+    float vf_clip = 0.0f, kl_coef = 0.0f;
+    if (EXT) {
+        vf_clip = POP ? ea.pop_ext[(size_t)blockIdx.y * kPopExtRow] : ea.vf_clip;
+        kl_coef = ea.kl_coef ? ea.kl_coef[POP ? blockIdx.y : 0] : 0.0f;
+    }
+    const bool vclip_on = EXT && vf_clip > 0.0f, kl_on = EXT && kl_coef > 0.0f;
     if (POP) {
         const size_t m = blockIdx.y;
         a.params += m * (size_t)a.P;
         a.idx += m * (size_t)pa.idx_stride;
         a.stats += m * 4;
-        a.slots += m * (size_t)gridDim.x * (size_t)(a.P + 4);
+        a.slots += m * (size_t)gridDim.x * (size_t)SS;
         const float *row = pa.table + m * kPopTableRow;
         a.lo = row[PT_LO];
         a.hi = row[PT_HI];
@@ -305,6 +324,8 @@ template <bool POP> __global__ void __launch_bounds__(kPpoBlock) ppo_grad_kernel
     float *SLOGP = DV + kTile, *SADV = SLOGP + kTile, *SRET = SADV + kTile, *RED = SRET + kTile;
     int *SACT = reinterpret_cast<int *>(RED + kTile * 4);
     long long *SIDX = reinterpret_cast<long long *>(SACT + kTile); // (8-byte aligned: every region above is a multiple of 2 floats)
+    // EXT: | v_old [64] | logp_old [64][4] | the fifth loss sum [64]
+    float *SVOLD = reinterpret_cast<float *>(SIDX + kTile), *SLPO = SVOLD + kTile, *RED5 = SLPO + kTile * 4;
 
     // packed offsets (include/shipsim.h)
     const float *P = a.params;
@@ -312,7 +333,7 @@ template <bool POP> __global__ void __launch_bounds__(kPpoBlock) ppo_grad_kernel
     const float *W1 = b0 + H, *b1 = W1 + H * H;
     const float *Wpi = a.L == 2 ? b1 + H : b0 + H;
     const float *bpi = Wpi + A * H, *Wv = bpi + A, *bv = Wv + H;
-    float *g = a.slots + (size_t)blockIdx.x * (a.P + 4);
+    float *g = a.slots + (size_t)blockIdx.x * SS;
     float *gW0 = g, *gb0 = g + H * D, *gW1 = gb0 + H, *gb1 = gW1 + H * H;
     float *gWpi = g + (Wpi - P), *gbpi = g + (bpi - P), *gWv = g + (Wv - P), *gbv = g + (bv - P);
 
@@ -324,7 +345,7 @@ template <bool POP> __global__ void __launch_bounds__(kPpoBlock) ppo_grad_kernel
     const float mean = a.stats[0], stdp = a.stats[1];
     const float *HL = a.L == 2 ? HB1 : HB0; // the last hidden layer
     float accb0 = 0.0f, accb1 = 0.0f, accW[4] = {0.0f, 0.0f, 0.0f, 0.0f}, accWv = 0.0f, accbh = 0.0f;
-    float st_pg = 0.0f, st_vl = 0.0f, st_en = 0.0f, st_cf = 0.0f;
+    float st_pg = 0.0f, st_vl = 0.0f, st_en = 0.0f, st_cf = 0.0f, st_kl = 0.0f;
     const long long ntiles = (a.M + kTile - 1) / kTile;
     bool first = true;
     for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -343,6 +364,11 @@ template <bool POP> __global__ void __launch_bounds__(kPpoBlock) ppo_grad_kernel
                 SLOGP[tid] = a.logp[j];
                 SADV[tid] = (a.adv[j] - mean) / stdp;
                 SRET[tid] = a.ret[j];
+                if (vclip_on) SVOLD[tid] = ea.v_old[j];
+                if (kl_on) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) SLPO[tid * 4 + c] = ea.logp_all[(size_t)j * 4 + c];
+                }
             }
         }
         __syncthreads();
@@ -410,8 +436,35 @@ template <bool POP> __global__ void __launch_bounds__(kPpoBlock) ppo_grad_kernel
                     if (j < A) dl[j] = glpa * ((j == act ? 1.0f : 0.0f) - p[j]) + gent * (-p[j] * (lp[j] + ent));
                 const float err = v - SRET[s];
                 dv = a.vf * 2.0f * err * a.invM;
+                float vl = err * err;
+                if (vclip_on) { // VL = max((v - ret)^2, (v_old + clamp(v - v_old, -c, c) - ret)^2): max and clamp as autograd takes them
+                    const float vo = SVOLD[s], d = v - vo;
+                    const float errc = (vo + fminf(fmaxf(d, -vf_clip), vf_clip)) - SRET[s];
+                    const float l1 = vl, l2 = errc * errc;
+                    const float w1 = l1 > l2 ? 1.0f : (l1 == l2 ? 0.5f : 0.0f), w2 = l2 > l1 ? 1.0f : (l1 == l2 ? 0.5f : 0.0f);
+                    const bool vin = d >= -vf_clip && d <= vf_clip;
+                    const float gv = w1 * (2.0f * err) + (vin ? w2 * (2.0f * errc) : 0.0f);
+                    dv = a.vf * gv * a.invM;
+                    vl = fmaxf(l1, l2);
+                }
+                if (kl_on) { // KL(old || new) = sum_j p_old[j] * (logp_old[j] - logp[j]); d/d logit j = p[j]*sum(p_old) - p_old[j]
+                    float po[4], spo = 0.0f, kl = 0.0f;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        po[j] = j < A ? expf(SLPO[s * 4 + j]) : 0.0f;
+                        if (j < A) {
+                            spo += po[j];
+                            kl += po[j] * (SLPO[s * 4 + j] - lp[j]);
+                        }
+                    }
+                    const float gk = kl_coef * a.invM;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (j < A) dl[j] += gk * (p[j] * spo - po[j]);
+                    st_kl += kl;
+                }
                 st_pg += -fminf(s1, s2);
-                st_vl += err * err;
+                st_vl += vl;
                 st_en += ent;
                 st_cf += fabsf(ratio - 1.0f) > a.clip ? 1.0f : 0.0f;
             }
@@ -467,13 +520,31 @@ template <bool POP> __global__ void __launch_bounds__(kPpoBlock) ppo_grad_kernel
         RED[tid * 4 + 1] = st_vl;
         RED[tid * 4 + 2] = st_en;
         RED[tid * 4 + 3] = st_cf;
+        if (EXT) RED5[tid] = st_kl;
     }
     __syncthreads();
     if (tid < 4) {
         float s = 0.0f;
         for (int i = 0; i < kTile; ++i) s += RED[i * 4 + tid];
         g[a.P + tid] = s;
+    } else if (EXT && tid == 4) {
+        float s = 0.0f;
+        for (int i = 0; i < kTile; ++i) s += RED5[i];
+        g[a.P + 4] = s;
+    } else if (EXT && tid < kExtStats) {
+        g[a.P + tid] = 0.0f;
     }
+}
+
+template <bool POP> __global__ void __launch_bounds__(kPpoBlock) ppo_grad_kernel(const GradArgs a, const PopGradArgs pa)
+{
+    ppo_grad_body<POP, false>(a, pa, ExtGradArgs{});
+}
+
+template <bool POP>
+__global__ void __launch_bounds__(kPpoBlock) ppo_grad_ext_kernel(const GradArgs a, const PopGradArgs pa, const ExtGradArgs ea)
+{
+    ppo_grad_body<POP, true>(a, pa, ea);
 }
 
 // grad[p] = sum over the slots (a fixed order); entries P..P+3 (when nstats) are the loss sums -> stats = sum / M.  With params: Adam, torch's
@@ -488,31 +559,10 @@ struct AdamArgs {
 // every member in one launch, grid (ceil(stride / 256), members): member m = blockIdx.y sums its own G slots, writes its stats row
 // (stats_out + m*stats_stride, nullable) and steps parameter row m / moments row m with ITS Adam constants of this step (adam row m:
 // the host's doubles, rounded as adam_args rounds them).
-template <bool POP>
-__global__ void __launch_bounds__(256) ppo_reduce_kernel(const float *__restrict__ slots, int G, int P, int stride, float fM,
-                                                         float *__restrict__ grad_out, float *__restrict__ stats_out,
-                                                         float *__restrict__ params, float *__restrict__ mv, const AdamArgs ad_,
-                                                         long long stats_stride, const float *__restrict__ adam)
+// the sum of entry p over the G slots in order, 64 at a time as a tree of 4 trees of 16 (the missing ones are zeros)
+__device__ __forceinline__ float slot_sum(const float *__restrict__ slots, int G, int stride, int p)
 {
-    AdamArgs ad = ad_;
-    if (POP) {
-        const size_t m = blockIdx.y;
-        const float *row = adam + m * kPopTableRow;
-        ad.w1 = row[0];
-        ad.one_minus_w1 = row[1];
-        ad.beta2 = row[2];
-        ad.w2 = row[3];
-        ad.bc2_sqrt = row[4];
-        ad.eps = row[5];
-        ad.step_size = row[6];
-        slots += m * (size_t)G * (size_t)stride;
-        if (stats_out) stats_out += m * (size_t)stats_stride;
-        params += m * (size_t)P;
-        mv += m * 2 * (size_t)P;
-    }
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= stride) return;
-    float s = 0.0f; // the slots in order, 64 at a time as a tree of 4 trees of 16 (the missing ones are zeros)
+    float s = 0.0f;
 #pragma unroll 1
     for (int b0 = 0; b0 < G; b0 += 64) {
         float u[4];
@@ -528,21 +578,158 @@ __global__ void __launch_bounds__(256) ppo_reduce_kernel(const float *__restrict
         }
         s += tree_sum<4>(u);
     }
+    return s;
+}
+
+// one Adam step of entry p with gradient s
+__device__ __forceinline__ void adam_apply(const AdamArgs &ad, float s, int p, int P, float *__restrict__ params, float *__restrict__ mv)
+{
+    float m = mv[p], v = mv[P + p];
+    m = fabsf(ad.w1) < 0.5f ? m + ad.w1 * (s - m) : s - (s - m) * ad.one_minus_w1;
+    v = v * ad.beta2;
+    v = v + ad.w2 * (s * s);
+    mv[p] = m;
+    mv[P + p] = v;
+    const float den = sqrtf(v) / ad.bc2_sqrt + ad.eps;
+    params[p] = params[p] + ad.step_size * (m / den);
+}
+
+// member m's Adam constants of this step: row m of the step's table rows
+__device__ __forceinline__ AdamArgs adam_row(const float *__restrict__ adam, size_t m)
+{
+    const float *row = adam + m * kPopTableRow;
+    AdamArgs ad;
+    ad.w1 = row[0];
+    ad.one_minus_w1 = row[1];
+    ad.beta2 = row[2];
+    ad.w2 = row[3];
+    ad.bc2_sqrt = row[4];
+    ad.eps = row[5];
+    ad.step_size = row[6];
+    return ad;
+}
+
+template <bool POP>
+__global__ void __launch_bounds__(256) ppo_reduce_kernel(const float *__restrict__ slots, int G, int P, int stride, float fM,
+                                                         float *__restrict__ grad_out, float *__restrict__ stats_out,
+                                                         float *__restrict__ params, float *__restrict__ mv, const AdamArgs ad_,
+                                                         long long stats_stride, const float *__restrict__ adam)
+{
+    AdamArgs ad = ad_;
+    if (POP) {
+        const size_t m = blockIdx.y;
+        ad = adam_row(adam, m);
+        slots += m * (size_t)G * (size_t)stride;
+        if (stats_out) stats_out += m * (size_t)stats_stride;
+        params += m * (size_t)P;
+        mv += m * 2 * (size_t)P;
+    }
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= stride) return;
+    const float s = slot_sum(slots, G, stride, p);
     if (p >= P) {
         if (stats_out) stats_out[p - P] = s / fM;
         return;
     }
     if (grad_out) grad_out[p] = s;
-    if (params) {
-        float m = mv[p], v = mv[P + p];
-        m = fabsf(ad.w1) < 0.5f ? m + ad.w1 * (s - m) : s - (s - m) * ad.one_minus_w1;
-        v = v * ad.beta2;
-        v = v + ad.w2 * (s * s);
-        mv[p] = m;
-        mv[P + p] = v;
-        const float den = sqrtf(v) / ad.bc2_sqrt + ad.eps;
-        params[p] = params[p] + ad.step_size * (m / den);
+    if (params) adam_apply(ad, s, p, P, params, mv);
+}
+
+// What the extended update adds to the reduction (stride = P + kExtStats).  The stats row is f32 [kExtStats]: the five loss means,
+// [5] the global gradient norm before clipping (0 here; ppo_clip_kernel writes it), [6] the KL coefficient in use, [7] 0.  The
+// member's mean(KL) of this minibatch is also added to klacc[m] (set, on an epoch's first chunk): a running f32 sum in chunk
+// order, which the adaptation kernel turns into the epoch's mean after the last minibatch.
+struct ExtReduceArgs {
+    const float *kl_coef; // f32 [members], nullable
+    float *klacc;         // f32 [members]
+    int first_chunk;      // this minibatch is the first of its epoch
+    float *gvec;          // non-NULL = the clip sequence: f32 [members][P] receives the gradient and part the sums of squares, no Adam
+    double *part;         // f64 [members][gridDim.x]
+};
+
+template <bool POP>
+__global__ void __launch_bounds__(256) ppo_reduce_ext_kernel(const float *__restrict__ slots, int G, int P, int stride, float fM,
+                                                             float *__restrict__ grad_out, float *__restrict__ stats_out,
+                                                             float *__restrict__ params, float *__restrict__ mv, const AdamArgs ad_,
+                                                             long long stats_stride, const float *__restrict__ adam,
+                                                             const ExtReduceArgs ea)
+{
+    __shared__ double sq[256];
+    AdamArgs ad = ad_;
+    const size_t m = POP ? blockIdx.y : 0;
+    if (POP) {
+        if (adam) ad = adam_row(adam, m);
+        slots += m * (size_t)G * (size_t)stride;
+        if (stats_out) stats_out += m * (size_t)stats_stride;
+        if (params) params += m * (size_t)P;
+        if (mv) mv += m * 2 * (size_t)P;
     }
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    const float s = p < stride ? slot_sum(slots, G, stride, p) : 0.0f;
+    if (p >= P && p < stride) {
+        const int q = p - P;
+        const float klc = ea.kl_coef ? ea.kl_coef[m] : 0.0f;
+        const float mean = s / fM;
+        if (stats_out) stats_out[q] = q < 5 ? mean : (q == 6 ? (klc > 0.0f ? klc : 0.0f) : 0.0f);
+        if (q == 4) ea.klacc[m] = ea.first_chunk ? mean : ea.klacc[m] + mean;
+    }
+    if (p < P) {
+        if (grad_out) grad_out[p] = s;
+        if (ea.gvec) ea.gvec[m * (size_t)P + p] = s;
+        else if (params) adam_apply(ad, s, p, P, params, mv);
+    }
+    if (ea.gvec) { // the workgroup's sum of squares, f64, a fixed tree
+        sq[threadIdx.x] = p < P ? (double)s * (double)s : 0.0;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) {
+            if ((int)threadIdx.x < w) sq[threadIdx.x] += sq[threadIdx.x + w];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) ea.part[m * (size_t)gridDim.x + blockIdx.x] = sq[0];
+    }
+}
+
+// The third launch of the clip sequence, grid (ceil(P / 256), members): every workgroup adds the member's nb partial sums of squares
+// in index order (f64), then in f32 norm = (float)sqrt(sum), coef = min(1, max_grad_norm / (norm + 1e-6f)) — torch's
+// clip_grad_norm_ — and Adam on g * coef.  A member with max_grad_norm <= 0 gets coef = 1.0f (exact) and a norm column of 0.
+// params NULL (ssg_ppo_grad_ext): the norm column alone.
+template <bool POP>
+__global__ void __launch_bounds__(256) ppo_clip_kernel(const float *__restrict__ gvec, const double *__restrict__ part, int nb, int P,
+                                                       float max_grad_norm, const float *__restrict__ pop_ext,
+                                                       float *__restrict__ stats_out, long long stats_stride, float *__restrict__ params,
+                                                       float *__restrict__ mv, const AdamArgs ad_, const float *__restrict__ adam)
+{
+    AdamArgs ad = ad_;
+    const size_t m = POP ? blockIdx.y : 0;
+    if (POP) {
+        if (adam) ad = adam_row(adam, m);
+        max_grad_norm = pop_ext[m * kPopExtRow + 1];
+        if (stats_out) stats_out += m * (size_t)stats_stride;
+        if (params) params += m * (size_t)P;
+        if (mv) mv += m * 2 * (size_t)P;
+    }
+    double sum = 0.0;
+    for (int b = 0; b < nb; ++b) sum += part[m * (size_t)nb + b];
+    const float norm = (float)sqrt(sum);
+    const bool on = max_grad_norm > 0.0f;
+    const float coef = on ? fminf(1.0f, max_grad_norm / (norm + 1e-6f)) : 1.0f;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p == 0 && stats_out) stats_out[5] = on ? norm : 0.0f;
+    if (p < P && params) adam_apply(ad, gvec[m * (size_t)P + p] * coef, p, P, params, mv);
+}
+
+// The last launch of an extended update with a KL target, one workgroup, lane m = member m: RLlib's update_kl on the f32 mean of the
+// last epoch's minibatch means of KL.  A member whose target is <= 0 keeps its coefficient.
+__global__ void __launch_bounds__(256) ppo_kl_adapt_kernel(int members, float *__restrict__ kl_coef, const float *__restrict__ klacc,
+                                                           float chunks, float kl_target, const float *__restrict__ pop_ext)
+{
+    const int m = threadIdx.x;
+    if (m >= members) return;
+    const float target = pop_ext ? pop_ext[(size_t)m * kPopExtRow + 2] : kl_target;
+    if (!(target > 0.0f)) return;
+    const float mean = klacc[m] / chunks;
+    if (mean > 2.0f * target) kl_coef[m] = kl_coef[m] * 1.5f;
+    else if (mean < 0.5f * target) kl_coef[m] = kl_coef[m] * 0.5f;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -640,11 +827,18 @@ size_t ppo_grad_lds_bytes(const ssg_policy &p)
     return floats * sizeof(float) + kTile * sizeof(int) + kTile * sizeof(long long) + 8;
 }
 
+// (the extended instantiations add v_old, four logp_old and the fifth loss sum per sample of the tile: 1.5 KB)
+size_t ppo_grad_ext_lds_bytes(const ssg_policy &p) { return ppo_grad_lds_bytes(p) + 6 * kTile * sizeof(float); }
+
 hipError_t prepare_ppo()
 {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ppo_grad_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(ppo_grad_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    const void *kernels[4] = {reinterpret_cast<const void *>(ppo_grad_kernel<false>), reinterpret_cast<const void *>(ppo_grad_kernel<true>),
+                              reinterpret_cast<const void *>(ppo_grad_ext_kernel<false>), reinterpret_cast<const void *>(ppo_grad_ext_kernel<true>)};
+    for (const void *k : kernels) {
+        hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t launch_ppo_gae(const ssg_ppo_hparams &hp, int K, int N, const double *rew, const uint8_t *done, const float *val,
@@ -696,6 +890,82 @@ hipError_t launch_ppo_grad(const ssg_policy &p, const ssg_ppo_hparams &hp, long 
     hipLaunchKernelGGL(ppo_reduce_kernel<false>, dim3((stride + 255) / 256), dim3(256), 0, stream, (const float *)a.slots, G, a.P, stride,
                        (float)M, grad_out, stats_out, adam_mv ? const_cast<float *>(p.dev_params) : nullptr, adam_mv, ad, 0ll,
                        (const float *)nullptr);
+    return hipGetLastError();
+}
+
+// the reduction (and, with ext.clip_seq, the clip launch) behind one extended minibatch of `members` members
+template <bool POP>
+static void launch_ext_reduce(int members, int G, int P, long long M, const PpoExtLaunch &ext, void *ws, size_t slots_off, float *grad_out,
+                              float *stats_out, long long stats_stride, float *params, float *adam_mv, const AdamArgs &ad,
+                              const float *adam_row, hipStream_t stream)
+{
+    const PpoExtLayout lay = ppo_ext_layout(slots_off, members, G, P);
+    char *base = static_cast<char *>(ws);
+    const int stride = P + kExtStats;
+    ExtReduceArgs ea;
+    ea.kl_coef = ext.kl_coef;
+    ea.klacc = reinterpret_cast<float *>(base + lay.klacc);
+    ea.first_chunk = ext.first_chunk ? 1 : 0;
+    ea.gvec = ext.clip_seq ? reinterpret_cast<float *>(base + lay.gvec) : nullptr;
+    ea.part = reinterpret_cast<double *>(base + lay.part);
+    const dim3 grid((unsigned)lay.nb, (unsigned)members);
+    hipLaunchKernelGGL(ppo_reduce_ext_kernel<POP>, grid, dim3(256), 0, stream, (const float *)(base + lay.slots), G, P, stride, (float)M,
+                       grad_out, stats_out, params, adam_mv, ad, stats_stride, adam_row, ea);
+    if (ext.clip_seq)
+        hipLaunchKernelGGL(ppo_clip_kernel<POP>, dim3((unsigned)((P + 255) / 256), (unsigned)members), dim3(256), 0, stream,
+                           (const float *)ea.gvec, (const double *)ea.part, lay.nb, P, ext.max_grad_norm, ext.pop_ext, stats_out, stats_stride,
+                           params, adam_mv, ad, adam_row);
+}
+
+hipError_t launch_ppo_grad_ext(const ssg_policy &p, const ssg_ppo_hparams &hp, const PpoExtLaunch &ext, long long n_samples, const float *x,
+                               const int32_t *act, const float *logp, const float *adv, const float *ret, const int64_t *idx, long long M,
+                               void *ws, float *grad_out, float *stats_out, float *adam_mv, int64_t step, hipStream_t stream)
+{
+    GradArgs a;
+    a.D = p.obs_dim;
+    a.H = p.hidden;
+    a.L = p.n_hidden_layers;
+    a.A = p.n_actions;
+    a.kind = p.activation;
+    a.params = p.dev_params;
+    a.x = x;
+    a.act = act;
+    a.logp = logp;
+    a.adv = adv;
+    a.ret = ret;
+    a.idx = idx;
+    a.M = M;
+    a.n_samples = n_samples;
+    a.stats = reinterpret_cast<const float *>(static_cast<const char *>(ws) + kPpoStatsOff);
+    a.slots = reinterpret_cast<float *>(static_cast<char *>(ws) + kPpoSlotsOff);
+    a.P = ppo_packed_len(p);
+    a.lo = (float)(1.0 - hp.clip);
+    a.hi = (float)(1.0 + hp.clip);
+    a.clip = (float)hp.clip;
+    a.vf = (float)hp.vf_coef;
+    a.ent = (float)hp.ent_coef;
+    a.invM = 1.0f / (float)M;
+    ExtGradArgs ea;
+    ea.logp_all = ext.logp_all;
+    ea.v_old = ext.value_old;
+    ea.kl_coef = ext.kl_coef;
+    ea.pop_ext = nullptr;
+    ea.vf_clip = ext.vf_clip;
+    const int G = ppo_grid(M);
+    a.slots = reinterpret_cast<float *>(static_cast<char *>(ws) + ppo_ext_layout(kPpoSlotsOff, 1, G, a.P).slots);
+    hipLaunchKernelGGL(ppo_grad_ext_kernel<false>, dim3(G), dim3(kPpoBlock), ppo_grad_ext_lds_bytes(p), stream, a, PopGradArgs{}, ea);
+    const AdamArgs ad = adam_mv ? adam_args(hp, step) : AdamArgs{};
+    launch_ext_reduce<false>(1, G, a.P, M, ext, ws, kPpoSlotsOff, grad_out, stats_out, 0ll, adam_mv ? const_cast<float *>(p.dev_params) : nullptr,
+                             adam_mv, ad, nullptr, stream);
+    return hipGetLastError();
+}
+
+hipError_t launch_kl_adapt(int members, const PpoExtLaunch &ext, float kl_target, int P, long long chunks, void *ws, size_t slots_off,
+                           hipStream_t stream)
+{
+    const PpoExtLayout lay = ppo_ext_layout(slots_off, members, 1, P);
+    hipLaunchKernelGGL(ppo_kl_adapt_kernel, dim3(1), dim3(256), 0, stream, members, ext.kl_coef,
+                       (const float *)(static_cast<char *>(ws) + lay.klacc), (float)chunks, kl_target, ext.pop_ext);
     return hipGetLastError();
 }
 
@@ -786,6 +1056,50 @@ hipError_t launch_pop_grad(const ssg_policy &p, int members, long long K, long l
     hipLaunchKernelGGL(ppo_reduce_kernel<true>, dim3((stride + 255) / 256, members), dim3(256), 0, stream, (const float *)a.slots, G, a.P,
                        stride, (float)M, (float *)nullptr, stats_out, const_cast<float *>(p.dev_params), adam_mv, AdamArgs{}, stats_stride,
                        adam_row);
+    return hipGetLastError();
+}
+
+hipError_t launch_pop_grad_ext(const ssg_policy &p, int members, long long K, long long N, const float *table, const float *adam_row,
+                               const PpoExtLaunch &ext, const float *x, const int32_t *act, const float *logp, const float *adv,
+                               const float *ret, const int64_t *idx, long long idx_stride, long long M, void *ws, float *stats_out,
+                               long long stats_stride, float *adam_mv, hipStream_t stream)
+{
+    PopGradArgs pa;
+    GradArgs a;
+    a.D = p.obs_dim;
+    a.H = p.hidden;
+    a.L = p.n_hidden_layers;
+    a.A = p.n_actions;
+    a.kind = p.activation;
+    a.params = p.dev_params;
+    a.x = x;
+    a.act = act;
+    a.logp = logp;
+    a.adv = adv;
+    a.ret = ret;
+    a.idx = idx;
+    a.M = M;
+    pa.n = N / members;
+    pa.N = N;
+    a.n_samples = K * pa.n;
+    a.stats = reinterpret_cast<const float *>(static_cast<const char *>(ws) + kPpoStatsOff);
+    a.slots = reinterpret_cast<float *>(static_cast<char *>(ws) + kPopSlotsOff);
+    a.P = ppo_packed_len(p);
+    a.lo = a.hi = a.clip = a.vf = a.ent = 0.0f; // (per member: the table)
+    a.invM = 1.0f / (float)M;
+    pa.idx_stride = idx_stride;
+    pa.table = table;
+    ExtGradArgs ea;
+    ea.logp_all = ext.logp_all;
+    ea.v_old = ext.value_old;
+    ea.kl_coef = ext.kl_coef;
+    ea.pop_ext = ext.pop_ext;
+    ea.vf_clip = 0.0f;
+    const int G = ppo_grid(M);
+    a.slots = reinterpret_cast<float *>(static_cast<char *>(ws) + ppo_ext_layout(kPopSlotsOff, members, G, a.P).slots);
+    hipLaunchKernelGGL(ppo_grad_ext_kernel<true>, dim3(G, members), dim3(kPpoBlock), ppo_grad_ext_lds_bytes(p), stream, a, pa, ea);
+    launch_ext_reduce<true>(members, G, a.P, M, ext, ws, kPopSlotsOff, nullptr, stats_out, stats_stride, const_cast<float *>(p.dev_params),
+                            adam_mv, AdamArgs{}, adam_row, stream);
     return hipGetLastError();
 }
 

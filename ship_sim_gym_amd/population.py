@@ -9,8 +9,9 @@ launch per rollout step, two launches for GAE, two per minibatch of the update â
 The handle's envs are split into P equal contiguous slices: member m owns envs [m*n, (m+1)*n), n = num_envs / P.  ``params`` is f32
 [P, L]; row m is a packed buffer of its own, and ``member(m)`` is a ``NativePolicy`` that shares it.  Hyper-parameters are per member
 (plain Python lists on ``PopulationPPO`` that a scheduler may rewrite between updates); epochs, minibatches and the batch size are common
-to the population (they shape the launches), there is no KL penalty (``NativePPO`` has none either), and a population lives on one
-handle with one architecture.
+to the population (they shape the launches), and a population lives on one handle with one architecture.  The extended loss terms of
+``NativePPO`` â€” ``vf_clip``, ``max_grad_norm``, ``kl_coef``, ``kl_target`` â€” are per member as well (``EXT_KEYS``); a member whose value
+is 0 has that term off and trains exactly as ``NativePPO`` without it.
 
 ``PBTScheduler`` is host-only (``random`` with its own seeded generator, no torch): ray 0.6's PopulationBasedTraining as the reference
 configures it, with the interval counted in updates instead of seconds of wall time.
@@ -113,15 +114,20 @@ class NativePopulation(object):
 
 
 HPARAM_KEYS = ("gamma", "lam", "clip", "vf_coef", "ent_coef", "lr", "beta1", "beta2", "eps", "adv_eps")
+# the extended update's per-member settings: lists like the ones above, except kl_coef, which is a device tensor f32 [P] (the update
+# adapts it on the device against kl_target)
+EXT_KEYS = ("vf_clip", "max_grad_norm", "kl_target")
 
 
 class PopulationPPO(object):
     """GAE and the PPO update of every member of a NativePopulation in shared launches (ssg_pop_gae / ssg_pop_update), the PBT exploit
     copy (ssg_pop_exploit) and per-member episode statistics (ssg_pop_episode_stats).  Owns the Adam moments [P, 2L], the workspace and
-    the episode carry columns.  Every hyper-parameter is a list of P floats (``self.lr[m] = ...``); defaults: NativePPO's."""
+    the episode carry columns.  Every hyper-parameter is a list of P floats (``self.lr[m] = ...``); defaults: NativePPO's.  So are
+    ``vf_clip``, ``max_grad_norm`` and ``kl_target`` (0 = off); ``kl_coef`` is given as a float or a list and kept as a device tensor
+    f32 [P] (``self.kl_coef``), since the update adapts it on the device.  With every extended setting 0 the plain entry points run."""
 
     def __init__(self, population, env, gamma=0.99, lam=0.95, clip=0.2, vf_coef=0.5, ent_coef=0.01, lr=3e-4, beta1=0.9, beta2=0.999,
-                 eps=1e-8, adv_eps=1e-8):
+                 eps=1e-8, adv_eps=1e-8, vf_clip=0.0, max_grad_norm=0.0, kl_coef=0.0, kl_target=0.0):
         torch = _torch()
         self.population, self.env = population, env
         P = len(population)
@@ -131,8 +137,8 @@ class PopulationPPO(object):
         if env.num_envs % P:
             raise ValueError("PopulationPPO: %d envs do not split into %d equal member slices" % (env.num_envs, P))
         given = dict(gamma=gamma, lam=lam, clip=clip, vf_coef=vf_coef, ent_coef=ent_coef, lr=lr, beta1=beta1, beta2=beta2, eps=eps,
-                     adv_eps=adv_eps)
-        for k in HPARAM_KEYS:
+                     adv_eps=adv_eps, vf_clip=vf_clip, max_grad_norm=max_grad_norm, kl_target=kl_target, kl_coef=kl_coef)
+        for k in HPARAM_KEYS + EXT_KEYS + ("kl_coef",):
             v = given[k]
             v = [float(x) for x in v] if isinstance(v, (list, tuple)) else [float(v)] * P
             if len(v) != P:
@@ -145,6 +151,7 @@ class PopulationPPO(object):
         self.workspace = torch.zeros(0, dtype=torch.uint8, device=dev)
         self.carry_return = torch.zeros(env.num_envs, dtype=torch.float64, device=dev)
         self.carry_length = torch.zeros(env.num_envs, dtype=torch.int32, device=dev)
+        self.kl_coef = torch.tensor(self.kl_coef, dtype=torch.float32).to(dev)  # (the list set above becomes the device tensor)
 
     # ------------------------------------------------------------------------------------------------
     def hparams(self):
@@ -218,6 +225,45 @@ class PopulationPPO(object):
         batch["adv"], batch["ret"] = adv, ret
         return adv, ret
 
+    def extended(self):
+        """True when some member has an extended term on: update() then goes through ssg_pop_update_ext."""
+        return any(v > 0.0 for k in EXT_KEYS[:2] for v in getattr(self, k)) or bool((self.kl_coef > 0).any())
+
+    def dist(self, batch):
+        """Every member's log-distribution over its columns of the batch's stored observations (ssg_pop_dist, one launch): f32
+        [K, N, 4], stored as batch["logp_all"].  With the acting parameters, logp_all.gather(act) is batch["logp"] bitwise."""
+        torch = _torch()
+        K, n_env = self._KN(batch)
+        dev, D = self.population.device, self.population.obs_dim
+        x = self._flat(batch, "obs", torch.float32, (K, n_env, D))
+        out = torch.empty((K, n_env, 4), dtype=torch.float32, device=dev)
+        pop, h = self.population.to_native(), self.env._h
+        with torch.cuda.device(dev):
+            N.check(N.lib().ssg_pop_dist(h, C.byref(pop), K, x, C.c_void_p(out.data_ptr()), self._stream()), h, "ssg_pop_dist")
+        batch["logp_all"] = out
+        return out
+
+    def _ext(self, batch, K, n_env):
+        """(the ssg_pop_ext record, the tensors it points into)"""
+        torch = _torch()
+        dev = self.population.device
+        rows = [[self.vf_clip[m], self.max_grad_norm[m], self.kl_target[m], 0.0] for m in range(self.n_members)]
+        table = torch.tensor(rows, dtype=torch.float64).to(torch.float32).to(dev)  # (rounded from double, as the library rounds)
+        ext = N.PopExt()
+        ext.struct_size = C.sizeof(N.PopExt)
+        ext.dev_ext = table.data_ptr()
+        if any(v > 0.0 for v in self.max_grad_norm):
+            ext.flags |= N.POP_EXT_GRAD_CLIP
+        if any(v > 0.0 for v in self.vf_clip):
+            ext.flags |= N.POP_EXT_VF_CLIP
+            ext.dev_value_old = self._flat(batch, "val", torch.float32, (K, n_env)).value
+        if bool((self.kl_coef > 0).any()):
+            if "logp_all" not in batch:
+                self.dist(batch)
+            ext.dev_kl_coef = self.kl_coef.data_ptr()
+            ext.dev_logp_all = self._flat(batch, "logp_all", torch.float32, (K, n_env, 4)).value
+        return ext, table
+
     def adv_stats(self):
         """f32 [P, 3] device view: per member the advantage mean, std + adv_eps and its inverse, as the last gae() left them."""
         return self.workspace[:16 * self.n_members].view(_torch().float32).view(self.n_members, 4)[:, :3]
@@ -225,7 +271,8 @@ class PopulationPPO(object):
     def update(self, batch, perm, epochs, minibatches, stats=False):
         """epochs x chunks of {gradient, Adam} for every member from ONE library call.  perm: int64 [P, epochs, K*n] â€” member m's
         minibatches are perm[m, e].chunk(minibatches), indices into ITS samples (i = t*n + e).  stats=True returns f32
-        [P, epochs * chunks, 4] (the minibatch means of the pg loss, (v - ret)^2, the entropy and the clip fraction)."""
+        [P, epochs * chunks, 4] (the minibatch means of the pg loss, (v - ret)^2, the entropy and the clip fraction); with an extended
+        term on for some member, 8 columns (NativePPO.grad's) and, at the end, the adaptation of ``kl_coef`` where kl_target > 0."""
         torch = _torch()
         K, n_env = self._KN(batch)
         P, dev, D = self.n_members, self.population.device, self.population.obs_dim
@@ -239,10 +286,20 @@ class PopulationPPO(object):
         chunk, n_chunks = chunk_split(n, minibatches)
         steps = int(epochs) * n_chunks
         self._ws(n, chunk)
-        st = torch.empty((P, steps, 4), dtype=torch.float32, device=dev) if stats else None
+        extended = self.extended()
+        st = torch.empty((P, steps, N.PPO_EXT_STATS if extended else 4), dtype=torch.float32, device=dev) if stats else None
         pop, h = self.population.to_native(), self.env._h
         with torch.cuda.device(dev):
             table = self._table(steps)
+            if extended:
+                ext, ext_table = self._ext(batch, K, n_env)
+                N.check(N.lib().ssg_pop_update_ext(h, C.byref(pop), C.byref(ext), C.c_void_p(table.data_ptr()), steps, K, *p,
+                                                   C.c_void_p(perm.data_ptr()), int(epochs), int(minibatches),
+                                                   C.c_void_p(self.adam_mv.data_ptr()), C.c_void_p(st.data_ptr()) if stats else None,
+                                                   C.c_void_p(self.workspace.data_ptr()), self.workspace.numel(), self._stream()), h,
+                        "ssg_pop_update_ext")
+                self.step += steps
+                return st
             N.check(N.lib().ssg_pop_update(h, C.byref(pop), C.c_void_p(table.data_ptr()), steps, K, *p, C.c_void_p(perm.data_ptr()),
                                            int(epochs), int(minibatches), C.c_void_p(self.adam_mv.data_ptr()),
                                            C.c_void_p(st.data_ptr()) if stats else None, C.c_void_p(self.workspace.data_ptr()),
@@ -252,7 +309,9 @@ class PopulationPPO(object):
 
     def exploit(self, src):
         """PBT's exploit on the device: member m takes the parameters and Adam moments of member src[m] (src[m] == m keeps).  A source
-        must not itself be a destination.  Hyper-parameters are the scheduler's business (PBTScheduler returns the new lists)."""
+        must not itself be a destination.  The source's ``kl_coef`` travels with its parameters: the coefficient was adapted to THOSE
+        parameters (to how far their updates move the distribution), so it belongs to the weights, not to the scheduler's
+        hyper-parameters.  Those are the scheduler's business (PBTScheduler returns the new lists)."""
         torch = _torch()
         src = [int(s) for s in src]
         if len(src) != self.n_members:
@@ -262,6 +321,7 @@ class PopulationPPO(object):
         with torch.cuda.device(self.population.device):
             N.check(N.lib().ssg_pop_exploit(h, C.byref(pop), arr, C.c_void_p(self.adam_mv.data_ptr()), self._stream()), h,
                     "ssg_pop_exploit")
+            self.kl_coef.copy_(self.kl_coef[torch.tensor(src, device=self.population.device)])
 
     def reset_episode_carry(self):
         """Forget the running episodes (call after an env reset)."""

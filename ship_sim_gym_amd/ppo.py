@@ -1,4 +1,5 @@
-"""NativePPO — GAE and the PPO update of a NativePolicy on the device (ssg_ppo_gae / ssg_ppo_grad / ssg_ppo_adam / ssg_ppo_update).
+"""NativePPO — GAE and the PPO update of a NativePolicy on the device (ssg_ppo_gae / ssg_ppo_grad / ssg_ppo_adam / ssg_ppo_update, and
+their _ext forms with the reference trainers' loss terms: value clipping, a KL penalty, gradient-norm clipping).
 
 The reference's PPO2 runs GAE and noptepochs x nminibatches of {loss, backward, Adam} after every rollout inside model.learn
 (train/stable_baselines/ppo.py:90); train/ppo_torch.py does the same in eager PyTorch.  ``NativePPO`` does it on the packed parameter
@@ -8,6 +9,12 @@ call ``policy.refresh()`` afterwards: that would copy the module's stale paramet
 
 A batch is the dict ``ShipVecEnv.rollout_policy`` returns (obs f32 [K, N, D], act i32, logp / val f32, rew f64, done u8 [K, N], last_val
 f32 [N]); ``gae`` adds "adv" and "ret" (f32 [K, N]) to it.  Sample i of the flattened batch is (t, e) = divmod(i, N).
+
+The extended terms are off by default.  ``vf_clip`` clips the value loss around the rollout's "val" (PPO2's cliprange_vf, RLlib's
+vf_clip_param), ``max_grad_norm`` is torch's clip_grad_norm_ on the whole gradient (PPO2's 0.5), ``kl_coef`` adds kl_coef * KL(old || new)
+and ``kl_target`` adapts that coefficient after every update as RLlib's update_kl does (train/rllib/pbt.py:55-62 starts it at 1.0).  The
+KL term needs the acting policy's whole distribution, batch["logp_all"] (f32 [K, N, 4]): ``dist(batch)`` computes it from the stored
+observations, and ``update`` does so itself when the batch has none — so call it BEFORE anything changes the parameters.
 """
 import ctypes as C
 
@@ -29,7 +36,8 @@ def chunk_split(n, minibatches):
 class NativePPO(object):
     """Defaults: train/ppo_torch.py's (Adam lr 3e-4, betas (0.9, 0.999), eps 1e-8; clip 0.2; loss pg + 0.5*vf - 0.01*entropy)."""
 
-    def __init__(self, policy, env, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, clip=0.2, vf_coef=0.5, ent_coef=0.01, adv_eps=1e-8):
+    def __init__(self, policy, env, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, clip=0.2, vf_coef=0.5, ent_coef=0.01, adv_eps=1e-8,
+                 vf_clip=0.0, max_grad_norm=0.0, kl_coef=0.0, kl_target=0.0):
         torch = _torch()
         self.policy, self.env = policy, env
         if env.states_history != policy.obs_dim:
@@ -43,6 +51,11 @@ class NativePPO(object):
         self.adam_mv = torch.zeros(2 * self.n_params, dtype=torch.float32, device=policy.device)  # m, then v
         self.step = 0  # Adam steps taken
         self.workspace = torch.zeros(0, dtype=torch.uint8, device=policy.device)
+        self.vf_clip, self.max_grad_norm, self.kl_target = float(vf_clip), float(max_grad_norm), float(kl_target)
+        # the KL coefficient is a device scalar: the update adapts it on the device (kl_target); 0 = no KL term
+        self.kl_coef = torch.full((1,), float(kl_coef), dtype=torch.float32, device=policy.device)
+        self._kl_on = float(kl_coef) > 0.0  # (decided here: a coefficient of 0 at construction is "no KL term")
+        self.force_ext = False  # True: the _ext entry points even with every term off (they then compute what the plain ones do)
 
     # ------------------------------------------------------------------------------------------------
     def _ws(self, n_samples, max_minibatch):
@@ -84,6 +97,44 @@ class NativePPO(object):
                 raise ValueError("NativePPO: batch[%r] has %d entries, the batch %d samples" % (k, batch[k].numel(), n))
         return n, ptrs
 
+    def extended(self):
+        """True when any of the extended terms is on: grad / update then go through the _ext entry points."""
+        return self.force_ext or self.vf_clip > 0.0 or self.max_grad_norm > 0.0 or self._kl_on
+
+    def dist(self, batch):
+        """The log-distribution of the CURRENT parameters over the batch's stored observations (ssg_ppo_dist): f32 [K, N, 4], columns
+        >= n_actions zero; stored as batch["logp_all"].  With the acting parameters, logp_all.gather(act) is batch["logp"] bitwise."""
+        torch = _torch()
+        x = self._flat(batch, "obs", torch.float32)
+        n = x.numel() // self.policy.obs_dim
+        out = torch.empty(tuple(x.shape[:-1]) + (4,), dtype=torch.float32, device=self.policy.device)
+        pol, h = self.policy.to_native(), self.env._h
+        with torch.cuda.device(self.policy.device):
+            N.check(N.lib().ssg_ppo_dist(h, C.byref(pol), n, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), self._stream()), h,
+                    "ssg_ppo_dist")
+        batch["logp_all"] = out
+        return out
+
+    def _ext(self, batch, n):
+        """The ssg_ppo_ext record over this object's settings and the batch's buffers."""
+        torch = _torch()
+        ext = N.PpoExt()
+        ext.struct_size = C.sizeof(N.PpoExt)
+        ext.vf_clip, ext.max_grad_norm, ext.kl_target = self.vf_clip, self.max_grad_norm, self.kl_target
+        if self._kl_on:
+            if "logp_all" not in batch:
+                self.dist(batch)
+            la = self._flat(batch, "logp_all", torch.float32)
+            if la.numel() != 4 * n:
+                raise ValueError("NativePPO: batch['logp_all'] has %d entries, the batch %d samples x 4" % (la.numel(), n))
+            ext.dev_kl_coef, ext.dev_logp_all = self.kl_coef.data_ptr(), la.data_ptr()
+        if self.vf_clip > 0.0:
+            val = self._flat(batch, "val", torch.float32)
+            if val.numel() != n:
+                raise ValueError("NativePPO: batch['val'] has %d entries, the batch %d samples" % (val.numel(), n))
+            ext.dev_value_old = val.data_ptr()
+        return ext
+
     # ------------------------------------------------------------------------------------------------
     def gae(self, batch, gamma=0.99, lam=0.95):
         """GAE over the rollout batch (train/ppo_torch.py's loop, bitwise): returns (adv, ret) f32 [K, N] and stores them in the batch
@@ -113,17 +164,25 @@ class NativePPO(object):
 
     def grad(self, batch, idx, stats=False):
         """The gradient (f32 [P], the packed layout) of the PPO loss over the samples idx (int64) of a batch gae() has seen; with
-        stats=True also the minibatch means (pg loss, (v - ret)^2, entropy, clip fraction) as f32 [4]."""
+        stats=True also the minibatch means (pg loss, (v - ret)^2, entropy, clip fraction) as f32 [4].  With an extended term on: the
+        extended loss's (unclipped) gradient and f32 [8] stats (plus mean KL, the gradient norm, the KL coefficient, 0)."""
         torch = _torch()
         n, p = self._samples(batch)
         idx = idx.to(device=self.policy.device, dtype=torch.int64).contiguous()
         M = idx.numel()
         self._ws(n, M)
         g = torch.empty(self.n_params, dtype=torch.float32, device=self.policy.device)
-        st = torch.empty(4, dtype=torch.float32, device=self.policy.device) if stats else None
+        ncol = N.PPO_EXT_STATS if self.extended() else 4
+        st = torch.empty(ncol, dtype=torch.float32, device=self.policy.device) if stats else None
         ws, nb = self._ws_ptr()
         pol, h = self.policy.to_native(), self.env._h
         with torch.cuda.device(self.policy.device):
+            if self.extended():
+                ext = self._ext(batch, n)
+                N.check(N.lib().ssg_ppo_grad_ext(h, C.byref(pol), C.byref(self.hp), C.byref(ext), n, *p, C.c_void_p(idx.data_ptr()), M,
+                                                 C.c_void_p(g.data_ptr()), C.c_void_p(st.data_ptr()) if stats else None, ws, nb,
+                                                 self._stream()), h, "ssg_ppo_grad_ext")
+                return (g, st) if stats else g
             N.check(N.lib().ssg_ppo_grad(h, C.byref(pol), C.byref(self.hp), n, *p, C.c_void_p(idx.data_ptr()), M, C.c_void_p(g.data_ptr()),
                                          C.c_void_p(st.data_ptr()) if stats else None, ws, nb, self._stream()), h, "ssg_ppo_grad")
         return (g, st) if stats else g
@@ -142,7 +201,9 @@ class NativePPO(object):
 
     def update(self, batch, perm, epochs, minibatches, stats=False):
         """epochs x minibatches of {gradient, Adam} from ONE library call: the minibatches are perm[e].chunk(minibatches) (perm: int64
-        [epochs, K*N], e.g. torch.randperm rows).  stats=True returns f32 [epochs * chunks, 4] (grad()'s stats per minibatch)."""
+        [epochs, K*N], e.g. torch.randperm rows).  stats=True returns f32 [epochs * chunks, 4] (grad()'s stats per minibatch; 8 columns
+        with an extended term on).  With the KL term on and no batch["logp_all"], the distribution is taken first, from the parameters
+        as they are on entry; with kl_target > 0 the call ends by adapting ``kl_coef`` on the device."""
         torch = _torch()
         n, p = self._samples(batch)
         perm = perm.to(device=self.policy.device, dtype=torch.int64).contiguous()
@@ -150,10 +211,19 @@ class NativePPO(object):
             raise ValueError("NativePPO.update: perm must be int64 [epochs, %d] (got %s)" % (n, tuple(perm.shape)))
         chunk, n_chunks = chunk_split(n, minibatches)
         self._ws(n, chunk)
-        st = torch.empty((int(epochs) * n_chunks, 4), dtype=torch.float32, device=self.policy.device) if stats else None
+        ncol = N.PPO_EXT_STATS if self.extended() else 4
+        st = torch.empty((int(epochs) * n_chunks, ncol), dtype=torch.float32, device=self.policy.device) if stats else None
         ws, nb = self._ws_ptr()
         pol, h = self.policy.to_native(), self.env._h
         with torch.cuda.device(self.policy.device):
+            if self.extended():
+                ext = self._ext(batch, n)
+                N.check(N.lib().ssg_ppo_update_ext(h, C.byref(pol), C.byref(self.hp), C.byref(ext), n, *p, C.c_void_p(perm.data_ptr()),
+                                                   int(epochs), int(minibatches), C.c_void_p(self.adam_mv.data_ptr()), self.step,
+                                                   C.c_void_p(st.data_ptr()) if stats else None, ws, nb, self._stream()), h,
+                        "ssg_ppo_update_ext")
+                self.step += int(epochs) * n_chunks
+                return st
             N.check(N.lib().ssg_ppo_update(h, C.byref(pol), C.byref(self.hp), n, *p, C.c_void_p(perm.data_ptr()), int(epochs),
                                            int(minibatches), C.c_void_p(self.adam_mv.data_ptr()), self.step,
                                            C.c_void_p(st.data_ptr()) if stats else None, ws, nb, self._stream()), h, "ssg_ppo_update")

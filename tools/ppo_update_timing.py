@@ -8,7 +8,10 @@ For each (envs, horizon) — default 65 536 x 32 and 4 096 x 64; default env (D 
 every update from the same parameters' values (their own copies) and draw their permutations from generators seeded alike.  One JSON
 line on stdout.  The kernels alone: `rocprofv3 --kernel-trace --stats -- python tools/ppo_update_timing.py --only native` (tools/README.md).
 
-    python tools/ppo_update_timing.py [--configs 65536x32,4096x64] [--repeats 7] [--only torch|native]
+    python tools/ppo_update_timing.py [--configs 65536x32,4096x64] [--repeats 7] [--only torch|native] [--ext]
+
+--ext adds, in the same run, the extended update (NativePPO with vf_clip 0.2, max_grad_norm 0.5, kl_coef 1.0, kl_target 0.01: GAE, the
+ssg_ppo_dist launch, ssg_ppo_update_ext) as the path "native_ext", and the ssg_ppo_dist launch alone as "dist".
 """
 import argparse
 import importlib.util
@@ -70,7 +73,7 @@ def torch_update(net, opt, b, horizon, envs, D, epochs, minibatches, gen, gamma=
             opt.step()
 
 
-def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4):
+def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext=False):
     from ship_sim_gym_amd.policy import NativePolicy
     from ship_sim_gym_amd.ppo import NativePPO
     torch.manual_seed(0)
@@ -107,7 +110,26 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4):
         ppo.gae(nb)
         ppo.update(nb, torch.stack([torch.randperm(n, device=dev, generator=g_n) for _ in range(epochs)]), epochs, minibatches)
 
+    ppo_x = NativePPO(pol, env, vf_clip=0.2, max_grad_norm=0.5, kl_coef=1.0, kl_target=0.01)
+    g_x = torch.Generator(device=dev)
+    g_x.manual_seed(1)
+
+    def run_native_ext():
+        with torch.no_grad():
+            for p, q in zip(net_n.parameters(), p0):
+                p.copy_(q)
+        pol.refresh()
+        ppo_x.kl_coef.fill_(1.0)
+        nb = dict(b)
+        ppo_x.gae(nb)
+        ppo_x.update(nb, torch.stack([torch.randperm(n, device=dev, generator=g_x) for _ in range(epochs)]), epochs, minibatches)
+
+    def run_dist():
+        ppo_x.dist(dict(b))
+
     paths = [(k, f) for k, f in (("torch", run_torch), ("native", run_native)) if only in (None, k)]
+    if ext:
+        paths += [("native_ext", run_native_ext), ("dist", run_dist)]
     times = {k: [] for k, _ in paths}
     for _ in range(2):
         for k, f in paths:
@@ -130,9 +152,10 @@ def main():
     ap.add_argument("--configs", default="65536x32,4096x64")
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--only", choices=("torch", "native"), default=None)
+    ap.add_argument("--ext", action="store_true", help="also time the extended update (all three terms on) and ssg_ppo_dist alone")
     a = ap.parse_args()
     mod = _ppo()
-    res = [measure(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.repeats, a.only, "cuda:0") for c in a.configs.split(",")]
+    res = [measure(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.repeats, a.only, "cuda:0", ext=a.ext) for c in a.configs.split(",")]
     print(json.dumps({"ppo_update_timing": res}))
 
 

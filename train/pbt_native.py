@@ -18,7 +18,11 @@ What differs from the reference, on purpose:
   that trains in lockstep has no per-trial clock, and a count makes runs reproducible);
 * of the six mutated hyper-parameters only lambda, clip_param and lr vary per member: num_sgd_iter, sgd_minibatch_size and
   train_batch_size shape the launches and are common to the population (--epochs, --minibatches, --horizon);
-* no kl_coeff (the device's PPO loss has no KL penalty), one handle on one GPU, one architecture.
+* one handle on one GPU, one architecture.
+
+The loss terms of the reference trainers' own PPO are opt-in: --kl-coeff 1.0 is the reference's setting (train/rllib/pbt.py:55-62; the
+coefficient then adapts per member against --kl-target, as RLlib's update_kl does, and travels with the weights on an exploit),
+--vf-clip is RLlib's vf_clip_param / PPO2's cliprange_vf, --max-grad-norm PPO2's 0.5.  Without them a run is the plain clipped loss.
 
 Logged per update: every member's episode_reward_mean (over the episodes that ended since the last perturbation); per perturbation:
 each exploit (member <- source) and each mutation (key, resample / perturb, old -> new).
@@ -44,6 +48,10 @@ def make_arg_parser():
     ap.add_argument("--minibatches", type=int, default=4)
     ap.add_argument("--lrs", default=None, help="comma-separated learning rates, one member each (overrides --members)")
     ap.add_argument("--no-pbt", dest="pbt", action="store_false", help="no exploit / explore: a plain sweep")
+    ap.add_argument("--kl-coeff", type=float, default=0.0, help="initial KL penalty coefficient (the reference: 1.0; 0 = no KL term)")
+    ap.add_argument("--kl-target", type=float, default=0.01, help="the coefficient adapts against this mean KL (RLlib's default)")
+    ap.add_argument("--vf-clip", type=float, default=0.0, help="value-loss clip range (0 = off)")
+    ap.add_argument("--max-grad-norm", type=float, default=0.0, help="global gradient-norm clip (PPO2: 0.5; 0 = off)")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -56,11 +64,13 @@ def parse_args(argv=None):
         a.members = len(a.lrs)
     if a.members < 1 or a.envs_per_member < 1 or a.updates < 1 or a.horizon < 1 or a.perturb_every < 1:
         ap.error("--members, --envs-per-member, --updates, --horizon and --perturb-every must be >= 1")
+    if a.kl_coeff < 0 or a.kl_target < 0 or a.vf_clip < 0 or a.max_grad_norm < 0:
+        ap.error("--kl-coeff, --kl-target, --vf-clip and --max-grad-norm must be >= 0")
     return a
 
 
 def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every=5, seed=0, epochs=2, minibatches=4, lrs=None,
-          pbt=True, device="cuda:0", log=print, return_details=False):
+          pbt=True, device="cuda:0", log=print, return_details=False, kl_coeff=0.0, kl_target=0.01, vf_clip=0.0, max_grad_norm=0.0):
     import torch
     from ship_gym.config import EnvConfig, GameConfig
     from ship_sim_gym_amd.population import NativePopulation, PBTScheduler, PopulationPPO
@@ -85,7 +95,8 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
     nets = [ActorCritic(D, A).to(dev) for _ in range(P)]
     scale = torch.full((D,), float(max(env.bounds)), dtype=torch.float64, device=dev)
     pop = NativePopulation.from_actor_critics(nets, scale)
-    ppo = PopulationPPO(pop, env, lam=INITIAL["lambda"], clip=INITIAL["clip_param"], lr=list(lrs) if lrs is not None else INITIAL["lr"])
+    ppo = PopulationPPO(pop, env, lam=INITIAL["lambda"], clip=INITIAL["clip_param"], lr=list(lrs) if lrs is not None else INITIAL["lr"],
+                        vf_clip=vf_clip, max_grad_norm=max_grad_norm, kl_coef=kl_coeff, kl_target=kl_target if kl_coeff > 0 else 0.0)
     sched = PBTScheduler(P, seed=seed, perturbation_interval=perturb_every)
     env.reset_tensor()
     window = torch.zeros((P, 3), dtype=torch.int64, device=dev)  # episodes since the last perturbation
@@ -95,7 +106,7 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
     for u in range(1, updates + 1):
         uniforms = torch.rand((horizon, P * n), generator=gen, device=dev)
         batch = env.rollout_population(pop, horizon, uniforms=uniforms, out=out)
-        out = {k: v for k, v in batch.items() if k not in ("adv", "ret")}
+        out = {k: v for k, v in batch.items() if k not in ("adv", "ret", "logp_all")}
         window += ppo.episode_stats(batch)
         ppo.gae(batch)
         perm = torch.rand((P, epochs, samples), generator=gen, device=dev).argsort(dim=-1)
@@ -118,7 +129,8 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
     torch.cuda.synchronize(dev)
     pop.load_into(nets)
     details = {"params": pop.params.detach().clone(), "exploits": exploits, "nets": nets,
-               "hparams": {"lambda": list(ppo.lam), "clip_param": list(ppo.clip), "lr": list(ppo.lr)}}
+               "hparams": {"lambda": list(ppo.lam), "clip_param": list(ppo.clip), "lr": list(ppo.lr)},
+               "kl_coef": ppo.kl_coef.detach().cpu().tolist()}
     env.close()
     return (history, details) if return_details else history
 
@@ -126,7 +138,8 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
 def main(argv=None):
     a = parse_args(argv)
     train(members=a.members, envs_per_member=a.envs_per_member, updates=a.updates, horizon=a.horizon, perturb_every=a.perturb_every,
-          seed=a.seed, epochs=a.epochs, minibatches=a.minibatches, lrs=a.lrs, pbt=a.pbt, device=a.device)
+          seed=a.seed, epochs=a.epochs, minibatches=a.minibatches, lrs=a.lrs, pbt=a.pbt, device=a.device, kl_coeff=a.kl_coeff,
+          kl_target=a.kl_target, vf_clip=a.vf_clip, max_grad_norm=a.max_grad_norm)
 
 
 if __name__ == "__main__":
