@@ -97,6 +97,8 @@ def lib():
         L.ora_world_get_ship.argtypes = [C.c_void_p, C.POINTER(Body)]
         L.ora_world_place_ship.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
         L.ora_world_space_step.argtypes = [C.c_void_p]
+        L.ora_world_poke_player.argtypes = [C.c_void_p, dp]
+        L.ora_world_poke_episode.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.ora_polys_collide.restype = C.c_int
         L.ora_polys_collide.argtypes = [C.POINTER(Poly), C.POINTER(Poly)]
         L.ora_circle_poly_collide.restype = C.c_int
@@ -357,6 +359,16 @@ class Batch:
         lib().ora_world_get_ship(w, C.byref(b))
         b.p = V2(float(x), float(y)); b.v = V2(float(vx), float(vy))
         lib().ora_world_set_ship(w, C.byref(b))
+
+    def poke_state(self, i, x, y, angle, vx=0.0, vy=0.0, w=0.0):
+        """Env i's player at pose (x, y, angle) with velocity (vx, vy, w), as a test writes the SSG_F_X, F_Y, F_ANGLE, F_VX, F_VY
+        and F_W columns (place_player is the case at rest)."""
+        lib().ora_world_poke_player(lib().ora_world_at(self._p, int(i)), _dp(np.array([x, y, angle, vx, vy, w], dtype=np.float64)))
+
+    def poke_episode(self, i, goal_mask, step_count):
+        """Env i's listed goals and step count, as a test writes the SSG_F_GOAL_MASK and SSG_F_STEP_COUNT columns: listed goals
+        whose bit is clear in goal_mask leave the list unreached (config 4: their bodies leave the space with them)."""
+        lib().ora_world_poke_episode(lib().ora_world_at(self._p, int(i)), int(goal_mask), int(step_count))
 
     def counters(self):
         """ORA_VAR_CHECK_SAT census summed over the batch: player pairs checked, SAT != cpCollide(player, other),

@@ -687,6 +687,19 @@ void ora_dyn_collide_solve(ora_world *w, int reached_mask)
     }
 }
 
+/* space.remove(goal shape, body) for the goals of `gone_mask` (original indices), outside a step: the body leaves the space and
+ * the shape's cached arbiters go with it, as after a step in which the player reached them */
+void ora_dyn_remove_goals(ora_world *w, int gone_mask)
+{
+    ora_dyn *d = &w->dyn;
+    for (int g = 0; g < w->cfg.n_goals; g++) {
+        if (!(gone_mask >> g & 1) || !(d->goal_in_space >> g & 1)) continue;
+        d->goal_in_space &= ~(1 << g);
+        for (int s = 0; s < ORA_N_SLOTS; s++)
+            if (s != ORA_SLOT_GOAL0 + g) arb_at(w, ORA_SLOT_GOAL0 + g, s)->state = ORA_ARB_NONE;
+    }
+}
+
 void ora_world_peek_dyn(const ora_world *w, double *o)
 {
     const ora_dyn *d = &w->dyn;

@@ -597,6 +597,31 @@ void ora_world_place_ship(ora_world *w, double x, double y, double a)
     b->rot = V(cos(a), sin(a));
     ora_poly_update(&w->ship_shape, b->p, b->rot);
 }
+/* The player at pose (x, y, a) with velocity (vx, vy, w): v6 = x, y, angle, vx, vy, w, as a caller that writes the SSG_F_X, F_Y,
+ * F_ANGLE, F_VX, F_VY and F_W columns of the HIP state does (ora_world_place_ship is the case at rest) */
+void ora_world_poke_player(ora_world *w, const double *v6)
+{
+    ora_body *b = &w->ship;
+    ora_world_place_ship(w, v6[0], v6[1], v6[2]);
+    b->v = V(v6[3], v6[4]);
+    b->w = v6[5];
+}
+/* The episode's bookkeeping as a caller that writes the SSG_F_GOAL_MASK and SSG_F_STEP_COUNT columns does: the goals still listed
+ * whose bit is clear in goal_mask leave the list (list order kept, nothing is reported as reached), step_count is set.  Config 4:
+ * their bodies leave the space with them. */
+void ora_world_poke_episode(ora_world *w, int goal_mask, int step_count)
+{
+    int n = 0;
+    if (w->cfg.n_traffic > 0) ora_dyn_remove_goals(w, ~goal_mask);
+    for (int g = 0; g < w->n_goals_alive; g++) {
+        if (!((goal_mask >> w->goal_id[g]) & 1)) continue;
+        w->goal_p[n] = w->goal_p[g];
+        w->goal_id[n] = w->goal_id[g];
+        n++;
+    }
+    w->n_goals_alive = n;
+    w->step_count = step_count;
+}
 /* ShipGame.update's `self.space.step(dt)` alone: cpSpaceStep with the begin-callbacks' effects (colliding, goal_reached, the
  * goal list), without the action, the lidar and the ShipEnv bookkeeping around it */
 void ora_world_space_step(ora_world *w)

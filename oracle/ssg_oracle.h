@@ -173,6 +173,8 @@ int ora_circle_segment_query(ora_v2 center, double r1, ora_v2 a, ora_v2 b, doubl
 void ora_world_set_ship(ora_world *w, const ora_body *b);
 void ora_world_get_ship(const ora_world *w, ora_body *b);
 void ora_world_place_ship(ora_world *w, double x, double y, double a);
+void ora_world_poke_player(ora_world *w, const double *v6);          /* x, y, angle, vx, vy, w */
+void ora_world_poke_episode(ora_world *w, int goal_mask, int step_count);
 void ora_world_space_step(ora_world *w);
 
 /* ---- world ---- */
@@ -210,6 +212,7 @@ void ora_world_census(const ora_world *w, double *out);
 void ora_dyn_reset(ora_world *w);
 void ora_dyn_integrate(ora_world *w);
 void ora_dyn_collide_solve(ora_world *w, int reached_mask);
+void ora_dyn_remove_goals(ora_world *w, int gone_mask);
 /* narrowphase exposed for unit tests: cpCollide(a, b) restated.  Returns the contact count (0..2) and fills
  * n, and per contact the absolute points p1/p2 and the hash. */
 int ora_collide_poly_poly(const ora_poly *a, const ora_poly *b, int slot_a, int slot_b, ora_v2 *n, ora_v2 *p1,
