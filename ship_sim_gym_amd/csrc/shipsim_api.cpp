@@ -1082,15 +1082,13 @@ static int check_hparams(ssg_handle *h, const ssg_ppo_hparams *hp, const char *w
 }
 
 static size_t ppo_need_gae(long long N) { return ssg::kPpoSlotsOff + (size_t)ssg::ppo_gae_blocks(N) * 16; }
-static size_t ppo_need_grad(const ssg_policy &p, long long M)
+// the workspace of one gradient minibatch of M samples for `members` policies, slots from slots_off (kPpoSlotsOff / kPopSlotsOff); ext:
+// slots of P + kExtStats floats behind the clip sequence's vector, partials and the KL sum
+static size_t need_grad(size_t slots_off, int members, const ssg_policy &p, long long M, bool ext)
 {
-    return ssg::kPpoSlotsOff + (size_t)ssg::ppo_grid(M) * (size_t)(ssg::ppo_packed_len(p) + 4) * sizeof(float);
-}
-
-// the extended update's workspace (slots of P + kExtStats floats behind the clip sequence's vector, partials and the KL sum)
-static size_t ppo_need_grad_ext(const ssg_policy &p, long long M)
-{
-    return ssg::ppo_ext_layout(ssg::kPpoSlotsOff, 1, ssg::ppo_grid(M), ssg::ppo_packed_len(p)).end;
+    const int G = ssg::ppo_grid(M), P = ssg::ppo_packed_len(p);
+    if (ext) return ssg::ppo_ext_layout(slots_off, members, G, P).end;
+    return slots_off + (size_t)members * (size_t)G * (size_t)(P + 4) * sizeof(float);
 }
 
 static int check_workspace(ssg_handle *h, const void *ws, size_t nbytes, size_t need, const char *what)
@@ -1119,7 +1117,8 @@ int ssg_ppo_workspace_nbytes(const ssg_policy *pol, int64_t n_samples, int64_t m
 {
     if (!nbytes || !check_policy_shape(pol) || n_samples < 1 || max_minibatch < 1)
         return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_ppo_workspace_nbytes: bad policy record, NULL nbytes or a size < 1");
-    *nbytes = std::max(ppo_need_gae(n_samples), std::max(ppo_need_grad(*pol, max_minibatch), ppo_need_grad_ext(*pol, max_minibatch)));
+    *nbytes = std::max(ppo_need_gae(n_samples), std::max(need_grad(ssg::kPpoSlotsOff, 1, *pol, max_minibatch, false),
+                                                         need_grad(ssg::kPpoSlotsOff, 1, *pol, max_minibatch, true)));
     return SSG_OK;
 }
 
@@ -1142,12 +1141,72 @@ int ssg_ppo_gae(ssg_handle *h, const ssg_ppo_hparams *hp, int K, int N, const do
     return SSG_OK;
 }
 
-static int check_batch(ssg_handle *h, int64_t n_samples, const float *x, const int32_t *act, const float *logp, const float *adv,
-                       const float *ret, const void *idx, const char *what)
+static int check_batch(ssg_handle *h, int64_t n_samples, const ssg::PpoBatch &b, const void *idx, const char *what)
 {
-    if (!x || !act || !logp || !adv || !ret || !idx)
+    if (!b.x || !b.act || !b.logp || !b.adv || !b.ret || !idx)
         return fail(h, SSG_ERR_BAD_ARG, std::string(what) + ": NULL x, act, logp, adv, ret or index buffer");
     if (n_samples < 1) return fail(h, SSG_ERR_BAD_ARG, std::string(what) + ": n_samples < 1");
+    return SSG_OK;
+}
+
+// The minibatch record of ONE policy's entry points, but for what changes per call or per minibatch (idx, M, step, the outputs, ext).
+static ssg::PpoMinibatch one_policy(const ssg_policy *pol, const ssg_ppo_hparams *hp, int64_t n_samples, const ssg::PpoBatch &batch, void *ws)
+{
+    ssg::PpoMinibatch mb = {};
+    mb.policy = pol;
+    mb.members = 1;
+    mb.n_samples = n_samples;
+    mb.batch = batch;
+    mb.ws = ws;
+    mb.slots_off = ssg::kPpoSlotsOff;
+    mb.hp = hp;
+    return mb;
+}
+
+// torch.chunk of n samples into `minibatches`: chunks of C = ceil(n / minibatches), the last one shorter — so ceil(n / C) of them
+struct Chunking {
+    long long C, chunks;
+};
+static Chunking chunking(long long n, int minibatches)
+{
+    const long long C = (n + minibatches - 1) / minibatches;
+    return {C, (n + C - 1) / C};
+}
+
+// The epochs x chunks loop of the four update entry points.  mb: the record as its entry point filled it, with idx = the [epochs][n]
+// permutation rows (a population: [members][epochs][n]), stats_out = the caller's stats rows or NULL, step = the Adam steps taken so
+// far, table = a population's table; ext: nullable.  Minibatch j of the call reads chunk j % chunks of permutation row j / chunks,
+// takes Adam step step + 1 + j (a population: the table's Adam rows 1 + j) and writes stats row j.  kl_adapt: end with the
+// adaptation of the coefficient(s) from the last epoch's chunks.  what: the entry point's name in a launch failure's message.
+static int run_update(ssg_handle *h, ssg::PpoMinibatch mb, ssg::PpoExtLaunch *ext, int epochs, int minibatches, bool kl_adapt, float kl_target,
+                      const char *what, hipStream_t st)
+{
+    const long long n = mb.n_samples;
+    const Chunking ck = chunking(n, minibatches);
+    const int cols = ext ? ssg::kExtStats : 4;
+    const int64_t *perm = mb.idx;
+    float *stats = mb.stats_out;
+    mb.ext = ext;
+    mb.idx_stride = (long long)epochs * n;
+    mb.stats_stride = cols * (long long)epochs * ck.chunks;
+    long long j = 0;
+    for (int ep = 0; ep < epochs; ++ep) {
+        for (long long b0 = 0; b0 < n; b0 += ck.C, ++j) {
+            mb.M = std::min(ck.C, n - b0);
+            mb.idx = perm + (size_t)ep * (size_t)n + (size_t)b0;
+            mb.stats_out = stats ? stats + cols * j : nullptr;
+            ++mb.step;
+            if (mb.table) mb.adam_row = mb.table + (size_t)(1 + j) * (size_t)mb.members * ssg::kPopTableRow;
+            if (ext) ext->first_chunk = b0 == 0;
+            hipError_t e = ssg::launch_ppo_minibatch(mb, st);
+            if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+        }
+    }
+    if (kl_adapt) {
+        hipError_t e = ssg::launch_kl_adapt(mb.members, *ext, kl_target, ssg::ppo_packed_len(*mb.policy), ck.chunks, mb.ws, mb.slots_off, st);
+        if (e != hipSuccess)
+            return fail(h, SSG_ERR_HIP, std::string(mb.table ? "population kl adapt launch: " : "kl adapt launch: ") + hipGetErrorString(e));
+    }
     return SSG_OK;
 }
 
@@ -1155,19 +1214,24 @@ int ssg_ppo_grad(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp
                  const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret, const int64_t *dev_idx,
                  int64_t M, float *dev_grad, float *dev_stats, void *dev_workspace, size_t workspace_nbytes, void *stream)
 {
+    const ssg::PpoBatch batch = {dev_x, dev_act, dev_logp, dev_adv, dev_ret};
     int rc = check_ready(h, false);
     if (rc != SSG_OK) return rc;
     rc = check_policy(h, pol, "ssg_ppo_grad");
     if (rc == SSG_OK) rc = check_hparams(h, hp, "ssg_ppo_grad");
-    if (rc == SSG_OK) rc = check_batch(h, n_samples, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_idx, "ssg_ppo_grad");
+    if (rc == SSG_OK) rc = check_batch(h, n_samples, batch, dev_idx, "ssg_ppo_grad");
     if (rc != SSG_OK) return rc;
     if (!dev_grad) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_grad: NULL dev_grad");
     if (M < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_grad: M < 1");
-    rc = check_workspace(h, dev_workspace, workspace_nbytes, ppo_need_grad(*pol, M), "ssg_ppo_grad");
+    rc = check_workspace(h, dev_workspace, workspace_nbytes, need_grad(ssg::kPpoSlotsOff, 1, *pol, M, false), "ssg_ppo_grad");
     if (rc == SSG_OK) rc = prepare_ppo(h);
     if (rc != SSG_OK) return rc;
-    hipError_t e = ssg::launch_ppo_grad(*pol, *hp, n_samples, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_idx, M, dev_workspace,
-                                        dev_grad, dev_stats, nullptr, 0, static_cast<hipStream_t>(stream));
+    ssg::PpoMinibatch mb = one_policy(pol, hp, n_samples, batch, dev_workspace);
+    mb.idx = dev_idx;
+    mb.M = M;
+    mb.grad_out = dev_grad;
+    mb.stats_out = dev_stats;
+    hipError_t e = ssg::launch_ppo_minibatch(mb, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("ppo grad launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
@@ -1192,30 +1256,25 @@ int ssg_ppo_update(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *
                    int epochs, int minibatches, float *dev_adam_mv, int64_t step0, float *dev_stats, void *dev_workspace,
                    size_t workspace_nbytes, void *stream)
 {
+    const ssg::PpoBatch batch = {dev_x, dev_act, dev_logp, dev_adv, dev_ret};
     int rc = check_ready(h, false);
     if (rc != SSG_OK) return rc;
     rc = check_policy(h, pol, "ssg_ppo_update");
     if (rc == SSG_OK) rc = check_hparams(h, hp, "ssg_ppo_update");
-    if (rc == SSG_OK) rc = check_batch(h, n_samples, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_perm, "ssg_ppo_update");
+    if (rc == SSG_OK) rc = check_batch(h, n_samples, batch, dev_perm, "ssg_ppo_update");
     if (rc != SSG_OK) return rc;
     if (!dev_adam_mv) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_update: NULL dev_adam_mv");
     if (epochs < 1 || minibatches < 1 || step0 < 0) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_update: epochs < 1, minibatches < 1 or step0 < 0");
-    const long long n = n_samples, C = (n + minibatches - 1) / minibatches; // torch.chunk: chunks of ceil(n / minibatches)
-    rc = check_workspace(h, dev_workspace, workspace_nbytes, ppo_need_grad(*pol, C), "ssg_ppo_update");
+    const size_t need = need_grad(ssg::kPpoSlotsOff, 1, *pol, chunking(n_samples, minibatches).C, false);
+    rc = check_workspace(h, dev_workspace, workspace_nbytes, need, "ssg_ppo_update");
     if (rc == SSG_OK) rc = prepare_ppo(h);
     if (rc != SSG_OK) return rc;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    int64_t step = step0, j = 0;
-    for (int ep = 0; ep < epochs; ++ep) {
-        for (long long b0 = 0; b0 < n; b0 += C, ++j) {
-            const long long M = std::min(C, n - b0);
-            hipError_t e = ssg::launch_ppo_grad(*pol, *hp, n_samples, dev_x, dev_act, dev_logp, dev_adv, dev_ret,
-                                                dev_perm + (size_t)ep * (size_t)n + (size_t)b0, M, dev_workspace, nullptr,
-                                                dev_stats ? dev_stats + 4 * j : nullptr, dev_adam_mv, ++step, st);
-            if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("ppo update launch: ") + hipGetErrorString(e));
-        }
-    }
-    return SSG_OK;
+    ssg::PpoMinibatch mb = one_policy(pol, hp, n_samples, batch, dev_workspace);
+    mb.idx = dev_perm;
+    mb.stats_out = dev_stats;
+    mb.adam_mv = dev_adam_mv;
+    mb.step = step0;
+    return run_update(h, mb, nullptr, epochs, minibatches, false, 0.0f, "ppo update", static_cast<hipStream_t>(stream));
 }
 
 // ABI 9 additions: a population of policies on one handle.  Order of the refusals: no handle (BAD_ARG), no state blob (NOT_BOUND), then
@@ -1294,6 +1353,20 @@ static ssg::PpoExtLaunch ext_launch(const ssg_ppo_ext &ext)
     return e;
 }
 
+// a population's: the members' constants are rows of dev_ext, the flags say which terms some member has on
+static ssg::PpoExtLaunch ext_launch(const ssg_pop_ext &ext)
+{
+    ssg::PpoExtLaunch e;
+    e.kl_coef = ext.dev_kl_coef;
+    e.logp_all = ext.dev_kl_coef ? ext.dev_logp_all : nullptr;
+    e.value_old = (ext.flags & SSG_POP_EXT_VF_CLIP) ? ext.dev_value_old : nullptr;
+    e.pop_ext = ext.dev_ext;
+    e.vf_clip = e.max_grad_norm = 0.0f; // (per member: dev_ext)
+    e.clip_seq = (ext.flags & SSG_POP_EXT_GRAD_CLIP) != 0;
+    e.first_chunk = true;
+    return e;
+}
+
 int ssg_ppo_dist(ssg_handle *h, const ssg_policy *pol, int64_t n_samples, const float *dev_x, float *dev_logp_all, void *stream)
 {
     int rc = pop_bound(h);
@@ -1314,20 +1387,27 @@ int ssg_ppo_grad_ext(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams
                      const int64_t *dev_idx, int64_t M, float *dev_grad, float *dev_stats, void *dev_workspace, size_t workspace_nbytes,
                      void *stream)
 {
+    const ssg::PpoBatch batch = {dev_x, dev_act, dev_logp, dev_adv, dev_ret};
     int rc = pop_bound(h);
     if (rc == SSG_OK) rc = check_policy(h, pol, "ssg_ppo_grad_ext");
     if (rc == SSG_OK) rc = check_hparams(h, hp, "ssg_ppo_grad_ext");
     if (rc == SSG_OK) rc = check_ext(h, ext, "ssg_ppo_grad_ext");
-    if (rc == SSG_OK) rc = check_batch(h, n_samples, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_idx, "ssg_ppo_grad_ext");
+    if (rc == SSG_OK) rc = check_batch(h, n_samples, batch, dev_idx, "ssg_ppo_grad_ext");
     if (rc != SSG_OK) return rc;
     if (!dev_grad) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_grad_ext: NULL dev_grad");
     if (M < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_grad_ext: M < 1");
-    rc = check_workspace(h, dev_workspace, workspace_nbytes, ppo_need_grad_ext(*pol, M), "ssg_ppo_grad_ext");
+    rc = check_workspace(h, dev_workspace, workspace_nbytes, need_grad(ssg::kPpoSlotsOff, 1, *pol, M, true), "ssg_ppo_grad_ext");
     if (rc == SSG_OK) rc = check_ready(h, false);
     if (rc == SSG_OK) rc = prepare_ppo(h);
     if (rc != SSG_OK) return rc;
-    hipError_t e = ssg::launch_ppo_grad_ext(*pol, *hp, ext_launch(*ext), n_samples, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_idx, M,
-                                            dev_workspace, dev_grad, dev_stats, nullptr, 0, static_cast<hipStream_t>(stream));
+    const ssg::PpoExtLaunch el = ext_launch(*ext);
+    ssg::PpoMinibatch mb = one_policy(pol, hp, n_samples, batch, dev_workspace);
+    mb.idx = dev_idx;
+    mb.M = M;
+    mb.ext = &el;
+    mb.grad_out = dev_grad;
+    mb.stats_out = dev_stats;
+    hipError_t e = ssg::launch_ppo_minibatch(mb, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("ppo grad_ext launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
@@ -1337,37 +1417,28 @@ int ssg_ppo_update_ext(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hpara
                        const int64_t *dev_perm, int epochs, int minibatches, float *dev_adam_mv, int64_t step0, float *dev_stats,
                        void *dev_workspace, size_t workspace_nbytes, void *stream)
 {
+    const ssg::PpoBatch batch = {dev_x, dev_act, dev_logp, dev_adv, dev_ret};
     int rc = pop_bound(h);
     if (rc == SSG_OK) rc = check_policy(h, pol, "ssg_ppo_update_ext");
     if (rc == SSG_OK) rc = check_hparams(h, hp, "ssg_ppo_update_ext");
     if (rc == SSG_OK) rc = check_ext(h, ext, "ssg_ppo_update_ext");
-    if (rc == SSG_OK) rc = check_batch(h, n_samples, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_perm, "ssg_ppo_update_ext");
+    if (rc == SSG_OK) rc = check_batch(h, n_samples, batch, dev_perm, "ssg_ppo_update_ext");
     if (rc != SSG_OK) return rc;
     if (!dev_adam_mv) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_update_ext: NULL dev_adam_mv");
     if (epochs < 1 || minibatches < 1 || step0 < 0) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_update_ext: epochs < 1, minibatches < 1 or step0 < 0");
-    const long long n = n_samples, C = (n + minibatches - 1) / minibatches, chunks = (n + C - 1) / C; // torch.chunk
-    rc = check_workspace(h, dev_workspace, workspace_nbytes, ppo_need_grad_ext(*pol, C), "ssg_ppo_update_ext");
+    const size_t need = need_grad(ssg::kPpoSlotsOff, 1, *pol, chunking(n_samples, minibatches).C, true);
+    rc = check_workspace(h, dev_workspace, workspace_nbytes, need, "ssg_ppo_update_ext");
     if (rc == SSG_OK) rc = check_ready(h, false);
     if (rc == SSG_OK) rc = prepare_ppo(h);
     if (rc != SSG_OK) return rc;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
     ssg::PpoExtLaunch el = ext_launch(*ext);
-    int64_t step = step0, j = 0;
-    for (int ep = 0; ep < epochs; ++ep) {
-        for (long long b0 = 0; b0 < n; b0 += C, ++j) {
-            const long long M = std::min(C, n - b0);
-            el.first_chunk = b0 == 0;
-            hipError_t e = ssg::launch_ppo_grad_ext(*pol, *hp, el, n_samples, dev_x, dev_act, dev_logp, dev_adv, dev_ret,
-                                                    dev_perm + (size_t)ep * (size_t)n + (size_t)b0, M, dev_workspace, nullptr,
-                                                    dev_stats ? dev_stats + ssg::kExtStats * j : nullptr, dev_adam_mv, ++step, st);
-            if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("ppo update_ext launch: ") + hipGetErrorString(e));
-        }
-    }
-    if (ext->kl_target > 0.0 && ext->dev_kl_coef) {
-        hipError_t e = ssg::launch_kl_adapt(1, el, (float)ext->kl_target, ssg::ppo_packed_len(*pol), chunks, dev_workspace, ssg::kPpoSlotsOff, st);
-        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("kl adapt launch: ") + hipGetErrorString(e));
-    }
-    return SSG_OK;
+    ssg::PpoMinibatch mb = one_policy(pol, hp, n_samples, batch, dev_workspace);
+    mb.idx = dev_perm;
+    mb.stats_out = dev_stats;
+    mb.adam_mv = dev_adam_mv;
+    mb.step = step0;
+    return run_update(h, mb, &el, epochs, minibatches, ext->kl_target > 0.0 && ext->dev_kl_coef, (float)ext->kl_target, "ppo update_ext",
+                      static_cast<hipStream_t>(stream));
 }
 
 int ssg_pop_act(ssg_handle *h, const ssg_population *pop, const double *dev_obs, const float *dev_uniform, uint64_t seed, int64_t step,
@@ -1445,23 +1516,14 @@ int ssg_pop_pack_hparams(int n_members, const ssg_ppo_hparams *hparams, int64_t 
 }
 
 static size_t pop_need_gae(int P, long long n) { return ssg::kPopSlotsOff + (size_t)P * (size_t)ssg::ppo_gae_blocks(n) * 16; }
-static size_t pop_need_grad(const ssg_policy &p, int P, long long M)
-{
-    return ssg::kPopSlotsOff + (size_t)P * (size_t)ssg::ppo_grid(M) * (size_t)(ssg::ppo_packed_len(p) + 4) * sizeof(float);
-}
-
-static size_t pop_need_grad_ext(const ssg_policy &p, int P, long long M)
-{
-    return ssg::ppo_ext_layout(ssg::kPopSlotsOff, P, ssg::ppo_grid(M), ssg::ppo_packed_len(p)).end;
-}
-
 int ssg_pop_workspace_nbytes(const ssg_population *pop, int64_t samples_per_member, int64_t max_minibatch, size_t *nbytes)
 {
     if (!nbytes || !pop_shape_ok(pop) || samples_per_member < 1 || max_minibatch < 1)
         return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_workspace_nbytes: bad population record, n_members out of range, NULL nbytes or a size < 1");
+    const ssg_policy pol = pop_policy(*pop);
     *nbytes = std::max(pop_need_gae(pop->n_members, samples_per_member),
-                       std::max(pop_need_grad(pop_policy(*pop), pop->n_members, max_minibatch),
-                                pop_need_grad_ext(pop_policy(*pop), pop->n_members, max_minibatch)));
+                       std::max(need_grad(ssg::kPopSlotsOff, pop->n_members, pol, max_minibatch, false),
+                                need_grad(ssg::kPopSlotsOff, pop->n_members, pol, max_minibatch, true)));
     return SSG_OK;
 }
 
@@ -1485,42 +1547,58 @@ int ssg_pop_gae(ssg_handle *h, const ssg_population *pop, const float *dev_table
     return SSG_OK;
 }
 
+// What ssg_pop_update and ssg_pop_update_ext refuse alike once the population record (and the ext record) passed, in their order;
+// then the minibatch record of the population's update, but for what run_update sets per minibatch.
+static int check_pop_update(ssg_handle *h, const ssg_policy *pol, int P, const float *dev_table, int table_steps, int K,
+                            const ssg::PpoBatch &batch, const int64_t *dev_perm, int epochs, int minibatches, float *dev_adam_mv,
+                            const char *what, ssg::PpoMinibatch *mb)
+{
+    const std::string w(what);
+    if (K < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": K < 1");
+    const int N = h->cfg.n_envs;
+    const long long n = (long long)K * (N / P); // samples per member
+    int rc = check_batch(h, n, batch, dev_perm, what);
+    if (rc != SSG_OK) return rc;
+    if (!dev_table || !dev_adam_mv) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_table or dev_adam_mv");
+    if (epochs < 1 || minibatches < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": epochs < 1 or minibatches < 1");
+    if ((long long)table_steps < (long long)epochs * chunking(n, minibatches).chunks)
+        return fail(h, SSG_ERR_BAD_ARG, w + ": the table holds fewer Adam steps than epochs * chunks");
+    *mb = {};
+    mb->policy = pol;
+    mb->members = P;
+    mb->n = N / P;
+    mb->N = N;
+    mb->n_samples = n;
+    mb->batch = batch;
+    mb->idx = dev_perm;
+    mb->slots_off = ssg::kPopSlotsOff;
+    mb->table = dev_table;
+    mb->adam_mv = dev_adam_mv;
+    return SSG_OK;
+}
+
 int ssg_pop_update(ssg_handle *h, const ssg_population *pop, const float *dev_table, int table_steps, int K, const float *dev_x,
                    const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret, const int64_t *dev_perm,
                    int epochs, int minibatches, float *dev_adam_mv, float *dev_stats, void *dev_workspace, size_t workspace_nbytes,
                    void *stream)
 {
+    const ssg::PpoBatch batch = {dev_x, dev_act, dev_logp, dev_adv, dev_ret};
     int rc = pop_bound(h);
     if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_update");
     if (rc != SSG_OK) return rc;
-    if (K < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update: K < 1");
-    const int P = pop->n_members, N = h->cfg.n_envs;
-    const long long n = (long long)K * (N / P); // samples per member
-    rc = check_batch(h, n, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_perm, "ssg_pop_update");
-    if (rc != SSG_OK) return rc;
-    if (!dev_table || !dev_adam_mv) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update: NULL dev_table or dev_adam_mv");
-    if (epochs < 1 || minibatches < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update: epochs < 1 or minibatches < 1");
-    const long long C = (n + minibatches - 1) / minibatches, chunks = (n + C - 1) / C; // torch.chunk
-    if ((long long)table_steps < (long long)epochs * chunks)
-        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update: the table holds fewer Adam steps than epochs * chunks");
     const ssg_policy pol = pop_policy(*pop);
-    rc = check_workspace(h, dev_workspace, workspace_nbytes, pop_need_grad(pol, P, C), "ssg_pop_update");
+    const int P = pop->n_members;
+    ssg::PpoMinibatch mb;
+    rc = check_pop_update(h, &pol, P, dev_table, table_steps, K, batch, dev_perm, epochs, minibatches, dev_adam_mv, "ssg_pop_update", &mb);
+    if (rc != SSG_OK) return rc;
+    const size_t need = need_grad(ssg::kPopSlotsOff, P, pol, chunking(mb.n_samples, minibatches).C, false);
+    rc = check_workspace(h, dev_workspace, workspace_nbytes, need, "ssg_pop_update");
     if (rc == SSG_OK) rc = check_ready(h, false);
     if (rc == SSG_OK) rc = prepare_ppo(h);
     if (rc != SSG_OK) return rc;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    long long j = 0;
-    for (int ep = 0; ep < epochs; ++ep) {
-        for (long long b0 = 0; b0 < n; b0 += C, ++j) {
-            const long long M = std::min(C, n - b0);
-            hipError_t e = ssg::launch_pop_grad(pol, P, K, N, dev_table, dev_table + (size_t)(1 + j) * (size_t)P * ssg::kPopTableRow, dev_x,
-                                                dev_act, dev_logp, dev_adv, dev_ret, dev_perm + (size_t)ep * (size_t)n + (size_t)b0,
-                                                (long long)epochs * n, M, dev_workspace, dev_stats ? dev_stats + 4 * j : nullptr,
-                                                4 * (long long)epochs * chunks, dev_adam_mv, st);
-            if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population update launch: ") + hipGetErrorString(e));
-        }
-    }
-    return SSG_OK;
+    mb.ws = dev_workspace;
+    mb.stats_out = dev_stats;
+    return run_update(h, mb, nullptr, epochs, minibatches, false, 0.0f, "population update", static_cast<hipStream_t>(stream));
 }
 
 int ssg_pop_dist(ssg_handle *h, const ssg_population *pop, int K, const float *dev_x, float *dev_logp_all, void *stream)
@@ -1544,6 +1622,7 @@ int ssg_pop_update_ext(ssg_handle *h, const ssg_population *pop, const ssg_pop_e
                        const int64_t *dev_perm, int epochs, int minibatches, float *dev_adam_mv, float *dev_stats, void *dev_workspace,
                        size_t workspace_nbytes, void *stream)
 {
+    const ssg::PpoBatch batch = {dev_x, dev_act, dev_logp, dev_adv, dev_ret};
     int rc = pop_bound(h);
     if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_update_ext");
     if (rc != SSG_OK) return rc;
@@ -1554,48 +1633,21 @@ int ssg_pop_update_ext(ssg_handle *h, const ssg_population *pop, const ssg_pop_e
     if (ext->dev_kl_coef && !ext->dev_logp_all) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: dev_kl_coef without dev_logp_all (ssg_pop_dist)");
     if ((ext->flags & SSG_POP_EXT_VF_CLIP) && !ext->dev_value_old)
         return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: SSG_POP_EXT_VF_CLIP without dev_value_old");
-    if (K < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: K < 1");
-    const int P = pop->n_members, N = h->cfg.n_envs;
-    const long long n = (long long)K * (N / P); // samples per member
-    rc = check_batch(h, n, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_perm, "ssg_pop_update_ext");
-    if (rc != SSG_OK) return rc;
-    if (!dev_table || !dev_adam_mv) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: NULL dev_table or dev_adam_mv");
-    if (epochs < 1 || minibatches < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: epochs < 1 or minibatches < 1");
-    const long long C = (n + minibatches - 1) / minibatches, chunks = (n + C - 1) / C; // torch.chunk
-    if ((long long)table_steps < (long long)epochs * chunks)
-        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: the table holds fewer Adam steps than epochs * chunks");
     const ssg_policy pol = pop_policy(*pop);
-    rc = check_workspace(h, dev_workspace, workspace_nbytes, pop_need_grad_ext(pol, P, C), "ssg_pop_update_ext");
+    const int P = pop->n_members;
+    ssg::PpoMinibatch mb;
+    rc = check_pop_update(h, &pol, P, dev_table, table_steps, K, batch, dev_perm, epochs, minibatches, dev_adam_mv, "ssg_pop_update_ext", &mb);
+    if (rc != SSG_OK) return rc;
+    const size_t need = need_grad(ssg::kPopSlotsOff, P, pol, chunking(mb.n_samples, minibatches).C, true);
+    rc = check_workspace(h, dev_workspace, workspace_nbytes, need, "ssg_pop_update_ext");
     if (rc == SSG_OK) rc = check_ready(h, false);
     if (rc == SSG_OK) rc = prepare_ppo(h);
     if (rc != SSG_OK) return rc;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    ssg::PpoExtLaunch el;
-    el.kl_coef = ext->dev_kl_coef;
-    el.logp_all = ext->dev_kl_coef ? ext->dev_logp_all : nullptr;
-    el.value_old = (ext->flags & SSG_POP_EXT_VF_CLIP) ? ext->dev_value_old : nullptr;
-    el.pop_ext = ext->dev_ext;
-    el.vf_clip = el.max_grad_norm = 0.0f; // (per member: dev_ext)
-    el.clip_seq = (ext->flags & SSG_POP_EXT_GRAD_CLIP) != 0;
-    el.first_chunk = true;
-    long long j = 0;
-    for (int ep = 0; ep < epochs; ++ep) {
-        for (long long b0 = 0; b0 < n; b0 += C, ++j) {
-            const long long M = std::min(C, n - b0);
-            el.first_chunk = b0 == 0;
-            hipError_t e = ssg::launch_pop_grad_ext(pol, P, K, N, dev_table, dev_table + (size_t)(1 + j) * (size_t)P * ssg::kPopTableRow, el,
-                                                    dev_x, dev_act, dev_logp, dev_adv, dev_ret,
-                                                    dev_perm + (size_t)ep * (size_t)n + (size_t)b0, (long long)epochs * n, M, dev_workspace,
-                                                    dev_stats ? dev_stats + ssg::kExtStats * j : nullptr,
-                                                    ssg::kExtStats * (long long)epochs * chunks, dev_adam_mv, st);
-            if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population update_ext launch: ") + hipGetErrorString(e));
-        }
-    }
-    if (ext->dev_kl_coef) {
-        hipError_t e = ssg::launch_kl_adapt(P, el, 0.0f, ssg::ppo_packed_len(pol), chunks, dev_workspace, ssg::kPopSlotsOff, st);
-        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population kl adapt launch: ") + hipGetErrorString(e));
-    }
-    return SSG_OK;
+    ssg::PpoExtLaunch el = ext_launch(*ext);
+    mb.ws = dev_workspace;
+    mb.stats_out = dev_stats;
+    return run_update(h, mb, &el, epochs, minibatches, ext->dev_kl_coef != nullptr, 0.0f, "population update_ext",
+                      static_cast<hipStream_t>(stream));
 }
 
 int ssg_pop_exploit(ssg_handle *h, const ssg_population *pop, const int32_t *src, float *dev_adam_mv, void *stream)

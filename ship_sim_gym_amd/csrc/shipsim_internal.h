@@ -217,11 +217,6 @@ size_t ppo_grad_lds_bytes(const ssg_policy &p);
 hipError_t prepare_ppo(); // (the dynamic-LDS limit of the gradient kernel: up to 151 KB at obs_dim 176, hidden 128, 2 layers)
 hipError_t launch_ppo_gae(const ssg_ppo_hparams &hp, int K, int N, const double *rew, const uint8_t *done, const float *val,
                           const float *last_val, float *adv, float *ret, void *ws, hipStream_t stream);
-// the gradient of one minibatch into the workspace's slots, then their sum: into grad_out (nullable) and, with adam_mv, Adam step
-// `step` on p.dev_params; stats_out (nullable): the minibatch's loss means
-hipError_t launch_ppo_grad(const ssg_policy &p, const ssg_ppo_hparams &hp, long long n_samples, const float *x, const int32_t *act,
-                           const float *logp, const float *adv, const float *ret, const int64_t *idx, long long M, void *ws,
-                           float *grad_out, float *stats_out, float *adam_mv, int64_t step, hipStream_t stream);
 hipError_t launch_ppo_adam(const ssg_policy &p, const ssg_ppo_hparams &hp, const float *grad, float *adam_mv, int64_t step,
                            hipStream_t stream);
 // A population of `members` policies on one handle (ssg_pop_*): p is the shared shape with dev_params = f32 [members][L]; member m owns
@@ -237,12 +232,6 @@ hipError_t launch_policy_pop(const ssg_policy &p, int members, int n, long long 
 void pop_pack(int members, const ssg_ppo_hparams *hp, int64_t step0, int n_steps, float *out); // host only
 hipError_t launch_pop_gae(int members, int K, int N, const float *table, const double *rew, const uint8_t *done, const float *val,
                           const float *last_val, float *adv, float *ret, void *ws, hipStream_t stream);
-// one minibatch of every member: the gradients (member m's indices at idx + m*idx_stride, member-local), then reduce + Adam with the
-// step's table rows adam_row; stats_out (nullable): member m's row at stats_out + m*stats_stride
-hipError_t launch_pop_grad(const ssg_policy &p, int members, long long K, long long N, const float *table, const float *adam_row,
-                           const float *x, const int32_t *act, const float *logp, const float *adv, const float *ret,
-                           const int64_t *idx, long long idx_stride, long long M, void *ws, float *stats_out, long long stats_stride,
-                           float *adam_mv, hipStream_t stream);
 hipError_t launch_pop_exploit(const ssg_policy &p, int members, const int32_t *src, float *adam_mv, hipStream_t stream);
 // The extended update (ssg_ppo_grad_ext / ssg_ppo_update_ext / ssg_pop_update_ext): value clip, KL penalty, gradient-norm clip.
 // From the plain path's slot offset the workspace holds the running sum of the epoch's mean(KL) (f32 [members]), the gradient vector of
@@ -276,14 +265,35 @@ struct PpoExtLaunch {
     bool first_chunk;                  // the minibatch is the first of its epoch (restarts the running KL sum)
 };
 size_t ppo_grad_ext_lds_bytes(const ssg_policy &p);
-// as launch_ppo_grad / launch_pop_grad, with stats rows of kExtStats floats
-hipError_t launch_ppo_grad_ext(const ssg_policy &p, const ssg_ppo_hparams &hp, const PpoExtLaunch &ext, long long n_samples, const float *x,
-                               const int32_t *act, const float *logp, const float *adv, const float *ret, const int64_t *idx, long long M,
-                               void *ws, float *grad_out, float *stats_out, float *adam_mv, int64_t step, hipStream_t stream);
-hipError_t launch_pop_grad_ext(const ssg_policy &p, int members, long long K, long long N, const float *table, const float *adam_row,
-                               const PpoExtLaunch &ext, const float *x, const int32_t *act, const float *logp, const float *adv,
-                               const float *ret, const int64_t *idx, long long idx_stride, long long M, void *ws, float *stats_out,
-                               long long stats_stride, float *adam_mv, hipStream_t stream);
+// the five per-sample columns of a batch (device): rows t*N + e of the [K][N] rollout buffers, x with obs_dim floats per row
+struct PpoBatch {
+    const float *x;
+    const int32_t *act;
+    const float *logp, *adv, *ret;
+};
+// One minibatch of `members` policies: the gradients into the workspace's slots, then per member their sum — into grad_out (nullable)
+// and, with adam_mv, one Adam step on its parameter row — and the minibatch's loss means into stats_out (nullable; member m's row at
+// stats_out + m*stats_stride; 4 floats, kExtStats with ext).  The constants are ONE policy's (hp, and the Adam step number `step`;
+// table NULL, members 1, n / N / idx_stride unused) or a population's (table: its loss rows, adam_row: this step's Adam rows).
+struct PpoMinibatch {
+    const ssg_policy *policy; // the shape; dev_params = f32 [members][P]
+    int members;
+    long long n, N;           // envs per member and of the batch: member m's sample i = t*n + e is row t*N + m*n + e
+    long long n_samples;      // samples per member (an index outside [0, n_samples) is a zero, gradient-free sample)
+    PpoBatch batch;
+    const int64_t *idx;       // M indices (member-local); member m's at idx + m*idx_stride
+    long long idx_stride, M;
+    void *ws;
+    size_t slots_off;         // kPpoSlotsOff or kPopSlotsOff
+    const ssg_ppo_hparams *hp;
+    int64_t step;
+    const float *table, *adam_row;
+    const PpoExtLaunch *ext;  // nullable: the extended loss and reduction
+    float *grad_out, *stats_out;
+    long long stats_stride;
+    float *adam_mv;
+};
+hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream);
 // RLlib's update_kl on every member's coefficient from the last epoch's `chunks` minibatches 
 hipError_t launch_kl_adapt(int members, const PpoExtLaunch &ext, float kl_target, int P, long long chunks, void *ws, size_t slots_off,
                            hipStream_t stream);

@@ -103,9 +103,9 @@ __global__ void __launch_bounds__(256) ppo_gae_kernel(int K, int N, const double
     gae_body(K, N, N, rew, done, val, last_val, adv_out, ret_out, gf, glf, part, rs, rq);
 }
 
-// The per-member constants of a population (ssg_pop_pack_hparams derives them on the host, in double, exactly as launch_ppo_gae,
-// launch_ppo_grad and adam_args do for one policy): kPopTableRow floats per member — lo, hi, clip, vf, ent, adv_eps, gamma, gamma*lam —
-// then per Adam step kPopTableRow floats per member: AdamArgs' seven fields.
+// The per-member constants of a population (ssg_pop_pack_hparams derives them on the host with loss_row and adam_args, the functions
+// one policy's launches take theirs from): kPopTableRow floats per member — lo, hi, clip, vf, ent, adv_eps, gamma, gamma*lam — then
+// per Adam step kPopTableRow floats per member: AdamArgs' seven fields (adam_to_row).
 enum { PT_LO = 0, PT_HI, PT_CLIP, PT_VF, PT_ENT, PT_ADV_EPS, PT_GF, PT_GLF };
 
 // GAE of a population: member m = blockIdx.y owns columns [m*n, (m+1)*n) of the [K][N] buffers, walks them with its own gamma /
@@ -555,10 +555,6 @@ struct AdamArgs {
     float w1, one_minus_w1, beta2, w2, bc2_sqrt, eps, step_size;
 };
 
-// POP = false: the launch of ssg_ppo_grad / ssg_ppo_adam / ssg_ppo_update (stats_stride, adam unused).  POP = true: reduce + Adam of
-// every member in one launch, grid (ceil(stride / 256), members): member m = blockIdx.y sums its own G slots, writes its stats row
-// (stats_out + m*stats_stride, nullable) and steps parameter row m / moments row m with ITS Adam constants of this step (adam row m:
-// the host's doubles, rounded as adam_args rounds them).
 // the sum of entry p over the G slots in order, 64 at a time as a tree of 4 trees of 16 (the missing ones are zeros)
 __device__ __forceinline__ float slot_sum(const float *__restrict__ slots, int G, int stride, int p)
 {
@@ -594,10 +590,21 @@ __device__ __forceinline__ void adam_apply(const AdamArgs &ad, float s, int p, i
     params[p] = params[p] + ad.step_size * (m / den);
 }
 
-// member m's Adam constants of this step: row m of the step's table rows
-__device__ __forceinline__ AdamArgs adam_row(const float *__restrict__ adam, size_t m)
+// AdamArgs as kPopTableRow floats of the population's table (pop_pack writes a row per member and step, the kernels read theirs)
+inline void adam_to_row(const AdamArgs &ad, float *row)
 {
-    const float *row = adam + m * kPopTableRow;
+    row[0] = ad.w1;
+    row[1] = ad.one_minus_w1;
+    row[2] = ad.beta2;
+    row[3] = ad.w2;
+    row[4] = ad.bc2_sqrt;
+    row[5] = ad.eps;
+    row[6] = ad.step_size;
+    row[7] = 0.0f;
+}
+
+__device__ __forceinline__ AdamArgs adam_from_row(const float *__restrict__ row)
+{
     AdamArgs ad;
     ad.w1 = row[0];
     ad.one_minus_w1 = row[1];
@@ -609,30 +616,17 @@ __device__ __forceinline__ AdamArgs adam_row(const float *__restrict__ adam, siz
     return ad;
 }
 
-template <bool POP>
-__global__ void __launch_bounds__(256) ppo_reduce_kernel(const float *__restrict__ slots, int G, int P, int stride, float fM,
-                                                         float *__restrict__ grad_out, float *__restrict__ stats_out,
-                                                         float *__restrict__ params, float *__restrict__ mv, const AdamArgs ad_,
-                                                         long long stats_stride, const float *__restrict__ adam)
+// A population's launch, member m = blockIdx.y: its Adam constants of this step (row m of the step's table rows), its run of `run`
+// floats of vec (the slots, or the clip sequence's gradient vector), its stats row, parameter row and moment rows.
+__device__ __forceinline__ void member_rows(size_t m, int P, size_t run, long long stats_stride, const float *__restrict__ adam, AdamArgs &ad,
+                                            const float *__restrict__ &vec, float *__restrict__ &stats_out, float *__restrict__ &params,
+                                            float *__restrict__ &mv)
 {
-    AdamArgs ad = ad_;
-    if (POP) {
-        const size_t m = blockIdx.y;
-        ad = adam_row(adam, m);
-        slots += m * (size_t)G * (size_t)stride;
-        if (stats_out) stats_out += m * (size_t)stats_stride;
-        params += m * (size_t)P;
-        mv += m * 2 * (size_t)P;
-    }
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= stride) return;
-    const float s = slot_sum(slots, G, stride, p);
-    if (p >= P) {
-        if (stats_out) stats_out[p - P] = s / fM;
-        return;
-    }
-    if (grad_out) grad_out[p] = s;
-    if (params) adam_apply(ad, s, p, P, params, mv);
+    ad = adam_from_row(adam + m * kPopTableRow);
+    vec += m * run;
+    if (stats_out) stats_out += m * (size_t)stats_stride;
+    if (params) params += m * (size_t)P;
+    if (mv) mv += m * 2 * (size_t)P;
 }
 
 // What the extended update adds to the reduction (stride = P + kExtStats).  The stats row is f32 [kExtStats]: the five loss means,
@@ -647,38 +641,41 @@ struct ExtReduceArgs {
     double *part;         // f64 [members][gridDim.x]
 };
 
-template <bool POP>
-__global__ void __launch_bounds__(256) ppo_reduce_ext_kernel(const float *__restrict__ slots, int G, int P, int stride, float fM,
-                                                             float *__restrict__ grad_out, float *__restrict__ stats_out,
-                                                             float *__restrict__ params, float *__restrict__ mv, const AdamArgs ad_,
-                                                             long long stats_stride, const float *__restrict__ adam,
-                                                             const ExtReduceArgs ea)
+// POP = false: one policy's launch (stats_stride, adam unused).  POP = true: reduce + Adam of every member in one launch, grid
+// (ceil(stride / 256), members): member m = blockIdx.y sums its own G slots, writes its stats row (stats_out + m*stats_stride,
+// nullable) and steps parameter row m / moments row m with ITS Adam constants of this step (adam row m: the host's doubles, rounded
+// as adam_args rounds them).
+// EXT = false: stats rows of 4 loss means (stride = P + 4, or P for ssg_ppo_adam's G = 1), ea and sq unused.  EXT = true: see
+// ExtReduceArgs; sq is the workgroup's 256 doubles of LDS.
+template <bool POP, bool EXT>
+__device__ __forceinline__ void ppo_reduce_body(const float *__restrict__ slots, int G, int P, int stride, float fM, float *__restrict__ grad_out,
+                                                float *__restrict__ stats_out, float *__restrict__ params, float *__restrict__ mv,
+                                                const AdamArgs &ad_, long long stats_stride, const float *__restrict__ adam,
+                                                const ExtReduceArgs &ea, double *sq)
 {
-    __shared__ double sq[256];
     AdamArgs ad = ad_;
     const size_t m = POP ? blockIdx.y : 0;
-    if (POP) {
-        if (adam) ad = adam_row(adam, m);
-        slots += m * (size_t)G * (size_t)stride;
-        if (stats_out) stats_out += m * (size_t)stats_stride;
-        if (params) params += m * (size_t)P;
-        if (mv) mv += m * 2 * (size_t)P;
-    }
+    if (POP) member_rows(m, P, (size_t)G * (size_t)stride, stats_stride, adam, ad, slots, stats_out, params, mv);
     const int p = blockIdx.x * 256 + threadIdx.x;
+    if (!EXT && p >= stride) return; // (EXT: every lane stays for the barriers of the sum of squares)
     const float s = p < stride ? slot_sum(slots, G, stride, p) : 0.0f;
     if (p >= P && p < stride) {
         const int q = p - P;
-        const float klc = ea.kl_coef ? ea.kl_coef[m] : 0.0f;
         const float mean = s / fM;
-        if (stats_out) stats_out[q] = q < 5 ? mean : (q == 6 ? (klc > 0.0f ? klc : 0.0f) : 0.0f);
-        if (q == 4) ea.klacc[m] = ea.first_chunk ? mean : ea.klacc[m] + mean;
+        if (!EXT) {
+            if (stats_out) stats_out[q] = mean;
+        } else {
+            const float klc = ea.kl_coef ? ea.kl_coef[m] : 0.0f;
+            if (stats_out) stats_out[q] = q < 5 ? mean : (q == 6 ? (klc > 0.0f ? klc : 0.0f) : 0.0f);
+            if (q == 4) ea.klacc[m] = ea.first_chunk ? mean : ea.klacc[m] + mean;
+        }
     }
     if (p < P) {
         if (grad_out) grad_out[p] = s;
-        if (ea.gvec) ea.gvec[m * (size_t)P + p] = s;
+        if (EXT && ea.gvec) ea.gvec[m * (size_t)P + p] = s;
         else if (params) adam_apply(ad, s, p, P, params, mv);
     }
-    if (ea.gvec) { // the workgroup's sum of squares, f64, a fixed tree
+    if (EXT && ea.gvec) { // the workgroup's sum of squares, f64, a fixed tree
         sq[threadIdx.x] = p < P ? (double)s * (double)s : 0.0;
         __syncthreads();
         for (int w = 128; w > 0; w >>= 1) {
@@ -687,6 +684,26 @@ __global__ void __launch_bounds__(256) ppo_reduce_ext_kernel(const float *__rest
         }
         if (threadIdx.x == 0) ea.part[m * (size_t)gridDim.x + blockIdx.x] = sq[0];
     }
+}
+
+template <bool POP>
+__global__ void __launch_bounds__(256) ppo_reduce_kernel(const float *__restrict__ slots, int G, int P, int stride, float fM,
+                                                         float *__restrict__ grad_out, float *__restrict__ stats_out,
+                                                         float *__restrict__ params, float *__restrict__ mv, const AdamArgs ad,
+                                                         long long stats_stride, const float *__restrict__ adam)
+{
+    ppo_reduce_body<POP, false>(slots, G, P, stride, fM, grad_out, stats_out, params, mv, ad, stats_stride, adam, ExtReduceArgs{}, nullptr);
+}
+
+template <bool POP>
+__global__ void __launch_bounds__(256) ppo_reduce_ext_kernel(const float *__restrict__ slots, int G, int P, int stride, float fM,
+                                                             float *__restrict__ grad_out, float *__restrict__ stats_out,
+                                                             float *__restrict__ params, float *__restrict__ mv, const AdamArgs ad,
+                                                             long long stats_stride, const float *__restrict__ adam,
+                                                             const ExtReduceArgs ea)
+{
+    __shared__ double sq[256];
+    ppo_reduce_body<POP, true>(slots, G, P, stride, fM, grad_out, stats_out, params, mv, ad, stats_stride, adam, ea, sq);
 }
 
 // The third launch of the clip sequence, grid (ceil(P / 256), members): every workgroup adds the member's nb partial sums of squares
@@ -702,11 +719,8 @@ __global__ void __launch_bounds__(256) ppo_clip_kernel(const float *__restrict__
     AdamArgs ad = ad_;
     const size_t m = POP ? blockIdx.y : 0;
     if (POP) {
-        if (adam) ad = adam_row(adam, m);
+        member_rows(m, P, (size_t)P, stats_stride, adam, ad, gvec, stats_out, params, mv);
         max_grad_norm = pop_ext[m * kPopExtRow + 1];
-        if (stats_out) stats_out += m * (size_t)stats_stride;
-        if (params) params += m * (size_t)P;
-        if (mv) mv += m * 2 * (size_t)P;
     }
     double sum = 0.0;
     for (int b = 0; b < nb; ++b) sum += part[m * (size_t)nb + b];
@@ -715,7 +729,7 @@ __global__ void __launch_bounds__(256) ppo_clip_kernel(const float *__restrict__
     const float coef = on ? fminf(1.0f, max_grad_norm / (norm + 1e-6f)) : 1.0f;
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p == 0 && stats_out) stats_out[5] = on ? norm : 0.0f;
-    if (p < P && params) adam_apply(ad, gvec[m * (size_t)P + p] * coef, p, P, params, mv);
+    if (p < P && params) adam_apply(ad, gvec[p] * coef, p, P, params, mv);
 }
 
 // The last launch of an extended update with a KL target, one workgroup, lane m = member m: RLlib's update_kl on the f32 mean of the
@@ -791,6 +805,21 @@ __global__ void __launch_bounds__(256) pop_episode_stats_kernel(int K, int N, in
     if (threadIdx.x < 3 && red[2][0] != 0) atomicAdd(out + (size_t)blockIdx.y * 3 + threadIdx.x, (unsigned long long)red[threadIdx.x][0]);
 }
 
+// One policy's row of loss / GAE constants (PT_*), f32 from the caller's doubles: torch rounds a Python scalar to f32 when it meets
+// an f32 tensor; 1 - clip, 1 + clip and gamma * lam are formed in double first.  The one place these roundings are written: a
+// population's table rows (pop_pack) and one policy's kernel arguments (launch_ppo_minibatch) both come from here.
+void loss_row(const ssg_ppo_hparams &hp, float *row)
+{
+    row[PT_LO] = (float)(1.0 - hp.clip);
+    row[PT_HI] = (float)(1.0 + hp.clip);
+    row[PT_CLIP] = (float)hp.clip;
+    row[PT_VF] = (float)hp.vf_coef;
+    row[PT_ENT] = (float)hp.ent_coef;
+    row[PT_ADV_EPS] = (float)hp.adv_eps;
+    row[PT_GF] = (float)hp.gamma;
+    row[PT_GLF] = (float)(hp.gamma * hp.lam);
+}
+
 AdamArgs adam_args(const ssg_ppo_hparams &hp, int64_t step)
 {
     const double bc1 = 1.0 - std::pow(hp.beta1, (double)step), bc2 = 1.0 - std::pow(hp.beta2, (double)step);
@@ -847,18 +876,25 @@ hipError_t launch_ppo_gae(const ssg_ppo_hparams &hp, int K, int N, const double 
     const int nb = ppo_gae_blocks(N);
     float *stats = reinterpret_cast<float *>(static_cast<char *>(ws) + kPpoStatsOff);
     double2 *part = reinterpret_cast<double2 *>(static_cast<char *>(ws) + kPpoSlotsOff);
-    // torch rounds a Python scalar to f32 when it multiplies an f32 tensor; gamma * lam is formed in double first
-    hipLaunchKernelGGL(ppo_gae_kernel, dim3(nb), dim3(256), 0, stream, K, N, rew, done, val, last_val, adv, ret, (float)hp.gamma,
-                       (float)(hp.gamma * hp.lam), part);
+    float row[kPopTableRow];
+    loss_row(hp, row);
+    hipLaunchKernelGGL(ppo_gae_kernel, dim3(nb), dim3(256), 0, stream, K, N, rew, done, val, last_val, adv, ret, row[PT_GF], row[PT_GLF],
+                       part);
     hipLaunchKernelGGL(ppo_gae_stats_kernel, dim3(1), dim3(256), 0, stream, (const double2 *)part, nb, (double)K * (double)N,
-                       (float)hp.adv_eps, stats);
+                       row[PT_ADV_EPS], stats);
     return hipGetLastError();
 }
 
-hipError_t launch_ppo_grad(const ssg_policy &p, const ssg_ppo_hparams &hp, long long n_samples, const float *x, const int32_t *act,
-                           const float *logp, const float *adv, const float *ret, const int64_t *idx, long long M, void *ws,
-                           float *grad_out, float *stats_out, float *adam_mv, int64_t step, hipStream_t stream)
+hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream)
 {
+    const ssg_policy &p = *mb.policy;
+    const bool pop = mb.table != nullptr; // a population reads its constants from the table: the POP instantiations
+    const PpoExtLaunch *ext = mb.ext;
+    const int P = ppo_packed_len(p), G = ppo_grid(mb.M), stride = P + (ext ? kExtStats : 4);
+    char *base = static_cast<char *>(mb.ws);
+    const PpoExtLayout lay = ext ? ppo_ext_layout(mb.slots_off, mb.members, G, P) : PpoExtLayout{};
+    float row[kPopTableRow] = {}; // (a population's gradient kernel reads row m of the table instead)
+    if (!pop) loss_row(*mb.hp, row);
     GradArgs a;
     a.D = p.obs_dim;
     a.H = p.hidden;
@@ -866,97 +902,57 @@ hipError_t launch_ppo_grad(const ssg_policy &p, const ssg_ppo_hparams &hp, long 
     a.A = p.n_actions;
     a.kind = p.activation;
     a.params = p.dev_params;
-    a.x = x;
-    a.act = act;
-    a.logp = logp;
-    a.adv = adv;
-    a.ret = ret;
-    a.idx = idx;
-    a.M = M;
-    a.n_samples = n_samples;
-    a.stats = reinterpret_cast<const float *>(static_cast<const char *>(ws) + kPpoStatsOff);
-    a.slots = reinterpret_cast<float *>(static_cast<char *>(ws) + kPpoSlotsOff);
-    a.P = ppo_packed_len(p);
-    a.lo = (float)(1.0 - hp.clip);
-    a.hi = (float)(1.0 + hp.clip);
-    a.clip = (float)hp.clip;
-    a.vf = (float)hp.vf_coef;
-    a.ent = (float)hp.ent_coef;
-    a.invM = 1.0f / (float)M;
-    const int G = ppo_grid(M);
-    hipLaunchKernelGGL(ppo_grad_kernel<false>, dim3(G), dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a, PopGradArgs{});
-    const int stride = a.P + 4;
-    const AdamArgs ad = adam_mv ? adam_args(hp, step) : AdamArgs{};
-    hipLaunchKernelGGL(ppo_reduce_kernel<false>, dim3((stride + 255) / 256), dim3(256), 0, stream, (const float *)a.slots, G, a.P, stride,
-                       (float)M, grad_out, stats_out, adam_mv ? const_cast<float *>(p.dev_params) : nullptr, adam_mv, ad, 0ll,
-                       (const float *)nullptr);
-    return hipGetLastError();
-}
-
-// the reduction (and, with ext.clip_seq, the clip launch) behind one extended minibatch of `members` members
-template <bool POP>
-static void launch_ext_reduce(int members, int G, int P, long long M, const PpoExtLaunch &ext, void *ws, size_t slots_off, float *grad_out,
-                              float *stats_out, long long stats_stride, float *params, float *adam_mv, const AdamArgs &ad,
-                              const float *adam_row, hipStream_t stream)
-{
-    const PpoExtLayout lay = ppo_ext_layout(slots_off, members, G, P);
-    char *base = static_cast<char *>(ws);
-    const int stride = P + kExtStats;
-    ExtReduceArgs ea;
-    ea.kl_coef = ext.kl_coef;
-    ea.klacc = reinterpret_cast<float *>(base + lay.klacc);
-    ea.first_chunk = ext.first_chunk ? 1 : 0;
-    ea.gvec = ext.clip_seq ? reinterpret_cast<float *>(base + lay.gvec) : nullptr;
-    ea.part = reinterpret_cast<double *>(base + lay.part);
-    const dim3 grid((unsigned)lay.nb, (unsigned)members);
-    hipLaunchKernelGGL(ppo_reduce_ext_kernel<POP>, grid, dim3(256), 0, stream, (const float *)(base + lay.slots), G, P, stride, (float)M,
-                       grad_out, stats_out, params, adam_mv, ad, stats_stride, adam_row, ea);
-    if (ext.clip_seq)
-        hipLaunchKernelGGL(ppo_clip_kernel<POP>, dim3((unsigned)((P + 255) / 256), (unsigned)members), dim3(256), 0, stream,
-                           (const float *)ea.gvec, (const double *)ea.part, lay.nb, P, ext.max_grad_norm, ext.pop_ext, stats_out, stats_stride,
-                           params, adam_mv, ad, adam_row);
-}
-
-hipError_t launch_ppo_grad_ext(const ssg_policy &p, const ssg_ppo_hparams &hp, const PpoExtLaunch &ext, long long n_samples, const float *x,
-                               const int32_t *act, const float *logp, const float *adv, const float *ret, const int64_t *idx, long long M,
-                               void *ws, float *grad_out, float *stats_out, float *adam_mv, int64_t step, hipStream_t stream)
-{
-    GradArgs a;
-    a.D = p.obs_dim;
-    a.H = p.hidden;
-    a.L = p.n_hidden_layers;
-    a.A = p.n_actions;
-    a.kind = p.activation;
-    a.params = p.dev_params;
-    a.x = x;
-    a.act = act;
-    a.logp = logp;
-    a.adv = adv;
-    a.ret = ret;
-    a.idx = idx;
-    a.M = M;
-    a.n_samples = n_samples;
-    a.stats = reinterpret_cast<const float *>(static_cast<const char *>(ws) + kPpoStatsOff);
-    a.slots = reinterpret_cast<float *>(static_cast<char *>(ws) + kPpoSlotsOff);
-    a.P = ppo_packed_len(p);
-    a.lo = (float)(1.0 - hp.clip);
-    a.hi = (float)(1.0 + hp.clip);
-    a.clip = (float)hp.clip;
-    a.vf = (float)hp.vf_coef;
-    a.ent = (float)hp.ent_coef;
-    a.invM = 1.0f / (float)M;
+    a.x = mb.batch.x;
+    a.act = mb.batch.act;
+    a.logp = mb.batch.logp;
+    a.adv = mb.batch.adv;
+    a.ret = mb.batch.ret;
+    a.idx = mb.idx;
+    a.M = mb.M;
+    a.n_samples = mb.n_samples;
+    a.stats = reinterpret_cast<const float *>(base + kPpoStatsOff);
+    a.slots = reinterpret_cast<float *>(base + (ext ? lay.slots : mb.slots_off));
+    a.P = P;
+    a.lo = row[PT_LO];
+    a.hi = row[PT_HI];
+    a.clip = row[PT_CLIP];
+    a.vf = row[PT_VF];
+    a.ent = row[PT_ENT];
+    a.invM = 1.0f / (float)mb.M;
+    PopGradArgs pa;
+    pa.n = mb.n;
+    pa.N = mb.N;
+    pa.idx_stride = mb.idx_stride;
+    pa.table = mb.table;
+    float *params = mb.adam_mv ? const_cast<float *>(p.dev_params) : nullptr;
+    const AdamArgs ad = mb.adam_mv && !pop ? adam_args(*mb.hp, mb.step) : AdamArgs{};
+    const dim3 ggrid((unsigned)G, (unsigned)mb.members), rgrid((unsigned)((stride + 255) / 256), (unsigned)mb.members);
+    if (!ext) {
+        hipLaunchKernelGGL(pop ? ppo_grad_kernel<true> : ppo_grad_kernel<false>, ggrid, dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a, pa);
+        hipLaunchKernelGGL(pop ? ppo_reduce_kernel<true> : ppo_reduce_kernel<false>, rgrid, dim3(256), 0, stream, (const float *)a.slots, G, P,
+                           stride, (float)mb.M, mb.grad_out, mb.stats_out, params, mb.adam_mv, ad, mb.stats_stride, mb.adam_row);
+        return hipGetLastError();
+    }
     ExtGradArgs ea;
-    ea.logp_all = ext.logp_all;
-    ea.v_old = ext.value_old;
-    ea.kl_coef = ext.kl_coef;
-    ea.pop_ext = nullptr;
-    ea.vf_clip = ext.vf_clip;
-    const int G = ppo_grid(M);
-    a.slots = reinterpret_cast<float *>(static_cast<char *>(ws) + ppo_ext_layout(kPpoSlotsOff, 1, G, a.P).slots);
-    hipLaunchKernelGGL(ppo_grad_ext_kernel<false>, dim3(G), dim3(kPpoBlock), ppo_grad_ext_lds_bytes(p), stream, a, PopGradArgs{}, ea);
-    const AdamArgs ad = adam_mv ? adam_args(hp, step) : AdamArgs{};
-    launch_ext_reduce<false>(1, G, a.P, M, ext, ws, kPpoSlotsOff, grad_out, stats_out, 0ll, adam_mv ? const_cast<float *>(p.dev_params) : nullptr,
-                             adam_mv, ad, nullptr, stream);
+    ea.logp_all = ext->logp_all;
+    ea.v_old = ext->value_old;
+    ea.kl_coef = ext->kl_coef;
+    ea.pop_ext = ext->pop_ext;
+    ea.vf_clip = ext->vf_clip;
+    hipLaunchKernelGGL(pop ? ppo_grad_ext_kernel<true> : ppo_grad_ext_kernel<false>, ggrid, dim3(kPpoBlock), ppo_grad_ext_lds_bytes(p), stream,
+                       a, pa, ea);
+    ExtReduceArgs er;
+    er.kl_coef = ext->kl_coef;
+    er.klacc = reinterpret_cast<float *>(base + lay.klacc);
+    er.first_chunk = ext->first_chunk ? 1 : 0;
+    er.gvec = ext->clip_seq ? reinterpret_cast<float *>(base + lay.gvec) : nullptr;
+    er.part = reinterpret_cast<double *>(base + lay.part);
+    hipLaunchKernelGGL(pop ? ppo_reduce_ext_kernel<true> : ppo_reduce_ext_kernel<false>, rgrid, dim3(256), 0, stream, (const float *)a.slots,
+                       G, P, stride, (float)mb.M, mb.grad_out, mb.stats_out, params, mb.adam_mv, ad, mb.stats_stride, mb.adam_row, er);
+    if (ext->clip_seq)
+        hipLaunchKernelGGL(pop ? ppo_clip_kernel<true> : ppo_clip_kernel<false>, dim3((unsigned)((P + 255) / 256), (unsigned)mb.members),
+                           dim3(256), 0, stream, (const float *)er.gvec, (const double *)er.part, lay.nb, P, ext->max_grad_norm, ext->pop_ext,
+                           mb.stats_out, mb.stats_stride, params, mb.adam_mv, ad, mb.adam_row);
     return hipGetLastError();
 }
 
@@ -983,30 +979,9 @@ hipError_t launch_ppo_adam(const ssg_policy &p, const ssg_ppo_hparams &hp, const
 // ------------------------------------------------------------------------------------------------------------------------------
 void pop_pack(int members, const ssg_ppo_hparams *hp, int64_t step0, int n_steps, float *out)
 {
-    for (int m = 0; m < members; ++m) { // launch_ppo_gae's and launch_ppo_grad's roundings
-        float *row = out + (size_t)m * kPopTableRow;
-        row[PT_LO] = (float)(1.0 - hp[m].clip);
-        row[PT_HI] = (float)(1.0 + hp[m].clip);
-        row[PT_CLIP] = (float)hp[m].clip;
-        row[PT_VF] = (float)hp[m].vf_coef;
-        row[PT_ENT] = (float)hp[m].ent_coef;
-        row[PT_ADV_EPS] = (float)hp[m].adv_eps;
-        row[PT_GF] = (float)hp[m].gamma;
-        row[PT_GLF] = (float)(hp[m].gamma * hp[m].lam);
-    }
+    for (int m = 0; m < members; ++m) loss_row(hp[m], out + (size_t)m * kPopTableRow);
     for (int j = 0; j < n_steps; ++j)
-        for (int m = 0; m < members; ++m) {
-            const AdamArgs ad = adam_args(hp[m], step0 + 1 + j);
-            float *row = out + ((size_t)(1 + j) * members + m) * kPopTableRow;
-            row[0] = ad.w1;
-            row[1] = ad.one_minus_w1;
-            row[2] = ad.beta2;
-            row[3] = ad.w2;
-            row[4] = ad.bc2_sqrt;
-            row[5] = ad.eps;
-            row[6] = ad.step_size;
-            row[7] = 0.0f;
-        }
+        for (int m = 0; m < members; ++m) adam_to_row(adam_args(hp[m], step0 + 1 + j), out + ((size_t)(1 + j) * members + m) * kPopTableRow);
 }
 
 hipError_t launch_pop_gae(int members, int K, int N, const float *table, const double *rew, const uint8_t *done, const float *val,
@@ -1017,89 +992,6 @@ hipError_t launch_pop_gae(int members, int K, int N, const float *table, const d
     double2 *part = reinterpret_cast<double2 *>(static_cast<char *>(ws) + kPopSlotsOff);
     hipLaunchKernelGGL(pop_gae_kernel, dim3(nb, members), dim3(256), 0, stream, K, N, n, nb, rew, done, val, last_val, adv, ret, table, part);
     hipLaunchKernelGGL(pop_gae_stats_kernel, dim3(members), dim3(256), 0, stream, (const double2 *)part, nb, (double)K * (double)n, table, stats);
-    return hipGetLastError();
-}
-
-hipError_t launch_pop_grad(const ssg_policy &p, int members, long long K, long long N, const float *table, const float *adam_row,
-                           const float *x, const int32_t *act, const float *logp, const float *adv, const float *ret,
-                           const int64_t *idx, long long idx_stride, long long M, void *ws, float *stats_out, long long stats_stride,
-                           float *adam_mv, hipStream_t stream)
-{
-    PopGradArgs pa;
-    GradArgs a;
-    a.D = p.obs_dim;
-    a.H = p.hidden;
-    a.L = p.n_hidden_layers;
-    a.A = p.n_actions;
-    a.kind = p.activation;
-    a.params = p.dev_params;
-    a.x = x;
-    a.act = act;
-    a.logp = logp;
-    a.adv = adv;
-    a.ret = ret;
-    a.idx = idx;
-    a.M = M;
-    pa.n = N / members;
-    pa.N = N;
-    a.n_samples = K * pa.n;
-    a.stats = reinterpret_cast<const float *>(static_cast<const char *>(ws) + kPpoStatsOff);
-    a.slots = reinterpret_cast<float *>(static_cast<char *>(ws) + kPopSlotsOff);
-    a.P = ppo_packed_len(p);
-    a.lo = a.hi = a.clip = a.vf = a.ent = 0.0f; // (per member: the table)
-    a.invM = 1.0f / (float)M;
-    pa.idx_stride = idx_stride;
-    pa.table = table;
-    const int G = ppo_grid(M);
-    hipLaunchKernelGGL(ppo_grad_kernel<true>, dim3(G, members), dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a, pa);
-    const int stride = a.P + 4;
-    hipLaunchKernelGGL(ppo_reduce_kernel<true>, dim3((stride + 255) / 256, members), dim3(256), 0, stream, (const float *)a.slots, G, a.P,
-                       stride, (float)M, (float *)nullptr, stats_out, const_cast<float *>(p.dev_params), adam_mv, AdamArgs{}, stats_stride,
-                       adam_row);
-    return hipGetLastError();
-}
-
-hipError_t launch_pop_grad_ext(const ssg_policy &p, int members, long long K, long long N, const float *table, const float *adam_row,
-                               const PpoExtLaunch &ext, const float *x, const int32_t *act, const float *logp, const float *adv,
-                               const float *ret, const int64_t *idx, long long idx_stride, long long M, void *ws, float *stats_out,
-                               long long stats_stride, float *adam_mv, hipStream_t stream)
-{
-    PopGradArgs pa;
-    GradArgs a;
-    a.D = p.obs_dim;
-    a.H = p.hidden;
-    a.L = p.n_hidden_layers;
-    a.A = p.n_actions;
-    a.kind = p.activation;
-    a.params = p.dev_params;
-    a.x = x;
-    a.act = act;
-    a.logp = logp;
-    a.adv = adv;
-    a.ret = ret;
-    a.idx = idx;
-    a.M = M;
-    pa.n = N / members;
-    pa.N = N;
-    a.n_samples = K * pa.n;
-    a.stats = reinterpret_cast<const float *>(static_cast<const char *>(ws) + kPpoStatsOff);
-    a.slots = reinterpret_cast<float *>(static_cast<char *>(ws) + kPopSlotsOff);
-    a.P = ppo_packed_len(p);
-    a.lo = a.hi = a.clip = a.vf = a.ent = 0.0f; // (per member: the table)
-    a.invM = 1.0f / (float)M;
-    pa.idx_stride = idx_stride;
-    pa.table = table;
-    ExtGradArgs ea;
-    ea.logp_all = ext.logp_all;
-    ea.v_old = ext.value_old;
-    ea.kl_coef = ext.kl_coef;
-    ea.pop_ext = ext.pop_ext;
-    ea.vf_clip = 0.0f;
-    const int G = ppo_grid(M);
-    a.slots = reinterpret_cast<float *>(static_cast<char *>(ws) + ppo_ext_layout(kPopSlotsOff, members, G, a.P).slots);
-    hipLaunchKernelGGL(ppo_grad_ext_kernel<true>, dim3(G, members), dim3(kPpoBlock), ppo_grad_ext_lds_bytes(p), stream, a, pa, ea);
-    launch_ext_reduce<true>(members, G, a.P, M, ext, ws, kPopSlotsOff, nullptr, stats_out, stats_stride, const_cast<float *>(p.dev_params),
-                            adam_mv, AdamArgs{}, adam_row, stream);
     return hipGetLastError();
 }
 

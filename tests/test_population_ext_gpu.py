@@ -121,6 +121,43 @@ def test_population_ext_update_is_bitwise_each_members_own(torch_cuda, setup):
     assert bool((st[0, :, 4] > 1e-3).all()) and ppo.kl_coef.tolist() == [2.25, 0.0, 0.0]
 
 
+@pytest.mark.parametrize("minibatches,chunks,last", [(3, 3, 132), (30, 29, 8)])
+def test_population_ext_update_at_uneven_chunkings_is_bitwise_each_members_own(torch_cuda, setup, minibatches, chunks, last):
+    """400 samples per member in 3 minibatches are chunks of 134, 134, 132; in 30 they are 29 chunks of 14, the last one of 8: the
+    table rows, the stats rows and the adaptation count CHUNKS, in the population's loop as in the single policy's."""
+    torch = torch_cuda
+    from ship_sim_gym_amd.population import PopulationPPO
+    from ship_sim_gym_amd.ppo import NativePPO
+    env, pop, b, shards, refs, sbs = setup
+    samples, epochs = K * N_ENVS, 2
+    sizes = [len(c) for c in torch.arange(samples).chunk(minibatches)]
+    assert len(sizes) == chunks and sizes[-1] == last and sizes[0] > last
+    lrs = [1e-3, 5e-4, 1e-4]
+    saved = pop.params.clone(), [r.params.clone() for r in refs]
+    try:
+        ppo = PopulationPPO(pop, env, lr=lrs, **EXT)
+        ppo.gae(b)
+        g = torch.Generator(device=DEV).manual_seed(minibatches)
+        perm = torch.stack([torch.stack([torch.randperm(samples, device=DEV, generator=g) for _ in range(epochs)]) for _ in range(P)])
+        st = ppo.update(b, perm, epochs, minibatches, stats=True)
+        assert st.shape == (P, epochs * chunks, 8) and bool(torch.isfinite(st).all()) and ppo.step == epochs * chunks
+        for m in range(P):
+            ref = NativePPO(refs[m], shards[m], lr=lrs[m], **{k: v[m] for k, v in EXT.items()})
+            ref.gae(sbs[m])
+            r_st = ref.update(sbs[m], perm[m], epochs, minibatches, stats=True)
+            assert r_st.shape[0] == epochs * chunks and ref.step == ppo.step
+            assert torch.equal(pop.params[m], refs[m].params), (m, "params")
+            assert torch.equal(ppo.adam_mv[m], ref.adam_mv), (m, "moments")
+            assert torch.equal(st[m, :, :r_st.shape[1]], r_st), (m, "stats", st[m].tolist(), r_st.tolist())
+            assert torch.equal(ppo.kl_coef[m:m + 1], ref.kl_coef), (m, "coefficient")
+        assert bool((st[2, :, 4:] == 0).all()) and bool((st[0, :, 4] > 0).all()) and bool((st[1, :, 5] > 0).all())
+        assert ppo.kl_coef.tolist() == [1.5, 0.0, 0.0]
+    finally:
+        pop.params.copy_(saved[0])
+        for r, p0 in zip(refs, saved[1]):
+            r.params.copy_(p0)
+
+
 def test_exploit_carries_the_coefficient(torch_cuda):
     torch = torch_cuda
     from ship_sim_gym_amd.population import NativePopulation, PopulationPPO

@@ -202,7 +202,7 @@ def _f32(x):
 
 
 def test_pack_hparams_is_the_single_policy_rounding(native):
-    """The table rows are the doubles launch_ppo_gae / launch_ppo_grad / adam_args form, rounded once to f32."""
+    """The table rows are the doubles loss_row / adam_args form for one policy's launches, rounded once to f32."""
     L = native.lib()
     P, steps, step0 = 3, 5, 7
     hp = _hparams(native, P, lam=[0.9, 0.95, 1.0], clip=[0.1, 0.2, 0.3], lr=[1e-3, 5e-4, 1e-5], beta1=[0.9, 0.3, 0.0],

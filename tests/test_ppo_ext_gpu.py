@@ -332,3 +332,45 @@ def test_whole_ext_update_against_f64_adapts_the_coefficient_and_repeats(torch_c
             assert bool((s2[:, 6] == float(got)).all())
     finally:
         pol.params.copy_(p0)
+
+
+@pytest.mark.parametrize("K,envs,minibatches,chunks", [(8, 125, 3, 3), (2, 5, 6, 5)])
+def test_whole_ext_update_at_uneven_chunkings(torch_cuda, K, envs, minibatches, chunks):
+    """The shapes of the plain path's test_update_uneven_chunks_and_continuity with the three terms on: a last chunk shorter than the
+    others (334, 334, 332), then fewer chunks than asked (5 of 2 samples).  Stats rows, Adam steps and the adaptation count CHUNKS."""
+    torch = torch_cuda
+    epochs = 2
+    env, pol, b, advn, st = _batch_for(torch, 64, 2, "tanh", 3, n=envs, K=K)
+    n = b["act"].numel()
+    assert n == K * envs and len(torch.arange(n).chunk(minibatches)) == chunks
+    g = torch.Generator(device="cuda:0").manual_seed(minibatches)
+    perm = torch.stack([torch.randperm(n, device="cuda:0", generator=g) for _ in range(epochs)])
+    assert [len(c) for c in perm[0].chunk(minibatches)] == [-(-n // minibatches)] * (chunks - 1) + [n - (chunks - 1) * -(-n // minibatches)]
+    p0 = pol.params.detach().clone()
+    max_norm = 0.05
+    kw = dict(vf_clip=VF_CLIP, max_grad_norm=max_norm, kl_coef=KL_COEF)
+    M = -(-n // minibatches)
+    try:
+        # a first run without adaptation: the mean KL of the last epoch, a quarter of which is a target the coefficient grows at
+        probe = _ppo(torch, pol, env, st, n, M, **kw)
+        s_probe = probe.update(b, perm, epochs, minibatches, stats=True)
+        assert s_probe.shape == (epochs * chunks, 8) and bool(torch.isfinite(s_probe).all()) and float(probe.kl_coef) == KL_COEF
+        mean_kl = float(s_probe[-chunks:, 4].mean())
+        print("mean KL of the last epoch: %.9g; gradient norms %s" % (mean_kl, s_probe[:, 5].tolist()))
+        assert mean_kl > 0.0
+        target = mean_kl / 4.0
+        pol.params.copy_(p0)
+        r64, c64, m64 = _ref_update(torch, pol, b, advn, perm, epochs, minibatches, torch.float64, max_norm, KL_COEF, target)
+        r32, c32, _ = _ref_update(torch, pol, b, advn, perm, epochs, minibatches, torch.float32, max_norm, KL_COEF, target)
+        ppo = _ppo(torch, pol, env, st, n, M, kl_target=target, **kw)
+        stats = ppo.update(b, perm, epochs, minibatches, stats=True)
+        assert stats.shape == (epochs * chunks, 8) and torch.equal(stats, s_probe)
+        assert ppo.step == epochs * chunks
+        assert bool((stats[:, 6] == KL_COEF).all()) and bool((stats[:, 5] > 0).all()) and bool((stats[:, 7] == 0).all())
+        want = _adapt(KL_COEF, stats[-chunks:, 4].cpu().numpy(), target)
+        got = ppo.kl_coef.cpu().numpy()[0]
+        assert got.dtype == np.float32 and got == want == np.float32(KL_COEF * 1.5), (got, want)
+        _check_per_tensor(torch, pol, pol.params.detach(), r64, r32, ("ext update", n, minibatches))
+        assert c64 == c32 == float(got) and abs(m64 - mean_kl) <= 1e-4 * mean_kl
+    finally:
+        pol.params.copy_(p0)
