@@ -422,6 +422,23 @@ int ssg_debug_clock_probe(uint64_t *dev_out, int n_blocks, int iters, void *stre
  *   [oh + A*H + A .. + H)       Wv  [1][H]
  *   [oh + A*H + A + H]          bv  [1]
  *   total: H*D + H + (n_hidden_layers - 1)*(H*H + H) + A*H + A + H + 1 floats.
+ *
+ * Separate value network (activation | SSG_POLICY_SEPARATE_VALUE): Stable-Baselines' MlpPolicy (net_arch [dict(vf=[64, 64], pi=[64, 64])],
+ * train/stable_baselines/ppo.py) and RLlib's default vf_share_layers = False (train/rllib/pbt.py).  Two towers of the same hidden and
+ * n_hidden_layers, one ending in the logits and one in the value; the buffer is torch.cat([p.flatten() ...]) of a module that declares
+ * pi_body, pi, vf_body, v in that order.  With T = H*D + H + (n_hidden_layers - 1)*(H*H + H) floats per tower:
+ *   [0 .. T)                    pi tower: W0 [H][D], b0 [H] [, W1 [H][H], b1 [H]]
+ *   [T .. T + A*H + A)          pi head:  Wpi [A][H], bpi [A]
+ *   [ov .. ov + T)              vf tower: V0 [H][D], c0 [H] [, V1 [H][H], c1 [H]]      ov = T + A*H + A
+ *   [ov + T .. ov + T + H + 1)  vf head:  Wv [1][H], bv [1]
+ *   total: 2*T + A*H + A + H + 1 floats.
+ * Both towers start from the same normalised row x; the logits depend on the pi tower and pi head alone, the value on the vf tower and
+ * vf head alone, each output still one k-ordered fmaf chain from its bias (a separate policy whose vf tower holds its pi tower's numbers
+ * gives bit for bit the outputs of the shared policy over that one body).  A launch runs only the tower it needs: the value-only
+ * forward (dev_last_value of ssg_rollout_policy / ssg_pop_rollout) skips the pi tower, ssg_ppo_dist / ssg_pop_dist skip the vf tower.
+ * In the gradient, vf_coef scales the vf tower's and vf head's entries only and the policy, entropy and KL terms reach the pi tower's and
+ * pi head's entries only.  Out of scope: hidden above SSG_POLICY_MAX_HIDDEN (RLlib's 256), towers of different width or depth,
+ * partially shared layers.
  * Forward, per env e: x[d] = (float)(obs[e][d] / obs_scale[d]) (f64 division, then one rounding to f32); every dense output is an
  * fmaf chain from its bias over k = 0, 1, ... in order, followed by tanh / ReLU on the hidden layers; logits = the pi head, value = the
  * v head.  Sampling (f32): m = max(logits), lse = m + log(sum exp(l - m)), logp_all = l - lse, cdf = cumsum(exp(logp_all)),
@@ -431,13 +448,14 @@ int ssg_debug_clock_probe(uint64_t *dev_out, int n_blocks, int iters, void *stre
 #define SSG_POLICY_MAX_HIDDEN 128
 #define SSG_POLICY_TANH 0
 #define SSG_POLICY_RELU 1
+#define SSG_POLICY_SEPARATE_VALUE 0x100 /* or-ed into `activation`: separate pi / vf towers (layout above) */
 typedef struct ssg_policy {
     uint32_t struct_size;        /* sizeof(ssg_policy) */
     int32_t obs_dim;             /* == history*(6+n_beams) of the handle */
     int32_t hidden;              /* 16..SSG_POLICY_MAX_HIDDEN, multiple of 16 */
     int32_t n_hidden_layers;     /* 1 or 2 */
     int32_t n_actions;           /* 2..4 (ssg_step accepts actions 0..3; the reference's action space is Discrete(3), ship_env.py:19) */
-    int32_t activation;          /* SSG_POLICY_TANH | SSG_POLICY_RELU */
+    int32_t activation;          /* low byte: SSG_POLICY_TANH or SSG_POLICY_RELU; bit SSG_POLICY_SEPARATE_VALUE; any other bit is refused */
     const float *dev_params;     /* packed f32, layout above */
     const double *dev_obs_scale; /* f64[obs_dim]: x = (float)(obs / scale) */
 } ssg_policy;
@@ -650,7 +668,7 @@ typedef struct ssg_population {
     int32_t hidden;
     int32_t n_hidden_layers;
     int32_t n_actions;
-    int32_t activation;
+    int32_t activation;          /* ssg_policy's encoding, SSG_POLICY_SEPARATE_VALUE included */
     int32_t reserved;            /* 0 */
     float *dev_params;           /* f32 [P][L]: row m = member m's packed parameters */
     const double *dev_obs_scale; /* f64[obs_dim], common to the population */

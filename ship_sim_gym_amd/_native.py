@@ -17,6 +17,7 @@ MAP_OFF_COUNTS, MAP_OFF_AABB, MAP_OFF_GOALS, MAP_OFF_SPAWN_GOAL, MAP_OFF_PLANES,
 FLAG_AUTO_RESET, FLAG_FIX_COLLISION_REWARD, FLAG_BANK_IN_GLOBAL, FLAG_EXACT_LIDAR, FLAG_DYN_MEMO_OFF = 0x1, 0x2, 0x4, 0x8, 0x10
 EV_COLLIDING, EV_GOAL_REACHED, EV_OUT_OF_BOUNDS, EV_MAX_STEPS, EV_NO_GOALS_LEFT = 0x1, 0x2, 0x4, 0x8, 0x10
 POLICY_MAX_HIDDEN, POLICY_TANH, POLICY_RELU = 128, 0, 1
+POLICY_SEPARATE_VALUE = 0x100  # or-ed into Policy.activation / Population.activation: separate pi / vf towers
 POP_MAX_MEMBERS = 256
 POP_EXT_GRAD_CLIP, POP_EXT_VF_CLIP = 0x1, 0x2
 PPO_EXT_STATS = 8  # stats columns of the _ext entry points

@@ -970,6 +970,13 @@ int ssg_rollout_traj(ssg_handle *h, const int32_t *dev_actions, int K, double *d
     return SSG_OK;
 }
 
+// the activation kind in the low byte, SSG_POLICY_SEPARATE_VALUE or not, and no other bit
+static bool activation_ok(int32_t activation)
+{
+    const int32_t kind = activation & ~SSG_POLICY_SEPARATE_VALUE;
+    return kind == SSG_POLICY_TANH || kind == SSG_POLICY_RELU;
+}
+
 // ABI 9: the policy in the loop.  Everything a call could refuse is refused here, before anything is enqueued.
 static int check_policy(ssg_handle *h, const ssg_policy *pol, const char *what)
 {
@@ -986,8 +993,8 @@ static int check_policy(ssg_handle *h, const ssg_policy *pol, const char *what)
         return fail(h, SSG_ERR_BAD_ARG, w + ": hidden must be a multiple of 16 in 16..SSG_POLICY_MAX_HIDDEN");
     if (pol->n_hidden_layers < 1 || pol->n_hidden_layers > 2) return fail(h, SSG_ERR_BAD_ARG, w + ": n_hidden_layers must be 1 or 2");
     if (pol->n_actions < 2 || pol->n_actions > 4) return fail(h, SSG_ERR_BAD_ARG, w + ": n_actions must be in 2..4 (ssg_step accepts actions 0..3)");
-    if (pol->activation != SSG_POLICY_TANH && pol->activation != SSG_POLICY_RELU)
-        return fail(h, SSG_ERR_BAD_ARG, w + ": activation must be SSG_POLICY_TANH or SSG_POLICY_RELU");
+    if (!activation_ok(pol->activation))
+        return fail(h, SSG_ERR_BAD_ARG, w + ": activation must be SSG_POLICY_TANH or SSG_POLICY_RELU, optionally with SSG_POLICY_SEPARATE_VALUE");
     if (!pol->dev_params || !pol->dev_obs_scale) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_params or dev_obs_scale");
     return SSG_OK;
 }
@@ -1065,7 +1072,7 @@ static int check_policy_shape(const ssg_policy *pol)
     return pol && pol->struct_size == sizeof(ssg_policy) && pol->obs_dim >= 1 && pol->obs_dim <= SSG_MAX_HISTORY * (6 + SSG_MAX_BEAMS) &&
            pol->hidden >= 16 && pol->hidden <= SSG_POLICY_MAX_HIDDEN && pol->hidden % 16 == 0 && pol->n_hidden_layers >= 1 &&
            pol->n_hidden_layers <= 2 && pol->n_actions >= 2 && pol->n_actions <= 4 &&
-           (pol->activation == SSG_POLICY_TANH || pol->activation == SSG_POLICY_RELU);
+           activation_ok(pol->activation);
 }
 
 static int check_hparams(ssg_handle *h, const ssg_ppo_hparams *hp, const char *what)

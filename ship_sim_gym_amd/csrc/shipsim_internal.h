@@ -202,8 +202,8 @@ hipError_t launch_refill_worlds(const DevCfg &c, uint64_t seed, double width_fra
 hipError_t launch_fill_actions(uint64_t seed, uint64_t step0, int K, long long env_base, int n, int32_t *out,
                                hipStream_t stream);
 // the policy kernel (shipsim_policy.hip): ssg_policy_act on n envs; act / logp NULL = value only (no sampling), x NULL = no x rows
-size_t policy_lds_bytes(const ssg_policy &p);
-hipError_t prepare_policy(); // (the dynamic-LDS limit of the kernel: up to 79 KB per workgroup at obs_dim 176, hidden 128)
+size_t policy_lds_bytes(const ssg_policy &p, bool both_towers); // (both_towers: a separate-value launch that also samples)
+hipError_t prepare_policy(); // (the dynamic-LDS limit of the kernels: up to 90 KB per workgroup at obs_dim 176, hidden 128; 124 KB when a separate-value launch keeps its third buffer)
 hipError_t launch_policy_act(const ssg_policy &p, int n, long long env_base, const double *obs, const float *uniform, uint64_t seed,
                              int64_t step, int32_t *act, float *logp, float *value, float *x, hipStream_t stream);
 // GAE and the PPO update (shipsim_ppo.hip).  Workspace: f32[4] advantage statistics at kPpoStatsOff (mean, std + adv_eps, its

@@ -16,6 +16,12 @@
 // library's.  An env's outputs depend on its own observation row, the parameters and its own uniform only: not on n_envs, the
 // workgroup geometry, env_id_base (except through the Philox counter, which is the GLOBAL env id) or on whether the launch comes from
 // ssg_policy_act or ssg_rollout_policy.
+//
+// Separate value network (SSG_POLICY_SEPARATE_VALUE, the SPLIT instantiations).  The pi tower runs dense, dense, then the logits head;
+// the vf tower then runs the same device functions from the same row x, and ends in the value head: every output is the same kind of
+// chain as above.  With two layers the shared plan overwrites x with the second layer's output; a launch that runs both towers keeps a
+// third activation buffer for it instead, so that x survives for the vf tower (re-forming x would read the f64 observation rows twice).
+// The value-only launch skips the pi tower, the dist kernel the vf tower: both keep the shared plan's two buffers.
 #include <cstdint>
 
 #include "shipsim_internal.h"
@@ -110,6 +116,60 @@ __device__ __forceinline__ void heads(const float *__restrict__ P, int H, int A,
     *v_out = v;
 }
 
+// The two heads on their own (SPLIT): the chains of heads(), each over its own tower's last layer.  P points at Wpi [A][H], bpi [A].
+__device__ __forceinline__ void head_pi(const float *__restrict__ P, int H, int A, const float *h, float *wt, int lane, float (&lg)[4])
+{
+    const float *Wpi = P, *bpi = P + A * H;
+    __syncthreads();
+    stage_rows(Wpi, A, H, H, wt, lane);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 4; ++j) lg[j] = j < A ? bpi[j] : 0.0f;
+    for (int k = 0; k < H; k += 4) {
+        float hv[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) hv[t] = h[(k + t) * kPolStride + lane];
+        float4 w[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[j] = *reinterpret_cast<const float4 *>(wt + j * H + k); // (rows A..3 unused: never summed)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const float hx = hv[t];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (j < A) lg[j] = fmaf(t == 0 ? w[j].x : t == 1 ? w[j].y : t == 2 ? w[j].z : w[j].w, hx, lg[j]);
+        }
+    }
+}
+
+// P points at Wv [1][H], bv [1].
+__device__ __forceinline__ float head_v(const float *__restrict__ P, int H, const float *h, float *wt, int lane)
+{
+    __syncthreads();
+    stage_rows(P, 1, H, H, wt, lane);
+    __syncthreads();
+    float v = P[H];
+    for (int k = 0; k < H; k += 4) {
+        const float4 w = *reinterpret_cast<const float4 *>(wt + k);
+        v = fmaf(w.x, h[(k + 0) * kPolStride + lane], v);
+        v = fmaf(w.y, h[(k + 1) * kPolStride + lane], v);
+        v = fmaf(w.z, h[(k + 2) * kPolStride + lane], v);
+        v = fmaf(w.w, h[(k + 3) * kPolStride + lane], v);
+    }
+    return v;
+}
+
+// One tower's body from the x rows in bufA: Linear(D, H) + act [+ Linear(H, H) + act, into h2].  Returns the last layer's rows.
+__device__ __forceinline__ const float *tower(const float *__restrict__ P, int D, int H, int L, int kind, const float *bufA, float *bufB,
+                                              float *h2, float *wt, int lane)
+{
+    dense(P, P + H * D, D, H, kind, bufA, bufB, wt, lane);
+    if (L != 2) return bufB;
+    P += H * D + H;
+    dense(P, P + H * H, H, H, kind, bufB, h2, wt, lane);
+    return h2;
+}
+
 // log(sum_j exp(lg[j])) over j < A, the formula order of ppo_torch's log_softmax
 __device__ __forceinline__ float log_sum_exp(const float (&lg)[4], int A)
 {
@@ -130,7 +190,9 @@ __device__ __forceinline__ float log_sum_exp(const float (&lg)[4], int A)
 // (workgroups of n envs, members): member m = blockIdx.y owns the n envs [m*n, (m+1)*n) of every buffer and the parameter row
 // params + m*plen, with a tail workgroup of its own, so an env's outputs are bit for bit those of the POP = false launch on that slice
 // with that row (the same code below).  The Philox counter stays the global env id: env_base + m*n + e.
-template <bool POP>
+// SPLIT: the separate-value layout (p.activation carries SSG_POLICY_SEPARATE_VALUE); a launch with act_out runs both towers and has the
+// third activation buffer behind bufB, the value-only launch runs the vf tower alone in the shared plan's two buffers.
+template <bool POP, bool SPLIT>
 __global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1, 2))) policy_act_kernel(const ssg_policy p, const float *__restrict__ params, const double *__restrict__ scale,
                                                               int n, long long env_base, const double *__restrict__ obs,
                                                               const float *__restrict__ uniform, uint64_t seed, int64_t step,
@@ -179,20 +241,33 @@ __global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1
     // (the first dense tile's barrier orders these stores before any lane reads another lane's column: after it every lane reads and
     // writes its own activation column only)
 
-    // 2. the body: Linear(D, H) + act [+ Linear(H, H) + act]
-    const float *P = params;
-    dense(P, P + H * D, D, H, p.activation, bufA, bufB, wt, lane);
-    P += H * D + H;
-    const float *h = bufB;
-    if (p.n_hidden_layers == 2) {
-        dense(P, P + H * H, H, H, p.activation, bufB, bufA, wt, lane);
-        P += H * H + H;
-        h = bufA;
-    }
-
-    // 3. the heads
     float lg[4], v;
-    heads(P, H, A, h, wt, lane, lg, &v);
+    if (SPLIT) {
+        // 2s + 3s. each tower's body and its head; x stays in bufA while the vf tower still needs it
+        const int L = p.n_hidden_layers, kind = p.activation & 0xff;
+        const int T = H * D + H + (L - 1) * (H * H + H); // floats of one tower
+        if (act_out) {
+            const float *h = tower(params, D, H, L, kind, bufA, bufB, bufB + H * kPolStride, wt, lane);
+            head_pi(params + T, H, A, h, wt, lane, lg);
+        }
+        const float *Pv = params + T + A * H + A;
+        const float *h = tower(Pv, D, H, L, kind, bufA, bufB, bufA, wt, lane);
+        v = head_v(Pv + T, H, h, wt, lane);
+    } else {
+        // 2. the body: Linear(D, H) + act [+ Linear(H, H) + act]
+        const float *P = params;
+        dense(P, P + H * D, D, H, p.activation, bufA, bufB, wt, lane);
+        P += H * D + H;
+        const float *h = bufB;
+        if (p.n_hidden_layers == 2) {
+            dense(P, P + H * H, H, H, p.activation, bufB, bufA, wt, lane);
+            P += H * H + H;
+            h = bufA;
+        }
+
+        // 3. the heads
+        heads(P, H, A, h, wt, lane, lg, &v);
+    }
     if (lane >= ne) return;
     const int e = e0 + lane;
     if (value_out) value_out[e] = v;
@@ -234,6 +309,9 @@ __global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1
 // step 2 on — the same dense, heads and log_sum_exp — so that logp_all[i][act[i]] is the rollout's logp[i] bit for bit.  Grid
 // (workgroups of n rows, members, K): the workgroup's rows start at row blockIdx.z*N + blockIdx.y*n and run under parameter row
 // blockIdx.y (one policy: members = 1, K = 1, n = the number of rows).  logp_all[i][j] = logit_j - lse for j < A, 0 for j >= A.
+// SPLIT: the pi tower and the pi head open the packed row as the shared body and Wpi / bpi do, so the body code is the same and only
+// the head differs; the vf tower is never read.
+template <bool SPLIT>
 __global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1, 2))) policy_dist_kernel(const ssg_policy p, const float *__restrict__ params, int n, long long N,
                                                                const float *__restrict__ x, float *__restrict__ logp_all, int plen)
 {
@@ -263,17 +341,19 @@ __global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1
             for (int r = 0; r < D; ++r) bufA[r * kPolStride + lane] = 0.0f;
         for (int r = D; r < R4; ++r) bufA[r * kPolStride + lane] = 0.0f;
     }
+    const int kind = SPLIT ? (p.activation & 0xff) : p.activation;
     const float *P = params;
-    dense(P, P + H * D, D, H, p.activation, bufA, bufB, wt, lane);
+    dense(P, P + H * D, D, H, kind, bufA, bufB, wt, lane);
     P += H * D + H;
     const float *h = bufB;
     if (p.n_hidden_layers == 2) {
-        dense(P, P + H * H, H, H, p.activation, bufB, bufA, wt, lane);
+        dense(P, P + H * H, H, H, kind, bufB, bufA, wt, lane);
         P += H * H + H;
         h = bufA;
     }
     float lg[4], v;
-    heads(P, H, A, h, wt, lane, lg, &v);
+    if (SPLIT) head_pi(P, H, A, h, wt, lane, lg);
+    else heads(P, H, A, h, wt, lane, lg, &v);
     if (lane >= ne) return;
     const float lse = log_sum_exp(lg, A);
     float4 out;
@@ -290,27 +370,36 @@ __global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1
 
 } // namespace
 
-size_t policy_lds_bytes(const ssg_policy &p)
+static bool is_split(const ssg_policy &p) { return (p.activation & SSG_POLICY_SEPARATE_VALUE) != 0; }
+
+// both_towers: a separate-value launch that samples actions too (two layers: the third activation buffer, H rows)
+size_t policy_lds_bytes(const ssg_policy &p, bool both_towers)
 {
     const size_t R4 = (size_t)(((p.obs_dim > p.hidden ? p.obs_dim : p.hidden) + 3) & ~3);
-    return (16 * R4 + (R4 + (size_t)p.hidden) * kPolStride) * sizeof(float);
+    const size_t third = is_split(p) && both_towers && p.n_hidden_layers == 2 ? (size_t)p.hidden : 0;
+    return (16 * R4 + (R4 + (size_t)p.hidden + third) * kPolStride) * sizeof(float);
 }
 
 hipError_t prepare_policy()
 {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(policy_act_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(policy_act_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(policy_dist_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    const void *kernels[6] = {reinterpret_cast<const void *>(policy_act_kernel<false, false>), reinterpret_cast<const void *>(policy_act_kernel<true, false>),
+                              reinterpret_cast<const void *>(policy_act_kernel<false, true>), reinterpret_cast<const void *>(policy_act_kernel<true, true>),
+                              reinterpret_cast<const void *>(policy_dist_kernel<false>), reinterpret_cast<const void *>(policy_dist_kernel<true>)};
+    for (const void *k : kernels) {
+        hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t launch_policy_act(const ssg_policy &p, int n, long long env_base, const double *obs, const float *uniform, uint64_t seed,
                              int64_t step, int32_t *act, float *logp, float *value, float *x, hipStream_t stream)
 {
     const unsigned grid = (unsigned)((n + kPolWave - 1) / kPolWave);
-    hipLaunchKernelGGL(policy_act_kernel<false>, dim3(grid), dim3(kPolWave), policy_lds_bytes(p), stream, p, p.dev_params, p.dev_obs_scale, n, env_base,
-                       obs, uniform, seed, step, act, logp, value, x, 0);
+    const auto kernel = is_split(p) ? policy_act_kernel<false, true> : policy_act_kernel<false, false>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kPolWave),
+                       policy_lds_bytes(p, act != nullptr), stream, p, p.dev_params, p.dev_obs_scale, n, env_base, obs, uniform, seed, step, act,
+                       logp, value, x, 0);
     return hipGetLastError();
 }
 
@@ -318,16 +407,18 @@ hipError_t launch_policy_pop(const ssg_policy &p, int members, int n, long long 
                              uint64_t seed, int64_t step, int32_t *act, float *logp, float *value, float *x, hipStream_t stream)
 {
     const unsigned grid = (unsigned)((n + kPolWave - 1) / kPolWave);
-    hipLaunchKernelGGL(policy_act_kernel<true>, dim3(grid, (unsigned)members), dim3(kPolWave), policy_lds_bytes(p), stream, p, p.dev_params,
-                       p.dev_obs_scale, n, env_base, obs, uniform, seed, step, act, logp, value, x, ppo_packed_len(p));
+    const auto kernel = is_split(p) ? policy_act_kernel<true, true> : policy_act_kernel<true, false>;
+    hipLaunchKernelGGL(kernel, dim3(grid, (unsigned)members),
+                       dim3(kPolWave), policy_lds_bytes(p, act != nullptr), stream, p, p.dev_params, p.dev_obs_scale, n, env_base, obs, uniform,
+                       seed, step, act, logp, value, x, ppo_packed_len(p));
     return hipGetLastError();
 }
 
 hipError_t launch_policy_dist(const ssg_policy &p, int members, int n, long long N, int K, const float *x, float *logp_all, hipStream_t stream)
 {
     const unsigned grid = (unsigned)((n + kPolWave - 1) / kPolWave);
-    hipLaunchKernelGGL(policy_dist_kernel, dim3(grid, (unsigned)members, (unsigned)K), dim3(kPolWave), policy_lds_bytes(p), stream, p, p.dev_params,
-                       n, N, x, logp_all, ppo_packed_len(p));
+    hipLaunchKernelGGL(is_split(p) ? policy_dist_kernel<true> : policy_dist_kernel<false>, dim3(grid, (unsigned)members, (unsigned)K),
+                       dim3(kPolWave), policy_lds_bytes(p, false), stream, p, p.dev_params, n, N, x, logp_all, ppo_packed_len(p));
     return hipGetLastError();
 }
 

@@ -16,6 +16,12 @@
 // weight gradients in its own slot of the caller's workspace (read-modify-write by the lane that owns the entry, so in tile order),
 // its bias / head gradients and loss sums in registers; a second kernel adds the slots (a fixed tree) and, for an update, applies
 // Adam to the packed parameters in place.  Deterministic for a given M (the grid depends on M only); no floating-point atomics.
+//
+// Separate value network (SSG_POLICY_SEPARATE_VALUE, the SPLIT instantiations).  The logits' deltas depend on the pi tower alone and the
+// value's on the vf tower alone, so a tile runs the body below once per tower over the same LDS: the sample scalars and the X rows are
+// loaded once, then the pi pass (forward over W0 / W1, logits, the policy, entropy and KL terms, backward into the pi tower's and pi
+// head's slot entries) and the vf pass (forward over V0 / V1, the value and its loss, backward into the vf tower's and vf head's).
+// No LDS beyond the shared plan's.
 #include <cmath>
 #include <cstdint>
 
@@ -172,7 +178,7 @@ __global__ void __launch_bounds__(256) pop_gae_stats_kernel(const double2 *__res
 // the minibatch gradient
 // ------------------------------------------------------------------------------------------------------------------------------
 struct GradArgs {
-    int D, H, L, A, kind;
+    int D, H, L, A, kind; // (kind: the activation's low byte)
     const float *params;
     const float *x;
     const int32_t *act;
@@ -284,7 +290,8 @@ struct ExtGradArgs {
 // computes for that member alone, tile for tile (the same code below).
 // EXT = false: the loss of ssg_ppo_grad (ea unused), slots of P + 4 floats.  EXT = true: plus the value clip and the KL penalty,
 // slots of P + kExtStats floats (the loss sums pg, VL, entropy, clip fraction, KL, then zeros).
-template <bool POP, bool EXT> __device__ __forceinline__ void ppo_grad_body(const GradArgs &a_, const PopGradArgs &pa, const ExtGradArgs &ea)
+// SPLIT = false: the shared body (one pass per tile: pi and vf below are both true, constants).  SPLIT = true: two passes per tile.
+template <bool POP, bool EXT, bool SPLIT> __device__ __forceinline__ void ppo_grad_body(const GradArgs &a_, const PopGradArgs &pa, const ExtGradArgs &ea)
 {
     extern __shared__ float4 lds4[];
     float *lds = reinterpret_cast<float *>(lds4);
@@ -329,12 +336,10 @@ template <bool POP, bool EXT> __device__ __forceinline__ void ppo_grad_body(cons
 
     // packed offsets (include/shipsim.h)
     const float *P = a.params;
-    const float *W0 = P, *b0 = P + H * D;
-    const float *W1 = b0 + H, *b1 = W1 + H * H;
-    const float *Wpi = a.L == 2 ? b1 + H : b0 + H;
-    const float *bpi = Wpi + A * H, *Wv = bpi + A, *bv = Wv + H;
+    const int T = H * D + H + (a.L - 1) * (H * H + H); // floats of one tower (the shared body)
+    const float *Wpi = P + T;
+    const float *bpi = Wpi + A * H, *Wv = bpi + A + (SPLIT ? T : 0), *bv = Wv + H;
     float *g = a.slots + (size_t)blockIdx.x * SS;
-    float *gW0 = g, *gb0 = g + H * D, *gW1 = gb0 + H, *gb1 = gW1 + H * H;
     float *gWpi = g + (Wpi - P), *gbpi = g + (bpi - P), *gWv = g + (Wv - P), *gbv = g + (bv - P);
 
     for (int i = tid; i < kTile * SX; i += kPpoBlock) X[i] = 0.0f; // (the padding columns stay zero)
@@ -344,7 +349,8 @@ template <bool POP, bool EXT> __device__ __forceinline__ void ppo_grad_body(cons
     }
     const float mean = a.stats[0], stdp = a.stats[1];
     const float *HL = a.L == 2 ? HB1 : HB0; // the last hidden layer
-    float accb0 = 0.0f, accb1 = 0.0f, accW[4] = {0.0f, 0.0f, 0.0f, 0.0f}, accWv = 0.0f, accbh = 0.0f;
+    float accb0 = 0.0f, accb1 = 0.0f, accb0v = 0.0f, accb1v = 0.0f; // (...v: the vf tower's, SPLIT)
+    float accW[4] = {0.0f, 0.0f, 0.0f, 0.0f}, accWv = 0.0f, accbh = 0.0f;
     float st_pg = 0.0f, st_vl = 0.0f, st_en = 0.0f, st_cf = 0.0f, st_kl = 0.0f;
     const long long ntiles = (a.M + kTile - 1) / kTile;
     bool first = true;
@@ -378,6 +384,13 @@ template <bool POP, bool EXT> __device__ __forceinline__ void ppo_grad_body(cons
             X[s * SX + d] = j >= 0 ? a.x[(size_t)j * D + d] : 0.0f;
         }
         __syncthreads();
+        for (int pass = 0; pass < (SPLIT ? 2 : 1); ++pass) {
+        // which heads this pass serves, and its tower in the packed row and in the slot
+        const bool pi = !SPLIT || pass == 0, vf = !SPLIT || pass == 1;
+        const int to = pass * (T + A * H + A);
+        const float *W0 = P + to, *b0 = W0 + H * D;
+        const float *W1 = b0 + H, *b1 = W1 + H * H;
+        float *gW0 = g + to, *gW1 = gW0 + H * D + H;
         // 2. forward body
         mm_forward(W0, b0, D, D4, NT, X, SX, HB0, SH, kind, wave, lane);
         __syncthreads();
@@ -396,12 +409,11 @@ template <bool POP, bool EXT> __device__ __forceinline__ void ppo_grad_body(cons
                 const float hk = h[k];
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    if (j < A) lg[j] = fmaf(WH[j * H + k], hk, lg[j]);
-                v = fmaf(WH[4 * H + k], hk, v);
+                    if (pi && j < A) lg[j] = fmaf(WH[j * H + k], hk, lg[j]);
+                if (vf) v = fmaf(WH[4 * H + k], hk, v);
             }
             float dl[4] = {0.0f, 0.0f, 0.0f, 0.0f}, dv = 0.0f;
-            if (SIDX[s] >= 0) {
-                v += bv[0];
+            if (pi && SIDX[s] >= 0) {
                 float m = -INFINITY;
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
@@ -434,19 +446,9 @@ template <bool POP, bool EXT> __device__ __forceinline__ void ppo_grad_body(cons
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
                     if (j < A) dl[j] = glpa * ((j == act ? 1.0f : 0.0f) - p[j]) + gent * (-p[j] * (lp[j] + ent));
-                const float err = v - SRET[s];
-                dv = a.vf * 2.0f * err * a.invM;
-                float vl = err * err;
-                if (vclip_on) { // VL = max((v - ret)^2, (v_old + clamp(v - v_old, -c, c) - ret)^2): max and clamp as autograd takes them
-                    const float vo = SVOLD[s], d = v - vo;
-                    const float errc = (vo + fminf(fmaxf(d, -vf_clip), vf_clip)) - SRET[s];
-                    const float l1 = vl, l2 = errc * errc;
-                    const float w1 = l1 > l2 ? 1.0f : (l1 == l2 ? 0.5f : 0.0f), w2 = l2 > l1 ? 1.0f : (l1 == l2 ? 0.5f : 0.0f);
-                    const bool vin = d >= -vf_clip && d <= vf_clip;
-                    const float gv = w1 * (2.0f * err) + (vin ? w2 * (2.0f * errc) : 0.0f);
-                    dv = a.vf * gv * a.invM;
-                    vl = fmaxf(l1, l2);
-                }
+                st_pg += -fminf(s1, s2);
+                st_en += ent;
+                st_cf += fabsf(ratio - 1.0f) > a.clip ? 1.0f : 0.0f;
                 if (kl_on) { // KL(old || new) = sum_j p_old[j] * (logp_old[j] - logp[j]); d/d logit j = p[j]*sum(p_old) - p_old[j]
                     float po[4], spo = 0.0f, kl = 0.0f;
 #pragma unroll
@@ -463,33 +465,50 @@ template <bool POP, bool EXT> __device__ __forceinline__ void ppo_grad_body(cons
                         if (j < A) dl[j] += gk * (p[j] * spo - po[j]);
                     st_kl += kl;
                 }
-                st_pg += -fminf(s1, s2);
-                st_vl += vl;
-                st_en += ent;
-                st_cf += fabsf(ratio - 1.0f) > a.clip ? 1.0f : 0.0f;
             }
+            if (vf && SIDX[s] >= 0) {
+                v += bv[0];
+                const float err = v - SRET[s];
+                dv = a.vf * 2.0f * err * a.invM;
+                float vl = err * err;
+                if (vclip_on) { // VL = max((v - ret)^2, (v_old + clamp(v - v_old, -c, c) - ret)^2): max and clamp as autograd takes them
+                    const float vo = SVOLD[s], d = v - vo;
+                    const float errc = (vo + fminf(fmaxf(d, -vf_clip), vf_clip)) - SRET[s];
+                    const float l1 = vl, l2 = errc * errc;
+                    const float w1 = l1 > l2 ? 1.0f : (l1 == l2 ? 0.5f : 0.0f), w2 = l2 > l1 ? 1.0f : (l1 == l2 ? 0.5f : 0.0f);
+                    const bool vin = d >= -vf_clip && d <= vf_clip;
+                    const float gv = w1 * (2.0f * err) + (vin ? w2 * (2.0f * errc) : 0.0f);
+                    dv = a.vf * gv * a.invM;
+                    vl = fmaxf(l1, l2);
+                }
+                st_vl += vl;
+            }
+            if (pi) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) DLOG[s * 4 + j] = dl[j];
-            DV[s] = dv;
+                for (int j = 0; j < 4; ++j) DLOG[s * 4 + j] = dl[j];
+            }
+            if (vf) DV[s] = dv;
         }
         __syncthreads();
         // 4. the heads' backward: the last hidden layer's delta, and the heads' own gradients (registers, one column per lane)
         for (int i = tid; i < kTile * H; i += kPpoBlock) {
             const int s = i / H, k = i - s * H;
-            float d = DV[s] * WH[4 * H + k];
-            for (int j = 0; j < A; ++j) d = fmaf(DLOG[s * 4 + j], WH[j * H + k], d);
+            float d = vf ? DV[s] * WH[4 * H + k] : 0.0f;
+            if (pi)
+                for (int j = 0; j < A; ++j) d = fmaf(DLOG[s * 4 + j], WH[j * H + k], d);
             DZ[s * SH + k] = d * dactivate(HL[s * SH + k], kind);
         }
         if (tid < H) {
             for (int s = 0; s < kTile; ++s) {
                 const float hk = HL[s * SH + tid];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) accW[j] = fmaf(DLOG[s * 4 + j], hk, accW[j]);
-                accWv = fmaf(DV[s], hk, accWv);
+                for (int j = 0; j < 4; ++j)
+                    if (pi) accW[j] = fmaf(DLOG[s * 4 + j], hk, accW[j]);
+                if (vf) accWv = fmaf(DV[s], hk, accWv);
             }
         } else if (tid >= 128 && tid <= 128 + A) {
             const int j = tid - 128;
-            accbh += j < A ? tile_sum(DLOG + j, 4) : tile_sum(DV, 1);
+            if (j < A ? pi : vf) accbh += j < A ? tile_sum(DLOG + j, 4) : tile_sum(DV, 1);
         }
         __syncthreads();
         // 5. the second hidden layer: dW1 = dZᵀ·HB0, db1, and the first layer's delta into HB1 (dead by now)
@@ -497,23 +516,29 @@ template <bool POP, bool EXT> __device__ __forceinline__ void ppo_grad_body(cons
         if (a.L == 2) {
             mm_wgrad(DZ, SH, HB0, SH, NT, NT, H, gW1, first, wave, lane);
             mm_backward(W1, H, DZ, HB0, HB1, SH, kind, wave, lane);
-            if (tid >= 128 && tid < 128 + H) accb1 += tile_sum(DZ + tid - 128, SH);
+            if (tid >= 128 && tid < 128 + H) (pass == 0 ? accb1 : accb1v) += tile_sum(DZ + tid - 128, SH);
             __syncthreads();
             DZ0 = HB1;
         }
         // 6. the first layer: dW0 = dZ0ᵀ·X, db0
         mm_wgrad(DZ0, SH, X, SX, NT, DT, D, gW0, first, wave, lane);
-        if (tid < H) accb0 += tile_sum(DZ0 + tid, SH);
+        if (tid < H) (pass == 0 ? accb0 : accb0v) += tile_sum(DZ0 + tid, SH);
         __syncthreads();
+        }
         first = false;
     }
     // the register-held sums into the slot
+    float *gb0 = g + H * D, *gb1 = gb0 + H + H * H;
     if (tid < H) {
         gb0[tid] = accb0;
         for (int j = 0; j < A; ++j) gWpi[j * H + tid] = accW[j];
         gWv[tid] = accWv;
+        if (SPLIT) gb0[T + A * H + A + tid] = accb0v;
     }
-    if (a.L == 2 && tid >= 128 && tid < 128 + H) gb1[tid - 128] = accb1;
+    if (a.L == 2 && tid >= 128 && tid < 128 + H) {
+        gb1[tid - 128] = accb1;
+        if (SPLIT) gb1[T + A * H + A + tid - 128] = accb1v;
+    }
     if (tid >= 128 && tid <= 128 + A) (tid - 128 < A ? gbpi[tid - 128] : gbv[0]) = accbh;
     if (tid < kTile) {
         RED[tid * 4 + 0] = st_pg;
@@ -536,15 +561,15 @@ template <bool POP, bool EXT> __device__ __forceinline__ void ppo_grad_body(cons
     }
 }
 
-template <bool POP> __global__ void __launch_bounds__(kPpoBlock) ppo_grad_kernel(const GradArgs a, const PopGradArgs pa)
+template <bool POP, bool SPLIT> __global__ void __launch_bounds__(kPpoBlock) ppo_grad_kernel(const GradArgs a, const PopGradArgs pa)
 {
-    ppo_grad_body<POP, false>(a, pa, ExtGradArgs{});
+    ppo_grad_body<POP, false, SPLIT>(a, pa, ExtGradArgs{});
 }
 
-template <bool POP>
+template <bool POP, bool SPLIT>
 __global__ void __launch_bounds__(kPpoBlock) ppo_grad_ext_kernel(const GradArgs a, const PopGradArgs pa, const ExtGradArgs ea)
 {
-    ppo_grad_body<POP, true>(a, pa, ea);
+    ppo_grad_body<POP, true, SPLIT>(a, pa, ea);
 }
 
 // grad[p] = sum over the slots (a fixed order); entries P..P+3 (when nstats) are the loss sums -> stats = sum / M.  With params: Adam, torch's
@@ -839,7 +864,8 @@ AdamArgs adam_args(const ssg_ppo_hparams &hp, int64_t step)
 int ppo_packed_len(const ssg_policy &p)
 {
     const int D = p.obs_dim, H = p.hidden, A = p.n_actions;
-    return H * D + H + (p.n_hidden_layers - 1) * (H * H + H) + A * H + A + H + 1;
+    const int tower = H * D + H + (p.n_hidden_layers - 1) * (H * H + H);
+    return ((p.activation & SSG_POLICY_SEPARATE_VALUE) ? 2 : 1) * tower + A * H + A + H + 1;
 }
 
 int ppo_grid(long long M)
@@ -859,10 +885,29 @@ size_t ppo_grad_lds_bytes(const ssg_policy &p)
 // (the extended instantiations add v_old, four logp_old and the fifth loss sum per sample of the tile: 1.5 KB)
 size_t ppo_grad_ext_lds_bytes(const ssg_policy &p) { return ppo_grad_lds_bytes(p) + 6 * kTile * sizeof(float); }
 
+// the gradient kernel's instantiation for a population or not, the extended loss or not, separate towers or not
+typedef void (*GradKernel)(const GradArgs, const PopGradArgs);
+typedef void (*GradExtKernel)(const GradArgs, const PopGradArgs, const ExtGradArgs);
+static GradKernel grad_plain(bool pop, bool split)
+{
+    if (split) return pop ? ppo_grad_kernel<true, true> : ppo_grad_kernel<false, true>;
+    return pop ? ppo_grad_kernel<true, false> : ppo_grad_kernel<false, false>;
+}
+static GradExtKernel grad_ext(bool pop, bool split)
+{
+    if (split) return pop ? ppo_grad_ext_kernel<true, true> : ppo_grad_ext_kernel<false, true>;
+    return pop ? ppo_grad_ext_kernel<true, false> : ppo_grad_ext_kernel<false, false>;
+}
+static const void *grad_kernel(bool pop, bool ext, bool split)
+{
+    return ext ? reinterpret_cast<const void *>(grad_ext(pop, split)) : reinterpret_cast<const void *>(grad_plain(pop, split));
+}
+
 hipError_t prepare_ppo()
 {
-    const void *kernels[4] = {reinterpret_cast<const void *>(ppo_grad_kernel<false>), reinterpret_cast<const void *>(ppo_grad_kernel<true>),
-                              reinterpret_cast<const void *>(ppo_grad_ext_kernel<false>), reinterpret_cast<const void *>(ppo_grad_ext_kernel<true>)};
+    const void *kernels[8] = {grad_kernel(false, false, false), grad_kernel(true, false, false), grad_kernel(false, true, false),
+                              grad_kernel(true, true, false),   grad_kernel(false, false, true), grad_kernel(true, false, true),
+                              grad_kernel(false, true, true),   grad_kernel(true, true, true)};
     for (const void *k : kernels) {
         hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
@@ -889,6 +934,7 @@ hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream)
 {
     const ssg_policy &p = *mb.policy;
     const bool pop = mb.table != nullptr; // a population reads its constants from the table: the POP instantiations
+    const bool split = (p.activation & SSG_POLICY_SEPARATE_VALUE) != 0;
     const PpoExtLaunch *ext = mb.ext;
     const int P = ppo_packed_len(p), G = ppo_grid(mb.M), stride = P + (ext ? kExtStats : 4);
     char *base = static_cast<char *>(mb.ws);
@@ -900,7 +946,7 @@ hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream)
     a.H = p.hidden;
     a.L = p.n_hidden_layers;
     a.A = p.n_actions;
-    a.kind = p.activation;
+    a.kind = p.activation & 0xff;
     a.params = p.dev_params;
     a.x = mb.batch.x;
     a.act = mb.batch.act;
@@ -928,7 +974,7 @@ hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream)
     const AdamArgs ad = mb.adam_mv && !pop ? adam_args(*mb.hp, mb.step) : AdamArgs{};
     const dim3 ggrid((unsigned)G, (unsigned)mb.members), rgrid((unsigned)((stride + 255) / 256), (unsigned)mb.members);
     if (!ext) {
-        hipLaunchKernelGGL(pop ? ppo_grad_kernel<true> : ppo_grad_kernel<false>, ggrid, dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a, pa);
+        hipLaunchKernelGGL(grad_plain(pop, split), ggrid, dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a, pa);
         hipLaunchKernelGGL(pop ? ppo_reduce_kernel<true> : ppo_reduce_kernel<false>, rgrid, dim3(256), 0, stream, (const float *)a.slots, G, P,
                            stride, (float)mb.M, mb.grad_out, mb.stats_out, params, mb.adam_mv, ad, mb.stats_stride, mb.adam_row);
         return hipGetLastError();
@@ -939,7 +985,7 @@ hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream)
     ea.kl_coef = ext->kl_coef;
     ea.pop_ext = ext->pop_ext;
     ea.vf_clip = ext->vf_clip;
-    hipLaunchKernelGGL(pop ? ppo_grad_ext_kernel<true> : ppo_grad_ext_kernel<false>, ggrid, dim3(kPpoBlock), ppo_grad_ext_lds_bytes(p), stream,
+    hipLaunchKernelGGL(grad_ext(pop, split), ggrid, dim3(kPpoBlock), ppo_grad_ext_lds_bytes(p), stream,
                        a, pa, ea);
     ExtReduceArgs er;
     er.kl_coef = ext->kl_coef;

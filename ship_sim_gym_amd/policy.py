@@ -6,6 +6,11 @@ to the library as ONE packed f32 device buffer — ``torch.cat([p.flatten() for 
 like train/ppo_torch.py's: ``body = Sequential(Linear, Tanh|ReLU[, Linear, Tanh|ReLU])``, heads ``pi`` (n_actions) and ``v`` (1) —
 plus the f64 observation scale.  ``refresh()`` re-packs it in place (same address) after an optimiser step.
 
+The reference trainers' own shape has a value network of its own (Stable-Baselines' ``MlpPolicy``: two 64-64 tanh towers; RLlib's
+default ``vf_share_layers=False``): ``pi_body`` and ``vf_body`` of one depth, width and activation, heads ``pi`` on the first and ``v``
+on the second, declared in the order ``pi_body, pi, vf_body, v``.  ``value_layers`` / ``from_actor_critic`` take that shape too
+(SSG_POLICY_SEPARATE_VALUE in the record's ``activation``).
+
 ``ShipVecEnv.policy_act`` / ``ShipVecEnv.rollout_policy`` run it.  ``forward_reference`` is a plain torch restatement for tests.
 """
 import ctypes as C
@@ -20,13 +25,19 @@ def _torch():
     return torch
 
 
-def packed_offsets(obs_dim, hidden, n_hidden_layers, n_actions):
-    """{name: (offset, shape)} of every tensor inside the packed buffer (include/shipsim.h, ssg_policy), and the total length."""
+def packed_offsets(obs_dim, hidden, n_hidden_layers, n_actions, separate_value=False):
+    """{name: (offset, shape)} of every tensor inside the packed buffer (include/shipsim.h, ssg_policy), and the total length.
+    separate_value: the vf tower V0, c0[, V1, c1] sits between the pi head and the v head."""
     D, H, A = int(obs_dim), int(hidden), int(n_actions)
     shapes = [("W0", (H, D)), ("b0", (H,))]
     if n_hidden_layers == 2:
         shapes += [("W1", (H, H)), ("b1", (H,))]
-    shapes += [("Wpi", (A, H)), ("bpi", (A,)), ("Wv", (1, H)), ("bv", (1,))]
+    shapes += [("Wpi", (A, H)), ("bpi", (A,))]
+    if separate_value:
+        shapes += [("V0", (H, D)), ("c0", (H,))]
+        if n_hidden_layers == 2:
+            shapes += [("V1", (H, H)), ("c1", (H,))]
+    shapes += [("Wv", (1, H)), ("bv", (1,))]
     out, o = {}, 0
     for name, shp in shapes:
         out[name] = (o, shp)
@@ -39,9 +50,11 @@ def packed_offsets(obs_dim, hidden, n_hidden_layers, n_actions):
 
 class NativePolicy(object):
     """layers: [(W0, b0)] or [(W0, b0), (W1, b1)] with W [out][in] (nn.Linear's order); pi, v: (W, b) of the heads; obs_scale: f64
-    [obs_dim] (or a number) — the device computes x = (float)(obs / obs_scale) as train/ppo_torch.py's normalise() does."""
+    [obs_dim] (or a number) — the device computes x = (float)(obs / obs_scale) as train/ppo_torch.py's normalise() does.
+    value_layers: None = `v` sits on `layers` (the shared body); otherwise the vf tower, a list of (W, b) shaped like `layers`, with
+    `pi` on `layers` and `v` on `value_layers`."""
 
-    def __init__(self, layers, pi, v, obs_scale, activation="tanh"):
+    def __init__(self, layers, pi, v, obs_scale, activation="tanh", value_layers=None):
         torch = _torch()
         if activation not in ACTIVATIONS:
             raise ValueError("activation must be 'tanh' or 'relu' (got %r)" % (activation,))
@@ -57,8 +70,16 @@ class NativePolicy(object):
         A = int(pi[0].shape[0])
         if A < 2 or A > 4:
             raise ValueError("NativePolicy: n_actions must be in 2..4 (ssg_step accepts actions 0..3; got %d)" % A)
-        want = [((H, D), (H,))] + [((H, H), (H,))] * (len(layers) - 1) + [((A, H), (A,)), ((1, H), (1,))]
-        for (W, b), (ws, bs) in zip(layers + [tuple(pi), tuple(v)], want):
+        tower = [((H, D), (H,))] + [((H, H), (H,))] * (len(layers) - 1)
+        self.separate_value = value_layers is not None
+        value_layers = [tuple(l) for l in value_layers] if self.separate_value else []
+        if self.separate_value and len(value_layers) != len(layers):
+            raise ValueError("NativePolicy: value_layers has %d layers, layers %d (both towers must have the same depth)"
+                             % (len(value_layers), len(layers)))
+        # (a vf tower of another width fails the shape check below)
+        ordered = layers + [tuple(pi)] + value_layers + [tuple(v)]  # the packed order
+        want = tower + [((A, H), (A,))] + (tower if self.separate_value else []) + [((1, H), (1,))]
+        for (W, b), (ws, bs) in zip(ordered, want):
             if tuple(W.shape) != ws or tuple(b.shape) != bs:
                 raise ValueError("NativePolicy: a (W, b) pair has shapes %s, %s where %s, %s belong" % (tuple(W.shape), tuple(b.shape), ws, bs))
             if W.dtype != torch.float32 or b.dtype != torch.float32 or W.device != W0.device or b.device != W0.device:
@@ -66,8 +87,8 @@ class NativePolicy(object):
         self.obs_dim, self.hidden, self.n_hidden_layers, self.n_actions = D, H, len(layers), A
         self.activation = activation
         self.device = W0.device
-        self._sources = [t for pair in layers + [tuple(pi), tuple(v)] for t in pair]
-        self.offsets, total = packed_offsets(D, H, len(layers), A)
+        self._sources = [t for pair in ordered for t in pair]
+        self.offsets, total = packed_offsets(D, H, len(layers), A, self.separate_value)
         with torch.no_grad():
             self.params = torch.empty(total, dtype=torch.float32, device=self.device)
             self.refresh()
@@ -81,28 +102,49 @@ class NativePolicy(object):
     @classmethod
     def from_actor_critic(cls, net, obs_scale):
         """A NativePolicy over the parameters OF `net` (refresh() picks up their new values after an optimiser step).  `net` must be
-        shaped like train/ppo_torch.py's ActorCritic; anything else raises ValueError."""
+        shaped like train/ppo_torch.py's ActorCritic, in one of its two shapes: ``body, pi, v`` (shared) or ``pi_body, pi, vf_body, v``
+        (separate value network); anything else raises ValueError."""
         nn = _torch().nn
+        shapes = "expected a module with body = nn.Sequential, pi = nn.Linear, v = nn.Linear (shared body), or with pi_body, vf_body = " \
+                 "nn.Sequential of one depth, width and activation, pi = nn.Linear, v = nn.Linear (separate value network)"
         body, pi, v = getattr(net, "body", None), getattr(net, "pi", None), getattr(net, "v", None)
-        if not isinstance(body, nn.Sequential) or not isinstance(pi, nn.Linear) or not isinstance(v, nn.Linear):
-            raise ValueError("from_actor_critic: expected a module with body = nn.Sequential, pi = nn.Linear, v = nn.Linear")
-        mods = list(body)
-        if len(mods) not in (2, 4):
-            raise ValueError("from_actor_critic: body must be Linear, act[, Linear, act] (1 or 2 hidden layers; got %d modules)" % len(mods))
+        pi_body, vf_body = getattr(net, "pi_body", None), getattr(net, "vf_body", None)
+        separate = pi_body is not None or vf_body is not None
+        if separate and body is not None:
+            raise ValueError("from_actor_critic: the module has both body and pi_body / vf_body; " + shapes)
+        if not isinstance(pi, nn.Linear) or not isinstance(v, nn.Linear):
+            raise ValueError("from_actor_critic: " + shapes)
+        bodies = [pi_body, vf_body] if separate else [body]
+        if not all(isinstance(b, nn.Sequential) for b in bodies):
+            raise ValueError("from_actor_critic: " + shapes)
         acts = {nn.Tanh: "tanh", nn.ReLU: "relu"}
         kinds = set()
-        layers = []
-        for lin, act in zip(mods[0::2], mods[1::2]):
-            if not isinstance(lin, nn.Linear) or type(act) not in acts or lin.bias is None:
-                raise ValueError("from_actor_critic: body must alternate nn.Linear (with bias) and nn.Tanh / nn.ReLU (got %s, %s)"
-                                 % (type(lin).__name__, type(act).__name__))
-            kinds.add(acts[type(act)])
-            layers.append((lin.weight, lin.bias))
+        towers = []
+        for b in bodies:
+            mods = list(b)
+            if len(mods) not in (2, 4):
+                raise ValueError("from_actor_critic: a body must be Linear, act[, Linear, act] (1 or 2 hidden layers; got %d modules)" % len(mods))
+            layers = []
+            for lin, act in zip(mods[0::2], mods[1::2]):
+                if not isinstance(lin, nn.Linear) or type(act) not in acts or lin.bias is None:
+                    raise ValueError("from_actor_critic: a body must alternate nn.Linear (with bias) and nn.Tanh / nn.ReLU (got %s, %s)"
+                                     % (type(lin).__name__, type(act).__name__))
+                kinds.add(acts[type(act)])
+                layers.append((lin.weight, lin.bias))
+            towers.append(layers)
         if len(kinds) != 1:
-            raise ValueError("from_actor_critic: every hidden layer must use the same activation")
+            raise ValueError("from_actor_critic: every hidden layer (of both towers) must use the same activation; " + shapes)
         if pi.bias is None or v.bias is None or v.out_features != 1:
             raise ValueError("from_actor_critic: heads must be nn.Linear with bias, v with one output")
-        return cls(layers, (pi.weight, pi.bias), (v.weight, v.bias), obs_scale, activation=kinds.pop())
+        if separate:
+            if len(towers[0]) != len(towers[1]) or towers[0][0][0].shape != towers[1][0][0].shape:
+                raise ValueError("from_actor_critic: pi_body and vf_body differ in depth or width; " + shapes)
+            names = [n for n, _ in net.named_children() if n in ("pi_body", "pi", "vf_body", "v")]
+            if names != ["pi_body", "pi", "vf_body", "v"]:
+                raise ValueError("from_actor_critic: the module must declare pi_body, pi, vf_body, v in that order (the packed layout is "
+                                 "torch.cat of its parameters()); got %s" % names)
+        return cls(towers[0], (pi.weight, pi.bias), (v.weight, v.bias), obs_scale, activation=kinds.pop(),
+                   value_layers=towers[1] if separate else None)
 
     def refresh(self):
         """Re-pack the parameters into the same device buffer (one torch.cat): call after every optimiser step."""
@@ -116,7 +158,7 @@ class NativePolicy(object):
         p = N.Policy()
         p.struct_size = C.sizeof(N.Policy)
         p.obs_dim, p.hidden, p.n_hidden_layers, p.n_actions = self.obs_dim, self.hidden, self.n_hidden_layers, self.n_actions
-        p.activation = ACTIVATIONS[self.activation]
+        p.activation = ACTIVATIONS[self.activation] | (N.POLICY_SEPARATE_VALUE if self.separate_value else 0)
         p.dev_params, p.dev_obs_scale = self.params.data_ptr(), self.obs_scale.data_ptr()
         return p
 
@@ -134,7 +176,12 @@ class NativePolicy(object):
             h = act(x @ t["W0"].T + t["b0"])
             if self.n_hidden_layers == 2:
                 h = act(h @ t["W1"].T + t["b1"])
-            return x, h @ t["Wpi"].T + t["bpi"], (h @ t["Wv"].T + t["bv"]).squeeze(-1)
+            hv = h
+            if self.separate_value:
+                hv = act(x @ t["V0"].T + t["c0"])
+                if self.n_hidden_layers == 2:
+                    hv = act(hv @ t["V1"].T + t["c1"])
+            return x, h @ t["Wpi"].T + t["bpi"], (hv @ t["Wv"].T + t["bv"]).squeeze(-1)
 
 
 def _numel(shape):

@@ -40,11 +40,12 @@ class NativePopulation(object):
         if not 1 <= len(members) <= N.POP_MAX_MEMBERS:
             raise ValueError("NativePopulation: 1..%d members (got %d)" % (N.POP_MAX_MEMBERS, len(members)))
         first = members[0]
-        shape = (first.obs_dim, first.hidden, first.n_hidden_layers, first.n_actions, first.activation, first.device)
+        shape = (first.obs_dim, first.hidden, first.n_hidden_layers, first.n_actions, first.activation, first.device, first.separate_value)
         for m, pol in enumerate(members):
-            if (pol.obs_dim, pol.hidden, pol.n_hidden_layers, pol.n_actions, pol.activation, pol.device) != shape:
-                raise ValueError("NativePopulation: member %d differs from member 0 in shape, activation or device" % m)
-        self.obs_dim, self.hidden, self.n_hidden_layers, self.n_actions, self.activation, self.device = shape
+            if (pol.obs_dim, pol.hidden, pol.n_hidden_layers, pol.n_actions, pol.activation, pol.device, pol.separate_value) != shape:
+                raise ValueError("NativePopulation: member %d differs from member 0 in shape (shared body or separate value network), "
+                                 "activation or device" % m)
+        self.obs_dim, self.hidden, self.n_hidden_layers, self.n_actions, self.activation, self.device, self.separate_value = shape
         self.offsets, self.n_params = first.offsets, first.params.numel()
         if obs_scale is None:
             obs_scale = first.obs_scale
@@ -63,13 +64,16 @@ class NativePopulation(object):
 
     @classmethod
     def from_actor_critics(cls, nets, obs_scale):
-        """A population over the parameters OF `nets` (modules shaped like train/ppo_torch.py's ActorCritic, all alike)."""
+        """A population over the parameters OF `nets` (modules shaped like train/ppo_torch.py's ActorCritic — shared body or separate
+        value network — all alike)."""
         return cls([NativePolicy.from_actor_critic(net, obs_scale) for net in nets])
 
     @classmethod
     def from_layers(cls, members, obs_scale, activation="tanh"):
-        """members: per member a (layers, pi, v) triple of (W, b) tensors, as NativePolicy's constructor takes them."""
-        return cls([NativePolicy(layers, pi, v, obs_scale, activation=activation) for layers, pi, v in members])
+        """members: per member a (layers, pi, v) triple of (W, b) tensors, as NativePolicy's constructor takes them, or a
+        (layers, pi, v, value_layers) quadruple for a separate value network."""
+        return cls([NativePolicy(m[0], m[1], m[2], obs_scale, activation=activation, value_layers=m[3] if len(m) > 3 else None)
+                    for m in members])
 
     def __len__(self):
         return len(self._members)
@@ -108,7 +112,7 @@ class NativePopulation(object):
         p.struct_size = C.sizeof(N.Population)
         p.n_members = len(self)
         p.obs_dim, p.hidden, p.n_hidden_layers, p.n_actions = self.obs_dim, self.hidden, self.n_hidden_layers, self.n_actions
-        p.activation = ACTIVATIONS[self.activation]
+        p.activation = ACTIVATIONS[self.activation] | (N.POLICY_SEPARATE_VALUE if self.separate_value else 0)
         p.dev_params, p.dev_obs_scale = self.params.data_ptr(), self.obs_scale.data_ptr()
         return p
 

@@ -9,7 +9,10 @@ the median per mode in us per rollout step.  The policy kernel's own time: HIP e
 on preallocated buffers (a launch-bound upper bound where the kernel is shorter than the host call; `rocprofv3 --kernel-trace --stats`
 gives the kernel alone, see tools/README.md).  One JSON line on stdout.
 
-    python tools/policy_rollout_timing.py [--envs 65536,4096] [--horizon 64] [--repeats 5]
+    python tools/policy_rollout_timing.py [--envs 65536,4096] [--horizon 64] [--repeats 5] [--separate-value]
+
+--separate-value measures, after each env count's shared-body figures and in the same process, the same things for ActorCritic with a
+value network of its own (two 64-64 towers: SSG_POLICY_SEPARATE_VALUE); its results carry "separate_value": true.
 """
 import argparse
 import ctypes as C
@@ -43,12 +46,12 @@ def _timed(fn):
     return e0.elapsed_time(e1) * 1e3  # us
 
 
-def measure(mod, n, horizon, repeats, dev):
+def measure(mod, n, horizon, repeats, dev, separate_value=False):
     torch.manual_seed(0)
     probe = mod.ShipVecEnv(1, mod.GameConfig, mod.EnvConfig, device=dev, n_maps=1)
     D, A = probe.states_history, probe.action_space.n
     probe.close()
-    net = mod.ActorCritic(D, A).to(dev)
+    net = mod.ActorCritic(D, A, separate_value=separate_value).to(dev)
     gen = torch.Generator(device=dev)
     gen.manual_seed(1)
     # graph mode, set up as train() does: reset, one eager warm-up step, reset, capture
@@ -93,7 +96,7 @@ def measure(mod, n, horizon, repeats, dev):
         s.env.close()
     g = statistics.median(times["graph"])
     nat = statistics.median(times["native"])
-    return {"envs": n, "obs_dim": D, "hidden": 64, "layers": 2, "n_actions": A, "horizon": horizon,
+    return {"envs": n, "separate_value": bool(separate_value), "obs_dim": D, "hidden": 64, "layers": 2, "n_actions": A, "horizon": horizon,
             "graph_us_per_step": round(g, 2), "native_us_per_step": round(nat, 2), "speedup": round(g / nat, 2),
             "native_env_steps_per_s": round(n / nat * 1e6), "policy_act_us": round(kernel_us, 2),
             "repeats_us": {k: [round(t, 2) for t in v] for k, v in times.items()}}
@@ -104,11 +107,12 @@ def main():
     ap.add_argument("--envs", default="65536,4096")
     ap.add_argument("--horizon", type=int, default=64)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--separate-value", action="store_true", help="also measure the separate-value-network shape, in the same process")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     mod = _ppo()
     dev = "cuda:0"
-    res = [measure(mod, int(n), a.horizon, a.repeats, dev) for n in a.envs.split(",")]
+    res = [measure(mod, int(n), a.horizon, a.repeats, dev, sep) for n in a.envs.split(",") for sep in ([False, True] if a.separate_value else [False])]
     print(json.dumps({"tool": "policy_rollout_timing", "device": torch.cuda.get_device_name(0), "results": res}))
 
 

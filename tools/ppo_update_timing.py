@@ -8,10 +8,12 @@ For each (envs, horizon) — default 65 536 x 32 and 4 096 x 64; default env (D 
 every update from the same parameters' values (their own copies) and draw their permutations from generators seeded alike.  One JSON
 line on stdout.  The kernels alone: `rocprofv3 --kernel-trace --stats -- python tools/ppo_update_timing.py --only native` (tools/README.md).
 
-    python tools/ppo_update_timing.py [--configs 65536x32,4096x64] [--repeats 7] [--only torch|native] [--ext]
+    python tools/ppo_update_timing.py [--configs 65536x32,4096x64] [--repeats 7] [--only torch|native] [--ext] [--separate-value]
 
 --ext adds, in the same run, the extended update (NativePPO with vf_clip 0.2, max_grad_norm 0.5, kl_coef 1.0, kl_target 0.01: GAE, the
 ssg_ppo_dist launch, ssg_ppo_update_ext) as the path "native_ext", and the ssg_ppo_dist launch alone as "dist".
+--separate-value measures, after each configuration's shared-body figures and in the same process, the same paths for ActorCritic with
+a value network of its own (two 64-64 towers: SSG_POLICY_SEPARATE_VALUE); its results carry "separate_value": true.
 """
 import argparse
 import importlib.util
@@ -73,20 +75,20 @@ def torch_update(net, opt, b, horizon, envs, D, epochs, minibatches, gen, gamma=
             opt.step()
 
 
-def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext=False):
+def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext=False, separate_value=False):
     from ship_sim_gym_amd.policy import NativePolicy
     from ship_sim_gym_amd.ppo import NativePPO
     torch.manual_seed(0)
     env = mod.ShipVecEnv(envs, mod.GameConfig, mod.EnvConfig, device=dev, n_maps=64)
     D, A = env.states_history, env.action_space.n
-    net = mod.ActorCritic(D, A).to(dev)
+    net = mod.ActorCritic(D, A, separate_value=separate_value).to(dev)
     scale = torch.full((D,), float(max(env.bounds)), dtype=torch.float64, device=dev)
     env.reset_tensor()
     pol_roll = NativePolicy.from_actor_critic(net, scale)
     b = dict(env.rollout_policy(pol_roll, horizon, seed=1))
     p0 = [p.detach().clone() for p in net.parameters()]
     # the torch path trains `net`; the native path a second module's packed parameters
-    net_n = mod.ActorCritic(D, A).to(dev)
+    net_n = mod.ActorCritic(D, A, separate_value=separate_value).to(dev)
     pol = NativePolicy.from_actor_critic(net_n, scale)
     opt = torch.optim.Adam(net.parameters(), lr=3e-4)
     ppo = NativePPO(pol, env)
@@ -138,7 +140,7 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
         for k, f in paths:
             times[k].append(_timed(f))
     env.close()
-    out = {"envs": envs, "horizon": horizon, "epochs": epochs, "minibatches": minibatches, "samples_per_minibatch": -(-n // minibatches)}
+    out = {"envs": envs, "separate_value": bool(separate_value), "horizon": horizon, "epochs": epochs, "minibatches": minibatches, "samples_per_minibatch": -(-n // minibatches)}
     for k, v in times.items():
         out[k + "_ms_per_update"] = statistics.median(v)
         out[k + "_ms_all"] = [round(x, 3) for x in v]
@@ -153,9 +155,11 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--only", choices=("torch", "native"), default=None)
     ap.add_argument("--ext", action="store_true", help="also time the extended update (all three terms on) and ssg_ppo_dist alone")
+    ap.add_argument("--separate-value", action="store_true", help="also measure the separate-value-network shape, in the same process")
     a = ap.parse_args()
     mod = _ppo()
-    res = [measure(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.repeats, a.only, "cuda:0", ext=a.ext) for c in a.configs.split(",")]
+    res = [measure(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.repeats, a.only, "cuda:0", ext=a.ext, separate_value=sep)
+           for c in a.configs.split(",") for sep in ([False, True] if a.separate_value else [False])]
     print(json.dumps({"ppo_update_timing": res}))
 
 

@@ -52,6 +52,8 @@ def make_arg_parser():
     ap.add_argument("--kl-target", type=float, default=0.01, help="the coefficient adapts against this mean KL (RLlib's default)")
     ap.add_argument("--vf-clip", type=float, default=0.0, help="value-loss clip range (0 = off)")
     ap.add_argument("--max-grad-norm", type=float, default=0.0, help="global gradient-norm clip (PPO2: 0.5; 0 = off)")
+    ap.add_argument("--separate-value", action="store_true",
+                    help="every member has a value network of its own (RLlib's default vf_share_layers=False) instead of a shared body")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -70,7 +72,8 @@ def parse_args(argv=None):
 
 
 def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every=5, seed=0, epochs=2, minibatches=4, lrs=None,
-          pbt=True, device="cuda:0", log=print, return_details=False, kl_coeff=0.0, kl_target=0.01, vf_clip=0.0, max_grad_norm=0.0):
+          pbt=True, device="cuda:0", log=print, return_details=False, kl_coeff=0.0, kl_target=0.01, vf_clip=0.0, max_grad_norm=0.0,
+          separate_value=False):
     import torch
     from ship_gym.config import EnvConfig, GameConfig
     from ship_sim_gym_amd.population import NativePopulation, PBTScheduler, PopulationPPO
@@ -92,7 +95,7 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
         for k, v in saved.items():
             setattr(GameConfig, k, v)
     D, A = env.states_history, env.action_space.n
-    nets = [ActorCritic(D, A).to(dev) for _ in range(P)]
+    nets = [ActorCritic(D, A, separate_value=separate_value).to(dev) for _ in range(P)]
     scale = torch.full((D,), float(max(env.bounds)), dtype=torch.float64, device=dev)
     pop = NativePopulation.from_actor_critics(nets, scale)
     ppo = PopulationPPO(pop, env, lam=INITIAL["lambda"], clip=INITIAL["clip_param"], lr=list(lrs) if lrs is not None else INITIAL["lr"],
@@ -139,7 +142,7 @@ def main(argv=None):
     a = parse_args(argv)
     train(members=a.members, envs_per_member=a.envs_per_member, updates=a.updates, horizon=a.horizon, perturb_every=a.perturb_every,
           seed=a.seed, epochs=a.epochs, minibatches=a.minibatches, lrs=a.lrs, pbt=a.pbt, device=a.device, kl_coeff=a.kl_coeff,
-          kl_target=a.kl_target, vf_clip=a.vf_clip, max_grad_norm=a.max_grad_norm)
+          kl_target=a.kl_target, vf_clip=a.vf_clip, max_grad_norm=a.max_grad_norm, separate_value=a.separate_value)
 
 
 if __name__ == "__main__":

@@ -4,7 +4,7 @@ device tensors — the role SubprocVecEnv + PPO2 play in the reference's train/s
 stable-baselines (absent from this image).  The env side is the only point: observations, rewards and dones never
 leave the GPU; the policy is a small MLP in fp32.
 
-    python train/ppo_torch.py --envs 4096 --updates 20 [--mode eager|graph|pingpong|native] [--update torch|native]
+    python train/ppo_torch.py --envs 4096 --updates 20 [--mode eager|graph|pingpong|native] [--update torch|native] [--separate-value]
 
 Four ways to run the rollout loop (the reference's `model.learn` -> runner.run(): one `env.step(actions)` per policy
 forward, train/stable_baselines/ppo.py:84-100,122-123) — same arithmetic, same results bit for bit:
@@ -52,13 +52,28 @@ from ship_sim_gym_amd.ppo import NativePPO  # noqa: E402
 
 
 class ActorCritic(nn.Module):
-    def __init__(self, obs_dim, n_actions, hidden=64):
+    """separate_value=False: one body under both heads.  True: the reference trainers' own shape — Stable-Baselines' MlpPolicy
+    (train/stable_baselines/ppo.py: net_arch [dict(vf=[64, 64], pi=[64, 64])], tanh) and RLlib's default vf_share_layers=False
+    (train/rllib/pbt.py) — a pi tower under the logits and a vf tower under the value, declared in the packed order
+    pi_body, pi, vf_body, v (ship_sim_gym_amd/policy.py)."""
+
+    def __init__(self, obs_dim, n_actions, hidden=64, separate_value=False):
         super().__init__()
-        self.body = nn.Sequential(nn.Linear(obs_dim, hidden), nn.Tanh(), nn.Linear(hidden, hidden), nn.Tanh())
-        self.pi = nn.Linear(hidden, n_actions)
-        self.v = nn.Linear(hidden, 1)
+        tower = lambda: nn.Sequential(nn.Linear(obs_dim, hidden), nn.Tanh(), nn.Linear(hidden, hidden), nn.Tanh())  # noqa: E731
+        self.separate_value = bool(separate_value)
+        if not self.separate_value:
+            self.body = tower()
+            self.pi = nn.Linear(hidden, n_actions)
+            self.v = nn.Linear(hidden, 1)
+        else:
+            self.pi_body = tower()
+            self.pi = nn.Linear(hidden, n_actions)
+            self.vf_body = tower()
+            self.v = nn.Linear(hidden, 1)
 
     def forward(self, x):
+        if self.separate_value:
+            return self.pi(self.pi_body(x)), self.v(self.vf_body(x)).squeeze(-1)
         h = self.body(x)
         return self.pi(h), self.v(h).squeeze(-1)
 
@@ -182,7 +197,7 @@ def rollout(shards, horizon, mode, gen, policy=None):
 
 
 def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, gamma=0.99, lam=0.95, clip=0.2,
-          device="cuda:0", seed=0, log=print, mode="eager", return_details=False, env_kw=None, update="torch"):
+          device="cuda:0", seed=0, log=print, mode="eager", return_details=False, env_kw=None, update="torch", separate_value=False):
     assert mode in ("eager", "graph", "pingpong", "native")
     if update not in ("torch", "native"):
         raise ValueError("update must be 'torch' or 'native' (got %r)" % (update,))
@@ -195,7 +210,7 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
     probe = ShipVecEnv(1, GameConfig, EnvConfig, device=device, n_maps=1)
     D, A = probe.states_history, probe.action_space.n
     probe.close()
-    net = ActorCritic(D, A).to(dev)
+    net = ActorCritic(D, A, separate_value=separate_value).to(dev)
     opt = torch.optim.Adam(net.parameters(), lr=lr)
     shards = make_shards(envs, mode, net, device, horizon, env_kw=env_kw)
     for sh in shards:
@@ -293,6 +308,8 @@ def make_arg_parser():
     ap.add_argument("--mode", choices=("eager", "graph", "pingpong", "native"), default="graph")
     ap.add_argument("--update", choices=("torch", "native"), default="torch",
                     help="where GAE and the PPO update run: eager PyTorch, or on the device (needs --mode native)")
+    ap.add_argument("--separate-value", action="store_true",
+                    help="a value network of its own (SB's MlpPolicy, RLlib's vf_share_layers=False) instead of a shared body; every --mode")
     return ap
 
 
@@ -307,4 +324,4 @@ def parse_args(argv=None):
 
 if __name__ == "__main__":
     a = parse_args()
-    train(envs=a.envs, updates=a.updates, horizon=a.horizon, mode=a.mode, update=a.update)
+    train(envs=a.envs, updates=a.updates, horizon=a.horizon, mode=a.mode, update=a.update, separate_value=a.separate_value)

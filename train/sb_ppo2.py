@@ -8,6 +8,7 @@ TensorBoard / model directories.
 
 stable-baselines (2.2.0 in the reference's requirements) is not part of this image: the imports are guarded, and
 `tests/test_trainer_scripts.py` drives main() up to the first reset / step_async / step_wait under stand-in modules."""
+# (MlpPolicy's own shape, two separate 64-64 tanh towers, on the device: train/ppo_torch.py --mode native --update native --separate-value)
 import argparse
 import os
 import sys
