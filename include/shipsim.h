@@ -647,7 +647,8 @@ int ssg_ppo_update_ext(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hpara
  * Samples.  The rollout buffers are the [K][N] buffers of ssg_rollout_policy, N = n_envs.  Member m's sample i = t*n + e (e < n) is
  * row t*N + m*n + e of them; dev_perm is int64 [P][epochs][K*n] of such member-local indices.
  *
- * Hyper-parameters are per member (a host array of P ssg_ppo_hparams); epochs and minibatches are common to the population.  The f32
+ * Hyper-parameters are per member (a host array of P ssg_ppo_hparams); epochs and minibatches are common to the population in
+ * ssg_pop_update / ssg_pop_update_ext and per member in ssg_pop_update_sched (below).  The f32
  * constants the kernels use (1 -+ clip, the coefficients, gamma, gamma*lam, adv_eps, and per Adam step 1-beta1, beta2, 1-beta2,
  * sqrt(1-beta2^t), eps, -lr/(1-beta1^t)) are derived on the host, in double, exactly as the single-policy entry points derive them, by
  * ssg_pop_pack_hparams into a caller buffer of SSG_POP_TABLE_FLOATS floats; the caller uploads it and passes the device copy
@@ -655,9 +656,9 @@ int ssg_ppo_update_ext(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hpara
  *
  * Workspace: ssg_pop_workspace_nbytes bytes, 256-byte aligned; ssg_pop_gae leaves f32 [P][4] advantage statistics (mean, std + adv_eps,
  * its inverse, 0) at its start, per member over that member's K*n samples, which ssg_pop_update reads.  dev_adam_mv: f32 [P][2L].
- * The extended loss terms are per member too (ssg_pop_update_ext below).  Out of scope: per-member epochs / minibatch sizes / batch
- * sizes (they change launch shapes), PPO2's per-minibatch advantage normalisation, populations spanning handles or GPUs, per-member
- * architectures.
+ * The extended loss terms are per member too (ssg_pop_update_ext below), and so may the epochs and the minibatch count be
+ * (ssg_pop_update_sched).  Out of scope: per-member batch sizes (train_batch_size: unequal env slices or rollout lengths), PPO2's
+ * per-minibatch advantage normalisation, populations spanning handles or GPUs, per-member architectures.
  * ------------------------------------------------------------------------------------------------- */
 #define SSG_POP_MAX_MEMBERS 256
 #define SSG_POP_TABLE_FLOATS(n_members, n_steps) ((size_t)(n_members) * 8u * (size_t)(1 + (n_steps)))
@@ -754,6 +755,50 @@ int ssg_pop_update_ext(ssg_handle *h, const ssg_population *pop, const ssg_pop_e
                        const float *dev_x, const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret,
                        const int64_t *dev_perm, int epochs, int minibatches, float *dev_adam_mv, float *dev_stats /* nullable */,
                        void *dev_workspace, size_t workspace_nbytes, void *stream);
+
+/* Per-member schedules: member m runs epochs[m] epochs of its own chunking of its K*n samples (minibatches[m] asked for; torch.chunk's
+ * split: chunks of C_m = ceil(K*n / minibatches[m]), the last one shorter, chunks_m = ceil(K*n / C_m) of them), steps_m = epochs[m] *
+ * chunks_m Adam steps in all.  Launch j of the update serves minibatch j of every member that still has one, n_launches = max steps_m
+ * launch groups, each as wide as max C_m needs.  What differs between the members within a launch travels in a device table of int32,
+ * SSG_POP_SCHED_ROW per member (steps_m, chunks_m, C_m, epochs[m], 0...) followed, per launch j and member m, by a record of
+ * SSG_POP_SCHED_ROW: [0..1] the int64 offset of the minibatch in the member's permutation rows (ep * K*n + b0), [2] its length M,
+ * [3] the member's own gradient grid G (min(ceil(M / 64), 512): the single-policy grid for M, so the member's sums run in the
+ * single-policy order), [4] 1 on the first chunk of an epoch, [5] 1 while j < steps_m (else the record is all zeros and the member
+ * sits the launch out), [6] the f32 bits of 1 / (float)M, [7] 0. */
+#define SSG_POP_SCHED_ROW 8
+#define SSG_POP_SCHED_INTS(n_members, n_launches) ((size_t)(n_members) * 8u * (size_t)(1 + (n_launches)))
+
+/* Replaces nothing (host only; ray hands every trial its own num_sgd_iter / sgd_minibatch_size in its config dict, train/rllib/pbt.py:40-41
+ * the mutated ones, :65-68 the initial draws).  Packs the schedule table for samples_per_member = K*n samples.  steps_out (nullable)
+ * receives steps_m, *n_launches_out max steps_m.  out == NULL is the size query: only those are written and the table needs
+ * SSG_POP_SCHED_INTS(n_members, *n_launches_out) int32.  SSG_ERR_BAD_ARG for NULL epochs / minibatches / n_launches_out, n_members out
+ * of range, samples_per_member < 1, an entry < 1, a step count beyond 2^31-1 or out_ints too small. */
+int ssg_pop_pack_schedule(int n_members, int64_t samples_per_member, const int32_t *epochs, const int32_t *minibatches,
+                          int32_t *out /* nullable */, size_t out_ints, int32_t *steps_out /* nullable */, int32_t *n_launches_out);
+
+/* Replaces nothing (host only; the per-trial optimiser state ray restores with a checkpoint, train/rllib/pbt.py:29-43).
+ * ssg_pop_pack_hparams for members that have taken different numbers of Adam steps (they do once their schedules differ, pbt.py:40-41):
+ * the Adam rows of member m are steps step0[m] + 1 .. step0[m] + n_steps — bitwise what ssg_pop_pack_hparams writes for that member
+ * when called with step0 = step0[m].  Refusals as ssg_pop_pack_hparams (NULL step0, an entry < 0). */
+int ssg_pop_pack_hparams_steps(int n_members, const ssg_ppo_hparams *hparams, const int64_t *step0, int n_steps, float *out,
+                               size_t out_floats);
+
+/* Replaces: the SGD phase of every trial with the trial's OWN num_sgd_iter and sgd_minibatch_size (train/rllib/pbt.py:40-41 mutated,
+ * :65-68 drawn from {10, 20, 30} and {128, 512, 2048}).  ssg_pop_update (ext == NULL) or ssg_pop_update_ext on per-member schedules:
+ * epochs / minibatches are host arrays of P entries, dev_sched the device copy of ssg_pop_pack_schedule's table for them, dev_table
+ * ssg_pop_pack_hparams(_steps)' for table_steps >= n_launches Adam steps, dev_perm int64 [P][perm_epochs][K*n] with perm_epochs >=
+ * max epochs (member m reads its first epochs[m] rows).  The workspace is ssg_pop_workspace_nbytes' for max_minibatch = max C_m.
+ * dev_stats (nullable): f32 [P][n_launches][4, or 8 with ext]; member m's rows past steps_m are not written.  Two launches per launch
+ * group (three with SSG_POP_EXT_GRAD_CLIP), plus the KL adaptation, in which member m divides by its own chunks_m.  Member m's
+ * parameters, moments, stats rows and coefficient are bitwise those of ssg_ppo_update(_ext) on its slice with epochs[m] and
+ * minibatches[m]; with equal entries the call computes what ssg_pop_update(_ext) computes.  SSG_ERR_BAD_ARG (nothing launched) as
+ * ssg_pop_update / ssg_pop_update_ext, and for NULL epochs / minibatches / dev_sched, an entry < 1, perm_epochs < max epochs or
+ * table_steps < n_launches. */
+int ssg_pop_update_sched(ssg_handle *h, const ssg_population *pop, const ssg_pop_ext *ext /* nullable: the plain loss */,
+                         const float *dev_table, int table_steps, const int32_t *dev_sched, const int32_t *epochs,
+                         const int32_t *minibatches, int perm_epochs, int K, const float *dev_x, const int32_t *dev_act,
+                         const float *dev_logp, const float *dev_adv, const float *dev_ret, const int64_t *dev_perm, float *dev_adam_mv,
+                         float *dev_stats /* nullable */, void *dev_workspace, size_t workspace_nbytes, void *stream);
 
 /* Replaces: PopulationBasedTraining's exploit step (train/rllib/pbt.py:29-43: a bottom-quantile trial restores a top-quantile trial's
  * checkpoint), on the device: member m takes the parameter row AND the Adam moments of member src[m] (host array int32 [P];

@@ -28,6 +28,16 @@ def pop_table_floats(n_members, n_steps):
     return int(n_members) * 8 * (1 + int(n_steps))
 
 
+POP_SCHED_ROW = 8  # int32 per member of a schedule table's header, and per member and launch of its records
+# a record's fields (include/shipsim.h): the int64 offset takes entries 0 and 1
+SCHED_M, SCHED_G, SCHED_FIRST, SCHED_ACTIVE, SCHED_INVM = 2, 3, 4, 5, 6
+
+
+def pop_sched_ints(n_members, n_launches):
+    """SSG_POP_SCHED_INTS: the int32 ssg_pop_pack_schedule writes for n_members members and n_launches launches."""
+    return int(n_members) * POP_SCHED_ROW * (1 + int(n_launches))
+
+
 (F_X, F_Y, F_VX, F_VY, F_ANGLE, F_W, F_CUM_REWARD, F_LIDAR, F_RUDDER, F_STEP_COUNT, F_MAP_ID, F_GOAL_MASK,
  F_STATS, F_TRAFFIC, F_GOAL_BODIES, F_DYN_FLAGS, F_EPISODES, F_DYN_MEMO_STATS,
  F_DYN_LIVE, F_DYN_ARB_META, F_DYN_ARB_HASH, F_DYN_ARB_IMPULSE) = range(22)
@@ -46,6 +56,7 @@ EXPORTS = (
     "ssg_pop_act", "ssg_pop_rollout", "ssg_pop_pack_hparams", "ssg_pop_workspace_nbytes", "ssg_pop_gae", "ssg_pop_update",
     "ssg_pop_exploit", "ssg_pop_episode_stats",
     "ssg_ppo_dist", "ssg_ppo_grad_ext", "ssg_ppo_update_ext", "ssg_pop_dist", "ssg_pop_update_ext",
+    "ssg_pop_pack_schedule", "ssg_pop_pack_hparams_steps", "ssg_pop_update_sched",
 )
 
 
@@ -187,6 +198,10 @@ def lib():
                                      vp, C.c_size_t, vp]
     L.ssg_pop_dist.argtypes = [vp, pp, C.c_int, vp, vp, vp]
     L.ssg_pop_update_ext.argtypes = [vp, pp, qp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_size_t, vp]
+    L.ssg_pop_pack_schedule.argtypes = [C.c_int, C.c_int64, i32p, i32p, i32p, C.c_size_t, i32p, i32p]
+    L.ssg_pop_pack_hparams_steps.argtypes = [C.c_int, hp, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_float), C.c_size_t]
+    L.ssg_pop_update_sched.argtypes = [vp, pp, qp, vp, C.c_int, vp, i32p, i32p, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                       C.c_size_t, vp]
     L.ssg_render.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, vp]
     L.ssg_dyn_invalidate.argtypes = [vp, vp, vp]
     L.ssg_host_convex_hull.argtypes = [C.c_int, dp, dp, ip]

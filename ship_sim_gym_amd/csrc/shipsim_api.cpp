@@ -1180,37 +1180,52 @@ static Chunking chunking(long long n, int minibatches)
     return {C, (n + C - 1) / C};
 }
 
-// The epochs x chunks loop of the four update entry points.  mb: the record as its entry point filled it, with idx = the [epochs][n]
-// permutation rows (a population: [members][epochs][n]), stats_out = the caller's stats rows or NULL, step = the Adam steps taken so
-// far, table = a population's table; ext: nullable.  Minibatch j of the call reads chunk j % chunks of permutation row j / chunks,
-// takes Adam step step + 1 + j (a population: the table's Adam rows 1 + j) and writes stats row j.  kl_adapt: end with the
-// adaptation of the coefficient(s) from the last epoch's chunks.  what: the entry point's name in a launch failure's message.
+// A population on per-member schedules (ssg_pop_update_sched): what run_update takes from the schedule instead of from epochs x chunks.
+struct PopSchedule {
+    const int32_t *dev_sched; // the device table: header rows, then the records of launch 0, 1, ...
+    long long n_launches;     // max steps_m
+    long long Cmax;           // max C_m: every launch is as wide as the longest minibatch of the call needs
+    int perm_epochs;          // permutation rows per member
+};
+
+// The loop of the five update entry points.  mb: the record as its entry point filled it, with idx = the [epochs][n] permutation rows
+// (a population: [members][epochs][n]), stats_out = the caller's stats rows or NULL, step = the Adam steps taken so far, table = a
+// population's table; ext: nullable.  Minibatch j of the call reads chunk j % chunks of permutation row j / chunks, takes Adam step
+// step + 1 + j (a population: the table's Adam rows 1 + j) and writes stats row j.  With sched (epochs / minibatches unused) launch j
+// serves minibatch j of every member that has one: M, the chunk's place and first_chunk are per member, in the table's records of
+// launch j; the launch itself is sized for Cmax.  kl_adapt: end with the adaptation of the coefficient(s) from the last epoch's
+// chunks.  what: the entry point's name in a launch failure's message.
 static int run_update(ssg_handle *h, ssg::PpoMinibatch mb, ssg::PpoExtLaunch *ext, int epochs, int minibatches, bool kl_adapt, float kl_target,
-                      const char *what, hipStream_t st)
+                      const char *what, hipStream_t st, const PopSchedule *sched = nullptr)
 {
     const long long n = mb.n_samples;
-    const Chunking ck = chunking(n, minibatches);
+    const Chunking ck = sched ? Chunking{sched->Cmax, 0} : chunking(n, minibatches);
+    const long long launches = sched ? sched->n_launches : (long long)epochs * ck.chunks;
     const int cols = ext ? ssg::kExtStats : 4;
     const int64_t *perm = mb.idx;
     float *stats = mb.stats_out;
     mb.ext = ext;
-    mb.idx_stride = (long long)epochs * n;
-    mb.stats_stride = cols * (long long)epochs * ck.chunks;
-    long long j = 0;
-    for (int ep = 0; ep < epochs; ++ep) {
-        for (long long b0 = 0; b0 < n; b0 += ck.C, ++j) {
+    mb.idx_stride = (long long)(sched ? sched->perm_epochs : epochs) * n;
+    mb.stats_stride = cols * launches;
+    for (long long j = 0; j < launches; ++j) {
+        if (sched) {
+            mb.M = sched->Cmax;
+            mb.sched = sched->dev_sched + (size_t)(1 + j) * (size_t)mb.members * ssg::kPopSchedRow;
+        } else {
+            const long long ep = j / ck.chunks, b0 = (j - ep * ck.chunks) * ck.C;
             mb.M = std::min(ck.C, n - b0);
             mb.idx = perm + (size_t)ep * (size_t)n + (size_t)b0;
-            mb.stats_out = stats ? stats + cols * j : nullptr;
-            ++mb.step;
-            if (mb.table) mb.adam_row = mb.table + (size_t)(1 + j) * (size_t)mb.members * ssg::kPopTableRow;
             if (ext) ext->first_chunk = b0 == 0;
-            hipError_t e = ssg::launch_ppo_minibatch(mb, st);
-            if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
         }
+        mb.stats_out = stats ? stats + cols * j : nullptr;
+        ++mb.step;
+        if (mb.table) mb.adam_row = mb.table + (size_t)(1 + j) * (size_t)mb.members * ssg::kPopTableRow;
+        hipError_t e = ssg::launch_ppo_minibatch(mb, st);
+        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
     }
     if (kl_adapt) {
-        hipError_t e = ssg::launch_kl_adapt(mb.members, *ext, kl_target, ssg::ppo_packed_len(*mb.policy), ck.chunks, mb.ws, mb.slots_off, st);
+        hipError_t e = ssg::launch_kl_adapt(mb.members, *ext, kl_target, ssg::ppo_packed_len(*mb.policy), ck.chunks,
+                                            sched ? sched->dev_sched : nullptr, mb.ws, mb.slots_off, st);
         if (e != hipSuccess)
             return fail(h, SSG_ERR_HIP, std::string(mb.table ? "population kl adapt launch: " : "kl adapt launch: ") + hipGetErrorString(e));
     }
@@ -1554,11 +1569,12 @@ int ssg_pop_gae(ssg_handle *h, const ssg_population *pop, const float *dev_table
     return SSG_OK;
 }
 
-// What ssg_pop_update and ssg_pop_update_ext refuse alike once the population record (and the ext record) passed, in their order;
-// then the minibatch record of the population's update, but for what run_update sets per minibatch.
+// What the population's update entry points refuse alike once the population record (and the ext record) passed, in their order;
+// then the minibatch record of the population's update, but for what run_update sets per minibatch.  sched: ssg_pop_update_sched's
+// per-member epochs / minibatches (checked by its caller, as the table's steps are) in place of the common ones.
 static int check_pop_update(ssg_handle *h, const ssg_policy *pol, int P, const float *dev_table, int table_steps, int K,
                             const ssg::PpoBatch &batch, const int64_t *dev_perm, int epochs, int minibatches, float *dev_adam_mv,
-                            const char *what, ssg::PpoMinibatch *mb)
+                            const char *what, ssg::PpoMinibatch *mb, bool sched = false)
 {
     const std::string w(what);
     if (K < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": K < 1");
@@ -1567,9 +1583,11 @@ static int check_pop_update(ssg_handle *h, const ssg_policy *pol, int P, const f
     int rc = check_batch(h, n, batch, dev_perm, what);
     if (rc != SSG_OK) return rc;
     if (!dev_table || !dev_adam_mv) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_table or dev_adam_mv");
-    if (epochs < 1 || minibatches < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": epochs < 1 or minibatches < 1");
-    if ((long long)table_steps < (long long)epochs * chunking(n, minibatches).chunks)
-        return fail(h, SSG_ERR_BAD_ARG, w + ": the table holds fewer Adam steps than epochs * chunks");
+    if (!sched) {
+        if (epochs < 1 || minibatches < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": epochs < 1 or minibatches < 1");
+        if ((long long)table_steps < (long long)epochs * chunking(n, minibatches).chunks)
+            return fail(h, SSG_ERR_BAD_ARG, w + ": the table holds fewer Adam steps than epochs * chunks");
+    }
     *mb = {};
     mb->policy = pol;
     mb->members = P;
@@ -1624,6 +1642,19 @@ int ssg_pop_dist(ssg_handle *h, const ssg_population *pop, int K, const float *d
     return SSG_OK;
 }
 
+// the ssg_pop_ext record, for ssg_pop_update_ext and ssg_pop_update_sched
+static int check_pop_ext(ssg_handle *h, const ssg_pop_ext *ext, const char *what)
+{
+    const std::string w(what);
+    if (!ext) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL ssg_pop_ext");
+    if (ext->struct_size != sizeof(ssg_pop_ext)) return fail(h, SSG_ERR_BAD_ARG, w + ": ssg_pop_ext.struct_size != sizeof(ssg_pop_ext)");
+    if (ext->flags & ~(SSG_POP_EXT_GRAD_CLIP | SSG_POP_EXT_VF_CLIP)) return fail(h, SSG_ERR_BAD_ARG, w + ": unknown ssg_pop_ext.flags bits");
+    if (!ext->dev_ext) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_ext");
+    if (ext->dev_kl_coef && !ext->dev_logp_all) return fail(h, SSG_ERR_BAD_ARG, w + ": dev_kl_coef without dev_logp_all (ssg_pop_dist)");
+    if ((ext->flags & SSG_POP_EXT_VF_CLIP) && !ext->dev_value_old) return fail(h, SSG_ERR_BAD_ARG, w + ": SSG_POP_EXT_VF_CLIP without dev_value_old");
+    return SSG_OK;
+}
+
 int ssg_pop_update_ext(ssg_handle *h, const ssg_population *pop, const ssg_pop_ext *ext, const float *dev_table, int table_steps, int K,
                        const float *dev_x, const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret,
                        const int64_t *dev_perm, int epochs, int minibatches, float *dev_adam_mv, float *dev_stats, void *dev_workspace,
@@ -1633,13 +1664,8 @@ int ssg_pop_update_ext(ssg_handle *h, const ssg_population *pop, const ssg_pop_e
     int rc = pop_bound(h);
     if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_update_ext");
     if (rc != SSG_OK) return rc;
-    if (!ext) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: NULL ssg_pop_ext");
-    if (ext->struct_size != sizeof(ssg_pop_ext)) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: ssg_pop_ext.struct_size != sizeof(ssg_pop_ext)");
-    if (ext->flags & ~(SSG_POP_EXT_GRAD_CLIP | SSG_POP_EXT_VF_CLIP)) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: unknown ssg_pop_ext.flags bits");
-    if (!ext->dev_ext) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: NULL dev_ext");
-    if (ext->dev_kl_coef && !ext->dev_logp_all) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: dev_kl_coef without dev_logp_all (ssg_pop_dist)");
-    if ((ext->flags & SSG_POP_EXT_VF_CLIP) && !ext->dev_value_old)
-        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_ext: SSG_POP_EXT_VF_CLIP without dev_value_old");
+    rc = check_pop_ext(h, ext, "ssg_pop_update_ext");
+    if (rc != SSG_OK) return rc;
     const ssg_policy pol = pop_policy(*pop);
     const int P = pop->n_members;
     ssg::PpoMinibatch mb;
@@ -1655,6 +1681,123 @@ int ssg_pop_update_ext(ssg_handle *h, const ssg_population *pop, const ssg_pop_e
     mb.stats_out = dev_stats;
     return run_update(h, mb, &el, epochs, minibatches, ext->dev_kl_coef != nullptr, 0.0f, "population update_ext",
                       static_cast<hipStream_t>(stream));
+}
+
+// The schedule of `members` members over n samples each: steps / launches / the longest chunk, and (out != NULL) the table.  false: an
+// entry < 1 or a step count that does not fit an int32.
+static bool pop_schedule(int members, long long n, const int32_t *epochs, const int32_t *minibatches, int32_t *out, int32_t *steps_out,
+                         long long *n_launches, long long *Cmax)
+{
+    long long launches = 0, cmax = 0;
+    for (int m = 0; m < members; ++m) {
+        if (epochs[m] < 1 || minibatches[m] < 1) return false;
+        const Chunking ck = chunking(n, minibatches[m]);
+        const long long steps = (long long)epochs[m] * ck.chunks;
+        if (steps > 0x7fffffffll || ck.C > 0x7fffffffll) return false;
+        if (steps_out) steps_out[m] = (int32_t)steps;
+        launches = std::max(launches, steps);
+        cmax = std::max(cmax, ck.C);
+    }
+    *n_launches = launches;
+    *Cmax = cmax;
+    if (!out) return true;
+    const size_t R = ssg::kPopSchedRow;
+    std::memset(out, 0, SSG_POP_SCHED_INTS(members, launches) * sizeof(int32_t));
+    for (int m = 0; m < members; ++m) {
+        const Chunking ck = chunking(n, minibatches[m]);
+        const long long steps = (long long)epochs[m] * ck.chunks;
+        int32_t *hdr = out + (size_t)m * R;
+        hdr[ssg::SH_STEPS] = (int32_t)steps;
+        hdr[ssg::SH_CHUNKS] = (int32_t)ck.chunks;
+        hdr[ssg::SH_C] = (int32_t)ck.C;
+        hdr[ssg::SH_EPOCHS] = epochs[m];
+        for (long long j = 0; j < steps; ++j) {
+            const long long ep = j / ck.chunks, b0 = (j - ep * ck.chunks) * ck.C, M = std::min(ck.C, n - b0), off = ep * n + b0;
+            int32_t *rec = out + ((size_t)(1 + j) * (size_t)members + (size_t)m) * R;
+            const float invM = 1.0f / (float)M; // (as launch_ppo_minibatch forms it for one policy's kernel arguments)
+            std::memcpy(rec + ssg::SR_OFF, &off, sizeof off);
+            rec[ssg::SR_M] = (int32_t)M;
+            rec[ssg::SR_G] = ssg::ppo_grid(M);
+            rec[ssg::SR_FIRST] = b0 == 0;
+            rec[ssg::SR_ACTIVE] = 1;
+            std::memcpy(rec + ssg::SR_INVM, &invM, sizeof invM);
+        }
+    }
+    return true;
+}
+
+int ssg_pop_pack_schedule(int n_members, int64_t samples_per_member, const int32_t *epochs, const int32_t *minibatches, int32_t *out,
+                          size_t out_ints, int32_t *steps_out, int32_t *n_launches_out)
+{
+    if (!epochs || !minibatches || !n_launches_out || n_members < 1 || n_members > SSG_POP_MAX_MEMBERS || samples_per_member < 1)
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_schedule: NULL epochs, minibatches or n_launches_out, n_members out of range or samples_per_member < 1");
+    long long launches = 0, cmax = 0;
+    if (!pop_schedule(n_members, samples_per_member, epochs, minibatches, nullptr, steps_out, &launches, &cmax))
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_schedule: a member's epochs or minibatches is < 1 (or its steps exceed 2^31-1)");
+    *n_launches_out = (int32_t)launches;
+    if (!out) return SSG_OK; // the size query
+    if (out_ints < SSG_POP_SCHED_INTS(n_members, launches))
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_schedule: out_ints < SSG_POP_SCHED_INTS(n_members, n_launches)");
+    pop_schedule(n_members, samples_per_member, epochs, minibatches, out, steps_out, &launches, &cmax);
+    return SSG_OK;
+}
+
+int ssg_pop_pack_hparams_steps(int n_members, const ssg_ppo_hparams *hparams, const int64_t *step0, int n_steps, float *out, size_t out_floats)
+{
+    if (!hparams || !out || !step0 || n_members < 1 || n_members > SSG_POP_MAX_MEMBERS || n_steps < 0)
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_hparams_steps: NULL pointer, n_members out of range or n_steps < 0");
+    for (int m = 0; m < n_members; ++m)
+        if (step0[m] < 0) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_hparams_steps: a member's step0 is < 0");
+    if (out_floats < SSG_POP_TABLE_FLOATS(n_members, n_steps))
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_hparams_steps: out_floats < SSG_POP_TABLE_FLOATS(n_members, n_steps)");
+    for (int m = 0; m < n_members; ++m) {
+        const int rc = check_hparams(nullptr, hparams + m, "ssg_pop_pack_hparams_steps");
+        if (rc != SSG_OK) return rc;
+    }
+    ssg::pop_pack_steps(n_members, hparams, step0, n_steps, out);
+    return SSG_OK;
+}
+
+int ssg_pop_update_sched(ssg_handle *h, const ssg_population *pop, const ssg_pop_ext *ext, const float *dev_table, int table_steps,
+                         const int32_t *dev_sched, const int32_t *epochs, const int32_t *minibatches, int perm_epochs, int K,
+                         const float *dev_x, const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret,
+                         const int64_t *dev_perm, float *dev_adam_mv, float *dev_stats, void *dev_workspace, size_t workspace_nbytes,
+                         void *stream)
+{
+    const char *what = "ssg_pop_update_sched";
+    const ssg::PpoBatch batch = {dev_x, dev_act, dev_logp, dev_adv, dev_ret};
+    int rc = pop_bound(h);
+    if (rc == SSG_OK) rc = check_population(h, pop, what);
+    if (rc == SSG_OK && ext) rc = check_pop_ext(h, ext, what);
+    if (rc != SSG_OK) return rc;
+    const ssg_policy pol = pop_policy(*pop);
+    const int P = pop->n_members;
+    ssg::PpoMinibatch mb;
+    rc = check_pop_update(h, &pol, P, dev_table, table_steps, K, batch, dev_perm, 0, 0, dev_adam_mv, what, &mb, true);
+    if (rc != SSG_OK) return rc;
+    if (!epochs || !minibatches) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_sched: NULL epochs or minibatches");
+    if (!dev_sched) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_sched: NULL dev_sched");
+    // (re-derived from the host arrays: what the device table was packed from decides the launches, their width and the workspace)
+    PopSchedule sc;
+    sc.dev_sched = dev_sched;
+    sc.perm_epochs = perm_epochs;
+    if (!pop_schedule(P, mb.n_samples, epochs, minibatches, nullptr, nullptr, &sc.n_launches, &sc.Cmax))
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_sched: a member's epochs or minibatches is < 1 (or its steps exceed 2^31-1)");
+    if (perm_epochs < *std::max_element(epochs, epochs + P))
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_sched: perm_epochs < the largest epochs of a member");
+    if ((long long)table_steps < sc.n_launches)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_sched: the table holds fewer Adam steps than the schedule's launches (max epochs * chunks)");
+    const size_t need = need_grad(ssg::kPopSlotsOff, P, pol, sc.Cmax, ext != nullptr);
+    rc = check_workspace(h, dev_workspace, workspace_nbytes, need, what);
+    if (rc == SSG_OK) rc = check_ready(h, false);
+    if (rc == SSG_OK) rc = prepare_ppo(h);
+    if (rc != SSG_OK) return rc;
+    mb.ws = dev_workspace;
+    mb.stats_out = dev_stats;
+    ssg::PpoExtLaunch el;
+    if (ext) el = ext_launch(*ext);
+    return run_update(h, mb, ext ? &el : nullptr, 0, 0, ext && ext->dev_kl_coef != nullptr, 0.0f,
+                      ext ? "population update_sched (ext)" : "population update_sched", static_cast<hipStream_t>(stream), &sc);
 }
 
 int ssg_pop_exploit(ssg_handle *h, const ssg_population *pop, const int32_t *src, float *dev_adam_mv, void *stream)

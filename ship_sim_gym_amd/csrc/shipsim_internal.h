@@ -226,10 +226,17 @@ hipError_t launch_ppo_adam(const ssg_policy &p, const ssg_ppo_hparams &hp, const
 // constants), then per Adam step kPopTableRow floats per member.
 constexpr size_t kPopSlotsOff = 4096;
 constexpr int kPopTableRow = 8;
+// The schedule table of ssg_pop_update_sched (ssg_pop_pack_schedule writes it, the caller uploads it): kPopSchedRow int32 per member —
+// SH_* — then per launch kPopSchedRow int32 per member — SR_*: what differs between the members within launch j, where member m runs
+// ITS minibatch j (chunk j % chunks_m of its permutation row j / chunks_m) or, past its steps_m, nothing.
+constexpr int kPopSchedRow = SSG_POP_SCHED_ROW;
+enum { SH_STEPS = 0, SH_CHUNKS, SH_C, SH_EPOCHS };
+enum { SR_OFF = 0 /* int64: entries [0], [1] */, SR_M = 2, SR_G, SR_FIRST, SR_ACTIVE, SR_INVM /* f32 bits of 1 / (float)M */ };
 static_assert(SSG_POP_MAX_MEMBERS * 16 <= kPopSlotsOff, "the members' advantage statistics fit in front of the slots");
 hipError_t launch_policy_pop(const ssg_policy &p, int members, int n, long long env_base, const double *obs, const float *uniform,
                              uint64_t seed, int64_t step, int32_t *act, float *logp, float *value, float *x, hipStream_t stream);
 void pop_pack(int members, const ssg_ppo_hparams *hp, int64_t step0, int n_steps, float *out); // host only
+void pop_pack_steps(int members, const ssg_ppo_hparams *hp, const int64_t *step0, int n_steps, float *out); // (a starting step per member)
 hipError_t launch_pop_gae(int members, int K, int N, const float *table, const double *rew, const uint8_t *done, const float *val,
                           const float *last_val, float *adv, float *ret, void *ws, hipStream_t stream);
 hipError_t launch_pop_exploit(const ssg_policy &p, int members, const int32_t *src, float *adam_mv, hipStream_t stream);
@@ -288,15 +295,18 @@ struct PpoMinibatch {
     const ssg_ppo_hparams *hp;
     int64_t step;
     const float *table, *adam_row;
+    const int32_t *sched;     // nullable; this launch's schedule records [members][kPopSchedRow]: M is then the LAUNCH's (max C_m, for
+                              // the grid and the slot stride) and idx every member's first permutation row; the records say the rest
     const PpoExtLaunch *ext;  // nullable: the extended loss and reduction
     float *grad_out, *stats_out;
     long long stats_stride;
     float *adam_mv;
 };
 hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream);
-// RLlib's update_kl on every member's coefficient from the last epoch's `chunks` minibatches 
-hipError_t launch_kl_adapt(int members, const PpoExtLaunch &ext, float kl_target, int P, long long chunks, void *ws, size_t slots_off,
-                           hipStream_t stream);
+// RLlib's update_kl on every member's coefficient from the last epoch's `chunks` minibatches (sched_hdr, nullable: the schedule
+// table, whose header row m holds member m's own chunk count)
+hipError_t launch_kl_adapt(int members, const PpoExtLaunch &ext, float kl_target, int P, long long chunks, const int32_t *sched_hdr, void *ws,
+                           size_t slots_off, hipStream_t stream);
 // the acting policy's log-distribution over stored x rows (shipsim_policy.hip): rows t*N + m*n + e, t < K, e < n, under parameter row m
 hipError_t launch_policy_dist(const ssg_policy &p, int members, int n, long long N, int K, const float *x, float *logp_all, hipStream_t stream);
 hipError_t launch_pop_episode_stats(int members, int K, int N, const double *rew, const uint8_t *done, double *carry_ret,

@@ -16,6 +16,8 @@
 // weight gradients in its own slot of the caller's workspace (read-modify-write by the lane that owns the entry, so in tile order),
 // its bias / head gradients and loss sums in registers; a second kernel adds the slots (a fixed tree) and, for an update, applies
 // Adam to the packed parameters in place.  Deterministic for a given M (the grid depends on M only); no floating-point atomics.
+// (A population on per-member schedules, the SCHED instantiations, keeps that: member m's tiles are dealt to ppo_grid(M_m) workgroups
+// of a wider launch, and its reduction adds those ppo_grid(M_m) slots.)
 //
 // Separate value network (SSG_POLICY_SEPARATE_VALUE, the SPLIT instantiations).  The logits' deltas depend on the pi tower alone and the
 // value's on the vf tower alone, so a tile runs the body below once per tower over the same LDS: the sample scalars and the X rows are
@@ -291,8 +293,17 @@ struct ExtGradArgs {
 // EXT = false: the loss of ssg_ppo_grad (ea unused), slots of P + 4 floats.  EXT = true: plus the value clip and the KL penalty,
 // slots of P + kExtStats floats (the loss sums pg, VL, entropy, clip fraction, KL, then zeros).
 // SPLIT = false: the shared body (one pass per tile: pi and vf below are both true, constants).  SPLIT = true: two passes per tile.
-template <bool POP, bool EXT, bool SPLIT> __device__ __forceinline__ void ppo_grad_body(const GradArgs &a_, const PopGradArgs &pa, const ExtGradArgs &ea)
+// SCHED (with POP): the members are on schedules of their own (ssg_pop_update_sched).  The launch is as wide as the longest minibatch
+// in the call needs, grid (ppo_grid(max C_m), members); member m's record of this launch gives ITS minibatch length M_m, its
+// offset into its permutation rows and G_m = ppo_grid(M_m) (0 when it has no minibatch left).  Workgroups blockIdx.x >= G_m leave
+// before the first barrier; the others deal the member's tiles among G_m — exactly the workgroups, tiles and slots of the POP = false
+// launch for M_m alone.  A template flag, not a nullable pointer, and kernels of their own that take the records (sched: this
+// launch's [members][kPopSchedRow], shipsim_internal.h) as one more argument: the other instantiations keep their argument layout and
+// compile from the text they had.
+template <bool POP, bool EXT, bool SPLIT, bool SCHED>
+__device__ __forceinline__ void ppo_grad_body(const GradArgs &a_, const PopGradArgs &pa, const ExtGradArgs &ea, const int32_t *sched)
 {
+    static_assert(POP || !SCHED, "a schedule is a population's");
     extern __shared__ float4 lds4[];
     float *lds = reinterpret_cast<float *>(lds4);
     GradArgs a = a_;
@@ -315,6 +326,15 @@ template <bool POP, bool EXT, bool SPLIT> __device__ __forceinline__ void ppo_gr
         a.clip = row[PT_CLIP];
         a.vf = row[PT_VF];
         a.ent = row[PT_ENT];
+    }
+    unsigned gm = 0; // SCHED: the member's own grid, the workgroups that share its tiles
+    if (SCHED) {
+        const int32_t *rec = sched + (size_t)blockIdx.y * kPopSchedRow;
+        gm = (unsigned)rec[SR_G];
+        if (blockIdx.x >= gm) return; // (uniform over the workgroup, and ahead of every barrier)
+        a.M = rec[SR_M];
+        a.idx += *reinterpret_cast<const long long *>(rec + SR_OFF);
+        a.invM = __int_as_float(rec[SR_INVM]);
     }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int D = a.D, H = a.H, A = a.A, kind = a.kind, NT = H / 16;
@@ -354,7 +374,7 @@ template <bool POP, bool EXT, bool SPLIT> __device__ __forceinline__ void ppo_gr
     float st_pg = 0.0f, st_vl = 0.0f, st_en = 0.0f, st_cf = 0.0f, st_kl = 0.0f;
     const long long ntiles = (a.M + kTile - 1) / kTile;
     bool first = true;
-    for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    for (long long tile = blockIdx.x; tile < ntiles; tile += SCHED ? gm : gridDim.x) {
         // 1. the tile's sample scalars, then its x rows (a row outside [0, n_samples) is a zero, gradient-free sample)
         if (tid < kTile) {
             const long long i = tile * kTile + tid;
@@ -563,13 +583,27 @@ template <bool POP, bool EXT, bool SPLIT> __device__ __forceinline__ void ppo_gr
 
 template <bool POP, bool SPLIT> __global__ void __launch_bounds__(kPpoBlock) ppo_grad_kernel(const GradArgs a, const PopGradArgs pa)
 {
-    ppo_grad_body<POP, false, SPLIT>(a, pa, ExtGradArgs{});
+    ppo_grad_body<POP, false, SPLIT, false>(a, pa, ExtGradArgs{}, nullptr);
 }
 
 template <bool POP, bool SPLIT>
 __global__ void __launch_bounds__(kPpoBlock) ppo_grad_ext_kernel(const GradArgs a, const PopGradArgs pa, const ExtGradArgs ea)
 {
-    ppo_grad_body<POP, true, SPLIT>(a, pa, ea);
+    ppo_grad_body<POP, true, SPLIT, false>(a, pa, ea, nullptr);
+}
+
+// a population on per-member schedules
+template <bool SPLIT>
+__global__ void __launch_bounds__(kPpoBlock) ppo_grad_sched_kernel(const GradArgs a, const PopGradArgs pa, const int32_t *__restrict__ sched)
+{
+    ppo_grad_body<true, false, SPLIT, true>(a, pa, ExtGradArgs{}, sched);
+}
+
+template <bool SPLIT>
+__global__ void __launch_bounds__(kPpoBlock) ppo_grad_ext_sched_kernel(const GradArgs a, const PopGradArgs pa, const ExtGradArgs ea,
+                                                                       const int32_t *__restrict__ sched)
+{
+    ppo_grad_body<true, true, SPLIT, true>(a, pa, ea, sched);
 }
 
 // grad[p] = sum over the slots (a fixed order); entries P..P+3 (when nstats) are the loss sums -> stats = sum / M.  With params: Adam, torch's
@@ -672,18 +706,30 @@ struct ExtReduceArgs {
 // as adam_args rounds them).
 // EXT = false: stats rows of 4 loss means (stride = P + 4, or P for ssg_ppo_adam's G = 1), ea and sq unused.  EXT = true: see
 // ExtReduceArgs; sq is the workgroup's 256 doubles of LDS.
-template <bool POP, bool EXT>
+// SCHED (with POP; sched = this launch's schedule records, else unused): the member's run of slots is the launch's (G of them), of
+// which it sums ITS first G_m = ppo_grid(M_m) and divides by its own (float)M_m; first_chunk is its record's.  A member without a
+// minibatch in this launch does nothing at all: no Adam step, no stats row, no klacc, gvec or part write.
+template <bool POP, bool EXT, bool SCHED>
 __device__ __forceinline__ void ppo_reduce_body(const float *__restrict__ slots, int G, int P, int stride, float fM, float *__restrict__ grad_out,
                                                 float *__restrict__ stats_out, float *__restrict__ params, float *__restrict__ mv,
                                                 const AdamArgs &ad_, long long stats_stride, const float *__restrict__ adam,
-                                                const ExtReduceArgs &ea, double *sq)
+                                                const ExtReduceArgs &ea, double *sq, const int32_t *__restrict__ sched)
 {
+    static_assert(POP || !SCHED, "a schedule is a population's");
     AdamArgs ad = ad_;
     const size_t m = POP ? blockIdx.y : 0;
+    int Gm = G, first_chunk = EXT ? ea.first_chunk : 0;
+    if (SCHED) {
+        const int32_t *rec = sched + m * kPopSchedRow;
+        if (!rec[SR_ACTIVE]) return; // (the whole workgroup: ahead of the barriers below)
+        Gm = rec[SR_G] < G ? rec[SR_G] : G;
+        fM = (float)rec[SR_M];
+        first_chunk = rec[SR_FIRST];
+    }
     if (POP) member_rows(m, P, (size_t)G * (size_t)stride, stats_stride, adam, ad, slots, stats_out, params, mv);
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (!EXT && p >= stride) return; // (EXT: every lane stays for the barriers of the sum of squares)
-    const float s = p < stride ? slot_sum(slots, G, stride, p) : 0.0f;
+    const float s = p < stride ? slot_sum(slots, Gm, stride, p) : 0.0f;
     if (p >= P && p < stride) {
         const int q = p - P;
         const float mean = s / fM;
@@ -692,7 +738,7 @@ __device__ __forceinline__ void ppo_reduce_body(const float *__restrict__ slots,
         } else {
             const float klc = ea.kl_coef ? ea.kl_coef[m] : 0.0f;
             if (stats_out) stats_out[q] = q < 5 ? mean : (q == 6 ? (klc > 0.0f ? klc : 0.0f) : 0.0f);
-            if (q == 4) ea.klacc[m] = ea.first_chunk ? mean : ea.klacc[m] + mean;
+            if (q == 4) ea.klacc[m] = first_chunk ? mean : ea.klacc[m] + mean;
         }
     }
     if (p < P) {
@@ -717,7 +763,8 @@ __global__ void __launch_bounds__(256) ppo_reduce_kernel(const float *__restrict
                                                          float *__restrict__ params, float *__restrict__ mv, const AdamArgs ad,
                                                          long long stats_stride, const float *__restrict__ adam)
 {
-    ppo_reduce_body<POP, false>(slots, G, P, stride, fM, grad_out, stats_out, params, mv, ad, stats_stride, adam, ExtReduceArgs{}, nullptr);
+    ppo_reduce_body<POP, false, false>(slots, G, P, stride, fM, grad_out, stats_out, params, mv, ad, stats_stride, adam, ExtReduceArgs{},
+                                       nullptr, nullptr);
 }
 
 template <bool POP>
@@ -728,21 +775,43 @@ __global__ void __launch_bounds__(256) ppo_reduce_ext_kernel(const float *__rest
                                                              const ExtReduceArgs ea)
 {
     __shared__ double sq[256];
-    ppo_reduce_body<POP, true>(slots, G, P, stride, fM, grad_out, stats_out, params, mv, ad, stats_stride, adam, ea, sq);
+    ppo_reduce_body<POP, true, false>(slots, G, P, stride, fM, grad_out, stats_out, params, mv, ad, stats_stride, adam, ea, sq, nullptr);
+}
+
+// a population on per-member schedules (no fM: every member divides by its record's M)
+__global__ void __launch_bounds__(256) ppo_reduce_sched_kernel(const float *__restrict__ slots, int G, int P, int stride,
+                                                               float *__restrict__ stats_out, float *__restrict__ params,
+                                                               float *__restrict__ mv, long long stats_stride,
+                                                               const float *__restrict__ adam, const int32_t *__restrict__ sched)
+{
+    ppo_reduce_body<true, false, true>(slots, G, P, stride, 0.0f, nullptr, stats_out, params, mv, AdamArgs{}, stats_stride, adam,
+                                       ExtReduceArgs{}, nullptr, sched);
+}
+
+__global__ void __launch_bounds__(256) ppo_reduce_ext_sched_kernel(const float *__restrict__ slots, int G, int P, int stride,
+                                                                   float *__restrict__ stats_out, float *__restrict__ params,
+                                                                   float *__restrict__ mv, long long stats_stride,
+                                                                   const float *__restrict__ adam, const ExtReduceArgs ea,
+                                                                   const int32_t *__restrict__ sched)
+{
+    __shared__ double sq[256];
+    ppo_reduce_body<true, true, true>(slots, G, P, stride, 0.0f, nullptr, stats_out, params, mv, AdamArgs{}, stats_stride, adam, ea, sq, sched);
 }
 
 // The third launch of the clip sequence, grid (ceil(P / 256), members): every workgroup adds the member's nb partial sums of squares
 // in index order (f64), then in f32 norm = (float)sqrt(sum), coef = min(1, max_grad_norm / (norm + 1e-6f)) — torch's
 // clip_grad_norm_ — and Adam on g * coef.  A member with max_grad_norm <= 0 gets coef = 1.0f (exact) and a norm column of 0.
-// params NULL (ssg_ppo_grad_ext): the norm column alone.
-template <bool POP>
-__global__ void __launch_bounds__(256) ppo_clip_kernel(const float *__restrict__ gvec, const double *__restrict__ part, int nb, int P,
-                                                       float max_grad_norm, const float *__restrict__ pop_ext,
-                                                       float *__restrict__ stats_out, long long stats_stride, float *__restrict__ params,
-                                                       float *__restrict__ mv, const AdamArgs ad_, const float *__restrict__ adam)
+// params NULL (ssg_ppo_grad_ext): the norm column alone.  SCHED: a member without a minibatch in this launch (its record) is skipped.
+template <bool POP, bool SCHED>
+__device__ __forceinline__ void ppo_clip_body(const float *__restrict__ gvec, const double *__restrict__ part, int nb, int P,
+                                              float max_grad_norm, const float *__restrict__ pop_ext, float *__restrict__ stats_out,
+                                              long long stats_stride, float *__restrict__ params, float *__restrict__ mv,
+                                              const AdamArgs &ad_, const float *__restrict__ adam, const int32_t *__restrict__ sched)
 {
+    static_assert(POP || !SCHED, "a schedule is a population's");
     AdamArgs ad = ad_;
     const size_t m = POP ? blockIdx.y : 0;
+    if (SCHED && !sched[m * kPopSchedRow + SR_ACTIVE]) return;
     if (POP) {
         member_rows(m, P, (size_t)P, stats_stride, adam, ad, gvec, stats_out, params, mv);
         max_grad_norm = pop_ext[m * kPopExtRow + 1];
@@ -757,13 +826,33 @@ __global__ void __launch_bounds__(256) ppo_clip_kernel(const float *__restrict__
     if (p < P && params) adam_apply(ad, gvec[p] * coef, p, P, params, mv);
 }
 
+template <bool POP>
+__global__ void __launch_bounds__(256) ppo_clip_kernel(const float *__restrict__ gvec, const double *__restrict__ part, int nb, int P,
+                                                       float max_grad_norm, const float *__restrict__ pop_ext,
+                                                       float *__restrict__ stats_out, long long stats_stride, float *__restrict__ params,
+                                                       float *__restrict__ mv, const AdamArgs ad, const float *__restrict__ adam)
+{
+    ppo_clip_body<POP, false>(gvec, part, nb, P, max_grad_norm, pop_ext, stats_out, stats_stride, params, mv, ad, adam, nullptr);
+}
+
+__global__ void __launch_bounds__(256) ppo_clip_sched_kernel(const float *__restrict__ gvec, const double *__restrict__ part, int nb, int P,
+                                                             const float *__restrict__ pop_ext, float *__restrict__ stats_out,
+                                                             long long stats_stride, float *__restrict__ params, float *__restrict__ mv,
+                                                             const float *__restrict__ adam, const int32_t *__restrict__ sched)
+{
+    ppo_clip_body<true, true>(gvec, part, nb, P, 0.0f, pop_ext, stats_out, stats_stride, params, mv, AdamArgs{}, adam, sched);
+}
+
 // The last launch of an extended update with a KL target, one workgroup, lane m = member m: RLlib's update_kl on the f32 mean of the
-// last epoch's minibatch means of KL.  A member whose target is <= 0 keeps its coefficient.
+// last epoch's minibatch means of KL.  A member whose target is <= 0 keeps its coefficient.  sched_hdr (nullable): the schedule table's
+// header rows — member m's last epoch had ITS chunks_m minibatches (and klacc[m] is that epoch's sum: an idle member never touches it).
 __global__ void __launch_bounds__(256) ppo_kl_adapt_kernel(int members, float *__restrict__ kl_coef, const float *__restrict__ klacc,
-                                                           float chunks, float kl_target, const float *__restrict__ pop_ext)
+                                                           float chunks, float kl_target, const float *__restrict__ pop_ext,
+                                                           const int32_t *__restrict__ sched_hdr)
 {
     const int m = threadIdx.x;
     if (m >= members) return;
+    if (sched_hdr) chunks = (float)sched_hdr[(size_t)m * kPopSchedRow + SH_CHUNKS];
     const float target = pop_ext ? pop_ext[(size_t)m * kPopExtRow + 2] : kl_target;
     if (!(target > 0.0f)) return;
     const float mean = klacc[m] / chunks;
@@ -885,7 +974,8 @@ size_t ppo_grad_lds_bytes(const ssg_policy &p)
 // (the extended instantiations add v_old, four logp_old and the fifth loss sum per sample of the tile: 1.5 KB)
 size_t ppo_grad_ext_lds_bytes(const ssg_policy &p) { return ppo_grad_lds_bytes(p) + 6 * kTile * sizeof(float); }
 
-// the gradient kernel's instantiation for a population or not, the extended loss or not, separate towers or not
+// the gradient kernel's instantiation for a population or not (and then on per-member schedules or not), the extended loss or not,
+// separate towers or not
 typedef void (*GradKernel)(const GradArgs, const PopGradArgs);
 typedef void (*GradExtKernel)(const GradArgs, const PopGradArgs, const ExtGradArgs);
 static GradKernel grad_plain(bool pop, bool split)
@@ -898,16 +988,22 @@ static GradExtKernel grad_ext(bool pop, bool split)
     if (split) return pop ? ppo_grad_ext_kernel<true, true> : ppo_grad_ext_kernel<false, true>;
     return pop ? ppo_grad_ext_kernel<true, false> : ppo_grad_ext_kernel<false, false>;
 }
-static const void *grad_kernel(bool pop, bool ext, bool split)
+typedef void (*GradSchedKernel)(const GradArgs, const PopGradArgs, const int32_t *);
+typedef void (*GradExtSchedKernel)(const GradArgs, const PopGradArgs, const ExtGradArgs, const int32_t *);
+static GradSchedKernel grad_plain_sched(bool split) { return split ? ppo_grad_sched_kernel<true> : ppo_grad_sched_kernel<false>; }
+static GradExtSchedKernel grad_ext_sched(bool split) { return split ? ppo_grad_ext_sched_kernel<true> : ppo_grad_ext_sched_kernel<false>; }
+static const void *grad_kernel(bool pop, bool ext, bool split, bool sched = false)
 {
+    if (sched) return ext ? reinterpret_cast<const void *>(grad_ext_sched(split)) : reinterpret_cast<const void *>(grad_plain_sched(split));
     return ext ? reinterpret_cast<const void *>(grad_ext(pop, split)) : reinterpret_cast<const void *>(grad_plain(pop, split));
 }
 
 hipError_t prepare_ppo()
 {
-    const void *kernels[8] = {grad_kernel(false, false, false), grad_kernel(true, false, false), grad_kernel(false, true, false),
-                              grad_kernel(true, true, false),   grad_kernel(false, false, true), grad_kernel(true, false, true),
-                              grad_kernel(false, true, true),   grad_kernel(true, true, true)};
+    const void *kernels[12] = {grad_kernel(false, false, false),      grad_kernel(true, false, false),      grad_kernel(false, true, false),
+                               grad_kernel(true, true, false),        grad_kernel(false, false, true),      grad_kernel(true, false, true),
+                               grad_kernel(false, true, true),        grad_kernel(true, true, true),        grad_kernel(true, false, false, true),
+                               grad_kernel(true, true, false, true),  grad_kernel(true, false, true, true), grad_kernel(true, true, true, true)};
     for (const void *k : kernels) {
         hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
@@ -934,6 +1030,8 @@ hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream)
 {
     const ssg_policy &p = *mb.policy;
     const bool pop = mb.table != nullptr; // a population reads its constants from the table: the POP instantiations
+    const bool sched = mb.sched != nullptr; // ... and its members' minibatches from the schedule records: the SCHED ones (G: the launch's)
+    if (sched && !pop) return hipErrorInvalidValue;
     const bool split = (p.activation & SSG_POLICY_SEPARATE_VALUE) != 0;
     const PpoExtLaunch *ext = mb.ext;
     const int P = ppo_packed_len(p), G = ppo_grid(mb.M), stride = P + (ext ? kExtStats : 4);
@@ -974,9 +1072,14 @@ hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream)
     const AdamArgs ad = mb.adam_mv && !pop ? adam_args(*mb.hp, mb.step) : AdamArgs{};
     const dim3 ggrid((unsigned)G, (unsigned)mb.members), rgrid((unsigned)((stride + 255) / 256), (unsigned)mb.members);
     if (!ext) {
-        hipLaunchKernelGGL(grad_plain(pop, split), ggrid, dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a, pa);
-        hipLaunchKernelGGL(pop ? ppo_reduce_kernel<true> : ppo_reduce_kernel<false>, rgrid, dim3(256), 0, stream, (const float *)a.slots, G, P,
-                           stride, (float)mb.M, mb.grad_out, mb.stats_out, params, mb.adam_mv, ad, mb.stats_stride, mb.adam_row);
+        if (sched) hipLaunchKernelGGL(grad_plain_sched(split), ggrid, dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a, pa, mb.sched);
+        else hipLaunchKernelGGL(grad_plain(pop, split), ggrid, dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a, pa);
+        if (sched)
+            hipLaunchKernelGGL(ppo_reduce_sched_kernel, rgrid, dim3(256), 0, stream, (const float *)a.slots, G, P, stride, mb.stats_out, params,
+                               mb.adam_mv, mb.stats_stride, mb.adam_row, mb.sched);
+        else
+            hipLaunchKernelGGL(pop ? ppo_reduce_kernel<true> : ppo_reduce_kernel<false>, rgrid, dim3(256), 0, stream, (const float *)a.slots, G,
+                               P, stride, (float)mb.M, mb.grad_out, mb.stats_out, params, mb.adam_mv, ad, mb.stats_stride, mb.adam_row);
         return hipGetLastError();
     }
     ExtGradArgs ea;
@@ -985,7 +1088,8 @@ hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream)
     ea.kl_coef = ext->kl_coef;
     ea.pop_ext = ext->pop_ext;
     ea.vf_clip = ext->vf_clip;
-    hipLaunchKernelGGL(grad_ext(pop, split), ggrid, dim3(kPpoBlock), ppo_grad_ext_lds_bytes(p), stream,
+    if (sched) hipLaunchKernelGGL(grad_ext_sched(split), ggrid, dim3(kPpoBlock), ppo_grad_ext_lds_bytes(p), stream, a, pa, ea, mb.sched);
+    else hipLaunchKernelGGL(grad_ext(pop, split), ggrid, dim3(kPpoBlock), ppo_grad_ext_lds_bytes(p), stream,
                        a, pa, ea);
     ExtReduceArgs er;
     er.kl_coef = ext->kl_coef;
@@ -993,21 +1097,30 @@ hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream)
     er.first_chunk = ext->first_chunk ? 1 : 0;
     er.gvec = ext->clip_seq ? reinterpret_cast<float *>(base + lay.gvec) : nullptr;
     er.part = reinterpret_cast<double *>(base + lay.part);
+    const dim3 cgrid((unsigned)((P + 255) / 256), (unsigned)mb.members);
+    if (sched) {
+        hipLaunchKernelGGL(ppo_reduce_ext_sched_kernel, rgrid, dim3(256), 0, stream, (const float *)a.slots, G, P, stride, mb.stats_out, params,
+                           mb.adam_mv, mb.stats_stride, mb.adam_row, er, mb.sched);
+        if (ext->clip_seq)
+            hipLaunchKernelGGL(ppo_clip_sched_kernel, cgrid, dim3(256), 0, stream, (const float *)er.gvec, (const double *)er.part, lay.nb, P,
+                               ext->pop_ext, mb.stats_out, mb.stats_stride, params, mb.adam_mv, mb.adam_row, mb.sched);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(pop ? ppo_reduce_ext_kernel<true> : ppo_reduce_ext_kernel<false>, rgrid, dim3(256), 0, stream, (const float *)a.slots,
                        G, P, stride, (float)mb.M, mb.grad_out, mb.stats_out, params, mb.adam_mv, ad, mb.stats_stride, mb.adam_row, er);
     if (ext->clip_seq)
-        hipLaunchKernelGGL(pop ? ppo_clip_kernel<true> : ppo_clip_kernel<false>, dim3((unsigned)((P + 255) / 256), (unsigned)mb.members),
+        hipLaunchKernelGGL(pop ? ppo_clip_kernel<true> : ppo_clip_kernel<false>, cgrid,
                            dim3(256), 0, stream, (const float *)er.gvec, (const double *)er.part, lay.nb, P, ext->max_grad_norm, ext->pop_ext,
                            mb.stats_out, mb.stats_stride, params, mb.adam_mv, ad, mb.adam_row);
     return hipGetLastError();
 }
 
-hipError_t launch_kl_adapt(int members, const PpoExtLaunch &ext, float kl_target, int P, long long chunks, void *ws, size_t slots_off,
-                           hipStream_t stream)
+hipError_t launch_kl_adapt(int members, const PpoExtLaunch &ext, float kl_target, int P, long long chunks, const int32_t *sched_hdr, void *ws,
+                           size_t slots_off, hipStream_t stream)
 {
     const PpoExtLayout lay = ppo_ext_layout(slots_off, members, 1, P);
     hipLaunchKernelGGL(ppo_kl_adapt_kernel, dim3(1), dim3(256), 0, stream, members, ext.kl_coef,
-                       (const float *)(static_cast<char *>(ws) + lay.klacc), (float)chunks, kl_target, ext.pop_ext);
+                       (const float *)(static_cast<char *>(ws) + lay.klacc), (float)chunks, kl_target, ext.pop_ext, sched_hdr);
     return hipGetLastError();
 }
 
@@ -1028,6 +1141,14 @@ void pop_pack(int members, const ssg_ppo_hparams *hp, int64_t step0, int n_steps
     for (int m = 0; m < members; ++m) loss_row(hp[m], out + (size_t)m * kPopTableRow);
     for (int j = 0; j < n_steps; ++j)
         for (int m = 0; m < members; ++m) adam_to_row(adam_args(hp[m], step0 + 1 + j), out + ((size_t)(1 + j) * members + m) * kPopTableRow);
+}
+
+// the same table for members that have taken different numbers of Adam steps: row (j, m) is Adam step step0[m] + 1 + j of member m
+void pop_pack_steps(int members, const ssg_ppo_hparams *hp, const int64_t *step0, int n_steps, float *out)
+{
+    for (int m = 0; m < members; ++m) loss_row(hp[m], out + (size_t)m * kPopTableRow);
+    for (int j = 0; j < n_steps; ++j)
+        for (int m = 0; m < members; ++m) adam_to_row(adam_args(hp[m], step0[m] + 1 + j), out + ((size_t)(1 + j) * members + m) * kPopTableRow);
 }
 
 hipError_t launch_pop_gae(int members, int K, int N, const float *table, const double *rew, const uint8_t *done, const float *val,

@@ -8,8 +8,9 @@ launch per rollout step, two launches for GAE, two per minibatch of the update â
 
 The handle's envs are split into P equal contiguous slices: member m owns envs [m*n, (m+1)*n), n = num_envs / P.  ``params`` is f32
 [P, L]; row m is a packed buffer of its own, and ``member(m)`` is a ``NativePolicy`` that shares it.  Hyper-parameters are per member
-(plain Python lists on ``PopulationPPO`` that a scheduler may rewrite between updates); epochs, minibatches and the batch size are common
-to the population (they shape the launches), and a population lives on one handle with one architecture.  The extended loss terms of
+(plain Python lists on ``PopulationPPO`` that a scheduler may rewrite between updates), and so may the epochs and the minibatch count
+of an update be (``update`` with lists: ssg_pop_update_sched â€” launch j then serves minibatch j of every member that still has one);
+the batch size is common to the population, which lives on one handle with one architecture.  The extended loss terms of
 ``NativePPO`` â€” ``vf_clip``, ``max_grad_norm``, ``kl_coef``, ``kl_target`` â€” are per member as well (``EXT_KEYS``); a member whose value
 is 0 has that term off and trains exactly as ``NativePPO`` without it.
 
@@ -151,11 +152,15 @@ class PopulationPPO(object):
         self.n_members, self.n_params, self.envs_per_member = P, population.n_params, env.num_envs // P
         dev = population.device
         self.adam_mv = torch.zeros((P, 2 * self.n_params), dtype=torch.float32, device=dev)  # per member: m, then v
-        self.step = 0  # Adam steps taken (common to the population: every update steps every member)
+        self.step = 0  # Adam steps taken (common to the population while every update steps every member alike)
+        # Adam steps taken per member.  They differ once an update ran on per-member schedules; while they are all equal, `step` is
+        # the count that is used (and may be set by the caller), and member_steps follows it.
+        self.member_steps = [0] * P
         self.workspace = torch.zeros(0, dtype=torch.uint8, device=dev)
         self.carry_return = torch.zeros(env.num_envs, dtype=torch.float64, device=dev)
         self.carry_length = torch.zeros(env.num_envs, dtype=torch.int32, device=dev)
         self.kl_coef = torch.tensor(self.kl_coef, dtype=torch.float32).to(dev)  # (the list set above becomes the device tensor)
+        self._last_samples = 0  # K * envs_per_member of the last batch gae() or update() saw (minibatches_for_size's default)
 
     # ------------------------------------------------------------------------------------------------
     def hparams(self):
@@ -167,15 +172,54 @@ class PopulationPPO(object):
                 setattr(arr[m], k, float(getattr(self, k)[m]))
         return arr
 
-    def _table(self, n_steps):
+    def diverged(self):
+        """True once the members have taken different numbers of Adam steps (an update on unequal schedules, or an exploit after one)."""
+        return len(set(self.member_steps)) > 1
+
+    def _steps0(self):
+        """The Adam steps every member has taken so far: ``step`` for all while they agree, else ``member_steps``."""
+        return list(self.member_steps) if self.diverged() else [int(self.step)] * self.n_members
+
+    def _advance(self, steps0, taken):
+        self.member_steps = [s + int(t) for s, t in zip(steps0, taken)]
+        self.step = max(self.member_steps)
+
+    def _table(self, n_steps, steps0=None):
         """The members' f32 constants for GAE, the loss and Adam steps self.step + 1 .. + n_steps, derived by the library on the host
-        in double (ssg_pop_pack_hparams) and uploaded: a fresh device tensor per call, so the lists may change right after."""
+        in double (ssg_pop_pack_hparams) and uploaded: a fresh device tensor per call, so the lists may change right after.  steps0: a
+        starting step per member (ssg_pop_pack_hparams_steps)."""
         torch = _torch()
         n = N.pop_table_floats(self.n_members, n_steps)
         buf = (C.c_float * n)()
-        N.check(N.lib().ssg_pop_pack_hparams(self.n_members, self.hparams(), int(self.step), int(n_steps), buf, n), None,
-                "ssg_pop_pack_hparams")
+        if steps0 is None:
+            N.check(N.lib().ssg_pop_pack_hparams(self.n_members, self.hparams(), int(self.step), int(n_steps), buf, n), None,
+                    "ssg_pop_pack_hparams")
+        else:
+            arr = (C.c_int64 * self.n_members)(*[int(x) for x in steps0])
+            N.check(N.lib().ssg_pop_pack_hparams_steps(self.n_members, self.hparams(), arr, int(n_steps), buf, n), None,
+                    "ssg_pop_pack_hparams_steps")
         return torch.tensor(list(buf), dtype=torch.float32).to(self.population.device)
+
+    def minibatches_for_size(self, size, samples=None):
+        """The minibatch count that makes minibatches of at most `size` samples out of a member's `samples` (default: the last
+        batch's K * envs_per_member): ceil(samples / size), clamped to [1, samples].  The chunk lengths stay torch.chunk's â€” every
+        chunk ceil(samples / count) long and the last one shorter, so chunks of AT MOST `size` â€” not RLlib's slicing of exactly
+        sgd_minibatch_size samples with a shorter remainder."""
+        n = int(self._last_samples if samples is None else samples)
+        if n < 1:
+            raise ValueError("PopulationPPO.minibatches_for_size: no batch seen yet; pass samples=")
+        return max(1, min(n, -(-n // max(1, int(size)))))
+
+    def pack_schedule(self, samples, epochs, minibatches):
+        """(int32 host table as a ctypes array, steps per member, launches) of ssg_pop_pack_schedule."""
+        P = self.n_members
+        ep, mb = (C.c_int32 * P)(*[int(e) for e in epochs]), (C.c_int32 * P)(*[int(b) for b in minibatches])
+        steps, launches = (C.c_int32 * P)(), C.c_int32()
+        N.check(N.lib().ssg_pop_pack_schedule(P, int(samples), ep, mb, None, 0, steps, C.byref(launches)), None, "ssg_pop_pack_schedule")
+        n = N.pop_sched_ints(P, launches.value)
+        buf = (C.c_int32 * n)()
+        N.check(N.lib().ssg_pop_pack_schedule(P, int(samples), ep, mb, buf, n, steps, C.byref(launches)), None, "ssg_pop_pack_schedule")
+        return buf, list(steps), int(launches.value)
 
     def _ws(self, samples_per_member, max_minibatch):
         """The workspace, grown to serve the sizes (its head â€” the members' advantage statistics â€” is kept when it grows)."""
@@ -218,11 +262,12 @@ class PopulationPPO(object):
         p = [self._flat(batch, "rew", torch.float64, (K, n_env)), self._flat(batch, "done", torch.uint8, (K, n_env)),
              self._flat(batch, "val", torch.float32, (K, n_env)), self._flat(batch, "last_val", torch.float32, (n_env,))]
         self._ws(K * self.envs_per_member, 1)
+        self._last_samples = K * self.envs_per_member
         adv = torch.empty((K, n_env), dtype=torch.float32, device=dev)
         ret = torch.empty_like(adv)
         pop, h = self.population.to_native(), self.env._h
         with torch.cuda.device(dev):
-            table = self._table(0)
+            table = self._table(0)  # (no Adam rows: the step counts do not enter)
             N.check(N.lib().ssg_pop_gae(h, C.byref(pop), C.c_void_p(table.data_ptr()), K, *p, C.c_void_p(adv.data_ptr()),
                                         C.c_void_p(ret.data_ptr()), C.c_void_p(self.workspace.data_ptr()), self.workspace.numel(),
                                         self._stream()), h, "ssg_pop_gae")
@@ -276,11 +321,20 @@ class PopulationPPO(object):
         """epochs x chunks of {gradient, Adam} for every member from ONE library call.  perm: int64 [P, epochs, K*n] â€” member m's
         minibatches are perm[m, e].chunk(minibatches), indices into ITS samples (i = t*n + e).  stats=True returns f32
         [P, epochs * chunks, 4] (the minibatch means of the pg loss, (v - ret)^2, the entropy and the clip fraction); with an extended
-        term on for some member, 8 columns (NativePPO.grad's) and, at the end, the adaptation of ``kl_coef`` where kl_target > 0."""
+        term on for some member, 8 columns (NativePPO.grad's) and, at the end, the adaptation of ``kl_coef`` where kl_target > 0.
+
+        epochs and / or minibatches may be lists of P ints: member m then runs epochs[m] epochs of its own chunking into minibatches[m]
+        (``minibatches_for_size`` turns a minibatch size into a count), still from ONE library call (ssg_pop_update_sched) whose launch
+        j serves minibatch j of every member that has one left.  perm is then int64 [P, max(epochs), K*n] (member m reads its first
+        epochs[m] rows), the stats f32 [P, n_launches, cols], zero in a member's rows past its own steps, and each member advances
+        ``member_steps`` by its own steps.  Either way member m's results are bitwise NativePPO.update's on its shard."""
         torch = _torch()
         K, n_env = self._KN(batch)
         P, dev, D = self.n_members, self.population.device, self.population.obs_dim
         n = K * self.envs_per_member
+        self._last_samples = n
+        if isinstance(epochs, (list, tuple)) or isinstance(minibatches, (list, tuple)):
+            return self._update_sched(batch, perm, epochs, minibatches, stats, K, n_env, n)
         p = [self._flat(batch, "obs", torch.float32, (K, n_env, D)), self._flat(batch, "act", torch.int32, (K, n_env)),
              self._flat(batch, "logp", torch.float32, (K, n_env)), self._flat(batch, "adv", torch.float32, (K, n_env)),
              self._flat(batch, "ret", torch.float32, (K, n_env))]
@@ -293,8 +347,9 @@ class PopulationPPO(object):
         extended = self.extended()
         st = torch.empty((P, steps, N.PPO_EXT_STATS if extended else 4), dtype=torch.float32, device=dev) if stats else None
         pop, h = self.population.to_native(), self.env._h
+        steps0 = self._steps0()
         with torch.cuda.device(dev):
-            table = self._table(steps)
+            table = self._table(steps, steps0 if self.diverged() else None)
             if extended:
                 ext, ext_table = self._ext(batch, K, n_env)
                 N.check(N.lib().ssg_pop_update_ext(h, C.byref(pop), C.byref(ext), C.c_void_p(table.data_ptr()), steps, K, *p,
@@ -302,20 +357,59 @@ class PopulationPPO(object):
                                                    C.c_void_p(self.adam_mv.data_ptr()), C.c_void_p(st.data_ptr()) if stats else None,
                                                    C.c_void_p(self.workspace.data_ptr()), self.workspace.numel(), self._stream()), h,
                         "ssg_pop_update_ext")
-                self.step += steps
+                self._advance(steps0, [steps] * P)
                 return st
             N.check(N.lib().ssg_pop_update(h, C.byref(pop), C.c_void_p(table.data_ptr()), steps, K, *p, C.c_void_p(perm.data_ptr()),
                                            int(epochs), int(minibatches), C.c_void_p(self.adam_mv.data_ptr()),
                                            C.c_void_p(st.data_ptr()) if stats else None, C.c_void_p(self.workspace.data_ptr()),
                                            self.workspace.numel(), self._stream()), h, "ssg_pop_update")
-        self.step += steps
+        self._advance(steps0, [steps] * P)
+        return st
+
+    def _update_sched(self, batch, perm, epochs, minibatches, stats, K, n_env, n):
+        """update() on per-member schedules (ssg_pop_update_sched)."""
+        torch = _torch()
+        P, dev, D = self.n_members, self.population.device, self.population.obs_dim
+        epochs = [int(e) for e in epochs] if isinstance(epochs, (list, tuple)) else [int(epochs)] * P
+        minibatches = [int(b) for b in minibatches] if isinstance(minibatches, (list, tuple)) else [int(minibatches)] * P
+        if len(epochs) != P or len(minibatches) != P:
+            raise ValueError("PopulationPPO.update: %d epochs and %d minibatches for %d members" % (len(epochs), len(minibatches), P))
+        if min(epochs) < 1 or min(minibatches) < 1:
+            raise ValueError("PopulationPPO.update: every member's epochs and minibatches must be >= 1")
+        p = [self._flat(batch, "obs", torch.float32, (K, n_env, D)), self._flat(batch, "act", torch.int32, (K, n_env)),
+             self._flat(batch, "logp", torch.float32, (K, n_env)), self._flat(batch, "adv", torch.float32, (K, n_env)),
+             self._flat(batch, "ret", torch.float32, (K, n_env))]
+        perm = perm.to(device=dev, dtype=torch.int64).contiguous()
+        if tuple(perm.shape) != (P, max(epochs), n):
+            raise ValueError("PopulationPPO.update: perm must be int64 [%d, %d, %d] = [P, max(epochs), K*n] (got %s)"
+                             % (P, max(epochs), n, tuple(perm.shape)))
+        sched, steps, launches = self.pack_schedule(n, epochs, minibatches)
+        self._ws(n, max(chunk_split(n, b)[0] for b in minibatches))
+        extended = self.extended()
+        st = torch.zeros((P, launches, N.PPO_EXT_STATS if extended else 4), dtype=torch.float32, device=dev) if stats else None
+        ep, mb = (C.c_int32 * P)(*epochs), (C.c_int32 * P)(*minibatches)
+        steps0 = self._steps0()
+        pop, h = self.population.to_native(), self.env._h
+        with torch.cuda.device(dev):
+            table = self._table(launches, steps0)
+            dev_sched = torch.frombuffer(sched, dtype=torch.int32).to(dev)  # (a copy: the host array is free after the call)
+            ext = ext_table = None
+            if extended:
+                ext, ext_table = self._ext(batch, K, n_env)
+            N.check(N.lib().ssg_pop_update_sched(h, C.byref(pop), C.byref(ext) if extended else None, C.c_void_p(table.data_ptr()),
+                                                 launches, C.c_void_p(dev_sched.data_ptr()), ep, mb, max(epochs), K, *p,
+                                                 C.c_void_p(perm.data_ptr()), C.c_void_p(self.adam_mv.data_ptr()),
+                                                 C.c_void_p(st.data_ptr()) if stats else None, C.c_void_p(self.workspace.data_ptr()),
+                                                 self.workspace.numel(), self._stream()), h, "ssg_pop_update_sched")
+        self._advance(steps0, steps)
         return st
 
     def exploit(self, src):
         """PBT's exploit on the device: member m takes the parameters and Adam moments of member src[m] (src[m] == m keeps).  A source
         must not itself be a destination.  The source's ``kl_coef`` travels with its parameters: the coefficient was adapted to THOSE
         parameters (to how far their updates move the distribution), so it belongs to the weights, not to the scheduler's
-        hyper-parameters.  Those are the scheduler's business (PBTScheduler returns the new lists)."""
+        hyper-parameters.  Those are the scheduler's business (PBTScheduler returns the new lists).  So does the source's Adam step
+        count (``member_steps``): the bias correction belongs to the moments that are copied."""
         torch = _torch()
         src = [int(s) for s in src]
         if len(src) != self.n_members:
@@ -326,6 +420,8 @@ class PopulationPPO(object):
             N.check(N.lib().ssg_pop_exploit(h, C.byref(pop), arr, C.c_void_p(self.adam_mv.data_ptr()), self._stream()), h,
                     "ssg_pop_exploit")
             self.kl_coef.copy_(self.kl_coef[torch.tensor(src, device=self.population.device)])
+        steps0 = self._steps0()
+        self._advance([steps0[s] for s in src], [0] * self.n_members)
 
     def reset_episode_carry(self):
         """Forget the running episodes (call after an env reset)."""
@@ -354,15 +450,20 @@ class PopulationPPO(object):
 LR_CHOICES = [1e-3, 5e-4, 1e-4, 5e-5, 1e-5]
 
 
-def reference_mutations():
-    """The three of the reference's six mutated hyper-parameters (train/rllib/pbt.py:34-41) that can vary per member here: a callable
-    draws a fresh value from the generator it is handed; a list is a set of choices.  (num_sgd_iter, sgd_minibatch_size and
-    train_batch_size shape the launches and stay common to the population.)"""
-    return {
+def reference_mutations(schedule=False):
+    """The reference's mutated hyper-parameters (train/rllib/pbt.py:34-41) that can vary per member here: a callable draws a fresh
+    value from the generator it is handed; a list is a set of choices.  By default the three that leave the launches alone;
+    schedule=True appends the two that set a member's update schedule, num_sgd_iter and sgd_minibatch_size (pbt.py:40-41), which
+    ``PopulationPPO.update`` takes per member.  (train_batch_size, the sixth, stays common to the population.)"""
+    out = {
         "lambda": lambda rng: rng.uniform(0.9, 1.0),
         "clip_param": lambda rng: rng.uniform(0.01, 0.5),
         "lr": list(LR_CHOICES),
     }
+    if schedule:
+        out["num_sgd_iter"] = lambda rng: rng.randint(1, 30)
+        out["sgd_minibatch_size"] = lambda rng: rng.randint(128, 16384)
+    return out
 
 
 class PBTScheduler(object):
@@ -373,7 +474,10 @@ class PBTScheduler(object):
     top quantile as its source and takes that member's hyper-parameters, then explores: for each mutated key, with probability
     `resample_probability` the value is redrawn from the key's generator / list; otherwise a continuous value is multiplied by 1.2 or
     0.8 and a list-valued one steps to the neighbouring entry (staying at an end of the list, as ray clamps it; a value that is not in
-    the list is redrawn).  As in ray, a perturbed continuous value is not clamped to the generator's range.
+    the list is redrawn).  As in ray, a perturbed continuous value is not clamped to the generator's range.  An int stays an int:
+    the perturbed value is int(old * 1.2) or int(old * 0.8), truncated â€” what ray 0.6's explore() does for int-valued entries as far as
+    its source is remembered (ray is not installed alongside this project, so that was not checked against it); a resample returns
+    whatever the generator returns.
     """
 
     def __init__(self, n_members, seed=0, perturbation_interval=1, quantile_fraction=0.25, resample_probability=0.33, mutations=None):
@@ -417,9 +521,9 @@ class PBTScheduler(object):
                 if self.rng.random() < self.resample_probability:
                     new[key], kind = dist(self.rng), "resample"
                 elif self.rng.random() > 0.5:
-                    new[key], kind = old * 1.2, "perturb"
+                    new[key], kind = int(old * 1.2) if isinstance(old, int) else old * 1.2, "perturb"
                 else:
-                    new[key], kind = old * 0.8, "perturb"
+                    new[key], kind = int(old * 0.8) if isinstance(old, int) else old * 0.8, "perturb"
             log.append((key, kind, old, new[key]))
         return new, log
 

@@ -13,10 +13,18 @@ K = 32 rollout steps, 2 epochs x 4 minibatches — on one handle of members * en
     milliseconds per update of the whole population.  Both start every repeat from the same parameters and zero moments and use the
     same pre-drawn permutations (drawing them is not timed).
 
+With ``--sched`` (per-member schedules, ssg_pop_update_sched), instead, per configuration:
+
+(c) a UNIFORM schedule (2 epochs x 4 minibatches for everyone) through the per-member entry (lists) against the common entry
+    (``ssg_pop_update``, the code path that existed before per-member schedules: the yardstick), update only, alternating in the same
+    run; ``uniform_spread`` is (max - min) / median over the common entry's repeats.
+(d) a SKEWED schedule — epochs 1..4 cycling over the members, minibatches cycling over 1, 4, 16 — through the per-member entry
+    against a loop of the members' ``NativePPO.update`` with the same schedules.
+
 Each figure: 2 warm-up runs, then the median of ``--repeats`` (5) runs, alternating the two paths, each bracketed by a synchronize and
 timed with HIP events.  One JSON line on stdout.
 
-    python tools/population_timing.py [--configs 16x4096,120x512] [--horizon 32] [--repeats 5]
+    python tools/population_timing.py [--configs 16x4096,120x512] [--horizon 32] [--repeats 5] [--sched]
 """
 import argparse
 import importlib.util
@@ -140,13 +148,96 @@ def measure(mod, members, n, horizon, repeats, dev, epochs=2, minibatches=4):
     return out
 
 
+def measure_sched(mod, members, n, horizon, repeats, dev, epochs=2, minibatches=4):
+    from ship_sim_gym_amd.population import NativePopulation, PopulationPPO
+    from ship_sim_gym_amd.ppo import NativePPO
+    torch.manual_seed(0)
+    P, N = members, members * n
+    env = mod.ShipVecEnv(N, mod.GameConfig, mod.EnvConfig, device=dev, n_maps=64)
+    D, A = env.states_history, env.action_space.n
+    scale = torch.full((D,), float(max(env.bounds)), dtype=torch.float64, device=dev)
+    nets = [mod.ActorCritic(D, A).to(dev) for _ in range(P)]
+    pop = NativePopulation.from_actor_critics(nets, scale)
+    seq = NativePopulation.from_actor_critics(nets, scale)
+    p0 = pop.params.clone()
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    U = torch.rand((horizon, N), generator=gen, device=dev)
+    env.reset_tensor()
+    b = dict(env.rollout_population(pop, horizon, uniforms=U))
+    samples = horizon * n
+    sk_epochs = [1 + m % 4 for m in range(P)]
+    sk_mbs = [(1, 4, 16)[m % 3] for m in range(P)]
+    perm = torch.rand((P, max(sk_epochs), samples), generator=gen, device=dev).argsort(dim=-1)
+    perm_u = perm[:, :epochs].contiguous()
+    ppo = PopulationPPO(pop, env)
+    ppo.gae(b)
+    slices = [{k: (v[:, m * n:(m + 1) * n] if k != "last_val" else v[m * n:(m + 1) * n]).contiguous() for k, v in b.items()}
+              for m in range(P)]
+    seq_ppos = [NativePPO(seq.member(m), env) for m in range(P)]
+    for m in range(P):
+        seq_ppos[m].gae(slices[m])
+    perm_m = [perm[m, :sk_epochs[m]].contiguous() for m in range(P)]
+    finals = {}
+
+    def restore(k):
+        if k == "seq":
+            seq.params.copy_(p0)
+            for q in seq_ppos:
+                q.adam_mv.zero_()
+                q.step = 0
+        else:
+            pop.params.copy_(p0)
+            ppo.adam_mv.zero_()
+            ppo.step, ppo.member_steps = 0, [0] * P
+
+    def common():
+        ppo.update(b, perm_u, epochs, minibatches)
+        finals["common"] = pop.params.clone()
+
+    def lists():
+        ppo.update(b, perm_u, [epochs] * P, [minibatches] * P)
+        finals["lists"] = pop.params.clone()
+
+    def skew_pop():
+        ppo.update(b, perm, sk_epochs, sk_mbs)
+        finals["skew_pop"] = pop.params.clone()
+
+    def skew_seq():
+        for m in range(P):
+            seq_ppos[m].update(slices[m], perm_m[m], sk_epochs[m], sk_mbs[m])
+        finals["seq"] = seq.params.clone()
+
+    out = {"members": P, "envs_per_member": n, "horizon": horizon, "uniform_epochs": epochs, "uniform_minibatches": minibatches,
+           "skew_epochs": "1..4 cycling", "skew_minibatches": "1, 4, 16 cycling"}
+    t = _alternate([("common", common), ("lists", lists)], repeats, before=restore)
+    for k in ("common", "lists"):
+        out["uniform_%s_ms" % k] = statistics.median(t[k])
+        out["uniform_%s_ms_all" % k] = [round(x, 3) for x in t[k]]
+    out["uniform_spread"] = (max(t["common"]) - min(t["common"])) / statistics.median(t["common"])
+    out["uniform_lists_over_common"] = out["uniform_lists_ms"] / out["uniform_common_ms"]
+    out["uniform_bitwise_equal"] = bool(torch.equal(finals["common"], finals["lists"]))
+    t = _alternate([("seq", skew_seq), ("skew_pop", skew_pop)], repeats, before=restore)
+    out["skew_seq_ms"], out["skew_pop_ms"] = statistics.median(t["seq"]), statistics.median(t["skew_pop"])
+    out["skew_seq_ms_all"], out["skew_pop_ms_all"] = [round(x, 3) for x in t["seq"]], [round(x, 3) for x in t["skew_pop"]]
+    out["skew_speedup"] = out["skew_seq_ms"] / out["skew_pop_ms"]
+    out["skew_bitwise_equal"] = bool(torch.equal(finals["seq"], finals["skew_pop"]))
+    env.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="16x4096,120x512")
     ap.add_argument("--horizon", type=int, default=32)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--sched", action="store_true", help="time per-member schedules (ssg_pop_update_sched) instead")
     a = ap.parse_args()
     mod = _ppo()
+    if a.sched:
+        res = [measure_sched(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.horizon, a.repeats, "cuda:0") for c in a.configs.split(",")]
+        print(json.dumps({"population_sched_timing": res}))
+        return
     res = [measure(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.horizon, a.repeats, "cuda:0") for c in a.configs.split(",")]
     print(json.dumps({"population_timing": res}))
 

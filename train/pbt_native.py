@@ -5,6 +5,8 @@ line changed and needs ray; this one needs only the library.
 
     python train/pbt_native.py --members 16 --envs-per-member 512 --updates 40 --horizon 32 --perturb-every 5 --seed 0
     python train/pbt_native.py --lrs 1e-3,1e-4,1e-5 --no-pbt        # the learning-rate sweep of train/stable_baselines/ppo.py:118-137
+    python train/pbt_native.py --mutate-schedule                    # num_sgd_iter and sgd_minibatch_size per member too (pbt.py:40-41)
+    python train/pbt_native.py --members 3 --epochs 1,2,4 --minibatches 4,4,8 --no-pbt   # a sweep over schedules
 
 One ShipVecEnv of members x envs-per-member envs; member m owns the contiguous slice [m*n, (m+1)*n).  Every update is one
 ``rollout_population`` (one policy launch per step for the whole population), then ``PopulationPPO.gae`` and ``.update`` (two launches
@@ -16,8 +18,14 @@ x0.8 or a neighbouring list entry otherwise) ranked by episode_reward_mean.
 What differs from the reference, on purpose:
 * --perturb-every counts UPDATES, not seconds of wall time (the reference perturbs every 600 s of a trial's own clock; a population
   that trains in lockstep has no per-trial clock, and a count makes runs reproducible);
-* of the six mutated hyper-parameters only lambda, clip_param and lr vary per member: num_sgd_iter, sgd_minibatch_size and
-  train_batch_size shape the launches and are common to the population (--epochs, --minibatches, --horizon);
+* of the six mutated hyper-parameters lambda, clip_param and lr always vary per member; num_sgd_iter and sgd_minibatch_size do with
+  --mutate-schedule (initial draws from the reference's {10, 20, 30} and {128, 512, 2048}, train/rllib/pbt.py:65-68; mutated as
+  :40-41; the source's schedule travels with an exploit) and are otherwise set by --epochs / --minibatches, which also take
+  comma-separated per-member lists; train_batch_size is common to the population (--horizon x --envs-per-member);
+* a schedule is clamped before use: num_sgd_iter to [1, --max-epochs] (the permutations are drawn as [P, max-epochs, samples]) and the
+  minibatch size to [min(128, samples), samples].  ray clamps nothing: there a trial whose sgd_minibatch_size exceeds its
+  train_batch_size simply fails.  A minibatch size becomes a minibatch count (ceil(samples / size)), and the chunks are torch.chunk's:
+  at most `size` long, not RLlib's exact slices;
 * one handle on one GPU, one architecture.
 
 The loss terms of the reference trainers' own PPO are opt-in: --kl-coeff 1.0 is the reference's setting (train/rllib/pbt.py:55-62; the
@@ -34,6 +42,12 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 INITIAL = {"lambda": 0.95, "clip_param": 0.2, "lr": 5e-4}  # train/rllib/pbt.py:60-62
+INITIAL_SCHEDULE = {"num_sgd_iter": [10, 20, 30], "sgd_minibatch_size": [128, 512, 2048]}  # train/rllib/pbt.py:65-68
+
+
+def clamp_schedule(num_sgd_iter, sgd_minibatch_size, samples, max_epochs):
+    """The schedule as it is used: num_sgd_iter in [1, max_epochs], the minibatch size in [min(128, samples), samples]; ints."""
+    return (max(1, min(int(max_epochs), int(num_sgd_iter))), max(min(128, int(samples)), min(int(samples), int(sgd_minibatch_size))))
 
 
 def make_arg_parser():
@@ -44,8 +58,12 @@ def make_arg_parser():
     ap.add_argument("--horizon", type=int, default=32, help="rollout steps per update (common to the population)")
     ap.add_argument("--perturb-every", type=int, default=5, help="perturbation interval in UPDATES (the reference: 600 s of wall time)")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--epochs", type=int, default=2)
-    ap.add_argument("--minibatches", type=int, default=4)
+    ap.add_argument("--epochs", default="2", help="epochs per update, or a comma-separated list, one member each")
+    ap.add_argument("--minibatches", default="4", help="minibatches per epoch, or a comma-separated list, one member each")
+    ap.add_argument("--mutate-schedule", action="store_true",
+                    help="num_sgd_iter and sgd_minibatch_size per member: drawn from the reference's sets, mutated and exploited "
+                         "(overrides --epochs / --minibatches)")
+    ap.add_argument("--max-epochs", type=int, default=30, help="upper clamp of a mutated num_sgd_iter")
     ap.add_argument("--lrs", default=None, help="comma-separated learning rates, one member each (overrides --members)")
     ap.add_argument("--no-pbt", dest="pbt", action="store_false", help="no exploit / explore: a plain sweep")
     ap.add_argument("--kl-coeff", type=float, default=0.0, help="initial KL penalty coefficient (the reference: 1.0; 0 = no KL term)")
@@ -64,6 +82,22 @@ def parse_args(argv=None):
     a.lrs = [float(x) for x in a.lrs.split(",")] if a.lrs else None
     if a.lrs is not None:
         a.members = len(a.lrs)
+    for key in ("epochs", "minibatches"):
+        try:
+            vals = [int(x) for x in str(getattr(a, key)).split(",")]
+        except ValueError:
+            ap.error("--%s takes an integer or a comma-separated list of integers" % key)
+        if min(vals) < 1:
+            ap.error("--%s must be >= 1" % key)
+        setattr(a, key, vals[0] if len(vals) == 1 else vals)
+    lists = [len(v) for v in (a.epochs, a.minibatches) if isinstance(v, list)]
+    if lists:
+        if a.lrs is None:
+            a.members = lists[0]
+        if any(n != a.members for n in lists):
+            ap.error("--epochs / --minibatches list %s entries for %d members" % (lists, a.members))
+    if a.max_epochs < 1:
+        ap.error("--max-epochs must be >= 1")
     if a.members < 1 or a.envs_per_member < 1 or a.updates < 1 or a.horizon < 1 or a.perturb_every < 1:
         ap.error("--members, --envs-per-member, --updates, --horizon and --perturb-every must be >= 1")
     if a.kl_coeff < 0 or a.kl_target < 0 or a.vf_clip < 0 or a.max_grad_norm < 0:
@@ -73,10 +107,11 @@ def parse_args(argv=None):
 
 def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every=5, seed=0, epochs=2, minibatches=4, lrs=None,
           pbt=True, device="cuda:0", log=print, return_details=False, kl_coeff=0.0, kl_target=0.01, vf_clip=0.0, max_grad_norm=0.0,
-          separate_value=False):
+          separate_value=False, mutate_schedule=False, max_epochs=30):
     import torch
     from ship_gym.config import EnvConfig, GameConfig
-    from ship_sim_gym_amd.population import NativePopulation, PBTScheduler, PopulationPPO
+    from ship_sim_gym_amd.population import NativePopulation, PBTScheduler, PopulationPPO, reference_mutations
+    from ship_sim_gym_amd.ppo import chunk_split
     from ship_sim_gym_amd.vec_env import ShipVecEnv
     from train.ppo_torch import ActorCritic
     from train.rllib_ppo import game_configuration
@@ -100,40 +135,76 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
     pop = NativePopulation.from_actor_critics(nets, scale)
     ppo = PopulationPPO(pop, env, lam=INITIAL["lambda"], clip=INITIAL["clip_param"], lr=list(lrs) if lrs is not None else INITIAL["lr"],
                         vf_clip=vf_clip, max_grad_norm=max_grad_norm, kl_coef=kl_coeff, kl_target=kl_target if kl_coeff > 0 else 0.0)
-    sched = PBTScheduler(P, seed=seed, perturbation_interval=perturb_every)
+    sched = PBTScheduler(P, seed=seed, perturbation_interval=perturb_every,
+                         mutations=reference_mutations(schedule=True) if mutate_schedule else None)
     env.reset_tensor()
     window = torch.zeros((P, 3), dtype=torch.int64, device=dev)  # episodes since the last perturbation
     scores = [float("-inf")] * P
     samples = horizon * n
     out, history, exploits = None, [], []
+    # the schedule: common ints (one launch shape for everyone, as before) or one entry per member
+    per_member = mutate_schedule or isinstance(epochs, (list, tuple)) or isinstance(minibatches, (list, tuple))
+    if mutate_schedule:
+        draws = [clamp_schedule(sched.rng.choice(INITIAL_SCHEDULE["num_sgd_iter"]), sched.rng.choice(INITIAL_SCHEDULE["sgd_minibatch_size"]),
+                                samples, max_epochs) for _ in range(P)]
+        iters, sizes = [d[0] for d in draws], [d[1] for d in draws]
+        log("schedule: num_sgd_iter %s  sgd_minibatch_size %s" % (iters, sizes))
+    elif per_member:
+        iters = [int(e) for e in epochs] if isinstance(epochs, (list, tuple)) else [int(epochs)] * P
+        counts = [int(b) for b in minibatches] if isinstance(minibatches, (list, tuple)) else [int(minibatches)] * P
+        if len(iters) != P or len(counts) != P:
+            raise ValueError("train: %d epochs and %d minibatches for %d members" % (len(iters), len(counts), P))
+        sizes = [chunk_split(samples, c)[0] for c in counts]
+    perm_epochs = max_epochs if mutate_schedule else (max(iters) if per_member else epochs)
     for u in range(1, updates + 1):
         uniforms = torch.rand((horizon, P * n), generator=gen, device=dev)
         batch = env.rollout_population(pop, horizon, uniforms=uniforms, out=out)
         out = {k: v for k, v in batch.items() if k not in ("adv", "ret", "logp_all")}
         window += ppo.episode_stats(batch)
         ppo.gae(batch)
-        perm = torch.rand((P, epochs, samples), generator=gen, device=dev).argsort(dim=-1)
-        ppo.update(batch, perm, epochs, minibatches)
+        perm = torch.rand((P, perm_epochs, samples), generator=gen, device=dev).argsort(dim=-1)
+        if per_member:
+            mbs = [ppo.minibatches_for_size(s, samples) for s in sizes] if mutate_schedule else counts
+            ppo.update(batch, perm[:, :max(iters)].contiguous(), iters, mbs)
+        else:
+            ppo.update(batch, perm, epochs, minibatches)
         w = window.cpu().tolist()
         scores = [w[m][0] / 100.0 / w[m][2] if w[m][2] else scores[m] for m in range(P)]
         history.append(list(scores))
         log("update %d  episode_reward_mean %s" % (u, " ".join("%d:%.3f" % (m, s) for m, s in enumerate(scores))))
         if pbt and sched.due(u):
-            src, new, events = sched.perturb(scores, {"lambda": ppo.lam, "clip_param": ppo.clip, "lr": ppo.lr})
+            hp = {"lambda": ppo.lam, "clip_param": ppo.clip, "lr": ppo.lr}
+            if mutate_schedule:
+                hp.update({"num_sgd_iter": iters, "sgd_minibatch_size": sizes})
+            elif per_member:  # a swept schedule is not mutated, but it is its member's configuration: it travels with an exploit
+                hp.update({"num_sgd_iter": iters, "minibatches": counts})
+            src, new, events = sched.perturb(scores, hp)
             ppo.exploit(src)
             ppo.lam, ppo.clip, ppo.lr = new["lambda"], new["clip_param"], new["lr"]
+            if mutate_schedule:
+                used = [clamp_schedule(i, s, samples, max_epochs) for i, s in zip(new["num_sgd_iter"], new["sgd_minibatch_size"])]
+                iters, sizes = [c[0] for c in used], [c[1] for c in used]
+            elif per_member:
+                iters, counts = new["num_sgd_iter"], new["minibatches"]
+                sizes = [chunk_split(samples, c)[0] for c in counts]
             for ev in events:
                 log("update %d  exploit: member %d <- member %d" % (u, ev["member"], ev["source"]))
                 for key, kind, old, val in ev["mutations"]:
                     log("update %d  mutation: member %d %s %s %.6g -> %.6g" % (u, ev["member"], key, kind, old, val))
+                if per_member:
+                    ev["schedule"] = {"num_sgd_iter": iters[ev["member"]], "sgd_minibatch_size": sizes[ev["member"]]}
+                    log("update %d  schedule: member %d num_sgd_iter %d sgd_minibatch_size %d (as used)"
+                        % (u, ev["member"], iters[ev["member"]], sizes[ev["member"]]))
                 scores[ev["member"]] = scores[ev["source"]]
             exploits += events
             window.zero_()
     torch.cuda.synchronize(dev)
     pop.load_into(nets)
     details = {"params": pop.params.detach().clone(), "exploits": exploits, "nets": nets,
-               "hparams": {"lambda": list(ppo.lam), "clip_param": list(ppo.clip), "lr": list(ppo.lr)},
-               "kl_coef": ppo.kl_coef.detach().cpu().tolist()}
+               "hparams": {"lambda": list(ppo.lam), "clip_param": list(ppo.clip), "lr": list(ppo.lr),
+                           "num_sgd_iter": list(iters) if per_member else [int(epochs)] * P,
+                           "sgd_minibatch_size": list(sizes) if per_member else [chunk_split(samples, minibatches)[0]] * P},
+               "member_steps": list(ppo.member_steps), "kl_coef": ppo.kl_coef.detach().cpu().tolist()}
     env.close()
     return (history, details) if return_details else history
 
@@ -142,7 +213,8 @@ def main(argv=None):
     a = parse_args(argv)
     train(members=a.members, envs_per_member=a.envs_per_member, updates=a.updates, horizon=a.horizon, perturb_every=a.perturb_every,
           seed=a.seed, epochs=a.epochs, minibatches=a.minibatches, lrs=a.lrs, pbt=a.pbt, device=a.device, kl_coeff=a.kl_coeff,
-          kl_target=a.kl_target, vf_clip=a.vf_clip, max_grad_norm=a.max_grad_norm, separate_value=a.separate_value)
+          kl_target=a.kl_target, vf_clip=a.vf_clip, max_grad_norm=a.max_grad_norm, separate_value=a.separate_value,
+          mutate_schedule=a.mutate_schedule, max_epochs=a.max_epochs)
 
 
 if __name__ == "__main__":
