@@ -483,6 +483,15 @@ int ssg_rollout_policy(ssg_handle *h, const ssg_policy *pol, int K, const float 
                        float *dev_x_KND /* nullable */, double *dev_reward_KN, uint8_t *dev_done_KN, uint8_t *dev_flags_KN /* nullable */,
                        float *dev_last_value /* nullable */, int64_t step_stride_envs, void *stream);
 
+/* Replaces: the deterministic action of a trained policy — Stable-Baselines' model.predict(obs, deterministic=True), and the
+ * agent.compute_action of the reference's evaluation script (train/rllib/rollout.py:15) run without exploration.  ssg_policy_act's
+ * forward, then instead of a draw: dev_actions[e] = the smallest j < n_actions whose logit is the maximum, dev_logp[e] = that logit
+ * - lse (the entry ssg_ppo_dist writes for it, bit for bit).  No uniform is read and no Philox round is run, so there is no seed or
+ * step; dev_value and dev_x are bit for bit what ssg_policy_act writes for the same observations.  One launch.  Validates and refuses
+ * as ssg_policy_act does. */
+int ssg_policy_act_greedy(ssg_handle *h, const ssg_policy *pol, const double *dev_obs, int32_t *dev_actions, float *dev_logp,
+                          float *dev_value, float *dev_x /* nullable */, void *stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * The PPO update on the device (additions to ABI 9)
  * What the reference's PPO2 does after every rollout inside model.learn (train/stable_baselines/ppo.py:90), and what
@@ -691,6 +700,12 @@ int ssg_pop_rollout(ssg_handle *h, const ssg_population *pop, int K, const float
                     float *dev_x_KND /* nullable */, double *dev_reward_KN, uint8_t *dev_done_KN, uint8_t *dev_flags_KN /* nullable */,
                     float *dev_last_value /* nullable */, int64_t step_stride_envs, void *stream);
 
+/* Replaces: train/rllib/rollout.py:15's compute_action for every trial of the PBT experiment at once (train/rllib/pbt.py:29-43).
+ * ssg_policy_act_greedy with env e under member e / n's parameter row, one launch for the whole population; each member's slice is
+ * bit for bit ssg_policy_act_greedy on that slice with that row.  Validates and refuses as ssg_pop_act does. */
+int ssg_pop_act_greedy(ssg_handle *h, const ssg_population *pop, const double *dev_obs, int32_t *dev_actions, float *dev_logp,
+                       float *dev_value, float *dev_x /* nullable */, void *stream);
+
 /* Replaces nothing (host only; no reference counterpart: ray hands every trial its own config dict, train/rllib/pbt.py:56-70).  Fills
  * out[0 .. SSG_POP_TABLE_FLOATS(n_members, n_steps)) with the members' f32 constants: 8 per member for GAE and the loss, then for Adam
  * steps step0 + 1 .. step0 + n_steps 8 per member and step (n_steps = 0: no Adam rows, enough for ssg_pop_gae).  SSG_ERR_BAD_ARG for
@@ -813,6 +828,72 @@ int ssg_pop_exploit(ssg_handle *h, const ssg_population *pop, const int32_t *src
  * member's row of dev_out (int64 [P][3], accumulated: the caller zeroes it).  Integer sums: order-free and exact.  One launch. */
 int ssg_pop_episode_stats(ssg_handle *h, int n_members, int K, const double *dev_reward_KN, const uint8_t *dev_done_KN,
                           double *dev_carry_return, int32_t *dev_carry_length, int64_t *dev_out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Evaluation (ABI 9 addition): run a policy, or a population, for whole episodes and report how it did
+ * The reference's evaluation script (train/rllib/rollout.py:8-26): act, step until done, print the episode's reward.  Here for every env
+ * of a handle at once, with no host synchronisation inside a call.  Every env contributes exactly its first E episodes (an env that
+ * crashes early does not weigh more than one that sails on), and each counted episode's ending is tallied from the SSG_EV_* bits of its
+ * done step.
+ *
+ * Per-env carry, caller-owned, zeroed by the caller after a reset: dev_carry_return f64 [N] (the running episode's return) and dev_carry
+ * int32 [N][4] = (length, goal events of the running episode, episodes counted so far, 0), 16-byte aligned.  While an env's episodes
+ * counted is below E, every step adds the reward to its return, 1 to its length and 1 to its goal events when the step's flags have
+ * SSG_EV_GOAL_REACHED; at a done step it adds to its row of dev_env_stats (int64 [N][SSG_EVAL_STATS], caller-zeroed):
+ *   [0] 1 (an episode)                 [1] llrint(100 * return), as ssg_pop_episode_stats counts it      [2] length
+ *   [3] 1 if the done step's flags have SSG_EV_COLLIDING       [4] ... SSG_EV_OUT_OF_BOUNDS      [5] ... SSG_EV_MAX_STEPS
+ *   [6] ... SSG_EV_NO_GOALS_LEFT       [7] the episode's goal events
+ * ([3]..[6] are not exclusive of each other), then zeroes return, length and goal events and bumps its episode count.  Once an env has
+ * counted E episodes its row and carry no longer change, though the env keeps stepping.  An episode still running when a call ends
+ * stays in the carry: a later call continues it.
+ * ------------------------------------------------------------------------------------------------- */
+#define SSG_EVAL_STATS 8
+#define SSG_EVAL_GREEDY 0x1u /* ssg_eval.flags: the arg-max action (ssg_policy_act_greedy) instead of a draw */
+typedef struct ssg_eval {
+    uint32_t struct_size;        /* sizeof(ssg_eval) */
+    uint32_t flags;              /* SSG_EVAL_GREEDY or 0; any other bit is refused */
+    int32_t episodes_per_env;    /* E >= 1 */
+    int32_t n_steps;             /* T >= 1: the iterations this call enqueues */
+    uint64_t seed;               /* Philox key of the sampled mode without uniforms, as ssg_rollout_policy keys it */
+    int64_t step0;               /* iteration k is step step0 + k of that stream */
+    const float *dev_uniform_TN; /* nullable: f32 [T][N], row k drives iteration k; refused together with SSG_EVAL_GREEDY */
+    double *dev_obs;             /* f64 [N][D]: the handle's current observations, rewritten by every step */
+    int32_t *dev_act;            /* one-row scratch buffers [N], rewritten by every iteration: all required */
+    float *dev_logp;
+    float *dev_value;
+    double *dev_reward;
+    uint8_t *dev_done;
+    uint8_t *dev_flags;
+    double *dev_carry_return;    /* f64 [N] */
+    int32_t *dev_carry;          /* int32 [N][4], 16-byte aligned */
+    int64_t *dev_env_stats;      /* int64 [N][SSG_EVAL_STATS] */
+} ssg_eval;
+
+/* Replaces: the loop of train/rllib/rollout.py:8-26 (compute_action, env.step until done, the episode's reward summed), T iterations
+ * enqueued from C on `stream` with no host synchronisation.  Iteration k: (1) the policy launch at step step0 + k — greedy, or sampling
+ * with row k of dev_uniform_TN, or Philox exactly as ssg_rollout_policy keys it; (2) ssg_rollout_traj(h, dev_act, 1, ...), the call
+ * ssg_rollout_policy makes: every handle kind it serves is served, with identical launches; (3) the accounting launch above.
+ * Everything refusable is refused before the first launch: what ssg_rollout_policy refuses (a capturing stream and an unfilled map ring
+ * among it), a bad ssg_eval record, a NULL required pointer, and a handle without SSG_FLAG_AUTO_RESET (a done env would never start its
+ * next episode). */
+int ssg_evaluate(ssg_handle *h, const ssg_policy *pol, const ssg_eval *ev, void *stream);
+
+/* Replaces: the `reward_total += reward` ... print of train/rllib/rollout.py:13-26 for a caller that steps the handle itself (ssg_step
+ * with its own actions): the accounting launch of ssg_evaluate alone, on one step's dev_reward / dev_done / dev_flags rows ([N] each),
+ * with episodes_per_env = E >= 1 and the carries and stats rows described above.  One launch.  SSG_ERR_BAD_ARG (nothing launched) for
+ * E < 1, a NULL pointer or a dev_carry that is not 16-byte aligned. */
+int ssg_eval_account(ssg_handle *h, int episodes_per_env, const double *dev_reward, const uint8_t *dev_done, const uint8_t *dev_flags,
+                     double *dev_carry_return, int32_t *dev_carry, int64_t *dev_env_stats, void *stream);
+
+/* Replaces: train/rllib/rollout.py:8-26 for every trial of the PBT experiment at once (train/rllib/pbt.py:29-43 ranks trials by training
+ * episodes; this is the held-out run).  ssg_evaluate with the population's one policy launch per step (ssg_pop_act / ssg_pop_act_greedy);
+ * member m's envs are rows [m*n, (m+1)*n) of every buffer, n = N / n_members.  Refuses what ssg_pop_rollout and ssg_evaluate refuse. */
+int ssg_pop_evaluate(ssg_handle *h, const ssg_population *pop, const ssg_eval *ev, void *stream);
+
+/* Replaces: the mean over rollouts a user of train/rllib/rollout.py:8-26 forms by hand.  dev_member_stats (int64 [n_members][SSG_EVAL_STATS])
+ * is WRITTEN, not accumulated, with the column sums of each member's n = N / n_members rows of dev_env_stats: one workgroup per member,
+ * a strided loop and an integer tree, no atomics.  n_members = 1 serves a single policy.  One launch. */
+int ssg_eval_reduce(ssg_handle *h, int n_members, const int64_t *dev_env_stats, int64_t *dev_member_stats, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Host-side geometry (what pymunk's cffi exposed at reset time); no GPU needed.

@@ -21,6 +21,10 @@ POLICY_SEPARATE_VALUE = 0x100  # or-ed into Policy.activation / Population.activ
 POP_MAX_MEMBERS = 256
 POP_EXT_GRAD_CLIP, POP_EXT_VF_CLIP = 0x1, 0x2
 PPO_EXT_STATS = 8  # stats columns of the _ext entry points
+EVAL_STATS, EVAL_GREEDY = 8, 0x1  # columns of an evaluation's stats rows; ssg_eval.flags
+# the columns (include/shipsim.h): episodes, llrint(100 * return), length, the four endings (not exclusive), goal events
+(EVAL_EPISODES, EVAL_RETURN100, EVAL_LENGTH, EVAL_COLLIDED, EVAL_OUT_OF_BOUNDS, EVAL_MAX_STEPS, EVAL_NO_GOALS_LEFT,
+ EVAL_GOALS) = range(8)
 
 
 def pop_table_floats(n_members, n_steps):
@@ -57,6 +61,7 @@ EXPORTS = (
     "ssg_pop_exploit", "ssg_pop_episode_stats",
     "ssg_ppo_dist", "ssg_ppo_grad_ext", "ssg_ppo_update_ext", "ssg_pop_dist", "ssg_pop_update_ext",
     "ssg_pop_pack_schedule", "ssg_pop_pack_hparams_steps", "ssg_pop_update_sched",
+    "ssg_policy_act_greedy", "ssg_pop_act_greedy", "ssg_evaluate", "ssg_pop_evaluate", "ssg_eval_reduce", "ssg_eval_account",
 )
 
 
@@ -119,6 +124,17 @@ class PopExt(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("flags", C.c_uint32), ("dev_ext", C.c_void_p), ("dev_kl_coef", C.c_void_p),
         ("dev_logp_all", C.c_void_p), ("dev_value_old", C.c_void_p),
+    ]
+
+
+class Eval(C.Structure):
+    """ssg_eval (ABI 9 addition): one call of the evaluation loop — mode, quota, steps, the scratch rows, carries and stats rows."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("flags", C.c_uint32), ("episodes_per_env", C.c_int32), ("n_steps", C.c_int32),
+        ("seed", C.c_uint64), ("step0", C.c_int64), ("dev_uniform_TN", C.c_void_p), ("dev_obs", C.c_void_p),
+        ("dev_act", C.c_void_p), ("dev_logp", C.c_void_p), ("dev_value", C.c_void_p), ("dev_reward", C.c_void_p),
+        ("dev_done", C.c_void_p), ("dev_flags", C.c_void_p), ("dev_carry_return", C.c_void_p), ("dev_carry", C.c_void_p),
+        ("dev_env_stats", C.c_void_p),
     ]
 
 
@@ -202,6 +218,12 @@ def lib():
     L.ssg_pop_pack_hparams_steps.argtypes = [C.c_int, hp, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_float), C.c_size_t]
     L.ssg_pop_update_sched.argtypes = [vp, pp, qp, vp, C.c_int, vp, i32p, i32p, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                        C.c_size_t, vp]
+    L.ssg_policy_act_greedy.argtypes = [vp, C.POINTER(Policy), vp, vp, vp, vp, vp, vp]
+    L.ssg_pop_act_greedy.argtypes = [vp, pp, vp, vp, vp, vp, vp, vp]
+    L.ssg_evaluate.argtypes = [vp, C.POINTER(Policy), C.POINTER(Eval), vp]
+    L.ssg_pop_evaluate.argtypes = [vp, pp, C.POINTER(Eval), vp]
+    L.ssg_eval_reduce.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.ssg_eval_account.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.ssg_render.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, vp]
     L.ssg_dyn_invalidate.argtypes = [vp, vp, vp]
     L.ssg_host_convex_hull.argtypes = [C.c_int, dp, dp, ip]

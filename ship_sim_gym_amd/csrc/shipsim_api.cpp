@@ -1025,6 +1025,23 @@ int ssg_policy_act(ssg_handle *h, const ssg_policy *pol, const double *dev_obs, 
     return SSG_OK;
 }
 
+int ssg_policy_act_greedy(ssg_handle *h, const ssg_policy *pol, const double *dev_obs, int32_t *dev_actions, float *dev_logp,
+                          float *dev_value, float *dev_x, void *stream)
+{
+    int rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    rc = check_policy(h, pol, "ssg_policy_act_greedy");
+    if (rc != SSG_OK) return rc;
+    if (!dev_obs || !dev_actions || !dev_logp || !dev_value)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_policy_act_greedy: NULL dev_obs, dev_actions, dev_logp or dev_value");
+    rc = prepare_policy(h);
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_policy_act_greedy(*pol, h->cfg.n_envs, dev_obs, dev_actions, dev_logp, dev_value, dev_x,
+                                                 static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("policy launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
 int ssg_rollout_policy(ssg_handle *h, const ssg_policy *pol, int K, const float *dev_uniform_KN, uint64_t seed, int64_t step0,
                        double *dev_obs, int32_t *dev_act_KN, float *dev_logp_KN, float *dev_value_KN, float *dev_x_KND,
                        double *dev_reward_KN, uint8_t *dev_done_KN, uint8_t *dev_flags_KN, float *dev_last_value,
@@ -1481,6 +1498,24 @@ int ssg_pop_act(ssg_handle *h, const ssg_population *pop, const double *dev_obs,
     return SSG_OK;
 }
 
+int ssg_pop_act_greedy(ssg_handle *h, const ssg_population *pop, const double *dev_obs, int32_t *dev_actions, float *dev_logp,
+                       float *dev_value, float *dev_x, void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_act_greedy");
+    if (rc != SSG_OK) return rc;
+    if (!dev_obs || !dev_actions || !dev_logp || !dev_value)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_act_greedy: NULL dev_obs, dev_actions, dev_logp or dev_value");
+    rc = check_ready(h, false);
+    if (rc == SSG_OK) rc = prepare_policy(h);
+    if (rc != SSG_OK) return rc;
+    const int P = pop->n_members;
+    hipError_t e = ssg::launch_policy_pop_greedy(pop_policy(*pop), P, h->cfg.n_envs / P, dev_obs, dev_actions, dev_logp, dev_value, dev_x,
+                                                 static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population policy launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
 int ssg_pop_rollout(ssg_handle *h, const ssg_population *pop, int K, const float *dev_uniform_KN, uint64_t seed, int64_t step0,
                     double *dev_obs, int32_t *dev_act_KN, float *dev_logp_KN, float *dev_value_KN, float *dev_x_KND,
                     double *dev_reward_KN, uint8_t *dev_done_KN, uint8_t *dev_flags_KN, float *dev_last_value, int64_t step_stride_envs,
@@ -1832,6 +1867,114 @@ int ssg_pop_episode_stats(ssg_handle *h, int n_members, int K, const double *dev
     hipError_t e = ssg::launch_pop_episode_stats(n_members, K, h->cfg.n_envs, dev_reward_KN, dev_done_KN, dev_carry_return,
                                                  dev_carry_length, dev_out, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population episode stats launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+// ABI 9 additions: evaluation.  Order of the refusals as for a population: no handle (BAD_ARG), no state blob (NOT_BOUND), everything
+// the host can judge about the records (BAD_ARG), and only then the bank and the device — nothing is enqueued before all of it passed.
+static int check_eval(ssg_handle *h, const ssg_eval *ev, const char *what)
+{
+    const std::string w(what);
+    if (!ev) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL ssg_eval");
+    if (ev->struct_size != sizeof(ssg_eval)) return fail(h, SSG_ERR_BAD_ARG, w + ": ssg_eval.struct_size != sizeof(ssg_eval)");
+    if (ev->flags & ~SSG_EVAL_GREEDY) return fail(h, SSG_ERR_BAD_ARG, w + ": unknown bit in ssg_eval.flags");
+    if (ev->episodes_per_env < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": episodes_per_env < 1");
+    if (ev->n_steps < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": n_steps < 1");
+    if ((ev->flags & SSG_EVAL_GREEDY) && ev->dev_uniform_TN)
+        return fail(h, SSG_ERR_BAD_ARG, w + ": dev_uniform_TN given together with SSG_EVAL_GREEDY (a greedy action reads no uniform)");
+    if (!(h->cfg.flags & SSG_FLAG_AUTO_RESET))
+        return fail(h, SSG_ERR_BAD_ARG, w + ": the handle lacks SSG_FLAG_AUTO_RESET (a done env would never start its next episode)");
+    if (!ev->dev_obs || !ev->dev_act || !ev->dev_logp || !ev->dev_value || !ev->dev_reward || !ev->dev_done || !ev->dev_flags)
+        return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_obs, dev_act, dev_logp, dev_value, dev_reward, dev_done or dev_flags");
+    if (!ev->dev_carry_return || !ev->dev_carry || !ev->dev_env_stats)
+        return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_carry_return, dev_carry or dev_env_stats");
+    if (reinterpret_cast<uintptr_t>(ev->dev_carry) % 16 != 0) return fail(h, SSG_ERR_BAD_ARG, w + ": dev_carry must be 16-byte aligned");
+    return SSG_OK;
+}
+
+// the loop of both entry points: pop == nullptr runs one policy
+static int run_evaluate(ssg_handle *h, const ssg_policy &pol, const ssg_population *pop, const ssg_eval &ev, const char *what, void *stream)
+{
+    int rc = check_ready(h, true);
+    if (rc != SSG_OK) return rc;
+    // what the per-step ssg_step would refuse, refused before the first policy launch
+    if (h->cfg.map_ring > 0 && !h->ring_ready) return fail(h, SSG_ERR_NOT_BOUND, "map_ring mode: call ssg_refill_worlds first");
+    rc = refuse_capture(h, stream, what);
+    if (rc != SSG_OK) return rc;
+    rc = prepare(h);
+    if (rc == SSG_OK) rc = prepare_policy(h);
+    if (rc != SSG_OK) return rc;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool greedy = (ev.flags & SSG_EVAL_GREEDY) != 0;
+    const int N = h->cfg.n_envs, P = pop ? pop->n_members : 1, n = N / P;
+    for (int k = 0; k < ev.n_steps; ++k) {
+        const float *u = ev.dev_uniform_TN ? ev.dev_uniform_TN + (size_t)k * (size_t)N : nullptr;
+        hipError_t e;
+        if (pop)
+            e = greedy ? ssg::launch_policy_pop_greedy(pol, P, n, ev.dev_obs, ev.dev_act, ev.dev_logp, ev.dev_value, nullptr, st)
+                       : ssg::launch_policy_pop(pol, P, n, h->cfg.env_id_base, ev.dev_obs, u, ev.seed, ev.step0 + k, ev.dev_act, ev.dev_logp,
+                                                ev.dev_value, nullptr, st);
+        else
+            e = greedy ? ssg::launch_policy_act_greedy(pol, N, ev.dev_obs, ev.dev_act, ev.dev_logp, ev.dev_value, nullptr, st)
+                       : ssg::launch_policy_act(pol, N, h->cfg.env_id_base, ev.dev_obs, u, ev.seed, ev.step0 + k, ev.dev_act, ev.dev_logp,
+                                                ev.dev_value, nullptr, st);
+        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string(what) + ": policy launch: " + hipGetErrorString(e));
+        // (ssg_step as it stands, the call ssg_rollout_policy makes)
+        rc = ssg_rollout_traj(h, ev.dev_act, 1, ev.dev_obs, ev.dev_reward, ev.dev_done, ev.dev_flags, 0, stream);
+        if (rc != SSG_OK) return rc;
+        e = ssg::launch_eval_account(N, ev.episodes_per_env, ev.dev_reward, ev.dev_done, ev.dev_flags, ev.dev_carry_return, ev.dev_carry,
+                                     ev.dev_env_stats, st);
+        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string(what) + ": accounting launch: " + hipGetErrorString(e));
+    }
+    return SSG_OK;
+}
+
+int ssg_evaluate(ssg_handle *h, const ssg_policy *pol, const ssg_eval *ev, void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc == SSG_OK) rc = check_policy(h, pol, "ssg_evaluate");
+    if (rc == SSG_OK) rc = check_eval(h, ev, "ssg_evaluate");
+    if (rc != SSG_OK) return rc;
+    return run_evaluate(h, *pol, nullptr, *ev, "ssg_evaluate", stream);
+}
+
+int ssg_pop_evaluate(ssg_handle *h, const ssg_population *pop, const ssg_eval *ev, void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_evaluate");
+    if (rc == SSG_OK) rc = check_eval(h, ev, "ssg_pop_evaluate");
+    if (rc != SSG_OK) return rc;
+    return run_evaluate(h, pop_policy(*pop), pop, *ev, "ssg_pop_evaluate", stream);
+}
+
+int ssg_eval_account(ssg_handle *h, int episodes_per_env, const double *dev_reward, const uint8_t *dev_done, const uint8_t *dev_flags,
+                     double *dev_carry_return, int32_t *dev_carry, int64_t *dev_env_stats, void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc != SSG_OK) return rc;
+    if (episodes_per_env < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_eval_account: episodes_per_env < 1");
+    if (!dev_reward || !dev_done || !dev_flags || !dev_carry_return || !dev_carry || !dev_env_stats)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_eval_account: NULL dev_reward, dev_done, dev_flags, dev_carry_return, dev_carry or dev_env_stats");
+    if (reinterpret_cast<uintptr_t>(dev_carry) % 16 != 0) return fail(h, SSG_ERR_BAD_ARG, "ssg_eval_account: dev_carry must be 16-byte aligned");
+    rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_eval_account(h->cfg.n_envs, episodes_per_env, dev_reward, dev_done, dev_flags, dev_carry_return, dev_carry,
+                                            dev_env_stats, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("evaluation accounting launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+int ssg_eval_reduce(ssg_handle *h, int n_members, const int64_t *dev_env_stats, int64_t *dev_member_stats, void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc != SSG_OK) return rc;
+    if (n_members < 1 || n_members > SSG_POP_MAX_MEMBERS || h->cfg.n_envs % n_members != 0)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_eval_reduce: n_members must be in 1..SSG_POP_MAX_MEMBERS and divide the handle's n_envs");
+    if (!dev_env_stats || !dev_member_stats) return fail(h, SSG_ERR_BAD_ARG, "ssg_eval_reduce: NULL dev_env_stats or dev_member_stats");
+    rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_eval_reduce(n_members, h->cfg.n_envs / n_members, dev_env_stats, dev_member_stats, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("evaluation reduce launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
 

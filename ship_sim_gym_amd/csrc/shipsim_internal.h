@@ -311,6 +311,16 @@ hipError_t launch_kl_adapt(int members, const PpoExtLaunch &ext, float kl_target
 hipError_t launch_policy_dist(const ssg_policy &p, int members, int n, long long N, int K, const float *x, float *logp_all, hipStream_t stream);
 hipError_t launch_pop_episode_stats(int members, int K, int N, const double *rew, const uint8_t *done, double *carry_ret,
                                     int32_t *carry_len, int64_t *out, hipStream_t stream);
+// the greedy mode of the policy kernel (shipsim_policy.hip): the arg-max action and its logp; no uniform, seed or step
+hipError_t launch_policy_act_greedy(const ssg_policy &p, int n, const double *obs, int32_t *act, float *logp, float *value, float *x, hipStream_t stream);
+hipError_t launch_policy_pop_greedy(const ssg_policy &p, int members, int n, const double *obs, int32_t *act, float *logp, float *value, float *x,
+                                    hipStream_t stream);
+// episode accounting of an evaluation run (shipsim_eval.hip): one step's rows into the per-env carries and stats rows (an env counts its
+// first E episodes), and the per-member column sums of the stats rows
+constexpr int kEvalCols = SSG_EVAL_STATS;
+hipError_t launch_eval_account(int N, int E, const double *rew, const uint8_t *done, const uint8_t *flags, double *carry_ret, int32_t *carry,
+                               int64_t *stats, hipStream_t stream);
+hipError_t launch_eval_reduce(int members, int n, const int64_t *stats, int64_t *out, hipStream_t stream);
 
 #ifdef __HIPCC__
 // One round of Philox4x32-10 (counter ctr, key key).  The counter-based streams of the library — fill_actions_kernel's actions

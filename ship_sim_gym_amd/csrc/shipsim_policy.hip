@@ -192,7 +192,10 @@ __device__ __forceinline__ float log_sum_exp(const float (&lg)[4], int A)
 // with that row (the same code below).  The Philox counter stays the global env id: env_base + m*n + e.
 // SPLIT: the separate-value layout (p.activation carries SSG_POLICY_SEPARATE_VALUE); a launch with act_out runs both towers and has the
 // third activation buffer behind bufB, the value-only launch runs the vf tower alone in the shared plan's two buffers.
-template <bool POP, bool SPLIT>
+// GREEDY (ssg_policy_act_greedy / ssg_pop_act_greedy, the evaluation loop): the same forward, then step 4 is the arg-max instead of a
+// draw — no Philox round, `uniform` never read; value and x are the sampling launch's bit for bit.  A template parameter, so the four
+// sampling instantiations keep their code.
+template <bool POP, bool SPLIT, bool GREEDY = false>
 __global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1, 2))) policy_act_kernel(const ssg_policy p, const float *__restrict__ params, const double *__restrict__ scale,
                                                               int n, long long env_base, const double *__restrict__ obs,
                                                               const float *__restrict__ uniform, uint64_t seed, int64_t step,
@@ -205,7 +208,7 @@ __global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1
         params += (size_t)blockIdx.y * (size_t)plen;
         env_base += (long long)m0;
         obs += m0 * D;
-        if (uniform) uniform += m0;
+        if (!GREEDY && uniform) uniform += m0;
         if (act_out) act_out += m0;
         if (logp_out) logp_out += m0;
         if (value_out) value_out += m0;
@@ -272,6 +275,20 @@ __global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1
     const int e = e0 + lane;
     if (value_out) value_out[e] = v;
     if (!act_out) return; // (the bootstrap forward of ssg_rollout_policy: value only)
+
+    if (GREEDY) {
+        // 4g. a = the smallest j < A whose logit is the maximum (a later equal logit does not replace it), logp = lg[a] - lse: the
+        // entry policy_dist_kernel writes for that action, bit for bit
+        const float lse = log_sum_exp(lg, A);
+        int a = 0;
+        float best = lg[0];
+#pragma unroll
+        for (int j = 1; j < 4; ++j)
+            if (j < A && lg[j] > best) { best = lg[j]; a = j; }
+        act_out[e] = a;
+        logp_out[e] = best - lse;
+        return;
+    }
 
     // 4. inverse-CDF sampling, the formula order of ppo_torch's Shard.step(): log_softmax, cumsum(exp), count(u > cdf[j]) over j < A-1
     const float lse = log_sum_exp(lg, A);
@@ -382,9 +399,11 @@ size_t policy_lds_bytes(const ssg_policy &p, bool both_towers)
 
 hipError_t prepare_policy()
 {
-    const void *kernels[6] = {reinterpret_cast<const void *>(policy_act_kernel<false, false>), reinterpret_cast<const void *>(policy_act_kernel<true, false>),
-                              reinterpret_cast<const void *>(policy_act_kernel<false, true>), reinterpret_cast<const void *>(policy_act_kernel<true, true>),
-                              reinterpret_cast<const void *>(policy_dist_kernel<false>), reinterpret_cast<const void *>(policy_dist_kernel<true>)};
+    const void *kernels[10] = {reinterpret_cast<const void *>(policy_act_kernel<false, false>), reinterpret_cast<const void *>(policy_act_kernel<true, false>),
+                               reinterpret_cast<const void *>(policy_act_kernel<false, true>), reinterpret_cast<const void *>(policy_act_kernel<true, true>),
+                               reinterpret_cast<const void *>(policy_dist_kernel<false>), reinterpret_cast<const void *>(policy_dist_kernel<true>),
+                               reinterpret_cast<const void *>(policy_act_kernel<false, false, true>), reinterpret_cast<const void *>(policy_act_kernel<true, false, true>),
+                               reinterpret_cast<const void *>(policy_act_kernel<false, true, true>), reinterpret_cast<const void *>(policy_act_kernel<true, true, true>)};
     for (const void *k : kernels) {
         hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
@@ -411,6 +430,26 @@ hipError_t launch_policy_pop(const ssg_policy &p, int members, int n, long long 
     hipLaunchKernelGGL(kernel, dim3(grid, (unsigned)members),
                        dim3(kPolWave), policy_lds_bytes(p, act != nullptr), stream, p, p.dev_params, p.dev_obs_scale, n, env_base, obs, uniform,
                        seed, step, act, logp, value, x, ppo_packed_len(p));
+    return hipGetLastError();
+}
+
+// the greedy launches: act / logp / value are all written (the callers refuse a NULL one), no uniform, seed or step
+hipError_t launch_policy_act_greedy(const ssg_policy &p, int n, const double *obs, int32_t *act, float *logp, float *value, float *x, hipStream_t stream)
+{
+    const unsigned grid = (unsigned)((n + kPolWave - 1) / kPolWave);
+    const auto kernel = is_split(p) ? policy_act_kernel<false, true, true> : policy_act_kernel<false, false, true>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kPolWave), policy_lds_bytes(p, true), stream, p, p.dev_params, p.dev_obs_scale, n, 0LL, obs,
+                       (const float *)nullptr, (uint64_t)0, (int64_t)0, act, logp, value, x, 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_pop_greedy(const ssg_policy &p, int members, int n, const double *obs, int32_t *act, float *logp, float *value, float *x,
+                                    hipStream_t stream)
+{
+    const unsigned grid = (unsigned)((n + kPolWave - 1) / kPolWave);
+    const auto kernel = is_split(p) ? policy_act_kernel<true, true, true> : policy_act_kernel<true, false, true>;
+    hipLaunchKernelGGL(kernel, dim3(grid, (unsigned)members), dim3(kPolWave), policy_lds_bytes(p, true), stream, p, p.dev_params, p.dev_obs_scale,
+                       n, 0LL, obs, (const float *)nullptr, (uint64_t)0, (int64_t)0, act, logp, value, x, ppo_packed_len(p));
     return hipGetLastError();
 }
 

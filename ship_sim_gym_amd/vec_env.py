@@ -607,12 +607,16 @@ class ShipVecEnv(*_BASES):
                              % (what, tuple(shape), self.device, t.dtype, tuple(t.shape), t.device))
         return C.c_void_p(t.data_ptr())
 
-    def policy_act(self, policy, seed=0, step=0, uniforms=None, x_out=None):
+    def policy_act(self, policy, seed=0, step=0, uniforms=None, x_out=None, greedy=False):
         """The policy forward + inverse-CDF sampling on the env's current `obs` (ssg_policy_act): returns (act int32 [N], logp [N],
         value [N], x [N, D] float32) device tensors.  uniforms: float32 [N] (e.g. torch.rand) or None = Philox keyed by (seed, step,
-        global env id).  x_out: a float32 [N, D] tensor to write the normalised observations into."""
+        global env id).  x_out: a float32 [N, D] tensor to write the normalised observations into.  greedy=True (ssg_policy_act_greedy):
+        the first action with the largest logit instead of a draw, and its logp; value and x are the sampling call's bit for bit, seed
+        and step are not used, and `uniforms` with it raises ValueError."""
         torch = _torch()
         self._check_policy(policy, "policy_act")
+        if greedy and uniforms is not None:
+            raise ValueError("policy_act: greedy=True reads no uniforms (pass one or the other)")
         n, D = self.num_envs, self.states_history
         up = self._f32_rows(uniforms, (n,), "policy_act uniforms") if uniforms is not None else None
         with torch.cuda.device(self.device):
@@ -622,6 +626,11 @@ class ShipVecEnv(*_BASES):
             x = x_out if x_out is not None else torch.empty((n, D), dtype=torch.float32, device=self.device)
             xp = self._f32_rows(x, (n, D), "policy_act x_out")
             pol = policy.to_native()
+            if greedy:
+                N.check(N.lib().ssg_policy_act_greedy(self._h, C.byref(pol), C.c_void_p(self.obs.data_ptr()), C.c_void_p(act.data_ptr()),
+                                                      C.c_void_p(logp.data_ptr()), C.c_void_p(val.data_ptr()), xp, self._stream()),
+                        self._h, "ssg_policy_act_greedy")
+                return act, logp, val, x
             N.check(N.lib().ssg_policy_act(self._h, C.byref(pol), C.c_void_p(self.obs.data_ptr()), up, int(seed), int(step),
                                            C.c_void_p(act.data_ptr()), C.c_void_p(logp.data_ptr()), C.c_void_p(val.data_ptr()), xp,
                                            self._stream()), self._h, "ssg_policy_act")
@@ -673,11 +682,14 @@ class ShipVecEnv(*_BASES):
         if self.num_envs % len(population):
             raise ValueError("%s: %d envs do not split into %d equal member slices" % (what, self.num_envs, len(population)))
 
-    def population_act(self, population, seed=0, step=0, uniforms=None, x_out=None):
+    def population_act(self, population, seed=0, step=0, uniforms=None, x_out=None, greedy=False):
         """policy_act with env e evaluated under member e // (N / P) of a NativePopulation (ssg_pop_act, one launch): returns (act
-        int32 [N], logp [N], value [N], x [N, D] float32) device tensors.  uniforms / x_out / Philox keying as policy_act."""
+        int32 [N], logp [N], value [N], x [N, D] float32) device tensors.  uniforms / x_out / Philox keying / greedy as policy_act
+        (greedy=True: ssg_pop_act_greedy)."""
         torch = _torch()
         self._check_population(population, "population_act")
+        if greedy and uniforms is not None:
+            raise ValueError("population_act: greedy=True reads no uniforms (pass one or the other)")
         n, D = self.num_envs, self.states_history
         up = self._f32_rows(uniforms, (n,), "population_act uniforms") if uniforms is not None else None
         with torch.cuda.device(self.device):
@@ -687,6 +699,11 @@ class ShipVecEnv(*_BASES):
             x = x_out if x_out is not None else torch.empty((n, D), dtype=torch.float32, device=self.device)
             xp = self._f32_rows(x, (n, D), "population_act x_out")
             pop = population.to_native()
+            if greedy:
+                N.check(N.lib().ssg_pop_act_greedy(self._h, C.byref(pop), C.c_void_p(self.obs.data_ptr()), C.c_void_p(act.data_ptr()),
+                                                   C.c_void_p(logp.data_ptr()), C.c_void_p(val.data_ptr()), xp, self._stream()),
+                        self._h, "ssg_pop_act_greedy")
+                return act, logp, val, x
             N.check(N.lib().ssg_pop_act(self._h, C.byref(pop), C.c_void_p(self.obs.data_ptr()), up, int(seed), int(step),
                                         C.c_void_p(act.data_ptr()), C.c_void_p(logp.data_ptr()), C.c_void_p(val.data_ptr()), xp,
                                         self._stream()), self._h, "ssg_pop_act")

@@ -34,6 +34,10 @@ coefficient then adapts per member against --kl-target, as RLlib's update_kl doe
 
 Logged per update: every member's episode_reward_mean (over the episodes that ended since the last perturbation); per perturbation:
 each exploit (member <- source) and each mutation (key, resample / perturb, old -> new).
+
+--eval-every U --eval-episodes E (default off): every U updates every member is evaluated greedily (the arg-max action) for E episodes
+per env on a second ShipVecEnv of its own (ship_sim_gym_amd/evaluate.py; the reference's train/rllib/rollout.py:8-26), so the training
+envs are not disturbed, and the table is printed.  The ranking stays by training episodes, the reference's reward_attr.
 """
 import argparse
 import os
@@ -72,6 +76,10 @@ def make_arg_parser():
     ap.add_argument("--max-grad-norm", type=float, default=0.0, help="global gradient-norm clip (PPO2: 0.5; 0 = off)")
     ap.add_argument("--separate-value", action="store_true",
                     help="every member has a value network of its own (RLlib's default vf_share_layers=False) instead of a shared body")
+    ap.add_argument("--eval-every", type=int, default=0, metavar="U",
+                    help="every U UPDATES evaluate every member greedily on a second env of its own and print it; 0 = off "
+                         "(the ranking stays by training episodes, the reference's reward_attr)")
+    ap.add_argument("--eval-episodes", type=int, default=1, metavar="E", help="episodes counted per env by each evaluation")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -102,12 +110,14 @@ def parse_args(argv=None):
         ap.error("--members, --envs-per-member, --updates, --horizon and --perturb-every must be >= 1")
     if a.kl_coeff < 0 or a.kl_target < 0 or a.vf_clip < 0 or a.max_grad_norm < 0:
         ap.error("--kl-coeff, --kl-target, --vf-clip and --max-grad-norm must be >= 0")
+    if a.eval_every < 0 or a.eval_episodes < 1:
+        ap.error("--eval-every must be >= 0 and --eval-episodes >= 1")
     return a
 
 
 def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every=5, seed=0, epochs=2, minibatches=4, lrs=None,
           pbt=True, device="cuda:0", log=print, return_details=False, kl_coeff=0.0, kl_target=0.01, vf_clip=0.0, max_grad_norm=0.0,
-          separate_value=False, mutate_schedule=False, max_epochs=30):
+          separate_value=False, mutate_schedule=False, max_epochs=30, eval_every=0, eval_episodes=1):
     import torch
     from ship_gym.config import EnvConfig, GameConfig
     from ship_sim_gym_amd.population import NativePopulation, PBTScheduler, PopulationPPO, reference_mutations
@@ -126,6 +136,8 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
     saved = {k: getattr(GameConfig, k) for k in ("FPS", "SPEED", "DEBUG", "BOUNDS")}
     try:  # (game_configuration writes the GameConfig class, as the reference's does; the env reads it once, here)
         env = ShipVecEnv(P * n, game_configuration(speed=30, fps=1000, debug=False), EnvConfig, device=device, n_maps=64)
+        # the held-out run's env (train/rllib/rollout.py:8-26): evaluation resets and steps it, the training envs keep their episodes
+        eval_env = ShipVecEnv(P * min(n, 256), GameConfig, EnvConfig, device=device, n_maps=64) if eval_every else None
     finally:
         for k, v in saved.items():
             setattr(GameConfig, k, v)
@@ -141,7 +153,11 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
     window = torch.zeros((P, 3), dtype=torch.int64, device=dev)  # episodes since the last perturbation
     scores = [float("-inf")] * P
     samples = horizon * n
-    out, history, exploits = None, [], []
+    out, history, exploits, evals = None, [], [], []
+    evaluator = None
+    if eval_env is not None:
+        from ship_sim_gym_amd.evaluate import NativeEvaluator, format_table
+        evaluator = NativeEvaluator(eval_env)
     # the schedule: common ints (one launch shape for everyone, as before) or one entry per member
     per_member = mutate_schedule or isinstance(epochs, (list, tuple)) or isinstance(minibatches, (list, tuple))
     if mutate_schedule:
@@ -172,6 +188,10 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
         scores = [w[m][0] / 100.0 / w[m][2] if w[m][2] else scores[m] for m in range(P)]
         history.append(list(scores))
         log("update %d  episode_reward_mean %s" % (u, " ".join("%d:%.3f" % (m, s) for m, s in enumerate(scores))))
+        if evaluator is not None and u % eval_every == 0:  # (printed only: PBT ranks by training episodes, as the reference does)
+            r = evaluator.evaluate(pop, eval_episodes, greedy=True)
+            evals.append((u, r["per_member"].cpu().tolist()))
+            log("update %d  greedy evaluation (%d envs x %d episodes per member)\n%s" % (u, eval_env.num_envs // P, eval_episodes, format_table(r)))
         if pbt and sched.due(u):
             hp = {"lambda": ppo.lam, "clip_param": ppo.clip, "lr": ppo.lr}
             if mutate_schedule:
@@ -204,7 +224,9 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
                "hparams": {"lambda": list(ppo.lam), "clip_param": list(ppo.clip), "lr": list(ppo.lr),
                            "num_sgd_iter": list(iters) if per_member else [int(epochs)] * P,
                            "sgd_minibatch_size": list(sizes) if per_member else [chunk_split(samples, minibatches)[0]] * P},
-               "member_steps": list(ppo.member_steps), "kl_coef": ppo.kl_coef.detach().cpu().tolist()}
+               "member_steps": list(ppo.member_steps), "kl_coef": ppo.kl_coef.detach().cpu().tolist(), "evaluations": evals}
+    if eval_env is not None:
+        eval_env.close()
     env.close()
     return (history, details) if return_details else history
 
@@ -214,7 +236,7 @@ def main(argv=None):
     train(members=a.members, envs_per_member=a.envs_per_member, updates=a.updates, horizon=a.horizon, perturb_every=a.perturb_every,
           seed=a.seed, epochs=a.epochs, minibatches=a.minibatches, lrs=a.lrs, pbt=a.pbt, device=a.device, kl_coeff=a.kl_coeff,
           kl_target=a.kl_target, vf_clip=a.vf_clip, max_grad_norm=a.max_grad_norm, separate_value=a.separate_value,
-          mutate_schedule=a.mutate_schedule, max_epochs=a.max_epochs)
+          mutate_schedule=a.mutate_schedule, max_epochs=a.max_epochs, eval_every=a.eval_every, eval_episodes=a.eval_episodes)
 
 
 if __name__ == "__main__":

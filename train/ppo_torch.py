@@ -5,6 +5,7 @@ stable-baselines (absent from this image).  The env side is the only point: obse
 leave the GPU; the policy is a small MLP in fp32.
 
     python train/ppo_torch.py --envs 4096 --updates 20 [--mode eager|graph|pingpong|native] [--update torch|native] [--separate-value]
+                              [--eval-every U --eval-episodes E]
 
 Four ways to run the rollout loop (the reference's `model.learn` -> runner.run(): one `env.step(actions)` per policy
 forward, train/stable_baselines/ppo.py:84-100,122-123) — same arithmetic, same results bit for bit:
@@ -29,6 +30,10 @@ Two ways to run the update after each rollout (GAE, advantage normalisation, epo
                calls, on the packed parameters the native rollout reads (no refresh); the minibatches are the same randperm chunks,
                drawn from the same generator.  Same loss, same conventions; the parameters agree with the torch update's to f32
                rounding (the module is loaded from the packed buffer at the end, NativePPO.load_into).
+
+``--eval-every U`` (``--mode native`` only; default off): every U updates the current policy is evaluated greedily for
+``--eval-episodes`` episodes per env on a second ShipVecEnv of its own (ship_sim_gym_amd/evaluate.py; the reference's
+train/rllib/rollout.py:8-26), so the training envs are not disturbed, and the result is printed.
 
 The sampling noise of a whole rollout is drawn in one call before it (uniforms [horizon, envs], inverse-CDF sampling inside
 the step), so a captured step holds no random-number generator state and replays exactly what the eager loop computes.
@@ -197,8 +202,13 @@ def rollout(shards, horizon, mode, gen, policy=None):
 
 
 def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, gamma=0.99, lam=0.95, clip=0.2,
-          device="cuda:0", seed=0, log=print, mode="eager", return_details=False, env_kw=None, update="torch", separate_value=False):
+          device="cuda:0", seed=0, log=print, mode="eager", return_details=False, env_kw=None, update="torch", separate_value=False,
+          eval_every=0, eval_episodes=1, eval_envs=None):
     assert mode in ("eager", "graph", "pingpong", "native")
+    if eval_every and mode != "native":
+        raise ValueError("eval_every evaluates the native policy on the device: it needs mode='native' (got mode=%r)" % (mode,))
+    if eval_every < 0 or eval_episodes < 1:
+        raise ValueError("eval_every must be >= 0 and eval_episodes >= 1")
     if update not in ("torch", "native"):
         raise ValueError("update must be 'torch' or 'native' (got %r)" % (update,))
     if update == "native" and mode != "native":
@@ -217,6 +227,11 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         sh.env.reset_tensor()
     policy = NativePolicy.from_actor_critic(net, shards[0].scale) if mode == "native" else None
     ppo = NativePPO(policy, shards[0].env, lr=lr, clip=clip) if update == "native" else None
+    evaluator, evals = None, []
+    if eval_every:  # a second env of its own: evaluation resets and steps it, the training envs keep their episodes
+        from ship_sim_gym_amd.evaluate import NativeEvaluator
+        eval_env = ShipVecEnv(int(eval_envs or min(envs, 1024)), GameConfig, EnvConfig, device=device, n_maps=64, **dict(env_kw or {}))
+        evaluator = NativeEvaluator(eval_env)
     if mode in ("graph", "pingpong"):
         # one eager warm-up step per shard OUTSIDE the capture (prepares the library's kernels and hipBLASLt's workspaces), then the
         # envs start over; the capture itself runs nothing
@@ -283,6 +298,13 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         history.append((u, mean_ret, goals_per_ep, float(b["rew"].mean())))
         log("update %3d  episodes %8d  mean return so far %+.3f  goals/episode %.3f  mean step reward %+.4f" % (
             u, st["episodes"], mean_ret, goals_per_ep, history[-1][3]))
+        if evaluator is not None and (u + 1) % eval_every == 0:
+            r = evaluator.evaluate(policy, eval_episodes, greedy=True)
+            evals.append((u, {k: (v[0] if hasattr(v, "__len__") else v) for k, v in r.items() if k not in ("per_env", "per_member")}))
+            log("update %3d  greedy evaluation (%d envs x %d episodes): mean return %+.3f  length %.1f  goals/episode %.3f  "
+                "collided %.2f  out of bounds %.2f  timed out %.2f" % (
+                    u, evaluator.env.num_envs, eval_episodes, r["return_mean"][0], r["length_mean"][0], r["goals_per_episode"][0],
+                    r["collision_rate"][0], r["out_of_bounds_rate"][0], r["max_steps_rate"][0]))
     torch.cuda.synchronize()
     t_all = time.perf_counter() - t_all0
     if ppo is not None:
@@ -293,7 +315,9 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
     details = {"mode": mode, "rollout_env_steps_per_s": steps / max(t_roll, 1e-9), "training_env_steps_per_s": steps / max(t_all, 1e-9),
                "rollout_us_per_step": t_roll * 1e6 / (horizon * updates), "rollout_seconds": t_roll, "update_seconds": t_upd, "total_seconds": t_all,
                "snapshots": snapshots, "final_state": [env_columns(sh.env) for sh in shards] if return_details is True else None,
-               "params": [p.detach().clone() for p in net.parameters()] if return_details is True else None}
+               "params": [p.detach().clone() for p in net.parameters()] if return_details is True else None, "evaluations": evals}
+    if evaluator is not None:
+        evaluator.env.close()
     for sh in shards:
         sh.graph = None
         sh.env.close()
@@ -310,6 +334,9 @@ def make_arg_parser():
                     help="where GAE and the PPO update run: eager PyTorch, or on the device (needs --mode native)")
     ap.add_argument("--separate-value", action="store_true",
                     help="a value network of its own (SB's MlpPolicy, RLlib's vf_share_layers=False) instead of a shared body; every --mode")
+    ap.add_argument("--eval-every", type=int, default=0, metavar="U",
+                    help="every U updates evaluate the policy greedily on a second env of its own (needs --mode native); 0 = off")
+    ap.add_argument("--eval-episodes", type=int, default=1, metavar="E", help="episodes counted per env by each evaluation")
     return ap
 
 
@@ -317,6 +344,10 @@ def parse_args(argv=None):
     """make_arg_parser().parse_args, refusing --update native without --mode native."""
     ap = make_arg_parser()
     a = ap.parse_args(argv)
+    if a.eval_every < 0 or a.eval_episodes < 1:
+        ap.error("--eval-every must be >= 0 and --eval-episodes >= 1")
+    if a.eval_every and a.mode != "native":
+        ap.error("--eval-every needs --mode native (the evaluation runs the native policy on the device)")
     if a.update == "native" and a.mode != "native":
         ap.error("--update native needs --mode native (the update runs on the native policy's packed parameters)")
     return a
@@ -324,4 +355,5 @@ def parse_args(argv=None):
 
 if __name__ == "__main__":
     a = parse_args()
-    train(envs=a.envs, updates=a.updates, horizon=a.horizon, mode=a.mode, update=a.update, separate_value=a.separate_value)
+    train(envs=a.envs, updates=a.updates, horizon=a.horizon, mode=a.mode, update=a.update, separate_value=a.separate_value,
+          eval_every=a.eval_every, eval_episodes=a.eval_episodes)
