@@ -666,14 +666,15 @@ int ssg_ppo_update_ext(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hpara
  * Workspace: ssg_pop_workspace_nbytes bytes, 256-byte aligned; ssg_pop_gae leaves f32 [P][4] advantage statistics (mean, std + adv_eps,
  * its inverse, 0) at its start, per member over that member's K*n samples, which ssg_pop_update reads.  dev_adam_mv: f32 [P][2L].
  * The extended loss terms are per member too (ssg_pop_update_ext below), and so may the epochs and the minibatch count be
- * (ssg_pop_update_sched).  Out of scope: per-member batch sizes (train_batch_size: unequal env slices or rollout lengths), PPO2's
- * per-minibatch advantage normalisation, populations spanning handles or GPUs, per-member architectures.
+ * (ssg_pop_update_sched), and the batch size (train_batch_size) as a member's share of the handle's envs: unequal slices,
+ * ssg_pop_set_slices below.  Out of scope: unequal rollout lengths, PPO2's per-minibatch advantage normalisation, populations spanning
+ * handles or GPUs, per-member architectures.
  * ------------------------------------------------------------------------------------------------- */
 #define SSG_POP_MAX_MEMBERS 256
 #define SSG_POP_TABLE_FLOATS(n_members, n_steps) ((size_t)(n_members) * 8u * (size_t)(1 + (n_steps)))
 typedef struct ssg_population {
     uint32_t struct_size;        /* sizeof(ssg_population) */
-    int32_t n_members;           /* P: 1..SSG_POP_MAX_MEMBERS, a divisor of the handle's n_envs */
+    int32_t n_members;           /* P: 1..SSG_POP_MAX_MEMBERS, a divisor of the handle's n_envs (or the P of ssg_pop_set_slices) */
     int32_t obs_dim;             /* the shape, as in ssg_policy */
     int32_t hidden;
     int32_t n_hidden_layers;
@@ -734,7 +735,8 @@ int ssg_pop_gae(ssg_handle *h, const ssg_population *pop, const float *dev_table
  * ssg_pop_pack_hparams' output for table_steps >= epochs*chunks Adam steps (its step0 is the population's Adam step count before this
  * call).  dev_stats (nullable): f32 [P][epochs*chunks][4].  Needs ssg_pop_gae's statistics in the workspace.  No floating-point
  * atomics; member m's parameters, moments and stats are bitwise those of ssg_ppo_update on its slice.  SSG_ERR_BAD_ARG (nothing
- * launched) for a bad record, NULL pointers, K < 1, epochs < 1, minibatches < 1, table_steps too small or a workspace too small. */
+ * launched) for a bad record, NULL pointers, K < 1, epochs < 1, minibatches < 1, table_steps too small or a workspace too small — and,
+ * like ssg_pop_update_ext, while slices are bound to the handle (ssg_pop_set_slices: the update then runs through ssg_pop_update_sched). */
 int ssg_pop_update(ssg_handle *h, const ssg_population *pop, const float *dev_table, int table_steps, int K, const float *dev_x,
                    const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret, const int64_t *dev_perm,
                    int epochs, int minibatches, float *dev_adam_mv, float *dev_stats /* nullable */, void *dev_workspace,
@@ -808,12 +810,63 @@ int ssg_pop_pack_hparams_steps(int n_members, const ssg_ppo_hparams *hparams, co
  * parameters, moments, stats rows and coefficient are bitwise those of ssg_ppo_update(_ext) on its slice with epochs[m] and
  * minibatches[m]; with equal entries the call computes what ssg_pop_update(_ext) computes.  SSG_ERR_BAD_ARG (nothing launched) as
  * ssg_pop_update / ssg_pop_update_ext, and for NULL epochs / minibatches / dev_sched, an entry < 1, perm_epochs < max epochs or
- * table_steps < n_launches. */
+ * table_steps < n_launches.  With unequal slices bound (ssg_pop_set_slices): see there for dev_sched, dev_perm and the workspace. */
 int ssg_pop_update_sched(ssg_handle *h, const ssg_population *pop, const ssg_pop_ext *ext /* nullable: the plain loss */,
                          const float *dev_table, int table_steps, const int32_t *dev_sched, const int32_t *epochs,
                          const int32_t *minibatches, int perm_epochs, int K, const float *dev_x, const int32_t *dev_act,
                          const float *dev_logp, const float *dev_adv, const float *dev_ret, const int64_t *dev_perm, float *dev_adam_mv,
                          float *dev_stats /* nullable */, void *dev_workspace, size_t workspace_nbytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Per-member batch sizes: unequal env slices (ABI 9 addition)
+ * The reference's sixth mutated hyper-parameter is train_batch_size (train/rllib/pbt.py:42, drawn from {10000, 20000, 40000} at :69-70).
+ * A population may be laid out over the handle's envs in contiguous slices of unequal size: member m owns envs [o_m, o_m + n_m), o_0 = 0,
+ * o_{m+1} = o_m + n_m, every n_m >= 1, sum n_m == n_envs.  All members still roll out the same K steps and update at the same moment; a
+ * member's batch is K * n_m samples (its SHARE of the handle's K * n_envs, not an absolute count).  Envs are fungible: the layout may
+ * be re-bound between updates without touching env state.
+ *
+ * The layout is bound to the handle (ssg_pop_set_slices), as the terminal-observation buffer and the map bank are.  While it is bound:
+ *  - a population whose n_members equals the bound P follows the slices and the divisor check does not apply; any other P is
+ *    SSG_ERR_BAD_ARG and nothing is launched — for every ssg_pop_* entry point that takes the handle, and for ssg_eval_reduce with
+ *    n_members > 1;
+ *  - ssg_pop_act, ssg_pop_act_greedy, ssg_pop_rollout, ssg_pop_dist, ssg_pop_evaluate: env e runs under the member whose slice holds
+ *    it, the Philox counter stays the global env id, still one policy launch (grid: workgroups of the largest slice x P; a workgroup
+ *    past its member's n_m leaves at once);
+ *  - ssg_pop_gae: member m walks its own columns, its partial sums are laid out as a single run over n_m envs lays them out (256-env
+ *    blocks from o_m) and its statistics divide by K * n_m; SSG_ERR_BAD_ARG when some K * n_m < 2;
+ *  - the update runs through ssg_pop_update_sched only (it already gives every member its own M, G and step count): ssg_pop_update
+ *    and ssg_pop_update_ext return SSG_ERR_BAD_ARG.  dev_sched must come from ssg_pop_pack_schedule_samples with samples[m] = K * n_m;
+ *    member m's sample i = t*n_m + e is row t*N + o_m + e; dev_perm is a FLAT int64 buffer: member m's block is perm_epochs rows of
+ *    K * n_m member-local indices, the blocks in member order, nothing padded to the widest member.  The workspace is
+ *    ssg_pop_workspace_nbytes' for samples_per_member = max K * n_m and max_minibatch = max C_m;
+ *  - ssg_pop_episode_stats and ssg_eval_reduce sum each member's own rows; ssg_pop_exploit does not depend on the slices.
+ * Contract: member m's rollout rows, advantages, statistics, parameters, moments, stats rows and KL coefficient are bit for bit what
+ * ssg_policy_act, ssg_rollout_policy, ssg_ppo_gae and ssg_ppo_update(_ext) compute on a handle of n_m envs with env_id_base + o_m.  With
+ * equal slices bound every result is bit for bit what it is with nothing bound; with nothing bound nothing changes.
+ * ------------------------------------------------------------------------------------------------- */
+#define SSG_POP_SLICE_ROW 4
+
+/* Replaces nothing (host only; ray hands every trial its own train_batch_size, train/rllib/pbt.py:69-70).  Packs the slices table:
+ * SSG_POP_SLICE_ROW int32 per member, row m = {o_m, n_m, the 256-env blocks of n_m, 0}.  SSG_ERR_BAD_ARG for NULL pointers, n_members
+ * outside 1..SSG_POP_MAX_MEMBERS, an entry < 1, a sum beyond 2^31-1 or out_ints < SSG_POP_SLICE_ROW * n_members. */
+int ssg_pop_pack_slices(int n_members, const int32_t *n_envs_per_member, int32_t *out, size_t out_ints);
+
+/* Replaces nothing (memory binding).  Binds the layout to the handle: the handle keeps a host copy of the P sizes and the caller's
+ * device pointer to the packed table (ssg_pop_pack_slices' output for the same sizes; the caller owns that memory and keeps it alive
+ * while the layout is bound).  n_members == 0 or a NULL pointer unbinds.  SSG_ERR_BAD_ARG (the binding stays as it was): a sum
+ * different from the handle's n_envs, an entry < 1, n_members outside 1..SSG_POP_MAX_MEMBERS. */
+int ssg_pop_set_slices(ssg_handle *h, int n_members, const int32_t *n_envs_per_member /* host [P] */,
+                       const int32_t *dev_slices /* device copy of the packed table */);
+
+/* Replaces nothing (introspection).  *n_members = the bound P (0: nothing bound); out (nullable) receives the P sizes. */
+int ssg_pop_get_slices(const ssg_handle *h, int *n_members, int32_t *out /* nullable: int32 [P] */);
+
+/* Replaces nothing (host only).  ssg_pop_pack_schedule with a sample count per member (samples[m] = K * n_m): C_m, chunks_m, M and G
+ * derive from the member's own count.  Header row m also carries, in entries [4..5], the int64 sum of samples[0..m): member m's block
+ * of the flat permutation buffer starts perm_epochs times that many entries in.  With all counts equal the records, and entries
+ * [0..3] of the header rows, are those of ssg_pop_pack_schedule.  Refusals as ssg_pop_pack_schedule (NULL samples, an entry < 1). */
+int ssg_pop_pack_schedule_samples(int n_members, const int64_t *samples /* [P]: K*n_m */, const int32_t *epochs, const int32_t *minibatches,
+                                  int32_t *out /* nullable */, size_t out_ints, int32_t *steps_out /* nullable */, int32_t *n_launches_out);
 
 /* Replaces: PopulationBasedTraining's exploit step (train/rllib/pbt.py:29-43: a bottom-quantile trial restores a top-quantile trial's
  * checkpoint), on the device: member m takes the parameter row AND the Adam moments of member src[m] (host array int32 [P];

@@ -32,9 +32,11 @@ def pop_table_floats(n_members, n_steps):
     return int(n_members) * 8 * (1 + int(n_steps))
 
 
+POP_SLICE_ROW = 4  # int32 per member of the slices table (ssg_pop_pack_slices): first env, envs, 256-env blocks, 0
 POP_SCHED_ROW = 8  # int32 per member of a schedule table's header, and per member and launch of its records
 # a record's fields (include/shipsim.h): the int64 offset takes entries 0 and 1
 SCHED_M, SCHED_G, SCHED_FIRST, SCHED_ACTIVE, SCHED_INVM = 2, 3, 4, 5, 6
+SCHED_HDR_PREFIX = 4  # a header row's int64 (entries 4, 5) of ssg_pop_pack_schedule_samples: the samples of the members before
 
 
 def pop_sched_ints(n_members, n_launches):
@@ -62,6 +64,7 @@ EXPORTS = (
     "ssg_ppo_dist", "ssg_ppo_grad_ext", "ssg_ppo_update_ext", "ssg_pop_dist", "ssg_pop_update_ext",
     "ssg_pop_pack_schedule", "ssg_pop_pack_hparams_steps", "ssg_pop_update_sched",
     "ssg_policy_act_greedy", "ssg_pop_act_greedy", "ssg_evaluate", "ssg_pop_evaluate", "ssg_eval_reduce", "ssg_eval_account",
+    "ssg_pop_pack_slices", "ssg_pop_set_slices", "ssg_pop_get_slices", "ssg_pop_pack_schedule_samples",
 )
 
 
@@ -218,6 +221,10 @@ def lib():
     L.ssg_pop_pack_hparams_steps.argtypes = [C.c_int, hp, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_float), C.c_size_t]
     L.ssg_pop_update_sched.argtypes = [vp, pp, qp, vp, C.c_int, vp, i32p, i32p, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                        C.c_size_t, vp]
+    L.ssg_pop_pack_slices.argtypes = [C.c_int, i32p, i32p, C.c_size_t]
+    L.ssg_pop_set_slices.argtypes = [vp, C.c_int, i32p, vp]
+    L.ssg_pop_get_slices.argtypes = [vp, ip, i32p]
+    L.ssg_pop_pack_schedule_samples.argtypes = [C.c_int, C.POINTER(C.c_int64), i32p, i32p, i32p, C.c_size_t, i32p, i32p]
     L.ssg_policy_act_greedy.argtypes = [vp, C.POINTER(Policy), vp, vp, vp, vp, vp, vp]
     L.ssg_pop_act_greedy.argtypes = [vp, pp, vp, vp, vp, vp, vp, vp]
     L.ssg_evaluate.argtypes = [vp, C.POINTER(Policy), C.POINTER(Eval), vp]

@@ -54,6 +54,10 @@ struct ssg_handle {
     bool host_ev_made[kHostSlots] = {};
     bool policy_prepared = false; // ssg_policy_act / ssg_rollout_policy: the policy kernel's dynamic-LDS limit is set
     bool ppo_prepared = false;    // ssg_ppo_grad / ssg_ppo_update: the gradient kernel's dynamic-LDS limit is set
+    // ssg_pop_set_slices: the members' env counts (empty: nothing bound), the caller's device table, the largest and smallest slice
+    std::vector<int32_t> pop_sizes;
+    const int32_t *dev_slices = nullptr;
+    int slice_max = 0, slice_min = 0;
     std::string err;
 };
 
@@ -1348,6 +1352,23 @@ static bool pop_shape_ok(const ssg_population *pop)
     return check_policy_shape(&p) != 0;
 }
 
+// P members against the handle's layout: the slices bound to it (ssg_pop_set_slices), else the equal split
+static int check_members(ssg_handle *h, int P, const char *what)
+{
+    char buf[200];
+    if (!h->pop_sizes.empty()) {
+        if ((int)h->pop_sizes.size() == P) return SSG_OK;
+        std::snprintf(buf, sizeof buf, ": %d members, but slices for %d members are bound to the handle (ssg_pop_set_slices)", P,
+                      (int)h->pop_sizes.size());
+        return fail(h, SSG_ERR_BAD_ARG, std::string(what) + buf);
+    }
+    if (h->cfg.n_envs % P != 0) {
+        std::snprintf(buf, sizeof buf, ": the handle's %d envs do not split into %d equal member slices", h->cfg.n_envs, P);
+        return fail(h, SSG_ERR_BAD_ARG, std::string(what) + buf);
+    }
+    return SSG_OK;
+}
+
 // the record against the handle: shape, member count, pointers
 static int check_population(ssg_handle *h, const ssg_population *pop, const char *what)
 {
@@ -1355,14 +1376,15 @@ static int check_population(ssg_handle *h, const ssg_population *pop, const char
     if (!pop) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL population");
     if (pop->struct_size != sizeof(ssg_population)) return fail(h, SSG_ERR_BAD_ARG, w + ": ssg_population.struct_size != sizeof(ssg_population)");
     if (pop->n_members < 1 || pop->n_members > SSG_POP_MAX_MEMBERS) return fail(h, SSG_ERR_BAD_ARG, w + ": n_members must be in 1..SSG_POP_MAX_MEMBERS");
-    if (h->cfg.n_envs % pop->n_members != 0) {
-        char buf[160];
-        std::snprintf(buf, sizeof buf, ": the handle's %d envs do not split into %d equal member slices", h->cfg.n_envs, pop->n_members);
-        return fail(h, SSG_ERR_BAD_ARG, w + buf);
-    }
+    const int rc = check_members(h, pop->n_members, what);
+    if (rc != SSG_OK) return rc;
     const ssg_policy p = pop_policy(*pop);
     return check_policy(h, &p, what);
 }
+
+// the slices table for a population that passed check_members (NULL: equal slices), and the launch's width
+static const int32_t *pop_slices(const ssg_handle *h) { return h->pop_sizes.empty() ? nullptr : h->dev_slices; }
+static int pop_width(const ssg_handle *h, int P) { return h->pop_sizes.empty() ? h->cfg.n_envs / P : h->slice_max; }
 
 // ABI 9 additions: the extended update.  Order of the refusals as for a population: no handle (BAD_ARG), no state blob (NOT_BOUND),
 // everything the host can judge (BAD_ARG), and only then the device.
@@ -1492,8 +1514,8 @@ int ssg_pop_act(ssg_handle *h, const ssg_population *pop, const double *dev_obs,
     if (rc == SSG_OK) rc = prepare_policy(h);
     if (rc != SSG_OK) return rc;
     const int P = pop->n_members;
-    hipError_t e = ssg::launch_policy_pop(pop_policy(*pop), P, h->cfg.n_envs / P, h->cfg.env_id_base, dev_obs, dev_uniform, seed, step,
-                                          dev_actions, dev_logp, dev_value, dev_x, static_cast<hipStream_t>(stream));
+    hipError_t e = ssg::launch_policy_pop(pop_policy(*pop), P, pop_width(h, P), h->cfg.env_id_base, dev_obs, dev_uniform, seed, step,
+                                          dev_actions, dev_logp, dev_value, dev_x, static_cast<hipStream_t>(stream), pop_slices(h));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population policy launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
@@ -1510,8 +1532,8 @@ int ssg_pop_act_greedy(ssg_handle *h, const ssg_population *pop, const double *d
     if (rc == SSG_OK) rc = prepare_policy(h);
     if (rc != SSG_OK) return rc;
     const int P = pop->n_members;
-    hipError_t e = ssg::launch_policy_pop_greedy(pop_policy(*pop), P, h->cfg.n_envs / P, dev_obs, dev_actions, dev_logp, dev_value, dev_x,
-                                                 static_cast<hipStream_t>(stream));
+    hipError_t e = ssg::launch_policy_pop_greedy(pop_policy(*pop), P, pop_width(h, P), dev_obs, dev_actions, dev_logp, dev_value, dev_x,
+                                                 static_cast<hipStream_t>(stream), pop_slices(h));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population policy launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
@@ -1538,13 +1560,14 @@ int ssg_pop_rollout(ssg_handle *h, const ssg_population *pop, int K, const float
     if (rc != SSG_OK) return rc;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const ssg_policy pol = pop_policy(*pop);
-    const int P = pop->n_members, n = h->cfg.n_envs / P;
+    const int P = pop->n_members, n = pop_width(h, P);
+    const int32_t *slices = pop_slices(h);
     const size_t S = (size_t)step_stride_envs, D = (size_t)pol.obs_dim;
     for (int k = 0; k < K; ++k) { // ssg_rollout_policy's sequence: one policy launch for the whole population, then the step
         const size_t r = (size_t)k * S;
         hipError_t e = ssg::launch_policy_pop(pol, P, n, h->cfg.env_id_base, dev_obs, dev_uniform_KN ? dev_uniform_KN + r : nullptr, seed,
                                               step0 + k, dev_act_KN + r, dev_logp_KN + r, dev_value_KN + r,
-                                              dev_x_KND ? dev_x_KND + r * D : nullptr, st);
+                                              dev_x_KND ? dev_x_KND + r * D : nullptr, st, slices);
         if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population policy launch: ") + hipGetErrorString(e));
         rc = ssg_rollout_traj(h, dev_act_KN + r, 1, dev_obs, dev_reward_KN + r, dev_done_KN + r, dev_flags_KN ? dev_flags_KN + r : nullptr, 0,
                               stream);
@@ -1552,7 +1575,7 @@ int ssg_pop_rollout(ssg_handle *h, const ssg_population *pop, int K, const float
     }
     if (dev_last_value) {
         hipError_t e = ssg::launch_policy_pop(pol, P, n, h->cfg.env_id_base, dev_obs, nullptr, seed, step0 + K, nullptr, nullptr,
-                                              dev_last_value, nullptr, st);
+                                              dev_last_value, nullptr, st, slices);
         if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population policy launch: ") + hipGetErrorString(e));
     }
     return SSG_OK;
@@ -1593,13 +1616,14 @@ int ssg_pop_gae(ssg_handle *h, const ssg_population *pop, const float *dev_table
     if (rc != SSG_OK) return rc;
     if (!dev_table || !dev_reward_KN || !dev_done_KN || !dev_value_KN || !dev_last_value || !dev_adv_KN || !dev_ret_KN)
         return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_gae: NULL table, reward, done, value, last value, adv or ret buffer");
-    const int P = pop->n_members, N = h->cfg.n_envs, n = N / P;
-    if (K < 1 || (long long)K * n < 2) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_gae: K must be >= 1 and K * (n_envs / n_members) >= 2");
+    const int P = pop->n_members, N = h->cfg.n_envs, n = pop_width(h, P), n_min = pop_slices(h) ? h->slice_min : n;
+    if (K < 1 || (long long)K * n_min < 2)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_gae: K must be >= 1 and K * (a member's envs) >= 2 for every member");
     rc = check_workspace(h, dev_workspace, workspace_nbytes, pop_need_gae(P, n), "ssg_pop_gae");
     if (rc == SSG_OK) rc = check_ready(h, false);
     if (rc != SSG_OK) return rc;
     hipError_t e = ssg::launch_pop_gae(P, K, N, dev_table, dev_reward_KN, dev_done_KN, dev_value_KN, dev_last_value, dev_adv_KN, dev_ret_KN,
-                                       dev_workspace, static_cast<hipStream_t>(stream));
+                                       dev_workspace, static_cast<hipStream_t>(stream), pop_slices(h), n);
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population gae launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
@@ -1614,7 +1638,9 @@ static int check_pop_update(ssg_handle *h, const ssg_policy *pol, int P, const f
     const std::string w(what);
     if (K < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": K < 1");
     const int N = h->cfg.n_envs;
-    const long long n = (long long)K * (N / P); // samples per member
+    if (pop_slices(h) && !sched)
+        return fail(h, SSG_ERR_BAD_ARG, w + ": slices are bound to the handle (ssg_pop_set_slices): the update runs through ssg_pop_update_sched");
+    const long long n = (long long)K * (N / P); // samples per member (unequal slices: unused, see ssg_pop_update_sched)
     int rc = check_batch(h, n, batch, dev_perm, what);
     if (rc != SSG_OK) return rc;
     if (!dev_table || !dev_adam_mv) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_table or dev_adam_mv");
@@ -1672,7 +1698,8 @@ int ssg_pop_dist(ssg_handle *h, const ssg_population *pop, int K, const float *d
     if (rc == SSG_OK) rc = prepare_policy(h);
     if (rc != SSG_OK) return rc;
     const int P = pop->n_members, N = h->cfg.n_envs;
-    hipError_t e = ssg::launch_policy_dist(pop_policy(*pop), P, N / P, N, K, dev_x, dev_logp_all, static_cast<hipStream_t>(stream));
+    hipError_t e = ssg::launch_policy_dist(pop_policy(*pop), P, pop_width(h, P), N, K, dev_x, dev_logp_all, static_cast<hipStream_t>(stream),
+                                           pop_slices(h));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population dist launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
@@ -1720,12 +1747,15 @@ int ssg_pop_update_ext(ssg_handle *h, const ssg_population *pop, const ssg_pop_e
 
 // The schedule of `members` members over n samples each: steps / launches / the longest chunk, and (out != NULL) the table.  false: an
 // entry < 1 or a step count that does not fit an int32.
-static bool pop_schedule(int members, long long n, const int32_t *epochs, const int32_t *minibatches, int32_t *out, int32_t *steps_out,
-                         long long *n_launches, long long *Cmax)
+// samples (nullable): a sample count per member in place of n (ssg_pop_pack_schedule_samples; every entry >= 1) — the header rows then
+// carry the prefix sums at SH_PREFIX.
+static bool pop_schedule(int members, long long n_all, const int32_t *epochs, const int32_t *minibatches, int32_t *out, int32_t *steps_out,
+                         long long *n_launches, long long *Cmax, const int64_t *samples = nullptr)
 {
     long long launches = 0, cmax = 0;
     for (int m = 0; m < members; ++m) {
         if (epochs[m] < 1 || minibatches[m] < 1) return false;
+        const long long n = samples ? (long long)samples[m] : n_all;
         const Chunking ck = chunking(n, minibatches[m]);
         const long long steps = (long long)epochs[m] * ck.chunks;
         if (steps > 0x7fffffffll || ck.C > 0x7fffffffll) return false;
@@ -1738,7 +1768,9 @@ static bool pop_schedule(int members, long long n, const int32_t *epochs, const 
     if (!out) return true;
     const size_t R = ssg::kPopSchedRow;
     std::memset(out, 0, SSG_POP_SCHED_INTS(members, launches) * sizeof(int32_t));
+    long long prefix = 0;
     for (int m = 0; m < members; ++m) {
+        const long long n = samples ? (long long)samples[m] : n_all;
         const Chunking ck = chunking(n, minibatches[m]);
         const long long steps = (long long)epochs[m] * ck.chunks;
         int32_t *hdr = out + (size_t)m * R;
@@ -1746,6 +1778,8 @@ static bool pop_schedule(int members, long long n, const int32_t *epochs, const 
         hdr[ssg::SH_CHUNKS] = (int32_t)ck.chunks;
         hdr[ssg::SH_C] = (int32_t)ck.C;
         hdr[ssg::SH_EPOCHS] = epochs[m];
+        if (samples) std::memcpy(hdr + ssg::SH_PREFIX, &prefix, sizeof prefix);
+        prefix += n;
         for (long long j = 0; j < steps; ++j) {
             const long long ep = j / ck.chunks, b0 = (j - ep * ck.chunks) * ck.C, M = std::min(ck.C, n - b0), off = ep * n + b0;
             int32_t *rec = out + ((size_t)(1 + j) * (size_t)members + (size_t)m) * R;
@@ -1774,6 +1808,91 @@ int ssg_pop_pack_schedule(int n_members, int64_t samples_per_member, const int32
     if (out_ints < SSG_POP_SCHED_INTS(n_members, launches))
         return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_schedule: out_ints < SSG_POP_SCHED_INTS(n_members, n_launches)");
     pop_schedule(n_members, samples_per_member, epochs, minibatches, out, steps_out, &launches, &cmax);
+    return SSG_OK;
+}
+
+int ssg_pop_pack_schedule_samples(int n_members, const int64_t *samples, const int32_t *epochs, const int32_t *minibatches, int32_t *out,
+                                  size_t out_ints, int32_t *steps_out, int32_t *n_launches_out)
+{
+    if (!samples || !epochs || !minibatches || !n_launches_out || n_members < 1 || n_members > SSG_POP_MAX_MEMBERS)
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_schedule_samples: NULL samples, epochs, minibatches or n_launches_out, or n_members out of range");
+    for (int m = 0; m < n_members; ++m)
+        if (samples[m] < 1) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_schedule_samples: a member's sample count is < 1");
+    long long launches = 0, cmax = 0;
+    if (!pop_schedule(n_members, 0, epochs, minibatches, nullptr, steps_out, &launches, &cmax, samples))
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_schedule_samples: a member's epochs or minibatches is < 1 (or its steps exceed 2^31-1)");
+    *n_launches_out = (int32_t)launches;
+    if (!out) return SSG_OK; // the size query
+    if (out_ints < SSG_POP_SCHED_INTS(n_members, launches))
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_schedule_samples: out_ints < SSG_POP_SCHED_INTS(n_members, n_launches)");
+    pop_schedule(n_members, 0, epochs, minibatches, out, steps_out, &launches, &cmax, samples);
+    return SSG_OK;
+}
+
+// the slices table of `P` sizes (out nullable: the checks alone); false: an entry < 1 or a sum beyond 2^31-1
+static bool pack_slices(int P, const int32_t *sizes, int32_t *out, long long *sum)
+{
+    long long o = 0;
+    for (int m = 0; m < P; ++m) {
+        if (sizes[m] < 1) return false;
+        if (out) {
+            int32_t *row = out + (size_t)m * SSG_POP_SLICE_ROW;
+            row[0] = (int32_t)o;
+            row[1] = sizes[m];
+            row[2] = ssg::ppo_gae_blocks(sizes[m]);
+            row[3] = 0;
+        }
+        o += sizes[m];
+        if (o > 0x7fffffffll) return false;
+    }
+    *sum = o;
+    return true;
+}
+
+int ssg_pop_pack_slices(int n_members, const int32_t *n_envs_per_member, int32_t *out, size_t out_ints)
+{
+    if (!n_envs_per_member || !out || n_members < 1 || n_members > SSG_POP_MAX_MEMBERS)
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_slices: NULL pointer or n_members out of range");
+    if (out_ints < (size_t)n_members * SSG_POP_SLICE_ROW)
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_slices: out_ints < SSG_POP_SLICE_ROW * n_members");
+    long long sum = 0;
+    if (!pack_slices(n_members, n_envs_per_member, nullptr, &sum))
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_slices: a member's env count is < 1 or the sum exceeds 2^31-1");
+    pack_slices(n_members, n_envs_per_member, out, &sum);
+    return SSG_OK;
+}
+
+int ssg_pop_set_slices(ssg_handle *h, int n_members, const int32_t *n_envs_per_member, const int32_t *dev_slices)
+{
+    if (!h) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_set_slices: NULL handle");
+    if (n_members == 0 || !n_envs_per_member || !dev_slices) { // unbind
+        h->pop_sizes.clear();
+        h->dev_slices = nullptr;
+        h->slice_max = h->slice_min = 0;
+        return SSG_OK;
+    }
+    if (n_members < 1 || n_members > SSG_POP_MAX_MEMBERS)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_set_slices: n_members must be in 1..SSG_POP_MAX_MEMBERS");
+    long long sum = 0;
+    if (!pack_slices(n_members, n_envs_per_member, nullptr, &sum))
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_set_slices: a member's env count is < 1 or the sum exceeds 2^31-1");
+    if (sum != (long long)h->cfg.n_envs) {
+        char buf[160];
+        std::snprintf(buf, sizeof buf, "ssg_pop_set_slices: the slices sum to %lld envs, the handle has %d", sum, h->cfg.n_envs);
+        return fail(h, SSG_ERR_BAD_ARG, buf);
+    }
+    h->pop_sizes.assign(n_envs_per_member, n_envs_per_member + n_members);
+    h->dev_slices = dev_slices;
+    h->slice_max = *std::max_element(h->pop_sizes.begin(), h->pop_sizes.end());
+    h->slice_min = *std::min_element(h->pop_sizes.begin(), h->pop_sizes.end());
+    return SSG_OK;
+}
+
+int ssg_pop_get_slices(const ssg_handle *h, int *n_members, int32_t *out)
+{
+    if (!h || !n_members) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_get_slices: NULL handle or n_members");
+    *n_members = (int)h->pop_sizes.size();
+    if (out) std::copy(h->pop_sizes.begin(), h->pop_sizes.end(), out);
     return SSG_OK;
 }
 
@@ -1816,7 +1935,18 @@ int ssg_pop_update_sched(ssg_handle *h, const ssg_population *pop, const ssg_pop
     PopSchedule sc;
     sc.dev_sched = dev_sched;
     sc.perm_epochs = perm_epochs;
-    if (!pop_schedule(P, mb.n_samples, epochs, minibatches, nullptr, nullptr, &sc.n_launches, &sc.Cmax))
+    // unequal slices: every member's own sample count, and what the SLICED kernels read instead of n, n_samples and idx_stride
+    std::vector<int64_t> samples;
+    if (const int32_t *slices = pop_slices(h)) {
+        for (int32_t n_m : h->pop_sizes) samples.push_back((int64_t)K * n_m);
+        mb.slices = slices;
+        mb.sched_hdr = dev_sched;
+        mb.K = K;
+        mb.perm_epochs = perm_epochs;
+        mb.n = 0;
+        mb.n_samples = *std::max_element(samples.begin(), samples.end());
+    }
+    if (!pop_schedule(P, mb.n_samples, epochs, minibatches, nullptr, nullptr, &sc.n_launches, &sc.Cmax, samples.empty() ? nullptr : samples.data()))
         return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_sched: a member's epochs or minibatches is < 1 (or its steps exceed 2^31-1)");
     if (perm_epochs < *std::max_element(epochs, epochs + P))
         return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_sched: perm_epochs < the largest epochs of a member");
@@ -1858,14 +1988,16 @@ int ssg_pop_episode_stats(ssg_handle *h, int n_members, int K, const double *dev
 {
     int rc = pop_bound(h);
     if (rc != SSG_OK) return rc;
-    if (n_members < 1 || n_members > SSG_POP_MAX_MEMBERS || h->cfg.n_envs % n_members != 0)
+    if (n_members < 1 || n_members > SSG_POP_MAX_MEMBERS)
         return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_episode_stats: n_members must be in 1..SSG_POP_MAX_MEMBERS and divide the handle's n_envs");
+    rc = check_members(h, n_members, "ssg_pop_episode_stats");
+    if (rc != SSG_OK) return rc;
     if (K < 1 || !dev_reward_KN || !dev_done_KN || !dev_carry_return || !dev_carry_length || !dev_out)
         return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_episode_stats: K < 1 or a NULL buffer");
     rc = check_ready(h, false);
     if (rc != SSG_OK) return rc;
     hipError_t e = ssg::launch_pop_episode_stats(n_members, K, h->cfg.n_envs, dev_reward_KN, dev_done_KN, dev_carry_return,
-                                                 dev_carry_length, dev_out, static_cast<hipStream_t>(stream));
+                                                 dev_carry_length, dev_out, static_cast<hipStream_t>(stream), pop_slices(h), pop_width(h, n_members));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population episode stats launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
@@ -1906,14 +2038,15 @@ static int run_evaluate(ssg_handle *h, const ssg_policy &pol, const ssg_populati
     if (rc != SSG_OK) return rc;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const bool greedy = (ev.flags & SSG_EVAL_GREEDY) != 0;
-    const int N = h->cfg.n_envs, P = pop ? pop->n_members : 1, n = N / P;
+    const int N = h->cfg.n_envs, P = pop ? pop->n_members : 1, n = pop ? pop_width(h, P) : N;
+    const int32_t *slices = pop ? pop_slices(h) : nullptr;
     for (int k = 0; k < ev.n_steps; ++k) {
         const float *u = ev.dev_uniform_TN ? ev.dev_uniform_TN + (size_t)k * (size_t)N : nullptr;
         hipError_t e;
         if (pop)
-            e = greedy ? ssg::launch_policy_pop_greedy(pol, P, n, ev.dev_obs, ev.dev_act, ev.dev_logp, ev.dev_value, nullptr, st)
+            e = greedy ? ssg::launch_policy_pop_greedy(pol, P, n, ev.dev_obs, ev.dev_act, ev.dev_logp, ev.dev_value, nullptr, st, slices)
                        : ssg::launch_policy_pop(pol, P, n, h->cfg.env_id_base, ev.dev_obs, u, ev.seed, ev.step0 + k, ev.dev_act, ev.dev_logp,
-                                                ev.dev_value, nullptr, st);
+                                                ev.dev_value, nullptr, st, slices);
         else
             e = greedy ? ssg::launch_policy_act_greedy(pol, N, ev.dev_obs, ev.dev_act, ev.dev_logp, ev.dev_value, nullptr, st)
                        : ssg::launch_policy_act(pol, N, h->cfg.env_id_base, ev.dev_obs, u, ev.seed, ev.step0 + k, ev.dev_act, ev.dev_logp,
@@ -1968,12 +2101,18 @@ int ssg_eval_reduce(ssg_handle *h, int n_members, const int64_t *dev_env_stats, 
 {
     int rc = pop_bound(h);
     if (rc != SSG_OK) return rc;
-    if (n_members < 1 || n_members > SSG_POP_MAX_MEMBERS || h->cfg.n_envs % n_members != 0)
+    if (n_members < 1 || n_members > SSG_POP_MAX_MEMBERS)
         return fail(h, SSG_ERR_BAD_ARG, "ssg_eval_reduce: n_members must be in 1..SSG_POP_MAX_MEMBERS and divide the handle's n_envs");
+    const bool whole = n_members == 1; // (one policy's reduce over the whole handle: the slices do not enter)
+    if (!whole) {
+        rc = check_members(h, n_members, "ssg_eval_reduce");
+        if (rc != SSG_OK) return rc;
+    }
     if (!dev_env_stats || !dev_member_stats) return fail(h, SSG_ERR_BAD_ARG, "ssg_eval_reduce: NULL dev_env_stats or dev_member_stats");
     rc = check_ready(h, false);
     if (rc != SSG_OK) return rc;
-    hipError_t e = ssg::launch_eval_reduce(n_members, h->cfg.n_envs / n_members, dev_env_stats, dev_member_stats, static_cast<hipStream_t>(stream));
+    hipError_t e = ssg::launch_eval_reduce(n_members, h->cfg.n_envs / n_members, dev_env_stats, dev_member_stats, static_cast<hipStream_t>(stream),
+                                           whole ? nullptr : pop_slices(h));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("evaluation reduce launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }

@@ -49,10 +49,10 @@ __global__ void __launch_bounds__(kEvalBlock) eval_account_kernel(int N, int E, 
 
 // grid (members): workgroup m writes (does not accumulate) the column sums of rows [m*n, (m+1)*n) of stats into out[m]: a strided loop
 // per lane, then an integer tree over the workgroup.
-__global__ void __launch_bounds__(kEvalBlock) eval_reduce_kernel(int n, const long long *__restrict__ stats, long long *__restrict__ out)
+// (the body of both kernels: the member's n rows start at `rows`)
+__device__ __forceinline__ void eval_reduce_body(int n, const long long *__restrict__ rows, long long *__restrict__ out,
+                                                 long long (*red)[kEvalBlock])
 {
-    __shared__ long long red[kEvalCols][kEvalBlock];
-    const long long *rows = stats + (size_t)blockIdx.x * (size_t)n * kEvalCols;
     long long s[kEvalCols];
 #pragma unroll
     for (int c = 0; c < kEvalCols; ++c) s[c] = 0;
@@ -73,6 +73,21 @@ __global__ void __launch_bounds__(kEvalBlock) eval_reduce_kernel(int n, const lo
     if (threadIdx.x < kEvalCols) out[(size_t)blockIdx.x * kEvalCols + threadIdx.x] = red[threadIdx.x][0];
 }
 
+__global__ void __launch_bounds__(kEvalBlock) eval_reduce_kernel(int n, const long long *__restrict__ stats, long long *__restrict__ out)
+{
+    __shared__ long long red[kEvalCols][kEvalBlock];
+    eval_reduce_body(n, stats + (size_t)blockIdx.x * (size_t)n * kEvalCols, out, red);
+}
+
+// on unequal slices (ssg_pop_set_slices): workgroup m sums rows [o_m, o_m + n_m), its row of the slices table
+__global__ void __launch_bounds__(kEvalBlock) eval_reduce_sliced_kernel(const int32_t *__restrict__ slices, const long long *__restrict__ stats,
+                                                                        long long *__restrict__ out)
+{
+    __shared__ long long red[kEvalCols][kEvalBlock];
+    const int32_t *row = slices + (size_t)blockIdx.x * SSG_POP_SLICE_ROW;
+    eval_reduce_body(row[1], stats + (size_t)row[0] * kEvalCols, out, red);
+}
+
 } // namespace
 
 hipError_t launch_eval_account(int N, int E, const double *rew, const uint8_t *done, const uint8_t *flags, double *carry_ret, int32_t *carry,
@@ -83,8 +98,13 @@ hipError_t launch_eval_account(int N, int E, const double *rew, const uint8_t *d
     return hipGetLastError();
 }
 
-hipError_t launch_eval_reduce(int members, int n, const int64_t *stats, int64_t *out, hipStream_t stream)
+hipError_t launch_eval_reduce(int members, int n, const int64_t *stats, int64_t *out, hipStream_t stream, const int32_t *slices)
 {
+    if (slices) {
+        hipLaunchKernelGGL(eval_reduce_sliced_kernel, dim3(members), dim3(kEvalBlock), 0, stream, slices, reinterpret_cast<const long long *>(stats),
+                           reinterpret_cast<long long *>(out));
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(eval_reduce_kernel, dim3(members), dim3(kEvalBlock), 0, stream, n, reinterpret_cast<const long long *>(stats),
                        reinterpret_cast<long long *>(out));
     return hipGetLastError();

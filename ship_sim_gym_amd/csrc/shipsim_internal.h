@@ -230,15 +230,19 @@ constexpr int kPopTableRow = 8;
 // SH_* — then per launch kPopSchedRow int32 per member — SR_*: what differs between the members within launch j, where member m runs
 // ITS minibatch j (chunk j % chunks_m of its permutation row j / chunks_m) or, past its steps_m, nothing.
 constexpr int kPopSchedRow = SSG_POP_SCHED_ROW;
-enum { SH_STEPS = 0, SH_CHUNKS, SH_C, SH_EPOCHS };
+enum { SH_STEPS = 0, SH_CHUNKS, SH_C, SH_EPOCHS, SH_PREFIX /* int64: entries [4], [5]; ssg_pop_pack_schedule_samples only */ };
 enum { SR_OFF = 0 /* int64: entries [0], [1] */, SR_M = 2, SR_G, SR_FIRST, SR_ACTIVE, SR_INVM /* f32 bits of 1 / (float)M */ };
 static_assert(SSG_POP_MAX_MEMBERS * 16 <= kPopSlotsOff, "the members' advantage statistics fit in front of the slots");
+// slices (nullable, here and below): the device table of ssg_pop_set_slices, SSG_POP_SLICE_ROW int32 per member = {o_m, n_m,
+// ppo_gae_blocks(n_m), 0}; member m then owns envs [o_m, o_m + n_m) and n is the LARGEST slice (the launch's width)
 hipError_t launch_policy_pop(const ssg_policy &p, int members, int n, long long env_base, const double *obs, const float *uniform,
-                             uint64_t seed, int64_t step, int32_t *act, float *logp, float *value, float *x, hipStream_t stream);
+                             uint64_t seed, int64_t step, int32_t *act, float *logp, float *value, float *x, hipStream_t stream,
+                             const int32_t *slices = nullptr);
 void pop_pack(int members, const ssg_ppo_hparams *hp, int64_t step0, int n_steps, float *out); // host only
 void pop_pack_steps(int members, const ssg_ppo_hparams *hp, const int64_t *step0, int n_steps, float *out); // (a starting step per member)
 hipError_t launch_pop_gae(int members, int K, int N, const float *table, const double *rew, const uint8_t *done, const float *val,
-                          const float *last_val, float *adv, float *ret, void *ws, hipStream_t stream);
+                          const float *last_val, float *adv, float *ret, void *ws, hipStream_t stream, const int32_t *slices = nullptr,
+                          int n_max = 0);
 hipError_t launch_pop_exploit(const ssg_policy &p, int members, const int32_t *src, float *adam_mv, hipStream_t stream);
 // The extended update (ssg_ppo_grad_ext / ssg_ppo_update_ext / ssg_pop_update_ext): value clip, KL penalty, gradient-norm clip.
 // From the plain path's slot offset the workspace holds the running sum of the epoch's mean(KL) (f32 [members]), the gradient vector of
@@ -301,6 +305,11 @@ struct PpoMinibatch {
     float *grad_out, *stats_out;
     long long stats_stride;
     float *adam_mv;
+    // a population on unequal slices (with sched): the slices table and the schedule table's header rows, whose entries SH_PREFIX hold
+    // the int64 sum of the samples of the members before m — member m's permutation block starts perm_epochs times that far into idx
+    // and its samples are K * n_m (n, n_samples and idx_stride are then unused)
+    const int32_t *slices, *sched_hdr;
+    long long K, perm_epochs;
 };
 hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream);
 // RLlib's update_kl on every member's coefficient from the last epoch's `chunks` minibatches (sched_hdr, nullable: the schedule
@@ -308,19 +317,20 @@ hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream);
 hipError_t launch_kl_adapt(int members, const PpoExtLaunch &ext, float kl_target, int P, long long chunks, const int32_t *sched_hdr, void *ws,
                            size_t slots_off, hipStream_t stream);
 // the acting policy's log-distribution over stored x rows (shipsim_policy.hip): rows t*N + m*n + e, t < K, e < n, under parameter row m
-hipError_t launch_policy_dist(const ssg_policy &p, int members, int n, long long N, int K, const float *x, float *logp_all, hipStream_t stream);
+hipError_t launch_policy_dist(const ssg_policy &p, int members, int n, long long N, int K, const float *x, float *logp_all, hipStream_t stream,
+                              const int32_t *slices = nullptr);
 hipError_t launch_pop_episode_stats(int members, int K, int N, const double *rew, const uint8_t *done, double *carry_ret,
-                                    int32_t *carry_len, int64_t *out, hipStream_t stream);
+                                    int32_t *carry_len, int64_t *out, hipStream_t stream, const int32_t *slices = nullptr, int n_max = 0);
 // the greedy mode of the policy kernel (shipsim_policy.hip): the arg-max action and its logp; no uniform, seed or step
 hipError_t launch_policy_act_greedy(const ssg_policy &p, int n, const double *obs, int32_t *act, float *logp, float *value, float *x, hipStream_t stream);
 hipError_t launch_policy_pop_greedy(const ssg_policy &p, int members, int n, const double *obs, int32_t *act, float *logp, float *value, float *x,
-                                    hipStream_t stream);
+                                    hipStream_t stream, const int32_t *slices = nullptr);
 // episode accounting of an evaluation run (shipsim_eval.hip): one step's rows into the per-env carries and stats rows (an env counts its
 // first E episodes), and the per-member column sums of the stats rows
 constexpr int kEvalCols = SSG_EVAL_STATS;
 hipError_t launch_eval_account(int N, int E, const double *rew, const uint8_t *done, const uint8_t *flags, double *carry_ret, int32_t *carry,
                                int64_t *stats, hipStream_t stream);
-hipError_t launch_eval_reduce(int members, int n, const int64_t *stats, int64_t *out, hipStream_t stream);
+hipError_t launch_eval_reduce(int members, int n, const int64_t *stats, int64_t *out, hipStream_t stream, const int32_t *slices = nullptr);
 
 #ifdef __HIPCC__
 // One round of Philox4x32-10 (counter ctr, key key).  The counter-based streams of the library — fill_actions_kernel's actions

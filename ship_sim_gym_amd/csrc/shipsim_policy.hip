@@ -195,16 +195,29 @@ __device__ __forceinline__ float log_sum_exp(const float (&lg)[4], int A)
 // GREEDY (ssg_policy_act_greedy / ssg_pop_act_greedy, the evaluation loop): the same forward, then step 4 is the arg-max instead of a
 // draw — no Philox round, `uniform` never read; value and x are the sampling launch's bit for bit.  A template parameter, so the four
 // sampling instantiations keep their code.
-template <bool POP, bool SPLIT, bool GREEDY = false>
-__global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1, 2))) policy_act_kernel(const ssg_policy p, const float *__restrict__ params, const double *__restrict__ scale,
-                                                              int n, long long env_base, const double *__restrict__ obs,
-                                                              const float *__restrict__ uniform, uint64_t seed, int64_t step,
-                                                              int32_t *__restrict__ act_out, float *__restrict__ logp_out,
-                                                              float *__restrict__ value_out, float *__restrict__ x_out, int plen)
+// SLICED (with POP; ssg_pop_set_slices): the members' slices are unequal.  Member m = blockIdx.y owns the n_m envs from o_m on, row m
+// = {o_m, n_m, ...} of the slices table; the grid is as wide as the largest slice needs, and a workgroup whose first env is past n_m
+// leaves as a whole ahead of every barrier.  Nothing below relies on a member's base being a multiple of the wave: every global access
+// is a scalar element of its row.  A kernel of its own takes the table, so the other instantiations keep their argument layout.
+template <bool POP, bool SPLIT, bool GREEDY, bool SLICED>
+__device__ __forceinline__ void policy_act_body(const ssg_policy &p, const float *__restrict__ params, const double *__restrict__ scale,
+                                                int n, long long env_base, const double *__restrict__ obs,
+                                                const float *__restrict__ uniform, uint64_t seed, int64_t step,
+                                                int32_t *__restrict__ act_out, float *__restrict__ logp_out,
+                                                float *__restrict__ value_out, float *__restrict__ x_out, int plen,
+                                                const int32_t *__restrict__ slices)
 {
+    static_assert(POP || !SLICED, "slices are a population's");
     extern __shared__ float4 lds4[];
     if (POP) { // the member's slice of every buffer
-        const size_t m0 = (size_t)blockIdx.y * (size_t)n, D = (size_t)p.obs_dim;
+        size_t m0 = (size_t)blockIdx.y * (size_t)n;
+        if (SLICED) {
+            const int32_t *row = slices + (size_t)blockIdx.y * SSG_POP_SLICE_ROW;
+            m0 = (size_t)row[0];
+            n = row[1];
+            if ((int)(blockIdx.x * kPolWave) >= n) return; // (uniform over the workgroup)
+        }
+        const size_t D = (size_t)p.obs_dim;
         params += (size_t)blockIdx.y * (size_t)plen;
         env_base += (long long)m0;
         obs += m0 * D;
@@ -322,22 +335,56 @@ __global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1
     logp_out[e] = lp;
 }
 
+template <bool POP, bool SPLIT, bool GREEDY = false>
+__global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1, 2))) policy_act_kernel(const ssg_policy p, const float *__restrict__ params, const double *__restrict__ scale,
+                                                              int n, long long env_base, const double *__restrict__ obs,
+                                                              const float *__restrict__ uniform, uint64_t seed, int64_t step,
+                                                              int32_t *__restrict__ act_out, float *__restrict__ logp_out,
+                                                              float *__restrict__ value_out, float *__restrict__ x_out, int plen)
+{
+    policy_act_body<POP, SPLIT, GREEDY, false>(p, params, scale, n, env_base, obs, uniform, seed, step, act_out, logp_out, value_out, x_out, plen,
+                                               nullptr);
+}
+
+// a population on unequal slices (no n: every member's is in the table)
+template <bool SPLIT, bool GREEDY>
+__global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1, 2))) policy_act_sliced_kernel(const ssg_policy p, const float *__restrict__ params, const double *__restrict__ scale,
+                                                              const int32_t *__restrict__ slices, long long env_base, const double *__restrict__ obs,
+                                                              const float *__restrict__ uniform, uint64_t seed, int64_t step,
+                                                              int32_t *__restrict__ act_out, float *__restrict__ logp_out,
+                                                              float *__restrict__ value_out, float *__restrict__ x_out, int plen)
+{
+    policy_act_body<true, SPLIT, GREEDY, true>(p, params, scale, 0, env_base, obs, uniform, seed, step, act_out, logp_out, value_out, x_out, plen,
+                                               slices);
+}
+
 // The acting policy's whole log-distribution over STORED x rows (ssg_ppo_dist / ssg_pop_dist): policy_act_kernel's forward from its
 // step 2 on — the same dense, heads and log_sum_exp — so that logp_all[i][act[i]] is the rollout's logp[i] bit for bit.  Grid
 // (workgroups of n rows, members, K): the workgroup's rows start at row blockIdx.z*N + blockIdx.y*n and run under parameter row
 // blockIdx.y (one policy: members = 1, K = 1, n = the number of rows).  logp_all[i][j] = logit_j - lse for j < A, 0 for j >= A.
 // SPLIT: the pi tower and the pi head open the packed row as the shared body and Wpi / bpi do, so the body code is the same and only
 // the head differs; the vf tower is never read.
-template <bool SPLIT>
-__global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1, 2))) policy_dist_kernel(const ssg_policy p, const float *__restrict__ params, int n, long long N,
-                                                               const float *__restrict__ x, float *__restrict__ logp_all, int plen)
+// SLICED: member blockIdx.y's rows of step blockIdx.z start at blockIdx.z*N + o_m and there are n_m of them (its row of the slices
+// table); a workgroup past n_m leaves ahead of every barrier.  An x row at o_m*D floats is not 16-byte aligned: the rows are read
+// element by element.  A logp_all row is 16 bytes per env whatever o_m is.
+template <bool SPLIT, bool SLICED>
+__device__ __forceinline__ void policy_dist_body(const ssg_policy &p, const float *__restrict__ params, int n, long long N,
+                                                 const float *__restrict__ x, float *__restrict__ logp_all, int plen,
+                                                 const int32_t *__restrict__ slices)
 {
     extern __shared__ float4 lds4[];
     const int lane = threadIdx.x;
     const int e0 = blockIdx.x * kPolWave;
+    size_t base = (size_t)blockIdx.y * (size_t)n;
+    if (SLICED) {
+        const int32_t *row = slices + (size_t)blockIdx.y * SSG_POP_SLICE_ROW;
+        base = (size_t)row[0];
+        n = row[1];
+        if (e0 >= n) return; // (uniform over the workgroup)
+    }
     const int ne = (n - e0 < kPolWave) ? n - e0 : kPolWave;
     const int D = p.obs_dim, H = p.hidden, A = p.n_actions;
-    const size_t row0 = (size_t)blockIdx.z * (size_t)N + (size_t)blockIdx.y * (size_t)n + (size_t)e0;
+    const size_t row0 = (size_t)blockIdx.z * (size_t)N + base + (size_t)e0;
     params += (size_t)blockIdx.y * (size_t)plen;
     const int R4 = ((D > H ? D : H) + 3) & ~3;
     float *wt = reinterpret_cast<float *>(lds4);
@@ -385,6 +432,21 @@ __global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1
     dst[3] = out.w;
 }
 
+template <bool SPLIT>
+__global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1, 2))) policy_dist_kernel(const ssg_policy p, const float *__restrict__ params, int n, long long N,
+                                                               const float *__restrict__ x, float *__restrict__ logp_all, int plen)
+{
+    policy_dist_body<SPLIT, false>(p, params, n, N, x, logp_all, plen, nullptr);
+}
+
+template <bool SPLIT>
+__global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1, 2))) policy_dist_sliced_kernel(const ssg_policy p, const float *__restrict__ params,
+                                                               const int32_t *__restrict__ slices, long long N,
+                                                               const float *__restrict__ x, float *__restrict__ logp_all, int plen)
+{
+    policy_dist_body<SPLIT, true>(p, params, 0, N, x, logp_all, plen, slices);
+}
+
 } // namespace
 
 static bool is_split(const ssg_policy &p) { return (p.activation & SSG_POLICY_SEPARATE_VALUE) != 0; }
@@ -399,7 +461,10 @@ size_t policy_lds_bytes(const ssg_policy &p, bool both_towers)
 
 hipError_t prepare_policy()
 {
-    const void *kernels[10] = {reinterpret_cast<const void *>(policy_act_kernel<false, false>), reinterpret_cast<const void *>(policy_act_kernel<true, false>),
+    const void *kernels[16] = {reinterpret_cast<const void *>(policy_act_sliced_kernel<false, false>), reinterpret_cast<const void *>(policy_act_sliced_kernel<true, false>),
+                               reinterpret_cast<const void *>(policy_act_sliced_kernel<false, true>), reinterpret_cast<const void *>(policy_act_sliced_kernel<true, true>),
+                               reinterpret_cast<const void *>(policy_dist_sliced_kernel<false>), reinterpret_cast<const void *>(policy_dist_sliced_kernel<true>),
+                               reinterpret_cast<const void *>(policy_act_kernel<false, false>), reinterpret_cast<const void *>(policy_act_kernel<true, false>),
                                reinterpret_cast<const void *>(policy_act_kernel<false, true>), reinterpret_cast<const void *>(policy_act_kernel<true, true>),
                                reinterpret_cast<const void *>(policy_dist_kernel<false>), reinterpret_cast<const void *>(policy_dist_kernel<true>),
                                reinterpret_cast<const void *>(policy_act_kernel<false, false, true>), reinterpret_cast<const void *>(policy_act_kernel<true, false, true>),
@@ -423,9 +488,16 @@ hipError_t launch_policy_act(const ssg_policy &p, int n, long long env_base, con
 }
 
 hipError_t launch_policy_pop(const ssg_policy &p, int members, int n, long long env_base, const double *obs, const float *uniform,
-                             uint64_t seed, int64_t step, int32_t *act, float *logp, float *value, float *x, hipStream_t stream)
+                             uint64_t seed, int64_t step, int32_t *act, float *logp, float *value, float *x, hipStream_t stream,
+                             const int32_t *slices)
 {
     const unsigned grid = (unsigned)((n + kPolWave - 1) / kPolWave);
+    if (slices) { // (n: the largest slice)
+        const auto sliced = is_split(p) ? policy_act_sliced_kernel<true, false> : policy_act_sliced_kernel<false, false>;
+        hipLaunchKernelGGL(sliced, dim3(grid, (unsigned)members), dim3(kPolWave), policy_lds_bytes(p, act != nullptr), stream, p, p.dev_params,
+                           p.dev_obs_scale, slices, env_base, obs, uniform, seed, step, act, logp, value, x, ppo_packed_len(p));
+        return hipGetLastError();
+    }
     const auto kernel = is_split(p) ? policy_act_kernel<true, true> : policy_act_kernel<true, false>;
     hipLaunchKernelGGL(kernel, dim3(grid, (unsigned)members),
                        dim3(kPolWave), policy_lds_bytes(p, act != nullptr), stream, p, p.dev_params, p.dev_obs_scale, n, env_base, obs, uniform,
@@ -444,18 +516,30 @@ hipError_t launch_policy_act_greedy(const ssg_policy &p, int n, const double *ob
 }
 
 hipError_t launch_policy_pop_greedy(const ssg_policy &p, int members, int n, const double *obs, int32_t *act, float *logp, float *value, float *x,
-                                    hipStream_t stream)
+                                    hipStream_t stream, const int32_t *slices)
 {
     const unsigned grid = (unsigned)((n + kPolWave - 1) / kPolWave);
+    if (slices) {
+        const auto sliced = is_split(p) ? policy_act_sliced_kernel<true, true> : policy_act_sliced_kernel<false, true>;
+        hipLaunchKernelGGL(sliced, dim3(grid, (unsigned)members), dim3(kPolWave), policy_lds_bytes(p, true), stream, p, p.dev_params, p.dev_obs_scale,
+                           slices, 0LL, obs, (const float *)nullptr, (uint64_t)0, (int64_t)0, act, logp, value, x, ppo_packed_len(p));
+        return hipGetLastError();
+    }
     const auto kernel = is_split(p) ? policy_act_kernel<true, true, true> : policy_act_kernel<true, false, true>;
     hipLaunchKernelGGL(kernel, dim3(grid, (unsigned)members), dim3(kPolWave), policy_lds_bytes(p, true), stream, p, p.dev_params, p.dev_obs_scale,
                        n, 0LL, obs, (const float *)nullptr, (uint64_t)0, (int64_t)0, act, logp, value, x, ppo_packed_len(p));
     return hipGetLastError();
 }
 
-hipError_t launch_policy_dist(const ssg_policy &p, int members, int n, long long N, int K, const float *x, float *logp_all, hipStream_t stream)
+hipError_t launch_policy_dist(const ssg_policy &p, int members, int n, long long N, int K, const float *x, float *logp_all, hipStream_t stream,
+                              const int32_t *slices)
 {
     const unsigned grid = (unsigned)((n + kPolWave - 1) / kPolWave);
+    if (slices) {
+        hipLaunchKernelGGL(is_split(p) ? policy_dist_sliced_kernel<true> : policy_dist_sliced_kernel<false>, dim3(grid, (unsigned)members, (unsigned)K),
+                           dim3(kPolWave), policy_lds_bytes(p, false), stream, p, p.dev_params, slices, N, x, logp_all, ppo_packed_len(p));
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(is_split(p) ? policy_dist_kernel<true> : policy_dist_kernel<false>, dim3(grid, (unsigned)members, (unsigned)K),
                        dim3(kPolWave), policy_lds_bytes(p, false), stream, p, p.dev_params, n, N, x, logp_all, ppo_packed_len(p));
     return hipGetLastError();

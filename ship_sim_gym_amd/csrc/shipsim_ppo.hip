@@ -129,6 +129,23 @@ __global__ void __launch_bounds__(256) pop_gae_kernel(int K, int N, int n, int n
              table[m * kPopTableRow + PT_GLF], part + m * (size_t)nb, rs, rq);
 }
 
+// GAE of a population on unequal slices (ssg_pop_set_slices), grid (blocks of the largest slice, members): member m walks its n_m
+// columns from o_m on (its row of the slices table) and lays its partial sums out as a run over n_m envs does, in its row of the
+// [members][nb] partials (nb: the blocks of the largest slice).  A workgroup past n_m leaves ahead of every barrier.
+__global__ void __launch_bounds__(256) pop_gae_sliced_kernel(int K, int N, const int32_t *__restrict__ slices, int nb,
+                                                             const double *__restrict__ rew, const uint8_t *__restrict__ done,
+                                                             const float *__restrict__ val, const float *__restrict__ last_val,
+                                                             float *__restrict__ adv_out, float *__restrict__ ret_out,
+                                                             const float *__restrict__ table, double2 *__restrict__ part)
+{
+    __shared__ double rs[256], rq[256];
+    const size_t m = blockIdx.y, e0 = (size_t)slices[m * SSG_POP_SLICE_ROW];
+    const int n = slices[m * SSG_POP_SLICE_ROW + 1];
+    if ((int)(blockIdx.x * 256) >= n) return; // (uniform over the workgroup)
+    gae_body(K, N, n, rew + e0, done + e0, val + e0, last_val + e0, adv_out + e0, ret_out + e0, table[m * kPopTableRow + PT_GF],
+             table[m * kPopTableRow + PT_GLF], part + m * (size_t)nb, rs, rq);
+}
+
 // stats[0] = mean, stats[1] = std + adv_eps (unbiased std, as torch's .std()), stats[2] = 1 / stats[1]
 __device__ __forceinline__ void gae_stats_body(const double2 *__restrict__ part, int nblocks, double n, float adv_eps,
                                                float *__restrict__ stats, double *rs, double *rq)
@@ -174,6 +191,17 @@ __global__ void __launch_bounds__(256) pop_gae_stats_kernel(const double2 *__res
     __shared__ double rs[256], rq[256];
     const size_t m = blockIdx.x;
     gae_stats_body(part + m * (size_t)nblocks, nblocks, n, table[m * kPopTableRow + PT_ADV_EPS], stats + m * 4, rs, rq);
+}
+
+// on unequal slices: the member's block count and its divisor K * n_m come from its row of the slices table; nb: the partials' row length
+__global__ void __launch_bounds__(256) pop_gae_stats_sliced_kernel(const double2 *__restrict__ part, int nb, int K,
+                                                                   const int32_t *__restrict__ slices, const float *__restrict__ table,
+                                                                   float *__restrict__ stats)
+{
+    __shared__ double rs[256], rq[256];
+    const size_t m = blockIdx.x;
+    const int32_t *row = slices + m * SSG_POP_SLICE_ROW;
+    gae_stats_body(part + m * (size_t)nb, row[2], (double)K * (double)row[1], table[m * kPopTableRow + PT_ADV_EPS], stats + m * 4, rs, rq);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -276,6 +304,14 @@ struct PopGradArgs {
     const float *table;   // [members][kPopTableRow]
 };
 
+// What a population on unequal slices adds (the SLICED instantiations; ssg_pop_set_slices): member m's envs are [o_m, o_m + n_m), its
+// row of `slices`; its samples are K * n_m, sample i = t*n_m + e is row t*N + o_m + e; its permutation block starts perm_epochs * (the
+// int64 at SH_PREFIX of its header row of the schedule table) entries into idx.
+struct SliceGradArgs {
+    const int32_t *slices, *sched_hdr;
+    long long K, perm_epochs;
+};
+
 // What the extended loss (ssg_ppo_grad_ext / ssg_ppo_update_ext / ssg_pop_update_ext) adds to GradArgs.  A term is off for a member
 // whose constant is <= 0 (or whose pointer is NULL): its samples then take exactly the operations of the plain loss.
 struct ExtGradArgs {
@@ -300,10 +336,14 @@ struct ExtGradArgs {
 // launch for M_m alone.  A template flag, not a nullable pointer, and kernels of their own that take the records (sched: this
 // launch's [members][kPopSchedRow], shipsim_internal.h) as one more argument: the other instantiations keep their argument layout and
 // compile from the text they had.
-template <bool POP, bool EXT, bool SPLIT, bool SCHED>
-__device__ __forceinline__ void ppo_grad_body(const GradArgs &a_, const PopGradArgs &pa, const ExtGradArgs &ea, const int32_t *sched)
+// SLICED (with SCHED): unequal slices, see SliceGradArgs; kernels of their own again.  Everything behind the gather — tiles, slots,
+// the reduction — depends on M_m and G_m alone, so it is the SCHED code unchanged.
+template <bool POP, bool EXT, bool SPLIT, bool SCHED, bool SLICED = false>
+__device__ __forceinline__ void ppo_grad_body(const GradArgs &a_, const PopGradArgs &pa, const ExtGradArgs &ea, const int32_t *sched,
+                                              const SliceGradArgs &sa = SliceGradArgs{})
 {
     static_assert(POP || !SCHED, "a schedule is a population's");
+    static_assert(SCHED || !SLICED, "unequal slices run on schedules");
     extern __shared__ float4 lds4[];
     float *lds = reinterpret_cast<float *>(lds4);
     GradArgs a = a_;
@@ -317,7 +357,7 @@ __device__ __forceinline__ void ppo_grad_body(const GradArgs &a_, const PopGradA
     if (POP) {
         const size_t m = blockIdx.y;
         a.params += m * (size_t)a.P;
-        a.idx += m * (size_t)pa.idx_stride;
+        if (!SLICED) a.idx += m * (size_t)pa.idx_stride;
         a.stats += m * 4;
         a.slots += m * (size_t)gridDim.x * (size_t)SS;
         const float *row = pa.table + m * kPopTableRow;
@@ -326,6 +366,14 @@ __device__ __forceinline__ void ppo_grad_body(const GradArgs &a_, const PopGradA
         a.clip = row[PT_CLIP];
         a.vf = row[PT_VF];
         a.ent = row[PT_ENT];
+    }
+    long long mem_n = pa.n, mem_base = POP ? (long long)blockIdx.y * pa.n : 0; // the member's envs and its first env
+    if (SLICED) {
+        const int32_t *row = sa.slices + (size_t)blockIdx.y * SSG_POP_SLICE_ROW;
+        mem_base = row[0];
+        mem_n = row[1];
+        a.n_samples = sa.K * mem_n;
+        a.idx += sa.perm_epochs * *reinterpret_cast<const long long *>(sa.sched_hdr + (size_t)blockIdx.y * kPopSchedRow + SH_PREFIX);
     }
     unsigned gm = 0; // SCHED: the member's own grid, the workgroups that share its tiles
     if (SCHED) {
@@ -381,8 +429,8 @@ __device__ __forceinline__ void ppo_grad_body(const GradArgs &a_, const PopGradA
             long long j = i < a.M ? a.idx[i] : -1;
             if (j >= a.n_samples) j = -1;
             if (POP && j >= 0) {
-                const long long t = j / pa.n;
-                j = t * pa.N + (long long)blockIdx.y * pa.n + (j - t * pa.n);
+                const long long t = j / mem_n;
+                j = t * pa.N + mem_base + (j - t * mem_n);
             }
             SIDX[tid] = j;
             if (j >= 0) {
@@ -604,6 +652,21 @@ __global__ void __launch_bounds__(kPpoBlock) ppo_grad_ext_sched_kernel(const Gra
                                                                        const int32_t *__restrict__ sched)
 {
     ppo_grad_body<true, true, SPLIT, true>(a, pa, ea, sched);
+}
+
+// ... on unequal slices
+template <bool SPLIT>
+__global__ void __launch_bounds__(kPpoBlock) ppo_grad_sliced_kernel(const GradArgs a, const PopGradArgs pa, const int32_t *__restrict__ sched,
+                                                                    const SliceGradArgs sa)
+{
+    ppo_grad_body<true, false, SPLIT, true, true>(a, pa, ExtGradArgs{}, sched, sa);
+}
+
+template <bool SPLIT>
+__global__ void __launch_bounds__(kPpoBlock) ppo_grad_ext_sliced_kernel(const GradArgs a, const PopGradArgs pa, const ExtGradArgs ea,
+                                                                        const int32_t *__restrict__ sched, const SliceGradArgs sa)
+{
+    ppo_grad_body<true, true, SPLIT, true, true>(a, pa, ea, sched, sa);
 }
 
 // grad[p] = sum over the slots (a fixed order); entries P..P+3 (when nstats) are the loss sums -> stats = sum / M.  With params: Adam, torch's
@@ -881,15 +944,15 @@ __global__ void __launch_bounds__(256) pop_exploit_kernel(const PopSrc s, int L,
 // grid (ceil(n / 256), members): one lane per env walks t = 0 .. K-1 with the env's carried return / length; an episode is counted at
 // its done step as the step kernel counts it (llrint(100 * cum): cum is a sum of {1, -1, -0.01} terms).  Integer sums per workgroup,
 // then three integer atomics per workgroup on the member's triple: order-free and exact.
-__global__ void __launch_bounds__(256) pop_episode_stats_kernel(int K, int N, int n, const double *__restrict__ rew,
-                                                                const uint8_t *__restrict__ done, double *__restrict__ carry_ret,
-                                                                int32_t *__restrict__ carry_len, unsigned long long *__restrict__ out)
+// (the body of both kernels: the member's n envs start at env e0; red: the workgroup's 3 x 256 integers of LDS)
+__device__ __forceinline__ void episode_stats_body(int K, int N, int n, size_t e0, const double *__restrict__ rew,
+                                                   const uint8_t *__restrict__ done, double *__restrict__ carry_ret,
+                                                   int32_t *__restrict__ carry_len, unsigned long long *__restrict__ out, long long (*red)[256])
 {
-    __shared__ long long red[3][256];
     const int el = blockIdx.x * 256 + threadIdx.x;
     long long s_ret = 0, s_len = 0, s_eps = 0;
     if (el < n) {
-        const size_t e = (size_t)blockIdx.y * (size_t)n + (size_t)el;
+        const size_t e = e0 + (size_t)el;
         double cum = carry_ret[e];
         int len = carry_len[e];
         for (int t = 0; t < K; ++t) {
@@ -917,6 +980,26 @@ __global__ void __launch_bounds__(256) pop_episode_stats_kernel(int K, int N, in
         __syncthreads();
     }
     if (threadIdx.x < 3 && red[2][0] != 0) atomicAdd(out + (size_t)blockIdx.y * 3 + threadIdx.x, (unsigned long long)red[threadIdx.x][0]);
+}
+
+__global__ void __launch_bounds__(256) pop_episode_stats_kernel(int K, int N, int n, const double *__restrict__ rew,
+                                                                const uint8_t *__restrict__ done, double *__restrict__ carry_ret,
+                                                                int32_t *__restrict__ carry_len, unsigned long long *__restrict__ out)
+{
+    __shared__ long long red[3][256];
+    episode_stats_body(K, N, n, (size_t)blockIdx.y * (size_t)n, rew, done, carry_ret, carry_len, out, red);
+}
+
+// on unequal slices: grid (blocks of the largest slice, members); member m's envs are its row of the slices table
+__global__ void __launch_bounds__(256) pop_episode_stats_sliced_kernel(int K, int N, const int32_t *__restrict__ slices,
+                                                                       const double *__restrict__ rew, const uint8_t *__restrict__ done,
+                                                                       double *__restrict__ carry_ret, int32_t *__restrict__ carry_len,
+                                                                       unsigned long long *__restrict__ out)
+{
+    __shared__ long long red[3][256];
+    const int32_t *row = slices + (size_t)blockIdx.y * SSG_POP_SLICE_ROW;
+    if ((int)(blockIdx.x * 256) >= row[1]) return; // (uniform over the workgroup, ahead of the barriers)
+    episode_stats_body(K, N, row[1], (size_t)row[0], rew, done, carry_ret, carry_len, out, red);
 }
 
 // One policy's row of loss / GAE constants (PT_*), f32 from the caller's doubles: torch rounds a Python scalar to f32 when it meets
@@ -992,6 +1075,11 @@ typedef void (*GradSchedKernel)(const GradArgs, const PopGradArgs, const int32_t
 typedef void (*GradExtSchedKernel)(const GradArgs, const PopGradArgs, const ExtGradArgs, const int32_t *);
 static GradSchedKernel grad_plain_sched(bool split) { return split ? ppo_grad_sched_kernel<true> : ppo_grad_sched_kernel<false>; }
 static GradExtSchedKernel grad_ext_sched(bool split) { return split ? ppo_grad_ext_sched_kernel<true> : ppo_grad_ext_sched_kernel<false>; }
+static const void *grad_kernel_sliced(bool ext, bool split)
+{
+    if (ext) return split ? reinterpret_cast<const void *>(ppo_grad_ext_sliced_kernel<true>) : reinterpret_cast<const void *>(ppo_grad_ext_sliced_kernel<false>);
+    return split ? reinterpret_cast<const void *>(ppo_grad_sliced_kernel<true>) : reinterpret_cast<const void *>(ppo_grad_sliced_kernel<false>);
+}
 static const void *grad_kernel(bool pop, bool ext, bool split, bool sched = false)
 {
     if (sched) return ext ? reinterpret_cast<const void *>(grad_ext_sched(split)) : reinterpret_cast<const void *>(grad_plain_sched(split));
@@ -1000,7 +1088,8 @@ static const void *grad_kernel(bool pop, bool ext, bool split, bool sched = fals
 
 hipError_t prepare_ppo()
 {
-    const void *kernels[12] = {grad_kernel(false, false, false),      grad_kernel(true, false, false),      grad_kernel(false, true, false),
+    const void *kernels[16] = {grad_kernel_sliced(false, false),      grad_kernel_sliced(true, false),      grad_kernel_sliced(false, true),
+                               grad_kernel_sliced(true, true),        grad_kernel(false, false, false),      grad_kernel(true, false, false),      grad_kernel(false, true, false),
                                grad_kernel(true, true, false),        grad_kernel(false, false, true),      grad_kernel(true, false, true),
                                grad_kernel(false, true, true),        grad_kernel(true, true, true),        grad_kernel(true, false, false, true),
                                grad_kernel(true, true, false, true),  grad_kernel(true, false, true, true), grad_kernel(true, true, true, true)};
@@ -1032,6 +1121,9 @@ hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream)
     const bool pop = mb.table != nullptr; // a population reads its constants from the table: the POP instantiations
     const bool sched = mb.sched != nullptr; // ... and its members' minibatches from the schedule records: the SCHED ones (G: the launch's)
     if (sched && !pop) return hipErrorInvalidValue;
+    const bool sliced = mb.slices != nullptr; // ... on unequal slices: the SLICED ones
+    if (sliced && !(sched && mb.sched_hdr)) return hipErrorInvalidValue;
+    const SliceGradArgs sa = {mb.slices, mb.sched_hdr, mb.K, mb.perm_epochs};
     const bool split = (p.activation & SSG_POLICY_SEPARATE_VALUE) != 0;
     const PpoExtLaunch *ext = mb.ext;
     const int P = ppo_packed_len(p), G = ppo_grid(mb.M), stride = P + (ext ? kExtStats : 4);
@@ -1072,7 +1164,10 @@ hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream)
     const AdamArgs ad = mb.adam_mv && !pop ? adam_args(*mb.hp, mb.step) : AdamArgs{};
     const dim3 ggrid((unsigned)G, (unsigned)mb.members), rgrid((unsigned)((stride + 255) / 256), (unsigned)mb.members);
     if (!ext) {
-        if (sched) hipLaunchKernelGGL(grad_plain_sched(split), ggrid, dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a, pa, mb.sched);
+        if (sliced)
+            hipLaunchKernelGGL(split ? ppo_grad_sliced_kernel<true> : ppo_grad_sliced_kernel<false>, ggrid, dim3(kPpoBlock), ppo_grad_lds_bytes(p),
+                               stream, a, pa, mb.sched, sa);
+        else if (sched) hipLaunchKernelGGL(grad_plain_sched(split), ggrid, dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a, pa, mb.sched);
         else hipLaunchKernelGGL(grad_plain(pop, split), ggrid, dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a, pa);
         if (sched)
             hipLaunchKernelGGL(ppo_reduce_sched_kernel, rgrid, dim3(256), 0, stream, (const float *)a.slots, G, P, stride, mb.stats_out, params,
@@ -1088,7 +1183,10 @@ hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream)
     ea.kl_coef = ext->kl_coef;
     ea.pop_ext = ext->pop_ext;
     ea.vf_clip = ext->vf_clip;
-    if (sched) hipLaunchKernelGGL(grad_ext_sched(split), ggrid, dim3(kPpoBlock), ppo_grad_ext_lds_bytes(p), stream, a, pa, ea, mb.sched);
+    if (sliced)
+        hipLaunchKernelGGL(split ? ppo_grad_ext_sliced_kernel<true> : ppo_grad_ext_sliced_kernel<false>, ggrid, dim3(kPpoBlock),
+                           ppo_grad_ext_lds_bytes(p), stream, a, pa, ea, mb.sched, sa);
+    else if (sched) hipLaunchKernelGGL(grad_ext_sched(split), ggrid, dim3(kPpoBlock), ppo_grad_ext_lds_bytes(p), stream, a, pa, ea, mb.sched);
     else hipLaunchKernelGGL(grad_ext(pop, split), ggrid, dim3(kPpoBlock), ppo_grad_ext_lds_bytes(p), stream,
                        a, pa, ea);
     ExtReduceArgs er;
@@ -1152,11 +1250,17 @@ void pop_pack_steps(int members, const ssg_ppo_hparams *hp, const int64_t *step0
 }
 
 hipError_t launch_pop_gae(int members, int K, int N, const float *table, const double *rew, const uint8_t *done, const float *val,
-                          const float *last_val, float *adv, float *ret, void *ws, hipStream_t stream)
+                          const float *last_val, float *adv, float *ret, void *ws, hipStream_t stream, const int32_t *slices, int n_max)
 {
-    const int n = N / members, nb = ppo_gae_blocks(n);
+    const int n = slices ? n_max : N / members, nb = ppo_gae_blocks(n);
     float *stats = reinterpret_cast<float *>(static_cast<char *>(ws) + kPpoStatsOff);
     double2 *part = reinterpret_cast<double2 *>(static_cast<char *>(ws) + kPopSlotsOff);
+    if (slices) {
+        hipLaunchKernelGGL(pop_gae_sliced_kernel, dim3(nb, members), dim3(256), 0, stream, K, N, slices, nb, rew, done, val, last_val, adv, ret,
+                           table, part);
+        hipLaunchKernelGGL(pop_gae_stats_sliced_kernel, dim3(members), dim3(256), 0, stream, (const double2 *)part, nb, K, slices, table, stats);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(pop_gae_kernel, dim3(nb, members), dim3(256), 0, stream, K, N, n, nb, rew, done, val, last_val, adv, ret, table, part);
     hipLaunchKernelGGL(pop_gae_stats_kernel, dim3(members), dim3(256), 0, stream, (const double2 *)part, nb, (double)K * (double)n, table, stats);
     return hipGetLastError();
@@ -1173,8 +1277,13 @@ hipError_t launch_pop_exploit(const ssg_policy &p, int members, const int32_t *s
 }
 
 hipError_t launch_pop_episode_stats(int members, int K, int N, const double *rew, const uint8_t *done, double *carry_ret,
-                                    int32_t *carry_len, int64_t *out, hipStream_t stream)
+                                    int32_t *carry_len, int64_t *out, hipStream_t stream, const int32_t *slices, int n_max)
 {
+    if (slices) {
+        hipLaunchKernelGGL(pop_episode_stats_sliced_kernel, dim3((n_max + 255) / 256, members), dim3(256), 0, stream, K, N, slices, rew, done,
+                           carry_ret, carry_len, reinterpret_cast<unsigned long long *>(out));
+        return hipGetLastError();
+    }
     const int n = N / members;
     hipLaunchKernelGGL(pop_episode_stats_kernel, dim3((n + 255) / 256, members), dim3(256), 0, stream, K, N, n, rew, done, carry_ret,
                        carry_len, reinterpret_cast<unsigned long long *>(out));

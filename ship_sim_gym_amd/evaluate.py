@@ -160,11 +160,13 @@ class NativeEvaluator(object):
         self.steps += 1
 
     def reduce(self, n_members=1):
-        """ssg_eval_reduce: int64 [n_members, 8] column sums of each member's rows of env_stats (a view of this object's buffer)."""
+        """ssg_eval_reduce: int64 [n_members, 8] column sums of each member's rows of env_stats (a view of this object's buffer); a
+        member's rows are its slice of the env's set_population_slices when one is bound."""
         torch = _torch()
         env = self.env
         P = int(n_members)
-        if P < 1 or P > N.POP_MAX_MEMBERS or env.num_envs % P:
+        sizes = env.population_slices if P > 1 else None  # (one policy's reduce is over the whole handle)
+        if P < 1 or P > N.POP_MAX_MEMBERS or (len(sizes) != P if sizes is not None else env.num_envs % P):
             raise ValueError("evaluate: %d envs do not split into %d member slices" % (env.num_envs, P))
         with torch.cuda.device(env.device):
             N.check(N.lib().ssg_eval_reduce(env._h, P, C.c_void_p(self.env_stats.data_ptr()), C.c_void_p(self.member_stats.data_ptr()),

@@ -10,7 +10,9 @@ The handle's envs are split into P equal contiguous slices: member m owns envs [
 [P, L]; row m is a packed buffer of its own, and ``member(m)`` is a ``NativePolicy`` that shares it.  Hyper-parameters are per member
 (plain Python lists on ``PopulationPPO`` that a scheduler may rewrite between updates), and so may the epochs and the minibatch count
 of an update be (``update`` with lists: ssg_pop_update_sched — launch j then serves minibatch j of every member that still has one);
-the batch size is common to the population, which lives on one handle with one architecture.  The extended loss terms of
+so may the batch size, as a member's share of the handle's envs (``ShipVecEnv.set_population_slices``: contiguous slices of unequal
+size; ``slices_for_batch_sizes`` turns batch sizes into slices) — every member still rolls out the same K steps on one handle with one
+architecture, and an update on unequal slices always runs on the schedule path.  The extended loss terms of
 ``NativePPO`` — ``vf_clip``, ``max_grad_norm``, ``kl_coef``, ``kl_target`` — are per member as well (``EXT_KEYS``); a member whose value
 is 0 has that term off and trains exactly as ``NativePPO`` without it.
 
@@ -20,6 +22,7 @@ configures it, with the interval counted in updates instead of seconds of wall t
 import ctypes as C
 import math
 import random
+from fractions import Fraction
 
 from . import _native as N
 from .policy import ACTIVATIONS, NativePolicy
@@ -139,8 +142,7 @@ class PopulationPPO(object):
         if env.states_history != population.obs_dim:
             raise ValueError("PopulationPPO: the env's observation width %d differs from the population's obs_dim %d"
                              % (env.states_history, population.obs_dim))
-        if env.num_envs % P:
-            raise ValueError("PopulationPPO: %d envs do not split into %d equal member slices" % (env.num_envs, P))
+        env._check_population(population, "PopulationPPO")  # (the env's slices for P members, else an equal split)
         given = dict(gamma=gamma, lam=lam, clip=clip, vf_coef=vf_coef, ent_coef=ent_coef, lr=lr, beta1=beta1, beta2=beta2, eps=eps,
                      adv_eps=adv_eps, vf_clip=vf_clip, max_grad_norm=max_grad_norm, kl_target=kl_target, kl_coef=kl_coef)
         for k in HPARAM_KEYS + EXT_KEYS + ("kl_coef",):
@@ -149,7 +151,7 @@ class PopulationPPO(object):
             if len(v) != P:
                 raise ValueError("PopulationPPO: %s has %d entries for %d members" % (k, len(v), P))
             setattr(self, k, v)
-        self.n_members, self.n_params, self.envs_per_member = P, population.n_params, env.num_envs // P
+        self.n_members, self.n_params = P, population.n_params
         dev = population.device
         self.adam_mv = torch.zeros((P, 2 * self.n_params), dtype=torch.float32, device=dev)  # per member: m, then v
         self.step = 0  # Adam steps taken (common to the population while every update steps every member alike)
@@ -160,7 +162,26 @@ class PopulationPPO(object):
         self.carry_return = torch.zeros(env.num_envs, dtype=torch.float64, device=dev)
         self.carry_length = torch.zeros(env.num_envs, dtype=torch.int32, device=dev)
         self.kl_coef = torch.tensor(self.kl_coef, dtype=torch.float32).to(dev)  # (the list set above becomes the device tensor)
-        self._last_samples = 0  # K * envs_per_member of the last batch gae() or update() saw (minibatches_for_size's default)
+        self._last_K = 0  # the rollout length of the last batch gae() or update() saw (minibatches_for_size's default)
+
+    @property
+    def member_envs(self):
+        """The members' env counts, a list of P ints: the env's slices (``set_population_slices``, read at every call, so the layout
+        may change between updates), else the equal split."""
+        sizes = self.env.population_slices
+        if sizes is None:
+            return [self.env.num_envs // self.n_members] * self.n_members
+        if len(sizes) != self.n_members:
+            raise ValueError("PopulationPPO: slices for %d members are bound to the env, the population has %d" % (len(sizes), self.n_members))
+        return sizes
+
+    @property
+    def envs_per_member(self):
+        """The env count every member has; raises when the env's slices are unequal (``member_envs`` lists them)."""
+        sizes = self.member_envs
+        if len(set(sizes)) > 1:
+            raise ValueError("PopulationPPO.envs_per_member: the members' slices are unequal (%s): see member_envs" % (sizes,))
+        return sizes[0]
 
     # ------------------------------------------------------------------------------------------------
     def hparams(self):
@@ -200,21 +221,32 @@ class PopulationPPO(object):
                     "ssg_pop_pack_hparams_steps")
         return torch.tensor(list(buf), dtype=torch.float32).to(self.population.device)
 
-    def minibatches_for_size(self, size, samples=None):
+    def minibatches_for_size(self, size, samples=None, member=None):
         """The minibatch count that makes minibatches of at most `size` samples out of a member's `samples` (default: the last
-        batch's K * envs_per_member): ceil(samples / size), clamped to [1, samples].  The chunk lengths stay torch.chunk's — every
+        batch's K * envs_per_member, or with member=m K * member_envs[m], that member's own): ceil(samples / size), clamped to [1, samples].  The chunk lengths stay torch.chunk's — every
         chunk ceil(samples / count) long and the last one shorter, so chunks of AT MOST `size` — not RLlib's slicing of exactly
         sgd_minibatch_size samples with a shorter remainder."""
-        n = int(self._last_samples if samples is None else samples)
+        if samples is None:
+            samples = self._last_K * (self.envs_per_member if member is None else self.member_envs[int(member)])
+        n = int(samples)
         if n < 1:
             raise ValueError("PopulationPPO.minibatches_for_size: no batch seen yet; pass samples=")
         return max(1, min(n, -(-n // max(1, int(size)))))
 
     def pack_schedule(self, samples, epochs, minibatches):
-        """(int32 host table as a ctypes array, steps per member, launches) of ssg_pop_pack_schedule."""
+        """(int32 host table as a ctypes array, steps per member, launches) of ssg_pop_pack_schedule — or, with `samples` a list of P
+        counts, of ssg_pop_pack_schedule_samples."""
         P = self.n_members
         ep, mb = (C.c_int32 * P)(*[int(e) for e in epochs]), (C.c_int32 * P)(*[int(b) for b in minibatches])
         steps, launches = (C.c_int32 * P)(), C.c_int32()
+        if isinstance(samples, (list, tuple)):
+            sm = (C.c_int64 * P)(*[int(x) for x in samples])
+            fn, what = N.lib().ssg_pop_pack_schedule_samples, "ssg_pop_pack_schedule_samples"
+            N.check(fn(P, sm, ep, mb, None, 0, steps, C.byref(launches)), None, what)
+            n = N.pop_sched_ints(P, launches.value)
+            buf = (C.c_int32 * n)()
+            N.check(fn(P, sm, ep, mb, buf, n, steps, C.byref(launches)), None, what)
+            return buf, list(steps), int(launches.value)
         N.check(N.lib().ssg_pop_pack_schedule(P, int(samples), ep, mb, None, 0, steps, C.byref(launches)), None, "ssg_pop_pack_schedule")
         n = N.pop_sched_ints(P, launches.value)
         buf = (C.c_int32 * n)()
@@ -261,8 +293,8 @@ class PopulationPPO(object):
         dev = self.population.device
         p = [self._flat(batch, "rew", torch.float64, (K, n_env)), self._flat(batch, "done", torch.uint8, (K, n_env)),
              self._flat(batch, "val", torch.float32, (K, n_env)), self._flat(batch, "last_val", torch.float32, (n_env,))]
-        self._ws(K * self.envs_per_member, 1)
-        self._last_samples = K * self.envs_per_member
+        self._ws(K * max(self.member_envs), 1)
+        self._last_K = K
         adv = torch.empty((K, n_env), dtype=torch.float32, device=dev)
         ret = torch.empty_like(adv)
         pop, h = self.population.to_native(), self.env._h
@@ -327,12 +359,18 @@ class PopulationPPO(object):
         (``minibatches_for_size`` turns a minibatch size into a count), still from ONE library call (ssg_pop_update_sched) whose launch
         j serves minibatch j of every member that has one left.  perm is then int64 [P, max(epochs), K*n] (member m reads its first
         epochs[m] rows), the stats f32 [P, n_launches, cols], zero in a member's rows past its own steps, and each member advances
-        ``member_steps`` by its own steps.  Either way member m's results are bitwise NativePPO.update's on its shard."""
+        ``member_steps`` by its own steps.  Either way member m's results are bitwise NativePPO.update's on its shard.
+
+        With slices bound to the env (``set_population_slices``) the update always runs on the schedule path, scalar epochs /
+        minibatches broadcast; member m has K * member_envs[m] samples, and perm is a list of P tensors int64 [max(epochs), K * n_m]
+        (or the flat buffer they concatenate to, member after member: nothing is padded to the widest member)."""
         torch = _torch()
         K, n_env = self._KN(batch)
         P, dev, D = self.n_members, self.population.device, self.population.obs_dim
+        self._last_K = K
+        if self.env.population_slices is not None:
+            return self._update_sched(batch, perm, epochs, minibatches, stats, K, n_env, [K * n_m for n_m in self.member_envs])
         n = K * self.envs_per_member
-        self._last_samples = n
         if isinstance(epochs, (list, tuple)) or isinstance(minibatches, (list, tuple)):
             return self._update_sched(batch, perm, epochs, minibatches, stats, K, n_env, n)
         p = [self._flat(batch, "obs", torch.float32, (K, n_env, D)), self._flat(batch, "act", torch.int32, (K, n_env)),
@@ -367,7 +405,7 @@ class PopulationPPO(object):
         return st
 
     def _update_sched(self, batch, perm, epochs, minibatches, stats, K, n_env, n):
-        """update() on per-member schedules (ssg_pop_update_sched)."""
+        """update() on per-member schedules (ssg_pop_update_sched).  n: the samples per member, or (slices bound) a list of P counts."""
         torch = _torch()
         P, dev, D = self.n_members, self.population.device, self.population.obs_dim
         epochs = [int(e) for e in epochs] if isinstance(epochs, (list, tuple)) else [int(epochs)] * P
@@ -379,12 +417,25 @@ class PopulationPPO(object):
         p = [self._flat(batch, "obs", torch.float32, (K, n_env, D)), self._flat(batch, "act", torch.int32, (K, n_env)),
              self._flat(batch, "logp", torch.float32, (K, n_env)), self._flat(batch, "adv", torch.float32, (K, n_env)),
              self._flat(batch, "ret", torch.float32, (K, n_env))]
-        perm = perm.to(device=dev, dtype=torch.int64).contiguous()
-        if tuple(perm.shape) != (P, max(epochs), n):
-            raise ValueError("PopulationPPO.update: perm must be int64 [%d, %d, %d] = [P, max(epochs), K*n] (got %s)"
-                             % (P, max(epochs), n, tuple(perm.shape)))
+        if isinstance(n, list):
+            if isinstance(perm, (list, tuple)):
+                if len(perm) != P or any(tuple(q.shape) != (max(epochs), n[m]) for m, q in enumerate(perm)):
+                    raise ValueError("PopulationPPO.update: perm must list %d tensors int64 [max(epochs) = %d, K*n_m] with K*n_m = %s"
+                                     % (P, max(epochs), n))
+                perm = torch.cat([q.to(device=dev, dtype=torch.int64).reshape(-1) for q in perm])
+            perm = perm.to(device=dev, dtype=torch.int64).contiguous()
+            if perm.numel() != max(epochs) * sum(n):
+                raise ValueError("PopulationPPO.update: the flat perm must hold max(epochs) * sum(K*n_m) = %d indices (got %d)"
+                                 % (max(epochs) * sum(n), perm.numel()))
+            n_max, c_max = max(n), max(chunk_split(n[m], minibatches[m])[0] for m in range(P))
+        else:
+            perm = perm.to(device=dev, dtype=torch.int64).contiguous()
+            if tuple(perm.shape) != (P, max(epochs), n):
+                raise ValueError("PopulationPPO.update: perm must be int64 [%d, %d, %d] = [P, max(epochs), K*n] (got %s)"
+                                 % (P, max(epochs), n, tuple(perm.shape)))
+            n_max, c_max = n, max(chunk_split(n, b)[0] for b in minibatches)
         sched, steps, launches = self.pack_schedule(n, epochs, minibatches)
-        self._ws(n, max(chunk_split(n, b)[0] for b in minibatches))
+        self._ws(n_max, c_max)
         extended = self.extended()
         st = torch.zeros((P, launches, N.PPO_EXT_STATS if extended else 4), dtype=torch.float32, device=dev) if stats else None
         ep, mb = (C.c_int32 * P)(*epochs), (C.c_int32 * P)(*minibatches)
@@ -430,7 +481,8 @@ class PopulationPPO(object):
 
     def episode_stats(self, batch):
         """int64 [P, 3] device tensor: per member (100 * sum of returns, sum of lengths, episodes) of the episodes that ENDED in this
-        rollout batch; episodes spanning batches are carried and counted once, at their end."""
+        rollout batch; episodes spanning batches are carried and counted once, at their end.  The carries are per env: after a
+        re-slice an episode in flight is credited to whichever member owns the env when it ends."""
         torch = _torch()
         K, n_env = self._KN(batch)
         dev = self.population.device
@@ -450,11 +502,41 @@ class PopulationPPO(object):
 LR_CHOICES = [1e-3, 5e-4, 1e-4, 5e-5, 1e-5]
 
 
-def reference_mutations(schedule=False):
-    """The reference's mutated hyper-parameters (train/rllib/pbt.py:34-41) that can vary per member here: a callable draws a fresh
+def slices_for_batch_sizes(batch_sizes, n_envs, quantum=64):
+    """Slice sizes (P ints summing to n_envs, each a multiple of `quantum`) for members that ask for `batch_sizes` samples per update.
+
+    The handle's K * n_envs samples per update are fixed, so a member's train_batch_size is its SHARE of them, not an absolute
+    count: two populations with batch sizes (1, 2) and (10000, 20000) get the same slices.  Deterministic apportionment: n_envs must be
+    a multiple of quantum and hold at least one quantum per member; every member gets one quantum, and the remaining quanta are dealt
+    by largest remainder in proportion to batch_sizes (ties to the lower index), so no member ends more than one quantum away from
+    its exact proportional share of them."""
+    sizes = [b if isinstance(b, int) else float(b) for b in batch_sizes]
+    P, n_envs, quantum = len(sizes), int(n_envs), int(quantum)
+    if P < 1 or quantum < 1 or n_envs < 1:
+        raise ValueError("slices_for_batch_sizes: at least one member, quantum >= 1 and n_envs >= 1")
+    if any(not (b > 0.0) or b == float("inf") for b in sizes):
+        raise ValueError("slices_for_batch_sizes: every batch size must be a positive finite number")
+    if n_envs % quantum:
+        raise ValueError("slices_for_batch_sizes: n_envs = %d is not a multiple of the quantum %d" % (n_envs, quantum))
+    rest = n_envs // quantum - P
+    if rest < 0:
+        raise ValueError("slices_for_batch_sizes: %d envs hold fewer than one quantum of %d per member (%d members)" % (n_envs, quantum, P))
+    sizes = [Fraction(b) for b in sizes]  # (exact, also for floats: the remainders are compared without rounding)
+    total = sum(sizes)
+    exact = [rest * b / total for b in sizes]
+    whole = [int(math.floor(x)) for x in exact]
+    order = sorted(range(P), key=lambda m: (-(exact[m] - whole[m]), m))
+    for m in order[:rest - sum(whole)]:
+        whole[m] += 1
+    return [quantum * (1 + w) for w in whole]
+
+
+def reference_mutations(schedule=False, batch=False):
+    """The reference's mutated hyper-parameters (train/rllib/pbt.py:34-42) that can vary per member here: a callable draws a fresh
     value from the generator it is handed; a list is a set of choices.  By default the three that leave the launches alone;
     schedule=True appends the two that set a member's update schedule, num_sgd_iter and sgd_minibatch_size (pbt.py:40-41), which
-    ``PopulationPPO.update`` takes per member.  (train_batch_size, the sixth, stays common to the population.)"""
+    ``PopulationPPO.update`` takes per member; batch=True the sixth, train_batch_size (pbt.py:42), which becomes the member's share of
+    the handle's envs (``slices_for_batch_sizes``)."""
     out = {
         "lambda": lambda rng: rng.uniform(0.9, 1.0),
         "clip_param": lambda rng: rng.uniform(0.01, 0.5),
@@ -463,6 +545,8 @@ def reference_mutations(schedule=False):
     if schedule:
         out["num_sgd_iter"] = lambda rng: rng.randint(1, 30)
         out["sgd_minibatch_size"] = lambda rng: rng.randint(128, 16384)
+    if batch:
+        out["train_batch_size"] = lambda rng: rng.randint(2000, 160000)
     return out
 
 

@@ -679,11 +679,52 @@ class ShipVecEnv(*_BASES):
     # ------------------------------------------------------------------------------------------------
     def _check_population(self, population, what):
         self._check_policy(population, what)
-        if self.num_envs % len(population):
+        sizes = self.population_slices
+        if sizes is not None:
+            if len(sizes) != len(population):
+                raise ValueError("%s: %d members, but slices for %d members are bound (set_population_slices)"
+                                 % (what, len(population), len(sizes)))
+        elif self.num_envs % len(population):
             raise ValueError("%s: %d envs do not split into %d equal member slices" % (what, self.num_envs, len(population)))
 
+    def set_population_slices(self, sizes):
+        """Lay a population out over this handle's envs in contiguous slices of unequal size (ssg_pop_set_slices): member m owns
+        sizes[m] envs from sum(sizes[:m]) on; every size >= 1, sum(sizes) == num_envs.  While bound, every population call on this env
+        (population_act, rollout_population, PopulationPPO, NativeEvaluator) follows the slices and takes a population of len(sizes)
+        members only.  None unbinds.  Env state is not touched: envs are fungible, so a layout may be re-bound between updates."""
+        torch = _torch()
+        if sizes is None:
+            N.check(N.lib().ssg_pop_set_slices(self._h, 0, None, None), self._h, "ssg_pop_set_slices")
+            self._pop_slices = None
+            return
+        sizes = [int(s) for s in sizes]
+        P = len(sizes)
+        arr = (C.c_int32 * max(P, 1))(*sizes)
+        n = N.POP_SLICE_ROW * P
+        buf = (C.c_int32 * max(n, 1))()
+        N.check(N.lib().ssg_pop_pack_slices(P, arr, buf, n), None, "ssg_pop_pack_slices")
+        if sum(sizes) != self.num_envs:
+            raise ValueError("set_population_slices: the sizes sum to %d, the handle has %d envs" % (sum(sizes), self.num_envs))
+        table = torch.tensor(list(buf), dtype=torch.int32).to(self.device)
+        N.check(N.lib().ssg_pop_set_slices(self._h, P, arr, C.c_void_p(table.data_ptr())), self._h, "ssg_pop_set_slices")
+        # (the device table is the caller's memory; an earlier one stays alive until launches that read it have been enqueued AND run:
+        # torch's allocator does not hand a freed block to another stream's work before that)
+        self._pop_slices = (sizes, table)
+
+    @property
+    def population_slices(self):
+        """The bound slice sizes (a list of P ints, as the library holds them: ssg_pop_get_slices), or None."""
+        if getattr(self, "_pop_slices", None) is None:
+            return None
+        P = C.c_int()
+        N.check(N.lib().ssg_pop_get_slices(self._h, C.byref(P), None), self._h, "ssg_pop_get_slices")
+        out = (C.c_int32 * max(P.value, 1))()
+        N.check(N.lib().ssg_pop_get_slices(self._h, C.byref(P), out), self._h, "ssg_pop_get_slices")
+        return [int(out[m]) for m in range(P.value)] or None
+
     def population_act(self, population, seed=0, step=0, uniforms=None, x_out=None, greedy=False):
-        """policy_act with env e evaluated under member e // (N / P) of a NativePopulation (ssg_pop_act, one launch): returns (act
+        """policy_act with env e evaluated under member e // (N / P) of a NativePopulation — or, with set_population_slices, under the
+        member whose slice holds it — (ssg_pop_act, one launch): returns (act
         int32 [N], logp [N], value [N], x [N, D] float32) device tensors.  uniforms / x_out / Philox keying / greedy as policy_act
         (greedy=True: ssg_pop_act_greedy)."""
         torch = _torch()
@@ -712,7 +753,7 @@ class ShipVecEnv(*_BASES):
     def rollout_population(self, population, K, seed=0, step0=0, uniforms=None, out=None):
         """rollout_policy with env e acting under member e // (N / P) of a NativePopulation (ssg_pop_rollout: one policy launch per step
         for the whole population, then ssg_step).  Same out-dict, uniforms, Philox keying and `out` as rollout_policy; member m's
-        columns are [m*n, (m+1)*n), n = N / P."""
+        columns are [m*n, (m+1)*n), n = N / P, or its slice of set_population_slices."""
         torch = _torch()
         self._check_population(population, "rollout_population")
         K, n = int(K), self.num_envs

@@ -21,10 +21,20 @@ With ``--sched`` (per-member schedules, ssg_pop_update_sched), instead, per conf
 (d) a SKEWED schedule — epochs 1..4 cycling over the members, minibatches cycling over 1, 4, 16 — through the per-member entry
     against a loop of the members' ``NativePPO.update`` with the same schedules.
 
+With ``--slices`` (per-member batch sizes: unequal env slices, ssg_pop_set_slices), instead, per configuration, on ONE handle whose
+layout is re-bound between the runs (binding is not timed):
+
+(e) EQUAL slices bound against nothing bound: the rollout step, and GAE + update (bound: the schedule path, which a sliced update
+    always takes; unbound: the common entry, whose code the slices do not touch: the yardstick).  ``*_spread`` is (max - min) / median
+    over the unbound path's repeats.
+(f) a SKEWED layout — batch shares cycling 1 : 2 : 4 : 8 over the members through ``slices_for_batch_sizes`` (quantum 64) — against
+    the equal layout at the same N: the rollout step; and its GAE + update against a loop of the members' ``NativePPO.gae`` +
+    ``.update`` on shards of those sizes.
+
 Each figure: 2 warm-up runs, then the median of ``--repeats`` (5) runs, alternating the two paths, each bracketed by a synchronize and
 timed with HIP events.  One JSON line on stdout.
 
-    python tools/population_timing.py [--configs 16x4096,120x512] [--horizon 32] [--repeats 5] [--sched]
+    python tools/population_timing.py [--configs 16x4096,120x512] [--horizon 32] [--repeats 5] [--sched | --slices]
 """
 import argparse
 import importlib.util
@@ -226,14 +236,130 @@ def measure_sched(mod, members, n, horizon, repeats, dev, epochs=2, minibatches=
     return out
 
 
+def measure_slices(mod, members, n, horizon, repeats, dev, epochs=2, minibatches=4):
+    from ship_sim_gym_amd.population import NativePopulation, PopulationPPO, slices_for_batch_sizes
+    from ship_sim_gym_amd.ppo import NativePPO
+    torch.manual_seed(0)
+    P, N = members, members * n
+    env = mod.ShipVecEnv(N, mod.GameConfig, mod.EnvConfig, device=dev, n_maps=64)
+    D, A = env.states_history, env.action_space.n
+    scale = torch.full((D,), float(max(env.bounds)), dtype=torch.float64, device=dev)
+    nets = [mod.ActorCritic(D, A).to(dev) for _ in range(P)]
+    pop = NativePopulation.from_actor_critics(nets, scale)
+    seq = NativePopulation.from_actor_critics(nets, scale)
+    p0 = pop.params.clone()
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    U = torch.rand((horizon, N), generator=gen, device=dev)
+    skew = slices_for_batch_sizes([(1, 2, 4, 8)[m % 4] for m in range(P)], N, 64)
+    offs = [sum(skew[:m]) for m in range(P)]
+    layouts = {"unbound": None, "equal": [n] * P, "skew": skew}
+    out = {"members": P, "envs": N, "horizon": horizon, "epochs": epochs, "minibatches": minibatches, "skew_shares": "1, 2, 4, 8 cycling",
+           "skew_min_envs": min(skew), "skew_max_envs": max(skew)}
+
+    # the rollout step under the three layouts
+    bufs = {}
+
+    def bind(k):
+        env.set_population_slices(layouts[k])
+        env.reset_tensor()
+
+    def roll(k):
+        def f():
+            bufs[k] = env.rollout_population(pop, horizon, uniforms=U, out=bufs.get(k))
+        return f
+
+    t = _alternate([(k, roll(k)) for k in layouts], repeats, before=bind)
+    for k in layouts:
+        out[k + "_step_us"] = statistics.median(t[k]) * 1e3 / horizon
+        out[k + "_step_us_all"] = [round(x * 1e3 / horizon, 2) for x in t[k]]
+    out["step_spread"] = (max(t["unbound"]) - min(t["unbound"])) / statistics.median(t["unbound"])
+    out["equal_step_over_unbound"] = out["equal_step_us"] / out["unbound_step_us"]
+    out["skew_step_over_equal"] = out["skew_step_us"] / out["equal_step_us"]
+    out["equal_rollout_bitwise_equal"] = all(bool(torch.equal(bufs["unbound"][k], bufs["equal"][k])) for k in bufs["unbound"])
+
+    # GAE + update: equal slices bound against nothing bound
+    ppo = PopulationPPO(pop, env)
+    samples = horizon * n
+    perm = torch.rand((P, epochs, samples), generator=gen, device=dev).argsort(dim=-1)
+    perm_list = [perm[m] for m in range(P)]
+    b_eq = {k: v.clone() for k, v in bufs["unbound"].items()}
+    finals = {}
+
+    def restore(k):
+        env.set_population_slices(layouts[k])
+        pop.params.copy_(p0)
+        ppo.adam_mv.zero_()
+        ppo.step, ppo.member_steps = 0, [0] * P
+
+    def upd(k):
+        def f():
+            nb = dict(b_eq)
+            ppo.gae(nb)
+            ppo.update(nb, perm_list if k == "equal" else perm, epochs, minibatches)
+            finals[k] = pop.params.clone()
+        return f
+
+    t = _alternate([(k, upd(k)) for k in ("unbound", "equal")], repeats, before=restore)
+    for k in ("unbound", "equal"):
+        out[k + "_update_ms"] = statistics.median(t[k])
+        out[k + "_update_ms_all"] = [round(x, 3) for x in t[k]]
+    out["update_spread"] = (max(t["unbound"]) - min(t["unbound"])) / statistics.median(t["unbound"])
+    out["equal_update_over_unbound"] = out["equal_update_ms"] / out["unbound_update_ms"]
+    out["equal_update_bitwise_equal"] = bool(torch.equal(finals["unbound"], finals["equal"]))
+
+    # GAE + update on the skewed layout against a loop over shards of those sizes
+    b_sk = {k: v.clone() for k, v in bufs["skew"].items()}
+    perm_sk = [torch.rand((epochs, horizon * s), generator=gen, device=dev).argsort(dim=-1) for s in skew]
+    shards = [{k: (v[:, o:o + s] if k != "last_val" else v[o:o + s]).contiguous() for k, v in b_sk.items()} for o, s in zip(offs, skew)]
+    seq_ppos = [NativePPO(seq.member(m), env) for m in range(P)]
+
+    def restore_sk(k):
+        if k == "skew_pop":
+            restore("skew")
+        else:
+            seq.params.copy_(p0)
+            for q in seq_ppos:
+                q.adam_mv.zero_()
+                q.step = 0
+
+    def skew_pop():
+        nb = dict(b_sk)
+        ppo.gae(nb)
+        ppo.update(nb, perm_sk, epochs, minibatches)
+        finals["skew_pop"] = pop.params.clone()
+
+    def skew_seq():
+        for m in range(P):
+            nb = dict(shards[m])
+            seq_ppos[m].gae(nb)
+            seq_ppos[m].update(nb, perm_sk[m], epochs, minibatches)
+        finals["skew_seq"] = seq.params.clone()
+
+    t = _alternate([("skew_seq", skew_seq), ("skew_pop", skew_pop)], repeats, before=restore_sk)
+    for k in ("skew_seq", "skew_pop"):
+        out[k + "_update_ms"] = statistics.median(t[k])
+        out[k + "_update_ms_all"] = [round(x, 3) for x in t[k]]
+    out["skew_update_speedup"] = out["skew_seq_update_ms"] / out["skew_pop_update_ms"]
+    out["skew_update_bitwise_equal"] = bool(torch.equal(finals["skew_seq"], finals["skew_pop"]))
+    env.set_population_slices(None)
+    env.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="16x4096,120x512")
     ap.add_argument("--horizon", type=int, default=32)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--sched", action="store_true", help="time per-member schedules (ssg_pop_update_sched) instead")
+    ap.add_argument("--slices", action="store_true", help="time unequal env slices (ssg_pop_set_slices) instead")
     a = ap.parse_args()
     mod = _ppo()
+    if a.slices:
+        res = [measure_slices(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.horizon, a.repeats, "cuda:0") for c in a.configs.split(",")]
+        print(json.dumps({"population_slices_timing": res}))
+        return
     if a.sched:
         res = [measure_sched(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.horizon, a.repeats, "cuda:0") for c in a.configs.split(",")]
         print(json.dumps({"population_sched_timing": res}))

@@ -7,6 +7,8 @@ line changed and needs ray; this one needs only the library.
     python train/pbt_native.py --lrs 1e-3,1e-4,1e-5 --no-pbt        # the learning-rate sweep of train/stable_baselines/ppo.py:118-137
     python train/pbt_native.py --mutate-schedule                    # num_sgd_iter and sgd_minibatch_size per member too (pbt.py:40-41)
     python train/pbt_native.py --members 3 --epochs 1,2,4 --minibatches 4,4,8 --no-pbt   # a sweep over schedules
+    python train/pbt_native.py --members 4 --envs 256 --mutate-batch --mutate-schedule   # train_batch_size per member too (pbt.py:42)
+    python train/pbt_native.py --members 3 --batch-shares 1,2,4 --no-pbt                 # a sweep over batch sizes
 
 One ShipVecEnv of members x envs-per-member envs; member m owns the contiguous slice [m*n, (m+1)*n).  Every update is one
 ``rollout_population`` (one policy launch per step for the whole population), then ``PopulationPPO.gae`` and ``.update`` (two launches
@@ -21,9 +23,16 @@ What differs from the reference, on purpose:
 * of the six mutated hyper-parameters lambda, clip_param and lr always vary per member; num_sgd_iter and sgd_minibatch_size do with
   --mutate-schedule (initial draws from the reference's {10, 20, 30} and {128, 512, 2048}, train/rllib/pbt.py:65-68; mutated as
   :40-41; the source's schedule travels with an exploit) and are otherwise set by --epochs / --minibatches, which also take
-  comma-separated per-member lists; train_batch_size is common to the population (--horizon x --envs-per-member);
+  comma-separated per-member lists;
+* train_batch_size, the sixth, is a member's SHARE of the handle's envs (--mutate-batch: initial draws from the reference's {10000,
+  20000, 40000}, train/rllib/pbt.py:69-70, mutated as :42, travelling with an exploit; --batch-shares a,b,c: fixed shares for a sweep).
+  The handle's horizon x envs samples per update are fixed, so the values are turned into contiguous env slices of unequal size by
+  ``slices_for_batch_sizes`` (multiples of --quantum envs, at least one quantum each) and member m trains on horizon x n_m samples.
+  After every perturbation the handle is re-sliced from the members' current values and the new sizes are logged.  Envs are fungible:
+  a re-slice touches no env state; the episode carries are per env and are kept, so an episode in flight is credited to whichever
+  member owns the env when it ends.  Without either flag train_batch_size is common to the population (--horizon x --envs-per-member);
 * a schedule is clamped before use: num_sgd_iter to [1, --max-epochs] (the permutations are drawn as [P, max-epochs, samples]) and the
-  minibatch size to [min(128, samples), samples].  ray clamps nothing: there a trial whose sgd_minibatch_size exceeds its
+  minibatch size to [min(128, samples), samples], samples being the member's own (horizon x its slice).  ray clamps nothing: there a trial whose sgd_minibatch_size exceeds its
   train_batch_size simply fails.  A minibatch size becomes a minibatch count (ceil(samples / size)), and the chunks are torch.chunk's:
   at most `size` long, not RLlib's exact slices;
 * one handle on one GPU, one architecture.
@@ -47,6 +56,21 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 INITIAL = {"lambda": 0.95, "clip_param": 0.2, "lr": 5e-4}  # train/rllib/pbt.py:60-62
 INITIAL_SCHEDULE = {"num_sgd_iter": [10, 20, 30], "sgd_minibatch_size": [128, 512, 2048]}  # train/rllib/pbt.py:65-68
+INITIAL_BATCH = [10000, 20000, 40000]  # train_batch_size, train/rllib/pbt.py:69-70
+
+
+def default_quantum(n_envs, members):
+    """The slice quantum when none is given: 64 envs (the policy kernel's tile) where that leaves at least four quanta per member,
+    else the largest smaller power of two that does and divides n_envs (at least 1)."""
+    q = 64
+    while q > 1 and (n_envs % q or n_envs // q < 4 * members):
+        q //= 2
+    return q
+
+
+def initial_batch_sizes(sched, members):
+    """The members' initial train_batch_size draws (from the scheduler's generator, after the schedule's draws when there are any)."""
+    return [sched.rng.choice(INITIAL_BATCH) for _ in range(members)]
 
 
 def clamp_schedule(num_sgd_iter, sgd_minibatch_size, samples, max_epochs):
@@ -58,6 +82,12 @@ def make_arg_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--members", type=int, default=16, help="population size (the reference: 120 samples)")
     ap.add_argument("--envs-per-member", type=int, default=512)
+    ap.add_argument("--envs", type=int, default=None, help="the handle's envs in all (overrides --envs-per-member: envs / members each)")
+    ap.add_argument("--mutate-batch", action="store_true",
+                    help="train_batch_size per member as its share of the envs: drawn from the reference's set, mutated and exploited; "
+                         "the handle is re-sliced after every perturbation")
+    ap.add_argument("--batch-shares", default=None, help="comma-separated fixed batch shares, one member each (unequal env slices; overrides --members)")
+    ap.add_argument("--quantum", type=int, default=None, help="slice sizes are multiples of this many envs (default: 64, less on a small handle)")
     ap.add_argument("--updates", type=int, default=40)
     ap.add_argument("--horizon", type=int, default=32, help="rollout steps per update (common to the population)")
     ap.add_argument("--perturb-every", type=int, default=5, help="perturbation interval in UPDATES (the reference: 600 s of wall time)")
@@ -104,6 +134,27 @@ def parse_args(argv=None):
             a.members = lists[0]
         if any(n != a.members for n in lists):
             ap.error("--epochs / --minibatches list %s entries for %d members" % (lists, a.members))
+    if a.batch_shares is not None:
+        try:
+            a.batch_shares = [float(x) for x in a.batch_shares.split(",")]
+        except ValueError:
+            ap.error("--batch-shares takes a comma-separated list of numbers")
+        if min(a.batch_shares) <= 0:
+            ap.error("--batch-shares must be > 0")
+        if a.mutate_batch:
+            ap.error("--batch-shares and --mutate-batch exclude each other")
+        if a.lrs is None and not lists:
+            a.members = len(a.batch_shares)
+        if len(a.batch_shares) != a.members:
+            ap.error("--batch-shares lists %d entries for %d members" % (len(a.batch_shares), a.members))
+    if a.envs is not None:
+        if a.envs < a.members:
+            ap.error("--envs must hold at least one env per member")
+        a.envs_per_member = max(1, a.envs // a.members)
+        if not (a.mutate_batch or a.batch_shares) and a.envs % a.members:
+            ap.error("--envs must be a multiple of --members (equal slices)")
+    if a.quantum is not None and a.quantum < 1:
+        ap.error("--quantum must be >= 1")
     if a.max_epochs < 1:
         ap.error("--max-epochs must be >= 1")
     if a.members < 1 or a.envs_per_member < 1 or a.updates < 1 or a.horizon < 1 or a.perturb_every < 1:
@@ -117,25 +168,36 @@ def parse_args(argv=None):
 
 def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every=5, seed=0, epochs=2, minibatches=4, lrs=None,
           pbt=True, device="cuda:0", log=print, return_details=False, kl_coeff=0.0, kl_target=0.01, vf_clip=0.0, max_grad_norm=0.0,
-          separate_value=False, mutate_schedule=False, max_epochs=30, eval_every=0, eval_episodes=1):
+          separate_value=False, mutate_schedule=False, max_epochs=30, eval_every=0, eval_episodes=1, envs=None, mutate_batch=False,
+          batch_shares=None, quantum=None):
     import torch
     from ship_gym.config import EnvConfig, GameConfig
-    from ship_sim_gym_amd.population import NativePopulation, PBTScheduler, PopulationPPO, reference_mutations
+    from ship_sim_gym_amd.population import NativePopulation, PBTScheduler, PopulationPPO, reference_mutations, slices_for_batch_sizes
     from ship_sim_gym_amd.ppo import chunk_split
     from ship_sim_gym_amd.vec_env import ShipVecEnv
     from train.ppo_torch import ActorCritic
     from train.rllib_ppo import game_configuration
 
     P, n = int(members), int(envs_per_member)
+    n_total = int(envs) if envs is not None else P * n
+    sliced = bool(mutate_batch) or batch_shares is not None
+    if mutate_batch and batch_shares is not None:
+        raise ValueError("train: mutate_batch and batch_shares exclude each other")
+    if not sliced and n_total % P:
+        raise ValueError("train: %d envs do not split into %d equal member slices" % (n_total, P))
+    n = max(1, n_total // P)
     if lrs is not None and len(lrs) != P:
         raise ValueError("train: %d learning rates for %d members" % (len(lrs), P))
+    if batch_shares is not None and len(batch_shares) != P:
+        raise ValueError("train: %d batch shares for %d members" % (len(batch_shares), P))
+    quantum = default_quantum(n_total, P) if quantum is None else int(quantum)
     torch.manual_seed(seed)
     dev = torch.device(device)
     gen = torch.Generator(device=dev)
     gen.manual_seed(seed + 1)
     saved = {k: getattr(GameConfig, k) for k in ("FPS", "SPEED", "DEBUG", "BOUNDS")}
     try:  # (game_configuration writes the GameConfig class, as the reference's does; the env reads it once, here)
-        env = ShipVecEnv(P * n, game_configuration(speed=30, fps=1000, debug=False), EnvConfig, device=device, n_maps=64)
+        env = ShipVecEnv(n_total, game_configuration(speed=30, fps=1000, debug=False), EnvConfig, device=device, n_maps=64)
         # the held-out run's env (train/rllib/rollout.py:8-26): evaluation resets and steps it, the training envs keep their episodes
         eval_env = ShipVecEnv(P * min(n, 256), GameConfig, EnvConfig, device=device, n_maps=64) if eval_every else None
     finally:
@@ -145,24 +207,36 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
     nets = [ActorCritic(D, A, separate_value=separate_value).to(dev) for _ in range(P)]
     scale = torch.full((D,), float(max(env.bounds)), dtype=torch.float64, device=dev)
     pop = NativePopulation.from_actor_critics(nets, scale)
+    sched = PBTScheduler(P, seed=seed, perturbation_interval=perturb_every,
+                         mutations=reference_mutations(schedule=mutate_schedule, batch=mutate_batch) if mutate_schedule or mutate_batch else None)
+    samples = horizon * n
+    member_samples = [samples] * P  # a member's own samples per update (unequal once the handle is sliced)
+    reslices = []
+    raw = None
+    if mutate_schedule:  # (drawn first: a seed's schedule does not depend on whether the batch is mutated too)
+        raw = [(sched.rng.choice(INITIAL_SCHEDULE["num_sgd_iter"]), sched.rng.choice(INITIAL_SCHEDULE["sgd_minibatch_size"])) for _ in range(P)]
+    batch_sizes = None
+    if sliced:
+        batch_sizes = initial_batch_sizes(sched, P) if mutate_batch else list(batch_shares)
+        slices = slices_for_batch_sizes(batch_sizes, n_total, quantum)
+        env.set_population_slices(slices)
+        member_samples = [horizon * s for s in slices]
+        reslices.append((0, list(slices)))
+        log("slices: train_batch_size %s -> envs %s (quantum %d)" % (batch_sizes, slices, quantum))
     ppo = PopulationPPO(pop, env, lam=INITIAL["lambda"], clip=INITIAL["clip_param"], lr=list(lrs) if lrs is not None else INITIAL["lr"],
                         vf_clip=vf_clip, max_grad_norm=max_grad_norm, kl_coef=kl_coeff, kl_target=kl_target if kl_coeff > 0 else 0.0)
-    sched = PBTScheduler(P, seed=seed, perturbation_interval=perturb_every,
-                         mutations=reference_mutations(schedule=True) if mutate_schedule else None)
     env.reset_tensor()
     window = torch.zeros((P, 3), dtype=torch.int64, device=dev)  # episodes since the last perturbation
     scores = [float("-inf")] * P
-    samples = horizon * n
     out, history, exploits, evals = None, [], [], []
     evaluator = None
     if eval_env is not None:
         from ship_sim_gym_amd.evaluate import NativeEvaluator, format_table
         evaluator = NativeEvaluator(eval_env)
     # the schedule: common ints (one launch shape for everyone, as before) or one entry per member
-    per_member = mutate_schedule or isinstance(epochs, (list, tuple)) or isinstance(minibatches, (list, tuple))
+    per_member = sliced or mutate_schedule or isinstance(epochs, (list, tuple)) or isinstance(minibatches, (list, tuple))
     if mutate_schedule:
-        draws = [clamp_schedule(sched.rng.choice(INITIAL_SCHEDULE["num_sgd_iter"]), sched.rng.choice(INITIAL_SCHEDULE["sgd_minibatch_size"]),
-                                samples, max_epochs) for _ in range(P)]
+        draws = [clamp_schedule(i, s, member_samples[m], max_epochs) for m, (i, s) in enumerate(raw)]
         iters, sizes = [d[0] for d in draws], [d[1] for d in draws]
         log("schedule: num_sgd_iter %s  sgd_minibatch_size %s" % (iters, sizes))
     elif per_member:
@@ -170,18 +244,24 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
         counts = [int(b) for b in minibatches] if isinstance(minibatches, (list, tuple)) else [int(minibatches)] * P
         if len(iters) != P or len(counts) != P:
             raise ValueError("train: %d epochs and %d minibatches for %d members" % (len(iters), len(counts), P))
-        sizes = [chunk_split(samples, c)[0] for c in counts]
+        sizes = [chunk_split(member_samples[m], c)[0] for m, c in enumerate(counts)]
     perm_epochs = max_epochs if mutate_schedule else (max(iters) if per_member else epochs)
     for u in range(1, updates + 1):
-        uniforms = torch.rand((horizon, P * n), generator=gen, device=dev)
+        uniforms = torch.rand((horizon, n_total), generator=gen, device=dev)
         batch = env.rollout_population(pop, horizon, uniforms=uniforms, out=out)
         out = {k: v for k, v in batch.items() if k not in ("adv", "ret", "logp_all")}
         window += ppo.episode_stats(batch)
         ppo.gae(batch)
-        perm = torch.rand((P, perm_epochs, samples), generator=gen, device=dev).argsort(dim=-1)
+        if sliced:  # member m's own rows: [perm_epochs, horizon * n_m], nothing padded to the widest member
+            perm = [torch.rand((perm_epochs, s), generator=gen, device=dev).argsort(dim=-1) for s in member_samples]
+        else:
+            perm = torch.rand((P, perm_epochs, samples), generator=gen, device=dev).argsort(dim=-1)
         if per_member:
-            mbs = [ppo.minibatches_for_size(s, samples) for s in sizes] if mutate_schedule else counts
-            ppo.update(batch, perm[:, :max(iters)].contiguous(), iters, mbs)
+            mbs = [ppo.minibatches_for_size(s, member_samples[m]) for m, s in enumerate(sizes)] if mutate_schedule else counts
+            if sliced:
+                ppo.update(batch, [q[:max(iters)].contiguous() for q in perm], iters, mbs)
+            else:
+                ppo.update(batch, perm[:, :max(iters)].contiguous(), iters, mbs)
         else:
             ppo.update(batch, perm, epochs, minibatches)
         w = window.cpu().tolist()
@@ -194,6 +274,10 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
             log("update %d  greedy evaluation (%d envs x %d episodes per member)\n%s" % (u, eval_env.num_envs // P, eval_episodes, format_table(r)))
         if pbt and sched.due(u):
             hp = {"lambda": ppo.lam, "clip_param": ppo.clip, "lr": ppo.lr}
+            if mutate_batch:
+                hp["train_batch_size"] = batch_sizes
+            elif sliced:  # (fixed shares are the member's configuration: they travel with an exploit, unmutated)
+                hp["batch_share"] = batch_sizes
             if mutate_schedule:
                 hp.update({"num_sgd_iter": iters, "sgd_minibatch_size": sizes})
             elif per_member:  # a swept schedule is not mutated, but it is its member's configuration: it travels with an exploit
@@ -201,12 +285,20 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
             src, new, events = sched.perturb(scores, hp)
             ppo.exploit(src)
             ppo.lam, ppo.clip, ppo.lr = new["lambda"], new["clip_param"], new["lr"]
-            if mutate_schedule:
-                used = [clamp_schedule(i, s, samples, max_epochs) for i, s in zip(new["num_sgd_iter"], new["sgd_minibatch_size"])]
+            if sliced:  # re-slice the handle from the members' current values; env state and the episode carries stay as they are
+                batch_sizes = new["train_batch_size"] if mutate_batch else new["batch_share"]
+                slices = slices_for_batch_sizes(batch_sizes, n_total, quantum)
+                env.set_population_slices(slices)
+                member_samples = [horizon * s for s in slices]
+                reslices.append((u, list(slices)))
+                log("update %d  re-slice: train_batch_size %s -> envs %s" % (u, batch_sizes, slices))
+            if mutate_schedule:  # (the minibatch-size clamp uses the member's own samples)
+                used = [clamp_schedule(i, s, member_samples[m], max_epochs)
+                        for m, (i, s) in enumerate(zip(new["num_sgd_iter"], new["sgd_minibatch_size"]))]
                 iters, sizes = [c[0] for c in used], [c[1] for c in used]
             elif per_member:
                 iters, counts = new["num_sgd_iter"], new["minibatches"]
-                sizes = [chunk_split(samples, c)[0] for c in counts]
+                sizes = [chunk_split(member_samples[m], c)[0] for m, c in enumerate(counts)]
             for ev in events:
                 log("update %d  exploit: member %d <- member %d" % (u, ev["member"], ev["source"]))
                 for key, kind, old, val in ev["mutations"]:
@@ -224,7 +316,9 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
                "hparams": {"lambda": list(ppo.lam), "clip_param": list(ppo.clip), "lr": list(ppo.lr),
                            "num_sgd_iter": list(iters) if per_member else [int(epochs)] * P,
                            "sgd_minibatch_size": list(sizes) if per_member else [chunk_split(samples, minibatches)[0]] * P},
-               "member_steps": list(ppo.member_steps), "kl_coef": ppo.kl_coef.detach().cpu().tolist(), "evaluations": evals}
+               "member_steps": list(ppo.member_steps), "kl_coef": ppo.kl_coef.detach().cpu().tolist(), "evaluations": evals,
+               "slices": list(env.population_slices) if sliced else [n] * P, "reslices": reslices,
+               "train_batch_size": list(batch_sizes) if sliced else [samples] * P}
     if eval_env is not None:
         eval_env.close()
     env.close()
@@ -236,7 +330,8 @@ def main(argv=None):
     train(members=a.members, envs_per_member=a.envs_per_member, updates=a.updates, horizon=a.horizon, perturb_every=a.perturb_every,
           seed=a.seed, epochs=a.epochs, minibatches=a.minibatches, lrs=a.lrs, pbt=a.pbt, device=a.device, kl_coeff=a.kl_coeff,
           kl_target=a.kl_target, vf_clip=a.vf_clip, max_grad_norm=a.max_grad_norm, separate_value=a.separate_value,
-          mutate_schedule=a.mutate_schedule, max_epochs=a.max_epochs, eval_every=a.eval_every, eval_episodes=a.eval_episodes)
+          mutate_schedule=a.mutate_schedule, max_epochs=a.max_epochs, eval_every=a.eval_every, eval_episodes=a.eval_episodes, envs=a.envs,
+          mutate_batch=a.mutate_batch, batch_shares=a.batch_shares, quantum=a.quantum)
 
 
 if __name__ == "__main__":
