@@ -78,6 +78,21 @@ __device__ __forceinline__ double readlane_f64(double v, int src_lane) // src_la
     return __hiloint2double(hi, lo);
 }
 
+// Moves for EXECUTION-MASKED regions.  A group of selects that share one condition (`v = cond ? a : v` for a dozen doubles, two
+// v_cndmask_b32 each, every step) is written as `if (cond) { set_*(v, a); ... }`: the values move under the execution mask —
+// one v_mov_b64 per double — and a wave none of whose lanes takes the branch (most wave-steps, when the condition is "this env
+// was reset") skips the region altogether (s_cbranch_execz).  The moves are one-instruction asm statements so that the compiler
+// does not turn the region back into selects; the mask set-up is scalar work.  A region holds moves only: no LDS access, no
+// wait, nothing another role sees.  The stored bits are those of the select.
+__device__ __forceinline__ void set_f64(double &d, double v) { asm volatile("v_mov_b64 %0, %1" : "+v"(d) : "v"(v)); }
+__device__ __forceinline__ void set_f64_uniform(double &d, double s) { asm volatile("v_mov_b64 %0, %1" : "+v"(d) : "s"(s)); } // s: wave-uniform
+__device__ __forceinline__ void set_f64_zero(double &d) { asm volatile("v_mov_b64 %0, 0" : "+v"(d)); }
+__device__ __forceinline__ void set_f64_one(double &d) { asm volatile("v_mov_b64 %0, 1.0" : "+v"(d)); }
+__device__ __forceinline__ void set_f64_minus_one(double &d) { asm volatile("v_mov_b64 %0, -1.0" : "+v"(d)); }
+template <class T> __device__ __forceinline__ void set_b32(T &d, T v) { static_assert(sizeof(T) == 4, "one register"); asm volatile("v_mov_b32 %0, %1" : "+v"(d) : "v"(v)); }
+__device__ __forceinline__ void set_b32_uniform(int &d, int s) { asm volatile("v_mov_b32 %0, %1" : "+v"(d) : "s"(s)); } // s: wave-uniform
+template <class T> __device__ __forceinline__ void set_b32_zero(T &d) { static_assert(sizeof(T) == 4, "one register"); asm volatile("v_mov_b32 %0, 0" : "+v"(d)); }
+
 // cpvforangle(a) = (cos a, sin a).  Deliberately NOT inlined: inside the fused K-step loop the compiler otherwise hoists
 // the polynomial coefficients of the inlined sincos out of the loop as live VGPR constants and, at the 128-VGPR
 // budget of a 1024-thread workgroup, spills them to scratch and reloads them on the critical path every step.
@@ -434,9 +449,13 @@ __device__ __forceinline__ void lidar_pass(const DevCfg &c, const int n_items, c
                 } else {
                     // candidate: 0 <= d/den <= 1; better: d/den >= best (cross-multiplied, dens > 0; ties -> later)
                     const bool better = front & (d <= den) & (d * bden >= bd * den);
+#ifdef SSG_NO_MASKED_BEST /* tools/build_variant.sh: the three selects, for A/B timing */
                     bd = better ? d : bd;
                     bden = better ? den : bden;
                     bj = better ? j : bj;
+#else
+                    if (better) { set_f64(bd, d); set_f64(bden, den); set_b32_uniform(bj, j); } // execution-masked (see set_f64): 3 moves for 5 selects
+#endif
                 }
             }
         }
@@ -646,6 +665,7 @@ __device__ __forceinline__ void lidar_query(const DevCfg &c, unsigned long long 
     // the same record's planes at the same LDS addresses (a broadcast) where the beam-major order put 64 different envs —
     // 64 records, several to a bank — next to each other (rocprofv3 SQ_LDS_BANK_CONFLICT: 27 % of the LDS pipe's busy cycles).
     unsigned needmask = 0u;
+    bool need[2 * NB0] = {}; // (the compares' own lane masks: what the queue stores below are predicated on)
     const double lca = c.lidar_dist * ca, lsa = c.lidar_dist * sa;
     const bool org0 = live & (cx <= ar[0]), org1 = live & (al[1] <= cx); // the origin itself is within the hull's x range
 #pragma unroll
@@ -665,8 +685,10 @@ __device__ __forceinline__ void lidar_query(const DevCfg &c, unsigned long long 
                 // on).  For banks laid out otherwise the test stays correct — it never drops a pair that could hit — and merely
                 // culls less.  Four compares, two min / max and the beam end's y per pair before; one compare now.)
                 const double ex = obs_fma(lca, beamtab[i], obs_fma(-lsa, beamtab[SSG_MAX_BEAMS + i], cx)); // cx + dist * cos(heading + phi_i)
-                needmask |= (org0 | (live & (ex <= ar[0]))) ? (1u << (2 * k + 0)) : 0u;
-                needmask |= (org1 | (live & (al[1] <= ex))) ? (1u << (2 * k + 1)) : 0u;
+                need[2 * k + 0] = org0 | (live & (ex <= ar[0]));
+                need[2 * k + 1] = org1 | (live & (al[1] <= ex));
+                needmask |= need[2 * k + 0] ? (1u << (2 * k + 0)) : 0u;
+                needmask |= need[2 * k + 1] ? (1u << (2 * k + 1)) : 0u;
             }
         }
     }
@@ -680,18 +702,24 @@ __device__ __forceinline__ void lidar_query(const DevCfg &c, unsigned long long 
         incl += __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xA, 0xF, false); // row_bcast:15 into rows 1 and 3
         incl += __builtin_amdgcn_update_dpp(0, incl, 0x143, 0xC, 0xF, false); // row_bcast:31 into rows 2 and 3
         n_items = __builtin_amdgcn_readlane(incl, 63);
-        int pos = incl - cnt;
+        // (a surviving pair is stored under the execution mask — scalar work — through a byte address that advances by two per
+        // survivor: a bit-field extract and a shift-add per pair, where a select between the slot and a trash word, its address,
+        // and the count's select and add were five instructions.  The advance is taken from a laundered copy of the mask, so
+        // that it does not become a value merged at the end of every predicated store.)
+        unsigned nm = needmask;
+        asm volatile("" : "+v"(nm));
+        char *qp = reinterpret_cast<char *>(queue) + 2 * (incl - cnt);
 #pragma unroll
         for (int k = 0; k < NB0; ++k) {
             if (k < b_count) {
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                    const bool need = (needmask >> (2 * k + s)) & 1u;
-                    queue[need ? pos : (kTrash + lane)] = (unsigned short)(lane | (k << 6) | (s << 10));
-                    pos += need ? 1 : 0;
+                    if (need[2 * k + s]) *reinterpret_cast<unsigned short *>(qp) = (unsigned short)(lane | (k << 6) | (s << 10));
+                    qp += 2u * ((nm >> (2 * k + s)) & 1u);
                 }
             }
         }
+        (void)kTrash;
     }
 #endif
     if (!SSG_ABL(3))
@@ -808,22 +836,45 @@ __device__ __forceinline__ void write_obs_pairs(double *buf /* 16-byte aligned, 
     static_assert(C_BEGIN % 2 == 0 && C_END % 2 == 0 && DH % 2 == 0 && NB >= 8, "pairs of columns; 64 x 8 doubles of buffer");
     int ln = lane;
     asm volatile("" : "+v"(ln)); // (positions derived from the lane id are not hoisted out of the step loop: registers)
-    const int wsw = (ln >> 2) & 3;
+    // Positions are BYTE offsets in 32 bits, computed once per call: the chunk's and the piece's displacements are compile-time
+    // constants that go into the instructions' immediate fields (LDS) or the wave-uniform base (HBM: scalar base + 32-bit lane
+    // offset), where a 64-bit address per store — row, pair and swizzle recomputed from the lane id each time — cost a dozen
+    // VALU instructions per 16-byte store.  A lane's piece jj of a chunk of np pairs per row is pair q = pidx % np of row
+    // r = pidx / np, pidx = lane + 64 jj.  For np = 4 and 2 that is row r0 + (64 / np) jj and the SAME pair and the same swizzle
+    // ((r >> 2) & 3 does not change when r grows by 16 or 32) for every jj; np = 1 has one piece; np = 3 is computed on the spot.
+    char *const bufc = reinterpret_cast<char *>(buf);
+    char *const outc = reinterpret_cast<char *>(obase);
+    const unsigned uln = (unsigned)ln;
+    const unsigned wrow = uln << 6, wsw16 = (uln << 2) & 48u;          // this lane's row in the buffer; 16 * its swizzle
+    const unsigned r4 = uln >> 2, q4 = uln & 3u;                        // np = 4: row and pair of piece 0
+    const unsigned l4 = (r4 << 6) + (((q4 ^ (uln >> 4)) & 3u) << 4), g4 = (r4 * DH + 2u * q4) * 8u;
+    const unsigned r2 = uln >> 1, q2 = uln & 1u;                        // np = 2
+    const unsigned l2 = (r2 << 6) + ((q2 ^ ((uln >> 3) & 3u)) << 4), g2 = (r2 * DH + 2u * q2) * 8u;
 #pragma unroll
     for (int c0 = C_BEGIN; c0 < C_END; c0 += 8) {
         constexpr int kMax = 4;
         const int np = ((C_END - c0) / 2 < kMax) ? (C_END - c0) / 2 : kMax; // pairs per row in this chunk (a constant once unrolled)
 #pragma unroll
         for (int q = 0; q < kMax; ++q)
-            if (q < np) *reinterpret_cast<double2 *>(buf + ln * 8 + 2 * (q ^ wsw)) = make_double2(val(c0 + 2 * q), val(c0 + 2 * q + 1));
+            if (q < np) *reinterpret_cast<double2 *>(bufc + (wrow + (wsw16 ^ (16u * q)))) = make_double2(val(c0 + 2 * q), val(c0 + 2 * q + 1));
 #pragma unroll
         for (int jj = 0; jj < kMax; ++jj) {
             if (jj < np) {
-                const int pidx = ln + 64 * jj;
-                const int r = (np == 4) ? (pidx >> 2) : (np == 2) ? (pidx >> 1) : (np == 1) ? pidx : pidx / 3;
-                const int q = pidx - r * np;
-                const double2 v = *reinterpret_cast<const double2 *>(buf + r * 8 + 2 * (q ^ ((r >> 2) & 3)));
-                if (r < rows_live) *reinterpret_cast<double2 *>(&obase[(unsigned)(r * DH + c0 + 2 * q)]) = v;
+                if (np == 4 || np == 2 || np == 1) {
+                    const int rstep = 64 / np;                                       // rows per piece
+                    const unsigned r0 = (np == 4) ? r4 : (np == 2) ? r2 : uln;
+                    const unsigned lat = (np == 4) ? l4 : (np == 2) ? l2 : wrow + wsw16;
+                    const unsigned gat = (np == 4) ? g4 : (np == 2) ? g2 : uln * (DH * 8u);
+                    const double2 v = *reinterpret_cast<const double2 *>(bufc + jj * rstep * 64 + lat);
+                    if ((int)r0 < rows_live - jj * rstep)
+                        *reinterpret_cast<double2 *>(outc + (size_t)((jj * rstep * DH + c0) * 8) + gat) = v;
+                } else {
+                    const int pidx = ln + 64 * jj;
+                    const int r = pidx / 3;
+                    const int q = pidx - r * np;
+                    const double2 v = *reinterpret_cast<const double2 *>(buf + r * 8 + 2 * (q ^ ((r >> 2) & 3)));
+                    if (r < rows_live) *reinterpret_cast<double2 *>(&obase[(unsigned)(r * DH + c0 + 2 * q)]) = v;
+                }
             }
         }
         __builtin_amdgcn_sched_barrier(0); // keep the chunks apart: the next chunk's values are not computed (and held) early
@@ -1345,9 +1396,13 @@ __global__ __launch_bounds__(tile_roles(EPW, DYN) * EPW) void step_kernel(const 
             if (k + 1 < K) {
                 // step k+1's pre-step pose: this step's post-step pose, or ShipGame.reset's spawn pose on the next map
                 const bool rs = auto_reset & ((gres[(k & 1) * EPW + tl] | (gdone[(k & 1) * EPW + tl] & 1u) | (DYN ? traffic_hit(k) : 0u)) != 0u);
-                ca = rs ? 1.0 : nca; sa = rs ? 0.0 : nsa;
-                cx = rs ? shiptab[0 * 8 + 6] : ncx; cy = rs ? shiptab[1 * 8 + 6] : ncy;
-                map_id = rs ? next_map(c, nmap, el_) : nmap;
+                const double spx = shiptab[0 * 8 + 6], spy = shiptab[1 * 8 + 6]; // (wave-uniform LDS reads, outside the masked region)
+                ca = nca; sa = nsa; cx = ncx; cy = ncy; map_id = nmap;
+                if (rs) { // execution-masked region (see set_f64): the spawn pose on the next record for the done lanes
+                    set_f64_one(ca); set_f64_zero(sa);
+                    set_f64(cx, spx); set_f64(cy, spy);
+                    set_b32(map_id, next_map(c, nmap, el_));
+                }
                 if constexpr (!LDS_BANK) {
                     if (rs) load_hdr_lidar(map_id * SSG_MAP_STRIDE); // only the lanes whose env moved to its next record gather
                 }
@@ -1602,12 +1657,7 @@ __global__ __launch_bounds__(tile_roles(EPW, DYN) * EPW) void step_kernel(const 
                 rs_gx = sg.x; rs_gy = sg.y;
             }
             double nv[F];
-            nv[0] = do_reset ? c.spawn_x : x;
-            nv[1] = do_reset ? c.spawn_y : y;
-            nv[2] = do_reset ? 0.0 : (double)rudder;
-            nv[3] = do_reset ? 0.0 : ang;
-            nv[4] = do_reset ? rs_gx : nf_gx;
-            nv[5] = do_reset ? rs_gy : nf_gy;
+            nv[0] = x; nv[1] = y; nv[2] = (double)rudder; nv[3] = ang; nv[4] = nf_gx; nv[5] = nf_gy; // (a reset env: overridden below)
             {
                 const unsigned long long *rk = reinterpret_cast<const unsigned long long *>(res_k);
 #pragma unroll
@@ -1633,8 +1683,19 @@ __global__ __launch_bounds__(tile_roles(EPW, DYN) * EPW) void step_kernel(const 
 #pragma unroll
                 for (int i = 0; i < NB; ++i) st_out(&trow[6 + i], nv[6 + i]);
             }
+            // Rows written whole below (no early / speculative half went out): a reset env's history half is -1 too.
+            const bool hist_whole = hist2 && !(kSplitOk && (spec || early));
+            if (do_reset) { // execution-masked region (see set_f64): ShipGame.reset's frame and -1 readings for the reset lanes
+                set_f64_uniform(nv[0], c.spawn_x); set_f64_uniform(nv[1], c.spawn_y);
+                set_f64_zero(nv[2]); set_f64_zero(nv[3]);
+                set_f64(nv[4], rs_gx); set_f64(nv[5], rs_gy);
 #pragma unroll
-            for (int i = 0; i < NB; ++i) nv[6 + i] = do_reset ? -1.0 : nv[6 + i]; // a fresh episode starts from -1 (models.py:36)
+                for (int i = 0; i < NB; ++i) set_f64_minus_one(nv[6 + i]); // a fresh episode starts from -1 (models.py:36)
+                if (hist_whole) { // (wave-uniform; the previous frame is dead after this step's row)
+#pragma unroll
+                    for (int j = 0; j < F; ++j) set_f64_minus_one(pv[j]);
+                }
+            }
             SSG_STAMP_K(6);
             {
                 double *__restrict__ obase = obs + ((size_t)tile_e0 + (size_t)k * (size_t)traj) * (size_t)(F * c.history); // tile start in HBM, this step's slot
@@ -1681,10 +1742,10 @@ __global__ __launch_bounds__(tile_roles(EPW, DYN) * EPW) void step_kernel(const 
                     } else if (hist2) {
                         if constexpr (kPairs)
                             write_obs_pairs<NB, true, 0, 2 * F>(colbuf, [&](int j) -> double {
-                                return (j < F) ? (do_reset ? -1.0 : pv[(j < F) ? j : 0]) : nv[(j < F) ? 0 : j - F]; }, obase, rows_live, lane);
+                                return (j < F) ? pv[(j < F) ? j : 0] : nv[(j < F) ? 0 : j - F]; }, obase, rows_live, lane);
                         else
                             write_obs_tile<NB, true, 0, kObsPasses>(ot, colbuf, [&](int j) -> double {
-                                return (j < F) ? (do_reset ? -1.0 : pv[(j < F) ? j : 0]) : nv[(j < F) ? 0 : j - F]; },
+                                return (j < F) ? pv[(j < F) ? j : 0] : nv[(j < F) ? 0 : j - F]; },
                                 obase, rows_live, lane);
                     } else {
                         if constexpr (kPairs)
@@ -2030,9 +2091,13 @@ __global__ __launch_bounds__(tile_roles(EPW, DYN) * EPW) void step_kernel(const 
     }
     SSG_STAMP_K(7);
     if (do_reset) {
-        x = c.spawn_x; y = c.spawn_y; vx = 0.0; vy = 0.0; ang = 0.0; w = 0.0; cum = 0.0;
-        rudder = 0; steps = 0;
-        gm = (1u << c.n_goals) - 1u;
+        // (the registers move under the execution mask, see set_f64: a wave without a done env skips them)
+        set_f64_uniform(x, c.spawn_x); set_f64_uniform(y, c.spawn_y);
+        set_f64_zero(vx); set_f64_zero(vy); set_f64_zero(ang); set_f64_zero(w); set_f64_zero(cum);
+        set_b32_zero(rudder); set_b32_zero(steps);
+        set_b32(gm, (1u << c.n_goals) - 1u);
+    }
+    if (do_reset) {
         // the pre-step rotation the next step's thrust will read: cpvforangle(0)
         pose[2 * EPW + tl] = 1.0; pose[3 * EPW + tl] = 0.0;
     }
