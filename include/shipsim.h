@@ -949,6 +949,83 @@ int ssg_pop_evaluate(ssg_handle *h, const ssg_population *pop, const ssg_eval *e
 int ssg_eval_reduce(ssg_handle *h, int n_members, const int64_t *dev_env_stats, int64_t *dev_member_stats, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Observation filter (ABI 9 addition): a running mean / std per observation column, kept and applied on the device
+ * The reference's RLlib trainers run "PPO" with its defaults (train/rllib/pbt.py:50, train/rllib/ppo.py:28), which in the RLlib
+ * generation those scripts are written for include observation_filter = "MeanStdFilter"; Stable-Baselines users wrap the SubprocVecEnv
+ * of train/stable_baselines/ppo.py:123 in VecNormalize for the same purpose.  This is that filter's arithmetic, defined below on its
+ * own terms: no bit parity with either library is claimed.  With nothing bound, nothing changes: x = (float)(obs / obs_scale).
+ *
+ * State, per member (one for a single policy) and observation column d, all f64: count, mean[d], M2[d] (the sum of squared
+ * deviations from the mean) and denom[d].  dev_state is f64 [n_members][SSG_FILTER_ROWS][obs_dim], row 0 = mean, row 1 = M2,
+ * row 2 = denom, row 3 = {count, 0, ...}; all zeros is the empty state.
+ *
+ * Merging a batch of n_b rows with batch mean mu_b and batch M2_b (Chan et al.), in exactly this association, every product and sum
+ * separately rounded (no fused multiply-add):
+ *     n'     = n + n_b
+ *     delta  = mu_b - mean
+ *     mean'  = mean + delta * (n_b / n')
+ *     M2'    = (M2 + M2_b) + (delta * delta) * (n * (n_b / n'))
+ *     denom' = sqrt(M2' / (n' - 1)) + eps     if n' >= 2, else 1.0
+ * Merging into an empty side (n == 0) takes the other side's values as they are.  A constant column c therefore keeps mean == c bit
+ * for bit and M2 == 0.0 through every merge, provided the batch's own mean is exact (below: whenever 256 * c is exact in f64).
+ *
+ * The reduction order of ssg_obs_filter_update over a member's n rows (row r = the r-th row of the member's slice).  It depends on r and
+ * n only — not on the launch geometry, on the other members, or on which compute unit ran what — so the result is bitwise reproducible:
+ *   1. Tiles.  Rows [256 t, min(256 t + 256, n)) form tile t, n_t rows.  Per column, with x[i] = the tile's i-th row for i < n_t and
+ *      0.0 for n_t <= i < 256: S = the halving tree over x (for h = 128, 64, ..., 1: x[i] = x[i] + x[i + h] for i < h; S = x[0]);
+ *      mu_t = S / n_t; then q[i] = (x[i] - mu_t) * (x[i] - mu_t) for i < n_t and 0.0 above, and M2_t = the same halving tree over q.
+ *   2. Runs.  With T = ceil(n / 256) tiles and L = ceil(T / 8), run g (0..7) holds tiles [g L, min(g L + L, T)) and is formed by
+ *      merging them, with the formula above, in increasing t into an empty state (a run may be empty).
+ *   3. The eight runs meet in a halving tree (for h = 4, 2, 1: run g = merge(run g, run g + h) for g < h), and run 0 is merged into the
+ *      running state as the batch.
+ *
+ * Normalising: x[d] = (float) clamp((obs[d] - mean[d]) / denom[d], -clip, +clip) — subtraction, division and clamp in f64, then one
+ * rounding to f32; clip == 0: no clamp.  A denom entry of 0.0 (the empty state; eps == 0 on a constant column) divides by 1, so the
+ * empty state behaves as mean = 0, denom = 1.  ssg_policy.dev_obs_scale is not read while a filter is bound.
+ *
+ * While a filter is bound to a handle (ssg_set_obs_filter), every policy launch on it forms x this way: ssg_policy_act,
+ * ssg_policy_act_greedy, ssg_rollout_policy and ssg_evaluate need n_members == 1, the ssg_pop_* counterparts n_members == P (member m
+ * uses its own state rows); anything else is SSG_ERR_BAD_ARG with nothing launched.  ssg_rollout_policy and ssg_pop_rollout enqueue
+ * ssg_obs_filter_update ahead of each step's policy launch when SSG_FILTER_UPDATE is set — first merge the N current rows, then
+ * normalise those same rows with the merged state, as both libraries do — and never for the value-only forward after the last step:
+ * those rows are step 0 of the next rollout.  ssg_policy_act*, ssg_pop_act*, ssg_evaluate and ssg_pop_evaluate never update
+ * (evaluation is frozen, like VecNormalize.training = False).  The PPO update reads the stored x rows and does not change.
+ * ------------------------------------------------------------------------------------------------- */
+#define SSG_FILTER_ROWS 4          /* state rows per member: mean, M2, denom, {count, 0, ...} */
+#define SSG_FILTER_UPDATE 0x1u     /* rollout loops merge each step's observations ahead of its policy launch */
+typedef struct ssg_obs_filter {
+    uint32_t struct_size, flags;   /* sizeof(ssg_obs_filter); SSG_FILTER_UPDATE or 0 (frozen); any other bit refused */
+    int32_t n_members, obs_dim;    /* 1 for a single policy, P for a population; history * (6 + n_beams) */
+    double clip, eps;              /* clip >= 0 (0: none), eps >= 0; NaN refused */
+    double *dev_state;             /* f64 [n_members][SSG_FILTER_ROWS][obs_dim], caller-owned; zero = empty */
+    void *dev_workspace;           /* caller-owned, >= ssg_obs_filter_workspace_nbytes(n_envs, obs_dim, n_members) bytes */
+    size_t workspace_nbytes;
+} ssg_obs_filter;
+
+/* Replaces nothing (host only; the libraries' filters allocate on the host as they go).  The workspace of ssg_obs_filter_update for a
+ * handle of n_envs envs: the tile partials, f64 [n_members][ceil(n_envs / 256)][2][obs_dim].  SSG_ERR_BAD_ARG for an argument < 1, NULL
+ * nbytes, obs_dim beyond SSG_MAX_HISTORY * (6 + SSG_MAX_BEAMS) or n_members beyond SSG_POP_MAX_MEMBERS. */
+int ssg_obs_filter_workspace_nbytes(int n_envs, int obs_dim, int n_members, size_t *nbytes);
+
+/* Replaces: the filter's update on a batch of observations — MeanStdFilter.__call__(x, update=True) behind the "PPO" default of
+ * train/rllib/pbt.py:50, VecNormalize's obs_rms.update around the env of train/stable_baselines/ppo.py:123 — as two launches on `stream`
+ * (tile partials, then one workgroup per member), whatever f->flags says.  dev_obs: f64 [n_envs][obs_dim] in the handle's row layout;
+ * member m's rows are [m n, (m + 1) n), n = n_envs / n_members, or its slice of ssg_pop_set_slices.  f need not be the bound record.
+ * Refuses (SSG_ERR_BAD_ARG, nothing launched) what ssg_set_obs_filter refuses, a NULL dev_obs, and an n_members the handle's envs do
+ * not split into. */
+int ssg_obs_filter_update(ssg_handle *h, const ssg_obs_filter *f, const double *dev_obs, void *stream);
+
+/* Replaces nothing (memory binding; the reference's counterpart is the "observation_filter" entry of the trainer config behind
+ * train/rllib/pbt.py:50).  Binds a copy of the record to the handle; the caller owns dev_state and dev_workspace and keeps them alive
+ * while it is bound.  NULL unbinds.  SSG_ERR_BAD_ARG, the binding left as it was: struct_size mismatch; obs_dim different from the
+ * handle's history * (6 + n_beams); n_members outside 1..SSG_POP_MAX_MEMBERS, or different from a bound slices layout; NULL dev_state
+ * or dev_workspace; workspace_nbytes below ssg_obs_filter_workspace_nbytes; an unknown flag; a negative or NaN clip or eps. */
+int ssg_set_obs_filter(ssg_handle *h, const ssg_obs_filter *f /* NULL unbinds */);
+
+/* Replaces nothing (introspection).  *out = the bound record; out->struct_size == 0 (all of *out zero): nothing bound. */
+int ssg_get_obs_filter(const ssg_handle *h, ssg_obs_filter *out /* struct_size 0: nothing bound */);
+
+/* ---------------------------------------------------------------------------------------------------
  * Host-side geometry (what pymunk's cffi exposed at reset time); no GPU needed.
  * ------------------------------------------------------------------------------------------------- */
 /* Replaces cpConvexHull as reached by pm.Poly(...) (models.py:96,180).  out_xy holds >= count pairs. */

@@ -25,6 +25,8 @@ EVAL_STATS, EVAL_GREEDY = 8, 0x1  # columns of an evaluation's stats rows; ssg_e
 # the columns (include/shipsim.h): episodes, llrint(100 * return), length, the four endings (not exclusive), goal events
 (EVAL_EPISODES, EVAL_RETURN100, EVAL_LENGTH, EVAL_COLLIDED, EVAL_OUT_OF_BOUNDS, EVAL_MAX_STEPS, EVAL_NO_GOALS_LEFT,
  EVAL_GOALS) = range(8)
+FILTER_ROWS, FILTER_UPDATE = 4, 0x1  # state rows per member of an observation filter (mean, M2, denom, count); ssg_obs_filter.flags
+FILTER_TILE, FILTER_RUNS = 256, 8  # ssg_obs_filter_update's reduction order: rows per tile, runs of tiles (include/shipsim.h)
 
 
 def pop_table_floats(n_members, n_steps):
@@ -65,6 +67,7 @@ EXPORTS = (
     "ssg_pop_pack_schedule", "ssg_pop_pack_hparams_steps", "ssg_pop_update_sched",
     "ssg_policy_act_greedy", "ssg_pop_act_greedy", "ssg_evaluate", "ssg_pop_evaluate", "ssg_eval_reduce", "ssg_eval_account",
     "ssg_pop_pack_slices", "ssg_pop_set_slices", "ssg_pop_get_slices", "ssg_pop_pack_schedule_samples",
+    "ssg_obs_filter_workspace_nbytes", "ssg_obs_filter_update", "ssg_set_obs_filter", "ssg_get_obs_filter",
 )
 
 
@@ -138,6 +141,15 @@ class Eval(C.Structure):
         ("dev_act", C.c_void_p), ("dev_logp", C.c_void_p), ("dev_value", C.c_void_p), ("dev_reward", C.c_void_p),
         ("dev_done", C.c_void_p), ("dev_flags", C.c_void_p), ("dev_carry_return", C.c_void_p), ("dev_carry", C.c_void_p),
         ("dev_env_stats", C.c_void_p),
+    ]
+
+
+class ObsFilterRecord(C.Structure):
+    """ssg_obs_filter (ABI 9 addition): a running mean / std observation filter — mode, shape, clip / eps, the state rows, the workspace."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_members", C.c_int32), ("obs_dim", C.c_int32),
+        ("clip", C.c_double), ("eps", C.c_double), ("dev_state", C.c_void_p), ("dev_workspace", C.c_void_p),
+        ("workspace_nbytes", C.c_size_t),
     ]
 
 
@@ -231,6 +243,10 @@ def lib():
     L.ssg_pop_evaluate.argtypes = [vp, pp, C.POINTER(Eval), vp]
     L.ssg_eval_reduce.argtypes = [vp, C.c_int, vp, vp, vp]
     L.ssg_eval_account.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.ssg_obs_filter_workspace_nbytes.argtypes = [C.c_int, C.c_int, C.c_int, szp]
+    L.ssg_obs_filter_update.argtypes = [vp, C.POINTER(ObsFilterRecord), vp, vp]
+    L.ssg_set_obs_filter.argtypes = [vp, C.POINTER(ObsFilterRecord)]
+    L.ssg_get_obs_filter.argtypes = [vp, C.POINTER(ObsFilterRecord)]
     L.ssg_render.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, vp]
     L.ssg_dyn_invalidate.argtypes = [vp, vp, vp]
     L.ssg_host_convex_hull.argtypes = [C.c_int, dp, dp, ip]

@@ -58,6 +58,9 @@ struct ssg_handle {
     std::vector<int32_t> pop_sizes;
     const int32_t *dev_slices = nullptr;
     int slice_max = 0, slice_min = 0;
+    // ssg_set_obs_filter: the bound record (a copy; struct_size 0: nothing bound) and whether the FILTER kernels' LDS limit is set
+    ssg_obs_filter flt{};
+    bool policy_filter_prepared = false;
     std::string err;
 };
 
@@ -1012,6 +1015,77 @@ static int prepare_policy(ssg_handle *h)
     return SSG_OK;
 }
 
+// ABI 9 addition: the observation filter.  The record against the handle: everything ssg_set_obs_filter refuses.
+static int check_filter(ssg_handle *h, const ssg_obs_filter *f, const char *what)
+{
+    const std::string w(what);
+    char buf[200];
+    if (f->struct_size != sizeof(ssg_obs_filter)) return fail(h, SSG_ERR_BAD_ARG, w + ": ssg_obs_filter.struct_size != sizeof(ssg_obs_filter)");
+    if (f->flags & ~SSG_FILTER_UPDATE) return fail(h, SSG_ERR_BAD_ARG, w + ": unknown bit in ssg_obs_filter.flags");
+    const int D = h->cfg.history * (6 + h->cfg.n_beams);
+    if (f->obs_dim != D) {
+        std::snprintf(buf, sizeof buf, ": obs_dim %d differs from the handle's history*(6+n_beams) = %d", f->obs_dim, D);
+        return fail(h, SSG_ERR_BAD_ARG, w + buf);
+    }
+    if (f->n_members < 1 || f->n_members > SSG_POP_MAX_MEMBERS) return fail(h, SSG_ERR_BAD_ARG, w + ": n_members must be in 1..SSG_POP_MAX_MEMBERS");
+    if (!h->pop_sizes.empty() && (int)h->pop_sizes.size() != f->n_members) {
+        std::snprintf(buf, sizeof buf, ": %d members, but slices for %d members are bound to the handle (ssg_pop_set_slices)", f->n_members,
+                      (int)h->pop_sizes.size());
+        return fail(h, SSG_ERR_BAD_ARG, w + buf);
+    }
+    if (!(f->clip >= 0.0) || !(f->eps >= 0.0)) return fail(h, SSG_ERR_BAD_ARG, w + ": clip and eps must be >= 0 (and not NaN)");
+    if (!f->dev_state || !f->dev_workspace) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_state or dev_workspace");
+    const size_t need = ssg::filter_workspace_bytes(h->cfg.n_envs, D, f->n_members);
+    if (f->workspace_nbytes < need) {
+        std::snprintf(buf, sizeof buf, ": workspace_nbytes %zu < %zu (ssg_obs_filter_workspace_nbytes)", f->workspace_nbytes, need);
+        return fail(h, SSG_ERR_BAD_ARG, w + buf);
+    }
+    return SSG_OK;
+}
+
+// a policy call of `members` members (1: a single policy) against the bound filter, if any: its member count must be the call's
+static int check_filter_members(ssg_handle *h, int members, const char *what)
+{
+    if (!h->flt.struct_size || h->flt.n_members == members) return SSG_OK;
+    char buf[200];
+    std::snprintf(buf, sizeof buf, ": the bound observation filter has %d members, this call %d (ssg_set_obs_filter)", h->flt.n_members, members);
+    return fail(h, SSG_ERR_BAD_ARG, std::string(what) + buf);
+}
+
+static int prepare_policy_filter(ssg_handle *h)
+{
+    if (!h->flt.struct_size || h->policy_filter_prepared) return SSG_OK;
+    hipError_t e = ssg::prepare_policy_filter();
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("prepare_policy_filter: ") + hipGetErrorString(e));
+    h->policy_filter_prepared = true;
+    return SSG_OK;
+}
+
+// One policy launch on the handle (pop_members 0: a single policy over n envs; else a population, n = the widest slice): the FILTER
+// kernels while a filter is bound, the launchers as they were otherwise.
+static hipError_t policy_launch(ssg_handle *h, const ssg_policy &p, bool greedy, int pop_members, int n, const double *obs, const float *uniform,
+                                uint64_t seed, int64_t step, int32_t *act, float *logp, float *value, float *x, hipStream_t st,
+                                const int32_t *slices)
+{
+    if (h->flt.struct_size) {
+        const ssg::ObsFilterArgs f = {h->flt.dev_state, h->flt.clip};
+        return ssg::launch_policy_filter(p, f, greedy, pop_members, n, h->cfg.env_id_base, obs, uniform, seed, step, act, logp, value, x, st, slices);
+    }
+    if (pop_members == 0)
+        return greedy ? ssg::launch_policy_act_greedy(p, n, obs, act, logp, value, x, st)
+                      : ssg::launch_policy_act(p, n, h->cfg.env_id_base, obs, uniform, seed, step, act, logp, value, x, st);
+    return greedy ? ssg::launch_policy_pop_greedy(p, pop_members, n, obs, act, logp, value, x, st, slices)
+                  : ssg::launch_policy_pop(p, pop_members, n, h->cfg.env_id_base, obs, uniform, seed, step, act, logp, value, x, st, slices);
+}
+
+// the rollout loops' merge of the current observation rows ahead of a step's policy launch: only with SSG_FILTER_UPDATE bound
+static hipError_t filter_step_update(ssg_handle *h, int n, const int32_t *slices, const double *obs, hipStream_t st)
+{
+    const ssg_obs_filter &f = h->flt;
+    if (!f.struct_size || !(f.flags & SSG_FILTER_UPDATE)) return hipSuccess;
+    return ssg::launch_filter_update(obs, f.obs_dim, f.n_members, n, slices, f.eps, f.dev_state, f.dev_workspace, st);
+}
+
 int ssg_policy_act(ssg_handle *h, const ssg_policy *pol, const double *dev_obs, const float *dev_uniform, uint64_t seed, int64_t step,
                    int32_t *dev_actions, float *dev_logp, float *dev_value, float *dev_x, void *stream)
 {
@@ -1021,10 +1095,12 @@ int ssg_policy_act(ssg_handle *h, const ssg_policy *pol, const double *dev_obs, 
     if (rc != SSG_OK) return rc;
     if (!dev_obs || !dev_actions || !dev_logp || !dev_value)
         return fail(h, SSG_ERR_BAD_ARG, "ssg_policy_act: NULL dev_obs, dev_actions, dev_logp or dev_value");
-    rc = prepare_policy(h);
+    rc = check_filter_members(h, 1, "ssg_policy_act");
+    if (rc == SSG_OK) rc = prepare_policy(h);
+    if (rc == SSG_OK) rc = prepare_policy_filter(h);
     if (rc != SSG_OK) return rc;
-    hipError_t e = ssg::launch_policy_act(*pol, h->cfg.n_envs, h->cfg.env_id_base, dev_obs, dev_uniform, seed, step, dev_actions, dev_logp,
-                                          dev_value, dev_x, static_cast<hipStream_t>(stream));
+    hipError_t e = policy_launch(h, *pol, false, 0, h->cfg.n_envs, dev_obs, dev_uniform, seed, step, dev_actions, dev_logp, dev_value, dev_x,
+                                 static_cast<hipStream_t>(stream), nullptr);
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("policy launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
@@ -1038,10 +1114,12 @@ int ssg_policy_act_greedy(ssg_handle *h, const ssg_policy *pol, const double *de
     if (rc != SSG_OK) return rc;
     if (!dev_obs || !dev_actions || !dev_logp || !dev_value)
         return fail(h, SSG_ERR_BAD_ARG, "ssg_policy_act_greedy: NULL dev_obs, dev_actions, dev_logp or dev_value");
-    rc = prepare_policy(h);
+    rc = check_filter_members(h, 1, "ssg_policy_act_greedy");
+    if (rc == SSG_OK) rc = prepare_policy(h);
+    if (rc == SSG_OK) rc = prepare_policy_filter(h);
     if (rc != SSG_OK) return rc;
-    hipError_t e = ssg::launch_policy_act_greedy(*pol, h->cfg.n_envs, dev_obs, dev_actions, dev_logp, dev_value, dev_x,
-                                                 static_cast<hipStream_t>(stream));
+    hipError_t e = policy_launch(h, *pol, true, 0, h->cfg.n_envs, dev_obs, nullptr, 0, 0, dev_actions, dev_logp, dev_value, dev_x,
+                                 static_cast<hipStream_t>(stream), nullptr);
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("policy launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
@@ -1059,29 +1137,33 @@ int ssg_rollout_policy(ssg_handle *h, const ssg_policy *pol, int K, const float 
         return fail(h, SSG_ERR_BAD_ARG, "ssg_rollout_policy: NULL dev_obs, act, logp, value, reward or done buffer");
     if (K < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_rollout_policy: K < 1");
     if (step_stride_envs < (int64_t)h->cfg.n_envs) return fail(h, SSG_ERR_BAD_ARG, "ssg_rollout_policy: step_stride_envs < n_envs (steps would overlap)");
+    rc = check_filter_members(h, 1, "ssg_rollout_policy");
+    if (rc != SSG_OK) return rc;
     // what the per-step ssg_step would refuse, refused before the first policy launch
     if (h->cfg.map_ring > 0 && !h->ring_ready) return fail(h, SSG_ERR_NOT_BOUND, "map_ring mode: call ssg_refill_worlds first");
     rc = refuse_capture(h, stream, "ssg_rollout_policy");
     if (rc != SSG_OK) return rc;
     rc = prepare(h);
     if (rc == SSG_OK) rc = prepare_policy(h);
+    if (rc == SSG_OK) rc = prepare_policy_filter(h);
     if (rc != SSG_OK) return rc;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t S = (size_t)step_stride_envs, D = (size_t)pol->obs_dim;
     for (int k = 0; k < K; ++k) {
         const size_t r = (size_t)k * S;
-        hipError_t e = ssg::launch_policy_act(*pol, h->cfg.n_envs, h->cfg.env_id_base, dev_obs, dev_uniform_KN ? dev_uniform_KN + r : nullptr,
-                                              seed, step0 + k, dev_act_KN + r, dev_logp_KN + r, dev_value_KN + r,
-                                              dev_x_KND ? dev_x_KND + r * D : nullptr, st);
+        hipError_t e = filter_step_update(h, h->cfg.n_envs, nullptr, dev_obs, st); // (first merge the step's rows, then normalise them)
+        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("observation filter launch: ") + hipGetErrorString(e));
+        e = policy_launch(h, *pol, false, 0, h->cfg.n_envs, dev_obs, dev_uniform_KN ? dev_uniform_KN + r : nullptr, seed, step0 + k,
+                          dev_act_KN + r, dev_logp_KN + r, dev_value_KN + r, dev_x_KND ? dev_x_KND + r * D : nullptr, st, nullptr);
         if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("policy launch: ") + hipGetErrorString(e));
         // (ssg_step as it stands: the same launches, frame shifts, dyn kernels and ring refills as a caller's own step)
         rc = ssg_rollout_traj(h, dev_act_KN + r, 1, dev_obs, dev_reward_KN + r, dev_done_KN + r, dev_flags_KN ? dev_flags_KN + r : nullptr, 0,
                               stream);
         if (rc != SSG_OK) return rc;
     }
-    if (dev_last_value) { // the value of the observation after the last step (PPO's bootstrap): a value-only forward
-        hipError_t e = ssg::launch_policy_act(*pol, h->cfg.n_envs, h->cfg.env_id_base, dev_obs, nullptr, seed, step0 + K, nullptr, nullptr,
-                                              dev_last_value, nullptr, st);
+    if (dev_last_value) { // the value of the observation after the last step (PPO's bootstrap): a value-only forward (no filter merge)
+        hipError_t e = policy_launch(h, *pol, false, 0, h->cfg.n_envs, dev_obs, nullptr, seed, step0 + K, nullptr, nullptr, dev_last_value, nullptr,
+                                     st, nullptr);
         if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("policy launch: ") + hipGetErrorString(e));
     }
     return SSG_OK;
@@ -1510,12 +1592,14 @@ int ssg_pop_act(ssg_handle *h, const ssg_population *pop, const double *dev_obs,
     if (rc != SSG_OK) return rc;
     if (!dev_obs || !dev_actions || !dev_logp || !dev_value)
         return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_act: NULL dev_obs, dev_actions, dev_logp or dev_value");
-    rc = check_ready(h, false);
+    rc = check_filter_members(h, pop->n_members, "ssg_pop_act");
+    if (rc == SSG_OK) rc = check_ready(h, false);
     if (rc == SSG_OK) rc = prepare_policy(h);
+    if (rc == SSG_OK) rc = prepare_policy_filter(h);
     if (rc != SSG_OK) return rc;
     const int P = pop->n_members;
-    hipError_t e = ssg::launch_policy_pop(pop_policy(*pop), P, pop_width(h, P), h->cfg.env_id_base, dev_obs, dev_uniform, seed, step,
-                                          dev_actions, dev_logp, dev_value, dev_x, static_cast<hipStream_t>(stream), pop_slices(h));
+    hipError_t e = policy_launch(h, pop_policy(*pop), false, P, pop_width(h, P), dev_obs, dev_uniform, seed, step, dev_actions, dev_logp,
+                                 dev_value, dev_x, static_cast<hipStream_t>(stream), pop_slices(h));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population policy launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
@@ -1528,12 +1612,14 @@ int ssg_pop_act_greedy(ssg_handle *h, const ssg_population *pop, const double *d
     if (rc != SSG_OK) return rc;
     if (!dev_obs || !dev_actions || !dev_logp || !dev_value)
         return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_act_greedy: NULL dev_obs, dev_actions, dev_logp or dev_value");
-    rc = check_ready(h, false);
+    rc = check_filter_members(h, pop->n_members, "ssg_pop_act_greedy");
+    if (rc == SSG_OK) rc = check_ready(h, false);
     if (rc == SSG_OK) rc = prepare_policy(h);
+    if (rc == SSG_OK) rc = prepare_policy_filter(h);
     if (rc != SSG_OK) return rc;
     const int P = pop->n_members;
-    hipError_t e = ssg::launch_policy_pop_greedy(pop_policy(*pop), P, pop_width(h, P), dev_obs, dev_actions, dev_logp, dev_value, dev_x,
-                                                 static_cast<hipStream_t>(stream), pop_slices(h));
+    hipError_t e = policy_launch(h, pop_policy(*pop), true, P, pop_width(h, P), dev_obs, nullptr, 0, 0, dev_actions, dev_logp, dev_value, dev_x,
+                                 static_cast<hipStream_t>(stream), pop_slices(h));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population policy launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
@@ -1550,6 +1636,8 @@ int ssg_pop_rollout(ssg_handle *h, const ssg_population *pop, int K, const float
         return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_rollout: NULL dev_obs, act, logp, value, reward or done buffer");
     if (K < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_rollout: K < 1");
     if (step_stride_envs < (int64_t)h->cfg.n_envs) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_rollout: step_stride_envs < n_envs (steps would overlap)");
+    rc = check_filter_members(h, pop->n_members, "ssg_pop_rollout");
+    if (rc != SSG_OK) return rc;
     rc = check_ready(h, true);
     if (rc != SSG_OK) return rc;
     if (h->cfg.map_ring > 0 && !h->ring_ready) return fail(h, SSG_ERR_NOT_BOUND, "map_ring mode: call ssg_refill_worlds first");
@@ -1557,6 +1645,7 @@ int ssg_pop_rollout(ssg_handle *h, const ssg_population *pop, int K, const float
     if (rc != SSG_OK) return rc;
     rc = prepare(h);
     if (rc == SSG_OK) rc = prepare_policy(h);
+    if (rc == SSG_OK) rc = prepare_policy_filter(h);
     if (rc != SSG_OK) return rc;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const ssg_policy pol = pop_policy(*pop);
@@ -1565,17 +1654,17 @@ int ssg_pop_rollout(ssg_handle *h, const ssg_population *pop, int K, const float
     const size_t S = (size_t)step_stride_envs, D = (size_t)pol.obs_dim;
     for (int k = 0; k < K; ++k) { // ssg_rollout_policy's sequence: one policy launch for the whole population, then the step
         const size_t r = (size_t)k * S;
-        hipError_t e = ssg::launch_policy_pop(pol, P, n, h->cfg.env_id_base, dev_obs, dev_uniform_KN ? dev_uniform_KN + r : nullptr, seed,
-                                              step0 + k, dev_act_KN + r, dev_logp_KN + r, dev_value_KN + r,
-                                              dev_x_KND ? dev_x_KND + r * D : nullptr, st, slices);
+        hipError_t e = filter_step_update(h, n, slices, dev_obs, st); // (every member's rows into its own state rows)
+        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("observation filter launch: ") + hipGetErrorString(e));
+        e = policy_launch(h, pol, false, P, n, dev_obs, dev_uniform_KN ? dev_uniform_KN + r : nullptr, seed, step0 + k, dev_act_KN + r,
+                          dev_logp_KN + r, dev_value_KN + r, dev_x_KND ? dev_x_KND + r * D : nullptr, st, slices);
         if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population policy launch: ") + hipGetErrorString(e));
         rc = ssg_rollout_traj(h, dev_act_KN + r, 1, dev_obs, dev_reward_KN + r, dev_done_KN + r, dev_flags_KN ? dev_flags_KN + r : nullptr, 0,
                               stream);
         if (rc != SSG_OK) return rc;
     }
     if (dev_last_value) {
-        hipError_t e = ssg::launch_policy_pop(pol, P, n, h->cfg.env_id_base, dev_obs, nullptr, seed, step0 + K, nullptr, nullptr,
-                                              dev_last_value, nullptr, st, slices);
+        hipError_t e = policy_launch(h, pol, false, P, n, dev_obs, nullptr, seed, step0 + K, nullptr, nullptr, dev_last_value, nullptr, st, slices);
         if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population policy launch: ") + hipGetErrorString(e));
     }
     return SSG_OK;
@@ -2035,6 +2124,7 @@ static int run_evaluate(ssg_handle *h, const ssg_policy &pol, const ssg_populati
     if (rc != SSG_OK) return rc;
     rc = prepare(h);
     if (rc == SSG_OK) rc = prepare_policy(h);
+    if (rc == SSG_OK) rc = prepare_policy_filter(h);
     if (rc != SSG_OK) return rc;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const bool greedy = (ev.flags & SSG_EVAL_GREEDY) != 0;
@@ -2042,15 +2132,9 @@ static int run_evaluate(ssg_handle *h, const ssg_policy &pol, const ssg_populati
     const int32_t *slices = pop ? pop_slices(h) : nullptr;
     for (int k = 0; k < ev.n_steps; ++k) {
         const float *u = ev.dev_uniform_TN ? ev.dev_uniform_TN + (size_t)k * (size_t)N : nullptr;
-        hipError_t e;
-        if (pop)
-            e = greedy ? ssg::launch_policy_pop_greedy(pol, P, n, ev.dev_obs, ev.dev_act, ev.dev_logp, ev.dev_value, nullptr, st, slices)
-                       : ssg::launch_policy_pop(pol, P, n, h->cfg.env_id_base, ev.dev_obs, u, ev.seed, ev.step0 + k, ev.dev_act, ev.dev_logp,
-                                                ev.dev_value, nullptr, st, slices);
-        else
-            e = greedy ? ssg::launch_policy_act_greedy(pol, N, ev.dev_obs, ev.dev_act, ev.dev_logp, ev.dev_value, nullptr, st)
-                       : ssg::launch_policy_act(pol, N, h->cfg.env_id_base, ev.dev_obs, u, ev.seed, ev.step0 + k, ev.dev_act, ev.dev_logp,
-                                                ev.dev_value, nullptr, st);
+        // (a bound observation filter is applied and never updated: evaluation is frozen)
+        hipError_t e = policy_launch(h, pol, greedy, pop ? P : 0, n, ev.dev_obs, u, ev.seed, ev.step0 + k, ev.dev_act, ev.dev_logp, ev.dev_value,
+                                     nullptr, st, slices);
         if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string(what) + ": policy launch: " + hipGetErrorString(e));
         // (ssg_step as it stands, the call ssg_rollout_policy makes)
         rc = ssg_rollout_traj(h, ev.dev_act, 1, ev.dev_obs, ev.dev_reward, ev.dev_done, ev.dev_flags, 0, stream);
@@ -2067,6 +2151,7 @@ int ssg_evaluate(ssg_handle *h, const ssg_policy *pol, const ssg_eval *ev, void 
     int rc = pop_bound(h);
     if (rc == SSG_OK) rc = check_policy(h, pol, "ssg_evaluate");
     if (rc == SSG_OK) rc = check_eval(h, ev, "ssg_evaluate");
+    if (rc == SSG_OK) rc = check_filter_members(h, 1, "ssg_evaluate");
     if (rc != SSG_OK) return rc;
     return run_evaluate(h, *pol, nullptr, *ev, "ssg_evaluate", stream);
 }
@@ -2076,8 +2161,58 @@ int ssg_pop_evaluate(ssg_handle *h, const ssg_population *pop, const ssg_eval *e
     int rc = pop_bound(h);
     if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_evaluate");
     if (rc == SSG_OK) rc = check_eval(h, ev, "ssg_pop_evaluate");
+    if (rc == SSG_OK) rc = check_filter_members(h, pop->n_members, "ssg_pop_evaluate");
     if (rc != SSG_OK) return rc;
     return run_evaluate(h, pop_policy(*pop), pop, *ev, "ssg_pop_evaluate", stream);
+}
+
+int ssg_obs_filter_workspace_nbytes(int n_envs, int obs_dim, int n_members, size_t *nbytes)
+{
+    if (!nbytes || n_envs < 1 || obs_dim < 1 || n_members < 1 || obs_dim > ssg::kFltMaxDim || n_members > SSG_POP_MAX_MEMBERS)
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_obs_filter_workspace_nbytes: NULL nbytes, an argument < 1, obs_dim or n_members out of range");
+    *nbytes = ssg::filter_workspace_bytes(n_envs, obs_dim, n_members);
+    return SSG_OK;
+}
+
+int ssg_set_obs_filter(ssg_handle *h, const ssg_obs_filter *f)
+{
+    if (!h) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_set_obs_filter: NULL handle");
+    if (!f) { // unbind
+        h->flt = ssg_obs_filter{};
+        return SSG_OK;
+    }
+    const int rc = check_filter(h, f, "ssg_set_obs_filter");
+    if (rc != SSG_OK) return rc; // (the binding stays as it was)
+    h->flt = *f;
+    return SSG_OK;
+}
+
+int ssg_get_obs_filter(const ssg_handle *h, ssg_obs_filter *out)
+{
+    if (!h || !out) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_get_obs_filter: NULL handle or out");
+    *out = h->flt;
+    return SSG_OK;
+}
+
+int ssg_obs_filter_update(ssg_handle *h, const ssg_obs_filter *f, const double *dev_obs, void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc != SSG_OK) return rc;
+    if (!f) return fail(h, SSG_ERR_BAD_ARG, "ssg_obs_filter_update: NULL ssg_obs_filter");
+    rc = check_filter(h, f, "ssg_obs_filter_update");
+    if (rc != SSG_OK) return rc;
+    if (!dev_obs) return fail(h, SSG_ERR_BAD_ARG, "ssg_obs_filter_update: NULL dev_obs");
+    const int P = f->n_members;
+    if (P > 1) {
+        rc = check_members(h, P, "ssg_obs_filter_update");
+        if (rc != SSG_OK) return rc;
+    }
+    rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_filter_update(dev_obs, f->obs_dim, P, P > 1 ? pop_width(h, P) : h->cfg.n_envs, P > 1 ? pop_slices(h) : nullptr,
+                                             f->eps, f->dev_state, f->dev_workspace, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("observation filter launch: ") + hipGetErrorString(e));
+    return SSG_OK;
 }
 
 int ssg_eval_account(ssg_handle *h, int episodes_per_env, const double *dev_reward, const uint8_t *dev_done, const uint8_t *dev_flags,

@@ -331,6 +331,22 @@ constexpr int kEvalCols = SSG_EVAL_STATS;
 hipError_t launch_eval_account(int N, int E, const double *rew, const uint8_t *done, const uint8_t *flags, double *carry_ret, int32_t *carry,
                                int64_t *stats, hipStream_t stream);
 hipError_t launch_eval_reduce(int members, int n, const int64_t *stats, int64_t *out, hipStream_t stream, const int32_t *slices = nullptr);
+// the observation filter (shipsim_filter.hip): 256-row tiles, staged at most kFltChunk columns at a time; the workspace holds launch 1's
+// partials, f64 [members][filter_tiles(widest slice)][2][D]
+constexpr int kFltTile = 256, kFltChunk = 31, kFltMaxDim = SSG_MAX_HISTORY * (6 + SSG_MAX_BEAMS);
+inline int filter_tiles(long long n) { return (int)((n + kFltTile - 1) / kFltTile); }
+size_t filter_workspace_bytes(int n_envs, int obs_dim, int members);
+// the two launches: member m's n rows [m*n, (m+1)*n) of obs, or its slice (then n: the largest slice), into its SSG_FILTER_ROWS state rows
+hipError_t launch_filter_update(const double *obs, int D, int members, int n, const int32_t *slices, double eps, double *state, void *ws,
+                                hipStream_t stream);
+// The policy kernels with a bound filter (shipsim_policy.hip built with -DSSG_POLICY_FILTER_TU, an object of its own so that the unfiltered
+// instantiations are compiled as before): x = (float)clamp((obs - mean) / denom, +-clip) from member m's state rows in place of
+// obs / scale; everything else, and every argument, as the launchers above (greedy: no uniform, seed or step; members 0: one policy).
+struct ObsFilterArgs { const double *state; double clip; };
+hipError_t prepare_policy_filter();
+hipError_t launch_policy_filter(const ssg_policy &p, const ObsFilterArgs &f, bool greedy, int members, int n, long long env_base, const double *obs,
+                                const float *uniform, uint64_t seed, int64_t step, int32_t *act, float *logp, float *value, float *x,
+                                hipStream_t stream, const int32_t *slices);
 
 #ifdef __HIPCC__
 // One round of Philox4x32-10 (counter ctr, key key).  The counter-based streams of the library — fill_actions_kernel's actions

@@ -184,6 +184,22 @@ __device__ __forceinline__ float log_sum_exp(const float (&lg)[4], int A)
     return m + logf(s);
 }
 
+// Step 1's element: x = (float)(obs / scale[d]); FILTER: (float)clamp((obs - mean[d]) / denom[d], -clip, +clip) from the rows staged in LDS
+template <bool FILTER>
+__device__ __forceinline__ float step1_x(double o, const double *__restrict__ scale, const double *fs, int d, int D, double clip)
+{
+    if constexpr (FILTER) {
+        double v = (o - fs[d]) / fs[D + d];
+        if (clip > 0.0) {
+            v = v < -clip ? -clip : v;
+            v = v > clip ? clip : v;
+        }
+        return (float)v;
+    } else {
+        return (float)(o / scale[d]);
+    }
+}
+
 // (waves_per_eu(1, 2): lets the scheduler keep all 16 weight reads of a step in flight — 113 VGPRs — instead of two at a time)
 //
 // POP = false: ssg_policy_act's launch, n envs under one parameter buffer (plen unused).  POP = true: a population in one launch, grid
@@ -199,13 +215,20 @@ __device__ __forceinline__ float log_sum_exp(const float (&lg)[4], int A)
 // = {o_m, n_m, ...} of the slices table; the grid is as wide as the largest slice needs, and a workgroup whose first env is past n_m
 // leaves as a whole ahead of every barrier.  Nothing below relies on a member's base being a multiple of the wave: every global access
 // is a scalar element of its row.  A kernel of its own takes the table, so the other instantiations keep their argument layout.
-template <bool POP, bool SPLIT, bool GREEDY, bool SLICED>
+// FILTER (ssg_set_obs_filter): step 1 forms x from a running mean / std filter instead of the fixed scale.  `scale` then points at the
+// filter's state rows, f64 [members][SSG_FILTER_ROWS][D] (mean, M2, denom, count), member m = blockIdx.y reads its own, and
+// x = (float)clamp((obs - mean) / denom, -clip, +clip): subtraction, division and clamp in f64, one rounding to f32; clip == 0: no
+// clamp; a denom entry of 0.0 (the rows of a state nothing was merged into yet) divides by 1.  Kernels of their own again (they take
+// clip), built in an object of their own (-DSSG_POLICY_FILTER_TU), and everything FILTER adds sits under `if constexpr (FILTER)` or in
+// step1_x: a declaration outside them, even an unused one, renumbers registers in the other instantiations.  Their device code is
+// compared with the previous build's whenever this body changes (profiles/obs_filter/README.md).
+template <bool POP, bool SPLIT, bool GREEDY, bool SLICED, bool FILTER = false>
 __device__ __forceinline__ void policy_act_body(const ssg_policy &p, const float *__restrict__ params, const double *__restrict__ scale,
                                                 int n, long long env_base, const double *__restrict__ obs,
                                                 const float *__restrict__ uniform, uint64_t seed, int64_t step,
                                                 int32_t *__restrict__ act_out, float *__restrict__ logp_out,
                                                 float *__restrict__ value_out, float *__restrict__ x_out, int plen,
-                                                const int32_t *__restrict__ slices)
+                                                const int32_t *__restrict__ slices, double clip = 0.0)
 {
     static_assert(POP || !SLICED, "slices are a population's");
     extern __shared__ float4 lds4[];
@@ -219,6 +242,7 @@ __device__ __forceinline__ void policy_act_body(const ssg_policy &p, const float
         }
         const size_t D = (size_t)p.obs_dim;
         params += (size_t)blockIdx.y * (size_t)plen;
+        if constexpr (FILTER) scale += (size_t)blockIdx.y * SSG_FILTER_ROWS * D;
         env_base += (long long)m0;
         obs += m0 * D;
         if (!GREEDY && uniform) uniform += m0;
@@ -244,8 +268,17 @@ __device__ __forceinline__ void policy_act_body(const ssg_policy &p, const float
         float *xdst = x_out ? x_out + (size_t)e0 * D : nullptr;
         const int total = ne * D, qd = kPolWave / D, rd = kPolWave % D;
         int d = lane % D, el = lane / D;
+        if constexpr (FILTER) { // mean [D], then denom [D] (0 -> 1), staged in the weight tile, which is free until the first dense
+            double *fs = reinterpret_cast<double *>(wt); // tile (its barrier follows this loop's last read)
+            for (int i = lane; i < D; i += kPolWave) {
+                const double den = scale[2 * D + i];
+                fs[i] = scale[i];
+                fs[D + i] = den == 0.0 ? 1.0 : den;
+            }
+            __syncthreads();
+        }
         for (int i = lane; i < total; i += kPolWave) {
-            const float xv = (float)(src[i] / scale[d]);
+            const float xv = step1_x<FILTER>(src[i], scale, reinterpret_cast<const double *>(wt), d, D, clip);
             bufA[d * kPolStride + el] = xv;
             if (xdst) xdst[i] = xv;
             d += rd;
@@ -447,9 +480,85 @@ __global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1
     policy_dist_body<SPLIT, true>(p, params, 0, N, x, logp_all, plen, slices);
 }
 
+#ifdef SSG_POLICY_FILTER_TU
+template <bool POP, bool SPLIT, bool GREEDY>
+__global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1, 2))) policy_act_filter_kernel(const ssg_policy p, const float *__restrict__ params, const double *__restrict__ fstate,
+                                                              int n, long long env_base, const double *__restrict__ obs,
+                                                              const float *__restrict__ uniform, uint64_t seed, int64_t step,
+                                                              int32_t *__restrict__ act_out, float *__restrict__ logp_out,
+                                                              float *__restrict__ value_out, float *__restrict__ x_out, int plen, double clip)
+{
+    policy_act_body<POP, SPLIT, GREEDY, false, true>(p, params, fstate, n, env_base, obs, uniform, seed, step, act_out, logp_out, value_out, x_out,
+                                                     plen, nullptr, clip);
+}
+
+template <bool SPLIT, bool GREEDY>
+__global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1, 2))) policy_act_sliced_filter_kernel(const ssg_policy p, const float *__restrict__ params, const double *__restrict__ fstate,
+                                                              const int32_t *__restrict__ slices, long long env_base, const double *__restrict__ obs,
+                                                              const float *__restrict__ uniform, uint64_t seed, int64_t step,
+                                                              int32_t *__restrict__ act_out, float *__restrict__ logp_out,
+                                                              float *__restrict__ value_out, float *__restrict__ x_out, int plen, double clip)
+{
+    policy_act_body<true, SPLIT, GREEDY, true, true>(p, params, fstate, 0, env_base, obs, uniform, seed, step, act_out, logp_out, value_out, x_out,
+                                                     plen, slices, clip);
+}
+#endif
+
 } // namespace
 
 static bool is_split(const ssg_policy &p) { return (p.activation & SSG_POLICY_SEPARATE_VALUE) != 0; }
+
+#ifdef SSG_POLICY_FILTER_TU
+// the FILTER instantiations, indexed [population][split][greedy] and [split][greedy]
+typedef void (*FilterKernel)(const ssg_policy, const float *, const double *, int, long long, const double *, const float *, uint64_t, int64_t,
+                             int32_t *, float *, float *, float *, int, double);
+typedef void (*FilterSlicedKernel)(const ssg_policy, const float *, const double *, const int32_t *, long long, const double *, const float *,
+                                   uint64_t, int64_t, int32_t *, float *, float *, float *, int, double);
+static FilterKernel filter_kernel(bool pop, bool split, bool greedy)
+{
+    static const FilterKernel k[2][2][2] = {
+        {{policy_act_filter_kernel<false, false, false>, policy_act_filter_kernel<false, false, true>},
+         {policy_act_filter_kernel<false, true, false>, policy_act_filter_kernel<false, true, true>}},
+        {{policy_act_filter_kernel<true, false, false>, policy_act_filter_kernel<true, false, true>},
+         {policy_act_filter_kernel<true, true, false>, policy_act_filter_kernel<true, true, true>}}};
+    return k[pop][split][greedy];
+}
+static FilterSlicedKernel filter_sliced_kernel(bool split, bool greedy)
+{
+    static const FilterSlicedKernel k[2][2] = {{policy_act_sliced_filter_kernel<false, false>, policy_act_sliced_filter_kernel<false, true>},
+                                               {policy_act_sliced_filter_kernel<true, false>, policy_act_sliced_filter_kernel<true, true>}};
+    return k[split][greedy];
+}
+
+hipError_t prepare_policy_filter()
+{
+    for (int i = 0; i < 12; ++i) {
+        const void *k = i < 8 ? reinterpret_cast<const void *>(filter_kernel((i & 4) != 0, (i & 2) != 0, (i & 1) != 0))
+                              : reinterpret_cast<const void *>(filter_sliced_kernel((i & 2) != 0, (i & 1) != 0));
+        hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_policy_filter(const ssg_policy &p, const ObsFilterArgs &f, bool greedy, int members, int n, long long env_base, const double *obs,
+                                const float *uniform, uint64_t seed, int64_t step, int32_t *act, float *logp, float *value, float *x,
+                                hipStream_t stream, const int32_t *slices)
+{
+    const unsigned grid = (unsigned)((n + kPolWave - 1) / kPolWave); // (n: the largest slice)
+    const size_t lds = policy_lds_bytes(p, act != nullptr);
+    const bool pop = members > 0;
+    if (greedy) { uniform = nullptr; seed = 0; step = 0; env_base = 0; }
+    if (slices)
+        hipLaunchKernelGGL(filter_sliced_kernel(is_split(p), greedy), dim3(grid, (unsigned)members), dim3(kPolWave), lds, stream, p, p.dev_params,
+                           f.state, slices, env_base, obs, uniform, seed, step, act, logp, value, x, ppo_packed_len(p), f.clip);
+    else
+        hipLaunchKernelGGL(filter_kernel(pop, is_split(p), greedy), dim3(grid, pop ? (unsigned)members : 1u), dim3(kPolWave), lds, stream, p,
+                           p.dev_params, f.state, n, env_base, obs, uniform, seed, step, act, logp, value, x, pop ? ppo_packed_len(p) : 0,
+                           f.clip);
+    return hipGetLastError();
+}
+#else
 
 // both_towers: a separate-value launch that samples actions too (two layers: the third activation buffer, H rows)
 size_t policy_lds_bytes(const ssg_policy &p, bool both_towers)
@@ -544,5 +653,7 @@ hipError_t launch_policy_dist(const ssg_policy &p, int members, int n, long long
                        dim3(kPolWave), policy_lds_bytes(p, false), stream, p, p.dev_params, n, N, x, logp_all, ppo_packed_len(p));
     return hipGetLastError();
 }
+
+#endif // SSG_POLICY_FILTER_TU
 
 } // namespace ssg

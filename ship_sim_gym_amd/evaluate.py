@@ -78,7 +78,9 @@ def derive(per_member):
 
 
 class NativeEvaluator(object):
-    """Owns the one-row scratch buffers, the carries and the stats tensors of evaluations on `env` (allocated once)."""
+    """Owns the one-row scratch buffers, the carries and the stats tensors of evaluations on `env` (allocated once).  An observation
+    filter bound to `env` (``env.set_obs_filter``; usually a trainer's ``ObsFilter.frozen(env)``) normalises the observations of every
+    policy launch and is never updated by an evaluation, whatever its record says."""
 
     def __init__(self, env):
         torch = _torch()

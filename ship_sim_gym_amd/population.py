@@ -460,17 +460,25 @@ class PopulationPPO(object):
         must not itself be a destination.  The source's ``kl_coef`` travels with its parameters: the coefficient was adapted to THOSE
         parameters (to how far their updates move the distribution), so it belongs to the weights, not to the scheduler's
         hyper-parameters.  Those are the scheduler's business (PBTScheduler returns the new lists).  So does the source's Adam step
-        count (``member_steps``): the bias correction belongs to the moments that are copied."""
+        count (``member_steps``): the bias correction belongs to the moments that are copied.  With an observation filter bound to
+        the env (``env.set_obs_filter``), the source's filter rows travel too: an exploited member must not keep statistics its new
+        weights were never trained on."""
         torch = _torch()
         src = [int(s) for s in src]
         if len(src) != self.n_members:
             raise ValueError("PopulationPPO.exploit: src has %d entries for %d members" % (len(src), self.n_members))
         arr = (C.c_int32 * len(src))(*src)
         pop, h = self.population.to_native(), self.env._h
+        flt = getattr(self.env, "obs_filter", None)
+        if flt is not None and flt.n_members != self.n_members:  # (judged before anything is copied)
+            raise ValueError("PopulationPPO.exploit: the env's observation filter has %d members, the population %d"
+                             % (flt.n_members, self.n_members))
         with torch.cuda.device(self.population.device):
             N.check(N.lib().ssg_pop_exploit(h, C.byref(pop), arr, C.c_void_p(self.adam_mv.data_ptr()), self._stream()), h,
                     "ssg_pop_exploit")
             self.kl_coef.copy_(self.kl_coef[torch.tensor(src, device=self.population.device)])
+            if flt is not None:  # (an indexed copy on the handle's stream; the gather is materialised before the copy writes)
+                flt.state.copy_(flt.state[torch.tensor(src, device=flt.state.device)])
         steps0 = self._steps0()
         self._advance([steps0[s] for s in src], [0] * self.n_members)
 

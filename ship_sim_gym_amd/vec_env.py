@@ -768,6 +768,34 @@ class ShipVecEnv(*_BASES):
                                             n, self._stream()), self._h, "ssg_pop_rollout")
         return {k: (v[:K] if k != "last_val" else v) for k, v in out.items()}
 
+    # ------------------------------------------------------------------------------------------------
+    # the observation filter (ssg_set_obs_filter; ship_sim_gym_amd/obs_filter.py)
+    # ------------------------------------------------------------------------------------------------
+    def set_obs_filter(self, f):
+        """Bind an ObsFilter (or one of its frozen() views) to this env: every policy launch on it — policy_act, rollout_policy,
+        population_act, rollout_population, NativeEvaluator — then forms x = clamp((obs - mean) / denom) from the filter's state instead
+        of obs / obs_scale, a single policy with a filter of 1 member, a population of P members with one of P; the rollout loops
+        merge each step's observations first when the filter is updating.  The library keeps a copy of the record, this env a
+        reference to the filter (whose tensors the launches read).  None unbinds; a refused binding leaves the old one in place."""
+        old = getattr(self, "_obs_filter", None)
+        if f is None:
+            N.check(N.lib().ssg_set_obs_filter(self._h, None), self._h, "ssg_set_obs_filter")
+        else:
+            if f.state.device != self.device:
+                raise ValueError("set_obs_filter: the filter lives on %s, the env on %s" % (f.state.device, self.device))
+            rec = f.to_native()
+            N.check(N.lib().ssg_set_obs_filter(self._h, C.byref(rec)), self._h, "ssg_set_obs_filter")
+        if old is not None and old is not f and self in old._bound:
+            old._bound.remove(self)
+        if f is not None and self not in f._bound:
+            f._bound.append(self)
+        self._obs_filter = f
+
+    @property
+    def obs_filter(self):
+        """The bound ObsFilter, or None."""
+        return getattr(self, "_obs_filter", None)
+
     def random_actions(self, seed, step0, K):
         """int32 [K, N] Philox action stream keyed by (seed, step, global env id), generated on the device."""
         torch = _torch()
@@ -852,6 +880,9 @@ class ShipVecEnv(*_BASES):
 
     def close(self):
         self.__dict__.pop("_traj_plans", None)
+        flt = self.__dict__.pop("_obs_filter", None)
+        if flt is not None and self in flt._bound:
+            flt._bound.remove(self)
         hs = self.__dict__.get("_host")
         if hs is not None:
             try:

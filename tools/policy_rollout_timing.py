@@ -13,6 +13,14 @@ gives the kernel alone, see tools/README.md).  One JSON line on stdout.
 
 --separate-value measures, after each env count's shared-body figures and in the same process, the same things for ActorCritic with a
 value network of its own (two 64-64 towers: SSG_POLICY_SEPARATE_VALUE); its results carry "separate_value": true.
+
+    python tools/policy_rollout_timing.py --obs-filter [--beams 8] [--envs 65536,4096] [--horizon 64] [--repeats 7]
+
+--obs-filter measures the observation filter (ship_sim_gym_amd/obs_filter.py) instead: on ONE native env per env count (--beams 8,
+history 2 -> D = 28) whole rollouts are timed with nothing bound, with a filter bound and updating, and with it bound frozen, the
+three alternating in every repeat; and the filter's two launches alone (50 back-to-back ssg_obs_filter_update calls).  Medians and
+every repeat in us per rollout step; the shader clock as rocm-smi reports it before and after (null when it cannot be read).  The
+unbound figure of two builds of the library is compared by running this mode alternately with SSG_LIB_PATH set to each.
 """
 import argparse
 import ctypes as C
@@ -102,16 +110,83 @@ def measure(mod, n, horizon, repeats, dev, separate_value=False):
             "repeats_us": {k: [round(t, 2) for t in v] for k, v in times.items()}}
 
 
+def _sclk():
+    """The shader clock line(s) of `rocm-smi --showclocks` for the first device (read only), or None."""
+    import subprocess
+    try:
+        out = subprocess.run(["rocm-smi", "-d", "0", "--showclocks"], capture_output=True, text=True, timeout=20).stdout
+    except Exception:
+        return None
+    lines = [ln.strip() for ln in out.splitlines() if "sclk" in ln.lower()]
+    return lines or None
+
+
+def measure_filter(mod, n, horizon, repeats, dev, beams):
+    from ship_sim_gym_amd.obs_filter import ObsFilter
+    torch.manual_seed(0)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    probe = mod.ShipVecEnv(1, mod.GameConfig, mod.EnvConfig, device=dev, n_maps=1, n_beams=beams)
+    D, A = probe.states_history, probe.action_space.n
+    probe.close()
+    net = mod.ActorCritic(D, A).to(dev)
+    shards = mod.make_shards(n, "native", net, dev, horizon, env_kw={"n_beams": beams})
+    env = shards[0].env
+    env.reset_tensor()
+    policy = mod.NativePolicy.from_actor_critic(net, shards[0].scale)
+    flt = ObsFilter(env)
+    frozen = flt.frozen()
+    bind = {"unbound": None, "updating": flt, "frozen": frozen}
+
+    def run(m):
+        env.set_obs_filter(bind[m])
+        mod.rollout(shards, horizon, "native", gen, policy)
+    clock0 = _sclk()
+    for m in ("unbound", "updating", "frozen") * 2:  # warm-up: two rollouts each
+        run(m)
+    torch.cuda.synchronize()
+    times = {m: [] for m in bind}
+    for _ in range(repeats):
+        for m in bind:
+            env.set_obs_filter(bind[m])
+            times[m].append(_timed(lambda: mod.rollout(shards, horizon, "native", gen, policy)) / horizon)
+    env.set_obs_filter(None)
+    rec = flt.to_native()
+    L, h, st, obs = N.lib(), env._h, env._stream(), C.c_void_p(env.obs.data_ptr())
+
+    def launches(k):
+        for _ in range(k):
+            N.check(L.ssg_obs_filter_update(h, C.byref(rec), obs, st), h, "ssg_obs_filter_update")
+    launches(5)
+    torch.cuda.synchronize()
+    update_us = [_timed(lambda: launches(50)) / 50 for _ in range(repeats)]
+    clock1 = _sclk()
+    env.close()
+    med = {m: statistics.median(v) for m, v in times.items()}
+    return {"envs": n, "obs_dim": D, "hidden": 64, "layers": 2, "n_actions": A, "horizon": horizon,
+            "unbound_us_per_step": round(med["unbound"], 2), "updating_us_per_step": round(med["updating"], 2),
+            "frozen_us_per_step": round(med["frozen"], 2), "filter_update_us": round(statistics.median(update_us), 2),
+            "repeats_us": {k: [round(t, 2) for t in v] for k, v in times.items()}, "filter_update_repeats_us": [round(t, 2) for t in update_us],
+            "sclk_before": clock0, "sclk_after": clock1}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", default="65536,4096")
     ap.add_argument("--horizon", type=int, default=64)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--separate-value", action="store_true", help="also measure the separate-value-network shape, in the same process")
+    ap.add_argument("--obs-filter", action="store_true", help="measure the observation filter instead (unbound / updating / frozen rollouts)")
+    ap.add_argument("--beams", type=int, default=8, help="lidar beams of the --obs-filter env (8 -> D = 28)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     mod = _ppo()
     dev = "cuda:0"
+    if a.obs_filter:
+        res = [measure_filter(mod, int(n), a.horizon, a.repeats, dev, a.beams) for n in a.envs.split(",")]
+        print(json.dumps({"tool": "policy_rollout_timing", "mode": "obs_filter", "lib": N.LIB_PATH, "device": torch.cuda.get_device_name(0),
+                          "results": res}))
+        return
     res = [measure(mod, int(n), a.horizon, a.repeats, dev, sep) for n in a.envs.split(",") for sep in ([False, True] if a.separate_value else [False])]
     print(json.dumps({"tool": "policy_rollout_timing", "device": torch.cuda.get_device_name(0), "results": res}))
 

@@ -3,6 +3,7 @@
 done, "Episode reward"), and the ``model.predict(obs, deterministic=True)`` loop Stable-Baselines users write, against this package.
 
     python train/evaluate_native.py --envs 4096 --episodes 4 [--checkpoint net.pt] [--sampled] [--separate-value] [--seed 0]
+                                     [--obs-filter FILE]
 
 Builds train/ppo_torch.py's ActorCritic — loaded from ``--checkpoint`` (a ``state_dict`` saved by ``torch.save``) or with seeded random
 weights — and runs it on ``--envs`` envs until every env has finished ``--episodes`` episodes (ship_sim_gym_amd/evaluate.py: one
@@ -10,6 +11,9 @@ policy launch, one step and one accounting launch per step, enqueued from C).  T
 ``--sampled``.  Every env contributes exactly its first ``--episodes`` episodes, so short episodes are not over-weighted.  Prints one
 row per policy: episodes, mean return and length, how the episodes ended (collision, out of bounds, time-out, no goals left; not
 exclusive of each other) and goals per episode.
+
+``--obs-filter FILE``: normalise the observations with the running mean / std statistics a training run saved (train/ppo_torch.py
+``--save-obs-filter``), frozen — an evaluation never updates them — instead of the fixed division by the largest bound.
 
 Out of scope here: recording trajectories (rollout.py --out) and rendering during evaluation.
 """
@@ -35,6 +39,8 @@ def make_arg_parser():
     ap.add_argument("--sampled", action="store_true", help="draw the actions (Philox keyed by --seed) instead of the arg-max")
     ap.add_argument("--separate-value", action="store_true", help="the ActorCritic has a value network of its own (pi_body, pi, vf_body, v)")
     ap.add_argument("--seed", type=int, default=0, help="of the random weights and of the sampled actions")
+    ap.add_argument("--obs-filter", default=None, metavar="FILE",
+                    help="observation filter statistics saved by train/ppo_torch.py --save-obs-filter (applied frozen); default: obs / max bound")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -43,7 +49,7 @@ def parse_args(argv=None):
     return make_arg_parser().parse_args(argv)
 
 
-def evaluate(envs=4096, episodes=4, checkpoint=None, sampled=False, separate_value=False, seed=0, device="cuda:0", log=print):
+def evaluate(envs=4096, episodes=4, checkpoint=None, sampled=False, separate_value=False, seed=0, device="cuda:0", log=print, obs_filter=None):
     import torch
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     from ppo_torch import ActorCritic
@@ -59,6 +65,11 @@ def evaluate(envs=4096, episodes=4, checkpoint=None, sampled=False, separate_val
     net = net.to(env.device)
     scale = torch.full((env.states_history,), float(max(env.bounds)), dtype=torch.float64, device=env.device)
     policy = NativePolicy.from_actor_critic(net, scale)
+    if obs_filter is not None:
+        from ship_sim_gym_amd.obs_filter import ObsFilter
+        sd = torch.load(obs_filter, map_location="cpu")
+        flt = ObsFilter(env, n_members=int(sd["n_members"]), update=False).load_state_dict(sd)
+        env.set_obs_filter(flt)
     result = NativeEvaluator(env).evaluate(policy, episodes, greedy=not sampled, seed=seed)
     log(format_table(result))
     if not result["complete"]:
@@ -72,4 +83,4 @@ def evaluate(envs=4096, episodes=4, checkpoint=None, sampled=False, separate_val
 if __name__ == "__main__":
     a = parse_args()
     evaluate(envs=a.envs, episodes=a.episodes, checkpoint=a.checkpoint, sampled=a.sampled, separate_value=a.separate_value, seed=a.seed,
-             device=a.device)
+             device=a.device, obs_filter=a.obs_filter)

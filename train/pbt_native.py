@@ -47,6 +47,12 @@ each exploit (member <- source) and each mutation (key, resample / perturb, old 
 --eval-every U --eval-episodes E (default off): every U updates every member is evaluated greedily (the arg-max action) for E episodes
 per env on a second ShipVecEnv of its own (ship_sim_gym_amd/evaluate.py; the reference's train/rllib/rollout.py:8-26), so the training
 envs are not disturbed, and the table is printed.  The ranking stays by training episodes, the reference's reward_attr.
+
+--obs-filter (default off): observations are normalised by a running mean / std filter on the device, one set of statistics per member
+(ship_sim_gym_amd/obs_filter.py; RLlib's "PPO" default MeanStdFilter behind train/rllib/pbt.py:50, where every trial has its own
+filter), instead of the fixed division by the largest bound.  Every rollout step merges each member's own rows into its statistics
+before the policy launch; the statistics stay with the member through a re-slice, travel with the weights on an exploit, and the
+--eval-every env reads them frozen.
 """
 import argparse
 import os
@@ -110,6 +116,8 @@ def make_arg_parser():
                     help="every U UPDATES evaluate every member greedily on a second env of its own and print it; 0 = off "
                          "(the ranking stays by training episodes, the reference's reward_attr)")
     ap.add_argument("--eval-episodes", type=int, default=1, metavar="E", help="episodes counted per env by each evaluation")
+    ap.add_argument("--obs-filter", action="store_true",
+                    help="normalise observations with a running mean / std filter per member on the device; default: obs / max bound")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -169,7 +177,7 @@ def parse_args(argv=None):
 def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every=5, seed=0, epochs=2, minibatches=4, lrs=None,
           pbt=True, device="cuda:0", log=print, return_details=False, kl_coeff=0.0, kl_target=0.01, vf_clip=0.0, max_grad_norm=0.0,
           separate_value=False, mutate_schedule=False, max_epochs=30, eval_every=0, eval_episodes=1, envs=None, mutate_batch=False,
-          batch_shares=None, quantum=None):
+          batch_shares=None, quantum=None, obs_filter=False):
     import torch
     from ship_gym.config import EnvConfig, GameConfig
     from ship_sim_gym_amd.population import NativePopulation, PBTScheduler, PopulationPPO, reference_mutations, slices_for_batch_sizes
@@ -225,6 +233,13 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
         log("slices: train_batch_size %s -> envs %s (quantum %d)" % (batch_sizes, slices, quantum))
     ppo = PopulationPPO(pop, env, lam=INITIAL["lambda"], clip=INITIAL["clip_param"], lr=list(lrs) if lrs is not None else INITIAL["lr"],
                         vf_clip=vf_clip, max_grad_norm=max_grad_norm, kl_coef=kl_coeff, kl_target=kl_target if kl_coeff > 0 else 0.0)
+    flt = None
+    if obs_filter:  # per-member statistics; a member's rows are its slice, whatever the slices currently are
+        from ship_sim_gym_amd.obs_filter import ObsFilter
+        flt = ObsFilter(env, n_members=P)
+        env.set_obs_filter(flt)
+        if eval_env is not None:
+            eval_env.set_obs_filter(flt.frozen(eval_env))
     env.reset_tensor()
     window = torch.zeros((P, 3), dtype=torch.int64, device=dev)  # episodes since the last perturbation
     scores = [float("-inf")] * P
@@ -319,6 +334,9 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
                "member_steps": list(ppo.member_steps), "kl_coef": ppo.kl_coef.detach().cpu().tolist(), "evaluations": evals,
                "slices": list(env.population_slices) if sliced else [n] * P, "reslices": reslices,
                "train_batch_size": list(batch_sizes) if sliced else [samples] * P}
+    if flt is not None:
+        details["obs_filter"] = flt.state_dict()
+        log("observation filter: rows merged per member %s" % [int(c) for c in details["obs_filter"]["state"][:, 3, 0].tolist()])
     if eval_env is not None:
         eval_env.close()
     env.close()
@@ -331,7 +349,7 @@ def main(argv=None):
           seed=a.seed, epochs=a.epochs, minibatches=a.minibatches, lrs=a.lrs, pbt=a.pbt, device=a.device, kl_coeff=a.kl_coeff,
           kl_target=a.kl_target, vf_clip=a.vf_clip, max_grad_norm=a.max_grad_norm, separate_value=a.separate_value,
           mutate_schedule=a.mutate_schedule, max_epochs=a.max_epochs, eval_every=a.eval_every, eval_episodes=a.eval_episodes, envs=a.envs,
-          mutate_batch=a.mutate_batch, batch_shares=a.batch_shares, quantum=a.quantum)
+          mutate_batch=a.mutate_batch, batch_shares=a.batch_shares, quantum=a.quantum, obs_filter=a.obs_filter)
 
 
 if __name__ == "__main__":

@@ -5,7 +5,7 @@ stable-baselines (absent from this image).  The env side is the only point: obse
 leave the GPU; the policy is a small MLP in fp32.
 
     python train/ppo_torch.py --envs 4096 --updates 20 [--mode eager|graph|pingpong|native] [--update torch|native] [--separate-value]
-                              [--eval-every U --eval-episodes E]
+                              [--eval-every U --eval-episodes E] [--obs-filter [--save-obs-filter FILE]]
 
 Four ways to run the rollout loop (the reference's `model.learn` -> runner.run(): one `env.step(actions)` per policy
 forward, train/stable_baselines/ppo.py:84-100,122-123) — same arithmetic, same results bit for bit:
@@ -34,6 +34,12 @@ Two ways to run the update after each rollout (GAE, advantage normalisation, epo
 ``--eval-every U`` (``--mode native`` only; default off): every U updates the current policy is evaluated greedily for
 ``--eval-episodes`` episodes per env on a second ShipVecEnv of its own (ship_sim_gym_amd/evaluate.py; the reference's
 train/rllib/rollout.py:8-26), so the training envs are not disturbed, and the result is printed.
+
+``--obs-filter`` (``--mode native`` only; default off): observations are normalised by a running mean / std filter on the device
+(ship_sim_gym_amd/obs_filter.py — RLlib's default MeanStdFilter, Stable-Baselines' VecNormalize) instead of the fixed division by the
+largest bound: every rollout step first merges its observations into the statistics, then normalises them; the ``--eval-every`` env
+gets a frozen view of the same statistics.  With ``--update native`` the per-update loss terms are printed as well.
+``--save-obs-filter FILE`` saves the statistics (``ObsFilter.state_dict``) for train/evaluate_native.py ``--obs-filter FILE``.
 
 The sampling noise of a whole rollout is drawn in one call before it (uniforms [horizon, envs], inverse-CDF sampling inside
 the step), so a captured step holds no random-number generator state and replays exactly what the eager loop computes.
@@ -203,8 +209,12 @@ def rollout(shards, horizon, mode, gen, policy=None):
 
 def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, gamma=0.99, lam=0.95, clip=0.2,
           device="cuda:0", seed=0, log=print, mode="eager", return_details=False, env_kw=None, update="torch", separate_value=False,
-          eval_every=0, eval_episodes=1, eval_envs=None):
+          eval_every=0, eval_episodes=1, eval_envs=None, obs_filter=False, save_obs_filter=None):
     assert mode in ("eager", "graph", "pingpong", "native")
+    if (obs_filter or save_obs_filter) and mode != "native":
+        raise ValueError("obs_filter normalises inside the native policy launch: it needs mode='native' (got mode=%r)" % (mode,))
+    if save_obs_filter and not obs_filter:
+        raise ValueError("save_obs_filter needs obs_filter=True")
     if eval_every and mode != "native":
         raise ValueError("eval_every evaluates the native policy on the device: it needs mode='native' (got mode=%r)" % (mode,))
     if eval_every < 0 or eval_episodes < 1:
@@ -227,11 +237,18 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         sh.env.reset_tensor()
     policy = NativePolicy.from_actor_critic(net, shards[0].scale) if mode == "native" else None
     ppo = NativePPO(policy, shards[0].env, lr=lr, clip=clip) if update == "native" else None
+    flt = None
+    if obs_filter:  # (the rollout loop merges each step's observations, then normalises them; obs_scale is no longer read)
+        from ship_sim_gym_amd.obs_filter import ObsFilter
+        flt = ObsFilter(shards[0].env)
+        shards[0].env.set_obs_filter(flt)
     evaluator, evals = None, []
     if eval_every:  # a second env of its own: evaluation resets and steps it, the training envs keep their episodes
         from ship_sim_gym_amd.evaluate import NativeEvaluator
         eval_env = ShipVecEnv(int(eval_envs or min(envs, 1024)), GameConfig, EnvConfig, device=device, n_maps=64, **dict(env_kw or {}))
         evaluator = NativeEvaluator(eval_env)
+        if flt is not None:
+            eval_env.set_obs_filter(flt.frozen(eval_env))  # the training statistics, never updated by an evaluation
     if mode in ("graph", "pingpong"):
         # one eager warm-up step per shard OUTSIDE the capture (prepares the library's kernels and hipBLASLt's workspaces), then the
         # envs start over; the capture itself runs nothing
@@ -259,7 +276,12 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
             nb = dict(shards[0].native_out)
             ppo.gae(nb, gamma, lam)
             n = horizon * envs
-            ppo.update(nb, torch.stack([torch.randperm(n, device=dev, generator=gen) for _ in range(epochs)]), epochs, minibatches)
+            st_upd = ppo.update(nb, torch.stack([torch.randperm(n, device=dev, generator=gen) for _ in range(epochs)]), epochs, minibatches,
+                                stats=flt is not None)
+            if flt is not None:
+                pg, vf, ent = (float(v) for v in st_upd[-1, :3])
+                log("update %3d  last minibatch: policy loss %+.5f  value loss %.5f  entropy %.5f  (obs filter: %d rows merged)" % (
+                    u, pg, vf, ent, int(flt.count[0].item())))
         else:
             if native_last_val is not None:
                 last_val = native_last_val
@@ -316,6 +338,11 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
                "rollout_us_per_step": t_roll * 1e6 / (horizon * updates), "rollout_seconds": t_roll, "update_seconds": t_upd, "total_seconds": t_all,
                "snapshots": snapshots, "final_state": [env_columns(sh.env) for sh in shards] if return_details is True else None,
                "params": [p.detach().clone() for p in net.parameters()] if return_details is True else None, "evaluations": evals}
+    if flt is not None:
+        details["obs_filter"] = flt.state_dict()
+        if save_obs_filter:
+            torch.save(details["obs_filter"], save_obs_filter)
+            log("observation filter statistics (%d rows merged) saved to %s" % (int(details["obs_filter"]["state"][0, 3, 0]), save_obs_filter))
     if evaluator is not None:
         evaluator.env.close()
     for sh in shards:
@@ -337,6 +364,9 @@ def make_arg_parser():
     ap.add_argument("--eval-every", type=int, default=0, metavar="U",
                     help="every U updates evaluate the policy greedily on a second env of its own (needs --mode native); 0 = off")
     ap.add_argument("--eval-episodes", type=int, default=1, metavar="E", help="episodes counted per env by each evaluation")
+    ap.add_argument("--obs-filter", action="store_true",
+                    help="normalise observations with a running mean / std filter on the device (needs --mode native); default: obs / max bound")
+    ap.add_argument("--save-obs-filter", default=None, metavar="FILE", help="save the filter's statistics at the end (needs --obs-filter)")
     return ap
 
 
@@ -350,10 +380,14 @@ def parse_args(argv=None):
         ap.error("--eval-every needs --mode native (the evaluation runs the native policy on the device)")
     if a.update == "native" and a.mode != "native":
         ap.error("--update native needs --mode native (the update runs on the native policy's packed parameters)")
+    if a.obs_filter and a.mode != "native":
+        ap.error("--obs-filter needs --mode native (the filter runs inside the native policy launch)")
+    if a.save_obs_filter and not a.obs_filter:
+        ap.error("--save-obs-filter needs --obs-filter")
     return a
 
 
 if __name__ == "__main__":
     a = parse_args()
     train(envs=a.envs, updates=a.updates, horizon=a.horizon, mode=a.mode, update=a.update, separate_value=a.separate_value,
-          eval_every=a.eval_every, eval_episodes=a.eval_episodes)
+          eval_every=a.eval_every, eval_episodes=a.eval_episodes, obs_filter=a.obs_filter, save_obs_filter=a.save_obs_filter)
