@@ -1043,129 +1043,12 @@ static int check_filter(ssg_handle *h, const ssg_obs_filter *f, const char *what
     return SSG_OK;
 }
 
-// a policy call of `members` members (1: a single policy) against the bound filter, if any: its member count must be the call's
-static int check_filter_members(ssg_handle *h, int members, const char *what)
-{
-    if (!h->flt.struct_size || h->flt.n_members == members) return SSG_OK;
-    char buf[200];
-    std::snprintf(buf, sizeof buf, ": the bound observation filter has %d members, this call %d (ssg_set_obs_filter)", h->flt.n_members, members);
-    return fail(h, SSG_ERR_BAD_ARG, std::string(what) + buf);
-}
-
 static int prepare_policy_filter(ssg_handle *h)
 {
     if (!h->flt.struct_size || h->policy_filter_prepared) return SSG_OK;
     hipError_t e = ssg::prepare_policy_filter();
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("prepare_policy_filter: ") + hipGetErrorString(e));
     h->policy_filter_prepared = true;
-    return SSG_OK;
-}
-
-// One policy launch on the handle (pop_members 0: a single policy over n envs; else a population, n = the widest slice): the FILTER
-// kernels while a filter is bound, the launchers as they were otherwise.
-static hipError_t policy_launch(ssg_handle *h, const ssg_policy &p, bool greedy, int pop_members, int n, const double *obs, const float *uniform,
-                                uint64_t seed, int64_t step, int32_t *act, float *logp, float *value, float *x, hipStream_t st,
-                                const int32_t *slices)
-{
-    if (h->flt.struct_size) {
-        const ssg::ObsFilterArgs f = {h->flt.dev_state, h->flt.clip};
-        return ssg::launch_policy_filter(p, f, greedy, pop_members, n, h->cfg.env_id_base, obs, uniform, seed, step, act, logp, value, x, st, slices);
-    }
-    if (pop_members == 0)
-        return greedy ? ssg::launch_policy_act_greedy(p, n, obs, act, logp, value, x, st)
-                      : ssg::launch_policy_act(p, n, h->cfg.env_id_base, obs, uniform, seed, step, act, logp, value, x, st);
-    return greedy ? ssg::launch_policy_pop_greedy(p, pop_members, n, obs, act, logp, value, x, st, slices)
-                  : ssg::launch_policy_pop(p, pop_members, n, h->cfg.env_id_base, obs, uniform, seed, step, act, logp, value, x, st, slices);
-}
-
-// the rollout loops' merge of the current observation rows ahead of a step's policy launch: only with SSG_FILTER_UPDATE bound
-static hipError_t filter_step_update(ssg_handle *h, int n, const int32_t *slices, const double *obs, hipStream_t st)
-{
-    const ssg_obs_filter &f = h->flt;
-    if (!f.struct_size || !(f.flags & SSG_FILTER_UPDATE)) return hipSuccess;
-    return ssg::launch_filter_update(obs, f.obs_dim, f.n_members, n, slices, f.eps, f.dev_state, f.dev_workspace, st);
-}
-
-int ssg_policy_act(ssg_handle *h, const ssg_policy *pol, const double *dev_obs, const float *dev_uniform, uint64_t seed, int64_t step,
-                   int32_t *dev_actions, float *dev_logp, float *dev_value, float *dev_x, void *stream)
-{
-    int rc = check_ready(h, false);
-    if (rc != SSG_OK) return rc;
-    rc = check_policy(h, pol, "ssg_policy_act");
-    if (rc != SSG_OK) return rc;
-    if (!dev_obs || !dev_actions || !dev_logp || !dev_value)
-        return fail(h, SSG_ERR_BAD_ARG, "ssg_policy_act: NULL dev_obs, dev_actions, dev_logp or dev_value");
-    rc = check_filter_members(h, 1, "ssg_policy_act");
-    if (rc == SSG_OK) rc = prepare_policy(h);
-    if (rc == SSG_OK) rc = prepare_policy_filter(h);
-    if (rc != SSG_OK) return rc;
-    hipError_t e = policy_launch(h, *pol, false, 0, h->cfg.n_envs, dev_obs, dev_uniform, seed, step, dev_actions, dev_logp, dev_value, dev_x,
-                                 static_cast<hipStream_t>(stream), nullptr);
-    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("policy launch: ") + hipGetErrorString(e));
-    return SSG_OK;
-}
-
-int ssg_policy_act_greedy(ssg_handle *h, const ssg_policy *pol, const double *dev_obs, int32_t *dev_actions, float *dev_logp,
-                          float *dev_value, float *dev_x, void *stream)
-{
-    int rc = check_ready(h, false);
-    if (rc != SSG_OK) return rc;
-    rc = check_policy(h, pol, "ssg_policy_act_greedy");
-    if (rc != SSG_OK) return rc;
-    if (!dev_obs || !dev_actions || !dev_logp || !dev_value)
-        return fail(h, SSG_ERR_BAD_ARG, "ssg_policy_act_greedy: NULL dev_obs, dev_actions, dev_logp or dev_value");
-    rc = check_filter_members(h, 1, "ssg_policy_act_greedy");
-    if (rc == SSG_OK) rc = prepare_policy(h);
-    if (rc == SSG_OK) rc = prepare_policy_filter(h);
-    if (rc != SSG_OK) return rc;
-    hipError_t e = policy_launch(h, *pol, true, 0, h->cfg.n_envs, dev_obs, nullptr, 0, 0, dev_actions, dev_logp, dev_value, dev_x,
-                                 static_cast<hipStream_t>(stream), nullptr);
-    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("policy launch: ") + hipGetErrorString(e));
-    return SSG_OK;
-}
-
-int ssg_rollout_policy(ssg_handle *h, const ssg_policy *pol, int K, const float *dev_uniform_KN, uint64_t seed, int64_t step0,
-                       double *dev_obs, int32_t *dev_act_KN, float *dev_logp_KN, float *dev_value_KN, float *dev_x_KND,
-                       double *dev_reward_KN, uint8_t *dev_done_KN, uint8_t *dev_flags_KN, float *dev_last_value,
-                       int64_t step_stride_envs, void *stream)
-{
-    int rc = check_ready(h, true);
-    if (rc != SSG_OK) return rc;
-    rc = check_policy(h, pol, "ssg_rollout_policy");
-    if (rc != SSG_OK) return rc;
-    if (!dev_obs || !dev_act_KN || !dev_logp_KN || !dev_value_KN || !dev_reward_KN || !dev_done_KN)
-        return fail(h, SSG_ERR_BAD_ARG, "ssg_rollout_policy: NULL dev_obs, act, logp, value, reward or done buffer");
-    if (K < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_rollout_policy: K < 1");
-    if (step_stride_envs < (int64_t)h->cfg.n_envs) return fail(h, SSG_ERR_BAD_ARG, "ssg_rollout_policy: step_stride_envs < n_envs (steps would overlap)");
-    rc = check_filter_members(h, 1, "ssg_rollout_policy");
-    if (rc != SSG_OK) return rc;
-    // what the per-step ssg_step would refuse, refused before the first policy launch
-    if (h->cfg.map_ring > 0 && !h->ring_ready) return fail(h, SSG_ERR_NOT_BOUND, "map_ring mode: call ssg_refill_worlds first");
-    rc = refuse_capture(h, stream, "ssg_rollout_policy");
-    if (rc != SSG_OK) return rc;
-    rc = prepare(h);
-    if (rc == SSG_OK) rc = prepare_policy(h);
-    if (rc == SSG_OK) rc = prepare_policy_filter(h);
-    if (rc != SSG_OK) return rc;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t S = (size_t)step_stride_envs, D = (size_t)pol->obs_dim;
-    for (int k = 0; k < K; ++k) {
-        const size_t r = (size_t)k * S;
-        hipError_t e = filter_step_update(h, h->cfg.n_envs, nullptr, dev_obs, st); // (first merge the step's rows, then normalise them)
-        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("observation filter launch: ") + hipGetErrorString(e));
-        e = policy_launch(h, *pol, false, 0, h->cfg.n_envs, dev_obs, dev_uniform_KN ? dev_uniform_KN + r : nullptr, seed, step0 + k,
-                          dev_act_KN + r, dev_logp_KN + r, dev_value_KN + r, dev_x_KND ? dev_x_KND + r * D : nullptr, st, nullptr);
-        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("policy launch: ") + hipGetErrorString(e));
-        // (ssg_step as it stands: the same launches, frame shifts, dyn kernels and ring refills as a caller's own step)
-        rc = ssg_rollout_traj(h, dev_act_KN + r, 1, dev_obs, dev_reward_KN + r, dev_done_KN + r, dev_flags_KN ? dev_flags_KN + r : nullptr, 0,
-                              stream);
-        if (rc != SSG_OK) return rc;
-    }
-    if (dev_last_value) { // the value of the observation after the last step (PPO's bootstrap): a value-only forward (no filter merge)
-        hipError_t e = policy_launch(h, *pol, false, 0, h->cfg.n_envs, dev_obs, nullptr, seed, step0 + K, nullptr, nullptr, dev_last_value, nullptr,
-                                     st, nullptr);
-        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("policy launch: ") + hipGetErrorString(e));
-    }
     return SSG_OK;
 }
 
@@ -1584,44 +1467,177 @@ int ssg_ppo_update_ext(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hpara
                       static_cast<hipStream_t>(stream));
 }
 
-int ssg_pop_act(ssg_handle *h, const ssg_population *pop, const double *dev_obs, const float *dev_uniform, uint64_t seed, int64_t step,
-                int32_t *dev_actions, float *dev_logp, float *dev_value, float *dev_x, void *stream)
+// Who acts in a policy call: one policy on all the handle's envs, or a population on its slices.  The two functions that fill the record
+// are the only places that know the difference; what: the entry point's name, for its messages.
+struct PolicyCall {
+    ssg_policy pol; // (a population's: the shared shape over its parameter rows)
+    int members;    // 0: one policy
+    int n;          // the launch's width: the envs, or the widest slice
+    const int32_t *slices;
+    const char *what;
+};
+
+static int one_policy_call(ssg_handle *h, const ssg_policy *pol, const char *what, PolicyCall &c)
+{
+    const int rc = check_policy(h, pol, what);
+    if (rc == SSG_OK) c = {*pol, 0, h->cfg.n_envs, nullptr, what};
+    return rc;
+}
+
+static int population_call(ssg_handle *h, const ssg_population *pop, const char *what, PolicyCall &c)
 {
     int rc = pop_bound(h);
-    if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_act");
+    if (rc == SSG_OK) rc = check_population(h, pop, what);
+    if (rc == SSG_OK) c = {pop_policy(*pop), pop->n_members, pop_width(h, pop->n_members), pop_slices(h), what};
+    return rc;
+}
+
+// the call's member count must be the bound observation filter's, if one is bound
+static int check_filter_members(ssg_handle *h, const PolicyCall &c)
+{
+    const int members = c.members ? c.members : 1;
+    if (!h->flt.struct_size || h->flt.n_members == members) return SSG_OK;
+    char buf[200];
+    std::snprintf(buf, sizeof buf, ": the bound observation filter has %d members, this call %d (ssg_set_obs_filter)", h->flt.n_members, members);
+    return fail(h, SSG_ERR_BAD_ARG, std::string(c.what) + buf);
+}
+
+// One policy launch of the call, with the FILTER kernels while a filter is bound.  l: the launch's own, leading part of the record (obs,
+// uniform, seed, step, act, logp, value, x, greedy).
+static hipError_t policy_launch(ssg_handle *h, const PolicyCall &c, ssg::PolicyLaunch l, hipStream_t st)
+{
+    const ssg::ObsFilterArgs f = {h->flt.dev_state, h->flt.clip};
+    l.policy = &c.pol;
+    l.members = c.members;
+    l.n = c.n;
+    l.slices = c.slices;
+    l.env_base = h->cfg.env_id_base;
+    l.filter = h->flt.struct_size ? &f : nullptr;
+    return ssg::launch_policy(l, st);
+}
+
+static int policy_launch_failed(ssg_handle *h, const PolicyCall &c, hipError_t e)
+{
+    return fail(h, SSG_ERR_HIP, std::string(c.members ? "population policy launch: " : "policy launch: ") + hipGetErrorString(e));
+}
+
+// the rollout loop's merge of the current observation rows ahead of a step's policy launch: only with SSG_FILTER_UPDATE bound
+static hipError_t filter_step_update(ssg_handle *h, const PolicyCall &c, const double *obs, hipStream_t st)
+{
+    const ssg_obs_filter &f = h->flt;
+    if (!f.struct_size || !(f.flags & SSG_FILTER_UPDATE)) return hipSuccess;
+    return ssg::launch_filter_update(obs, f.obs_dim, f.n_members, c.n, c.slices, f.eps, f.dev_state, f.dev_workspace, st);
+}
+
+// What a loop of policy launches and steps asks last, once the host has judged the entry point's own arguments: the filter's member
+// count, the bank and the device, what the per-step ssg_step would refuse (before the first policy launch), the kernels' attributes.
+static int prepare_steps(ssg_handle *h, const PolicyCall &c, void *stream)
+{
+    int rc = check_filter_members(h, c);
+    if (rc == SSG_OK) rc = check_ready(h, true);
     if (rc != SSG_OK) return rc;
-    if (!dev_obs || !dev_actions || !dev_logp || !dev_value)
-        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_act: NULL dev_obs, dev_actions, dev_logp or dev_value");
-    rc = check_filter_members(h, pop->n_members, "ssg_pop_act");
+    if (h->cfg.map_ring > 0 && !h->ring_ready) return fail(h, SSG_ERR_NOT_BOUND, "map_ring mode: call ssg_refill_worlds first");
+    rc = refuse_capture(h, stream, c.what);
+    if (rc == SSG_OK) rc = prepare(h);
+    if (rc == SSG_OK) rc = prepare_policy(h);
+    if (rc == SSG_OK) rc = prepare_policy_filter(h);
+    return rc;
+}
+
+// The body of the four act entry points; l as for policy_launch.  (The single-policy entries have asked check_ready already, ahead of
+// their record: the order of their refusals.)
+static int policy_act(ssg_handle *h, const PolicyCall &c, const ssg::PolicyLaunch &l, void *stream)
+{
+    if (!l.obs || !l.act || !l.logp || !l.value)
+        return fail(h, SSG_ERR_BAD_ARG, std::string(c.what) + ": NULL dev_obs, dev_actions, dev_logp or dev_value");
+    int rc = check_filter_members(h, c);
     if (rc == SSG_OK) rc = check_ready(h, false);
     if (rc == SSG_OK) rc = prepare_policy(h);
     if (rc == SSG_OK) rc = prepare_policy_filter(h);
     if (rc != SSG_OK) return rc;
-    const int P = pop->n_members;
-    hipError_t e = policy_launch(h, pop_policy(*pop), false, P, pop_width(h, P), dev_obs, dev_uniform, seed, step, dev_actions, dev_logp,
-                                 dev_value, dev_x, static_cast<hipStream_t>(stream), pop_slices(h));
-    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population policy launch: ") + hipGetErrorString(e));
-    return SSG_OK;
+    const hipError_t e = policy_launch(h, c, l, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? SSG_OK : policy_launch_failed(h, c, e);
+}
+
+int ssg_policy_act(ssg_handle *h, const ssg_policy *pol, const double *dev_obs, const float *dev_uniform, uint64_t seed, int64_t step,
+                   int32_t *dev_actions, float *dev_logp, float *dev_value, float *dev_x, void *stream)
+{
+    PolicyCall c;
+    int rc = check_ready(h, false);
+    if (rc == SSG_OK) rc = one_policy_call(h, pol, "ssg_policy_act", c);
+    return rc != SSG_OK ? rc : policy_act(h, c, {dev_obs, dev_uniform, seed, step, dev_actions, dev_logp, dev_value, dev_x, false}, stream);
+}
+
+int ssg_policy_act_greedy(ssg_handle *h, const ssg_policy *pol, const double *dev_obs, int32_t *dev_actions, float *dev_logp,
+                          float *dev_value, float *dev_x, void *stream)
+{
+    PolicyCall c;
+    int rc = check_ready(h, false);
+    if (rc == SSG_OK) rc = one_policy_call(h, pol, "ssg_policy_act_greedy", c);
+    return rc != SSG_OK ? rc : policy_act(h, c, {dev_obs, nullptr, 0, 0, dev_actions, dev_logp, dev_value, dev_x, true}, stream);
+}
+
+int ssg_pop_act(ssg_handle *h, const ssg_population *pop, const double *dev_obs, const float *dev_uniform, uint64_t seed, int64_t step,
+                int32_t *dev_actions, float *dev_logp, float *dev_value, float *dev_x, void *stream)
+{
+    PolicyCall c;
+    const int rc = population_call(h, pop, "ssg_pop_act", c);
+    return rc != SSG_OK ? rc : policy_act(h, c, {dev_obs, dev_uniform, seed, step, dev_actions, dev_logp, dev_value, dev_x, false}, stream);
 }
 
 int ssg_pop_act_greedy(ssg_handle *h, const ssg_population *pop, const double *dev_obs, int32_t *dev_actions, float *dev_logp,
                        float *dev_value, float *dev_x, void *stream)
 {
-    int rc = pop_bound(h);
-    if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_act_greedy");
+    PolicyCall c;
+    const int rc = population_call(h, pop, "ssg_pop_act_greedy", c);
+    return rc != SSG_OK ? rc : policy_act(h, c, {dev_obs, nullptr, 0, 0, dev_actions, dev_logp, dev_value, dev_x, true}, stream);
+}
+
+// The body of both rollout entry points: K times the filter's merge (if it updates), ONE policy launch for everyone and the step, then
+// the bootstrap value.  (ssg_rollout_policy has asked check_ready already, ahead of its record: the order of its refusals.)
+static int policy_rollout(ssg_handle *h, const PolicyCall &c, int K, const float *dev_uniform_KN, uint64_t seed, int64_t step0, double *dev_obs,
+                          int32_t *dev_act_KN, float *dev_logp_KN, float *dev_value_KN, float *dev_x_KND, double *dev_reward_KN,
+                          uint8_t *dev_done_KN, uint8_t *dev_flags_KN, float *dev_last_value, int64_t step_stride_envs, void *stream)
+{
+    const std::string w(c.what);
+    if (!dev_obs || !dev_act_KN || !dev_logp_KN || !dev_value_KN || !dev_reward_KN || !dev_done_KN)
+        return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_obs, act, logp, value, reward or done buffer");
+    if (K < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": K < 1");
+    if (step_stride_envs < (int64_t)h->cfg.n_envs) return fail(h, SSG_ERR_BAD_ARG, w + ": step_stride_envs < n_envs (steps would overlap)");
+    int rc = prepare_steps(h, c, stream);
     if (rc != SSG_OK) return rc;
-    if (!dev_obs || !dev_actions || !dev_logp || !dev_value)
-        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_act_greedy: NULL dev_obs, dev_actions, dev_logp or dev_value");
-    rc = check_filter_members(h, pop->n_members, "ssg_pop_act_greedy");
-    if (rc == SSG_OK) rc = check_ready(h, false);
-    if (rc == SSG_OK) rc = prepare_policy(h);
-    if (rc == SSG_OK) rc = prepare_policy_filter(h);
-    if (rc != SSG_OK) return rc;
-    const int P = pop->n_members;
-    hipError_t e = policy_launch(h, pop_policy(*pop), true, P, pop_width(h, P), dev_obs, nullptr, 0, 0, dev_actions, dev_logp, dev_value, dev_x,
-                                 static_cast<hipStream_t>(stream), pop_slices(h));
-    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population policy launch: ") + hipGetErrorString(e));
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t S = (size_t)step_stride_envs, D = (size_t)c.pol.obs_dim;
+    for (int k = 0; k < K; ++k) {
+        const size_t r = (size_t)k * S;
+        hipError_t e = filter_step_update(h, c, dev_obs, st); // (first merge the step's rows, a member's into its own state rows, then normalise them)
+        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("observation filter launch: ") + hipGetErrorString(e));
+        e = policy_launch(h, c, {dev_obs, dev_uniform_KN ? dev_uniform_KN + r : nullptr, seed, step0 + k, dev_act_KN + r, dev_logp_KN + r,
+                                 dev_value_KN + r, dev_x_KND ? dev_x_KND + r * D : nullptr, false}, st);
+        if (e != hipSuccess) return policy_launch_failed(h, c, e);
+        // (ssg_step as it stands: the same launches, frame shifts, dyn kernels and ring refills as a caller's own step)
+        rc = ssg_rollout_traj(h, dev_act_KN + r, 1, dev_obs, dev_reward_KN + r, dev_done_KN + r, dev_flags_KN ? dev_flags_KN + r : nullptr, 0,
+                              stream);
+        if (rc != SSG_OK) return rc;
+    }
+    if (dev_last_value) { // the value of the observation after the last step (PPO's bootstrap): a value-only forward (no filter merge)
+        const hipError_t e = policy_launch(h, c, {dev_obs, nullptr, seed, step0 + K, nullptr, nullptr, dev_last_value, nullptr, false}, st);
+        if (e != hipSuccess) return policy_launch_failed(h, c, e);
+    }
     return SSG_OK;
+}
+
+int ssg_rollout_policy(ssg_handle *h, const ssg_policy *pol, int K, const float *dev_uniform_KN, uint64_t seed, int64_t step0,
+                       double *dev_obs, int32_t *dev_act_KN, float *dev_logp_KN, float *dev_value_KN, float *dev_x_KND,
+                       double *dev_reward_KN, uint8_t *dev_done_KN, uint8_t *dev_flags_KN, float *dev_last_value,
+                       int64_t step_stride_envs, void *stream)
+{
+    PolicyCall c;
+    int rc = check_ready(h, true);
+    if (rc == SSG_OK) rc = one_policy_call(h, pol, "ssg_rollout_policy", c);
+    if (rc != SSG_OK) return rc;
+    return policy_rollout(h, c, K, dev_uniform_KN, seed, step0, dev_obs, dev_act_KN, dev_logp_KN, dev_value_KN, dev_x_KND, dev_reward_KN,
+                          dev_done_KN, dev_flags_KN, dev_last_value, step_stride_envs, stream);
 }
 
 int ssg_pop_rollout(ssg_handle *h, const ssg_population *pop, int K, const float *dev_uniform_KN, uint64_t seed, int64_t step0,
@@ -1629,45 +1645,11 @@ int ssg_pop_rollout(ssg_handle *h, const ssg_population *pop, int K, const float
                     double *dev_reward_KN, uint8_t *dev_done_KN, uint8_t *dev_flags_KN, float *dev_last_value, int64_t step_stride_envs,
                     void *stream)
 {
-    int rc = pop_bound(h);
-    if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_rollout");
+    PolicyCall c;
+    const int rc = population_call(h, pop, "ssg_pop_rollout", c);
     if (rc != SSG_OK) return rc;
-    if (!dev_obs || !dev_act_KN || !dev_logp_KN || !dev_value_KN || !dev_reward_KN || !dev_done_KN)
-        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_rollout: NULL dev_obs, act, logp, value, reward or done buffer");
-    if (K < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_rollout: K < 1");
-    if (step_stride_envs < (int64_t)h->cfg.n_envs) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_rollout: step_stride_envs < n_envs (steps would overlap)");
-    rc = check_filter_members(h, pop->n_members, "ssg_pop_rollout");
-    if (rc != SSG_OK) return rc;
-    rc = check_ready(h, true);
-    if (rc != SSG_OK) return rc;
-    if (h->cfg.map_ring > 0 && !h->ring_ready) return fail(h, SSG_ERR_NOT_BOUND, "map_ring mode: call ssg_refill_worlds first");
-    rc = refuse_capture(h, stream, "ssg_pop_rollout");
-    if (rc != SSG_OK) return rc;
-    rc = prepare(h);
-    if (rc == SSG_OK) rc = prepare_policy(h);
-    if (rc == SSG_OK) rc = prepare_policy_filter(h);
-    if (rc != SSG_OK) return rc;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    const ssg_policy pol = pop_policy(*pop);
-    const int P = pop->n_members, n = pop_width(h, P);
-    const int32_t *slices = pop_slices(h);
-    const size_t S = (size_t)step_stride_envs, D = (size_t)pol.obs_dim;
-    for (int k = 0; k < K; ++k) { // ssg_rollout_policy's sequence: one policy launch for the whole population, then the step
-        const size_t r = (size_t)k * S;
-        hipError_t e = filter_step_update(h, n, slices, dev_obs, st); // (every member's rows into its own state rows)
-        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("observation filter launch: ") + hipGetErrorString(e));
-        e = policy_launch(h, pol, false, P, n, dev_obs, dev_uniform_KN ? dev_uniform_KN + r : nullptr, seed, step0 + k, dev_act_KN + r,
-                          dev_logp_KN + r, dev_value_KN + r, dev_x_KND ? dev_x_KND + r * D : nullptr, st, slices);
-        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population policy launch: ") + hipGetErrorString(e));
-        rc = ssg_rollout_traj(h, dev_act_KN + r, 1, dev_obs, dev_reward_KN + r, dev_done_KN + r, dev_flags_KN ? dev_flags_KN + r : nullptr, 0,
-                              stream);
-        if (rc != SSG_OK) return rc;
-    }
-    if (dev_last_value) {
-        hipError_t e = policy_launch(h, pol, false, P, n, dev_obs, nullptr, seed, step0 + K, nullptr, nullptr, dev_last_value, nullptr, st, slices);
-        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population policy launch: ") + hipGetErrorString(e));
-    }
-    return SSG_OK;
+    return policy_rollout(h, c, K, dev_uniform_KN, seed, step0, dev_obs, dev_act_KN, dev_logp_KN, dev_value_KN, dev_x_KND, dev_reward_KN,
+                          dev_done_KN, dev_flags_KN, dev_last_value, step_stride_envs, stream);
 }
 
 int ssg_pop_pack_hparams(int n_members, const ssg_ppo_hparams *hparams, int64_t step0, int n_steps, float *out, size_t out_floats)
@@ -2113,57 +2095,44 @@ static int check_eval(ssg_handle *h, const ssg_eval *ev, const char *what)
     return SSG_OK;
 }
 
-// the loop of both entry points: pop == nullptr runs one policy
-static int run_evaluate(ssg_handle *h, const ssg_policy &pol, const ssg_population *pop, const ssg_eval &ev, const char *what, void *stream)
+// both entry points behind their record
+static int run_evaluate(ssg_handle *h, const PolicyCall &c, const ssg_eval *evp, void *stream)
 {
-    int rc = check_ready(h, true);
+    int rc = check_eval(h, evp, c.what);
+    if (rc == SSG_OK) rc = prepare_steps(h, c, stream);
     if (rc != SSG_OK) return rc;
-    // what the per-step ssg_step would refuse, refused before the first policy launch
-    if (h->cfg.map_ring > 0 && !h->ring_ready) return fail(h, SSG_ERR_NOT_BOUND, "map_ring mode: call ssg_refill_worlds first");
-    rc = refuse_capture(h, stream, what);
-    if (rc != SSG_OK) return rc;
-    rc = prepare(h);
-    if (rc == SSG_OK) rc = prepare_policy(h);
-    if (rc == SSG_OK) rc = prepare_policy_filter(h);
-    if (rc != SSG_OK) return rc;
+    const ssg_eval &ev = *evp;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const bool greedy = (ev.flags & SSG_EVAL_GREEDY) != 0;
-    const int N = h->cfg.n_envs, P = pop ? pop->n_members : 1, n = pop ? pop_width(h, P) : N;
-    const int32_t *slices = pop ? pop_slices(h) : nullptr;
+    const int N = h->cfg.n_envs;
     for (int k = 0; k < ev.n_steps; ++k) {
         const float *u = ev.dev_uniform_TN ? ev.dev_uniform_TN + (size_t)k * (size_t)N : nullptr;
         // (a bound observation filter is applied and never updated: evaluation is frozen)
-        hipError_t e = policy_launch(h, pol, greedy, pop ? P : 0, n, ev.dev_obs, u, ev.seed, ev.step0 + k, ev.dev_act, ev.dev_logp, ev.dev_value,
-                                     nullptr, st, slices);
-        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string(what) + ": policy launch: " + hipGetErrorString(e));
-        // (ssg_step as it stands, the call ssg_rollout_policy makes)
+        hipError_t e = policy_launch(h, c, {ev.dev_obs, u, ev.seed, ev.step0 + k, ev.dev_act, ev.dev_logp, ev.dev_value, nullptr, greedy}, st);
+        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string(c.what) + ": policy launch: " + hipGetErrorString(e));
+        // (ssg_step as it stands, the call the rollouts make)
         rc = ssg_rollout_traj(h, ev.dev_act, 1, ev.dev_obs, ev.dev_reward, ev.dev_done, ev.dev_flags, 0, stream);
         if (rc != SSG_OK) return rc;
         e = ssg::launch_eval_account(N, ev.episodes_per_env, ev.dev_reward, ev.dev_done, ev.dev_flags, ev.dev_carry_return, ev.dev_carry,
                                      ev.dev_env_stats, st);
-        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string(what) + ": accounting launch: " + hipGetErrorString(e));
+        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string(c.what) + ": accounting launch: " + hipGetErrorString(e));
     }
     return SSG_OK;
 }
 
 int ssg_evaluate(ssg_handle *h, const ssg_policy *pol, const ssg_eval *ev, void *stream)
 {
+    PolicyCall c;
     int rc = pop_bound(h);
-    if (rc == SSG_OK) rc = check_policy(h, pol, "ssg_evaluate");
-    if (rc == SSG_OK) rc = check_eval(h, ev, "ssg_evaluate");
-    if (rc == SSG_OK) rc = check_filter_members(h, 1, "ssg_evaluate");
-    if (rc != SSG_OK) return rc;
-    return run_evaluate(h, *pol, nullptr, *ev, "ssg_evaluate", stream);
+    if (rc == SSG_OK) rc = one_policy_call(h, pol, "ssg_evaluate", c);
+    return rc == SSG_OK ? run_evaluate(h, c, ev, stream) : rc;
 }
 
 int ssg_pop_evaluate(ssg_handle *h, const ssg_population *pop, const ssg_eval *ev, void *stream)
 {
-    int rc = pop_bound(h);
-    if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_evaluate");
-    if (rc == SSG_OK) rc = check_eval(h, ev, "ssg_pop_evaluate");
-    if (rc == SSG_OK) rc = check_filter_members(h, pop->n_members, "ssg_pop_evaluate");
-    if (rc != SSG_OK) return rc;
-    return run_evaluate(h, pop_policy(*pop), pop, *ev, "ssg_pop_evaluate", stream);
+    PolicyCall c;
+    const int rc = population_call(h, pop, "ssg_pop_evaluate", c);
+    return rc == SSG_OK ? run_evaluate(h, c, ev, stream) : rc;
 }
 
 int ssg_obs_filter_workspace_nbytes(int n_envs, int obs_dim, int n_members, size_t *nbytes)

@@ -201,11 +201,33 @@ hipError_t launch_refill_worlds(const DevCfg &c, uint64_t seed, double width_fra
                                 double *bank, double *raw, hipStream_t stream);
 hipError_t launch_fill_actions(uint64_t seed, uint64_t step0, int K, long long env_base, int n, int32_t *out,
                                hipStream_t stream);
-// the policy kernel (shipsim_policy.hip): ssg_policy_act on n envs; act / logp NULL = value only (no sampling), x NULL = no x rows
+// The policy kernel (shipsim_policy.hip).  One acting launch: one policy over n envs (members 0), or a population — p is then the shared
+// shape with dev_params = f32 [members][L], and member m acts on the n = N / members envs [m*n, (m+1)*n) or, with slices (see below),
+// on its slice, n being the largest.  act / logp NULL = value only (no sampling), x NULL = no x rows.  greedy: the arg-max action and its
+// logp; act, logp and value are all written and uniform, seed, step and env_base are not read.  filter (nullable): the kernels of
+// shipsim_policy_filter.o, x = (float)clamp((obs - mean) / denom, +-clip) from member m's state rows in place of obs / scale.
+struct ObsFilterArgs { const double *state; double clip; };
+struct PolicyLaunch {
+    const double *obs;
+    const float *uniform; // nullable: then Philox draws under (seed, step)
+    uint64_t seed;
+    int64_t step;
+    int32_t *act;
+    float *logp, *value, *x;
+    bool greedy;
+    const ssg_policy *policy;
+    int members, n;
+    const int32_t *slices; // nullable
+    long long env_base;    // the global id of env 0 (the uniforms' counter)
+    const ObsFilterArgs *filter;
+};
 size_t policy_lds_bytes(const ssg_policy &p, bool both_towers); // (both_towers: a separate-value launch that also samples)
 hipError_t prepare_policy(); // (the dynamic-LDS limit of the kernels: up to 90 KB per workgroup at obs_dim 176, hidden 128; 124 KB when a separate-value launch keeps its third buffer)
-hipError_t launch_policy_act(const ssg_policy &p, int n, long long env_base, const double *obs, const float *uniform, uint64_t seed,
-                             int64_t step, int32_t *act, float *logp, float *value, float *x, hipStream_t stream);
+hipError_t launch_policy(const PolicyLaunch &l, hipStream_t stream);
+// the same with l.filter set, in an object of its own (-DSSG_POLICY_FILTER_TU) so that the unfiltered instantiations are compiled as before;
+// launch_policy hands such a record on
+hipError_t prepare_policy_filter();
+hipError_t launch_policy_filter(const PolicyLaunch &l, hipStream_t stream);
 // GAE and the PPO update (shipsim_ppo.hip).  Workspace: f32[4] advantage statistics at kPpoStatsOff (mean, std + adv_eps, its
 // inverse), then from kPpoSlotsOff the gradient kernel's per-workgroup slots [grid][P + 4] — or, during ssg_ppo_gae, its f64 partials.
 constexpr size_t kPpoStatsOff = 0, kPpoSlotsOff = 256;
@@ -235,9 +257,6 @@ enum { SR_OFF = 0 /* int64: entries [0], [1] */, SR_M = 2, SR_G, SR_FIRST, SR_AC
 static_assert(SSG_POP_MAX_MEMBERS * 16 <= kPopSlotsOff, "the members' advantage statistics fit in front of the slots");
 // slices (nullable, here and below): the device table of ssg_pop_set_slices, SSG_POP_SLICE_ROW int32 per member = {o_m, n_m,
 // ppo_gae_blocks(n_m), 0}; member m then owns envs [o_m, o_m + n_m) and n is the LARGEST slice (the launch's width)
-hipError_t launch_policy_pop(const ssg_policy &p, int members, int n, long long env_base, const double *obs, const float *uniform,
-                             uint64_t seed, int64_t step, int32_t *act, float *logp, float *value, float *x, hipStream_t stream,
-                             const int32_t *slices = nullptr);
 void pop_pack(int members, const ssg_ppo_hparams *hp, int64_t step0, int n_steps, float *out); // host only
 void pop_pack_steps(int members, const ssg_ppo_hparams *hp, const int64_t *step0, int n_steps, float *out); // (a starting step per member)
 hipError_t launch_pop_gae(int members, int K, int N, const float *table, const double *rew, const uint8_t *done, const float *val,
@@ -321,10 +340,6 @@ hipError_t launch_policy_dist(const ssg_policy &p, int members, int n, long long
                               const int32_t *slices = nullptr);
 hipError_t launch_pop_episode_stats(int members, int K, int N, const double *rew, const uint8_t *done, double *carry_ret,
                                     int32_t *carry_len, int64_t *out, hipStream_t stream, const int32_t *slices = nullptr, int n_max = 0);
-// the greedy mode of the policy kernel (shipsim_policy.hip): the arg-max action and its logp; no uniform, seed or step
-hipError_t launch_policy_act_greedy(const ssg_policy &p, int n, const double *obs, int32_t *act, float *logp, float *value, float *x, hipStream_t stream);
-hipError_t launch_policy_pop_greedy(const ssg_policy &p, int members, int n, const double *obs, int32_t *act, float *logp, float *value, float *x,
-                                    hipStream_t stream, const int32_t *slices = nullptr);
 // episode accounting of an evaluation run (shipsim_eval.hip): one step's rows into the per-env carries and stats rows (an env counts its
 // first E episodes), and the per-member column sums of the stats rows
 constexpr int kEvalCols = SSG_EVAL_STATS;
@@ -339,14 +354,6 @@ size_t filter_workspace_bytes(int n_envs, int obs_dim, int members);
 // the two launches: member m's n rows [m*n, (m+1)*n) of obs, or its slice (then n: the largest slice), into its SSG_FILTER_ROWS state rows
 hipError_t launch_filter_update(const double *obs, int D, int members, int n, const int32_t *slices, double eps, double *state, void *ws,
                                 hipStream_t stream);
-// The policy kernels with a bound filter (shipsim_policy.hip built with -DSSG_POLICY_FILTER_TU, an object of its own so that the unfiltered
-// instantiations are compiled as before): x = (float)clamp((obs - mean) / denom, +-clip) from member m's state rows in place of
-// obs / scale; everything else, and every argument, as the launchers above (greedy: no uniform, seed or step; members 0: one policy).
-struct ObsFilterArgs { const double *state; double clip; };
-hipError_t prepare_policy_filter();
-hipError_t launch_policy_filter(const ssg_policy &p, const ObsFilterArgs &f, bool greedy, int members, int n, long long env_base, const double *obs,
-                                const float *uniform, uint64_t seed, int64_t step, int32_t *act, float *logp, float *value, float *x,
-                                hipStream_t stream, const int32_t *slices);
 
 #ifdef __HIPCC__
 // One round of Philox4x32-10 (counter ctr, key key).  The counter-based streams of the library — fill_actions_kernel's actions

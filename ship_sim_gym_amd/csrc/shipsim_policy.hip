@@ -508,55 +508,63 @@ __global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1
 
 static bool is_split(const ssg_policy &p) { return (p.activation & SSG_POLICY_SEPARATE_VALUE) != 0; }
 
-#ifdef SSG_POLICY_FILTER_TU
-// the FILTER instantiations, indexed [population][split][greedy] and [split][greedy]
-typedef void (*FilterKernel)(const ssg_policy, const float *, const double *, int, long long, const double *, const float *, uint64_t, int64_t,
-                             int32_t *, float *, float *, float *, int, double);
-typedef void (*FilterSlicedKernel)(const ssg_policy, const float *, const double *, const int32_t *, long long, const double *, const float *,
-                                   uint64_t, int64_t, int32_t *, float *, float *, float *, int, double);
-static FilterKernel filter_kernel(bool pop, bool split, bool greedy)
+// the dynamic-LDS limit of `count` kernels of a table
+template <class Kernel>
+static hipError_t raise_lds_limit(const Kernel *k, int count)
 {
-    static const FilterKernel k[2][2][2] = {
-        {{policy_act_filter_kernel<false, false, false>, policy_act_filter_kernel<false, false, true>},
-         {policy_act_filter_kernel<false, true, false>, policy_act_filter_kernel<false, true, true>}},
-        {{policy_act_filter_kernel<true, false, false>, policy_act_filter_kernel<true, false, true>},
-         {policy_act_filter_kernel<true, true, false>, policy_act_filter_kernel<true, true, true>}}};
-    return k[pop][split][greedy];
-}
-static FilterSlicedKernel filter_sliced_kernel(bool split, bool greedy)
-{
-    static const FilterSlicedKernel k[2][2] = {{policy_act_sliced_filter_kernel<false, false>, policy_act_sliced_filter_kernel<false, true>},
-                                               {policy_act_sliced_filter_kernel<true, false>, policy_act_sliced_filter_kernel<true, true>}};
-    return k[split][greedy];
-}
-
-hipError_t prepare_policy_filter()
-{
-    for (int i = 0; i < 12; ++i) {
-        const void *k = i < 8 ? reinterpret_cast<const void *>(filter_kernel((i & 4) != 0, (i & 2) != 0, (i & 1) != 0))
-                              : reinterpret_cast<const void *>(filter_sliced_kernel((i & 2) != 0, (i & 1) != 0));
-        hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    for (int i = 0; i < count; ++i) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k[i]), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
-hipError_t launch_policy_filter(const ssg_policy &p, const ObsFilterArgs &f, bool greedy, int members, int n, long long env_base, const double *obs,
-                                const float *uniform, uint64_t seed, int64_t step, int32_t *act, float *logp, float *value, float *x,
-                                hipStream_t stream, const int32_t *slices)
+// One acting launch with an object's kernel for equal slices (or one policy) and its kernel for a slices table.  third: the kernels'
+// third argument (the scale row, or the filter's state rows); extra: what they take after plen (the filter's clip).  A greedy launch
+// writes act, logp and value (the callers refuse a NULL one) and reads no uniform, seed, step or env id.
+template <class Kernel, class SlicedKernel, class... Extra>
+static hipError_t launch_act(Kernel kernel, SlicedKernel sliced, const PolicyLaunch &l, const double *third, hipStream_t stream, Extra... extra)
 {
-    const unsigned grid = (unsigned)((n + kPolWave - 1) / kPolWave); // (n: the largest slice)
-    const size_t lds = policy_lds_bytes(p, act != nullptr);
-    const bool pop = members > 0;
-    if (greedy) { uniform = nullptr; seed = 0; step = 0; env_base = 0; }
-    if (slices)
-        hipLaunchKernelGGL(filter_sliced_kernel(is_split(p), greedy), dim3(grid, (unsigned)members), dim3(kPolWave), lds, stream, p, p.dev_params,
-                           f.state, slices, env_base, obs, uniform, seed, step, act, logp, value, x, ppo_packed_len(p), f.clip);
+    const ssg_policy &p = *l.policy;
+    const bool pop = l.members > 0;
+    const dim3 grid((unsigned)((l.n + kPolWave - 1) / kPolWave), pop ? (unsigned)l.members : 1u); // (n: with slices, the largest)
+    const size_t lds = policy_lds_bytes(p, l.greedy || l.act != nullptr);
+    const int plen = pop ? ppo_packed_len(p) : 0;
+    const float *uniform = l.greedy ? nullptr : l.uniform;
+    const uint64_t seed = l.greedy ? 0 : l.seed;
+    const int64_t step = l.greedy ? 0 : l.step;
+    const long long env_base = l.greedy ? 0 : l.env_base;
+    if (l.slices)
+        hipLaunchKernelGGL(sliced, grid, dim3(kPolWave), lds, stream, p, p.dev_params, third, l.slices, env_base, l.obs, uniform, seed, step,
+                           l.act, l.logp, l.value, l.x, plen, extra...);
     else
-        hipLaunchKernelGGL(filter_kernel(pop, is_split(p), greedy), dim3(grid, pop ? (unsigned)members : 1u), dim3(kPolWave), lds, stream, p,
-                           p.dev_params, f.state, n, env_base, obs, uniform, seed, step, act, logp, value, x, pop ? ppo_packed_len(p) : 0,
-                           f.clip);
+        hipLaunchKernelGGL(kernel, grid, dim3(kPolWave), lds, stream, p, p.dev_params, third, l.n, env_base, l.obs, uniform, seed, step, l.act,
+                           l.logp, l.value, l.x, plen, extra...);
     return hipGetLastError();
+}
+
+#ifdef SSG_POLICY_FILTER_TU
+// the FILTER instantiations, indexed [population][split][greedy] and [split][greedy]
+typedef decltype(&policy_act_filter_kernel<false, false, false>) FilterKernel;
+typedef decltype(&policy_act_sliced_filter_kernel<false, false>) FilterSlicedKernel;
+static const FilterKernel kFilter[2][2][2] = {
+    {{policy_act_filter_kernel<false, false, false>, policy_act_filter_kernel<false, false, true>},
+     {policy_act_filter_kernel<false, true, false>, policy_act_filter_kernel<false, true, true>}},
+    {{policy_act_filter_kernel<true, false, false>, policy_act_filter_kernel<true, false, true>},
+     {policy_act_filter_kernel<true, true, false>, policy_act_filter_kernel<true, true, true>}}};
+static const FilterSlicedKernel kFilterSliced[2][2] = {{policy_act_sliced_filter_kernel<false, false>, policy_act_sliced_filter_kernel<false, true>},
+                                                       {policy_act_sliced_filter_kernel<true, false>, policy_act_sliced_filter_kernel<true, true>}};
+
+hipError_t prepare_policy_filter()
+{
+    const hipError_t e = raise_lds_limit(&kFilter[0][0][0], 8);
+    return e != hipSuccess ? e : raise_lds_limit(&kFilterSliced[0][0], 4);
+}
+
+hipError_t launch_policy_filter(const PolicyLaunch &l, hipStream_t stream)
+{
+    const bool split = is_split(*l.policy);
+    return launch_act(kFilter[l.members > 0][split][l.greedy], kFilterSliced[split][l.greedy], l, l.filter->state, stream, l.filter->clip);
 }
 #else
 
@@ -568,76 +576,37 @@ size_t policy_lds_bytes(const ssg_policy &p, bool both_towers)
     return (16 * R4 + (R4 + (size_t)p.hidden + third) * kPolStride) * sizeof(float);
 }
 
+// The instantiations without a filter.  A kernel's place in the object file follows its first mention here, so the tables are in the
+// order, and indexed in the order, that keeps the object's device code what it has been: on a slices table [greedy][split], on equal
+// slices or for one policy [split][population], sampling ahead of policy_dist's pair and greedy behind it.
+typedef decltype(&policy_act_kernel<false, false, false>) ActKernel;
+typedef decltype(&policy_act_sliced_kernel<false, false>) ActSlicedKernel;
+typedef decltype(&policy_dist_kernel<false>) DistKernel;
+typedef decltype(&policy_dist_sliced_kernel<false>) DistSlicedKernel;
+static const ActSlicedKernel kActSliced[2][2] = {{policy_act_sliced_kernel<false, false>, policy_act_sliced_kernel<true, false>},
+                                                 {policy_act_sliced_kernel<false, true>, policy_act_sliced_kernel<true, true>}};
+static const DistSlicedKernel kDistSliced[2] = {policy_dist_sliced_kernel<false>, policy_dist_sliced_kernel<true>};
+static const ActKernel kAct[2][2] = {{policy_act_kernel<false, false, false>, policy_act_kernel<true, false, false>},
+                                     {policy_act_kernel<false, true, false>, policy_act_kernel<true, true, false>}};
+static const DistKernel kDist[2] = {policy_dist_kernel<false>, policy_dist_kernel<true>};
+static const ActKernel kActGreedy[2][2] = {{policy_act_kernel<false, false, true>, policy_act_kernel<true, false, true>},
+                                           {policy_act_kernel<false, true, true>, policy_act_kernel<true, true, true>}};
+
 hipError_t prepare_policy()
 {
-    const void *kernels[16] = {reinterpret_cast<const void *>(policy_act_sliced_kernel<false, false>), reinterpret_cast<const void *>(policy_act_sliced_kernel<true, false>),
-                               reinterpret_cast<const void *>(policy_act_sliced_kernel<false, true>), reinterpret_cast<const void *>(policy_act_sliced_kernel<true, true>),
-                               reinterpret_cast<const void *>(policy_dist_sliced_kernel<false>), reinterpret_cast<const void *>(policy_dist_sliced_kernel<true>),
-                               reinterpret_cast<const void *>(policy_act_kernel<false, false>), reinterpret_cast<const void *>(policy_act_kernel<true, false>),
-                               reinterpret_cast<const void *>(policy_act_kernel<false, true>), reinterpret_cast<const void *>(policy_act_kernel<true, true>),
-                               reinterpret_cast<const void *>(policy_dist_kernel<false>), reinterpret_cast<const void *>(policy_dist_kernel<true>),
-                               reinterpret_cast<const void *>(policy_act_kernel<false, false, true>), reinterpret_cast<const void *>(policy_act_kernel<true, false, true>),
-                               reinterpret_cast<const void *>(policy_act_kernel<false, true, true>), reinterpret_cast<const void *>(policy_act_kernel<true, true, true>)};
-    for (const void *k : kernels) {
-        hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    hipError_t e = raise_lds_limit(&kActSliced[0][0], 4);
+    if (e == hipSuccess) e = raise_lds_limit(kDistSliced, 2);
+    if (e == hipSuccess) e = raise_lds_limit(&kAct[0][0], 4);
+    if (e == hipSuccess) e = raise_lds_limit(kDist, 2);
+    if (e == hipSuccess) e = raise_lds_limit(&kActGreedy[0][0], 4);
+    return e;
 }
 
-hipError_t launch_policy_act(const ssg_policy &p, int n, long long env_base, const double *obs, const float *uniform, uint64_t seed,
-                             int64_t step, int32_t *act, float *logp, float *value, float *x, hipStream_t stream)
+hipError_t launch_policy(const PolicyLaunch &l, hipStream_t stream)
 {
-    const unsigned grid = (unsigned)((n + kPolWave - 1) / kPolWave);
-    const auto kernel = is_split(p) ? policy_act_kernel<false, true> : policy_act_kernel<false, false>;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kPolWave),
-                       policy_lds_bytes(p, act != nullptr), stream, p, p.dev_params, p.dev_obs_scale, n, env_base, obs, uniform, seed, step, act,
-                       logp, value, x, 0);
-    return hipGetLastError();
-}
-
-hipError_t launch_policy_pop(const ssg_policy &p, int members, int n, long long env_base, const double *obs, const float *uniform,
-                             uint64_t seed, int64_t step, int32_t *act, float *logp, float *value, float *x, hipStream_t stream,
-                             const int32_t *slices)
-{
-    const unsigned grid = (unsigned)((n + kPolWave - 1) / kPolWave);
-    if (slices) { // (n: the largest slice)
-        const auto sliced = is_split(p) ? policy_act_sliced_kernel<true, false> : policy_act_sliced_kernel<false, false>;
-        hipLaunchKernelGGL(sliced, dim3(grid, (unsigned)members), dim3(kPolWave), policy_lds_bytes(p, act != nullptr), stream, p, p.dev_params,
-                           p.dev_obs_scale, slices, env_base, obs, uniform, seed, step, act, logp, value, x, ppo_packed_len(p));
-        return hipGetLastError();
-    }
-    const auto kernel = is_split(p) ? policy_act_kernel<true, true> : policy_act_kernel<true, false>;
-    hipLaunchKernelGGL(kernel, dim3(grid, (unsigned)members),
-                       dim3(kPolWave), policy_lds_bytes(p, act != nullptr), stream, p, p.dev_params, p.dev_obs_scale, n, env_base, obs, uniform,
-                       seed, step, act, logp, value, x, ppo_packed_len(p));
-    return hipGetLastError();
-}
-
-// the greedy launches: act / logp / value are all written (the callers refuse a NULL one), no uniform, seed or step
-hipError_t launch_policy_act_greedy(const ssg_policy &p, int n, const double *obs, int32_t *act, float *logp, float *value, float *x, hipStream_t stream)
-{
-    const unsigned grid = (unsigned)((n + kPolWave - 1) / kPolWave);
-    const auto kernel = is_split(p) ? policy_act_kernel<false, true, true> : policy_act_kernel<false, false, true>;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kPolWave), policy_lds_bytes(p, true), stream, p, p.dev_params, p.dev_obs_scale, n, 0LL, obs,
-                       (const float *)nullptr, (uint64_t)0, (int64_t)0, act, logp, value, x, 0);
-    return hipGetLastError();
-}
-
-hipError_t launch_policy_pop_greedy(const ssg_policy &p, int members, int n, const double *obs, int32_t *act, float *logp, float *value, float *x,
-                                    hipStream_t stream, const int32_t *slices)
-{
-    const unsigned grid = (unsigned)((n + kPolWave - 1) / kPolWave);
-    if (slices) {
-        const auto sliced = is_split(p) ? policy_act_sliced_kernel<true, true> : policy_act_sliced_kernel<false, true>;
-        hipLaunchKernelGGL(sliced, dim3(grid, (unsigned)members), dim3(kPolWave), policy_lds_bytes(p, true), stream, p, p.dev_params, p.dev_obs_scale,
-                           slices, 0LL, obs, (const float *)nullptr, (uint64_t)0, (int64_t)0, act, logp, value, x, ppo_packed_len(p));
-        return hipGetLastError();
-    }
-    const auto kernel = is_split(p) ? policy_act_kernel<true, true, true> : policy_act_kernel<true, false, true>;
-    hipLaunchKernelGGL(kernel, dim3(grid, (unsigned)members), dim3(kPolWave), policy_lds_bytes(p, true), stream, p, p.dev_params, p.dev_obs_scale,
-                       n, 0LL, obs, (const float *)nullptr, (uint64_t)0, (int64_t)0, act, logp, value, x, ppo_packed_len(p));
-    return hipGetLastError();
+    if (l.filter) return launch_policy_filter(l, stream);
+    const bool split = is_split(*l.policy), pop = l.members > 0;
+    return launch_act((l.greedy ? kActGreedy : kAct)[split][pop], kActSliced[l.greedy][split], l, l.policy->dev_obs_scale, stream);
 }
 
 hipError_t launch_policy_dist(const ssg_policy &p, int members, int n, long long N, int K, const float *x, float *logp_all, hipStream_t stream,

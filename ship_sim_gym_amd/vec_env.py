@@ -613,27 +613,29 @@ class ShipVecEnv(*_BASES):
         global env id).  x_out: a float32 [N, D] tensor to write the normalised observations into.  greedy=True (ssg_policy_act_greedy):
         the first action with the largest logit instead of a draw, and its logp; value and x are the sampling call's bit for bit, seed
         and step are not used, and `uniforms` with it raises ValueError."""
+        return self._act(self._check_policy, policy, "ssg_policy_act", "policy_act", seed, step, uniforms, x_out, greedy)
+
+    def _act(self, check, record, c_name, what, seed, step, uniforms, x_out, greedy):
+        """policy_act / population_act: `check` judges the record, c_name is its sampling entry point (c_name + "_greedy": the other)."""
         torch = _torch()
-        self._check_policy(policy, "policy_act")
+        check(record, what)
         if greedy and uniforms is not None:
-            raise ValueError("policy_act: greedy=True reads no uniforms (pass one or the other)")
+            raise ValueError("%s: greedy=True reads no uniforms (pass one or the other)" % what)
         n, D = self.num_envs, self.states_history
-        up = self._f32_rows(uniforms, (n,), "policy_act uniforms") if uniforms is not None else None
+        up = self._f32_rows(uniforms, (n,), what + " uniforms") if uniforms is not None else None
         with torch.cuda.device(self.device):
             act = torch.empty(n, dtype=torch.int32, device=self.device)
             logp = torch.empty(n, dtype=torch.float32, device=self.device)
             val = torch.empty(n, dtype=torch.float32, device=self.device)
             x = x_out if x_out is not None else torch.empty((n, D), dtype=torch.float32, device=self.device)
-            xp = self._f32_rows(x, (n, D), "policy_act x_out")
-            pol = policy.to_native()
+            xp = self._f32_rows(x, (n, D), what + " x_out")
+            rec = record.to_native()
             if greedy:
-                N.check(N.lib().ssg_policy_act_greedy(self._h, C.byref(pol), C.c_void_p(self.obs.data_ptr()), C.c_void_p(act.data_ptr()),
-                                                      C.c_void_p(logp.data_ptr()), C.c_void_p(val.data_ptr()), xp, self._stream()),
-                        self._h, "ssg_policy_act_greedy")
-                return act, logp, val, x
-            N.check(N.lib().ssg_policy_act(self._h, C.byref(pol), C.c_void_p(self.obs.data_ptr()), up, int(seed), int(step),
-                                           C.c_void_p(act.data_ptr()), C.c_void_p(logp.data_ptr()), C.c_void_p(val.data_ptr()), xp,
-                                           self._stream()), self._h, "ssg_policy_act")
+                c_name, draw = c_name + "_greedy", ()
+            else:
+                draw = (up, int(seed), int(step))
+            N.check(getattr(N.lib(), c_name)(self._h, C.byref(rec), C.c_void_p(self.obs.data_ptr()), *draw, C.c_void_p(act.data_ptr()),
+                                             C.c_void_p(logp.data_ptr()), C.c_void_p(val.data_ptr()), xp, self._stream()), self._h, c_name)
         return act, logp, val, x
 
     def rollout_policy(self, policy, K, seed=0, step0=0, uniforms=None, out=None):
@@ -643,18 +645,22 @@ class ShipVecEnv(*_BASES):
         [K, N], last_val f32 [N] (the value of the observation after the last step).  uniforms: float32 [K, N] or None = Philox keyed
         by (seed, step0 + k, global env id).  out: such a dict, preallocated (first dimension >= K), to write into.  Leaves `obs`
         holding the observation after the last step, like K step_tensor calls."""
+        return self._rollout(self._check_policy, policy, "ssg_rollout_policy", "rollout_policy", K, seed, step0, uniforms, out)
+
+    def _rollout(self, check, record, c_name, what, K, seed, step0, uniforms, out):
+        """rollout_policy / rollout_population: `check` judges the record, c_name is its entry point."""
         torch = _torch()
-        self._check_policy(policy, "rollout_policy")
+        check(record, what)
         K, n = int(K), self.num_envs
         if K < 1:
-            raise ValueError("rollout_policy: K must be >= 1")
-        up = self._f32_rows(uniforms, (K, n), "rollout_policy uniforms") if uniforms is not None else None
+            raise ValueError("%s: K must be >= 1" % what)
+        up = self._f32_rows(uniforms, (K, n), what + " uniforms") if uniforms is not None else None
         with torch.cuda.device(self.device):
-            out, p = self._rollout_buffers(K, out, "rollout_policy")
-            pol = policy.to_native()
-            N.check(N.lib().ssg_rollout_policy(self._h, C.byref(pol), K, up, int(seed), int(step0), C.c_void_p(self.obs.data_ptr()),
-                                               p["act"], p["logp"], p["val"], p["obs"], p["rew"], p["done"], p["flags"], p["last_val"],
-                                               n, self._stream()), self._h, "ssg_rollout_policy")
+            out, p = self._rollout_buffers(K, out, what)
+            rec = record.to_native()
+            N.check(getattr(N.lib(), c_name)(self._h, C.byref(rec), K, up, int(seed), int(step0), C.c_void_p(self.obs.data_ptr()),
+                                             p["act"], p["logp"], p["val"], p["obs"], p["rew"], p["done"], p["flags"], p["last_val"],
+                                             n, self._stream()), self._h, c_name)
         return {k: (v[:K] if k != "last_val" else v) for k, v in out.items()}
 
     def _rollout_buffers(self, K, out, what):
@@ -727,46 +733,13 @@ class ShipVecEnv(*_BASES):
         member whose slice holds it — (ssg_pop_act, one launch): returns (act
         int32 [N], logp [N], value [N], x [N, D] float32) device tensors.  uniforms / x_out / Philox keying / greedy as policy_act
         (greedy=True: ssg_pop_act_greedy)."""
-        torch = _torch()
-        self._check_population(population, "population_act")
-        if greedy and uniforms is not None:
-            raise ValueError("population_act: greedy=True reads no uniforms (pass one or the other)")
-        n, D = self.num_envs, self.states_history
-        up = self._f32_rows(uniforms, (n,), "population_act uniforms") if uniforms is not None else None
-        with torch.cuda.device(self.device):
-            act = torch.empty(n, dtype=torch.int32, device=self.device)
-            logp = torch.empty(n, dtype=torch.float32, device=self.device)
-            val = torch.empty(n, dtype=torch.float32, device=self.device)
-            x = x_out if x_out is not None else torch.empty((n, D), dtype=torch.float32, device=self.device)
-            xp = self._f32_rows(x, (n, D), "population_act x_out")
-            pop = population.to_native()
-            if greedy:
-                N.check(N.lib().ssg_pop_act_greedy(self._h, C.byref(pop), C.c_void_p(self.obs.data_ptr()), C.c_void_p(act.data_ptr()),
-                                                   C.c_void_p(logp.data_ptr()), C.c_void_p(val.data_ptr()), xp, self._stream()),
-                        self._h, "ssg_pop_act_greedy")
-                return act, logp, val, x
-            N.check(N.lib().ssg_pop_act(self._h, C.byref(pop), C.c_void_p(self.obs.data_ptr()), up, int(seed), int(step),
-                                        C.c_void_p(act.data_ptr()), C.c_void_p(logp.data_ptr()), C.c_void_p(val.data_ptr()), xp,
-                                        self._stream()), self._h, "ssg_pop_act")
-        return act, logp, val, x
+        return self._act(self._check_population, population, "ssg_pop_act", "population_act", seed, step, uniforms, x_out, greedy)
 
     def rollout_population(self, population, K, seed=0, step0=0, uniforms=None, out=None):
         """rollout_policy with env e acting under member e // (N / P) of a NativePopulation (ssg_pop_rollout: one policy launch per step
         for the whole population, then ssg_step).  Same out-dict, uniforms, Philox keying and `out` as rollout_policy; member m's
         columns are [m*n, (m+1)*n), n = N / P, or its slice of set_population_slices."""
-        torch = _torch()
-        self._check_population(population, "rollout_population")
-        K, n = int(K), self.num_envs
-        if K < 1:
-            raise ValueError("rollout_population: K must be >= 1")
-        up = self._f32_rows(uniforms, (K, n), "rollout_population uniforms") if uniforms is not None else None
-        with torch.cuda.device(self.device):
-            out, p = self._rollout_buffers(K, out, "rollout_population")
-            pop = population.to_native()
-            N.check(N.lib().ssg_pop_rollout(self._h, C.byref(pop), K, up, int(seed), int(step0), C.c_void_p(self.obs.data_ptr()),
-                                            p["act"], p["logp"], p["val"], p["obs"], p["rew"], p["done"], p["flags"], p["last_val"],
-                                            n, self._stream()), self._h, "ssg_pop_rollout")
-        return {k: (v[:K] if k != "last_val" else v) for k, v in out.items()}
+        return self._rollout(self._check_population, population, "ssg_pop_rollout", "rollout_population", K, seed, step0, uniforms, out)
 
     # ------------------------------------------------------------------------------------------------
     # the observation filter (ssg_set_obs_filter; ship_sim_gym_amd/obs_filter.py)

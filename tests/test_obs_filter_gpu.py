@@ -290,6 +290,57 @@ def test_population_members_are_single_policy_filters(torch_cuda, sizes):
     env.close()
 
 
+@pytest.mark.parametrize("layers", [1, 2])
+@pytest.mark.parametrize("sizes", [None, (1, 63, 128)], ids=["equal", "sliced"])
+def test_separate_value_population_members_are_single_policy_filters(torch_cuda, sizes, layers):
+    """The FILTER kernels of a population whose members have a separate value network — on equal slices and on a slices table, sampled,
+    greedy and the value-only bootstrap forward — against the single-policy path with a filter of its own on each member's shard
+    (test_policy_act_normalises_with_the_published_state checks that path for a separate value network).  The smallest shapes that
+    still tell the kernels, grids and LDS sizes apart: D = 8, hidden 16, one and two layers (two: the third activation buffer), and
+    slices of one env, a partial wave and two workgroups."""
+    torch = torch_cuda
+    from ship_sim_gym_amd.population import NativePopulation
+    from ship_sim_gym_amd.vec_env import ShipVecEnv
+    P, N, D, H, K = 3, 192, 8, 16, 3
+
+    def vec(n, base=0):
+        env = ShipVecEnv(n, n_maps=64, n_beams=2, env_config=env_config(1), env_id_base=base)
+        assert env.states_history == D
+        return env
+
+    def members():
+        return [split_policy(torch, D, H, layers, seed=60 + m)[1] for m in range(P)]
+
+    env = vec(N)
+    if sizes is not None:
+        env.set_population_slices(sizes)
+    sz = list(sizes) if sizes is not None else [N // P] * P
+    offs = [sum(sz[:m]) for m in range(P)]
+    refs, pop = members(), NativePopulation(members())
+    flt = _filter(env, n_members=P)
+    env.set_obs_filter(flt)
+    env.reset_tensor()
+    rb = env.rollout_population(pop, K, seed=7)
+    assert flt.count.tolist() == [float(K * s) for s in sz]
+    acts = {greedy: env.population_act(pop, seed=3, step=1, greedy=greedy) for greedy in (False, True)}
+    assert not torch.equal(acts[False][0], acts[True][0])
+    for m, (o, n) in enumerate(zip(offs, sz)):
+        sh = vec(n, base=o)
+        fs = _filter(sh)
+        sh.set_obs_filter(fs)
+        sh.reset_tensor()
+        rs = sh.rollout_policy(refs[m], K, seed=7)
+        for k in KEYS:
+            got = rb[k][o:o + n] if k == "last_val" else rb[k][:, o:o + n]
+            assert got.dtype == rs[k].dtype and torch.equal(got, rs[k]), (m, k)
+        assert torch.equal(env.obs[o:o + n], sh.obs) and torch.equal(flt.state[m], fs.state[0]), m
+        for greedy, pa in acts.items():
+            sa = sh.policy_act(refs[m], seed=3, step=1, greedy=greedy)
+            assert all(p.dtype == q.dtype and torch.equal(p[o:o + n], q) for p, q in zip(pa, sa)), (m, greedy)
+        sh.close()
+    env.close()
+
+
 def test_evaluation_is_frozen(torch_cuda):
     torch = torch_cuda
     from ship_sim_gym_amd.evaluate import NativeEvaluator, eval_walk
