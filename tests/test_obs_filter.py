@@ -122,7 +122,7 @@ def _columns(rng, n):
 CONST = (4, 5)
 
 
-@pytest.mark.parametrize("n", [1, 2, 63, 255, 256, 257, 769, 4096])
+@pytest.mark.parametrize("n", [1, 2, 63, 255, 256, 257, 769, 4096, 2049, 16385, 35000])
 def test_merge_reference_against_long_double(n):
     """After T successive merges of n rows each: |mean - ref| <= 16 T u max|column|, |M2 - ref| <= 64 T u ref (u = 2^-53; ref: the
     two-pass mean and sum of squared deviations over all rows so far in np.longdouble), constant columns exact."""
@@ -149,6 +149,65 @@ def test_merge_reference_against_long_double(n):
             np.testing.assert_array_equal(st[2], np.sqrt(st[1] / (T * n - 1.0)) + 1e-8)
         else:
             np.testing.assert_array_equal(st[2], np.ones(7))
+
+
+EXACT_OFFSETS = (0.0, 2.0 ** 20, 2.0 ** 30)
+EXACT_C = 0.27  # 8 x the worst measured ratio: test_merge_reference_on_an_ill_conditioned_exact_column's docstring
+
+
+def _exact_column(rng, n, offset):
+    """k 2^-10 + offset with k uniform in -1024..1024: every value, and every sum of such values in Python integers, is exact."""
+    k = rng.randint(-1024, 1025, n)
+    return k, k * 2.0 ** -10 + offset
+
+
+@pytest.mark.parametrize("n", [2049, 16385])
+def test_merge_reference_on_an_ill_conditioned_exact_column(n):
+    """What the reduction order delivers when the mean dwarfs the spread.  One column per offset in {0, 2^20, 2^30} of values
+    k 2^-10 + offset (k uniform integers in -1024..1024), three successive merges of n rows each; the exact mean and M2 of all rows so
+    far come from Python integers: mean = offset + 2^-10 sum(k) / N, M2 = 2^-20 (sum(k^2) - sum(k)^2 / N).
+
+    * mean, every offset: |mean - exact| <= 16 T u max|x|, the bound of test_merge_reference_against_long_double.
+    * M2, offset 0 (well conditioned): that test's 64 T u exact.
+    * M2, offset > 0: |M2 - exact| <= c kappa u exact with kappa = offset / std (std: the exact sample standard deviation of the rows so
+      far, about 0.577 here, so kappa is about 1.8e6 and 1.9e9) and u = 2^-53.  The two-pass tile sums are as accurate as the well
+      conditioned case; what grows with kappa is the Chan merge's delta * delta term, delta being a difference of two means that each
+      carry an error of some u * offset.  So the error is a multiple of kappa u, and the multiple is measured, not derived: over the
+      cases of this test (both n, both offsets, T = 1..3) the worst |M2 - exact| / (kappa u exact) of merge_reference is
+      0.0337 (n = 2049, T = 3, offset 2^20; per case, printed below: 0.0001 .. 0.0337 at 2^20 and 0.0022 .. 0.0168 at 2^30), and
+      c = EXACT_C = 0.27 is eight times that, rounded up to two digits: the ratio varies several-fold between draws of one size.
+
+    tests/test_obs_filter_domain_gpu.py feeds columns of this kind to the device and requires merge_reference's bits, which carries
+    these bounds over to the kernels without a tolerance on the device side."""
+    from fractions import Fraction
+    from ship_sim_gym_amd.obs_filter import merge_reference
+    D = len(EXACT_OFFSETS)
+    rng = np.random.RandomState(7000 + n)
+    st = np.zeros((4, D))
+    ks = [np.zeros(0, dtype=np.int64) for _ in EXACT_OFFSETS]
+    for T in range(1, 4):
+        rows = np.empty((n, D))
+        for c, off in enumerate(EXACT_OFFSETS):
+            k, rows[:, c] = _exact_column(rng, n, off)
+            ks[c] = np.concatenate([ks[c], k.astype(np.int64)])
+        st = merge_reference(st, rows)
+        N = T * n
+        assert st[3, 0] == N
+        for c, off in enumerate(EXACT_OFFSETS):
+            s1, s2 = int(ks[c].sum()), int((ks[c] * ks[c]).sum())
+            mean = Fraction(int(off)) + Fraction(s1, N * 1024)
+            m2 = Fraction(s2 * N - s1 * s1, N * 1024 * 1024)
+            std = float(m2 / (N - 1)) ** 0.5
+            e_mean, e_m2 = abs(Fraction(st[0, c]) - mean), abs(Fraction(st[1, c]) - m2)
+            rel = float(e_m2 / m2)
+            print("n %d T %d offset %g: |mean err| %.3e = %.2f u |mean|   |M2 err| / M2 %.3e = %.2f u%s"
+                  % (n, T, off, float(e_mean), float(e_mean) / (U * max(abs(float(mean)), 1e-300)), rel, rel / U,
+                     " = %.4f kappa u" % (rel / (off / std * U)) if off else ""))
+            assert e_mean <= Fraction(16 * T * U * np.abs(ks[c] * 2.0 ** -10 + off).max()), (T, off, float(e_mean))
+            if off == 0.0:
+                assert e_m2 <= Fraction(64 * T * U) * m2, (T, off, rel)
+            else:
+                assert e_m2 <= Fraction(EXACT_C * (off / std) * U) * m2, (T, off, rel, rel / (off / std * U))
 
 
 def test_merge_reference_order_is_the_documented_one():

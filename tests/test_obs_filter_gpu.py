@@ -5,7 +5,10 @@ population — the single-policy path on a handle of n_m envs with env_id_base +
 square root (2 ulp).
 
 Shapes: n in {1, 2, 255, 256, 257, 769} (one row, below / at / above the 256-row tile, four tiles of which one a tail) and D in
-{7, 28, 48} (history 1 with 1 beam; history 2 with 8 beams; history 3 with 10 beams: the frame-shift path, and two column chunks)."""
+{7, 28, 48} (history 1 with 1 beam; history 2 with 8 beams; history 3 with 10 beams: the frame-shift path, and two column chunks).
+Everything above T = 4 tiles and D = 48 — runs of several tiles, empty runs, the second and third prefetch group, the column chunks
+up to D = 176, populations at the member limit and on slices with surplus workgroups, counts past 2^31, the filtered policy kernels at
+the extreme widths — is in tests/test_obs_filter_domain_gpu.py."""
 import ctypes as C
 import os
 import subprocess
