@@ -1026,6 +1026,77 @@ int ssg_set_obs_filter(ssg_handle *h, const ssg_obs_filter *f /* NULL unbinds */
 int ssg_get_obs_filter(const ssg_handle *h, ssg_obs_filter *out /* struct_size 0: nothing bound */);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Return filter (ABI 9 addition): the rewards of a rollout divided by a running standard deviation of the discounted return
+ * The other half of the wrapper above: Stable-Baselines users of train/stable_baselines/ppo.py:123 get VecNormalize(norm_reward=True)
+ * by default, which keeps a discounted return per env, updates a running variance with every step's returns and divides the step's
+ * rewards by the running standard deviation.  This is that on the device, for a whole rollout's [K][N] reward buffer in one call
+ * between the rollout and GAE, defined below on its own terms: no bit parity with Stable-Baselines is claimed (it uses the population
+ * variance and sqrt(var + eps)).  Nothing is bound to the handle, the rollout loops do not change, and the raw reward buffer is left as
+ * it is (episode statistics and evaluation read it): the call writes a second buffer, which ssg_ppo_gae / ssg_pop_gae take in place
+ * of the raw one.
+ *
+ * State, per member (one for a single policy), all f64: dev_state is [n_members][SSG_FILTER_ROWS], the observation filter's rows at
+ * obs_dim = 1: {mean, M2, denom, count}; all zeros is the empty state.  dev_carry, f64 [n_envs], is the discounted return in flight of
+ * every env: zero at the start, owned by the caller, zeroed by the caller when the envs are reset by hand.  dev_gamma, f64 [n_members],
+ * is the members' discounts, on the device.
+ *
+ * The walk, in f64, every product and sum separately rounded (no fused multiply-add).  For env e of member m and k = 0 .. K-1:
+ *     c       = c * gamma[m] + rew[k][e]        (the product, then the sum)
+ *     s[k][e] = c                               (the sample that enters the statistics)
+ *     c       = 0.0 where done[k][e] != 0       (after the sample is taken: VecNormalize's ret[news] = 0)
+ * and after row K-1 c is written back to dev_carry[e].
+ *
+ * Batch k of member m is its n_m samples s[k][.] in the order of its rows, reduced exactly as ssg_obs_filter_update reduces one column
+ * of n_m rows (above: 256-row tiles with the two halving trees, eight runs of consecutive tiles merged in tile order, the halving tree
+ * over the runs), and state_k = merge(state_{k-1}, batch_k) with the merge above in its stated association;
+ * denom_k = sqrt(M2_k / (n_k - 1)) + eps for n_k >= 2, else 1.0.  After the call the state is state_{K-1}.
+ *
+ * Output: out[k][e] = clamp(rew[k][e] / denom_k[m], -clip, +clip), in f64; clip == 0: no clamp; a denom of 0.0 (eps == 0 on constant
+ * returns) divides by 1.  Step k is divided by statistics that already include step k, as the library does.  The mean is kept but not
+ * subtracted.
+ *
+ * Frozen (SSG_RET_FILTER_UPDATE clear): dev_state and dev_carry are neither read-modified nor written, and every row is divided by the
+ * state's own denom (1 for the empty state).
+ *
+ * The result depends on a row's index within its member's slice, on n_m, K and the inputs only — not on the launch geometry or on the
+ * other members — so it is bitwise reproducible, and two calls over K1 and then K2 rows leave what one call over the K1 + K2 rows does.
+ * ------------------------------------------------------------------------------------------------- */
+#define SSG_RET_FILTER_UPDATE 0x1u       /* walk the returns and merge them into the state; clear: frozen */
+#define SSG_RET_FILTER_MAX_STEPS 1024    /* the largest K of one ssg_ret_filter_apply call (split a longer rollout into several calls) */
+typedef struct ssg_ret_filter {
+    uint32_t struct_size, flags;   /* sizeof(ssg_ret_filter); SSG_RET_FILTER_UPDATE or 0 (frozen); any other bit refused */
+    int32_t n_members, reserved;   /* 1 for a single policy, P for a population (equal split or the ssg_pop_set_slices layout); 0 */
+    double clip, eps;              /* clip >= 0 (0: none), eps >= 0; NaN refused */
+    const double *dev_gamma;       /* f64 [n_members], each in [0, 1] (the caller's to check: the host does not read device memory) */
+    double *dev_state;             /* f64 [n_members][SSG_FILTER_ROWS], caller-owned; zero = empty */
+    double *dev_carry;             /* f64 [n_envs], caller-owned; zero at the start */
+    void *dev_workspace;           /* caller-owned, >= ssg_ret_filter_workspace_nbytes(n_envs, K, n_members) bytes */
+    size_t workspace_nbytes;
+} ssg_ret_filter;
+
+/* Replaces nothing (host only; VecNormalize allocates on the host as it goes).  The workspace of ssg_ret_filter_apply for a handle of
+ * n_envs envs and calls of up to K steps: the tile partials, f64 [n_members][K][ceil(n_envs / 256)][2], then the denoms, f64
+ * [K][n_members] — 8 * n_members * K * (2 * ceil(n_envs / 256) + 1) bytes.  SSG_ERR_BAD_ARG for an argument < 1, NULL nbytes, K beyond
+ * SSG_RET_FILTER_MAX_STEPS or n_members beyond SSG_POP_MAX_MEMBERS. */
+int ssg_ret_filter_workspace_nbytes(int n_envs, int K, int n_members, size_t *nbytes);
+
+/* Replaces: the reward branch of VecNormalize.step_wait (ret = ret * gamma + rews; ret_rms.update(ret); rews = clip(rews /
+ * sqrt(ret_rms.var + eps)); ret[news] = 0) as wrapped around the env of train/stable_baselines/ppo.py:123, for the K steps of a rollout
+ * at once: three launches on `stream` (the walk with its tile partials; one workgroup per member; the division), one when frozen.
+ * dev_reward_KN / dev_done_KN: the rollout's f64 / u8 [K][step_stride_envs] buffers in the handle's row layout (what
+ * ssg_rollout_policy / ssg_pop_rollout wrote); member m's envs are columns [m n, (m + 1) n), n = n_envs / n_members, or its slice of
+ * ssg_pop_set_slices.  dev_reward_out_KN: f64, the same stride, WRITTEN for every k < K and e < n_envs (padding columns are not
+ * touched); it must not be the input buffer.  dev_denom_KP (nullable): f64 [K][n_members], the divisor of every row (1.0 where the
+ * denom was 0.0).  The arguments are judged first, then the handle (SSG_ERR_NOT_BOUND without a state blob, like every call that
+ * launches).  Refuses (SSG_ERR_BAD_ARG, nothing launched): a NULL handle or record; struct_size mismatch;
+ * an unknown flag; n_members outside 1..SSG_POP_MAX_MEMBERS, different from a bound slices layout, or one the handle's envs do not
+ * split into; a negative or NaN clip or eps; NULL dev_gamma, dev_state, dev_carry or dev_workspace; K < 1 or K >
+ * SSG_RET_FILTER_MAX_STEPS; step_stride_envs < n_envs; NULL dev_reward_KN, dev_done_KN or dev_reward_out_KN; dev_reward_out_KN ==
+ * dev_reward_KN; workspace_nbytes below ssg_ret_filter_workspace_nbytes(n_envs, K, n_members). */
+int ssg_ret_filter_apply(ssg_handle *h, const ssg_ret_filter *f, int K, const double *dev_reward_KN, const uint8_t *dev_done_KN,
+                         int64_t step_stride_envs, double *dev_reward_out_KN, double *dev_denom_KP, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Host-side geometry (what pymunk's cffi exposed at reset time); no GPU needed.
  * ------------------------------------------------------------------------------------------------- */
 /* Replaces cpConvexHull as reached by pm.Poly(...) (models.py:96,180).  out_xy holds >= count pairs. */

@@ -27,6 +27,7 @@ EVAL_STATS, EVAL_GREEDY = 8, 0x1  # columns of an evaluation's stats rows; ssg_e
  EVAL_GOALS) = range(8)
 FILTER_ROWS, FILTER_UPDATE = 4, 0x1  # state rows per member of an observation filter (mean, M2, denom, count); ssg_obs_filter.flags
 FILTER_TILE, FILTER_RUNS = 256, 8  # ssg_obs_filter_update's reduction order: rows per tile, runs of tiles (include/shipsim.h)
+RET_FILTER_UPDATE, RET_FILTER_MAX_STEPS = 0x1, 1024  # ssg_ret_filter.flags; the largest K of one ssg_ret_filter_apply call
 
 
 def pop_table_floats(n_members, n_steps):
@@ -68,6 +69,7 @@ EXPORTS = (
     "ssg_policy_act_greedy", "ssg_pop_act_greedy", "ssg_evaluate", "ssg_pop_evaluate", "ssg_eval_reduce", "ssg_eval_account",
     "ssg_pop_pack_slices", "ssg_pop_set_slices", "ssg_pop_get_slices", "ssg_pop_pack_schedule_samples",
     "ssg_obs_filter_workspace_nbytes", "ssg_obs_filter_update", "ssg_set_obs_filter", "ssg_get_obs_filter",
+    "ssg_ret_filter_workspace_nbytes", "ssg_ret_filter_apply",
 )
 
 
@@ -150,6 +152,16 @@ class ObsFilterRecord(C.Structure):
         ("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_members", C.c_int32), ("obs_dim", C.c_int32),
         ("clip", C.c_double), ("eps", C.c_double), ("dev_state", C.c_void_p), ("dev_workspace", C.c_void_p),
         ("workspace_nbytes", C.c_size_t),
+    ]
+
+
+class RetFilterRecord(C.Structure):
+    """ssg_ret_filter (ABI 9 addition): return normalisation — mode, member count, clip / eps, the members' discounts, the state rows,
+    the per-env carry, the workspace."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_members", C.c_int32), ("reserved", C.c_int32),
+        ("clip", C.c_double), ("eps", C.c_double), ("dev_gamma", C.c_void_p), ("dev_state", C.c_void_p), ("dev_carry", C.c_void_p),
+        ("dev_workspace", C.c_void_p), ("workspace_nbytes", C.c_size_t),
     ]
 
 
@@ -247,6 +259,8 @@ def lib():
     L.ssg_obs_filter_update.argtypes = [vp, C.POINTER(ObsFilterRecord), vp, vp]
     L.ssg_set_obs_filter.argtypes = [vp, C.POINTER(ObsFilterRecord)]
     L.ssg_get_obs_filter.argtypes = [vp, C.POINTER(ObsFilterRecord)]
+    L.ssg_ret_filter_workspace_nbytes.argtypes = [C.c_int, C.c_int, C.c_int, szp]
+    L.ssg_ret_filter_apply.argtypes = [vp, C.POINTER(RetFilterRecord), C.c_int, vp, vp, C.c_int64, vp, vp, vp]
     L.ssg_render.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, vp]
     L.ssg_dyn_invalidate.argtypes = [vp, vp, vp]
     L.ssg_host_convex_hull.argtypes = [C.c_int, dp, dp, ip]

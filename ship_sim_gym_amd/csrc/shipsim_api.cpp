@@ -2184,6 +2184,64 @@ int ssg_obs_filter_update(ssg_handle *h, const ssg_obs_filter *f, const double *
     return SSG_OK;
 }
 
+// ABI 9 addition: the return filter.  Everything the host can judge comes first (BAD_ARG), then the handle's state blob and the device.
+int ssg_ret_filter_workspace_nbytes(int n_envs, int K, int n_members, size_t *nbytes)
+{
+    if (!nbytes || n_envs < 1 || K < 1 || n_members < 1 || K > SSG_RET_FILTER_MAX_STEPS || n_members > SSG_POP_MAX_MEMBERS)
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_ret_filter_workspace_nbytes: NULL nbytes, an argument < 1, K or n_members out of range");
+    *nbytes = ssg::ret_filter_workspace_bytes(n_envs, K, n_members);
+    return SSG_OK;
+}
+
+int ssg_ret_filter_apply(ssg_handle *h, const ssg_ret_filter *f, int K, const double *dev_reward_KN, const uint8_t *dev_done_KN,
+                         int64_t step_stride_envs, double *dev_reward_out_KN, double *dev_denom_KP, void *stream)
+{
+    const std::string w("ssg_ret_filter_apply");
+    char buf[200];
+    if (!h) return fail(nullptr, SSG_ERR_BAD_ARG, w + ": NULL handle");
+    if (!f) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL ssg_ret_filter");
+    if (f->struct_size != sizeof(ssg_ret_filter)) return fail(h, SSG_ERR_BAD_ARG, w + ": ssg_ret_filter.struct_size != sizeof(ssg_ret_filter)");
+    if (f->flags & ~SSG_RET_FILTER_UPDATE) return fail(h, SSG_ERR_BAD_ARG, w + ": unknown bit in ssg_ret_filter.flags");
+    const int P = f->n_members, N = h->cfg.n_envs;
+    if (P < 1 || P > SSG_POP_MAX_MEMBERS) return fail(h, SSG_ERR_BAD_ARG, w + ": n_members must be in 1..SSG_POP_MAX_MEMBERS");
+    int rc = check_members(h, P, "ssg_ret_filter_apply"); // (a bound slices layout for another member count, or envs that do not split)
+    if (rc != SSG_OK) return rc;
+    if (!(f->clip >= 0.0) || !(f->eps >= 0.0)) return fail(h, SSG_ERR_BAD_ARG, w + ": clip and eps must be >= 0 (and not NaN)");
+    if (!f->dev_gamma || !f->dev_state || !f->dev_carry || !f->dev_workspace)
+        return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_gamma, dev_state, dev_carry or dev_workspace");
+    if (K < 1 || K > SSG_RET_FILTER_MAX_STEPS) return fail(h, SSG_ERR_BAD_ARG, w + ": K must be in 1..SSG_RET_FILTER_MAX_STEPS");
+    if (step_stride_envs < N) return fail(h, SSG_ERR_BAD_ARG, w + ": step_stride_envs < n_envs");
+    if (!dev_reward_KN || !dev_done_KN || !dev_reward_out_KN) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL reward, done or output buffer");
+    if (dev_reward_out_KN == dev_reward_KN) return fail(h, SSG_ERR_BAD_ARG, w + ": the output buffer must not be the reward buffer");
+    const size_t need = ssg::ret_filter_workspace_bytes(N, K, P);
+    if (f->workspace_nbytes < need) {
+        std::snprintf(buf, sizeof buf, ": workspace_nbytes %zu < %zu (ssg_ret_filter_workspace_nbytes)", f->workspace_nbytes, need);
+        return fail(h, SSG_ERR_BAD_ARG, w + buf);
+    }
+    rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    ssg::RetFilterLaunch l;
+    l.rew = dev_reward_KN;
+    l.done = dev_done_KN;
+    l.K = K;
+    l.stride = (size_t)step_stride_envs;
+    l.members = P;
+    l.n = P > 1 ? pop_width(h, P) : N;
+    l.slices = P > 1 ? pop_slices(h) : nullptr;
+    l.update = (f->flags & SSG_RET_FILTER_UPDATE) != 0;
+    l.clip = f->clip;
+    l.eps = f->eps;
+    l.gamma = f->dev_gamma;
+    l.state = f->dev_state;
+    l.carry = f->dev_carry;
+    l.workspace = f->dev_workspace;
+    l.out = dev_reward_out_KN;
+    l.denom_out = dev_denom_KP;
+    hipError_t e = ssg::launch_ret_filter(l, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("return filter launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
 int ssg_eval_account(ssg_handle *h, int episodes_per_env, const double *dev_reward, const uint8_t *dev_done, const uint8_t *dev_flags,
                      double *dev_carry_return, int32_t *dev_carry, int64_t *dev_env_stats, void *stream)
 {

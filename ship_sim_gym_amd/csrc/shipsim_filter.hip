@@ -16,36 +16,11 @@
 // operation for operation in numpy: ship_sim_gym_amd/obs_filter.py, merge_reference.
 #include <cstdint>
 
+#include "shipsim_filter_common.h"
 #include "shipsim_internal.h"
 
 namespace ssg {
 namespace {
-
-constexpr int kFltRuns = 8; // runs of consecutive tiles in the finalise launch
-
-// x[0] + ... + x[255] as a halving tree (s[i] += s[i + h] for h = 128, 64, ..., 1) over one wave: lane l holds entries l, l + 64,
-// l + 128 and l + 192.  The total is lane 0's; every lane returns it.
-__device__ __forceinline__ double wave_tree_sum(double v0, double v1, double v2, double v3)
-{
-    const double a0 = v0 + v2, a1 = v1 + v3; // h = 128
-    double s = a0 + a1;                      // h = 64
-#pragma unroll
-    for (int h = 32; h > 0; h >>= 1) s = s + __shfl_down(s, h, 64); // (lanes >= h hold values nothing below reads)
-    return __shfl(s, 0, 64);
-}
-
-// member m's rows: [m*n, (m+1)*n), or its row {o_m, n_m, ...} of the slices table
-__device__ __forceinline__ void member_rows(const int32_t *__restrict__ slices, int m, int n, size_t *row0, int *rows)
-{
-    if (slices) {
-        const int32_t *row = slices + (size_t)m * SSG_POP_SLICE_ROW;
-        *row0 = (size_t)row[0];
-        *rows = row[1];
-    } else {
-        *row0 = (size_t)m * (size_t)n;
-        *rows = n;
-    }
-}
 
 // Launch 1.  part: f64 [members][gridDim.x][2][D] = the tile's mean and M2 per column.  The tile is staged kFltChunk columns at a time
 // (all D at once when they fit: then the reads are one linear run over the tile's block); LDS rows have an odd stride in doubles, so
@@ -109,19 +84,6 @@ __global__ void __launch_bounds__(kFltTile) filter_partials_kernel(const double 
             }
         }
     }
-}
-
-struct Stat { double n, mean, m2; };
-
-// a <- a merged with b, in the header's association; an empty side leaves the other as it is
-__device__ __forceinline__ void merge(Stat &a, const Stat &b)
-{
-    if (b.n == 0.0) return;
-    if (a.n == 0.0) { a = b; return; }
-    const double n2 = a.n + b.n, w = b.n / n2, delta = b.mean - a.mean;
-    a.mean = a.mean + delta * w;
-    a.m2 = (a.m2 + b.m2) + (delta * delta) * (a.n * w);
-    a.n = n2;
 }
 
 // Launch 2.  tiles_stride: launch 1's gridDim.x.  The member's T = ceil(n_m / 256) tiles form kFltRuns runs of L = ceil(T / kFltRuns)

@@ -354,6 +354,28 @@ size_t filter_workspace_bytes(int n_envs, int obs_dim, int members);
 // the two launches: member m's n rows [m*n, (m+1)*n) of obs, or its slice (then n: the largest slice), into its SSG_FILTER_ROWS state rows
 hipError_t launch_filter_update(const double *obs, int D, int members, int n, const int32_t *slices, double eps, double *state, void *ws,
                                 hipStream_t stream);
+// the return filter (shipsim_retfilter.hip): the workspace holds the walk's tile partials, f64 [members][K][filter_tiles(n_envs)][2], then
+// the chain's denoms, f64 [K][members]
+size_t ret_filter_workspace_bytes(int n_envs, int K, int members);
+// One call's launches: walk, chain and normalise when `update`, else normalise alone with the state's own denom.  Member m's envs are
+// columns [m*n, (m+1)*n) of the [K][stride] buffers, or its slice (then n: the largest slice).
+struct RetFilterLaunch {
+    const double *rew;
+    const uint8_t *done;
+    int K;
+    size_t stride;
+    int members, n;
+    const int32_t *slices;
+    bool update;
+    double clip, eps;
+    const double *gamma; // f64 [members]
+    double *state;       // f64 [members][SSG_FILTER_ROWS]
+    double *carry;       // f64 [n_envs]
+    void *workspace;
+    double *out;         // [K][stride]
+    double *denom_out;   // nullable: f64 [K][members]
+};
+hipError_t launch_ret_filter(const RetFilterLaunch &l, hipStream_t stream);
 
 #ifdef __HIPCC__
 // One round of Philox4x32-10 (counter ctr, key key).  The counter-based streams of the library — fill_actions_kernel's actions

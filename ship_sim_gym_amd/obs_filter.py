@@ -9,8 +9,8 @@ population when there are several: bound to a ``ShipVecEnv`` (``env.set_obs_filt
 ``x`` rows with it, and the rollout loops merge each step's observations ahead of the step's policy launch.  The arithmetic is defined
 in include/shipsim.h (section "Observation filter") on its own terms; no bit parity with either library is claimed.
 
-Not covered: reward / return normalisation (``VecNormalize(norm_reward)``), merging the statistics of several handles or GPUs (RLlib
-synchronises its workers' filters), a per-column clip.
+``VecNormalize``'s other half, reward / return normalisation (``norm_reward``), is ship_sim_gym_amd/ret_filter.py's ``ReturnFilter``.
+Not covered: merging the statistics of several handles or GPUs (RLlib synchronises its workers' filters), a per-column clip.
 
 ``merge_reference`` is a numpy restatement of the device's reduction, the same tiles and trees operation for operation, for tests.
 """

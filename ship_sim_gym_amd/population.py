@@ -163,6 +163,7 @@ class PopulationPPO(object):
         self.carry_length = torch.zeros(env.num_envs, dtype=torch.int32, device=dev)
         self.kl_coef = torch.tensor(self.kl_coef, dtype=torch.float32).to(dev)  # (the list set above becomes the device tensor)
         self._last_K = 0  # the rollout length of the last batch gae() or update() saw (minibatches_for_size's default)
+        self.return_filter = None  # set_return_filter: the ReturnFilter whose state rows travel with an exploit
 
     @property
     def member_envs(self):
@@ -285,13 +286,25 @@ class PopulationPPO(object):
         return int(rew.shape[0]), self.env.num_envs
 
     # ------------------------------------------------------------------------------------------------
-    def gae(self, batch):
+    def set_return_filter(self, flt):
+        """Register a ``ReturnFilter`` of P members (None: none) so that ``exploit`` copies the source member's state rows with its
+        weights.  ``gae(batch, return_filter=f)`` applies a filter whether or not it is registered."""
+        if flt is not None and flt.n_members != self.n_members:
+            raise ValueError("PopulationPPO.set_return_filter: the filter has %d members, the population %d" % (flt.n_members, self.n_members))
+        self.return_filter = flt
+        return self
+
+    def gae(self, batch, return_filter=None):
         """GAE of every member over its columns of the rollout batch (``rollout_population``'s dict) with its own gamma / lam: returns
-        (adv, ret) f32 [K, N], stored in the batch as "adv" / "ret"; leaves the per-member advantage statistics for update()."""
+        (adv, ret) f32 [K, N], stored in the batch as "adv" / "ret"; leaves the per-member advantage statistics for update().
+        return_filter (a ``ReturnFilter`` of P members): it is applied to the batch first and GAE runs on batch["rew_norm"];
+        batch["rew"] stays as it is."""
         torch = _torch()
         K, n_env = self._KN(batch)
         dev = self.population.device
-        p = [self._flat(batch, "rew", torch.float64, (K, n_env)), self._flat(batch, "done", torch.uint8, (K, n_env)),
+        if return_filter is not None:
+            return_filter.apply(batch)
+        p = [self._flat(batch, "rew" if return_filter is None else "rew_norm", torch.float64, (K, n_env)), self._flat(batch, "done", torch.uint8, (K, n_env)),
              self._flat(batch, "val", torch.float32, (K, n_env)), self._flat(batch, "last_val", torch.float32, (n_env,))]
         self._ws(K * max(self.member_envs), 1)
         self._last_K = K
@@ -462,7 +475,8 @@ class PopulationPPO(object):
         hyper-parameters.  Those are the scheduler's business (PBTScheduler returns the new lists).  So does the source's Adam step
         count (``member_steps``): the bias correction belongs to the moments that are copied.  With an observation filter bound to
         the env (``env.set_obs_filter``), the source's filter rows travel too: an exploited member must not keep statistics its new
-        weights were never trained on."""
+        weights were never trained on.  So do the state rows of a return filter registered with ``set_return_filter``: the source's
+        value head was trained on rewards at the source's scale.  That filter's carries are per env and stay."""
         torch = _torch()
         src = [int(s) for s in src]
         if len(src) != self.n_members:
@@ -479,6 +493,9 @@ class PopulationPPO(object):
             self.kl_coef.copy_(self.kl_coef[torch.tensor(src, device=self.population.device)])
             if flt is not None:  # (an indexed copy on the handle's stream; the gather is materialised before the copy writes)
                 flt.state.copy_(flt.state[torch.tensor(src, device=flt.state.device)])
+            if self.return_filter is not None:
+                rf = self.return_filter
+                rf.state.copy_(rf.state[torch.tensor(src, device=rf.state.device)])
         steps0 = self._steps0()
         self._advance([steps0[s] for s in src], [0] * self.n_members)
 

@@ -136,11 +136,14 @@ class NativePPO(object):
         return ext
 
     # ------------------------------------------------------------------------------------------------
-    def gae(self, batch, gamma=0.99, lam=0.95):
+    def gae(self, batch, gamma=0.99, lam=0.95, return_filter=None):
         """GAE over the rollout batch (train/ppo_torch.py's loop, bitwise): returns (adv, ret) f32 [K, N] and stores them in the batch
-        as "adv" / "ret".  Also leaves the advantage mean / std on the device for the update (adv_stats())."""
+        as "adv" / "ret".  Also leaves the advantage mean / std on the device for the update (adv_stats()).  return_filter (a
+        ``ReturnFilter``): it is applied to the batch first and GAE runs on batch["rew_norm"]; batch["rew"] stays as it is."""
         torch = _torch()
-        rew, done, val, last = (self._flat(batch, "rew", torch.float64), self._flat(batch, "done", torch.uint8),
+        if return_filter is not None:
+            return_filter.apply(batch)
+        rew, done, val, last = (self._flat(batch, "rew" if return_filter is None else "rew_norm", torch.float64), self._flat(batch, "done", torch.uint8),
                                 self._flat(batch, "val", torch.float32), self._flat(batch, "last_val", torch.float32))
         K, n_env = int(rew.shape[0]), int(rew.shape[1])
         if tuple(done.shape) != (K, n_env) or tuple(val.shape) != (K, n_env) or tuple(last.shape) != (n_env,):

@@ -8,12 +8,15 @@ For each (envs, horizon) — default 65 536 x 32 and 4 096 x 64; default env (D 
 every update from the same parameters' values (their own copies) and draw their permutations from generators seeded alike.  One JSON
 line on stdout.  The kernels alone: `rocprofv3 --kernel-trace --stats -- python tools/ppo_update_timing.py --only native` (tools/README.md).
 
-    python tools/ppo_update_timing.py [--configs 65536x32,4096x64] [--repeats 7] [--only torch|native] [--ext] [--separate-value]
+    python tools/ppo_update_timing.py [--configs 65536x32,4096x64] [--repeats 7] [--only torch|native] [--ext] [--separate-value] [--ret-filter]
 
 --ext adds, in the same run, the extended update (NativePPO with vf_clip 0.2, max_grad_norm 0.5, kl_coef 1.0, kl_target 0.01: GAE, the
 ssg_ppo_dist launch, ssg_ppo_update_ext) as the path "native_ext", and the ssg_ppo_dist launch alone as "dist".
 --separate-value measures, after each configuration's shared-body figures and in the same process, the same paths for ActorCritic with
 a value network of its own (two 64-64 towers: SSG_POLICY_SEPARATE_VALUE); its results carry "separate_value": true.
+--ret-filter adds, in the same run and alternating with the others, return normalisation (ship_sim_gym_amd/ret_filter.py): "gae" (ssg_ppo_gae
+alone), "ret_gae" (ssg_ret_filter_apply updating, then GAE on its output), "ret_frozen" (the frozen apply alone: one launch), "ret_apply"
+(the updating apply alone: three launches) and "native_ret" (the whole GAE + update with the filter, to set against "native").
 """
 import argparse
 import importlib.util
@@ -75,7 +78,7 @@ def torch_update(net, opt, b, horizon, envs, D, epochs, minibatches, gen, gamma=
             opt.step()
 
 
-def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext=False, separate_value=False):
+def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext=False, separate_value=False, ret_filter=False):
     from ship_sim_gym_amd.policy import NativePolicy
     from ship_sim_gym_amd.ppo import NativePPO
     torch.manual_seed(0)
@@ -129,9 +132,27 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
     def run_dist():
         ppo_x.dist(dict(b))
 
+    from ship_sim_gym_amd.ret_filter import ReturnFilter
+    rflt, rfrozen = ReturnFilter(env), ReturnFilter(env, update=False)
+    g_r = torch.Generator(device=dev)
+    g_r.manual_seed(1)
+
+    def run_native_ret():
+        with torch.no_grad():
+            for p, q in zip(net_n.parameters(), p0):
+                p.copy_(q)
+        pol.refresh()
+        nb = dict(b)
+        ppo.gae(nb, return_filter=rflt)
+        ppo.update(nb, torch.stack([torch.randperm(n, device=dev, generator=g_r) for _ in range(epochs)]), epochs, minibatches)
+
     paths = [(k, f) for k, f in (("torch", run_torch), ("native", run_native)) if only in (None, k)]
     if ext:
         paths += [("native_ext", run_native_ext), ("dist", run_dist)]
+    if ret_filter:
+        rfrozen.state.copy_(rflt.state)  # (whatever it holds: the frozen call's cost does not depend on it)
+        paths += [("gae", lambda: ppo.gae(dict(b))), ("ret_gae", lambda: ppo.gae(dict(b), return_filter=rflt)),
+                  ("ret_frozen", lambda: rfrozen.apply(dict(b))), ("ret_apply", lambda: rflt.apply(dict(b))), ("native_ret", run_native_ret)]
     times = {k: [] for k, _ in paths}
     for _ in range(2):
         for k, f in paths:
@@ -156,9 +177,11 @@ def main():
     ap.add_argument("--only", choices=("torch", "native"), default=None)
     ap.add_argument("--ext", action="store_true", help="also time the extended update (all three terms on) and ssg_ppo_dist alone")
     ap.add_argument("--separate-value", action="store_true", help="also measure the separate-value-network shape, in the same process")
+    ap.add_argument("--ret-filter", action="store_true", help="also time return normalisation: GAE alone, apply + GAE, the frozen apply, "
+                                                              "the updating apply, and the whole GAE + update with the filter")
     a = ap.parse_args()
     mod = _ppo()
-    res = [measure(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.repeats, a.only, "cuda:0", ext=a.ext, separate_value=sep)
+    res = [measure(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.repeats, a.only, "cuda:0", ext=a.ext, separate_value=sep, ret_filter=a.ret_filter)
            for c in a.configs.split(",") for sep in ([False, True] if a.separate_value else [False])]
     print(json.dumps({"ppo_update_timing": res}))
 

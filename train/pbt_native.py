@@ -53,6 +53,12 @@ envs are not disturbed, and the table is printed.  The ranking stays by training
 filter), instead of the fixed division by the largest bound.  Every rollout step merges each member's own rows into its statistics
 before the policy launch; the statistics stay with the member through a re-slice, travel with the weights on an exploit, and the
 --eval-every env reads them frozen.
+
+--norm-reward (default off): the rewards each member's GAE sees are divided by a running standard deviation of its envs' discounted
+returns, kept on the device per member (ship_sim_gym_amd/ret_filter.py; the reward half of Stable-Baselines' VecNormalize, with the
+member's own gamma): one library call per rollout between the rollout and GAE.  The raw rewards, which episode_reward_mean reads, stay
+as they are; a member's statistics travel with its weights on an exploit, the per-env returns in flight stay with their envs.
+--reward-clip C clamps the normalised rewards to +-C (default 10; 0: none).
 """
 import argparse
 import os
@@ -118,6 +124,10 @@ def make_arg_parser():
     ap.add_argument("--eval-episodes", type=int, default=1, metavar="E", help="episodes counted per env by each evaluation")
     ap.add_argument("--obs-filter", action="store_true",
                     help="normalise observations with a running mean / std filter per member on the device; default: obs / max bound")
+    ap.add_argument("--norm-reward", action="store_true",
+                    help="divide the rewards GAE sees by a running std of the discounted return, per member on the device; default: raw rewards")
+    ap.add_argument("--reward-clip", type=float, default=10.0, metavar="C",
+                    help="clamp the normalised rewards to +-C (needs --norm-reward; 0: no clamp)")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -171,13 +181,17 @@ def parse_args(argv=None):
         ap.error("--kl-coeff, --kl-target, --vf-clip and --max-grad-norm must be >= 0")
     if a.eval_every < 0 or a.eval_episodes < 1:
         ap.error("--eval-every must be >= 0 and --eval-episodes >= 1")
+    if a.reward_clip != 10.0 and not a.norm_reward:
+        ap.error("--reward-clip needs --norm-reward")
+    if not a.reward_clip >= 0.0:
+        ap.error("--reward-clip must be >= 0")
     return a
 
 
 def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every=5, seed=0, epochs=2, minibatches=4, lrs=None,
           pbt=True, device="cuda:0", log=print, return_details=False, kl_coeff=0.0, kl_target=0.01, vf_clip=0.0, max_grad_norm=0.0,
           separate_value=False, mutate_schedule=False, max_epochs=30, eval_every=0, eval_episodes=1, envs=None, mutate_batch=False,
-          batch_shares=None, quantum=None, obs_filter=False):
+          batch_shares=None, quantum=None, obs_filter=False, norm_reward=False, reward_clip=10.0):
     import torch
     from ship_gym.config import EnvConfig, GameConfig
     from ship_sim_gym_amd.population import NativePopulation, PBTScheduler, PopulationPPO, reference_mutations, slices_for_batch_sizes
@@ -240,6 +254,11 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
         env.set_obs_filter(flt)
         if eval_env is not None:
             eval_env.set_obs_filter(flt.frozen(eval_env))
+    rflt = None
+    if norm_reward:  # per-member statistics of the discounted returns; applied between the rollout and GAE, nothing is bound to the env
+        from ship_sim_gym_amd.ret_filter import ReturnFilter
+        rflt = ReturnFilter(env, n_members=P, gamma=ppo.gamma, clip=reward_clip)
+        ppo.set_return_filter(rflt)  # (an exploit copies the source's state rows with its weights)
     env.reset_tensor()
     window = torch.zeros((P, 3), dtype=torch.int64, device=dev)  # episodes since the last perturbation
     scores = [float("-inf")] * P
@@ -264,9 +283,11 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
     for u in range(1, updates + 1):
         uniforms = torch.rand((horizon, n_total), generator=gen, device=dev)
         batch = env.rollout_population(pop, horizon, uniforms=uniforms, out=out)
-        out = {k: v for k, v in batch.items() if k not in ("adv", "ret", "logp_all")}
+        out = {k: v for k, v in batch.items() if k not in ("adv", "ret", "logp_all", "rew_norm", "rew_denom")}
         window += ppo.episode_stats(batch)
-        ppo.gae(batch)
+        if rflt is not None:
+            rflt.set_gamma(ppo.gamma)  # (the members' own discounts, whatever they currently are)
+        ppo.gae(batch, return_filter=rflt)
         if sliced:  # member m's own rows: [perm_epochs, horizon * n_m], nothing padded to the widest member
             perm = [torch.rand((perm_epochs, s), generator=gen, device=dev).argsort(dim=-1) for s in member_samples]
         else:
@@ -337,6 +358,10 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
     if flt is not None:
         details["obs_filter"] = flt.state_dict()
         log("observation filter: rows merged per member %s" % [int(c) for c in details["obs_filter"]["state"][:, 3, 0].tolist()])
+    if rflt is not None:
+        details["ret_filter"] = rflt.state_dict()
+        log("return filter: returns merged per member %s  std %s" % ([int(c) for c in details["ret_filter"]["state"][:, 3].tolist()],
+                                                                     ["%.5f" % d for d in details["ret_filter"]["state"][:, 2].tolist()]))
     if eval_env is not None:
         eval_env.close()
     env.close()
@@ -349,7 +374,8 @@ def main(argv=None):
           seed=a.seed, epochs=a.epochs, minibatches=a.minibatches, lrs=a.lrs, pbt=a.pbt, device=a.device, kl_coeff=a.kl_coeff,
           kl_target=a.kl_target, vf_clip=a.vf_clip, max_grad_norm=a.max_grad_norm, separate_value=a.separate_value,
           mutate_schedule=a.mutate_schedule, max_epochs=a.max_epochs, eval_every=a.eval_every, eval_episodes=a.eval_episodes, envs=a.envs,
-          mutate_batch=a.mutate_batch, batch_shares=a.batch_shares, quantum=a.quantum, obs_filter=a.obs_filter)
+          mutate_batch=a.mutate_batch, batch_shares=a.batch_shares, quantum=a.quantum, obs_filter=a.obs_filter,
+          norm_reward=a.norm_reward, reward_clip=a.reward_clip)
 
 
 if __name__ == "__main__":

@@ -6,6 +6,7 @@ leave the GPU; the policy is a small MLP in fp32.
 
     python train/ppo_torch.py --envs 4096 --updates 20 [--mode eager|graph|pingpong|native] [--update torch|native] [--separate-value]
                               [--eval-every U --eval-episodes E] [--obs-filter [--save-obs-filter FILE]]
+                              [--norm-reward [--reward-clip C]]
 
 Four ways to run the rollout loop (the reference's `model.learn` -> runner.run(): one `env.step(actions)` per policy
 forward, train/stable_baselines/ppo.py:84-100,122-123) — same arithmetic, same results bit for bit:
@@ -40,6 +41,11 @@ train/rllib/rollout.py:8-26), so the training envs are not disturbed, and the re
 largest bound: every rollout step first merges its observations into the statistics, then normalises them; the ``--eval-every`` env
 gets a frozen view of the same statistics.  With ``--update native`` the per-update loss terms are printed as well.
 ``--save-obs-filter FILE`` saves the statistics (``ObsFilter.state_dict``) for train/evaluate_native.py ``--obs-filter FILE``.
+
+``--norm-reward`` (``--mode native --update native`` only; default off): the rewards GAE sees are divided by a running standard deviation
+of the per-env discounted return, kept on the device (ship_sim_gym_amd/ret_filter.py — the reward half of Stable-Baselines'
+VecNormalize, its default): one library call per rollout between ``rollout_policy`` and GAE; the raw rewards, which the logged
+statistics read, stay as they are.  ``--reward-clip C`` clamps the normalised rewards to +-C (default 10, VecNormalize's; 0: none).
 
 The sampling noise of a whole rollout is drawn in one call before it (uniforms [horizon, envs], inverse-CDF sampling inside
 the step), so a captured step holds no random-number generator state and replays exactly what the eager loop computes.
@@ -209,12 +215,16 @@ def rollout(shards, horizon, mode, gen, policy=None):
 
 def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, gamma=0.99, lam=0.95, clip=0.2,
           device="cuda:0", seed=0, log=print, mode="eager", return_details=False, env_kw=None, update="torch", separate_value=False,
-          eval_every=0, eval_episodes=1, eval_envs=None, obs_filter=False, save_obs_filter=None):
+          eval_every=0, eval_episodes=1, eval_envs=None, obs_filter=False, save_obs_filter=None,
+          norm_reward=False, reward_clip=10.0):
     assert mode in ("eager", "graph", "pingpong", "native")
     if (obs_filter or save_obs_filter) and mode != "native":
         raise ValueError("obs_filter normalises inside the native policy launch: it needs mode='native' (got mode=%r)" % (mode,))
     if save_obs_filter and not obs_filter:
         raise ValueError("save_obs_filter needs obs_filter=True")
+    if norm_reward and (mode != "native" or update != "native"):
+        raise ValueError("norm_reward normalises the native rollout's reward buffer ahead of the device's GAE: it needs mode='native' and "
+                         "update='native' (got mode=%r, update=%r)" % (mode, update))
     if eval_every and mode != "native":
         raise ValueError("eval_every evaluates the native policy on the device: it needs mode='native' (got mode=%r)" % (mode,))
     if eval_every < 0 or eval_episodes < 1:
@@ -242,6 +252,10 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         from ship_sim_gym_amd.obs_filter import ObsFilter
         flt = ObsFilter(shards[0].env)
         shards[0].env.set_obs_filter(flt)
+    rflt = None
+    if norm_reward:  # (applied to each rollout's reward buffer between the rollout and GAE; nothing is bound to the env)
+        from ship_sim_gym_amd.ret_filter import ReturnFilter
+        rflt = ReturnFilter(shards[0].env, gamma=gamma, clip=reward_clip)
     evaluator, evals = None, []
     if eval_every:  # a second env of its own: evaluation resets and steps it, the training envs keep their episodes
         from ship_sim_gym_amd.evaluate import NativeEvaluator
@@ -274,14 +288,18 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         t1 = time.perf_counter()
         if ppo is not None:  # GAE + the whole update on the device, on the rollout's own buffers (the same randperm draws)
             nb = dict(shards[0].native_out)
-            ppo.gae(nb, gamma, lam)
+            ppo.gae(nb, gamma, lam, return_filter=rflt)
             n = horizon * envs
             st_upd = ppo.update(nb, torch.stack([torch.randperm(n, device=dev, generator=gen) for _ in range(epochs)]), epochs, minibatches,
-                                stats=flt is not None)
-            if flt is not None:
+                                stats=flt is not None or rflt is not None)
+            if st_upd is not None:
                 pg, vf, ent = (float(v) for v in st_upd[-1, :3])
-                log("update %3d  last minibatch: policy loss %+.5f  value loss %.5f  entropy %.5f  (obs filter: %d rows merged)" % (
-                    u, pg, vf, ent, int(flt.count[0].item())))
+                notes = []
+                if flt is not None:
+                    notes.append("(obs filter: %d rows merged)" % int(flt.count[0].item()))
+                if rflt is not None:
+                    notes.append("(return filter: %d returns merged, std %.5f)" % (int(rflt.count[0].item()), float(rflt.denom[0].item())))
+                log("update %3d  last minibatch: policy loss %+.5f  value loss %.5f  entropy %.5f  %s" % (u, pg, vf, ent, "  ".join(notes)))
         else:
             if native_last_val is not None:
                 last_val = native_last_val
@@ -343,6 +361,8 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         if save_obs_filter:
             torch.save(details["obs_filter"], save_obs_filter)
             log("observation filter statistics (%d rows merged) saved to %s" % (int(details["obs_filter"]["state"][0, 3, 0]), save_obs_filter))
+    if rflt is not None:
+        details["ret_filter"] = rflt.state_dict()
     if evaluator is not None:
         evaluator.env.close()
     for sh in shards:
@@ -367,6 +387,11 @@ def make_arg_parser():
     ap.add_argument("--obs-filter", action="store_true",
                     help="normalise observations with a running mean / std filter on the device (needs --mode native); default: obs / max bound")
     ap.add_argument("--save-obs-filter", default=None, metavar="FILE", help="save the filter's statistics at the end (needs --obs-filter)")
+    ap.add_argument("--norm-reward", action="store_true",
+                    help="divide the rewards GAE sees by a running std of the discounted return, on the device (needs --mode native "
+                         "--update native); default: raw rewards")
+    ap.add_argument("--reward-clip", type=float, default=10.0, metavar="C",
+                    help="clamp the normalised rewards to +-C (needs --norm-reward; 0: no clamp)")
     return ap
 
 
@@ -384,10 +409,17 @@ def parse_args(argv=None):
         ap.error("--obs-filter needs --mode native (the filter runs inside the native policy launch)")
     if a.save_obs_filter and not a.obs_filter:
         ap.error("--save-obs-filter needs --obs-filter")
+    if a.norm_reward and (a.mode != "native" or a.update != "native"):
+        ap.error("--norm-reward needs --mode native --update native (it runs between the native rollout and the device's GAE)")
+    if a.reward_clip != 10.0 and not a.norm_reward:
+        ap.error("--reward-clip needs --norm-reward")
+    if not a.reward_clip >= 0.0:
+        ap.error("--reward-clip must be >= 0")
     return a
 
 
 if __name__ == "__main__":
     a = parse_args()
     train(envs=a.envs, updates=a.updates, horizon=a.horizon, mode=a.mode, update=a.update, separate_value=a.separate_value,
-          eval_every=a.eval_every, eval_episodes=a.eval_episodes, obs_filter=a.obs_filter, save_obs_filter=a.save_obs_filter)
+          eval_every=a.eval_every, eval_episodes=a.eval_episodes, obs_filter=a.obs_filter, save_obs_filter=a.save_obs_filter,
+          norm_reward=a.norm_reward, reward_clip=a.reward_clip)
