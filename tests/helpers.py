@@ -73,90 +73,3 @@ class OracleSample:
         self.worst = max(self.worst, err)
         self.n_done += int(r_done.sum())
         self.steps += 1
-
-
-# ------------------------------------------------------------------------------------------------------------------------------------
-# The policy / PPO references shared by test_policy_native_gpu.py, test_ppo_native_gpu.py and test_ppo_domain_gpu.py
-# ------------------------------------------------------------------------------------------------------------------------------------
-def actor_critic_policy(torch, D, H=64, layers=2, act="tanh", A=3, seed=0, device="cuda:0"):
-    """An (nn.Module, NativePolicy) pair: `layers` hidden layers of width H, heads pi [A] and v, seeded uniform weights, obs scale 600."""
-    from ship_sim_gym_amd.policy import NativePolicy
-    nn = torch.nn
-    g = torch.Generator().manual_seed(seed)
-    mods = [nn.Linear(D, H), nn.Tanh() if act == "tanh" else nn.ReLU()]
-    if layers == 2:
-        mods += [nn.Linear(H, H), nn.Tanh() if act == "tanh" else nn.ReLU()]
-    net = nn.Module()
-    net.body, net.pi, net.v = nn.Sequential(*mods), nn.Linear(H, A), nn.Linear(H, 1)
-    with torch.no_grad():
-        for p in net.parameters():
-            p.copy_(torch.rand(p.shape, generator=g) * 2 - 1).mul_(1.5 / p.shape[-1] ** 0.5)
-    net = net.to(device)
-    return net, NativePolicy.from_actor_critic(net, torch.full((D,), 600.0, dtype=torch.float64, device=device))
-
-
-def torch_gae(torch, b, gamma=0.99, lam=0.95):
-    """train/ppo_torch.py's GAE loop, restated on the native rollout's buffers (rew / done as ppo_torch converts them)."""
-    rew, done, val = b["rew"].float(), b["done"].float(), b["val"]
-    K, n = rew.shape
-    adv = torch.zeros(n, device=rew.device)
-    advs, rets = [None] * K, [None] * K
-    nxt = b["last_val"]
-    for t in reversed(range(K)):
-        nonterm = 1.0 - done[t]
-        delta = rew[t] + gamma * nxt * nonterm - val[t]
-        adv = delta + gamma * lam * nonterm * adv
-        advs[t], rets[t] = adv, adv + val[t]
-        nxt = val[t]
-    return torch.stack(advs), torch.stack(rets)
-
-
-def unpack(p, offsets):
-    return {k: p[o: o + int(np.prod(s))].view(*s) for k, (o, s) in offsets.items()}
-
-
-def ppo_loss(torch, p, offsets, L, act, x, a, logp_old, advn, ret, clip=0.2, vf_coef=0.5, ent_coef=0.01):
-    """ppo_torch's minibatch loss on packed parameters p (any dtype); returns (loss, pg, (v-ret)^2 mean, entropy mean, clip fraction)."""
-    t = unpack(p, offsets)
-    f = torch.tanh if act == "tanh" else torch.relu
-    h = f(x @ t["W0"].T + t["b0"])
-    if L == 2:
-        h = f(h @ t["W1"].T + t["b1"])
-    logits, v = h @ t["Wpi"].T + t["bpi"], (h @ t["Wv"].T + t["bv"]).squeeze(-1)
-    dist = torch.distributions.Categorical(logits=logits)
-    ratio = torch.exp(dist.log_prob(a) - logp_old)
-    pg = -torch.min(ratio * advn, torch.clamp(ratio, 1 - clip, 1 + clip) * advn).mean()
-    vl = (v - ret).pow(2).mean()
-    ent = dist.entropy().mean()
-    cf = ((ratio - 1).abs() > clip).to(x.dtype).mean()
-    return pg + vf_coef * vl - ent_coef * ent, pg, vl, ent, cf
-
-
-def check_per_tensor(torch, pol, mine, ref64, ref32, what):
-    """Per packed tensor: max|mine - f64| <= 4 * max|torch f32 - f64| + 1e-6 * max|f64|."""
-    for k, (o, s) in pol.offsets.items():
-        n = int(np.prod(s))
-        g64 = ref64[o: o + n].double()
-        e_mine = float((mine[o: o + n].double() - g64).abs().max())
-        e_t32 = float((ref32[o: o + n].double() - g64).abs().max())
-        bound = 4 * e_t32 + 1e-6 * float(g64.abs().max())
-        assert e_mine <= bound, (what, k, e_mine, e_t32, bound)
-
-
-def stepwise_rollout(env, pol, K, seed, step0, uniforms=None):
-    """ssg_rollout_policy restated as K x {policy_act, step_tensor} plus the bootstrap value."""
-    import torch
-    rows = {k: [] for k in ("obs", "act", "logp", "val", "rew", "done", "flags")}
-    for k in range(K):
-        a, lp, v, x = env.policy_act(pol, seed=seed, step=step0 + k, uniforms=None if uniforms is None else uniforms[k])
-        rows["obs"].append(x); rows["act"].append(a); rows["logp"].append(lp); rows["val"].append(v)
-        _, r, d, f = env.step_tensor(a)
-        rows["rew"].append(r.clone()); rows["done"].append(d.clone()); rows["flags"].append(f.clone())
-    out = {k: torch.stack(v) for k, v in rows.items()}
-    out["last_val"] = env.policy_act(pol, seed=seed, step=step0 + K)[2]
-    return out
-
-
-def assert_same_rollout(torch, a, b, what):
-    for k in ("obs", "act", "logp", "val", "rew", "done", "flags", "last_val"):
-        assert a[k].dtype == b[k].dtype and torch.equal(a[k], b[k]), (what, k)

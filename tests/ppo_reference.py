@@ -1,0 +1,291 @@
+"""The one torch reference of the on-device policy and PPO loss, for every GPU test of the training path: seeded policies (shared body
+or separate towers), the forward on a packed buffer, the two minibatch losses, their autograd gradient and whole updates in any dtype,
+the project's acceptance bound, and rollout-shaped synthetic batches.
+
+The acceptance rule of every gradient / update test is check_per_tensor's: max|mine - f64| <= 4 max|torch f32 - f64| + 1e-6 max|f64|
+per packed tensor, so the f32 arithmetic of THIS file is part of what is asserted.  plain_loss and ext_loss stay two functions on
+purpose: Categorical and log_softmax / -(p * logp).sum give equal losses but f32 gradients that differ in the last bits."""
+import numpy as np
+
+from gpu_support import DEV
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# policies
+# ------------------------------------------------------------------------------------------------------------------------------------
+def actor_critic_policy(torch, D, H=64, layers=2, act="tanh", A=3, seed=0, device=DEV):
+    """An (nn.Module, NativePolicy) pair: `layers` hidden layers of width H, heads pi [A] and v, seeded uniform weights, obs scale 600."""
+    from ship_sim_gym_amd.policy import NativePolicy
+    nn = torch.nn
+    g = torch.Generator().manual_seed(seed)
+    mods = [nn.Linear(D, H), nn.Tanh() if act == "tanh" else nn.ReLU()]
+    if layers == 2:
+        mods += [nn.Linear(H, H), nn.Tanh() if act == "tanh" else nn.ReLU()]
+    net = nn.Module()
+    net.body, net.pi, net.v = nn.Sequential(*mods), nn.Linear(H, A), nn.Linear(H, 1)
+    with torch.no_grad():
+        for p in net.parameters():
+            p.copy_(torch.rand(p.shape, generator=g) * 2 - 1).mul_(1.5 / p.shape[-1] ** 0.5)
+    net = net.to(device)
+    return net, NativePolicy.from_actor_critic(net, torch.full((D,), 600.0, dtype=torch.float64, device=device))
+
+
+def split_module(torch, D, H=64, layers=2, act="tanh", A=3, seed=0, same_towers=False, device=DEV):
+    """A module declaring pi_body, pi, vf_body, v with seeded uniform weights (actor_critic_policy's scaling); same_towers: the vf tower
+    holds the pi tower's numbers."""
+    nn = torch.nn
+    g = torch.Generator().manual_seed(seed)
+
+    def tower():
+        mods = [nn.Linear(D, H), nn.Tanh() if act == "tanh" else nn.ReLU()]
+        if layers == 2:
+            mods += [nn.Linear(H, H), nn.Tanh() if act == "tanh" else nn.ReLU()]
+        return nn.Sequential(*mods)
+
+    net = nn.Module()
+    net.pi_body, net.pi, net.vf_body, net.v = tower(), nn.Linear(H, A), tower(), nn.Linear(H, 1)
+    with torch.no_grad():
+        for p in net.parameters():
+            p.copy_(torch.rand(p.shape, generator=g) * 2 - 1).mul_(1.5 / p.shape[-1] ** 0.5)
+        if same_towers:
+            for p, q in zip(net.vf_body.parameters(), net.pi_body.parameters()):
+                p.copy_(q)
+    return net.to(device)
+
+
+def split_policy(torch, D, H=64, layers=2, act="tanh", A=3, seed=0, same_towers=False, device=DEV):
+    from ship_sim_gym_amd.policy import NativePolicy
+    net = split_module(torch, D, H, layers, act, A, seed, same_towers, device)
+    pol = NativePolicy.from_actor_critic(net, torch.full((D,), 600.0, dtype=torch.float64, device=device))
+    assert pol.separate_value
+    return net, pol
+
+
+def shared_over_pi_tower(torch, net, pol):
+    """The shared NativePolicy over `net`'s pi tower and both heads (its own copy of the numbers)."""
+    from ship_sim_gym_amd.policy import NativePolicy
+    mods = list(net.pi_body)
+    layers = [(m.weight.detach().clone(), m.bias.detach().clone()) for m in mods[0::2]]
+    heads = [(m.weight.detach().clone(), m.bias.detach().clone()) for m in (net.pi, net.v)]
+    out = NativePolicy(layers, heads[0], heads[1], pol.obs_scale, activation=pol.activation)
+    assert not out.separate_value
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# the forward and the two losses on a packed buffer
+# ------------------------------------------------------------------------------------------------------------------------------------
+def unpack(p, offsets):
+    return {k: p[o: o + int(np.prod(s))].view(*s) for k, (o, s) in offsets.items()}
+
+
+def forward(torch, p, offsets, L, act, x):
+    """(logits, value) of a packed buffer p (any dtype): a shared body, or separate towers when the buffer holds V0."""
+    t = unpack(p, offsets)
+    f = torch.tanh if act == "tanh" else torch.relu
+    split = "V0" in offsets
+    h = hv = f(x @ t["W0"].T + t["b0"])
+    if split:
+        hv = f(x @ t["V0"].T + t["c0"])
+    if L == 2:
+        h = f(h @ t["W1"].T + t["b1"])
+        hv = f(hv @ t["V1"].T + t["c1"]) if split else h
+    return h @ t["Wpi"].T + t["bpi"], (hv @ t["Wv"].T + t["bv"]).squeeze(-1)
+
+
+def plain_loss(torch, p, offsets, L, act, x, a, logp_old, advn, ret, clip=0.2, vf_coef=0.5, ent_coef=0.01):
+    """ppo_torch's minibatch loss on packed parameters p (any dtype); returns (loss, pg, (v-ret)^2 mean, entropy mean, clip fraction)."""
+    logits, v = forward(torch, p, offsets, L, act, x)
+    dist = torch.distributions.Categorical(logits=logits)
+    ratio = torch.exp(dist.log_prob(a) - logp_old)
+    pg = -torch.min(ratio * advn, torch.clamp(ratio, 1 - clip, 1 + clip) * advn).mean()
+    vl = (v - ret).pow(2).mean()
+    ent = dist.entropy().mean()
+    cf = ((ratio - 1).abs() > clip).to(x.dtype).mean()
+    return pg + vf_coef * vl - ent_coef * ent, pg, vl, ent, cf
+
+
+def ext_loss(torch, p, offsets, L, act, x, a, logp_old, advn, ret, v_old, lpa_old, clip=0.2, vf_coef=0.5, ent_coef=0.01, vf_clip=0.0,
+             kl_coef=0.0):
+    """The extended minibatch loss on packed parameters p (any dtype): returns (loss, pg, mean VL, entropy mean, clip fraction,
+    mean KL, (v - v_old, (v - ret)^2, clipped (v_c - ret)^2)).  lpa_old: [M, A] (the acting policy's log-distribution)."""
+    logits, v = forward(torch, p, offsets, L, act, x)
+    lpa = torch.log_softmax(logits, -1)
+    ratio = torch.exp(lpa.gather(-1, a.unsqueeze(-1)).squeeze(-1) - logp_old)
+    pg = -torch.min(ratio * advn, torch.clamp(ratio, 1 - clip, 1 + clip) * advn).mean()
+    l1 = (v - ret).pow(2)
+    l2 = (v_old + torch.clamp(v - v_old, -vf_clip, vf_clip) - ret).pow(2)
+    vl = torch.max(l1, l2).mean() if vf_clip > 0 else l1.mean()
+    ent = -(lpa.exp() * lpa).sum(-1).mean()
+    kl = (lpa_old.exp() * (lpa_old - lpa)).sum(-1).mean()
+    cf = ((ratio - 1).abs() > clip).to(x.dtype).mean()
+    loss = pg + vf_coef * vl - ent_coef * ent
+    if kl_coef > 0:
+        loss = loss + kl_coef * kl
+    return loss, pg, vl, ent, cf, kl, (v - v_old, l1, l2)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# gradients and whole updates
+# ------------------------------------------------------------------------------------------------------------------------------------
+def minibatch(torch, pol, b, idx, advn, dtype):
+    """Rows idx of the flattened batch in `dtype`, in the losses' argument order: x, a, logp, advn, ret, and for a batch that carries
+    the acting policy's distribution (logp_all) also val and logp_all[:, :A]."""
+    flat = lambda k: b[k].reshape(-1)[idx].to(dtype)  # noqa: E731
+    out = (b["obs"].reshape(-1, pol.obs_dim)[idx].to(dtype), b["act"].reshape(-1)[idx].long(), flat("logp"), advn[idx].to(dtype), flat("ret"))
+    if "logp_all" in b:
+        out += (flat("val"), b["logp_all"].reshape(-1, 4)[idx][:, :pol.n_actions].to(dtype))
+    return out
+
+
+def _loss(torch, pol, p, mb, loss_kw):
+    """plain_loss on a five-column minibatch, ext_loss on a seven-column one."""
+    return (ext_loss if len(mb) == 7 else plain_loss)(torch, p, pol.offsets, pol.n_hidden_layers, pol.activation, *mb, **loss_kw)
+
+
+def ref_grad(torch, pol, b, idx, advn, dtype, **loss_kw):
+    """Autograd of the minibatch loss at pol's parameters in `dtype`: (gradient, [pg, VL, entropy, clip fraction]) under plain_loss,
+    (gradient, [.., KL], (v - v_old, l1, l2)) under ext_loss — the loss of a batch that carries logp_all."""
+    p = pol.params.detach().to(dtype).clone().requires_grad_(True)
+    out = _loss(torch, pol, p, minibatch(torch, pol, b, idx, advn, dtype), loss_kw)
+    out[0].backward()
+    terms = [float(o.detach()) for o in out[1:6]]
+    return (p.grad.detach(), terms) + tuple(out[6:])
+
+
+def ref_update(torch, pol, b, advn, perms, minibatches, dtype, adam=None, max_grad_norm=0, **loss_kw):
+    """ppo_torch's update loop in `dtype` from pol's parameters, with ONE torch.optim.Adam(**adam) (lr 3e-4 by default) over one
+    [epochs, n] perm or a list of them (consecutive calls): every perm row is torch.chunk'ed into `minibatches`, and gradients are
+    clipped with clip_grad_norm_ where max_grad_norm > 0.  Returns (parameters, Adam's state, the minibatches' mean KLs in order —
+    empty under plain_loss)."""
+    p = pol.params.detach().to(dtype).clone().requires_grad_(True)
+    opt = torch.optim.Adam([p], **(adam or {"lr": 3e-4}))
+    kls = []
+    for perm in perms if isinstance(perms, (list, tuple)) else [perms]:
+        for row in perm:
+            for idx in row.chunk(minibatches):
+                out = _loss(torch, pol, p, minibatch(torch, pol, b, idx, advn, dtype), loss_kw)
+                opt.zero_grad()
+                out[0].backward()
+                if max_grad_norm > 0:
+                    torch.nn.utils.clip_grad_norm_([p], max_grad_norm)
+                opt.step()
+                kls += [float(o.detach()) for o in out[5:6]]
+    return p.detach(), opt.state[p], kls
+
+
+def kl_adapt(coef, kls, target):
+    """RLlib's update_kl restated in numpy float32 on the last epoch's minibatch means, summed in chunk order."""
+    s = np.float32(0.0)
+    for k in kls:
+        s = np.float32(s + np.float32(k))
+    mean = np.float32(s / np.float32(len(kls)))
+    t = np.float32(target)
+    if mean > np.float32(2.0) * t:
+        return np.float32(np.float32(coef) * np.float32(1.5))
+    if mean < np.float32(0.5) * t:
+        return np.float32(np.float32(coef) * np.float32(0.5))
+    return np.float32(coef)
+
+
+def check_per_tensor(torch, pol, mine, ref64, ref32, what, verbose=False):
+    """Per packed tensor: max|mine - f64| <= 4 * max|torch f32 - f64| + 1e-6 * max|f64|; verbose prints each figure before it asserts."""
+    for k, (o, s) in pol.offsets.items():
+        n = int(np.prod(s))
+        g64 = ref64[o: o + n].double()
+        e_mine = float((mine[o: o + n].double() - g64).abs().max())
+        e_t32 = float((ref32[o: o + n].double() - g64).abs().max())
+        bound = 4 * e_t32 + 1e-6 * float(g64.abs().max())
+        if verbose:
+            print("%s %s: |mine - f64| %.3e  |torch f32 - f64| %.3e  bound %.3e" % (what, k, e_mine, e_t32, bound))
+        assert e_mine <= bound, (what, k, e_mine, e_t32, bound)
+
+
+def nan_fill(ppo, head=256):
+    """Fill the workspace past the advantage statistics with NaN bytes: every slot entry must be written before it is read."""
+    ppo.workspace[head:].fill_(0xFF)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# GAE and rollouts
+# ------------------------------------------------------------------------------------------------------------------------------------
+def torch_gae(torch, b, gamma=0.99, lam=0.95):
+    """train/ppo_torch.py's GAE loop, restated on the native rollout's buffers (rew / done as ppo_torch converts them)."""
+    rew, done, val = b["rew"].float(), b["done"].float(), b["val"]
+    K, n = rew.shape
+    adv = torch.zeros(n, device=rew.device)
+    advs, rets = [None] * K, [None] * K
+    nxt = b["last_val"]
+    for t in reversed(range(K)):
+        nonterm = 1.0 - done[t]
+        delta = rew[t] + gamma * nxt * nonterm - val[t]
+        adv = delta + gamma * lam * nonterm * adv
+        advs[t], rets[t] = adv, adv + val[t]
+        nxt = val[t]
+    return torch.stack(advs), torch.stack(rets)
+
+
+def stepwise_rollout(env, pol, K, seed, step0, uniforms=None):
+    """ssg_rollout_policy restated as K x {policy_act, step_tensor} plus the bootstrap value."""
+    import torch
+    rows = {k: [] for k in ("obs", "act", "logp", "val", "rew", "done", "flags")}
+    for k in range(K):
+        a, lp, v, x = env.policy_act(pol, seed=seed, step=step0 + k, uniforms=None if uniforms is None else uniforms[k])
+        rows["obs"].append(x); rows["act"].append(a); rows["logp"].append(lp); rows["val"].append(v)
+        _, r, d, f = env.step_tensor(a)
+        rows["rew"].append(r.clone()); rows["done"].append(d.clone()); rows["flags"].append(f.clone())
+    out = {k: torch.stack(v) for k, v in rows.items()}
+    out["last_val"] = env.policy_act(pol, seed=seed, step=step0 + K)[2]
+    return out
+
+
+def assert_same_rollout(torch, a, b, what):
+    for k in ("obs", "act", "logp", "val", "rew", "done", "flags", "last_val"):
+        assert a[k].dtype == b[k].dtype and torch.equal(a[k], b[k]), (what, k)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# synthetic batches: the dict rollout_policy returns, with controlled extremes
+# ------------------------------------------------------------------------------------------------------------------------------------
+def _synthetic_inputs(torch, pol, K, N, seed):
+    """What the two synthetic batches draw alike: obs f32 [K, N, D] with rows at the real scale (obs / 600), reset rows (obs = -1) and
+    ~5 % of rows scaled x50 (tanh saturates to exactly +-1 in f32), and the actions.  Returns (generator, its f64 uniforms, x, act)."""
+    D, A = pol.obs_dim, pol.n_actions
+    g = torch.Generator(device=DEV).manual_seed(seed)
+
+    def u(*shape):
+        return torch.rand(shape, generator=g, device=DEV, dtype=torch.float64)
+
+    obs = u(K, N, D) * 600.0
+    obs[u(K, N) < 0.1] = -1.0
+    x = (obs / pol.obs_scale).float()
+    x[u(K, N) < 0.05] *= 50.0
+    return g, u, x, (u(K, N) * A).long().clamp_(max=A - 1)
+
+
+def synthetic_batch(torch, pol, K, N, seed):
+    """logp_all_old = a perturbed copy of the current distribution, logp_old gathered from it (ratios clipped on both sides, ties
+    inside), val = the current value + U(-0.2, 0.2): every branch of the extended loss occurs."""
+    A = pol.n_actions
+    g, u, x, act = _synthetic_inputs(torch, pol, K, N, seed)
+    with torch.no_grad():
+        logits, v = forward(torch, pol.params.detach().double(), pol.offsets, pol.n_hidden_layers, pol.activation, x.double())
+        old = torch.log_softmax(torch.log_softmax(logits, -1) + 0.5 * torch.randn(logits.shape, generator=g, device=DEV, dtype=torch.float64), -1)
+    logp_all = torch.zeros((K, N, 4), device=DEV)
+    logp_all[..., :A] = old.float()
+    logp = logp_all.gather(-1, act.unsqueeze(-1)).squeeze(-1)
+    return dict(obs=x.contiguous(), act=act.to(torch.int32).contiguous(), logp=logp.contiguous(), logp_all=logp_all.contiguous(),
+                rew=torch.randn((K, N), generator=g, device=DEV, dtype=torch.float64), done=(u(K, N) < 0.05).to(torch.uint8),
+                val=(v + (u(K, N) - 0.5) * 0.4).float().contiguous(), last_val=torch.randn((N,), generator=g, device=DEV))
+
+
+def synthetic_batch_logp_noise(torch, pol, K, N, seed):
+    """logp_old = the current policy's logp + U(-0.4, 0.4) (ratios clipped on both sides, min() ties inside the range), val drawn from
+    N(0, 1), no logp_all: the plain loss's batch."""
+    g, u, x, act = _synthetic_inputs(torch, pol, K, N, seed)
+    logits, _ = forward(torch, pol.params.detach().double(), pol.offsets, pol.n_hidden_layers, pol.activation, x.double())
+    logp = (torch.log_softmax(logits, -1).gather(-1, act.unsqueeze(-1)).squeeze(-1) + (u(K, N) - 0.5) * 0.8).float()
+    return dict(obs=x.contiguous(), act=act.to(torch.int32).contiguous(), logp=logp.contiguous(),
+                rew=torch.randn((K, N), generator=g, device=DEV, dtype=torch.float64),
+                done=(u(K, N) < 0.05).to(torch.uint8), val=torch.randn((K, N), generator=g, device=DEV),
+                last_val=torch.randn((N,), generator=g, device=DEV))

@@ -12,19 +12,14 @@ import collections
 import numpy as np
 import pytest
 
+from gpu_support import torch_cuda  # noqa: F401
+
 import dyn_scenes as DS
 
 pytestmark = pytest.mark.gpu
 
 K = 40
 LAYOUTS = ((len(DS.RECORDS), True), (len(DS.RECORDS), False), (72, True), (72, False))
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch
 
 
 def _fingerprint(parts, mult):

@@ -2,13 +2,14 @@
 ship_sim_gym_amd/evaluate.py; train/evaluate_native.py): the symbols in the header and the binding, the ssg_eval record against ctypes,
 every refusal before any device work, eval_walk on an oracle trajectory, and the script's and evaluate()'s argument handling.  No GPU."""
 import ctypes as C
-import importlib.util
 import os
 import re
 import types
 
 import numpy as np
 import pytest
+
+from gpu_support import load_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EVAL_SYMBOLS = ("ssg_policy_act_greedy", "ssg_pop_act_greedy", "ssg_evaluate", "ssg_pop_evaluate", "ssg_eval_reduce", "ssg_eval_account")
@@ -272,15 +273,8 @@ def test_eval_walk_split_with_the_carry_gives_the_same_rows(trajectory):
 # ------------------------------------------------------------------------------------------------------------------------------------
 # the script and evaluate()'s arguments
 # ------------------------------------------------------------------------------------------------------------------------------------
-def _script():
-    spec = importlib.util.spec_from_file_location("evaluate_native_cpu", os.path.join(ROOT, "train", "evaluate_native.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_evaluate_script_parses_its_arguments():
-    mod = _script()
+    mod = load_script("train/evaluate_native.py")
     with pytest.raises(SystemExit) as ex:
         mod.parse_args(["--help"])
     assert ex.value.code == 0

@@ -10,29 +10,10 @@ import sys
 import numpy as np
 import pytest
 
-from helpers import actor_critic_policy as _shared_policy
-from split_helpers import split_policy as _split_policy
+from gpu_support import DEV, ROOT, env_config as _env_config, same_columns as _same_columns, torch_cuda  # noqa: F401
+from ppo_reference import actor_critic_policy as _shared_policy, split_policy as _split_policy
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch
-
-
-def _env_config(history=2, max_steps=1000):
-    from ship_sim_gym_amd.config import EnvConfig
-
-    class E(EnvConfig):
-        HISTORY_SIZE = history
-        MAX_STEPS = max_steps
-    return E
 
 
 def _vec(n, history=2, max_steps=1000, **kw):
@@ -51,17 +32,6 @@ def _constant_policy(torch, D, bias, H=16):
     z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=DEV)  # noqa: E731
     b = torch.tensor(bias, dtype=torch.float32, device=DEV)
     return NativePolicy([(z(H, D), z(H))], (z(len(bias), H), b), (z(1, H), z(1)), 600.0)
-
-
-def _columns(env):
-    from ship_sim_gym_amd import _native as N
-    return {name: env.field(getattr(N, name)).clone() for name in
-            ("F_X", "F_Y", "F_VX", "F_VY", "F_ANGLE", "F_W", "F_LIDAR", "F_RUDDER", "F_STEP_COUNT", "F_MAP_ID", "F_GOAL_MASK", "F_CUM_REWARD")}
-
-
-def _same_columns(torch, a, b):
-    ca, cb = _columns(a), _columns(b)
-    return all(torch.equal(ca[k], cb[k]) for k in ca)
 
 
 def _walk(r, E, carry=None):

@@ -18,6 +18,8 @@ import os
 import numpy as np
 import pytest
 
+from gpu_support import torch_cuda  # noqa: F401
+
 import event_scenes as ES
 
 pytestmark = pytest.mark.gpu
@@ -29,13 +31,6 @@ ROWS = ((1, 2, False, 5, 1), (8, 1, True, 6, 1), (8, 3, False, 5, 1), (10, 2, Tr
 LAYOUTS = (("64", False), ("128", False), ("256", False), ("64", True), ("128", True), ("256", True))
 K = ES.K
 _cache = {}
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch
 
 
 def _scenes(O, n_goals):

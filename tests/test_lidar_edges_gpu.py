@@ -16,6 +16,8 @@ import os
 import numpy as np
 import pytest
 
+from gpu_support import torch_cuda  # noqa: F401
+
 import lidar_scenes as LS
 
 pytestmark = pytest.mark.gpu
@@ -25,13 +27,6 @@ pytestmark = pytest.mark.gpu
 # six bank / workgroup layouts.
 ROWS = ((1, 2, False), (7, 1, False), (8, 1, True), (8, 2, False), (10, 1, False), (10, 2, True), (16, 1, False), (16, 2, False))
 LAYOUTS = (("64", False), ("128", False), ("256", False), ("64", True), ("128", True), ("256", True))
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch
 
 
 def _gpu_run(torch, native, lay, scenes, nb, hist, exact, blk, in_global):

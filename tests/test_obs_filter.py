@@ -3,12 +3,13 @@ entry points as header, binding and library see them, the workspace size, what s
 numpy restatement of the device's reduction against a two-pass long-double computation, the state_dict round trip and the trainers'
 flags.  Nothing here launches a kernel."""
 import ctypes as C
-import importlib.util
 import os
 import re
 
 import numpy as np
 import pytest
+
+from gpu_support import load_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -53
@@ -300,15 +301,8 @@ def test_state_dict_round_trip_and_normalise():
             ObsFilter(_Env(), **bad)
 
 
-def _script(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "train", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_trainer_flags(capsys):
-    ppo = _script("ppo_torch")
+    ppo = load_script("train/ppo_torch.py")
     a = ppo.parse_args(["--mode", "native"])
     assert a.obs_filter is False and a.save_obs_filter is None          # off by default
     a = ppo.parse_args(["--mode", "native", "--update", "native", "--obs-filter", "--save-obs-filter", "f.pt"])
@@ -321,7 +315,7 @@ def test_trainer_flags(capsys):
             ppo.train(envs=8, updates=1, mode=mode, obs_filter=True)     # (refused before any env is made)
     with pytest.raises(SystemExit):
         ppo.parse_args(["--mode", "native", "--save-obs-filter", "f.pt"])
-    pbt = _script("pbt_native")
+    pbt = load_script("train/pbt_native.py")
     assert pbt.parse_args([]).obs_filter is False and pbt.parse_args(["--obs-filter"]).obs_filter is True
-    ev = _script("evaluate_native")
+    ev = load_script("train/evaluate_native.py")
     assert ev.parse_args([]).obs_filter is None and ev.parse_args(["--obs-filter", "f.pt"]).obs_filter == "f.pt"

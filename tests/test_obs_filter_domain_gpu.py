@@ -17,22 +17,14 @@ finalise loop):
 import numpy as np
 import pytest
 
-from helpers import actor_critic_policy, assert_same_rollout
-from split_helpers import env_config, split_module
+from gpu_support import DEV, env_config, torch_cuda  # noqa: F401
+from ppo_reference import actor_critic_policy, assert_same_rollout, split_module
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 HIST_BEAMS = {7: (1, 1), 32: (2, 10), 33: (3, 5), 63: (7, 3), 64: (4, 10), 176: (8, 16)}
 TILE, RUNS = 256, 8
 KEYS = ("obs", "act", "logp", "val", "rew", "done", "flags")
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch
 
 
 def _vec(n, D, base=0):

@@ -17,23 +17,14 @@ import sys
 import numpy as np
 import pytest
 
-from helpers import actor_critic_policy, assert_same_rollout, stepwise_rollout
-from split_helpers import env_config, split_policy
+from gpu_support import DEV, ROOT, env_config, torch_cuda  # noqa: F401
+from ppo_reference import actor_critic_policy, assert_same_rollout, split_policy, stepwise_rollout
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
 HIST_BEAMS = {7: (1, 1), 28: (2, 8), 48: (3, 10)}
 SIZES = (1, 2, 255, 256, 257, 769)
 KEYS = ("obs", "act", "logp", "val", "rew", "done", "flags", "last_val")
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch
 
 
 def _vec(n, D, base=0, max_steps=None):

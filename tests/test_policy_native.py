@@ -1,7 +1,6 @@
 """CPU-side checks of the policy in the loop (ABI 9): the packed parameter layout include/shipsim.h documents, the module checks of
 NativePolicy.from_actor_critic, the ctypes record against the header, and the trainer's `native` mode.  No GPU needed."""
 import ctypes as C
-import importlib.util
 import os
 import re
 
@@ -10,14 +9,9 @@ import pytest
 import torch
 import torch.nn as nn
 
+from gpu_support import load_script
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _ppo_mod():
-    spec = importlib.util.spec_from_file_location("ppo_torch_cpu", os.path.join(ROOT, "train", "ppo_torch.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def _header():
@@ -67,7 +61,7 @@ def _numpy_forward(buf, D, H, L, A, act, x):
 
 def test_packing_is_torch_cat_of_the_actor_critic_parameters():
     from ship_sim_gym_amd.policy import NativePolicy, packed_offsets
-    mod = _ppo_mod()
+    mod = load_script("train/ppo_torch.py")
     torch.manual_seed(0)
     net = mod.ActorCritic(32, 3)
     pol = NativePolicy.from_actor_critic(net, torch.full((32,), 600.0, dtype=torch.float64))
@@ -175,7 +169,7 @@ def test_policy_entry_points_refuse_before_touching_a_device(native):
 
 
 def test_trainer_offers_native_mode():
-    mod = _ppo_mod()
+    mod = load_script("train/ppo_torch.py")
     ap = mod.make_arg_parser()
     assert ap.parse_args(["--mode", "native"]).mode == "native"
     for m in ("eager", "graph", "pingpong"):

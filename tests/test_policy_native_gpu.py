@@ -3,57 +3,21 @@ against torch on the env's real observations, its Philox uniforms, the fused rol
 invariance, the env stepping exactly as it does under rollout_tensor, the other handle kinds, argument errors, and ppo_torch's
 `native` mode against its eager mode."""
 import ctypes as C
-import importlib.util
-import os
 
 import numpy as np
 import pytest
 
-from helpers import actor_critic_policy as _policy, assert_same_rollout as _assert_same, stepwise_rollout as _stepwise
+from gpu_support import env_config as _env_config, load_script, same_columns as _same_columns, torch_sample as _torch_sample
+from gpu_support import torch_cuda  # noqa: F401
+from ppo_reference import actor_critic_policy as _policy, assert_same_rollout as _assert_same, stepwise_rollout as _stepwise
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch
 
 
 def _vec(n, **kw):
     from ship_sim_gym_amd.vec_env import ShipVecEnv
     kw.setdefault("n_maps", 64)
     return ShipVecEnv(n, **kw)
-
-
-def _env_config(history):
-    from ship_sim_gym_amd.config import EnvConfig
-
-    class E(EnvConfig):
-        HISTORY_SIZE = history
-    return E
-
-
-def _torch_sample(torch, logits, u):
-    """ppo_torch's Shard.step() sampling: log_softmax, cumsum(exp), count(u > cdf[:, :-1])."""
-    logp_all = torch.log_softmax(logits, dim=-1)
-    cdf = logp_all.exp().cumsum(dim=-1)
-    act = (u.unsqueeze(-1) > cdf[:, :-1]).sum(dim=-1)
-    return act, logp_all.gather(-1, act.unsqueeze(-1)).squeeze(-1), cdf
-
-
-def _columns(env):
-    from ship_sim_gym_amd import _native as N
-    return {name: env.field(getattr(N, name)).clone() for name in
-            ("F_X", "F_Y", "F_VX", "F_VY", "F_ANGLE", "F_W", "F_LIDAR", "F_RUDDER", "F_STEP_COUNT", "F_MAP_ID", "F_GOAL_MASK", "F_CUM_REWARD")}
-
-
-def _same_columns(torch, a, b):
-    ca, cb = _columns(a), _columns(b)
-    return all(torch.equal(ca[k], cb[k]) for k in ca)
 
 
 def test_forward_matches_torch_on_real_observations(torch_cuda):
@@ -304,16 +268,9 @@ def test_bad_arguments_raise_and_launch_nothing(torch_cuda):
         e.close()
 
 
-def _ppo_mod():
-    spec = importlib.util.spec_from_file_location("ppo_torch_native", os.path.join(ROOT, "train", "ppo_torch.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_ppo_native_mode_trains_and_matches_eager_rollouts(torch_cuda):
     torch = torch_cuda
-    mod = _ppo_mod()
+    mod = load_script("train/ppo_torch.py")
     n, H = 4096, 32
     hist, got = mod.train(envs=n, updates=3, horizon=H, log=lambda s: None, mode="native", return_details=True)
     assert len(hist) == 3 and all(np.isfinite(h[1]) and np.isfinite(h[3]) for h in hist)

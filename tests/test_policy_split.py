@@ -2,25 +2,19 @@
 record sizes, the workspace sizes for the longer packed row and their refusals of other flag bits, the packed layout against torch.cat
 of a separate-tower module, what from_actor_critic accepts and refuses, and the trainers' --separate-value option.  No GPU."""
 import ctypes as C
-import importlib.util
 import itertools
 import os
 import re
 
 import pytest
 
+from gpu_support import load_script
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _header():
     return open(os.path.join(ROOT, "include", "shipsim.h")).read()
-
-
-def _mod(name, rel):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, *rel))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def split_len(D, H, L, A):
@@ -145,7 +139,7 @@ def test_from_actor_critic_takes_the_separate_module_on_cpu(native, L, act):
     pol.refresh()
     assert torch.equal(pol.unpack()["V0"], net.vf_body[0].weight.detach()) and torch.equal(pol.unpack()["b0"], net.pi_body[0].bias.detach())
     # a shared module still gives the shared record
-    mod = _mod("ppo_torch_split_cpu", ("train", "ppo_torch.py"))
+    mod = load_script("train/ppo_torch.py")
     shared = NativePolicy.from_actor_critic(mod.ActorCritic(D, A, hidden=H), 2.0)
     assert not shared.separate_value and shared.to_native().activation == native.POLICY_TANH
 
@@ -182,7 +176,7 @@ def test_population_refuses_mixed_shapes():
     from ship_sim_gym_amd.policy import NativePolicy
     from ship_sim_gym_amd.population import NativePopulation
     D, H, A = 7, 16, 3
-    mod = _mod("ppo_torch_split_cpu2", ("train", "ppo_torch.py"))
+    mod = load_script("train/ppo_torch.py")
     split = NativePolicy.from_actor_critic(_towers(torch, D, H, 2, A), 2.0)
     shared = NativePolicy.from_actor_critic(mod.ActorCritic(D, A, hidden=H), 2.0)
     with pytest.raises(ValueError, match="member 1"):
@@ -194,7 +188,7 @@ def test_population_refuses_mixed_shapes():
 
 def test_trainers_offer_separate_value_and_keep_the_shared_module():
     import torch
-    mod = _mod("ppo_torch_split_cpu3", ("train", "ppo_torch.py"))
+    mod = load_script("train/ppo_torch.py")
     assert mod.parse_args([]).separate_value is False
     for m in ("eager", "graph", "pingpong", "native"):
         assert mod.parse_args(["--mode", m, "--separate-value"]).separate_value is True
@@ -214,5 +208,5 @@ def test_trainers_offer_separate_value_and_keep_the_shared_module():
     assert [n for n, _ in sep.named_children()] == ["pi_body", "pi", "vf_body", "v"]
     logits, value = sep(torch.zeros(5, 32))
     assert tuple(logits.shape) == (5, 3) and tuple(value.shape) == (5,)
-    pbt = _mod("pbt_native_split_cpu", ("train", "pbt_native.py"))
+    pbt = load_script("train/pbt_native.py")
     assert pbt.parse_args([]).separate_value is False and pbt.parse_args(["--separate-value"]).separate_value is True

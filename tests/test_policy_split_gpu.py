@@ -7,8 +7,8 @@ import ctypes as C
 
 import pytest
 
-from helpers import assert_same_rollout, stepwise_rollout
-from split_helpers import DEV, shared_over_pi_tower, split_policy, vec
+from gpu_support import DEV, torch_cuda, torch_sample as _torch_sample, vec  # noqa: F401
+from ppo_reference import assert_same_rollout, shared_over_pi_tower, split_policy, stepwise_rollout
 
 pytestmark = pytest.mark.gpu
 
@@ -17,13 +17,6 @@ pytestmark = pytest.mark.gpu
 CASES = [(64, 7, 16, 1, 2, "tanh"), (100, 22, 48, 2, 3, "relu"), (100, 7, 128, 2, 4, "tanh"), (64, 22, 16, 2, 4, "relu"),
          (100, 22, 128, 1, 3, "tanh"), (64, 7, 48, 1, 4, "relu"), (100, 7, 48, 2, 2, "tanh"), (64, 22, 128, 1, 2, "relu"),
          (100, 22, 16, 1, 3, "relu"), (100, 176, 128, 2, 3, "tanh")]
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch
 
 
 def _warm(env, steps=6):
@@ -67,13 +60,6 @@ def test_identical_towers_are_the_shared_policy_bitwise(torch_cuda, n, D, H, L, 
     assert bool((la_split[..., A:] == 0).all())
     a.close()
     b.close()
-
-
-def _torch_sample(torch, logits, u):
-    logp_all = torch.log_softmax(logits, dim=-1)
-    cdf = logp_all.exp().cumsum(dim=-1)
-    act = (u.unsqueeze(-1) > cdf[:, :-1]).sum(dim=-1)
-    return act, logp_all.gather(-1, act.unsqueeze(-1)).squeeze(-1), cdf
 
 
 @pytest.mark.parametrize("n,D,H,L,A,act", CASES)

@@ -1,25 +1,13 @@
 """GPU checks of the extended update for a population (ssg_pop_dist, ssg_pop_update_ext; PopulationPPO's vf_clip / max_grad_norm /
 kl_coef / kl_target).  The reference of every check is the single-policy path: member m's update is NativePPO's with that member's
 settings on a ``ShipVecEnv(n, n_maps=64, env_id_base=m*n)`` shard, and every comparison is torch.equal."""
-import importlib.util
-import os
-
 import pytest
 
-from helpers import actor_critic_policy
+from gpu_support import DEV, load_script, torch_cuda  # noqa: F401
+from population_harness import age, close_all, shard_rollouts, stacked_perms
+from ppo_reference import actor_critic_policy
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-ROLLOUT_KEYS = ("obs", "act", "logp", "val", "rew", "done", "flags")
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch
 
 
 def _vec(n, base=0):
@@ -29,10 +17,6 @@ def _vec(n, base=0):
 
 def _members(torch, D, P, seed=100):
     return [actor_critic_policy(torch, D, seed=seed + m)[1] for m in range(P)]
-
-
-def _cols(t, m, n):
-    return t[:, m * n:(m + 1) * n]
 
 
 # P = 3: the reference's RLlib loss, PPO2's loss with its own clip range, and a member with everything off
@@ -45,45 +29,11 @@ def setup(torch_cuda):
     """One population rollout and the P shard rollouts (asserted equal); then, in both, the acting policy is made an older one:
     the same noise on the log-distribution and on the value prediction."""
     torch = torch_cuda
-    from ship_sim_gym_amd.population import NativePopulation, PopulationPPO
-    from ship_sim_gym_amd.ppo import NativePPO
-    env = _vec(P * N_ENVS)
-    D = env.states_history
-    pop, refs = NativePopulation(_members(torch, D, P)), _members(torch, D, P)
-    env.reset_tensor()
-    b = dict(env.rollout_population(pop, K, seed=7))
-    ppo = PopulationPPO(pop, env)
-    la = ppo.dist(b).clone()
-    g = torch.Generator(device=DEV).manual_seed(3)
-    A = pop.n_actions
-    noise = 0.3 * torch.randn((K, P * N_ENVS, A), generator=g, device=DEV)
-    vnoise = (torch.rand((K, P * N_ENVS), generator=g, device=DEV) - 0.5) * 0.4
-    shards, sbs = [], []
-    for m in range(P):
-        sh = _vec(N_ENVS, base=m * N_ENVS)
-        sh.reset_tensor()
-        sb = dict(sh.rollout_policy(refs[m], K, seed=7))
-        for k in ROLLOUT_KEYS:
-            assert torch.equal(_cols(b[k], m, N_ENVS), sb[k]), (m, k)
-        # ssg_pop_dist's rows are ssg_ppo_dist's per member, and both reproduce the rollout's logp
-        sla = NativePPO(refs[m], sh).dist(sb)
-        assert torch.equal(_cols(la, m, N_ENVS), sla), m
-        assert torch.equal(sla.gather(-1, sb["act"].long().unsqueeze(-1)).squeeze(-1), sb["logp"]), m
-        shards.append(sh)
-        sbs.append(sb)
-    assert bool((la[..., A:] == 0).all())
-    old = torch.zeros_like(la)
-    old[..., :A] = torch.log_softmax(la[..., :A] + noise, -1)
-    b["logp_all"] = old
-    b["logp"] = old.gather(-1, b["act"].long().unsqueeze(-1)).squeeze(-1).contiguous()
-    b["val"] = (b["val"] + vnoise).contiguous()
-    for m in range(P):
-        for k in ("logp_all", "logp", "val"):
-            sbs[m][k] = _cols(b[k], m, N_ENVS).contiguous()
+    sizes = [N_ENVS] * P
+    env, pop, b, shards, refs, sbs = shard_rollouts(torch, _vec, lambda D: _members(torch, D, P), sizes, K, 7)
+    age(torch, b, sbs, sizes, pop.n_actions, b["logp_all"], torch.Generator(device=DEV).manual_seed(3), False)
     yield env, pop, b, shards, refs, sbs
-    env.close()
-    for sh in shards:
-        sh.close()
+    close_all(env, shards)
 
 
 def test_population_ext_update_is_bitwise_each_members_own(torch_cuda, setup):
@@ -104,7 +54,7 @@ def test_population_ext_update_is_bitwise_each_members_own(torch_cuda, setup):
         ref_ppos.append(ref)
     assert [r.extended() for r in ref_ppos] == [True, True, False]        # member 2 runs the PLAIN entry points
     for round_ in range(2):                                                # the second update continues the first
-        perm = torch.stack([torch.stack([torch.randperm(samples, device=DEV, generator=g) for _ in range(2)]) for _ in range(P)])
+        perm = stacked_perms(torch, g, P, 2, samples)
         st = ppo.update(b, perm, 2, 2, stats=True)
         assert st.shape == (P, 4, 8) and bool(torch.isfinite(st).all())
         for m in range(P):
@@ -138,7 +88,7 @@ def test_population_ext_update_at_uneven_chunkings_is_bitwise_each_members_own(t
         ppo = PopulationPPO(pop, env, lr=lrs, **EXT)
         ppo.gae(b)
         g = torch.Generator(device=DEV).manual_seed(minibatches)
-        perm = torch.stack([torch.stack([torch.randperm(samples, device=DEV, generator=g) for _ in range(epochs)]) for _ in range(P)])
+        perm = stacked_perms(torch, g, P, epochs, samples)
         st = ppo.update(b, perm, epochs, minibatches, stats=True)
         assert st.shape == (P, epochs * chunks, 8) and bool(torch.isfinite(st).all()) and ppo.step == epochs * chunks
         for m in range(P):
@@ -173,9 +123,7 @@ def test_exploit_carries_the_coefficient(torch_cuda):
 
 def test_pbt_trainer_with_the_references_loss_terms(torch_cuda):
     torch = torch_cuda
-    spec = importlib.util.spec_from_file_location("pbt_native_ext_gpu", os.path.join(ROOT, "train", "pbt_native.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    mod = load_script("train/pbt_native.py")
     hist, det = mod.train(members=4, envs_per_member=64, updates=2, perturb_every=1, seed=0, log=lambda s: None, return_details=True,
                           kl_coeff=1.0, max_grad_norm=0.5)
     assert len(hist) == 2 and det["params"].shape[0] == 4 and bool(torch.isfinite(det["params"]).all())

@@ -2,38 +2,14 @@
 the single-policy path as it stands: member m's parameters are NativePolicy row m, its envs a ``ShipVecEnv(n, n_maps=64,
 env_id_base=m*n)`` shard (train/ppo_torch.py's make_shards relies on such shards reproducing the unsplit batch), its update NativePPO's.
 Every comparison is torch.equal: per member the population's launches run the single path's operations in the single path's order."""
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 
-from helpers import actor_critic_policy
+from gpu_support import DEV, env_config as _env_config, load_script, state_columns as _columns, torch_cuda  # noqa: F401
+from population_harness import ROLLOUT_KEYS, close_all as _close, cols, member_hparams, shard_reference, shard_rollouts, stacked_perms
+from ppo_reference import actor_critic_policy
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-ROLLOUT_KEYS = ("obs", "act", "logp", "val", "rew", "done", "flags")
-STATE_COLUMNS = ("F_X", "F_Y", "F_VX", "F_VY", "F_ANGLE", "F_W", "F_LIDAR", "F_RUDDER", "F_STEP_COUNT", "F_MAP_ID", "F_GOAL_MASK",
-                 "F_CUM_REWARD")  # train/ppo_torch.py's env_columns()
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch
-
-
-def _env_config(history=2, max_steps=None):
-    from ship_sim_gym_amd.config import EnvConfig
-
-    class E(EnvConfig):
-        HISTORY_SIZE = history
-    if max_steps is not None:
-        E.MAX_STEPS = max_steps
-    return E
 
 
 def _vec(n, base=0, **kw):
@@ -51,15 +27,6 @@ def _population(torch, D, P, seed=100):
     return NativePopulation(_members(torch, D, P, seed))
 
 
-def _columns(env):
-    from ship_sim_gym_amd import _native as N
-    return {name: env.field(getattr(N, name)).clone() for name in STATE_COLUMNS}
-
-
-def _cols(t, m, n):
-    return t[..., m * n:(m + 1) * n] if t.dim() != 3 else t[:, m * n:(m + 1) * n]
-
-
 def _check_rollout(torch, P, n, K, philox, env_kw=None, seed=5, step0=3):
     """One population rollout against P shard rollouts; returns the number of env-steps compared."""
     env_kw = dict(env_kw or {})
@@ -72,18 +39,18 @@ def _check_rollout(torch, P, n, K, philox, env_kw=None, seed=5, step0=3):
     U = None if philox else torch.rand((K, P * n), generator=g, device=DEV)
     env.reset_tensor()
     b = env.rollout_population(pop, K, seed=seed, step0=step0, uniforms=U)
-    cols = _columns(env)
+    state = _columns(env)
     final_obs = env.obs.clone()
     for m in range(P):
         sh = _vec(n, base=m * n, **env_kw)
         sh.reset_tensor()
         r = sh.rollout_policy(pop.member(m), K, seed=seed, step0=step0, uniforms=None if philox else U[:, m * n:(m + 1) * n].contiguous())
         for k in ROLLOUT_KEYS:
-            assert b[k].dtype == r[k].dtype and torch.equal(_cols(b[k], m, n), r[k]), (P, n, m, k)
+            assert b[k].dtype == r[k].dtype and torch.equal(cols(b[k], m, [n] * P), r[k]), (P, n, m, k)
         assert torch.equal(b["last_val"][m * n:(m + 1) * n], r["last_val"]), (P, n, m, "last_val")
         assert torch.equal(final_obs[m * n:(m + 1) * n], sh.obs), (P, n, m, "final obs")
         for name, col in _columns(sh).items():
-            assert torch.equal(cols[name][..., m * n:(m + 1) * n], col), (P, n, m, name)
+            assert torch.equal(state[name][..., m * n:(m + 1) * n], col), (P, n, m, name)
         sh.close()
     if P == 1:  # the same handle, the single-policy call
         env.reset_tensor()
@@ -107,7 +74,7 @@ def test_rollout_with_traffic_ships(torch_cuda):
 
 
 def test_rollout_with_three_frames_of_history(torch_cuda):
-    _check_rollout(torch_cuda, 3, 77, 8, True, env_kw={"env_config": _env_config(history=3)})
+    _check_rollout(torch_cuda, 3, 77, 8, True, env_kw={"env_config": _env_config(3)})
 
 
 def test_rollout_refuses_bad_populations(torch_cuda):
@@ -127,36 +94,17 @@ def test_rollout_refuses_bad_populations(torch_cuda):
 def _batches(torch, P, n, K, seed=7):
     """(env, pop, batch, shard envs, reference policies, shard batches): one population rollout and the P shard rollouts (asserted
     equal), then the same forced dones (terminations mid-rollout) and the same older-policy logp (ratios clipped on both sides) in both."""
-    env = _vec(P * n)
-    D = env.states_history
-    pop, refs = _population(torch, D, P), _members(torch, D, P)
-    env.reset_tensor()
-    b = dict(env.rollout_population(pop, K, seed=seed))
+    env, pop, b, shards, refs, sbs = shard_rollouts(torch, _vec, lambda D: _members(torch, D, P), [n] * P, K, seed)
     g = torch.Generator(device=DEV).manual_seed(P + n + K)
     forced = torch.rand(b["done"].shape, generator=g, device=DEV) < 0.05
     noise = (torch.rand(b["logp"].shape, generator=g, device=DEV) - 0.5) * 0.8
-    shards, sbs = [], []
-    for m in range(P):
-        sh = _vec(n, base=m * n)
-        sh.reset_tensor()
-        sb = dict(sh.rollout_policy(refs[m], K, seed=seed))
-        for k in ROLLOUT_KEYS:
-            assert torch.equal(_cols(b[k], m, n), sb[k]), (m, k)
-        assert torch.equal(b["last_val"][m * n:(m + 1) * n], sb["last_val"])
+    for m, sb in enumerate(sbs):
         sb["done"] = (sb["done"] | forced[:, m * n:(m + 1) * n]).to(torch.uint8).contiguous()
         sb["logp"] = (sb["logp"] + noise[:, m * n:(m + 1) * n]).contiguous()
-        shards.append(sh)
-        sbs.append(sb)
     b["done"] = (b["done"] | forced).to(torch.uint8).contiguous()
     b["logp"] = (b["logp"] + noise).contiguous()
     assert int(b["done"].sum()) > 0
     return env, pop, b, shards, refs, sbs
-
-
-def _close(env, shards):
-    env.close()
-    for sh in shards:
-        sh.close()
 
 
 @pytest.mark.parametrize("P,n,K", [(3, 1000, 10), (5, 77, 8), (16, 4096, 8)])
@@ -180,26 +128,20 @@ def test_gae_is_bitwise_each_members_own(torch_cuda, P, n, K):
 
 
 def _check_update(torch, P, n, K, epochs, minibatch_counts):
-    from ship_sim_gym_amd.ppo import NativePPO, chunk_split
+    from ship_sim_gym_amd.ppo import chunk_split
     from ship_sim_gym_amd.population import PopulationPPO
     env, pop, b, shards, refs, sbs = _batches(torch, P, n, K)
-    hp = {"lr": [1e-3 / (1 + m) for m in range(P)], "clip": [0.1 + 0.05 * (m % 5) for m in range(P)],
-          "ent_coef": [0.0 + 0.005 * (m % 4) for m in range(P)], "beta1": [0.3 if m == 1 else 0.9 - 0.02 * (m % 3) for m in range(P)],
-          "lam": [0.9 + 0.02 * (m % 5) for m in range(P)]}
+    hp = member_hparams(P)
     assert P < 2 or (hp["beta1"][1] <= 0.5 < hp["beta1"][0])               # both of lerp's branches run
     ppo = PopulationPPO(pop, env, **hp)
     ppo.gae(b)
-    ref_ppos = []
-    for m in range(P):
-        ref = NativePPO(refs[m], shards[m], lr=hp["lr"][m], betas=(hp["beta1"][m], 0.999), clip=hp["clip"][m], ent_coef=hp["ent_coef"][m])
-        ref.gae(sbs[m], 0.99, hp["lam"][m])
-        ref_ppos.append(ref)
+    ref_ppos = [shard_reference(torch, m, hp, {}, refs, shards, sbs) for m in range(P)]
     samples = K * n
     g = torch.Generator(device=DEV).manual_seed(11)
     p0 = pop.params.clone()
     for i, mb in enumerate(minibatch_counts):
         chunk, n_chunks = chunk_split(samples, mb)
-        perm = torch.stack([torch.stack([torch.randperm(samples, device=DEV, generator=g) for _ in range(epochs)]) for _ in range(P)])
+        perm = stacked_perms(torch, g, P, epochs, samples)
         step_before = ppo.step
         st = ppo.update(b, perm, epochs, mb, stats=True)
         assert st.shape == (P, epochs * n_chunks, 4) and bool(torch.isfinite(st).all())
@@ -282,7 +224,7 @@ def test_episode_stats_match_a_forward_walk_and_the_handles_counters(torch_cuda)
     torch = torch_cuda
     from ship_sim_gym_amd.population import PopulationPPO
     P, n, K = 4, 250, 64
-    env = _vec(P * n, env_config=_env_config(max_steps=40))               # K > max_steps: every env ends an episode per rollout
+    env = _vec(P * n, env_config=_env_config(2, max_steps=40))               # K > max_steps: every env ends an episode per rollout
     pop = _population(torch, env.states_history, P)
     ppo = PopulationPPO(pop, env)
     env.reset_tensor()
@@ -313,16 +255,9 @@ def test_episode_stats_match_a_forward_walk_and_the_handles_counters(torch_cuda)
     env.close()
 
 
-def _pbt_mod():
-    spec = importlib.util.spec_from_file_location("pbt_native_gpu", os.path.join(ROOT, "train", "pbt_native.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_pbt_trainer_runs_exploits_and_is_reproducible(torch_cuda):
     torch = torch_cuda
-    mod = _pbt_mod()
+    mod = load_script("train/pbt_native.py")
     lines = []
     kw = dict(members=4, envs_per_member=512, updates=3, perturb_every=1, seed=0, return_details=True)
     hist, det = mod.train(log=lines.append, **kw)

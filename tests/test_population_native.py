@@ -2,7 +2,6 @@
 symbols in the header and the binding, the record against ctypes, the refusals before any device work, the workspace size, the host
 table against the single-policy roundings, the PBT scheduler's semantics, and the trainer's argument parsing.  No GPU."""
 import ctypes as C
-import importlib.util
 import math
 import os
 import re
@@ -10,6 +9,8 @@ import struct
 import sys
 
 import pytest
+
+from gpu_support import load_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 POP_SYMBOLS = ("ssg_pop_act", "ssg_pop_rollout", "ssg_pop_pack_hparams", "ssg_pop_workspace_nbytes", "ssg_pop_gae", "ssg_pop_update",
@@ -331,16 +332,9 @@ def test_scheduler_module_imports_without_torch_or_ray():
     assert out.stdout.strip() == "[3, 1, 2, 3]"
 
 
-def _pbt_mod():
-    spec = importlib.util.spec_from_file_location("pbt_native_cpu", os.path.join(ROOT, "train", "pbt_native.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_pbt_trainer_parses_its_arguments_and_imports_without_ray(monkeypatch):
     monkeypatch.setitem(sys.modules, "ray", None)                           # import ray -> ImportError
-    mod = _pbt_mod()
+    mod = load_script("train/pbt_native.py")
     a = mod.parse_args([])
     assert (a.members, a.envs_per_member, a.horizon, a.perturb_every, a.seed, a.pbt, a.lrs) == (16, 512, 32, 5, 0, True, None)
     a = mod.parse_args(["--members", "4", "--envs-per-member", "512", "--updates", "3", "--horizon", "16", "--perturb-every", "1",

@@ -2,12 +2,13 @@
 mutations, train/pbt_native.py's flags).  The schedule table is checked against a Python restatement built on ppo.chunk_split — the
 chunking NativePPO.update documents — so a record here is exactly the minibatch the single-policy loop would run at that step."""
 import ctypes as C
-import importlib.util
 import os
 import struct
 import sys
 
 import pytest
+
+from gpu_support import load_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -244,16 +245,9 @@ def test_schedule_mutations_are_seed_deterministic():
 # ------------------------------------------------------------------------------------------------------------------------------------
 # the trainer's arguments
 # ------------------------------------------------------------------------------------------------------------------------------------
-def _pbt_mod():
-    spec = importlib.util.spec_from_file_location("pbt_native_sched_cpu", os.path.join(ROOT, "train", "pbt_native.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_trainer_parses_schedule_flags_lists_and_clamps(monkeypatch):
     monkeypatch.setitem(sys.modules, "ray", None)
-    mod = _pbt_mod()
+    mod = load_script("train/pbt_native.py")
     a = mod.parse_args([])
     assert (a.epochs, a.minibatches, a.mutate_schedule, a.max_epochs, a.members) == (2, 4, False, 30, 16)    # the defaults stay ints
     a = mod.parse_args(["--epochs", "3", "--minibatches", "8"])

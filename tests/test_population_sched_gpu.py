@@ -5,29 +5,19 @@ member's settings and Adam step count, and every comparison is torch.equal — p
 The idiom is tests/test_population_gpu.py's and tests/test_population_split_gpu.py's: one population rollout and the P shard rollouts
 asserted equal, then the same forced dones and the same older acting policy (noise on its log-distribution and value) in both."""
 import ctypes as C
-import importlib.util
 import math
-import os
 
 import pytest
 
-from helpers import actor_critic_policy
-from split_helpers import split_policy
-from split_helpers import vec as split_vec
+from gpu_support import DEV, load_script, vec as split_vec
+from gpu_support import torch_cuda  # noqa: F401
+from population_harness import age, cached, member_hparams as _hp, shard_reference as _reference, shard_rollouts, stacked_perms as _perm
+from population_harness import close_cached  # noqa: F401
+from ppo_reference import actor_critic_policy, split_policy
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-ROLLOUT_KEYS = ("obs", "act", "logp", "val", "rew", "done", "flags")
 SPLIT_SHAPE = (22, 48, 2, 3, "tanh")  # D, H, layers, A, activation of the separate-value population
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch
 
 
 def _vec(n, base=0, split=False):
@@ -44,79 +34,15 @@ def _members(torch, D, P, split, seed=100):
     return [actor_critic_policy(torch, D, seed=seed + m)[1] for m in range(P)]
 
 
-_SETUPS = {}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _close_cached():
-    yield
-    for env, pop, b, shards, refs, sbs in _SETUPS.values():
-        env.close()
-        for sh in shards:
-            sh.close()
-    _SETUPS.clear()
-
-
 def _setup(torch, P, n, K, split=False):
     """(env, pop, batch, shard envs, reference policies, shard batches), computed once per shape and left unchanged: every test works
     on copies of the dicts and restores the parameters."""
-    key = (P, n, K, split)
-    if key in _SETUPS:
-        return _SETUPS[key]
-    from ship_sim_gym_amd.population import NativePopulation, PopulationPPO
-    env = _vec(P * n, split=split)
-    D = env.states_history
-    pop, refs = NativePopulation(_members(torch, D, P, split)), _members(torch, D, P, split)
-    A = pop.n_actions
-    env.reset_tensor()
-    b = dict(env.rollout_population(pop, K, seed=7))
-    la = PopulationPPO(pop, env).dist(b).clone()
-    g = torch.Generator(device=DEV).manual_seed(P * 1000 + n + K)
-    noise = 0.3 * torch.randn((K, P * n, A), generator=g, device=DEV)
-    vnoise = (torch.rand((K, P * n), generator=g, device=DEV) - 0.5) * 0.4
-    forced = torch.rand((K, P * n), generator=g, device=DEV) < 0.05
-    shards, sbs = [], []
-    for m in range(P):
-        sh = _vec(n, base=m * n, split=split)
-        sh.reset_tensor()
-        sb = dict(sh.rollout_policy(refs[m], K, seed=7))
-        for k in ROLLOUT_KEYS:
-            assert b[k].dtype == sb[k].dtype and torch.equal(b[k][:, m * n:(m + 1) * n], sb[k]), (m, k)
-        assert torch.equal(b["last_val"][m * n:(m + 1) * n], sb["last_val"]), m
-        shards.append(sh)
-        sbs.append(sb)
-    assert not torch.equal(b["val"][0, :n], b["val"][0, n:2 * n])                  # the members really differ
-    old = torch.zeros_like(la)
-    old[..., :A] = torch.log_softmax(la[..., :A] + noise, -1)
-    b["logp_all"] = old
-    b["logp"] = old.gather(-1, b["act"].long().unsqueeze(-1)).squeeze(-1).contiguous()
-    b["val"] = (b["val"] + vnoise).contiguous()
-    b["done"] = (b["done"] | forced).to(torch.uint8).contiguous()
-    assert int(forced.sum()) > 0
-    for m in range(P):
-        for k in ("logp_all", "logp", "val", "done"):
-            sbs[m][k] = b[k][:, m * n:(m + 1) * n].contiguous()
-    _SETUPS[key] = (env, pop, b, shards, refs, sbs)
-    return _SETUPS[key]
-
-
-def _hp(P):
-    """Per-member loss / Adam constants; member 1's beta1 takes lerp's other branch."""
-    return {"lr": [1e-3 / (1 + m) for m in range(P)], "clip": [0.1 + 0.05 * (m % 5) for m in range(P)],
-            "ent_coef": [0.005 * (m % 4) for m in range(P)], "beta1": [0.3 if m == 1 else 0.9 - 0.02 * (m % 3) for m in range(P)],
-            "lam": [0.9 + 0.02 * (m % 5) for m in range(P)]}
-
-
-def _reference(torch, m, hp, ext, refs, shards, sbs):
-    from ship_sim_gym_amd.ppo import NativePPO
-    ref = NativePPO(refs[m], shards[m], lr=hp["lr"][m], betas=(hp["beta1"][m], 0.999), clip=hp["clip"][m], ent_coef=hp["ent_coef"][m],
-                    **{k: v[m] for k, v in ext.items()})
-    ref.gae(sbs[m], 0.99, hp["lam"][m])
-    return ref
-
-
-def _perm(torch, g, P, rows, samples):
-    return torch.stack([torch.stack([torch.randperm(samples, device=DEV, generator=g) for _ in range(rows)]) for _ in range(P)])
+    def make():
+        setup = shard_rollouts(torch, lambda n, base: _vec(n, base, split), lambda D: _members(torch, D, P, split), [n] * P, K, 7)
+        env, pop, b, shards, refs, sbs = setup
+        age(torch, b, sbs, [n] * P, pop.n_actions, b["logp_all"], torch.Generator(device=DEV).manual_seed(P * 1000 + n + K), True)
+        return setup
+    return cached((P, n, K, split), make)
 
 
 def _expected_steps(samples, epochs, minibatches):
@@ -365,16 +291,9 @@ def test_update_sched_refuses_bad_arguments(torch_cuda):
     assert ext_table is not None
 
 
-def _pbt_mod():
-    spec = importlib.util.spec_from_file_location("pbt_native_sched_gpu", os.path.join(ROOT, "train", "pbt_native.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_trainer_mutates_and_exploits_schedules_reproducibly(torch_cuda):
     torch = torch_cuda
-    mod = _pbt_mod()
+    mod = load_script("train/pbt_native.py")
     lines = []
     kw = dict(members=4, envs_per_member=64, horizon=8, updates=4, perturb_every=2, mutate_schedule=True, seed=0, return_details=True)
     hist, det = mod.train(log=lines.append, **kw)

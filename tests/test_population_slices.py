@@ -2,7 +2,6 @@
 ssg_pop_pack_schedule_samples, population.slices_for_batch_sizes, the train_batch_size mutation and train/pbt_native.py's flags.  The
 schedule table is checked against a Python restatement built on ppo.chunk_split, member by member with the member's OWN sample count."""
 import ctypes as C
-import importlib.util
 import os
 import random
 import struct
@@ -10,14 +9,9 @@ from fractions import Fraction
 
 import pytest
 
+from gpu_support import load_script
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _pbt_mod():
-    spec = importlib.util.spec_from_file_location("pbt_native_slices", os.path.join(ROOT, "train", "pbt_native.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -274,7 +268,7 @@ def test_reference_mutations_carry_train_batch_size_on_request():
 # train/pbt_native.py
 # ------------------------------------------------------------------------------------------------------------------------------------
 def test_pbt_trainer_parses_the_batch_flags():
-    mod = _pbt_mod()
+    mod = load_script("train/pbt_native.py")
     a = mod.parse_args([])
     assert (a.mutate_batch, a.batch_shares, a.envs, a.quantum) == (False, None, None, None)
     a = mod.parse_args(["--members", "4", "--envs", "256", "--mutate-batch", "--mutate-schedule"])
@@ -293,7 +287,7 @@ def test_pbt_trainer_parses_the_batch_flags():
 
 
 def test_clamp_schedule_uses_the_members_own_samples():
-    mod = _pbt_mod()
+    mod = load_script("train/pbt_native.py")
     from ship_sim_gym_amd.population import slices_for_batch_sizes
     slices = slices_for_batch_sizes([10000, 20000, 40000, 10000], 256, 16)   # 48, 64, 112, 32 envs
     assert slices == [48, 64, 112, 32]

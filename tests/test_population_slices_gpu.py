@@ -6,30 +6,21 @@ m is ``NativePolicy`` / ``NativePPO`` on a ``ShipVecEnv(n_m, n_maps=64, env_id_b
 The base layout is P = 4 with (1, 63, 64, 257) envs and K = 5: a one-env member, slices below and exactly at the policy tile of 64,
 one that crosses a 256-env GAE block, and member bases 1, 64 and 128 (an unaligned and two aligned ones)."""
 import ctypes as C
-import importlib.util
-import os
 
 import numpy as np
 import pytest
 
-from helpers import actor_critic_policy
-from split_helpers import split_policy
-from split_helpers import vec as split_vec
+from gpu_support import DEV, load_script, vec as split_vec
+from gpu_support import torch_cuda  # noqa: F401
+from population_harness import ROLLOUT_KEYS, age, cached, member_hparams as _hp, perms_per_member as _perms, shard_reference as _reference, \
+    shard_rollouts, stacked_perms
+from population_harness import close_cached  # noqa: F401
+from ppo_reference import actor_critic_policy, split_policy
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-ROLLOUT_KEYS = ("obs", "act", "logp", "val", "rew", "done", "flags")
 SPLIT_SHAPE = (22, 48, 2, 3, "tanh")  # D, H, layers, A, activation of the separate-value population
 SIZES, K = (1, 63, 64, 257), 5
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch
 
 
 def _offsets(sizes):
@@ -50,87 +41,24 @@ def _members(torch, D, P, split, seed=100):
     return [actor_critic_policy(torch, D, seed=seed + m)[1] for m in range(P)]
 
 
-_SETUPS = {}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _close_cached():
-    yield
-    for env, pop, b, shards, refs, sbs in _SETUPS.values():
-        env.close()
-        for sh in shards:
-            sh.close()
-    _SETUPS.clear()
-
-
 def _setup(torch, sizes, K, split=False):
     """(env with `sizes` bound, pop, batch, shard envs, reference policies, shard batches), computed once per shape and left unchanged.
     The rollout — every ROLLOUT_KEYS column slice and last_val — is asserted equal to the shards' here; then the same forced dones and
     the same older acting policy (noise on its log-distribution and value) go into both."""
-    key = (tuple(sizes), K, split)
-    if key in _SETUPS:
-        return _SETUPS[key]
-    from ship_sim_gym_amd.population import NativePopulation, PopulationPPO
-    P, N, offs = len(sizes), sum(sizes), _offsets(sizes)
-    env = _vec(N, split=split)
-    env.set_population_slices(sizes)
-    assert env.population_slices == list(sizes)
-    D = env.states_history
-    pop, refs = NativePopulation(_members(torch, D, P, split)), _members(torch, D, P, split)
-    A = pop.n_actions
-    env.reset_tensor()
-    b = dict(env.rollout_population(pop, K, seed=7))
-    ppo = PopulationPPO(pop, env)
-    assert ppo.member_envs == list(sizes)
-    la = ppo.dist(b).clone()
-    assert torch.equal(la.gather(-1, b["act"].long().unsqueeze(-1)).squeeze(-1), b["logp"])     # ssg_pop_dist on the slices
-    g = torch.Generator(device=DEV).manual_seed(P * 1000 + N + K)
-    noise = 0.3 * torch.randn((K, N, A), generator=g, device=DEV)
-    vnoise = (torch.rand((K, N), generator=g, device=DEV) - 0.5) * 0.4
-    forced = torch.rand((K, N), generator=g, device=DEV) < 0.05
-    shards, sbs = [], []
-    for m, (o, n) in enumerate(zip(offs, sizes)):
-        sh = _vec(n, base=o, split=split)
-        sh.reset_tensor()
-        sb = dict(sh.rollout_policy(refs[m], K, seed=7))
-        for k in ROLLOUT_KEYS:
-            assert b[k].dtype == sb[k].dtype and torch.equal(b[k][:, o:o + n], sb[k]), (m, k)
-        assert torch.equal(b["last_val"][o:o + n], sb["last_val"]), m
-        assert torch.equal(env.obs[o:o + n], sh.obs), m
-        shards.append(sh)
-        sbs.append(sb)
-    old = torch.zeros_like(la)
-    old[..., :A] = torch.log_softmax(la[..., :A] + noise, -1)
-    b["logp_all"] = old
-    b["logp"] = old.gather(-1, b["act"].long().unsqueeze(-1)).squeeze(-1).contiguous()
-    b["val"] = (b["val"] + vnoise).contiguous()
-    b["done"] = (b["done"] | forced).to(torch.uint8).contiguous()
-    assert int(forced.sum()) > 0
-    for m, (o, n) in enumerate(zip(offs, sizes)):
-        for k in ("logp_all", "logp", "val", "done"):
-            sbs[m][k] = b[k][:, o:o + n].contiguous()
-    _SETUPS[key] = (env, pop, b, shards, refs, sbs)
-    return _SETUPS[key]
+    def make_env(n, base):
+        env = _vec(n, base, split)
+        if n == sum(sizes):                                                 # the population's handle
+            env.set_population_slices(sizes)
+            assert env.population_slices == list(sizes)
+        return env
 
-
-def _hp(P):
-    """Per-member loss / Adam constants; member 1's beta1 takes lerp's other branch."""
-    return {"lr": [1e-3 / (1 + m) for m in range(P)], "clip": [0.1 + 0.05 * (m % 5) for m in range(P)],
-            "ent_coef": [0.005 * (m % 4) for m in range(P)], "beta1": [0.3 if m == 1 else 0.9 - 0.02 * (m % 3) for m in range(P)],
-            "lam": [0.9 + 0.02 * (m % 5) for m in range(P)]}
-
-
-def _reference(torch, m, hp, ext, refs, shards, sbs):
-    from ship_sim_gym_amd.ppo import NativePPO
-    ref = NativePPO(refs[m], shards[m], lr=hp["lr"][m], betas=(hp["beta1"][m], 0.999), clip=hp["clip"][m], ent_coef=hp["ent_coef"][m],
-                    **{k: v[m] for k, v in ext.items()})
-    ref.gae(sbs[m], 0.99, hp["lam"][m])
-    return ref
-
-
-def _perms(torch, g, rows, samples):
-    """A list of P tensors [rows, K*n_m]: member m's own permutations."""
-    return [torch.stack([torch.randperm(s, device=DEV, generator=g) for _ in range(rows)]) for s in samples]
+    def make():
+        P, N = len(sizes), sum(sizes)
+        setup = shard_rollouts(torch, make_env, lambda D: _members(torch, D, P, split), sizes, K, 7)
+        env, pop, b, shards, refs, sbs = setup
+        age(torch, b, sbs, sizes, pop.n_actions, b["logp_all"], torch.Generator(device=DEV).manual_seed(P * 1000 + N + K), True)
+        return setup
+    return cached((tuple(sizes), K, split), make)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -263,7 +191,7 @@ def test_equal_slices_bound_change_nothing(torch_cuda):
         adv, ret = ppo.gae(b)
         stats = ppo.adv_stats().clone()
         la = ppo.dist(b).clone()
-        perm = torch.stack([torch.stack([torch.randperm(K4 * n, device=DEV, generator=g) for _ in range(3)]) for _ in range(P)])
+        perm = stacked_perms(torch, g, P, 3, K4 * n)
         st = ppo.update(b, [perm[m] for m in range(P)] if bound else perm, [1, 3, 2], [4, 1, 5], stats=True)
         act = env.population_act(pop, seed=1, step=2)
         ev = NativeEvaluator(env)
@@ -421,13 +349,6 @@ def test_refusals_launch_nothing_and_leave_the_buffers_untouched(torch_cuda):
 # ------------------------------------------------------------------------------------------------------------------------------------
 # train/pbt_native.py --mutate-batch
 # ------------------------------------------------------------------------------------------------------------------------------------
-def _pbt_mod():
-    spec = importlib.util.spec_from_file_location("pbt_native_slices_gpu", os.path.join(ROOT, "train", "pbt_native.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def _seed_that_reslices(mod, P, n_envs, quantum):
     """The first seed whose first perturbation changes the slices WHOEVER ranks bottom and top — found on the CPU from the scheduler
     alone: the scheduler's draws do not depend on which members they are for."""
@@ -456,7 +377,7 @@ def _seed_that_reslices(mod, P, n_envs, quantum):
 
 def test_pbt_trainer_mutates_the_batch_and_reslices(torch_cuda):
     torch = torch_cuda
-    mod = _pbt_mod()
+    mod = load_script("train/pbt_native.py")
     P, n_envs, quantum = 4, 256, 16
     seed = _seed_that_reslices(mod, P, n_envs, quantum)
     lines = []

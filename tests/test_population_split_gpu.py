@@ -3,95 +3,39 @@ The reference of every check is the single-policy path on the member's slice alo
 ``ShipVecEnv(n, env_id_base=m*n)``, NativePPO's update — and every comparison is torch.equal.  P = 3 members x n = 100 envs: a full
 wave plus a tail per member."""
 import ctypes as C
-import importlib.util
-import os
 
 import pytest
 
-from split_helpers import DEV, split_module, split_policy, vec
+from gpu_support import DEV, load_script, vec
+from gpu_support import torch_cuda  # noqa: F401
+from population_harness import age, cached, cols, shard_rollouts, stacked_perms
+from population_harness import close_cached  # noqa: F401
+from ppo_reference import actor_critic_policy, split_module, split_policy
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P, N_ENVS, K = 3, 100, 4
-ROLLOUT_KEYS = ("obs", "act", "logp", "val", "rew", "done", "flags")
+SIZES = [N_ENVS] * P
 # per member: RLlib's loss, PPO2's loss, everything off
 EXT = {"vf_clip": [10.0, 0.05, 0.0], "max_grad_norm": [0.0, 0.03, 0.0], "kl_coef": [1.0, 0.0, 0.0], "kl_target": [1e-4, 0.0, 0.0]}
 SHAPES = [(22, 48, 2, 3, "tanh"), (7, 16, 1, 4, "relu")]
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch
 
 
 def _members(torch, D, H, L, A, act, seed=100):
     return [split_policy(torch, D, H, L, act, A, seed=seed + m)[1] for m in range(P)]
 
 
-def _cols(t, m):
-    return t[:, m * N_ENVS:(m + 1) * N_ENVS]
-
-
-_SETUPS = {}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _close_cached():
-    yield
-    for env, pop, b, shards, refs, sbs in _SETUPS.values():
-        env.close()
-        for sh in shards:
-            sh.close()
-    _SETUPS.clear()
-
-
 def _setup(torch, shape):
     """One population rollout and the P shard rollouts (asserted equal, bootstrap value and ssg_pop_dist rows included); then, in
     both, the acting policy is made an older one: the same noise on the log-distribution and on the value prediction."""
-    if shape in _SETUPS:
-        return _SETUPS[shape]
-    from ship_sim_gym_amd.population import NativePopulation, PopulationPPO
-    from ship_sim_gym_amd.ppo import NativePPO
-    D, H, L, A, act = shape
-    env = vec(P * N_ENVS, D)
-    pop, refs = NativePopulation(_members(torch, D, H, L, A, act)), _members(torch, D, H, L, A, act)
-    assert pop.separate_value and pop.to_native().activation & 0x100
-    env.reset_tensor()
-    b = dict(env.rollout_population(pop, K, seed=7))
-    la = PopulationPPO(pop, env).dist(b).clone()
-    g = torch.Generator(device=DEV).manual_seed(3)
-    noise = 0.3 * torch.randn((K, P * N_ENVS, A), generator=g, device=DEV)
-    vnoise = (torch.rand((K, P * N_ENVS), generator=g, device=DEV) - 0.5) * 0.4
-    forced = torch.rand((K, P * N_ENVS), generator=g, device=DEV) < 0.05
-    shards, sbs = [], []
-    for m in range(P):
-        sh = vec(N_ENVS, D, base=m * N_ENVS)
-        sh.reset_tensor()
-        sb = dict(sh.rollout_policy(refs[m], K, seed=7))
-        for k in ROLLOUT_KEYS:
-            assert b[k].dtype == sb[k].dtype and torch.equal(_cols(b[k], m), sb[k]), (m, k)
-        assert torch.equal(b["last_val"][m * N_ENVS:(m + 1) * N_ENVS], sb["last_val"]), m
-        assert torch.equal(env.obs[m * N_ENVS:(m + 1) * N_ENVS], sh.obs), m
-        sla = NativePPO(refs[m], sh).dist(sb)
-        assert torch.equal(_cols(la, m), sla), m
-        assert torch.equal(sla.gather(-1, sb["act"].long().unsqueeze(-1)).squeeze(-1), sb["logp"]), m
-        shards.append(sh)
-        sbs.append(sb)
-    assert not torch.equal(b["val"][0, :N_ENVS], b["val"][0, N_ENVS:2 * N_ENVS])      # the members really differ
-    old = torch.zeros_like(la)
-    old[..., :A] = torch.log_softmax(la[..., :A] + noise, -1)
-    b["logp_all"] = old
-    b["logp"] = old.gather(-1, b["act"].long().unsqueeze(-1)).squeeze(-1).contiguous()
-    b["val"] = (b["val"] + vnoise).contiguous()
-    b["done"] = (b["done"] | forced).to(torch.uint8).contiguous()
-    for m in range(P):
-        for k in ("logp_all", "logp", "val", "done"):
-            sbs[m][k] = _cols(b[k], m).contiguous()
-    _SETUPS[shape] = (env, pop, b, shards, refs, sbs)
-    return _SETUPS[shape]
+    def make():
+        D, H, L, A, act = shape
+        setup = shard_rollouts(torch, lambda n, base: vec(n, D, base=base), lambda D: _members(torch, D, H, L, A, act), SIZES, K, 7)
+        env, pop, b, shards, refs, sbs = setup
+        assert pop.separate_value and pop.to_native().activation & 0x100
+        age(torch, b, sbs, SIZES, A, b["logp_all"], torch.Generator(device=DEV).manual_seed(3), True)
+        return setup
+    return cached(shape, make)
 
 
 @pytest.mark.parametrize("shape", SHAPES)
@@ -128,13 +72,13 @@ def test_gae_and_update_are_bitwise_each_members_own(torch_cuda, shape, ext):
         for m in range(P):
             ref = NativePPO(refs[m], shards[m], lr=lrs[m], **{k: v[m] for k, v in terms.items()})
             r_adv, r_ret = ref.gae(sbs[m], 0.99, lams[m])
-            assert torch.equal(_cols(adv, m), r_adv) and torch.equal(_cols(ret, m), r_ret), m
+            assert torch.equal(cols(adv, m, SIZES), r_adv) and torch.equal(cols(ret, m, SIZES), r_ret), m
             assert torch.equal(stats[m], ref.adv_stats()), m
             ref_ppos.append(ref)
         samples = K * N_ENVS
         g = torch.Generator(device=DEV).manual_seed(11)
         for round_ in range(2):                                            # 3 minibatches: chunks of 134, 134, 132; the second continues
-            perm = torch.stack([torch.stack([torch.randperm(samples, device=DEV, generator=g) for _ in range(2)]) for _ in range(P)])
+            perm = stacked_perms(torch, g, P, 2, samples)
             ppo.workspace[4096:].fill_(0xFF)                               # NaN bytes past the members' advantage statistics
             st = ppo.update(b, perm, 2, 3, stats=True)
             assert st.shape == (P, 6, 8 if ext else 4) and bool(torch.isfinite(st).all())
@@ -188,7 +132,6 @@ def test_exploit_copies_the_longer_rows_and_load_into_round_trips(torch_cuda):
     again = NativePopulation.from_layers([triple(net) for net in others], scale, activation=act)
     assert again.separate_value and torch.equal(again.params, pop.params)
     # one architecture per population
-    from helpers import actor_critic_policy
     with pytest.raises(ValueError, match="member 1"):
         NativePopulation([pop.member(0), actor_critic_policy(torch, D, H, L, act, A)[1]])
     env.close()
@@ -250,9 +193,7 @@ def test_bad_flag_bits_are_refused_and_launch_nothing(torch_cuda):
 
 def test_pbt_trainer_with_separate_value_networks(torch_cuda):
     torch = torch_cuda
-    spec = importlib.util.spec_from_file_location("pbt_native_split_gpu", os.path.join(ROOT, "train", "pbt_native.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    mod = load_script("train/pbt_native.py")
     hist, det = mod.train(members=4, envs_per_member=64, updates=2, horizon=8, perturb_every=1, seed=0, log=lambda s: None,
                           return_details=True, kl_coeff=1.0, max_grad_norm=0.5, separate_value=True)
     assert len(hist) == 2 and det["params"].shape[0] == 4 and bool(torch.isfinite(det["params"]).all())

@@ -14,28 +14,11 @@ import itertools
 import numpy as np
 import pytest
 
-from helpers import actor_critic_policy, assert_same_rollout, check_per_tensor, ppo_loss, stepwise_rollout, torch_gae
+from gpu_support import DEV, HIST_BEAMS, env_config as _env_config, torch_cuda  # noqa: F401
+from ppo_reference import actor_critic_policy, assert_same_rollout, check_per_tensor, forward, ref_grad, ref_update, stepwise_rollout, \
+    synthetic_batch_logp_noise as _synthetic, torch_gae
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-# obs_dim D = history * (6 + n_beams)
-HIST_BEAMS = {7: (1, 1), 22: (1, 16), 27: (3, 3), 44: (4, 5), 88: (8, 5), 176: (8, 16)}
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch
-
-
-def _env_config(history):
-    from ship_sim_gym_amd.config import EnvConfig
-
-    class E(EnvConfig):
-        HISTORY_SIZE = history
-    return E
 
 
 def _vec(n, history, n_beams, n_maps=4):
@@ -64,39 +47,6 @@ def _ppo(torch, env, H, L, act, A, seed=0, **kw):
     return pol, NativePPO(pol, env, **kw)
 
 
-def _logp64(torch, pol, x, a):
-    """log pi(a | x) of the packed policy, in f64."""
-    from helpers import unpack
-    t = {k: v.double() for k, v in unpack(pol.params.detach(), pol.offsets).items()}
-    f = torch.tanh if pol.activation == "tanh" else torch.relu
-    h = f(x.double() @ t["W0"].T + t["b0"])
-    if pol.n_hidden_layers == 2:
-        h = f(h @ t["W1"].T + t["b1"])
-    return torch.log_softmax(h @ t["Wpi"].T + t["bpi"], -1).gather(-1, a.long().unsqueeze(-1)).squeeze(-1)
-
-
-def _synthetic(torch, pol, K, N, seed):
-    """A rollout-shaped batch (the dict rollout_policy returns) with controlled extremes; see the module docstring."""
-    D, A = pol.obs_dim, pol.n_actions
-    g = torch.Generator(device=DEV).manual_seed(seed)
-
-    def u(*shape):
-        return torch.rand(shape, generator=g, device=DEV, dtype=torch.float64)
-
-    obs = u(K, N, D) * 600.0
-    obs[u(K, N) < 0.1] = -1.0                                  # reset rows
-    x = (obs / pol.obs_scale).float()
-    big = u(K, N) < 0.05
-    x[big] *= 50.0                                             # saturate tanh to exactly +-1
-    act = (u(K, N) * A).long().clamp_(max=A - 1)
-    logp = (_logp64(torch, pol, x, act) + (u(K, N) - 0.5) * 0.8).float()
-    b = dict(obs=x.contiguous(), act=act.to(torch.int32).contiguous(), logp=logp.contiguous(),
-             rew=torch.randn((K, N), generator=g, device=DEV, dtype=torch.float64),
-             done=(u(K, N) < 0.05).to(torch.uint8), val=torch.randn((K, N), generator=g, device=DEV),
-             last_val=torch.randn((N,), generator=g, device=DEV))
-    return b
-
-
 def _prepare(torch, pol, ppo, K, N, seed):
     """A synthetic batch after ppo.gae (the gradient reads the workspace statistics gae left), and its normalised advantages."""
     b = _synthetic(torch, pol, K, N, seed)
@@ -105,22 +55,13 @@ def _prepare(torch, pol, ppo, K, N, seed):
     return b, (b["adv"].reshape(-1) - st[0]) / st[1]
 
 
-def _ref_grad(torch, pol, b, idx, advn, dtype, clip=0.2, vf_coef=0.5, ent_coef=0.01):
-    x = b["obs"].reshape(-1, pol.obs_dim)[idx].to(dtype)
-    a = b["act"].reshape(-1)[idx].long()
-    lo, an, rt = b["logp"].reshape(-1)[idx].to(dtype), advn[idx].to(dtype), b["ret"].reshape(-1)[idx].to(dtype)
-    p = pol.params.detach().to(dtype).clone().requires_grad_(True)
-    out = ppo_loss(torch, p, pol.offsets, pol.n_hidden_layers, pol.activation, x, a, lo, an, rt, clip, vf_coef, ent_coef)
-    out[0].backward()
-    return p.grad.detach(), [float(o.detach()) for o in out[1:]]
-
-
 def _check_grad(torch, pol, ppo, b, advn, idx, what, coefs=(0.2, 0.5, 0.01)):
     """grad() against f64 / f32 autograd (per packed tensor), its stats against f32, and bitwise run to run."""
     mine, st = ppo.grad(b, idx, stats=True)
     assert torch.equal(mine, ppo.grad(b, idx)), what
-    r64, _ = _ref_grad(torch, pol, b, idx, advn, torch.float64, *coefs)
-    r32, terms32 = _ref_grad(torch, pol, b, idx, advn, torch.float32, *coefs)
+    kw = dict(zip(("clip", "vf_coef", "ent_coef"), coefs))
+    r64, _ = ref_grad(torch, pol, b, idx, advn, torch.float64, **kw)
+    r32, terms32 = ref_grad(torch, pol, b, idx, advn, torch.float32, **kw)
     check_per_tensor(torch, pol, mine, r64, r32, what)
     for got, want in zip(st.tolist(), terms32):
         assert abs(got - want) <= 1e-5 * abs(want) + 1e-6, (what, st.tolist(), terms32)
@@ -289,23 +230,6 @@ def test_gae_domain(torch_cuda, envs):
 UPDATE_HP = dict(lr=1e-3, betas=(0.3, 0.95), eps=1e-6)
 
 
-def _ref_updates(torch, pol, b, advn, perms, minibatches, dtype):
-    """ppo_torch's update loop over consecutive calls (perms: one [epochs, n] tensor per call) with ONE torch.optim.Adam."""
-    p = pol.params.detach().to(dtype).clone().requires_grad_(True)
-    opt = torch.optim.Adam([p], **UPDATE_HP)
-    x = b["obs"].reshape(-1, pol.obs_dim).to(dtype)
-    a, lo = b["act"].reshape(-1).long(), b["logp"].reshape(-1).to(dtype)
-    an, rt = advn.to(dtype), b["ret"].reshape(-1).to(dtype)
-    for perm in perms:
-        for e in range(perm.shape[0]):
-            for mb in perm[e].chunk(minibatches):
-                loss = ppo_loss(torch, p, pol.offsets, pol.n_hidden_layers, pol.activation, x[mb], a[mb], lo[mb], an[mb], rt[mb])[0]
-                opt.zero_grad()
-                loss.backward()
-                opt.step()
-    return p.detach(), opt.state[p]
-
-
 @pytest.mark.parametrize("K,N,minibatches,chunks", [(8, 125, 3, 3), (8, 125, 6, 6), (2, 5, 6, 5)])
 def test_update_uneven_chunks_and_continuity(torch_cuda, envs, K, N, minibatches, chunks):
     torch = torch_cuda
@@ -315,8 +239,8 @@ def test_update_uneven_chunks_and_continuity(torch_cuda, envs, K, N, minibatches
     b, advn = _prepare(torch, pol, ppo, K, N, seed=88)
     g = torch.Generator(device=DEV).manual_seed(minibatches)
     perms = [torch.stack([torch.randperm(n, device=DEV, generator=g) for _ in range(2)]) for _ in range(2)]
-    r64, s64 = _ref_updates(torch, pol, b, advn, perms, minibatches, torch.float64)
-    r32, s32 = _ref_updates(torch, pol, b, advn, perms, minibatches, torch.float32)
+    r64, s64, _ = ref_update(torch, pol, b, advn, perms, minibatches, torch.float64, adam=UPDATE_HP)
+    r32, s32, _ = ref_update(torch, pol, b, advn, perms, minibatches, torch.float32, adam=UPDATE_HP)
     for perm in perms:
         st = ppo.update(b, perm, 2, minibatches, stats=True)
         assert st.shape == (2 * chunks, 4) and bool(torch.isfinite(st).all())
@@ -400,13 +324,8 @@ def test_update_moment_with_beta1_zero_is_the_gradient(torch_cuda, envs):
 # ------------------------------------------------------------------------------------------------------------------------------------
 def _forward64(torch, pol, x):
     """The forward restated in f64 on the f32 parameters: (logp_all [N, A], value [N])."""
-    from helpers import unpack
-    t = {k: v.double() for k, v in unpack(pol.params.detach(), pol.offsets).items()}
-    f = torch.tanh if pol.activation == "tanh" else torch.relu
-    h = f(x.double() @ t["W0"].T + t["b0"])
-    if pol.n_hidden_layers == 2:
-        h = f(h @ t["W1"].T + t["b1"])
-    return torch.log_softmax(h @ t["Wpi"].T + t["bpi"], -1), (h @ t["Wv"].T + t["bv"]).squeeze(-1)
+    logits, v = forward(torch, pol.params.detach().double(), pol.offsets, pol.n_hidden_layers, pol.activation, x.double())
+    return torch.log_softmax(logits, -1), v
 
 
 @pytest.mark.parametrize("history,n_beams", [(1, 1), (1, 16), (4, 16), (8, 16)])

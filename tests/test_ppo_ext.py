@@ -2,9 +2,10 @@
 ssg_ppo_update_ext, ssg_pop_dist, ssg_pop_update_ext): the symbols in the header and the binding, the ssg_ppo_ext / ssg_pop_ext records
 against ctypes, every refusal before any device work, the workspace size, and the PBT trainer's switches.  No GPU."""
 import ctypes as C
-import importlib.util
 import os
 import re
+
+from gpu_support import load_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXT_SYMBOLS = ("ssg_ppo_dist", "ssg_ppo_grad_ext", "ssg_ppo_update_ext", "ssg_pop_dist", "ssg_pop_update_ext")
@@ -237,17 +238,10 @@ def test_population_ext_refusals_before_any_device_work(native):
         L.ssg_destroy(h)
 
 
-def _pbt_mod():
-    spec = importlib.util.spec_from_file_location("pbt_native_ext_cpu", os.path.join(ROOT, "train", "pbt_native.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_pbt_trainer_leaves_the_extended_terms_off_by_default():
     import inspect
     import pytest
-    mod = _pbt_mod()
+    mod = load_script("train/pbt_native.py")
     a = mod.parse_args([])
     assert (a.kl_coeff, a.kl_target, a.vf_clip, a.max_grad_norm) == (0.0, 0.01, 0.0, 0.0)   # kl_target alone switches nothing on
     sig = inspect.signature(mod.train).parameters

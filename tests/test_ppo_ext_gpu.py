@@ -5,48 +5,19 @@ update with the three terms on against the f64 reference of the same update, the
 import numpy as np
 import pytest
 
-from helpers import actor_critic_policy as _policy, check_per_tensor as _check_per_tensor, unpack as _unpack
+from gpu_support import torch_cuda  # noqa: F401
+from ppo_reference import actor_critic_policy as _policy, check_per_tensor as _check_per_tensor, kl_adapt as _adapt, \
+    ref_grad as _ref_grad, ref_update
 
 pytestmark = pytest.mark.gpu
 
 VF_CLIP, KL_COEF = 0.05, 1.0
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch
+TERMS = dict(vf_clip=VF_CLIP, kl_coef=KL_COEF)
 
 
 def _vec(n):
     from ship_sim_gym_amd.vec_env import ShipVecEnv
     return ShipVecEnv(n, n_maps=64)
-
-
-def ext_loss(torch, p, offsets, L, act, x, a, logp_old, advn, ret, v_old, lpa_old, clip=0.2, vf_coef=0.5, ent_coef=0.01, vf_clip=0.0,
-             kl_coef=0.0):
-    """The extended minibatch loss on packed parameters p (any dtype): returns (loss, pg, mean VL, entropy mean, clip fraction,
-    mean KL, (v - v_old, (v - ret)^2, clipped (v_c - ret)^2)).  lpa_old: [M, A] (the acting policy's log-distribution)."""
-    t = _unpack(p, offsets)
-    f = torch.tanh if act == "tanh" else torch.relu
-    h = f(x @ t["W0"].T + t["b0"])
-    if L == 2:
-        h = f(h @ t["W1"].T + t["b1"])
-    logits, v = h @ t["Wpi"].T + t["bpi"], (h @ t["Wv"].T + t["bv"]).squeeze(-1)
-    lpa = torch.log_softmax(logits, -1)
-    ratio = torch.exp(lpa.gather(-1, a.unsqueeze(-1)).squeeze(-1) - logp_old)
-    pg = -torch.min(ratio * advn, torch.clamp(ratio, 1 - clip, 1 + clip) * advn).mean()
-    l1 = (v - ret).pow(2)
-    l2 = (v_old + torch.clamp(v - v_old, -vf_clip, vf_clip) - ret).pow(2)
-    vl = torch.max(l1, l2).mean() if vf_clip > 0 else l1.mean()
-    ent = -(lpa.exp() * lpa).sum(-1).mean()
-    kl = (lpa_old.exp() * (lpa_old - lpa)).sum(-1).mean()
-    cf = ((ratio - 1).abs() > clip).to(x.dtype).mean()
-    loss = pg + vf_coef * vl - ent_coef * ent
-    if kl_coef > 0:
-        loss = loss + kl_coef * kl
-    return loss, pg, vl, ent, cf, kl, (v - v_old, l1, l2)
 
 
 _BATCHES = {}
@@ -95,23 +66,6 @@ def _ppo(torch, pol, env, st, n, M, **kw):
     ppo._ws(n, M)
     ppo.workspace[:12].view(torch.float32).copy_(st)
     return ppo
-
-
-def _ref_terms(torch, pol, b, idx, advn, dtype, p=None, vf_clip=VF_CLIP, kl_coef=KL_COEF):
-    A = pol.n_actions
-    x = b["obs"].reshape(-1, pol.obs_dim)[idx].to(dtype)
-    a = b["act"].reshape(-1)[idx].long()
-    lo, an, rt = b["logp"].reshape(-1)[idx].to(dtype), advn[idx].to(dtype), b["ret"].reshape(-1)[idx].to(dtype)
-    vo, la = b["val"].reshape(-1)[idx].to(dtype), b["logp_all"].reshape(-1, 4)[idx][:, :A].to(dtype)
-    if p is None:
-        p = pol.params.detach().to(dtype).clone().requires_grad_(True)
-    return p, ext_loss(torch, p, pol.offsets, pol.n_hidden_layers, pol.activation, x, a, lo, an, rt, vo, la, vf_clip=vf_clip, kl_coef=kl_coef)
-
-
-def _ref_grad(torch, pol, b, idx, advn, dtype):
-    p, out = _ref_terms(torch, pol, b, idx, advn, dtype)
-    out[0].backward()
-    return p.grad.detach(), [float(o.detach()) for o in out[1:6]], out[6]
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -180,8 +134,8 @@ def _grad_case(torch, H, L, act, A, n, K, sizes, need_branches):
         mine, stats = ppo.grad(b, idx, stats=True)
         again = ppo.grad(b, idx)
         assert torch.equal(mine, again), M                              # bitwise run to run
-        r64, terms64, (dv, l1, l2) = _ref_grad(torch, pol, b, idx, advn, torch.float64)
-        r32, terms32, _ = _ref_grad(torch, pol, b, idx, advn, torch.float32)
+        r64, terms64, (dv, l1, l2) = _ref_grad(torch, pol, b, idx, advn, torch.float64, **TERMS)
+        r32, terms32, _ = _ref_grad(torch, pol, b, idx, advn, torch.float32, **TERMS)
         if M in need_branches:  # on the f64 reference: every branch of the value clip and of its max occurs, and the KL term is alive
             below, inside, above = dv < -VF_CLIP, dv.abs() <= VF_CLIP, dv > VF_CLIP
             assert int(below.sum()) > 0 and int(inside.sum()) > 0 and int(above.sum()) > 0
@@ -211,15 +165,6 @@ def test_ext_grad_over_more_than_512_tiles(torch_cuda):
 # ------------------------------------------------------------------------------------------------------------------------------------
 # 4. gradient-norm clipping
 # ------------------------------------------------------------------------------------------------------------------------------------
-def _ref_clip_step(torch, pol, b, idx, advn, dtype, max_norm):
-    p, out = _ref_terms(torch, pol, b, idx, advn, dtype)
-    opt = torch.optim.Adam([p], lr=3e-4)
-    out[0].backward()
-    torch.nn.utils.clip_grad_norm_([p], max_norm)
-    opt.step()
-    return p.detach()
-
-
 def test_grad_norm_clip_is_clip_grad_norm_then_adam(torch_cuda):
     torch = torch_cuda
     env, pol, b, advn, st = _batch_for(torch, 64, 2, "tanh", 3)
@@ -247,8 +192,8 @@ def test_grad_norm_clip_is_clip_grad_norm_then_adam(torch_cuda):
         assert float(s_tight[0, 5]) == norm
         mine = pol.params.detach().clone()
         pol.params.copy_(p0)
-        r64 = _ref_clip_step(torch, pol, b, perm[0], advn, torch.float64, 0.5 * norm)
-        r32 = _ref_clip_step(torch, pol, b, perm[0], advn, torch.float32, 0.5 * norm)
+        r64 = ref_update(torch, pol, b, advn, perm, 1, torch.float64, max_grad_norm=0.5 * norm, **TERMS)[0]
+        r32 = ref_update(torch, pol, b, advn, perm, 1, torch.float32, max_grad_norm=0.5 * norm, **TERMS)[0]
         _check_per_tensor(torch, pol, mine, r64, r32, "clipped step")
         # the moments hold the CLIPPED gradient: m = 0.1 * g * coef after the first step
         g_raw = _ppo(torch, pol, env, st, n, n, **kw).grad(b, perm[0])
@@ -262,37 +207,14 @@ def test_grad_norm_clip_is_clip_grad_norm_then_adam(torch_cuda):
 # ------------------------------------------------------------------------------------------------------------------------------------
 # 5. a whole update with the three terms on
 # ------------------------------------------------------------------------------------------------------------------------------------
-def _adapt(coef, kls, target):
-    """RLlib's update_kl restated in numpy float32 on the last epoch's minibatch means, summed in chunk order."""
-    s = np.float32(0.0)
-    for k in kls:
-        s = np.float32(s + np.float32(k))
-    mean = np.float32(s / np.float32(len(kls)))
-    t = np.float32(target)
-    if mean > np.float32(2.0) * t:
-        return np.float32(np.float32(coef) * np.float32(1.5))
-    if mean < np.float32(0.5) * t:
-        return np.float32(np.float32(coef) * np.float32(0.5))
-    return np.float32(coef)
-
-
 def _ref_update(torch, pol, b, advn, perm, epochs, minibatches, dtype, max_norm, kl_coef, kl_target):
-    p = pol.params.detach().to(dtype).clone().requires_grad_(True)
-    opt = torch.optim.Adam([p], lr=3e-4)
-    kls = []
-    for e in range(epochs):
-        kls = []
-        for mb in perm[e].chunk(minibatches):
-            _, out = _ref_terms(torch, pol, b, mb, advn, dtype, p=p, kl_coef=kl_coef)
-            opt.zero_grad()
-            out[0].backward()
-            torch.nn.utils.clip_grad_norm_([p], max_norm)
-            opt.step()
-            kls.append(float(out[5].detach()))
+    """(parameters, the adapted coefficient, the last epoch's mean KL) of the reference update with the three terms on."""
+    p, _, kls = ref_update(torch, pol, b, advn, perm[:epochs], minibatches, dtype, max_grad_norm=max_norm, vf_clip=VF_CLIP, kl_coef=kl_coef)
+    kls = kls[-(len(kls) // epochs):]
     mean = sum(kls) / len(kls)
     if kl_target > 0:
         kl_coef = kl_coef * 1.5 if mean > 2 * kl_target else (kl_coef * 0.5 if mean < 0.5 * kl_target else kl_coef)
-    return p.detach(), kl_coef, mean
+    return p, kl_coef, mean
 
 
 def test_whole_ext_update_against_f64_adapts_the_coefficient_and_repeats(torch_cuda):

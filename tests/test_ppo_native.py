@@ -1,11 +1,12 @@
 """CPU-side checks of the device PPO update (GAE + gradient + Adam, ABI 9 additions): the new symbols in the header and the binding,
 the ssg_ppo_hparams record against ctypes, argument refusals before any device work, and the trainer's --update option.  No GPU."""
 import ctypes as C
-import importlib.util
 import os
 import re
 
 import pytest
+
+from gpu_support import load_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PPO_SYMBOLS = ("ssg_ppo_workspace_nbytes", "ssg_ppo_gae", "ssg_ppo_grad", "ssg_ppo_adam", "ssg_ppo_update")
@@ -13,13 +14,6 @@ PPO_SYMBOLS = ("ssg_ppo_workspace_nbytes", "ssg_ppo_gae", "ssg_ppo_grad", "ssg_p
 
 def _header():
     return open(os.path.join(ROOT, "include", "shipsim.h")).read()
-
-
-def _ppo_mod():
-    spec = importlib.util.spec_from_file_location("ppo_torch_update_cpu", os.path.join(ROOT, "train", "ppo_torch.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def test_ppo_symbols_are_declared_exported_and_abi_stays_9(native):
@@ -93,7 +87,7 @@ def test_ppo_entry_points_refuse_before_touching_a_device(native):
 
 
 def test_trainer_offers_native_update_only_with_native_mode():
-    mod = _ppo_mod()
+    mod = load_script("train/ppo_torch.py")
     assert mod.parse_args(["--mode", "native", "--update", "native"]).update == "native"
     assert mod.parse_args([]).update == "torch" and mod.make_arg_parser().parse_args([]).update == "torch"
     for m in ("eager", "graph", "pingpong"):

@@ -1,25 +1,14 @@
 """GPU checks of GAE and the PPO update on the device (ship_sim_gym_amd/ppo.py, ssg_ppo_*): GAE bitwise against train/ppo_torch.py's
 loop, the minibatch gradient against an f64 autograd reference, Adam against torch.optim.Adam, a whole update against the f64
 reference of the same update (and run to run bitwise), and ppo_torch's --update native."""
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 
-from helpers import actor_critic_policy as _policy, check_per_tensor as _check_per_tensor, ppo_loss as _loss, torch_gae as _torch_gae, \
-    unpack as _unpack
+from gpu_support import load_script, torch_cuda  # noqa: F401
+from ppo_reference import actor_critic_policy as _policy, check_per_tensor as _check_per_tensor, forward as _forward, \
+    ref_grad as _ref_grad, ref_update as _ref_update, torch_gae as _torch_gae
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch
 
 
 def _vec(n):
@@ -53,16 +42,6 @@ def test_gae_is_bitwise_the_trainers_loop(torch_cuda, n, K):
     mine = (adv.reshape(-1) - st[0]) / st[1]
     assert float((mine - ref_norm).abs().max()) <= 1e-5
     env.close()
-
-
-def _ref_grad(torch, pol, b, idx, advn, dtype):
-    x = b["obs"].reshape(-1, pol.obs_dim)[idx].to(dtype)
-    a = b["act"].reshape(-1)[idx].long()
-    lo, an, rt = b["logp"].reshape(-1)[idx].to(dtype), advn[idx].to(dtype), b["ret"].reshape(-1)[idx].to(dtype)
-    p = pol.params.detach().to(dtype).clone().requires_grad_(True)
-    out = _loss(torch, p, pol.offsets, pol.n_hidden_layers, pol.activation, x, a, lo, an, rt)
-    out[0].backward()
-    return p.grad.detach(), [float(o.detach()) for o in out[1:]]
 
 
 def _batch_for(torch, H, L, act, A, n=4096, K=10, seed=0):
@@ -109,10 +88,8 @@ def test_clipped_on_both_sides_and_ties(torch_cuda):
     torch = torch_cuda
     env, pol, ppo, b, advn = _batch_for(torch, 64, 2, "tanh", 3)
     with torch.no_grad():
-        x = b["obs"].reshape(-1, pol.obs_dim)
-        t = _unpack(pol.params, pol.offsets)
-        h = torch.tanh(torch.tanh(x @ t["W0"].T + t["b0"]) @ t["W1"].T + t["b1"])
-        lp = torch.log_softmax(h @ t["Wpi"].T + t["bpi"], -1).gather(-1, b["act"].reshape(-1, 1).long()).squeeze(-1)
+        logits, _ = _forward(torch, pol.params, pol.offsets, pol.n_hidden_layers, pol.activation, b["obs"].reshape(-1, pol.obs_dim))
+        lp = torch.log_softmax(logits, -1).gather(-1, b["act"].reshape(-1, 1).long()).squeeze(-1)
         r = torch.exp(lp - b["logp"].reshape(-1))
     assert int((r < 0.8).sum()) > 0 and int((r > 1.2).sum()) > 0 and int(((r >= 0.8) & (r <= 1.2)).sum()) > 0
     env.close()
@@ -136,21 +113,6 @@ def test_adam_matches_torch_optim(torch_cuda):
     env.close()
 
 
-def _ref_update(torch, pol, b, advn, perm, epochs, minibatches, dtype):
-    p = pol.params.detach().to(dtype).clone().requires_grad_(True)
-    opt = torch.optim.Adam([p], lr=3e-4)
-    x = b["obs"].reshape(-1, pol.obs_dim).to(dtype)
-    a, lo = b["act"].reshape(-1).long(), b["logp"].reshape(-1).to(dtype)
-    an, rt = advn.to(dtype), b["ret"].reshape(-1).to(dtype)
-    for e in range(epochs):
-        for mb in perm[e].chunk(minibatches):
-            loss = _loss(torch, p, pol.offsets, pol.n_hidden_layers, pol.activation, x[mb], a[mb], lo[mb], an[mb], rt[mb])[0]
-            opt.zero_grad()
-            loss.backward()
-            opt.step()
-    return p.detach()
-
-
 def test_whole_update_against_f64_and_run_to_run(torch_cuda):
     torch = torch_cuda
     from ship_sim_gym_amd.ppo import NativePPO
@@ -159,8 +121,8 @@ def test_whole_update_against_f64_and_run_to_run(torch_cuda):
     g = torch.Generator(device="cuda:0").manual_seed(11)
     perm = torch.stack([torch.randperm(n, device="cuda:0", generator=g) for _ in range(2)])
     p0 = pol.params.detach().clone()
-    r64 = _ref_update(torch, pol, b, advn, perm, 2, 4, torch.float64)
-    r32 = _ref_update(torch, pol, b, advn, perm, 2, 4, torch.float32)
+    r64 = _ref_update(torch, pol, b, advn, perm, 4, torch.float64)[0]
+    r32 = _ref_update(torch, pol, b, advn, perm, 4, torch.float32)[0]
     st = ppo.update(b, perm, 2, 4, stats=True)
     assert st.shape == (8, 4) and bool(torch.isfinite(st).all())
     first = pol.params.detach().clone()
@@ -176,16 +138,9 @@ def test_whole_update_against_f64_and_run_to_run(torch_cuda):
     env.close()
 
 
-def _ppo_mod():
-    spec = importlib.util.spec_from_file_location("ppo_torch_update_gpu", os.path.join(ROOT, "train", "ppo_torch.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_trainer_native_update(torch_cuda):
     torch = torch_cuda
-    mod = _ppo_mod()
+    mod = load_script("train/ppo_torch.py")
     hist, det = mod.train(envs=4096, updates=3, horizon=32, log=lambda s: None, mode="native", update="native", return_details=True)
     assert len(hist) == 3 and all(np.isfinite(h[1]) and np.isfinite(h[3]) for h in hist)
     assert det["update_seconds"] > 0 and all(bool(torch.isfinite(p).all()) for p in det["params"])

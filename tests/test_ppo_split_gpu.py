@@ -5,14 +5,15 @@ loss and for the extended one with the value clip, the KL penalty and the gradie
 shared policy (identical towers, vf_coef = 0); whole updates against the f64 update, run to run, ext-all-off against plain, and the
 rollout seeing both towers' new weights; refusals of other flag bits.
 
-Batches are synthetic (split_helpers.synthetic_batch) on 64-env handles, one per obs_dim: the PPO calls take their own K, N.  Indices are
+Batches are synthetic (ppo_reference.synthetic_batch) on 64-env handles, one per obs_dim: the PPO calls take their own K, N.  Indices are
 drawn with replacement (they repeat), and the workspace past the advantage statistics is filled with NaN bytes before every gradient."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-from split_helpers import DEV, check_per_tensor, nan_fill, shared_over_pi_tower, split_loss, split_policy, synthetic_batch, vec
+from gpu_support import DEV, torch_cuda, vec  # noqa: F401
+from ppo_reference import check_per_tensor, nan_fill, ref_grad, ref_update, shared_over_pi_tower, split_policy, synthetic_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -23,13 +24,6 @@ MB = (1, 63, 65, 200)              # one sample, a tile less one, a tile plus on
 SHAPES = [(7, 16, 1, 2, "tanh"), (22, 16, 2, 3, "relu"), (22, 48, 1, 4, "relu"), (7, 48, 2, 2, "relu"), (7, 128, 1, 3, "tanh"),
           (22, 128, 2, 4, "tanh"), (176, 128, 2, 3, "tanh")]
 EXT_ON = dict(vf_clip=0.05, kl_coef=1.0, max_grad_norm=0.5)
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch
 
 
 @pytest.fixture(scope="module")
@@ -55,19 +49,6 @@ def _ppo(torch, pol, env, b, max_m, **kw):
     return ppo, (b["adv"].reshape(-1) - st[0]) / st[1]
 
 
-def _ref_grad(torch, pol, b, idx, advn, dtype, vf_coef=0.5, vf_clip=0.0, kl_coef=0.0):
-    A = pol.n_actions
-    x = b["obs"].reshape(-1, pol.obs_dim)[idx].to(dtype)
-    a = b["act"].reshape(-1)[idx].long()
-    lo, an, rt = b["logp"].reshape(-1)[idx].to(dtype), advn[idx].to(dtype), b["ret"].reshape(-1)[idx].to(dtype)
-    vo, la = b["val"].reshape(-1)[idx].to(dtype), b["logp_all"].reshape(-1, 4)[idx][:, :A].to(dtype)
-    p = pol.params.detach().to(dtype).clone().requires_grad_(True)
-    out = split_loss(torch, p, pol.offsets, pol.n_hidden_layers, pol.activation, x, a, lo, an, rt, vo, la, vf_coef=vf_coef, vf_clip=vf_clip,
-                     kl_coef=kl_coef)
-    out[0].backward()
-    return p.grad.detach(), [float(o.detach()) for o in out[1:]]
-
-
 def _check_grad(torch, pol, ppo, b, advn, idx, what, ext):
     nan_fill(ppo)
     mine, st = ppo.grad(b, idx, stats=True)
@@ -75,9 +56,9 @@ def _check_grad(torch, pol, ppo, b, advn, idx, what, ext):
     assert torch.equal(mine, ppo.grad(b, idx)), what                       # bitwise run to run
     assert bool(torch.isfinite(mine).all()) and bool(torch.isfinite(st).all()), what
     kw = dict(vf_clip=EXT_ON["vf_clip"], kl_coef=EXT_ON["kl_coef"]) if ext else {}
-    r64, _ = _ref_grad(torch, pol, b, idx, advn, torch.float64, **kw)
-    r32, terms32 = _ref_grad(torch, pol, b, idx, advn, torch.float32, **kw)
-    check_per_tensor(torch, pol, mine, r64, r32, what)
+    r64 = ref_grad(torch, pol, b, idx, advn, torch.float64, **kw)[0]
+    r32, terms32 = ref_grad(torch, pol, b, idx, advn, torch.float32, **kw)[:2]
+    check_per_tensor(torch, pol, mine, r64, r32, what, verbose=True)
     got = st.tolist()
     print("%s stats %s torch f32 %s" % (what, got, terms32))
     for k in range(5 if ext else 4):                                       # pg, VL, entropy, clip fraction[, KL]
@@ -152,27 +133,6 @@ def test_grad_decomposes_exactly(torch_cuda, envs, D, H, L, A, act, ext):
         assert torch.equal(st_s, st_h), M                                   # the loss sums keep their meaning and order
 
 
-def _ref_update(torch, pol, b, advn, perm, minibatches, dtype, ext, max_grad_norm=0.0, **adam):
-    p = pol.params.detach().to(dtype).clone().requires_grad_(True)
-    opt = torch.optim.Adam([p], **adam)
-    A = pol.n_actions
-    x = b["obs"].reshape(-1, pol.obs_dim).to(dtype)
-    a, lo = b["act"].reshape(-1).long(), b["logp"].reshape(-1).to(dtype)
-    an, rt = advn.to(dtype), b["ret"].reshape(-1).to(dtype)
-    vo, la = b["val"].reshape(-1).to(dtype), b["logp_all"].reshape(-1, 4)[:, :A].to(dtype)
-    kw = dict(vf_clip=EXT_ON["vf_clip"], kl_coef=EXT_ON["kl_coef"]) if ext else {}
-    for e in range(perm.shape[0]):
-        for mb in perm[e].chunk(minibatches):
-            loss = split_loss(torch, p, pol.offsets, pol.n_hidden_layers, pol.activation, x[mb], a[mb], lo[mb], an[mb], rt[mb], vo[mb], la[mb],
-                              **kw)[0]
-            opt.zero_grad()
-            loss.backward()
-            if max_grad_norm > 0:
-                torch.nn.utils.clip_grad_norm_([p], max_grad_norm)
-            opt.step()
-    return p.detach(), opt.state[p]
-
-
 UPDATE_HP = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8)
 
 
@@ -193,13 +153,14 @@ def test_whole_update_against_f64_and_run_to_run(torch_cuda, envs, D, H, L, A, a
     perm = torch.stack([torch.randperm(n, device=DEV, generator=g) for _ in range(2)])
     p0, stats = pol.params.detach().clone(), ppo.adv_stats().clone()
     mgn = EXT_ON["max_grad_norm"] if ext else 0.0
-    r64, s64 = _ref_update(torch, pol, b, advn, perm, 3, torch.float64, ext, mgn, **UPDATE_HP)
-    r32, s32 = _ref_update(torch, pol, b, advn, perm, 3, torch.float32, ext, mgn, **UPDATE_HP)
+    terms = dict(vf_clip=EXT_ON["vf_clip"], kl_coef=EXT_ON["kl_coef"]) if ext else {}
+    r64, s64, _ = ref_update(torch, pol, b, advn, perm, 3, torch.float64, adam=UPDATE_HP, max_grad_norm=mgn, **terms)
+    r32, s32, _ = ref_update(torch, pol, b, advn, perm, 3, torch.float32, adam=UPDATE_HP, max_grad_norm=mgn, **terms)
     nan_fill(ppo)
     st = ppo.update(dict(b), perm, 2, 3, stats=True)
     assert st.shape == (6, 8 if ext else 4) and bool(torch.isfinite(st).all()) and ppo.step == 6 == int(s64["step"])
     first, first_mv = pol.params.detach().clone(), ppo.adam_mv.clone()
-    check_per_tensor(torch, pol, first, r64, r32, ("update", D, H, L, A, act, ext))
+    check_per_tensor(torch, pol, first, r64, r32, ("update", D, H, L, A, act, ext), verbose=True)
     P = ppo.n_params
     for mine, name in ((ppo.adam_mv[:P], "exp_avg"), (ppo.adam_mv[P:], "exp_avg_sq")):
         for k, (o, s) in pol.offsets.items():

@@ -3,12 +3,13 @@ as header, binding and library see them, the workspace size against its document
 judges its arguments on the host before it asks for a state blob or a device), the numpy restatement against a plain hand loop, and
 the trainers' flags.  Nothing here launches a kernel."""
 import ctypes as C
-import importlib.util
 import os
 import re
 
 import numpy as np
 import pytest
+
+from gpu_support import load_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -247,15 +248,8 @@ def test_filter_object_on_the_host(native):
             ReturnFilter(_Env(), **bad)
 
 
-def _script(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "train", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_trainer_flags(capsys):
-    ppo = _script("ppo_torch")
+    ppo = load_script("train/ppo_torch.py")
     a = ppo.parse_args(["--mode", "native", "--update", "native"])
     assert a.norm_reward is False and a.reward_clip == 10.0                     # off by default
     a = ppo.parse_args(["--mode", "native", "--update", "native", "--norm-reward", "--reward-clip", "5"])
@@ -272,7 +266,7 @@ def test_trainer_flags(capsys):
     for kw in (dict(mode="eager"), dict(mode="native", update="torch")):
         with pytest.raises(ValueError):
             ppo.train(envs=8, updates=1, norm_reward=True, **kw)               # (refused before any env is made)
-    pbt = _script("pbt_native")
+    pbt = load_script("train/pbt_native.py")
     assert pbt.parse_args([]).norm_reward is False and pbt.parse_args([]).reward_clip == 10.0
     a = pbt.parse_args(["--norm-reward", "--reward-clip", "2.5"])
     assert a.norm_reward is True and a.reward_clip == 2.5

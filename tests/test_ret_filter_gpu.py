@@ -16,21 +16,12 @@ import sys
 import numpy as np
 import pytest
 
-from helpers import actor_critic_policy
-from split_helpers import vec
+from gpu_support import DEV, ROOT, torch_cuda, vec  # noqa: F401
+from ppo_reference import actor_critic_policy
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
 D = 7
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch
 
 
 def _inputs(K, n, seed):

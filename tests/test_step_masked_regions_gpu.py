@@ -27,6 +27,8 @@ import os
 import numpy as np
 import pytest
 
+from gpu_support import torch_cuda  # noqa: F401
+
 import event_scenes as ES
 from lidar_scenes import layouts
 
@@ -39,13 +41,6 @@ SPIN_W = 2.0 * math.pi / 1.4   # with damping 0.4 the angle is back after two st
 SPIN_AT = (340.0, 300.0)       # 65 in front of the right bank of banks3_12 (lidar range 100), out of reach of the left one
 SPAWN_GOALS = [[310.0, 45.0], [250.0, 40.0]]  # inside the hull of a ship at the spawn point (300, 25); the next nearest
 ALL, NONE = frozenset(range(64)), frozenset()
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    return torch
 
 
 def _records():

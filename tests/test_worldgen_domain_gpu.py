@@ -38,6 +38,8 @@ import time
 import numpy as np
 import pytest
 
+from gpu_support import torch_cuda  # noqa: F401
+
 import worldgen_law as W
 
 pytestmark = pytest.mark.gpu
@@ -105,13 +107,6 @@ def test_every_record_of_the_sweep_is_the_oracles_and_the_census_is_met(torch_cu
     assert n_worlds >= 20000 and total.worlds == n_worlds
     assert total.shortfalls() == []
     assert total.rays["ray_miss"] >= 50   # gen_goal_path's fallback arm (the flat world)
-
-
-@pytest.fixture
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
 
 
 def test_a_fresh_device_ring_refilled_after_stepping_is_the_oracles(torch_cuda, oracle, native, monkeypatch):
