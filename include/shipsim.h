@@ -667,8 +667,8 @@ int ssg_ppo_update_ext(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hpara
  * its inverse, 0) at its start, per member over that member's K*n samples, which ssg_pop_update reads.  dev_adam_mv: f32 [P][2L].
  * The extended loss terms are per member too (ssg_pop_update_ext below), and so may the epochs and the minibatch count be
  * (ssg_pop_update_sched), and the batch size (train_batch_size) as a member's share of the handle's envs: unequal slices,
- * ssg_pop_set_slices below.  Out of scope: unequal rollout lengths, PPO2's per-minibatch advantage normalisation, populations spanning
- * handles or GPUs, per-member architectures.
+ * ssg_pop_set_slices below.  PPO2's per-minibatch advantage normalisation is a mode of the handle (ssg_ppo_set_adv_norm
+ * below), common to the members.  Out of scope: unequal rollout lengths, populations spanning handles or GPUs, per-member architectures.
  * ------------------------------------------------------------------------------------------------- */
 #define SSG_POP_MAX_MEMBERS 256
 #define SSG_POP_TABLE_FLOATS(n_members, n_steps) ((size_t)(n_members) * 8u * (size_t)(1 + (n_steps)))
@@ -1095,6 +1095,54 @@ int ssg_ret_filter_workspace_nbytes(int n_envs, int K, int n_members, size_t *nb
  * dev_reward_KN; workspace_nbytes below ssg_ret_filter_workspace_nbytes(n_envs, K, n_members). */
 int ssg_ret_filter_apply(ssg_handle *h, const ssg_ret_filter *f, int K, const double *dev_reward_KN, const uint8_t *dev_done_KN,
                          int64_t step_stride_envs, double *dev_reward_out_KN, double *dev_denom_KP, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Per-minibatch advantage normalisation (ABI 9 addition): PPO2's rule in the device update
+ * train/stable_baselines/ppo.py:90 trains with PPO2, whose _train_step re-normalises the advantages inside every minibatch:
+ * advs = (advs - advs.mean()) / (advs.std() + 1e-8) over the minibatch's own samples.  The loss section above normalises once per
+ * rollout, with the statistics ssg_ppo_gae / ssg_pop_gae leave in the workspace (train/ppo_torch.py's rule, and RLlib's).  The mode is
+ * bound to the handle together with a caller-owned scratch, as ssg_set_terminal_obs and ssg_set_obs_filter bind theirs.
+ *
+ * SSG_ADV_NORM_BATCH (the default): A = (adv - mean) / (std + adv_eps) with the workspace's batch statistics, as above.
+ * SSG_ADV_NORM_MINIBATCH: for every minibatch of every member, with s, q and c the f64 sums of adv, adv^2 and 1 over the minibatch's
+ * indices that lie in [0, n_samples) (an index outside stays the zero, gradient-free sample it is and counts for nothing):
+ *   mean = s / c;   var = max(0, (q - s*mean) / (c - 1));   std+ = (float)sqrt(var) + adv_eps;   A = (adv - (float)mean) / std+
+ * the estimator of ssg_ppo_gae (the unbiased std) over the minibatch.  c == 1: var = 0, so the one sample's A is 0 — what PPO2's numpy
+ * std gives; torch.std would give NaN.  c == 0: mean 0, std+ 1.  adv_eps is the policy's (ssg_ppo_hparams) or the member's (its table
+ * row).  The row f32[4] = {mean, std+, 1/std+, 0} of member m is written to the scratch's stats rows, where the gradient kernel reads
+ * it; the batch statistics in the workspace are not touched, so switching back to SSG_ADV_NORM_BATCH needs no new GAE.  No bit parity
+ * with Stable-Baselines is claimed: PPO2 uses the population std, a relative difference of about 1 / (2M).
+ *
+ * Order of the sums (a function of the minibatch's length M alone; no floating-point atomics).  Two launches per minibatch ahead of the
+ * gradient launch, on its stream.  Partials, grid (64, members) x 256 threads: a member with M indices uses B = min(64, ceil(M / 1024))
+ * workgroups; thread t of workgroup b takes positions i = b*256 + t, then steps by B*256 while i < M, adding in that order; the 256
+ * threads' sums are added as a halving tree (w = 128 .. 1: entry t += entry t + w); one (s, q, c) per workgroup.  Finalise, one
+ * workgroup per member: entry b = partial b for b < B and 0 beyond, the same tree, then the row.  A member of a schedule without a
+ * minibatch in a launch keeps its row.
+ *
+ * Scratch: f32 [n_members][4] stats rows, then f64 [n_members][64][3] partials (member m's workgroup b: s, q, c; a minibatch writes
+ * its first B), each part rounded up to 256 bytes.  Two updates in flight on one handle would share it: one update at a time per
+ * handle, as with the workspace.
+ * ------------------------------------------------------------------------------------------------- */
+#define SSG_ADV_NORM_BATCH 0
+#define SSG_ADV_NORM_MINIBATCH 1
+
+/* Replaces nothing (memory binding; PPO2 behind train/stable_baselines/ppo.py:90 normalises on the host as it goes): the scratch size
+ * for n_members members (1 for one policy).  SSG_ERR_BAD_ARG for NULL nbytes or n_members outside 1..SSG_POP_MAX_MEMBERS. */
+int ssg_ppo_adv_norm_nbytes(int n_members, size_t *nbytes);
+
+/* Replaces: the choice PPO2 makes in _train_step behind model.learn (train/stable_baselines/ppo.py:90) to normalise the advantages per
+ * minibatch.  Binds the mode and the caller-owned, 256-byte aligned device scratch to the handle (host only, nothing launched); while
+ * SSG_ADV_NORM_MINIBATCH is bound, ssg_ppo_grad, ssg_ppo_grad_ext, ssg_ppo_update, ssg_ppo_update_ext, ssg_pop_update,
+ * ssg_pop_update_ext and ssg_pop_update_sched normalise per minibatch, and one of them called with more members than n_members is
+ * refused (SSG_ERR_BAD_ARG, nothing launched).  SSG_ADV_NORM_BATCH unbinds (the other arguments are then not read).  SSG_ERR_BAD_ARG,
+ * the binding left as it was: a NULL handle; an unknown mode; with SSG_ADV_NORM_MINIBATCH an n_members outside
+ * 1..SSG_POP_MAX_MEMBERS, a NULL or misaligned dev_scratch, or scratch_nbytes below ssg_ppo_adv_norm_nbytes(n_members). */
+int ssg_ppo_set_adv_norm(ssg_handle *h, int mode, int n_members, void *dev_scratch, size_t scratch_nbytes);
+
+/* Replaces nothing (introspection; train/stable_baselines/ppo.py:90 has no such switch).  *mode = the bound mode, *n_members = the
+ * member count its scratch serves (0 with SSG_ADV_NORM_BATCH). */
+int ssg_ppo_get_adv_norm(const ssg_handle *h, int *mode, int *n_members);
 
 /* ---------------------------------------------------------------------------------------------------
  * Host-side geometry (what pymunk's cffi exposed at reset time); no GPU needed.

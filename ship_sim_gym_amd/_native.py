@@ -28,6 +28,8 @@ EVAL_STATS, EVAL_GREEDY = 8, 0x1  # columns of an evaluation's stats rows; ssg_e
 FILTER_ROWS, FILTER_UPDATE = 4, 0x1  # state rows per member of an observation filter (mean, M2, denom, count); ssg_obs_filter.flags
 FILTER_TILE, FILTER_RUNS = 256, 8  # ssg_obs_filter_update's reduction order: rows per tile, runs of tiles (include/shipsim.h)
 RET_FILTER_UPDATE, RET_FILTER_MAX_STEPS = 0x1, 1024  # ssg_ret_filter.flags; the largest K of one ssg_ret_filter_apply call
+ADV_NORM_BATCH, ADV_NORM_MINIBATCH = 0, 1  # ssg_ppo_set_adv_norm's modes: once per rollout (the default), PPO2's per minibatch
+ADV_NORM_BLOCKS, ADV_NORM_SPAN = 64, 1024  # its reduction order: workgroups at most per member, minibatch positions per workgroup below that
 
 
 def pop_table_floats(n_members, n_steps):
@@ -70,6 +72,7 @@ EXPORTS = (
     "ssg_pop_pack_slices", "ssg_pop_set_slices", "ssg_pop_get_slices", "ssg_pop_pack_schedule_samples",
     "ssg_obs_filter_workspace_nbytes", "ssg_obs_filter_update", "ssg_set_obs_filter", "ssg_get_obs_filter",
     "ssg_ret_filter_workspace_nbytes", "ssg_ret_filter_apply",
+    "ssg_ppo_adv_norm_nbytes", "ssg_ppo_set_adv_norm", "ssg_ppo_get_adv_norm",
 )
 
 
@@ -261,6 +264,9 @@ def lib():
     L.ssg_get_obs_filter.argtypes = [vp, C.POINTER(ObsFilterRecord)]
     L.ssg_ret_filter_workspace_nbytes.argtypes = [C.c_int, C.c_int, C.c_int, szp]
     L.ssg_ret_filter_apply.argtypes = [vp, C.POINTER(RetFilterRecord), C.c_int, vp, vp, C.c_int64, vp, vp, vp]
+    L.ssg_ppo_adv_norm_nbytes.argtypes = [C.c_int, szp]
+    L.ssg_ppo_set_adv_norm.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
+    L.ssg_ppo_get_adv_norm.argtypes = [vp, ip, ip]
     L.ssg_render.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, vp]
     L.ssg_dyn_invalidate.argtypes = [vp, vp, vp]
     L.ssg_host_convex_hull.argtypes = [C.c_int, dp, dp, ip]

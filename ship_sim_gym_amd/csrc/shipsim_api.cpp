@@ -61,6 +61,9 @@ struct ssg_handle {
     // ssg_set_obs_filter: the bound record (a copy; struct_size 0: nothing bound) and whether the FILTER kernels' LDS limit is set
     ssg_obs_filter flt{};
     bool policy_filter_prepared = false;
+    // ssg_ppo_set_adv_norm: the mode (SSG_ADV_NORM_BATCH: nothing bound), the member count the scratch serves and the caller's scratch
+    int adv_norm_mode = SSG_ADV_NORM_BATCH, adv_norm_members = 0;
+    void *adv_norm_scratch = nullptr;
     std::string err;
 };
 
@@ -1156,6 +1159,26 @@ static ssg::PpoMinibatch one_policy(const ssg_policy *pol, const ssg_ppo_hparams
     return mb;
 }
 
+// Per-minibatch advantage normalisation (ssg_ppo_set_adv_norm): while it is bound, every minibatch of the gradient / update entry points
+// takes its statistics from the handle's scratch (its stats rows, then its partials) instead of the workspace's batch statistics.
+static void adv_norm_bind(const ssg_handle *h, ssg::PpoMinibatch &mb)
+{
+    if (h->adv_norm_mode != SSG_ADV_NORM_MINIBATCH) return;
+    char *base = static_cast<char *>(h->adv_norm_scratch);
+    mb.adv_stats = reinterpret_cast<float *>(base);
+    mb.adv_part = reinterpret_cast<double *>(base + ssg::adv_norm_stats_bytes(h->adv_norm_members));
+}
+
+// the call's member count must fit the bound scratch
+static int check_adv_norm_members(ssg_handle *h, int members, const char *what)
+{
+    if (h->adv_norm_mode != SSG_ADV_NORM_MINIBATCH || members <= h->adv_norm_members) return SSG_OK;
+    char buf[200];
+    std::snprintf(buf, sizeof buf, ": %d members, but the bound advantage-normalisation scratch serves n_members = %d (ssg_ppo_set_adv_norm)", members,
+                  h->adv_norm_members);
+    return fail(h, SSG_ERR_BAD_ARG, std::string(what) + buf);
+}
+
 // torch.chunk of n samples into `minibatches`: chunks of C = ceil(n / minibatches), the last one shorter — so ceil(n / C) of them
 struct Chunking {
     long long C, chunks;
@@ -1235,6 +1258,7 @@ int ssg_ppo_grad(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp
     if (rc == SSG_OK) rc = prepare_ppo(h);
     if (rc != SSG_OK) return rc;
     ssg::PpoMinibatch mb = one_policy(pol, hp, n_samples, batch, dev_workspace);
+    adv_norm_bind(h, mb);
     mb.idx = dev_idx;
     mb.M = M;
     mb.grad_out = dev_grad;
@@ -1278,6 +1302,7 @@ int ssg_ppo_update(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *
     if (rc == SSG_OK) rc = prepare_ppo(h);
     if (rc != SSG_OK) return rc;
     ssg::PpoMinibatch mb = one_policy(pol, hp, n_samples, batch, dev_workspace);
+    adv_norm_bind(h, mb);
     mb.idx = dev_perm;
     mb.stats_out = dev_stats;
     mb.adam_mv = dev_adam_mv;
@@ -1428,6 +1453,7 @@ int ssg_ppo_grad_ext(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams
     if (rc != SSG_OK) return rc;
     const ssg::PpoExtLaunch el = ext_launch(*ext);
     ssg::PpoMinibatch mb = one_policy(pol, hp, n_samples, batch, dev_workspace);
+    adv_norm_bind(h, mb);
     mb.idx = dev_idx;
     mb.M = M;
     mb.ext = &el;
@@ -1459,6 +1485,7 @@ int ssg_ppo_update_ext(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hpara
     if (rc != SSG_OK) return rc;
     ssg::PpoExtLaunch el = ext_launch(*ext);
     ssg::PpoMinibatch mb = one_policy(pol, hp, n_samples, batch, dev_workspace);
+    adv_norm_bind(h, mb);
     mb.idx = dev_perm;
     mb.stats_out = dev_stats;
     mb.adam_mv = dev_adam_mv;
@@ -1713,6 +1740,7 @@ static int check_pop_update(ssg_handle *h, const ssg_policy *pol, int P, const f
         return fail(h, SSG_ERR_BAD_ARG, w + ": slices are bound to the handle (ssg_pop_set_slices): the update runs through ssg_pop_update_sched");
     const long long n = (long long)K * (N / P); // samples per member (unequal slices: unused, see ssg_pop_update_sched)
     int rc = check_batch(h, n, batch, dev_perm, what);
+    if (rc == SSG_OK) rc = check_adv_norm_members(h, P, what);
     if (rc != SSG_OK) return rc;
     if (!dev_table || !dev_adam_mv) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_table or dev_adam_mv");
     if (!sched) {
@@ -1731,6 +1759,7 @@ static int check_pop_update(ssg_handle *h, const ssg_policy *pol, int P, const f
     mb->slots_off = ssg::kPopSlotsOff;
     mb->table = dev_table;
     mb->adam_mv = dev_adam_mv;
+    adv_norm_bind(h, *mb);
     return SSG_OK;
 }
 
@@ -2160,6 +2189,55 @@ int ssg_get_obs_filter(const ssg_handle *h, ssg_obs_filter *out)
 {
     if (!h || !out) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_get_obs_filter: NULL handle or out");
     *out = h->flt;
+    return SSG_OK;
+}
+
+// ABI 9 addition: per-minibatch advantage normalisation.  Host only: nothing here touches the device.
+int ssg_ppo_adv_norm_nbytes(int n_members, size_t *nbytes)
+{
+    if (!nbytes || n_members < 1 || n_members > SSG_POP_MAX_MEMBERS)
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_ppo_adv_norm_nbytes: NULL nbytes or n_members outside 1..SSG_POP_MAX_MEMBERS");
+    *nbytes = ssg::adv_norm_bytes(n_members);
+    return SSG_OK;
+}
+
+int ssg_ppo_set_adv_norm(ssg_handle *h, int mode, int n_members, void *dev_scratch, size_t scratch_nbytes)
+{
+    if (!h) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_ppo_set_adv_norm: NULL handle");
+    if (mode != SSG_ADV_NORM_BATCH && mode != SSG_ADV_NORM_MINIBATCH) {
+        char buf[120];
+        std::snprintf(buf, sizeof buf, "ssg_ppo_set_adv_norm: unknown mode %d (SSG_ADV_NORM_BATCH or SSG_ADV_NORM_MINIBATCH)", mode);
+        return fail(h, SSG_ERR_BAD_ARG, buf); // (the binding stays as it was, here and below)
+    }
+    if (mode == SSG_ADV_NORM_BATCH) { // unbind
+        h->adv_norm_mode = SSG_ADV_NORM_BATCH;
+        h->adv_norm_members = 0;
+        h->adv_norm_scratch = nullptr;
+        return SSG_OK;
+    }
+    if (n_members < 1 || n_members > SSG_POP_MAX_MEMBERS)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_set_adv_norm: n_members must be in 1..SSG_POP_MAX_MEMBERS");
+    if (!dev_scratch) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_set_adv_norm: NULL dev_scratch with SSG_ADV_NORM_MINIBATCH");
+    if (reinterpret_cast<uintptr_t>(dev_scratch) % 256 != 0)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_set_adv_norm: dev_scratch must be 256-byte aligned");
+    const size_t need = ssg::adv_norm_bytes(n_members);
+    if (scratch_nbytes < need) {
+        char buf[200];
+        std::snprintf(buf, sizeof buf, "ssg_ppo_set_adv_norm: scratch_nbytes of %zu bytes, n_members = %d needs %zu (ssg_ppo_adv_norm_nbytes)",
+                      scratch_nbytes, n_members, need);
+        return fail(h, SSG_ERR_BAD_ARG, buf);
+    }
+    h->adv_norm_mode = mode;
+    h->adv_norm_members = n_members;
+    h->adv_norm_scratch = dev_scratch;
+    return SSG_OK;
+}
+
+int ssg_ppo_get_adv_norm(const ssg_handle *h, int *mode, int *n_members)
+{
+    if (!h || !mode || !n_members) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_ppo_get_adv_norm: NULL handle, mode or n_members");
+    *mode = h->adv_norm_mode;
+    *n_members = h->adv_norm_members;
     return SSG_OK;
 }
 

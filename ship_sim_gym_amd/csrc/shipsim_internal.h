@@ -329,8 +329,36 @@ struct PpoMinibatch {
     // and its samples are K * n_m (n, n_samples and idx_stride are then unused)
     const int32_t *slices, *sched_hdr;
     long long K, perm_epochs;
+    // per-minibatch advantage normalisation (ssg_ppo_set_adv_norm; both NULL: the batch statistics in the workspace): the scratch's
+    // stats rows and partials.  The two launches of shipsim_advnorm.hip then run ahead of the gradient launch, which reads these rows.
+    float *adv_stats;
+    double *adv_part;
 };
 hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream);
+// Per-minibatch advantage statistics (shipsim_advnorm.hip).  Scratch: f32 [members][4] rows, then f64 [members][kAdvNormBlocks][3]
+// partials (s, q, c), each part rounded up to 256 bytes.
+constexpr int kAdvNormBlocks = 64;
+inline size_t adv_norm_stats_bytes(int members) { return ((size_t)members * 4 * sizeof(float) + 255) & ~(size_t)255; }
+inline size_t adv_norm_bytes(int members)
+{
+    return adv_norm_stats_bytes(members) + (((size_t)members * kAdvNormBlocks * 3 * sizeof(double) + 255) & ~(size_t)255);
+}
+// The minibatch as PpoMinibatch names it (table NULL: one policy, adv_eps its own; else adv_eps is column adv_eps_col of table row m).
+struct AdvNormLaunch {
+    const float *adv;
+    const int64_t *idx;
+    long long M, n_samples;
+    int members;
+    long long n, N, idx_stride;
+    const float *table;
+    int adv_eps_col;
+    float adv_eps;
+    const int32_t *sched, *slices, *sched_hdr;
+    long long K, perm_epochs;
+    float *stats;
+    double *part;
+};
+hipError_t launch_adv_norm(const AdvNormLaunch &l, hipStream_t stream);
 // RLlib's update_kl on every member's coefficient from the last epoch's `chunks` minibatches (sched_hdr, nullable: the schedule
 // table, whose header row m holds member m's own chunk count)
 hipError_t launch_kl_adapt(int members, const PpoExtLaunch &ext, float kl_target, int P, long long chunks, const int32_t *sched_hdr, void *ws,

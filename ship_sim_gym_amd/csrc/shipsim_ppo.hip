@@ -1147,7 +1147,32 @@ hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream)
     a.M = mb.M;
     a.n_samples = mb.n_samples;
     a.stats = reinterpret_cast<const float *>(base + kPpoStatsOff);
-    a.slots = reinterpret_cast<float *>(base + (ext ? lay.slots : mb.slots_off));
+    if (mb.adv_stats) { // per-minibatch normalisation: this minibatch's own statistics first (two launches), into the scratch's rows
+        if (!mb.adv_part) return hipErrorInvalidValue;
+        AdvNormLaunch an = {};
+        an.adv = mb.batch.adv;
+        an.idx = mb.idx;
+        an.M = mb.M;
+        an.n_samples = mb.n_samples;
+        an.members = mb.members;
+        an.n = mb.n;
+        an.N = mb.N;
+        an.idx_stride = mb.idx_stride;
+        an.table = mb.table;
+        an.adv_eps_col = PT_ADV_EPS;
+        an.adv_eps = row[PT_ADV_EPS];
+        an.sched = mb.sched;
+        an.slices = mb.slices;
+        an.sched_hdr = mb.sched_hdr;
+        an.K = mb.K;
+        an.perm_epochs = mb.perm_epochs;
+        an.stats = mb.adv_stats;
+        an.part = mb.adv_part;
+        const hipError_t e = launch_adv_norm(an, stream);
+        if (e != hipSuccess) return e;
+        a.stats = mb.adv_stats;
+    }
+    a.slots =reinterpret_cast<float *>(base + (ext ? lay.slots : mb.slots_off));
     a.P = P;
     a.lo = row[PT_LO];
     a.hi = row[PT_HI];

@@ -26,7 +26,7 @@ from fractions import Fraction
 
 from . import _native as N
 from .policy import ACTIVATIONS, NativePolicy
-from .ppo import chunk_split
+from .ppo import adv_norm_mode, adv_norm_scratch, adv_norm_views, chunk_split
 
 
 def _torch():
@@ -132,13 +132,20 @@ class PopulationPPO(object):
     copy (ssg_pop_exploit) and per-member episode statistics (ssg_pop_episode_stats).  Owns the Adam moments [P, 2L], the workspace and
     the episode carry columns.  Every hyper-parameter is a list of P floats (``self.lr[m] = ...``); defaults: NativePPO's.  So are
     ``vf_clip``, ``max_grad_norm`` and ``kl_target`` (0 = off); ``kl_coef`` is given as a float or a list and kept as a device tensor
-    f32 [P] (``self.kl_coef``), since the update adapts it on the device.  With every extended setting 0 the plain entry points run."""
+    f32 [P] (``self.kl_coef``), since the update adapts it on the device.  With every extended setting 0 the plain entry points run.
+    ``adv_norm="minibatch"`` (one mode for all members) normalises every member's advantages inside each of ITS minibatches, as
+    Stable-Baselines' PPO2 does, instead of once per rollout (ssg_ppo_set_adv_norm; ``minibatch_adv_stats()``)."""
 
     def __init__(self, population, env, gamma=0.99, lam=0.95, clip=0.2, vf_coef=0.5, ent_coef=0.01, lr=3e-4, beta1=0.9, beta2=0.999,
-                 eps=1e-8, adv_eps=1e-8, vf_clip=0.0, max_grad_norm=0.0, kl_coef=0.0, kl_target=0.0):
+                 eps=1e-8, adv_eps=1e-8, vf_clip=0.0, max_grad_norm=0.0, kl_coef=0.0, kl_target=0.0, adv_norm="batch"):
         torch = _torch()
         self.population, self.env = population, env
         P = len(population)
+        # "batch": every member's advantages are normalised once per rollout; "minibatch": inside every minibatch (PPO2's rule), the
+        # same mode for all members
+        self.adv_norm = adv_norm
+        self._adv_mode = adv_norm_mode(adv_norm, "PopulationPPO")
+        self._adv_scratch = adv_norm_scratch(P, population.device) if self._adv_mode == N.ADV_NORM_MINIBATCH else None
         if env.states_history != population.obs_dim:
             raise ValueError("PopulationPPO: the env's observation width %d differs from the population's obs_dim %d"
                              % (env.states_history, population.obs_dim))
@@ -362,6 +369,17 @@ class PopulationPPO(object):
         """f32 [P, 3] device view: per member the advantage mean, std + adv_eps and its inverse, as the last gae() left them."""
         return self.workspace[:16 * self.n_members].view(_torch().float32).view(self.n_members, 4)[:, :3]
 
+    def _bind_adv_norm(self):
+        """(Re)bind this object's mode on the env (host only): two trainers on one env cannot inherit each other's."""
+        self.env.set_adv_norm(self._adv_mode, self._adv_scratch, self.n_members)
+
+    def minibatch_adv_stats(self):
+        """f32 [P, 4] device view of the scratch: per member {mean, std + adv_eps, its inverse, 0} of the LAST minibatch an update() of
+        this object normalised that member by (adv_norm="minibatch" only)."""
+        if self._adv_scratch is None:
+            raise ValueError("PopulationPPO.minibatch_adv_stats: adv_norm is %r" % (self.adv_norm,))
+        return adv_norm_views(self._adv_scratch, self.n_members)[0]
+
     def update(self, batch, perm, epochs, minibatches, stats=False):
         """epochs x chunks of {gradient, Adam} for every member from ONE library call.  perm: int64 [P, epochs, K*n] — member m's
         minibatches are perm[m, e].chunk(minibatches), indices into ITS samples (i = t*n + e).  stats=True returns f32
@@ -399,6 +417,7 @@ class PopulationPPO(object):
         st = torch.empty((P, steps, N.PPO_EXT_STATS if extended else 4), dtype=torch.float32, device=dev) if stats else None
         pop, h = self.population.to_native(), self.env._h
         steps0 = self._steps0()
+        self._bind_adv_norm()
         with torch.cuda.device(dev):
             table = self._table(steps, steps0 if self.diverged() else None)
             if extended:
@@ -454,6 +473,7 @@ class PopulationPPO(object):
         ep, mb = (C.c_int32 * P)(*epochs), (C.c_int32 * P)(*minibatches)
         steps0 = self._steps0()
         pop, h = self.population.to_native(), self.env._h
+        self._bind_adv_norm()
         with torch.cuda.device(dev):
             table = self._table(launches, steps0)
             dev_sched = torch.frombuffer(sched, dtype=torch.int32).to(dev)  # (a copy: the host array is free after the call)

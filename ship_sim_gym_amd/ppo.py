@@ -15,6 +15,10 @@ vf_clip_param), ``max_grad_norm`` is torch's clip_grad_norm_ on the whole gradie
 and ``kl_target`` adapts that coefficient after every update as RLlib's update_kl does (train/rllib/pbt.py:55-62 starts it at 1.0).  The
 KL term needs the acting policy's whole distribution, batch["logp_all"] (f32 [K, N, 4]): ``dist(batch)`` computes it from the stored
 observations, and ``update`` does so itself when the batch has none — so call it BEFORE anything changes the parameters.
+
+``adv_norm="minibatch"`` normalises the advantages inside every minibatch with that minibatch's own mean and unbiased std, as PPO2's
+_train_step does (ssg_ppo_set_adv_norm), instead of once per rollout with gae()'s statistics; ``minibatch_adv_stats()`` shows the last
+minibatch's row and ``minibatch_adv_reference`` restates the device's order of operations in numpy.
 """
 import ctypes as C
 
@@ -33,13 +37,88 @@ def chunk_split(n, minibatches):
     return chunk, -(-int(n) // chunk)
 
 
+ADV_NORM_MODES = {"batch": N.ADV_NORM_BATCH, "minibatch": N.ADV_NORM_MINIBATCH}
+
+
+def adv_norm_mode(name, who):
+    """The library's mode for a trainer's ``adv_norm`` argument ("batch" or "minibatch")."""
+    if name not in ADV_NORM_MODES:
+        raise ValueError("%s: adv_norm must be 'batch' or 'minibatch' (got %r)" % (who, name))
+    return ADV_NORM_MODES[name]
+
+
+def adv_norm_scratch(n_members, device):
+    """A zeroed scratch tensor of ssg_ppo_adv_norm_nbytes(n_members) bytes (torch's allocations are 256-byte aligned)."""
+    need = C.c_size_t()
+    N.check(N.lib().ssg_ppo_adv_norm_nbytes(int(n_members), C.byref(need)), None, "ssg_ppo_adv_norm_nbytes")
+    return _torch().zeros(need.value, dtype=_torch().uint8, device=device)
+
+
+def adv_norm_views(scratch, n_members):
+    """(stats f32 [n_members, 4], partials f64 [n_members, 64, 3]) device views of a scratch of adv_norm_scratch(n_members): every
+    member's row {mean, std + adv_eps, its inverse, 0} and its (s, q, c) partials, of which the last minibatch of M indices wrote the
+    first min(64, ceil(M / 1024))."""
+    torch = _torch()
+    P = int(n_members)
+    off = (16 * P + 255) // 256 * 256
+    return (scratch[:16 * P].view(torch.float32).view(P, 4),
+            scratch[off: off + P * N.ADV_NORM_BLOCKS * 24].view(torch.float64).view(P, N.ADV_NORM_BLOCKS, 3))
+
+
+def _tree256(x):
+    """The 256-entry halving tree of the kernels (w = 128 .. 1: entry t += entry t + w) down column 0 of x (f64 [256, c], overwritten)."""
+    w = 128
+    while w:
+        x[:w] += x[w: 2 * w]
+        w >>= 1
+    return x[0]
+
+
+def minibatch_adv_reference(adv_gathered_f32, valid, adv_eps, partials=False):
+    """The two launches of SSG_ADV_NORM_MINIBATCH restated in numpy, in their order of operations: the stats row f32 [4] = {mean,
+    std + adv_eps, its inverse, 0} of ONE minibatch.  adv_gathered_f32: the advantages at the minibatch's M positions, in the
+    minibatch's order (anything where valid is False); valid: bool [M], the positions whose index lies in [0, n_samples).
+    partials=True: (row, the first launch's f64 [B, 3] partials (s, q, c), B = min(64, ceil(M / 1024))) — the f32 row alone seldom
+    shows a change of the f64 order, the partials do."""
+    import numpy as np
+    a = np.where(np.asarray(valid, dtype=bool), np.asarray(adv_gathered_f32, dtype=np.float32), np.float32(0)).astype(np.float64)
+    c = np.asarray(valid, dtype=bool).astype(np.float64).reshape(-1)
+    a = a.reshape(-1)
+    M = a.size
+    B = min(N.ADV_NORM_BLOCKS, -(-M // N.ADV_NORM_SPAN))
+    span = max(B, 1) * 256
+    rounds = -(-M // span) if M else 0
+    cols = np.zeros((rounds * span, 3))
+    cols[:M, 0], cols[:M, 1], cols[:M, 2] = a, a * a, c
+    cols = cols.reshape(rounds, max(B, 1), 256, 3)
+    acc = np.zeros((max(B, 1), 256, 3))
+    for r in range(rounds):  # thread t of workgroup b: positions b*256 + t, then steps of B*256, added in that order
+        acc += cols[r]
+    part = np.zeros((256, 3))
+    for b in range(B):  # the workgroup's tree; one (s, q, c) partial
+        part[b] = _tree256(acc[b].copy())
+    s, q, cnt = _tree256(part.copy())  # the finalising workgroup: partial b in entry b, zeros beyond
+    if cnt == 0.0:
+        row = np.array([0.0, 1.0, 1.0, 0.0], dtype=np.float32)
+    else:
+        mean = s / cnt
+        var = max(0.0, (q - s * mean) / (cnt - 1.0)) if cnt > 1.0 else 0.0
+        stdp = np.float32(np.sqrt(var)) + np.float32(adv_eps)
+        row = np.array([np.float32(mean), stdp, np.float32(1.0) / stdp, 0.0], dtype=np.float32)
+    return (row, part[:B].copy()) if partials else row
+
+
 class NativePPO(object):
     """Defaults: train/ppo_torch.py's (Adam lr 3e-4, betas (0.9, 0.999), eps 1e-8; clip 0.2; loss pg + 0.5*vf - 0.01*entropy)."""
 
     def __init__(self, policy, env, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, clip=0.2, vf_coef=0.5, ent_coef=0.01, adv_eps=1e-8,
-                 vf_clip=0.0, max_grad_norm=0.0, kl_coef=0.0, kl_target=0.0):
+                 vf_clip=0.0, max_grad_norm=0.0, kl_coef=0.0, kl_target=0.0, adv_norm="batch"):
         torch = _torch()
         self.policy, self.env = policy, env
+        # "batch": the advantages are normalised once per rollout (gae()'s statistics); "minibatch": inside every minibatch, PPO2's rule
+        self.adv_norm = adv_norm
+        self._adv_mode = adv_norm_mode(adv_norm, "NativePPO")
+        self._adv_scratch = adv_norm_scratch(1, policy.device) if self._adv_mode == N.ADV_NORM_MINIBATCH else None
         if env.states_history != policy.obs_dim:
             raise ValueError("NativePPO: the env's observation width %d differs from the policy's obs_dim %d" % (env.states_history, policy.obs_dim))
         hp = N.PpoHparams()
@@ -165,6 +244,23 @@ class NativePPO(object):
         """f32 [3] device view: the advantage mean, std + adv_eps and its inverse, as the last gae() left them."""
         return self.workspace[:16].view(_torch().float32)[:3]
 
+    def _bind_adv_norm(self):
+        """(Re)bind this object's mode on the env (host only): two trainers on one env cannot inherit each other's."""
+        self.env.set_adv_norm(self._adv_mode, self._adv_scratch, 1)
+
+    def minibatch_adv_stats(self):
+        """f32 [1, 4] device view of the scratch: {mean, std + adv_eps, its inverse, 0} of the LAST minibatch a grad() / update() call
+        of this object normalised by (adv_norm="minibatch" only)."""
+        if self._adv_scratch is None:
+            raise ValueError("NativePPO.minibatch_adv_stats: adv_norm is %r" % (self.adv_norm,))
+        return adv_norm_views(self._adv_scratch, 1)[0]
+
+    def minibatch_adv_partials(self):
+        """f64 [1, 64, 3] device view of the scratch: the (s, q, c) partial sums of that last minibatch (adv_norm_views)."""
+        if self._adv_scratch is None:
+            raise ValueError("NativePPO.minibatch_adv_partials: adv_norm is %r" % (self.adv_norm,))
+        return adv_norm_views(self._adv_scratch, 1)[1]
+
     def grad(self, batch, idx, stats=False):
         """The gradient (f32 [P], the packed layout) of the PPO loss over the samples idx (int64) of a batch gae() has seen; with
         stats=True also the minibatch means (pg loss, (v - ret)^2, entropy, clip fraction) as f32 [4].  With an extended term on: the
@@ -179,6 +275,7 @@ class NativePPO(object):
         st = torch.empty(ncol, dtype=torch.float32, device=self.policy.device) if stats else None
         ws, nb = self._ws_ptr()
         pol, h = self.policy.to_native(), self.env._h
+        self._bind_adv_norm()
         with torch.cuda.device(self.policy.device):
             if self.extended():
                 ext = self._ext(batch, n)
@@ -218,6 +315,7 @@ class NativePPO(object):
         st = torch.empty((int(epochs) * n_chunks, ncol), dtype=torch.float32, device=self.policy.device) if stats else None
         ws, nb = self._ws_ptr()
         pol, h = self.policy.to_native(), self.env._h
+        self._bind_adv_norm()
         with torch.cuda.device(self.policy.device):
             if self.extended():
                 ext = self._ext(batch, n)

@@ -769,6 +769,23 @@ class ShipVecEnv(*_BASES):
         """The bound ObsFilter, or None."""
         return getattr(self, "_obs_filter", None)
 
+    # ------------------------------------------------------------------------------------------------
+    # per-minibatch advantage normalisation (ssg_ppo_set_adv_norm; NativePPO / PopulationPPO bind their own before every call)
+    # ------------------------------------------------------------------------------------------------
+    def set_adv_norm(self, mode, scratch=None, n_members=1):
+        """Bind the advantage-normalisation mode of the device PPO update: N.ADV_NORM_BATCH (the default: once per rollout, nothing
+        bound) or N.ADV_NORM_MINIBATCH (PPO2's rule) with `scratch`, a uint8 device tensor of ssg_ppo_adv_norm_nbytes(n_members) bytes
+        that the caller keeps alive.  Host only; a refused binding leaves the old one in place."""
+        ptr, nb = (C.c_void_p(scratch.data_ptr()), scratch.numel() * scratch.element_size()) if scratch is not None else (None, 0)
+        N.check(N.lib().ssg_ppo_set_adv_norm(self._h, int(mode), int(n_members), ptr, nb), self._h, "ssg_ppo_set_adv_norm")
+        self._adv_norm_scratch = scratch if int(mode) == N.ADV_NORM_MINIBATCH else None
+
+    def adv_norm(self):
+        """(mode, n_members) as bound (ssg_ppo_get_adv_norm)."""
+        mode, members = C.c_int(), C.c_int()
+        N.check(N.lib().ssg_ppo_get_adv_norm(self._h, C.byref(mode), C.byref(members)), self._h, "ssg_ppo_get_adv_norm")
+        return mode.value, members.value
+
     def random_actions(self, seed, step0, K):
         """int32 [K, N] Philox action stream keyed by (seed, step, global env id), generated on the device."""
         torch = _torch()

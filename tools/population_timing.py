@@ -31,10 +31,16 @@ layout is re-bound between the runs (binding is not timed):
     the equal layout at the same N: the rollout step; and its GAE + update against a loop of the members' ``NativePPO.gae`` +
     ``.update`` on shards of those sizes.
 
+With ``--adv-norm`` (per-minibatch advantage normalisation, ssg_ppo_set_adv_norm), instead, per configuration:
+
+(g) GAE + update of the population with ``adv_norm="minibatch"`` against the same with ``adv_norm="batch"`` (the yardstick: the code
+    path that existed before), two PopulationPPO objects on one handle, alternating; ``batch_spread`` is (max - min) / median over
+    the batch-mode repeats.
+
 Each figure: 2 warm-up runs, then the median of ``--repeats`` (5) runs, alternating the two paths, each bracketed by a synchronize and
 timed with HIP events.  One JSON line on stdout.
 
-    python tools/population_timing.py [--configs 16x4096,120x512] [--horizon 32] [--repeats 5] [--sched | --slices]
+    python tools/population_timing.py [--configs 16x4096,120x512] [--horizon 32] [--repeats 5] [--sched | --slices | --adv-norm]
 """
 import argparse
 import importlib.util
@@ -347,6 +353,49 @@ def measure_slices(mod, members, n, horizon, repeats, dev, epochs=2, minibatches
     return out
 
 
+def measure_adv_norm(mod, members, n, horizon, repeats, dev, epochs=2, minibatches=4):
+    from ship_sim_gym_amd.population import NativePopulation, PopulationPPO
+    torch.manual_seed(0)
+    P, N = members, members * n
+    env = mod.ShipVecEnv(N, mod.GameConfig, mod.EnvConfig, device=dev, n_maps=64)
+    D, A = env.states_history, env.action_space.n
+    scale = torch.full((D,), float(max(env.bounds)), dtype=torch.float64, device=dev)
+    pop = NativePopulation.from_actor_critics([mod.ActorCritic(D, A).to(dev) for _ in range(P)], scale)
+    p0 = pop.params.clone()
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    env.reset_tensor()
+    b = dict(env.rollout_population(pop, horizon, uniforms=torch.rand((horizon, N), generator=gen, device=dev)))
+    samples = horizon * n
+    perm = torch.rand((P, epochs, samples), generator=gen, device=dev).argsort(dim=-1)
+    ppos = {"batch": PopulationPPO(pop, env), "minibatch": PopulationPPO(pop, env, adv_norm="minibatch")}  # (each call binds its own mode)
+
+    def restore(k):
+        pop.params.copy_(p0)
+        ppos[k].adam_mv.zero_()
+        ppos[k].step = 0
+        ppos[k].member_steps = [0] * P
+
+    def upd(k):
+        def run():
+            nb = dict(b)
+            ppos[k].gae(nb)
+            ppos[k].update(nb, perm, epochs, minibatches)
+        return run
+
+    t = _alternate([("batch", upd("batch")), ("minibatch", upd("minibatch"))], repeats, before=restore)
+    out = {}
+    for k in ("batch", "minibatch"):
+        out[k + "_update_ms"] = statistics.median(t[k])
+        out[k + "_update_ms_all"] = [round(x, 3) for x in t[k]]
+    out["batch_spread"] = (max(t["batch"]) - min(t["batch"])) / statistics.median(t["batch"])
+    out["minibatch_over_batch"] = out["minibatch_update_ms"] / out["batch_update_ms"]
+    env.close()
+    out.update({"members": P, "envs_per_member": n, "horizon": horizon, "epochs": epochs, "minibatches": minibatches,
+                "samples_per_minibatch": -(-samples // minibatches)})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="16x4096,120x512")
@@ -354,8 +403,13 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--sched", action="store_true", help="time per-member schedules (ssg_pop_update_sched) instead")
     ap.add_argument("--slices", action="store_true", help="time unequal env slices (ssg_pop_set_slices) instead")
+    ap.add_argument("--adv-norm", action="store_true", help="time per-minibatch advantage normalisation against batch mode instead")
     a = ap.parse_args()
     mod = _ppo()
+    if a.adv_norm:
+        res = [measure_adv_norm(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.horizon, a.repeats, "cuda:0") for c in a.configs.split(",")]
+        print(json.dumps({"population_adv_norm_timing": res}))
+        return
     if a.slices:
         res = [measure_slices(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.horizon, a.repeats, "cuda:0") for c in a.configs.split(",")]
         print(json.dumps({"population_slices_timing": res}))

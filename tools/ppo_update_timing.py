@@ -9,6 +9,7 @@ every update from the same parameters' values (their own copies) and draw their 
 line on stdout.  The kernels alone: `rocprofv3 --kernel-trace --stats -- python tools/ppo_update_timing.py --only native` (tools/README.md).
 
     python tools/ppo_update_timing.py [--configs 65536x32,4096x64] [--repeats 7] [--only torch|native] [--ext] [--separate-value] [--ret-filter]
+                                      [--adv-norm]
 
 --ext adds, in the same run, the extended update (NativePPO with vf_clip 0.2, max_grad_norm 0.5, kl_coef 1.0, kl_target 0.01: GAE, the
 ssg_ppo_dist launch, ssg_ppo_update_ext) as the path "native_ext", and the ssg_ppo_dist launch alone as "dist".
@@ -17,6 +18,8 @@ a value network of its own (two 64-64 towers: SSG_POLICY_SEPARATE_VALUE); its re
 --ret-filter adds, in the same run and alternating with the others, return normalisation (ship_sim_gym_amd/ret_filter.py): "gae" (ssg_ppo_gae
 alone), "ret_gae" (ssg_ret_filter_apply updating, then GAE on its output), "ret_frozen" (the frozen apply alone: one launch), "ret_apply"
 (the updating apply alone: three launches) and "native_ret" (the whole GAE + update with the filter, to set against "native").
+--adv-norm adds, in the same run and alternating with the others, "native_mbnorm": the whole GAE + update of a NativePPO with
+adv_norm="minibatch" (two more launches ahead of every minibatch's gradient launch), to set against "native" (batch mode).
 """
 import argparse
 import importlib.util
@@ -78,7 +81,8 @@ def torch_update(net, opt, b, horizon, envs, D, epochs, minibatches, gen, gamma=
             opt.step()
 
 
-def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext=False, separate_value=False, ret_filter=False):
+def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext=False, separate_value=False, ret_filter=False,
+            adv_norm=False):
     from ship_sim_gym_amd.policy import NativePolicy
     from ship_sim_gym_amd.ppo import NativePPO
     torch.manual_seed(0)
@@ -146,7 +150,22 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
         ppo.gae(nb, return_filter=rflt)
         ppo.update(nb, torch.stack([torch.randperm(n, device=dev, generator=g_r) for _ in range(epochs)]), epochs, minibatches)
 
+    ppo_m = NativePPO(pol, env, adv_norm="minibatch") if adv_norm else None  # (every call binds its object's own mode on the env)
+    g_m = torch.Generator(device=dev)
+    g_m.manual_seed(1)
+
+    def run_native_mbnorm():
+        with torch.no_grad():
+            for p, q in zip(net_n.parameters(), p0):
+                p.copy_(q)
+        pol.refresh()
+        nb = dict(b)
+        ppo_m.gae(nb)
+        ppo_m.update(nb, torch.stack([torch.randperm(n, device=dev, generator=g_m) for _ in range(epochs)]), epochs, minibatches)
+
     paths = [(k, f) for k, f in (("torch", run_torch), ("native", run_native)) if only in (None, k)]
+    if adv_norm:
+        paths.append(("native_mbnorm", run_native_mbnorm))
     if ext:
         paths += [("native_ext", run_native_ext), ("dist", run_dist)]
     if ret_filter:
@@ -179,9 +198,11 @@ def main():
     ap.add_argument("--separate-value", action="store_true", help="also measure the separate-value-network shape, in the same process")
     ap.add_argument("--ret-filter", action="store_true", help="also time return normalisation: GAE alone, apply + GAE, the frozen apply, "
                                                               "the updating apply, and the whole GAE + update with the filter")
+    ap.add_argument("--adv-norm", action="store_true", help="also time the whole GAE + update with per-minibatch advantage normalisation")
     a = ap.parse_args()
     mod = _ppo()
-    res = [measure(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.repeats, a.only, "cuda:0", ext=a.ext, separate_value=sep, ret_filter=a.ret_filter)
+    res = [measure(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.repeats, a.only, "cuda:0", ext=a.ext, separate_value=sep, ret_filter=a.ret_filter,
+                   adv_norm=a.adv_norm)
            for c in a.configs.split(",") for sep in ([False, True] if a.separate_value else [False])]
     print(json.dumps({"ppo_update_timing": res}))
 

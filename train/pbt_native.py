@@ -128,6 +128,8 @@ def make_arg_parser():
                     help="divide the rewards GAE sees by a running std of the discounted return, per member on the device; default: raw rewards")
     ap.add_argument("--reward-clip", type=float, default=10.0, metavar="C",
                     help="clamp the normalised rewards to +-C (needs --norm-reward; 0: no clamp)")
+    ap.add_argument("--adv-norm", choices=("batch", "minibatch"), default="batch",
+                    help="normalise every member's advantages once per rollout, or inside every minibatch as Stable-Baselines' PPO2 does")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -191,7 +193,7 @@ def parse_args(argv=None):
 def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every=5, seed=0, epochs=2, minibatches=4, lrs=None,
           pbt=True, device="cuda:0", log=print, return_details=False, kl_coeff=0.0, kl_target=0.01, vf_clip=0.0, max_grad_norm=0.0,
           separate_value=False, mutate_schedule=False, max_epochs=30, eval_every=0, eval_episodes=1, envs=None, mutate_batch=False,
-          batch_shares=None, quantum=None, obs_filter=False, norm_reward=False, reward_clip=10.0):
+          batch_shares=None, quantum=None, obs_filter=False, norm_reward=False, reward_clip=10.0, adv_norm="batch"):
     import torch
     from ship_gym.config import EnvConfig, GameConfig
     from ship_sim_gym_amd.population import NativePopulation, PBTScheduler, PopulationPPO, reference_mutations, slices_for_batch_sizes
@@ -246,7 +248,7 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
         reslices.append((0, list(slices)))
         log("slices: train_batch_size %s -> envs %s (quantum %d)" % (batch_sizes, slices, quantum))
     ppo = PopulationPPO(pop, env, lam=INITIAL["lambda"], clip=INITIAL["clip_param"], lr=list(lrs) if lrs is not None else INITIAL["lr"],
-                        vf_clip=vf_clip, max_grad_norm=max_grad_norm, kl_coef=kl_coeff, kl_target=kl_target if kl_coeff > 0 else 0.0)
+                        vf_clip=vf_clip, max_grad_norm=max_grad_norm, kl_coef=kl_coeff, kl_target=kl_target if kl_coeff > 0 else 0.0, adv_norm=adv_norm)
     flt = None
     if obs_filter:  # per-member statistics; a member's rows are its slice, whatever the slices currently are
         from ship_sim_gym_amd.obs_filter import ObsFilter
@@ -375,7 +377,7 @@ def main(argv=None):
           kl_target=a.kl_target, vf_clip=a.vf_clip, max_grad_norm=a.max_grad_norm, separate_value=a.separate_value,
           mutate_schedule=a.mutate_schedule, max_epochs=a.max_epochs, eval_every=a.eval_every, eval_episodes=a.eval_episodes, envs=a.envs,
           mutate_batch=a.mutate_batch, batch_shares=a.batch_shares, quantum=a.quantum, obs_filter=a.obs_filter,
-          norm_reward=a.norm_reward, reward_clip=a.reward_clip)
+          norm_reward=a.norm_reward, reward_clip=a.reward_clip, adv_norm=a.adv_norm)
 
 
 if __name__ == "__main__":

@@ -216,8 +216,10 @@ def rollout(shards, horizon, mode, gen, policy=None):
 def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, gamma=0.99, lam=0.95, clip=0.2,
           device="cuda:0", seed=0, log=print, mode="eager", return_details=False, env_kw=None, update="torch", separate_value=False,
           eval_every=0, eval_episodes=1, eval_envs=None, obs_filter=False, save_obs_filter=None,
-          norm_reward=False, reward_clip=10.0):
+          norm_reward=False, reward_clip=10.0, adv_norm="batch"):
     assert mode in ("eager", "graph", "pingpong", "native")
+    if adv_norm not in ("batch", "minibatch"):
+        raise ValueError("adv_norm must be 'batch' or 'minibatch' (got %r)" % (adv_norm,))
     if (obs_filter or save_obs_filter) and mode != "native":
         raise ValueError("obs_filter normalises inside the native policy launch: it needs mode='native' (got mode=%r)" % (mode,))
     if save_obs_filter and not obs_filter:
@@ -246,7 +248,7 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
     for sh in shards:
         sh.env.reset_tensor()
     policy = NativePolicy.from_actor_critic(net, shards[0].scale) if mode == "native" else None
-    ppo = NativePPO(policy, shards[0].env, lr=lr, clip=clip) if update == "native" else None
+    ppo = NativePPO(policy, shards[0].env, lr=lr, clip=clip, adv_norm=adv_norm) if update == "native" else None
     flt = None
     if obs_filter:  # (the rollout loop merges each step's observations, then normalises them; obs_scale is no longer read)
         from ship_sim_gym_amd.obs_filter import ObsFilter
@@ -317,7 +319,8 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
                 nxt = b["val"][t]
             b_obs, b_act = b["obs"].reshape(horizon * envs, D), b["act"].reshape(-1)
             b_logp, b_adv, b_ret = b["logp"].reshape(-1), torch.cat(advs), torch.cat(rets)
-            b_adv = (b_adv - b_adv.mean()) / (b_adv.std() + 1e-8)
+            if adv_norm == "batch":
+                b_adv = (b_adv - b_adv.mean()) / (b_adv.std() + 1e-8)
             n = b_obs.shape[0]
             for _ in range(epochs):
                 perm = torch.randperm(n, device=dev, generator=gen)
@@ -325,7 +328,11 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
                     logits, val = net(b_obs[mb])
                     dist = torch.distributions.Categorical(logits=logits)
                     ratio = torch.exp(dist.log_prob(b_act[mb]) - b_logp[mb])
-                    pg = -torch.min(ratio * b_adv[mb], torch.clamp(ratio, 1 - clip, 1 + clip) * b_adv[mb]).mean()
+                    mb_adv = b_adv[mb]
+                    if adv_norm == "minibatch":  # PPO2's rule, as the device update applies it: the minibatch's own mean / unbiased std
+                        mb_std = mb_adv.std() if mb_adv.numel() > 1 else mb_adv.new_zeros(())  # (one sample: a std of 0, not NaN)
+                        mb_adv = (mb_adv - mb_adv.mean()) / (mb_std + 1e-8)
+                    pg = -torch.min(ratio * mb_adv, torch.clamp(ratio, 1 - clip, 1 + clip) * mb_adv).mean()
                     loss = pg + 0.5 * (val - b_ret[mb]).pow(2).mean() - 0.01 * dist.entropy().mean()
                     opt.zero_grad(); loss.backward(); opt.step()
             if policy is not None:
@@ -392,6 +399,8 @@ def make_arg_parser():
                          "--update native); default: raw rewards")
     ap.add_argument("--reward-clip", type=float, default=10.0, metavar="C",
                     help="clamp the normalised rewards to +-C (needs --norm-reward; 0: no clamp)")
+    ap.add_argument("--adv-norm", choices=("batch", "minibatch"), default="batch",
+                    help="normalise the advantages once per rollout, or inside every minibatch as Stable-Baselines' PPO2 does (either --update)")
     return ap
 
 
@@ -422,4 +431,4 @@ if __name__ == "__main__":
     a = parse_args()
     train(envs=a.envs, updates=a.updates, horizon=a.horizon, mode=a.mode, update=a.update, separate_value=a.separate_value,
           eval_every=a.eval_every, eval_episodes=a.eval_episodes, obs_filter=a.obs_filter, save_obs_filter=a.save_obs_filter,
-          norm_reward=a.norm_reward, reward_clip=a.reward_clip)
+          norm_reward=a.norm_reward, reward_clip=a.reward_clip, adv_norm=a.adv_norm)
