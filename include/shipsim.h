@@ -596,7 +596,12 @@ int ssg_ppo_update(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *
  *
  * The coefficient's adaptation (kl_target > 0; RLlib's update_kl): the last launch of an _ext update takes the f32 mean of mean(KL)
  * over the last epoch's minibatches (a running f32 sum in chunk order, kept in the workspace, divided by the number of chunks) and
- * multiplies *dev_kl_coef by 1.5 when that mean is above 2*kl_target, by 0.5 when it is below 0.5*kl_target.
+ * multiplies *dev_kl_coef by 1.5 when that mean is above 2*kl_target, by 0.5 when it is below 0.5*kl_target.  Both inequalities
+ * are strict, in f32: a mean of exactly 2*kl_target or 0.5*kl_target leaves the coefficient alone.  The divisor is the number of
+ * chunks MADE (ceil(n / ceil(n / minibatches)), which can be fewer than minibatches), and the sum restarts on every epoch's first
+ * chunk, so neither an earlier epoch nor an earlier call enters.  On per-member schedules (ssg_pop_update_sched) member m's mean is
+ * over ITS last epoch's chunks_m minibatches, however many launches ago that epoch ended.  A kl_target <= 0 keeps the coefficient,
+ * whatever the sum holds; the sum is kept whether or not dev_stats is given.
  *
  * Stats rows of the _ext entry points are f32[8]: [0..3] as above with [1] = mean(VL), [4] mean(KL), [5] the global gradient norm
  * before clipping (0 when max_grad_norm is off), [6] the KL coefficient the minibatch used, [7] 0.  No floating-point atomics; a

@@ -174,18 +174,43 @@ def ref_update(torch, pol, b, advn, perms, minibatches, dtype, adam=None, max_gr
     return p.detach(), opt.state[p], kls
 
 
-def kl_adapt(coef, kls, target):
-    """RLlib's update_kl restated in numpy float32 on the last epoch's minibatch means, summed in chunk order."""
+def kl_mean(kls, divisor=None):
+    """The device's mean of minibatch means: their float32 sum in chunk order over float32(len(kls)) — or over `divisor`, for the
+    means a WRONG divisor would give."""
     s = np.float32(0.0)
     for k in kls:
         s = np.float32(s + np.float32(k))
-    mean = np.float32(s / np.float32(len(kls)))
+    return np.float32(s / np.float32(len(kls) if divisor is None else divisor))
+
+
+def kl_factor(mean, target):
+    """update_kl's decision on a float32 mean: 1.5 above 2 x target, 0.5 below 0.5 x target, else 1 (both inequalities strict)."""
     t = np.float32(target)
     if mean > np.float32(2.0) * t:
-        return np.float32(np.float32(coef) * np.float32(1.5))
+        return 1.5
     if mean < np.float32(0.5) * t:
-        return np.float32(np.float32(coef) * np.float32(0.5))
-    return np.float32(coef)
+        return 0.5
+    return 1.0
+
+
+def kl_adapt(coef, kls, target):
+    """RLlib's update_kl restated in numpy float32 on the last epoch's minibatch means, summed in chunk order."""
+    factor = kl_factor(kl_mean(kls), target)
+    return np.float32(coef) if factor == 1.0 else np.float32(np.float32(coef) * np.float32(factor))
+
+
+KL_BOUNDARY_FACTORS = (1.5, 1.0, 1.0, 0.5)
+
+
+def kl_boundary_targets(kls):
+    """[(target, expected factor)] x 4, in KL_BOUNDARY_FACTORS' order: the float32 targets at the two boundaries of kl_adapt's decision
+    on `kls` (the last epoch's minibatch means), as python floats — the float32 just below mean / 2 (the mean is above 2 x target:
+    1.5), mean / 2 and 2 x mean themselves (both inequalities are strict: 1), the float32 just above 2 x mean (0.5).  Halving and
+    doubling a normal float32 are exact, so each target is a float32 and passes a double -> float conversion unchanged."""
+    mean = kl_mean(kls)
+    half, twice = np.float32(mean / np.float32(2.0)), np.float32(np.float32(2.0) * mean)
+    targets = [np.nextafter(half, np.float32(0.0)), half, twice, np.nextafter(twice, np.float32(np.inf))]
+    return [(float(t), f) for t, f in zip(targets, KL_BOUNDARY_FACTORS)]
 
 
 def check_per_tensor(torch, pol, mine, ref64, ref32, what, verbose=False):

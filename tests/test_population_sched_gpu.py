@@ -124,7 +124,8 @@ EXT4 = {"vf_clip": [10.0, 0.05, 0.0, 0.2], "max_grad_norm": [0.0, 0.03, 0.0, 0.5
 
 def test_extended_loss_on_uneven_schedules(torch_cuda):
     """800 samples per member; steps 8 / 1 / 15 / 6 (chunks of 200, 800, 160 and 267, 267, 266).  Each member's coefficient is adapted
-    from ITS last epoch's chunks: member 0's mean KL is far above 2 x 1e-4 (x 1.5), member 3's far below 0.5 x 10 (x 0.5)."""
+    from ITS last epoch's chunks: member 0's mean KL is far above 2 x 1e-4 (x 1.5), member 3's far below 0.5 x 10 (x 0.5).
+    (Targets AT the decision's boundaries, which tell the epoch's mean from a wrong sum or divisor: tests/test_kl_adapt_gpu.py.)"""
     torch = torch_cuda
     assert _expected_steps(800, [2, 1, 3, 2], [4, 1, 5, 3]) == [8, 1, 15, 6]
     ppo, refs, st = _check_rounds(torch, _setup(torch, 4, 100, 8), 8, EXT4, [([2, 1, 3, 2], [4, 1, 5, 3])])

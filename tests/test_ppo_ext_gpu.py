@@ -218,6 +218,7 @@ def _ref_update(torch, pol, b, advn, perm, epochs, minibatches, dtype, max_norm,
 
 
 def test_whole_ext_update_against_f64_adapts_the_coefficient_and_repeats(torch_cuda):
+    """The targets here are a factor of 4 from the mean KL; tests/test_kl_adapt_gpu.py puts them AT the decision's boundaries."""
     torch = torch_cuda
     env, pol, b, advn, st = _batch_for(torch, 64, 2, "tanh", 3, n=2048, K=8)
     n = b["act"].numel()
@@ -259,7 +260,8 @@ def test_whole_ext_update_against_f64_adapts_the_coefficient_and_repeats(torch_c
 @pytest.mark.parametrize("K,envs,minibatches,chunks", [(8, 125, 3, 3), (2, 5, 6, 5)])
 def test_whole_ext_update_at_uneven_chunkings(torch_cuda, K, envs, minibatches, chunks):
     """The shapes of the plain path's test_update_uneven_chunks_and_continuity with the three terms on: a last chunk shorter than the
-    others (334, 334, 332), then fewer chunks than asked (5 of 2 samples).  Stats rows, Adam steps and the adaptation count CHUNKS."""
+    others (334, 334, 332), then fewer chunks than asked (5 of 2 samples).  Stats rows, Adam steps and the adaptation count CHUNKS.
+    (The target is a factor of 4 from the mean KL; tests/test_kl_adapt_gpu.py has these chunkings AT the decision's boundaries.)"""
     torch = torch_cuda
     epochs = 2
     env, pol, b, advn, st = _batch_for(torch, 64, 2, "tanh", 3, n=envs, K=K)
