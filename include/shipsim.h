@@ -1150,6 +1150,47 @@ int ssg_ppo_set_adv_norm(ssg_handle *h, int mode, int n_members, void *dev_scrat
 int ssg_ppo_get_adv_norm(const ssg_handle *h, int *mode, int *n_members);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The minibatch permutations (ABI 9 addition): the shuffle of the update, drawn by the library
+ * Both reference trainers shuffle inside their update: PPO2's learn runs np.random.shuffle(inds) once per epoch behind model.learn
+ * (train/stable_baselines/ppo.py:90), and RLlib's SGD shuffles its minibatches the same way (train/rllib/pbt.py:50-62).  The update
+ * entry points above read a dev_perm the caller made; these fill one, so that a C caller needs no sort and no generator of its own.
+ *
+ * Element i of a row is a pure function of (seed, update, member, epoch, n, i), n the row's length: a keyed 8-round Feistel network
+ * over the smallest bit width b >= 8 with 2^b >= n, re-applied while the value is >= n (cycle walking); the round keys come from
+ * (seed, update, member, epoch, n) through a 64-bit integer mixer.  csrc/shipsim_perm.h is the definition (and the argument why every
+ * row is an exact permutation of [0, n)); the host entry and the kernel compile that one text, and ppo.perm_reference restates it in
+ * numpy.  The rows are bitwise reproducible: they do not depend on the launch geometry, the stream, the device or the entry point.
+ * `update` is the caller's count of updates (any value >= 0; the Python classes count their calls of update()), `member` the
+ * population member (0 for one policy), `epoch` the row within the call.  The stream of values is this library's own: it is NOT
+ * seed-compatible with numpy's or torch's generators, and no statistical claim beyond tests/test_perm.py's is made — it is a shuffle
+ * for minibatches, not a cryptographic permutation.  1 <= n <= 2^32.
+ *
+ * The walk is capped at 256 applications; a lane that reached the cap would write -1, which the gradient kernels treat as a zero,
+ * gradient-free sample.  csrc/shipsim_perm.h says why a row never holds one.
+ * ------------------------------------------------------------------------------------------------- */
+/* Replaces: np.random.shuffle(inds) of PPO2's learn (behind model.learn, train/stable_baselines/ppo.py:90), restated for the host; no
+ * device is needed.  Writes elements [first, first + count) of the row keyed (seed, update, member, epoch) over [0, n) to out (int64
+ * [count]).  SSG_ERR_BAD_ARG: NULL out; update, member or epoch < 0; n outside 1..2^32; first < 0, count < 1 or first + count > n. */
+int ssg_host_perm(uint64_t seed, int64_t update, int member, int epoch, int64_t n, int64_t first, int64_t count, int64_t *out);
+
+/* Replaces: the `noptepochs` shuffles of one PPO2 update (np.random.shuffle(inds) per epoch, train/stable_baselines/ppo.py:90).  Writes
+ * dev_perm int64 [epochs][n_samples], the layout ssg_ppo_update / ssg_ppo_update_ext read: row e is the row keyed (seed, update, member,
+ * e) over [0, n_samples), bit for bit ssg_host_perm's.  One launch on `stream`; no scratch, no atomics.  The arguments are judged first,
+ * then the handle (SSG_ERR_NOT_BOUND without a state blob, like every call that launches).  SSG_ERR_BAD_ARG, nothing launched: a NULL
+ * handle or dev_perm; update or member < 0; epochs < 1; n_samples outside 1..2^32. */
+int ssg_ppo_perm(ssg_handle *h, uint64_t seed, int64_t update, int member, int epochs, int64_t n_samples, int64_t *dev_perm, void *stream);
+
+/* Replaces: the same shuffles for every member of a population in ONE launch (each trial of train/rllib/pbt.py:50-62 shuffles its own
+ * minibatches, and each of the three PPO2 models of train/stable_baselines/ppo.py:90 shuffles inside its learn).  Member m's rows are bit for bit ssg_ppo_perm(..., member = m, n_samples = K * n_m): a member is the single policy on
+ * its shard here too.  Without slices bound to the handle: dev_perm int64 [members][perm_epochs][K * n], what ssg_pop_update /
+ * ssg_pop_update_ext (perm_epochs = epochs) and ssg_pop_update_sched read on equal slices.  With slices bound (ssg_pop_set_slices):
+ * the flat, unpadded layout ssg_pop_update_sched reads there — member m's block starts perm_epochs * (the samples K * n_j of the
+ * members j < m) entries in and holds perm_epochs rows of K * n_m; `n` is not read.  perm_epochs * K * n_envs entries are written in
+ * all.  SSG_ERR_BAD_ARG, nothing launched: a NULL handle or dev_perm; update < 0; K < 1; perm_epochs < 1; members outside
+ * 1..SSG_POP_MAX_MEMBERS or different from the bound slices' member count; without slices n < 1; a row longer than 2^32. */
+int ssg_pop_perm(ssg_handle *h, uint64_t seed, int64_t update, int members, int K, int n, int perm_epochs, int64_t *dev_perm, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Host-side geometry (what pymunk's cffi exposed at reset time); no GPU needed.
  * ------------------------------------------------------------------------------------------------- */
 /* Replaces cpConvexHull as reached by pm.Poly(...) (models.py:96,180).  out_xy holds >= count pairs. */

@@ -30,6 +30,8 @@ FILTER_TILE, FILTER_RUNS = 256, 8  # ssg_obs_filter_update's reduction order: ro
 RET_FILTER_UPDATE, RET_FILTER_MAX_STEPS = 0x1, 1024  # ssg_ret_filter.flags; the largest K of one ssg_ret_filter_apply call
 ADV_NORM_BATCH, ADV_NORM_MINIBATCH = 0, 1  # ssg_ppo_set_adv_norm's modes: once per rollout (the default), PPO2's per minibatch
 ADV_NORM_BLOCKS, ADV_NORM_SPAN = 64, 1024  # its reduction order: workgroups at most per member, minibatch positions per workgroup below that
+# the minibatch permutations (csrc/shipsim_perm.h): Feistel rounds, the bit-width floor, the cycle walk's cap, the largest row
+PERM_ROUNDS, PERM_MIN_BITS, PERM_WALK_CAP, PERM_MAX_N = 8, 8, 256, 1 << 32
 
 
 def pop_table_floats(n_members, n_steps):
@@ -73,6 +75,7 @@ EXPORTS = (
     "ssg_obs_filter_workspace_nbytes", "ssg_obs_filter_update", "ssg_set_obs_filter", "ssg_get_obs_filter",
     "ssg_ret_filter_workspace_nbytes", "ssg_ret_filter_apply",
     "ssg_ppo_adv_norm_nbytes", "ssg_ppo_set_adv_norm", "ssg_ppo_get_adv_norm",
+    "ssg_host_perm", "ssg_ppo_perm", "ssg_pop_perm",
 )
 
 
@@ -267,6 +270,9 @@ def lib():
     L.ssg_ppo_adv_norm_nbytes.argtypes = [C.c_int, szp]
     L.ssg_ppo_set_adv_norm.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
     L.ssg_ppo_get_adv_norm.argtypes = [vp, ip, ip]
+    L.ssg_host_perm.argtypes = [C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
+    L.ssg_ppo_perm.argtypes = [vp, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int64, vp, vp]
+    L.ssg_pop_perm.argtypes = [vp, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     L.ssg_render.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, vp]
     L.ssg_dyn_invalidate.argtypes = [vp, vp, vp]
     L.ssg_host_convex_hull.argtypes = [C.c_int, dp, dp, ip]

@@ -12,6 +12,7 @@
 
 #include "shipsim.h"
 #include "shipsim_internal.h"
+#include "shipsim_perm.h"
 
 struct ssg_handle {
     ssg_config cfg;
@@ -2239,6 +2240,77 @@ int ssg_ppo_get_adv_norm(const ssg_handle *h, int *mode, int *n_members)
     *mode = h->adv_norm_mode;
     *n_members = h->adv_norm_members;
     return SSG_OK;
+}
+
+// ABI 9 addition: the minibatch permutations (shipsim_perm.h).  The arguments are judged first (BAD_ARG), then the handle's state blob
+// (NOT_BOUND) and the device; nothing is enqueued before all of it passed.
+int ssg_host_perm(uint64_t seed, int64_t update, int member, int epoch, int64_t n, int64_t first, int64_t count, int64_t *out)
+{
+    if (!out) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_host_perm: NULL out");
+    if (update < 0 || member < 0 || epoch < 0) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_host_perm: update, member or epoch < 0");
+    if (n < 1 || (uint64_t)n > ssg::kPermMaxN) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_host_perm: n must be in 1..2^32");
+    if (first < 0 || count < 1 || first >= n || count > n - first)
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_host_perm: [first, first + count) must be a non-empty window of [0, n)");
+    const ssg::PermKey key = ssg::perm_key(seed, (uint64_t)update, (uint32_t)member, (uint32_t)epoch, (uint64_t)n);
+    for (int64_t i = 0; i < count; ++i) out[i] = ssg::perm_at(key, (uint32_t)(first + i));
+    return SSG_OK;
+}
+
+static int run_perm(ssg_handle *h, const ssg::PermLaunch &l, void *stream, const char *what)
+{
+    int rc = pop_bound(h);
+    if (rc == SSG_OK) rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    const hipError_t e = static_cast<hipError_t>(ssg::launch_perm(l, stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+int ssg_ppo_perm(ssg_handle *h, uint64_t seed, int64_t update, int member, int epochs, int64_t n_samples, int64_t *dev_perm, void *stream)
+{
+    if (!h) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_ppo_perm: NULL handle");
+    if (!dev_perm) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_perm: NULL dev_perm");
+    if (update < 0 || member < 0 || epochs < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_perm: update or member < 0, or epochs < 1");
+    if (n_samples < 1 || (uint64_t)n_samples > ssg::kPermMaxN) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_perm: n_samples must be in 1..2^32");
+    ssg::PermLaunch l{};
+    l.seed = seed;
+    l.update = (uint64_t)update;
+    l.member0 = member;
+    l.members = 1;
+    l.epochs = epochs;
+    l.n = n_samples;
+    l.out = dev_perm;
+    return run_perm(h, l, stream, "ssg_ppo_perm");
+}
+
+int ssg_pop_perm(ssg_handle *h, uint64_t seed, int64_t update, int members, int K, int n, int perm_epochs, int64_t *dev_perm, void *stream)
+{
+    if (!h) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_perm: NULL handle");
+    if (!dev_perm) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_perm: NULL dev_perm");
+    if (update < 0 || K < 1 || perm_epochs < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_perm: update < 0, K < 1 or perm_epochs < 1");
+    if (members < 1 || members > SSG_POP_MAX_MEMBERS) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_perm: members must be in 1..SSG_POP_MAX_MEMBERS");
+    ssg::PermLaunch l{};
+    l.seed = seed;
+    l.update = (uint64_t)update;
+    l.members = members;
+    l.epochs = perm_epochs;
+    l.K = K;
+    l.out = dev_perm;
+    if (!h->pop_sizes.empty()) {
+        if ((int)h->pop_sizes.size() != members) {
+            char buf[200];
+            std::snprintf(buf, sizeof buf, "ssg_pop_perm: %d members, but slices for %d members are bound to the handle (ssg_pop_set_slices)", members,
+                          (int)h->pop_sizes.size());
+            return fail(h, SSG_ERR_BAD_ARG, buf);
+        }
+        l.slices = h->dev_slices;
+        l.n = (long long)K * h->slice_max; // (the widest row; n is not read)
+    } else {
+        if (n < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_perm: n < 1");
+        l.n = (long long)K * n;
+    }
+    if ((uint64_t)l.n > ssg::kPermMaxN) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_perm: a row of K * n entries exceeds 2^32");
+    return run_perm(h, l, stream, "ssg_pop_perm");
 }
 
 int ssg_obs_filter_update(ssg_handle *h, const ssg_obs_filter *f, const double *dev_obs, void *stream)

@@ -134,13 +134,18 @@ class PopulationPPO(object):
     ``vf_clip``, ``max_grad_norm`` and ``kl_target`` (0 = off); ``kl_coef`` is given as a float or a list and kept as a device tensor
     f32 [P] (``self.kl_coef``), since the update adapts it on the device.  With every extended setting 0 the plain entry points run.
     ``adv_norm="minibatch"`` (one mode for all members) normalises every member's advantages inside each of ITS minibatches, as
-    Stable-Baselines' PPO2 does, instead of once per rollout (ssg_ppo_set_adv_norm; ``minibatch_adv_stats()``)."""
+    Stable-Baselines' PPO2 does, instead of once per rollout (ssg_ppo_set_adv_norm; ``minibatch_adv_stats()``).
+    ``perm_seed``: the library draws the members' minibatch permutations (ssg_pop_perm, one launch): ``update(batch, None, ...)``
+    shuffles every member as ``NativePPO(perm_seed=..., member=m)`` shuffles alone, keyed by ``updates``, this object's count of
+    update() calls; ``draw_perm`` returns them in the layout the bound state makes ``update`` expect."""
 
     def __init__(self, population, env, gamma=0.99, lam=0.95, clip=0.2, vf_coef=0.5, ent_coef=0.01, lr=3e-4, beta1=0.9, beta2=0.999,
-                 eps=1e-8, adv_eps=1e-8, vf_clip=0.0, max_grad_norm=0.0, kl_coef=0.0, kl_target=0.0, adv_norm="batch"):
+                 eps=1e-8, adv_eps=1e-8, vf_clip=0.0, max_grad_norm=0.0, kl_coef=0.0, kl_target=0.0, adv_norm="batch", perm_seed=None):
         torch = _torch()
         self.population, self.env = population, env
         P = len(population)
+        self.perm_seed = None if perm_seed is None else int(perm_seed)  # None: the caller brings every perm
+        self.updates = 0  # calls of update(); like `step`, a checkpoint may set it
         # "batch": every member's advantages are normalised once per rollout; "minibatch": inside every minibatch (PPO2's rule), the
         # same mode for all members
         self.adv_norm = adv_norm
@@ -380,6 +385,32 @@ class PopulationPPO(object):
             raise ValueError("PopulationPPO.minibatch_adv_stats: adv_norm is %r" % (self.adv_norm,))
         return adv_norm_views(self._adv_scratch, self.n_members)[0]
 
+    def draw_perm(self, batch_or_K, epochs, out=None):
+        """The permutations update(batch, None, epochs, ...) would use NOW, in the layout update() expects of `perm` in the env's
+        current state (ssg_pop_perm, one launch on the current stream): member m's row e is keyed (perm_seed, updates, m, e) over its
+        own K * n_m samples — NativePPO(perm_seed=..., member=m).draw_perm's rows bit for bit.  epochs: an int or the members' list
+        (max(epochs) rows each).  Equal slices: int64 [P, max(epochs), K*n]; slices bound to the env: the flat int64
+        [max(epochs) * K * num_envs] buffer, member after member.  batch_or_K: a batch or its rollout length K; out: a tensor of
+        that shape to fill."""
+        torch = _torch()
+        if self.perm_seed is None:
+            raise ValueError("PopulationPPO.draw_perm: no perm_seed was given")
+        K = self._KN(batch_or_K)[0] if isinstance(batch_or_K, dict) else int(batch_or_K)
+        E = max(int(e) for e in epochs) if isinstance(epochs, (list, tuple)) else int(epochs)
+        P, dev = self.n_members, self.population.device
+        sizes = self.member_envs
+        sliced = self.env.population_slices is not None
+        shape = (E * K * sum(sizes),) if sliced else (P, E, K * sizes[0])
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int64, device=dev)
+        if out.dtype != torch.int64 or out.device != dev or not out.is_contiguous() or tuple(out.shape) != shape:
+            raise ValueError("PopulationPPO.draw_perm: out must be a contiguous int64 %s tensor on %s" % (shape, dev))
+        h = self.env._h
+        with torch.cuda.device(dev):
+            N.check(N.lib().ssg_pop_perm(h, self.perm_seed, self.updates, P, K, sizes[0], E, C.c_void_p(out.data_ptr()), self._stream()),
+                    h, "ssg_pop_perm")
+        return out
+
     def update(self, batch, perm, epochs, minibatches, stats=False):
         """epochs x chunks of {gradient, Adam} for every member from ONE library call.  perm: int64 [P, epochs, K*n] — member m's
         minibatches are perm[m, e].chunk(minibatches), indices into ITS samples (i = t*n + e).  stats=True returns f32
@@ -394,7 +425,21 @@ class PopulationPPO(object):
 
         With slices bound to the env (``set_population_slices``) the update always runs on the schedule path, scalar epochs /
         minibatches broadcast; member m has K * member_envs[m] samples, and perm is a list of P tensors int64 [max(epochs), K * n_m]
-        (or the flat buffer they concatenate to, member after member: nothing is padded to the widest member)."""
+        (or the flat buffer they concatenate to, member after member: nothing is padded to the widest member).
+
+        perm=None (needs a perm_seed): the library draws the permutations, ``draw_perm``'s, in whichever of these layouts applies.  Every
+        call counts in ``updates``, the key of those draws."""
+        if perm is None:
+            if self.perm_seed is None:
+                raise ValueError("PopulationPPO.update: perm=None needs a perm_seed (PopulationPPO(..., perm_seed=...)); else pass the "
+                                 "permutations")
+            perm = self.draw_perm(batch, epochs)
+        st = self._update(batch, perm, epochs, minibatches, stats)
+        self.updates += 1
+        return st
+
+    def _update(self, batch, perm, epochs, minibatches, stats=False):
+        """update() with the permutations given."""
         torch = _torch()
         K, n_env = self._KN(batch)
         P, dev, D = self.n_members, self.population.device, self.population.obs_dim

@@ -19,6 +19,12 @@ observations, and ``update`` does so itself when the batch has none — so call 
 ``adv_norm="minibatch"`` normalises the advantages inside every minibatch with that minibatch's own mean and unbiased std, as PPO2's
 _train_step does (ssg_ppo_set_adv_norm), instead of once per rollout with gae()'s statistics; ``minibatch_adv_stats()`` shows the last
 minibatch's row and ``minibatch_adv_reference`` restates the device's order of operations in numpy.
+
+``perm_seed`` lets the library draw the minibatch permutations (ssg_ppo_perm): ``update(batch, None, ...)`` then shuffles as PPO2's learn
+does per epoch (np.random.shuffle(inds), train/stable_baselines/ppo.py:90), each row a counter-based permutation keyed by (perm_seed,
+``updates``, ``member``, epoch) — the object's count of update() calls, kept beside ``step`` and settable from a checkpoint.
+``draw_perm`` returns such rows, ``host_perm`` is the library's host restatement and ``perm_reference`` the numpy one.  The stream is the
+library's own: it is not seed-compatible with numpy or torch.
 """
 import ctypes as C
 
@@ -108,13 +114,101 @@ def minibatch_adv_reference(adv_gathered_f32, valid, adv_eps, partials=False):
     return (row, part[:B].copy()) if partials else row
 
 
+_M64 = (1 << 64) - 1
+
+
+def _mix64(z):
+    """csrc/shipsim_perm.h's perm_mix64 (the splitmix64 finaliser) on a Python int."""
+    z &= _M64
+    z ^= z >> 30
+    z = z * 0xBF58476D1CE4E5B9 & _M64
+    z ^= z >> 27
+    z = z * 0x94D049BB133111EB & _M64
+    return z ^ z >> 31
+
+
+def perm_bits(n):
+    """The network's bit width for a row of n: the smallest b >= 8 with 2^b >= n."""
+    b = N.PERM_MIN_BITS
+    while b < 32 and (1 << b) < n:
+        b += 1
+    return b
+
+
+def perm_round_keys(seed, update, member, epoch, n):
+    """The 8 round keys (Python ints < 2^32) of the row keyed (seed, update, member, epoch) over [0, n): perm_key of shipsim_perm.h."""
+    k = _mix64((int(seed) & _M64) ^ 0x5353475045524D31)
+    k = _mix64(k + int(update))
+    k = _mix64(k + ((int(member) << 32) | int(epoch)))
+    k = _mix64(k + int(n))
+    return [_mix64(k + (r + 1) * 0x9E3779B97F4A7C15) >> 32 for r in range(N.PERM_ROUNDS)]
+
+
+def perm_reference(seed, update, member, epoch, n, first=0, count=None, walks=False):
+    """The permutation of csrc/shipsim_perm.h restated in numpy: elements [first, first + count) (default: the whole row) of the row
+    keyed (seed, update, member, epoch) over [0, n), as int64.  The 8-round alternating Feistel network over b = perm_bits(n) bits
+    (L the high b // 2 bits), re-applied while the value is >= n, at most 256 times (then -1).  walks=True: (row, the number of
+    applications each element took)."""
+    import numpy as np
+    n = int(n)
+    if not 1 <= n <= N.PERM_MAX_N:
+        raise ValueError("perm_reference: n must be in 1..2^32 (got %d)" % n)
+    count = n - int(first) if count is None else int(count)
+    if first < 0 or count < 1 or first + count > n:
+        raise ValueError("perm_reference: [first, first + count) must be a non-empty window of [0, %d)" % n)
+    keys = [np.uint32(k) for k in perm_round_keys(seed, update, member, epoch, n)]
+    b = perm_bits(n)
+    wl = b // 2
+    wr = b - wl
+    x = np.arange(first, first + count, dtype=np.uint64).astype(np.uint32)
+    out = np.full(count, -1, dtype=np.int64)
+    taken = np.zeros(count, dtype=np.int64)
+    live = np.arange(count)
+    for it in range(N.PERM_WALK_CAP):
+        ml, mr = np.uint32((1 << wl) - 1), np.uint32((1 << wr) - 1)
+        L, R = x >> np.uint32(wr), x & mr
+        for key in keys:
+            v = R ^ key
+            v = v ^ (v >> np.uint32(16))
+            v = v * np.uint32(0x85EBCA6B)
+            v = v ^ (v >> np.uint32(13))
+            v = v * np.uint32(0xC2B2AE35)
+            v = v ^ (v >> np.uint32(16))
+            L, R = R, L ^ (v & ml)
+            ml, mr = mr, ml
+        x = (L << np.uint32(wr)) | R
+        done = x.astype(np.uint64) < np.uint64(n) if n < N.PERM_MAX_N else np.ones(x.shape, dtype=bool)
+        out[live[done]] = x[done].astype(np.int64)
+        taken[live[done]] = it + 1
+        live, x = live[~done], x[~done]
+        if not live.size:
+            break
+    taken[live] = N.PERM_WALK_CAP
+    return (out, taken) if walks else out
+
+
+def host_perm(seed, update, member, epoch, n, first=0, count=None):
+    """ssg_host_perm: the library's own host restatement of the same row (no device needed), as a numpy int64 array."""
+    import numpy as np
+    count = int(n) - int(first) if count is None else int(count)
+    out = np.empty(max(count, 1), dtype=np.int64)
+    N.check(N.lib().ssg_host_perm(int(seed), int(update), int(member), int(epoch), int(n), int(first), count,
+                                  out.ctypes.data_as(C.POINTER(C.c_int64))), None, "ssg_host_perm")
+    return out[:count]
+
+
 class NativePPO(object):
     """Defaults: train/ppo_torch.py's (Adam lr 3e-4, betas (0.9, 0.999), eps 1e-8; clip 0.2; loss pg + 0.5*vf - 0.01*entropy)."""
 
     def __init__(self, policy, env, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, clip=0.2, vf_coef=0.5, ent_coef=0.01, adv_eps=1e-8,
-                 vf_clip=0.0, max_grad_norm=0.0, kl_coef=0.0, kl_target=0.0, adv_norm="batch"):
+                 vf_clip=0.0, max_grad_norm=0.0, kl_coef=0.0, kl_target=0.0, adv_norm="batch", perm_seed=None, member=0):
         torch = _torch()
         self.policy, self.env = policy, env
+        # the key of the permutations the library draws (draw_perm; update(perm=None)): the seed (None: the caller brings every perm),
+        # the member this object stands for (a population member's twin passes its index) and the update() calls so far
+        self.perm_seed = None if perm_seed is None else int(perm_seed)
+        self.member = int(member)
+        self.updates = 0  # calls of update(); like `step`, a checkpoint may set it
         # "batch": the advantages are normalised once per rollout (gae()'s statistics); "minibatch": inside every minibatch, PPO2's rule
         self.adv_norm = adv_norm
         self._adv_mode = adv_norm_mode(adv_norm, "NativePPO")
@@ -299,13 +393,35 @@ class NativePPO(object):
                                          self.step + 1, self._stream()), h, "ssg_ppo_adam")
         self.step += 1
 
+    def draw_perm(self, batch_or_n, epochs, out=None):
+        """int64 [epochs, n] on the policy's device: the permutations update(batch, None, epochs, ...) would use NOW — row e keyed
+        (perm_seed, updates, member, e) over the batch's n samples (ssg_ppo_perm, one launch on the current stream).  batch_or_n: a
+        batch or its sample count; out: a tensor of that shape to fill."""
+        torch = _torch()
+        if self.perm_seed is None:
+            raise ValueError("NativePPO.draw_perm: no perm_seed was given")
+        n = int(batch_or_n) if not isinstance(batch_or_n, dict) else batch_or_n["obs"].numel() // self.policy.obs_dim
+        if out is None:
+            out = torch.empty((int(epochs), n), dtype=torch.int64, device=self.policy.device)
+        if out.dtype != torch.int64 or out.device != self.policy.device or not out.is_contiguous() or tuple(out.shape) != (int(epochs), n):
+            raise ValueError("NativePPO.draw_perm: out must be a contiguous int64 [%d, %d] tensor on %s" % (int(epochs), n, self.policy.device))
+        h = self.env._h
+        with torch.cuda.device(self.policy.device):
+            N.check(N.lib().ssg_ppo_perm(h, self.perm_seed, self.updates, self.member, int(epochs), n, C.c_void_p(out.data_ptr()),
+                                         self._stream()), h, "ssg_ppo_perm")
+        return out
+
     def update(self, batch, perm, epochs, minibatches, stats=False):
         """epochs x minibatches of {gradient, Adam} from ONE library call: the minibatches are perm[e].chunk(minibatches) (perm: int64
-        [epochs, K*N], e.g. torch.randperm rows).  stats=True returns f32 [epochs * chunks, 4] (grad()'s stats per minibatch; 8 columns
-        with an extended term on).  With the KL term on and no batch["logp_all"], the distribution is taken first, from the parameters
-        as they are on entry; with kl_target > 0 the call ends by adapting ``kl_coef`` on the device."""
+        [epochs, K*N], e.g. torch.randperm rows; None: draw_perm's, which needs a perm_seed).  stats=True returns f32
+        [epochs * chunks, 4] (grad()'s stats per minibatch; 8 columns with an extended term on).  With the KL term on and no batch["logp_all"], the distribution is taken first, from the parameters
+        as they are on entry; with kl_target > 0 the call ends by adapting ``kl_coef`` on the device.  Every call counts in ``updates``."""
         torch = _torch()
+        if perm is None and self.perm_seed is None:
+            raise ValueError("NativePPO.update: perm=None needs a perm_seed (NativePPO(..., perm_seed=...)); else pass the permutations")
         n, p = self._samples(batch)
+        if perm is None:
+            perm = self.draw_perm(n, epochs)
         perm = perm.to(device=self.policy.device, dtype=torch.int64).contiguous()
         if tuple(perm.shape) != (int(epochs), n):
             raise ValueError("NativePPO.update: perm must be int64 [epochs, %d] (got %s)" % (n, tuple(perm.shape)))
@@ -324,11 +440,13 @@ class NativePPO(object):
                                                    C.c_void_p(st.data_ptr()) if stats else None, ws, nb, self._stream()), h,
                         "ssg_ppo_update_ext")
                 self.step += int(epochs) * n_chunks
+                self.updates += 1
                 return st
             N.check(N.lib().ssg_ppo_update(h, C.byref(pol), C.byref(self.hp), n, *p, C.c_void_p(perm.data_ptr()), int(epochs),
                                            int(minibatches), C.c_void_p(self.adam_mv.data_ptr()), self.step,
                                            C.c_void_p(st.data_ptr()) if stats else None, ws, nb, self._stream()), h, "ssg_ppo_update")
         self.step += int(epochs) * n_chunks
+        self.updates += 1
         return st
 
     def load_into(self, net):

@@ -37,10 +37,18 @@ With ``--adv-norm`` (per-minibatch advantage normalisation, ssg_ppo_set_adv_norm
     path that existed before), two PopulationPPO objects on one handle, alternating; ``batch_spread`` is (max - min) / median over
     the batch-mode repeats.
 
+With ``--perm`` (the minibatch permutations drawn by the library, ssg_pop_perm), instead, per configuration and for perm_epochs 2 and 30
+(the rows a trainer draws per member: the epochs, or --max-epochs of train/pbt_native.py --mutate-schedule):
+
+(h) the draw alone — torch's (``torch.rand((P, perm_epochs, samples)).argsort(-1)``, what the trainers and the figures above use)
+    against ``PopulationPPO.draw_perm`` (one launch into a fresh tensor) — with each draw's peak device memory above what was
+    allocated before it (torch's allocator statistics; the result included); and GAE + update (2 epochs x 4 minibatches, reading the
+    first 2 rows) with each draw of all perm_epochs rows INSIDE the timed region, all four alternating.
+
 Each figure: 2 warm-up runs, then the median of ``--repeats`` (5) runs, alternating the two paths, each bracketed by a synchronize and
 timed with HIP events.  One JSON line on stdout.
 
-    python tools/population_timing.py [--configs 16x4096,120x512] [--horizon 32] [--repeats 5] [--sched | --slices | --adv-norm]
+    python tools/population_timing.py [--configs 16x4096,120x512] [--horizon 32] [--repeats 5] [--sched | --slices | --adv-norm | --perm]
 """
 import argparse
 import importlib.util
@@ -396,6 +404,67 @@ def measure_adv_norm(mod, members, n, horizon, repeats, dev, epochs=2, minibatch
     return out
 
 
+def _peak_bytes(fn):
+    """Peak device memory during fn() above what was allocated before it (the result included)."""
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    before = torch.cuda.memory_allocated()
+    out = fn()
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated() - before
+    del out
+    return int(peak)
+
+
+def measure_perm(mod, members, n, horizon, repeats, dev, epochs=2, minibatches=4, perm_epochs_list=(2, 30)):
+    from ship_sim_gym_amd.population import NativePopulation, PopulationPPO
+    torch.manual_seed(0)
+    P, N = members, members * n
+    env = mod.ShipVecEnv(N, mod.GameConfig, mod.EnvConfig, device=dev, n_maps=64)
+    D, A = env.states_history, env.action_space.n
+    scale = torch.full((D,), float(max(env.bounds)), dtype=torch.float64, device=dev)
+    pop = NativePopulation.from_actor_critics([mod.ActorCritic(D, A).to(dev) for _ in range(P)], scale)
+    p0 = pop.params.clone()
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    env.reset_tensor()
+    b = dict(env.rollout_population(pop, horizon, uniforms=torch.rand((horizon, N), generator=gen, device=dev)))
+    samples = horizon * n
+    ppo = PopulationPPO(pop, env, perm_seed=1)
+    out = {"members": P, "envs_per_member": n, "horizon": horizon, "epochs": epochs, "minibatches": minibatches, "by_perm_epochs": []}
+
+    def restore(k):
+        pop.params.copy_(p0)
+        ppo.adam_mv.zero_()
+        ppo.step = 0
+        ppo.member_steps = [0] * P
+
+    for E in perm_epochs_list:
+        def draw_torch():
+            return torch.rand((P, E, samples), generator=gen, device=dev).argsort(dim=-1)
+
+        def draw_native():
+            return ppo.draw_perm(horizon, E)
+
+        def upd(draw):
+            def run():
+                nb = dict(b)
+                ppo.gae(nb)
+                ppo.update(nb, draw()[:, :epochs].contiguous(), epochs, minibatches)
+            return run
+
+        t = _alternate([("draw_torch", draw_torch), ("draw_native", draw_native), ("update_torch_draw", upd(draw_torch)),
+                        ("update_native_draw", upd(draw_native))], repeats, before=restore)
+        rec = {"perm_epochs": E, "indices": P * E * samples}
+        for k, v in t.items():
+            rec[k + "_ms"] = statistics.median(v)
+            rec[k + "_ms_all"] = [round(x, 4) for x in v]
+        rec["draw_torch_peak_bytes"], rec["draw_native_peak_bytes"] = _peak_bytes(draw_torch), _peak_bytes(draw_native)
+        out["by_perm_epochs"].append(rec)
+    env.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="16x4096,120x512")
@@ -404,8 +473,13 @@ def main():
     ap.add_argument("--sched", action="store_true", help="time per-member schedules (ssg_pop_update_sched) instead")
     ap.add_argument("--slices", action="store_true", help="time unequal env slices (ssg_pop_set_slices) instead")
     ap.add_argument("--adv-norm", action="store_true", help="time per-minibatch advantage normalisation against batch mode instead")
+    ap.add_argument("--perm", action="store_true", help="time the permutation draws (torch's against the library's) and GAE + update with each instead")
     a = ap.parse_args()
     mod = _ppo()
+    if a.perm:
+        res = [measure_perm(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.horizon, a.repeats, "cuda:0") for c in a.configs.split(",")]
+        print(json.dumps({"population_perm_timing": res}))
+        return
     if a.adv_norm:
         res = [measure_adv_norm(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.horizon, a.repeats, "cuda:0") for c in a.configs.split(",")]
         print(json.dumps({"population_adv_norm_timing": res}))

@@ -9,7 +9,7 @@ every update from the same parameters' values (their own copies) and draw their 
 line on stdout.  The kernels alone: `rocprofv3 --kernel-trace --stats -- python tools/ppo_update_timing.py --only native` (tools/README.md).
 
     python tools/ppo_update_timing.py [--configs 65536x32,4096x64] [--repeats 7] [--only torch|native] [--ext] [--separate-value] [--ret-filter]
-                                      [--adv-norm]
+                                      [--adv-norm] [--perm]
 
 --ext adds, in the same run, the extended update (NativePPO with vf_clip 0.2, max_grad_norm 0.5, kl_coef 1.0, kl_target 0.01: GAE, the
 ssg_ppo_dist launch, ssg_ppo_update_ext) as the path "native_ext", and the ssg_ppo_dist launch alone as "dist".
@@ -20,6 +20,10 @@ alone), "ret_gae" (ssg_ret_filter_apply updating, then GAE on its output), "ret_
 (the updating apply alone: three launches) and "native_ret" (the whole GAE + update with the filter, to set against "native").
 --adv-norm adds, in the same run and alternating with the others, "native_mbnorm": the whole GAE + update of a NativePPO with
 adv_norm="minibatch" (two more launches ahead of every minibatch's gradient launch), to set against "native" (batch mode).
+--perm adds, in the same run and alternating with the others: "perm_torch" (the draw "native" makes inside its timed region, alone:
+torch.randperm per epoch, stacked), "perm_native" (NativePPO.draw_perm alone: ssg_ppo_perm, one launch into a fresh tensor) and
+"native_permnative" (the whole GAE + update with update(perm=None), the library drawing), to set against "native"; and each draw's
+peak device memory above what was allocated before it (torch's allocator statistics; the result tensor included), in bytes.
 """
 import argparse
 import importlib.util
@@ -81,8 +85,20 @@ def torch_update(net, opt, b, horizon, envs, D, epochs, minibatches, gen, gamma=
             opt.step()
 
 
+def _peak_bytes(fn):
+    """Peak device memory during fn() above what was allocated before it (the result included)."""
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    before = torch.cuda.memory_allocated()
+    out = fn()
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated() - before
+    del out
+    return int(peak)
+
+
 def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext=False, separate_value=False, ret_filter=False,
-            adv_norm=False):
+            adv_norm=False, perm=False):
     from ship_sim_gym_amd.policy import NativePolicy
     from ship_sim_gym_amd.ppo import NativePPO
     torch.manual_seed(0)
@@ -163,9 +179,30 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
         ppo_m.gae(nb)
         ppo_m.update(nb, torch.stack([torch.randperm(n, device=dev, generator=g_m) for _ in range(epochs)]), epochs, minibatches)
 
+    ppo_p = NativePPO(pol, env, perm_seed=1) if perm else None
+    g_p = torch.Generator(device=dev)
+    g_p.manual_seed(1)
+
+    def run_native_permnative():
+        with torch.no_grad():
+            for p, q in zip(net_n.parameters(), p0):
+                p.copy_(q)
+        pol.refresh()
+        nb = dict(b)
+        ppo_p.gae(nb)
+        ppo_p.update(nb, None, epochs, minibatches)
+
+    def draw_torch():
+        return torch.stack([torch.randperm(n, device=dev, generator=g_p) for _ in range(epochs)])
+
+    def draw_native():
+        return ppo_p.draw_perm(n, epochs)
+
     paths = [(k, f) for k, f in (("torch", run_torch), ("native", run_native)) if only in (None, k)]
     if adv_norm:
         paths.append(("native_mbnorm", run_native_mbnorm))
+    if perm:
+        paths += [("perm_torch", draw_torch), ("perm_native", draw_native), ("native_permnative", run_native_permnative)]
     if ext:
         paths += [("native_ext", run_native_ext), ("dist", run_dist)]
     if ret_filter:
@@ -179,11 +216,13 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
     for _ in range(repeats):
         for k, f in paths:
             times[k].append(_timed(f))
+    peaks = {"perm_torch_peak_bytes": _peak_bytes(draw_torch), "perm_native_peak_bytes": _peak_bytes(draw_native)} if perm else {}
     env.close()
     out = {"envs": envs, "separate_value": bool(separate_value), "horizon": horizon, "epochs": epochs, "minibatches": minibatches, "samples_per_minibatch": -(-n // minibatches)}
     for k, v in times.items():
         out[k + "_ms_per_update"] = statistics.median(v)
         out[k + "_ms_all"] = [round(x, 3) for x in v]
+    out.update(peaks)
     if "torch" in times and "native" in times:
         out["speedup"] = out["torch_ms_per_update"] / out["native_ms_per_update"]
     return out
@@ -199,10 +238,12 @@ def main():
     ap.add_argument("--ret-filter", action="store_true", help="also time return normalisation: GAE alone, apply + GAE, the frozen apply, "
                                                               "the updating apply, and the whole GAE + update with the filter")
     ap.add_argument("--adv-norm", action="store_true", help="also time the whole GAE + update with per-minibatch advantage normalisation")
+    ap.add_argument("--perm", action="store_true", help="also time the permutation draws alone (torch's and the library's), the whole GAE + "
+                                                        "update with the library drawing, and each draw's peak memory")
     a = ap.parse_args()
     mod = _ppo()
     res = [measure(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.repeats, a.only, "cuda:0", ext=a.ext, separate_value=sep, ret_filter=a.ret_filter,
-                   adv_norm=a.adv_norm)
+                   adv_norm=a.adv_norm, perm=a.perm)
            for c in a.configs.split(",") for sep in ([False, True] if a.separate_value else [False])]
     print(json.dumps({"ppo_update_timing": res}))
 

@@ -130,6 +130,8 @@ def make_arg_parser():
                     help="clamp the normalised rewards to +-C (needs --norm-reward; 0: no clamp)")
     ap.add_argument("--adv-norm", choices=("batch", "minibatch"), default="batch",
                     help="normalise every member's advantages once per rollout, or inside every minibatch as Stable-Baselines' PPO2 does")
+    ap.add_argument("--perm", choices=("torch", "native"), default="torch",
+                    help="who shuffles every member's minibatches: torch (rand + argsort), or the library on the device, one launch")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -193,7 +195,7 @@ def parse_args(argv=None):
 def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every=5, seed=0, epochs=2, minibatches=4, lrs=None,
           pbt=True, device="cuda:0", log=print, return_details=False, kl_coeff=0.0, kl_target=0.01, vf_clip=0.0, max_grad_norm=0.0,
           separate_value=False, mutate_schedule=False, max_epochs=30, eval_every=0, eval_episodes=1, envs=None, mutate_batch=False,
-          batch_shares=None, quantum=None, obs_filter=False, norm_reward=False, reward_clip=10.0, adv_norm="batch"):
+          batch_shares=None, quantum=None, obs_filter=False, norm_reward=False, reward_clip=10.0, adv_norm="batch", perm="torch"):
     import torch
     from ship_gym.config import EnvConfig, GameConfig
     from ship_sim_gym_amd.population import NativePopulation, PBTScheduler, PopulationPPO, reference_mutations, slices_for_batch_sizes
@@ -202,6 +204,9 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
     from train.ppo_torch import ActorCritic
     from train.rllib_ppo import game_configuration
 
+    if perm not in ("torch", "native"):
+        raise ValueError("train: perm must be 'torch' or 'native' (got %r)" % (perm,))
+    native_perm = perm == "native"
     P, n = int(members), int(envs_per_member)
     n_total = int(envs) if envs is not None else P * n
     sliced = bool(mutate_batch) or batch_shares is not None
@@ -248,7 +253,8 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
         reslices.append((0, list(slices)))
         log("slices: train_batch_size %s -> envs %s (quantum %d)" % (batch_sizes, slices, quantum))
     ppo = PopulationPPO(pop, env, lam=INITIAL["lambda"], clip=INITIAL["clip_param"], lr=list(lrs) if lrs is not None else INITIAL["lr"],
-                        vf_clip=vf_clip, max_grad_norm=max_grad_norm, kl_coef=kl_coeff, kl_target=kl_target if kl_coeff > 0 else 0.0, adv_norm=adv_norm)
+                        vf_clip=vf_clip, max_grad_norm=max_grad_norm, kl_coef=kl_coeff, kl_target=kl_target if kl_coeff > 0 else 0.0, adv_norm=adv_norm,
+                        perm_seed=seed if native_perm else None)
     flt = None
     if obs_filter:  # per-member statistics; a member's rows are its slice, whatever the slices currently are
         from ship_sim_gym_amd.obs_filter import ObsFilter
@@ -290,13 +296,17 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
         if rflt is not None:
             rflt.set_gamma(ppo.gamma)  # (the members' own discounts, whatever they currently are)
         ppo.gae(batch, return_filter=rflt)
-        if sliced:  # member m's own rows: [perm_epochs, horizon * n_m], nothing padded to the widest member
+        if native_perm:  # update() draws what it needs itself: max(iters) rows per member, in the bound layout, keyed by its count
+            perm = None
+        elif sliced:  # member m's own rows: [perm_epochs, horizon * n_m], nothing padded to the widest member
             perm = [torch.rand((perm_epochs, s), generator=gen, device=dev).argsort(dim=-1) for s in member_samples]
         else:
             perm = torch.rand((P, perm_epochs, samples), generator=gen, device=dev).argsort(dim=-1)
         if per_member:
             mbs = [ppo.minibatches_for_size(s, member_samples[m]) for m, s in enumerate(sizes)] if mutate_schedule else counts
-            if sliced:
+            if native_perm:
+                ppo.update(batch, None, iters, mbs)
+            elif sliced:
                 ppo.update(batch, [q[:max(iters)].contiguous() for q in perm], iters, mbs)
             else:
                 ppo.update(batch, perm[:, :max(iters)].contiguous(), iters, mbs)
@@ -377,7 +387,7 @@ def main(argv=None):
           kl_target=a.kl_target, vf_clip=a.vf_clip, max_grad_norm=a.max_grad_norm, separate_value=a.separate_value,
           mutate_schedule=a.mutate_schedule, max_epochs=a.max_epochs, eval_every=a.eval_every, eval_episodes=a.eval_episodes, envs=a.envs,
           mutate_batch=a.mutate_batch, batch_shares=a.batch_shares, quantum=a.quantum, obs_filter=a.obs_filter,
-          norm_reward=a.norm_reward, reward_clip=a.reward_clip, adv_norm=a.adv_norm)
+          norm_reward=a.norm_reward, reward_clip=a.reward_clip, adv_norm=a.adv_norm, perm=a.perm)
 
 
 if __name__ == "__main__":

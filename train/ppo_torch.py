@@ -216,8 +216,13 @@ def rollout(shards, horizon, mode, gen, policy=None):
 def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, gamma=0.99, lam=0.95, clip=0.2,
           device="cuda:0", seed=0, log=print, mode="eager", return_details=False, env_kw=None, update="torch", separate_value=False,
           eval_every=0, eval_episodes=1, eval_envs=None, obs_filter=False, save_obs_filter=None,
-          norm_reward=False, reward_clip=10.0, adv_norm="batch"):
+          norm_reward=False, reward_clip=10.0, adv_norm="batch", perm="torch"):
     assert mode in ("eager", "graph", "pingpong", "native")
+    if perm not in ("torch", "native"):
+        raise ValueError("perm must be 'torch' or 'native' (got %r)" % (perm,))
+    if perm == "native" and update != "native":
+        raise ValueError("perm='native' draws the permutations for the device update: it needs update='native' (got update=%r)" % (update,))
+    native_perm = perm == "native"
     if adv_norm not in ("batch", "minibatch"):
         raise ValueError("adv_norm must be 'batch' or 'minibatch' (got %r)" % (adv_norm,))
     if (obs_filter or save_obs_filter) and mode != "native":
@@ -248,7 +253,8 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
     for sh in shards:
         sh.env.reset_tensor()
     policy = NativePolicy.from_actor_critic(net, shards[0].scale) if mode == "native" else None
-    ppo = NativePPO(policy, shards[0].env, lr=lr, clip=clip, adv_norm=adv_norm) if update == "native" else None
+    ppo = (NativePPO(policy, shards[0].env, lr=lr, clip=clip, adv_norm=adv_norm, perm_seed=seed if native_perm else None)
+           if update == "native" else None)
     flt = None
     if obs_filter:  # (the rollout loop merges each step's observations, then normalises them; obs_scale is no longer read)
         from ship_sim_gym_amd.obs_filter import ObsFilter
@@ -292,8 +298,9 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
             nb = dict(shards[0].native_out)
             ppo.gae(nb, gamma, lam, return_filter=rflt)
             n = horizon * envs
-            st_upd = ppo.update(nb, torch.stack([torch.randperm(n, device=dev, generator=gen) for _ in range(epochs)]), epochs, minibatches,
-                                stats=flt is not None or rflt is not None)
+            # perm "native": the library shuffles (a row per epoch, keyed by the seed and the update's number); else torch's generator
+            rows = None if native_perm else torch.stack([torch.randperm(n, device=dev, generator=gen) for _ in range(epochs)])
+            st_upd = ppo.update(nb, rows, epochs, minibatches, stats=flt is not None or rflt is not None)
             if st_upd is not None:
                 pg, vf, ent = (float(v) for v in st_upd[-1, :3])
                 notes = []
@@ -401,6 +408,8 @@ def make_arg_parser():
                     help="clamp the normalised rewards to +-C (needs --norm-reward; 0: no clamp)")
     ap.add_argument("--adv-norm", choices=("batch", "minibatch"), default="batch",
                     help="normalise the advantages once per rollout, or inside every minibatch as Stable-Baselines' PPO2 does (either --update)")
+    ap.add_argument("--perm", choices=("torch", "native"), default="torch",
+                    help="who shuffles the update's minibatches: torch.randperm, or the library on the device (needs --update native)")
     return ap
 
 
@@ -414,6 +423,8 @@ def parse_args(argv=None):
         ap.error("--eval-every needs --mode native (the evaluation runs the native policy on the device)")
     if a.update == "native" and a.mode != "native":
         ap.error("--update native needs --mode native (the update runs on the native policy's packed parameters)")
+    if a.perm == "native" and a.update != "native":
+        ap.error("--perm native needs --update native (the library draws the permutations of the device update)")
     if a.obs_filter and a.mode != "native":
         ap.error("--obs-filter needs --mode native (the filter runs inside the native policy launch)")
     if a.save_obs_filter and not a.obs_filter:
@@ -431,4 +442,4 @@ if __name__ == "__main__":
     a = parse_args()
     train(envs=a.envs, updates=a.updates, horizon=a.horizon, mode=a.mode, update=a.update, separate_value=a.separate_value,
           eval_every=a.eval_every, eval_episodes=a.eval_episodes, obs_filter=a.obs_filter, save_obs_filter=a.save_obs_filter,
-          norm_reward=a.norm_reward, reward_clip=a.reward_clip, adv_norm=a.adv_norm)
+          norm_reward=a.norm_reward, reward_clip=a.reward_clip, adv_norm=a.adv_norm, perm=a.perm)
