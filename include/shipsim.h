@@ -477,7 +477,8 @@ int ssg_policy_act(ssg_handle *h, const ssg_policy *pol, const double *dev_obs, 
  * k-1 (>= n_envs, as in ssg_rollout_traj).  dev_last_value (nullable): the value of the observation after step K-1 (the bootstrap
  * value of PPO's GAE), one more value-only forward.  Every handle ssg_step serves is served (history 1..8, n_ships = 4, map_ring), with
  * the same launches ssg_step issues.  SSG_ERR_BAD_ARG (nothing launched) for a bad policy record, NULL required pointers, K < 1 or a
- * stride < n_envs. */
+ * stride < n_envs.  With a time-out record bound (ssg_set_timeout_boot, below) the loop also keeps every step's terminal observations
+ * and ends with one more launch, ssg_timeout_values; it then needs dev_flags_KN and refuses a capturing stream. */
 int ssg_rollout_policy(ssg_handle *h, const ssg_policy *pol, int K, const float *dev_uniform_KN /* nullable */, uint64_t seed,
                        int64_t step0, double *dev_obs, int32_t *dev_act_KN, float *dev_logp_KN, float *dev_value_KN,
                        float *dev_x_KND /* nullable */, double *dev_reward_KN, uint8_t *dev_done_KN, uint8_t *dev_flags_KN /* nullable */,
@@ -1189,6 +1190,92 @@ int ssg_ppo_perm(ssg_handle *h, uint64_t seed, int64_t update, int member, int e
  * all.  SSG_ERR_BAD_ARG, nothing launched: a NULL handle or dev_perm; update < 0; K < 1; perm_epochs < 1; members outside
  * 1..SSG_POP_MAX_MEMBERS or different from the bound slices' member count; without slices n < 1; a row longer than 2^32. */
 int ssg_pop_perm(ssg_handle *h, uint64_t seed, int64_t update, int members, int K, int n, int perm_epochs, int64_t *dev_perm, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Time-out bootstrap (ABI 9 addition): GAE that bootstraps a timed-out episode from the value of its terminal observation
+ * The env ends an episode for five reasons (the SSG_EV_* bits); four are ends of the task, the fifth is the clock
+ * (ship_env.py:131: step_count >= MAX_STEPS).  ssg_ppo_gae scores all five alike: delta = rew + gamma * 0 - val.  The observation
+ * carries no clock, so the value network cannot tell a state at step 999 from the same state at step 3, yet gets targets several
+ * units apart (the step reward is -0.01): the time-limit bias of Pardo et al. 2018, which Stable-Baselines3 and RLlib correct by
+ * adding gamma * V(terminal observation) at a truncation.  This is that correction; it is opt-in, and with nothing bound and the
+ * plain GAE entry points nothing changes.
+ *
+ * Sample (k, e) is a TIME-OUT when its flags byte f has (f & SSG_EV_MAX_STEPS) != 0 and (f & (SSG_EV_COLLIDING |
+ * SSG_EV_OUT_OF_BOUNDS | SSG_EV_NO_GOALS_LEFT)) == 0; SSG_EV_GOAL_REACHED does not matter (a goal reached on the last allowed step,
+ * with goals left, is still a time-out).  The bits are independent: a collision on the step that exhausts the clock carries both and
+ * is a true terminal.  boot[k][e] = V(terminal observation of env e at step k) for a time-out, +0.0f for every other sample.
+ *
+ * The values cost ONE launch per rollout, not one per step.  While a record is bound (ssg_set_timeout_boot), ssg_rollout_policy /
+ * ssg_pop_rollout point the step kernel's terminal-observation rows (ssg_set_terminal_obs) at row k of dev_term_obs_KND for step k,
+ * put back whatever the caller had bound there once the loop is done, and after the last-value forward enqueue ssg_timeout_values /
+ * ssg_pop_timeout_values over the K rows.  Every other output of the rollout, and the env state, is bit for bit what it is with
+ * nothing bound.  Such a rollout needs dev_flags_KN and K <= rows (SSG_ERR_BAD_ARG otherwise), and refuses a capturing stream
+ * (SSG_ERR_UNSUPPORTED: the handle's terminal-observation binding changes from step to step), each with nothing launched.
+ *
+ * Memory.  dev_term_obs_KND holds rows * n_envs * D * 8 bytes — 537 MB at 65 536 envs x 32 rows x D = 32, 67 MB at 4 096 x 64.  It is
+ * written sparsely (the rows of the envs a step resets), read where a wave holds a time-out, allocated by the caller only when the
+ * feature is on, and reused across rollouts.  Rows of envs that were not reset hold stale or never-written memory; the launch selects,
+ * it never multiplies.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct ssg_timeout_boot {
+    uint32_t struct_size;       /* sizeof(ssg_timeout_boot) */
+    int32_t rows;               /* >= 1: the longest rollout (K) the buffers serve */
+    double *dev_term_obs_KND;   /* f64 [rows][n_envs][D], D = history * (6 + n_beams), caller-owned; need not be initialised */
+    float *dev_boot_KN;         /* f32, row k at k * step_stride_envs of the rollout (>= rows * step_stride_envs floats), caller-owned */
+} ssg_timeout_boot;
+
+/* Replaces: the `done` of ShipEnv.step at the clock (ship_env.py:131) as the trainers read it — nothing in the reference tells a
+ * time-out from a terminal state (memory binding; the libraries' counterpart is the TimeLimit.truncated / terminal_observation entry
+ * of the info dict).  Binds a copy of the record to the handle (host only, nothing launched); NULL unbinds.  The binding left as it
+ * was: history > 2 is SSG_ERR_UNSUPPORTED and a handle without SSG_FLAG_AUTO_RESET SSG_ERR_BAD_ARG, as ssg_set_terminal_obs refuses
+ * them; SSG_ERR_BAD_ARG for a struct_size mismatch, rows < 1 or a NULL buffer. */
+int ssg_set_timeout_boot(ssg_handle *h, const ssg_timeout_boot *rec /* NULL unbinds */);
+
+/* Replaces nothing (introspection).  *out = the bound record; out->struct_size == 0 (all of *out zero): nothing bound. */
+int ssg_get_timeout_boot(const ssg_handle *h, ssg_timeout_boot *out /* struct_size 0: nothing bound */);
+
+/* Replaces: the value of the terminal observation that Stable-Baselines3 / RLlib add at a truncation, for the episodes ShipEnv.step
+ * ends at the clock (ship_env.py:131), over the K rows of a rollout in ONE launch on `stream`: grid (workgroups of 64 envs, 1, K).
+ * A workgroup (one wave) reads its 64 flag bytes of row k (dev_flags_KN + k * step_stride_envs); with no time-out among them it
+ * writes +0.0f for its envs and leaves; otherwise it runs ssg_policy_act's value-only forward (the vf tower alone with
+ * SSG_POLICY_SEPARATE_VALUE, else the body and the v head; the fixed scale or the bound observation filter) on its rows of
+ * dev_term_obs_KND + k * n_envs * D and writes, per env, the value for a time-out and +0.0f otherwise (a select).  Every entry
+ * dev_boot_KN[k * step_stride_envs + e], k < K, e < n_envs, is written by every call: the buffer needs no clearing.  A time-out's
+ * value is bit for bit what ssg_policy_act writes as dev_value for that observation row under the same parameters and filter
+ * state.  A bound observation filter's state is read as the rollout left it (the state dev_last_value was computed under) and never
+ * updated by this launch.  No record need be bound.  SSG_ERR_BAD_ARG (nothing launched): a bad policy record, a NULL buffer, K outside
+ * 1..65535, step_stride_envs < n_envs, a bound filter of another member count. */
+int ssg_timeout_values(ssg_handle *h, const ssg_policy *pol, int K, const uint8_t *dev_flags_KN, const double *dev_term_obs_KND,
+                       float *dev_boot_KN, int64_t step_stride_envs, void *stream);
+
+/* Replaces: the same for the trials of train/rllib/pbt.py:50-62, every member's in ONE launch: grid (workgroups of the widest slice,
+ * members, K), member m on its columns [m n, (m + 1) n), n = n_envs / P, or its slice of ssg_pop_set_slices, under its parameter row
+ * and its filter state rows.  Member m's entries are bit for bit ssg_timeout_values' on its shard.  Refuses as ssg_timeout_values
+ * and as ssg_pop_act do. */
+int ssg_pop_timeout_values(ssg_handle *h, const ssg_population *pop, int K, const uint8_t *dev_flags_KN, const double *dev_term_obs_KND,
+                           float *dev_boot_KN, int64_t step_stride_envs, void *stream);
+
+/* Replaces: the advantage / return computation behind model.learn (train/stable_baselines/ppo.py:90) with the truncation handled as
+ * Stable-Baselines3's collect_rollouts does (ship_env.py:131 is where the clock ends an episode).  ssg_ppo_gae's arguments plus
+ * dev_boot_KN (f32, rows N apart: ssg_timeout_values' output).  The walk, in f32, t = K-1 .. 0:
+ *     nonterm = 1 - done;  v = val[i]
+ *     tgt     = done ? boot[i] : nxt                        (a select)
+ *     delta   = (rew[i] + gamma*tgt) - v
+ *     adv     = delta + ((gamma*lam)*nonterm)*adv;  ret = adv + v;  nxt = v
+ * The lambda chain is still cut at every done (the next row belongs to a new episode); only the one-step target changes.  The
+ * advantage statistics and the partials' layout are ssg_ppo_gae's; with an all-zero boot, adv, ret and the statistics are bit for bit
+ * ssg_ppo_gae's (finite inputs; rewards other than -0.0, which the env never pays).  Two launches.  Refuses as ssg_ppo_gae, and a NULL
+ * dev_boot_KN. */
+int ssg_ppo_gae_boot(ssg_handle *h, const ssg_ppo_hparams *hp, int K, int N, const double *dev_reward_KN, const uint8_t *dev_done_KN,
+                     const float *dev_value_KN, const float *dev_last_value, const float *dev_boot_KN, float *dev_adv_KN,
+                     float *dev_ret_KN, void *dev_workspace, size_t workspace_nbytes, void *stream);
+
+/* Replaces: the same for every trial of train/rllib/pbt.py:50-62 in two launches: ssg_pop_gae's arguments plus dev_boot_KN (rows
+ * n_envs apart), on equal slices or the ssg_pop_set_slices layout; member m is bit for bit ssg_ppo_gae_boot on its shard with its own
+ * gamma / lambda.  Refuses as ssg_pop_gae, and a NULL dev_boot_KN. */
+int ssg_pop_gae_boot(ssg_handle *h, const ssg_population *pop, const float *dev_table, int K, const double *dev_reward_KN,
+                     const uint8_t *dev_done_KN, const float *dev_value_KN, const float *dev_last_value, const float *dev_boot_KN,
+                     float *dev_adv_KN, float *dev_ret_KN, void *dev_workspace, size_t workspace_nbytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Host-side geometry (what pymunk's cffi exposed at reset time); no GPU needed.

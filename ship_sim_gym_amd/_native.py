@@ -76,6 +76,7 @@ EXPORTS = (
     "ssg_ret_filter_workspace_nbytes", "ssg_ret_filter_apply",
     "ssg_ppo_adv_norm_nbytes", "ssg_ppo_set_adv_norm", "ssg_ppo_get_adv_norm",
     "ssg_host_perm", "ssg_ppo_perm", "ssg_pop_perm",
+    "ssg_set_timeout_boot", "ssg_get_timeout_boot", "ssg_timeout_values", "ssg_pop_timeout_values", "ssg_ppo_gae_boot", "ssg_pop_gae_boot",
 )
 
 
@@ -169,6 +170,20 @@ class RetFilterRecord(C.Structure):
         ("clip", C.c_double), ("eps", C.c_double), ("dev_gamma", C.c_void_p), ("dev_state", C.c_void_p), ("dev_carry", C.c_void_p),
         ("dev_workspace", C.c_void_p), ("workspace_nbytes", C.c_size_t),
     ]
+
+
+class TimeoutBootRecord(C.Structure):
+    """ssg_timeout_boot (ABI 9 addition): the time-out bootstrap's buffers — the rows they serve, the terminal observations f64
+    [rows][n_envs][D], the values f32 [rows][stride]."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("rows", C.c_int32), ("dev_term_obs_KND", C.c_void_p), ("dev_boot_KN", C.c_void_p),
+    ]
+
+
+def is_timeout(flags):
+    """The time-out predicate of include/shipsim.h on a flags byte (an int, or a numpy / torch integer array): the clock ended the
+    episode (EV_MAX_STEPS) and no true terminal did (EV_COLLIDING, EV_OUT_OF_BOUNDS, EV_NO_GOALS_LEFT); EV_GOAL_REACHED does not matter."""
+    return ((flags & EV_MAX_STEPS) != 0) & ((flags & (EV_COLLIDING | EV_OUT_OF_BOUNDS | EV_NO_GOALS_LEFT)) == 0)
 
 
 _lib = None
@@ -273,6 +288,12 @@ def lib():
     L.ssg_host_perm.argtypes = [C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
     L.ssg_ppo_perm.argtypes = [vp, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int64, vp, vp]
     L.ssg_pop_perm.argtypes = [vp, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.ssg_set_timeout_boot.argtypes = [vp, C.POINTER(TimeoutBootRecord)]
+    L.ssg_get_timeout_boot.argtypes = [vp, C.POINTER(TimeoutBootRecord)]
+    L.ssg_timeout_values.argtypes = [vp, C.POINTER(Policy), C.c_int, vp, vp, vp, C.c_int64, vp]
+    L.ssg_pop_timeout_values.argtypes = [vp, pp, C.c_int, vp, vp, vp, C.c_int64, vp]
+    L.ssg_ppo_gae_boot.argtypes = [vp, C.POINTER(PpoHparams), C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.ssg_pop_gae_boot.argtypes = [vp, pp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     L.ssg_render.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, vp]
     L.ssg_dyn_invalidate.argtypes = [vp, vp, vp]
     L.ssg_host_convex_hull.argtypes = [C.c_int, dp, dp, ip]

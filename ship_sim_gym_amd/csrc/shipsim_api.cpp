@@ -62,6 +62,9 @@ struct ssg_handle {
     // ssg_set_obs_filter: the bound record (a copy; struct_size 0: nothing bound) and whether the FILTER kernels' LDS limit is set
     ssg_obs_filter flt{};
     bool policy_filter_prepared = false;
+    // ssg_set_timeout_boot: the bound record (a copy; struct_size 0: nothing bound) and whether the time-out kernels' LDS limit is set
+    ssg_timeout_boot tob{};
+    bool policy_boot_prepared = false;
     // ssg_ppo_set_adv_norm: the mode (SSG_ADV_NORM_BATCH: nothing bound), the member count the scratch serves and the caller's scratch
     int adv_norm_mode = SSG_ADV_NORM_BATCH, adv_norm_members = 0;
     void *adv_norm_scratch = nullptr;
@@ -1056,6 +1059,15 @@ static int prepare_policy_filter(ssg_handle *h)
     return SSG_OK;
 }
 
+static int prepare_policy_boot(ssg_handle *h)
+{
+    if (h->policy_boot_prepared) return SSG_OK;
+    hipError_t e = ssg::prepare_policy_boot();
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("prepare_policy_boot: ") + hipGetErrorString(e));
+    h->policy_boot_prepared = true;
+    return SSG_OK;
+}
+
 // ABI 9 additions: GAE and the PPO update.  As above, everything a call could refuse is refused before anything is enqueued.
 static int check_policy_shape(const ssg_policy *pol)
 {
@@ -1119,23 +1131,42 @@ int ssg_ppo_workspace_nbytes(const ssg_policy *pol, int64_t n_samples, int64_t m
     return SSG_OK;
 }
 
+// The body of ssg_ppo_gae and ssg_ppo_gae_boot (with_boot: dev_boot_KN is required and the BOOT walk runs).
+static int ppo_gae(ssg_handle *h, const ssg_ppo_hparams *hp, int K, int N, const double *dev_reward_KN, const uint8_t *dev_done_KN,
+                   const float *dev_value_KN, const float *dev_last_value, const float *dev_boot_KN, bool with_boot, float *dev_adv_KN,
+                   float *dev_ret_KN, void *dev_workspace, size_t workspace_nbytes, void *stream, const char *what)
+{
+    const std::string w(what);
+    int rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    rc = check_hparams(h, hp, what);
+    if (rc != SSG_OK) return rc;
+    if (!dev_reward_KN || !dev_done_KN || !dev_value_KN || !dev_last_value || !dev_adv_KN || !dev_ret_KN)
+        return fail(h, SSG_ERR_BAD_ARG, w + ": NULL reward, done, value, last value, adv or ret buffer");
+    if (with_boot && !dev_boot_KN) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_boot_KN");
+    if (K < 1 || N < 1 || (long long)K * N < 2) return fail(h, SSG_ERR_BAD_ARG, w + ": K and N must be >= 1 and K*N >= 2");
+    rc = check_workspace(h, dev_workspace, workspace_nbytes, ppo_need_gae(N), what);
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_ppo_gae(*hp, K, N, dev_reward_KN, dev_done_KN, dev_value_KN, dev_last_value, dev_adv_KN, dev_ret_KN,
+                                       dev_workspace, static_cast<hipStream_t>(stream), with_boot ? dev_boot_KN : nullptr);
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("gae launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
 int ssg_ppo_gae(ssg_handle *h, const ssg_ppo_hparams *hp, int K, int N, const double *dev_reward_KN, const uint8_t *dev_done_KN,
                 const float *dev_value_KN, const float *dev_last_value, float *dev_adv_KN, float *dev_ret_KN, void *dev_workspace,
                 size_t workspace_nbytes, void *stream)
 {
-    int rc = check_ready(h, false);
-    if (rc != SSG_OK) return rc;
-    rc = check_hparams(h, hp, "ssg_ppo_gae");
-    if (rc != SSG_OK) return rc;
-    if (!dev_reward_KN || !dev_done_KN || !dev_value_KN || !dev_last_value || !dev_adv_KN || !dev_ret_KN)
-        return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_gae: NULL reward, done, value, last value, adv or ret buffer");
-    if (K < 1 || N < 1 || (long long)K * N < 2) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_gae: K and N must be >= 1 and K*N >= 2");
-    rc = check_workspace(h, dev_workspace, workspace_nbytes, ppo_need_gae(N), "ssg_ppo_gae");
-    if (rc != SSG_OK) return rc;
-    hipError_t e = ssg::launch_ppo_gae(*hp, K, N, dev_reward_KN, dev_done_KN, dev_value_KN, dev_last_value, dev_adv_KN, dev_ret_KN,
-                                       dev_workspace, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("gae launch: ") + hipGetErrorString(e));
-    return SSG_OK;
+    return ppo_gae(h, hp, K, N, dev_reward_KN, dev_done_KN, dev_value_KN, dev_last_value, nullptr, false, dev_adv_KN, dev_ret_KN, dev_workspace,
+                   workspace_nbytes, stream, "ssg_ppo_gae");
+}
+
+int ssg_ppo_gae_boot(ssg_handle *h, const ssg_ppo_hparams *hp, int K, int N, const double *dev_reward_KN, const uint8_t *dev_done_KN,
+                     const float *dev_value_KN, const float *dev_last_value, const float *dev_boot_KN, float *dev_adv_KN,
+                     float *dev_ret_KN, void *dev_workspace, size_t workspace_nbytes, void *stream)
+{
+    return ppo_gae(h, hp, K, N, dev_reward_KN, dev_done_KN, dev_value_KN, dev_last_value, dev_boot_KN, true, dev_adv_KN, dev_ret_KN,
+                   dev_workspace, workspace_nbytes, stream, "ssg_ppo_gae_boot");
 }
 
 static int check_batch(ssg_handle *h, int64_t n_samples, const ssg::PpoBatch &b, const void *idx, const char *what)
@@ -1621,8 +1652,58 @@ int ssg_pop_act_greedy(ssg_handle *h, const ssg_population *pop, const double *d
     return rc != SSG_OK ? rc : policy_act(h, c, {dev_obs, nullptr, 0, 0, dev_actions, dev_logp, dev_value, dev_x, true}, stream);
 }
 
+// One launch of the time-out values over K rows (ssg_timeout_values, ssg_pop_timeout_values, the end of a rollout with a record bound)
+static hipError_t timeout_launch(ssg_handle *h, const PolicyCall &c, int K, const uint8_t *flags, const double *term_obs, float *boot,
+                                 int64_t stride, hipStream_t st)
+{
+    const ssg::ObsFilterArgs f = {h->flt.dev_state, h->flt.clip};
+    ssg::PolicyLaunch l = {};
+    l.policy = &c.pol;
+    l.members = c.members;
+    l.n = c.n;
+    l.slices = c.slices;
+    l.filter = h->flt.struct_size ? &f : nullptr;
+    return ssg::launch_timeout_values(l, {K, h->cfg.n_envs, (size_t)stride, flags, term_obs, boot}, st);
+}
+
+// The body of ssg_timeout_values / ssg_pop_timeout_values, once their record passed.
+static int timeout_values(ssg_handle *h, const PolicyCall &c, int K, const uint8_t *dev_flags_KN, const double *dev_term_obs_KND,
+                          float *dev_boot_KN, int64_t step_stride_envs, void *stream)
+{
+    const std::string w(c.what);
+    if (!dev_flags_KN || !dev_term_obs_KND || !dev_boot_KN) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_flags_KN, dev_term_obs_KND or dev_boot_KN");
+    if (K < 1 || K > 65535) return fail(h, SSG_ERR_BAD_ARG, w + ": K must be in 1..65535");
+    if (step_stride_envs < (int64_t)h->cfg.n_envs) return fail(h, SSG_ERR_BAD_ARG, w + ": step_stride_envs < n_envs (rows would overlap)");
+    int rc = check_filter_members(h, c);
+    if (rc == SSG_OK) rc = check_ready(h, false);
+    if (rc == SSG_OK) rc = prepare_policy_boot(h);
+    if (rc != SSG_OK) return rc;
+    const hipError_t e = timeout_launch(h, c, K, dev_flags_KN, dev_term_obs_KND, dev_boot_KN, step_stride_envs, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? SSG_OK : fail(h, SSG_ERR_HIP, std::string("time-out values launch: ") + hipGetErrorString(e));
+}
+
+int ssg_timeout_values(ssg_handle *h, const ssg_policy *pol, int K, const uint8_t *dev_flags_KN, const double *dev_term_obs_KND,
+                       float *dev_boot_KN, int64_t step_stride_envs, void *stream)
+{
+    PolicyCall c;
+    int rc = check_ready(h, false);
+    if (rc == SSG_OK) rc = one_policy_call(h, pol, "ssg_timeout_values", c);
+    return rc != SSG_OK ? rc : timeout_values(h, c, K, dev_flags_KN, dev_term_obs_KND, dev_boot_KN, step_stride_envs, stream);
+}
+
+int ssg_pop_timeout_values(ssg_handle *h, const ssg_population *pop, int K, const uint8_t *dev_flags_KN, const double *dev_term_obs_KND,
+                           float *dev_boot_KN, int64_t step_stride_envs, void *stream)
+{
+    PolicyCall c;
+    const int rc = population_call(h, pop, "ssg_pop_timeout_values", c);
+    return rc != SSG_OK ? rc : timeout_values(h, c, K, dev_flags_KN, dev_term_obs_KND, dev_boot_KN, step_stride_envs, stream);
+}
+
 // The body of both rollout entry points: K times the filter's merge (if it updates), ONE policy launch for everyone and the step, then
 // the bootstrap value.  (ssg_rollout_policy has asked check_ready already, ahead of its record: the order of its refusals.)
+// With a time-out record bound (ssg_set_timeout_boot): step k's terminal observations go to row k of the record's rows — h->dev.term_obs
+// is a host-side field handed to every launch — the caller's own ssg_set_terminal_obs binding is back in place on every way out of the
+// loop, and one launch after the bootstrap forward turns the K rows of flags into the record's boot rows.
 static int policy_rollout(ssg_handle *h, const PolicyCall &c, int K, const float *dev_uniform_KN, uint64_t seed, int64_t step0, double *dev_obs,
                           int32_t *dev_act_KN, float *dev_logp_KN, float *dev_value_KN, float *dev_x_KND, double *dev_reward_KN,
                           uint8_t *dev_done_KN, uint8_t *dev_flags_KN, float *dev_last_value, int64_t step_stride_envs, void *stream)
@@ -1632,12 +1713,31 @@ static int policy_rollout(ssg_handle *h, const PolicyCall &c, int K, const float
         return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_obs, act, logp, value, reward or done buffer");
     if (K < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": K < 1");
     if (step_stride_envs < (int64_t)h->cfg.n_envs) return fail(h, SSG_ERR_BAD_ARG, w + ": step_stride_envs < n_envs (steps would overlap)");
-    int rc = prepare_steps(h, c, stream);
-    if (rc != SSG_OK) return rc;
     const hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool boot = h->tob.struct_size != 0;
+    if (boot) {
+        if (K > h->tob.rows || K > 65535)
+            return fail(h, SSG_ERR_BAD_ARG, w + ": K exceeds the rows of the bound time-out record (ssg_set_timeout_boot), or 65535");
+        if (!dev_flags_KN) return fail(h, SSG_ERR_BAD_ARG, w + ": a time-out record is bound (ssg_set_timeout_boot): dev_flags_KN is required");
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
+        else if (cs != hipStreamCaptureStatusNone)
+            return fail(h, SSG_ERR_UNSUPPORTED, w + ": the stream is capturing a HIP graph, and with a time-out record bound (ssg_set_timeout_boot) "
+                                                    "the handle's terminal-observation rows change from step to step");
+    }
+    int rc = prepare_steps(h, c, stream);
+    if (rc == SSG_OK && boot) rc = prepare_policy_boot(h);
+    if (rc != SSG_OK) return rc;
     const size_t S = (size_t)step_stride_envs, D = (size_t)c.pol.obs_dim;
+    // (restores the caller's terminal-observation binding on every way out of this function)
+    struct TermObsGuard {
+        ssg_handle *h;
+        double *saved;
+        ~TermObsGuard() { h->dev.term_obs = saved; }
+    } guard = {h, h->dev.term_obs};
     for (int k = 0; k < K; ++k) {
         const size_t r = (size_t)k * S;
+        if (boot) h->dev.term_obs = h->tob.dev_term_obs_KND + (size_t)k * (size_t)h->cfg.n_envs * D;
         hipError_t e = filter_step_update(h, c, dev_obs, st); // (first merge the step's rows, a member's into its own state rows, then normalise them)
         if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("observation filter launch: ") + hipGetErrorString(e));
         e = policy_launch(h, c, {dev_obs, dev_uniform_KN ? dev_uniform_KN + r : nullptr, seed, step0 + k, dev_act_KN + r, dev_logp_KN + r,
@@ -1651,6 +1751,10 @@ static int policy_rollout(ssg_handle *h, const PolicyCall &c, int K, const float
     if (dev_last_value) { // the value of the observation after the last step (PPO's bootstrap): a value-only forward (no filter merge)
         const hipError_t e = policy_launch(h, c, {dev_obs, nullptr, seed, step0 + K, nullptr, nullptr, dev_last_value, nullptr, false}, st);
         if (e != hipSuccess) return policy_launch_failed(h, c, e);
+    }
+    if (boot) {
+        const hipError_t e = timeout_launch(h, c, K, dev_flags_KN, h->tob.dev_term_obs_KND, h->tob.dev_boot_KN, step_stride_envs, st);
+        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("time-out values launch: ") + hipGetErrorString(e));
     }
     return SSG_OK;
 }
@@ -1706,25 +1810,44 @@ int ssg_pop_workspace_nbytes(const ssg_population *pop, int64_t samples_per_memb
     return SSG_OK;
 }
 
+// The body of ssg_pop_gae and ssg_pop_gae_boot (with_boot: dev_boot_KN is required and the BOOT walk runs).
+static int pop_gae(ssg_handle *h, const ssg_population *pop, const float *dev_table, int K, const double *dev_reward_KN,
+                   const uint8_t *dev_done_KN, const float *dev_value_KN, const float *dev_last_value, const float *dev_boot_KN, bool with_boot,
+                   float *dev_adv_KN, float *dev_ret_KN, void *dev_workspace, size_t workspace_nbytes, void *stream, const char *what)
+{
+    const std::string w(what);
+    int rc = pop_bound(h);
+    if (rc == SSG_OK) rc = check_population(h, pop, what);
+    if (rc != SSG_OK) return rc;
+    if (!dev_table || !dev_reward_KN || !dev_done_KN || !dev_value_KN || !dev_last_value || !dev_adv_KN || !dev_ret_KN)
+        return fail(h, SSG_ERR_BAD_ARG, w + ": NULL table, reward, done, value, last value, adv or ret buffer");
+    if (with_boot && !dev_boot_KN) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_boot_KN");
+    const int P = pop->n_members, N = h->cfg.n_envs, n = pop_width(h, P), n_min = pop_slices(h) ? h->slice_min : n;
+    if (K < 1 || (long long)K * n_min < 2)
+        return fail(h, SSG_ERR_BAD_ARG, w + ": K must be >= 1 and K * (a member's envs) >= 2 for every member");
+    rc = check_workspace(h, dev_workspace, workspace_nbytes, pop_need_gae(P, n), what);
+    if (rc == SSG_OK) rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_pop_gae(P, K, N, dev_table, dev_reward_KN, dev_done_KN, dev_value_KN, dev_last_value, dev_adv_KN, dev_ret_KN,
+                                       dev_workspace, static_cast<hipStream_t>(stream), pop_slices(h), n, with_boot ? dev_boot_KN : nullptr);
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population gae launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
 int ssg_pop_gae(ssg_handle *h, const ssg_population *pop, const float *dev_table, int K, const double *dev_reward_KN,
                 const uint8_t *dev_done_KN, const float *dev_value_KN, const float *dev_last_value, float *dev_adv_KN, float *dev_ret_KN,
                 void *dev_workspace, size_t workspace_nbytes, void *stream)
 {
-    int rc = pop_bound(h);
-    if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_gae");
-    if (rc != SSG_OK) return rc;
-    if (!dev_table || !dev_reward_KN || !dev_done_KN || !dev_value_KN || !dev_last_value || !dev_adv_KN || !dev_ret_KN)
-        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_gae: NULL table, reward, done, value, last value, adv or ret buffer");
-    const int P = pop->n_members, N = h->cfg.n_envs, n = pop_width(h, P), n_min = pop_slices(h) ? h->slice_min : n;
-    if (K < 1 || (long long)K * n_min < 2)
-        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_gae: K must be >= 1 and K * (a member's envs) >= 2 for every member");
-    rc = check_workspace(h, dev_workspace, workspace_nbytes, pop_need_gae(P, n), "ssg_pop_gae");
-    if (rc == SSG_OK) rc = check_ready(h, false);
-    if (rc != SSG_OK) return rc;
-    hipError_t e = ssg::launch_pop_gae(P, K, N, dev_table, dev_reward_KN, dev_done_KN, dev_value_KN, dev_last_value, dev_adv_KN, dev_ret_KN,
-                                       dev_workspace, static_cast<hipStream_t>(stream), pop_slices(h), n);
-    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population gae launch: ") + hipGetErrorString(e));
-    return SSG_OK;
+    return pop_gae(h, pop, dev_table, K, dev_reward_KN, dev_done_KN, dev_value_KN, dev_last_value, nullptr, false, dev_adv_KN, dev_ret_KN,
+                   dev_workspace, workspace_nbytes, stream, "ssg_pop_gae");
+}
+
+int ssg_pop_gae_boot(ssg_handle *h, const ssg_population *pop, const float *dev_table, int K, const double *dev_reward_KN,
+                     const uint8_t *dev_done_KN, const float *dev_value_KN, const float *dev_last_value, const float *dev_boot_KN,
+                     float *dev_adv_KN, float *dev_ret_KN, void *dev_workspace, size_t workspace_nbytes, void *stream)
+{
+    return pop_gae(h, pop, dev_table, K, dev_reward_KN, dev_done_KN, dev_value_KN, dev_last_value, dev_boot_KN, true, dev_adv_KN, dev_ret_KN,
+                   dev_workspace, workspace_nbytes, stream, "ssg_pop_gae_boot");
 }
 
 // What the population's update entry points refuse alike once the population record (and the ext record) passed, in their order;
@@ -2446,6 +2569,31 @@ int ssg_set_terminal_obs(ssg_handle *h, double *dev_term_obs)
     if (dev_term_obs && !(h->cfg.flags & SSG_FLAG_AUTO_RESET))
         return fail(h, SSG_ERR_BAD_ARG, "ssg_set_terminal_obs: only a handle that resets its done envs in-kernel (SSG_FLAG_AUTO_RESET) replaces terminal observations");
     h->dev.term_obs = dev_term_obs;
+    return SSG_OK;
+}
+
+int ssg_set_timeout_boot(ssg_handle *h, const ssg_timeout_boot *rec)
+{
+    if (!h) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_set_timeout_boot: NULL handle");
+    if (!rec) {
+        h->tob = ssg_timeout_boot{};
+        return SSG_OK;
+    }
+    if (h->cfg.history > 2)
+        return fail(h, SSG_ERR_UNSUPPORTED, "ssg_set_timeout_boot: history > 2 builds its rows in the frame-shift kernel: no terminal observations (ssg_set_terminal_obs)");
+    if (!(h->cfg.flags & SSG_FLAG_AUTO_RESET))
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_set_timeout_boot: only a handle that resets its done envs in-kernel (SSG_FLAG_AUTO_RESET) stores terminal observations");
+    if (rec->struct_size != sizeof(ssg_timeout_boot)) return fail(h, SSG_ERR_BAD_ARG, "ssg_set_timeout_boot: ssg_timeout_boot.struct_size != sizeof(ssg_timeout_boot)");
+    if (rec->rows < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_set_timeout_boot: rows < 1");
+    if (!rec->dev_term_obs_KND || !rec->dev_boot_KN) return fail(h, SSG_ERR_BAD_ARG, "ssg_set_timeout_boot: NULL dev_term_obs_KND or dev_boot_KN");
+    h->tob = *rec;
+    return SSG_OK;
+}
+
+int ssg_get_timeout_boot(const ssg_handle *h, ssg_timeout_boot *out)
+{
+    if (!h || !out) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_get_timeout_boot: NULL handle or out");
+    *out = h->tob;
     return SSG_OK;
 }
 

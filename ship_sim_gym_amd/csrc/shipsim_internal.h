@@ -228,6 +228,18 @@ hipError_t launch_policy(const PolicyLaunch &l, hipStream_t stream);
 // launch_policy hands such a record on
 hipError_t prepare_policy_filter();
 hipError_t launch_policy_filter(const PolicyLaunch &l, hipStream_t stream);
+// The time-out values of a rollout's K rows (ssg_timeout_values / ssg_pop_timeout_values), in a third object of shipsim_policy.hip
+// (-DSSG_POLICY_BOOT_TU).  Of l it reads policy, members, n, slices and filter; row k's flags and boot entries start k*stride in, its
+// observation rows k*n_envs*obs_dim doubles into term_obs.
+struct TimeoutLaunch {
+    int K, n_envs;
+    size_t stride;
+    const uint8_t *flags;
+    const double *term_obs;
+    float *boot;
+};
+hipError_t prepare_policy_boot();
+hipError_t launch_timeout_values(const PolicyLaunch &l, const TimeoutLaunch &t, hipStream_t stream);
 // GAE and the PPO update (shipsim_ppo.hip).  Workspace: f32[4] advantage statistics at kPpoStatsOff (mean, std + adv_eps, its
 // inverse), then from kPpoSlotsOff the gradient kernel's per-workgroup slots [grid][P + 4] — or, during ssg_ppo_gae, its f64 partials.
 constexpr size_t kPpoStatsOff = 0, kPpoSlotsOff = 256;
@@ -238,7 +250,7 @@ int ppo_grid(long long M); // gradient workgroups for a minibatch of M samples
 size_t ppo_grad_lds_bytes(const ssg_policy &p);
 hipError_t prepare_ppo(); // (the dynamic-LDS limit of the gradient kernel: up to 151 KB at obs_dim 176, hidden 128, 2 layers)
 hipError_t launch_ppo_gae(const ssg_ppo_hparams &hp, int K, int N, const double *rew, const uint8_t *done, const float *val,
-                          const float *last_val, float *adv, float *ret, void *ws, hipStream_t stream);
+                          const float *last_val, float *adv, float *ret, void *ws, hipStream_t stream, const float *boot = nullptr);
 hipError_t launch_ppo_adam(const ssg_policy &p, const ssg_ppo_hparams &hp, const float *grad, float *adam_mv, int64_t step,
                            hipStream_t stream);
 // A population of `members` policies on one handle (ssg_pop_*): p is the shared shape with dev_params = f32 [members][L]; member m owns
@@ -261,7 +273,7 @@ void pop_pack(int members, const ssg_ppo_hparams *hp, int64_t step0, int n_steps
 void pop_pack_steps(int members, const ssg_ppo_hparams *hp, const int64_t *step0, int n_steps, float *out); // (a starting step per member)
 hipError_t launch_pop_gae(int members, int K, int N, const float *table, const double *rew, const uint8_t *done, const float *val,
                           const float *last_val, float *adv, float *ret, void *ws, hipStream_t stream, const int32_t *slices = nullptr,
-                          int n_max = 0);
+                          int n_max = 0, const float *boot = nullptr);
 hipError_t launch_pop_exploit(const ssg_policy &p, int members, const int32_t *src, float *adam_mv, hipStream_t stream);
 // The extended update (ssg_ppo_grad_ext / ssg_ppo_update_ext / ssg_pop_update_ext): value clip, KL penalty, gradient-norm clip.
 // From the plain path's slot offset the workspace holds the running sum of the epoch's mean(KL) (f32 [members]), the gradient vector of

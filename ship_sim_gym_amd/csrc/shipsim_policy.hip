@@ -22,6 +22,10 @@
 // chain as above.  With two layers the shared plan overwrites x with the second layer's output; a launch that runs both towers keeps a
 // third activation buffer for it instead, so that x survives for the vf tower (re-forming x would read the f64 observation rows twice).
 // The value-only launch skips the pi tower, the dist kernel the vf tower: both keep the shared plan's two buffers.
+//
+// Time-out values (ssg_timeout_values / ssg_pop_timeout_values, -DSSG_POLICY_BOOT_TU): the value-only forward over the terminal
+// observations of a rollout's K rows in one launch, for the waves whose flags hold a time-out (timeout_value_kernel, at the end of the
+// kernels).
 #include <cstdint>
 
 #include "shipsim_internal.h"
@@ -504,6 +508,95 @@ __global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1
 }
 #endif
 
+#ifdef SSG_POLICY_BOOT_TU
+// The time-out values of a rollout (ssg_timeout_values / ssg_pop_timeout_values): boot[k][e] = V(terminal observation of env e at step
+// k) where the flags byte says the clock alone ended the episode, +0.0f elsewhere.  Grid (workgroups of n envs, members, K), policy_dist's
+// geometry: workgroup (x, m, k) owns the envs [m0 + 64 x, ...) of member m (m0 = m*n, or its row of the slices table; one policy: members
+// = 1, n = the envs) in row k: flags and boot k*stride entries in, the observation rows k*n_envs*D doubles into term_obs.  It reads its
+// 64 flag bytes; with no time-out lane it writes +0.0f for its live lanes and leaves ahead of every barrier (uniform: one wave).
+// Otherwise the value-only forward of policy_act_body on its rows — the same step1_x, dense, tower, heads / head_v, in its order, so a
+// time-out's value is ssg_policy_act's dev_value for that row bit for bit — and per lane a SELECT: the rows of lanes the step did not
+// reset hold stale or never-written memory (a NaN there must not reach boot through a product).  A filter's state rows are read, never
+// updated.  A kernel of its own in an object of its own (-DSSG_POLICY_BOOT_TU): the other objects' device code stays what it is.
+template <bool SPLIT, bool FILTER>
+__global__ void __launch_bounds__(kPolWave) __attribute__((amdgpu_waves_per_eu(1, 2))) timeout_value_kernel(const ssg_policy p, const float *__restrict__ params, const double *__restrict__ scale,
+                                                              int n, int n_envs, size_t stride, const int32_t *__restrict__ slices,
+                                                              const uint8_t *__restrict__ flags, const double *__restrict__ term_obs,
+                                                              float *__restrict__ boot, int plen, double clip)
+{
+    extern __shared__ float4 lds4[];
+    size_t m0 = (size_t)blockIdx.y * (size_t)n;
+    if (slices) {
+        const int32_t *row = slices + (size_t)blockIdx.y * SSG_POP_SLICE_ROW;
+        m0 = (size_t)row[0];
+        n = row[1];
+        if ((int)(blockIdx.x * kPolWave) >= n) return; // (uniform over the workgroup)
+    }
+    const int lane = threadIdx.x;
+    const int e0 = blockIdx.x * kPolWave;
+    const int ne = (n - e0 < kPolWave) ? n - e0 : kPolWave; // tail workgroup: lanes >= ne read no flag and store nothing
+    const size_t k = blockIdx.z, o = k * stride + m0 + (size_t)e0 + (size_t)lane;
+    bool timeout = false;
+    if (lane < ne) {
+        const unsigned f = flags[o];
+        timeout = (f & SSG_EV_MAX_STEPS) != 0 && (f & (SSG_EV_COLLIDING | SSG_EV_OUT_OF_BOUNDS | SSG_EV_NO_GOALS_LEFT)) == 0;
+    }
+    if (!__any(timeout)) {
+        if (lane < ne) boot[o] = 0.0f;
+        return;
+    }
+    const int D = p.obs_dim, H = p.hidden, A = p.n_actions;
+    params += (size_t)blockIdx.y * (size_t)plen;
+    if constexpr (FILTER) scale += (size_t)blockIdx.y * SSG_FILTER_ROWS * (size_t)D;
+    const int R4 = ((D > H ? D : H) + 3) & ~3;
+    float *wt = reinterpret_cast<float *>(lds4);
+    float *bufA = wt + 16 * R4;
+    float *bufB = bufA + R4 * kPolStride;
+    { // policy_act_body's step 1 on the workgroup's ne terminal-observation rows (no x rows are kept)
+        const double *src = term_obs + ((k * (size_t)n_envs + m0) + (size_t)e0) * (size_t)D;
+        const int total = ne * D, qd = kPolWave / D, rd = kPolWave % D;
+        int d = lane % D, el = lane / D;
+        if constexpr (FILTER) {
+            double *fs = reinterpret_cast<double *>(wt);
+            for (int i = lane; i < D; i += kPolWave) {
+                const double den = scale[2 * D + i];
+                fs[i] = scale[i];
+                fs[D + i] = den == 0.0 ? 1.0 : den;
+            }
+            __syncthreads();
+        }
+        for (int i = lane; i < total; i += kPolWave) {
+            bufA[d * kPolStride + el] = step1_x<FILTER>(src[i], scale, reinterpret_cast<const double *>(wt), d, D, clip);
+            d += rd;
+            el += qd;
+            if (d >= D) { d -= D; ++el; }
+        }
+        for (int r = D; r < R4; ++r) bufA[r * kPolStride + lane] = 0.0f;
+    }
+    float v;
+    if (SPLIT) { // the vf tower alone, in the shared plan's two buffers
+        const int L = p.n_hidden_layers, kind = p.activation & 0xff;
+        const int T = H * D + H + (L - 1) * (H * H + H);
+        const float *Pv = params + T + A * H + A;
+        const float *h = tower(Pv, D, H, L, kind, bufA, bufB, bufA, wt, lane);
+        v = head_v(Pv + T, H, h, wt, lane);
+    } else {
+        const float *P = params;
+        dense(P, P + H * D, D, H, p.activation, bufA, bufB, wt, lane);
+        P += H * D + H;
+        const float *h = bufB;
+        if (p.n_hidden_layers == 2) {
+            dense(P, P + H * H, H, H, p.activation, bufB, bufA, wt, lane);
+            P += H * H + H;
+            h = bufA;
+        }
+        float lg[4];
+        heads(P, H, A, h, wt, lane, lg, &v);
+    }
+    if (lane < ne) boot[o] = timeout ? v : 0.0f;
+}
+#endif
+
 } // namespace
 
 static bool is_split(const ssg_policy &p) { return (p.activation & SSG_POLICY_SEPARATE_VALUE) != 0; }
@@ -565,6 +658,24 @@ hipError_t launch_policy_filter(const PolicyLaunch &l, hipStream_t stream)
 {
     const bool split = is_split(*l.policy);
     return launch_act(kFilter[l.members > 0][split][l.greedy], kFilterSliced[split][l.greedy], l, l.filter->state, stream, l.filter->clip);
+}
+#elif defined(SSG_POLICY_BOOT_TU)
+// the time-out value instantiations, indexed [split][filter]
+typedef decltype(&timeout_value_kernel<false, false>) TimeoutKernel;
+static const TimeoutKernel kTimeout[2][2] = {{timeout_value_kernel<false, false>, timeout_value_kernel<false, true>},
+                                             {timeout_value_kernel<true, false>, timeout_value_kernel<true, true>}};
+
+hipError_t prepare_policy_boot() { return raise_lds_limit(&kTimeout[0][0], 4); }
+
+hipError_t launch_timeout_values(const PolicyLaunch &l, const TimeoutLaunch &t, hipStream_t stream)
+{
+    const ssg_policy &p = *l.policy;
+    const bool pop = l.members > 0;
+    const dim3 grid((unsigned)((l.n + kPolWave - 1) / kPolWave), pop ? (unsigned)l.members : 1u, (unsigned)t.K); // (n: with slices, the largest)
+    hipLaunchKernelGGL(kTimeout[is_split(p)][l.filter != nullptr], grid, dim3(kPolWave), policy_lds_bytes(p, false), stream, p, p.dev_params,
+                       l.filter ? l.filter->state : p.dev_obs_scale, l.n, t.n_envs, t.stride, l.slices, t.flags, t.term_obs, t.boot,
+                       pop ? ppo_packed_len(p) : 0, l.filter ? l.filter->clip : 0.0);
+    return hipGetLastError();
 }
 #else
 

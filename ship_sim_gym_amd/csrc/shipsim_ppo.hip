@@ -69,9 +69,15 @@ __device__ __forceinline__ float tile_sum(const float *v, int stride)
 // ------------------------------------------------------------------------------------------------------------------------------
 // The walk of workgroup blockIdx.x's 256 envs out of n, over [K] rows that are N apart (the body of both GAE kernels; every pointer
 // is the first env's of the batch the workgroup belongs to, rs / rq its 2 x 256 doubles of LDS).
+// BOOT (ssg_ppo_gae_boot / ssg_pop_gae_boot): a done sample's one-step target is boot[i] (the value of a timed-out episode's terminal
+// observation, +0 for a true terminal) instead of 0 — a select; the lambda chain is cut at every done as before.  Kernels of their own
+// below the three walks; everything BOOT adds sits under `if constexpr (BOOT)`, so the three kernels without it keep their code
+// (how to check: profiles/timeout_boot/README.md).
+template <bool BOOT = false>
 __device__ __forceinline__ void gae_body(int K, int N, int n, const double *__restrict__ rew, const uint8_t *__restrict__ done,
                                          const float *__restrict__ val, const float *__restrict__ last_val, float *__restrict__ adv_out,
-                                         float *__restrict__ ret_out, float gf, float glf, double2 *__restrict__ part, double *rs, double *rq)
+                                         float *__restrict__ ret_out, float gf, float glf, double2 *__restrict__ part, double *rs, double *rq,
+                                         const float *__restrict__ boot = nullptr)
 {
     const int e = blockIdx.x * 256 + threadIdx.x;
     double s = 0.0, q = 0.0;
@@ -80,7 +86,14 @@ __device__ __forceinline__ void gae_body(int K, int N, int n, const double *__re
         for (int t = K - 1; t >= 0; --t) {
             const size_t i = (size_t)t * N + e;
             const float nonterm = 1.0f - (float)done[i], v = val[i];
-            const float delta = ((float)rew[i] + (gf * nxt) * nonterm) - v;
+            float delta;
+            if constexpr (BOOT) {
+                const float bt = boot[i]; // (read for every sample, with the row's other loads: not a load that waits for done[i])
+                const float tgt = done[i] ? bt : nxt;
+                delta = ((float)rew[i] + gf * tgt) - v;
+            } else {
+                delta = ((float)rew[i] + (gf * nxt) * nonterm) - v;
+            }
             adv = delta + (glf * nonterm) * adv;
             adv_out[i] = adv;
             ret_out[i] = adv + v;
@@ -144,6 +157,43 @@ __global__ void __launch_bounds__(256) pop_gae_sliced_kernel(int K, int N, const
     if ((int)(blockIdx.x * 256) >= n) return; // (uniform over the workgroup)
     gae_body(K, N, n, rew + e0, done + e0, val + e0, last_val + e0, adv_out + e0, ret_out + e0, table[m * kPopTableRow + PT_GF],
              table[m * kPopTableRow + PT_GLF], part + m * (size_t)nb, rs, rq);
+}
+
+// The three walks above with BOOT: the same geometry, partials and argument order, plus the boot rows (N apart, like every buffer).
+__global__ void __launch_bounds__(256) ppo_gae_boot_kernel(int K, int N, const double *__restrict__ rew, const uint8_t *__restrict__ done,
+                                                           const float *__restrict__ val, const float *__restrict__ last_val,
+                                                           float *__restrict__ adv_out, float *__restrict__ ret_out, float gf, float glf,
+                                                           double2 *__restrict__ part, const float *__restrict__ boot)
+{
+    __shared__ double rs[256], rq[256];
+    gae_body<true>(K, N, N, rew, done, val, last_val, adv_out, ret_out, gf, glf, part, rs, rq, boot);
+}
+
+__global__ void __launch_bounds__(256) pop_gae_boot_kernel(int K, int N, int n, int nb, const double *__restrict__ rew,
+                                                           const uint8_t *__restrict__ done, const float *__restrict__ val,
+                                                           const float *__restrict__ last_val, float *__restrict__ adv_out,
+                                                           float *__restrict__ ret_out, const float *__restrict__ table,
+                                                           double2 *__restrict__ part, const float *__restrict__ boot)
+{
+    __shared__ double rs[256], rq[256];
+    const size_t m = blockIdx.y, e0 = m * (size_t)n;
+    gae_body<true>(K, N, n, rew + e0, done + e0, val + e0, last_val + e0, adv_out + e0, ret_out + e0, table[m * kPopTableRow + PT_GF],
+                   table[m * kPopTableRow + PT_GLF], part + m * (size_t)nb, rs, rq, boot + e0);
+}
+
+__global__ void __launch_bounds__(256) pop_gae_boot_sliced_kernel(int K, int N, const int32_t *__restrict__ slices, int nb,
+                                                                  const double *__restrict__ rew, const uint8_t *__restrict__ done,
+                                                                  const float *__restrict__ val, const float *__restrict__ last_val,
+                                                                  float *__restrict__ adv_out, float *__restrict__ ret_out,
+                                                                  const float *__restrict__ table, double2 *__restrict__ part,
+                                                                  const float *__restrict__ boot)
+{
+    __shared__ double rs[256], rq[256];
+    const size_t m = blockIdx.y, e0 = (size_t)slices[m * SSG_POP_SLICE_ROW];
+    const int n = slices[m * SSG_POP_SLICE_ROW + 1];
+    if ((int)(blockIdx.x * 256) >= n) return; // (uniform over the workgroup)
+    gae_body<true>(K, N, n, rew + e0, done + e0, val + e0, last_val + e0, adv_out + e0, ret_out + e0, table[m * kPopTableRow + PT_GF],
+                   table[m * kPopTableRow + PT_GLF], part + m * (size_t)nb, rs, rq, boot + e0);
 }
 
 // stats[0] = mean, stats[1] = std + adv_eps (unbiased std, as torch's .std()), stats[2] = 1 / stats[1]
@@ -1101,15 +1151,19 @@ hipError_t prepare_ppo()
 }
 
 hipError_t launch_ppo_gae(const ssg_ppo_hparams &hp, int K, int N, const double *rew, const uint8_t *done, const float *val,
-                          const float *last_val, float *adv, float *ret, void *ws, hipStream_t stream)
+                          const float *last_val, float *adv, float *ret, void *ws, hipStream_t stream, const float *boot)
 {
     const int nb = ppo_gae_blocks(N);
     float *stats = reinterpret_cast<float *>(static_cast<char *>(ws) + kPpoStatsOff);
     double2 *part = reinterpret_cast<double2 *>(static_cast<char *>(ws) + kPpoSlotsOff);
     float row[kPopTableRow];
     loss_row(hp, row);
-    hipLaunchKernelGGL(ppo_gae_kernel, dim3(nb), dim3(256), 0, stream, K, N, rew, done, val, last_val, adv, ret, row[PT_GF], row[PT_GLF],
-                       part);
+    if (boot)
+        hipLaunchKernelGGL(ppo_gae_boot_kernel, dim3(nb), dim3(256), 0, stream, K, N, rew, done, val, last_val, adv, ret, row[PT_GF],
+                           row[PT_GLF], part, boot);
+    else
+        hipLaunchKernelGGL(ppo_gae_kernel, dim3(nb), dim3(256), 0, stream, K, N, rew, done, val, last_val, adv, ret, row[PT_GF], row[PT_GLF],
+                           part);
     hipLaunchKernelGGL(ppo_gae_stats_kernel, dim3(1), dim3(256), 0, stream, (const double2 *)part, nb, (double)K * (double)N,
                        row[PT_ADV_EPS], stats);
     return hipGetLastError();
@@ -1275,18 +1329,27 @@ void pop_pack_steps(int members, const ssg_ppo_hparams *hp, const int64_t *step0
 }
 
 hipError_t launch_pop_gae(int members, int K, int N, const float *table, const double *rew, const uint8_t *done, const float *val,
-                          const float *last_val, float *adv, float *ret, void *ws, hipStream_t stream, const int32_t *slices, int n_max)
+                          const float *last_val, float *adv, float *ret, void *ws, hipStream_t stream, const int32_t *slices, int n_max,
+                          const float *boot)
 {
     const int n = slices ? n_max : N / members, nb = ppo_gae_blocks(n);
     float *stats = reinterpret_cast<float *>(static_cast<char *>(ws) + kPpoStatsOff);
     double2 *part = reinterpret_cast<double2 *>(static_cast<char *>(ws) + kPopSlotsOff);
     if (slices) {
-        hipLaunchKernelGGL(pop_gae_sliced_kernel, dim3(nb, members), dim3(256), 0, stream, K, N, slices, nb, rew, done, val, last_val, adv, ret,
-                           table, part);
+        if (boot)
+            hipLaunchKernelGGL(pop_gae_boot_sliced_kernel, dim3(nb, members), dim3(256), 0, stream, K, N, slices, nb, rew, done, val, last_val,
+                               adv, ret, table, part, boot);
+        else
+            hipLaunchKernelGGL(pop_gae_sliced_kernel, dim3(nb, members), dim3(256), 0, stream, K, N, slices, nb, rew, done, val, last_val, adv,
+                               ret, table, part);
         hipLaunchKernelGGL(pop_gae_stats_sliced_kernel, dim3(members), dim3(256), 0, stream, (const double2 *)part, nb, K, slices, table, stats);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(pop_gae_kernel, dim3(nb, members), dim3(256), 0, stream, K, N, n, nb, rew, done, val, last_val, adv, ret, table, part);
+    if (boot)
+        hipLaunchKernelGGL(pop_gae_boot_kernel, dim3(nb, members), dim3(256), 0, stream, K, N, n, nb, rew, done, val, last_val, adv, ret, table,
+                           part, boot);
+    else
+        hipLaunchKernelGGL(pop_gae_kernel, dim3(nb, members), dim3(256), 0, stream, K, N, n, nb, rew, done, val, last_val, adv, ret, table, part);
     hipLaunchKernelGGL(pop_gae_stats_kernel, dim3(members), dim3(256), 0, stream, (const double2 *)part, nb, (double)K * (double)n, table, stats);
     return hipGetLastError();
 }

@@ -310,7 +310,8 @@ class PopulationPPO(object):
         """GAE of every member over its columns of the rollout batch (``rollout_population``'s dict) with its own gamma / lam: returns
         (adv, ret) f32 [K, N], stored in the batch as "adv" / "ret"; leaves the per-member advantage statistics for update().
         return_filter (a ``ReturnFilter`` of P members): it is applied to the batch first and GAE runs on batch["rew_norm"];
-        batch["rew"] stays as it is."""
+        batch["rew"] stays as it is.  With "boot" in the batch (env.set_timeout_bootstrap): ssg_pop_gae_boot — a done sample's one-step
+        target is gamma_m * boot instead of 0; boot goes in as it is, with a return filter too."""
         torch = _torch()
         K, n_env = self._KN(batch)
         dev = self.population.device
@@ -318,6 +319,10 @@ class PopulationPPO(object):
             return_filter.apply(batch)
         p = [self._flat(batch, "rew" if return_filter is None else "rew_norm", torch.float64, (K, n_env)), self._flat(batch, "done", torch.uint8, (K, n_env)),
              self._flat(batch, "val", torch.float32, (K, n_env)), self._flat(batch, "last_val", torch.float32, (n_env,))]
+        name = "ssg_pop_gae"
+        if "boot" in batch:
+            p.append(self._flat(batch, "boot", torch.float32, (K, n_env)))
+            name = "ssg_pop_gae_boot"
         self._ws(K * max(self.member_envs), 1)
         self._last_K = K
         adv = torch.empty((K, n_env), dtype=torch.float32, device=dev)
@@ -325,9 +330,9 @@ class PopulationPPO(object):
         pop, h = self.population.to_native(), self.env._h
         with torch.cuda.device(dev):
             table = self._table(0)  # (no Adam rows: the step counts do not enter)
-            N.check(N.lib().ssg_pop_gae(h, C.byref(pop), C.c_void_p(table.data_ptr()), K, *p, C.c_void_p(adv.data_ptr()),
-                                        C.c_void_p(ret.data_ptr()), C.c_void_p(self.workspace.data_ptr()), self.workspace.numel(),
-                                        self._stream()), h, "ssg_pop_gae")
+            N.check(getattr(N.lib(), name)(h, C.byref(pop), C.c_void_p(table.data_ptr()), K, *p, C.c_void_p(adv.data_ptr()),
+                                           C.c_void_p(ret.data_ptr()), C.c_void_p(self.workspace.data_ptr()), self.workspace.numel(),
+                                           self._stream()), h, name)
         batch["adv"], batch["ret"] = adv, ret
         return adv, ret
 

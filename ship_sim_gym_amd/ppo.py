@@ -20,6 +20,10 @@ observations, and ``update`` does so itself when the batch has none — so call 
 _train_step does (ssg_ppo_set_adv_norm), instead of once per rollout with gae()'s statistics; ``minibatch_adv_stats()`` shows the last
 minibatch's row and ``minibatch_adv_reference`` restates the device's order of operations in numpy.
 
+With ``env.set_timeout_bootstrap(True)`` the rollout's batch carries "boot" (f32 [K, N]: the value of a timed-out episode's terminal
+observation, +0 elsewhere) and ``gae`` takes a done sample's one-step target from it (ssg_ppo_gae_boot) instead of scoring a time-out as
+a return of 0; ``gae_boot_reference`` restates that walk and its statistics in numpy.
+
 ``perm_seed`` lets the library draw the minibatch permutations (ssg_ppo_perm): ``update(batch, None, ...)`` then shuffles as PPO2's learn
 does per epoch (np.random.shuffle(inds), train/stable_baselines/ppo.py:90), each row a counter-based permutation keyed by (perm_seed,
 ``updates``, ``member``, epoch) — the object's count of update() calls, kept beside ``step`` and settable from a checkpoint.
@@ -112,6 +116,47 @@ def minibatch_adv_reference(adv_gathered_f32, valid, adv_eps, partials=False):
         stdp = np.float32(np.sqrt(var)) + np.float32(adv_eps)
         row = np.array([np.float32(mean), stdp, np.float32(1.0) / stdp, 0.0], dtype=np.float32)
     return (row, part[:B].copy()) if partials else row
+
+
+def gae_boot_reference(rew, done, val, last_val, boot, gamma=0.99, lam=0.95, adv_eps=1e-8):
+    """ssg_ppo_gae_boot restated in numpy, in the device's order of operations: (adv f32 [K, N], ret f32 [K, N], stats f32 [4] =
+    {mean, std + adv_eps, its inverse, 0}).  rew f64, done u8, val / boot f32 [K, N], last_val f32 [N].  The walk, in f32, every
+    product and sum separately rounded, t = K-1 .. 0:  nonterm = 1 - done;  tgt = boot where done else nxt (a select);  delta = (rew
+    + gamma*tgt) - val;  adv = delta + ((gamma*lam)*nonterm)*adv;  ret = adv + val;  nxt = val.  The statistics: per env the f64 sums
+    of adv and adv^2 in the walk's order, the 256-env blocks' halving trees, the blocks' partials added per thread (block b, b + 256,
+    ...) and one more tree.  With an all-zero boot this is ssg_ppo_gae (finite inputs, no reward of -0.0)."""
+    import numpy as np
+    f32 = np.float32
+    rew, done = np.asarray(rew, dtype=np.float64), np.asarray(done) != 0
+    val, boot, nxt = np.asarray(val, dtype=f32), np.asarray(boot, dtype=f32), np.asarray(last_val, dtype=f32).copy()
+    K, n = rew.shape
+    gf, glf = f32(gamma), f32(float(gamma) * float(lam))
+    adv_out, ret_out = np.empty((K, n), dtype=f32), np.empty((K, n), dtype=f32)
+    adv = np.zeros(n, dtype=f32)
+    nb = -(-n // 256)
+    s, q = np.zeros(nb * 256), np.zeros(nb * 256)
+    for t in range(K - 1, -1, -1):
+        nonterm = f32(1) - done[t].astype(f32)
+        tgt = np.where(done[t], boot[t], nxt)
+        delta = (rew[t].astype(f32) + gf * tgt) - val[t]
+        adv = delta + (glf * nonterm) * adv
+        adv_out[t], ret_out[t] = adv, adv + val[t]
+        nxt = val[t]
+        a = adv.astype(np.float64)
+        s[:n] += a
+        q[:n] += a * a
+    part = np.zeros((-(-nb // 256) * 256, 2))
+    for b in range(nb):
+        part[b] = _tree256(np.stack([s[b * 256: b * 256 + 256], q[b * 256: b * 256 + 256]], axis=1))
+    acc = np.zeros((256, 2))
+    for r in range(part.shape[0] // 256):  # thread t: partials t, t + 256, ... in that order
+        acc += part[r * 256: r * 256 + 256]
+    ss, qq = _tree256(acc)
+    cnt = float(K) * float(n)
+    mean = ss / cnt
+    var = max(0.0, (qq - ss * mean) / (cnt - 1.0))
+    stdp = f32(np.sqrt(var)) + f32(adv_eps)
+    return adv_out, ret_out, np.array([f32(mean), stdp, f32(1.0) / stdp, 0.0], dtype=f32)
 
 
 _M64 = (1 << 64) - 1
@@ -312,7 +357,9 @@ class NativePPO(object):
     def gae(self, batch, gamma=0.99, lam=0.95, return_filter=None):
         """GAE over the rollout batch (train/ppo_torch.py's loop, bitwise): returns (adv, ret) f32 [K, N] and stores them in the batch
         as "adv" / "ret".  Also leaves the advantage mean / std on the device for the update (adv_stats()).  return_filter (a
-        ``ReturnFilter``): it is applied to the batch first and GAE runs on batch["rew_norm"]; batch["rew"] stays as it is."""
+        ``ReturnFilter``): it is applied to the batch first and GAE runs on batch["rew_norm"]; batch["rew"] stays as it is.  With
+        "boot" in the batch (env.set_timeout_bootstrap): ssg_ppo_gae_boot — a done sample's one-step target is gamma * boot instead of 0;
+        boot goes in as it is, with a return filter too (the value network already lives in normalised-return units)."""
         torch = _torch()
         if return_filter is not None:
             return_filter.apply(batch)
@@ -327,10 +374,16 @@ class NativePPO(object):
         ret = torch.empty_like(adv)
         ws, nb = self._ws_ptr()
         h = self.env._h
+        name, boot = "ssg_ppo_gae", ()
+        if "boot" in batch:
+            bt = self._flat(batch, "boot", torch.float32)
+            if tuple(bt.shape) != (K, n_env):
+                raise ValueError("NativePPO.gae: batch['boot'] must be [K, N]")
+            name, boot = "ssg_ppo_gae_boot", (C.c_void_p(bt.data_ptr()),)
         with torch.cuda.device(self.policy.device):
-            N.check(N.lib().ssg_ppo_gae(h, C.byref(self.hp), K, n_env, C.c_void_p(rew.data_ptr()), C.c_void_p(done.data_ptr()),
-                                        C.c_void_p(val.data_ptr()), C.c_void_p(last.data_ptr()), C.c_void_p(adv.data_ptr()),
-                                        C.c_void_p(ret.data_ptr()), ws, nb, self._stream()), h, "ssg_ppo_gae")
+            N.check(getattr(N.lib(), name)(h, C.byref(self.hp), K, n_env, C.c_void_p(rew.data_ptr()), C.c_void_p(done.data_ptr()),
+                                           C.c_void_p(val.data_ptr()), C.c_void_p(last.data_ptr()), *boot, C.c_void_p(adv.data_ptr()),
+                                           C.c_void_p(ret.data_ptr()), ws, nb, self._stream()), h, name)
         batch["adv"], batch["ret"] = adv, ret
         return adv, ret
 

@@ -656,12 +656,16 @@ class ShipVecEnv(*_BASES):
             raise ValueError("%s: K must be >= 1" % what)
         up = self._f32_rows(uniforms, (K, n), what + " uniforms") if uniforms is not None else None
         with torch.cuda.device(self.device):
+            boot = self._timeout_rows(K, out, what)
             out, p = self._rollout_buffers(K, out, what)
             rec = record.to_native()
             N.check(getattr(N.lib(), c_name)(self._h, C.byref(rec), K, up, int(seed), int(step0), C.c_void_p(self.obs.data_ptr()),
                                              p["act"], p["logp"], p["val"], p["obs"], p["rew"], p["done"], p["flags"], p["last_val"],
                                              n, self._stream()), self._h, c_name)
-        return {k: (v[:K] if k != "last_val" else v) for k, v in out.items()}
+        res = {k: (v[:K] if k != "last_val" else v) for k, v in out.items() if k != "boot"}
+        if boot is not None:  # (with the bootstrap off a caller's out["boot"] is not part of the batch: nothing wrote it)
+            res["boot"] = boot[:K]
+        return res
 
     def _rollout_buffers(self, K, out, what):
         """The out-dict of a policy-in-the-loop rollout of K steps (allocated, or the caller's checked) and its tensors' C pointers."""
@@ -740,6 +744,93 @@ class ShipVecEnv(*_BASES):
         for the whole population, then ssg_step).  Same out-dict, uniforms, Philox keying and `out` as rollout_policy; member m's
         columns are [m*n, (m+1)*n), n = N / P, or its slice of set_population_slices."""
         return self._rollout(self._check_population, population, "ssg_pop_rollout", "rollout_population", K, seed, step0, uniforms, out)
+
+    # ------------------------------------------------------------------------------------------------
+    # the time-out bootstrap (ssg_set_timeout_boot): the value of a timed-out episode's terminal observation, for GAE
+    # ------------------------------------------------------------------------------------------------
+    def set_timeout_bootstrap(self, on=True, rows=None):
+        """Switch the time-out bootstrap on or off.  While it is on, rollout_policy / rollout_population also return batch["boot"]
+        (f32 [K, N]): V(terminal observation) where the clock alone ended the episode (EV_MAX_STEPS without EV_COLLIDING,
+        EV_OUT_OF_BOUNDS or EV_NO_GOALS_LEFT), +0.0 elsewhere — one more launch per rollout, after the last-value forward; every other
+        entry of the batch and the env state stay bit for bit what they are with it off.  NativePPO.gae / PopulationPPO.gae then
+        bootstrap those samples from it.  rows: the longest rollout to allocate for now (the buffers grow when a rollout asks for
+        more).  The terminal observations take rows * N * D * 8 bytes of device memory (537 MB at 65 536 envs x 32 steps x D = 32,
+        67 MB at 4 096 x 64), allocated here, reused by every rollout, freed when switched off.  Needs in-kernel auto-reset and
+        history <= 2, like enable_terminal_obs, whose own binding stays in place between rollouts.  A refused call leaves the
+        previous state."""
+        if not on:
+            N.check(N.lib().ssg_set_timeout_boot(self._h, None), self._h, "ssg_set_timeout_boot")
+            self._timeout_boot = None
+            return
+        self._bind_timeout_boot(max(1, int(rows or 1)), None)
+
+    @property
+    def timeout_bootstrap(self):
+        """The rows the bound time-out buffers serve (ssg_get_timeout_boot), or 0 with the bootstrap off."""
+        rec = N.TimeoutBootRecord()
+        N.check(N.lib().ssg_get_timeout_boot(self._h, C.byref(rec)), self._h, "ssg_get_timeout_boot")
+        return int(rec.rows) if rec.struct_size else 0
+
+    def _bind_timeout_boot(self, rows, boot):
+        """Bind a record of `rows` rows: the kept terminal-observation rows if they serve that many (else new ones), and `boot` (None:
+        the kept or a new f32 [rows, N])."""
+        torch = _torch()
+        old = getattr(self, "_timeout_boot", None)
+        with torch.cuda.device(self.device):
+            if old is not None and old["term_obs"].shape[0] >= rows:
+                term = old["term_obs"]
+            else:
+                old = None  # (grown: the kept boot rows are too short as well)
+                term = torch.empty((rows, self.num_envs, self.states_history), dtype=torch.float64, device=self.device)
+            if boot is None:
+                boot = old["boot"] if old is not None else torch.empty((term.shape[0], self.num_envs), dtype=torch.float32, device=self.device)
+        rec = N.TimeoutBootRecord()
+        rec.struct_size, rec.rows = C.sizeof(N.TimeoutBootRecord), min(int(term.shape[0]), int(boot.shape[0]))
+        rec.dev_term_obs_KND, rec.dev_boot_KN = term.data_ptr(), boot.data_ptr()
+        N.check(N.lib().ssg_set_timeout_boot(self._h, C.byref(rec)), self._h, "ssg_set_timeout_boot")
+        self._timeout_boot = {"term_obs": term, "boot": boot}
+
+    def timeout_values(self, record, flags, term_obs, out=None):
+        """The time-out values of K rows in one launch (ssg_timeout_values for a NativePolicy, ssg_pop_timeout_values for a
+        NativePopulation): flags u8 [K, N] (a rollout's), term_obs f64 [K, N, D] (the terminal observations, read only where a wave of
+        64 envs holds a time-out) -> f32 [K, N]: the value ``policy_act`` gives for that observation row where N.is_timeout(flags),
+        +0.0 elsewhere.  Needs no bootstrap to be switched on; a bound observation filter is read, never updated."""
+        torch = _torch()
+        from .population import NativePopulation
+        pop = isinstance(record, NativePopulation)
+        what = "timeout_values"
+        (self._check_population if pop else self._check_policy)(record, what)
+        n, D = self.num_envs, self.states_history
+        if (flags.dtype != torch.uint8 or flags.device != self.device or not flags.is_contiguous() or flags.dim() != 2
+                or int(flags.shape[1]) != n or int(flags.shape[0]) < 1):
+            raise ValueError("%s: flags must be a contiguous uint8 tensor [K, %d] on %s" % (what, n, self.device))
+        K = int(flags.shape[0])
+        if (term_obs.dtype != torch.float64 or term_obs.device != self.device or not term_obs.is_contiguous()
+                or tuple(term_obs.shape) != (K, n, D)):
+            raise ValueError("%s: term_obs must be a contiguous float64 tensor %s on %s" % (what, (K, n, D), self.device))
+        with torch.cuda.device(self.device):
+            if out is None:
+                out = torch.empty((K, n), dtype=torch.float32, device=self.device)
+            op = self._f32_rows(out, (K, n), what + " out")
+            rec = record.to_native()
+            name = "ssg_pop_timeout_values" if pop else "ssg_timeout_values"
+            N.check(getattr(N.lib(), name)(self._h, C.byref(rec), K, C.c_void_p(flags.data_ptr()), C.c_void_p(term_obs.data_ptr()), op, n,
+                                           self._stream()), self._h, name)
+        return out[:K]
+
+    def _timeout_rows(self, K, out, what):
+        """Ahead of a rollout of K steps: None with the bootstrap off; else the f32 [>= K, N] tensor the rollout writes its time-out
+        values into — out["boot"] when the caller's out-dict has one, else a new one per rollout (a batch kept across rollouts keeps
+        its values) — bound together with terminal-observation rows that serve K."""
+        torch = _torch()
+        if getattr(self, "_timeout_boot", None) is None:
+            return None
+        boot = out.get("boot") if out is not None else None
+        if boot is None:
+            boot = torch.empty((K, self.num_envs), dtype=torch.float32, device=self.device)
+        self._f32_rows(boot, (K, self.num_envs), what + " out['boot']")
+        self._bind_timeout_boot(K, boot)
+        return boot
 
     # ------------------------------------------------------------------------------------------------
     # the observation filter (ssg_set_obs_filter; ship_sim_gym_amd/obs_filter.py)
@@ -870,6 +961,7 @@ class ShipVecEnv(*_BASES):
 
     def close(self):
         self.__dict__.pop("_traj_plans", None)
+        self.__dict__.pop("_timeout_boot", None)
         flt = self.__dict__.pop("_obs_filter", None)
         if flt is not None and self in flt._bound:
             flt._bound.remove(self)

@@ -21,6 +21,16 @@ history 2 -> D = 28) whole rollouts are timed with nothing bound, with a filter 
 three alternating in every repeat; and the filter's two launches alone (50 back-to-back ssg_obs_filter_update calls).  Medians and
 every repeat in us per rollout step; the shader clock as rocm-smi reports it before and after (null when it cannot be read).  The
 unbound figure of two builds of the library is compared by running this mode alternately with SSG_LIB_PATH set to each.
+
+    python tools/policy_rollout_timing.py --timeout-bootstrap [--envs 65536,4096] [--horizon 32,64] [--repeats 7]
+
+--timeout-bootstrap measures the time-out bootstrap (ShipVecEnv.set_timeout_bootstrap) instead: on ONE native env per env count (the
+default env, D = 32; --horizon lists one rollout length per env count) whole rollouts are timed with nothing bound and with the
+record bound, alternating in every repeat (the bound figure includes the one ssg_timeout_values launch, spread over the horizon);
+then, alone and back to back, that launch over the horizon's rows with no time-out in the batch ("none"), with every env timing out
+on one row ("one_row": the start of training, when every episode runs into the clock together) and with every sample a time-out
+("all_rows"), and ssg_ppo_dist over the same number of rows (a forward of every row, to set "all_rows" against).  Medians and every
+repeat; rollouts in us per step, launches in us per launch.
 """
 import argparse
 import ctypes as C
@@ -170,18 +180,96 @@ def measure_filter(mod, n, horizon, repeats, dev, beams):
             "sclk_before": clock0, "sclk_after": clock1}
 
 
+def measure_timeout(mod, n, horizon, repeats, dev):
+    torch.manual_seed(0)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    probe = mod.ShipVecEnv(1, mod.GameConfig, mod.EnvConfig, device=dev, n_maps=1)
+    D, A = probe.states_history, probe.action_space.n
+    probe.close()
+    net = mod.ActorCritic(D, A).to(dev)
+    shards = mod.make_shards(n, "native", net, dev, horizon)
+    env = shards[0].env
+    env.reset_tensor()
+    policy = mod.NativePolicy.from_actor_critic(net, shards[0].scale)
+
+    def run(bound):
+        if bool(env.timeout_bootstrap) != bound:
+            env.set_timeout_bootstrap(bound, rows=horizon)
+        mod.rollout(shards, horizon, "native", gen, policy)
+    clock0 = _sclk()
+    for m in (False, True) * 2:  # warm-up: two rollouts each
+        run(m)
+    torch.cuda.synchronize()
+    times = {"unbound": [], "bound": []}
+    for _ in range(repeats):
+        for name, m in (("unbound", False), ("bound", True)):
+            if bool(env.timeout_bootstrap) != m:
+                env.set_timeout_bootstrap(m, rows=horizon)
+            times[name].append(_timed(lambda: mod.rollout(shards, horizon, "native", gen, policy)) / horizon)
+    env.set_timeout_bootstrap(False)
+    # the launch alone, on rows of its own: real observations everywhere, so that a forward runs on what a rollout would hand it
+    rows = env.obs.unsqueeze(0).expand(horizon, n, D).contiguous()
+    out = torch.empty((horizon, n), dtype=torch.float32, device=dev)
+    flags = {"none": torch.zeros((horizon, n), dtype=torch.uint8, device=dev), "one_row": torch.zeros((horizon, n), dtype=torch.uint8, device=dev),
+             "all_rows": torch.full((horizon, n), N.EV_MAX_STEPS, dtype=torch.uint8, device=dev)}
+    flags["one_row"][horizon // 2] = N.EV_MAX_STEPS
+    x = torch.zeros((horizon * n, D), dtype=torch.float32, device=dev)
+    logp_all = torch.empty((horizon * n, 4), dtype=torch.float32, device=dev)
+    pol = policy.to_native()
+    L, h, st = N.lib(), env._h, env._stream()
+
+    def dist(k):
+        for _ in range(k):
+            N.check(L.ssg_ppo_dist(h, C.byref(pol), horizon * n, C.c_void_p(x.data_ptr()), C.c_void_p(logp_all.data_ptr()), st), h, "ssg_ppo_dist")
+
+    def values(f, k):
+        for _ in range(k):
+            env.timeout_values(policy, f, rows, out=out)
+    launch = {}
+    for name, f in flags.items():
+        values(f, 3)
+        torch.cuda.synchronize()
+        launch[name] = [_timed(lambda: values(f, 20)) / 20 for _ in range(repeats)]
+    dist(3)
+    torch.cuda.synchronize()
+    launch["ppo_dist"] = [_timed(lambda: dist(20)) / 20 for _ in range(repeats)]
+    clock1 = _sclk()
+    env.close()
+    res = {"envs": n, "obs_dim": D, "hidden": 64, "layers": 2, "n_actions": A, "horizon": horizon,
+           "term_obs_bytes": horizon * n * D * 8,
+           "unbound_us_per_step": round(statistics.median(times["unbound"]), 2), "bound_us_per_step": round(statistics.median(times["bound"]), 2),
+           "repeats_us": {k: [round(t, 2) for t in v] for k, v in times.items()}, "sclk_before": clock0, "sclk_after": clock1}
+    for name, v in launch.items():
+        res["launch_%s_us" % name] = round(statistics.median(v), 2)
+        res["launch_%s_repeats_us" % name] = [round(t, 2) for t in v]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", default="65536,4096")
-    ap.add_argument("--horizon", type=int, default=64)
+    ap.add_argument("--horizon", default="64", help="rollout steps; with --timeout-bootstrap a comma-separated list, one per env count")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--separate-value", action="store_true", help="also measure the separate-value-network shape, in the same process")
     ap.add_argument("--obs-filter", action="store_true", help="measure the observation filter instead (unbound / updating / frozen rollouts)")
     ap.add_argument("--beams", type=int, default=8, help="lidar beams of the --obs-filter env (8 -> D = 28)")
+    ap.add_argument("--timeout-bootstrap", action="store_true",
+                    help="measure the time-out bootstrap instead (unbound / bound rollouts, the one launch alone)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     mod = _ppo()
     dev = "cuda:0"
+    horizons = [int(x) for x in a.horizon.split(",")]
+    a.horizon = horizons[0]
+    if a.timeout_bootstrap:
+        envs = [int(n) for n in a.envs.split(",")]
+        if len(horizons) == 1:
+            horizons = horizons * len(envs)
+        res = [measure_timeout(mod, n, k, a.repeats, dev) for n, k in zip(envs, horizons)]
+        print(json.dumps({"tool": "policy_rollout_timing", "mode": "timeout_bootstrap", "lib": N.LIB_PATH,
+                          "device": torch.cuda.get_device_name(0), "results": res}))
+        return
     if a.obs_filter:
         res = [measure_filter(mod, int(n), a.horizon, a.repeats, dev, a.beams) for n in a.envs.split(",")]
         print(json.dumps({"tool": "policy_rollout_timing", "mode": "obs_filter", "lib": N.LIB_PATH, "device": torch.cuda.get_device_name(0),

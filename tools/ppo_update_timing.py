@@ -9,7 +9,7 @@ every update from the same parameters' values (their own copies) and draw their 
 line on stdout.  The kernels alone: `rocprofv3 --kernel-trace --stats -- python tools/ppo_update_timing.py --only native` (tools/README.md).
 
     python tools/ppo_update_timing.py [--configs 65536x32,4096x64] [--repeats 7] [--only torch|native] [--ext] [--separate-value] [--ret-filter]
-                                      [--adv-norm] [--perm]
+                                      [--adv-norm] [--perm] [--timeout-bootstrap]
 
 --ext adds, in the same run, the extended update (NativePPO with vf_clip 0.2, max_grad_norm 0.5, kl_coef 1.0, kl_target 0.01: GAE, the
 ssg_ppo_dist launch, ssg_ppo_update_ext) as the path "native_ext", and the ssg_ppo_dist launch alone as "dist".
@@ -24,6 +24,8 @@ adv_norm="minibatch" (two more launches ahead of every minibatch's gradient laun
 torch.randperm per epoch, stacked), "perm_native" (NativePPO.draw_perm alone: ssg_ppo_perm, one launch into a fresh tensor) and
 "native_permnative" (the whole GAE + update with update(perm=None), the library drawing), to set against "native"; and each draw's
 peak device memory above what was allocated before it (torch's allocator statistics; the result tensor included), in bytes.
+--timeout-bootstrap adds, in the same run and alternating with the others: "gae_plain" (ssg_ppo_gae alone) and "gae_boot"
+(ssg_ppo_gae_boot alone, on the same batch plus a "boot" buffer that holds a value at a tenth of the samples and marks them done).
 """
 import argparse
 import importlib.util
@@ -98,7 +100,7 @@ def _peak_bytes(fn):
 
 
 def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext=False, separate_value=False, ret_filter=False,
-            adv_norm=False, perm=False):
+            adv_norm=False, perm=False, timeout_bootstrap=False):
     from ship_sim_gym_amd.policy import NativePolicy
     from ship_sim_gym_amd.ppo import NativePPO
     torch.manual_seed(0)
@@ -205,6 +207,11 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
         paths += [("perm_torch", draw_torch), ("perm_native", draw_native), ("native_permnative", run_native_permnative)]
     if ext:
         paths += [("native_ext", run_native_ext), ("dist", run_dist)]
+    if timeout_bootstrap:  # the same rows, a tenth of them done with a value to bootstrap from (GAE's cost does not depend on how many)
+        hit = torch.rand((horizon, envs), generator=g_n, device=dev) < 0.1
+        b_boot = dict(b, done=(b["done"] | hit).to(torch.uint8).contiguous(), boot=torch.where(hit, torch.ones_like(b["val"]), torch.zeros_like(b["val"])))
+        b_plain = {k: v for k, v in b_boot.items() if k != "boot"}
+        paths += [("gae_plain", lambda: ppo.gae(dict(b_plain))), ("gae_boot", lambda: ppo.gae(dict(b_boot)))]
     if ret_filter:
         rfrozen.state.copy_(rflt.state)  # (whatever it holds: the frozen call's cost does not depend on it)
         paths += [("gae", lambda: ppo.gae(dict(b))), ("ret_gae", lambda: ppo.gae(dict(b), return_filter=rflt)),
@@ -240,10 +247,11 @@ def main():
     ap.add_argument("--adv-norm", action="store_true", help="also time the whole GAE + update with per-minibatch advantage normalisation")
     ap.add_argument("--perm", action="store_true", help="also time the permutation draws alone (torch's and the library's), the whole GAE + "
                                                         "update with the library drawing, and each draw's peak memory")
+    ap.add_argument("--timeout-bootstrap", action="store_true", help="also time ssg_ppo_gae_boot against ssg_ppo_gae, each alone")
     a = ap.parse_args()
     mod = _ppo()
     res = [measure(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.repeats, a.only, "cuda:0", ext=a.ext, separate_value=sep, ret_filter=a.ret_filter,
-                   adv_norm=a.adv_norm, perm=a.perm)
+                   adv_norm=a.adv_norm, perm=a.perm, timeout_bootstrap=a.timeout_bootstrap)
            for c in a.configs.split(",") for sep in ([False, True] if a.separate_value else [False])]
     print(json.dumps({"ppo_update_timing": res}))
 

@@ -132,6 +132,9 @@ def make_arg_parser():
                     help="normalise every member's advantages once per rollout, or inside every minibatch as Stable-Baselines' PPO2 does")
     ap.add_argument("--perm", choices=("torch", "native"), default="torch",
                     help="who shuffles every member's minibatches: torch (rand + argsort), or the library on the device, one launch")
+    ap.add_argument("--timeout-bootstrap", action="store_true",
+                    help="GAE bootstraps an episode the clock ended from the value of its terminal observation instead of scoring it as a "
+                         "return of 0; default: every done alike")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -195,7 +198,8 @@ def parse_args(argv=None):
 def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every=5, seed=0, epochs=2, minibatches=4, lrs=None,
           pbt=True, device="cuda:0", log=print, return_details=False, kl_coeff=0.0, kl_target=0.01, vf_clip=0.0, max_grad_norm=0.0,
           separate_value=False, mutate_schedule=False, max_epochs=30, eval_every=0, eval_episodes=1, envs=None, mutate_batch=False,
-          batch_shares=None, quantum=None, obs_filter=False, norm_reward=False, reward_clip=10.0, adv_norm="batch", perm="torch"):
+          batch_shares=None, quantum=None, obs_filter=False, norm_reward=False, reward_clip=10.0, adv_norm="batch", perm="torch",
+          timeout_bootstrap=False):
     import torch
     from ship_gym.config import EnvConfig, GameConfig
     from ship_sim_gym_amd.population import NativePopulation, PBTScheduler, PopulationPPO, reference_mutations, slices_for_batch_sizes
@@ -267,6 +271,8 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
         from ship_sim_gym_amd.ret_filter import ReturnFilter
         rflt = ReturnFilter(env, n_members=P, gamma=ppo.gamma, clip=reward_clip)
         ppo.set_return_filter(rflt)  # (an exploit copies the source's state rows with its weights)
+    if timeout_bootstrap:  # (the rollout then also returns "boot", which gae() reads: a time-out is no longer scored as a return of 0)
+        env.set_timeout_bootstrap(True, rows=horizon)
     env.reset_tensor()
     window = torch.zeros((P, 3), dtype=torch.int64, device=dev)  # episodes since the last perturbation
     scores = [float("-inf")] * P
@@ -387,7 +393,7 @@ def main(argv=None):
           kl_target=a.kl_target, vf_clip=a.vf_clip, max_grad_norm=a.max_grad_norm, separate_value=a.separate_value,
           mutate_schedule=a.mutate_schedule, max_epochs=a.max_epochs, eval_every=a.eval_every, eval_episodes=a.eval_episodes, envs=a.envs,
           mutate_batch=a.mutate_batch, batch_shares=a.batch_shares, quantum=a.quantum, obs_filter=a.obs_filter,
-          norm_reward=a.norm_reward, reward_clip=a.reward_clip, adv_norm=a.adv_norm, perm=a.perm)
+          norm_reward=a.norm_reward, reward_clip=a.reward_clip, adv_norm=a.adv_norm, perm=a.perm, timeout_bootstrap=a.timeout_bootstrap)
 
 
 if __name__ == "__main__":

@@ -216,7 +216,7 @@ def rollout(shards, horizon, mode, gen, policy=None):
 def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, gamma=0.99, lam=0.95, clip=0.2,
           device="cuda:0", seed=0, log=print, mode="eager", return_details=False, env_kw=None, update="torch", separate_value=False,
           eval_every=0, eval_episodes=1, eval_envs=None, obs_filter=False, save_obs_filter=None,
-          norm_reward=False, reward_clip=10.0, adv_norm="batch", perm="torch"):
+          norm_reward=False, reward_clip=10.0, adv_norm="batch", perm="torch", timeout_bootstrap=False):
     assert mode in ("eager", "graph", "pingpong", "native")
     if perm not in ("torch", "native"):
         raise ValueError("perm must be 'torch' or 'native' (got %r)" % (perm,))
@@ -232,6 +232,9 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
     if norm_reward and (mode != "native" or update != "native"):
         raise ValueError("norm_reward normalises the native rollout's reward buffer ahead of the device's GAE: it needs mode='native' and "
                          "update='native' (got mode=%r, update=%r)" % (mode, update))
+    if timeout_bootstrap and (mode != "native" or update != "native"):
+        raise ValueError("timeout_bootstrap takes the value of a time-out's terminal observation in the native rollout and hands it to the "
+                         "device's GAE: it needs mode='native' and update='native' (got mode=%r, update=%r)" % (mode, update))
     if eval_every and mode != "native":
         raise ValueError("eval_every evaluates the native policy on the device: it needs mode='native' (got mode=%r)" % (mode,))
     if eval_every < 0 or eval_episodes < 1:
@@ -260,6 +263,8 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         from ship_sim_gym_amd.obs_filter import ObsFilter
         flt = ObsFilter(shards[0].env)
         shards[0].env.set_obs_filter(flt)
+    if timeout_bootstrap:  # (the rollout then also returns "boot", which gae() reads: a time-out is no longer scored as a return of 0)
+        shards[0].env.set_timeout_bootstrap(True, rows=horizon)
     rflt = None
     if norm_reward:  # (applied to each rollout's reward buffer between the rollout and GAE; nothing is bound to the env)
         from ship_sim_gym_amd.ret_filter import ReturnFilter
@@ -410,6 +415,9 @@ def make_arg_parser():
                     help="normalise the advantages once per rollout, or inside every minibatch as Stable-Baselines' PPO2 does (either --update)")
     ap.add_argument("--perm", choices=("torch", "native"), default="torch",
                     help="who shuffles the update's minibatches: torch.randperm, or the library on the device (needs --update native)")
+    ap.add_argument("--timeout-bootstrap", action="store_true",
+                    help="GAE bootstraps an episode the clock ended from the value of its terminal observation instead of scoring it as a "
+                         "return of 0 (needs --mode native --update native); default: every done alike")
     return ap
 
 
@@ -431,6 +439,8 @@ def parse_args(argv=None):
         ap.error("--save-obs-filter needs --obs-filter")
     if a.norm_reward and (a.mode != "native" or a.update != "native"):
         ap.error("--norm-reward needs --mode native --update native (it runs between the native rollout and the device's GAE)")
+    if a.timeout_bootstrap and (a.mode != "native" or a.update != "native"):
+        ap.error("--timeout-bootstrap needs --mode native --update native (the torch-mode update has no time-out bootstrap)")
     if a.reward_clip != 10.0 and not a.norm_reward:
         ap.error("--reward-clip needs --norm-reward")
     if not a.reward_clip >= 0.0:
@@ -442,4 +452,5 @@ if __name__ == "__main__":
     a = parse_args()
     train(envs=a.envs, updates=a.updates, horizon=a.horizon, mode=a.mode, update=a.update, separate_value=a.separate_value,
           eval_every=a.eval_every, eval_episodes=a.eval_episodes, obs_filter=a.obs_filter, save_obs_filter=a.save_obs_filter,
-          norm_reward=a.norm_reward, reward_clip=a.reward_clip, adv_norm=a.adv_norm, perm=a.perm)
+          norm_reward=a.norm_reward, reward_clip=a.reward_clip, adv_norm=a.adv_norm, perm=a.perm,
+          timeout_bootstrap=a.timeout_bootstrap)
