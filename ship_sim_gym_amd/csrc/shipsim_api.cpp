@@ -1177,20 +1177,6 @@ static int check_batch(ssg_handle *h, int64_t n_samples, const ssg::PpoBatch &b,
     return SSG_OK;
 }
 
-// The minibatch record of ONE policy's entry points, but for what changes per call or per minibatch (idx, M, step, the outputs, ext).
-static ssg::PpoMinibatch one_policy(const ssg_policy *pol, const ssg_ppo_hparams *hp, int64_t n_samples, const ssg::PpoBatch &batch, void *ws)
-{
-    ssg::PpoMinibatch mb = {};
-    mb.policy = pol;
-    mb.members = 1;
-    mb.n_samples = n_samples;
-    mb.batch = batch;
-    mb.ws = ws;
-    mb.slots_off = ssg::kPpoSlotsOff;
-    mb.hp = hp;
-    return mb;
-}
-
 // Per-minibatch advantage normalisation (ssg_ppo_set_adv_norm): while it is bound, every minibatch of the gradient / update entry points
 // takes its statistics from the handle's scratch (its stats rows, then its partials) instead of the workspace's batch statistics.
 static void adv_norm_bind(const ssg_handle *h, ssg::PpoMinibatch &mb)
@@ -1221,85 +1207,6 @@ static Chunking chunking(long long n, int minibatches)
     return {C, (n + C - 1) / C};
 }
 
-// A population on per-member schedules (ssg_pop_update_sched): what run_update takes from the schedule instead of from epochs x chunks.
-struct PopSchedule {
-    const int32_t *dev_sched; // the device table: header rows, then the records of launch 0, 1, ...
-    long long n_launches;     // max steps_m
-    long long Cmax;           // max C_m: every launch is as wide as the longest minibatch of the call needs
-    int perm_epochs;          // permutation rows per member
-};
-
-// The loop of the five update entry points.  mb: the record as its entry point filled it, with idx = the [epochs][n] permutation rows
-// (a population: [members][epochs][n]), stats_out = the caller's stats rows or NULL, step = the Adam steps taken so far, table = a
-// population's table; ext: nullable.  Minibatch j of the call reads chunk j % chunks of permutation row j / chunks, takes Adam step
-// step + 1 + j (a population: the table's Adam rows 1 + j) and writes stats row j.  With sched (epochs / minibatches unused) launch j
-// serves minibatch j of every member that has one: M, the chunk's place and first_chunk are per member, in the table's records of
-// launch j; the launch itself is sized for Cmax.  kl_adapt: end with the adaptation of the coefficient(s) from the last epoch's
-// chunks.  what: the entry point's name in a launch failure's message.
-static int run_update(ssg_handle *h, ssg::PpoMinibatch mb, ssg::PpoExtLaunch *ext, int epochs, int minibatches, bool kl_adapt, float kl_target,
-                      const char *what, hipStream_t st, const PopSchedule *sched = nullptr)
-{
-    const long long n = mb.n_samples;
-    const Chunking ck = sched ? Chunking{sched->Cmax, 0} : chunking(n, minibatches);
-    const long long launches = sched ? sched->n_launches : (long long)epochs * ck.chunks;
-    const int cols = ext ? ssg::kExtStats : 4;
-    const int64_t *perm = mb.idx;
-    float *stats = mb.stats_out;
-    mb.ext = ext;
-    mb.idx_stride = (long long)(sched ? sched->perm_epochs : epochs) * n;
-    mb.stats_stride = cols * launches;
-    for (long long j = 0; j < launches; ++j) {
-        if (sched) {
-            mb.M = sched->Cmax;
-            mb.sched = sched->dev_sched + (size_t)(1 + j) * (size_t)mb.members * ssg::kPopSchedRow;
-        } else {
-            const long long ep = j / ck.chunks, b0 = (j - ep * ck.chunks) * ck.C;
-            mb.M = std::min(ck.C, n - b0);
-            mb.idx = perm + (size_t)ep * (size_t)n + (size_t)b0;
-            if (ext) ext->first_chunk = b0 == 0;
-        }
-        mb.stats_out = stats ? stats + cols * j : nullptr;
-        ++mb.step;
-        if (mb.table) mb.adam_row = mb.table + (size_t)(1 + j) * (size_t)mb.members * ssg::kPopTableRow;
-        hipError_t e = ssg::launch_ppo_minibatch(mb, st);
-        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
-    }
-    if (kl_adapt) {
-        hipError_t e = ssg::launch_kl_adapt(mb.members, *ext, kl_target, ssg::ppo_packed_len(*mb.policy), ck.chunks,
-                                            sched ? sched->dev_sched : nullptr, mb.ws, mb.slots_off, st);
-        if (e != hipSuccess)
-            return fail(h, SSG_ERR_HIP, std::string(mb.table ? "population kl adapt launch: " : "kl adapt launch: ") + hipGetErrorString(e));
-    }
-    return SSG_OK;
-}
-
-int ssg_ppo_grad(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, int64_t n_samples, const float *dev_x,
-                 const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret, const int64_t *dev_idx,
-                 int64_t M, float *dev_grad, float *dev_stats, void *dev_workspace, size_t workspace_nbytes, void *stream)
-{
-    const ssg::PpoBatch batch = {dev_x, dev_act, dev_logp, dev_adv, dev_ret};
-    int rc = check_ready(h, false);
-    if (rc != SSG_OK) return rc;
-    rc = check_policy(h, pol, "ssg_ppo_grad");
-    if (rc == SSG_OK) rc = check_hparams(h, hp, "ssg_ppo_grad");
-    if (rc == SSG_OK) rc = check_batch(h, n_samples, batch, dev_idx, "ssg_ppo_grad");
-    if (rc != SSG_OK) return rc;
-    if (!dev_grad) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_grad: NULL dev_grad");
-    if (M < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_grad: M < 1");
-    rc = check_workspace(h, dev_workspace, workspace_nbytes, need_grad(ssg::kPpoSlotsOff, 1, *pol, M, false), "ssg_ppo_grad");
-    if (rc == SSG_OK) rc = prepare_ppo(h);
-    if (rc != SSG_OK) return rc;
-    ssg::PpoMinibatch mb = one_policy(pol, hp, n_samples, batch, dev_workspace);
-    adv_norm_bind(h, mb);
-    mb.idx = dev_idx;
-    mb.M = M;
-    mb.grad_out = dev_grad;
-    mb.stats_out = dev_stats;
-    hipError_t e = ssg::launch_ppo_minibatch(mb, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("ppo grad launch: ") + hipGetErrorString(e));
-    return SSG_OK;
-}
-
 int ssg_ppo_adam(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, const float *dev_grad, float *dev_adam_mv,
                  int64_t step, void *stream)
 {
@@ -1313,33 +1220,6 @@ int ssg_ppo_adam(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp
     hipError_t e = ssg::launch_ppo_adam(*pol, *hp, dev_grad, dev_adam_mv, step, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("adam launch: ") + hipGetErrorString(e));
     return SSG_OK;
-}
-
-int ssg_ppo_update(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, int64_t n_samples, const float *dev_x,
-                   const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret, const int64_t *dev_perm,
-                   int epochs, int minibatches, float *dev_adam_mv, int64_t step0, float *dev_stats, void *dev_workspace,
-                   size_t workspace_nbytes, void *stream)
-{
-    const ssg::PpoBatch batch = {dev_x, dev_act, dev_logp, dev_adv, dev_ret};
-    int rc = check_ready(h, false);
-    if (rc != SSG_OK) return rc;
-    rc = check_policy(h, pol, "ssg_ppo_update");
-    if (rc == SSG_OK) rc = check_hparams(h, hp, "ssg_ppo_update");
-    if (rc == SSG_OK) rc = check_batch(h, n_samples, batch, dev_perm, "ssg_ppo_update");
-    if (rc != SSG_OK) return rc;
-    if (!dev_adam_mv) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_update: NULL dev_adam_mv");
-    if (epochs < 1 || minibatches < 1 || step0 < 0) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_update: epochs < 1, minibatches < 1 or step0 < 0");
-    const size_t need = need_grad(ssg::kPpoSlotsOff, 1, *pol, chunking(n_samples, minibatches).C, false);
-    rc = check_workspace(h, dev_workspace, workspace_nbytes, need, "ssg_ppo_update");
-    if (rc == SSG_OK) rc = prepare_ppo(h);
-    if (rc != SSG_OK) return rc;
-    ssg::PpoMinibatch mb = one_policy(pol, hp, n_samples, batch, dev_workspace);
-    adv_norm_bind(h, mb);
-    mb.idx = dev_perm;
-    mb.stats_out = dev_stats;
-    mb.adam_mv = dev_adam_mv;
-    mb.step = step0;
-    return run_update(h, mb, nullptr, epochs, minibatches, false, 0.0f, "ppo update", static_cast<hipStream_t>(stream));
 }
 
 // ABI 9 additions: a population of policies on one handle.  Order of the refusals: no handle (BAD_ARG), no state blob (NOT_BOUND), then
@@ -1408,48 +1288,6 @@ static int check_population(ssg_handle *h, const ssg_population *pop, const char
 static const int32_t *pop_slices(const ssg_handle *h) { return h->pop_sizes.empty() ? nullptr : h->dev_slices; }
 static int pop_width(const ssg_handle *h, int P) { return h->pop_sizes.empty() ? h->cfg.n_envs / P : h->slice_max; }
 
-// ABI 9 additions: the extended update.  Order of the refusals as for a population: no handle (BAD_ARG), no state blob (NOT_BOUND),
-// everything the host can judge (BAD_ARG), and only then the device.
-static int check_ext(ssg_handle *h, const ssg_ppo_ext *ext, const char *what)
-{
-    const std::string w(what);
-    if (!ext) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL ssg_ppo_ext");
-    if (ext->struct_size != sizeof(ssg_ppo_ext)) return fail(h, SSG_ERR_BAD_ARG, w + ": ssg_ppo_ext.struct_size != sizeof(ssg_ppo_ext)");
-    if (!std::isfinite(ext->vf_clip) || !std::isfinite(ext->max_grad_norm) || !std::isfinite(ext->kl_target))
-        return fail(h, SSG_ERR_BAD_ARG, w + ": vf_clip, max_grad_norm or kl_target is not finite");
-    if (ext->dev_kl_coef && !ext->dev_logp_all) return fail(h, SSG_ERR_BAD_ARG, w + ": dev_kl_coef without dev_logp_all (ssg_ppo_dist)");
-    if (ext->vf_clip > 0.0 && !ext->dev_value_old) return fail(h, SSG_ERR_BAD_ARG, w + ": vf_clip > 0 without dev_value_old");
-    return SSG_OK;
-}
-
-static ssg::PpoExtLaunch ext_launch(const ssg_ppo_ext &ext)
-{
-    ssg::PpoExtLaunch e;
-    e.kl_coef = ext.dev_kl_coef;
-    e.logp_all = ext.dev_kl_coef ? ext.dev_logp_all : nullptr;
-    e.vf_clip = ext.vf_clip > 0.0 ? (float)ext.vf_clip : 0.0f;
-    e.value_old = ext.vf_clip > 0.0 ? ext.dev_value_old : nullptr;
-    e.max_grad_norm = ext.max_grad_norm > 0.0 ? (float)ext.max_grad_norm : 0.0f;
-    e.clip_seq = ext.max_grad_norm > 0.0;
-    e.pop_ext = nullptr;
-    e.first_chunk = true;
-    return e;
-}
-
-// a population's: the members' constants are rows of dev_ext, the flags say which terms some member has on
-static ssg::PpoExtLaunch ext_launch(const ssg_pop_ext &ext)
-{
-    ssg::PpoExtLaunch e;
-    e.kl_coef = ext.dev_kl_coef;
-    e.logp_all = ext.dev_kl_coef ? ext.dev_logp_all : nullptr;
-    e.value_old = (ext.flags & SSG_POP_EXT_VF_CLIP) ? ext.dev_value_old : nullptr;
-    e.pop_ext = ext.dev_ext;
-    e.vf_clip = e.max_grad_norm = 0.0f; // (per member: dev_ext)
-    e.clip_seq = (ext.flags & SSG_POP_EXT_GRAD_CLIP) != 0;
-    e.first_chunk = true;
-    return e;
-}
-
 int ssg_ppo_dist(ssg_handle *h, const ssg_policy *pol, int64_t n_samples, const float *dev_x, float *dev_logp_all, void *stream)
 {
     int rc = pop_bound(h);
@@ -1463,67 +1301,6 @@ int ssg_ppo_dist(ssg_handle *h, const ssg_policy *pol, int64_t n_samples, const 
     hipError_t e = ssg::launch_policy_dist(*pol, 1, (int)n_samples, n_samples, 1, dev_x, dev_logp_all, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("policy dist launch: ") + hipGetErrorString(e));
     return SSG_OK;
-}
-
-int ssg_ppo_grad_ext(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, const ssg_ppo_ext *ext, int64_t n_samples,
-                     const float *dev_x, const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret,
-                     const int64_t *dev_idx, int64_t M, float *dev_grad, float *dev_stats, void *dev_workspace, size_t workspace_nbytes,
-                     void *stream)
-{
-    const ssg::PpoBatch batch = {dev_x, dev_act, dev_logp, dev_adv, dev_ret};
-    int rc = pop_bound(h);
-    if (rc == SSG_OK) rc = check_policy(h, pol, "ssg_ppo_grad_ext");
-    if (rc == SSG_OK) rc = check_hparams(h, hp, "ssg_ppo_grad_ext");
-    if (rc == SSG_OK) rc = check_ext(h, ext, "ssg_ppo_grad_ext");
-    if (rc == SSG_OK) rc = check_batch(h, n_samples, batch, dev_idx, "ssg_ppo_grad_ext");
-    if (rc != SSG_OK) return rc;
-    if (!dev_grad) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_grad_ext: NULL dev_grad");
-    if (M < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_grad_ext: M < 1");
-    rc = check_workspace(h, dev_workspace, workspace_nbytes, need_grad(ssg::kPpoSlotsOff, 1, *pol, M, true), "ssg_ppo_grad_ext");
-    if (rc == SSG_OK) rc = check_ready(h, false);
-    if (rc == SSG_OK) rc = prepare_ppo(h);
-    if (rc != SSG_OK) return rc;
-    const ssg::PpoExtLaunch el = ext_launch(*ext);
-    ssg::PpoMinibatch mb = one_policy(pol, hp, n_samples, batch, dev_workspace);
-    adv_norm_bind(h, mb);
-    mb.idx = dev_idx;
-    mb.M = M;
-    mb.ext = &el;
-    mb.grad_out = dev_grad;
-    mb.stats_out = dev_stats;
-    hipError_t e = ssg::launch_ppo_minibatch(mb, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("ppo grad_ext launch: ") + hipGetErrorString(e));
-    return SSG_OK;
-}
-
-int ssg_ppo_update_ext(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, const ssg_ppo_ext *ext, int64_t n_samples,
-                       const float *dev_x, const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret,
-                       const int64_t *dev_perm, int epochs, int minibatches, float *dev_adam_mv, int64_t step0, float *dev_stats,
-                       void *dev_workspace, size_t workspace_nbytes, void *stream)
-{
-    const ssg::PpoBatch batch = {dev_x, dev_act, dev_logp, dev_adv, dev_ret};
-    int rc = pop_bound(h);
-    if (rc == SSG_OK) rc = check_policy(h, pol, "ssg_ppo_update_ext");
-    if (rc == SSG_OK) rc = check_hparams(h, hp, "ssg_ppo_update_ext");
-    if (rc == SSG_OK) rc = check_ext(h, ext, "ssg_ppo_update_ext");
-    if (rc == SSG_OK) rc = check_batch(h, n_samples, batch, dev_perm, "ssg_ppo_update_ext");
-    if (rc != SSG_OK) return rc;
-    if (!dev_adam_mv) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_update_ext: NULL dev_adam_mv");
-    if (epochs < 1 || minibatches < 1 || step0 < 0) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_update_ext: epochs < 1, minibatches < 1 or step0 < 0");
-    const size_t need = need_grad(ssg::kPpoSlotsOff, 1, *pol, chunking(n_samples, minibatches).C, true);
-    rc = check_workspace(h, dev_workspace, workspace_nbytes, need, "ssg_ppo_update_ext");
-    if (rc == SSG_OK) rc = check_ready(h, false);
-    if (rc == SSG_OK) rc = prepare_ppo(h);
-    if (rc != SSG_OK) return rc;
-    ssg::PpoExtLaunch el = ext_launch(*ext);
-    ssg::PpoMinibatch mb = one_policy(pol, hp, n_samples, batch, dev_workspace);
-    adv_norm_bind(h, mb);
-    mb.idx = dev_perm;
-    mb.stats_out = dev_stats;
-    mb.adam_mv = dev_adam_mv;
-    mb.step = step0;
-    return run_update(h, mb, &el, epochs, minibatches, ext->kl_target > 0.0 && ext->dev_kl_coef, (float)ext->kl_target, "ppo update_ext",
-                      static_cast<hipStream_t>(stream));
 }
 
 // Who acts in a policy call: one policy on all the handle's envs, or a population on its slices.  The two functions that fill the record
@@ -1784,20 +1561,6 @@ int ssg_pop_rollout(ssg_handle *h, const ssg_population *pop, int K, const float
                           dev_done_KN, dev_flags_KN, dev_last_value, step_stride_envs, stream);
 }
 
-int ssg_pop_pack_hparams(int n_members, const ssg_ppo_hparams *hparams, int64_t step0, int n_steps, float *out, size_t out_floats)
-{
-    if (!hparams || !out || n_members < 1 || n_members > SSG_POP_MAX_MEMBERS || n_steps < 0 || step0 < 0)
-        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_hparams: NULL pointer, n_members out of range, n_steps < 0 or step0 < 0");
-    if (out_floats < SSG_POP_TABLE_FLOATS(n_members, n_steps))
-        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_hparams: out_floats < SSG_POP_TABLE_FLOATS(n_members, n_steps)");
-    for (int m = 0; m < n_members; ++m) {
-        const int rc = check_hparams(nullptr, hparams + m, "ssg_pop_pack_hparams");
-        if (rc != SSG_OK) return rc;
-    }
-    ssg::pop_pack(n_members, hparams, step0, n_steps, out);
-    return SSG_OK;
-}
-
 static size_t pop_need_gae(int P, long long n) { return ssg::kPopSlotsOff + (size_t)P * (size_t)ssg::ppo_gae_blocks(n) * 16; }
 int ssg_pop_workspace_nbytes(const ssg_population *pop, int64_t samples_per_member, int64_t max_minibatch, size_t *nbytes)
 {
@@ -1850,67 +1613,6 @@ int ssg_pop_gae_boot(ssg_handle *h, const ssg_population *pop, const float *dev_
                    dev_workspace, workspace_nbytes, stream, "ssg_pop_gae_boot");
 }
 
-// What the population's update entry points refuse alike once the population record (and the ext record) passed, in their order;
-// then the minibatch record of the population's update, but for what run_update sets per minibatch.  sched: ssg_pop_update_sched's
-// per-member epochs / minibatches (checked by its caller, as the table's steps are) in place of the common ones.
-static int check_pop_update(ssg_handle *h, const ssg_policy *pol, int P, const float *dev_table, int table_steps, int K,
-                            const ssg::PpoBatch &batch, const int64_t *dev_perm, int epochs, int minibatches, float *dev_adam_mv,
-                            const char *what, ssg::PpoMinibatch *mb, bool sched = false)
-{
-    const std::string w(what);
-    if (K < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": K < 1");
-    const int N = h->cfg.n_envs;
-    if (pop_slices(h) && !sched)
-        return fail(h, SSG_ERR_BAD_ARG, w + ": slices are bound to the handle (ssg_pop_set_slices): the update runs through ssg_pop_update_sched");
-    const long long n = (long long)K * (N / P); // samples per member (unequal slices: unused, see ssg_pop_update_sched)
-    int rc = check_batch(h, n, batch, dev_perm, what);
-    if (rc == SSG_OK) rc = check_adv_norm_members(h, P, what);
-    if (rc != SSG_OK) return rc;
-    if (!dev_table || !dev_adam_mv) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_table or dev_adam_mv");
-    if (!sched) {
-        if (epochs < 1 || minibatches < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": epochs < 1 or minibatches < 1");
-        if ((long long)table_steps < (long long)epochs * chunking(n, minibatches).chunks)
-            return fail(h, SSG_ERR_BAD_ARG, w + ": the table holds fewer Adam steps than epochs * chunks");
-    }
-    *mb = {};
-    mb->policy = pol;
-    mb->members = P;
-    mb->n = N / P;
-    mb->N = N;
-    mb->n_samples = n;
-    mb->batch = batch;
-    mb->idx = dev_perm;
-    mb->slots_off = ssg::kPopSlotsOff;
-    mb->table = dev_table;
-    mb->adam_mv = dev_adam_mv;
-    adv_norm_bind(h, *mb);
-    return SSG_OK;
-}
-
-int ssg_pop_update(ssg_handle *h, const ssg_population *pop, const float *dev_table, int table_steps, int K, const float *dev_x,
-                   const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret, const int64_t *dev_perm,
-                   int epochs, int minibatches, float *dev_adam_mv, float *dev_stats, void *dev_workspace, size_t workspace_nbytes,
-                   void *stream)
-{
-    const ssg::PpoBatch batch = {dev_x, dev_act, dev_logp, dev_adv, dev_ret};
-    int rc = pop_bound(h);
-    if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_update");
-    if (rc != SSG_OK) return rc;
-    const ssg_policy pol = pop_policy(*pop);
-    const int P = pop->n_members;
-    ssg::PpoMinibatch mb;
-    rc = check_pop_update(h, &pol, P, dev_table, table_steps, K, batch, dev_perm, epochs, minibatches, dev_adam_mv, "ssg_pop_update", &mb);
-    if (rc != SSG_OK) return rc;
-    const size_t need = need_grad(ssg::kPopSlotsOff, P, pol, chunking(mb.n_samples, minibatches).C, false);
-    rc = check_workspace(h, dev_workspace, workspace_nbytes, need, "ssg_pop_update");
-    if (rc == SSG_OK) rc = check_ready(h, false);
-    if (rc == SSG_OK) rc = prepare_ppo(h);
-    if (rc != SSG_OK) return rc;
-    mb.ws = dev_workspace;
-    mb.stats_out = dev_stats;
-    return run_update(h, mb, nullptr, epochs, minibatches, false, 0.0f, "population update", static_cast<hipStream_t>(stream));
-}
-
 int ssg_pop_dist(ssg_handle *h, const ssg_population *pop, int K, const float *dev_x, float *dev_logp_all, void *stream)
 {
     int rc = pop_bound(h);
@@ -1926,47 +1628,6 @@ int ssg_pop_dist(ssg_handle *h, const ssg_population *pop, int K, const float *d
                                            pop_slices(h));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population dist launch: ") + hipGetErrorString(e));
     return SSG_OK;
-}
-
-// the ssg_pop_ext record, for ssg_pop_update_ext and ssg_pop_update_sched
-static int check_pop_ext(ssg_handle *h, const ssg_pop_ext *ext, const char *what)
-{
-    const std::string w(what);
-    if (!ext) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL ssg_pop_ext");
-    if (ext->struct_size != sizeof(ssg_pop_ext)) return fail(h, SSG_ERR_BAD_ARG, w + ": ssg_pop_ext.struct_size != sizeof(ssg_pop_ext)");
-    if (ext->flags & ~(SSG_POP_EXT_GRAD_CLIP | SSG_POP_EXT_VF_CLIP)) return fail(h, SSG_ERR_BAD_ARG, w + ": unknown ssg_pop_ext.flags bits");
-    if (!ext->dev_ext) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_ext");
-    if (ext->dev_kl_coef && !ext->dev_logp_all) return fail(h, SSG_ERR_BAD_ARG, w + ": dev_kl_coef without dev_logp_all (ssg_pop_dist)");
-    if ((ext->flags & SSG_POP_EXT_VF_CLIP) && !ext->dev_value_old) return fail(h, SSG_ERR_BAD_ARG, w + ": SSG_POP_EXT_VF_CLIP without dev_value_old");
-    return SSG_OK;
-}
-
-int ssg_pop_update_ext(ssg_handle *h, const ssg_population *pop, const ssg_pop_ext *ext, const float *dev_table, int table_steps, int K,
-                       const float *dev_x, const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret,
-                       const int64_t *dev_perm, int epochs, int minibatches, float *dev_adam_mv, float *dev_stats, void *dev_workspace,
-                       size_t workspace_nbytes, void *stream)
-{
-    const ssg::PpoBatch batch = {dev_x, dev_act, dev_logp, dev_adv, dev_ret};
-    int rc = pop_bound(h);
-    if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_update_ext");
-    if (rc != SSG_OK) return rc;
-    rc = check_pop_ext(h, ext, "ssg_pop_update_ext");
-    if (rc != SSG_OK) return rc;
-    const ssg_policy pol = pop_policy(*pop);
-    const int P = pop->n_members;
-    ssg::PpoMinibatch mb;
-    rc = check_pop_update(h, &pol, P, dev_table, table_steps, K, batch, dev_perm, epochs, minibatches, dev_adam_mv, "ssg_pop_update_ext", &mb);
-    if (rc != SSG_OK) return rc;
-    const size_t need = need_grad(ssg::kPopSlotsOff, P, pol, chunking(mb.n_samples, minibatches).C, true);
-    rc = check_workspace(h, dev_workspace, workspace_nbytes, need, "ssg_pop_update_ext");
-    if (rc == SSG_OK) rc = check_ready(h, false);
-    if (rc == SSG_OK) rc = prepare_ppo(h);
-    if (rc != SSG_OK) return rc;
-    ssg::PpoExtLaunch el = ext_launch(*ext);
-    mb.ws = dev_workspace;
-    mb.stats_out = dev_stats;
-    return run_update(h, mb, &el, epochs, minibatches, ext->dev_kl_coef != nullptr, 0.0f, "population update_ext",
-                      static_cast<hipStream_t>(stream));
 }
 
 // The schedule of `members` members over n samples each: steps / launches / the longest chunk, and (out != NULL) the table.  false: an
@@ -2019,38 +1680,41 @@ static bool pop_schedule(int members, long long n_all, const int32_t *epochs, co
     return true;
 }
 
-int ssg_pop_pack_schedule(int n_members, int64_t samples_per_member, const int32_t *epochs, const int32_t *minibatches, int32_t *out,
-                          size_t out_ints, int32_t *steps_out, int32_t *n_launches_out)
+// The body of ssg_pop_pack_schedule and ssg_pop_pack_schedule_samples (per_member: `samples` lists a count per member in place of n_all).
+static int pack_schedule(int n_members, int64_t n_all, const int64_t *samples, bool per_member, const int32_t *epochs, const int32_t *minibatches,
+                         int32_t *out, size_t out_ints, int32_t *steps_out, int32_t *n_launches_out, const char *what)
 {
-    if (!epochs || !minibatches || !n_launches_out || n_members < 1 || n_members > SSG_POP_MAX_MEMBERS || samples_per_member < 1)
-        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_schedule: NULL epochs, minibatches or n_launches_out, n_members out of range or samples_per_member < 1");
+    const std::string w(what);
+    const bool bad = !epochs || !minibatches || !n_launches_out || n_members < 1 || n_members > SSG_POP_MAX_MEMBERS;
+    if (per_member) {
+        if (bad || !samples) return fail(nullptr, SSG_ERR_BAD_ARG, w + ": NULL samples, epochs, minibatches or n_launches_out, or n_members out of range");
+        for (int m = 0; m < n_members; ++m)
+            if (samples[m] < 1) return fail(nullptr, SSG_ERR_BAD_ARG, w + ": a member's sample count is < 1");
+    } else if (bad || n_all < 1)
+        return fail(nullptr, SSG_ERR_BAD_ARG, w + ": NULL epochs, minibatches or n_launches_out, n_members out of range or samples_per_member < 1");
     long long launches = 0, cmax = 0;
-    if (!pop_schedule(n_members, samples_per_member, epochs, minibatches, nullptr, steps_out, &launches, &cmax))
-        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_schedule: a member's epochs or minibatches is < 1 (or its steps exceed 2^31-1)");
+    if (!pop_schedule(n_members, n_all, epochs, minibatches, nullptr, steps_out, &launches, &cmax, samples))
+        return fail(nullptr, SSG_ERR_BAD_ARG, w + ": a member's epochs or minibatches is < 1 (or its steps exceed 2^31-1)");
     *n_launches_out = (int32_t)launches;
     if (!out) return SSG_OK; // the size query
     if (out_ints < SSG_POP_SCHED_INTS(n_members, launches))
-        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_schedule: out_ints < SSG_POP_SCHED_INTS(n_members, n_launches)");
-    pop_schedule(n_members, samples_per_member, epochs, minibatches, out, steps_out, &launches, &cmax);
+        return fail(nullptr, SSG_ERR_BAD_ARG, w + ": out_ints < SSG_POP_SCHED_INTS(n_members, n_launches)");
+    pop_schedule(n_members, n_all, epochs, minibatches, out, steps_out, &launches, &cmax, samples);
     return SSG_OK;
+}
+
+int ssg_pop_pack_schedule(int n_members, int64_t samples_per_member, const int32_t *epochs, const int32_t *minibatches, int32_t *out,
+                          size_t out_ints, int32_t *steps_out, int32_t *n_launches_out)
+{
+    return pack_schedule(n_members, samples_per_member, nullptr, false, epochs, minibatches, out, out_ints, steps_out, n_launches_out,
+                         "ssg_pop_pack_schedule");
 }
 
 int ssg_pop_pack_schedule_samples(int n_members, const int64_t *samples, const int32_t *epochs, const int32_t *minibatches, int32_t *out,
                                   size_t out_ints, int32_t *steps_out, int32_t *n_launches_out)
 {
-    if (!samples || !epochs || !minibatches || !n_launches_out || n_members < 1 || n_members > SSG_POP_MAX_MEMBERS)
-        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_schedule_samples: NULL samples, epochs, minibatches or n_launches_out, or n_members out of range");
-    for (int m = 0; m < n_members; ++m)
-        if (samples[m] < 1) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_schedule_samples: a member's sample count is < 1");
-    long long launches = 0, cmax = 0;
-    if (!pop_schedule(n_members, 0, epochs, minibatches, nullptr, steps_out, &launches, &cmax, samples))
-        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_schedule_samples: a member's epochs or minibatches is < 1 (or its steps exceed 2^31-1)");
-    *n_launches_out = (int32_t)launches;
-    if (!out) return SSG_OK; // the size query
-    if (out_ints < SSG_POP_SCHED_INTS(n_members, launches))
-        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_schedule_samples: out_ints < SSG_POP_SCHED_INTS(n_members, n_launches)");
-    pop_schedule(n_members, 0, epochs, minibatches, out, steps_out, &launches, &cmax, samples);
-    return SSG_OK;
+    return pack_schedule(n_members, 0, samples, true, epochs, minibatches, out, out_ints, steps_out, n_launches_out,
+                         "ssg_pop_pack_schedule_samples");
 }
 
 // the slices table of `P` sizes (out nullable: the checks alone); false: an entry < 1 or a sum beyond 2^31-1
@@ -2120,20 +1784,391 @@ int ssg_pop_get_slices(const ssg_handle *h, int *n_members, int32_t *out)
     return SSG_OK;
 }
 
-int ssg_pop_pack_hparams_steps(int n_members, const ssg_ppo_hparams *hparams, const int64_t *step0, int n_steps, float *out, size_t out_floats)
+// The body of ssg_pop_pack_hparams and ssg_pop_pack_hparams_steps (per_member: `steps` lists a starting step per member in place of step0).
+static int pack_hparams(int n_members, const ssg_ppo_hparams *hparams, int64_t step0, const int64_t *steps, bool per_member, int n_steps,
+                        float *out, size_t out_floats, const char *what)
 {
-    if (!hparams || !out || !step0 || n_members < 1 || n_members > SSG_POP_MAX_MEMBERS || n_steps < 0)
-        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_hparams_steps: NULL pointer, n_members out of range or n_steps < 0");
-    for (int m = 0; m < n_members; ++m)
-        if (step0[m] < 0) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_hparams_steps: a member's step0 is < 0");
+    const std::string w(what);
+    const bool bad = !hparams || !out || n_members < 1 || n_members > SSG_POP_MAX_MEMBERS || n_steps < 0;
+    if (per_member) {
+        if (bad || !steps) return fail(nullptr, SSG_ERR_BAD_ARG, w + ": NULL pointer, n_members out of range or n_steps < 0");
+        for (int m = 0; m < n_members; ++m)
+            if (steps[m] < 0) return fail(nullptr, SSG_ERR_BAD_ARG, w + ": a member's step0 is < 0");
+    } else if (bad || step0 < 0)
+        return fail(nullptr, SSG_ERR_BAD_ARG, w + ": NULL pointer, n_members out of range, n_steps < 0 or step0 < 0");
     if (out_floats < SSG_POP_TABLE_FLOATS(n_members, n_steps))
-        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_pop_pack_hparams_steps: out_floats < SSG_POP_TABLE_FLOATS(n_members, n_steps)");
+        return fail(nullptr, SSG_ERR_BAD_ARG, w + ": out_floats < SSG_POP_TABLE_FLOATS(n_members, n_steps)");
     for (int m = 0; m < n_members; ++m) {
-        const int rc = check_hparams(nullptr, hparams + m, "ssg_pop_pack_hparams_steps");
+        const int rc = check_hparams(nullptr, hparams + m, what);
         if (rc != SSG_OK) return rc;
     }
-    ssg::pop_pack_steps(n_members, hparams, step0, n_steps, out);
+    if (per_member) ssg::pop_pack_steps(n_members, hparams, steps, n_steps, out);
+    else ssg::pop_pack(n_members, hparams, step0, n_steps, out);
     return SSG_OK;
+}
+
+int ssg_pop_pack_hparams(int n_members, const ssg_ppo_hparams *hparams, int64_t step0, int n_steps, float *out, size_t out_floats)
+{
+    return pack_hparams(n_members, hparams, step0, nullptr, false, n_steps, out, out_floats, "ssg_pop_pack_hparams");
+}
+
+int ssg_pop_pack_hparams_steps(int n_members, const ssg_ppo_hparams *hparams, const int64_t *step0, int n_steps, float *out, size_t out_floats)
+{
+    return pack_hparams(n_members, hparams, 0, step0, true, n_steps, out, out_floats, "ssg_pop_pack_hparams_steps");
+}
+
+// ABI 9 additions: the gradient and the update of one policy and of a population — ssg_ppo_grad / _grad_ext / _update / _update_ext,
+// ssg_pop_update / _update_ext / _update_sched.  The entry point writes its own arguments into an UpdateCall; one of two fillers refuses
+// what the host can judge and completes the record — they are the only places that know one policy from a population — and update_call
+// is the tail all seven share: the workspace, the device, the kernels' attributes, then the one launch or the loop.  As everywhere,
+// nothing is enqueued before every refusal has passed.
+
+// A population on per-member schedules (ssg_pop_update_sched): what run_update takes from the schedule instead of from epochs x chunks.
+struct PopSchedule {
+    const int32_t *dev_sched; // the device table: header rows, then the records of launch 0, 1, ...
+    long long n_launches;     // max steps_m
+    long long Cmax;           // max C_m: every launch is as wide as the longest minibatch of the call needs
+    int perm_epochs;          // permutation rows per member
+};
+
+struct UpdateCall {
+    const char *what, *launch; // the entry point's name in its messages, and what a launch failure's message begins with
+    // From the entry point: batch, ws, stats_out, and idx + M + grad_out (a gradient call: M indices) or idx + adam_mv (an update: the
+    // [epochs][n] permutation rows; a population: [members][epochs][n]) with, for one policy, step = the Adam steps taken so far.  The
+    // rest from the filler, but for what changes per minibatch.
+    ssg::PpoMinibatch mb;
+    size_t ws_nbytes;
+    bool loop;                // false: a gradient call — ONE launch, no Adam step
+    int epochs, minibatches;  // the loop on a common schedule, or
+    bool sched;               // ... on per-member ones:
+    PopSchedule sc;
+    bool ext;                 // the extended loss:
+    ssg::PpoExtLaunch el;
+    bool kl_adapt;            // ... and whether the loop ends with the adaptation of the KL coefficient(s)
+    float kl_target;          // (one policy's; a population's are rows of dev_ext)
+    ssg_policy pol;           // what mb.policy points to, so a filled record is not copied (a population's: the shape over its rows)
+    bool device_checked;      // the filler has consulted the device already (see one_policy_update)
+};
+
+static int check_ext(ssg_handle *h, const ssg_ppo_ext *ext, const char *what)
+{
+    const std::string w(what);
+    if (!ext) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL ssg_ppo_ext");
+    if (ext->struct_size != sizeof(ssg_ppo_ext)) return fail(h, SSG_ERR_BAD_ARG, w + ": ssg_ppo_ext.struct_size != sizeof(ssg_ppo_ext)");
+    if (!std::isfinite(ext->vf_clip) || !std::isfinite(ext->max_grad_norm) || !std::isfinite(ext->kl_target))
+        return fail(h, SSG_ERR_BAD_ARG, w + ": vf_clip, max_grad_norm or kl_target is not finite");
+    if (ext->dev_kl_coef && !ext->dev_logp_all) return fail(h, SSG_ERR_BAD_ARG, w + ": dev_kl_coef without dev_logp_all (ssg_ppo_dist)");
+    if (ext->vf_clip > 0.0 && !ext->dev_value_old) return fail(h, SSG_ERR_BAD_ARG, w + ": vf_clip > 0 without dev_value_old");
+    return SSG_OK;
+}
+
+static ssg::PpoExtLaunch ext_launch(const ssg_ppo_ext &ext)
+{
+    ssg::PpoExtLaunch e;
+    e.kl_coef = ext.dev_kl_coef;
+    e.logp_all = ext.dev_kl_coef ? ext.dev_logp_all : nullptr;
+    e.vf_clip = ext.vf_clip > 0.0 ? (float)ext.vf_clip : 0.0f;
+    e.value_old = ext.vf_clip > 0.0 ? ext.dev_value_old : nullptr;
+    e.max_grad_norm = ext.max_grad_norm > 0.0 ? (float)ext.max_grad_norm : 0.0f;
+    e.clip_seq = ext.max_grad_norm > 0.0;
+    e.pop_ext = nullptr;
+    e.first_chunk = true;
+    return e;
+}
+
+// ONE policy on all the handle's samples.  c.ext: `ext` is required (the _ext entry points).
+// The two orders of refusal.  The _ext pair refuses as every later entry point does (the comment above pop_bound): no handle, no state
+// blob, everything the host can judge, and only then the device, in the tail.  ssg_ppo_grad and ssg_ppo_update are older than that rule
+// and keep the order they shipped with, which callers can see: the device first (check_ready; a NULL handle is a bare SSG_ERR_BAD_ARG
+// without a message), then the arguments.  The tail then leaves the device alone.
+static int one_policy_update(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, const ssg_ppo_ext *ext, int64_t n_samples,
+                             UpdateCall &c)
+{
+    const std::string w(c.what);
+    c.device_checked = !c.ext;
+    int rc = c.device_checked ? check_ready(h, false) : pop_bound(h);
+    if (rc == SSG_OK) rc = check_policy(h, pol, c.what);
+    if (rc == SSG_OK) rc = check_hparams(h, hp, c.what);
+    if (rc == SSG_OK && c.ext) rc = check_ext(h, ext, c.what);
+    if (rc == SSG_OK) rc = check_batch(h, n_samples, c.mb.batch, c.mb.idx, c.what);
+    if (rc != SSG_OK) return rc;
+    if (c.loop) {
+        if (!c.mb.adam_mv) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_adam_mv");
+        if (c.epochs < 1 || c.minibatches < 1 || c.mb.step < 0) return fail(h, SSG_ERR_BAD_ARG, w + ": epochs < 1, minibatches < 1 or step0 < 0");
+    } else {
+        if (!c.mb.grad_out) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_grad");
+        if (c.mb.M < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": M < 1");
+    }
+    c.pol = *pol;
+    c.mb.policy = &c.pol;
+    c.mb.members = 1;
+    c.mb.n_samples = n_samples;
+    c.mb.slots_off = ssg::kPpoSlotsOff;
+    c.mb.hp = hp;
+    if (c.ext) {
+        c.el = ext_launch(*ext);
+        c.kl_adapt = ext->kl_target > 0.0 && ext->dev_kl_coef;
+        c.kl_target = (float)ext->kl_target;
+    }
+    return SSG_OK;
+}
+
+// the ssg_pop_ext record, for ssg_pop_update_ext and ssg_pop_update_sched
+static int check_pop_ext(ssg_handle *h, const ssg_pop_ext *ext, const char *what)
+{
+    const std::string w(what);
+    if (!ext) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL ssg_pop_ext");
+    if (ext->struct_size != sizeof(ssg_pop_ext)) return fail(h, SSG_ERR_BAD_ARG, w + ": ssg_pop_ext.struct_size != sizeof(ssg_pop_ext)");
+    if (ext->flags & ~(SSG_POP_EXT_GRAD_CLIP | SSG_POP_EXT_VF_CLIP)) return fail(h, SSG_ERR_BAD_ARG, w + ": unknown ssg_pop_ext.flags bits");
+    if (!ext->dev_ext) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_ext");
+    if (ext->dev_kl_coef && !ext->dev_logp_all) return fail(h, SSG_ERR_BAD_ARG, w + ": dev_kl_coef without dev_logp_all (ssg_pop_dist)");
+    if ((ext->flags & SSG_POP_EXT_VF_CLIP) && !ext->dev_value_old) return fail(h, SSG_ERR_BAD_ARG, w + ": SSG_POP_EXT_VF_CLIP without dev_value_old");
+    return SSG_OK;
+}
+
+// a population's: the members' constants are rows of dev_ext, the flags say which terms some member has on
+static ssg::PpoExtLaunch ext_launch(const ssg_pop_ext &ext)
+{
+    ssg::PpoExtLaunch e;
+    e.kl_coef = ext.dev_kl_coef;
+    e.logp_all = ext.dev_kl_coef ? ext.dev_logp_all : nullptr;
+    e.value_old = (ext.flags & SSG_POP_EXT_VF_CLIP) ? ext.dev_value_old : nullptr;
+    e.pop_ext = ext.dev_ext;
+    e.vf_clip = e.max_grad_norm = 0.0f; // (per member: dev_ext)
+    e.clip_seq = (ext.flags & SSG_POP_EXT_GRAD_CLIP) != 0;
+    e.first_chunk = true;
+    return e;
+}
+
+// A population on the handle's slices, every member on its K * (its envs) samples.  c.ext: `ext` is required.  c.sched: the per-member
+// epochs / minibatches (host arrays, from which the launches, their width and the workspace are re-derived: what the device table was
+// packed from decides them) with the device table and the permutation rows per member, in place of c.epochs / c.minibatches; unequal
+// slices run only so.
+static int population_update(ssg_handle *h, const ssg_population *pop, const ssg_pop_ext *ext, const float *dev_table, int table_steps, int K,
+                             const int32_t *dev_sched, const int32_t *epochs, const int32_t *minibatches, int perm_epochs, UpdateCall &c)
+{
+    const std::string w(c.what);
+    int rc = pop_bound(h);
+    if (rc == SSG_OK) rc = check_population(h, pop, c.what);
+    if (rc == SSG_OK && c.ext) rc = check_pop_ext(h, ext, c.what);
+    if (rc != SSG_OK) return rc;
+    if (K < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": K < 1");
+    const int P = pop->n_members, N = h->cfg.n_envs;
+    const int32_t *slices = pop_slices(h);
+    if (slices && !c.sched)
+        return fail(h, SSG_ERR_BAD_ARG, w + ": slices are bound to the handle (ssg_pop_set_slices): the update runs through ssg_pop_update_sched");
+    long long n = (long long)K * (N / P); // samples per member (unequal slices: the widest member's, below)
+    rc = check_batch(h, n, c.mb.batch, c.mb.idx, c.what);
+    if (rc == SSG_OK) rc = check_adv_norm_members(h, P, c.what);
+    if (rc != SSG_OK) return rc;
+    if (!dev_table || !c.mb.adam_mv) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_table or dev_adam_mv");
+    c.mb.n = N / P;
+    if (!c.sched) {
+        if (c.epochs < 1 || c.minibatches < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": epochs < 1 or minibatches < 1");
+        if ((long long)table_steps < (long long)c.epochs * chunking(n, c.minibatches).chunks)
+            return fail(h, SSG_ERR_BAD_ARG, w + ": the table holds fewer Adam steps than epochs * chunks");
+    } else {
+        if (!epochs || !minibatches) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL epochs or minibatches");
+        if (!dev_sched) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_sched");
+        c.sc.dev_sched = dev_sched;
+        c.sc.perm_epochs = perm_epochs;
+        // unequal slices: every member's own sample count, and what the SLICED kernels read instead of n, n_samples and idx_stride
+        std::vector<int64_t> samples;
+        if (slices) {
+            for (int32_t n_m : h->pop_sizes) samples.push_back((int64_t)K * n_m);
+            c.mb.slices = slices;
+            c.mb.sched_hdr = dev_sched;
+            c.mb.K = K;
+            c.mb.perm_epochs = perm_epochs;
+            c.mb.n = 0;
+            n = *std::max_element(samples.begin(), samples.end());
+        }
+        if (!pop_schedule(P, n, epochs, minibatches, nullptr, nullptr, &c.sc.n_launches, &c.sc.Cmax, samples.empty() ? nullptr : samples.data()))
+            return fail(h, SSG_ERR_BAD_ARG, w + ": a member's epochs or minibatches is < 1 (or its steps exceed 2^31-1)");
+        if (perm_epochs < *std::max_element(epochs, epochs + P)) return fail(h, SSG_ERR_BAD_ARG, w + ": perm_epochs < the largest epochs of a member");
+        if ((long long)table_steps < c.sc.n_launches)
+            return fail(h, SSG_ERR_BAD_ARG, w + ": the table holds fewer Adam steps than the schedule's launches (max epochs * chunks)");
+    }
+    c.pol = pop_policy(*pop);
+    c.mb.policy = &c.pol;
+    c.mb.members = P;
+    c.mb.N = N;
+    c.mb.n_samples = n;
+    c.mb.slots_off = ssg::kPopSlotsOff;
+    c.mb.table = dev_table;
+    if (c.ext) {
+        c.el = ext_launch(*ext);
+        c.kl_adapt = ext->dev_kl_coef != nullptr;
+    }
+    return SSG_OK;
+}
+
+// The loop of the five update entry points.  c.mb: idx = the permutation rows, stats_out = the caller's stats rows or NULL, step = the
+// Adam steps taken so far, table = a population's table.  Minibatch j of the call reads chunk j % chunks of permutation row j / chunks,
+// takes Adam step step + 1 + j (a population: the table's Adam rows 1 + j) and writes stats row j.  With c.sched launch j serves
+// minibatch j of every member that has one: M, the chunk's place and first_chunk are per member, in the table's records of launch j; the
+// launch itself is sized for Cmax.  c.kl_adapt: end with the adaptation of the coefficient(s) from the last epoch's chunks.
+static int run_update(ssg_handle *h, UpdateCall &c, hipStream_t st)
+{
+    ssg::PpoMinibatch mb = c.mb;
+    ssg::PpoExtLaunch *ext = c.ext ? &c.el : nullptr;
+    const PopSchedule *sched = c.sched ? &c.sc : nullptr;
+    const long long n = mb.n_samples;
+    const Chunking ck = sched ? Chunking{sched->Cmax, 0} : chunking(n, c.minibatches);
+    const long long launches = sched ? sched->n_launches : (long long)c.epochs * ck.chunks;
+    const int cols = ext ? ssg::kExtStats : 4;
+    const int64_t *perm = mb.idx;
+    float *stats = mb.stats_out;
+    mb.ext = ext;
+    mb.idx_stride = (long long)(sched ? sched->perm_epochs : c.epochs) * n;
+    mb.stats_stride = cols * launches;
+    for (long long j = 0; j < launches; ++j) {
+        if (sched) {
+            mb.M = sched->Cmax;
+            mb.sched = sched->dev_sched + (size_t)(1 + j) * (size_t)mb.members * ssg::kPopSchedRow;
+        } else {
+            const long long ep = j / ck.chunks, b0 = (j - ep * ck.chunks) * ck.C;
+            mb.M = std::min(ck.C, n - b0);
+            mb.idx = perm + (size_t)ep * (size_t)n + (size_t)b0;
+            if (ext) ext->first_chunk = b0 == 0;
+        }
+        mb.stats_out = stats ? stats + cols * j : nullptr;
+        ++mb.step;
+        if (mb.table) mb.adam_row = mb.table + (size_t)(1 + j) * (size_t)mb.members * ssg::kPopTableRow;
+        hipError_t e = ssg::launch_ppo_minibatch(mb, st);
+        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string(c.launch) + " launch: " + hipGetErrorString(e));
+    }
+    if (c.kl_adapt) {
+        hipError_t e = ssg::launch_kl_adapt(mb.members, *ext, c.kl_target, ssg::ppo_packed_len(c.pol), ck.chunks,
+                                            sched ? sched->dev_sched : nullptr, mb.ws, mb.slots_off, st);
+        if (e != hipSuccess)
+            return fail(h, SSG_ERR_HIP, std::string(mb.table ? "population kl adapt launch: " : "kl adapt launch: ") + hipGetErrorString(e));
+    }
+    return SSG_OK;
+}
+
+// The tail of all seven: the workspace against the widest minibatch of the call, the device, the kernels' attributes, the bound
+// per-minibatch normalisation, and then the gradient call's one launch or the loop.
+static int update_call(ssg_handle *h, UpdateCall &c, void *stream)
+{
+    const long long M = !c.loop ? c.mb.M : c.sched ? c.sc.Cmax : chunking(c.mb.n_samples, c.minibatches).C;
+    int rc = check_workspace(h, c.mb.ws, c.ws_nbytes, need_grad(c.mb.slots_off, c.mb.members, c.pol, M, c.ext), c.what);
+    if (rc == SSG_OK && !c.device_checked) rc = check_ready(h, false);
+    if (rc == SSG_OK) rc = prepare_ppo(h);
+    if (rc != SSG_OK) return rc;
+    adv_norm_bind(h, c.mb);
+    if (c.loop) return run_update(h, c, static_cast<hipStream_t>(stream));
+    c.mb.ext = c.ext ? &c.el : nullptr;
+    hipError_t e = ssg::launch_ppo_minibatch(c.mb, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string(c.launch) + " launch: " + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+// what every one of the seven writes into its record first
+static UpdateCall update_args(const char *what, const char *launch, bool ext, const float *dev_x, const int32_t *dev_act, const float *dev_logp,
+                              const float *dev_adv, const float *dev_ret, const int64_t *dev_idx, float *dev_stats, void *dev_workspace,
+                              size_t workspace_nbytes)
+{
+    UpdateCall c = {};
+    c.what = what;
+    c.launch = launch;
+    c.ext = ext;
+    c.mb.batch = {dev_x, dev_act, dev_logp, dev_adv, dev_ret};
+    c.mb.idx = dev_idx;
+    c.mb.stats_out = dev_stats;
+    c.mb.ws = dev_workspace;
+    c.ws_nbytes = workspace_nbytes;
+    return c;
+}
+
+// ... and an update after it: the loop, its moments and, where they are common, its epochs and minibatches
+static void update_loop(UpdateCall &c, float *dev_adam_mv, int epochs, int minibatches)
+{
+    c.loop = true;
+    c.mb.adam_mv = dev_adam_mv;
+    c.epochs = epochs;
+    c.minibatches = minibatches;
+}
+
+static int ppo_grad(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, const ssg_ppo_ext *ext, int64_t n_samples, int64_t M,
+                    float *dev_grad, UpdateCall c, void *stream)
+{
+    c.mb.M = M;
+    c.mb.grad_out = dev_grad;
+    const int rc = one_policy_update(h, pol, hp, ext, n_samples, c);
+    return rc == SSG_OK ? update_call(h, c, stream) : rc;
+}
+
+int ssg_ppo_grad(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, int64_t n_samples, const float *dev_x,
+                 const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret, const int64_t *dev_idx,
+                 int64_t M, float *dev_grad, float *dev_stats, void *dev_workspace, size_t workspace_nbytes, void *stream)
+{
+    return ppo_grad(h, pol, hp, nullptr, n_samples, M, dev_grad,
+                    update_args("ssg_ppo_grad", "ppo grad", false, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_idx, dev_stats, dev_workspace,
+                                workspace_nbytes), stream);
+}
+
+int ssg_ppo_grad_ext(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, const ssg_ppo_ext *ext, int64_t n_samples,
+                     const float *dev_x, const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret,
+                     const int64_t *dev_idx, int64_t M, float *dev_grad, float *dev_stats, void *dev_workspace, size_t workspace_nbytes,
+                     void *stream)
+{
+    return ppo_grad(h, pol, hp, ext, n_samples, M, dev_grad,
+                    update_args("ssg_ppo_grad_ext", "ppo grad_ext", true, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_idx, dev_stats,
+                                dev_workspace, workspace_nbytes), stream);
+}
+
+static int ppo_update(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, const ssg_ppo_ext *ext, int64_t n_samples, int epochs,
+                      int minibatches, float *dev_adam_mv, int64_t step0, UpdateCall c, void *stream)
+{
+    update_loop(c, dev_adam_mv, epochs, minibatches);
+    c.mb.step = step0;
+    const int rc = one_policy_update(h, pol, hp, ext, n_samples, c);
+    return rc == SSG_OK ? update_call(h, c, stream) : rc;
+}
+
+int ssg_ppo_update(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, int64_t n_samples, const float *dev_x,
+                   const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret, const int64_t *dev_perm,
+                   int epochs, int minibatches, float *dev_adam_mv, int64_t step0, float *dev_stats, void *dev_workspace,
+                   size_t workspace_nbytes, void *stream)
+{
+    return ppo_update(h, pol, hp, nullptr, n_samples, epochs, minibatches, dev_adam_mv, step0,
+                      update_args("ssg_ppo_update", "ppo update", false, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_perm, dev_stats,
+                                  dev_workspace, workspace_nbytes), stream);
+}
+
+int ssg_ppo_update_ext(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, const ssg_ppo_ext *ext, int64_t n_samples,
+                       const float *dev_x, const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret,
+                       const int64_t *dev_perm, int epochs, int minibatches, float *dev_adam_mv, int64_t step0, float *dev_stats,
+                       void *dev_workspace, size_t workspace_nbytes, void *stream)
+{
+    return ppo_update(h, pol, hp, ext, n_samples, epochs, minibatches, dev_adam_mv, step0,
+                      update_args("ssg_ppo_update_ext", "ppo update_ext", true, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_perm, dev_stats,
+                                  dev_workspace, workspace_nbytes), stream);
+}
+
+int ssg_pop_update(ssg_handle *h, const ssg_population *pop, const float *dev_table, int table_steps, int K, const float *dev_x,
+                   const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret, const int64_t *dev_perm,
+                   int epochs, int minibatches, float *dev_adam_mv, float *dev_stats, void *dev_workspace, size_t workspace_nbytes,
+                   void *stream)
+{
+    UpdateCall c = update_args("ssg_pop_update", "population update", false, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_perm, dev_stats,
+                               dev_workspace, workspace_nbytes);
+    update_loop(c, dev_adam_mv, epochs, minibatches);
+    const int rc = population_update(h, pop, nullptr, dev_table, table_steps, K, nullptr, nullptr, nullptr, 0, c);
+    return rc == SSG_OK ? update_call(h, c, stream) : rc;
+}
+
+int ssg_pop_update_ext(ssg_handle *h, const ssg_population *pop, const ssg_pop_ext *ext, const float *dev_table, int table_steps, int K,
+                       const float *dev_x, const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret,
+                       const int64_t *dev_perm, int epochs, int minibatches, float *dev_adam_mv, float *dev_stats, void *dev_workspace,
+                       size_t workspace_nbytes, void *stream)
+{
+    UpdateCall c = update_args("ssg_pop_update_ext", "population update_ext", true, dev_x, dev_act, dev_logp, dev_adv, dev_ret, dev_perm,
+                               dev_stats, dev_workspace, workspace_nbytes);
+    update_loop(c, dev_adam_mv, epochs, minibatches);
+    const int rc = population_update(h, pop, ext, dev_table, table_steps, K, nullptr, nullptr, nullptr, 0, c);
+    return rc == SSG_OK ? update_call(h, c, stream) : rc;
 }
 
 int ssg_pop_update_sched(ssg_handle *h, const ssg_population *pop, const ssg_pop_ext *ext, const float *dev_table, int table_steps,
@@ -2142,51 +2177,12 @@ int ssg_pop_update_sched(ssg_handle *h, const ssg_population *pop, const ssg_pop
                          const int64_t *dev_perm, float *dev_adam_mv, float *dev_stats, void *dev_workspace, size_t workspace_nbytes,
                          void *stream)
 {
-    const char *what = "ssg_pop_update_sched";
-    const ssg::PpoBatch batch = {dev_x, dev_act, dev_logp, dev_adv, dev_ret};
-    int rc = pop_bound(h);
-    if (rc == SSG_OK) rc = check_population(h, pop, what);
-    if (rc == SSG_OK && ext) rc = check_pop_ext(h, ext, what);
-    if (rc != SSG_OK) return rc;
-    const ssg_policy pol = pop_policy(*pop);
-    const int P = pop->n_members;
-    ssg::PpoMinibatch mb;
-    rc = check_pop_update(h, &pol, P, dev_table, table_steps, K, batch, dev_perm, 0, 0, dev_adam_mv, what, &mb, true);
-    if (rc != SSG_OK) return rc;
-    if (!epochs || !minibatches) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_sched: NULL epochs or minibatches");
-    if (!dev_sched) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_sched: NULL dev_sched");
-    // (re-derived from the host arrays: what the device table was packed from decides the launches, their width and the workspace)
-    PopSchedule sc;
-    sc.dev_sched = dev_sched;
-    sc.perm_epochs = perm_epochs;
-    // unequal slices: every member's own sample count, and what the SLICED kernels read instead of n, n_samples and idx_stride
-    std::vector<int64_t> samples;
-    if (const int32_t *slices = pop_slices(h)) {
-        for (int32_t n_m : h->pop_sizes) samples.push_back((int64_t)K * n_m);
-        mb.slices = slices;
-        mb.sched_hdr = dev_sched;
-        mb.K = K;
-        mb.perm_epochs = perm_epochs;
-        mb.n = 0;
-        mb.n_samples = *std::max_element(samples.begin(), samples.end());
-    }
-    if (!pop_schedule(P, mb.n_samples, epochs, minibatches, nullptr, nullptr, &sc.n_launches, &sc.Cmax, samples.empty() ? nullptr : samples.data()))
-        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_sched: a member's epochs or minibatches is < 1 (or its steps exceed 2^31-1)");
-    if (perm_epochs < *std::max_element(epochs, epochs + P))
-        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_sched: perm_epochs < the largest epochs of a member");
-    if ((long long)table_steps < sc.n_launches)
-        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_update_sched: the table holds fewer Adam steps than the schedule's launches (max epochs * chunks)");
-    const size_t need = need_grad(ssg::kPopSlotsOff, P, pol, sc.Cmax, ext != nullptr);
-    rc = check_workspace(h, dev_workspace, workspace_nbytes, need, what);
-    if (rc == SSG_OK) rc = check_ready(h, false);
-    if (rc == SSG_OK) rc = prepare_ppo(h);
-    if (rc != SSG_OK) return rc;
-    mb.ws = dev_workspace;
-    mb.stats_out = dev_stats;
-    ssg::PpoExtLaunch el;
-    if (ext) el = ext_launch(*ext);
-    return run_update(h, mb, ext ? &el : nullptr, 0, 0, ext && ext->dev_kl_coef != nullptr, 0.0f,
-                      ext ? "population update_sched (ext)" : "population update_sched", static_cast<hipStream_t>(stream), &sc);
+    UpdateCall c = update_args("ssg_pop_update_sched", ext ? "population update_sched (ext)" : "population update_sched", ext != nullptr, dev_x,
+                               dev_act, dev_logp, dev_adv, dev_ret, dev_perm, dev_stats, dev_workspace, workspace_nbytes);
+    update_loop(c, dev_adam_mv, 0, 0);
+    c.sched = true;
+    const int rc = population_update(h, pop, ext, dev_table, table_steps, K, dev_sched, epochs, minibatches, perm_epochs, c);
+    return rc == SSG_OK ? update_call(h, c, stream) : rc;
 }
 
 int ssg_pop_exploit(ssg_handle *h, const ssg_population *pop, const int32_t *src, float *dev_adam_mv, void *stream)

@@ -1107,47 +1107,38 @@ size_t ppo_grad_lds_bytes(const ssg_policy &p)
 // (the extended instantiations add v_old, four logp_old and the fifth loss sum per sample of the tile: 1.5 KB)
 size_t ppo_grad_ext_lds_bytes(const ssg_policy &p) { return ppo_grad_lds_bytes(p) + 6 * kTile * sizeof(float); }
 
-// the gradient kernel's instantiation for a population or not (and then on per-member schedules or not), the extended loss or not,
-// separate towers or not
-typedef void (*GradKernel)(const GradArgs, const PopGradArgs);
-typedef void (*GradExtKernel)(const GradArgs, const PopGradArgs, const ExtGradArgs);
-static GradKernel grad_plain(bool pop, bool split)
+// The gradient kernel's instantiations: for a population or not (and then on per-member schedules, and on unequal slices, or not), the
+// extended loss or not, separate towers or not.  prepare_ppo walks the tables, launch_ppo_minibatch indexes them.  Every table lists the
+// instantiations with their flags ON first, so it is indexed [!split] (and then [!pop]): an instantiation's place in the object's .text
+// follows its first mention, and these orders, of the tables and inside them, keep the object's device code byte for byte.
+static decltype(&ppo_grad_kernel<false, false>) const kGrad[2][2] = {{ppo_grad_kernel<true, true>, ppo_grad_kernel<false, true>},
+                                                                    {ppo_grad_kernel<true, false>, ppo_grad_kernel<false, false>}};
+static decltype(&ppo_grad_ext_kernel<false, false>) const kGradExt[2][2] = {{ppo_grad_ext_kernel<true, true>, ppo_grad_ext_kernel<false, true>},
+                                                                            {ppo_grad_ext_kernel<true, false>, ppo_grad_ext_kernel<false, false>}};
+static decltype(&ppo_grad_sched_kernel<false>) const kGradSched[2] = {ppo_grad_sched_kernel<true>, ppo_grad_sched_kernel<false>};
+static decltype(&ppo_grad_ext_sched_kernel<false>) const kGradExtSched[2] = {ppo_grad_ext_sched_kernel<true>, ppo_grad_ext_sched_kernel<false>};
+static decltype(&ppo_grad_ext_sliced_kernel<false>) const kGradExtSliced[2] = {ppo_grad_ext_sliced_kernel<true>, ppo_grad_ext_sliced_kernel<false>};
+static decltype(&ppo_grad_sliced_kernel<false>) const kGradSliced[2] = {ppo_grad_sliced_kernel<true>, ppo_grad_sliced_kernel<false>};
+
+// (the dynamic-LDS limit of the gradient kernels: up to 151 KB at obs_dim 176, hidden 128, 2 layers)
+template <typename Kernel> static hipError_t raise_lds_limit(const Kernel *k, int count)
 {
-    if (split) return pop ? ppo_grad_kernel<true, true> : ppo_grad_kernel<false, true>;
-    return pop ? ppo_grad_kernel<true, false> : ppo_grad_kernel<false, false>;
-}
-static GradExtKernel grad_ext(bool pop, bool split)
-{
-    if (split) return pop ? ppo_grad_ext_kernel<true, true> : ppo_grad_ext_kernel<false, true>;
-    return pop ? ppo_grad_ext_kernel<true, false> : ppo_grad_ext_kernel<false, false>;
-}
-typedef void (*GradSchedKernel)(const GradArgs, const PopGradArgs, const int32_t *);
-typedef void (*GradExtSchedKernel)(const GradArgs, const PopGradArgs, const ExtGradArgs, const int32_t *);
-static GradSchedKernel grad_plain_sched(bool split) { return split ? ppo_grad_sched_kernel<true> : ppo_grad_sched_kernel<false>; }
-static GradExtSchedKernel grad_ext_sched(bool split) { return split ? ppo_grad_ext_sched_kernel<true> : ppo_grad_ext_sched_kernel<false>; }
-static const void *grad_kernel_sliced(bool ext, bool split)
-{
-    if (ext) return split ? reinterpret_cast<const void *>(ppo_grad_ext_sliced_kernel<true>) : reinterpret_cast<const void *>(ppo_grad_ext_sliced_kernel<false>);
-    return split ? reinterpret_cast<const void *>(ppo_grad_sliced_kernel<true>) : reinterpret_cast<const void *>(ppo_grad_sliced_kernel<false>);
-}
-static const void *grad_kernel(bool pop, bool ext, bool split, bool sched = false)
-{
-    if (sched) return ext ? reinterpret_cast<const void *>(grad_ext_sched(split)) : reinterpret_cast<const void *>(grad_plain_sched(split));
-    return ext ? reinterpret_cast<const void *>(grad_ext(pop, split)) : reinterpret_cast<const void *>(grad_plain(pop, split));
+    for (int i = 0; i < count; ++i) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k[i]), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t prepare_ppo()
 {
-    const void *kernels[16] = {grad_kernel_sliced(false, false),      grad_kernel_sliced(true, false),      grad_kernel_sliced(false, true),
-                               grad_kernel_sliced(true, true),        grad_kernel(false, false, false),      grad_kernel(true, false, false),      grad_kernel(false, true, false),
-                               grad_kernel(true, true, false),        grad_kernel(false, false, true),      grad_kernel(true, false, true),
-                               grad_kernel(false, true, true),        grad_kernel(true, true, true),        grad_kernel(true, false, false, true),
-                               grad_kernel(true, true, false, true),  grad_kernel(true, false, true, true), grad_kernel(true, true, true, true)};
-    for (const void *k : kernels) {
-        hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    hipError_t e = raise_lds_limit(&kGrad[0][0], 4);
+    if (e == hipSuccess) e = raise_lds_limit(&kGradExt[0][0], 4);
+    if (e == hipSuccess) e = raise_lds_limit(kGradSched, 2);
+    if (e == hipSuccess) e = raise_lds_limit(kGradExtSched, 2);
+    if (e == hipSuccess) e = raise_lds_limit(kGradExtSliced, 2);
+    if (e == hipSuccess) e = raise_lds_limit(kGradSliced, 2);
+    return e;
 }
 
 hipError_t launch_ppo_gae(const ssg_ppo_hparams &hp, int K, int N, const double *rew, const uint8_t *done, const float *val,
@@ -1243,11 +1234,9 @@ hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream)
     const AdamArgs ad = mb.adam_mv && !pop ? adam_args(*mb.hp, mb.step) : AdamArgs{};
     const dim3 ggrid((unsigned)G, (unsigned)mb.members), rgrid((unsigned)((stride + 255) / 256), (unsigned)mb.members);
     if (!ext) {
-        if (sliced)
-            hipLaunchKernelGGL(split ? ppo_grad_sliced_kernel<true> : ppo_grad_sliced_kernel<false>, ggrid, dim3(kPpoBlock), ppo_grad_lds_bytes(p),
-                               stream, a, pa, mb.sched, sa);
-        else if (sched) hipLaunchKernelGGL(grad_plain_sched(split), ggrid, dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a, pa, mb.sched);
-        else hipLaunchKernelGGL(grad_plain(pop, split), ggrid, dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a, pa);
+        if (sliced) hipLaunchKernelGGL(kGradSliced[!split], ggrid, dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a, pa, mb.sched, sa);
+        else if (sched) hipLaunchKernelGGL(kGradSched[!split], ggrid, dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a, pa, mb.sched);
+        else hipLaunchKernelGGL(kGrad[!split][!pop], ggrid, dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a, pa);
         if (sched)
             hipLaunchKernelGGL(ppo_reduce_sched_kernel, rgrid, dim3(256), 0, stream, (const float *)a.slots, G, P, stride, mb.stats_out, params,
                                mb.adam_mv, mb.stats_stride, mb.adam_row, mb.sched);
@@ -1262,12 +1251,9 @@ hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream)
     ea.kl_coef = ext->kl_coef;
     ea.pop_ext = ext->pop_ext;
     ea.vf_clip = ext->vf_clip;
-    if (sliced)
-        hipLaunchKernelGGL(split ? ppo_grad_ext_sliced_kernel<true> : ppo_grad_ext_sliced_kernel<false>, ggrid, dim3(kPpoBlock),
-                           ppo_grad_ext_lds_bytes(p), stream, a, pa, ea, mb.sched, sa);
-    else if (sched) hipLaunchKernelGGL(grad_ext_sched(split), ggrid, dim3(kPpoBlock), ppo_grad_ext_lds_bytes(p), stream, a, pa, ea, mb.sched);
-    else hipLaunchKernelGGL(grad_ext(pop, split), ggrid, dim3(kPpoBlock), ppo_grad_ext_lds_bytes(p), stream,
-                       a, pa, ea);
+    if (sliced) hipLaunchKernelGGL(kGradExtSliced[!split], ggrid, dim3(kPpoBlock), ppo_grad_ext_lds_bytes(p), stream, a, pa, ea, mb.sched, sa);
+    else if (sched) hipLaunchKernelGGL(kGradExtSched[!split], ggrid, dim3(kPpoBlock), ppo_grad_ext_lds_bytes(p), stream, a, pa, ea, mb.sched);
+    else hipLaunchKernelGGL(kGradExt[!split][!pop], ggrid, dim3(kPpoBlock), ppo_grad_ext_lds_bytes(p), stream, a, pa, ea);
     ExtReduceArgs er;
     er.kl_coef = ext->kl_coef;
     er.klacc = reinterpret_cast<float *>(base + lay.klacc);

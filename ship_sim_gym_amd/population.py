@@ -26,7 +26,7 @@ from fractions import Fraction
 
 from . import _native as N
 from .policy import ACTIVATIONS, NativePolicy
-from .ppo import adv_norm_mode, adv_norm_scratch, adv_norm_views, chunk_split
+from .ppo import DeviceTrainer, adv_norm_mode, adv_norm_scratch, adv_norm_views, chunk_split, load_packed
 
 
 def _torch():
@@ -94,20 +94,11 @@ class NativePopulation(object):
 
     def load_into(self, nets):
         """Copy row m into nets[m] (modules shaped like the members), for checkpoints."""
-        torch = _torch()
         nets = list(nets)
         if len(nets) != len(self):
             raise ValueError("NativePopulation.load_into: %d modules for %d members" % (len(nets), len(self)))
-        with torch.no_grad():
-            for m, net in enumerate(nets):
-                params = list(net.parameters())
-                if sum(q.numel() for q in params) != self.n_params:
-                    raise ValueError("NativePopulation.load_into: module %d has %d parameters, a member %d"
-                                     % (m, sum(q.numel() for q in params), self.n_params))
-                o = 0
-                for q in params:
-                    q.copy_(self.params[m, o: o + q.numel()].view_as(q))
-                    o += q.numel()
+        for m, net in enumerate(nets):
+            load_packed(self.params[m], net, "NativePopulation.load_into: module %d has %%d parameters, a member %d" % (m, self.n_params))
         return nets
 
     def to_native(self):
@@ -127,7 +118,7 @@ HPARAM_KEYS = ("gamma", "lam", "clip", "vf_coef", "ent_coef", "lr", "beta1", "be
 EXT_KEYS = ("vf_clip", "max_grad_norm", "kl_target")
 
 
-class PopulationPPO(object):
+class PopulationPPO(DeviceTrainer):
     """GAE and the PPO update of every member of a NativePopulation in shared launches (ssg_pop_gae / ssg_pop_update), the PBT exploit
     copy (ssg_pop_exploit) and per-member episode statistics (ssg_pop_episode_stats).  Owns the Adam moments [P, 2L], the workspace and
     the episode carry columns.  Every hyper-parameter is a list of P floats (``self.lr[m] = ...``); defaults: NativePPO's.  So are
@@ -142,7 +133,7 @@ class PopulationPPO(object):
     def __init__(self, population, env, gamma=0.99, lam=0.95, clip=0.2, vf_coef=0.5, ent_coef=0.01, lr=3e-4, beta1=0.9, beta2=0.999,
                  eps=1e-8, adv_eps=1e-8, vf_clip=0.0, max_grad_norm=0.0, kl_coef=0.0, kl_target=0.0, adv_norm="batch", perm_seed=None):
         torch = _torch()
-        self.population, self.env = population, env
+        self.population, self.env, self._device = population, env, population.device
         P = len(population)
         self.perm_seed = None if perm_seed is None else int(perm_seed)  # None: the caller brings every perm
         self.updates = 0  # calls of update(); like `step`, a checkpoint may set it
@@ -225,13 +216,10 @@ class PopulationPPO(object):
         torch = _torch()
         n = N.pop_table_floats(self.n_members, n_steps)
         buf = (C.c_float * n)()
-        if steps0 is None:
-            N.check(N.lib().ssg_pop_pack_hparams(self.n_members, self.hparams(), int(self.step), int(n_steps), buf, n), None,
-                    "ssg_pop_pack_hparams")
-        else:
-            arr = (C.c_int64 * self.n_members)(*[int(x) for x in steps0])
-            N.check(N.lib().ssg_pop_pack_hparams_steps(self.n_members, self.hparams(), arr, int(n_steps), buf, n), None,
-                    "ssg_pop_pack_hparams_steps")
+        name, step0 = "ssg_pop_pack_hparams", int(self.step)
+        if steps0 is not None:
+            name, step0 = "ssg_pop_pack_hparams_steps", (C.c_int64 * self.n_members)(*[int(x) for x in steps0])
+        N.check(getattr(N.lib(), name)(self.n_members, self.hparams(), step0, int(n_steps), buf, n), None, name)
         return torch.tensor(list(buf), dtype=torch.float32).to(self.population.device)
 
     def minibatches_for_size(self, size, samples=None, member=None):
@@ -253,35 +241,21 @@ class PopulationPPO(object):
         ep, mb = (C.c_int32 * P)(*[int(e) for e in epochs]), (C.c_int32 * P)(*[int(b) for b in minibatches])
         steps, launches = (C.c_int32 * P)(), C.c_int32()
         if isinstance(samples, (list, tuple)):
-            sm = (C.c_int64 * P)(*[int(x) for x in samples])
-            fn, what = N.lib().ssg_pop_pack_schedule_samples, "ssg_pop_pack_schedule_samples"
-            N.check(fn(P, sm, ep, mb, None, 0, steps, C.byref(launches)), None, what)
-            n = N.pop_sched_ints(P, launches.value)
-            buf = (C.c_int32 * n)()
-            N.check(fn(P, sm, ep, mb, buf, n, steps, C.byref(launches)), None, what)
-            return buf, list(steps), int(launches.value)
-        N.check(N.lib().ssg_pop_pack_schedule(P, int(samples), ep, mb, None, 0, steps, C.byref(launches)), None, "ssg_pop_pack_schedule")
+            name, sm = "ssg_pop_pack_schedule_samples", (C.c_int64 * P)(*[int(x) for x in samples])
+        else:
+            name, sm = "ssg_pop_pack_schedule", int(samples)
+
+        def pack(buf, n):
+            N.check(getattr(N.lib(), name)(P, sm, ep, mb, buf, n, steps, C.byref(launches)), None, name)
+        pack(None, 0)  # the size query
         n = N.pop_sched_ints(P, launches.value)
         buf = (C.c_int32 * n)()
-        N.check(N.lib().ssg_pop_pack_schedule(P, int(samples), ep, mb, buf, n, steps, C.byref(launches)), None, "ssg_pop_pack_schedule")
+        pack(buf, n)
         return buf, list(steps), int(launches.value)
 
     def _ws(self, samples_per_member, max_minibatch):
         """The workspace, grown to serve the sizes (its head — the members' advantage statistics — is kept when it grows)."""
-        torch = _torch()
-        need = C.c_size_t()
-        pop = self.population.to_native()
-        N.check(N.lib().ssg_pop_workspace_nbytes(C.byref(pop), int(samples_per_member), int(max_minibatch), C.byref(need)), None,
-                "ssg_pop_workspace_nbytes")
-        if self.workspace.numel() < need.value:
-            ws = torch.zeros(need.value + 256, dtype=torch.uint8, device=self.population.device)
-            if self.workspace.numel():
-                ws[:16 * self.n_members].copy_(self.workspace[:16 * self.n_members])
-            self.workspace = ws
-        return self.workspace
-
-    def _stream(self):
-        return C.c_void_p(_torch().cuda.current_stream(self.population.device).cuda_stream)
+        return self._grow("ssg_pop_workspace_nbytes", self.population.to_native(), samples_per_member, max_minibatch, 16 * self.n_members)
 
     def _flat(self, batch, key, dtype, shape):
         t = batch[key]
@@ -444,98 +418,75 @@ class PopulationPPO(object):
         return st
 
     def _update(self, batch, perm, epochs, minibatches, stats=False):
-        """update() with the permutations given."""
+        """update() with the permutations given: on a common schedule (ssg_pop_update / ssg_pop_update_ext), or — a list among epochs /
+        minibatches, or slices bound to the env — on per-member schedules (ssg_pop_update_sched)."""
         torch = _torch()
         K, n_env = self._KN(batch)
         P, dev, D = self.n_members, self.population.device, self.population.obs_dim
         self._last_K = K
-        if self.env.population_slices is not None:
-            return self._update_sched(batch, perm, epochs, minibatches, stats, K, n_env, [K * n_m for n_m in self.member_envs])
-        n = K * self.envs_per_member
-        if isinstance(epochs, (list, tuple)) or isinstance(minibatches, (list, tuple)):
-            return self._update_sched(batch, perm, epochs, minibatches, stats, K, n_env, n)
+        sliced = self.env.population_slices is not None
+        n = [K * n_m for n_m in self.member_envs] if sliced else K * self.envs_per_member  # samples per member (sliced: P counts)
+        sched = sliced or isinstance(epochs, (list, tuple)) or isinstance(minibatches, (list, tuple))
+        if sched:
+            epochs = [int(e) for e in epochs] if isinstance(epochs, (list, tuple)) else [int(epochs)] * P
+            minibatches = [int(b) for b in minibatches] if isinstance(minibatches, (list, tuple)) else [int(minibatches)] * P
+            if len(epochs) != P or len(minibatches) != P:
+                raise ValueError("PopulationPPO.update: %d epochs and %d minibatches for %d members" % (len(epochs), len(minibatches), P))
+            if min(epochs) < 1 or min(minibatches) < 1:
+                raise ValueError("PopulationPPO.update: every member's epochs and minibatches must be >= 1")
         p = [self._flat(batch, "obs", torch.float32, (K, n_env, D)), self._flat(batch, "act", torch.int32, (K, n_env)),
              self._flat(batch, "logp", torch.float32, (K, n_env)), self._flat(batch, "adv", torch.float32, (K, n_env)),
              self._flat(batch, "ret", torch.float32, (K, n_env))]
+        if sliced and isinstance(perm, (list, tuple)):
+            if len(perm) != P or any(tuple(q.shape) != (max(epochs), n[m]) for m, q in enumerate(perm)):
+                raise ValueError("PopulationPPO.update: perm must list %d tensors int64 [max(epochs) = %d, K*n_m] with K*n_m = %s"
+                                 % (P, max(epochs), n))
+            perm = torch.cat([q.to(device=dev, dtype=torch.int64).reshape(-1) for q in perm])
         perm = perm.to(device=dev, dtype=torch.int64).contiguous()
-        if tuple(perm.shape) != (P, int(epochs), n):
-            raise ValueError("PopulationPPO.update: perm must be int64 [%d, %d, %d] (got %s)" % (P, int(epochs), n, tuple(perm.shape)))
-        chunk, n_chunks = chunk_split(n, minibatches)
-        steps = int(epochs) * n_chunks
-        self._ws(n, chunk)
-        extended = self.extended()
-        st = torch.empty((P, steps, N.PPO_EXT_STATS if extended else 4), dtype=torch.float32, device=dev) if stats else None
-        pop, h = self.population.to_native(), self.env._h
-        steps0 = self._steps0()
-        self._bind_adv_norm()
-        with torch.cuda.device(dev):
-            table = self._table(steps, steps0 if self.diverged() else None)
-            if extended:
-                ext, ext_table = self._ext(batch, K, n_env)
-                N.check(N.lib().ssg_pop_update_ext(h, C.byref(pop), C.byref(ext), C.c_void_p(table.data_ptr()), steps, K, *p,
-                                                   C.c_void_p(perm.data_ptr()), int(epochs), int(minibatches),
-                                                   C.c_void_p(self.adam_mv.data_ptr()), C.c_void_p(st.data_ptr()) if stats else None,
-                                                   C.c_void_p(self.workspace.data_ptr()), self.workspace.numel(), self._stream()), h,
-                        "ssg_pop_update_ext")
-                self._advance(steps0, [steps] * P)
-                return st
-            N.check(N.lib().ssg_pop_update(h, C.byref(pop), C.c_void_p(table.data_ptr()), steps, K, *p, C.c_void_p(perm.data_ptr()),
-                                           int(epochs), int(minibatches), C.c_void_p(self.adam_mv.data_ptr()),
-                                           C.c_void_p(st.data_ptr()) if stats else None, C.c_void_p(self.workspace.data_ptr()),
-                                           self.workspace.numel(), self._stream()), h, "ssg_pop_update")
-        self._advance(steps0, [steps] * P)
-        return st
-
-    def _update_sched(self, batch, perm, epochs, minibatches, stats, K, n_env, n):
-        """update() on per-member schedules (ssg_pop_update_sched).  n: the samples per member, or (slices bound) a list of P counts."""
-        torch = _torch()
-        P, dev, D = self.n_members, self.population.device, self.population.obs_dim
-        epochs = [int(e) for e in epochs] if isinstance(epochs, (list, tuple)) else [int(epochs)] * P
-        minibatches = [int(b) for b in minibatches] if isinstance(minibatches, (list, tuple)) else [int(minibatches)] * P
-        if len(epochs) != P or len(minibatches) != P:
-            raise ValueError("PopulationPPO.update: %d epochs and %d minibatches for %d members" % (len(epochs), len(minibatches), P))
-        if min(epochs) < 1 or min(minibatches) < 1:
-            raise ValueError("PopulationPPO.update: every member's epochs and minibatches must be >= 1")
-        p = [self._flat(batch, "obs", torch.float32, (K, n_env, D)), self._flat(batch, "act", torch.int32, (K, n_env)),
-             self._flat(batch, "logp", torch.float32, (K, n_env)), self._flat(batch, "adv", torch.float32, (K, n_env)),
-             self._flat(batch, "ret", torch.float32, (K, n_env))]
-        if isinstance(n, list):
-            if isinstance(perm, (list, tuple)):
-                if len(perm) != P or any(tuple(q.shape) != (max(epochs), n[m]) for m, q in enumerate(perm)):
-                    raise ValueError("PopulationPPO.update: perm must list %d tensors int64 [max(epochs) = %d, K*n_m] with K*n_m = %s"
-                                     % (P, max(epochs), n))
-                perm = torch.cat([q.to(device=dev, dtype=torch.int64).reshape(-1) for q in perm])
-            perm = perm.to(device=dev, dtype=torch.int64).contiguous()
+        if sliced:
             if perm.numel() != max(epochs) * sum(n):
                 raise ValueError("PopulationPPO.update: the flat perm must hold max(epochs) * sum(K*n_m) = %d indices (got %d)"
                                  % (max(epochs) * sum(n), perm.numel()))
-            n_max, c_max = max(n), max(chunk_split(n[m], minibatches[m])[0] for m in range(P))
-        else:
-            perm = perm.to(device=dev, dtype=torch.int64).contiguous()
+        elif sched:
             if tuple(perm.shape) != (P, max(epochs), n):
                 raise ValueError("PopulationPPO.update: perm must be int64 [%d, %d, %d] = [P, max(epochs), K*n] (got %s)"
                                  % (P, max(epochs), n, tuple(perm.shape)))
-            n_max, c_max = n, max(chunk_split(n, b)[0] for b in minibatches)
-        sched, steps, launches = self.pack_schedule(n, epochs, minibatches)
-        self._ws(n_max, c_max)
-        extended = self.extended()
-        st = torch.zeros((P, launches, N.PPO_EXT_STATS if extended else 4), dtype=torch.float32, device=dev) if stats else None
-        ep, mb = (C.c_int32 * P)(*epochs), (C.c_int32 * P)(*minibatches)
+        elif tuple(perm.shape) != (P, int(epochs), n):
+            raise ValueError("PopulationPPO.update: perm must be int64 [%d, %d, %d] (got %s)" % (P, int(epochs), n, tuple(perm.shape)))
         steps0 = self._steps0()
+        if sched:  # launches: the longest member's steps; a stats row past a member's own steps stays zero
+            table_sched, taken, launches = self.pack_schedule(n, epochs, minibatches)
+            self._ws(max(n) if sliced else n, max(chunk_split(n[m] if sliced else n, minibatches[m])[0] for m in range(P)))
+            table_steps0 = steps0
+        else:
+            chunk, n_chunks = chunk_split(n, minibatches)
+            launches = int(epochs) * n_chunks
+            taken = [launches] * P
+            self._ws(n, chunk)
+            table_steps0 = steps0 if self.diverged() else None
+        extended = self.extended()
+        st = None
+        if stats:
+            st = (torch.zeros if sched else torch.empty)((P, launches, N.PPO_EXT_STATS if extended else 4), dtype=torch.float32, device=dev)
         pop, h = self.population.to_native(), self.env._h
         self._bind_adv_norm()
         with torch.cuda.device(dev):
-            table = self._table(launches, steps0)
-            dev_sched = torch.frombuffer(sched, dtype=torch.int32).to(dev)  # (a copy: the host array is free after the call)
-            ext = ext_table = None
-            if extended:
-                ext, ext_table = self._ext(batch, K, n_env)
-            N.check(N.lib().ssg_pop_update_sched(h, C.byref(pop), C.byref(ext) if extended else None, C.c_void_p(table.data_ptr()),
-                                                 launches, C.c_void_p(dev_sched.data_ptr()), ep, mb, max(epochs), K, *p,
-                                                 C.c_void_p(perm.data_ptr()), C.c_void_p(self.adam_mv.data_ptr()),
-                                                 C.c_void_p(st.data_ptr()) if stats else None, C.c_void_p(self.workspace.data_ptr()),
-                                                 self.workspace.numel(), self._stream()), h, "ssg_pop_update_sched")
-        self._advance(steps0, steps)
+            table = self._table(launches, table_steps0)
+            if sched:
+                dev_sched = torch.frombuffer(table_sched, dtype=torch.int32).to(dev)  # (a copy: the host array is free after the call)
+            ext, ext_table = self._ext(batch, K, n_env) if extended else (None, None)
+            if sched:
+                name = "ssg_pop_update_sched"
+                args = (C.byref(ext) if extended else None, C.c_void_p(table.data_ptr()), launches, C.c_void_p(dev_sched.data_ptr()),
+                        (C.c_int32 * P)(*epochs), (C.c_int32 * P)(*minibatches), max(epochs), K, *p, C.c_void_p(perm.data_ptr()))
+            else:
+                name = "ssg_pop_update_ext" if extended else "ssg_pop_update"
+                args = ((C.byref(ext),) if extended else ()) + (C.c_void_p(table.data_ptr()), launches, K, *p, C.c_void_p(perm.data_ptr()),
+                                                                 int(epochs), int(minibatches))
+            N.check(getattr(N.lib(), name)(h, C.byref(pop), *args, C.c_void_p(self.adam_mv.data_ptr()),
+                                           C.c_void_p(st.data_ptr()) if stats else None, C.c_void_p(self.workspace.data_ptr()),
+                                           self.workspace.numel(), self._stream()), h, name)
+        self._advance(steps0, taken)
         return st
 
     def exploit(self, src):

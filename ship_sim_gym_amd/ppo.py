@@ -242,13 +242,44 @@ def host_perm(seed, update, member, epoch, n, first=0, count=None):
     return out[:count]
 
 
-class NativePPO(object):
+def load_packed(row, net, mismatch):
+    """Copy the packed parameters `row` into `net` (its parameters in torch.cat order); mismatch % (the module's count): the ValueError."""
+    params = list(net.parameters())
+    if sum(q.numel() for q in params) != row.numel():
+        raise ValueError(mismatch % sum(q.numel() for q in params))
+    o = 0
+    with _torch().no_grad():
+        for q in params:
+            q.copy_(row[o: o + q.numel()].view_as(q))
+            o += q.numel()
+    return net
+
+
+class DeviceTrainer(object):
+    """What NativePPO and PopulationPPO share: ``workspace`` on ``_device``, its growth and the current stream."""
+
+    def _grow(self, query, record, n_samples, max_minibatch, head):
+        """The workspace, grown to what `query` asks for the record and the sizes; its first `head` bytes (gae()'s statistics) are kept."""
+        need = C.c_size_t()
+        N.check(getattr(N.lib(), query)(C.byref(record), int(n_samples), int(max_minibatch), C.byref(need)), None, query)
+        if self.workspace.numel() < need.value:
+            ws = _torch().zeros(need.value + 256, dtype=_torch().uint8, device=self._device)
+            if self.workspace.numel():
+                ws[:head].copy_(self.workspace[:head])
+            self.workspace = ws
+        return self.workspace
+
+    def _stream(self):
+        return C.c_void_p(_torch().cuda.current_stream(self._device).cuda_stream)
+
+
+class NativePPO(DeviceTrainer):
     """Defaults: train/ppo_torch.py's (Adam lr 3e-4, betas (0.9, 0.999), eps 1e-8; clip 0.2; loss pg + 0.5*vf - 0.01*entropy)."""
 
     def __init__(self, policy, env, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, clip=0.2, vf_coef=0.5, ent_coef=0.01, adv_eps=1e-8,
                  vf_clip=0.0, max_grad_norm=0.0, kl_coef=0.0, kl_target=0.0, adv_norm="batch", perm_seed=None, member=0):
         torch = _torch()
-        self.policy, self.env = policy, env
+        self.policy, self.env, self._device = policy, env, policy.device
         # the key of the permutations the library draws (draw_perm; update(perm=None)): the seed (None: the caller brings every perm),
         # the member this object stands for (a population member's twin passes its index) and the update() calls so far
         self.perm_seed = None if perm_seed is None else int(perm_seed)
@@ -279,24 +310,11 @@ class NativePPO(object):
     def _ws(self, n_samples, max_minibatch):
         """The workspace, grown to serve n_samples and minibatches of max_minibatch (its first 16 bytes — the advantage
         statistics ssg_ppo_gae left — are kept when it grows)."""
-        torch = _torch()
-        need = C.c_size_t()
-        pol = self.policy.to_native()
-        N.check(N.lib().ssg_ppo_workspace_nbytes(C.byref(pol), int(n_samples), int(max_minibatch), C.byref(need)), None,
-                "ssg_ppo_workspace_nbytes")
-        if self.workspace.numel() < need.value:
-            ws = torch.zeros(need.value + 256, dtype=torch.uint8, device=self.policy.device)
-            if self.workspace.numel():
-                ws[:16].copy_(self.workspace[:16])
-            self.workspace = ws
-        return self.workspace
+        return self._grow("ssg_ppo_workspace_nbytes", self.policy.to_native(), n_samples, max_minibatch, 16)
 
     def _ws_ptr(self):
         # (torch's allocations are 256-byte aligned; the header requires it)
         return C.c_void_p(self.workspace.data_ptr()), self.workspace.numel()
-
-    def _stream(self):
-        return C.c_void_p(_torch().cuda.current_stream(self.policy.device).cuda_stream)
 
     def _flat(self, batch, key, dtype):
         t = batch[key]
@@ -353,6 +371,18 @@ class NativePPO(object):
             ext.dev_value_old = val.data_ptr()
         return ext
 
+    def _call(self, name, batch, n, *args):
+        """The gradient / update entry point `name` or, with an extended term on, its _ext form, which takes the ssg_ppo_ext record
+        behind the hyper-parameters; args: what the entry point takes between n and the workspace."""
+        ws, nb = self._ws_ptr()
+        pol, h = self.policy.to_native(), self.env._h
+        self._bind_adv_norm()
+        with _torch().cuda.device(self.policy.device):
+            ext = ()
+            if self.extended():
+                name, ext = name + "_ext", (C.byref(self._ext(batch, n)),)
+            N.check(getattr(N.lib(), name)(h, C.byref(pol), C.byref(self.hp), *ext, n, *args, ws, nb, self._stream()), h, name)
+
     # ------------------------------------------------------------------------------------------------
     def gae(self, batch, gamma=0.99, lam=0.95, return_filter=None):
         """GAE over the rollout batch (train/ppo_torch.py's loop, bitwise): returns (adv, ret) f32 [K, N] and stores them in the batch
@@ -395,18 +425,19 @@ class NativePPO(object):
         """(Re)bind this object's mode on the env (host only): two trainers on one env cannot inherit each other's."""
         self.env.set_adv_norm(self._adv_mode, self._adv_scratch, 1)
 
+    def _adv_views(self, who):
+        if self._adv_scratch is None:
+            raise ValueError("NativePPO.%s: adv_norm is %r" % (who, self.adv_norm))
+        return adv_norm_views(self._adv_scratch, 1)
+
     def minibatch_adv_stats(self):
         """f32 [1, 4] device view of the scratch: {mean, std + adv_eps, its inverse, 0} of the LAST minibatch a grad() / update() call
         of this object normalised by (adv_norm="minibatch" only)."""
-        if self._adv_scratch is None:
-            raise ValueError("NativePPO.minibatch_adv_stats: adv_norm is %r" % (self.adv_norm,))
-        return adv_norm_views(self._adv_scratch, 1)[0]
+        return self._adv_views("minibatch_adv_stats")[0]
 
     def minibatch_adv_partials(self):
         """f64 [1, 64, 3] device view of the scratch: the (s, q, c) partial sums of that last minibatch (adv_norm_views)."""
-        if self._adv_scratch is None:
-            raise ValueError("NativePPO.minibatch_adv_partials: adv_norm is %r" % (self.adv_norm,))
-        return adv_norm_views(self._adv_scratch, 1)[1]
+        return self._adv_views("minibatch_adv_partials")[1]
 
     def grad(self, batch, idx, stats=False):
         """The gradient (f32 [P], the packed layout) of the PPO loss over the samples idx (int64) of a batch gae() has seen; with
@@ -420,18 +451,8 @@ class NativePPO(object):
         g = torch.empty(self.n_params, dtype=torch.float32, device=self.policy.device)
         ncol = N.PPO_EXT_STATS if self.extended() else 4
         st = torch.empty(ncol, dtype=torch.float32, device=self.policy.device) if stats else None
-        ws, nb = self._ws_ptr()
-        pol, h = self.policy.to_native(), self.env._h
-        self._bind_adv_norm()
-        with torch.cuda.device(self.policy.device):
-            if self.extended():
-                ext = self._ext(batch, n)
-                N.check(N.lib().ssg_ppo_grad_ext(h, C.byref(pol), C.byref(self.hp), C.byref(ext), n, *p, C.c_void_p(idx.data_ptr()), M,
-                                                 C.c_void_p(g.data_ptr()), C.c_void_p(st.data_ptr()) if stats else None, ws, nb,
-                                                 self._stream()), h, "ssg_ppo_grad_ext")
-                return (g, st) if stats else g
-            N.check(N.lib().ssg_ppo_grad(h, C.byref(pol), C.byref(self.hp), n, *p, C.c_void_p(idx.data_ptr()), M, C.c_void_p(g.data_ptr()),
-                                         C.c_void_p(st.data_ptr()) if stats else None, ws, nb, self._stream()), h, "ssg_ppo_grad")
+        self._call("ssg_ppo_grad", batch, n, *p, C.c_void_p(idx.data_ptr()), M, C.c_void_p(g.data_ptr()),
+                   C.c_void_p(st.data_ptr()) if stats else None)
         return (g, st) if stats else g
 
     def adam_step(self, grad):
@@ -482,35 +503,12 @@ class NativePPO(object):
         self._ws(n, chunk)
         ncol = N.PPO_EXT_STATS if self.extended() else 4
         st = torch.empty((int(epochs) * n_chunks, ncol), dtype=torch.float32, device=self.policy.device) if stats else None
-        ws, nb = self._ws_ptr()
-        pol, h = self.policy.to_native(), self.env._h
-        self._bind_adv_norm()
-        with torch.cuda.device(self.policy.device):
-            if self.extended():
-                ext = self._ext(batch, n)
-                N.check(N.lib().ssg_ppo_update_ext(h, C.byref(pol), C.byref(self.hp), C.byref(ext), n, *p, C.c_void_p(perm.data_ptr()),
-                                                   int(epochs), int(minibatches), C.c_void_p(self.adam_mv.data_ptr()), self.step,
-                                                   C.c_void_p(st.data_ptr()) if stats else None, ws, nb, self._stream()), h,
-                        "ssg_ppo_update_ext")
-                self.step += int(epochs) * n_chunks
-                self.updates += 1
-                return st
-            N.check(N.lib().ssg_ppo_update(h, C.byref(pol), C.byref(self.hp), n, *p, C.c_void_p(perm.data_ptr()), int(epochs),
-                                           int(minibatches), C.c_void_p(self.adam_mv.data_ptr()), self.step,
-                                           C.c_void_p(st.data_ptr()) if stats else None, ws, nb, self._stream()), h, "ssg_ppo_update")
+        self._call("ssg_ppo_update", batch, n, *p, C.c_void_p(perm.data_ptr()), int(epochs), int(minibatches),
+                   C.c_void_p(self.adam_mv.data_ptr()), self.step, C.c_void_p(st.data_ptr()) if stats else None)
         self.step += int(epochs) * n_chunks
         self.updates += 1
         return st
 
     def load_into(self, net):
         """Copy the packed parameters into `net` (shaped like the policy: its parameters in torch.cat order)."""
-        torch = _torch()
-        params = list(net.parameters())
-        if sum(q.numel() for q in params) != self.n_params:
-            raise ValueError("NativePPO.load_into: the module has %d parameters, the policy %d" % (sum(q.numel() for q in params), self.n_params))
-        o = 0
-        with torch.no_grad():
-            for q in params:
-                q.copy_(self.policy.params[o: o + q.numel()].view_as(q))
-                o += q.numel()
-        return net
+        return load_packed(self.policy.params, net, "NativePPO.load_into: the module has %%d parameters, the policy %d" % self.n_params)
