@@ -171,28 +171,28 @@ __global__ void __launch_bounds__(256) adv_norm_final_kernel(const AdvNormArgs a
 
 hipError_t launch_adv_norm(const AdvNormLaunch &l, hipStream_t stream)
 {
-    if (!l.stats || !l.part || l.members < 1) return hipErrorInvalidValue;
+    if (!l.stats || !l.part || l.lay.members < 1) return hipErrorInvalidValue;
     AdvNormArgs a;
     a.adv = l.adv;
     a.idx = l.idx;
     a.M = l.M;
     a.n_samples = l.n_samples;
     a.pop = l.table != nullptr;
-    a.n = l.n;
+    a.n = l.lay.n;
     a.N = l.N;
     a.idx_stride = l.idx_stride;
     a.table = l.table;
     a.adv_eps_col = l.adv_eps_col;
     a.adv_eps = l.adv_eps;
     a.sched = l.sched;
-    a.slices = l.slices;
+    a.slices = l.lay.slices;
     a.sched_hdr = l.sched_hdr;
     a.K = l.K;
     a.perm_epochs = l.perm_epochs;
     a.part = l.part;
     a.stats = l.stats;
-    hipLaunchKernelGGL(adv_norm_partial_kernel, dim3(kAdvNormBlocks, (unsigned)l.members), dim3(256), 0, stream, a);
-    hipLaunchKernelGGL(adv_norm_final_kernel, dim3((unsigned)l.members), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(adv_norm_partial_kernel, dim3(kAdvNormBlocks, (unsigned)l.lay.members), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(adv_norm_final_kernel, dim3((unsigned)l.lay.members), dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 

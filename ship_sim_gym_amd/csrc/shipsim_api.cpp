@@ -1022,6 +1022,28 @@ static int prepare_policy(ssg_handle *h)
     return SSG_OK;
 }
 
+// The resolver of ssg::MemberLayout (shipsim_internal.h), in two parts; every entry point takes its layout from one of them and hands it
+// down as it is.  P members (1..SSG_POP_MAX_MEMBERS: the caller's range check) against the handle: the table bound to it
+// (ssg_pop_set_slices), which must be for P members, else the equal split — which the envs must allow where the call launches on it
+// (equal_split; ssg_set_obs_filter binds and ssg_pop_perm draws without asking).
+static int member_layout(ssg_handle *h, int P, const char *what, bool equal_split, ssg::MemberLayout &lay)
+{
+    char buf[200];
+    const int bound = (int)h->pop_sizes.size(), N = h->cfg.n_envs;
+    if (bound && bound != P)
+        std::snprintf(buf, sizeof buf, ": %d members, but slices for %d members are bound to the handle (ssg_pop_set_slices)", P, bound);
+    else if (!bound && equal_split && N % P != 0)
+        std::snprintf(buf, sizeof buf, ": the handle's %d envs do not split into %d equal member slices", N, P);
+    else {
+        lay = bound ? ssg::MemberLayout{P, h->slice_max, h->dev_slices} : ssg::MemberLayout{P, N / P, nullptr};
+        return SSG_OK;
+    }
+    return fail(h, SSG_ERR_BAD_ARG, std::string(what) + buf);
+}
+
+// ... and one policy on the whole handle, whatever is bound
+static ssg::MemberLayout whole_layout(const ssg_handle *h) { return {1, h->cfg.n_envs, nullptr}; }
+
 // ABI 9 addition: the observation filter.  The record against the handle: everything ssg_set_obs_filter refuses.
 static int check_filter(ssg_handle *h, const ssg_obs_filter *f, const char *what)
 {
@@ -1035,11 +1057,9 @@ static int check_filter(ssg_handle *h, const ssg_obs_filter *f, const char *what
         return fail(h, SSG_ERR_BAD_ARG, w + buf);
     }
     if (f->n_members < 1 || f->n_members > SSG_POP_MAX_MEMBERS) return fail(h, SSG_ERR_BAD_ARG, w + ": n_members must be in 1..SSG_POP_MAX_MEMBERS");
-    if (!h->pop_sizes.empty() && (int)h->pop_sizes.size() != f->n_members) {
-        std::snprintf(buf, sizeof buf, ": %d members, but slices for %d members are bound to the handle (ssg_pop_set_slices)", f->n_members,
-                      (int)h->pop_sizes.size());
-        return fail(h, SSG_ERR_BAD_ARG, w + buf);
-    }
+    ssg::MemberLayout lay; // (a table bound for another member count; whether the envs split equally is the launching call's question)
+    const int rc = member_layout(h, f->n_members, what, false, lay);
+    if (rc != SSG_OK) return rc;
     if (!(f->clip >= 0.0) || !(f->eps >= 0.0)) return fail(h, SSG_ERR_BAD_ARG, w + ": clip and eps must be >= 0 (and not NaN)");
     if (!f->dev_state || !f->dev_workspace) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_state or dev_workspace");
     const size_t need = ssg::filter_workspace_bytes(h->cfg.n_envs, D, f->n_members);
@@ -1254,39 +1274,18 @@ static bool pop_shape_ok(const ssg_population *pop)
     return check_policy_shape(&p) != 0;
 }
 
-// P members against the handle's layout: the slices bound to it (ssg_pop_set_slices), else the equal split
-static int check_members(ssg_handle *h, int P, const char *what)
-{
-    char buf[200];
-    if (!h->pop_sizes.empty()) {
-        if ((int)h->pop_sizes.size() == P) return SSG_OK;
-        std::snprintf(buf, sizeof buf, ": %d members, but slices for %d members are bound to the handle (ssg_pop_set_slices)", P,
-                      (int)h->pop_sizes.size());
-        return fail(h, SSG_ERR_BAD_ARG, std::string(what) + buf);
-    }
-    if (h->cfg.n_envs % P != 0) {
-        std::snprintf(buf, sizeof buf, ": the handle's %d envs do not split into %d equal member slices", h->cfg.n_envs, P);
-        return fail(h, SSG_ERR_BAD_ARG, std::string(what) + buf);
-    }
-    return SSG_OK;
-}
-
-// the record against the handle: shape, member count, pointers
-static int check_population(ssg_handle *h, const ssg_population *pop, const char *what)
+// the record against the handle: shape, member count (lay: its layout), pointers
+static int check_population(ssg_handle *h, const ssg_population *pop, const char *what, ssg::MemberLayout &lay)
 {
     const std::string w(what);
     if (!pop) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL population");
     if (pop->struct_size != sizeof(ssg_population)) return fail(h, SSG_ERR_BAD_ARG, w + ": ssg_population.struct_size != sizeof(ssg_population)");
     if (pop->n_members < 1 || pop->n_members > SSG_POP_MAX_MEMBERS) return fail(h, SSG_ERR_BAD_ARG, w + ": n_members must be in 1..SSG_POP_MAX_MEMBERS");
-    const int rc = check_members(h, pop->n_members, what);
+    const int rc = member_layout(h, pop->n_members, what, true, lay);
     if (rc != SSG_OK) return rc;
     const ssg_policy p = pop_policy(*pop);
     return check_policy(h, &p, what);
 }
-
-// the slices table for a population that passed check_members (NULL: equal slices), and the launch's width
-static const int32_t *pop_slices(const ssg_handle *h) { return h->pop_sizes.empty() ? nullptr : h->dev_slices; }
-static int pop_width(const ssg_handle *h, int P) { return h->pop_sizes.empty() ? h->cfg.n_envs / P : h->slice_max; }
 
 int ssg_ppo_dist(ssg_handle *h, const ssg_policy *pol, int64_t n_samples, const float *dev_x, float *dev_logp_all, void *stream)
 {
@@ -1298,7 +1297,8 @@ int ssg_ppo_dist(ssg_handle *h, const ssg_policy *pol, int64_t n_samples, const 
     rc = check_ready(h, false);
     if (rc == SSG_OK) rc = prepare_policy(h);
     if (rc != SSG_OK) return rc;
-    hipError_t e = ssg::launch_policy_dist(*pol, 1, (int)n_samples, n_samples, 1, dev_x, dev_logp_all, static_cast<hipStream_t>(stream));
+    // (one policy over n_samples stored rows, which need not be the handle's envs)
+    hipError_t e = ssg::launch_policy_dist(*pol, {1, (int)n_samples, nullptr}, n_samples, 1, dev_x, dev_logp_all, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("policy dist launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
@@ -1307,34 +1307,33 @@ int ssg_ppo_dist(ssg_handle *h, const ssg_policy *pol, int64_t n_samples, const 
 // are the only places that know the difference; what: the entry point's name, for its messages.
 struct PolicyCall {
     ssg_policy pol; // (a population's: the shared shape over its parameter rows)
-    int members;    // 0: one policy
-    int n;          // the launch's width: the envs, or the widest slice
-    const int32_t *slices;
+    ssg::MemberLayout lay;
+    bool pop;
     const char *what;
 };
 
 static int one_policy_call(ssg_handle *h, const ssg_policy *pol, const char *what, PolicyCall &c)
 {
     const int rc = check_policy(h, pol, what);
-    if (rc == SSG_OK) c = {*pol, 0, h->cfg.n_envs, nullptr, what};
+    if (rc == SSG_OK) c = {*pol, whole_layout(h), false, what};
     return rc;
 }
 
 static int population_call(ssg_handle *h, const ssg_population *pop, const char *what, PolicyCall &c)
 {
+    ssg::MemberLayout lay;
     int rc = pop_bound(h);
-    if (rc == SSG_OK) rc = check_population(h, pop, what);
-    if (rc == SSG_OK) c = {pop_policy(*pop), pop->n_members, pop_width(h, pop->n_members), pop_slices(h), what};
+    if (rc == SSG_OK) rc = check_population(h, pop, what, lay);
+    if (rc == SSG_OK) c = {pop_policy(*pop), lay, true, what};
     return rc;
 }
 
 // the call's member count must be the bound observation filter's, if one is bound
 static int check_filter_members(ssg_handle *h, const PolicyCall &c)
 {
-    const int members = c.members ? c.members : 1;
-    if (!h->flt.struct_size || h->flt.n_members == members) return SSG_OK;
+    if (!h->flt.struct_size || h->flt.n_members == c.lay.members) return SSG_OK;
     char buf[200];
-    std::snprintf(buf, sizeof buf, ": the bound observation filter has %d members, this call %d (ssg_set_obs_filter)", h->flt.n_members, members);
+    std::snprintf(buf, sizeof buf, ": the bound observation filter has %d members, this call %d (ssg_set_obs_filter)", h->flt.n_members, c.lay.members);
     return fail(h, SSG_ERR_BAD_ARG, std::string(c.what) + buf);
 }
 
@@ -1344,9 +1343,8 @@ static hipError_t policy_launch(ssg_handle *h, const PolicyCall &c, ssg::PolicyL
 {
     const ssg::ObsFilterArgs f = {h->flt.dev_state, h->flt.clip};
     l.policy = &c.pol;
-    l.members = c.members;
-    l.n = c.n;
-    l.slices = c.slices;
+    l.lay = c.lay;
+    l.pop = c.pop;
     l.env_base = h->cfg.env_id_base;
     l.filter = h->flt.struct_size ? &f : nullptr;
     return ssg::launch_policy(l, st);
@@ -1354,7 +1352,7 @@ static hipError_t policy_launch(ssg_handle *h, const PolicyCall &c, ssg::PolicyL
 
 static int policy_launch_failed(ssg_handle *h, const PolicyCall &c, hipError_t e)
 {
-    return fail(h, SSG_ERR_HIP, std::string(c.members ? "population policy launch: " : "policy launch: ") + hipGetErrorString(e));
+    return fail(h, SSG_ERR_HIP, std::string(c.pop ? "population policy launch: " : "policy launch: ") + hipGetErrorString(e));
 }
 
 // the rollout loop's merge of the current observation rows ahead of a step's policy launch: only with SSG_FILTER_UPDATE bound
@@ -1362,7 +1360,7 @@ static hipError_t filter_step_update(ssg_handle *h, const PolicyCall &c, const d
 {
     const ssg_obs_filter &f = h->flt;
     if (!f.struct_size || !(f.flags & SSG_FILTER_UPDATE)) return hipSuccess;
-    return ssg::launch_filter_update(obs, f.obs_dim, f.n_members, c.n, c.slices, f.eps, f.dev_state, f.dev_workspace, st);
+    return ssg::launch_filter_update(obs, f.obs_dim, c.lay, f.eps, f.dev_state, f.dev_workspace, st); // (check_filter_members: the filter's members are the call's)
 }
 
 // What a loop of policy launches and steps asks last, once the host has judged the entry point's own arguments: the filter's member
@@ -1436,9 +1434,8 @@ static hipError_t timeout_launch(ssg_handle *h, const PolicyCall &c, int K, cons
     const ssg::ObsFilterArgs f = {h->flt.dev_state, h->flt.clip};
     ssg::PolicyLaunch l = {};
     l.policy = &c.pol;
-    l.members = c.members;
-    l.n = c.n;
-    l.slices = c.slices;
+    l.lay = c.lay;
+    l.pop = c.pop;
     l.filter = h->flt.struct_size ? &f : nullptr;
     return ssg::launch_timeout_values(l, {K, h->cfg.n_envs, (size_t)stride, flags, term_obs, boot}, st);
 }
@@ -1579,20 +1576,20 @@ static int pop_gae(ssg_handle *h, const ssg_population *pop, const float *dev_ta
                    float *dev_adv_KN, float *dev_ret_KN, void *dev_workspace, size_t workspace_nbytes, void *stream, const char *what)
 {
     const std::string w(what);
+    ssg::MemberLayout lay;
     int rc = pop_bound(h);
-    if (rc == SSG_OK) rc = check_population(h, pop, what);
+    if (rc == SSG_OK) rc = check_population(h, pop, what, lay);
     if (rc != SSG_OK) return rc;
     if (!dev_table || !dev_reward_KN || !dev_done_KN || !dev_value_KN || !dev_last_value || !dev_adv_KN || !dev_ret_KN)
         return fail(h, SSG_ERR_BAD_ARG, w + ": NULL table, reward, done, value, last value, adv or ret buffer");
     if (with_boot && !dev_boot_KN) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_boot_KN");
-    const int P = pop->n_members, N = h->cfg.n_envs, n = pop_width(h, P), n_min = pop_slices(h) ? h->slice_min : n;
-    if (K < 1 || (long long)K * n_min < 2)
+    if (K < 1 || (long long)K * (lay.slices ? h->slice_min : lay.n) < 2)
         return fail(h, SSG_ERR_BAD_ARG, w + ": K must be >= 1 and K * (a member's envs) >= 2 for every member");
-    rc = check_workspace(h, dev_workspace, workspace_nbytes, pop_need_gae(P, n), what);
+    rc = check_workspace(h, dev_workspace, workspace_nbytes, pop_need_gae(lay.members, lay.n), what);
     if (rc == SSG_OK) rc = check_ready(h, false);
     if (rc != SSG_OK) return rc;
-    hipError_t e = ssg::launch_pop_gae(P, K, N, dev_table, dev_reward_KN, dev_done_KN, dev_value_KN, dev_last_value, dev_adv_KN, dev_ret_KN,
-                                       dev_workspace, static_cast<hipStream_t>(stream), pop_slices(h), n, with_boot ? dev_boot_KN : nullptr);
+    hipError_t e = ssg::launch_pop_gae(lay, K, h->cfg.n_envs, dev_table, dev_reward_KN, dev_done_KN, dev_value_KN, dev_last_value,
+                                       with_boot ? dev_boot_KN : nullptr, dev_adv_KN, dev_ret_KN, dev_workspace, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population gae launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
@@ -1615,17 +1612,16 @@ int ssg_pop_gae_boot(ssg_handle *h, const ssg_population *pop, const float *dev_
 
 int ssg_pop_dist(ssg_handle *h, const ssg_population *pop, int K, const float *dev_x, float *dev_logp_all, void *stream)
 {
+    ssg::MemberLayout lay;
     int rc = pop_bound(h);
-    if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_dist");
+    if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_dist", lay);
     if (rc != SSG_OK) return rc;
     if (!dev_x || !dev_logp_all) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_dist: NULL dev_x or dev_logp_all");
     if (K < 1 || K > 65535) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_dist: K must be in 1..65535");
     rc = check_ready(h, false);
     if (rc == SSG_OK) rc = prepare_policy(h);
     if (rc != SSG_OK) return rc;
-    const int P = pop->n_members, N = h->cfg.n_envs;
-    hipError_t e = ssg::launch_policy_dist(pop_policy(*pop), P, pop_width(h, P), N, K, dev_x, dev_logp_all, static_cast<hipStream_t>(stream),
-                                           pop_slices(h));
+    hipError_t e = ssg::launch_policy_dist(pop_policy(*pop), lay, h->cfg.n_envs, K, dev_x, dev_logp_all, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population dist launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
@@ -1901,7 +1897,7 @@ static int one_policy_update(ssg_handle *h, const ssg_policy *pol, const ssg_ppo
     }
     c.pol = *pol;
     c.mb.policy = &c.pol;
-    c.mb.members = 1;
+    c.mb.lay = whole_layout(h);
     c.mb.n_samples = n_samples;
     c.mb.slots_off = ssg::kPpoSlotsOff;
     c.mb.hp = hp;
@@ -1949,12 +1945,12 @@ static int population_update(ssg_handle *h, const ssg_population *pop, const ssg
 {
     const std::string w(c.what);
     int rc = pop_bound(h);
-    if (rc == SSG_OK) rc = check_population(h, pop, c.what);
+    if (rc == SSG_OK) rc = check_population(h, pop, c.what, c.mb.lay);
     if (rc == SSG_OK && c.ext) rc = check_pop_ext(h, ext, c.what);
     if (rc != SSG_OK) return rc;
     if (K < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": K < 1");
     const int P = pop->n_members, N = h->cfg.n_envs;
-    const int32_t *slices = pop_slices(h);
+    const int32_t *slices = c.mb.lay.slices;
     if (slices && !c.sched)
         return fail(h, SSG_ERR_BAD_ARG, w + ": slices are bound to the handle (ssg_pop_set_slices): the update runs through ssg_pop_update_sched");
     long long n = (long long)K * (N / P); // samples per member (unequal slices: the widest member's, below)
@@ -1962,7 +1958,6 @@ static int population_update(ssg_handle *h, const ssg_population *pop, const ssg
     if (rc == SSG_OK) rc = check_adv_norm_members(h, P, c.what);
     if (rc != SSG_OK) return rc;
     if (!dev_table || !c.mb.adam_mv) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_table or dev_adam_mv");
-    c.mb.n = N / P;
     if (!c.sched) {
         if (c.epochs < 1 || c.minibatches < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": epochs < 1 or minibatches < 1");
         if ((long long)table_steps < (long long)c.epochs * chunking(n, c.minibatches).chunks)
@@ -1976,11 +1971,9 @@ static int population_update(ssg_handle *h, const ssg_population *pop, const ssg
         std::vector<int64_t> samples;
         if (slices) {
             for (int32_t n_m : h->pop_sizes) samples.push_back((int64_t)K * n_m);
-            c.mb.slices = slices;
             c.mb.sched_hdr = dev_sched;
             c.mb.K = K;
             c.mb.perm_epochs = perm_epochs;
-            c.mb.n = 0;
             n = *std::max_element(samples.begin(), samples.end());
         }
         if (!pop_schedule(P, n, epochs, minibatches, nullptr, nullptr, &c.sc.n_launches, &c.sc.Cmax, samples.empty() ? nullptr : samples.data()))
@@ -1991,7 +1984,6 @@ static int population_update(ssg_handle *h, const ssg_population *pop, const ssg
     }
     c.pol = pop_policy(*pop);
     c.mb.policy = &c.pol;
-    c.mb.members = P;
     c.mb.N = N;
     c.mb.n_samples = n;
     c.mb.slots_off = ssg::kPopSlotsOff;
@@ -2025,7 +2017,7 @@ static int run_update(ssg_handle *h, UpdateCall &c, hipStream_t st)
     for (long long j = 0; j < launches; ++j) {
         if (sched) {
             mb.M = sched->Cmax;
-            mb.sched = sched->dev_sched + (size_t)(1 + j) * (size_t)mb.members * ssg::kPopSchedRow;
+            mb.sched = sched->dev_sched + (size_t)(1 + j) * (size_t)mb.lay.members * ssg::kPopSchedRow;
         } else {
             const long long ep = j / ck.chunks, b0 = (j - ep * ck.chunks) * ck.C;
             mb.M = std::min(ck.C, n - b0);
@@ -2034,12 +2026,12 @@ static int run_update(ssg_handle *h, UpdateCall &c, hipStream_t st)
         }
         mb.stats_out = stats ? stats + cols * j : nullptr;
         ++mb.step;
-        if (mb.table) mb.adam_row = mb.table + (size_t)(1 + j) * (size_t)mb.members * ssg::kPopTableRow;
+        if (mb.table) mb.adam_row = mb.table + (size_t)(1 + j) * (size_t)mb.lay.members * ssg::kPopTableRow;
         hipError_t e = ssg::launch_ppo_minibatch(mb, st);
         if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string(c.launch) + " launch: " + hipGetErrorString(e));
     }
     if (c.kl_adapt) {
-        hipError_t e = ssg::launch_kl_adapt(mb.members, *ext, c.kl_target, ssg::ppo_packed_len(c.pol), ck.chunks,
+        hipError_t e = ssg::launch_kl_adapt(mb.lay.members, *ext, c.kl_target, ssg::ppo_packed_len(c.pol), ck.chunks,
                                             sched ? sched->dev_sched : nullptr, mb.ws, mb.slots_off, st);
         if (e != hipSuccess)
             return fail(h, SSG_ERR_HIP, std::string(mb.table ? "population kl adapt launch: " : "kl adapt launch: ") + hipGetErrorString(e));
@@ -2052,7 +2044,7 @@ static int run_update(ssg_handle *h, UpdateCall &c, hipStream_t st)
 static int update_call(ssg_handle *h, UpdateCall &c, void *stream)
 {
     const long long M = !c.loop ? c.mb.M : c.sched ? c.sc.Cmax : chunking(c.mb.n_samples, c.minibatches).C;
-    int rc = check_workspace(h, c.mb.ws, c.ws_nbytes, need_grad(c.mb.slots_off, c.mb.members, c.pol, M, c.ext), c.what);
+    int rc = check_workspace(h, c.mb.ws, c.ws_nbytes, need_grad(c.mb.slots_off, c.mb.lay.members, c.pol, M, c.ext), c.what);
     if (rc == SSG_OK && !c.device_checked) rc = check_ready(h, false);
     if (rc == SSG_OK) rc = prepare_ppo(h);
     if (rc != SSG_OK) return rc;
@@ -2187,8 +2179,9 @@ int ssg_pop_update_sched(ssg_handle *h, const ssg_population *pop, const ssg_pop
 
 int ssg_pop_exploit(ssg_handle *h, const ssg_population *pop, const int32_t *src, float *dev_adam_mv, void *stream)
 {
+    ssg::MemberLayout lay;
     int rc = pop_bound(h);
-    if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_exploit");
+    if (rc == SSG_OK) rc = check_population(h, pop, "ssg_pop_exploit", lay);
     if (rc != SSG_OK) return rc;
     if (!src || !dev_adam_mv) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_exploit: NULL src or dev_adam_mv");
     const int P = pop->n_members;
@@ -2210,14 +2203,15 @@ int ssg_pop_episode_stats(ssg_handle *h, int n_members, int K, const double *dev
     if (rc != SSG_OK) return rc;
     if (n_members < 1 || n_members > SSG_POP_MAX_MEMBERS)
         return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_episode_stats: n_members must be in 1..SSG_POP_MAX_MEMBERS and divide the handle's n_envs");
-    rc = check_members(h, n_members, "ssg_pop_episode_stats");
+    ssg::MemberLayout lay;
+    rc = member_layout(h, n_members, "ssg_pop_episode_stats", true, lay);
     if (rc != SSG_OK) return rc;
     if (K < 1 || !dev_reward_KN || !dev_done_KN || !dev_carry_return || !dev_carry_length || !dev_out)
         return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_episode_stats: K < 1 or a NULL buffer");
     rc = check_ready(h, false);
     if (rc != SSG_OK) return rc;
-    hipError_t e = ssg::launch_pop_episode_stats(n_members, K, h->cfg.n_envs, dev_reward_KN, dev_done_KN, dev_carry_return,
-                                                 dev_carry_length, dev_out, static_cast<hipStream_t>(stream), pop_slices(h), pop_width(h, n_members));
+    hipError_t e = ssg::launch_pop_episode_stats(lay, K, h->cfg.n_envs, dev_reward_KN, dev_done_KN, dev_carry_return, dev_carry_length, dev_out,
+                                                 static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("population episode stats launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
@@ -2415,15 +2409,12 @@ int ssg_pop_perm(ssg_handle *h, uint64_t seed, int64_t update, int members, int 
     l.epochs = perm_epochs;
     l.K = K;
     l.out = dev_perm;
-    if (!h->pop_sizes.empty()) {
-        if ((int)h->pop_sizes.size() != members) {
-            char buf[200];
-            std::snprintf(buf, sizeof buf, "ssg_pop_perm: %d members, but slices for %d members are bound to the handle (ssg_pop_set_slices)", members,
-                          (int)h->pop_sizes.size());
-            return fail(h, SSG_ERR_BAD_ARG, buf);
-        }
-        l.slices = h->dev_slices;
-        l.n = (long long)K * h->slice_max; // (the widest row; n is not read)
+    ssg::MemberLayout lay; // (no table bound: the caller's n, which need not be an equal split of the handle's envs)
+    const int rc = member_layout(h, members, "ssg_pop_perm", false, lay);
+    if (rc != SSG_OK) return rc;
+    if (lay.slices) {
+        l.slices = lay.slices;
+        l.n = (long long)K * lay.n; // (the widest row; n is not read)
     } else {
         if (n < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_perm: n < 1");
         l.n = (long long)K * n;
@@ -2440,15 +2431,11 @@ int ssg_obs_filter_update(ssg_handle *h, const ssg_obs_filter *f, const double *
     rc = check_filter(h, f, "ssg_obs_filter_update");
     if (rc != SSG_OK) return rc;
     if (!dev_obs) return fail(h, SSG_ERR_BAD_ARG, "ssg_obs_filter_update: NULL dev_obs");
-    const int P = f->n_members;
-    if (P > 1) {
-        rc = check_members(h, P, "ssg_obs_filter_update");
-        if (rc != SSG_OK) return rc;
-    }
-    rc = check_ready(h, false);
+    ssg::MemberLayout lay = whole_layout(h); // (one member: the whole handle, and the envs' split is not asked)
+    if (f->n_members > 1) rc = member_layout(h, f->n_members, "ssg_obs_filter_update", true, lay);
+    if (rc == SSG_OK) rc = check_ready(h, false);
     if (rc != SSG_OK) return rc;
-    hipError_t e = ssg::launch_filter_update(dev_obs, f->obs_dim, P, P > 1 ? pop_width(h, P) : h->cfg.n_envs, P > 1 ? pop_slices(h) : nullptr,
-                                             f->eps, f->dev_state, f->dev_workspace, static_cast<hipStream_t>(stream));
+    hipError_t e = ssg::launch_filter_update(dev_obs, f->obs_dim, lay, f->eps, f->dev_state, f->dev_workspace, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("observation filter launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
@@ -2473,8 +2460,10 @@ int ssg_ret_filter_apply(ssg_handle *h, const ssg_ret_filter *f, int K, const do
     if (f->flags & ~SSG_RET_FILTER_UPDATE) return fail(h, SSG_ERR_BAD_ARG, w + ": unknown bit in ssg_ret_filter.flags");
     const int P = f->n_members, N = h->cfg.n_envs;
     if (P < 1 || P > SSG_POP_MAX_MEMBERS) return fail(h, SSG_ERR_BAD_ARG, w + ": n_members must be in 1..SSG_POP_MAX_MEMBERS");
-    int rc = check_members(h, P, "ssg_ret_filter_apply"); // (a bound slices layout for another member count, or envs that do not split)
+    ssg::MemberLayout lay;
+    int rc = member_layout(h, P, "ssg_ret_filter_apply", true, lay); // (asked for one member too, which then runs on the whole handle)
     if (rc != SSG_OK) return rc;
+    if (P == 1) lay = whole_layout(h);
     if (!(f->clip >= 0.0) || !(f->eps >= 0.0)) return fail(h, SSG_ERR_BAD_ARG, w + ": clip and eps must be >= 0 (and not NaN)");
     if (!f->dev_gamma || !f->dev_state || !f->dev_carry || !f->dev_workspace)
         return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_gamma, dev_state, dev_carry or dev_workspace");
@@ -2494,9 +2483,7 @@ int ssg_ret_filter_apply(ssg_handle *h, const ssg_ret_filter *f, int K, const do
     l.done = dev_done_KN;
     l.K = K;
     l.stride = (size_t)step_stride_envs;
-    l.members = P;
-    l.n = P > 1 ? pop_width(h, P) : N;
-    l.slices = P > 1 ? pop_slices(h) : nullptr;
+    l.lay = lay;
     l.update = (f->flags & SSG_RET_FILTER_UPDATE) != 0;
     l.clip = f->clip;
     l.eps = f->eps;
@@ -2534,16 +2521,13 @@ int ssg_eval_reduce(ssg_handle *h, int n_members, const int64_t *dev_env_stats, 
     if (rc != SSG_OK) return rc;
     if (n_members < 1 || n_members > SSG_POP_MAX_MEMBERS)
         return fail(h, SSG_ERR_BAD_ARG, "ssg_eval_reduce: n_members must be in 1..SSG_POP_MAX_MEMBERS and divide the handle's n_envs");
-    const bool whole = n_members == 1; // (one policy's reduce over the whole handle: the slices do not enter)
-    if (!whole) {
-        rc = check_members(h, n_members, "ssg_eval_reduce");
-        if (rc != SSG_OK) return rc;
-    }
+    ssg::MemberLayout lay = whole_layout(h); // (one policy's reduce over the whole handle: the slices do not enter)
+    if (n_members > 1) rc = member_layout(h, n_members, "ssg_eval_reduce", true, lay);
+    if (rc != SSG_OK) return rc;
     if (!dev_env_stats || !dev_member_stats) return fail(h, SSG_ERR_BAD_ARG, "ssg_eval_reduce: NULL dev_env_stats or dev_member_stats");
     rc = check_ready(h, false);
     if (rc != SSG_OK) return rc;
-    hipError_t e = ssg::launch_eval_reduce(n_members, h->cfg.n_envs / n_members, dev_env_stats, dev_member_stats, static_cast<hipStream_t>(stream),
-                                           whole ? nullptr : pop_slices(h));
+    hipError_t e = ssg::launch_eval_reduce(lay, dev_env_stats, dev_member_stats, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("evaluation reduce launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }

@@ -98,15 +98,14 @@ hipError_t launch_eval_account(int N, int E, const double *rew, const uint8_t *d
     return hipGetLastError();
 }
 
-hipError_t launch_eval_reduce(int members, int n, const int64_t *stats, int64_t *out, hipStream_t stream, const int32_t *slices)
+hipError_t launch_eval_reduce(const MemberLayout &lay, const int64_t *stats, int64_t *out, hipStream_t stream)
 {
-    if (slices) {
-        hipLaunchKernelGGL(eval_reduce_sliced_kernel, dim3(members), dim3(kEvalBlock), 0, stream, slices, reinterpret_cast<const long long *>(stats),
+    if (lay.slices)
+        hipLaunchKernelGGL(eval_reduce_sliced_kernel, dim3(lay.members), dim3(kEvalBlock), 0, stream, lay.slices,
+                           reinterpret_cast<const long long *>(stats), reinterpret_cast<long long *>(out));
+    else
+        hipLaunchKernelGGL(eval_reduce_kernel, dim3(lay.members), dim3(kEvalBlock), 0, stream, lay.n, reinterpret_cast<const long long *>(stats),
                            reinterpret_cast<long long *>(out));
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(eval_reduce_kernel, dim3(members), dim3(kEvalBlock), 0, stream, n, reinterpret_cast<const long long *>(stats),
-                       reinterpret_cast<long long *>(out));
     return hipGetLastError();
 }
 

@@ -153,16 +153,15 @@ size_t filter_workspace_bytes(int n_envs, int obs_dim, int members)
     return (size_t)members * (size_t)filter_tiles(n_envs) * 2 * (size_t)obs_dim * sizeof(double);
 }
 
-hipError_t launch_filter_update(const double *obs, int D, int members, int n, const int32_t *slices, double eps, double *state, void *ws,
-                                hipStream_t stream)
+hipError_t launch_filter_update(const double *obs, int D, const MemberLayout &lay, double eps, double *state, void *ws, hipStream_t stream)
 {
-    const int tiles = filter_tiles(n); // (n: the largest slice)
+    const int tiles = filter_tiles(lay.n);
     double *part = static_cast<double *>(ws);
-    hipLaunchKernelGGL(filter_partials_kernel, dim3((unsigned)tiles, (unsigned)members), dim3(kFltTile), 0, stream, obs, D, n, slices, part);
+    hipLaunchKernelGGL(filter_partials_kernel, dim3((unsigned)tiles, (unsigned)lay.members), dim3(kFltTile), 0, stream, obs, D, lay.n, lay.slices, part);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(filter_finalise_kernel, dim3((unsigned)members), dim3(kFltTile), 0, stream, (const double *)part, tiles, D, n, slices, eps,
-                       state);
+    hipLaunchKernelGGL(filter_finalise_kernel, dim3((unsigned)lay.members), dim3(kFltTile), 0, stream, (const double *)part, tiles, D, lay.n, lay.slices,
+                       eps, state);
     return hipGetLastError();
 }
 

@@ -201,10 +201,22 @@ hipError_t launch_refill_worlds(const DevCfg &c, uint64_t seed, double width_fra
                                 double *bank, double *raw, hipStream_t stream);
 hipError_t launch_fill_actions(uint64_t seed, uint64_t step0, int K, long long env_base, int n, int32_t *out,
                                hipStream_t stream);
-// The policy kernel (shipsim_policy.hip).  One acting launch: one policy over n envs (members 0), or a population — p is then the shared
-// shape with dev_params = f32 [members][L], and member m acts on the n = N / members envs [m*n, (m+1)*n) or, with slices (see below),
-// on its slice, n being the largest.  act / logp NULL = value only (no sampling), x NULL = no x rows.  greedy: the arg-max action and its
-// logp; act, logp and value are all written and uniform, seed, step and env_base are not read.  filter (nullable): the kernels of
+// How a launch's envs are divided among members.  ONE convention, for every launcher below and for the entry points that resolve it
+// (shipsim_api.cpp: member_layout, whole_layout) and hand it down unchanged:
+//   members >= 1;
+//   n is the launch's WIDTH: all envs for one policy, else the equal slice N / members — member m owns envs [m*n, (m+1)*n) — or the
+//     widest slice of a bound table;
+//   slices is NULL unless a table is bound and applies: the device table of ssg_pop_set_slices, SSG_POP_SLICE_ROW int32 per member =
+//     {o_m, n_m, ppo_gae_blocks(n_m), 0}; member m then owns envs [o_m, o_m + n_m).
+// Whether a launch runs a population's instantiations (a parameter row per member) is a separate fact, said beside the record.
+struct MemberLayout {
+    int members, n;
+    const int32_t *slices;
+};
+// The policy kernel (shipsim_policy.hip).  One acting launch: one policy over its layout's envs, or a population (pop) — p is then the
+// shared shape with dev_params = f32 [members][L], and member m acts on its envs.  act / logp NULL = value only (no sampling), x NULL = no
+// x rows.  greedy: the arg-max action and its logp; act, logp and value are all written and uniform, seed, step and env_base are not
+// read.  filter (nullable): the kernels of
 // shipsim_policy_filter.o, x = (float)clamp((obs - mean) / denom, +-clip) from member m's state rows in place of obs / scale.
 struct ObsFilterArgs { const double *state; double clip; };
 struct PolicyLaunch {
@@ -216,8 +228,8 @@ struct PolicyLaunch {
     float *logp, *value, *x;
     bool greedy;
     const ssg_policy *policy;
-    int members, n;
-    const int32_t *slices; // nullable
+    MemberLayout lay;
+    bool pop;              // the POP instantiations: parameter row m for member m
     long long env_base;    // the global id of env 0 (the uniforms' counter)
     const ObsFilterArgs *filter;
 };
@@ -229,7 +241,7 @@ hipError_t launch_policy(const PolicyLaunch &l, hipStream_t stream);
 hipError_t prepare_policy_filter();
 hipError_t launch_policy_filter(const PolicyLaunch &l, hipStream_t stream);
 // The time-out values of a rollout's K rows (ssg_timeout_values / ssg_pop_timeout_values), in a third object of shipsim_policy.hip
-// (-DSSG_POLICY_BOOT_TU).  Of l it reads policy, members, n, slices and filter; row k's flags and boot entries start k*stride in, its
+// (-DSSG_POLICY_BOOT_TU).  Of l it reads policy, lay, pop and filter; row k's flags and boot entries start k*stride in, its
 // observation rows k*n_envs*obs_dim doubles into term_obs.
 struct TimeoutLaunch {
     int K, n_envs;
@@ -267,13 +279,10 @@ constexpr int kPopSchedRow = SSG_POP_SCHED_ROW;
 enum { SH_STEPS = 0, SH_CHUNKS, SH_C, SH_EPOCHS, SH_PREFIX /* int64: entries [4], [5]; ssg_pop_pack_schedule_samples only */ };
 enum { SR_OFF = 0 /* int64: entries [0], [1] */, SR_M = 2, SR_G, SR_FIRST, SR_ACTIVE, SR_INVM /* f32 bits of 1 / (float)M */ };
 static_assert(SSG_POP_MAX_MEMBERS * 16 <= kPopSlotsOff, "the members' advantage statistics fit in front of the slots");
-// slices (nullable, here and below): the device table of ssg_pop_set_slices, SSG_POP_SLICE_ROW int32 per member = {o_m, n_m,
-// ppo_gae_blocks(n_m), 0}; member m then owns envs [o_m, o_m + n_m) and n is the LARGEST slice (the launch's width)
 void pop_pack(int members, const ssg_ppo_hparams *hp, int64_t step0, int n_steps, float *out); // host only
 void pop_pack_steps(int members, const ssg_ppo_hparams *hp, const int64_t *step0, int n_steps, float *out); // (a starting step per member)
-hipError_t launch_pop_gae(int members, int K, int N, const float *table, const double *rew, const uint8_t *done, const float *val,
-                          const float *last_val, float *adv, float *ret, void *ws, hipStream_t stream, const int32_t *slices = nullptr,
-                          int n_max = 0, const float *boot = nullptr);
+hipError_t launch_pop_gae(const MemberLayout &lay, int K, int N, const float *table, const double *rew, const uint8_t *done, const float *val,
+                          const float *last_val, const float *boot /* nullable */, float *adv, float *ret, void *ws, hipStream_t stream);
 hipError_t launch_pop_exploit(const ssg_policy &p, int members, const int32_t *src, float *adam_mv, hipStream_t stream);
 // The extended update (ssg_ppo_grad_ext / ssg_ppo_update_ext / ssg_pop_update_ext): value clip, KL penalty, gradient-norm clip.
 // From the plain path's slot offset the workspace holds the running sum of the epoch's mean(KL) (f32 [members]), the gradient vector of
@@ -316,11 +325,11 @@ struct PpoBatch {
 // One minibatch of `members` policies: the gradients into the workspace's slots, then per member their sum — into grad_out (nullable)
 // and, with adam_mv, one Adam step on its parameter row — and the minibatch's loss means into stats_out (nullable; member m's row at
 // stats_out + m*stats_stride; 4 floats, kExtStats with ext).  The constants are ONE policy's (hp, and the Adam step number `step`;
-// table NULL, members 1, n / N / idx_stride unused) or a population's (table: its loss rows, adam_row: this step's Adam rows).
+// table NULL, lay.members 1, lay.n / N / idx_stride unused) or a population's (table: its loss rows, adam_row: this step's Adam rows).
 struct PpoMinibatch {
     const ssg_policy *policy; // the shape; dev_params = f32 [members][P]
-    int members;
-    long long n, N;           // envs per member and of the batch: member m's sample i = t*n + e is row t*N + m*n + e
+    MemberLayout lay;         // member m's sample i = t*n + e is row t*N + m*n + e, N the envs of the batch
+    long long N;
     long long n_samples;      // samples per member (an index outside [0, n_samples) is a zero, gradient-free sample)
     PpoBatch batch;
     const int64_t *idx;       // M indices (member-local); member m's at idx + m*idx_stride
@@ -336,10 +345,10 @@ struct PpoMinibatch {
     float *grad_out, *stats_out;
     long long stats_stride;
     float *adam_mv;
-    // a population on unequal slices (with sched): the slices table and the schedule table's header rows, whose entries SH_PREFIX hold
+    // a population on unequal slices (lay.slices, with sched): the schedule table's header rows, whose entries SH_PREFIX hold
     // the int64 sum of the samples of the members before m — member m's permutation block starts perm_epochs times that far into idx
-    // and its samples are K * n_m (n, n_samples and idx_stride are then unused)
-    const int32_t *slices, *sched_hdr;
+    // and its samples are K * n_m (lay.n, n_samples and idx_stride are then unused)
+    const int32_t *sched_hdr;
     long long K, perm_epochs;
     // per-minibatch advantage normalisation (ssg_ppo_set_adv_norm; both NULL: the batch statistics in the workspace): the scratch's
     // stats rows and partials.  The two launches of shipsim_advnorm.hip then run ahead of the gradient launch, which reads these rows.
@@ -360,12 +369,12 @@ struct AdvNormLaunch {
     const float *adv;
     const int64_t *idx;
     long long M, n_samples;
-    int members;
-    long long n, N, idx_stride;
+    MemberLayout lay;
+    long long N, idx_stride;
     const float *table;
     int adv_eps_col;
     float adv_eps;
-    const int32_t *sched, *slices, *sched_hdr;
+    const int32_t *sched, *sched_hdr;
     long long K, perm_epochs;
     float *stats;
     double *part;
@@ -375,37 +384,34 @@ hipError_t launch_adv_norm(const AdvNormLaunch &l, hipStream_t stream);
 // table, whose header row m holds member m's own chunk count)
 hipError_t launch_kl_adapt(int members, const PpoExtLaunch &ext, float kl_target, int P, long long chunks, const int32_t *sched_hdr, void *ws,
                            size_t slots_off, hipStream_t stream);
-// the acting policy's log-distribution over stored x rows (shipsim_policy.hip): rows t*N + m*n + e, t < K, e < n, under parameter row m
-hipError_t launch_policy_dist(const ssg_policy &p, int members, int n, long long N, int K, const float *x, float *logp_all, hipStream_t stream,
-                              const int32_t *slices = nullptr);
-hipError_t launch_pop_episode_stats(int members, int K, int N, const double *rew, const uint8_t *done, double *carry_ret,
-                                    int32_t *carry_len, int64_t *out, hipStream_t stream, const int32_t *slices = nullptr, int n_max = 0);
+// the acting policy's log-distribution over stored x rows (shipsim_policy.hip): member m's rows t*N + (its envs), t < K, under parameter row m
+hipError_t launch_policy_dist(const ssg_policy &p, const MemberLayout &lay, long long N, int K, const float *x, float *logp_all, hipStream_t stream);
+hipError_t launch_pop_episode_stats(const MemberLayout &lay, int K, int N, const double *rew, const uint8_t *done, double *carry_ret,
+                                    int32_t *carry_len, int64_t *out, hipStream_t stream);
 // episode accounting of an evaluation run (shipsim_eval.hip): one step's rows into the per-env carries and stats rows (an env counts its
 // first E episodes), and the per-member column sums of the stats rows
 constexpr int kEvalCols = SSG_EVAL_STATS;
 hipError_t launch_eval_account(int N, int E, const double *rew, const uint8_t *done, const uint8_t *flags, double *carry_ret, int32_t *carry,
                                int64_t *stats, hipStream_t stream);
-hipError_t launch_eval_reduce(int members, int n, const int64_t *stats, int64_t *out, hipStream_t stream, const int32_t *slices = nullptr);
+hipError_t launch_eval_reduce(const MemberLayout &lay, const int64_t *stats, int64_t *out, hipStream_t stream);
 // the observation filter (shipsim_filter.hip): 256-row tiles, staged at most kFltChunk columns at a time; the workspace holds launch 1's
 // partials, f64 [members][filter_tiles(widest slice)][2][D]
 constexpr int kFltTile = 256, kFltChunk = 31, kFltMaxDim = SSG_MAX_HISTORY * (6 + SSG_MAX_BEAMS);
 inline int filter_tiles(long long n) { return (int)((n + kFltTile - 1) / kFltTile); }
 size_t filter_workspace_bytes(int n_envs, int obs_dim, int members);
-// the two launches: member m's n rows [m*n, (m+1)*n) of obs, or its slice (then n: the largest slice), into its SSG_FILTER_ROWS state rows
-hipError_t launch_filter_update(const double *obs, int D, int members, int n, const int32_t *slices, double eps, double *state, void *ws,
-                                hipStream_t stream);
+// the two launches: the rows of member m's envs of obs into its SSG_FILTER_ROWS state rows
+hipError_t launch_filter_update(const double *obs, int D, const MemberLayout &lay, double eps, double *state, void *ws, hipStream_t stream);
 // the return filter (shipsim_retfilter.hip): the workspace holds the walk's tile partials, f64 [members][K][filter_tiles(n_envs)][2], then
 // the chain's denoms, f64 [K][members]
 size_t ret_filter_workspace_bytes(int n_envs, int K, int members);
 // One call's launches: walk, chain and normalise when `update`, else normalise alone with the state's own denom.  Member m's envs are
-// columns [m*n, (m+1)*n) of the [K][stride] buffers, or its slice (then n: the largest slice).
+// columns of the [K][stride] buffers.
 struct RetFilterLaunch {
     const double *rew;
     const uint8_t *done;
     int K;
     size_t stride;
-    int members, n;
-    const int32_t *slices;
+    MemberLayout lay;
     bool update;
     double clip, eps;
     const double *gamma; // f64 [members]

@@ -619,19 +619,18 @@ template <class Kernel, class SlicedKernel, class... Extra>
 static hipError_t launch_act(Kernel kernel, SlicedKernel sliced, const PolicyLaunch &l, const double *third, hipStream_t stream, Extra... extra)
 {
     const ssg_policy &p = *l.policy;
-    const bool pop = l.members > 0;
-    const dim3 grid((unsigned)((l.n + kPolWave - 1) / kPolWave), pop ? (unsigned)l.members : 1u); // (n: with slices, the largest)
+    const dim3 grid((unsigned)((l.lay.n + kPolWave - 1) / kPolWave), (unsigned)l.lay.members);
     const size_t lds = policy_lds_bytes(p, l.greedy || l.act != nullptr);
-    const int plen = pop ? ppo_packed_len(p) : 0;
+    const int plen = l.pop ? ppo_packed_len(p) : 0;
     const float *uniform = l.greedy ? nullptr : l.uniform;
     const uint64_t seed = l.greedy ? 0 : l.seed;
     const int64_t step = l.greedy ? 0 : l.step;
     const long long env_base = l.greedy ? 0 : l.env_base;
-    if (l.slices)
-        hipLaunchKernelGGL(sliced, grid, dim3(kPolWave), lds, stream, p, p.dev_params, third, l.slices, env_base, l.obs, uniform, seed, step,
+    if (l.lay.slices)
+        hipLaunchKernelGGL(sliced, grid, dim3(kPolWave), lds, stream, p, p.dev_params, third, l.lay.slices, env_base, l.obs, uniform, seed, step,
                            l.act, l.logp, l.value, l.x, plen, extra...);
     else
-        hipLaunchKernelGGL(kernel, grid, dim3(kPolWave), lds, stream, p, p.dev_params, third, l.n, env_base, l.obs, uniform, seed, step, l.act,
+        hipLaunchKernelGGL(kernel, grid, dim3(kPolWave), lds, stream, p, p.dev_params, third, l.lay.n, env_base, l.obs, uniform, seed, step, l.act,
                            l.logp, l.value, l.x, plen, extra...);
     return hipGetLastError();
 }
@@ -657,7 +656,7 @@ hipError_t prepare_policy_filter()
 hipError_t launch_policy_filter(const PolicyLaunch &l, hipStream_t stream)
 {
     const bool split = is_split(*l.policy);
-    return launch_act(kFilter[l.members > 0][split][l.greedy], kFilterSliced[split][l.greedy], l, l.filter->state, stream, l.filter->clip);
+    return launch_act(kFilter[l.pop][split][l.greedy], kFilterSliced[split][l.greedy], l, l.filter->state, stream, l.filter->clip);
 }
 #elif defined(SSG_POLICY_BOOT_TU)
 // the time-out value instantiations, indexed [split][filter]
@@ -670,11 +669,10 @@ hipError_t prepare_policy_boot() { return raise_lds_limit(&kTimeout[0][0], 4); }
 hipError_t launch_timeout_values(const PolicyLaunch &l, const TimeoutLaunch &t, hipStream_t stream)
 {
     const ssg_policy &p = *l.policy;
-    const bool pop = l.members > 0;
-    const dim3 grid((unsigned)((l.n + kPolWave - 1) / kPolWave), pop ? (unsigned)l.members : 1u, (unsigned)t.K); // (n: with slices, the largest)
+    const dim3 grid((unsigned)((l.lay.n + kPolWave - 1) / kPolWave), (unsigned)l.lay.members, (unsigned)t.K);
     hipLaunchKernelGGL(kTimeout[is_split(p)][l.filter != nullptr], grid, dim3(kPolWave), policy_lds_bytes(p, false), stream, p, p.dev_params,
-                       l.filter ? l.filter->state : p.dev_obs_scale, l.n, t.n_envs, t.stride, l.slices, t.flags, t.term_obs, t.boot,
-                       pop ? ppo_packed_len(p) : 0, l.filter ? l.filter->clip : 0.0);
+                       l.filter ? l.filter->state : p.dev_obs_scale, l.lay.n, t.n_envs, t.stride, l.lay.slices, t.flags, t.term_obs, t.boot,
+                       l.pop ? ppo_packed_len(p) : 0, l.filter ? l.filter->clip : 0.0);
     return hipGetLastError();
 }
 #else
@@ -716,21 +714,18 @@ hipError_t prepare_policy()
 hipError_t launch_policy(const PolicyLaunch &l, hipStream_t stream)
 {
     if (l.filter) return launch_policy_filter(l, stream);
-    const bool split = is_split(*l.policy), pop = l.members > 0;
-    return launch_act((l.greedy ? kActGreedy : kAct)[split][pop], kActSliced[l.greedy][split], l, l.policy->dev_obs_scale, stream);
+    const bool split = is_split(*l.policy);
+    return launch_act((l.greedy ? kActGreedy : kAct)[split][l.pop], kActSliced[l.greedy][split], l, l.policy->dev_obs_scale, stream);
 }
 
-hipError_t launch_policy_dist(const ssg_policy &p, int members, int n, long long N, int K, const float *x, float *logp_all, hipStream_t stream,
-                              const int32_t *slices)
+hipError_t launch_policy_dist(const ssg_policy &p, const MemberLayout &lay, long long N, int K, const float *x, float *logp_all, hipStream_t stream)
 {
-    const unsigned grid = (unsigned)((n + kPolWave - 1) / kPolWave);
-    if (slices) {
-        hipLaunchKernelGGL(is_split(p) ? policy_dist_sliced_kernel<true> : policy_dist_sliced_kernel<false>, dim3(grid, (unsigned)members, (unsigned)K),
-                           dim3(kPolWave), policy_lds_bytes(p, false), stream, p, p.dev_params, slices, N, x, logp_all, ppo_packed_len(p));
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(is_split(p) ? policy_dist_kernel<true> : policy_dist_kernel<false>, dim3(grid, (unsigned)members, (unsigned)K),
-                       dim3(kPolWave), policy_lds_bytes(p, false), stream, p, p.dev_params, n, N, x, logp_all, ppo_packed_len(p));
+    const dim3 grid((unsigned)((lay.n + kPolWave - 1) / kPolWave), (unsigned)lay.members, (unsigned)K);
+    const size_t lds = policy_lds_bytes(p, false);
+    if (lay.slices)
+        hipLaunchKernelGGL(kDistSliced[is_split(p)], grid, dim3(kPolWave), lds, stream, p, p.dev_params, lay.slices, N, x, logp_all, ppo_packed_len(p));
+    else
+        hipLaunchKernelGGL(kDist[is_split(p)], grid, dim3(kPolWave), lds, stream, p, p.dev_params, lay.n, N, x, logp_all, ppo_packed_len(p));
     return hipGetLastError();
 }
 

@@ -1166,14 +1166,14 @@ hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream)
     const bool pop = mb.table != nullptr; // a population reads its constants from the table: the POP instantiations
     const bool sched = mb.sched != nullptr; // ... and its members' minibatches from the schedule records: the SCHED ones (G: the launch's)
     if (sched && !pop) return hipErrorInvalidValue;
-    const bool sliced = mb.slices != nullptr; // ... on unequal slices: the SLICED ones
+    const bool sliced = mb.lay.slices != nullptr; // ... on unequal slices: the SLICED ones
     if (sliced && !(sched && mb.sched_hdr)) return hipErrorInvalidValue;
-    const SliceGradArgs sa = {mb.slices, mb.sched_hdr, mb.K, mb.perm_epochs};
+    const SliceGradArgs sa = {mb.lay.slices, mb.sched_hdr, mb.K, mb.perm_epochs};
     const bool split = (p.activation & SSG_POLICY_SEPARATE_VALUE) != 0;
     const PpoExtLaunch *ext = mb.ext;
     const int P = ppo_packed_len(p), G = ppo_grid(mb.M), stride = P + (ext ? kExtStats : 4);
     char *base = static_cast<char *>(mb.ws);
-    const PpoExtLayout lay = ext ? ppo_ext_layout(mb.slots_off, mb.members, G, P) : PpoExtLayout{};
+    const PpoExtLayout lay = ext ? ppo_ext_layout(mb.slots_off, mb.lay.members, G, P) : PpoExtLayout{};
     float row[kPopTableRow] = {}; // (a population's gradient kernel reads row m of the table instead)
     if (!pop) loss_row(*mb.hp, row);
     GradArgs a;
@@ -1199,15 +1199,13 @@ hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream)
         an.idx = mb.idx;
         an.M = mb.M;
         an.n_samples = mb.n_samples;
-        an.members = mb.members;
-        an.n = mb.n;
+        an.lay = mb.lay;
         an.N = mb.N;
         an.idx_stride = mb.idx_stride;
         an.table = mb.table;
         an.adv_eps_col = PT_ADV_EPS;
         an.adv_eps = row[PT_ADV_EPS];
         an.sched = mb.sched;
-        an.slices = mb.slices;
         an.sched_hdr = mb.sched_hdr;
         an.K = mb.K;
         an.perm_epochs = mb.perm_epochs;
@@ -1226,13 +1224,13 @@ hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream)
     a.ent = row[PT_ENT];
     a.invM = 1.0f / (float)mb.M;
     PopGradArgs pa;
-    pa.n = mb.n;
+    pa.n = mb.lay.n;
     pa.N = mb.N;
     pa.idx_stride = mb.idx_stride;
     pa.table = mb.table;
     float *params = mb.adam_mv ? const_cast<float *>(p.dev_params) : nullptr;
     const AdamArgs ad = mb.adam_mv && !pop ? adam_args(*mb.hp, mb.step) : AdamArgs{};
-    const dim3 ggrid((unsigned)G, (unsigned)mb.members), rgrid((unsigned)((stride + 255) / 256), (unsigned)mb.members);
+    const dim3 ggrid((unsigned)G, (unsigned)mb.lay.members), rgrid((unsigned)((stride + 255) / 256), (unsigned)mb.lay.members);
     if (!ext) {
         if (sliced) hipLaunchKernelGGL(kGradSliced[!split], ggrid, dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a, pa, mb.sched, sa);
         else if (sched) hipLaunchKernelGGL(kGradSched[!split], ggrid, dim3(kPpoBlock), ppo_grad_lds_bytes(p), stream, a, pa, mb.sched);
@@ -1260,7 +1258,7 @@ hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream)
     er.first_chunk = ext->first_chunk ? 1 : 0;
     er.gvec = ext->clip_seq ? reinterpret_cast<float *>(base + lay.gvec) : nullptr;
     er.part = reinterpret_cast<double *>(base + lay.part);
-    const dim3 cgrid((unsigned)((P + 255) / 256), (unsigned)mb.members);
+    const dim3 cgrid((unsigned)((P + 255) / 256), (unsigned)mb.lay.members);
     if (sched) {
         hipLaunchKernelGGL(ppo_reduce_ext_sched_kernel, rgrid, dim3(256), 0, stream, (const float *)a.slots, G, P, stride, mb.stats_out, params,
                            mb.adam_mv, mb.stats_stride, mb.adam_row, er, mb.sched);
@@ -1314,11 +1312,11 @@ void pop_pack_steps(int members, const ssg_ppo_hparams *hp, const int64_t *step0
         for (int m = 0; m < members; ++m) adam_to_row(adam_args(hp[m], step0[m] + 1 + j), out + ((size_t)(1 + j) * members + m) * kPopTableRow);
 }
 
-hipError_t launch_pop_gae(int members, int K, int N, const float *table, const double *rew, const uint8_t *done, const float *val,
-                          const float *last_val, float *adv, float *ret, void *ws, hipStream_t stream, const int32_t *slices, int n_max,
-                          const float *boot)
+hipError_t launch_pop_gae(const MemberLayout &lay, int K, int N, const float *table, const double *rew, const uint8_t *done, const float *val,
+                          const float *last_val, const float *boot, float *adv, float *ret, void *ws, hipStream_t stream)
 {
-    const int n = slices ? n_max : N / members, nb = ppo_gae_blocks(n);
+    const int members = lay.members, n = lay.n, nb = ppo_gae_blocks(n);
+    const int32_t *slices = lay.slices;
     float *stats = reinterpret_cast<float *>(static_cast<char *>(ws) + kPpoStatsOff);
     double2 *part = reinterpret_cast<double2 *>(static_cast<char *>(ws) + kPopSlotsOff);
     if (slices) {
@@ -1350,17 +1348,16 @@ hipError_t launch_pop_exploit(const ssg_policy &p, int members, const int32_t *s
     return hipGetLastError();
 }
 
-hipError_t launch_pop_episode_stats(int members, int K, int N, const double *rew, const uint8_t *done, double *carry_ret,
-                                    int32_t *carry_len, int64_t *out, hipStream_t stream, const int32_t *slices, int n_max)
+hipError_t launch_pop_episode_stats(const MemberLayout &lay, int K, int N, const double *rew, const uint8_t *done, double *carry_ret,
+                                    int32_t *carry_len, int64_t *out, hipStream_t stream)
 {
-    if (slices) {
-        hipLaunchKernelGGL(pop_episode_stats_sliced_kernel, dim3((n_max + 255) / 256, members), dim3(256), 0, stream, K, N, slices, rew, done,
-                           carry_ret, carry_len, reinterpret_cast<unsigned long long *>(out));
-        return hipGetLastError();
-    }
-    const int n = N / members;
-    hipLaunchKernelGGL(pop_episode_stats_kernel, dim3((n + 255) / 256, members), dim3(256), 0, stream, K, N, n, rew, done, carry_ret,
-                       carry_len, reinterpret_cast<unsigned long long *>(out));
+    const dim3 grid((lay.n + 255) / 256, lay.members);
+    if (lay.slices)
+        hipLaunchKernelGGL(pop_episode_stats_sliced_kernel, grid, dim3(256), 0, stream, K, N, lay.slices, rew, done, carry_ret, carry_len,
+                           reinterpret_cast<unsigned long long *>(out));
+    else
+        hipLaunchKernelGGL(pop_episode_stats_kernel, grid, dim3(256), 0, stream, K, N, lay.n, rew, done, carry_ret, carry_len,
+                           reinterpret_cast<unsigned long long *>(out));
     return hipGetLastError();
 }
 

@@ -216,24 +216,25 @@ size_t ret_filter_workspace_bytes(int n_envs, int K, int members)
 
 hipError_t launch_ret_filter(const RetFilterLaunch &l, hipStream_t stream)
 {
-    const int tiles = filter_tiles(l.n); // (n: the largest slice)
+    const MemberLayout &lay = l.lay;
+    const int tiles = filter_tiles(lay.n);
     double *part = static_cast<double *>(l.workspace);
-    double *denom = part + (size_t)l.members * (size_t)l.K * (size_t)tiles * 2;
+    double *denom = part + (size_t)lay.members * (size_t)l.K * (size_t)tiles * 2;
     const dim3 block(kFltTile);
     if (l.update) {
-        hipLaunchKernelGGL(ret_walk_kernel, dim3((unsigned)tiles, (unsigned)l.members), block, 0, stream, l.rew, l.done, l.K, l.stride, l.n,
-                           l.slices, l.gamma, l.carry, part);
+        hipLaunchKernelGGL(ret_walk_kernel, dim3((unsigned)tiles, (unsigned)lay.members), block, 0, stream, l.rew, l.done, l.K, l.stride, lay.n,
+                           lay.slices, l.gamma, l.carry, part);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(ret_chain_kernel, dim3((unsigned)l.members), block, 0, stream, (const double *)part, tiles, l.K, l.n, l.slices, l.eps,
+        hipLaunchKernelGGL(ret_chain_kernel, dim3((unsigned)lay.members), block, 0, stream, (const double *)part, tiles, l.K, lay.n, lay.slices, l.eps,
                            l.state, denom);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     const double *den = l.update ? denom : l.state + 2;
-    const size_t den_k = l.update ? (size_t)l.members : 0, den_m = l.update ? 1 : SSG_FILTER_ROWS;
-    hipLaunchKernelGGL(ret_normalise_kernel, dim3((unsigned)tiles, (unsigned)l.members, (unsigned)((l.K + kRetRows - 1) / kRetRows)), block, 0,
-                       stream, l.rew, l.K, l.stride, l.n, l.slices, den, den_k, den_m, l.clip, l.out, l.denom_out);
+    const size_t den_k = l.update ? (size_t)lay.members : 0, den_m = l.update ? 1 : SSG_FILTER_ROWS;
+    hipLaunchKernelGGL(ret_normalise_kernel, dim3((unsigned)tiles, (unsigned)lay.members, (unsigned)((l.K + kRetRows - 1) / kRetRows)), block, 0,
+                       stream, l.rew, l.K, l.stride, lay.n, lay.slices, den, den_k, den_m, l.clip, l.out, l.denom_out);
     return hipGetLastError();
 }
 
