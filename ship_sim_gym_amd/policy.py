@@ -153,6 +153,74 @@ class NativePolicy(object):
             torch.cat([t.detach().reshape(-1) for t in self._sources], out=self.params)
         return self.params
 
+    # ------------------------------------------------------------------------------------------------
+    # state (ship_sim_gym_amd/checkpoint.py)
+    # ------------------------------------------------------------------------------------------------
+    def architecture(self):
+        """The fields that fix the packed layout, as (name, value) pairs: what a state must agree with."""
+        return [("obs_dim", self.obs_dim), ("hidden", self.hidden), ("n_hidden_layers", self.n_hidden_layers),
+                ("n_actions", self.n_actions), ("activation", self.activation), ("separate_value", bool(self.separate_value))]
+
+    def state_dict(self):
+        """The architecture, the packed parameters and the observation scale (CPU copies; plain data only)."""
+        sd = dict(self.architecture())
+        sd["params"], sd["obs_scale"] = self.params.detach().cpu().clone(), self.obs_scale.detach().cpu().clone()
+        return sd
+
+    def load_state_dict(self, sd):
+        """Take a state_dict's parameters and observation scale, in place (``params`` keeps its address).  Everything is checked first:
+        an architecture field, a shape or a dtype that differs raises ValueError naming the field with both values, and the object
+        stays as it was.  The tensors this policy was built over (a module's parameters, for ``from_actor_critic``) get the loaded
+        values as well, so that a later ``refresh()`` re-packs what was loaded."""
+        from .checkpoint import check_state
+        check_state("NativePolicy.load_state_dict", sd, self.architecture(), [("params", self.params), ("obs_scale", self.obs_scale)])
+        with _torch().no_grad():
+            self.params.copy_(sd["params"])
+            self.obs_scale.copy_(sd["obs_scale"])
+            self.push_sources()
+        return self
+
+    def push_sources(self):
+        """The reverse of ``refresh()``: copy the packed buffer into the tensors it was packed from."""
+        o = 0
+        with _torch().no_grad():
+            for t in self._sources:
+                t.copy_(self.params[o: o + t.numel()].view_as(t))
+                o += t.numel()
+
+    @classmethod
+    def from_state_dict(cls, sd, device, row=None):
+        """A NativePolicy on `device` built from a state_dict alone (no module): the architecture comes from the state.  row: for a
+        NativePopulation's state, the member whose row of ``params`` to take."""
+        torch = _torch()
+        from .checkpoint import check_values
+        who = "NativePolicy.from_state_dict"
+        if not isinstance(sd, dict):
+            raise ValueError("%s: a state dict is a dict (got a %s)" % (who, type(sd).__name__))
+        check_values(who, sd, [("obs_dim", int), ("hidden", int), ("n_hidden_layers", int), ("n_actions", int), ("activation", str),
+                               ("separate_value", bool)])
+        params, scale = sd.get("params"), sd.get("obs_scale")
+        if not torch.is_tensor(params) or not torch.is_tensor(scale):
+            raise ValueError("%s: params and obs_scale must be tensors" % who)
+        if row is not None:
+            if params.dim() != 2 or not 0 <= int(row) < params.shape[0]:
+                raise ValueError("%s: member %r of a params tensor %s" % (who, row, tuple(params.shape)))
+            params = params[int(row)]
+        D, H, L, A = sd["obs_dim"], sd["hidden"], sd["n_hidden_layers"], sd["n_actions"]
+        if L not in (1, 2) or D < 1 or H < 1 or A < 1:
+            raise ValueError("%s: obs_dim %d, hidden %d, n_hidden_layers %d, n_actions %d is no architecture" % (who, D, H, L, A))
+        offsets, total = packed_offsets(D, H, L, A, sd["separate_value"])
+        if params.dtype != torch.float32 or params.dim() != 1 or params.numel() != total:
+            raise ValueError("%s: params is a %s tensor %s, the architecture packs into float32 (%d,)"
+                             % (who, params.dtype, tuple(params.shape), total))
+        flat = params.detach().to(device=device).clone()
+        t = {k: flat[o: o + _numel(s)].view(*s) for k, (o, s) in offsets.items()}
+        layers = [(t["W0"], t["b0"])] + ([(t["W1"], t["b1"])] if L == 2 else [])
+        value_layers = None
+        if sd["separate_value"]:
+            value_layers = [(t["V0"], t["c0"])] + ([(t["V1"], t["c1"])] if L == 2 else [])
+        return cls(layers, (t["Wpi"], t["bpi"]), (t["Wv"], t["bv"]), scale.to(device), activation=sd["activation"], value_layers=value_layers)
+
     def to_native(self):
         """The ssg_policy record (pointers into this object's tensors: keep the policy alive while the library uses it)."""
         p = N.Policy()

@@ -101,6 +101,46 @@ class NativePopulation(object):
             load_packed(self.params[m], net, "NativePopulation.load_into: module %d has %%d parameters, a member %d" % (m, self.n_params))
         return nets
 
+    # ------------------------------------------------------------------------------------------------
+    # state (ship_sim_gym_amd/checkpoint.py)
+    # ------------------------------------------------------------------------------------------------
+    def architecture(self):
+        """The member count and the fields that fix a row's layout, as (name, value) pairs: what a state must agree with."""
+        return [("n_members", len(self))] + self._members[0].architecture()
+
+    def state_dict(self):
+        """The architecture, ``params`` [P, L] and the observation scale (CPU copies; plain data only)."""
+        sd = dict(self.architecture())
+        sd["params"], sd["obs_scale"] = self.params.detach().cpu().clone(), self.obs_scale.detach().cpu().clone()
+        return sd
+
+    def load_state_dict(self, sd):
+        """Take a state_dict's rows and observation scale, in place.  Checked first: a member count, an architecture field, a shape or
+        a dtype that differs raises ValueError naming the field with both values, and nothing is copied.  The tensors the members
+        were built over (the modules' parameters) get the loaded rows, then ``refresh()`` re-packs them: the rows, the members' views
+        and the modules agree afterwards."""
+        from .checkpoint import check_state
+        check_state("NativePopulation.load_state_dict", sd, self.architecture(), [("params", self.params), ("obs_scale", self.obs_scale)])
+        with _torch().no_grad():
+            self.params.copy_(sd["params"])
+            self.obs_scale.copy_(sd["obs_scale"])
+            for pol in self._members:
+                pol.push_sources()
+        self.refresh()
+        return self
+
+    @classmethod
+    def from_state_dict(cls, sd, device):
+        """A NativePopulation on `device` built from a state_dict alone (no modules): the architecture comes from the state."""
+        from .checkpoint import check_values
+        if not isinstance(sd, dict):
+            raise ValueError("NativePopulation.from_state_dict: a state dict is a dict (got a %s)" % type(sd).__name__)
+        check_values("NativePopulation.from_state_dict", sd, [("n_members", int)])
+        params = sd.get("params")
+        if not _torch().is_tensor(params) or params.dim() != 2 or int(params.shape[0]) != sd["n_members"]:
+            raise ValueError("NativePopulation.from_state_dict: params must be a tensor [n_members = %d, L]" % sd["n_members"])
+        return cls([NativePolicy.from_state_dict(sd, device, row=m) for m in range(sd["n_members"])])
+
     def to_native(self):
         """The ssg_population record (pointers into this object's tensors: keep it alive while the library uses it)."""
         p = N.Population()
@@ -136,7 +176,7 @@ class PopulationPPO(DeviceTrainer):
         self.population, self.env, self._device = population, env, population.device
         P = len(population)
         self.perm_seed = None if perm_seed is None else int(perm_seed)  # None: the caller brings every perm
-        self.updates = 0  # calls of update(); like `step`, a checkpoint may set it
+        self.updates = 0  # calls of update(); like `step`, load_state_dict() sets it
         # "batch": every member's advantages are normalised once per rollout; "minibatch": inside every minibatch (PPO2's rule), the
         # same mode for all members
         self.adv_norm = adv_norm
@@ -541,6 +581,52 @@ class PopulationPPO(DeviceTrainer):
                     h, "ssg_pop_episode_stats")
         return out
 
+    # ------------------------------------------------------------------------------------------------
+    # state (ship_sim_gym_amd/checkpoint.py)
+    # ------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        """What the next update depends on besides the population and the batch (CPU copies; plain data only): the Adam moments
+        [P, 2L], ``step``, ``member_steps``, ``updates``, ``kl_coef`` [P], every per-member hyper-parameter list (HPARAM_KEYS and
+        EXT_KEYS), ``adv_norm``, ``perm_seed`` (with ``has_perm_seed``: the state holds no None), the episode carries and ``last_K``.
+
+        Not state: the workspace (gae() rewrites the statistics at its head before update() reads them, and a checkpoint is taken
+        between an update and the next rollout), the per-minibatch scratch, and the env's slices, which belong to the layout the
+        caller binds.  A ``ReturnFilter`` registered with ``set_return_filter`` is saved by its owner, not here."""
+        sd = {"n_members": self.n_members, "adam_mv": self.adam_mv.detach().cpu().clone(), "step": int(self.step),
+              "member_steps": [int(s) for s in self.member_steps], "updates": int(self.updates),
+              "kl_coef": self.kl_coef.detach().cpu().clone(), "adv_norm": self.adv_norm,
+              "has_perm_seed": self.perm_seed is not None, "perm_seed": int(self.perm_seed or 0),
+              "carry_return": self.carry_return.detach().cpu().clone(), "carry_length": self.carry_length.detach().cpu().clone(),
+              "last_K": int(self._last_K)}
+        for k in HPARAM_KEYS + EXT_KEYS:
+            sd[k] = [float(v) for v in getattr(self, k)]
+        return sd
+
+    def load_state_dict(self, sd):
+        """Become the trainer the state was taken from.  Checked first, all of it: the member count, ``adv_norm`` (the mode and its
+        scratch are made at construction), every tensor's shape and dtype, every list's length.  A mismatch raises ValueError naming
+        the field with both values and leaves this object as it was."""
+        from .checkpoint import check_state, check_values
+        who, P = "PopulationPPO.load_state_dict", self.n_members
+        check_state(who, sd, [("n_members", P), ("adv_norm", self.adv_norm)],
+                    [("adam_mv", self.adam_mv), ("kl_coef", self.kl_coef), ("carry_return", self.carry_return),
+                     ("carry_length", self.carry_length)])
+        lists = ("member_steps",) + HPARAM_KEYS + EXT_KEYS
+        check_values(who, sd, [("step", int), ("updates", int), ("has_perm_seed", bool), ("perm_seed", int), ("last_K", int)]
+                     + [(k, list) for k in lists])
+        bad = ["%s lists %d values in the state, this object has %d members" % (k, len(sd[k]), P) for k in lists if len(sd[k]) != P]
+        bad += ["%s holds %r" % (k, v) for k in lists for v in sd[k] if isinstance(v, bool) or not isinstance(v, (int, float))]
+        if bad:
+            raise ValueError("%s: %s" % (who, "; ".join(bad)))
+        for name in ("adam_mv", "kl_coef", "carry_return", "carry_length"):
+            getattr(self, name).copy_(sd[name])
+        self.step, self.updates, self._last_K = int(sd["step"]), int(sd["updates"]), int(sd["last_K"])
+        self.member_steps = [int(s) for s in sd["member_steps"]]
+        self.perm_seed = int(sd["perm_seed"]) if sd["has_perm_seed"] else None
+        for k in HPARAM_KEYS + EXT_KEYS:
+            setattr(self, k, [float(v) for v in sd[k]])
+        return self
+
 
 # ------------------------------------------------------------------------------------------------------------------------------------
 # the scheduler (host only)
@@ -625,6 +711,45 @@ class PBTScheduler(object):
     def due(self, update):
         """True after update number `update` (1, 2, ...) when a perturbation is due."""
         return update > 0 and update % self.interval == 0
+
+    def _arguments(self):
+        """The constructor's arguments as plain data, as (name, value) pairs; a mutation that is a list is its values, one that draws
+        from the generator is the string "callable" (a function is not data: the scheduler that loads a state brings its own)."""
+        return [("n_members", self.n_members), ("perturbation_interval", self.interval), ("quantile_fraction", self.quantile_fraction),
+                ("resample_probability", self.resample_probability),
+                ("mutations", {str(k): (list(d) if isinstance(d, list) else "callable") for k, d in self.mutations.items()})]
+
+    def state_dict(self):
+        """The constructor's arguments and the generator's state, as plain data (ints, floats, strings, lists, dicts: no tuple, no
+        torch).  ``due`` reads the interval and the caller's update number, ``perturb`` the generator and its arguments: the scheduler
+        keeps no counter of its own, so this is all of it.  After ``load_state_dict`` the next ``perturb(scores, hparams)`` returns
+        what the original's next call returns."""
+        version, internal, gauss = self.rng.getstate()
+        sd = dict(self._arguments())
+        sd["rng"] = {"version": int(version), "state": [int(x) for x in internal], "gauss_next": [] if gauss is None else [float(gauss)]}
+        return sd
+
+    def load_state_dict(self, sd):
+        """Take a state_dict's generator state.  The constructor's arguments must be the state's (a mutated key's list too; a key that
+        draws from the generator must be one here as well): ValueError otherwise, naming the field with both values, and nothing
+        changes."""
+        if not isinstance(sd, dict):
+            raise ValueError("PBTScheduler.load_state_dict: a state dict is a dict (got a %s)" % type(sd).__name__)
+        bad = ["%s is %r in the state and %r in this object" % (k, sd.get(k, "missing"), v) for k, v in self._arguments() if sd.get(k, None) != v]
+        rng = sd.get("rng")
+        ok = isinstance(rng, dict) and isinstance(rng.get("version"), int) and isinstance(rng.get("state"), list) and \
+            all(isinstance(x, int) for x in rng["state"]) and isinstance(rng.get("gauss_next"), list) and len(rng["gauss_next"]) <= 1
+        if not ok:
+            bad.append("rng must hold version (int), state (a list of ints) and gauss_next (a list of at most one float)")
+        if bad:
+            raise ValueError("PBTScheduler.load_state_dict: " + "; ".join(bad))
+        probe = random.Random()
+        try:  # (a state of the wrong length or version is refused by the generator itself: try it on a scratch one first)
+            probe.setstate((rng["version"], tuple(rng["state"]), rng["gauss_next"][0] if rng["gauss_next"] else None))
+        except (TypeError, ValueError) as ex:
+            raise ValueError("PBTScheduler.load_state_dict: rng is no generator state (%s)" % ex)
+        self.rng.setstate(probe.getstate())
+        return self
 
     def quantiles(self, scores):
         """(bottom, top): member indices of the lowest / highest scoring quantile (ties broken by index; disjoint)."""

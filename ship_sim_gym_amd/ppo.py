@@ -5,7 +5,8 @@ The reference's PPO2 runs GAE and noptepochs x nminibatches of {loss, backward, 
 (train/stable_baselines/ppo.py:90); train/ppo_torch.py does the same in eager PyTorch.  ``NativePPO`` does it on the packed parameter
 buffer of a ``NativePolicy``: Adam writes ``policy.params`` in place, so the next ``rollout_policy`` acts with the new weights (do NOT
 call ``policy.refresh()`` afterwards: that would copy the module's stale parameters back).  ``load_into(net)`` copies them into the
-``nn.Module`` (checkpoints).  It owns the Adam moments and the workspace.
+``nn.Module``.  It owns the Adam moments and the workspace; ``state_dict()`` / ``load_state_dict()`` save and restore what the next
+update depends on (with ``NativePolicy.state_dict()`` for the parameters; ship_sim_gym_amd/checkpoint.py writes the file).
 
 A batch is the dict ``ShipVecEnv.rollout_policy`` returns (obs f32 [K, N, D], act i32, logp / val f32, rew f64, done u8 [K, N], last_val
 f32 [N]); ``gae`` adds "adv" and "ret" (f32 [K, N]) to it.  Sample i of the flattened batch is (t, e) = divmod(i, N).
@@ -26,7 +27,7 @@ a return of 0; ``gae_boot_reference`` restates that walk and its statistics in n
 
 ``perm_seed`` lets the library draw the minibatch permutations (ssg_ppo_perm): ``update(batch, None, ...)`` then shuffles as PPO2's learn
 does per epoch (np.random.shuffle(inds), train/stable_baselines/ppo.py:90), each row a counter-based permutation keyed by (perm_seed,
-``updates``, ``member``, epoch) — the object's count of update() calls, kept beside ``step`` and settable from a checkpoint.
+``updates``, ``member``, epoch) — the object's count of update() calls, kept beside ``step`` and restored by ``load_state_dict``.
 ``draw_perm`` returns such rows, ``host_perm`` is the library's host restatement and ``perm_reference`` the numpy one.  The stream is the
 library's own: it is not seed-compatible with numpy or torch.
 """
@@ -48,6 +49,7 @@ def chunk_split(n, minibatches):
 
 
 ADV_NORM_MODES = {"batch": N.ADV_NORM_BATCH, "minibatch": N.ADV_NORM_MINIBATCH}
+HP_FIELDS = tuple(name for name, _ in N.PpoHparams._fields_ if name != "struct_size")  # every field of ssg_ppo_hparams that is a setting
 
 
 def adv_norm_mode(name, who):
@@ -284,7 +286,7 @@ class NativePPO(DeviceTrainer):
         # the member this object stands for (a population member's twin passes its index) and the update() calls so far
         self.perm_seed = None if perm_seed is None else int(perm_seed)
         self.member = int(member)
-        self.updates = 0  # calls of update(); like `step`, a checkpoint may set it
+        self.updates = 0  # calls of update(); like `step`, load_state_dict() sets it
         # "batch": the advantages are normalised once per rollout (gae()'s statistics); "minibatch": inside every minibatch, PPO2's rule
         self.adv_norm = adv_norm
         self._adv_mode = adv_norm_mode(adv_norm, "NativePPO")
@@ -512,3 +514,43 @@ class NativePPO(DeviceTrainer):
     def load_into(self, net):
         """Copy the packed parameters into `net` (shaped like the policy: its parameters in torch.cat order)."""
         return load_packed(self.policy.params, net, "NativePPO.load_into: the module has %%d parameters, the policy %d" % self.n_params)
+
+    # ------------------------------------------------------------------------------------------------
+    # state (ship_sim_gym_amd/checkpoint.py)
+    # ------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        """What the next update() depends on besides the policy and the batch (CPU copies; plain data only): the Adam moments, ``step``,
+        ``updates``, the KL coefficient and whether the KL term is on, every field of ``hp``, the extended terms' settings, ``adv_norm``,
+        ``perm_seed`` (with ``has_perm_seed``: the state holds no None) and ``member``.
+
+        The workspace is NOT state.  A checkpoint is taken between an update() and the next rollout; the only thing the workspace
+        carries from one call to another is the advantage statistics gae() writes into its head for the update() that follows, and the
+        next gae() rewrites them before anything reads them.  The per-minibatch scratch of adv_norm="minibatch" is rewritten by every
+        minibatch in the same way.  The policy's parameters are the policy's state (``NativePolicy.state_dict``)."""
+        return {"adam_mv": self.adam_mv.detach().cpu().clone(), "step": int(self.step), "updates": int(self.updates),
+                "kl_coef": self.kl_coef.detach().cpu().clone(), "kl_on": bool(self._kl_on),
+                "hp": {k: float(getattr(self.hp, k)) for k in HP_FIELDS},
+                "vf_clip": self.vf_clip, "max_grad_norm": self.max_grad_norm, "kl_target": self.kl_target, "adv_norm": self.adv_norm,
+                "has_perm_seed": self.perm_seed is not None, "perm_seed": int(self.perm_seed or 0), "member": int(self.member)}
+
+    def load_state_dict(self, sd):
+        """Become the trainer the state was taken from.  Checked first, all of it: the moments' and the coefficient's shape and dtype,
+        ``adv_norm`` (the mode and its scratch are made at construction: it must be the state's), the types of everything else.  A
+        mismatch raises ValueError naming the field with both values and leaves this object as it was.  Then the tensors are copied in
+        place and the counters and settings taken over."""
+        from .checkpoint import check_state, check_values
+        who = "NativePPO.load_state_dict"
+        check_state(who, sd, [("adv_norm", self.adv_norm)], [("adam_mv", self.adam_mv), ("kl_coef", self.kl_coef)])
+        num = (int, float)
+        check_values(who, sd, [("step", int), ("updates", int), ("kl_on", bool), ("hp", dict), ("vf_clip", num), ("max_grad_norm", num),
+                               ("kl_target", num), ("has_perm_seed", bool), ("perm_seed", int), ("member", int)])
+        check_values(who + ": hp", sd["hp"], [(k, num) for k in HP_FIELDS])
+        self.adam_mv.copy_(sd["adam_mv"])
+        self.kl_coef.copy_(sd["kl_coef"])
+        self.step, self.updates, self._kl_on = int(sd["step"]), int(sd["updates"]), bool(sd["kl_on"])
+        for k in HP_FIELDS:
+            setattr(self.hp, k, float(sd["hp"][k]))
+        self.vf_clip, self.max_grad_norm, self.kl_target = float(sd["vf_clip"]), float(sd["max_grad_norm"]), float(sd["kl_target"])
+        self.perm_seed = int(sd["perm_seed"]) if sd["has_perm_seed"] else None
+        self.member = int(sd["member"])
+        return self

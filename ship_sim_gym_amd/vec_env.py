@@ -462,11 +462,116 @@ class ShipVecEnv(*_BASES):
         return {"sum_return": float(s[0]) / 100.0, "sum_length": int(s[1]), "episodes": int(s[2]), "goals_hit": int(s[3])}
 
     # ------------------------------------------------------------------------------------------------
+    # snapshot / restore (ship_sim_gym_amd/checkpoint.py's "env" section)
+    # ------------------------------------------------------------------------------------------------
+    def fingerprint(self):
+        """The configuration a snapshot belongs to, as plain data: a snapshot is restored only into an env of the same fingerprint."""
+        c = self.cfg
+        return {"num_envs": int(self.num_envs), "history": int(c.history), "n_beams": int(c.n_beams), "n_ships": int(c.n_ships),
+                "map_mode": str(self.map_mode), "env_id_base": int(self.env_id_base), "bounds": [float(b) for b in self.bounds],
+                "max_steps": int(c.max_steps), "flags": int(c.flags), "n_goals": int(c.n_goals), "dt": float(c.dt),
+                "state_nbytes": int(self.state.numel()), "out_nbytes": int(self._out_nbytes)}
+
+    def check_snapshot_supported(self, what):
+        """NotImplementedError for the handles whose launches depend on host state inside the library's handle."""
+        why = None
+        if self.n_ships != 1:
+            why = "n_ships = %d: the contact solver's queue, memo generation and bank epoch live in the handle" % self.n_ships
+        elif self.map_mode != "bank":
+            why = "map_mode = %r: %s" % (self.map_mode, "the rings' refill credit and seed live in the handle" if self.map_mode == "fresh_device"
+                                         else "the worlds are drawn on the host from the global random streams")
+        elif int(self.cfg.history) > 2:
+            why = "history = %d: only handles with history <= 2 launch with constant arguments" % int(self.cfg.history)
+        elif self.rllib:
+            why = "rllib = True: which envs await their reset_at is kept on the host"
+        if why is not None:
+            raise NotImplementedError("ShipVecEnv.%s: not supported for this handle (%s); supported: n_ships = 1, map_mode = 'bank', "
+                                      "history <= 2, rllib = False" % (what, why))
+
+    def snapshot(self):
+        """The env's whole mutable state as plain data (CPU tensors, ints, floats, strings, lists, dicts), taken between two calls:
+        ``state`` (the state blob: every column, the episode counters of ``stats()``), ``out`` (the output block: obs | reward | done
+        | flags, of which the next policy launch reads obs), ``bank`` with ``n_maps``, and ``fingerprint``.  ``restore`` on an env of
+        the same fingerprint makes every later step, rollout and statistic bit for bit what this env goes on to compute.
+
+        Supported: one ship, map_mode="bank", history <= 2, rllib=False — the handles whose launches take constant arguments
+        (include/shipsim.h, at ssg_rollout).  Anything else raises NotImplementedError before anything is touched.
+
+        For these handles the blob, the output rows and the bank are all there is.  The host-side fields of ``struct ssg_handle``
+        (csrc/shipsim_api.cpp) and why none of them is state here:
+        * cfg, dev, n_pad, the off_* offsets, nbytes, block, lds, lds_bytes: functions of the configuration and of n_maps; ``restore``
+          re-installs the bank through ``set_bank``, which derives them again;
+        * state, bank, n_maps: pointers and a count; the tensors behind them are what the snapshot holds;
+        * prepared, policy_prepared, ppo_prepared, policy_filter_prepared, policy_boot_prepared: "the kernel's LDS limit is set", set
+          again on demand;
+        * zeroed: "the blob was zeroed by a full reset"; ``restore`` runs the env's first full reset itself when none has happened,
+          so that a later ``reset_tensor()`` keeps the restored counters as it keeps the original's;
+        * remap_pending: set when a bank shrinks; the remap it asks for takes map ids modulo n_maps, which the restored ids satisfy;
+        * dyn, dyn_queue_valid, dyn_seq, n_classify, masked_resets_since_step, memo_gen, memo_clear_pending, memo_steps, the
+          off_dyn_* offsets: config 4 only (n_ships = 4);
+        * ring_ready, ring_seed, ring_width_frac, ring_credit, off_ring_*: map_ring only (map_mode="fresh_device");
+        * time_kernels, t_dyn_ms, t_step_ms, t_steps: a measurement aid's accumulators;
+        * host_ev, host_ev_made: completion events of the numpy protocols' copies; no step may be in flight (checked);
+        * pop_sizes, dev_slices, slice_max, slice_min, flt, tob, adv_norm_*: bindings (population slices, observation filter,
+          time-out bootstrap, advantage normalisation) that their owners bind again; their own state is their owners';
+        * err: the last error's text.
+        Not saved either: ``term_obs`` and the time-out bootstrap's rows, which a step or a rollout writes before anyone reads them."""
+        self.check_snapshot_supported("snapshot")
+        self._no_step_in_flight("snapshot")
+        return {"fingerprint": self.fingerprint(), "state": self.state.detach().cpu().clone(), "out": self._out_blob.detach().cpu().clone(),
+                "bank": self.bank.detach().cpu().clone(), "n_maps": int(self.n_maps)}
+
+    def _no_step_in_flight(self, what):
+        if self._host is not None and self._host["inflight"] is not None:
+            raise N.ShipSimError("ShipVecEnv.%s: a step_async is in flight; call step_wait first" % what)
+
+    def restore(self, snap):
+        """Put a ``snapshot()`` back, in place: the state blob, the output block and the bank keep their addresses, so the tensors
+        (``obs``, ``reward``, ``done``, ``flags``, ``field()`` views) and the pointers this env handed out stay valid; the bank is
+        re-installed through ``set_bank`` (a bank of another n_maps replaces the tensor).  Checked first: NotImplementedError for an
+        unsupported handle, ValueError for a snapshot of another fingerprint (every differing key with both values) or with tensors
+        of the wrong size — and then nothing has changed."""
+        torch = _torch()
+        self.check_snapshot_supported("restore")
+        self._no_step_in_flight("restore")
+        if not isinstance(snap, dict) or not isinstance(snap.get("fingerprint"), dict):
+            raise ValueError("ShipVecEnv.restore: not a snapshot (no fingerprint)")
+        mine, theirs = self.fingerprint(), snap["fingerprint"]
+        bad = ["%s is %r in the snapshot and %r in this env" % (k, theirs.get(k, "missing"), mine.get(k, "missing"))
+               for k in sorted(set(mine) | set(theirs)) if k not in theirs or k not in mine or theirs[k] != mine[k]]
+        state, out, bank, n_maps = snap.get("state"), snap.get("out"), snap.get("bank"), snap.get("n_maps")
+        for name, t, dt, shape in (("state", state, torch.uint8, (self.state.numel(),)), ("out", out, torch.uint8, (self._out_nbytes,))):
+            if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape:
+                bad.append("%s must be a %s tensor %s" % (name, dt, shape))
+        if (not torch.is_tensor(bank) or bank.dtype != torch.float64 or bank.dim() != 2 or int(bank.shape[1]) != N.MAP_STRIDE
+                or isinstance(n_maps, bool) or not isinstance(n_maps, int) or int(bank.shape[0]) != n_maps or n_maps < 1):
+            bad.append("bank must be a float64 tensor [n_maps, %d] with n_maps >= 1" % N.MAP_STRIDE)
+        if bad:
+            raise ValueError("ShipVecEnv.restore: " + "; ".join(bad))
+        with torch.cuda.device(self.device):
+            if not getattr(self, "_full_reset_done", False):
+                self.reset_tensor()  # (the handle's first full reset zeroes the blob: let it happen before the blob is written)
+            self.state.copy_(state)
+            self._out_blob.copy_(out)
+            new_bank = bank.contiguous().to(self.device)
+            same_shape = tuple(self.bank.shape) == tuple(new_bank.shape)
+            if not (same_shape and torch.equal(self.bank, new_bank)):
+                self.bank_polys = self.bank_goals = None  # (host copies, if any, no longer describe the bank)
+            if same_shape:
+                self.bank.copy_(new_bank)
+                new_bank = self.bank
+            self.set_bank(new_bank)
+        self._pending = None
+        return self
+
+    # ------------------------------------------------------------------------------------------------
     # tensor API (zero-copy; what a GPU-resident policy should use)
     # ------------------------------------------------------------------------------------------------
     def reset_tensor(self, mask=None, map_ids=None):
         torch = _torch()
         mp, ip = self._mask_ptr(mask, "reset_tensor"), self._ids_ptr(map_ids, "reset_tensor")
+        if mask is None:
+            self._full_reset_done = True
         with torch.cuda.device(self.device):
             if self.map_mode == "fresh" and map_ids is None:
                 ids = torch.arange(self.num_envs, dtype=torch.int32, device=self.device)

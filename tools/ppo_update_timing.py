@@ -9,7 +9,7 @@ every update from the same parameters' values (their own copies) and draw their 
 line on stdout.  The kernels alone: `rocprofv3 --kernel-trace --stats -- python tools/ppo_update_timing.py --only native` (tools/README.md).
 
     python tools/ppo_update_timing.py [--configs 65536x32,4096x64] [--repeats 7] [--only torch|native] [--ext] [--separate-value] [--ret-filter]
-                                      [--adv-norm] [--perm] [--timeout-bootstrap]
+                                      [--adv-norm] [--perm] [--timeout-bootstrap] [--checkpoint]
 
 --ext adds, in the same run, the extended update (NativePPO with vf_clip 0.2, max_grad_norm 0.5, kl_coef 1.0, kl_target 0.01: GAE, the
 ssg_ppo_dist launch, ssg_ppo_update_ext) as the path "native_ext", and the ssg_ppo_dist launch alone as "dist".
@@ -26,6 +26,11 @@ torch.randperm per epoch, stacked), "perm_native" (NativePPO.draw_perm alone: ss
 peak device memory above what was allocated before it (torch's allocator statistics; the result tensor included), in bytes.
 --timeout-bootstrap adds, in the same run and alternating with the others: "gae_plain" (ssg_ppo_gae alone) and "gae_boot"
 (ssg_ppo_gae_boot alone, on the same batch plus a "boot" buffer that holds a value at a tenth of the samples and marks them done).
+--checkpoint adds, in the same run and alternating with the others, "checkpoint_save": one ship_sim_gym_amd/checkpoint.py save of what
+train/ppo_torch.py --save writes between two updates (the policy, the trainer, the env's snapshot, an observation and a return filter, a
+loop section), host wall-clock milliseconds from the first state_dict() to the renamed file (device-to-host copies, pickling and the
+file system; the path is under --checkpoint-dir, default the system's temporary directory), to set against "native", the GAE + update
+of the same process; and the file's size in bytes.  What --save-every 1 costs per update is the first against the second.
 """
 import argparse
 import importlib.util
@@ -99,8 +104,18 @@ def _peak_bytes(fn):
     return int(peak)
 
 
+def _wall_ms(fn):
+    """Host wall-clock milliseconds of fn() between two synchronizes (for work that is mostly on the host)."""
+    import time
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
 def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext=False, separate_value=False, ret_filter=False,
-            adv_norm=False, perm=False, timeout_bootstrap=False):
+            adv_norm=False, perm=False, timeout_bootstrap=False, checkpoint=False, checkpoint_dir=None):
     from ship_sim_gym_amd.policy import NativePolicy
     from ship_sim_gym_amd.ppo import NativePPO
     torch.manual_seed(0)
@@ -200,7 +215,25 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
     def draw_native():
         return ppo_p.draw_perm(n, epochs)
 
+    ckpt_path = None
+    if checkpoint:
+        import tempfile
+        from ship_sim_gym_amd import checkpoint as ckpt_mod
+        from ship_sim_gym_amd.obs_filter import ObsFilter
+        oflt = ObsFilter(env)  # (not bound: its state is saved, whatever it holds)
+        ckpt_path = os.path.join(checkpoint_dir or tempfile.gettempdir(), "ppo_update_timing_%d_%dx%d.ckpt" % (os.getpid(), envs, horizon))
+        g_c = torch.Generator(device=dev)
+        g_c.manual_seed(1)
+
+        def run_checkpoint_save():
+            ckpt_mod.save(ckpt_path, {"policy": pol.state_dict(), "trainer": ppo.state_dict(), "env": env.snapshot(),
+                                      "obs_filter": oflt.state_dict(), "ret_filter": rflt.state_dict(),
+                                      "loop": {"update": 0, "gen_state": g_c.get_state().cpu().clone(), "history": [], "best": float("-inf")},
+                                      "config": {"envs": envs, "horizon": horizon}})
+
     paths = [(k, f) for k, f in (("torch", run_torch), ("native", run_native)) if only in (None, k)]
+    if checkpoint:
+        paths.append(("checkpoint_save", run_checkpoint_save))
     if adv_norm:
         paths.append(("native_mbnorm", run_native_mbnorm))
     if perm:
@@ -217,12 +250,13 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
         paths += [("gae", lambda: ppo.gae(dict(b))), ("ret_gae", lambda: ppo.gae(dict(b), return_filter=rflt)),
                   ("ret_frozen", lambda: rfrozen.apply(dict(b))), ("ret_apply", lambda: rflt.apply(dict(b))), ("native_ret", run_native_ret)]
     times = {k: [] for k, _ in paths}
+    timer = {"checkpoint_save": _wall_ms}  # (a save is host work: HIP events would bracket only its copies)
     for _ in range(2):
         for k, f in paths:
-            _timed(f)
+            timer.get(k, _timed)(f)
     for _ in range(repeats):
         for k, f in paths:
-            times[k].append(_timed(f))
+            times[k].append(timer.get(k, _timed)(f))
     peaks = {"perm_torch_peak_bytes": _peak_bytes(draw_torch), "perm_native_peak_bytes": _peak_bytes(draw_native)} if perm else {}
     env.close()
     out = {"envs": envs, "separate_value": bool(separate_value), "horizon": horizon, "epochs": epochs, "minibatches": minibatches, "samples_per_minibatch": -(-n // minibatches)}
@@ -230,6 +264,9 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
         out[k + "_ms_per_update"] = statistics.median(v)
         out[k + "_ms_all"] = [round(x, 3) for x in v]
     out.update(peaks)
+    if ckpt_path is not None:
+        out["checkpoint_file_bytes"] = os.path.getsize(ckpt_path)
+        os.remove(ckpt_path)
     if "torch" in times and "native" in times:
         out["speedup"] = out["torch_ms_per_update"] / out["native_ms_per_update"]
     return out
@@ -248,10 +285,14 @@ def main():
     ap.add_argument("--perm", action="store_true", help="also time the permutation draws alone (torch's and the library's), the whole GAE + "
                                                         "update with the library drawing, and each draw's peak memory")
     ap.add_argument("--timeout-bootstrap", action="store_true", help="also time ssg_ppo_gae_boot against ssg_ppo_gae, each alone")
+    ap.add_argument("--checkpoint", action="store_true", help="also time one checkpoint save (policy, trainer, env, both filters) and report "
+                                                              "the file's size, next to the GAE + update of the same process")
+    ap.add_argument("--checkpoint-dir", default=None, help="where --checkpoint writes its file (default: the system's temporary directory)")
     a = ap.parse_args()
     mod = _ppo()
     res = [measure(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.repeats, a.only, "cuda:0", ext=a.ext, separate_value=sep, ret_filter=a.ret_filter,
-                   adv_norm=a.adv_norm, perm=a.perm, timeout_bootstrap=a.timeout_bootstrap)
+                   adv_norm=a.adv_norm, perm=a.perm, timeout_bootstrap=a.timeout_bootstrap, checkpoint=a.checkpoint,
+                   checkpoint_dir=a.checkpoint_dir)
            for c in a.configs.split(",") for sep in ([False, True] if a.separate_value else [False])]
     print(json.dumps({"ppo_update_timing": res}))
 

@@ -2,11 +2,17 @@
 """Evaluate a policy for whole episodes on the device: the reference's train/rllib/rollout.py:8-26 (compute_action, env.step until
 done, "Episode reward"), and the ``model.predict(obs, deterministic=True)`` loop Stable-Baselines users write, against this package.
 
-    python train/evaluate_native.py --envs 4096 --episodes 4 [--checkpoint net.pt] [--sampled] [--separate-value] [--seed 0]
+    python train/evaluate_native.py --envs 4096 --episodes 4 [--checkpoint FILE [--member M]] [--sampled] [--separate-value] [--seed 0]
                                      [--obs-filter FILE]
 
-Builds train/ppo_torch.py's ActorCritic — loaded from ``--checkpoint`` (a ``state_dict`` saved by ``torch.save``) or with seeded random
-weights — and runs it on ``--envs`` envs until every env has finished ``--episodes`` episodes (ship_sim_gym_amd/evaluate.py: one
+``--checkpoint FILE`` is a checkpoint of train/ppo_torch.py or train/pbt_native.py (``--save`` / ``--save-best``;
+ship_sim_gym_amd/checkpoint.py): the architecture comes from the file (``--separate-value`` is unnecessary, and refused when it
+contradicts the file), the beam count follows the policy's observation width, and the file's observation filter is applied frozen
+unless ``--obs-filter FILE`` overrides it.  A population file evaluates every member, one table row each, on ``--envs`` / P envs per
+member; ``--member M`` evaluates that member alone on all of them.  A plain module ``state_dict`` saved by ``torch.save`` works as
+before: it is loaded into train/ppo_torch.py's ActorCritic.  Without ``--checkpoint`` the weights are seeded random ones.
+
+The policy runs on ``--envs`` envs until every env has finished ``--episodes`` episodes (ship_sim_gym_amd/evaluate.py: one
 policy launch, one step and one accounting launch per step, enqueued from C).  The action is the arg-max by default, a draw with
 ``--sampled``.  Every env contributes exactly its first ``--episodes`` episodes, so short episodes are not over-weighted.  Prints one
 row per policy: episodes, mean return and length, how the episodes ended (collision, out of bounds, time-out, no goals left; not
@@ -33,7 +39,11 @@ def _positive(text):
 
 def make_arg_parser():
     ap = argparse.ArgumentParser(description="Evaluate an ActorCritic for whole episodes on the device (the reference's rollout.py).")
-    ap.add_argument("--checkpoint", default=None, help="a state_dict saved by torch.save; random weights otherwise")
+    ap.add_argument("--checkpoint", default=None, metavar="FILE",
+                    help="a checkpoint written by the trainers' --save / --save-best, or a module state_dict saved by torch.save; random "
+                         "weights otherwise")
+    ap.add_argument("--member", type=int, default=None, metavar="M",
+                    help="of a population checkpoint: evaluate this member alone (default: every member, one row each)")
     ap.add_argument("--envs", type=_positive, default=4096)
     ap.add_argument("--episodes", type=_positive, default=4, help="episodes counted per env")
     ap.add_argument("--sampled", action="store_true", help="draw the actions (Philox keyed by --seed) instead of the arg-max")
@@ -49,26 +59,66 @@ def parse_args(argv=None):
     return make_arg_parser().parse_args(argv)
 
 
-def evaluate(envs=4096, episodes=4, checkpoint=None, sampled=False, separate_value=False, seed=0, device="cuda:0", log=print, obs_filter=None):
+def evaluate(envs=4096, episodes=4, checkpoint=None, sampled=False, separate_value=False, seed=0, device="cuda:0", log=print, obs_filter=None,
+             member=None, env_kw=None):
     import torch
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     from ppo_torch import ActorCritic
     from ship_gym.config import EnvConfig, GameConfig
+    from ship_sim_gym_amd import checkpoint as ckpt_mod
     from ship_sim_gym_amd.evaluate import NativeEvaluator, format_table
+    from ship_sim_gym_amd.obs_filter import ObsFilter
     from ship_sim_gym_amd.policy import NativePolicy
+    from ship_sim_gym_amd.population import NativePopulation
     from ship_sim_gym_amd.vec_env import ShipVecEnv
     torch.manual_seed(seed)
-    env = ShipVecEnv(envs, GameConfig, EnvConfig, device=device)
-    net = ActorCritic(env.states_history, env.action_space.n, separate_value=separate_value)
+    env_kw = dict(env_kw or {})
+    ckpt = None
     if checkpoint is not None:
-        net.load_state_dict(torch.load(checkpoint, map_location="cpu"))
-    net = net.to(env.device)
-    scale = torch.full((env.states_history,), float(max(env.bounds)), dtype=torch.float64, device=env.device)
-    policy = NativePolicy.from_actor_critic(net, scale)
-    if obs_filter is not None:
-        from ship_sim_gym_amd.obs_filter import ObsFilter
-        sd = torch.load(obs_filter, map_location="cpu")
-        flt = ObsFilter(env, n_members=int(sd["n_members"]), update=False).load_state_dict(sd)
+        content = ckpt_mod.read(checkpoint)  # (a checkpoint and a module's state_dict both load without running any code of the file's)
+        if ckpt_mod.is_checkpoint(content):
+            ckpt = ckpt_mod.validate(content, (), str(checkpoint))
+    if member is not None and (ckpt is None or "population" not in ckpt):
+        raise ValueError("evaluate: member picks a member of a population checkpoint; %s" % (
+            "no checkpoint was given" if checkpoint is None else "%s holds one policy" % checkpoint))
+    filter_sd = None
+    if ckpt is not None:
+        arch = ckpt["population"] if "population" in ckpt else ckpt["policy"]
+        if separate_value and not arch["separate_value"]:
+            raise ValueError("evaluate: separate_value contradicts %s, whose policy has a shared body" % checkpoint)
+        if "n_beams" not in env_kw:  # (the observation width is history * (6 + beams): the env must produce what the policy reads)
+            hist = int(EnvConfig.HISTORY_SIZE)
+            if arch["obs_dim"] % hist or arch["obs_dim"] // hist <= 6:
+                raise ValueError("evaluate: the file's obs_dim %d is no history %d x (6 + beams)" % (arch["obs_dim"], hist))
+            env_kw["n_beams"] = arch["obs_dim"] // hist - 6
+        filter_sd = ckpt.get("obs_filter")
+        if "population" in ckpt:
+            P = int(ckpt["population"]["n_members"])
+            if member is not None and not 0 <= int(member) < P:
+                raise ValueError("evaluate: member %d of a population of %d" % (member, P))
+            if member is None and envs % P:
+                raise ValueError("evaluate: %d envs do not split into the file's %d members" % (envs, P))
+    env = ShipVecEnv(envs, GameConfig, EnvConfig, device=device, **env_kw)
+    if ckpt is None:
+        net = ActorCritic(env.states_history, env.action_space.n, separate_value=separate_value)
+        if checkpoint is not None:
+            net.load_state_dict(content)
+        net = net.to(env.device)
+        scale = torch.full((env.states_history,), float(max(env.bounds)), dtype=torch.float64, device=env.device)
+        policy = NativePolicy.from_actor_critic(net, scale)
+    elif "population" in ckpt:
+        if member is not None:
+            policy = NativePolicy.from_state_dict(ckpt["population"], env.device, row=int(member))
+            if filter_sd is not None:  # that member's statistics, as a filter of one member
+                filter_sd = dict(filter_sd, state=filter_sd["state"][int(member): int(member) + 1].clone(), n_members=1)
+        else:
+            policy = NativePopulation.from_state_dict(ckpt["population"], env.device)
+    else:
+        policy = NativePolicy.from_state_dict(ckpt["policy"], env.device)
+    if obs_filter is not None:  # (overrides the checkpoint's)
+        filter_sd = torch.load(obs_filter, map_location="cpu")
+    if filter_sd is not None:
+        flt = ObsFilter(env, n_members=int(filter_sd["n_members"]), update=False).load_state_dict(filter_sd)
         env.set_obs_filter(flt)
     result = NativeEvaluator(env).evaluate(policy, episodes, greedy=not sampled, seed=seed)
     log(format_table(result))
@@ -83,4 +133,4 @@ def evaluate(envs=4096, episodes=4, checkpoint=None, sampled=False, separate_val
 if __name__ == "__main__":
     a = parse_args()
     evaluate(envs=a.envs, episodes=a.episodes, checkpoint=a.checkpoint, sampled=a.sampled, separate_value=a.separate_value, seed=a.seed,
-             device=a.device, obs_filter=a.obs_filter)
+             device=a.device, obs_filter=a.obs_filter, member=a.member)

@@ -59,6 +59,16 @@ returns, kept on the device per member (ship_sim_gym_amd/ret_filter.py; the rewa
 member's own gamma): one library call per rollout between the rollout and GAE.  The raw rewards, which episode_reward_mean reads, stay
 as they are; a member's statistics travel with its weights on an exploit, the per-env returns in flight stay with their envs.
 --reward-clip C clamps the normalised rewards to +-C (default 10; 0: none).
+
+--save FILE writes a checkpoint at the end (ship_sim_gym_amd/checkpoint.py; the reference's checkpoint_at_end, train/rllib/pbt.py:53),
+--save-every U also after every U updates (its checkpoint_freq, :54), --save-best FILE after every update in which the best member's
+episode_reward_mean exceeds the best so far (never after an update in which no episode ended; the file holds the whole population and
+names the member).  A file holds the population, the trainer, both filters, the env's snapshot, the scheduler with its generator, this
+loop's state (the torch generator, the score window and history, the exploit and re-slice logs, the current schedules, batch sizes and
+slices) and the run's arguments; it is written at the end of an update's iteration, after a perturbation that was due.  --resume FILE
+continues that run bit for bit: repeat the original command line and add --resume; --updates stays the TOTAL and may be raised, the
+--save* and --eval-* options may change, any other argument that differs from the file's is refused.  train/evaluate_native.py
+--checkpoint FILE evaluates such a file, every member or --member M.
 """
 import argparse
 import os
@@ -88,6 +98,34 @@ def initial_batch_sizes(sched, members):
 def clamp_schedule(num_sgd_iter, sgd_minibatch_size, samples, max_epochs):
     """The schedule as it is used: num_sgd_iter in [1, max_epochs], the minibatch size in [min(128, samples), samples]; ints."""
     return (max(1, min(int(max_epochs), int(num_sgd_iter))), max(min(128, int(samples)), min(int(samples), int(sgd_minibatch_size))))
+
+
+# what a resumed run may change: everything else in train()'s arguments is the run's configuration (the checkpoint's "config" section)
+CONFIG_EXEMPT = ("updates", "save", "save_every", "save_best", "resume", "eval_every", "eval_episodes", "log", "return_details")
+RESUME_SECTIONS = ("population", "trainer", "env", "scheduler", "loop", "config")
+
+
+def run_config(**kwargs):
+    """The "config" section of a run of train(**kwargs): its effective arguments (defaults filled in) without CONFIG_EXEMPT, as
+    plain data."""
+    import inspect
+    from ship_sim_gym_amd.checkpoint import plain_config
+    args = {k: p.default for k, p in inspect.signature(train).parameters.items()}
+    unknown = sorted(set(kwargs) - set(args))
+    if unknown:
+        raise TypeError("train() has no argument %s" % ", ".join(unknown))
+    args.update(kwargs)
+    return plain_config({k: v for k, v in args.items() if k not in CONFIG_EXEMPT})
+
+
+def plain_events(events):
+    """Exploit events as a checkpoint holds them: the mutation tuples as lists."""
+    return [dict(ev, mutations=[list(mu) for mu in ev["mutations"]]) for ev in events]
+
+
+def events_from_plain(events):
+    """plain_events undone: the events as perturb() returned them."""
+    return [dict(ev, mutations=[tuple(mu) for mu in ev["mutations"]]) for ev in events]
 
 
 def make_arg_parser():
@@ -136,6 +174,17 @@ def make_arg_parser():
                     help="GAE bootstraps an episode the clock ended from the value of its terminal observation instead of scoring it as a "
                          "return of 0; default: every done alike")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--hidden", type=int, default=64, help="width of the hidden layers (a multiple of 16 up to 128)")
+    ap.add_argument("--save", default=None, metavar="FILE",
+                    help="write a checkpoint at the end (ship_sim_gym_amd/checkpoint.py): the population, the trainer, both filters, the "
+                         "env, the scheduler and this loop's state — what --resume and train/evaluate_native.py --checkpoint read")
+    ap.add_argument("--save-every", type=int, default=0, metavar="U", help="also rewrite --save after every U updates (atomically); 0 = off")
+    ap.add_argument("--save-best", default=None, metavar="FILE",
+                    help="write a checkpoint after every update in which the best member's episode_reward_mean exceeds the best so far "
+                         "(the whole population; the file names the member)")
+    ap.add_argument("--resume", default=None, metavar="FILE",
+                    help="continue the run a checkpoint was saved from, bit for bit: repeat the original command line; --updates stays "
+                         "the TOTAL and may be raised")
     return ap
 
 
@@ -192,6 +241,10 @@ def parse_args(argv=None):
         ap.error("--reward-clip needs --norm-reward")
     if not a.reward_clip >= 0.0:
         ap.error("--reward-clip must be >= 0")
+    if a.save_every < 0:
+        ap.error("--save-every must be >= 0")
+    if a.save_every and not a.save:
+        ap.error("--save-every needs --save (the file it rewrites)")
     return a
 
 
@@ -199,14 +252,24 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
           pbt=True, device="cuda:0", log=print, return_details=False, kl_coeff=0.0, kl_target=0.01, vf_clip=0.0, max_grad_norm=0.0,
           separate_value=False, mutate_schedule=False, max_epochs=30, eval_every=0, eval_episodes=1, envs=None, mutate_batch=False,
           batch_shares=None, quantum=None, obs_filter=False, norm_reward=False, reward_clip=10.0, adv_norm="batch", perm="torch",
-          timeout_bootstrap=False):
+          timeout_bootstrap=False, hidden=64, env_kw=None, save=None, save_every=0, save_best=None, resume=None):
+    config = run_config(**dict(locals()))  # (first statement: the arguments, nothing else)
     import torch
     from ship_gym.config import EnvConfig, GameConfig
+    from ship_sim_gym_amd import checkpoint
     from ship_sim_gym_amd.population import NativePopulation, PBTScheduler, PopulationPPO, reference_mutations, slices_for_batch_sizes
     from ship_sim_gym_amd.ppo import chunk_split
     from ship_sim_gym_amd.vec_env import ShipVecEnv
-    from train.ppo_torch import ActorCritic
+    from train.ppo_torch import ActorCritic, open_resume
     from train.rllib_ppo import game_configuration
+
+    if save_every < 0 or (save_every and not save):
+        raise ValueError("train: save_every must be >= 0 and needs save (the file it rewrites)")
+    ckpt = None
+    if resume:  # (read and compared before any device work: a wrong command line costs nothing)
+        ckpt = open_resume(resume, config, RESUME_SECTIONS + (("obs_filter",) if obs_filter else ()) + (("ret_filter",) if norm_reward else ()),
+                           exempt=CONFIG_EXEMPT)
+    env_kw = dict(env_kw or {})
 
     if perm not in ("torch", "native"):
         raise ValueError("train: perm must be 'torch' or 'native' (got %r)" % (perm,))
@@ -230,14 +293,14 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
     gen.manual_seed(seed + 1)
     saved = {k: getattr(GameConfig, k) for k in ("FPS", "SPEED", "DEBUG", "BOUNDS")}
     try:  # (game_configuration writes the GameConfig class, as the reference's does; the env reads it once, here)
-        env = ShipVecEnv(n_total, game_configuration(speed=30, fps=1000, debug=False), EnvConfig, device=device, n_maps=64)
+        env = ShipVecEnv(n_total, game_configuration(speed=30, fps=1000, debug=False), EnvConfig, device=device, n_maps=64, **env_kw)
         # the held-out run's env (train/rllib/rollout.py:8-26): evaluation resets and steps it, the training envs keep their episodes
-        eval_env = ShipVecEnv(P * min(n, 256), GameConfig, EnvConfig, device=device, n_maps=64) if eval_every else None
+        eval_env = ShipVecEnv(P * min(n, 256), GameConfig, EnvConfig, device=device, n_maps=64, **env_kw) if eval_every else None
     finally:
         for k, v in saved.items():
             setattr(GameConfig, k, v)
     D, A = env.states_history, env.action_space.n
-    nets = [ActorCritic(D, A, separate_value=separate_value).to(dev) for _ in range(P)]
+    nets = [ActorCritic(D, A, hidden=hidden, separate_value=separate_value).to(dev) for _ in range(P)]
     scale = torch.full((D,), float(max(env.bounds)), dtype=torch.float64, device=dev)
     pop = NativePopulation.from_actor_critics(nets, scale)
     sched = PBTScheduler(P, seed=seed, perturbation_interval=perturb_every,
@@ -294,11 +357,62 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
             raise ValueError("train: %d epochs and %d minibatches for %d members" % (len(iters), len(counts), P))
         sizes = [chunk_split(member_samples[m], c)[0] for m, c in enumerate(counts)]
     perm_epochs = max_epochs if mutate_schedule else (max(iters) if per_member else epochs)
-    for u in range(1, updates + 1):
+    if save or save_best:
+        env.check_snapshot_supported("snapshot")  # (refuse now, not after the training, a handle that cannot be saved)
+    # --save-best: the best member's episode_reward_mean so far, the update and the member it belongs to; episodes ended per update
+    best, best_update, best_member, ended_log = float("-inf"), 0, -1, []
+    start = 1
+    if ckpt is not None:  # everything is built and bound as the configuration says; now the saved layout, then the saved state
+        loop = ckpt["loop"]
+        if sliced:  # (the layout the run had when it was saved, not the initial one)
+            batch_sizes, slices = list(loop["batch_sizes"]), [int(x) for x in loop["slices"]]
+            env.set_population_slices(slices)
+            member_samples = [horizon * x for x in slices]
+        if per_member:
+            iters, sizes = [int(x) for x in loop["iters"]], [int(x) for x in loop["sizes"]]
+            if not mutate_schedule:
+                counts = [int(x) for x in loop["counts"]]
+        pop.load_state_dict(ckpt["population"])
+        ppo.load_state_dict(ckpt["trainer"])
+        if flt is not None:
+            flt.load_state_dict(ckpt["obs_filter"])
+        if rflt is not None:
+            rflt.load_state_dict(ckpt["ret_filter"])
+        sched.load_state_dict(ckpt["scheduler"])
+        env.restore(ckpt["env"])
+        gen.set_state(loop["gen_state"])
+        window.copy_(loop["window"])
+        scores, history = [float(x) for x in loop["scores"]], [list(r) for r in loop["history"]]
+        exploits, reslices = events_from_plain(loop["exploits"]), [(int(r[0]), list(r[1])) for r in loop["reslices"]]
+        best, best_update, best_member = float(loop["best"]), int(loop["best_update"]), int(loop["best_member"])
+        ended_log = [int(x) for x in loop["episodes_ended"]]
+        start = int(loop["update"]) + 1
+        log("resumed from %s: %d updates done, continuing at update %d of %d" % (resume, start - 1, start, updates))
+
+    def write(path, u):
+        """The checkpoint after update u (and after its perturbation, when one was due): everything a resumed run needs."""
+        sections = {"config": config, "population": pop.state_dict(), "trainer": ppo.state_dict(), "env": env.snapshot(),
+                    "scheduler": sched.state_dict(),
+                    "loop": {"update": int(u), "gen_state": gen.get_state().cpu().clone(), "history": [list(r) for r in history],
+                             "scores": list(scores), "window": window.detach().cpu().clone(), "exploits": plain_events(exploits),
+                             "reslices": [[int(r[0]), list(r[1])] for r in reslices],
+                             "iters": list(iters) if per_member else [], "sizes": list(sizes) if per_member else [],
+                             "counts": list(counts) if per_member and not mutate_schedule else [],
+                             "batch_sizes": list(batch_sizes) if sliced else [], "slices": list(env.population_slices) if sliced else [],
+                             "best": float(best), "best_update": int(best_update), "best_member": int(best_member),
+                             "episodes_ended": list(ended_log)}}
+        if flt is not None:
+            sections["obs_filter"] = flt.state_dict()
+        if rflt is not None:
+            sections["ret_filter"] = rflt.state_dict()
+        checkpoint.save(path, sections)
+
+    for u in range(start, updates + 1):
         uniforms = torch.rand((horizon, n_total), generator=gen, device=dev)
         batch = env.rollout_population(pop, horizon, uniforms=uniforms, out=out)
         out = {k: v for k, v in batch.items() if k not in ("adv", "ret", "logp_all", "rew_norm", "rew_denom")}
-        window += ppo.episode_stats(batch)
+        ep = ppo.episode_stats(batch)
+        window += ep
         if rflt is not None:
             rflt.set_gamma(ppo.gamma)  # (the members' own discounts, whatever they currently are)
         ppo.gae(batch, return_filter=rflt)
@@ -322,6 +436,10 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
         scores = [w[m][0] / 100.0 / w[m][2] if w[m][2] else scores[m] for m in range(P)]
         history.append(list(scores))
         log("update %d  episode_reward_mean %s" % (u, " ".join("%d:%.3f" % (m, s) for m, s in enumerate(scores))))
+        ended_log.append(int(ep[:, 2].sum().item()))
+        new_best = ended_log[-1] > 0 and max(scores) > best  # (an update in which no episode ended never is one)
+        if new_best:
+            best, best_update, best_member = max(scores), u, scores.index(max(scores))
         if evaluator is not None and u % eval_every == 0:  # (printed only: PBT ranks by training episodes, as the reference does)
             r = evaluator.evaluate(pop, eval_episodes, greedy=True)
             evals.append((u, r["per_member"].cpu().tolist()))
@@ -364,7 +482,15 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
                 scores[ev["member"]] = scores[ev["source"]]
             exploits += events
             window.zero_()
+        if new_best and save_best:  # (after the perturbation, so that the file resumes like any other; the best member ranks top: a source, not a destination)
+            write(save_best, u)
+            log("update %d  member %d's episode_reward_mean %.3f is the best so far: saved to %s" % (u, best_member, best, save_best))
+        if save and save_every and u % save_every == 0:
+            write(save, u)
     torch.cuda.synchronize(dev)
+    if save:
+        write(save, max(updates, start - 1))
+        log("checkpoint after update %d saved to %s" % (max(updates, start - 1), save))
     pop.load_into(nets)
     details = {"params": pop.params.detach().clone(), "exploits": exploits, "nets": nets,
                "hparams": {"lambda": list(ppo.lam), "clip_param": list(ppo.clip), "lr": list(ppo.lr),
@@ -372,7 +498,9 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
                            "sgd_minibatch_size": list(sizes) if per_member else [chunk_split(samples, minibatches)[0]] * P},
                "member_steps": list(ppo.member_steps), "kl_coef": ppo.kl_coef.detach().cpu().tolist(), "evaluations": evals,
                "slices": list(env.population_slices) if sliced else [n] * P, "reslices": reslices,
-               "train_batch_size": list(batch_sizes) if sliced else [samples] * P}
+               "train_batch_size": list(batch_sizes) if sliced else [samples] * P,
+               "best": best, "best_update": best_update, "best_member": best_member, "episodes_ended": list(ended_log),
+               "env_state": env.state.detach().cpu().clone() if return_details else None}
     if flt is not None:
         details["obs_filter"] = flt.state_dict()
         log("observation filter: rows merged per member %s" % [int(c) for c in details["obs_filter"]["state"][:, 3, 0].tolist()])
@@ -393,7 +521,8 @@ def main(argv=None):
           kl_target=a.kl_target, vf_clip=a.vf_clip, max_grad_norm=a.max_grad_norm, separate_value=a.separate_value,
           mutate_schedule=a.mutate_schedule, max_epochs=a.max_epochs, eval_every=a.eval_every, eval_episodes=a.eval_episodes, envs=a.envs,
           mutate_batch=a.mutate_batch, batch_shares=a.batch_shares, quantum=a.quantum, obs_filter=a.obs_filter,
-          norm_reward=a.norm_reward, reward_clip=a.reward_clip, adv_norm=a.adv_norm, perm=a.perm, timeout_bootstrap=a.timeout_bootstrap)
+          norm_reward=a.norm_reward, reward_clip=a.reward_clip, adv_norm=a.adv_norm, perm=a.perm, timeout_bootstrap=a.timeout_bootstrap,
+          hidden=a.hidden, save=a.save, save_every=a.save_every, save_best=a.save_best, resume=a.resume)
 
 
 if __name__ == "__main__":

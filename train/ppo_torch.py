@@ -7,6 +7,7 @@ leave the GPU; the policy is a small MLP in fp32.
     python train/ppo_torch.py --envs 4096 --updates 20 [--mode eager|graph|pingpong|native] [--update torch|native] [--separate-value]
                               [--eval-every U --eval-episodes E] [--obs-filter [--save-obs-filter FILE]]
                               [--norm-reward [--reward-clip C]]
+                              [--save FILE [--save-every U]] [--save-best FILE] [--resume FILE]
 
 Four ways to run the rollout loop (the reference's `model.learn` -> runner.run(): one `env.step(actions)` per policy
 forward, train/stable_baselines/ppo.py:84-100,122-123) — same arithmetic, same results bit for bit:
@@ -46,6 +47,16 @@ gets a frozen view of the same statistics.  With ``--update native`` the per-upd
 of the per-env discounted return, kept on the device (ship_sim_gym_amd/ret_filter.py — the reward half of Stable-Baselines'
 VecNormalize, its default): one library call per rollout between ``rollout_policy`` and GAE; the raw rewards, which the logged
 statistics read, stay as they are.  ``--reward-clip C`` clamps the normalised rewards to +-C (default 10, VecNormalize's; 0: none).
+
+``--save FILE`` writes a checkpoint at the end (ship_sim_gym_amd/checkpoint.py; the reference's ``model.save``,
+train/stable_baselines/ppo.py:100), ``--save-every U`` also after every U updates, ``--save-best FILE`` after every update whose
+episode_reward_mean — the mean return of the episodes that ended during it — exceeds the best so far (the reference callback's
+best_model.pkl, :25-52; an update in which no episode ended never writes).  With ``--mode native --update native`` a file holds the
+policy, the trainer (Adam moments, step and update counts), both filters, the env's snapshot, this loop's state (the generator, the
+history, the best score) and the run's arguments, and ``--resume FILE`` continues that run bit for bit: repeat the original command
+line and add ``--resume``; ``--updates`` stays the TOTAL and may be raised, the ``--save*`` and ``--eval-*`` options may change, any
+other argument that differs from the file's is refused.  In the other modes ``--save`` writes the policy alone (the torch optimiser's
+state is out of scope), which train/evaluate_native.py ``--checkpoint FILE`` reads and ``--resume`` refuses.
 
 The sampling noise of a whole rollout is drawn in one call before it (uniforms [horizon, envs], inverse-CDF sampling inside
 the step), so a captured step holds no random-number generator state and replays exactly what the eager loop computes.
@@ -213,11 +224,55 @@ def rollout(shards, horizon, mode, gen, policy=None):
     return {k: cat("buf_" + k) for k in ("obs", "act", "logp", "val", "rew", "done")}
 
 
+# what a resumed run may change: everything else in train()'s arguments is the run's configuration (the checkpoint's "config" section)
+CONFIG_EXEMPT = ("updates", "save", "save_every", "save_best", "save_obs_filter", "resume", "eval_every", "eval_episodes", "eval_envs", "log",
+                 "return_details")
+RESUME_SECTIONS = ("policy", "trainer", "env", "loop", "config")
+
+
+def run_config(**kwargs):
+    """The "config" section of a run of train(**kwargs): its effective arguments (defaults filled in) without CONFIG_EXEMPT, as
+    plain data."""
+    import inspect
+    from ship_sim_gym_amd.checkpoint import plain_config
+    args = {k: p.default for k, p in inspect.signature(train).parameters.items()}
+    unknown = sorted(set(kwargs) - set(args))
+    if unknown:
+        raise TypeError("train() has no argument %s" % ", ".join(unknown))
+    args.update(kwargs)
+    return plain_config({k: v for k, v in args.items() if k not in CONFIG_EXEMPT})
+
+
+def open_resume(path, config, require=RESUME_SECTIONS, who="train", exempt=CONFIG_EXEMPT):
+    """Read the checkpoint a run resumes from and compare its configuration with this run's (host only, before any device work):
+    ValueError for a file that holds no trainer state, for a missing section, and for arguments that differ — every key, with both
+    values."""
+    from ship_sim_gym_amd import checkpoint
+    ckpt = checkpoint.load(path)
+    if "trainer" not in ckpt:
+        raise ValueError("%s: %s holds no trainer section: it was saved by a run whose update is not the device's (--mode native --update "
+                         "native), so it can be evaluated but not resumed" % (who, path))
+    checkpoint.validate(ckpt, require, str(path))
+    diff = checkpoint.config_differences(ckpt["config"], config)
+    if diff:
+        raise ValueError("%s: cannot resume from %s: the arguments differ from the file's config in %s (only %s may change)" % (
+            who, path, "; ".join("%s (the file has %r, this run %r)" % (k, ckpt["config"].get(k, "nothing"), config.get(k, "nothing")) for k in diff),
+            ", ".join(exempt)))
+    return ckpt
+
+
 def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, gamma=0.99, lam=0.95, clip=0.2,
           device="cuda:0", seed=0, log=print, mode="eager", return_details=False, env_kw=None, update="torch", separate_value=False,
           eval_every=0, eval_episodes=1, eval_envs=None, obs_filter=False, save_obs_filter=None,
-          norm_reward=False, reward_clip=10.0, adv_norm="batch", perm="torch", timeout_bootstrap=False):
+          norm_reward=False, reward_clip=10.0, adv_norm="batch", perm="torch", timeout_bootstrap=False, hidden=64,
+          save=None, save_every=0, save_best=None, resume=None):
+    config = run_config(**dict(locals()))  # (first statement: the arguments, nothing else)
     assert mode in ("eager", "graph", "pingpong", "native")
+    if save_every < 0 or (save_every and not save):
+        raise ValueError("save_every must be >= 0 and needs save (the file it rewrites)")
+    if resume and (mode != "native" or update != "native"):
+        raise ValueError("resume restores the device trainer's state: it needs mode='native' and update='native' (got mode=%r, update=%r)"
+                         % (mode, update))
     if perm not in ("torch", "native"):
         raise ValueError("perm must be 'torch' or 'native' (got %r)" % (perm,))
     if perm == "native" and update != "native":
@@ -243,14 +298,19 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         raise ValueError("update must be 'torch' or 'native' (got %r)" % (update,))
     if update == "native" and mode != "native":
         raise ValueError("update='native' runs on the native policy's packed parameters: it needs mode='native' (got mode=%r)" % (mode,))
+    from ship_sim_gym_amd import checkpoint
+    ckpt = None
+    if resume:  # (read and compared before any device work: a wrong command line costs nothing)
+        ckpt = open_resume(resume, config, RESUME_SECTIONS + (("obs_filter",) if obs_filter else ()) + (("ret_filter",) if norm_reward else ()))
     torch.manual_seed(seed)
     dev = torch.device(device)
     gen = torch.Generator(device=dev)
     gen.manual_seed(seed + 1)
-    probe = ShipVecEnv(1, GameConfig, EnvConfig, device=device, n_maps=1)
+    probe = ShipVecEnv(1, GameConfig, EnvConfig, device=device, n_maps=1,  # (the observation width follows the beam count)
+                       **{k: v for k, v in dict(env_kw or {}).items() if k == "n_beams"})
     D, A = probe.states_history, probe.action_space.n
     probe.close()
-    net = ActorCritic(D, A, separate_value=separate_value).to(dev)
+    net = ActorCritic(D, A, hidden=hidden, separate_value=separate_value).to(dev)
     opt = torch.optim.Adam(net.parameters(), lr=lr)
     shards = make_shards(envs, mode, net, device, horizon, env_kw=env_kw)
     for sh in shards:
@@ -289,7 +349,48 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         torch.cuda.synchronize()
     history, t_roll, t_upd, t_all0 = [], 0.0, 0.0, time.perf_counter()
     snapshots = []
-    for u in range(updates):
+    # --save-best (the reference callback's best_model.pkl, train/stable_baselines/ppo.py:25-52): an update's score is the mean return
+    # of the episodes that ended during it (-inf when none did, which never counts as a best)
+    ep_scores, best, best_update = [], float("-inf"), -1
+    if save or save_best:
+        if ppo is not None:
+            shards[0].env.check_snapshot_supported("snapshot")  # (refuse now, not after the training, a handle that cannot be saved)
+    st0 = {k: sum(sh.env.stats()[k] for sh in shards) for k in ("sum_return", "episodes")}
+    seen_episodes, seen_return = st0["episodes"], st0["sum_return"]
+    start = 0
+    if ckpt is not None:  # everything is built and bound as the configuration says; now take the saved state over
+        loop = ckpt["loop"]
+        policy.load_state_dict(ckpt["policy"])
+        ppo.load_state_dict(ckpt["trainer"])
+        if flt is not None:
+            flt.load_state_dict(ckpt["obs_filter"])
+        if rflt is not None:
+            rflt.load_state_dict(ckpt["ret_filter"])
+        shards[0].env.restore(ckpt["env"])
+        gen.set_state(loop["gen_state"])
+        history = [tuple(r) for r in loop["history"]]
+        ep_scores, best, best_update = list(loop["scores"]), float(loop["best"]), int(loop["best_update"])
+        seen_episodes, seen_return = int(loop["episodes"]), float(loop["sum_return"])
+        start = int(loop["update"]) + 1
+        log("resumed from %s: %d updates done, continuing at update %d of %d" % (resume, start, start, updates))
+
+    def write(path, u):
+        """The checkpoint after update u: everything a resumed run needs with the device update, else the policy (for evaluation)."""
+        sections = {"config": config,
+                    "loop": {"update": int(u), "gen_state": gen.get_state().cpu().clone(), "history": [list(r) for r in history],
+                             "scores": list(ep_scores), "best": float(best), "best_update": int(best_update),
+                             "episodes": int(seen_episodes), "sum_return": float(seen_return)}}
+        if ppo is not None:
+            sections.update(policy=policy.state_dict(), trainer=ppo.state_dict(), env=shards[0].env.snapshot())
+            if rflt is not None:
+                sections["ret_filter"] = rflt.state_dict()
+        else:  # (the torch update trains the module: pack it as evaluation reads it)
+            sections["policy"] = (policy if policy is not None else NativePolicy.from_actor_critic(net, shards[0].scale)).state_dict()
+        if flt is not None:
+            sections["obs_filter"] = flt.state_dict()
+        checkpoint.save(path, sections)
+
+    for u in range(start, updates):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         b = rollout(shards, horizon, mode, gen, policy)
@@ -357,6 +458,16 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         history.append((u, mean_ret, goals_per_ep, float(b["rew"].mean())))
         log("update %3d  episodes %8d  mean return so far %+.3f  goals/episode %.3f  mean step reward %+.4f" % (
             u, st["episodes"], mean_ret, goals_per_ep, history[-1][3]))
+        ended = st["episodes"] - seen_episodes
+        ep_scores.append((st["sum_return"] - seen_return) / ended if ended > 0 else float("-inf"))
+        seen_episodes, seen_return = st["episodes"], st["sum_return"]
+        if ep_scores[-1] > best:  # (an update in which no episode ended scores -inf: it never gets here)
+            best, best_update = ep_scores[-1], u
+            if save_best:
+                write(save_best, u)
+                log("update %3d  episode_reward_mean %+.3f over %d episodes: the best so far, saved to %s" % (u, best, ended, save_best))
+        if save and save_every and (u + 1) % save_every == 0:
+            write(save, u)
         if evaluator is not None and (u + 1) % eval_every == 0:
             r = evaluator.evaluate(policy, eval_episodes, greedy=True)
             evals.append((u, {k: (v[0] if hasattr(v, "__len__") else v) for k, v in r.items() if k not in ("per_env", "per_member")}))
@@ -366,15 +477,20 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
                     r["collision_rate"][0], r["out_of_bounds_rate"][0], r["max_steps_rate"][0]))
     torch.cuda.synchronize()
     t_all = time.perf_counter() - t_all0
+    if save:
+        write(save, max(updates, start) - 1)
+        log("checkpoint after update %d saved to %s" % (max(updates, start) - 1, save))
     if ppo is not None:
-        ppo.load_into(net)  # the module gets the device-trained parameters (details["params"], checkpoints)
-    steps = envs * horizon * updates
+        ppo.load_into(net)  # the module gets the device-trained parameters (details["params"])
+    steps = envs * horizon * max(0, updates - start)  # (this process's own; a resumed run did not step the updates it loaded)
     log("rollout (%s): %.1f M env-steps/s with the policy in the loop; whole training loop (rollout + PPO update): %.1f M env-steps/s" % (
         mode, steps / max(t_roll, 1e-9) / 1e6, steps / max(t_all, 1e-9) / 1e6))
     details = {"mode": mode, "rollout_env_steps_per_s": steps / max(t_roll, 1e-9), "training_env_steps_per_s": steps / max(t_all, 1e-9),
-               "rollout_us_per_step": t_roll * 1e6 / (horizon * updates), "rollout_seconds": t_roll, "update_seconds": t_upd, "total_seconds": t_all,
+               "rollout_us_per_step": t_roll * 1e6 / (horizon * max(1, updates - start)), "rollout_seconds": t_roll, "update_seconds": t_upd, "total_seconds": t_all,
                "snapshots": snapshots, "final_state": [env_columns(sh.env) for sh in shards] if return_details is True else None,
-               "params": [p.detach().clone() for p in net.parameters()] if return_details is True else None, "evaluations": evals}
+               "params": [p.detach().clone() for p in net.parameters()] if return_details is True else None, "evaluations": evals,
+               "episode_reward_mean": list(ep_scores), "best": best, "best_update": best_update,
+               "env_state": shards[0].env.state.detach().cpu().clone() if return_details is True else None}
     if flt is not None:
         details["obs_filter"] = flt.state_dict()
         if save_obs_filter:
@@ -418,6 +534,17 @@ def make_arg_parser():
     ap.add_argument("--timeout-bootstrap", action="store_true",
                     help="GAE bootstraps an episode the clock ended from the value of its terminal observation instead of scoring it as a "
                          "return of 0 (needs --mode native --update native); default: every done alike")
+    ap.add_argument("--hidden", type=int, default=64, help="width of the hidden layers (the native policy: a multiple of 16 up to 128)")
+    ap.add_argument("--save", default=None, metavar="FILE",
+                    help="write a checkpoint at the end (ship_sim_gym_amd/checkpoint.py): with --mode native --update native everything a "
+                         "--resume needs, else the policy alone, for train/evaluate_native.py --checkpoint")
+    ap.add_argument("--save-every", type=int, default=0, metavar="U", help="also rewrite --save after every U updates (atomically); 0 = off")
+    ap.add_argument("--save-best", default=None, metavar="FILE",
+                    help="write a checkpoint after every update whose episode_reward_mean (the mean return of the episodes that ended "
+                         "during it) exceeds the best so far")
+    ap.add_argument("--resume", default=None, metavar="FILE",
+                    help="continue the run a checkpoint was saved from, bit for bit (needs --mode native --update native): repeat the "
+                         "original command line; --updates stays the TOTAL and may be raised")
     return ap
 
 
@@ -445,6 +572,12 @@ def parse_args(argv=None):
         ap.error("--reward-clip needs --norm-reward")
     if not a.reward_clip >= 0.0:
         ap.error("--reward-clip must be >= 0")
+    if a.save_every < 0:
+        ap.error("--save-every must be >= 0")
+    if a.save_every and not a.save:
+        ap.error("--save-every needs --save (the file it rewrites)")
+    if a.resume and (a.mode != "native" or a.update != "native"):
+        ap.error("--resume needs --mode native --update native (it restores the device trainer's state)")
     return a
 
 
@@ -453,4 +586,5 @@ if __name__ == "__main__":
     train(envs=a.envs, updates=a.updates, horizon=a.horizon, mode=a.mode, update=a.update, separate_value=a.separate_value,
           eval_every=a.eval_every, eval_episodes=a.eval_episodes, obs_filter=a.obs_filter, save_obs_filter=a.save_obs_filter,
           norm_reward=a.norm_reward, reward_clip=a.reward_clip, adv_norm=a.adv_norm, perm=a.perm,
-          timeout_bootstrap=a.timeout_bootstrap)
+          timeout_bootstrap=a.timeout_bootstrap, hidden=a.hidden, save=a.save, save_every=a.save_every, save_best=a.save_best,
+          resume=a.resume)
