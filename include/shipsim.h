@@ -1278,6 +1278,78 @@ int ssg_pop_gae_boot(ssg_handle *h, const ssg_population *pop, const float *dev_
                      float *dev_adv_KN, float *dev_ret_KN, void *dev_workspace, size_t workspace_nbytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Data parallel (additions to ABI 9): one policy trained from the experience of W env shards
+ * The RLlib reference scripts collect experience on cpu_count() - 1 workers and train ONE policy from all of it
+ * (train/rllib/ppo.py:34-35, train/rllib/pbt.py:57-58); the Stable-Baselines script does the same over a SubprocVecEnv
+ * (train/stable_baselines/ppo.py:122-123).  Here every shard (a handle: a rank of ship_sim_gym_amd/sharding.py, or one of several handles
+ * of one process) runs ssg_ppo_gae and, per minibatch, ssg_ppo_grad / ssg_ppo_grad_ext on its own samples; the caller gathers the
+ * shards' rows (an all-gather, or a stack), and EVERY shard then runs the same two calls below on the same gathered rows in the same
+ * order.  Same arithmetic on same inputs: the parameters, moments and KL coefficient stay bit-identical on all shards with no
+ * parameter broadcast.  The library moves no data between devices; the gather is the caller's.
+ *
+ * Advantage statistics over the job.  ssg_ppo_gae leaves per-workgroup f64 partials of sum(adv) and sum(adv^2) at the start of the
+ * workspace's slots; ssg_ppo_adv_moments re-adds them in the order the statistics launch used and returns the shard's moments
+ * {S, Q, n, 0}.  The slots overwrite those partials once a gradient entry point runs: take the moments between GAE and the first
+ * gradient.  ssg_ppo_set_adv_moments sums the gathered rows in row order (f64) and writes
+ *   mean = S/n;  var = max(0, (Q - S*mean) / (n - 1));  std+ = (float)sqrt(var) + adv_eps;  {(float)mean, std+, 1/std+, 0}
+ * where ssg_ppo_gae wrote its own: with one row, its own shard's, the head of the workspace is bit for bit what ssg_ppo_gae left.
+ *
+ * Apply.  Row r of dev_rows (f32 [W][P + 8]) holds shard r's gradient of its LOCAL minibatch of M_r samples (the mean-loss gradient
+ * ssg_ppo_grad / ssg_ppo_grad_ext write; with the extended loss taken with max_grad_norm = 0, so unclipped and without a norm
+ * launch), then that shard's stats row (the plain loss's four columns zero-padded to 8).  With w_r = (float)((double)M_r / (double)sum M),
+ * formed on the host:
+ *   g[p] = w_0*row_0[p];   g[p] = g[p] + w_r*row_r[p]  for r = 1 .. W-1
+ * every product and every sum rounded to f32 on its own (no fused multiply-add): the mean-loss gradient of the job's minibatch.  Stats
+ * columns 0..4 are combined the same way; column 6 is the KL coefficient in use, columns 5 and 7 as ssg_ppo_update_ext writes them.
+ * One launch of ceil((P + 8) / 256) workgroups of 256, entry p on lane p % 256 of workgroup p / 256; without gradient-norm clipping it
+ * ends with Adam step `step` (ssg_ppo_adam's constants and formula).  With ext->max_grad_norm > 0 each workgroup also forms the f64
+ * sum of squares of its entries p < P (a halving tree), and the clip launch of ssg_ppo_update_ext follows: partials in index order,
+ * norm = (float)sqrt(sum), coef = min(1, max_grad_norm / (norm + 1e-6f)), Adam on g*coef.  With ext the running f32 sum of mean(KL)
+ * (a workspace word of this call's own: the shards' local gradient calls do not disturb it) is set on first_chunk and added to
+ * otherwise; with last_chunk, a coefficient and kl_target > 0 the adaptation launch follows, dividing that sum by n_chunks — the
+ * number of applies since first_chunk, this one included, which the caller states in the record.  With W = 1 all of this is bit
+ * for bit what one minibatch of ssg_ppo_update / ssg_ppo_update_ext does to the parameters, moments, stats row and coefficient.
+ * ------------------------------------------------------------------------------------------------- */
+#define SSG_DP_MAX_SHARDS 64
+typedef struct ssg_ppo_shards {
+    uint32_t struct_size;   /* sizeof(ssg_ppo_shards) */
+    int32_t n_shards;       /* W in 1..SSG_DP_MAX_SHARDS */
+    const float *dev_rows;  /* f32 [W][P + 8] on the device */
+    const int64_t *counts;  /* HOST int64 [W]: M_r >= 1, the samples of shard r's minibatch */
+    int32_t first_chunk;    /* the minibatch is the first of its epoch: the running KL sum restarts */
+    int32_t last_chunk;     /* ... the last of the update: with kl_target > 0 and a coefficient the adaptation follows */
+    int32_t n_chunks;       /* read with last_chunk when the adaptation runs: its divisor, >= 1 */
+    int32_t reserved;       /* 0 */
+} ssg_ppo_shards;
+
+/* Replaces: the first half of the advantage standardisation RLlib applies to the experience its workers collected
+ * (train/rllib/ppo.py:34-35: num_workers) — a shard's share of it.  Valid between ssg_ppo_gae / ssg_ppo_gae_boot over K x N and the
+ * next gradient entry point on the same workspace.  Writes dev_out4 (f64 [4] on the device) = {S = sum adv, Q = sum adv^2,
+ * (double)K*N, 0}.  One launch on `stream`.  SSG_ERR_BAD_ARG (nothing launched): NULL pointers, K < 1, N < 1 or a workspace too
+ * small for ssg_ppo_gae over N envs. */
+int ssg_ppo_adv_moments(ssg_handle *h, int K, int N, void *dev_workspace, size_t workspace_nbytes, double *dev_out4, void *stream);
+
+/* Replaces: the second half — the statistics of the whole job's advantages (train/rllib/pbt.py:57-58 trains one policy from all
+ * workers' samples), from the gathered moments dev_rows (f64 [n_shards][4], rows in shard order), into the workspace where the
+ * gradient entry points read them.  One launch, one lane.  A job of fewer than 2 samples has no unbiased std: the device refuses it
+ * by writing NaN statistics (a launch has no return code), which every later gradient shows.  SSG_ERR_BAD_ARG (nothing launched):
+ * NULL pointers, n_shards outside 1..SSG_DP_MAX_SHARDS, an adv_eps that is not finite, a workspace of fewer than 256 bytes. */
+int ssg_ppo_set_adv_moments(ssg_handle *h, int n_shards, const double *dev_rows /* [W][4] */, double adv_eps, void *dev_workspace,
+                            size_t workspace_nbytes, void *stream);
+
+/* Replaces: the SGD step RLlib's trainer takes on the batch gathered from its workers (train/rllib/ppo.py:34-35,
+ * train/rllib/pbt.py:57-58) and PPO2's over its SubprocVecEnv (train/stable_baselines/ppo.py:122-123): the apply described above.
+ * ext NULL: the plain loss (one launch, no workspace use beyond the check).  ext: its max_grad_norm, kl_target and dev_kl_coef are
+ * read (the batch pointers are not); one launch, two with max_grad_norm > 0, one more for the adaptation.  dev_stats (nullable):
+ * f32[8].  SSG_ERR_BAD_ARG (nothing launched): a bad policy, hparams, ext or shards record (struct_size, n_shards out of range,
+ * reserved != 0, n_chunks < 1 where it is read), NULL dev_rows, counts or dev_adam_mv, a count < 1, step < 1, a workspace too small
+ * (ssg_ppo_workspace_nbytes covers it), or SSG_ADV_NORM_MINIBATCH bound to the handle: per-minibatch statistics would have to be
+ * job-wide too, which is out of scope. */
+int ssg_ppo_apply_shards(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, const ssg_ppo_ext *ext /* nullable */,
+                         const ssg_ppo_shards *sh, float *dev_adam_mv, int64_t step, float *dev_stats /* nullable */,
+                         void *dev_workspace, size_t workspace_nbytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Host-side geometry (what pymunk's cffi exposed at reset time); no GPU needed.
  * ------------------------------------------------------------------------------------------------- */
 /* Replaces cpConvexHull as reached by pm.Poly(...) (models.py:96,180).  out_xy holds >= count pairs. */

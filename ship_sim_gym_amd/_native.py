@@ -77,7 +77,9 @@ EXPORTS = (
     "ssg_ppo_adv_norm_nbytes", "ssg_ppo_set_adv_norm", "ssg_ppo_get_adv_norm",
     "ssg_host_perm", "ssg_ppo_perm", "ssg_pop_perm",
     "ssg_set_timeout_boot", "ssg_get_timeout_boot", "ssg_timeout_values", "ssg_pop_timeout_values", "ssg_ppo_gae_boot", "ssg_pop_gae_boot",
+    "ssg_ppo_adv_moments", "ssg_ppo_set_adv_moments", "ssg_ppo_apply_shards",
 )
+DP_MAX_SHARDS = 64  # ssg_ppo_shards.n_shards at most
 
 
 class ShipSimError(RuntimeError):
@@ -177,6 +179,15 @@ class TimeoutBootRecord(C.Structure):
     [rows][n_envs][D], the values f32 [rows][stride]."""
     _fields_ = [
         ("struct_size", C.c_uint32), ("rows", C.c_int32), ("dev_term_obs_KND", C.c_void_p), ("dev_boot_KN", C.c_void_p),
+    ]
+
+
+class PpoShards(C.Structure):
+    """ssg_ppo_shards (ABI 9 addition): the gathered rows of one data-parallel minibatch — W, the device rows f32 [W][P + 8], the HOST
+    counts int64 [W], the chunk's place in its epoch and update, and the adaptation's divisor."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_shards", C.c_int32), ("dev_rows", C.c_void_p), ("counts", C.POINTER(C.c_int64)),
+        ("first_chunk", C.c_int32), ("last_chunk", C.c_int32), ("n_chunks", C.c_int32), ("reserved", C.c_int32),
     ]
 
 
@@ -294,6 +305,9 @@ def lib():
     L.ssg_pop_timeout_values.argtypes = [vp, pp, C.c_int, vp, vp, vp, C.c_int64, vp]
     L.ssg_ppo_gae_boot.argtypes = [vp, C.POINTER(PpoHparams), C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     L.ssg_pop_gae_boot.argtypes = [vp, pp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.ssg_ppo_adv_moments.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, vp, vp]
+    L.ssg_ppo_set_adv_moments.argtypes = [vp, C.c_int, vp, C.c_double, vp, C.c_size_t, vp]
+    L.ssg_ppo_apply_shards.argtypes = [vp, C.POINTER(Policy), hp, xp, C.POINTER(PpoShards), vp, C.c_int64, vp, vp, C.c_size_t, vp]
     L.ssg_render.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, vp]
     L.ssg_dyn_invalidate.argtypes = [vp, vp, vp]
     L.ssg_host_convex_hull.argtypes = [C.c_int, dp, dp, ip]

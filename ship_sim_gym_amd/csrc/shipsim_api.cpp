@@ -2139,6 +2139,91 @@ int ssg_ppo_update_ext(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hpara
                                   dev_workspace, workspace_nbytes), stream);
 }
 
+// ABI 9 additions: data parallel — the job-wide advantage statistics and the apply of W shards' gradient rows.  Refusals in the order
+// of every later entry point (the comment above pop_bound): the handle, the state blob, what the host can judge, then the device.
+int ssg_ppo_adv_moments(ssg_handle *h, int K, int N, void *dev_workspace, size_t workspace_nbytes, double *dev_out4, void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc != SSG_OK) return rc;
+    if (!dev_out4) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_adv_moments: NULL dev_out4");
+    if (K < 1 || N < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_adv_moments: K and N must be >= 1");
+    rc = check_workspace(h, dev_workspace, workspace_nbytes, ppo_need_gae(N), "ssg_ppo_adv_moments");
+    if (rc == SSG_OK) rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_dp_adv_moments(K, N, dev_workspace, dev_out4, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("adv moments launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+int ssg_ppo_set_adv_moments(ssg_handle *h, int n_shards, const double *dev_rows, double adv_eps, void *dev_workspace, size_t workspace_nbytes,
+                            void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc != SSG_OK) return rc;
+    if (!dev_rows) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_set_adv_moments: NULL dev_rows");
+    if (n_shards < 1 || n_shards > SSG_DP_MAX_SHARDS) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_set_adv_moments: n_shards must be in 1..SSG_DP_MAX_SHARDS");
+    if (!std::isfinite(adv_eps)) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_set_adv_moments: adv_eps is not finite");
+    rc = check_workspace(h, dev_workspace, workspace_nbytes, ssg::kPpoSlotsOff, "ssg_ppo_set_adv_moments");
+    if (rc == SSG_OK) rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_dp_set_adv_moments(n_shards, dev_rows, adv_eps, dev_workspace, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("set adv moments launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+int ssg_ppo_apply_shards(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, const ssg_ppo_ext *ext, const ssg_ppo_shards *sh,
+                         float *dev_adam_mv, int64_t step, float *dev_stats, void *dev_workspace, size_t workspace_nbytes, void *stream)
+{
+    const char *what = "ssg_ppo_apply_shards";
+    const std::string w(what);
+    int rc = pop_bound(h);
+    if (rc == SSG_OK) rc = check_policy(h, pol, what);
+    if (rc == SSG_OK) rc = check_hparams(h, hp, what);
+    if (rc != SSG_OK) return rc;
+    if (ext) { // (the batch pointers of the record are not read here: check_ext's rules about them are the gradient call's)
+        if (ext->struct_size != sizeof(ssg_ppo_ext)) return fail(h, SSG_ERR_BAD_ARG, w + ": ssg_ppo_ext.struct_size != sizeof(ssg_ppo_ext)");
+        if (!std::isfinite(ext->vf_clip) || !std::isfinite(ext->max_grad_norm) || !std::isfinite(ext->kl_target))
+            return fail(h, SSG_ERR_BAD_ARG, w + ": vf_clip, max_grad_norm or kl_target is not finite");
+    }
+    if (!sh) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL ssg_ppo_shards");
+    if (sh->struct_size != sizeof(ssg_ppo_shards)) return fail(h, SSG_ERR_BAD_ARG, w + ": ssg_ppo_shards.struct_size != sizeof(ssg_ppo_shards)");
+    if (sh->n_shards < 1 || sh->n_shards > SSG_DP_MAX_SHARDS) return fail(h, SSG_ERR_BAD_ARG, w + ": n_shards must be in 1..SSG_DP_MAX_SHARDS");
+    if (sh->reserved != 0) return fail(h, SSG_ERR_BAD_ARG, w + ": ssg_ppo_shards.reserved must be 0");
+    if (!sh->dev_rows || !sh->counts || !dev_adam_mv) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_rows, counts or dev_adam_mv");
+    for (int r = 0; r < sh->n_shards; ++r)
+        if (sh->counts[r] < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": a shard's count is < 1");
+    if (step < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": step must be >= 1");
+    const bool adapt = ext && sh->last_chunk && ext->dev_kl_coef && ext->kl_target > 0.0;
+    if (adapt && sh->n_chunks < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": n_chunks must be >= 1 where the adaptation runs");
+    if (h->adv_norm_mode == SSG_ADV_NORM_MINIBATCH)
+        return fail(h, SSG_ERR_BAD_ARG, w + ": SSG_ADV_NORM_MINIBATCH is bound to the handle (ssg_ppo_set_adv_norm): per-minibatch statistics "
+                                            "across shards are out of scope");
+    const size_t need = ext ? ssg::ppo_ext_layout(ssg::kPpoSlotsOff, 1, 1, ssg::ppo_packed_len(*pol)).slots : ssg::kPpoSlotsOff;
+    rc = check_workspace(h, dev_workspace, workspace_nbytes, need, what);
+    if (rc == SSG_OK) rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    ssg::DpApply a = {};
+    a.policy = pol;
+    a.hp = hp;
+    a.ext = ext != nullptr;
+    a.max_grad_norm = ext && ext->max_grad_norm > 0.0 ? (float)ext->max_grad_norm : 0.0f;
+    a.kl_target = ext ? (float)ext->kl_target : 0.0f;
+    a.kl_coef = ext ? ext->dev_kl_coef : nullptr;
+    a.n_shards = sh->n_shards;
+    a.rows = sh->dev_rows;
+    a.counts = sh->counts;
+    a.first_chunk = sh->first_chunk != 0;
+    a.last_chunk = sh->last_chunk != 0;
+    a.n_chunks = sh->n_chunks;
+    a.adam_mv = dev_adam_mv;
+    a.step = step;
+    a.stats_out = dev_stats;
+    a.ws = dev_workspace;
+    hipError_t e = ssg::launch_dp_apply(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("apply shards launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
 int ssg_pop_update(ssg_handle *h, const ssg_population *pop, const float *dev_table, int table_steps, int K, const float *dev_x,
                    const int32_t *dev_act, const float *dev_logp, const float *dev_adv, const float *dev_ret, const int64_t *dev_perm,
                    int epochs, int minibatches, float *dev_adam_mv, float *dev_stats, void *dev_workspace, size_t workspace_nbytes,

@@ -384,6 +384,32 @@ hipError_t launch_adv_norm(const AdvNormLaunch &l, hipStream_t stream);
 // table, whose header row m holds member m's own chunk count)
 hipError_t launch_kl_adapt(int members, const PpoExtLaunch &ext, float kl_target, int P, long long chunks, const int32_t *sched_hdr, void *ws,
                            size_t slots_off, hipStream_t stream);
+// Data parallel (ssg_ppo_adv_moments / ssg_ppo_set_adv_moments / ssg_ppo_apply_shards; the end of shipsim_ppo.hip).  The apply keeps
+// its running sum of mean(KL) at float kDpKlaccFloat of the extended layout's klacc part: float 0 is the gradient entry points' own,
+// which every shard's local ssg_ppo_grad_ext overwrites between two applies.
+constexpr int kDpKlaccFloat = 4;
+hipError_t launch_dp_adv_moments(int K, int N, void *ws, double *out4, hipStream_t stream);
+hipError_t launch_dp_set_adv_moments(int n_shards, const double *rows, double adv_eps, void *ws, hipStream_t stream);
+// One apply: the rows f32 [n_shards][P + kExtStats] combined with the weights counts[r] / sum(counts), then the clip (ext and
+// max_grad_norm > 0: two launches) and Adam step `step`; with last_chunk, a coefficient and kl_target > 0 the adaptation launch
+// follows, dividing the running sum by n_chunks.
+struct DpApply {
+    const ssg_policy *policy;
+    const ssg_ppo_hparams *hp;
+    bool ext;                     // the extended loss's stats columns, KL sum and clip; false: the plain loss (no workspace use)
+    float max_grad_norm, kl_target;
+    float *kl_coef;               // device f32 [1], nullable
+    int n_shards;
+    const float *rows;
+    const int64_t *counts;        // host
+    bool first_chunk, last_chunk;
+    int n_chunks;
+    float *adam_mv;
+    int64_t step;
+    float *stats_out;             // nullable, f32 [kExtStats]
+    void *ws;
+};
+hipError_t launch_dp_apply(const DpApply &a, hipStream_t stream);
 // the acting policy's log-distribution over stored x rows (shipsim_policy.hip): member m's rows t*N + (its envs), t < K, under parameter row m
 hipError_t launch_policy_dist(const ssg_policy &p, const MemberLayout &lay, long long N, int K, const float *x, float *logp_all, hipStream_t stream);
 hipError_t launch_pop_episode_stats(const MemberLayout &lay, int K, int N, const double *rew, const uint8_t *done, double *carry_ret,

@@ -24,6 +24,9 @@
 // loaded once, then the pi pass (forward over W0 / W1, logits, the policy, entropy and KL terms, backward into the pi tower's and pi
 // head's slot entries) and the vf pass (forward over V0 / V1, the value and its loss, backward into the vf tower's and vf head's).
 // No LDS beyond the shared plan's.
+//
+// Data parallel (ssg_ppo_adv_moments / ssg_ppo_set_adv_moments / ssg_ppo_apply_shards): three small kernels at the end of the file
+// make the advantage statistics job-wide and apply the gathered gradient rows of W shards, the same arithmetic on every rank.
 #include <cmath>
 #include <cstdint>
 
@@ -1358,6 +1361,155 @@ hipError_t launch_pop_episode_stats(const MemberLayout &lay, int K, int N, const
     else
         hipLaunchKernelGGL(pop_episode_stats_kernel, grid, dim3(256), 0, stream, K, N, lay.n, rew, done, carry_ret, carry_len,
                            reinterpret_cast<unsigned long long *>(out));
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// data parallel: one policy trained from W shards' gradients (ssg_ppo_adv_moments / ssg_ppo_set_adv_moments / ssg_ppo_apply_shards)
+// ------------------------------------------------------------------------------------------------------------------------------
+// Every rank runs these launches on the same gathered rows, so the ranks' parameters stay bit-identical without a broadcast.  The
+// kernels sit at the end of the object, behind everything it held: those kernels keep their device code (profiles/dp/README.md).
+namespace {
+
+// GAE's f64 partials, added again in gae_stats_body's order, as the shard's moments {S, Q, n, 0} instead of its statistics.
+__global__ void __launch_bounds__(256) dp_adv_moments_kernel(const double2 *__restrict__ part, int nblocks, double n, double *__restrict__ out4)
+{
+    __shared__ double rs[256], rq[256];
+    double s = 0.0, q = 0.0;
+    for (int b = threadIdx.x; b < nblocks; b += 256) {
+        s += part[b].x;
+        q += part[b].y;
+    }
+    rs[threadIdx.x] = s;
+    rq[threadIdx.x] = q;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            rs[threadIdx.x] += rs[threadIdx.x + w];
+            rq[threadIdx.x] += rq[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out4[0] = rs[0];
+        out4[1] = rq[0];
+        out4[2] = n;
+        out4[3] = 0.0;
+    }
+}
+
+// One lane: the W rows' S, Q and n in row order (f64), then gae_stats_body's formula.  Fewer than 2 samples in all have no unbiased
+// std: the row becomes NaN, which no later gradient can mistake for statistics (the device has no return code).
+__global__ void __launch_bounds__(64) dp_set_adv_moments_kernel(int W, const double *__restrict__ rows, float adv_eps, float *__restrict__ stats)
+{
+    if (threadIdx.x != 0) return;
+    double S = 0.0, Q = 0.0, n = 0.0;
+    for (int r = 0; r < W; ++r) {
+        S += rows[r * 4 + 0];
+        Q += rows[r * 4 + 1];
+        n += rows[r * 4 + 2];
+    }
+    if (!(n >= 2.0)) {
+        const float bad = __int_as_float(0x7fc00000);
+        stats[0] = bad;
+        stats[1] = bad;
+        stats[2] = bad;
+        stats[3] = 0.0f;
+        return;
+    }
+    const double mean = S / n;
+    double var = (Q - S * mean) / (n - 1.0);
+    if (var < 0.0) var = 0.0;
+    const float stdp = (float)sqrt(var) + adv_eps;
+    stats[0] = (float)mean;
+    stats[1] = stdp;
+    stats[2] = 1.0f / stdp;
+    stats[3] = 0.0f;
+}
+
+struct DpWeights {
+    float w[SSG_DP_MAX_SHARDS]; // by value in the kernel arguments: M_r / sum M, rounded on the host
+};
+
+// Grid ceil((P + kExtStats) / 256), entry p on lane p % 256 of workgroup p / 256 — ppo_reduce_ext_kernel's partition, so the sums of
+// squares below are its partials.  g = w_0*row_0[p], then g = g + w_r*row_r[p] in row order, every product and sum rounded to f32
+// on its own.  p < P: the gradient entry — into gvec with the clip sequence (ppo_clip_kernel follows), else one Adam step.  p >= P:
+// the stats columns, as ppo_reduce_body's EXT branch writes them; ext == 0 (the plain loss): columns 0..3, the rest zero, no KL sum.
+__global__ void __launch_bounds__(256) dp_apply_kernel(const float *__restrict__ rows, int W, const DpWeights wt, int P, int ext,
+                                                       const float *__restrict__ kl_coef, float *__restrict__ klacc, int first_chunk,
+                                                       float *__restrict__ gvec, double *__restrict__ part, float *__restrict__ stats_out,
+                                                       float *__restrict__ params, float *__restrict__ mv, const AdamArgs ad)
+{
+    __shared__ double sq[256];
+    const int stride = P + kExtStats;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    float s = 0.0f;
+    if (p < stride) {
+        s = __fmul_rn(wt.w[0], rows[p]);
+        for (int r = 1; r < W; ++r) s = __fadd_rn(s, __fmul_rn(wt.w[r], rows[(size_t)r * stride + p]));
+    }
+    if (p >= P && p < stride) {
+        const int q = p - P;
+        const float klc = ext && kl_coef ? kl_coef[0] : 0.0f;
+        if (stats_out) stats_out[q] = q < 5 ? s : (q == 6 ? (klc > 0.0f ? klc : 0.0f) : 0.0f);
+        if (ext && q == 4) klacc[0] = first_chunk ? s : klacc[0] + s;
+    }
+    if (p < P) {
+        if (gvec) gvec[p] = s;
+        else adam_apply(ad, s, p, P, params, mv);
+    }
+    if (gvec) { // the workgroup's sum of squares, f64, ppo_reduce_body's tree
+        sq[threadIdx.x] = p < P ? (double)s * (double)s : 0.0;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) {
+            if ((int)threadIdx.x < w) sq[threadIdx.x] += sq[threadIdx.x + w];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) part[blockIdx.x] = sq[0];
+    }
+}
+
+} // namespace
+
+hipError_t launch_dp_adv_moments(int K, int N, void *ws, double *out4, hipStream_t stream)
+{
+    const double2 *part = reinterpret_cast<const double2 *>(static_cast<char *>(ws) + kPpoSlotsOff);
+    hipLaunchKernelGGL(dp_adv_moments_kernel, dim3(1), dim3(256), 0, stream, part, ppo_gae_blocks(N), (double)K * (double)N, out4);
+    return hipGetLastError();
+}
+
+hipError_t launch_dp_set_adv_moments(int n_shards, const double *rows, double adv_eps, void *ws, hipStream_t stream)
+{
+    float *stats = reinterpret_cast<float *>(static_cast<char *>(ws) + kPpoStatsOff);
+    hipLaunchKernelGGL(dp_set_adv_moments_kernel, dim3(1), dim3(64), 0, stream, n_shards, rows, (float)adv_eps, stats);
+    return hipGetLastError();
+}
+
+hipError_t launch_dp_apply(const DpApply &a, hipStream_t stream)
+{
+    const ssg_policy &p = *a.policy;
+    const int P = ppo_packed_len(p), stride = P + kExtStats;
+    const PpoExtLayout lay = ppo_ext_layout(kPpoSlotsOff, 1, 1, P);
+    char *base = static_cast<char *>(a.ws);
+    DpWeights wt = {};
+    double total = 0.0;
+    for (int r = 0; r < a.n_shards; ++r) total += (double)a.counts[r];
+    for (int r = 0; r < a.n_shards; ++r) wt.w[r] = (float)((double)a.counts[r] / total);
+    const bool clip = a.ext && a.max_grad_norm > 0.0f;
+    float *klacc = a.ext ? reinterpret_cast<float *>(base + lay.klacc) + kDpKlaccFloat : nullptr;
+    float *gvec = clip ? reinterpret_cast<float *>(base + lay.gvec) : nullptr;
+    double *part = clip ? reinterpret_cast<double *>(base + lay.part) : nullptr;
+    float *params = const_cast<float *>(p.dev_params);
+    const AdamArgs ad = adam_args(*a.hp, a.step);
+    hipLaunchKernelGGL(dp_apply_kernel, dim3((stride + 255) / 256), dim3(256), 0, stream, a.rows, a.n_shards, wt, P, a.ext ? 1 : 0,
+                       (const float *)a.kl_coef, klacc, a.first_chunk ? 1 : 0, gvec, part, a.stats_out, params, a.adam_mv, ad);
+    if (clip)
+        hipLaunchKernelGGL(ppo_clip_kernel<false>, dim3((P + 255) / 256), dim3(256), 0, stream, (const float *)gvec, (const double *)part,
+                           lay.nb, P, a.max_grad_norm, (const float *)nullptr, a.stats_out, 0ll, params, a.adam_mv, ad,
+                           (const float *)nullptr);
+    if (a.ext && a.last_chunk && a.kl_coef && a.kl_target > 0.0f)
+        hipLaunchKernelGGL(ppo_kl_adapt_kernel, dim3(1), dim3(256), 0, stream, 1, a.kl_coef, (const float *)klacc, (float)a.n_chunks,
+                           a.kl_target, (const float *)nullptr, (const int32_t *)nullptr);
     return hipGetLastError();
 }
 

@@ -59,6 +59,26 @@ def all_reduce_stats(stats_tensor, group=None):
     return stats_tensor
 
 
+def all_gather_rows(t, group=None):
+    """The ranks' tensors `t` (one shape and dtype on every rank) stacked in rank order: [W, *t.shape] on t's device, the same bits on
+    every rank (the gather of ship_sim_gym_amd/dp.py's gradient rows and advantage moments).  gloo carries it through host memory, as
+    broadcast_tensor does; without an initialised process group it is t[None]."""
+    import torch
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return t[None]
+    W = dist.get_world_size(group)
+    src = t.contiguous()
+    if _through_host(src, group):
+        h = src.cpu()
+        out = torch.empty((W,) + tuple(h.shape), dtype=h.dtype)
+        dist.all_gather(list(out.unbind(0)), h, group=group)  # (the views are written in place)
+        return out.to(t.device)
+    out = torch.empty((W,) + tuple(src.shape), dtype=src.dtype, device=src.device)
+    dist.all_gather(list(out.unbind(0)), src, group=group)
+    return out
+
+
 def global_stats(vec, group=None):
     """Episode counters of the WHOLE sharded job (every rank gets the same dict): the per-handle int64 counters the
     step kernel accumulates, summed on the device and all-reduced over ranks."""

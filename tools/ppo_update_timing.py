@@ -9,7 +9,7 @@ every update from the same parameters' values (their own copies) and draw their 
 line on stdout.  The kernels alone: `rocprofv3 --kernel-trace --stats -- python tools/ppo_update_timing.py --only native` (tools/README.md).
 
     python tools/ppo_update_timing.py [--configs 65536x32,4096x64] [--repeats 7] [--only torch|native] [--ext] [--separate-value] [--ret-filter]
-                                      [--adv-norm] [--perm] [--timeout-bootstrap] [--checkpoint]
+                                      [--adv-norm] [--perm] [--timeout-bootstrap] [--checkpoint] [--dp]
 
 --ext adds, in the same run, the extended update (NativePPO with vf_clip 0.2, max_grad_norm 0.5, kl_coef 1.0, kl_target 0.01: GAE, the
 ssg_ppo_dist launch, ssg_ppo_update_ext) as the path "native_ext", and the ssg_ppo_dist launch alone as "dist".
@@ -31,6 +31,10 @@ train/ppo_torch.py --save writes between two updates (the policy, the trainer, t
 loop section), host wall-clock milliseconds from the first state_dict() to the renamed file (device-to-host copies, pickling and the
 file system; the path is under --checkpoint-dir, default the system's temporary directory), to set against "native", the GAE + update
 of the same process; and the file's size in bytes.  What --save-every 1 costs per update is the first against the second.
+--dp adds, in the same run and alternating with the others, "native_dp": the whole GAE + update through DataParallelPPO
+(ship_sim_gym_amd/dp.py) on ONE rank, to set against "native" — what leaving the C loop costs: a Python iteration per minibatch, a
+gather that is a no-op, the moments launches and the apply launch in place of the reduction; and "apply_rows_w1" / "_w2" / "_w8":
+ssg_ppo_apply_shards alone on 1, 2 and 8 gathered rows (the plain loss: one launch).
 """
 import argparse
 import importlib.util
@@ -115,7 +119,7 @@ def _wall_ms(fn):
 
 
 def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext=False, separate_value=False, ret_filter=False,
-            adv_norm=False, perm=False, timeout_bootstrap=False, checkpoint=False, checkpoint_dir=None):
+            adv_norm=False, perm=False, timeout_bootstrap=False, checkpoint=False, checkpoint_dir=None, dp=False):
     from ship_sim_gym_amd.policy import NativePolicy
     from ship_sim_gym_amd.ppo import NativePPO
     torch.manual_seed(0)
@@ -215,6 +219,26 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
     def draw_native():
         return ppo_p.draw_perm(n, epochs)
 
+    if dp:  # one rank of a data-parallel job: the Python loop, a gather that is a no-op, and the apply launch in place of the reduction
+        from ship_sim_gym_amd.dp import DataParallelPPO
+        ppo_d = DataParallelPPO(pol, env)
+        g_d = torch.Generator(device=dev)
+        g_d.manual_seed(1)
+
+        def run_native_dp():
+            with torch.no_grad():
+                for p, q in zip(net_n.parameters(), p0):
+                    p.copy_(q)
+            pol.refresh()
+            nb = dict(b)
+            ppo_d.gae(nb)
+            ppo_d.update(nb, torch.stack([torch.randperm(n, device=dev, generator=g_d) for _ in range(epochs)]), epochs, minibatches)
+
+        def apply_alone(W):
+            rows = torch.randn((W, ppo_d.n_params + 8), device=dev) * 1e-3
+            counts = [-(-n // minibatches)] * W
+            return lambda: ppo_d.apply_rows(rows, counts, True, False)
+
     ckpt_path = None
     if checkpoint:
         import tempfile
@@ -234,6 +258,8 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
     paths = [(k, f) for k, f in (("torch", run_torch), ("native", run_native)) if only in (None, k)]
     if checkpoint:
         paths.append(("checkpoint_save", run_checkpoint_save))
+    if dp:
+        paths += [("native_dp", run_native_dp)] + [("apply_rows_w%d" % W, apply_alone(W)) for W in (1, 2, 8)]
     if adv_norm:
         paths.append(("native_mbnorm", run_native_mbnorm))
     if perm:
@@ -288,11 +314,13 @@ def main():
     ap.add_argument("--checkpoint", action="store_true", help="also time one checkpoint save (policy, trainer, env, both filters) and report "
                                                               "the file's size, next to the GAE + update of the same process")
     ap.add_argument("--checkpoint-dir", default=None, help="where --checkpoint writes its file (default: the system's temporary directory)")
+    ap.add_argument("--dp", action="store_true", help="also time the whole GAE + update through DataParallelPPO on one rank, and the apply "
+                                                      "launch alone on 1, 2 and 8 rows")
     a = ap.parse_args()
     mod = _ppo()
     res = [measure(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.repeats, a.only, "cuda:0", ext=a.ext, separate_value=sep, ret_filter=a.ret_filter,
                    adv_norm=a.adv_norm, perm=a.perm, timeout_bootstrap=a.timeout_bootstrap, checkpoint=a.checkpoint,
-                   checkpoint_dir=a.checkpoint_dir)
+                   checkpoint_dir=a.checkpoint_dir, dp=a.dp)
            for c in a.configs.split(",") for sep in ([False, True] if a.separate_value else [False])]
     print(json.dumps({"ppo_update_timing": res}))
 

@@ -7,7 +7,7 @@ leave the GPU; the policy is a small MLP in fp32.
     python train/ppo_torch.py --envs 4096 --updates 20 [--mode eager|graph|pingpong|native] [--update torch|native] [--separate-value]
                               [--eval-every U --eval-episodes E] [--obs-filter [--save-obs-filter FILE]]
                               [--norm-reward [--reward-clip C]]
-                              [--save FILE [--save-every U]] [--save-best FILE] [--resume FILE]
+                              [--save FILE [--save-every U]] [--save-best FILE] [--resume FILE] [--gpus W]
 
 Four ways to run the rollout loop (the reference's `model.learn` -> runner.run(): one `env.step(actions)` per policy
 forward, train/stable_baselines/ppo.py:84-100,122-123) — same arithmetic, same results bit for bit:
@@ -57,6 +57,16 @@ history, the best score) and the run's arguments, and ``--resume FILE`` continue
 line and add ``--resume``; ``--updates`` stays the TOTAL and may be raised, the ``--save*`` and ``--eval-*`` options may change, any
 other argument that differs from the file's is refused.  In the other modes ``--save`` writes the policy alone (the torch optimiser's
 state is out of scope), which train/evaluate_native.py ``--checkpoint FILE`` reads and ``--resume`` refuses.
+
+``--gpus W`` (``--mode native --update native`` only): ONE policy trained data-parallel on W ranks, one per GPU, as the RLlib scripts
+train one policy from the experience of their workers (train/rllib/ppo.py:34-35, train/rllib/pbt.py:57-58).  The script starts the W
+rank processes itself and waits for them; under a launcher's environment (``RANK`` / ``WORLD_SIZE`` > 1) it is a rank itself.
+``--envs`` is the job's total: rank r owns the global envs of ``sharding.shard_range``, every rank builds the same policy from the
+seed and draws the whole job's uniforms, and the update goes through ship_sim_gym_amd/dp.py's ``DataParallelPPO`` (local gradients,
+an all-gather of the rows, the same apply on every rank: no parameter broadcast).  Rank 0 logs the job-wide episode statistics,
+evaluates and writes ``--save`` (the policy and the trainer); every rank prints a checksum of its parameters, and the lines agree.
+``--resume``, ``--save-every``, ``--obs-filter``, ``--norm-reward`` and ``--adv-norm minibatch`` are refused with more than one rank.
+``SSG_TRAIN_SHARE_DEVICE=1`` (tests on a one-GPU box) puts every rank on device 0 over gloo.
 
 The sampling noise of a whole rollout is drawn in one call before it (uniforms [horizon, envs], inverse-CDF sampling inside
 the step), so a captured step holds no random-number generator state and replays exactly what the eager loop computes.
@@ -174,12 +184,23 @@ def env_columns(env):
             ("F_X", "F_Y", "F_VX", "F_VY", "F_ANGLE", "F_W", "F_LIDAR", "F_RUDDER", "F_STEP_COUNT", "F_MAP_ID", "F_GOAL_MASK", "F_CUM_REWARD")}
 
 
-def make_shards(envs, mode, net, device, horizon, n_maps=64, env_kw=None):
+def job_ranks():
+    """(rank, world) of the process group this process has joined; (0, 1) without one: the single-process run."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank(), dist.get_world_size()
+    return 0, 1
+
+
+def make_shards(envs, mode, net, device, horizon, n_maps=64, env_kw=None, env_range=None):
     """The rollout's env shards: one ShipVecEnv, or (pingpong) two halves that together are the same batch — global env ids,
-    map assignment and therefore every result are those of the unsplit batch (ship_sim_gym_amd/sharding.py)."""
+    map assignment and therefore every result are those of the unsplit batch (ship_sim_gym_amd/sharding.py).  env_range = (lo, hi):
+    this rank's shard of a data-parallel job's envs, global ids [lo, hi), instead of all of them."""
     env_kw = dict(env_kw or {})
     sizes = [envs] if mode != "pingpong" else [envs - envs // 2, envs // 2]
     shards, base = [], 0
+    if env_range is not None:
+        sizes, base = [env_range[1] - env_range[0]], env_range[0]
     for n in sizes:
         env = ShipVecEnv(n, GameConfig, EnvConfig, device=device, n_maps=n_maps, env_id_base=base, **env_kw)  # was: SubprocVecEnv([make_env()]*n)
         scale = torch.full((env.states_history,), float(max(env.bounds)), dtype=torch.float64, device=device)
@@ -188,10 +209,14 @@ def make_shards(envs, mode, net, device, horizon, n_maps=64, env_kw=None):
     return shards
 
 
-def rollout(shards, horizon, mode, gen, policy=None):
+def rollout(shards, horizon, mode, gen, policy=None, job=None):
     """`horizon` policy-in-the-loop steps of every shard; returns the rollout buffers concatenated over the shards (env axis).
-    mode "native" (one shard, `policy` = its NativePolicy) also returns "last_val", the device's bootstrap value."""
-    full = torch.rand((horizon, sum(sh.n for sh in shards)), generator=gen, device=shards[0].noise.device)
+    mode "native" (one shard, `policy` = its NativePolicy) also returns "last_val", the device's bootstrap value.  job = (lo, hi, total):
+    a rank of a data-parallel job draws the WHOLE job's uniforms (every rank the same, from the same generator) and samples with its
+    own columns [lo, hi), so the job's rollout is the single process's over `total` envs."""
+    full = torch.rand((horizon, sum(sh.n for sh in shards) if job is None else job[2]), generator=gen, device=shards[0].noise.device)
+    if job is not None:
+        full = full[:, job[0]: job[1]].contiguous()
     if mode == "native":
         sh = shards[0]
         o = sh.env.rollout_policy(policy, horizon, uniforms=full, out=getattr(sh, "native_out", None))
@@ -298,6 +323,22 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         raise ValueError("update must be 'torch' or 'native' (got %r)" % (update,))
     if update == "native" and mode != "native":
         raise ValueError("update='native' runs on the native policy's packed parameters: it needs mode='native' (got mode=%r)" % (mode,))
+    # Data parallel: this process is one rank of a job that trains ONE policy (ship_sim_gym_amd/dp.py).  `envs` is the job's total, every
+    # rank builds the same policy from the same seed, and only rank 0 logs, evaluates and saves.
+    rank, world = job_ranks()
+    env_range = None
+    if world > 1:
+        if mode != "native" or update != "native":
+            raise ValueError("a multi-rank run trains through the device update: it needs mode='native' and update='native' (got mode=%r, "
+                             "update=%r)" % (mode, update))
+        for flag, on in (("--resume", resume), ("--save-every", save_every), ("--obs-filter", obs_filter or save_obs_filter),
+                         ("--norm-reward", norm_reward), ("--adv-norm minibatch", adv_norm == "minibatch")):
+            if on:
+                raise ValueError("%s is not supported with more than one rank (%d ranks)" % (flag, world))
+        from ship_sim_gym_amd import sharding
+        env_range = sharding.shard_range(envs, rank, world)
+        if rank != 0:
+            log = lambda *a, **k: None  # noqa: E731
     from ship_sim_gym_amd import checkpoint
     ckpt = None
     if resume:  # (read and compared before any device work: a wrong command line costs nothing)
@@ -312,12 +353,26 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
     probe.close()
     net = ActorCritic(D, A, hidden=hidden, separate_value=separate_value).to(dev)
     opt = torch.optim.Adam(net.parameters(), lr=lr)
-    shards = make_shards(envs, mode, net, device, horizon, env_kw=env_kw)
+    shards = make_shards(envs, mode, net, device, horizon, env_kw=env_kw, env_range=env_range)
+    if world > 1:
+        sharding.broadcast_bank(shards[0].env, src=0)
     for sh in shards:
         sh.env.reset_tensor()
     policy = NativePolicy.from_actor_critic(net, shards[0].scale) if mode == "native" else None
-    ppo = (NativePPO(policy, shards[0].env, lr=lr, clip=clip, adv_norm=adv_norm, perm_seed=seed if native_perm else None)
-           if update == "native" else None)
+    if world > 1:  # (refuses, on every rank alike, shards that would make different numbers of minibatches)
+        from ship_sim_gym_amd.dp import DataParallelPPO
+        ppo = DataParallelPPO(policy, shards[0].env, plan=(horizon, minibatches), lr=lr, clip=clip, perm_seed=seed if native_perm else None)
+    else:
+        ppo = (NativePPO(policy, shards[0].env, lr=lr, clip=clip, adv_norm=adv_norm, perm_seed=seed if native_perm else None)
+               if update == "native" else None)
+    job = None if world == 1 else (env_range[0], env_range[1], envs)
+    n_local = envs if world == 1 else env_range[1] - env_range[0]
+
+    def episode_stats():
+        """The episode counters so far: this process's envs', or (every rank calls it: an all-reduce) the whole job's."""
+        if world > 1:
+            return sharding.global_stats(shards[0].env)
+        return {k: sum(sh.env.stats()[k] for sh in shards) for k in ("sum_return", "episodes", "goals_hit")}
     flt = None
     if obs_filter:  # (the rollout loop merges each step's observations, then normalises them; obs_scale is no longer read)
         from ship_sim_gym_amd.obs_filter import ObsFilter
@@ -330,7 +385,7 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         from ship_sim_gym_amd.ret_filter import ReturnFilter
         rflt = ReturnFilter(shards[0].env, gamma=gamma, clip=reward_clip)
     evaluator, evals = None, []
-    if eval_every:  # a second env of its own: evaluation resets and steps it, the training envs keep their episodes
+    if eval_every and rank == 0:  # a second env of its own (a data-parallel job evaluates on rank 0): evaluation resets and steps it, the training envs keep their episodes
         from ship_sim_gym_amd.evaluate import NativeEvaluator
         eval_env = ShipVecEnv(int(eval_envs or min(envs, 1024)), GameConfig, EnvConfig, device=device, n_maps=64, **dict(env_kw or {}))
         evaluator = NativeEvaluator(eval_env)
@@ -353,9 +408,9 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
     # of the episodes that ended during it (-inf when none did, which never counts as a best)
     ep_scores, best, best_update = [], float("-inf"), -1
     if save or save_best:
-        if ppo is not None:
+        if ppo is not None and world == 1:
             shards[0].env.check_snapshot_supported("snapshot")  # (refuse now, not after the training, a handle that cannot be saved)
-    st0 = {k: sum(sh.env.stats()[k] for sh in shards) for k in ("sum_return", "episodes")}
+    st0 = episode_stats()
     seen_episodes, seen_return = st0["episodes"], st0["sum_return"]
     start = 0
     if ckpt is not None:  # everything is built and bound as the configuration says; now take the saved state over
@@ -380,7 +435,9 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
                     "loop": {"update": int(u), "gen_state": gen.get_state().cpu().clone(), "history": [list(r) for r in history],
                              "scores": list(ep_scores), "best": float(best), "best_update": int(best_update),
                              "episodes": int(seen_episodes), "sum_return": float(seen_return)}}
-        if ppo is not None:
+        if ppo is not None and world > 1:  # (rank 0's file: the policy and the trainer; per-rank env snapshots are out of scope)
+            sections.update(policy=policy.state_dict(), trainer=ppo.state_dict())
+        elif ppo is not None:
             sections.update(policy=policy.state_dict(), trainer=ppo.state_dict(), env=shards[0].env.snapshot())
             if rflt is not None:
                 sections["ret_filter"] = rflt.state_dict()
@@ -393,7 +450,7 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
     for u in range(start, updates):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        b = rollout(shards, horizon, mode, gen, policy)
+        b = rollout(shards, horizon, mode, gen, policy, job=job)
         torch.cuda.synchronize()
         t_roll += time.perf_counter() - t0
         native_last_val = b.pop("last_val", None)
@@ -403,7 +460,7 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         if ppo is not None:  # GAE + the whole update on the device, on the rollout's own buffers (the same randperm draws)
             nb = dict(shards[0].native_out)
             ppo.gae(nb, gamma, lam, return_filter=rflt)
-            n = horizon * envs
+            n = horizon * n_local  # (a rank shuffles its own samples)
             # perm "native": the library shuffles (a row per epoch, keyed by the seed and the update's number); else torch's generator
             rows = None if native_perm else torch.stack([torch.randperm(n, device=dev, generator=gen) for _ in range(epochs)])
             st_upd = ppo.update(nb, rows, epochs, minibatches, stats=flt is not None or rflt is not None)
@@ -452,7 +509,7 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
                 policy.refresh()
         torch.cuda.synchronize()
         t_upd += time.perf_counter() - t1
-        st = {k: sum(sh.env.stats()[k] for sh in shards) for k in ("sum_return", "episodes", "goals_hit")}
+        st = episode_stats()
         mean_ret = st["sum_return"] / max(st["episodes"], 1)
         goals_per_ep = st["goals_hit"] / max(st["episodes"], 1)
         history.append((u, mean_ret, goals_per_ep, float(b["rew"].mean())))
@@ -463,7 +520,7 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         seen_episodes, seen_return = st["episodes"], st["sum_return"]
         if ep_scores[-1] > best:  # (an update in which no episode ended scores -inf: it never gets here)
             best, best_update = ep_scores[-1], u
-            if save_best:
+            if save_best and rank == 0:
                 write(save_best, u)
                 log("update %3d  episode_reward_mean %+.3f over %d episodes: the best so far, saved to %s" % (u, best, ended, save_best))
         if save and save_every and (u + 1) % save_every == 0:
@@ -477,11 +534,15 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
                     r["collision_rate"][0], r["out_of_bounds_rate"][0], r["max_steps_rate"][0]))
     torch.cuda.synchronize()
     t_all = time.perf_counter() - t_all0
-    if save:
+    if save and rank == 0:
         write(save, max(updates, start) - 1)
         log("checkpoint after update %d saved to %s" % (max(updates, start) - 1, save))
     if ppo is not None:
         ppo.load_into(net)  # the module gets the device-trained parameters (details["params"])
+    if world > 1:  # every rank prints it: the ranks hold the same bits, so the lines are the same
+        import hashlib
+        print("parameter checksum after %d Adam steps: %s" % (ppo.step, hashlib.sha256(policy.params.detach().cpu().numpy().tobytes()).hexdigest()),
+              flush=True)
     steps = envs * horizon * max(0, updates - start)  # (this process's own; a resumed run did not step the updates it loaded)
     log("rollout (%s): %.1f M env-steps/s with the policy in the loop; whole training loop (rollout + PPO update): %.1f M env-steps/s" % (
         mode, steps / max(t_roll, 1e-9) / 1e6, steps / max(t_all, 1e-9) / 1e6))
@@ -535,6 +596,10 @@ def make_arg_parser():
                     help="GAE bootstraps an episode the clock ended from the value of its terminal observation instead of scoring it as a "
                          "return of 0 (needs --mode native --update native); default: every done alike")
     ap.add_argument("--hidden", type=int, default=64, help="width of the hidden layers (the native policy: a multiple of 16 up to 128)")
+    ap.add_argument("--gpus", type=int, default=1, metavar="W",
+                    help="train ONE policy data-parallel on W ranks, one per GPU (needs --mode native --update native): this process "
+                         "starts the W rank processes and waits for them; --envs is the job's total.  Under a launcher's environment "
+                         "(RANK / WORLD_SIZE) the process is a rank itself")
     ap.add_argument("--save", default=None, metavar="FILE",
                     help="write a checkpoint at the end (ship_sim_gym_amd/checkpoint.py): with --mode native --update native everything a "
                          "--resume needs, else the policy alone, for train/evaluate_native.py --checkpoint")
@@ -578,13 +643,93 @@ def parse_args(argv=None):
         ap.error("--save-every needs --save (the file it rewrites)")
     if a.resume and (a.mode != "native" or a.update != "native"):
         ap.error("--resume needs --mode native --update native (it restores the device trainer's state)")
+    if a.gpus < 1 or a.gpus > 64:
+        ap.error("--gpus must be in 1..64")
+    ranks = max(a.gpus, int(os.environ.get("WORLD_SIZE", "1")))
+    if ranks > 1:
+        if a.mode != "native" or a.update != "native":
+            ap.error("more than one rank (--gpus / WORLD_SIZE = %d) needs --mode native --update native" % ranks)
+        for flag, on in (("--resume", a.resume), ("--save-every", a.save_every), ("--obs-filter", a.obs_filter or a.save_obs_filter),
+                         ("--norm-reward", a.norm_reward), ("--adv-norm minibatch", a.adv_norm == "minibatch")):
+            if on:
+                ap.error("%s is not supported with more than one rank (%d ranks): see README.md, Data parallel" % (flag, ranks))
     return a
 
 
-if __name__ == "__main__":
-    a = parse_args()
-    train(envs=a.envs, updates=a.updates, horizon=a.horizon, mode=a.mode, update=a.update, separate_value=a.separate_value,
+def launch_ranks(world, argv):
+    """Start `world` fresh rank processes of this script with the same arguments (RANK / LOCAL_RANK / WORLD_SIZE and a free local
+    port in their environment), wait for them, and return the first non-zero exit code (0: all succeeded).  When a rank fails the
+    others are ended: a rank waiting in a collective for a dead peer would wait for ever."""
+    import socket
+    import subprocess
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    procs = []
+    for r in range(world):
+        env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+        procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__)] + list(argv), env=env))
+    rc, left = 0, list(procs)
+    while left and rc == 0:
+        for p in list(left):
+            try:
+                code = p.wait(timeout=0.2)
+            except subprocess.TimeoutExpired:
+                continue
+            left.remove(p)
+            rc = rc or code
+    for p in left:  # (only after a failure)
+        p.terminate()
+    for p in left:
+        try:
+            p.wait(timeout=30)
+        except subprocess.TimeoutExpired:
+            p.kill()
+            p.wait()
+    return rc
+
+
+def join_job():
+    """Join the launcher's process group (RANK / WORLD_SIZE / MASTER_* in the environment) and return this rank's device: nccl
+    (RCCL) with one GPU per rank, or — SSG_TRAIN_SHARE_DEVICE=1, for tests on a one-GPU box — gloo with every rank on device 0."""
+    import torch.distributed as dist
+    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+    share = os.environ.get("SSG_TRAIN_SHARE_DEVICE") == "1"
+    local = 0 if share else int(os.environ.get("LOCAL_RANK", str(rank)))
+    if torch.cuda.device_count() <= local:
+        sys.exit("train/ppo_torch.py: rank %d needs device %d, the node shows %d (SSG_TRAIN_SHARE_DEVICE=1 shares device 0 over gloo)"
+                 % (rank, local, torch.cuda.device_count()))
+    dev = torch.device("cuda", local)
+    torch.cuda.set_device(dev)
+    if share:
+        dist.init_process_group("gloo", rank=rank, world_size=world)
+    else:
+        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
+    return dev
+
+
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
+    a = parse_args(argv)
+    in_job = "RANK" in os.environ and int(os.environ.get("WORLD_SIZE", "1")) > 1
+    if a.gpus > 1 and not in_job:
+        return launch_ranks(a.gpus, argv)
+    device = "cuda:0"
+    if in_job:
+        if a.gpus > 1 and a.gpus != int(os.environ["WORLD_SIZE"]):
+            sys.exit("train/ppo_torch.py: --gpus %d but WORLD_SIZE=%s" % (a.gpus, os.environ["WORLD_SIZE"]))
+        device = str(join_job())
+    train(device=device, envs=a.envs, updates=a.updates, horizon=a.horizon, mode=a.mode, update=a.update, separate_value=a.separate_value,
           eval_every=a.eval_every, eval_episodes=a.eval_episodes, obs_filter=a.obs_filter, save_obs_filter=a.save_obs_filter,
           norm_reward=a.norm_reward, reward_clip=a.reward_clip, adv_norm=a.adv_norm, perm=a.perm,
           timeout_bootstrap=a.timeout_bootstrap, hidden=a.hidden, save=a.save, save_every=a.save_every, save_best=a.save_best,
           resume=a.resume)
+    if in_job:
+        import torch.distributed as dist
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
