@@ -1,8 +1,9 @@
 """CPU checks of the return filter (include/shipsim.h "Return filter"; ship_sim_gym_amd/ret_filter.py): the record and the entry points
 as header, binding and library see them, the workspace size against its documented formula, what ssg_ret_filter_apply refuses (it
-judges its arguments on the host before it asks for a state blob or a device), the numpy restatement against a plain hand loop, and
-the trainers' flags.  Nothing here launches a kernel."""
+judges its arguments on the host before it asks for a state blob or a device), the numpy restatement against a plain hand loop and, at the shapes of
+tests/test_ret_filter_domain_gpu.py, against exact rational arithmetic, and the trainers' flags.  Nothing here launches a kernel."""
 import ctypes as C
+import fractions
 import os
 import re
 
@@ -10,6 +11,7 @@ import numpy as np
 import pytest
 
 from gpu_support import load_script
+from ret_filter_support import _geometry, _ill_inputs, _inputs, _ramp_inputs, _samples
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -190,6 +192,71 @@ def test_reference_against_a_hand_loop():
     # one row, one env: a single sample has denom 1
     st, carry, out, den = ret_filter_reference(np.zeros(4), [0.25], [[2.0]], [[0]], 0.5, 0.0, 1e-8)
     assert st.tolist() == [2.125, 0.0, 1.0, 1.0] and carry.tolist() == [2.125] and out.tolist() == [[2.0]] and den.tolist() == [1.0]
+
+
+def _exact_mean_m2(samples):
+    """(mean, M2, N) of all samples as fractions.Fraction.  Every f64 is an integer over a power of two, so the two sums are formed as
+    Python integers over the largest such power and divided once: M2 = sum x^2 - (sum x)^2 / N, exactly."""
+    ratios = [float(v).as_integer_ratio() for v in np.asarray(samples, dtype=np.float64).ravel()]
+    big = max(q for _, q in ratios)
+    ints = [p * (big // q) for p, q in ratios]
+    n = len(ints)
+    s1, s2 = sum(ints), sum(i * i for i in ints)
+    return fractions.Fraction(s1, big * n), fractions.Fraction(s2, big * big) - fractions.Fraction(s1 * s1, big * big * n), n
+
+
+#             name              K     n      inputs        gamma  dones
+EXACT_CASES = [("K33-n257", 33, 257, _inputs, 0.99, True),
+               ("K65-n2049-ramp", 65, 2049, _ramp_inputs, 0.99, True),
+               ("K1024-n3", 1024, 3, _inputs, 0.99, True),
+               ("K3-n16385-ramp", 3, 16385, _ramp_inputs, 0.99, True),
+               ("K5-n4097-ill", 5, 4097, _ill_inputs, 0.0, True),
+               ("K40-n300-ill", 40, 300, _ill_inputs, 0.0, True),
+               ("K1024-n3-gamma1-no-dones", 1024, 3, _inputs, 1.0, False)]
+
+
+@pytest.mark.parametrize("name,K,n,make,gamma,dones", EXACT_CASES, ids=[c[0] for c in EXACT_CASES])
+def test_reference_against_exact_arithmetic(name, K, n, make, gamma, dones):
+    """The restatement's (mean, M2) over a whole call from the empty state against the exact mean and M2 of the same K n samples.  The
+    samples come from the documented recurrence, which is elementwise, so every implementation forms the same f64 values; their mean
+    and M2 are then computed in fractions.Fraction.  This is the one check of the reduction order and of the merge that shares nothing
+    with the device's order: tests/test_ret_filter_domain_gpu.py compares the kernels with the restatement bit for bit, so a mistake the
+    two shared in the order or in the merge would show here and nowhere else.
+
+    Bound.  With u = 2^-53, M2 is a sum of non-negative terms (squared deviations, and delta^2 weights at every merge), built in
+    levels: 8 levels of a tile's halving tree, at most L merges along a run, 3 levels of the tree over the runs, K merges into the
+    state: depth = 8 + L + 3 + K on the longest path.  Each level rounds a few times (the sum, the product delta * delta, the weight
+    n (n_b / n'), their product: at most 8 roundings counting those of delta itself), and a sum of non-negative terms carries relative
+    errors forward without amplifying them, so the roundings of the M2 path alone give a relative error of at most 8 u depth.  What
+    does amplify is the error of the means: a mean near |mean| is known to about u depth |mean| absolute, it enters delta, and an error
+    e in the deltas moves M2 by up to about 2 e sqrt(N M2): relative to M2 that is u depth |mean| sqrt(N / M2) <= u depth kappa with
+    kappa = sqrt(1 + N mean^2 / M2), the condition number of the variance.  Hence
+        |M2 - exact| <= 8 u depth kappa exact      and      |mean - exact| <= 8 u depth kappa sqrt(M2 / N),
+    the second because a mean's error is a sum of rounding errors of quantities of size |mean| <= kappa sqrt(M2 / N).  kappa is taken
+    from the exact values.
+
+    Measured with these inputs (errors in units of u, and the bound 8 depth kappa in the same unit): see profiles/ret_filter/README.md."""
+    from ship_sim_gym_amd.ret_filter import ret_filter_reference
+    rew, done = make(K, n, seed=1000 * n + K)
+    if not dones:
+        done = np.zeros_like(done)
+    s, carry = _samples(np.zeros(n), rew, done, gamma)
+    st, ref_carry, _, _ = ret_filter_reference(np.zeros(4), np.zeros(n), rew, done, gamma)
+    assert np.array_equal(ref_carry, carry) and st[3] == K * n
+    mean, m2, N = _exact_mean_m2(s)
+    assert N == K * n and m2 > 0
+    u = 2.0 ** -53
+    depth = 8 + _geometry(n)[1] + 3 + K
+    kappa = float(1 + N * mean * mean / m2) ** 0.5
+    err_m2 = float(abs(fractions.Fraction(float(st[1])) - m2) / m2)
+    err_mean = float(abs(fractions.Fraction(float(st[0])) - mean))
+    scale = float(m2 / N) ** 0.5
+    print("%s: kappa %.4g  depth %d  M2 error %.4g u (bound %.4g u)  mean error %.4g u sqrt(M2/N) (same bound)"
+          % (name, kappa, depth, err_m2 / u, 8 * depth * kappa, err_mean / scale / u))
+    assert err_m2 <= 8 * u * depth * kappa, (err_m2 / u, 8 * depth * kappa)
+    assert err_mean <= 8 * u * depth * kappa * scale, (err_mean / scale / u, 8 * depth * kappa)
+    if "ill" in name:
+        assert kappa > 1e6 and (s == rew).all()                            # (gamma = 0: the samples are the rewards)
 
 
 def test_frozen_reference():

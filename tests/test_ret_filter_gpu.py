@@ -7,7 +7,9 @@ walk and of the device's reduction order): count, mean, M2 and the carry bit for
 
 Shapes: n in {1, 2, 255, 256, 257, 769} (one env, below / at / above the 256-env tile, four tiles of which one a tail) x K in {1, 2, 5}
 (below, half of and above the four-step staging); n = 2049 and 4097 at K = 3 (runs of 2 and 3 tiles, empty runs, a one-row tail tile);
-K = 9 on a row pitch of n + 5 (two full stagings and one step, padded rows)."""
+K = 9 on a row pitch of n + 5 (two full stagings and one step, padded rows).  The inputs, the comparison rule and the handles fixture
+live in tests/ret_filter_support.py; the rest of the domain — every pass count of the three launches up to K = 1024, runs of more than
+eight tiles, the value edges, the member limit — is in tests/test_ret_filter_domain_gpu.py."""
 import os
 import re
 import subprocess
@@ -18,80 +20,11 @@ import pytest
 
 from gpu_support import DEV, ROOT, torch_cuda, vec  # noqa: F401
 from ppo_reference import actor_critic_policy
+from ret_filter_support import D, _check, _dev, _filter, _inputs, handles  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-D = 7
-
-
-def _inputs(K, n, seed):
-    """(rew f64 [K, n], done u8 [K, n]) in numpy."""
-    rng = np.random.RandomState(seed)
-    rew = rng.choice([-0.01, 1.0, -1.0], size=(K, n), p=[0.9, 0.05, 0.05])
-    rew[:, rng.randint(n)] = rng.uniform(-2.0, 2.0, K)
-    done = (rng.random_sample((K, n)) < 0.05).astype(np.uint8)
-    if n >= 2:
-        done[:, 0], done[:, n - 1] = 0, 1
-    return rew, done
-
-
-def _dev(torch, rew, done, pad=0):
-    """The device copies, as [:, :n] views of buffers with a row pitch of n + pad (the padding holds NaN / 0xFF)."""
-    K, n = rew.shape
-    r = torch.full((K, n + pad), float("nan"), dtype=torch.float64, device=DEV)
-    d = torch.full((K, n + pad), 0xFF, dtype=torch.uint8, device=DEV)
-    r[:, :n] = torch.from_numpy(rew).to(DEV)
-    d[:, :n] = torch.from_numpy(done).to(DEV)
-    return r[:, :n], d[:, :n]
-
-
-def _filter(env, **kw):
-    from ship_sim_gym_amd.ret_filter import ReturnFilter
-    return ReturnFilter(env, **kw)
-
-
-def _ulp_close(got, want, ulps=2):
-    return np.all(np.abs(got - want) <= ulps * np.spacing(np.abs(want)))
-
-
-def _check(flt, state0, carry0, rew, done, out, denom, member=0, cols=None, gamma=None):
-    """One member's results of an updating apply against ret_filter_reference.  state0 [4] / carry0 [n_m]: what the member had before;
-    rew / done: numpy [K, n_m], the member's columns; out / denom: the device's.  Returns (state, carry) of the device (numpy)."""
-    from ship_sim_gym_amd.ret_filter import ret_filter_reference
-    cols = slice(0, rew.shape[1]) if cols is None else cols
-    gamma = flt.gamma[member] if gamma is None else gamma
-    want_state, want_carry, _, want_den = ret_filter_reference(state0, carry0, rew, done, gamma, flt.clip, flt.eps)
-    st, carry = flt.state[member].cpu().numpy(), flt.carry[cols].cpu().numpy()
-    den = denom[:, member].cpu().numpy()
-    got = out[:, cols].cpu().numpy()
-    assert st[3] == want_state[3] == state0[3] + rew.size, (st[3], want_state[3])
-    assert st[0] == want_state[0] and st[1] == want_state[1], (st, want_state)
-    assert np.array_equal(carry, want_carry)
-    assert _ulp_close(den, want_den), np.abs(den - want_den).max()
-    own = np.sqrt(st[1] / (st[3] - 1.0)) + flt.eps if st[3] >= 2 else 1.0
-    assert _ulp_close(st[2], own) and st[2] == den[-1], (st[2], own, den[-1])
-    want = rew / den[:, None]
-    if flt.clip > 0.0:
-        want = np.clip(want, -flt.clip, flt.clip)
-    assert np.array_equal(got, want), np.abs(got - want).max()
-    return st, carry
-
-
 SHAPES = [(n, K, 0) for n in (1, 2, 255, 256, 257, 769) for K in (1, 2, 5)] + [(2049, 3, 0), (4097, 3, 0), (257, 9, 5)]
-
-
-@pytest.fixture(scope="module")
-def handles(torch_cuda):
-    """One handle per env count of the module (an env is the handle only: nothing here steps it)."""
-    made = {}
-
-    def get(n):
-        if n not in made:
-            made[n] = vec(n, D)
-        return made[n]
-    yield get
-    for env in made.values():
-        env.close()
 
 
 @pytest.mark.parametrize("n,K,pad", SHAPES, ids=["n%d-K%d%s" % (n, K, "-pad%d" % p if p else "") for n, K, p in SHAPES])
