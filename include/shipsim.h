@@ -1301,6 +1301,7 @@ int ssg_pop_gae_boot(ssg_handle *h, const ssg_population *pop, const float *dev_
  *   g[p] = w_0*row_0[p];   g[p] = g[p] + w_r*row_r[p]  for r = 1 .. W-1
  * every product and every sum rounded to f32 on its own (no fused multiply-add): the mean-loss gradient of the job's minibatch.  Stats
  * columns 0..4 are combined the same way; column 6 is the KL coefficient in use, columns 5 and 7 as ssg_ppo_update_ext writes them.
+ * With ext NULL only columns 0..3 are combined: columns 4..7 are written as zeros whatever the rows hold there.
  * One launch of ceil((P + 8) / 256) workgroups of 256, entry p on lane p % 256 of workgroup p / 256; without gradient-norm clipping it
  * ends with Adam step `step` (ssg_ppo_adam's constants and formula).  With ext->max_grad_norm > 0 each workgroup also forms the f64
  * sum of squares of its entries p < P (a halving tree), and the clip launch of ssg_ppo_update_ext follows: partials in index order,

@@ -1451,7 +1451,7 @@ __global__ void __launch_bounds__(256) dp_apply_kernel(const float *__restrict__
     if (p >= P && p < stride) {
         const int q = p - P;
         const float klc = ext && kl_coef ? kl_coef[0] : 0.0f;
-        if (stats_out) stats_out[q] = q < 5 ? s : (q == 6 ? (klc > 0.0f ? klc : 0.0f) : 0.0f);
+        if (stats_out) stats_out[q] = q < (ext ? 5 : 4) ? s : (q == 6 ? (klc > 0.0f ? klc : 0.0f) : 0.0f);
         if (ext && q == 4) klacc[0] = first_chunk ? s : klacc[0] + s;
     }
     if (p < P) {

@@ -56,7 +56,9 @@ def moments_reference(rows, adv_eps):
     if not n >= 2.0:
         return np.array([np.nan, np.nan, np.nan, 0.0], dtype=np.float32)
     mean = S / n
-    var = max(0.0, (Q - S * mean) / (n - 1.0))
+    var = (Q - S * mean) / (n - 1.0)
+    if var < 0.0:  # (the device's comparison: a NaN variance stays NaN, which max(0.0, var) would turn into 0)
+        var = 0.0
     stdp = np.float32(np.sqrt(var)) + np.float32(adv_eps)
     return np.array([np.float32(mean), stdp, np.float32(1.0) / stdp, 0.0], dtype=np.float32)
 
@@ -96,7 +98,7 @@ def apply_reference(rows, counts, params, adam_mv, step, hp, max_grad_norm=0.0, 
     """ssg_ppo_apply_shards in numpy, in the device's order of operations.  rows f32 [W, P + 8], counts the W sample counts, params f32
     [P], adam_mv f32 [2P], step the Adam step to take.  ext: the extended loss's columns (kl_coef: the coefficient in use or None;
     klacc: the running KL sum before the call).  Returns a dict: g (the combined gradient, unclipped), norm and coef (f32; 0 and 1
-    with the clip off), params, adam_mv, stats f32 [8], klacc and kl_coef after the call."""
+    with the clip off), params, adam_mv, stats f32 [8] (columns 4..7 zero under the plain loss), klacc and kl_coef after the call."""
     import numpy as np
     f32 = np.float32
     rows = np.asarray(rows, dtype=f32)
@@ -109,7 +111,8 @@ def apply_reference(rows, counts, params, adam_mv, step, hp, max_grad_norm=0.0, 
     g, tail = s[:P].copy(), s[P:]
     klc = f32(kl_coef) if (ext and kl_coef is not None) else f32(0.0)
     stats = np.zeros(8, dtype=f32)
-    stats[:5] = tail[:5]
+    ncol = 5 if ext else 4  # (the plain loss has no KL column: whatever the rows hold there, columns 4..7 are zero)
+    stats[:ncol] = tail[:ncol]
     stats[6] = klc if klc > 0 else f32(0.0)
     klacc = f32(klacc)
     if ext:

@@ -153,24 +153,25 @@ def ref_grad(torch, pol, b, idx, advn, dtype, **loss_kw):
     return (p.grad.detach(), terms) + tuple(out[6:])
 
 
-def ref_update(torch, pol, b, advn, perms, minibatches, dtype, adam=None, max_grad_norm=0, **loss_kw):
+def ref_update(torch, pol, b, advn, perms, minibatches, dtype, adam=None, max_grad_norm=0, index_lists=None, **loss_kw):
     """ppo_torch's update loop in `dtype` from pol's parameters, with ONE torch.optim.Adam(**adam) (lr 3e-4 by default) over one
     [epochs, n] perm or a list of them (consecutive calls): every perm row is torch.chunk'ed into `minibatches`, and gradients are
-    clipped with clip_grad_norm_ where max_grad_norm > 0.  Returns (parameters, Adam's state, the minibatches' mean KLs in order —
-    empty under plain_loss)."""
+    clipped with clip_grad_norm_ where max_grad_norm > 0.  index_lists (perms and minibatches are then unused): the minibatches
+    themselves, one index tensor each, in the order they are taken.  Returns (parameters, Adam's state, the minibatches' mean KLs in
+    order — empty under plain_loss)."""
     p = pol.params.detach().to(dtype).clone().requires_grad_(True)
     opt = torch.optim.Adam([p], **(adam or {"lr": 3e-4}))
     kls = []
-    for perm in perms if isinstance(perms, (list, tuple)) else [perms]:
-        for row in perm:
-            for idx in row.chunk(minibatches):
-                out = _loss(torch, pol, p, minibatch(torch, pol, b, idx, advn, dtype), loss_kw)
-                opt.zero_grad()
-                out[0].backward()
-                if max_grad_norm > 0:
-                    torch.nn.utils.clip_grad_norm_([p], max_grad_norm)
-                opt.step()
-                kls += [float(o.detach()) for o in out[5:6]]
+    if index_lists is None:
+        index_lists = [idx for perm in (perms if isinstance(perms, (list, tuple)) else [perms]) for row in perm for idx in row.chunk(minibatches)]
+    for idx in index_lists:
+        out = _loss(torch, pol, p, minibatch(torch, pol, b, idx, advn, dtype), loss_kw)
+        opt.zero_grad()
+        out[0].backward()
+        if max_grad_norm > 0:
+            torch.nn.utils.clip_grad_norm_([p], max_grad_norm)
+        opt.step()
+        kls += [float(o.detach()) for o in out[5:6]]
     return p.detach(), opt.state[p], kls
 
 

@@ -22,8 +22,10 @@ def test_one_shard_is_the_identity_on_the_gradient():
     params, mv = rng.randn(P).astype(np.float32), np.abs(rng.randn(2 * P)).astype(np.float32)
     out = dp.apply_reference(row, [467], params, mv, 3, HP)
     assert dp.shard_weights([467]).tolist() == [1.0]
-    assert np.array_equal(out["g"], row[0, :P]) and np.array_equal(out["stats"][:5], row[0, P:P + 5])
-    assert out["norm"] == 0 and out["coef"] == 1 and list(out["stats"][5:]) == [0, 0, 0]
+    assert np.array_equal(out["g"], row[0, :P]) and np.array_equal(out["stats"][:4], row[0, P:P + 4])
+    assert out["norm"] == 0 and out["coef"] == 1 and list(out["stats"][4:]) == [0, 0, 0, 0]  # (the plain loss has no KL column)
+    ext = dp.apply_reference(row, [467], params, mv, 3, HP, ext=True)
+    assert np.array_equal(ext["stats"][:5], row[0, P:P + 5]) and list(ext["stats"][5:]) == [0, 0, 0] and np.array_equal(ext["params"], out["params"])
     p2, mv2 = dp.adam_reference(row[0, :P], params, mv, 3, HP)
     assert np.array_equal(out["params"], p2) and np.array_equal(out["adam_mv"], mv2)
     assert not np.array_equal(p2, params)
@@ -95,6 +97,82 @@ def test_moments_of_one_row_are_the_gae_statistics():
     assert np.all(np.abs(both[:3] - stats[:3]) <= np.spacing(np.abs(stats[:3])))
     assert abs(float(both[0]) - a.mean()) <= np.spacing(np.float32(a.mean())) and abs(float(both[1]) - a.std(ddof=1)) <= 2e-7 * a.std(ddof=1)
     assert np.isnan(dp.moments_reference([[1.0, 1.0, 1.0, 0.0]], 1e-8)[:3]).all()
+
+
+@pytest.mark.parametrize("W,P", [(3, 5), (64, 3)])
+def test_references_against_exact_rational_arithmetic(W, P):
+    """apply_reference's combine and moments_reference against fractions.Fraction, so that the GPU modules' bitwise agreement with
+    them is agreement with the arithmetic and not with a shared mistake.
+
+    The combine, u = 2^-24: entry p is W products and W - 1 sums, 2W - 1 roundings, and every weight carries its own rounding (the f64
+    quotient rounded to f32).  A term w_r row_r[p] passes through at most W + 1 of them (its weight, its product, the W - 1 sums), so
+    |g - exact| <= ((1 + u')^(W + 1) - 1) sum_r |w_r row_r[p]|, u' = u (1 + 2^-29) for the weight's double rounding — below the bound
+    asserted here, (2W - 1) u sum_r |w_r row_r[p]| for the entry's roundings plus u sum_r |w_r row_r[p]| for the weights', for every
+    W >= 2.  (No product here is subnormal.)
+
+    The mean: with row sums that are exact in f64 it is the exact S / n rounded to f64 once, then to f32 once."""
+    from fractions import Fraction as Fr
+    from ship_sim_gym_amd import dp
+    rng = np.random.RandomState(100 * W + P)
+    counts = [int(c) for c in rng.randint(1, 2000, W)]
+    rows = (rng.randn(W, P + 8) * np.exp(rng.randn(W, 1))).astype(np.float32)
+    out = dp.apply_reference(rows, counts, np.zeros(P, np.float32), np.zeros(2 * P, np.float32), 1, HP, ext=True, kl_coef=1.0)
+    got = np.concatenate([out["g"], out["stats"][:5]])
+    total, u, worst = sum(counts), Fr(1, 2 ** 24), Fr(0)
+    assert W >= 2 and (1 + u * (1 + Fr(1, 2 ** 29))) ** (W + 1) - 1 <= 2 * W * u
+    for p in range(P + 5):
+        terms = [Fr(c, total) * Fr(float(rows[r, p])) for r, c in enumerate(counts)]
+        err, bound = abs(Fr(float(got[p])) - sum(terms)), 2 * W * u * sum(abs(t) for t in terms)
+        assert err <= bound, (p, float(err), float(bound))
+        worst = max(worst, err / bound)
+    print("combine W=%d: worst |g - exact| / bound %.3f" % (W, float(worst)))
+    assert worst > 0  # (the f32 combine is not exact: the bound is not met by accident)
+    w = dp.shard_weights(counts)
+    assert all(abs(Fr(float(w[r])) - Fr(c, total)) <= u * Fr(c, total) for r, c in enumerate(counts))
+    # the moments: S_r multiples of 2^-10 below 2^20, Q_r likewise, integer n_r — every f64 sum of W of them is exact
+    m = np.zeros((W, 4))
+    m[:, 2] = rng.randint(1, 5000, W)
+    m[:, 0] = np.round(rng.randn(W) * m[:, 2] * 1024) / 1024
+    m[:, 1] = np.round((m[:, 0] ** 2 / m[:, 2] + m[:, 2] * (0.5 + rng.rand(W))) * 1024) / 1024
+    S, Q2, n = (sum(Fr(float(v)) for v in m[:, c]) for c in range(3))
+    assert all(float(x) == float(np.sum(m[:, c])) and Fr(float(x)) == x for c, x in enumerate((S, Q2, n)))
+    row = dp.moments_reference(m, 1e-8)
+    mean = S / n
+    assert row[0] == np.float32(float(mean))  # (int / int true division is correctly rounded: one f64 rounding, then one f32)
+    assert abs(Fr(float(row[0])) - mean) <= (u + Fr(1, 2 ** 53)) * (1 + u) * abs(mean)
+    var = (Q2 - S * mean) / (n - 1)
+    assert var > 0 and abs(float(row[1]) - float(var) ** 0.5) <= 4 * float(u) * float(var) ** 0.5 and row[2] == np.float32(1.0) / row[1]
+
+
+def test_support_restatements_agree_with_the_references():
+    """tests/dp_support.py's sums (what the GPU module compares the workspace's partials with) against the references that form the
+    same sums inside: apply_reference's norm, gae_boot_reference's statistics past one trip of the strided loop."""
+    import dp_support as S
+    from ship_sim_gym_amd import dp
+    from ship_sim_gym_amd.ppo import _tree256, gae_boot_reference
+    rng = np.random.RandomState(9)
+    P = 600
+    rows = rng.randn(2, P + 8).astype(np.float32)
+    out = dp.apply_reference(rows, [3, 5], np.zeros(P, np.float32), np.zeros(2 * P, np.float32), 1, HP, max_grad_norm=0.5, ext=True)
+    part = S.square_partials(out["g"], P + 8)
+    assert part.shape == (3,) and S.norm_of_partials(part) == out["norm"]
+    tail = float(np.sum(out["g"][512:].astype(np.float64) ** 2))  # (the third workgroup: 88 entries, then zeros)
+    assert abs(part[2] - tail) <= 88 * 2.0 ** -53 * tail
+    x = rng.randn(4, 256)
+    assert np.array_equal(S.trees256(x), [_tree256(r.copy().reshape(256, 1))[0] for r in x])
+    K, n = 1, 65537
+    rew, done = rng.randn(K, n), (rng.rand(K, n) < 0.1).astype(np.uint8)
+    val, last = rng.randn(K, n).astype(np.float32), rng.randn(n).astype(np.float32)
+    adv, _, stats = gae_boot_reference(rew, done, val, last, np.zeros((K, n), np.float32))
+    a = np.zeros(257 * 256)
+    a[:n] = adv[0].astype(np.float64)
+    gae_part = np.stack([S.trees256(a), S.trees256(a * a)], axis=1)  # K = 1: a workgroup's partial is the tree over its 256 envs
+    s, q, trips = S.readd_partials(gae_part)
+    assert trips == 2 and np.array_equal(dp.moments_reference([[s, q, float(n), 0.0]], 1e-8), stats)
+    assert S.bits(np.array([-0.0, 0.0], np.float32)).tolist() == [0x80000000, 0]
+    with pytest.raises(AssertionError):
+        S.assert_bits(np.array([-0.0], np.float32), np.array([0.0], np.float32), "signed zero")
+    S.assert_bits(np.array([np.nan, 1.0], np.float32), np.array([-np.nan, 1.0], np.float32), "NaN payloads", nan_ok=True)
 
 
 def test_chunk_counts():

@@ -14,6 +14,7 @@ import sys
 import numpy as np
 import pytest
 
+from dp_support import KLACC, f32 as _f32, layout as _layout
 from gpu_support import ROOT, torch_cuda  # noqa: F401
 from ppo_reference import actor_critic_policy, check_per_tensor, ref_grad, split_policy, synthetic_batch
 
@@ -21,22 +22,11 @@ pytestmark = pytest.mark.gpu
 
 H, K, N_SHARD, EPOCHS, MINIBATCHES = 32, 7, 200, 2, 3
 EXT = dict(vf_clip=0.2, max_grad_norm=0.5, kl_coef=1.0, kl_target=0.01)
-KLACC = 256 + 16  # the apply's running KL sum in the workspace: float 4 of the extended layout's first part
 
 
 def _vec(n=N_SHARD, base=0):
     from ship_sim_gym_amd.vec_env import ShipVecEnv
     return ShipVecEnv(n, n_maps=16, env_id_base=base)
-
-
-def _f32(t):
-    return t.detach().cpu().numpy()
-
-
-def _layout(P):
-    """Byte offsets of the clip sequence's gradient vector and partials in the workspace (csrc/shipsim_internal.h: ppo_ext_layout)."""
-    gvec = 256 + 256
-    return gvec, gvec + (4 * P + 255) // 256 * 256
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
