@@ -361,7 +361,10 @@ int ssg_dyn_invalidate(ssg_handle *h, const uint8_t *dev_mask, void *stream);
 /* Replaces: ShipGame.render + ShipGame.get_screen (game.py:133-138,197-229) for ONE env: an RGB frame of `width` x
  * `height` pixels covering the env's bounds, laid out like pygame.surfarray.array3d ([x][y][3], screen y down).
  * flags bit 0 = GameConfig.DEBUG drawing (shapes in their colours + one circle per lidar beam end); the yellow
- * player marker is always drawn.  Debugging / video aid (`metadata['render.modes']` lists 'rgb_array',
+ * player marker is always drawn.  A beam whose origin lies inside a bank hull (or on its boundary) is drawn as a hit at
+ * the beam's far end, as cpShapeSegmentQuery reports it.  Arguments are checked before the handle's bindings: a NULL
+ * handle or buffer, an env_index outside 0 .. n_envs-1 or a width / height outside 1 .. 8192 is SSG_ERR_BAD_ARG on any
+ * handle, then an unbound handle is SSG_ERR_NOT_BOUND.  Debugging / video aid (`metadata['render.modes']` lists 'rgb_array',
  * ship_env.py:18); not a hot path. */
 int ssg_render(ssg_handle *h, int env_index, int width, int height, uint8_t *dev_rgb, uint32_t flags, void *stream);
 

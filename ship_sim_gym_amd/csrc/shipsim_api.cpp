@@ -2730,10 +2730,12 @@ int ssg_dyn_invalidate(ssg_handle *h, const uint8_t *dev_mask, void *stream)
 
 int ssg_render(ssg_handle *h, int env_index, int width, int height, uint8_t *dev_rgb, uint32_t flags, void *stream)
 {
-    int rc = check_ready(h, true);
-    if (rc != SSG_OK) return rc;
+    // the arguments first: a bad one is refused before anything asks for a device
+    if (!h) return SSG_ERR_BAD_ARG;
     if (!dev_rgb || env_index < 0 || env_index >= h->cfg.n_envs || width < 1 || height < 1 || width > 8192 || height > 8192)
         return fail(h, SSG_ERR_BAD_ARG, "ssg_render: bad argument");
+    int rc = check_ready(h, true);
+    if (rc != SSG_OK) return rc;
     hipError_t e = ssg::launch_render(h->dev, h->dyn, env_index, width, height, dev_rgb, flags, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("render launch: ") + hipGetErrorString(e));
     return SSG_OK;

@@ -4,8 +4,13 @@
 // pymunk's debug draw paints every shape of the space in insertion order with its colour — banks (139, 69, 19)
 // models.py:181, goals green game.py:88, the player white game.py:275, traffic black game.py:284-286 — then one
 // radius-10 circle per lidar beam at the beam's end point (red where it hit a bank, green where it did not,
-// game.py:207-225); finally a yellow radius-10 circle at the player's position (game.py:227-229).  Screen y points
-// down (`invert_p`, game.py:73-75); the buffer is laid out like pygame.surfarray.array3d: [x][y][rgb].
+// game.py:207-225; a beam whose origin lies inside a bank or on its boundary is a hit reported at the beam's far end, as
+// cpShapeSegmentQuery reports it); finally a yellow radius-10 circle at the player's position (game.py:227-229).  The
+// radii are 10 world units at every frame size.  The beams are queried at the current pose (the reference draws the
+// previous step's results and rounds circle centres to integer pixels).  Screen y points down (`invert_p`,
+// game.py:73-75); the buffer is laid out like pygame.surfarray.array3d: [x][y][rgb]; pixel (sx, sy) shows the world point
+// ((sx + 0.5) W / width, H - (sy + 0.5) H / height).  A goal is drawn while its bit of the goal mask is set, from the
+// bank record (n_ships == 1) or from its body's position (config 4).
 // One thread per pixel: filled convex shapes are half-plane tests against the same splitting planes the physics uses.
 // Not pixel-identical to pygame's scan conversion or pymunk's outline style (neither is available to compare).
 #include <hip/hip_runtime.h>
@@ -42,15 +47,18 @@ __device__ bool in_ship(const double *hull, const double *nrm, double px, double
     return in;
 }
 
-// cpPolyShapeSegmentQuery (radius 0) of the segment a->b against one hull: smallest entering alpha, or 2 = miss
+// cpShapeSegmentQuery (radius 0) of the segment a->b against one hull: smallest entering alpha, 2 = miss, or -1 = the point
+// query at a is not positive (a inside the hull or on its boundary): a hit at alpha 0 whose reported point stays b, the far end
 __device__ double seg_hull(const double *pl, int n, double ax, double ay, double bx, double by)
 {
     double best = 2.0;
+    bool inside = n > 0;
     for (int j = 0; j < n; ++j) {
         const double *q = pl + SSG_PLANE_DOUBLES * j;
         const double nx = q[2], ny = q[3];
         const double an = ax * nx + ay * ny, bn = bx * nx + by * ny;
         const double d = an - q[4];
+        inside &= d <= 0.0;
         if (d < 0.0) continue;
         const double t = d / fmax(an - bn, 2.2250738585072014e-308);
         if (t < 0.0 || t > 1.0) continue;
@@ -60,7 +68,7 @@ __device__ double seg_hull(const double *pl, int n, double ax, double ay, double
         const double dtmin = nx * qp[1] - ny * qp[0], dtmax = nx * q[1] - ny * q[0];
         if (dtmin <= dt && dt <= dtmax && t < best) best = t;
     }
-    return best;
+    return inside ? -1.0 : best;
 }
 
 } // namespace
@@ -93,7 +101,7 @@ __global__ void render_kernel(const DevCfg c, const DynCfg d, int e, int width, 
         double alpha = 2.0;
         for (int s = 0; s < 2 && alpha > 1.0; ++s) // first listed shape that reports a hit wins
             alpha = seg_hull(rec + SSG_MAP_OFF_PLANES + s * SSG_MAX_HULL * SSG_PLANE_DOUBLES, (int)rec[SSG_MAP_OFF_COUNTS + s], ox, oy, ex, ey);
-        const double tt = alpha <= 1.0 ? alpha : 1.0;
+        const double tt = (alpha >= 0.0 && alpha <= 1.0) ? alpha : 1.0; // a miss and an origin inside a hull both report the far end
         beam_x[i] = ox + (ex - ox) * tt; beam_y[i] = oy + (ey - oy) * tt; beam_hit[i] = alpha <= 1.0;
     }
     __syncthreads();
@@ -119,12 +127,10 @@ __global__ void render_kernel(const DevCfg c, const DynCfg d, int e, int width, 
                 const double *t = c.dyn_f64 + (size_t)(DC_TRAFFIC + 9 * k) * np + e;
                 if (in_ship(d.thull[k], d.tnrm[k], t[0], t[np], t[2 * np], x, y)) { R = 0; G = 0; B = 0; }
             }
-        const double sxr = c.width / width; // the circles have a radius of 10 screen pixels of the reference's screen
         for (int i = 0; i < c.n_beams; ++i) {
             const double ddx = x - beam_x[i], ddy = y - beam_y[i];
             if (ddx * ddx + ddy * ddy <= 100.0) { R = beam_hit[i] ? 255 : 0; G = beam_hit[i] ? 0 : 255; B = 0; }
         }
-        (void)sxr;
     }
     if ((x - px) * (x - px) + (y - py) * (y - py) <= 100.0) { R = 255; G = 255; B = 0; }
     uint8_t *o = rgb + ((size_t)sx * height + sy) * 3;

@@ -118,6 +118,29 @@ def test_state_layout_and_unbound_errors(native):
         L.ssg_destroy(h2)
 
 
+def test_render_refuses_bad_arguments_before_any_device_work(native):
+    """ssg_render checks its arguments before it looks at the handle's bindings or asks for a device: SSG_ERR_BAD_ARG (-1) for a NULL
+    handle or buffer, an env_index outside 0 .. n_envs-1 and a width or height outside 1 .. 8192, on a handle that has no state blob;
+    with arguments in range the same handle answers SSG_ERR_NOT_BOUND (-3).  (That 8192 renders is checked on the GPU.)"""
+    L = native.lib()
+    c = native.default_config()
+    c.n_envs = 8
+    h = C.c_void_p()
+    native.check(L.ssg_create(C.byref(c), C.byref(h)))
+    buf = C.c_void_p(0x1000)  # never dereferenced: no call here gets as far as a launch
+    assert L.ssg_render(None, 0, 4, 4, buf, 1, None) == -1
+    assert L.ssg_render(h, 0, 4, 4, None, 1, None) == -1 and b"ssg_render" in L.ssg_last_error(h)
+    for e in (-1, 8):
+        assert L.ssg_render(h, e, 4, 4, buf, 1, None) == -1, e
+    for v in (0, -1, 8193):
+        assert L.ssg_render(h, 0, v, 4, buf, 1, None) == -1, v
+        assert L.ssg_render(h, 0, 4, v, buf, 0, None) == -1, v
+    assert L.ssg_render(h, 0, 4, 4, buf, 1, None) == -3 and b"ssg_bind_state" in L.ssg_last_error(h)
+    for e, w, hh in ((7, 8192, 1), (0, 1, 8192), (7, 8192, 8192)):  # the limits themselves are arguments in range
+        assert L.ssg_render(h, e, w, hh, buf, 0, None) == -3, (e, w, hh)
+    L.ssg_destroy(h)
+
+
 def test_host_geometry_agrees_with_oracle(native, oracle):
     """Two independent implementations (Andrew monotone chain in C++ vs QuickHull in C) of what pm.Poly / the fat
     segment queries of gen_goal_path did for the reference, on the reference's own maps."""
