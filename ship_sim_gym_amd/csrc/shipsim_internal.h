@@ -508,11 +508,16 @@ __device__ __forceinline__ int reset_env(const DevCfg &c, const int e, const int
 
 // sin / cos of a body angle (cpvforangle).  The library's sincos is ~190 instructions of full-range machinery; body
 // angles stay within a few turns, so for |a| <= 2^18 this is a three-term Cody-Waite reduction by pi/2 with FMAs
-// (error < 2^-100 |a|) followed by the fdlibm / musl kernels on [-pi/4, pi/4] with the reduction's tail: within 1 ulp
-// of a correctly rounded sin / cos (checked against glibc on 2e7 arguments: 97.6 % identical, the rest 1 ulp), the
-// same class as the library's own result; (0) -> (0, 1) exactly.  One definition for the step kernel and the dyn
-// kernels, so the player's rotation has the same bits wherever it is recomputed.
-__device__ __forceinline__ void sincos_body(double a, double *sn_out, double *cs_out)
+// (error < 2^-100 |a|) followed by the fdlibm / musl kernels on [-pi/4, pi/4] with the reduction's tail.  The contract,
+// for |a| <= 2^18: |error| <= max(1 ulp of the exact result, 2^-100 |a|) — within 1 ulp of sin / cos wherever the
+// result is large enough for the reduction's error to resolve, and 2^-100 |a| absolute at the doubles nearest k pi/2,
+// whose exact sin or cos is tiny (hundreds of ulps of a 1e-14 result there, 1e-27 absolute: the same class as the
+// library's own result for a body's rotation); sin is odd and cos even bit for bit; (0) -> (0, 1) exactly.  Asserted
+// against an exact (mpmath) fixture built around these edges by tests/test_sincos.py, on a host build of this very
+// function (it is pure IEEE f64 with fma and rint: host and device bits agree), and on the step kernel's own bits in
+// every layout by tests/test_sincos_gpu.py; the measured errors: profiles/sincos/README.md.  One definition for the
+// step kernel and the dyn kernels, so the player's rotation has the same bits wherever it is recomputed.
+__host__ __device__ __forceinline__ void sincos_body(double a, double *sn_out, double *cs_out)
 {
     if (!(fabs(a) <= 262144.0)) { // (also NaN / inf)
         sincos(a, sn_out, cs_out);

@@ -100,8 +100,10 @@ template <class T> __device__ __forceinline__ void set_b32_zero(T &d) { static_a
 // The arithmetic: the library's sincos is ~190 instructions on role 3's chain every step (full-range Payne-Hanek
 // machinery); body angles stay within a few turns, so for |a| <= 2^18 this is a three-term Cody-Waite reduction by pi/2
 // with FMAs (error < 2^-100 |a|) followed by the fdlibm / musl kernels on [-pi/4, pi/4] with the reduction's tail:
-// within 1 ulp of a correctly rounded sin / cos (checked against glibc on 2e7 arguments: 97.6 % identical, the rest
-// 1 ulp), the same class as the library's own result; sincos_call(0) = (0, 1) exactly (cpvforangle(0)).
+// |error| <= max(1 ulp of the exact result, 2^-100 |a|), i.e. within 1 ulp of sin / cos except at the doubles nearest
+// k pi/2, where the tiny result carries the reduction's absolute error instead (sincos_body's comment in
+// shipsim_internal.h); sincos_call(0) = (0, 1) exactly (cpvforangle(0)).  tests/test_sincos.py asserts the bound on
+// an exact fixture, tests/test_sincos_gpu.py on the bits this call and the DYN instantiation's inlined copy return.
 __device__ __attribute__((noinline)) double2 sincos_call(double a) // returns (sin a, cos a) in registers
 {
     double2 o;
