@@ -66,36 +66,6 @@ def _timed(fn):
     return e0.elapsed_time(e1)  # ms
 
 
-def torch_update(net, opt, b, horizon, envs, D, epochs, minibatches, gen, gamma=0.99, lam=0.95, clip=0.2):
-    """train/ppo_torch.py's update, as it runs after a native rollout (rew / done converted as rollout() does)."""
-    dev = b["obs"].device
-    rew, done, val = b["rew"].float(), b["done"].float(), b["val"]
-    adv = torch.zeros(envs, device=dev)
-    advs, rets = [None] * horizon, [None] * horizon
-    nxt = b["last_val"]
-    for t in reversed(range(horizon)):
-        nonterm = 1.0 - done[t]
-        delta = rew[t] + gamma * nxt * nonterm - val[t]
-        adv = delta + gamma * lam * nonterm * adv
-        advs[t], rets[t] = adv, adv + val[t]
-        nxt = val[t]
-    b_obs, b_act = b["obs"].reshape(horizon * envs, D), b["act"].long().reshape(-1)
-    b_logp, b_adv, b_ret = b["logp"].reshape(-1), torch.cat(advs), torch.cat(rets)
-    b_adv = (b_adv - b_adv.mean()) / (b_adv.std() + 1e-8)
-    n = b_obs.shape[0]
-    for _ in range(epochs):
-        perm = torch.randperm(n, device=dev, generator=gen)
-        for mb in perm.chunk(minibatches):
-            logits, v = net(b_obs[mb])
-            dist = torch.distributions.Categorical(logits=logits)
-            ratio = torch.exp(dist.log_prob(b_act[mb]) - b_logp[mb])
-            pg = -torch.min(ratio * b_adv[mb], torch.clamp(ratio, 1 - clip, 1 + clip) * b_adv[mb]).mean()
-            loss = pg + 0.5 * (v - b_ret[mb]).pow(2).mean() - 0.01 * dist.entropy().mean()
-            opt.zero_grad()
-            loss.backward()
-            opt.step()
-
-
 def _peak_bytes(fn):
     """Peak device memory during fn() above what was allocated before it (the result included)."""
     torch.cuda.synchronize()
@@ -136,103 +106,54 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
     pol = NativePolicy.from_actor_critic(net_n, scale)
     opt = torch.optim.Adam(net.parameters(), lr=3e-4)
     ppo = NativePPO(pol, env)
-    g_t, g_n = torch.Generator(device=dev), torch.Generator(device=dev)
-    g_t.manual_seed(1)
-    g_n.manual_seed(1)
     n = horizon * envs
+
+    def seeded():
+        g = torch.Generator(device=dev)
+        g.manual_seed(1)
+        return g
+    g_t, g_n, g_p = seeded(), seeded(), seeded()
 
     def run_torch():
         with torch.no_grad():
             for p, q in zip(net.parameters(), p0):
                 p.copy_(q)
-        torch_update(net, opt, b, horizon, envs, D, epochs, minibatches, g_t)
+        # train/ppo_torch.py's update, as it runs after a native rollout (rew / done / act converted as rollout() does, inside the timing)
+        mod.torch_update(net, opt, dict(b, rew=b["rew"].float(), done=b["done"].float(), act=b["act"].long()), b["last_val"], epochs,
+                         minibatches, g_t)
 
-    def run_native():
-        with torch.no_grad():
-            for p, q in zip(net_n.parameters(), p0):
-                p.copy_(q)
-        pol.refresh()
-        nb = dict(b)
-        ppo.gae(nb)
-        ppo.update(nb, torch.stack([torch.randperm(n, device=dev, generator=g_n) for _ in range(epochs)]), epochs, minibatches)
-
-    ppo_x = NativePPO(pol, env, vf_clip=0.2, max_grad_norm=0.5, kl_coef=1.0, kl_target=0.01)
-    g_x = torch.Generator(device=dev)
-    g_x.manual_seed(1)
-
-    def run_native_ext():
-        with torch.no_grad():
-            for p, q in zip(net_n.parameters(), p0):
-                p.copy_(q)
-        pol.refresh()
-        ppo_x.kl_coef.fill_(1.0)
-        nb = dict(b)
-        ppo_x.gae(nb)
-        ppo_x.update(nb, torch.stack([torch.randperm(n, device=dev, generator=g_x) for _ in range(epochs)]), epochs, minibatches)
-
-    def run_dist():
-        ppo_x.dist(dict(b))
-
-    from ship_sim_gym_amd.ret_filter import ReturnFilter
-    rflt, rfrozen = ReturnFilter(env), ReturnFilter(env, update=False)
-    g_r = torch.Generator(device=dev)
-    g_r.manual_seed(1)
-
-    def run_native_ret():
-        with torch.no_grad():
-            for p, q in zip(net_n.parameters(), p0):
-                p.copy_(q)
-        pol.refresh()
-        nb = dict(b)
-        ppo.gae(nb, return_filter=rflt)
-        ppo.update(nb, torch.stack([torch.randperm(n, device=dev, generator=g_r) for _ in range(epochs)]), epochs, minibatches)
-
-    ppo_m = NativePPO(pol, env, adv_norm="minibatch") if adv_norm else None  # (every call binds its object's own mode on the env)
-    g_m = torch.Generator(device=dev)
-    g_m.manual_seed(1)
-
-    def run_native_mbnorm():
-        with torch.no_grad():
-            for p, q in zip(net_n.parameters(), p0):
-                p.copy_(q)
-        pol.refresh()
-        nb = dict(b)
-        ppo_m.gae(nb)
-        ppo_m.update(nb, torch.stack([torch.randperm(n, device=dev, generator=g_m) for _ in range(epochs)]), epochs, minibatches)
-
-    ppo_p = NativePPO(pol, env, perm_seed=1) if perm else None
-    g_p = torch.Generator(device=dev)
-    g_p.manual_seed(1)
-
-    def run_native_permnative():
-        with torch.no_grad():
-            for p, q in zip(net_n.parameters(), p0):
-                p.copy_(q)
-        pol.refresh()
-        nb = dict(b)
-        ppo_p.gae(nb)
-        ppo_p.update(nb, None, epochs, minibatches)
-
-    def draw_torch():
-        return torch.stack([torch.randperm(n, device=dev, generator=g_p) for _ in range(epochs)])
-
-    def draw_native():
-        return ppo_p.draw_perm(n, epochs)
-
-    if dp:  # one rank of a data-parallel job: the Python loop, a gather that is a no-op, and the apply launch in place of the reduction
-        from ship_sim_gym_amd.dp import DataParallelPPO
-        ppo_d = DataParallelPPO(pol, env)
-        g_d = torch.Generator(device=dev)
-        g_d.manual_seed(1)
-
-        def run_native_dp():
+    def native_path(trainer, gen, before=None, **gae_kw):
+        """The whole GAE + update of `trainer` from the start parameters, its permutations drawn from gen (None: by the library)."""
+        def run():
             with torch.no_grad():
                 for p, q in zip(net_n.parameters(), p0):
                     p.copy_(q)
             pol.refresh()
+            if before is not None:
+                before()
             nb = dict(b)
-            ppo_d.gae(nb)
-            ppo_d.update(nb, torch.stack([torch.randperm(n, device=dev, generator=g_d) for _ in range(epochs)]), epochs, minibatches)
+            trainer.gae(nb, **gae_kw)
+            rows = None if gen is None else torch.stack([torch.randperm(n, device=dev, generator=gen) for _ in range(epochs)])
+            trainer.update(nb, rows, epochs, minibatches)
+        return run
+
+    from ship_sim_gym_amd.ret_filter import ReturnFilter
+    rflt, rfrozen = ReturnFilter(env), ReturnFilter(env, update=False)
+    ppo_x = NativePPO(pol, env, vf_clip=0.2, max_grad_norm=0.5, kl_coef=1.0, kl_target=0.01)
+    ppo_m = NativePPO(pol, env, adv_norm="minibatch") if adv_norm else None  # (every call binds its object's own mode on the env)
+    ppo_p = NativePPO(pol, env, perm_seed=1) if perm else None
+    run_native, run_native_ret = native_path(ppo, g_n), native_path(ppo, seeded(), return_filter=rflt)
+    run_native_ext = native_path(ppo_x, seeded(), before=lambda: ppo_x.kl_coef.fill_(1.0))
+    run_native_mbnorm, run_native_permnative = native_path(ppo_m, seeded()), native_path(ppo_p, None)
+
+    run_dist = lambda: ppo_x.dist(dict(b))  # noqa: E731
+    draw_torch = lambda: torch.stack([torch.randperm(n, device=dev, generator=g_p) for _ in range(epochs)])  # noqa: E731
+    draw_native = lambda: ppo_p.draw_perm(n, epochs)  # noqa: E731
+
+    if dp:  # one rank of a data-parallel job: the Python loop, a gather that is a no-op, and the apply launch in place of the reduction
+        from ship_sim_gym_amd.dp import DataParallelPPO
+        ppo_d = DataParallelPPO(pol, env)
+        run_native_dp = native_path(ppo_d, seeded())
 
         def apply_alone(W):
             rows = torch.randn((W, ppo_d.n_params + 8), device=dev) * 1e-3

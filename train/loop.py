@@ -1,0 +1,85 @@
+"""What train/ppo_torch.py and train/pbt_native.py do alike, once: a run's "config" section, opening the checkpoint it resumes from, the
+value checks of both command lines, and binding the filters, the time-out bootstrap and the evaluator to the envs.  Host only: importing
+it imports no torch.  What merely looks alike — the loop-state records, the save-best rules — differs in substance and stays apart."""
+
+
+def run_config(train_fn, exempt, kwargs):
+    """The "config" section of a run of train_fn(**kwargs): its effective arguments (defaults filled in) without `exempt`, as plain data."""
+    import inspect
+    from ship_sim_gym_amd.checkpoint import plain_config
+    args = {k: p.default for k, p in inspect.signature(train_fn).parameters.items()}
+    unknown = sorted(set(kwargs) - set(args))
+    if unknown:
+        raise TypeError("train() has no argument %s" % ", ".join(unknown))
+    args.update(kwargs)
+    return plain_config({k: v for k, v in args.items() if k not in exempt})
+
+
+def open_resume(path, config, require, who="train", exempt=()):
+    """Read the checkpoint a run resumes from and compare its configuration with this run's (host only, before any device work):
+    ValueError for a file without trainer state, for a missing section, and for arguments that differ — every key, with both values."""
+    from ship_sim_gym_amd import checkpoint
+    ckpt = checkpoint.load(path)
+    if "trainer" not in ckpt:
+        raise ValueError("%s: %s holds no trainer section: it was saved by a run whose update is not the device's (--mode native --update "
+                         "native), so it can be evaluated but not resumed" % (who, path))
+    checkpoint.validate(ckpt, require, str(path))
+    diff = checkpoint.config_differences(ckpt["config"], config)
+    if diff:
+        raise ValueError("%s: cannot resume from %s: the arguments differ from the file's config in %s (only %s may change)" % (
+            who, path, "; ".join("%s (the file has %r, this run %r)" % (k, ckpt["config"].get(k, "nothing"), config.get(k, "nothing")) for k in diff),
+            ", ".join(exempt)))
+    return ckpt
+
+
+def resume_sections(base, obs_filter, norm_reward):
+    """The sections a resumed run needs: the script's own and one per filter that is on."""
+    return tuple(base) + (("obs_filter",) if obs_filter else ()) + (("ret_filter",) if norm_reward else ())
+
+
+def check_flag_values(a, error):
+    """The value checks both command lines share (a: the parsed arguments; error: the parser's, which exits)."""
+    if a.eval_every < 0 or a.eval_episodes < 1:
+        error("--eval-every must be >= 0 and --eval-episodes >= 1")
+    if a.reward_clip != 10.0 and not a.norm_reward:
+        error("--reward-clip needs --norm-reward")
+    if not a.reward_clip >= 0.0:
+        error("--reward-clip must be >= 0")
+    if a.save_every < 0:
+        error("--save-every must be >= 0")
+    if a.save_every and not a.save:
+        error("--save-every needs --save (the file it rewrites)")
+
+
+def bind_env(env, horizon, n_members=1, obs_filter=False, norm_reward=False, gamma=0.99, reward_clip=10.0, timeout_bootstrap=False,
+             eval_env=None):
+    """Bind what the configuration asks for to a training env of n_members members; returns (obs filter, return filter, evaluator), None
+    where off.  The obs filter is bound to the env (the rollout merges each step's rows, then normalises) and, frozen, to eval_env; the
+    bootstrap makes the rollout return "boot", which gae() reads; the return filter is applied per rollout, between the rollout and GAE."""
+    flt = rflt = evaluator = None
+    if obs_filter:
+        from ship_sim_gym_amd.obs_filter import ObsFilter
+        flt = ObsFilter(env, n_members=n_members)
+        env.set_obs_filter(flt)
+    if timeout_bootstrap:
+        env.set_timeout_bootstrap(True, rows=horizon)
+    if norm_reward:
+        from ship_sim_gym_amd.ret_filter import ReturnFilter
+        rflt = ReturnFilter(env, n_members=n_members, gamma=gamma, clip=reward_clip)
+    if eval_env is not None:  # an env of its own: evaluation resets and steps it, the training envs keep their episodes
+        from ship_sim_gym_amd.evaluate import NativeEvaluator
+        evaluator = NativeEvaluator(eval_env)
+        if flt is not None:
+            eval_env.set_obs_filter(flt.frozen(eval_env))  # the training statistics, never updated by an evaluation
+    return flt, rflt, evaluator
+
+
+def filter_sections(flt, rflt):
+    """The checkpoint sections of the filters that are on."""
+    return {k: f.state_dict() for k, f in (("obs_filter", flt), ("ret_filter", rflt)) if f is not None}
+
+
+def load_filters(ckpt, flt, rflt):
+    for k, f in (("obs_filter", flt), ("ret_filter", rflt)):
+        if f is not None:
+            f.load_state_dict(ckpt[k])

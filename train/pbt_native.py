@@ -75,6 +75,7 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from train import loop  # noqa: E402  (host only: no torch)
 
 INITIAL = {"lambda": 0.95, "clip_param": 0.2, "lr": 5e-4}  # train/rllib/pbt.py:60-62
 INITIAL_SCHEDULE = {"num_sgd_iter": [10, 20, 30], "sgd_minibatch_size": [128, 512, 2048]}  # train/rllib/pbt.py:65-68
@@ -106,16 +107,8 @@ RESUME_SECTIONS = ("population", "trainer", "env", "scheduler", "loop", "config"
 
 
 def run_config(**kwargs):
-    """The "config" section of a run of train(**kwargs): its effective arguments (defaults filled in) without CONFIG_EXEMPT, as
-    plain data."""
-    import inspect
-    from ship_sim_gym_amd.checkpoint import plain_config
-    args = {k: p.default for k, p in inspect.signature(train).parameters.items()}
-    unknown = sorted(set(kwargs) - set(args))
-    if unknown:
-        raise TypeError("train() has no argument %s" % ", ".join(unknown))
-    args.update(kwargs)
-    return plain_config({k: v for k, v in args.items() if k not in CONFIG_EXEMPT})
+    """The "config" section of a run of train(**kwargs): its effective arguments without CONFIG_EXEMPT, as plain data."""
+    return loop.run_config(train, CONFIG_EXEMPT, kwargs)
 
 
 def plain_events(events):
@@ -235,17 +228,239 @@ def parse_args(argv=None):
         ap.error("--members, --envs-per-member, --updates, --horizon and --perturb-every must be >= 1")
     if a.kl_coeff < 0 or a.kl_target < 0 or a.vf_clip < 0 or a.max_grad_norm < 0:
         ap.error("--kl-coeff, --kl-target, --vf-clip and --max-grad-norm must be >= 0")
-    if a.eval_every < 0 or a.eval_episodes < 1:
-        ap.error("--eval-every must be >= 0 and --eval-episodes >= 1")
-    if a.reward_clip != 10.0 and not a.norm_reward:
-        ap.error("--reward-clip needs --norm-reward")
-    if not a.reward_clip >= 0.0:
-        ap.error("--reward-clip must be >= 0")
-    if a.save_every < 0:
-        ap.error("--save-every must be >= 0")
-    if a.save_every and not a.save:
-        ap.error("--save-every needs --save (the file it rewrites)")
+    loop.check_flag_values(a, ap.error)
     return a
+
+
+class LoopState(object):
+    """What the loop carries from one update to the next — with the generator's state, the checkpoint's "loop" section: the last update
+    done, the scores and their history, the episode window they come from (a device tensor: episodes since the last perturbation), the
+    exploit and re-slice logs, the schedule as used (iters, sizes, counts when it is swept; empty when it is common), the layout (batch
+    sizes and slices; empty when equal), the best score, its update and member, the episodes ended per update.  member_samples is not saved."""
+    KINDS = tuple((k, int) for k in ("update", "best_update", "best_member")) + (("best", float),) + tuple((k, list) for k in (
+        "history", "scores", "exploits", "reslices", "iters", "sizes", "counts", "batch_sizes", "slices", "episodes_ended"))
+
+    def __init__(self, members, window, samples):
+        self.update, self.history, self.scores, self.window, self.member_samples = 0, [], [float("-inf")] * members, window, [samples] * members
+        self.exploits, self.reslices, self.iters, self.sizes, self.counts, self.batch_sizes, self.slices = [], [], [], [], [], [], []
+        self.best, self.best_update, self.best_member, self.episodes_ended = float("-inf"), 0, -1, []
+
+    def state_dict(self, gen):
+        return {"update": int(self.update), "gen_state": gen.get_state().cpu().clone(), "history": [list(r) for r in self.history],
+                "scores": list(self.scores), "window": self.window.detach().cpu().clone(), "exploits": plain_events(self.exploits),
+                "reslices": [[int(r[0]), list(r[1])] for r in self.reslices], "iters": list(self.iters), "sizes": list(self.sizes),
+                "counts": list(self.counts), "batch_sizes": list(self.batch_sizes), "slices": list(self.slices), "best": float(self.best),
+                "best_update": int(self.best_update), "best_member": int(self.best_member), "episodes_ended": list(self.episodes_ended)}
+
+    def load_state_dict(self, sd, gen):
+        import torch
+        from ship_sim_gym_amd.checkpoint import check_values
+        check_values("train: the checkpoint's loop section", sd, self.KINDS + (("gen_state", torch.Tensor), ("window", torch.Tensor)))
+        gen.set_state(sd["gen_state"])
+        self.window.copy_(sd["window"])
+        for k, _ in self.KINDS:  # (plain data of the kinds just checked, as state_dict wrote it)
+            setattr(self, k, sd[k])
+        self.exploits, self.reslices = events_from_plain(sd["exploits"]), [(r[0], r[1]) for r in sd["reslices"]]
+
+
+def plan(run):
+    """The host side of a run (run: train()'s arguments), before the first env is built: refuse what does not fit, then add what follows
+    from the arguments: P members on n_total envs, sliced or n each, the schedule per member or common, the permutation rows drawn."""
+    if run.save_every < 0 or (run.save_every and not run.save):
+        raise ValueError("train: save_every must be >= 0 and needs save (the file it rewrites)")
+    if run.perm not in ("torch", "native"):
+        raise ValueError("train: perm must be 'torch' or 'native' (got %r)" % (run.perm,))
+    P = run.P = int(run.members)
+    run.n_total = int(run.envs) if run.envs is not None else P * int(run.envs_per_member)
+    run.sliced = bool(run.mutate_batch) or run.batch_shares is not None
+    if run.mutate_batch and run.batch_shares is not None:
+        raise ValueError("train: mutate_batch and batch_shares exclude each other")
+    if not run.sliced and run.n_total % P:
+        raise ValueError("train: %d envs do not split into %d equal member slices" % (run.n_total, P))
+    for name, what in (("lrs", "learning rates"), ("batch_shares", "batch shares")):
+        if getattr(run, name) is not None and len(getattr(run, name)) != P:
+            raise ValueError("train: %d %s for %d members" % (len(getattr(run, name)), what, P))
+    run.n, run.native_perm = max(1, run.n_total // P), run.perm == "native"
+    run.quantum = default_quantum(run.n_total, P) if run.quantum is None else int(run.quantum)
+    # the schedule: common ints (one launch shape for everyone) or one entry per member
+    swept = [isinstance(x, (list, tuple)) for x in (run.epochs, run.minibatches)]
+    run.per_member = run.sliced or bool(run.mutate_schedule) or any(swept)
+    if run.per_member and not run.mutate_schedule:
+        run.iters0 = [int(e) for e in run.epochs] if swept[0] else [int(run.epochs)] * P
+        run.counts0 = [int(b) for b in run.minibatches] if swept[1] else [int(run.minibatches)] * P
+        if len(run.iters0) != P or len(run.counts0) != P:
+            raise ValueError("train: %d epochs and %d minibatches for %d members" % (len(run.iters0), len(run.counts0), P))
+    run.perm_epochs = run.max_epochs if run.mutate_schedule else (max(run.iters0) if run.per_member else run.epochs)
+
+
+def bind_layout(run, state, log, u=None, batch_sizes=None):
+    """From batch sizes to bound slices: the members' values become env slices, logged under update u (0: the initial layout), the env
+    is bound to them and member_samples follows.  Without batch_sizes the record's own layout is bound: a resumed run's, as it was
+    saved, whose log is the file's.  Env state and the episode carries stay as they are."""
+    from ship_sim_gym_amd.population import slices_for_batch_sizes
+    if batch_sizes is not None:
+        state.batch_sizes = list(batch_sizes)
+        state.slices = slices_for_batch_sizes(state.batch_sizes, run.n_total, run.quantum)
+        state.reslices.append((u, list(state.slices)))
+        log("slices: train_batch_size %s -> envs %s (quantum %d)" % (state.batch_sizes, state.slices, run.quantum) if u == 0 else
+            "update %d  re-slice: train_batch_size %s -> envs %s" % (u, state.batch_sizes, state.slices))
+    run.env.set_population_slices(state.slices)
+    state.member_samples = [run.horizon * s for s in state.slices]
+
+
+def set_schedule(state, max_epochs, raw=None, iters=None, counts=None):
+    """The schedule as it is used, from the members' own samples: a mutated one (raw: (num_sgd_iter, sgd_minibatch_size) per member)
+    clamped, or a swept one (iters, counts) with the minibatch sizes its counts make."""
+    from ship_sim_gym_amd.ppo import chunk_split
+    if raw is not None:
+        used = [clamp_schedule(i, s, state.member_samples[m], max_epochs) for m, (i, s) in enumerate(raw)]
+        state.iters, state.sizes = [c[0] for c in used], [c[1] for c in used]
+    else:
+        state.iters, state.counts = list(iters), list(counts)
+        state.sizes = [chunk_split(state.member_samples[m], c)[0] for m, c in enumerate(state.counts)]
+
+
+def build(run, log):
+    """The run's objects, in the order that decides the bits: the global seed, the device generator (seed + 1), the envs, the nets in
+    member order, the scheduler, whose generator draws the schedules before the batch sizes, the layout, the trainer, what the
+    configuration binds, the reset.  Returns the loop-state record."""
+    import torch
+    from ship_gym.config import EnvConfig, GameConfig
+    from ship_sim_gym_amd.population import NativePopulation, PBTScheduler, PopulationPPO, reference_mutations
+    from ship_sim_gym_amd.vec_env import ShipVecEnv
+    from train.ppo_torch import ActorCritic
+    from train.rllib_ppo import game_configuration
+    P, env_kw = run.P, dict(run.env_kw or {})
+    torch.manual_seed(run.seed)
+    run.dev = torch.device(run.device)
+    run.gen = torch.Generator(device=run.dev)
+    run.gen.manual_seed(run.seed + 1)
+    saved = {k: getattr(GameConfig, k) for k in ("FPS", "SPEED", "DEBUG", "BOUNDS")}
+    try:  # (game_configuration writes the GameConfig class, as the reference's does; the env reads it once, here)
+        run.env = ShipVecEnv(run.n_total, game_configuration(speed=30, fps=1000, debug=False), EnvConfig, device=run.device, n_maps=64, **env_kw)
+        # the held-out run's env (train/rllib/rollout.py:8-26): evaluation resets and steps it, the training envs keep their episodes
+        run.eval_env = ShipVecEnv(P * min(run.n, 256), GameConfig, EnvConfig, device=run.device, n_maps=64, **env_kw) if run.eval_every else None
+    finally:
+        for k, v in saved.items():
+            setattr(GameConfig, k, v)
+    D, A = run.env.states_history, run.env.action_space.n
+    run.nets = [ActorCritic(D, A, hidden=run.hidden, separate_value=run.separate_value).to(run.dev) for _ in range(P)]
+    run.pop = NativePopulation.from_actor_critics(run.nets, torch.full((D,), float(max(run.env.bounds)), dtype=torch.float64, device=run.dev))
+    mutations = reference_mutations(schedule=run.mutate_schedule, batch=run.mutate_batch) if run.mutate_schedule or run.mutate_batch else None
+    run.sched = PBTScheduler(P, seed=run.seed, perturbation_interval=run.perturb_every, mutations=mutations)
+    state = LoopState(P, torch.zeros((P, 3), dtype=torch.int64, device=run.dev), run.horizon * run.n)
+    if run.mutate_schedule:  # (drawn first: a seed's schedule does not depend on whether the batch is mutated too)
+        raw = [(run.sched.rng.choice(INITIAL_SCHEDULE["num_sgd_iter"]), run.sched.rng.choice(INITIAL_SCHEDULE["sgd_minibatch_size"])) for _ in range(P)]
+    if run.sliced:
+        bind_layout(run, state, log, 0, initial_batch_sizes(run.sched, P) if run.mutate_batch else run.batch_shares)
+    if run.mutate_schedule:
+        set_schedule(state, run.max_epochs, raw=raw)
+        log("schedule: num_sgd_iter %s  sgd_minibatch_size %s" % (state.iters, state.sizes))
+    elif run.per_member:
+        set_schedule(state, run.max_epochs, iters=run.iters0, counts=run.counts0)
+    run.ppo = PopulationPPO(run.pop, run.env, lam=INITIAL["lambda"], clip=INITIAL["clip_param"], lr=list(run.lrs) if run.lrs is not None else INITIAL["lr"],
+                            vf_clip=run.vf_clip, max_grad_norm=run.max_grad_norm, kl_coef=run.kl_coeff, kl_target=run.kl_target if run.kl_coeff > 0 else 0.0,
+                            adv_norm=run.adv_norm, perm_seed=run.seed if run.native_perm else None)
+    # per-member statistics: a member's rows are its slice, whatever the slices currently are
+    run.flt, run.rflt, run.evaluator = loop.bind_env(run.env, run.horizon, P, run.obs_filter, run.norm_reward, run.ppo.gamma, run.reward_clip,
+                                                     run.timeout_bootstrap, run.eval_env)
+    if run.rflt is not None:
+        run.ppo.set_return_filter(run.rflt)  # (an exploit copies the source's state rows with its weights)
+    run.env.reset_tensor()
+    if run.save or run.save_best:
+        run.env.check_snapshot_supported("snapshot")  # (refuse now, not after the training, a handle that cannot be saved)
+    return state
+
+
+def load_run(run, state, ckpt, log):
+    """Everything is built and bound as the configuration says; now the saved layout, then the saved states."""
+    state.load_state_dict(ckpt["loop"], run.gen)
+    if run.sliced:
+        bind_layout(run, state, log)
+    run.pop.load_state_dict(ckpt["population"])
+    run.ppo.load_state_dict(ckpt["trainer"])
+    loop.load_filters(ckpt, run.flt, run.rflt)
+    run.sched.load_state_dict(ckpt["scheduler"])
+    run.env.restore(ckpt["env"])
+
+
+def write_checkpoint(path, run, state):
+    """The checkpoint after update state.update (and after its perturbation, when one was due): everything a resumed run needs."""
+    from ship_sim_gym_amd import checkpoint
+    checkpoint.save(path, dict(loop.filter_sections(run.flt, run.rflt), config=run.config, population=run.pop.state_dict(),
+                               trainer=run.ppo.state_dict(), env=run.env.snapshot(), scheduler=run.sched.state_dict(), loop=state.state_dict(run.gen)))
+
+
+def draw_permutations(run, state):
+    """One update's permutations from the generator: None with perm "native" (update() draws its own, keyed by its count); sliced, member
+    m's own rows [perm_epochs, horizon * n_m] in member order; else one draw [P, perm_epochs, samples].  Always perm_epochs rows."""
+    import torch
+    if run.native_perm:
+        return None
+    if run.sliced:
+        return [torch.rand((run.perm_epochs, s), generator=run.gen, device=run.dev).argsort(dim=-1) for s in state.member_samples]
+    return torch.rand((run.P, run.perm_epochs, state.member_samples[0]), generator=run.gen, device=run.dev).argsort(dim=-1)
+
+
+def update_population(run, state, batch, perm):
+    """The population's PPO update on one rollout: the common schedule, or every member's own, on max(iters) of the drawn rows."""
+    if not run.per_member:
+        return run.ppo.update(batch, perm, run.epochs, run.minibatches)
+    mbs = [run.ppo.minibatches_for_size(s, state.member_samples[m]) for m, s in enumerate(state.sizes)] if run.mutate_schedule else state.counts
+    if perm is not None:
+        perm = [q[:max(state.iters)].contiguous() for q in perm] if run.sliced else perm[:, :max(state.iters)].contiguous()
+    run.ppo.update(batch, perm, state.iters, mbs)
+
+
+def account(state, u, ep, log):
+    """After update u: every member's episode_reward_mean over its window (none ended: it keeps its score), the history row, and how
+    many episodes ended during the update, which is returned."""
+    w, P = state.window.cpu().tolist(), len(state.scores)
+    state.update, state.scores = u, [w[m][0] / 100.0 / w[m][2] if w[m][2] else state.scores[m] for m in range(P)]
+    state.history.append(list(state.scores))
+    log("update %d  episode_reward_mean %s" % (u, " ".join("%d:%.3f" % (m, s) for m, s in enumerate(state.scores))))
+    state.episodes_ended.append(int(ep[:, 2].sum().item()))
+    return state.episodes_ended[-1]
+
+
+def evaluate(run, u, episodes, log):
+    """One greedy evaluation of every member (printed only: PBT ranks by training episodes, as the reference does)."""
+    from ship_sim_gym_amd.evaluate import format_table
+    r = run.evaluator.evaluate(run.pop, episodes, greedy=True)
+    log("update %d  greedy evaluation (%d envs x %d episodes per member)\n%s" % (u, run.eval_env.num_envs // run.P, episodes, format_table(r)))
+    return (u, r["per_member"].cpu().tolist())
+
+
+def perturb(run, state, u, log):
+    """One perturbation, on the loop-state record: the members' hyper-parameters -> sched.perturb -> the exploit -> the new values taken
+    over -> the handle re-sliced -> the schedule re-made from the members' own samples -> the events logged -> the window reset."""
+    ppo = run.ppo
+    hp = {"lambda": ppo.lam, "clip_param": ppo.clip, "lr": ppo.lr}
+    if run.sliced:  # (fixed shares are the member's configuration: they travel with an exploit, unmutated)
+        hp["train_batch_size" if run.mutate_batch else "batch_share"] = state.batch_sizes
+    if run.per_member:  # (a swept schedule is not mutated either, and travels with an exploit too)
+        hp.update({"num_sgd_iter": state.iters, "sgd_minibatch_size": state.sizes} if run.mutate_schedule else
+                  {"num_sgd_iter": state.iters, "minibatches": state.counts})
+    src, new, events = run.sched.perturb(state.scores, hp)
+    ppo.exploit(src)
+    ppo.lam, ppo.clip, ppo.lr = new["lambda"], new["clip_param"], new["lr"]
+    if run.sliced:
+        bind_layout(run, state, log, u, new["train_batch_size" if run.mutate_batch else "batch_share"])
+    if run.mutate_schedule:  # (the minibatch-size clamp uses the member's own samples)
+        set_schedule(state, run.max_epochs, raw=list(zip(new["num_sgd_iter"], new["sgd_minibatch_size"])))
+    elif run.per_member:
+        set_schedule(state, run.max_epochs, iters=new["num_sgd_iter"], counts=new["minibatches"])
+    for ev in events:
+        m = ev["member"]
+        log("update %d  exploit: member %d <- member %d" % (u, m, ev["source"]))
+        for key, kind, old, val in ev["mutations"]:
+            log("update %d  mutation: member %d %s %s %.6g -> %.6g" % (u, m, key, kind, old, val))
+        if run.per_member:
+            ev["schedule"] = {"num_sgd_iter": state.iters[m], "sgd_minibatch_size": state.sizes[m]}
+            log("update %d  schedule: member %d num_sgd_iter %d sgd_minibatch_size %d (as used)" % (u, m, state.iters[m], state.sizes[m]))
+        state.scores[m] = state.scores[ev["source"]]
+    state.exploits += events
+    state.window.zero_()
 
 
 def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every=5, seed=0, epochs=2, minibatches=4, lrs=None,
@@ -254,275 +469,71 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
           batch_shares=None, quantum=None, obs_filter=False, norm_reward=False, reward_clip=10.0, adv_norm="batch", perm="torch",
           timeout_bootstrap=False, hidden=64, env_kw=None, save=None, save_every=0, save_best=None, resume=None):
     config = run_config(**dict(locals()))  # (first statement: the arguments, nothing else)
+    run = argparse.Namespace(**locals())  # the run record: the arguments and the config; plan() and build() add to it
     import torch
-    from ship_gym.config import EnvConfig, GameConfig
-    from ship_sim_gym_amd import checkpoint
-    from ship_sim_gym_amd.population import NativePopulation, PBTScheduler, PopulationPPO, reference_mutations, slices_for_batch_sizes
     from ship_sim_gym_amd.ppo import chunk_split
-    from ship_sim_gym_amd.vec_env import ShipVecEnv
-    from train.ppo_torch import ActorCritic, open_resume
-    from train.rllib_ppo import game_configuration
-
-    if save_every < 0 or (save_every and not save):
-        raise ValueError("train: save_every must be >= 0 and needs save (the file it rewrites)")
-    ckpt = None
-    if resume:  # (read and compared before any device work: a wrong command line costs nothing)
-        ckpt = open_resume(resume, config, RESUME_SECTIONS + (("obs_filter",) if obs_filter else ()) + (("ret_filter",) if norm_reward else ()),
-                           exempt=CONFIG_EXEMPT)
-    env_kw = dict(env_kw or {})
-
-    if perm not in ("torch", "native"):
-        raise ValueError("train: perm must be 'torch' or 'native' (got %r)" % (perm,))
-    native_perm = perm == "native"
-    P, n = int(members), int(envs_per_member)
-    n_total = int(envs) if envs is not None else P * n
-    sliced = bool(mutate_batch) or batch_shares is not None
-    if mutate_batch and batch_shares is not None:
-        raise ValueError("train: mutate_batch and batch_shares exclude each other")
-    if not sliced and n_total % P:
-        raise ValueError("train: %d envs do not split into %d equal member slices" % (n_total, P))
-    n = max(1, n_total // P)
-    if lrs is not None and len(lrs) != P:
-        raise ValueError("train: %d learning rates for %d members" % (len(lrs), P))
-    if batch_shares is not None and len(batch_shares) != P:
-        raise ValueError("train: %d batch shares for %d members" % (len(batch_shares), P))
-    quantum = default_quantum(n_total, P) if quantum is None else int(quantum)
-    torch.manual_seed(seed)
-    dev = torch.device(device)
-    gen = torch.Generator(device=dev)
-    gen.manual_seed(seed + 1)
-    saved = {k: getattr(GameConfig, k) for k in ("FPS", "SPEED", "DEBUG", "BOUNDS")}
-    try:  # (game_configuration writes the GameConfig class, as the reference's does; the env reads it once, here)
-        env = ShipVecEnv(n_total, game_configuration(speed=30, fps=1000, debug=False), EnvConfig, device=device, n_maps=64, **env_kw)
-        # the held-out run's env (train/rllib/rollout.py:8-26): evaluation resets and steps it, the training envs keep their episodes
-        eval_env = ShipVecEnv(P * min(n, 256), GameConfig, EnvConfig, device=device, n_maps=64, **env_kw) if eval_every else None
-    finally:
-        for k, v in saved.items():
-            setattr(GameConfig, k, v)
-    D, A = env.states_history, env.action_space.n
-    nets = [ActorCritic(D, A, hidden=hidden, separate_value=separate_value).to(dev) for _ in range(P)]
-    scale = torch.full((D,), float(max(env.bounds)), dtype=torch.float64, device=dev)
-    pop = NativePopulation.from_actor_critics(nets, scale)
-    sched = PBTScheduler(P, seed=seed, perturbation_interval=perturb_every,
-                         mutations=reference_mutations(schedule=mutate_schedule, batch=mutate_batch) if mutate_schedule or mutate_batch else None)
-    samples = horizon * n
-    member_samples = [samples] * P  # a member's own samples per update (unequal once the handle is sliced)
-    reslices = []
-    raw = None
-    if mutate_schedule:  # (drawn first: a seed's schedule does not depend on whether the batch is mutated too)
-        raw = [(sched.rng.choice(INITIAL_SCHEDULE["num_sgd_iter"]), sched.rng.choice(INITIAL_SCHEDULE["sgd_minibatch_size"])) for _ in range(P)]
-    batch_sizes = None
-    if sliced:
-        batch_sizes = initial_batch_sizes(sched, P) if mutate_batch else list(batch_shares)
-        slices = slices_for_batch_sizes(batch_sizes, n_total, quantum)
-        env.set_population_slices(slices)
-        member_samples = [horizon * s for s in slices]
-        reslices.append((0, list(slices)))
-        log("slices: train_batch_size %s -> envs %s (quantum %d)" % (batch_sizes, slices, quantum))
-    ppo = PopulationPPO(pop, env, lam=INITIAL["lambda"], clip=INITIAL["clip_param"], lr=list(lrs) if lrs is not None else INITIAL["lr"],
-                        vf_clip=vf_clip, max_grad_norm=max_grad_norm, kl_coef=kl_coeff, kl_target=kl_target if kl_coeff > 0 else 0.0, adv_norm=adv_norm,
-                        perm_seed=seed if native_perm else None)
-    flt = None
-    if obs_filter:  # per-member statistics; a member's rows are its slice, whatever the slices currently are
-        from ship_sim_gym_amd.obs_filter import ObsFilter
-        flt = ObsFilter(env, n_members=P)
-        env.set_obs_filter(flt)
-        if eval_env is not None:
-            eval_env.set_obs_filter(flt.frozen(eval_env))
-    rflt = None
-    if norm_reward:  # per-member statistics of the discounted returns; applied between the rollout and GAE, nothing is bound to the env
-        from ship_sim_gym_amd.ret_filter import ReturnFilter
-        rflt = ReturnFilter(env, n_members=P, gamma=ppo.gamma, clip=reward_clip)
-        ppo.set_return_filter(rflt)  # (an exploit copies the source's state rows with its weights)
-    if timeout_bootstrap:  # (the rollout then also returns "boot", which gae() reads: a time-out is no longer scored as a return of 0)
-        env.set_timeout_bootstrap(True, rows=horizon)
-    env.reset_tensor()
-    window = torch.zeros((P, 3), dtype=torch.int64, device=dev)  # episodes since the last perturbation
-    scores = [float("-inf")] * P
-    out, history, exploits, evals = None, [], [], []
-    evaluator = None
-    if eval_env is not None:
-        from ship_sim_gym_amd.evaluate import NativeEvaluator, format_table
-        evaluator = NativeEvaluator(eval_env)
-    # the schedule: common ints (one launch shape for everyone, as before) or one entry per member
-    per_member = sliced or mutate_schedule or isinstance(epochs, (list, tuple)) or isinstance(minibatches, (list, tuple))
-    if mutate_schedule:
-        draws = [clamp_schedule(i, s, member_samples[m], max_epochs) for m, (i, s) in enumerate(raw)]
-        iters, sizes = [d[0] for d in draws], [d[1] for d in draws]
-        log("schedule: num_sgd_iter %s  sgd_minibatch_size %s" % (iters, sizes))
-    elif per_member:
-        iters = [int(e) for e in epochs] if isinstance(epochs, (list, tuple)) else [int(epochs)] * P
-        counts = [int(b) for b in minibatches] if isinstance(minibatches, (list, tuple)) else [int(minibatches)] * P
-        if len(iters) != P or len(counts) != P:
-            raise ValueError("train: %d epochs and %d minibatches for %d members" % (len(iters), len(counts), P))
-        sizes = [chunk_split(member_samples[m], c)[0] for m, c in enumerate(counts)]
-    perm_epochs = max_epochs if mutate_schedule else (max(iters) if per_member else epochs)
-    if save or save_best:
-        env.check_snapshot_supported("snapshot")  # (refuse now, not after the training, a handle that cannot be saved)
-    # --save-best: the best member's episode_reward_mean so far, the update and the member it belongs to; episodes ended per update
-    best, best_update, best_member, ended_log = float("-inf"), 0, -1, []
-    start = 1
-    if ckpt is not None:  # everything is built and bound as the configuration says; now the saved layout, then the saved state
-        loop = ckpt["loop"]
-        if sliced:  # (the layout the run had when it was saved, not the initial one)
-            batch_sizes, slices = list(loop["batch_sizes"]), [int(x) for x in loop["slices"]]
-            env.set_population_slices(slices)
-            member_samples = [horizon * x for x in slices]
-        if per_member:
-            iters, sizes = [int(x) for x in loop["iters"]], [int(x) for x in loop["sizes"]]
-            if not mutate_schedule:
-                counts = [int(x) for x in loop["counts"]]
-        pop.load_state_dict(ckpt["population"])
-        ppo.load_state_dict(ckpt["trainer"])
-        if flt is not None:
-            flt.load_state_dict(ckpt["obs_filter"])
-        if rflt is not None:
-            rflt.load_state_dict(ckpt["ret_filter"])
-        sched.load_state_dict(ckpt["scheduler"])
-        env.restore(ckpt["env"])
-        gen.set_state(loop["gen_state"])
-        window.copy_(loop["window"])
-        scores, history = [float(x) for x in loop["scores"]], [list(r) for r in loop["history"]]
-        exploits, reslices = events_from_plain(loop["exploits"]), [(int(r[0]), list(r[1])) for r in loop["reslices"]]
-        best, best_update, best_member = float(loop["best"]), int(loop["best_update"]), int(loop["best_member"])
-        ended_log = [int(x) for x in loop["episodes_ended"]]
-        start = int(loop["update"]) + 1
-        log("resumed from %s: %d updates done, continuing at update %d of %d" % (resume, start - 1, start, updates))
-
-    def write(path, u):
-        """The checkpoint after update u (and after its perturbation, when one was due): everything a resumed run needs."""
-        sections = {"config": config, "population": pop.state_dict(), "trainer": ppo.state_dict(), "env": env.snapshot(),
-                    "scheduler": sched.state_dict(),
-                    "loop": {"update": int(u), "gen_state": gen.get_state().cpu().clone(), "history": [list(r) for r in history],
-                             "scores": list(scores), "window": window.detach().cpu().clone(), "exploits": plain_events(exploits),
-                             "reslices": [[int(r[0]), list(r[1])] for r in reslices],
-                             "iters": list(iters) if per_member else [], "sizes": list(sizes) if per_member else [],
-                             "counts": list(counts) if per_member and not mutate_schedule else [],
-                             "batch_sizes": list(batch_sizes) if sliced else [], "slices": list(env.population_slices) if sliced else [],
-                             "best": float(best), "best_update": int(best_update), "best_member": int(best_member),
-                             "episodes_ended": list(ended_log)}}
-        if flt is not None:
-            sections["obs_filter"] = flt.state_dict()
-        if rflt is not None:
-            sections["ret_filter"] = rflt.state_dict()
-        checkpoint.save(path, sections)
-
-    for u in range(start, updates + 1):
-        uniforms = torch.rand((horizon, n_total), generator=gen, device=dev)
-        batch = env.rollout_population(pop, horizon, uniforms=uniforms, out=out)
+    # check (every refusal on the host, then the file a run resumes from, before any device work), build and bind, resume
+    plan(run)
+    ckpt = loop.open_resume(resume, config, loop.resume_sections(RESUME_SECTIONS, obs_filter, norm_reward), exempt=CONFIG_EXEMPT) if resume else None
+    state = build(run, log)
+    if ckpt is not None:
+        load_run(run, state, ckpt, log)
+        log("resumed from %s: %d updates done, continuing at update %d of %d" % (resume, state.update, state.update + 1, updates))
+    out, evals = None, []
+    for u in range(state.update + 1, updates + 1):
+        uniforms = torch.rand((horizon, run.n_total), generator=run.gen, device=run.dev)
+        batch = run.env.rollout_population(run.pop, horizon, uniforms=uniforms, out=out)
         out = {k: v for k, v in batch.items() if k not in ("adv", "ret", "logp_all", "rew_norm", "rew_denom")}
-        ep = ppo.episode_stats(batch)
-        window += ep
-        if rflt is not None:
-            rflt.set_gamma(ppo.gamma)  # (the members' own discounts, whatever they currently are)
-        ppo.gae(batch, return_filter=rflt)
-        if native_perm:  # update() draws what it needs itself: max(iters) rows per member, in the bound layout, keyed by its count
-            perm = None
-        elif sliced:  # member m's own rows: [perm_epochs, horizon * n_m], nothing padded to the widest member
-            perm = [torch.rand((perm_epochs, s), generator=gen, device=dev).argsort(dim=-1) for s in member_samples]
-        else:
-            perm = torch.rand((P, perm_epochs, samples), generator=gen, device=dev).argsort(dim=-1)
-        if per_member:
-            mbs = [ppo.minibatches_for_size(s, member_samples[m]) for m, s in enumerate(sizes)] if mutate_schedule else counts
-            if native_perm:
-                ppo.update(batch, None, iters, mbs)
-            elif sliced:
-                ppo.update(batch, [q[:max(iters)].contiguous() for q in perm], iters, mbs)
-            else:
-                ppo.update(batch, perm[:, :max(iters)].contiguous(), iters, mbs)
-        else:
-            ppo.update(batch, perm, epochs, minibatches)
-        w = window.cpu().tolist()
-        scores = [w[m][0] / 100.0 / w[m][2] if w[m][2] else scores[m] for m in range(P)]
-        history.append(list(scores))
-        log("update %d  episode_reward_mean %s" % (u, " ".join("%d:%.3f" % (m, s) for m, s in enumerate(scores))))
-        ended_log.append(int(ep[:, 2].sum().item()))
-        new_best = ended_log[-1] > 0 and max(scores) > best  # (an update in which no episode ended never is one)
+        ep = run.ppo.episode_stats(batch)
+        state.window += ep
+        if run.rflt is not None:
+            run.rflt.set_gamma(run.ppo.gamma)  # (the members' own discounts, whatever they currently are)
+        run.ppo.gae(batch, return_filter=run.rflt)
+        update_population(run, state, batch, draw_permutations(run, state))
+        ended = account(state, u, ep, log)
+        # save-best: the best member's episode_reward_mean so far (an update in which no episode ended never is one) ...
+        new_best = ended > 0 and max(state.scores) > state.best
         if new_best:
-            best, best_update, best_member = max(scores), u, scores.index(max(scores))
-        if evaluator is not None and u % eval_every == 0:  # (printed only: PBT ranks by training episodes, as the reference does)
-            r = evaluator.evaluate(pop, eval_episodes, greedy=True)
-            evals.append((u, r["per_member"].cpu().tolist()))
-            log("update %d  greedy evaluation (%d envs x %d episodes per member)\n%s" % (u, eval_env.num_envs // P, eval_episodes, format_table(r)))
-        if pbt and sched.due(u):
-            hp = {"lambda": ppo.lam, "clip_param": ppo.clip, "lr": ppo.lr}
-            if mutate_batch:
-                hp["train_batch_size"] = batch_sizes
-            elif sliced:  # (fixed shares are the member's configuration: they travel with an exploit, unmutated)
-                hp["batch_share"] = batch_sizes
-            if mutate_schedule:
-                hp.update({"num_sgd_iter": iters, "sgd_minibatch_size": sizes})
-            elif per_member:  # a swept schedule is not mutated, but it is its member's configuration: it travels with an exploit
-                hp.update({"num_sgd_iter": iters, "minibatches": counts})
-            src, new, events = sched.perturb(scores, hp)
-            ppo.exploit(src)
-            ppo.lam, ppo.clip, ppo.lr = new["lambda"], new["clip_param"], new["lr"]
-            if sliced:  # re-slice the handle from the members' current values; env state and the episode carries stay as they are
-                batch_sizes = new["train_batch_size"] if mutate_batch else new["batch_share"]
-                slices = slices_for_batch_sizes(batch_sizes, n_total, quantum)
-                env.set_population_slices(slices)
-                member_samples = [horizon * s for s in slices]
-                reslices.append((u, list(slices)))
-                log("update %d  re-slice: train_batch_size %s -> envs %s" % (u, batch_sizes, slices))
-            if mutate_schedule:  # (the minibatch-size clamp uses the member's own samples)
-                used = [clamp_schedule(i, s, member_samples[m], max_epochs)
-                        for m, (i, s) in enumerate(zip(new["num_sgd_iter"], new["sgd_minibatch_size"]))]
-                iters, sizes = [c[0] for c in used], [c[1] for c in used]
-            elif per_member:
-                iters, counts = new["num_sgd_iter"], new["minibatches"]
-                sizes = [chunk_split(member_samples[m], c)[0] for m, c in enumerate(counts)]
-            for ev in events:
-                log("update %d  exploit: member %d <- member %d" % (u, ev["member"], ev["source"]))
-                for key, kind, old, val in ev["mutations"]:
-                    log("update %d  mutation: member %d %s %s %.6g -> %.6g" % (u, ev["member"], key, kind, old, val))
-                if per_member:
-                    ev["schedule"] = {"num_sgd_iter": iters[ev["member"]], "sgd_minibatch_size": sizes[ev["member"]]}
-                    log("update %d  schedule: member %d num_sgd_iter %d sgd_minibatch_size %d (as used)"
-                        % (u, ev["member"], iters[ev["member"]], sizes[ev["member"]]))
-                scores[ev["member"]] = scores[ev["source"]]
-            exploits += events
-            window.zero_()
-        if new_best and save_best:  # (after the perturbation, so that the file resumes like any other; the best member ranks top: a source, not a destination)
-            write(save_best, u)
-            log("update %d  member %d's episode_reward_mean %.3f is the best so far: saved to %s" % (u, best_member, best, save_best))
+            state.best, state.best_update, state.best_member = max(state.scores), u, state.scores.index(max(state.scores))
+        if run.evaluator is not None and u % eval_every == 0:
+            evals.append(evaluate(run, u, eval_episodes, log))
+        if pbt and run.sched.due(u):
+            perturb(run, state, u, log)
+        if new_best and save_best:  # ... written after the perturbation, so that the file resumes like any other (the best member ranks top: a source, not a destination)
+            write_checkpoint(save_best, run, state)
+            log("update %d  member %d's episode_reward_mean %.3f is the best so far: saved to %s" % (u, state.best_member, state.best, save_best))
         if save and save_every and u % save_every == 0:
-            write(save, u)
-    torch.cuda.synchronize(dev)
+            write_checkpoint(save, run, state)
+    # finish
+    torch.cuda.synchronize(run.dev)
     if save:
-        write(save, max(updates, start - 1))
-        log("checkpoint after update %d saved to %s" % (max(updates, start - 1), save))
-    pop.load_into(nets)
-    details = {"params": pop.params.detach().clone(), "exploits": exploits, "nets": nets,
+        write_checkpoint(save, run, state)
+        log("checkpoint after update %d saved to %s" % (state.update, save))
+    run.pop.load_into(run.nets)
+    P, samples, ppo = run.P, horizon * run.n, run.ppo
+    details = {"params": run.pop.params.detach().clone(), "exploits": state.exploits, "nets": run.nets,
                "hparams": {"lambda": list(ppo.lam), "clip_param": list(ppo.clip), "lr": list(ppo.lr),
-                           "num_sgd_iter": list(iters) if per_member else [int(epochs)] * P,
-                           "sgd_minibatch_size": list(sizes) if per_member else [chunk_split(samples, minibatches)[0]] * P},
+                           "num_sgd_iter": list(state.iters) if run.per_member else [int(epochs)] * P,
+                           "sgd_minibatch_size": list(state.sizes) if run.per_member else [chunk_split(samples, minibatches)[0]] * P},
                "member_steps": list(ppo.member_steps), "kl_coef": ppo.kl_coef.detach().cpu().tolist(), "evaluations": evals,
-               "slices": list(env.population_slices) if sliced else [n] * P, "reslices": reslices,
-               "train_batch_size": list(batch_sizes) if sliced else [samples] * P,
-               "best": best, "best_update": best_update, "best_member": best_member, "episodes_ended": list(ended_log),
-               "env_state": env.state.detach().cpu().clone() if return_details else None}
-    if flt is not None:
-        details["obs_filter"] = flt.state_dict()
+               "slices": list(run.env.population_slices) if run.sliced else [run.n] * P, "reslices": state.reslices,
+               "train_batch_size": list(state.batch_sizes) if run.sliced else [samples] * P,
+               "best": state.best, "best_update": state.best_update, "best_member": state.best_member, "episodes_ended": list(state.episodes_ended),
+               "env_state": run.env.state.detach().cpu().clone() if return_details else None}
+    details.update(loop.filter_sections(run.flt, run.rflt))
+    if run.flt is not None:
         log("observation filter: rows merged per member %s" % [int(c) for c in details["obs_filter"]["state"][:, 3, 0].tolist()])
-    if rflt is not None:
-        details["ret_filter"] = rflt.state_dict()
+    if run.rflt is not None:
         log("return filter: returns merged per member %s  std %s" % ([int(c) for c in details["ret_filter"]["state"][:, 3].tolist()],
                                                                      ["%.5f" % d for d in details["ret_filter"]["state"][:, 2].tolist()]))
-    if eval_env is not None:
-        eval_env.close()
-    env.close()
-    return (history, details) if return_details else history
+    if run.eval_env is not None:
+        run.eval_env.close()
+    run.env.close()
+    return (state.history, details) if return_details else state.history
 
 
 def main(argv=None):
-    a = parse_args(argv)
-    train(members=a.members, envs_per_member=a.envs_per_member, updates=a.updates, horizon=a.horizon, perturb_every=a.perturb_every,
-          seed=a.seed, epochs=a.epochs, minibatches=a.minibatches, lrs=a.lrs, pbt=a.pbt, device=a.device, kl_coeff=a.kl_coeff,
-          kl_target=a.kl_target, vf_clip=a.vf_clip, max_grad_norm=a.max_grad_norm, separate_value=a.separate_value,
-          mutate_schedule=a.mutate_schedule, max_epochs=a.max_epochs, eval_every=a.eval_every, eval_episodes=a.eval_episodes, envs=a.envs,
-          mutate_batch=a.mutate_batch, batch_shares=a.batch_shares, quantum=a.quantum, obs_filter=a.obs_filter,
-          norm_reward=a.norm_reward, reward_clip=a.reward_clip, adv_norm=a.adv_norm, perm=a.perm, timeout_bootstrap=a.timeout_bootstrap,
-          hidden=a.hidden, save=a.save, save_every=a.save_every, save_best=a.save_best, resume=a.resume)
+    train(**vars(parse_args(argv)))  # (every flag is an argument of train() of the same name)
 
 
 if __name__ == "__main__":

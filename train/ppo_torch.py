@@ -87,6 +87,7 @@ from ship_gym.config import EnvConfig, GameConfig  # noqa: E402  (the reference'
 from ship_sim_gym_amd.vec_env import ShipVecEnv  # noqa: E402
 from ship_sim_gym_amd.policy import NativePolicy  # noqa: E402
 from ship_sim_gym_amd.ppo import NativePPO  # noqa: E402
+from train import loop  # noqa: E402
 
 
 class ActorCritic(nn.Module):
@@ -253,37 +254,245 @@ def rollout(shards, horizon, mode, gen, policy=None, job=None):
 CONFIG_EXEMPT = ("updates", "save", "save_every", "save_best", "save_obs_filter", "resume", "eval_every", "eval_episodes", "eval_envs", "log",
                  "return_details")
 RESUME_SECTIONS = ("policy", "trainer", "env", "loop", "config")
+open_resume = loop.open_resume  # (importable from here, as it was)
 
 
 def run_config(**kwargs):
-    """The "config" section of a run of train(**kwargs): its effective arguments (defaults filled in) without CONFIG_EXEMPT, as
-    plain data."""
-    import inspect
-    from ship_sim_gym_amd.checkpoint import plain_config
-    args = {k: p.default for k, p in inspect.signature(train).parameters.items()}
-    unknown = sorted(set(kwargs) - set(args))
-    if unknown:
-        raise TypeError("train() has no argument %s" % ", ".join(unknown))
-    args.update(kwargs)
-    return plain_config({k: v for k, v in args.items() if k not in CONFIG_EXEMPT})
+    """The "config" section of a run of train(**kwargs): its effective arguments without CONFIG_EXEMPT, as plain data."""
+    return loop.run_config(train, CONFIG_EXEMPT, kwargs)
 
 
-def open_resume(path, config, require=RESUME_SECTIONS, who="train", exempt=CONFIG_EXEMPT):
-    """Read the checkpoint a run resumes from and compare its configuration with this run's (host only, before any device work):
-    ValueError for a file that holds no trainer state, for a missing section, and for arguments that differ — every key, with both
-    values."""
+# What needs what, once, for parse_args (ap.error) and train() (ValueError).  NEEDS: a need's flag, its spelling in train(), when it is met.
+# A row of REQUIREMENTS: the name in train() ("ranks": the job's size), the flag, when it is on, its needs, refused with > 1 rank?, why.
+NEEDS = {"mode": ("--mode native", "mode='native'", lambda a: a.mode == "native"),
+         "update": ("--update native", "update='native'", lambda a: a.update == "native"),
+         "obs_filter": ("--obs-filter", "obs_filter=True", lambda a: bool(a.obs_filter)),
+         "save": ("--save", "save", lambda a: bool(a.save))}
+REQUIREMENTS = (  # (a row that needs more stands before the row of what it needs: the refusal then names the flag that asks for most)
+    ("save_obs_filter", "--save-obs-filter", lambda a: bool(a.save_obs_filter), ("mode", "obs_filter"), True, "it saves that filter's statistics"),
+    ("obs_filter", "--obs-filter", lambda a: bool(a.obs_filter), ("mode",), True, "the filter runs inside the native policy launch"),
+    ("norm_reward", "--norm-reward", lambda a: bool(a.norm_reward), ("mode", "update"), True, "it runs between the native rollout and the device's GAE"),
+    ("timeout_bootstrap", "--timeout-bootstrap", lambda a: bool(a.timeout_bootstrap), ("mode", "update"), False,
+     "the native rollout hands the terminal observation's value to the device's GAE; the torch update has no time-out bootstrap"),
+    ("eval_every", "--eval-every", lambda a: bool(a.eval_every), ("mode",), False, "the evaluation runs the native policy on the device"),
+    ("perm", "--perm native", lambda a: a.perm == "native", ("update",), False, "the library draws the permutations of the device update"),
+    ("resume", "--resume", lambda a: bool(a.resume), ("mode", "update"), True, "it restores the device trainer's state"),
+    ("save_every", "--save-every", lambda a: bool(a.save_every), ("save",), True, "the file it rewrites"),
+    ("adv_norm", "--adv-norm minibatch", lambda a: a.adv_norm == "minibatch", (), True, "a rank's minibatch statistics are not the job's"),
+    ("ranks", "more than one rank (--gpus / WORLD_SIZE)", lambda a: a.ranks > 1, ("mode", "update"), False, "the ranks train through the device update"),
+    ("update", "--update native", lambda a: a.update == "native", ("mode",), False, "the update runs on the native policy's packed parameters"),
+)
+
+
+def check_requirements(args, ranks, error=None):
+    """Walk REQUIREMENTS over the arguments `args` (a dict) of a run of `ranks` ranks.  The first row that is on and misses a need, or is
+    refused with more than one rank, goes to the parser's `error` with the flags in the text, or is a ValueError with train()'s names."""
+    a = argparse.Namespace(**dict(args, ranks=ranks))
+    for name, flag, on, needs, one_rank_only, why in REQUIREMENTS:
+        text = None
+        if on(a) and not all(NEEDS[k][2](a) for k in needs):
+            text = ("%s needs %s (%s)" % (flag, " ".join(NEEDS[k][0] for k in needs), why) if error else
+                    "%s: it needs %s (%s; got mode=%r, update=%r)" % (name, " and ".join(NEEDS[k][1] for k in needs), why, a.mode, a.update))
+        elif on(a) and one_rank_only and ranks > 1:
+            text = "%s is not supported with more than one rank (%d ranks): %s" % (flag if error else "%s (%s)" % (name, flag), ranks, why)
+        if text and error:
+            error(text)
+        if text:
+            raise ValueError(text)
+
+
+def check_train_arguments(a, ranks):
+    """Every host-side refusal of train(**vars(a)), before the first env is built: the values, then REQUIREMENTS."""
+    assert a.mode in ("eager", "graph", "pingpong", "native")
+    for name, allowed in (("perm", ("torch", "native")), ("adv_norm", ("batch", "minibatch")), ("update", ("torch", "native"))):
+        if getattr(a, name) not in allowed:
+            raise ValueError("%s must be %r or %r (got %r)" % ((name,) + allowed + (getattr(a, name),)))
+    if a.save_every < 0 or a.eval_every < 0 or a.eval_episodes < 1:
+        raise ValueError("save_every and eval_every must be >= 0 and eval_episodes >= 1")
+    check_requirements(vars(a), ranks)
+
+
+class LoopState(object):
+    """What the loop carries from one update to the next — with the generator's state, the checkpoint's "loop" section: the last update
+    done, the history rows, every update's score (the mean return of the episodes that ended during it, -inf when none did), the best
+    score and its update (the reference callback's best_model.pkl, train/stable_baselines/ppo.py:25-52) and the env counters so far."""
+    KINDS = (("update", int), ("gen_state", torch.Tensor), ("history", list), ("scores", list), ("best", float), ("best_update", int),
+             ("episodes", int), ("sum_return", float))
+
+    def __init__(self, episodes=0, sum_return=0.0):
+        self.update, self.history, self.scores, self.best, self.best_update, self.episodes, self.sum_return = -1, [], [], float("-inf"), -1, episodes, sum_return
+
+    def state_dict(self, gen):
+        return {"update": int(self.update), "gen_state": gen.get_state().cpu().clone(), "history": [list(r) for r in self.history],
+                "scores": list(self.scores), "best": float(self.best), "best_update": int(self.best_update),
+                "episodes": int(self.episodes), "sum_return": float(self.sum_return)}
+
+    def load_state_dict(self, sd, gen):
+        from ship_sim_gym_amd.checkpoint import check_values
+        check_values("train: the checkpoint's loop section", sd, self.KINDS)
+        gen.set_state(sd["gen_state"])
+        self.update, self.history, self.scores = sd["update"], [tuple(r) for r in sd["history"]], list(sd["scores"])
+        self.best, self.best_update, self.episodes, self.sum_return = sd["best"], sd["best_update"], sd["episodes"], sd["sum_return"]
+
+
+def build_run(run, rank, world):
+    """Add the run's objects to train()'s arguments, in the order that decides the bits: the global seed, the device generator (seed + 1),
+    the probe env, the module (it draws from the global generator), the shards — a rank's own of the job's `envs` —, policy and trainer."""
+    from ship_sim_gym_amd import sharding
+    env_range = sharding.shard_range(run.envs, rank, world) if world > 1 else None
+    torch.manual_seed(run.seed)
+    run.rank, run.world, run.dev = rank, world, torch.device(run.device)
+    run.gen = torch.Generator(device=run.dev)
+    run.gen.manual_seed(run.seed + 1)
+    probe = ShipVecEnv(1, GameConfig, EnvConfig, device=run.device, n_maps=1,  # (the observation width follows the beam count)
+                       **{k: v for k, v in dict(run.env_kw or {}).items() if k == "n_beams"})
+    D, A = probe.states_history, probe.action_space.n
+    probe.close()
+    run.net = ActorCritic(D, A, hidden=run.hidden, separate_value=run.separate_value).to(run.dev)
+    run.opt = torch.optim.Adam(run.net.parameters(), lr=run.lr)
+    run.shards = make_shards(run.envs, run.mode, run.net, run.device, run.horizon, env_kw=run.env_kw, env_range=env_range)
+    run.env = run.shards[0].env
+    if world > 1:
+        sharding.broadcast_bank(run.env, src=0)
+    for sh in run.shards:
+        sh.env.reset_tensor()
+    run.policy = NativePolicy.from_actor_critic(run.net, run.shards[0].scale) if run.mode == "native" else None
+    perm_seed, run.ppo = run.seed if run.perm == "native" else None, None
+    if world > 1:  # (refuses, on every rank alike, shards that would make different numbers of minibatches)
+        from ship_sim_gym_amd.dp import DataParallelPPO
+        run.ppo = DataParallelPPO(run.policy, run.env, plan=(run.horizon, run.minibatches), lr=run.lr, clip=run.clip, perm_seed=perm_seed)
+    elif run.update == "native":
+        run.ppo = NativePPO(run.policy, run.env, lr=run.lr, clip=run.clip, adv_norm=run.adv_norm, perm_seed=perm_seed)
+    run.job = None if world == 1 else (env_range[0], env_range[1], run.envs)
+    run.n_local = run.envs if world == 1 else env_range[1] - env_range[0]
+
+
+def capture_graphs(run):
+    """One eager warm-up step per shard OUTSIDE the capture (it prepares the library's kernels and hipBLASLt's workspaces), then the envs
+    start over; the capture itself runs nothing."""
+    for sh in run.shards:
+        sh.step()
+        sh.env.reset_tensor()
+        sh.t.zero_()
+    torch.cuda.synchronize()
+    for sh in run.shards:
+        sh.capture(torch.cuda.Stream(device=run.dev))
+    torch.cuda.synchronize()
+
+
+def episode_stats(run):
+    """The episode counters so far: this process's envs', or (every rank calls it: an all-reduce) the whole job's."""
+    if run.world > 1:
+        from ship_sim_gym_amd import sharding
+        return sharding.global_stats(run.env)
+    return {k: sum(sh.env.stats()[k] for sh in run.shards) for k in ("sum_return", "episodes", "goals_hit")}
+
+
+def load_run(run, state, ckpt):
+    """Everything is built and bound as the configuration says; now take the saved state over."""
+    run.policy.load_state_dict(ckpt["policy"])
+    run.ppo.load_state_dict(ckpt["trainer"])
+    loop.load_filters(ckpt, run.flt, run.rflt)
+    run.env.restore(ckpt["env"])
+    state.load_state_dict(ckpt["loop"], run.gen)
+
+
+def write_checkpoint(path, run, state):
+    """The checkpoint after update state.update: everything a resumed run needs with the device update, else the policy (for evaluation)."""
     from ship_sim_gym_amd import checkpoint
-    ckpt = checkpoint.load(path)
-    if "trainer" not in ckpt:
-        raise ValueError("%s: %s holds no trainer section: it was saved by a run whose update is not the device's (--mode native --update "
-                         "native), so it can be evaluated but not resumed" % (who, path))
-    checkpoint.validate(ckpt, require, str(path))
-    diff = checkpoint.config_differences(ckpt["config"], config)
-    if diff:
-        raise ValueError("%s: cannot resume from %s: the arguments differ from the file's config in %s (only %s may change)" % (
-            who, path, "; ".join("%s (the file has %r, this run %r)" % (k, ckpt["config"].get(k, "nothing"), config.get(k, "nothing")) for k in diff),
-            ", ".join(exempt)))
-    return ckpt
+    sections = dict(loop.filter_sections(run.flt, run.rflt), config=run.config, loop=state.state_dict(run.gen))
+    if run.ppo is not None:  # (a job's file is rank 0's: the policy and the trainer; per-rank env snapshots are out of scope)
+        sections.update(policy=run.policy.state_dict(), trainer=run.ppo.state_dict(), **({"env": run.env.snapshot()} if run.world == 1 else {}))
+    else:  # (the torch update trains the module: pack it as evaluation reads it)
+        sections["policy"] = (run.policy if run.policy is not None else NativePolicy.from_actor_critic(run.net, run.shards[0].scale)).state_dict()
+    checkpoint.save(path, sections)
+
+
+def native_update(run, u, log):
+    """GAE + the whole update on the device, on the rollout's own buffers; perm "native": the library shuffles (a row per epoch, keyed
+    by the seed and the update's number), else torch's generator does (the same randperm draws as the torch update)."""
+    nb = dict(run.shards[0].native_out)
+    run.ppo.gae(nb, run.gamma, run.lam, return_filter=run.rflt)
+    n = run.horizon * run.n_local  # (a rank shuffles its own samples)
+    rows = None if run.perm == "native" else torch.stack([torch.randperm(n, device=run.dev, generator=run.gen) for _ in range(run.epochs)])
+    st_upd = run.ppo.update(nb, rows, run.epochs, run.minibatches, stats=run.flt is not None or run.rflt is not None)
+    if st_upd is not None:
+        pg, vf, ent = (float(v) for v in st_upd[-1, :3])
+        notes = []
+        if run.flt is not None:
+            notes.append("(obs filter: %d rows merged)" % int(run.flt.count[0].item()))
+        if run.rflt is not None:
+            notes.append("(return filter: %d returns merged, std %.5f)" % (int(run.rflt.count[0].item()), float(run.rflt.denom[0].item())))
+        log("update %3d  last minibatch: policy loss %+.5f  value loss %.5f  entropy %.5f  %s" % (u, pg, vf, ent, "  ".join(notes)))
+
+
+def torch_update(net, opt, b, last_val, epochs, minibatches, gen, gamma=0.99, lam=0.95, clip=0.2, adv_norm="batch"):
+    """The eager update on a rollout b (obs [horizon, envs, D]; act int64, the rest float32 [horizon, envs]) and the values after its
+    last step, on whatever device they are: GAE, then epochs x minibatches of loss, backward, Adam.  One randperm from `gen` per epoch."""
+    horizon, envs, D = b["obs"].shape
+    dev = b["obs"].device
+    adv = torch.zeros(envs, device=dev)
+    advs, rets = [None] * horizon, [None] * horizon
+    nxt = last_val
+    for t in reversed(range(horizon)):           # GAE; a done env's next obs belongs to a fresh episode (auto-reset)
+        nonterm = 1.0 - b["done"][t]
+        delta = b["rew"][t] + gamma * nxt * nonterm - b["val"][t]
+        adv = delta + gamma * lam * nonterm * adv
+        advs[t], rets[t] = adv, adv + b["val"][t]
+        nxt = b["val"][t]
+    b_obs, b_act = b["obs"].reshape(horizon * envs, D), b["act"].reshape(-1)
+    b_logp, b_adv, b_ret = b["logp"].reshape(-1), torch.cat(advs), torch.cat(rets)
+    if adv_norm == "batch":
+        b_adv = (b_adv - b_adv.mean()) / (b_adv.std() + 1e-8)
+    n = b_obs.shape[0]
+    for _ in range(epochs):
+        perm = torch.randperm(n, device=dev, generator=gen)
+        for mb in perm.chunk(minibatches):
+            logits, val = net(b_obs[mb])
+            dist = torch.distributions.Categorical(logits=logits)
+            ratio = torch.exp(dist.log_prob(b_act[mb]) - b_logp[mb])
+            mb_adv = b_adv[mb]
+            if adv_norm == "minibatch":  # PPO2's rule, as the device update applies it: the minibatch's own mean / unbiased std
+                mb_std = mb_adv.std() if mb_adv.numel() > 1 else mb_adv.new_zeros(())  # (one sample: a std of 0, not NaN)
+                mb_adv = (mb_adv - mb_adv.mean()) / (mb_std + 1e-8)
+            pg = -torch.min(ratio * mb_adv, torch.clamp(ratio, 1 - clip, 1 + clip) * mb_adv).mean()
+            loss = pg + 0.5 * (val - b_ret[mb]).pow(2).mean() - 0.01 * dist.entropy().mean()
+            opt.zero_grad(); loss.backward(); opt.step()
+
+
+def eager_update(run, b, last_val):
+    """torch_update on the module, from the native rollout's last value or a forward on the envs' current observations; then re-pack."""
+    if last_val is None:
+        with torch.no_grad():
+            last_val = torch.cat([run.net(normalise(sh.env.obs, sh.scale))[1] for sh in run.shards])
+    torch_update(run.net, run.opt, b, last_val, run.epochs, run.minibatches, run.gen, run.gamma, run.lam, run.clip, run.adv_norm)
+    if run.policy is not None:
+        run.policy.refresh()
+
+
+def account(run, state, u, b, log):
+    """After update u: the history row and the update's score (-inf: no episode ended, never a best).  Returns how many ended."""
+    st = episode_stats(run)
+    mean_ret = st["sum_return"] / max(st["episodes"], 1)
+    goals_per_ep = st["goals_hit"] / max(st["episodes"], 1)
+    state.update = u
+    state.history.append((u, mean_ret, goals_per_ep, float(b["rew"].mean())))
+    log("update %3d  episodes %8d  mean return so far %+.3f  goals/episode %.3f  mean step reward %+.4f" % (
+        u, st["episodes"], mean_ret, goals_per_ep, state.history[-1][3]))
+    ended = st["episodes"] - state.episodes
+    state.scores.append((st["sum_return"] - state.sum_return) / ended if ended > 0 else float("-inf"))
+    state.episodes, state.sum_return = st["episodes"], st["sum_return"]
+    return ended
+
+
+def evaluate(run, u, episodes, log):
+    """One greedy evaluation on the evaluator's own env: the (update, results) entry of details["evaluations"]."""
+    r = run.evaluator.evaluate(run.policy, episodes, greedy=True)
+    log("update %3d  greedy evaluation (%d envs x %d episodes): mean return %+.3f  length %.1f  goals/episode %.3f  "
+        "collided %.2f  out of bounds %.2f  timed out %.2f" % (
+            u, run.evaluator.env.num_envs, episodes, r["return_mean"][0], r["length_mean"][0], r["goals_per_episode"][0],
+            r["collision_rate"][0], r["out_of_bounds_rate"][0], r["max_steps_rate"][0]))
+    return (u, {k: (v[0] if hasattr(v, "__len__") else v) for k, v in r.items() if k not in ("per_env", "per_member")})
 
 
 def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, gamma=0.99, lam=0.95, clip=0.2,
@@ -292,279 +501,87 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
           norm_reward=False, reward_clip=10.0, adv_norm="batch", perm="torch", timeout_bootstrap=False, hidden=64,
           save=None, save_every=0, save_best=None, resume=None):
     config = run_config(**dict(locals()))  # (first statement: the arguments, nothing else)
-    assert mode in ("eager", "graph", "pingpong", "native")
-    if save_every < 0 or (save_every and not save):
-        raise ValueError("save_every must be >= 0 and needs save (the file it rewrites)")
-    if resume and (mode != "native" or update != "native"):
-        raise ValueError("resume restores the device trainer's state: it needs mode='native' and update='native' (got mode=%r, update=%r)"
-                         % (mode, update))
-    if perm not in ("torch", "native"):
-        raise ValueError("perm must be 'torch' or 'native' (got %r)" % (perm,))
-    if perm == "native" and update != "native":
-        raise ValueError("perm='native' draws the permutations for the device update: it needs update='native' (got update=%r)" % (update,))
-    native_perm = perm == "native"
-    if adv_norm not in ("batch", "minibatch"):
-        raise ValueError("adv_norm must be 'batch' or 'minibatch' (got %r)" % (adv_norm,))
-    if (obs_filter or save_obs_filter) and mode != "native":
-        raise ValueError("obs_filter normalises inside the native policy launch: it needs mode='native' (got mode=%r)" % (mode,))
-    if save_obs_filter and not obs_filter:
-        raise ValueError("save_obs_filter needs obs_filter=True")
-    if norm_reward and (mode != "native" or update != "native"):
-        raise ValueError("norm_reward normalises the native rollout's reward buffer ahead of the device's GAE: it needs mode='native' and "
-                         "update='native' (got mode=%r, update=%r)" % (mode, update))
-    if timeout_bootstrap and (mode != "native" or update != "native"):
-        raise ValueError("timeout_bootstrap takes the value of a time-out's terminal observation in the native rollout and hands it to the "
-                         "device's GAE: it needs mode='native' and update='native' (got mode=%r, update=%r)" % (mode, update))
-    if eval_every and mode != "native":
-        raise ValueError("eval_every evaluates the native policy on the device: it needs mode='native' (got mode=%r)" % (mode,))
-    if eval_every < 0 or eval_episodes < 1:
-        raise ValueError("eval_every must be >= 0 and eval_episodes >= 1")
-    if update not in ("torch", "native"):
-        raise ValueError("update must be 'torch' or 'native' (got %r)" % (update,))
-    if update == "native" and mode != "native":
-        raise ValueError("update='native' runs on the native policy's packed parameters: it needs mode='native' (got mode=%r)" % (mode,))
-    # Data parallel: this process is one rank of a job that trains ONE policy (ship_sim_gym_amd/dp.py).  `envs` is the job's total, every
-    # rank builds the same policy from the same seed, and only rank 0 logs, evaluates and saves.
+    run = argparse.Namespace(**locals())  # the run record: the arguments and the config; build_run() and the bind step add the objects
+    # check: every refusal on the host, then the file a run resumes from, before any device work (a wrong command line costs nothing)
     rank, world = job_ranks()
-    env_range = None
-    if world > 1:
-        if mode != "native" or update != "native":
-            raise ValueError("a multi-rank run trains through the device update: it needs mode='native' and update='native' (got mode=%r, "
-                             "update=%r)" % (mode, update))
-        for flag, on in (("--resume", resume), ("--save-every", save_every), ("--obs-filter", obs_filter or save_obs_filter),
-                         ("--norm-reward", norm_reward), ("--adv-norm minibatch", adv_norm == "minibatch")):
-            if on:
-                raise ValueError("%s is not supported with more than one rank (%d ranks)" % (flag, world))
-        from ship_sim_gym_amd import sharding
-        env_range = sharding.shard_range(envs, rank, world)
-        if rank != 0:
-            log = lambda *a, **k: None  # noqa: E731
-    from ship_sim_gym_amd import checkpoint
-    ckpt = None
-    if resume:  # (read and compared before any device work: a wrong command line costs nothing)
-        ckpt = open_resume(resume, config, RESUME_SECTIONS + (("obs_filter",) if obs_filter else ()) + (("ret_filter",) if norm_reward else ()))
-    torch.manual_seed(seed)
-    dev = torch.device(device)
-    gen = torch.Generator(device=dev)
-    gen.manual_seed(seed + 1)
-    probe = ShipVecEnv(1, GameConfig, EnvConfig, device=device, n_maps=1,  # (the observation width follows the beam count)
-                       **{k: v for k, v in dict(env_kw or {}).items() if k == "n_beams"})
-    D, A = probe.states_history, probe.action_space.n
-    probe.close()
-    net = ActorCritic(D, A, hidden=hidden, separate_value=separate_value).to(dev)
-    opt = torch.optim.Adam(net.parameters(), lr=lr)
-    shards = make_shards(envs, mode, net, device, horizon, env_kw=env_kw, env_range=env_range)
-    if world > 1:
-        sharding.broadcast_bank(shards[0].env, src=0)
-    for sh in shards:
-        sh.env.reset_tensor()
-    policy = NativePolicy.from_actor_critic(net, shards[0].scale) if mode == "native" else None
-    if world > 1:  # (refuses, on every rank alike, shards that would make different numbers of minibatches)
-        from ship_sim_gym_amd.dp import DataParallelPPO
-        ppo = DataParallelPPO(policy, shards[0].env, plan=(horizon, minibatches), lr=lr, clip=clip, perm_seed=seed if native_perm else None)
-    else:
-        ppo = (NativePPO(policy, shards[0].env, lr=lr, clip=clip, adv_norm=adv_norm, perm_seed=seed if native_perm else None)
-               if update == "native" else None)
-    job = None if world == 1 else (env_range[0], env_range[1], envs)
-    n_local = envs if world == 1 else env_range[1] - env_range[0]
-
-    def episode_stats():
-        """The episode counters so far: this process's envs', or (every rank calls it: an all-reduce) the whole job's."""
-        if world > 1:
-            return sharding.global_stats(shards[0].env)
-        return {k: sum(sh.env.stats()[k] for sh in shards) for k in ("sum_return", "episodes", "goals_hit")}
-    flt = None
-    if obs_filter:  # (the rollout loop merges each step's observations, then normalises them; obs_scale is no longer read)
-        from ship_sim_gym_amd.obs_filter import ObsFilter
-        flt = ObsFilter(shards[0].env)
-        shards[0].env.set_obs_filter(flt)
-    if timeout_bootstrap:  # (the rollout then also returns "boot", which gae() reads: a time-out is no longer scored as a return of 0)
-        shards[0].env.set_timeout_bootstrap(True, rows=horizon)
-    rflt = None
-    if norm_reward:  # (applied to each rollout's reward buffer between the rollout and GAE; nothing is bound to the env)
-        from ship_sim_gym_amd.ret_filter import ReturnFilter
-        rflt = ReturnFilter(shards[0].env, gamma=gamma, clip=reward_clip)
-    evaluator, evals = None, []
-    if eval_every and rank == 0:  # a second env of its own (a data-parallel job evaluates on rank 0): evaluation resets and steps it, the training envs keep their episodes
-        from ship_sim_gym_amd.evaluate import NativeEvaluator
-        eval_env = ShipVecEnv(int(eval_envs or min(envs, 1024)), GameConfig, EnvConfig, device=device, n_maps=64, **dict(env_kw or {}))
-        evaluator = NativeEvaluator(eval_env)
-        if flt is not None:
-            eval_env.set_obs_filter(flt.frozen(eval_env))  # the training statistics, never updated by an evaluation
+    check_train_arguments(run, world)
+    if rank != 0:  # (a data-parallel job trains ONE policy, ship_sim_gym_amd/dp.py: only rank 0 logs, evaluates and saves)
+        log = lambda *_, **__: None  # noqa: E731
+    ckpt = open_resume(resume, config, loop.resume_sections(RESUME_SECTIONS, obs_filter, norm_reward), exempt=CONFIG_EXEMPT) if resume else None
+    # build, bind, resume
+    build_run(run, rank, world)
+    eval_env = (ShipVecEnv(int(eval_envs or min(envs, 1024)), GameConfig, EnvConfig, device=device, n_maps=64, **dict(env_kw or {}))
+                if eval_every and rank == 0 else None)
+    run.flt, run.rflt, run.evaluator = loop.bind_env(run.env, horizon, 1, obs_filter, norm_reward, gamma, reward_clip, timeout_bootstrap, eval_env)
     if mode in ("graph", "pingpong"):
-        # one eager warm-up step per shard OUTSIDE the capture (prepares the library's kernels and hipBLASLt's workspaces), then the
-        # envs start over; the capture itself runs nothing
-        for sh in shards:
-            sh.step()
-            sh.env.reset_tensor()
-            sh.t.zero_()
-        torch.cuda.synchronize()
-        for sh in shards:
-            sh.capture(torch.cuda.Stream(device=dev))
-        torch.cuda.synchronize()
-    history, t_roll, t_upd, t_all0 = [], 0.0, 0.0, time.perf_counter()
-    snapshots = []
-    # --save-best (the reference callback's best_model.pkl, train/stable_baselines/ppo.py:25-52): an update's score is the mean return
-    # of the episodes that ended during it (-inf when none did, which never counts as a best)
-    ep_scores, best, best_update = [], float("-inf"), -1
-    if save or save_best:
-        if ppo is not None and world == 1:
-            shards[0].env.check_snapshot_supported("snapshot")  # (refuse now, not after the training, a handle that cannot be saved)
-    st0 = episode_stats()
-    seen_episodes, seen_return = st0["episodes"], st0["sum_return"]
-    start = 0
-    if ckpt is not None:  # everything is built and bound as the configuration says; now take the saved state over
-        loop = ckpt["loop"]
-        policy.load_state_dict(ckpt["policy"])
-        ppo.load_state_dict(ckpt["trainer"])
-        if flt is not None:
-            flt.load_state_dict(ckpt["obs_filter"])
-        if rflt is not None:
-            rflt.load_state_dict(ckpt["ret_filter"])
-        shards[0].env.restore(ckpt["env"])
-        gen.set_state(loop["gen_state"])
-        history = [tuple(r) for r in loop["history"]]
-        ep_scores, best, best_update = list(loop["scores"]), float(loop["best"]), int(loop["best_update"])
-        seen_episodes, seen_return = int(loop["episodes"]), float(loop["sum_return"])
-        start = int(loop["update"]) + 1
-        log("resumed from %s: %d updates done, continuing at update %d of %d" % (resume, start, start, updates))
-
-    def write(path, u):
-        """The checkpoint after update u: everything a resumed run needs with the device update, else the policy (for evaluation)."""
-        sections = {"config": config,
-                    "loop": {"update": int(u), "gen_state": gen.get_state().cpu().clone(), "history": [list(r) for r in history],
-                             "scores": list(ep_scores), "best": float(best), "best_update": int(best_update),
-                             "episodes": int(seen_episodes), "sum_return": float(seen_return)}}
-        if ppo is not None and world > 1:  # (rank 0's file: the policy and the trainer; per-rank env snapshots are out of scope)
-            sections.update(policy=policy.state_dict(), trainer=ppo.state_dict())
-        elif ppo is not None:
-            sections.update(policy=policy.state_dict(), trainer=ppo.state_dict(), env=shards[0].env.snapshot())
-            if rflt is not None:
-                sections["ret_filter"] = rflt.state_dict()
-        else:  # (the torch update trains the module: pack it as evaluation reads it)
-            sections["policy"] = (policy if policy is not None else NativePolicy.from_actor_critic(net, shards[0].scale)).state_dict()
-        if flt is not None:
-            sections["obs_filter"] = flt.state_dict()
-        checkpoint.save(path, sections)
-
+        capture_graphs(run)
+    snapshots, evals, t_roll, t_upd, t_all0 = [], [], 0.0, 0.0, time.perf_counter()
+    if (save or save_best) and run.ppo is not None and world == 1:
+        run.env.check_snapshot_supported("snapshot")  # (refuse now, not after the training, a handle that cannot be saved)
+    st0 = episode_stats(run)
+    state = LoopState(st0["episodes"], st0["sum_return"])
+    if ckpt is not None:
+        load_run(run, state, ckpt)
+        log("resumed from %s: %d updates done, continuing at update %d of %d" % (resume, state.update + 1, state.update + 1, updates))
+    start = state.update + 1
     for u in range(start, updates):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        b = rollout(shards, horizon, mode, gen, policy, job=job)
+        b = rollout(run.shards, horizon, mode, run.gen, run.policy, job=run.job)
         torch.cuda.synchronize()
         t_roll += time.perf_counter() - t0
         native_last_val = b.pop("last_val", None)
         if return_details is True:
             snapshots.append({k: v.clone() for k, v in b.items()})
         t1 = time.perf_counter()
-        if ppo is not None:  # GAE + the whole update on the device, on the rollout's own buffers (the same randperm draws)
-            nb = dict(shards[0].native_out)
-            ppo.gae(nb, gamma, lam, return_filter=rflt)
-            n = horizon * n_local  # (a rank shuffles its own samples)
-            # perm "native": the library shuffles (a row per epoch, keyed by the seed and the update's number); else torch's generator
-            rows = None if native_perm else torch.stack([torch.randperm(n, device=dev, generator=gen) for _ in range(epochs)])
-            st_upd = ppo.update(nb, rows, epochs, minibatches, stats=flt is not None or rflt is not None)
-            if st_upd is not None:
-                pg, vf, ent = (float(v) for v in st_upd[-1, :3])
-                notes = []
-                if flt is not None:
-                    notes.append("(obs filter: %d rows merged)" % int(flt.count[0].item()))
-                if rflt is not None:
-                    notes.append("(return filter: %d returns merged, std %.5f)" % (int(rflt.count[0].item()), float(rflt.denom[0].item())))
-                log("update %3d  last minibatch: policy loss %+.5f  value loss %.5f  entropy %.5f  %s" % (u, pg, vf, ent, "  ".join(notes)))
+        if run.ppo is not None:
+            native_update(run, u, log)
         else:
-            if native_last_val is not None:
-                last_val = native_last_val
-            else:
-                with torch.no_grad():
-                    last_val = torch.cat([net(normalise(sh.env.obs, sh.scale))[1] for sh in shards])
-            adv = torch.zeros(envs, device=dev)
-            advs, rets = [None] * horizon, [None] * horizon
-            nxt = last_val
-            for t in reversed(range(horizon)):           # GAE; a done env's next obs belongs to a fresh episode (auto-reset)
-                nonterm = 1.0 - b["done"][t]
-                delta = b["rew"][t] + gamma * nxt * nonterm - b["val"][t]
-                adv = delta + gamma * lam * nonterm * adv
-                advs[t], rets[t] = adv, adv + b["val"][t]
-                nxt = b["val"][t]
-            b_obs, b_act = b["obs"].reshape(horizon * envs, D), b["act"].reshape(-1)
-            b_logp, b_adv, b_ret = b["logp"].reshape(-1), torch.cat(advs), torch.cat(rets)
-            if adv_norm == "batch":
-                b_adv = (b_adv - b_adv.mean()) / (b_adv.std() + 1e-8)
-            n = b_obs.shape[0]
-            for _ in range(epochs):
-                perm = torch.randperm(n, device=dev, generator=gen)
-                for mb in perm.chunk(minibatches):
-                    logits, val = net(b_obs[mb])
-                    dist = torch.distributions.Categorical(logits=logits)
-                    ratio = torch.exp(dist.log_prob(b_act[mb]) - b_logp[mb])
-                    mb_adv = b_adv[mb]
-                    if adv_norm == "minibatch":  # PPO2's rule, as the device update applies it: the minibatch's own mean / unbiased std
-                        mb_std = mb_adv.std() if mb_adv.numel() > 1 else mb_adv.new_zeros(())  # (one sample: a std of 0, not NaN)
-                        mb_adv = (mb_adv - mb_adv.mean()) / (mb_std + 1e-8)
-                    pg = -torch.min(ratio * mb_adv, torch.clamp(ratio, 1 - clip, 1 + clip) * mb_adv).mean()
-                    loss = pg + 0.5 * (val - b_ret[mb]).pow(2).mean() - 0.01 * dist.entropy().mean()
-                    opt.zero_grad(); loss.backward(); opt.step()
-            if policy is not None:
-                policy.refresh()
+            eager_update(run, b, native_last_val)
         torch.cuda.synchronize()
         t_upd += time.perf_counter() - t1
-        st = episode_stats()
-        mean_ret = st["sum_return"] / max(st["episodes"], 1)
-        goals_per_ep = st["goals_hit"] / max(st["episodes"], 1)
-        history.append((u, mean_ret, goals_per_ep, float(b["rew"].mean())))
-        log("update %3d  episodes %8d  mean return so far %+.3f  goals/episode %.3f  mean step reward %+.4f" % (
-            u, st["episodes"], mean_ret, goals_per_ep, history[-1][3]))
-        ended = st["episodes"] - seen_episodes
-        ep_scores.append((st["sum_return"] - seen_return) / ended if ended > 0 else float("-inf"))
-        seen_episodes, seen_return = st["episodes"], st["sum_return"]
-        if ep_scores[-1] > best:  # (an update in which no episode ended scores -inf: it never gets here)
-            best, best_update = ep_scores[-1], u
+        ended = account(run, state, u, b, log)
+        if state.scores[-1] > state.best:  # save-best: written at once (an update in which no episode ended scores -inf: never here)
+            state.best, state.best_update = state.scores[-1], u
             if save_best and rank == 0:
-                write(save_best, u)
-                log("update %3d  episode_reward_mean %+.3f over %d episodes: the best so far, saved to %s" % (u, best, ended, save_best))
+                write_checkpoint(save_best, run, state)
+                log("update %3d  episode_reward_mean %+.3f over %d episodes: the best so far, saved to %s" % (u, state.best, ended, save_best))
         if save and save_every and (u + 1) % save_every == 0:
-            write(save, u)
-        if evaluator is not None and (u + 1) % eval_every == 0:
-            r = evaluator.evaluate(policy, eval_episodes, greedy=True)
-            evals.append((u, {k: (v[0] if hasattr(v, "__len__") else v) for k, v in r.items() if k not in ("per_env", "per_member")}))
-            log("update %3d  greedy evaluation (%d envs x %d episodes): mean return %+.3f  length %.1f  goals/episode %.3f  "
-                "collided %.2f  out of bounds %.2f  timed out %.2f" % (
-                    u, evaluator.env.num_envs, eval_episodes, r["return_mean"][0], r["length_mean"][0], r["goals_per_episode"][0],
-                    r["collision_rate"][0], r["out_of_bounds_rate"][0], r["max_steps_rate"][0]))
+            write_checkpoint(save, run, state)
+        if run.evaluator is not None and (u + 1) % eval_every == 0:
+            evals.append(evaluate(run, u, eval_episodes, log))
+    # finish
     torch.cuda.synchronize()
     t_all = time.perf_counter() - t_all0
     if save and rank == 0:
-        write(save, max(updates, start) - 1)
-        log("checkpoint after update %d saved to %s" % (max(updates, start) - 1, save))
-    if ppo is not None:
-        ppo.load_into(net)  # the module gets the device-trained parameters (details["params"])
+        write_checkpoint(save, run, state)
+        log("checkpoint after update %d saved to %s" % (state.update, save))
+    if run.ppo is not None:
+        run.ppo.load_into(run.net)  # the module gets the device-trained parameters (details["params"])
     if world > 1:  # every rank prints it: the ranks hold the same bits, so the lines are the same
         import hashlib
-        print("parameter checksum after %d Adam steps: %s" % (ppo.step, hashlib.sha256(policy.params.detach().cpu().numpy().tobytes()).hexdigest()),
-              flush=True)
+        print("parameter checksum after %d Adam steps: %s" % (
+            run.ppo.step, hashlib.sha256(run.policy.params.detach().cpu().numpy().tobytes()).hexdigest()), flush=True)
     steps = envs * horizon * max(0, updates - start)  # (this process's own; a resumed run did not step the updates it loaded)
     log("rollout (%s): %.1f M env-steps/s with the policy in the loop; whole training loop (rollout + PPO update): %.1f M env-steps/s" % (
         mode, steps / max(t_roll, 1e-9) / 1e6, steps / max(t_all, 1e-9) / 1e6))
+    full = return_details is True
     details = {"mode": mode, "rollout_env_steps_per_s": steps / max(t_roll, 1e-9), "training_env_steps_per_s": steps / max(t_all, 1e-9),
                "rollout_us_per_step": t_roll * 1e6 / (horizon * max(1, updates - start)), "rollout_seconds": t_roll, "update_seconds": t_upd, "total_seconds": t_all,
-               "snapshots": snapshots, "final_state": [env_columns(sh.env) for sh in shards] if return_details is True else None,
-               "params": [p.detach().clone() for p in net.parameters()] if return_details is True else None, "evaluations": evals,
-               "episode_reward_mean": list(ep_scores), "best": best, "best_update": best_update,
-               "env_state": shards[0].env.state.detach().cpu().clone() if return_details is True else None}
-    if flt is not None:
-        details["obs_filter"] = flt.state_dict()
-        if save_obs_filter:
-            torch.save(details["obs_filter"], save_obs_filter)
-            log("observation filter statistics (%d rows merged) saved to %s" % (int(details["obs_filter"]["state"][0, 3, 0]), save_obs_filter))
-    if rflt is not None:
-        details["ret_filter"] = rflt.state_dict()
-    if evaluator is not None:
-        evaluator.env.close()
-    for sh in shards:
+               "snapshots": snapshots, "final_state": [env_columns(sh.env) for sh in run.shards] if full else None,
+               "params": [p.detach().clone() for p in run.net.parameters()] if full else None, "evaluations": evals,
+               "episode_reward_mean": list(state.scores), "best": state.best, "best_update": state.best_update,
+               "env_state": run.env.state.detach().cpu().clone() if full else None}
+    details.update(loop.filter_sections(run.flt, run.rflt))
+    if run.flt is not None and save_obs_filter:
+        torch.save(details["obs_filter"], save_obs_filter)
+        log("observation filter statistics (%d rows merged) saved to %s" % (int(details["obs_filter"]["state"][0, 3, 0]), save_obs_filter))
+    if run.evaluator is not None:
+        run.evaluator.env.close()
+    for sh in run.shards:
         sh.graph = None
         sh.env.close()
-    return (history, details) if return_details else history
+    return (state.history, details) if return_details else state.history
 
 
 def make_arg_parser():
@@ -614,45 +631,13 @@ def make_arg_parser():
 
 
 def parse_args(argv=None):
-    """make_arg_parser().parse_args, refusing --update native without --mode native."""
+    """make_arg_parser().parse_args, then the shared value checks and REQUIREMENTS for the job's size (--gpus, or a launcher's WORLD_SIZE)."""
     ap = make_arg_parser()
     a = ap.parse_args(argv)
-    if a.eval_every < 0 or a.eval_episodes < 1:
-        ap.error("--eval-every must be >= 0 and --eval-episodes >= 1")
-    if a.eval_every and a.mode != "native":
-        ap.error("--eval-every needs --mode native (the evaluation runs the native policy on the device)")
-    if a.update == "native" and a.mode != "native":
-        ap.error("--update native needs --mode native (the update runs on the native policy's packed parameters)")
-    if a.perm == "native" and a.update != "native":
-        ap.error("--perm native needs --update native (the library draws the permutations of the device update)")
-    if a.obs_filter and a.mode != "native":
-        ap.error("--obs-filter needs --mode native (the filter runs inside the native policy launch)")
-    if a.save_obs_filter and not a.obs_filter:
-        ap.error("--save-obs-filter needs --obs-filter")
-    if a.norm_reward and (a.mode != "native" or a.update != "native"):
-        ap.error("--norm-reward needs --mode native --update native (it runs between the native rollout and the device's GAE)")
-    if a.timeout_bootstrap and (a.mode != "native" or a.update != "native"):
-        ap.error("--timeout-bootstrap needs --mode native --update native (the torch-mode update has no time-out bootstrap)")
-    if a.reward_clip != 10.0 and not a.norm_reward:
-        ap.error("--reward-clip needs --norm-reward")
-    if not a.reward_clip >= 0.0:
-        ap.error("--reward-clip must be >= 0")
-    if a.save_every < 0:
-        ap.error("--save-every must be >= 0")
-    if a.save_every and not a.save:
-        ap.error("--save-every needs --save (the file it rewrites)")
-    if a.resume and (a.mode != "native" or a.update != "native"):
-        ap.error("--resume needs --mode native --update native (it restores the device trainer's state)")
+    loop.check_flag_values(a, ap.error)
     if a.gpus < 1 or a.gpus > 64:
         ap.error("--gpus must be in 1..64")
-    ranks = max(a.gpus, int(os.environ.get("WORLD_SIZE", "1")))
-    if ranks > 1:
-        if a.mode != "native" or a.update != "native":
-            ap.error("more than one rank (--gpus / WORLD_SIZE = %d) needs --mode native --update native" % ranks)
-        for flag, on in (("--resume", a.resume), ("--save-every", a.save_every), ("--obs-filter", a.obs_filter or a.save_obs_filter),
-                         ("--norm-reward", a.norm_reward), ("--adv-norm minibatch", a.adv_norm == "minibatch")):
-            if on:
-                ap.error("%s is not supported with more than one rank (%d ranks): see README.md, Data parallel" % (flag, ranks))
+    check_requirements(vars(a), max(a.gpus, int(os.environ.get("WORLD_SIZE", "1"))), ap.error)
     return a
 
 
@@ -719,11 +704,7 @@ def main(argv=None):
         if a.gpus > 1 and a.gpus != int(os.environ["WORLD_SIZE"]):
             sys.exit("train/ppo_torch.py: --gpus %d but WORLD_SIZE=%s" % (a.gpus, os.environ["WORLD_SIZE"]))
         device = str(join_job())
-    train(device=device, envs=a.envs, updates=a.updates, horizon=a.horizon, mode=a.mode, update=a.update, separate_value=a.separate_value,
-          eval_every=a.eval_every, eval_episodes=a.eval_episodes, obs_filter=a.obs_filter, save_obs_filter=a.save_obs_filter,
-          norm_reward=a.norm_reward, reward_clip=a.reward_clip, adv_norm=a.adv_norm, perm=a.perm,
-          timeout_bootstrap=a.timeout_bootstrap, hidden=a.hidden, save=a.save, save_every=a.save_every, save_best=a.save_best,
-          resume=a.resume)
+    train(device=device, **{k: v for k, v in vars(a).items() if k != "gpus"})  # (every other flag is an argument of train() of the same name)
     if in_job:
         import torch.distributed as dist
         dist.barrier()
