@@ -368,6 +368,18 @@ int ssg_dyn_invalidate(ssg_handle *h, const uint8_t *dev_mask, void *stream);
  * ship_env.py:18); not a hot path. */
 int ssg_render(ssg_handle *h, int env_index, int width, int height, uint8_t *dev_rgb, uint32_t flags, void *stream);
 
+/* Replaces: the env.render() of every step of the evaluation loop (train/rllib/rollout.py:18-19) over ShipGame.render + get_screen
+ * (game.py:133-138,197-229), for `count` envs in ONE launch: a grid over (128-pixel column blocks, rows, frame).  dev_env_ids is a
+ * DEVICE array int32 [count]; frame i (dev_rgb + i * width * height * 3, laid out [width][height][3]) is bit for bit what
+ * ssg_render(h, dev_env_ids[i], width, height, ..., flags) writes: both kernels call the same per-block beam set-up and the same
+ * per-pixel function.  The ids live on the device and the host cannot see them: a frame whose id is outside 0 .. n_envs-1 is skipped
+ * by the kernel and left UNWRITTEN (the other frames are drawn).  Ids may repeat.  The checks of ssg_render in its order — NULL
+ * handle, NULL buffers or a width / height outside 1 .. 8192 — plus count outside 1 .. SSG_RENDER_MAX_ENVS and
+ * count * width * height * 3 above 2^31: SSG_ERR_BAD_ARG on any handle; then an unbound handle is SSG_ERR_NOT_BOUND. */
+#define SSG_RENDER_MAX_ENVS 4096
+int ssg_render_envs(ssg_handle *h, const int32_t *dev_env_ids, int count, int width, int height, uint8_t *dev_rgb, uint32_t flags,
+                    void *stream);
+
 /* Measurement aid (config 4; no reference counterpart): with enable != 0, every following ssg_step / ssg_rollout* call brackets the
  * two launches of each step — the full cpSpaceStep of the queued envs, the step kernel — with HIP events on the caller's stream and
  * waits for its own work at the end of the call.  Returns the averages (microseconds per step) and the number of steps accumulated
@@ -956,6 +968,78 @@ int ssg_pop_evaluate(ssg_handle *h, const ssg_population *pop, const ssg_eval *e
  * is WRITTEN, not accumulated, with the column sums of each member's n = N / n_members rows of dev_env_stats: one workgroup per member,
  * a strided loop and an integer tree, no atomics.  n_members = 1 serves a single policy.  One launch. */
 int ssg_eval_reduce(ssg_handle *h, int n_members, const int64_t *dev_env_stats, int64_t *dev_member_stats, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Evaluation recorder (addition to ABI 9): the trajectories, and optionally the frames, of a few envs of an evaluation run
+ * The reference's evaluation loop renders every step (train/rllib/rollout.py:18-19) and with --out keeps
+ * [state, action, next_state, reward, done] of every step (train/rllib/rollout.py:20-28).  While a record is bound to a handle,
+ * ssg_evaluate / ssg_pop_evaluate keep exactly that for R tracked envs, on the device, with no host synchronisation and no atomics.
+ *
+ * Slot r tracks env e = env_ids[r].  All buffers are the caller's, on the device, env-major (a slot's C steps are contiguous):
+ * obs / next_obs f64 [R][C][D] (D = history * (6 + n_beams)), act i32 / logp f32 / value f32 / reward f64 / done u8 / flags u8 [R][C],
+ * cursor i32 [R] (steps kept so far) and overflow i32 [R] (counted steps that found the slot full); the caller zeroes cursor and
+ * overflow to start a recording, and nothing else needs initialising.
+ *
+ * Iteration k of the loop, for every slot r:
+ *   - the slot is ACTIVE iff env e has counted fewer than E = ssg_eval.episodes_per_env episodes (dev_carry[e][2] < E, read BEFORE
+ *     this iteration's accounting launch) and cursor[r] < C.  An active slot writes, at t = cursor[r]:
+ *       obs[r][t]      env e's row of dev_obs as the policy launch read it: the raw f64 row, before any observation filter
+ *       act, logp, value [r][t]   the policy launch's outputs for e
+ *       reward, done, flags [r][t]   the step's
+ *       next_obs[r][t] the TERMINAL observation of the step (env e's row of dev_term_obs) when done, else e's row of dev_obs after it
+ *       frames[r][t / S] when frames are on and t % S == 0: bit for bit the frame ssg_render(h, e, W, H, ..., frame_flags) draws at
+ *                      the moment obs[r][t] was current — BEFORE the step: what the agent saw when it chose act[r][t]
+ *     and then cursor[r] += 1;
+ *   - a slot whose env still counts but whose cursor[r] == C writes nothing and adds 1 to overflow[r];
+ *   - a slot whose env has counted E episodes touches nothing, ever.
+ * The kept steps of a slot are therefore exactly the steps the accounting counted, until the capacity runs out; episodes are cut
+ * where done is set, and a later call continues at the cursors as it continues the carries.  The post-crash state of a done step is
+ * never drawn: the env is reset inside the step, so the frame after a done step shows the next episode's first state.
+ *
+ * Launches.  Per iteration: one R-lane launch ahead of the policy launch (obs), one R-lane launch between the step and the accounting
+ * launch (everything else, the cursors), and with frames one launch of R x W x H pixels ahead of the step.  For the duration of the
+ * call the step kernel's terminal-observation rows (ssg_set_terminal_obs) point at dev_term_obs; the caller's own binding is back in
+ * place on every way out.  The handle's state blob, observations, reward / done / flags rows, carries and stats rows are bit for bit
+ * what they are with nothing bound, and with nothing bound the loop enqueues exactly the launches it enqueued before this addition.
+ * ------------------------------------------------------------------------------------------------- */
+#define SSG_EVAL_REC_MAX_ENVS 64
+typedef struct ssg_eval_recorder {
+    uint32_t struct_size;     /* sizeof(ssg_eval_recorder) */
+    int32_t n_tracked;        /* R in 1..SSG_EVAL_REC_MAX_ENVS */
+    const int32_t *env_ids;   /* HOST int32 [R]: distinct, each in [0, n_envs), any order; copied by ssg_set_eval_recorder */
+    int32_t capacity;         /* C >= 1: the steps kept per tracked env, across all of its episodes */
+    int32_t frame_width;      /* W, H in 1..8192 and S >= 1: read only with dev_frames != NULL */
+    int32_t frame_height;
+    int32_t frame_every;      /* S: a frame for every S-th kept step of a slot (t % S == 0) */
+    uint32_t frame_flags;     /* bit 0 = debug drawing, as ssg_render's flags */
+    uint32_t reserved;        /* 0 */
+    double *dev_obs;          /* f64 [R][C][D] */
+    double *dev_next_obs;     /* f64 [R][C][D] */
+    int32_t *dev_act;         /* [R][C] each */
+    float *dev_logp;
+    float *dev_value;
+    double *dev_reward;
+    uint8_t *dev_done;
+    uint8_t *dev_flags;
+    int32_t *dev_cursor;      /* i32 [R] */
+    int32_t *dev_overflow;    /* i32 [R] */
+    double *dev_term_obs;     /* f64 [n_envs][D]: scratch for the step kernel's terminal-observation rows; need not be initialised */
+    uint8_t *dev_frames;      /* nullable (no frames): u8 [R][ceil(C / S)][W][H][3], each frame laid out as ssg_render's */
+} ssg_eval_recorder;
+
+/* Replaces: `rollout.append([state, action, next_state, reward, done])` and env.render() of train/rllib/rollout.py:18-21, as a record
+ * bound to the handle (host only, nothing launched, nothing allocated); NULL unbinds.  The library checks env_ids and keeps its own
+ * copy, which every recorder launch receives by value: the caller's array is free when the call returns.  Every refusal is made
+ * before anything changes and leaves the previous binding in place: SSG_ERR_UNSUPPORTED for history > 2 (no terminal observations:
+ * ssg_set_terminal_obs); SSG_ERR_BAD_ARG for a handle without SSG_FLAG_AUTO_RESET, a struct_size mismatch, reserved != 0, n_tracked
+ * outside 1..SSG_EVAL_REC_MAX_ENVS, capacity < 1, a NULL env_ids or required buffer, an env id that repeats or lies outside
+ * [0, n_envs), and with dev_frames: frame_width or frame_height outside 1..8192, frame_every < 1, or more than 2^31 bytes of frames
+ * per slot (ceil(C / S) * W * H * 3). */
+int ssg_set_eval_recorder(ssg_handle *h, const ssg_eval_recorder *rec /* NULL unbinds */);
+
+/* Replaces nothing (introspection).  *out = the bound record; out->struct_size == 0 (all of *out zero): nothing bound.  out->env_ids
+ * points at the library's own copy, valid until the next ssg_set_eval_recorder or ssg_destroy on the handle. */
+int ssg_get_eval_recorder(const ssg_handle *h, ssg_eval_recorder *out /* struct_size 0: nothing bound */);
 
 /* ---------------------------------------------------------------------------------------------------
  * Observation filter (ABI 9 addition): a running mean / std per observation column, kept and applied on the device

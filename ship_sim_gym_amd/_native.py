@@ -78,7 +78,10 @@ EXPORTS = (
     "ssg_host_perm", "ssg_ppo_perm", "ssg_pop_perm",
     "ssg_set_timeout_boot", "ssg_get_timeout_boot", "ssg_timeout_values", "ssg_pop_timeout_values", "ssg_ppo_gae_boot", "ssg_pop_gae_boot",
     "ssg_ppo_adv_moments", "ssg_ppo_set_adv_moments", "ssg_ppo_apply_shards",
+    "ssg_render_envs", "ssg_set_eval_recorder", "ssg_get_eval_recorder",
 )
+RENDER_MAX_ENVS = 4096  # frames of one ssg_render_envs launch at most
+EVAL_REC_MAX_ENVS = 64  # tracked envs of an evaluation recorder at most
 DP_MAX_SHARDS = 64  # ssg_ppo_shards.n_shards at most
 
 
@@ -179,6 +182,20 @@ class TimeoutBootRecord(C.Structure):
     [rows][n_envs][D], the values f32 [rows][stride]."""
     _fields_ = [
         ("struct_size", C.c_uint32), ("rows", C.c_int32), ("dev_term_obs_KND", C.c_void_p), ("dev_boot_KN", C.c_void_p),
+    ]
+
+
+class EvalRecorderRecord(C.Structure):
+    """ssg_eval_recorder (addition to ABI 9): the tracked envs (a HOST int32 array the library copies), the steps kept per env, the
+    frame geometry, and the caller's device buffers — the trajectory rows [R][C](...), cursor / overflow [R], the terminal-observation
+    scratch [n_envs][D] and the optional frames [R][ceil(C / S)][W][H][3]."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_tracked", C.c_int32), ("env_ids", C.POINTER(C.c_int32)), ("capacity", C.c_int32),
+        ("frame_width", C.c_int32), ("frame_height", C.c_int32), ("frame_every", C.c_int32), ("frame_flags", C.c_uint32),
+        ("reserved", C.c_uint32), ("dev_obs", C.c_void_p), ("dev_next_obs", C.c_void_p), ("dev_act", C.c_void_p),
+        ("dev_logp", C.c_void_p), ("dev_value", C.c_void_p), ("dev_reward", C.c_void_p), ("dev_done", C.c_void_p),
+        ("dev_flags", C.c_void_p), ("dev_cursor", C.c_void_p), ("dev_overflow", C.c_void_p), ("dev_term_obs", C.c_void_p),
+        ("dev_frames", C.c_void_p),
     ]
 
 
@@ -309,6 +326,9 @@ def lib():
     L.ssg_ppo_set_adv_moments.argtypes = [vp, C.c_int, vp, C.c_double, vp, C.c_size_t, vp]
     L.ssg_ppo_apply_shards.argtypes = [vp, C.POINTER(Policy), hp, xp, C.POINTER(PpoShards), vp, C.c_int64, vp, vp, C.c_size_t, vp]
     L.ssg_render.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, vp]
+    L.ssg_render_envs.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, vp]
+    L.ssg_set_eval_recorder.argtypes = [vp, C.POINTER(EvalRecorderRecord)]
+    L.ssg_get_eval_recorder.argtypes = [vp, C.POINTER(EvalRecorderRecord)]
     L.ssg_dyn_invalidate.argtypes = [vp, vp, vp]
     L.ssg_host_convex_hull.argtypes = [C.c_int, dp, dp, ip]
     L.ssg_host_moment_for_poly.argtypes = [C.c_double, C.c_int, dp, dp]

@@ -65,6 +65,9 @@ struct ssg_handle {
     // ssg_set_timeout_boot: the bound record (a copy; struct_size 0: nothing bound) and whether the time-out kernels' LDS limit is set
     ssg_timeout_boot tob{};
     bool policy_boot_prepared = false;
+    // ssg_set_eval_recorder: the bound record (a copy; struct_size 0: nothing bound), its env_ids pointing at the copy beside it
+    ssg_eval_recorder rec{};
+    ssg::EvalRecIds rec_ids{};
     // ssg_ppo_set_adv_norm: the mode (SSG_ADV_NORM_BATCH: nothing bound), the member count the scratch serves and the caller's scratch
     int adv_norm_mode = SSG_ADV_NORM_BATCH, adv_norm_members = 0;
     void *adv_norm_scratch = nullptr;
@@ -1473,6 +1476,14 @@ int ssg_pop_timeout_values(ssg_handle *h, const ssg_population *pop, int K, cons
     return rc != SSG_OK ? rc : timeout_values(h, c, K, dev_flags_KN, dev_term_obs_KND, dev_boot_KN, step_stride_envs, stream);
 }
 
+// Restores the caller's terminal-observation binding (ssg_set_terminal_obs) on every way out of a loop that points h->dev.term_obs at
+// rows of its own for the duration of a call: policy_rollout with a time-out record bound, run_evaluate with a recorder bound.
+struct TermObsGuard {
+    ssg_handle *h;
+    double *saved;
+    ~TermObsGuard() { h->dev.term_obs = saved; }
+};
+
 // The body of both rollout entry points: K times the filter's merge (if it updates), ONE policy launch for everyone and the step, then
 // the bootstrap value.  (ssg_rollout_policy has asked check_ready already, ahead of its record: the order of its refusals.)
 // With a time-out record bound (ssg_set_timeout_boot): step k's terminal observations go to row k of the record's rows — h->dev.term_obs
@@ -1503,12 +1514,7 @@ static int policy_rollout(ssg_handle *h, const PolicyCall &c, int K, const float
     if (rc == SSG_OK && boot) rc = prepare_policy_boot(h);
     if (rc != SSG_OK) return rc;
     const size_t S = (size_t)step_stride_envs, D = (size_t)c.pol.obs_dim;
-    // (restores the caller's terminal-observation binding on every way out of this function)
-    struct TermObsGuard {
-        ssg_handle *h;
-        double *saved;
-        ~TermObsGuard() { h->dev.term_obs = saved; }
-    } guard = {h, h->dev.term_obs};
+    TermObsGuard guard = {h, h->dev.term_obs};
     for (int k = 0; k < K; ++k) {
         const size_t r = (size_t)k * S;
         if (boot) h->dev.term_obs = h->tob.dev_term_obs_KND + (size_t)k * (size_t)h->cfg.n_envs * D;
@@ -2333,14 +2339,36 @@ static int run_evaluate(ssg_handle *h, const PolicyCall &c, const ssg_eval *evp,
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const bool greedy = (ev.flags & SSG_EVAL_GREEDY) != 0;
     const int N = h->cfg.n_envs;
+    // With a recorder bound (ssg_set_eval_recorder): the step kernel's terminal-observation rows are the record's for this call, and
+    // each iteration gains the recorder's launches — obs (and the frames) ahead of the step, the rest ahead of the accounting.
+    const bool rec = h->rec.struct_size != 0;
+    TermObsGuard guard = {h, h->dev.term_obs};
+    ssg::EvalRecLaunch rl = {};
+    if (rec) {
+        const ssg_eval_recorder &r = h->rec;
+        h->dev.term_obs = r.dev_term_obs;
+        rl = {r.n_tracked, r.capacity, h->cfg.history * (6 + h->cfg.n_beams), ev.episodes_per_env, ev.dev_carry, r.dev_cursor, r.dev_overflow,
+              r.dev_obs, r.dev_next_obs, r.dev_act, r.dev_logp, r.dev_value, r.dev_reward, r.dev_done, r.dev_flags, r.dev_term_obs, r.dev_frames,
+              r.frame_width, r.frame_height, r.frame_every, r.dev_frames ? (r.capacity + r.frame_every - 1) / r.frame_every : 0, r.frame_flags};
+    }
     for (int k = 0; k < ev.n_steps; ++k) {
         const float *u = ev.dev_uniform_TN ? ev.dev_uniform_TN + (size_t)k * (size_t)N : nullptr;
+        if (rec) {
+            hipError_t e = ssg::launch_eval_record_obs(rl, h->rec_ids, ev.dev_obs, st);
+            if (e == hipSuccess && rl.frames) e = ssg::launch_eval_record_frames(h->dev, h->dyn, rl, h->rec_ids, st);
+            if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string(c.what) + ": recorder launch: " + hipGetErrorString(e));
+        }
         // (a bound observation filter is applied and never updated: evaluation is frozen)
         hipError_t e = policy_launch(h, c, {ev.dev_obs, u, ev.seed, ev.step0 + k, ev.dev_act, ev.dev_logp, ev.dev_value, nullptr, greedy}, st);
         if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string(c.what) + ": policy launch: " + hipGetErrorString(e));
         // (ssg_step as it stands, the call the rollouts make)
         rc = ssg_rollout_traj(h, ev.dev_act, 1, ev.dev_obs, ev.dev_reward, ev.dev_done, ev.dev_flags, 0, stream);
         if (rc != SSG_OK) return rc;
+        if (rec) {
+            e = ssg::launch_eval_record_step(rl, h->rec_ids, ev.dev_obs, ev.dev_act, ev.dev_logp, ev.dev_value, ev.dev_reward, ev.dev_done,
+                                             ev.dev_flags, st);
+            if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string(c.what) + ": recorder launch: " + hipGetErrorString(e));
+        }
         e = ssg::launch_eval_account(N, ev.episodes_per_env, ev.dev_reward, ev.dev_done, ev.dev_flags, ev.dev_carry_return, ev.dev_carry,
                                      ev.dev_env_stats, st);
         if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string(c.what) + ": accounting launch: " + hipGetErrorString(e));
@@ -2361,6 +2389,52 @@ int ssg_pop_evaluate(ssg_handle *h, const ssg_population *pop, const ssg_eval *e
     PolicyCall c;
     const int rc = population_call(h, pop, "ssg_pop_evaluate", c);
     return rc == SSG_OK ? run_evaluate(h, c, ev, stream) : rc;
+}
+
+int ssg_set_eval_recorder(ssg_handle *h, const ssg_eval_recorder *rec)
+{
+    const char *w = "ssg_set_eval_recorder: ";
+    if (!h) return fail(nullptr, SSG_ERR_BAD_ARG, std::string(w) + "NULL handle");
+    if (!rec) { // unbind
+        h->rec = ssg_eval_recorder{};
+        return SSG_OK;
+    }
+    if (h->cfg.history > 2)
+        return fail(h, SSG_ERR_UNSUPPORTED, std::string(w) + "history > 2 builds its rows in the frame-shift kernel: no terminal observations (ssg_set_terminal_obs)");
+    if (!(h->cfg.flags & SSG_FLAG_AUTO_RESET))
+        return fail(h, SSG_ERR_BAD_ARG, std::string(w) + "only a handle that resets its done envs in-kernel (SSG_FLAG_AUTO_RESET) is evaluated and stores terminal observations");
+    if (rec->struct_size != sizeof(ssg_eval_recorder)) return fail(h, SSG_ERR_BAD_ARG, std::string(w) + "ssg_eval_recorder.struct_size != sizeof(ssg_eval_recorder)");
+    if (rec->reserved != 0) return fail(h, SSG_ERR_BAD_ARG, std::string(w) + "ssg_eval_recorder.reserved must be 0");
+    if (rec->n_tracked < 1 || rec->n_tracked > SSG_EVAL_REC_MAX_ENVS) return fail(h, SSG_ERR_BAD_ARG, std::string(w) + "n_tracked must be in 1..SSG_EVAL_REC_MAX_ENVS");
+    if (rec->capacity < 1) return fail(h, SSG_ERR_BAD_ARG, std::string(w) + "capacity < 1");
+    if (!rec->env_ids || !rec->dev_obs || !rec->dev_next_obs || !rec->dev_act || !rec->dev_logp || !rec->dev_value || !rec->dev_reward ||
+        !rec->dev_done || !rec->dev_flags || !rec->dev_cursor || !rec->dev_overflow || !rec->dev_term_obs)
+        return fail(h, SSG_ERR_BAD_ARG, std::string(w) + "NULL env_ids or a NULL required buffer (all but dev_frames are required)");
+    for (int r = 0; r < rec->n_tracked; ++r) {
+        if (rec->env_ids[r] < 0 || rec->env_ids[r] >= h->cfg.n_envs) return fail(h, SSG_ERR_BAD_ARG, std::string(w) + "an env id is outside [0, n_envs)");
+        for (int q = 0; q < r; ++q)
+            if (rec->env_ids[q] == rec->env_ids[r]) return fail(h, SSG_ERR_BAD_ARG, std::string(w) + "an env id repeats (two slots would record one env)");
+    }
+    if (rec->dev_frames) {
+        if (rec->frame_width < 1 || rec->frame_height < 1 || rec->frame_width > 8192 || rec->frame_height > 8192)
+            return fail(h, SSG_ERR_BAD_ARG, std::string(w) + "frame_width and frame_height must be in 1..8192");
+        if (rec->frame_every < 1) return fail(h, SSG_ERR_BAD_ARG, std::string(w) + "frame_every < 1");
+        const long long slots = ((long long)rec->capacity + rec->frame_every - 1) / rec->frame_every;
+        if (slots * rec->frame_width * rec->frame_height * 3 > (1ll << 31))
+            return fail(h, SSG_ERR_BAD_ARG, std::string(w) + "more than 2^31 bytes of frames per slot (ceil(capacity / frame_every) * width * height * 3)");
+    }
+    h->rec = *rec;
+    std::copy(rec->env_ids, rec->env_ids + rec->n_tracked, h->rec_ids.e);
+    std::fill(h->rec_ids.e + rec->n_tracked, h->rec_ids.e + SSG_EVAL_REC_MAX_ENVS, 0);
+    h->rec.env_ids = h->rec_ids.e;
+    return SSG_OK;
+}
+
+int ssg_get_eval_recorder(const ssg_handle *h, ssg_eval_recorder *out)
+{
+    if (!h || !out) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_get_eval_recorder: NULL handle or out");
+    *out = h->rec;
+    return SSG_OK;
 }
 
 int ssg_obs_filter_workspace_nbytes(int n_envs, int obs_dim, int n_members, size_t *nbytes)
@@ -2738,6 +2812,22 @@ int ssg_render(ssg_handle *h, int env_index, int width, int height, uint8_t *dev
     if (rc != SSG_OK) return rc;
     hipError_t e = ssg::launch_render(h->dev, h->dyn, env_index, width, height, dev_rgb, flags, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("render launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+int ssg_render_envs(ssg_handle *h, const int32_t *dev_env_ids, int count, int width, int height, uint8_t *dev_rgb, uint32_t flags, void *stream)
+{
+    // ssg_render's checks in its order (the ids are on the device: the kernel skips a frame whose id is out of range)
+    if (!h) return SSG_ERR_BAD_ARG;
+    if (!dev_rgb || !dev_env_ids || width < 1 || height < 1 || width > 8192 || height > 8192)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_render_envs: bad argument");
+    if (count < 1 || count > SSG_RENDER_MAX_ENVS) return fail(h, SSG_ERR_BAD_ARG, "ssg_render_envs: count must be in 1..SSG_RENDER_MAX_ENVS");
+    if ((long long)count * width * height * 3 > (1ll << 31))
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_render_envs: count * width * height * 3 exceeds 2^31 bytes (render in blocks)");
+    int rc = check_ready(h, true);
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_render_envs(h->dev, h->dyn, dev_env_ids, count, width, height, dev_rgb, flags, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("render_envs launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
 

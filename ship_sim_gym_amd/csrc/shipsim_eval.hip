@@ -1,4 +1,5 @@
-// shipsim_eval.hip — episode accounting of an evaluation run: ssg_evaluate / ssg_pop_evaluate / ssg_eval_reduce (include/shipsim.h).
+// shipsim_eval.hip — episode accounting of an evaluation run: ssg_evaluate / ssg_pop_evaluate / ssg_eval_reduce (include/shipsim.h), and
+// the evaluation recorder's two row launches (ssg_set_eval_recorder; its frames are drawn in shipsim_render.hip).
 //
 // What the reference's train/rllib/rollout.py:8-26 does on the host for one env — add up the reward until done, print it — for every env
 // of a handle on the device, one small launch after every step: an env counts its FIRST E episodes and then stops counting, so every
@@ -88,7 +89,68 @@ __global__ void __launch_bounds__(kEvalBlock) eval_reduce_sliced_kernel(const in
     eval_reduce_body(row[1], stats + (size_t)row[0] * kEvalCols, out, red);
 }
 
+// The evaluation recorder (ssg_set_eval_recorder; what train/rllib/rollout.py:20-21 appends per step): one lane per slot, R <= 64 lanes,
+// one workgroup.  Both kernels read the carries the previous iteration's accounting launch left and the cursors the previous
+// iteration's record_step left, so they agree on which slots are active (eval_rec_step); neither touches anything of the handle's.
+constexpr int kRecBlock = SSG_EVAL_REC_MAX_ENVS;
+
+// ahead of the policy launch: the raw observation row the policy is about to read
+__global__ void __launch_bounds__(kRecBlock) eval_record_obs_kernel(const EvalRecLaunch r, const EvalRecIds ids, const double *__restrict__ dev_obs)
+{
+    const int s = threadIdx.x;
+    if (s >= r.R) return;
+    const int e = ids.e[s];
+    const int t = eval_rec_step(r, e, s);
+    if (t < 0) return;
+    const double *src = dev_obs + (size_t)e * r.D;
+    double *dst = r.obs + ((size_t)s * r.C + t) * r.D;
+    for (int d = 0; d < r.D; ++d) dst[d] = src[d];
+}
+
+// between the step and the accounting launch: the policy's outputs, the step's rows, next_obs, then the cursor; a full slot of an env
+// that still counts adds 1 to its overflow count instead
+__global__ void __launch_bounds__(kRecBlock) eval_record_step_kernel(const EvalRecLaunch r, const EvalRecIds ids, const double *__restrict__ dev_obs,
+                                                                    const int32_t *__restrict__ act, const float *__restrict__ logp,
+                                                                    const float *__restrict__ value, const double *__restrict__ rew,
+                                                                    const uint8_t *__restrict__ done, const uint8_t *__restrict__ flags)
+{
+    const int s = threadIdx.x;
+    if (s >= r.R) return;
+    const int e = ids.e[s];
+    if (r.carry[4 * (size_t)e + 2] >= r.E) return;
+    const int t = r.cursor[s];
+    if (t >= r.C) {
+        r.overflow[s] += 1;
+        return;
+    }
+    const size_t i = (size_t)s * r.C + t;
+    const uint8_t dn = done[e];
+    r.act[i] = act[e];
+    r.logp[i] = logp[e];
+    r.value[i] = value[e];
+    r.reward[i] = rew[e];
+    r.done[i] = dn;
+    r.flags[i] = flags[e];
+    const double *src = (dn ? r.term_obs : dev_obs) + (size_t)e * r.D;
+    double *dst = r.next_obs + i * r.D;
+    for (int d = 0; d < r.D; ++d) dst[d] = src[d];
+    r.cursor[s] = t + 1;
+}
+
 } // namespace
+
+hipError_t launch_eval_record_obs(const EvalRecLaunch &r, const EvalRecIds &ids, const double *dev_obs, hipStream_t stream)
+{
+    hipLaunchKernelGGL(eval_record_obs_kernel, dim3(1), dim3(kRecBlock), 0, stream, r, ids, dev_obs);
+    return hipGetLastError();
+}
+
+hipError_t launch_eval_record_step(const EvalRecLaunch &r, const EvalRecIds &ids, const double *dev_obs, const int32_t *act, const float *logp,
+                                   const float *value, const double *rew, const uint8_t *done, const uint8_t *flags, hipStream_t stream)
+{
+    hipLaunchKernelGGL(eval_record_step_kernel, dim3(1), dim3(kRecBlock), 0, stream, r, ids, dev_obs, act, logp, value, rew, done, flags);
+    return hipGetLastError();
+}
 
 hipError_t launch_eval_account(int N, int E, const double *rew, const uint8_t *done, const uint8_t *flags, double *carry_ret, int32_t *carry,
                                int64_t *stats, hipStream_t stream)

@@ -420,6 +420,42 @@ constexpr int kEvalCols = SSG_EVAL_STATS;
 hipError_t launch_eval_account(int N, int E, const double *rew, const uint8_t *done, const uint8_t *flags, double *carry_ret, int32_t *carry,
                                int64_t *stats, hipStream_t stream);
 hipError_t launch_eval_reduce(const MemberLayout &lay, const int64_t *stats, int64_t *out, hipStream_t stream);
+// the evaluation recorder (ssg_set_eval_recorder): what its launches need of the bound record and of the call.  The tracked env ids
+// travel by value (kernarg memory): the library's copy of the caller's host array.
+struct EvalRecIds {
+    int32_t e[SSG_EVAL_REC_MAX_ENVS];
+};
+struct EvalRecLaunch {
+    int R, C, D, E;          // slots, steps per slot, observation width, the call's episodes_per_env
+    const int32_t *carry;    // the call's dev_carry: int32 [N][4], [2] = episodes counted
+    int32_t *cursor, *overflow;
+    double *obs, *next_obs;
+    int32_t *act;
+    float *logp, *value;
+    double *reward;
+    uint8_t *done, *flags;
+    const double *term_obs;  // the record's rows, where the step kernel stored the terminal observations
+    uint8_t *frames;         // nullable
+    int fw, fh, fevery, fslots; // frame size, S, frames per slot = ceil(C / S)
+    unsigned fflags;
+};
+// the step index t = cursor[slot] an ACTIVE slot writes in this iteration, or -1: its env has counted E episodes, or the slot is full.
+// Nothing these launches write enters it, and the accounting launch comes after them: all of an iteration's launches agree.
+__device__ __forceinline__ int eval_rec_step(const EvalRecLaunch &r, int e, int slot)
+{
+    if (r.carry[4 * (size_t)e + 2] >= r.E) return -1;
+    const int t = r.cursor[slot];
+    return t < r.C ? t : -1;
+}
+// (shipsim_eval.hip) ahead of the policy launch: the active slots' rows of dev_obs; between the step and the accounting launch: the
+// policy's and the step's outputs for the active slots, next_obs, and the cursors
+hipError_t launch_eval_record_obs(const EvalRecLaunch &r, const EvalRecIds &ids, const double *dev_obs, hipStream_t stream);
+hipError_t launch_eval_record_step(const EvalRecLaunch &r, const EvalRecIds &ids, const double *dev_obs, const int32_t *act, const float *logp,
+                                   const float *value, const double *rew, const uint8_t *done, const uint8_t *flags, hipStream_t stream);
+// (shipsim_render.hip) `count` frames in one launch, frame i = env ids[i]; and the recorder's frames of the active slots, ahead of the step
+hipError_t launch_render_envs(const DevCfg &c, const DynCfg &d, const int32_t *ids, int count, int width, int height, uint8_t *rgb,
+                              unsigned flags, hipStream_t stream);
+hipError_t launch_eval_record_frames(const DevCfg &c, const DynCfg &d, const EvalRecLaunch &r, const EvalRecIds &ids, hipStream_t stream);
 // the observation filter (shipsim_filter.hip): 256-row tiles, staged at most kFltChunk columns at a time; the workspace holds launch 1's
 // partials, f64 [members][filter_tiles(widest slice)][2][D]
 constexpr int kFltTile = 256, kFltChunk = 31, kFltMaxDim = SSG_MAX_HISTORY * (6 + SSG_MAX_BEAMS);

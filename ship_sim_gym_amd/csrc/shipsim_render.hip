@@ -1,4 +1,5 @@
-// shipsim_render.hip — `rgb_array` frames of single envs (debugging / videos, not a hot path).
+// shipsim_render.hip — `rgb_array` frames: of one env (ssg_render), of many in one launch (ssg_render_envs), and of the evaluation
+// recorder's tracked envs (ssg_set_eval_recorder); one rasteriser behind all three (debugging / videos).
 //
 // Replaces ShipGame.render + get_screen (game.py:133-138,197-229): the screen is cleared to (0, 0, 200); in debug mode
 // pymunk's debug draw paints every shape of the space in insertion order with its colour — banks (139, 69, 19)
@@ -71,21 +72,37 @@ __device__ double seg_hull(const double *pl, int n, double ax, double ay, double
     return inside ? -1.0 : best;
 }
 
-} // namespace
+// what both halves of a frame read of env e
+struct RenderEnv {
+    double px, py, ang;
+    const double *rec;
+    unsigned gmask;
+};
 
-__global__ void render_kernel(const DevCfg c, const DynCfg d, int e, int width, int height, uint8_t *__restrict__ rgb,
-                              unsigned flags)
+__device__ __forceinline__ RenderEnv render_env(const DevCfg &c, int e)
 {
-    __shared__ double beam_x[SSG_MAX_BEAMS], beam_y[SSG_MAX_BEAMS];
-    __shared__ int beam_hit[SSG_MAX_BEAMS];
     const size_t np = (size_t)c.n_pad;
-    const double px = c.f64cols[(size_t)COL_X * np + e], py = c.f64cols[(size_t)COL_Y * np + e];
-    const double ang = c.f64cols[(size_t)COL_A * np + e];
-    const int map_id = c.i32cols[(size_t)ICOL_MAP * np + e];
-    const double *rec = c.bank + (size_t)map_id * SSG_MAP_STRIDE;
-    const unsigned gmask = c.mask[e];
-    const bool debug = flags & 1u;
-    if (debug && threadIdx.x < (unsigned)c.n_beams) {
+    RenderEnv v;
+    v.px = c.f64cols[(size_t)COL_X * np + e];
+    v.py = c.f64cols[(size_t)COL_Y * np + e];
+    v.ang = c.f64cols[(size_t)COL_A * np + e];
+    v.rec = c.bank + (size_t)c.i32cols[(size_t)ICOL_MAP * np + e] * SSG_MAP_STRIDE;
+    v.gmask = c.mask[e];
+    return v;
+}
+
+// the beam ends of one frame, in the workgroup's LDS
+struct RenderBeams {
+    double x[SSG_MAX_BEAMS], y[SSG_MAX_BEAMS];
+    int hit[SSG_MAX_BEAMS];
+};
+
+// Per workgroup, ahead of its pixels (the caller puts a __syncthreads() between the two): lane i < n_beams queries beam i.
+__device__ __forceinline__ void render_beams(const DevCfg &c, const RenderEnv &v, unsigned flags, RenderBeams &bm)
+{
+    const double px = v.px, py = v.py, ang = v.ang;
+    const double *rec = v.rec;
+    if ((flags & 1u) && threadIdx.x < (unsigned)c.n_beams) {
         // LiDAR.query on the current pose (models.py:39-76): origin = position + half the world AABB extents
         double sa, ca;
         sincos(ang, &sa, &ca);
@@ -102,11 +119,19 @@ __global__ void render_kernel(const DevCfg c, const DynCfg d, int e, int width, 
         for (int s = 0; s < 2 && alpha > 1.0; ++s) // first listed shape that reports a hit wins
             alpha = seg_hull(rec + SSG_MAP_OFF_PLANES + s * SSG_MAX_HULL * SSG_PLANE_DOUBLES, (int)rec[SSG_MAP_OFF_COUNTS + s], ox, oy, ex, ey);
         const double tt = (alpha >= 0.0 && alpha <= 1.0) ? alpha : 1.0; // a miss and an origin inside a hull both report the far end
-        beam_x[i] = ox + (ex - ox) * tt; beam_y[i] = oy + (ey - oy) * tt; beam_hit[i] = alpha <= 1.0;
+        bm.x[i] = ox + (ex - ox) * tt; bm.y[i] = oy + (ey - oy) * tt; bm.hit[i] = alpha <= 1.0;
     }
-    __syncthreads();
-    const int sx = blockIdx.x * blockDim.x + threadIdx.x, sy = blockIdx.y;
-    if (sx >= width) return;
+}
+
+// Pixel (sx, sy) of env e's frame into rgb ([width][height][3]); sx < width is the caller's check.
+__device__ __forceinline__ void render_pixel(const DevCfg &c, const DynCfg &d, int e, const RenderEnv &v, int width, int height, int sx, int sy,
+                                             uint8_t *__restrict__ rgb, unsigned flags, const RenderBeams &bm)
+{
+    const size_t np = (size_t)c.n_pad;
+    const double px = v.px, py = v.py, ang = v.ang;
+    const double *rec = v.rec;
+    const unsigned gmask = v.gmask;
+    const bool debug = flags & 1u;
     // pixel centre -> world point (screen y points down)
     const double x = (sx + 0.5) * (c.width / width), y = c.height - (sy + 0.5) * (c.height / height);
     uint8_t R = 0, G = 0, B = 200; // screen.fill((0, 0, 200))
@@ -128,8 +153,8 @@ __global__ void render_kernel(const DevCfg c, const DynCfg d, int e, int width, 
                 if (in_ship(d.thull[k], d.tnrm[k], t[0], t[np], t[2 * np], x, y)) { R = 0; G = 0; B = 0; }
             }
         for (int i = 0; i < c.n_beams; ++i) {
-            const double ddx = x - beam_x[i], ddy = y - beam_y[i];
-            if (ddx * ddx + ddy * ddy <= 100.0) { R = beam_hit[i] ? 255 : 0; G = beam_hit[i] ? 0 : 255; B = 0; }
+            const double ddx = x - bm.x[i], ddy = y - bm.y[i];
+            if (ddx * ddx + ddy * ddy <= 100.0) { R = bm.hit[i] ? 255 : 0; G = bm.hit[i] ? 0 : 255; B = 0; }
         }
     }
     if ((x - px) * (x - px) + (y - py) * (y - py) <= 100.0) { R = 255; G = 255; B = 0; }
@@ -137,12 +162,73 @@ __global__ void render_kernel(const DevCfg c, const DynCfg d, int e, int width, 
     o[0] = R; o[1] = G; o[2] = B;
 }
 
+// One frame's share of a workgroup: grid x = 128-pixel column blocks, grid y = rows; every lane takes part in the beam set-up.
+__device__ __forceinline__ void render_frame(const DevCfg &c, const DynCfg &d, int e, int width, int height, uint8_t *__restrict__ rgb,
+                                             unsigned flags, RenderBeams &bm)
+{
+    const RenderEnv v = render_env(c, e);
+    render_beams(c, v, flags, bm);
+    __syncthreads();
+    const int sx = blockIdx.x * blockDim.x + threadIdx.x, sy = blockIdx.y;
+    if (sx >= width) return;
+    render_pixel(c, d, e, v, width, height, sx, sy, rgb, flags, bm);
+}
+
+constexpr int kRenderBlock = 128;
+
+} // namespace
+
+__global__ void render_kernel(const DevCfg c, const DynCfg d, int e, int width, int height, uint8_t *__restrict__ rgb,
+                              unsigned flags)
+{
+    __shared__ RenderBeams bm;
+    render_frame(c, d, e, width, height, rgb, flags, bm);
+}
+
+// grid z = frame: frame i shows env ids[i]; an id outside 0 .. n_envs-1 leaves its frame unwritten (uniform over the workgroup)
+__global__ void render_envs_kernel(const DevCfg c, const DynCfg d, const int32_t *__restrict__ ids, int width, int height,
+                                   uint8_t *__restrict__ rgb, unsigned flags)
+{
+    __shared__ RenderBeams bm;
+    const int e = ids[blockIdx.z];
+    if (e < 0 || e >= c.n_envs) return;
+    render_frame(c, d, e, width, height, rgb + (size_t)blockIdx.z * width * height * 3, flags, bm);
+}
+
+// the evaluation recorder's frames (ssg_set_eval_recorder), ahead of the step: grid z = slot; an active slot whose step index t is a
+// multiple of S draws its env into frame t / S of the slot (uniform over the workgroup)
+__global__ void eval_record_frames_kernel(const DevCfg c, const DynCfg d, const EvalRecLaunch r, const EvalRecIds ids)
+{
+    __shared__ RenderBeams bm;
+    const int s = blockIdx.z, e = ids.e[s];
+    const int t = eval_rec_step(r, e, s);
+    if (t < 0 || t % r.fevery != 0) return;
+    render_frame(c, d, e, r.fw, r.fh, r.frames + ((size_t)s * r.fslots + t / r.fevery) * ((size_t)r.fw * r.fh * 3), r.fflags, bm);
+}
+
+static dim3 render_grid(int width, int height, int frames)
+{
+    return dim3((unsigned)((width + kRenderBlock - 1) / kRenderBlock), (unsigned)height, (unsigned)frames);
+}
+
 hipError_t launch_render(const DevCfg &c, const DynCfg &d, int e, int width, int height, uint8_t *rgb, unsigned flags,
                          hipStream_t stream)
 {
-    const int block = 128;
-    hipLaunchKernelGGL(render_kernel, dim3((unsigned)((width + block - 1) / block), (unsigned)height), dim3(block), 0, stream, c, d,
-                       e, width, height, rgb, flags);
+    hipLaunchKernelGGL(render_kernel, render_grid(width, height, 1), dim3(kRenderBlock), 0, stream, c, d, e, width, height, rgb, flags);
+    return hipGetLastError();
+}
+
+hipError_t launch_render_envs(const DevCfg &c, const DynCfg &d, const int32_t *ids, int count, int width, int height, uint8_t *rgb,
+                              unsigned flags, hipStream_t stream)
+{
+    hipLaunchKernelGGL(render_envs_kernel, render_grid(width, height, count), dim3(kRenderBlock), 0, stream, c, d, ids, width, height, rgb,
+                       flags);
+    return hipGetLastError();
+}
+
+hipError_t launch_eval_record_frames(const DevCfg &c, const DynCfg &d, const EvalRecLaunch &r, const EvalRecIds &ids, hipStream_t stream)
+{
+    hipLaunchKernelGGL(eval_record_frames_kernel, render_grid(r.fw, r.fh, r.R), dim3(kRenderBlock), 0, stream, c, d, r, ids);
     return hipGetLastError();
 }
 

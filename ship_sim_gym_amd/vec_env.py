@@ -512,8 +512,9 @@ class ShipVecEnv(*_BASES):
         * ring_ready, ring_seed, ring_width_frac, ring_credit, off_ring_*: map_ring only (map_mode="fresh_device");
         * time_kernels, t_dyn_ms, t_step_ms, t_steps: a measurement aid's accumulators;
         * host_ev, host_ev_made: completion events of the numpy protocols' copies; no step may be in flight (checked);
-        * pop_sizes, dev_slices, slice_max, slice_min, flt, tob, adv_norm_*: bindings (population slices, observation filter,
-          time-out bootstrap, advantage normalisation) that their owners bind again; their own state is their owners';
+        * pop_sizes, dev_slices, slice_max, slice_min, flt, tob, rec, rec_ids, adv_norm_*: bindings (population slices, observation
+          filter, time-out bootstrap, evaluation recorder, advantage normalisation) that their owners bind again; their own state is
+          their owners';
         * err: the last error's text.
         Not saved either: ``term_obs`` and the time-out bootstrap's rows, which a step or a rollout writes before anyone reads them."""
         self.check_snapshot_supported("snapshot")
@@ -1099,6 +1100,23 @@ class ShipVecEnv(*_BASES):
                                        self._stream()), self._h, "ssg_render")
         return img
 
+    def get_screens(self, envs, width=None, height=None, debug=True):
+        """get_screen for several envs in ONE launch (ssg_render_envs): uint8 [len(envs), width, height, 3], frame i bit for bit
+        get_screen(envs[i]).  envs: a sequence of env indices, or an int32 device tensor of them; at most RENDER_MAX_ENVS frames and
+        2^31 bytes per call.  An index outside 0 .. num_envs-1 leaves its frame unwritten (the ids are only read on the device)."""
+        torch = _torch()
+        width = int(width or self.bounds[0])
+        height = int(height or self.bounds[1])
+        with torch.cuda.device(self.device):
+            if torch.is_tensor(envs):
+                ids = envs.to(device=self.device, dtype=torch.int32).contiguous().reshape(-1)
+            else:
+                ids = torch.tensor([int(e) for e in envs], dtype=torch.int32, device=self.device)
+            out = torch.empty((ids.numel(), width, height, 3), dtype=torch.uint8, device=self.device)
+            N.check(N.lib().ssg_render_envs(self._h, C.c_void_p(ids.data_ptr()), ids.numel(), width, height, C.c_void_p(out.data_ptr()),
+                                            1 if debug else 0, self._stream()), self._h, "ssg_render_envs")
+        return out
+
     def render(self, mode='human', close=False, env=0):
         """ShipEnv.render (ship_env.py:158-168) only writes a text line (done by the ShipEnv facade); 'rgb_array'
         returns the frame the reference's screen would hold, as a numpy array [H, W, 3]."""
@@ -1142,7 +1160,15 @@ class ShipVecEnv(*_BASES):
         return [False for _ in self._indices(indices)]
 
     def get_images(self):
-        return [self.render(mode='rgb_array', env=i) for i in range(self.num_envs)]
+        """render('rgb_array') of every env, as a list of [H, W, 3] arrays: one launch and one device-to-host copy per block of envs
+        (get_screens; a block holds at most 64 MiB of frames) instead of one of each per env."""
+        frame_bytes = int(self.bounds[0]) * int(self.bounds[1]) * 3
+        block = max(1, min(N.RENDER_MAX_ENVS, (64 << 20) // frame_bytes))
+        images = []
+        for start in range(0, self.num_envs, block):
+            frames = self.get_screens(range(start, min(start + block, self.num_envs))).cpu()
+            images.extend(frames[i].permute(1, 0, 2).numpy() for i in range(frames.shape[0]))
+        return images
 
     @property
     def unwrapped(self):

@@ -12,6 +12,10 @@ bound where the kernel is shorter than the host call (`rocprofv3 --kernel-trace 
 One JSON line on stdout.
 
     python tools/eval_timing.py [--envs 65536,4096] [--steps 64] [--repeats 5]
+
+``--record R [--frame-size WxH]`` times the evaluation recorder (ssg_set_eval_recorder) instead: the greedy evaluation step with
+nothing bound, with R tracked envs, and with R tracked envs and WxH frames (default 64x64), alternating in one process
+(measure_record).
 """
 import argparse
 import importlib.util
@@ -88,14 +92,64 @@ def measure(mod, n, steps, repeats, dev):
             "repeats_us": {k: [round(t, 2) for t in v] for k, v in times.items()}}
 
 
+def measure_record(mod, n, steps, repeats, dev, R, size):
+    """The greedy evaluation step with nothing bound, with R tracked envs (evenly spaced over the handle) and with R tracked envs
+    and frames of `size`, alternating, on ONE env; the capacity is the call's step count and the cursors are zeroed ahead of every
+    call (outside the timed region), so every slot writes a row — and a frame, S = 1 — at every step: the recorder's most expensive
+    case.  Median us per step per case and every repeat."""
+    from ship_sim_gym_amd.evaluate import EvalRecorder
+    torch.manual_seed(0)
+    env = mod.ShipVecEnv(n, mod.GameConfig, mod.EnvConfig, device=dev, n_maps=64)
+    D, A = env.states_history, env.action_space.n
+    net = mod.ActorCritic(D, A).to(dev)
+    scale = torch.full((D,), float(max(env.bounds)), dtype=torch.float64, device=dev)
+    policy = mod.NativePolicy.from_actor_critic(net, scale)
+    env.reset_tensor()
+    ev = NativeEvaluator(env)
+    ids = [i * n // R for i in range(R)]
+    recorders = {"nothing_bound": None, "tracked": EvalRecorder(env, ids, steps), "tracked_frames": EvalRecorder(env, ids, steps, frames=size)}
+    quota = 1 << 30
+
+    def call(rec):
+        if rec is not None:
+            rec.reset()
+        torch.cuda.synchronize()
+        return _timed(lambda: ev.run(policy, quota, steps, greedy=True, recorder=rec)) / steps
+
+    for _ in range(2):
+        for rec in recorders.values():
+            call(rec)
+    times = {k: [] for k in recorders}
+    for _ in range(repeats):
+        for k, rec in recorders.items():
+            times[k].append(call(rec))
+    assert all(int(c) == steps for k in ("tracked", "tracked_frames") for c in recorders[k].steps)  # every slot wrote every step
+    med = {k: statistics.median(v) for k, v in times.items()}
+    env.close()
+    return {"envs": n, "obs_dim": D, "steps": steps, "tracked": R, "frame_size": list(size),
+            "nothing_bound_us_per_step": round(med["nothing_bound"], 2), "tracked_us_per_step": round(med["tracked"], 2),
+            "tracked_frames_us_per_step": round(med["tracked_frames"], 2),
+            "tracked_minus_nothing_us": round(med["tracked"] - med["nothing_bound"], 2),
+            "frames_minus_tracked_us": round(med["tracked_frames"] - med["tracked"], 2),
+            "repeats_us": {k: [round(t, 2) for t in v] for k, v in times.items()}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", default="65536,4096")
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--record", type=int, default=0, metavar="R",
+                    help="time the evaluation step with nothing bound, with R tracked envs and with R tracked envs and frames instead")
+    ap.add_argument("--frame-size", default="64x64", metavar="WxH", help="of --record's frames")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     mod = _ppo()
+    if a.record:
+        size = tuple(int(t) for t in a.frame_size.lower().split("x"))
+        res = [measure_record(mod, int(n), a.steps, a.repeats, "cuda:0", a.record, size) for n in a.envs.split(",")]
+        print(json.dumps({"tool": "eval_timing --record", "device": torch.cuda.get_device_name(0), "results": res}))
+        return
     res = [measure(mod, int(n), a.steps, a.repeats, "cuda:0") for n in a.envs.split(",")]
     print(json.dumps({"tool": "eval_timing", "device": torch.cuda.get_device_name(0), "results": res}))
 

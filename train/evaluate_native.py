@@ -4,6 +4,8 @@ done, "Episode reward"), and the ``model.predict(obs, deterministic=True)`` loop
 
     python train/evaluate_native.py --envs 4096 --episodes 4 [--checkpoint FILE [--member M]] [--sampled] [--separate-value] [--seed 0]
                                      [--obs-filter FILE]
+                                     [--record-envs 0,5,17 [--out FILE] [--frames FILE.npz [--frame-size WxH] [--frame-every S]]
+                                      [--record-steps C]]
 
 ``--checkpoint FILE`` is a checkpoint of train/ppo_torch.py or train/pbt_native.py (``--save`` / ``--save-best``;
 ship_sim_gym_amd/checkpoint.py): the architecture comes from the file (``--separate-value`` is unnecessary, and refused when it
@@ -21,7 +23,16 @@ exclusive of each other) and goals per episode.
 ``--obs-filter FILE``: normalise the observations with the running mean / std statistics a training run saved (train/ppo_torch.py
 ``--save-obs-filter``), frozen — an evaluation never updates them — instead of the fixed division by the largest bound.
 
-Out of scope here: recording trajectories (rollout.py --out) and rendering during evaluation.
+``--record-envs 0,5,17`` records those envs' counted steps on the device while the evaluation runs (ship_sim_gym_amd/evaluate.py,
+EvalRecorder) and prints one ``Episode reward`` line per recorded episode, as rollout.py:26 does.  ``--out FILE`` pickles
+[state, action, next_state, reward, done] per step, a list per episode, as rollout.py --out writes it (rollout.py:20-28); next_state
+of a done step is the episode's terminal observation.  ``--frames FILE.npz`` saves one uint8 array [T', H, W, 3] per recorded episode
+(``episode_0000`` ...), a frame for every ``--frame-every``-th kept step of ``--frame-size`` pixels (default 128x128), each drawn
+before its step: what the agent saw when it acted.  ``--record-steps C`` bounds the steps kept per env (default episodes *
+max_steps, which always suffices); a slot that ran full is reported.
+
+Out of scope here: the frame after a crash (a done env is reset inside the step, so the next frame shows the new episode), a video
+encoder, and recording during training rollouts.
 """
 import argparse
 import os
@@ -35,6 +46,26 @@ def _positive(text):
     if v < 1:
         raise argparse.ArgumentTypeError("must be >= 1 (got %s)" % text)
     return v
+
+
+def _env_list(text):
+    try:
+        ids = [int(t) for t in text.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError("a comma-separated list of env indices (got %s)" % text)
+    if not ids or min(ids) < 0 or len(set(ids)) != len(ids):
+        raise argparse.ArgumentTypeError("distinct env indices >= 0 (got %s)" % text)
+    return ids
+
+
+def _size(text):
+    try:
+        w, h = (int(t) for t in text.lower().split("x"))
+    except ValueError:
+        raise argparse.ArgumentTypeError("WxH, e.g. 128x128 (got %s)" % text)
+    if not (1 <= w <= 8192 and 1 <= h <= 8192):
+        raise argparse.ArgumentTypeError("width and height must be in 1..8192 (got %s)" % text)
+    return w, h
 
 
 def make_arg_parser():
@@ -51,6 +82,12 @@ def make_arg_parser():
     ap.add_argument("--seed", type=int, default=0, help="of the random weights and of the sampled actions")
     ap.add_argument("--obs-filter", default=None, metavar="FILE",
                     help="observation filter statistics saved by train/ppo_torch.py --save-obs-filter (applied frozen); default: obs / max bound")
+    ap.add_argument("--record-envs", type=_env_list, default=None, metavar="0,5,17", help="record these envs' trajectories on the device")
+    ap.add_argument("--out", default=None, metavar="FILE", help="pickle the recorded episodes as rollout.py --out does (needs --record-envs)")
+    ap.add_argument("--frames", default=None, metavar="FILE.npz", help="save one uint8 [T', H, W, 3] array per recorded episode (needs --record-envs)")
+    ap.add_argument("--frame-size", type=_size, default=(128, 128), metavar="WxH")
+    ap.add_argument("--frame-every", type=_positive, default=1, metavar="S", help="a frame for every S-th kept step")
+    ap.add_argument("--record-steps", type=_positive, default=None, metavar="C", help="steps kept per recorded env (default episodes * max_steps)")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -60,19 +97,23 @@ def parse_args(argv=None):
 
 
 def evaluate(envs=4096, episodes=4, checkpoint=None, sampled=False, separate_value=False, seed=0, device="cuda:0", log=print, obs_filter=None,
-             member=None, env_kw=None):
+             member=None, env_kw=None, record_envs=None, out=None, frames=None, frame_size=(128, 128), frame_every=1, record_steps=None):
     import torch
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     from ppo_torch import ActorCritic
     from ship_gym.config import EnvConfig, GameConfig
     from ship_sim_gym_amd import checkpoint as ckpt_mod
-    from ship_sim_gym_amd.evaluate import NativeEvaluator, format_table
+    from ship_sim_gym_amd.evaluate import EvalRecorder, NativeEvaluator, format_table
     from ship_sim_gym_amd.obs_filter import ObsFilter
     from ship_sim_gym_amd.policy import NativePolicy
     from ship_sim_gym_amd.population import NativePopulation
     from ship_sim_gym_amd.vec_env import ShipVecEnv
     torch.manual_seed(seed)
     env_kw = dict(env_kw or {})
+    if (out is not None or frames is not None) and not record_envs:
+        raise ValueError("evaluate: out and frames save what record_envs records; no env was named")
+    if record_envs and max(record_envs) >= envs:
+        raise ValueError("evaluate: record_envs names env %d of %d" % (max(record_envs), envs))
     ckpt = None
     if checkpoint is not None:
         content = ckpt_mod.read(checkpoint)  # (a checkpoint and a module's state_dict both load without running any code of the file's)
@@ -120,17 +161,46 @@ def evaluate(envs=4096, episodes=4, checkpoint=None, sampled=False, separate_val
     if filter_sd is not None:
         flt = ObsFilter(env, n_members=int(filter_sd["n_members"]), update=False).load_state_dict(filter_sd)
         env.set_obs_filter(flt)
-    result = NativeEvaluator(env).evaluate(policy, episodes, greedy=not sampled, seed=seed)
+    recorder = None
+    if record_envs:
+        recorder = EvalRecorder(env, record_envs, record_steps or episodes * int(env.cfg.max_steps),
+                                frames=frame_size if frames is not None else None, frame_every=frame_every)
+    result = NativeEvaluator(env).evaluate(policy, episodes, greedy=not sampled, seed=seed, recorder=recorder)
     log(format_table(result))
     if not result["complete"]:
         log("(some env did not finish %d episodes within %d steps)" % (episodes, result["steps"]))
-    out = {k: v for k, v in result.items() if k not in ("per_env", "per_member")}
-    out["per_member"] = result["per_member"].cpu().numpy().copy()
+    res = {k: v for k, v in result.items() if k not in ("per_env", "per_member")}
+    res["per_member"] = result["per_member"].cpu().numpy().copy()
+    if recorder is not None:
+        save_recording(recorder, out, frames, log)
     env.close()
-    return out
+    return res
+
+
+def save_recording(recorder, out, frames, log):
+    """One "Episode reward" line per recorded episode (rollout.py:26), a warning per slot that ran full, the pickle and the frames."""
+    import pickle
+    import numpy as np
+    per_slot = recorder.episodes()
+    for e, eps in zip(recorder.env_ids, per_slot):
+        for ep in eps:
+            total = 0.0
+            for r in ep["reward"]:  # (summed in order, as rollout.py:17 does)
+                total += float(r)
+            log("Episode reward %r (env %d, %d steps%s)" % (total, e, len(ep["reward"]), "" if ep["complete"] else ", incomplete"))
+    for e, lost in zip(recorder.env_ids, recorder.overflow):
+        if lost:
+            log("warning: env %d counted %d steps past the %d kept (--record-steps)" % (e, lost, recorder.capacity))
+    if out is not None:
+        with open(out, "wb") as f:
+            pickle.dump(recorder.as_rollouts(), f)
+    if frames is not None:
+        arrays = {"episode_%04d" % i: ep["frames"] for i, ep in enumerate(ep for eps in per_slot for ep in eps)}
+        np.savez(frames, **arrays)
 
 
 if __name__ == "__main__":
     a = parse_args()
     evaluate(envs=a.envs, episodes=a.episodes, checkpoint=a.checkpoint, sampled=a.sampled, separate_value=a.separate_value, seed=a.seed,
-             device=a.device, obs_filter=a.obs_filter, member=a.member)
+             device=a.device, obs_filter=a.obs_filter, member=a.member, record_envs=a.record_envs, out=a.out, frames=a.frames,
+             frame_size=a.frame_size, frame_every=a.frame_every, record_steps=a.record_steps)
