@@ -1042,6 +1042,78 @@ int ssg_set_eval_recorder(ssg_handle *h, const ssg_eval_recorder *rec /* NULL un
 int ssg_get_eval_recorder(const ssg_handle *h, ssg_eval_recorder *out /* struct_size 0: nothing bound */);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Episode log (addition to ABI 9): every finished TRAINING episode on record, in a ring on the device
+ * The reference's Stable-Baselines script wraps its envs in Monitor and reads the per-episode (r, l, t) rows back with load_results /
+ * ts2xy (train/stable_baselines/ppo.py:7-8,38-40): its callback plots return against timesteps and keeps the best model by
+ * np.mean(y[-100:]), the mean of the last 100 episodes (train/stable_baselines/ppo.py:25-52).  ssg_pop_episode_stats and the handle's
+ * counters give one sum per update; this keeps the episodes themselves.  Nothing is bound to the handle: the record below and all of
+ * its buffers are the caller's, as with ssg_eval_recorder, and a call reads the [K][N] reward / done / flags rows a rollout left.
+ *
+ * Per-env carry, caller-owned, zero after a reset: dev_carry_return f64 [N] (the running episode's return) and dev_carry int32 [N][2] =
+ * (length, goal events of the running episode).  Every step adds the reward to the return (in step order, in f64, as
+ * ssg_pop_episode_stats adds it), 1 to the length and 1 to the goal events when the step's flags have SSG_EV_GOAL_REACHED; a done step
+ * appends one ssg_episode_record and zeroes the three.  An episode still running when a call ends stays in the carry.
+ *
+ * The order contract.  The episodes that end in one call are ranked by (t ascending, then env ascending): the order of
+ * np.nonzero(done) on the [K, N] array.  With head = dev_head[0] before the call and count = the episodes the call ends, the episode of
+ * rank r goes to slot (head + r) % capacity.  When count > capacity, the records of rank below count - capacity are not written at all
+ * (later ranks of the same call own their slots), so two ranks never race for a slot.  Then dev_head[0] = head + count and
+ * dev_head[1] = count.  The ring and the head depend on the inputs alone — not on the launch geometry, not on the member layout (only
+ * the member bits of `end` do), not on how a sequence of steps is cut into calls: two calls over K1 and then K2 rows leave, bit for bit,
+ * the ring, dev_head[0] and the carries that one call over the K1 + K2 rows leaves (dev_head[1] is the last call's own count).
+ *
+ * Launches: three on `stream`, always — no atomics, no host synchronisation.  (a) count: one workgroup per (row, 256-env tile) counts the
+ * tile's done bytes of that row (wave ballots and popcounts) into the workspace's counts[t * tiles + tile]; (b) scan: ONE workgroup
+ * turns counts into its exclusive prefix sums in index order (integers: exact), copies dev_head[0] and the total into the workspace and
+ * advances dev_head; (c) walk: one lane per env walks t = 0 .. K-1 with its carries, eight rows loaded at a time; at a done step its
+ * rank is the scanned entry of (t, tile) plus its rank among the tile's done lanes of that row (a ballot prefix per wave; the four
+ * waves' counts meet in LDS, one barrier per eight rows), and it writes its record with two 16-byte vector stores.  The walk reads the
+ * old head from the workspace, never from dev_head.
+ * The member of env e is e / (N / n_members) on equal slices and a binary search of the slices table otherwise, once per lane.
+ * One call at a time per workspace.
+ * ------------------------------------------------------------------------------------------------- */
+#define SSG_EPISODE_LOG_MAX_CELLS (1 << 22) /* K * ceil(n_envs / 256) of one call at most: what the one scanning workgroup takes on */
+typedef struct ssg_episode_record {
+    double ret;      /* the episode's return: carry + rew[t0] + ... + rew[t], added in step order in f64 */
+    int64_t step;    /* step0 + t of its done step */
+    int32_t env;     /* global env id: the handle's env_id_base + e */
+    int32_t length;  /* steps, carried across calls */
+    int32_t goals;   /* steps of the episode whose flags had SSG_EV_GOAL_REACHED (0 when dev_flags_KN is NULL) */
+    uint32_t end;    /* low byte: the done step's flags byte (0 when NULL); bits 8..15: the member that owns the env */
+} ssg_episode_record;
+
+typedef struct ssg_episode_log {
+    uint32_t struct_size;            /* sizeof(ssg_episode_log) */
+    int32_t n_members;               /* 1 for a single policy, P for a population (equal split or the ssg_pop_set_slices layout) */
+    int64_t capacity;                /* slots of the ring, >= 1 */
+    ssg_episode_record *dev_records; /* [capacity], 16-byte aligned; need not be initialised */
+    int64_t *dev_head;               /* int64 [2], caller-zeroed: [0] episodes ever appended, [1] episodes appended by the last call */
+    double *dev_carry_return;        /* f64 [n_envs] */
+    int32_t *dev_carry;              /* int32 [n_envs][2]: length, goal events; 8-byte aligned */
+    void *dev_workspace;             /* >= ssg_episode_log_workspace_nbytes(n_envs, K) bytes, 16-byte aligned */
+    size_t workspace_nbytes;
+} ssg_episode_log;
+
+/* Replaces nothing (host only; Monitor appends to a file as it goes).  The workspace of ssg_episode_log_append for a handle of n_envs
+ * envs and calls of up to K rows: int64 [2] (the head before the call, the call's count), then int32 [K * ceil(n_envs / 256)] (the
+ * counts, scanned in place) — 16 + 4 * K * ceil(n_envs / 256) bytes.  SSG_ERR_BAD_ARG for NULL nbytes, an argument < 1 or
+ * K * ceil(n_envs / 256) above SSG_EPISODE_LOG_MAX_CELLS. */
+int ssg_episode_log_workspace_nbytes(int n_envs, int K, size_t *nbytes);
+
+/* Replaces: Monitor's per-episode (r, l, t) rows, read by load_results / ts2xy in train/stable_baselines/ppo.py:7-8,38-40 — for the K
+ * rows of a rollout at once, as described above: three launches on `stream`.  dev_reward_KN / dev_done_KN / dev_flags_KN: the rollout's
+ * f64 / u8 / u8 [K][step_stride_envs] buffers in the handle's row layout (what ssg_rollout_policy / ssg_pop_rollout wrote); with
+ * dev_flags_KN NULL every record has goals = 0 and a zero low byte of `end`.  Row t is step step0 + t.  The arguments are judged first,
+ * then the handle (SSG_ERR_NOT_BOUND without a state blob, like every call that launches).  Refuses (SSG_ERR_BAD_ARG, nothing launched,
+ * head and ring untouched): a NULL handle or record; struct_size mismatch; capacity < 1; n_members outside 1..SSG_POP_MAX_MEMBERS,
+ * different from a bound slices layout, or one the handle's envs do not split into; NULL dev_records, dev_head, dev_carry_return,
+ * dev_carry or dev_workspace; a dev_records or dev_workspace that is not 16-byte aligned, a dev_carry that is not 8-byte aligned;
+ * K < 1; K * ceil(n_envs / 256) above SSG_EPISODE_LOG_MAX_CELLS; step_stride_envs < n_envs; NULL dev_reward_KN or dev_done_KN;
+ * workspace_nbytes below ssg_episode_log_workspace_nbytes(n_envs, K). */
+int ssg_episode_log_append(ssg_handle *h, const ssg_episode_log *log, int K, int64_t step0, const double *dev_reward_KN,
+                           const uint8_t *dev_done_KN, const uint8_t *dev_flags_KN /* nullable */, int64_t step_stride_envs, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Observation filter (ABI 9 addition): a running mean / std per observation column, kept and applied on the device
  * The reference's RLlib trainers run "PPO" with its defaults (train/rllib/pbt.py:50, train/rllib/ppo.py:28), which in the RLlib
  * generation those scripts are written for include observation_filter = "MeanStdFilter"; Stable-Baselines users wrap the SubprocVecEnv

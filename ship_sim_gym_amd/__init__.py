@@ -7,7 +7,7 @@ gym / VecEnv / VectorEnv facades.  All stepping runs in hand-written gfx950 HIP 
 from .config import EnvConfig, GameConfig, LidarConfig  # noqa: F401
 from .curriculum import Curriculum  # noqa: F401
 
-__all__ = ["EnvConfig", "GameConfig", "LidarConfig", "Curriculum", "ShipEnv", "ShipVecEnv"]
+__all__ = ["EnvConfig", "GameConfig", "LidarConfig", "Curriculum", "ShipEnv", "ShipVecEnv", "EpisodeLog", "MonitorWriter"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require torch or the built library
@@ -17,4 +17,7 @@ def __getattr__(name):  # lazy: importing the package must not require torch or 
     if name == "ShipEnv":
         from .ship_env import ShipEnv
         return ShipEnv
+    if name in ("EpisodeLog", "MonitorWriter"):
+        from . import episode_log
+        return getattr(episode_log, name)
     raise AttributeError(name)

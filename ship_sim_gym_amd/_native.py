@@ -79,10 +79,12 @@ EXPORTS = (
     "ssg_set_timeout_boot", "ssg_get_timeout_boot", "ssg_timeout_values", "ssg_pop_timeout_values", "ssg_ppo_gae_boot", "ssg_pop_gae_boot",
     "ssg_ppo_adv_moments", "ssg_ppo_set_adv_moments", "ssg_ppo_apply_shards",
     "ssg_render_envs", "ssg_set_eval_recorder", "ssg_get_eval_recorder",
+    "ssg_episode_log_workspace_nbytes", "ssg_episode_log_append",
 )
 RENDER_MAX_ENVS = 4096  # frames of one ssg_render_envs launch at most
 EVAL_REC_MAX_ENVS = 64  # tracked envs of an evaluation recorder at most
 DP_MAX_SHARDS = 64  # ssg_ppo_shards.n_shards at most
+EPISODE_LOG_MAX_CELLS = 1 << 22  # K * ceil(n_envs / 256) of one ssg_episode_log_append call at most
 
 
 class ShipSimError(RuntimeError):
@@ -196,6 +198,23 @@ class EvalRecorderRecord(C.Structure):
         ("dev_logp", C.c_void_p), ("dev_value", C.c_void_p), ("dev_reward", C.c_void_p), ("dev_done", C.c_void_p),
         ("dev_flags", C.c_void_p), ("dev_cursor", C.c_void_p), ("dev_overflow", C.c_void_p), ("dev_term_obs", C.c_void_p),
         ("dev_frames", C.c_void_p),
+    ]
+
+
+class EpisodeRecord(C.Structure):
+    """ssg_episode_record (addition to ABI 9): one finished episode, 32 bytes (episode_log.RECORD_DTYPE is the numpy view of it)."""
+    _fields_ = [
+        ("ret", C.c_double), ("step", C.c_int64), ("env", C.c_int32), ("length", C.c_int32), ("goals", C.c_int32), ("end", C.c_uint32),
+    ]
+
+
+class EpisodeLogRecord(C.Structure):
+    """ssg_episode_log (addition to ABI 9): the ring [capacity] of ssg_episode_record and its head int64 [2], the per-env carries (f64
+    [n_envs]; int32 [n_envs][2]) and the workspace — all the caller's, on the device."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_members", C.c_int32), ("capacity", C.c_int64), ("dev_records", C.c_void_p),
+        ("dev_head", C.c_void_p), ("dev_carry_return", C.c_void_p), ("dev_carry", C.c_void_p), ("dev_workspace", C.c_void_p),
+        ("workspace_nbytes", C.c_size_t),
     ]
 
 
@@ -329,6 +348,8 @@ def lib():
     L.ssg_render_envs.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, vp]
     L.ssg_set_eval_recorder.argtypes = [vp, C.POINTER(EvalRecorderRecord)]
     L.ssg_get_eval_recorder.argtypes = [vp, C.POINTER(EvalRecorderRecord)]
+    L.ssg_episode_log_workspace_nbytes.argtypes = [C.c_int, C.c_int, szp]
+    L.ssg_episode_log_append.argtypes = [vp, C.POINTER(EpisodeLogRecord), C.c_int, C.c_int64, vp, vp, vp, C.c_int64, vp]
     L.ssg_dyn_invalidate.argtypes = [vp, vp, vp]
     L.ssg_host_convex_hull.argtypes = [C.c_int, dp, dp, ip]
     L.ssg_host_moment_for_poly.argtypes = [C.c_double, C.c_int, dp, dp]

@@ -8,6 +8,7 @@ can be read without trusting it:
     trainer               NativePPO.state_dict() or PopulationPPO.state_dict()
     obs_filter            ObsFilter.state_dict()
     ret_filter            ReturnFilter.state_dict()
+    episode_log           EpisodeLog.state_dict()
     env                   ShipVecEnv.snapshot()
     scheduler             PBTScheduler.state_dict()
     loop                  the trainer script's own state (the last finished update, its generator, its history, the best score)
@@ -21,7 +22,7 @@ import os
 
 FORMAT = "ssg-checkpoint"
 VERSION = 1
-SECTIONS = ("policy", "population", "trainer", "obs_filter", "ret_filter", "env", "scheduler", "loop", "config")
+SECTIONS = ("policy", "population", "trainer", "obs_filter", "ret_filter", "episode_log", "env", "scheduler", "loop", "config")
 
 
 def _torch():

@@ -2657,6 +2657,68 @@ int ssg_ret_filter_apply(ssg_handle *h, const ssg_ret_filter *f, int K, const do
     return SSG_OK;
 }
 
+// ABI 9 addition: the episode log.  Everything the host can judge comes first (BAD_ARG), then the handle's state blob and the device.
+int ssg_episode_log_workspace_nbytes(int n_envs, int K, size_t *nbytes)
+{
+    if (!nbytes || n_envs < 1 || K < 1 || (long long)K * ssg::filter_tiles(n_envs) > SSG_EPISODE_LOG_MAX_CELLS)
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_episode_log_workspace_nbytes: NULL nbytes, an argument < 1 or K * tiles above SSG_EPISODE_LOG_MAX_CELLS");
+    *nbytes = ssg::episode_log_workspace_bytes(n_envs, K);
+    return SSG_OK;
+}
+
+int ssg_episode_log_append(ssg_handle *h, const ssg_episode_log *log, int K, int64_t step0, const double *dev_reward_KN,
+                           const uint8_t *dev_done_KN, const uint8_t *dev_flags_KN, int64_t step_stride_envs, void *stream)
+{
+    const std::string w("ssg_episode_log_append");
+    char buf[200];
+    if (!h) return fail(nullptr, SSG_ERR_BAD_ARG, w + ": NULL handle");
+    if (!log) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL ssg_episode_log");
+    if (log->struct_size != sizeof(ssg_episode_log)) return fail(h, SSG_ERR_BAD_ARG, w + ": ssg_episode_log.struct_size != sizeof(ssg_episode_log)");
+    if (log->capacity < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": capacity < 1");
+    const int P = log->n_members, N = h->cfg.n_envs;
+    if (P < 1 || P > SSG_POP_MAX_MEMBERS) return fail(h, SSG_ERR_BAD_ARG, w + ": n_members must be in 1..SSG_POP_MAX_MEMBERS");
+    ssg::MemberLayout lay;
+    int rc = member_layout(h, P, "ssg_episode_log_append", true, lay); // (asked for one member too, which then owns the whole handle)
+    if (rc != SSG_OK) return rc;
+    if (P == 1) lay = whole_layout(h);
+    if (!log->dev_records || !log->dev_head || !log->dev_carry_return || !log->dev_carry || !log->dev_workspace)
+        return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_records, dev_head, dev_carry_return, dev_carry or dev_workspace");
+    if (reinterpret_cast<uintptr_t>(log->dev_records) % 16 != 0 || reinterpret_cast<uintptr_t>(log->dev_workspace) % 16 != 0 ||
+        reinterpret_cast<uintptr_t>(log->dev_carry) % 8 != 0 || reinterpret_cast<uintptr_t>(log->dev_head) % 8 != 0)
+        return fail(h, SSG_ERR_BAD_ARG, w + ": dev_records and dev_workspace must be 16-byte aligned, dev_carry and dev_head 8-byte aligned");
+    if (K < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": K < 1");
+    if ((long long)K * ssg::filter_tiles(N) > SSG_EPISODE_LOG_MAX_CELLS)
+        return fail(h, SSG_ERR_BAD_ARG, w + ": K * ceil(n_envs / 256) above SSG_EPISODE_LOG_MAX_CELLS (split the rows into several calls)");
+    if (step_stride_envs < N) return fail(h, SSG_ERR_BAD_ARG, w + ": step_stride_envs < n_envs");
+    if (!dev_reward_KN || !dev_done_KN) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL reward or done buffer");
+    const size_t need = ssg::episode_log_workspace_bytes(N, K);
+    if (log->workspace_nbytes < need) {
+        std::snprintf(buf, sizeof buf, ": workspace_nbytes %zu < %zu (ssg_episode_log_workspace_nbytes)", log->workspace_nbytes, need);
+        return fail(h, SSG_ERR_BAD_ARG, w + buf);
+    }
+    rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    ssg::EpisodeLogLaunch l;
+    l.K = K;
+    l.N = N;
+    l.stride = (size_t)step_stride_envs;
+    l.step0 = step0;
+    l.env_base = h->cfg.env_id_base;
+    l.capacity = log->capacity;
+    l.lay = lay;
+    l.rew = dev_reward_KN;
+    l.done = dev_done_KN;
+    l.flags = dev_flags_KN;
+    l.carry_ret = log->dev_carry_return;
+    l.carry = log->dev_carry;
+    l.head = log->dev_head;
+    l.workspace = log->dev_workspace;
+    l.records = log->dev_records;
+    hipError_t e = ssg::launch_episode_log(l, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("episode log launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
 int ssg_eval_account(ssg_handle *h, int episodes_per_env, const double *dev_reward, const uint8_t *dev_done, const uint8_t *dev_flags,
                      double *dev_carry_return, int32_t *dev_carry, int64_t *dev_env_stats, void *stream)
 {

@@ -484,6 +484,25 @@ struct RetFilterLaunch {
     double *denom_out;   // nullable: f64 [K][members]
 };
 hipError_t launch_ret_filter(const RetFilterLaunch &l, hipStream_t stream);
+// the episode log (shipsim_eplog.hip): the workspace holds int64 [2] (the head before the call, the call's count), then the counts of
+// every (row, 256-env tile), int32 [K][filter_tiles(n_envs)], scanned in place
+size_t episode_log_workspace_bytes(int n_envs, int K);
+// One call's three launches (count, scan, walk): the episodes that end in the [K][stride] rows go to records[(head + rank) % capacity],
+// rank in (t, env) order.  lay decides the member bits of a record only.
+struct EpisodeLogLaunch {
+    int K, N;
+    size_t stride;
+    long long step0, env_base, capacity;
+    MemberLayout lay;
+    const double *rew;
+    const uint8_t *done, *flags; // flags nullable
+    double *carry_ret;           // f64 [N]
+    int32_t *carry;              // int32 [N][2]
+    int64_t *head;               // int64 [2]
+    void *workspace;
+    ssg_episode_record *records; // [capacity]
+};
+hipError_t launch_episode_log(const EpisodeLogLaunch &l, hipStream_t stream);
 
 #ifdef __HIPCC__
 // One round of Philox4x32-10 (counter ctr, key key).  The counter-based streams of the library — fill_actions_kernel's actions

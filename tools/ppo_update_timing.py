@@ -9,7 +9,7 @@ every update from the same parameters' values (their own copies) and draw their 
 line on stdout.  The kernels alone: `rocprofv3 --kernel-trace --stats -- python tools/ppo_update_timing.py --only native` (tools/README.md).
 
     python tools/ppo_update_timing.py [--configs 65536x32,4096x64] [--repeats 7] [--only torch|native] [--ext] [--separate-value] [--ret-filter]
-                                      [--adv-norm] [--perm] [--timeout-bootstrap] [--checkpoint] [--dp]
+                                      [--adv-norm] [--perm] [--timeout-bootstrap] [--checkpoint] [--dp] [--episode-log]
 
 --ext adds, in the same run, the extended update (NativePPO with vf_clip 0.2, max_grad_norm 0.5, kl_coef 1.0, kl_target 0.01: GAE, the
 ssg_ppo_dist launch, ssg_ppo_update_ext) as the path "native_ext", and the ssg_ppo_dist launch alone as "dist".
@@ -35,6 +35,9 @@ of the same process; and the file's size in bytes.  What --save-every 1 costs pe
 (ship_sim_gym_amd/dp.py) on ONE rank, to set against "native" — what leaving the C loop costs: a Python iteration per minibatch, a
 gather that is a no-op, the moments launches and the apply launch in place of the reduction; and "apply_rows_w1" / "_w2" / "_w8":
 ssg_ppo_apply_shards alone on 1, 2 and 8 gathered rows (the plain loss: one launch).
+--episode-log adds, in the same run and alternating with the others: "eplog_append" (EpisodeLog.append alone: ssg_episode_log_append, three
+launches), "episode_stats" (ssg_pop_episode_stats alone with one member: the closest existing walk, one launch), "gae_alone" (ssg_ppo_gae
+alone) and "native_eplog" (the append, then the whole GAE + update), to set against "native".
 """
 import argparse
 import importlib.util
@@ -89,7 +92,7 @@ def _wall_ms(fn):
 
 
 def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext=False, separate_value=False, ret_filter=False,
-            adv_norm=False, perm=False, timeout_bootstrap=False, checkpoint=False, checkpoint_dir=None, dp=False):
+            adv_norm=False, perm=False, timeout_bootstrap=False, checkpoint=False, checkpoint_dir=None, dp=False, episode_log=False):
     from ship_sim_gym_amd.policy import NativePolicy
     from ship_sim_gym_amd.ppo import NativePPO
     torch.manual_seed(0)
@@ -177,6 +180,20 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
                                       "config": {"envs": envs, "horizon": horizon}})
 
     paths = [(k, f) for k, f in (("torch", run_torch), ("native", run_native)) if only in (None, k)]
+    if episode_log:  # the append reads the rollout's own rows; the carries and the ring keep running from call to call, as in training
+        import ctypes as C
+        from ship_sim_gym_amd import _native as N
+        from ship_sim_gym_amd.episode_log import EpisodeLog
+        eplog = EpisodeLog(env)
+        st_ret, st_len = torch.zeros(envs, dtype=torch.float64, device=dev), torch.zeros(envs, dtype=torch.int32, device=dev)
+        st_out = torch.zeros((1, 3), dtype=torch.int64, device=dev)
+
+        def run_episode_stats():
+            N.check(N.lib().ssg_pop_episode_stats(env._h, 1, horizon, C.c_void_p(b["rew"].data_ptr()), C.c_void_p(b["done"].data_ptr()),
+                                                  C.c_void_p(st_ret.data_ptr()), C.c_void_p(st_len.data_ptr()), C.c_void_p(st_out.data_ptr()),
+                                                  env._stream()), env._h, "ssg_pop_episode_stats")
+        paths += [("eplog_append", lambda: eplog.append(b)), ("episode_stats", run_episode_stats), ("gae_alone", lambda: ppo.gae(dict(b))),
+                  ("native_eplog", native_path(ppo, seeded(), before=lambda: eplog.append(b)))]
     if checkpoint:
         paths.append(("checkpoint_save", run_checkpoint_save))
     if dp:
@@ -211,6 +228,8 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
         out[k + "_ms_per_update"] = statistics.median(v)
         out[k + "_ms_all"] = [round(x, 3) for x in v]
     out.update(peaks)
+    if episode_log:
+        out["episodes_per_append"] = int(b["done"].ne(0).sum().item())
     if ckpt_path is not None:
         out["checkpoint_file_bytes"] = os.path.getsize(ckpt_path)
         os.remove(ckpt_path)
@@ -237,11 +256,13 @@ def main():
     ap.add_argument("--checkpoint-dir", default=None, help="where --checkpoint writes its file (default: the system's temporary directory)")
     ap.add_argument("--dp", action="store_true", help="also time the whole GAE + update through DataParallelPPO on one rank, and the apply "
                                                       "launch alone on 1, 2 and 8 rows")
+    ap.add_argument("--episode-log", action="store_true", help="also time the episode log's append alone, ssg_pop_episode_stats alone, GAE "
+                                                               "alone, and the whole GAE + update with the append ahead of it")
     a = ap.parse_args()
     mod = _ppo()
     res = [measure(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.repeats, a.only, "cuda:0", ext=a.ext, separate_value=sep, ret_filter=a.ret_filter,
                    adv_norm=a.adv_norm, perm=a.perm, timeout_bootstrap=a.timeout_bootstrap, checkpoint=a.checkpoint,
-                   checkpoint_dir=a.checkpoint_dir, dp=a.dp)
+                   checkpoint_dir=a.checkpoint_dir, dp=a.dp, episode_log=a.episode_log)
            for c in a.configs.split(",") for sep in ([False, True] if a.separate_value else [False])]
     print(json.dumps({"ppo_update_timing": res}))
 

@@ -32,9 +32,14 @@ def open_resume(path, config, require, who="train", exempt=()):
     return ckpt
 
 
-def resume_sections(base, obs_filter, norm_reward):
-    """The sections a resumed run needs: the script's own and one per filter that is on."""
-    return tuple(base) + (("obs_filter",) if obs_filter else ()) + (("ret_filter",) if norm_reward else ())
+# the checkpoint sections that depend on the configuration: the section, and the train() argument that switches it on
+OPTIONAL_SECTIONS = (("obs_filter", "obs_filter"), ("ret_filter", "norm_reward"), ("episode_log", "episode_log"))
+
+
+def resume_sections(base, obs_filter, norm_reward, episode_log=None):
+    """The sections a resumed run needs: the script's own and one per row of OPTIONAL_SECTIONS that is on."""
+    on = {"obs_filter": obs_filter, "norm_reward": norm_reward, "episode_log": episode_log}
+    return tuple(base) + tuple(section for section, arg in OPTIONAL_SECTIONS if on[arg])
 
 
 def check_flag_values(a, error):
@@ -49,6 +54,10 @@ def check_flag_values(a, error):
         error("--save-every must be >= 0")
     if a.save_every and not a.save:
         error("--save-every needs --save (the file it rewrites)")
+    if a.episode_log_capacity < 1:
+        error("--episode-log-capacity must be >= 1")
+    if a.episode_log_capacity != 65536 and not a.episode_log:
+        error("--episode-log-capacity needs --episode-log")
 
 
 def bind_env(env, horizon, n_members=1, obs_filter=False, norm_reward=False, gamma=0.99, reward_clip=10.0, timeout_bootstrap=False,
@@ -83,3 +92,32 @@ def load_filters(ckpt, flt, rflt):
     for k, f in (("obs_filter", flt), ("ret_filter", rflt)):
         if f is not None:
             f.load_state_dict(ckpt[k])
+
+
+def add_episode_log_flags(ap):
+    """The flags both command lines share for the episode log."""
+    ap.add_argument("--episode-log", default=None, metavar="FILE",
+                    help="record every finished training episode on the device and write them to FILE in Stable-Baselines' monitor "
+                         "format (r,l,t and more), flushed once per update; default: off")
+    ap.add_argument("--episode-log-capacity", type=int, default=65536, metavar="C",
+                    help="episodes the device ring holds between two flushes (needs --episode-log); older ones are dropped with a warning")
+
+
+def bind_episode_log(env, path, capacity, n_members=1, resume=False):
+    """(EpisodeLog, MonitorWriter) of a run that asks for one, else (None, None).  A resumed run keeps the file: loading the log's
+    state cuts it back to the rows the checkpoint had written."""
+    if not path:
+        return None, None
+    from ship_sim_gym_amd.episode_log import EpisodeLog, MonitorWriter
+    eplog = EpisodeLog(env, capacity=capacity, n_members=n_members)
+    return eplog, MonitorWriter(path, eplog, resume=bool(resume))
+
+
+def episode_log_section(eplog):
+    """The checkpoint section of the episode log when it is on."""
+    return {"episode_log": eplog.state_dict()} if eplog is not None else {}
+
+
+def load_episode_log(ckpt, eplog):
+    if eplog is not None:
+        eplog.load_state_dict(ckpt["episode_log"])

@@ -175,6 +175,7 @@ def make_arg_parser():
     ap.add_argument("--save-best", default=None, metavar="FILE",
                     help="write a checkpoint after every update in which the best member's episode_reward_mean exceeds the best so far "
                          "(the whole population; the file names the member)")
+    loop.add_episode_log_flags(ap)
     ap.add_argument("--resume", default=None, metavar="FILE",
                     help="continue the run a checkpoint was saved from, bit for bit: repeat the original command line; --updates stays "
                          "the TOTAL and may be raised")
@@ -268,6 +269,8 @@ def plan(run):
     from the arguments: P members on n_total envs, sliced or n each, the schedule per member or common, the permutation rows drawn."""
     if run.save_every < 0 or (run.save_every and not run.save):
         raise ValueError("train: save_every must be >= 0 and needs save (the file it rewrites)")
+    if run.episode_log_capacity < 1:
+        raise ValueError("train: episode_log_capacity must be >= 1")
     if run.perm not in ("torch", "native"):
         raise ValueError("train: perm must be 'torch' or 'native' (got %r)" % (run.perm,))
     P = run.P = int(run.members)
@@ -366,6 +369,8 @@ def build(run, log):
                                                      run.timeout_bootstrap, run.eval_env)
     if run.rflt is not None:
         run.ppo.set_return_filter(run.rflt)  # (an exploit copies the source's state rows with its weights)
+    # the episode log: a record names the member that owns the env when its episode ends, whatever the slices currently are
+    run.eplog, run.epwriter = loop.bind_episode_log(run.env, run.episode_log, run.episode_log_capacity, P, run.resume)
     run.env.reset_tensor()
     if run.save or run.save_best:
         run.env.check_snapshot_supported("snapshot")  # (refuse now, not after the training, a handle that cannot be saved)
@@ -380,6 +385,7 @@ def load_run(run, state, ckpt, log):
     run.pop.load_state_dict(ckpt["population"])
     run.ppo.load_state_dict(ckpt["trainer"])
     loop.load_filters(ckpt, run.flt, run.rflt)
+    loop.load_episode_log(ckpt, run.eplog)
     run.sched.load_state_dict(ckpt["scheduler"])
     run.env.restore(ckpt["env"])
 
@@ -387,7 +393,7 @@ def load_run(run, state, ckpt, log):
 def write_checkpoint(path, run, state):
     """The checkpoint after update state.update (and after its perturbation, when one was due): everything a resumed run needs."""
     from ship_sim_gym_amd import checkpoint
-    checkpoint.save(path, dict(loop.filter_sections(run.flt, run.rflt), config=run.config, population=run.pop.state_dict(),
+    checkpoint.save(path, dict(loop.filter_sections(run.flt, run.rflt), **loop.episode_log_section(run.eplog), config=run.config, population=run.pop.state_dict(),
                                trainer=run.ppo.state_dict(), env=run.env.snapshot(), scheduler=run.sched.state_dict(), loop=state.state_dict(run.gen)))
 
 
@@ -467,14 +473,15 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
           pbt=True, device="cuda:0", log=print, return_details=False, kl_coeff=0.0, kl_target=0.01, vf_clip=0.0, max_grad_norm=0.0,
           separate_value=False, mutate_schedule=False, max_epochs=30, eval_every=0, eval_episodes=1, envs=None, mutate_batch=False,
           batch_shares=None, quantum=None, obs_filter=False, norm_reward=False, reward_clip=10.0, adv_norm="batch", perm="torch",
-          timeout_bootstrap=False, hidden=64, env_kw=None, save=None, save_every=0, save_best=None, resume=None):
+          timeout_bootstrap=False, hidden=64, env_kw=None, save=None, save_every=0, save_best=None, resume=None, episode_log=None,
+          episode_log_capacity=65536):
     config = run_config(**dict(locals()))  # (first statement: the arguments, nothing else)
     run = argparse.Namespace(**locals())  # the run record: the arguments and the config; plan() and build() add to it
     import torch
     from ship_sim_gym_amd.ppo import chunk_split
     # check (every refusal on the host, then the file a run resumes from, before any device work), build and bind, resume
     plan(run)
-    ckpt = loop.open_resume(resume, config, loop.resume_sections(RESUME_SECTIONS, obs_filter, norm_reward), exempt=CONFIG_EXEMPT) if resume else None
+    ckpt = loop.open_resume(resume, config, loop.resume_sections(RESUME_SECTIONS, obs_filter, norm_reward, episode_log), exempt=CONFIG_EXEMPT) if resume else None
     state = build(run, log)
     if ckpt is not None:
         load_run(run, state, ckpt, log)
@@ -486,11 +493,15 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
         out = {k: v for k, v in batch.items() if k not in ("adv", "ret", "logp_all", "rew_norm", "rew_denom")}
         ep = run.ppo.episode_stats(batch)
         state.window += ep
+        if run.eplog is not None:
+            run.eplog.append(batch)  # (no host synchronisation; flushed below, next to the update's log line)
         if run.rflt is not None:
             run.rflt.set_gamma(run.ppo.gamma)  # (the members' own discounts, whatever they currently are)
         run.ppo.gae(batch, return_filter=run.rflt)
         update_population(run, state, batch, draw_permutations(run, state))
         ended = account(state, u, ep, log)
+        if run.eplog is not None:  # the cycle's one copy of the ring to the host
+            log("update %d  episode log: %d rows written, %d in all" % (u, run.epwriter.flush(), run.eplog.rows_written))
         # save-best: the best member's episode_reward_mean so far (an update in which no episode ended never is one) ...
         new_best = ended > 0 and max(state.scores) > state.best
         if new_best:

@@ -267,7 +267,8 @@ def run_config(**kwargs):
 NEEDS = {"mode": ("--mode native", "mode='native'", lambda a: a.mode == "native"),
          "update": ("--update native", "update='native'", lambda a: a.update == "native"),
          "obs_filter": ("--obs-filter", "obs_filter=True", lambda a: bool(a.obs_filter)),
-         "save": ("--save", "save", lambda a: bool(a.save))}
+         "save": ("--save", "save", lambda a: bool(a.save)),
+         "episode_log": ("--episode-log", "episode_log", lambda a: bool(a.episode_log))}
 REQUIREMENTS = (  # (a row that needs more stands before the row of what it needs: the refusal then names the flag that asks for most)
     ("save_obs_filter", "--save-obs-filter", lambda a: bool(a.save_obs_filter), ("mode", "obs_filter"), True, "it saves that filter's statistics"),
     ("obs_filter", "--obs-filter", lambda a: bool(a.obs_filter), ("mode",), True, "the filter runs inside the native policy launch"),
@@ -284,11 +285,19 @@ REQUIREMENTS = (  # (a row that needs more stands before the row of what it need
 )
 
 
+# The episode log's rows, in the same form and walked by the same function, ahead of the rows above.
+EPISODE_LOG_REQUIREMENTS = (
+    ("best_window", "--best-window", lambda a: bool(a.best_window), ("episode_log",), True, "the window is over the log's last episodes"),
+    ("episode_log", "--episode-log", lambda a: bool(a.episode_log), ("mode", "update"), True,
+     "it reads the native rollout's reward / done / flags rows; a job's ranks would each hold a log of their own envs"),
+)
+
+
 def check_requirements(args, ranks, error=None):
-    """Walk REQUIREMENTS over the arguments `args` (a dict) of a run of `ranks` ranks.  The first row that is on and misses a need, or is
+    """Walk EPISODE_LOG_REQUIREMENTS and REQUIREMENTS over the arguments `args` (a dict) of a run of `ranks` ranks.  The first row that is on and misses a need, or is
     refused with more than one rank, goes to the parser's `error` with the flags in the text, or is a ValueError with train()'s names."""
     a = argparse.Namespace(**dict(args, ranks=ranks))
-    for name, flag, on, needs, one_rank_only, why in REQUIREMENTS:
+    for name, flag, on, needs, one_rank_only, why in EPISODE_LOG_REQUIREMENTS + REQUIREMENTS:
         text = None
         if on(a) and not all(NEEDS[k][2](a) for k in needs):
             text = ("%s needs %s (%s)" % (flag, " ".join(NEEDS[k][0] for k in needs), why) if error else
@@ -309,6 +318,8 @@ def check_train_arguments(a, ranks):
             raise ValueError("%s must be %r or %r (got %r)" % ((name,) + allowed + (getattr(a, name),)))
     if a.save_every < 0 or a.eval_every < 0 or a.eval_episodes < 1:
         raise ValueError("save_every and eval_every must be >= 0 and eval_episodes >= 1")
+    if a.episode_log_capacity < 1 or a.best_window < 0:
+        raise ValueError("episode_log_capacity must be >= 1 and best_window >= 0")
     check_requirements(vars(a), ranks)
 
 
@@ -393,6 +404,7 @@ def load_run(run, state, ckpt):
     run.policy.load_state_dict(ckpt["policy"])
     run.ppo.load_state_dict(ckpt["trainer"])
     loop.load_filters(ckpt, run.flt, run.rflt)
+    loop.load_episode_log(ckpt, run.eplog)
     run.env.restore(ckpt["env"])
     state.load_state_dict(ckpt["loop"], run.gen)
 
@@ -401,6 +413,7 @@ def write_checkpoint(path, run, state):
     """The checkpoint after update state.update: everything a resumed run needs with the device update, else the policy (for evaluation)."""
     from ship_sim_gym_amd import checkpoint
     sections = dict(loop.filter_sections(run.flt, run.rflt), config=run.config, loop=state.state_dict(run.gen))
+    sections.update(loop.episode_log_section(run.eplog))
     if run.ppo is not None:  # (a job's file is rank 0's: the policy and the trainer; per-rank env snapshots are out of scope)
         sections.update(policy=run.policy.state_dict(), trainer=run.ppo.state_dict(), **({"env": run.env.snapshot()} if run.world == 1 else {}))
     else:  # (the torch update trains the module: pack it as evaluation reads it)
@@ -482,6 +495,12 @@ def account(run, state, u, b, log):
     ended = st["episodes"] - state.episodes
     state.scores.append((st["sum_return"] - state.sum_return) / ended if ended > 0 else float("-inf"))
     state.episodes, state.sum_return = st["episodes"], st["sum_return"]
+    if run.eplog is not None:  # the cycle's one copy of the ring to the host; then the window's score in place of the update's own
+        written = run.epwriter.flush()
+        if run.best_window > 0 and ended > 0:
+            state.scores[-1] = run.eplog.mean_last(run.best_window)
+        log("update %3d  episode log: %d rows written, %d in all%s" % (u, written, run.eplog.rows_written, (
+            "  mean return of the last %d at most: %+.3f" % (run.best_window, state.scores[-1]) if run.best_window > 0 and ended > 0 else "")))
     return ended
 
 
@@ -499,7 +518,7 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
           device="cuda:0", seed=0, log=print, mode="eager", return_details=False, env_kw=None, update="torch", separate_value=False,
           eval_every=0, eval_episodes=1, eval_envs=None, obs_filter=False, save_obs_filter=None,
           norm_reward=False, reward_clip=10.0, adv_norm="batch", perm="torch", timeout_bootstrap=False, hidden=64,
-          save=None, save_every=0, save_best=None, resume=None):
+          save=None, save_every=0, save_best=None, resume=None, episode_log=None, episode_log_capacity=65536, best_window=0):
     config = run_config(**dict(locals()))  # (first statement: the arguments, nothing else)
     run = argparse.Namespace(**locals())  # the run record: the arguments and the config; build_run() and the bind step add the objects
     # check: every refusal on the host, then the file a run resumes from, before any device work (a wrong command line costs nothing)
@@ -507,12 +526,13 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
     check_train_arguments(run, world)
     if rank != 0:  # (a data-parallel job trains ONE policy, ship_sim_gym_amd/dp.py: only rank 0 logs, evaluates and saves)
         log = lambda *_, **__: None  # noqa: E731
-    ckpt = open_resume(resume, config, loop.resume_sections(RESUME_SECTIONS, obs_filter, norm_reward), exempt=CONFIG_EXEMPT) if resume else None
+    ckpt = open_resume(resume, config, loop.resume_sections(RESUME_SECTIONS, obs_filter, norm_reward, episode_log), exempt=CONFIG_EXEMPT) if resume else None
     # build, bind, resume
     build_run(run, rank, world)
     eval_env = (ShipVecEnv(int(eval_envs or min(envs, 1024)), GameConfig, EnvConfig, device=device, n_maps=64, **dict(env_kw or {}))
                 if eval_every and rank == 0 else None)
     run.flt, run.rflt, run.evaluator = loop.bind_env(run.env, horizon, 1, obs_filter, norm_reward, gamma, reward_clip, timeout_bootstrap, eval_env)
+    run.eplog, run.epwriter = loop.bind_episode_log(run.env, episode_log, episode_log_capacity, 1, resume)
     if mode in ("graph", "pingpong"):
         capture_graphs(run)
     snapshots, evals, t_roll, t_upd, t_all0 = [], [], 0.0, 0.0, time.perf_counter()
@@ -531,6 +551,8 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         torch.cuda.synchronize()
         t_roll += time.perf_counter() - t0
         native_last_val = b.pop("last_val", None)
+        if run.eplog is not None:
+            run.eplog.append(run.shards[0].native_out)  # (the rollout's own f64 / u8 rows; no host synchronisation)
         if return_details is True:
             snapshots.append({k: v.clone() for k, v in b.items()})
         t1 = time.perf_counter()
@@ -541,7 +563,7 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         torch.cuda.synchronize()
         t_upd += time.perf_counter() - t1
         ended = account(run, state, u, b, log)
-        if state.scores[-1] > state.best:  # save-best: written at once (an update in which no episode ended scores -inf: never here)
+        if state.scores[-1] > state.best:  # save-best: written at once (an update in which no episode ended scores -inf: never here; --best-window: the score is the log's window mean)
             state.best, state.best_update = state.scores[-1], u
             if save_best and rank == 0:
                 write_checkpoint(save_best, run, state)
@@ -624,6 +646,10 @@ def make_arg_parser():
     ap.add_argument("--save-best", default=None, metavar="FILE",
                     help="write a checkpoint after every update whose episode_reward_mean (the mean return of the episodes that ended "
                          "during it) exceeds the best so far")
+    loop.add_episode_log_flags(ap)
+    ap.add_argument("--best-window", type=int, default=0, metavar="W",
+                    help="--save-best compares the mean return of the last W finished episodes (the reference callback's "
+                         "np.mean(y[-100:]); needs --episode-log) instead of the mean over the episodes of one update; 0 = off")
     ap.add_argument("--resume", default=None, metavar="FILE",
                     help="continue the run a checkpoint was saved from, bit for bit (needs --mode native --update native): repeat the "
                          "original command line; --updates stays the TOTAL and may be raised")
@@ -635,6 +661,8 @@ def parse_args(argv=None):
     ap = make_arg_parser()
     a = ap.parse_args(argv)
     loop.check_flag_values(a, ap.error)
+    if a.best_window < 0:
+        ap.error("--best-window must be >= 0")
     if a.gpus < 1 or a.gpus > 64:
         ap.error("--gpus must be in 1..64")
     check_requirements(vars(a), max(a.gpus, int(os.environ.get("WORLD_SIZE", "1"))), ap.error)
