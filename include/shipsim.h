@@ -919,7 +919,7 @@ int ssg_pop_episode_stats(ssg_handle *h, int n_members, int K, const double *dev
  *   [6] ... SSG_EV_NO_GOALS_LEFT       [7] the episode's goal events
  * ([3]..[6] are not exclusive of each other), then zeroes return, length and goal events and bumps its episode count.  Once an env has
  * counted E episodes its row and carry no longer change, though the env keeps stepping.  An episode still running when a call ends
- * stays in the carry: a later call continues it.
+ * stays in the carry: a later call continues it.  The carry's fourth word is neither read nor computed: it keeps the caller's value.
  * ------------------------------------------------------------------------------------------------- */
 #define SSG_EVAL_STATS 8
 #define SSG_EVAL_GREEDY 0x1u /* ssg_eval.flags: the arg-max action (ssg_policy_act_greedy) instead of a draw */

@@ -5,6 +5,7 @@ Every comparison is torch.equal: per member the population's launches run the si
 import numpy as np
 import pytest
 
+from accounting_support import episode_stats_walk, layout
 from gpu_support import DEV, env_config as _env_config, load_script, state_columns as _columns, torch_cuda  # noqa: F401
 from population_harness import ROLLOUT_KEYS, close_all as _close, cols, member_hparams, shard_reference, shard_rollouts, stacked_perms
 from ppo_reference import actor_critic_policy
@@ -229,22 +230,12 @@ def test_episode_stats_match_a_forward_walk_and_the_handles_counters(torch_cuda)
     ppo = PopulationPPO(pop, env)
     env.reset_tensor()
     before = env.field_stats_tensor().cpu().numpy().copy()
-    cum, length = np.zeros(P * n), np.zeros(P * n, dtype=np.int64)
+    cum, length = np.zeros(P * n), np.zeros(P * n, dtype=np.int32)
     total = np.zeros((P, 3), dtype=np.int64)
     for r in range(3):
         b = env.rollout_population(pop, K, seed=9, step0=r * K)
         got = ppo.episode_stats(b).cpu().numpy()
-        rew, done = b["rew"].cpu().numpy(), b["done"].cpu().numpy()
-        want = np.zeros((P, 3), dtype=np.int64)
-        for t in range(K):
-            cum += rew[t]
-            length += 1
-            d = done[t] != 0
-            for m in range(P):
-                dm = d[m * n:(m + 1) * n]
-                want[m] += (np.rint(cum[m * n:(m + 1) * n][dm] * 100.0).astype(np.int64).sum(), length[m * n:(m + 1) * n][dm].sum(), dm.sum())
-            cum[d] = 0.0
-            length[d] = 0
+        want, (cum, length) = episode_stats_walk(b["rew"].cpu().numpy(), b["done"].cpu().numpy(), cum, length, *layout([n] * P))
         assert np.array_equal(got, want), (r, got, want)
         assert (got[:, 2] >= n).all()                                       # every member finished episodes: nothing passes vacuously
         total += got

@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from accounting_support import episode_stats_walk
 from gpu_support import DEV, load_script, vec as split_vec
 from gpu_support import torch_cuda  # noqa: F401
 from population_harness import ROLLOUT_KEYS, age, cached, member_hparams as _hp, perms_per_member as _perms, shard_reference as _reference, \
@@ -232,21 +233,11 @@ def test_episode_stats_sum_each_members_own_columns(torch_cuda):
     pop = NativePopulation(_members(torch, env.states_history, P, False))
     ppo = PopulationPPO(pop, env)
     env.reset_tensor()
-    cum, length = np.zeros(N), np.zeros(N, dtype=np.int64)
+    cum, length = np.zeros(N), np.zeros(N, dtype=np.int32)
     for r in range(2):
         b = env.rollout_population(pop, KK, seed=9, step0=r * KK)
         got = ppo.episode_stats(b).cpu().numpy()
-        rew, done = b["rew"].cpu().numpy(), b["done"].cpu().numpy()
-        want = np.zeros((P, 3), dtype=np.int64)
-        for t in range(KK):
-            cum += rew[t]
-            length += 1
-            d = done[t] != 0
-            for m, (o, n) in enumerate(zip(_offsets(SIZES), SIZES)):
-                dm = d[o:o + n]
-                want[m] += (np.rint(cum[o:o + n][dm] * 100.0).astype(np.int64).sum(), length[o:o + n][dm].sum(), dm.sum())
-            cum[d] = 0.0
-            length[d] = 0
+        want, (cum, length) = episode_stats_walk(b["rew"].cpu().numpy(), b["done"].cpu().numpy(), cum, length, _offsets(SIZES), SIZES)
         assert np.array_equal(got, want), (r, got, want)
         assert (got[:, 2] >= np.array(SIZES)).all()                         # every member finished episodes, the one-env member too
         assert np.array_equal(ppo.carry_length.cpu().numpy(), length) and np.array_equal(ppo.carry_return.cpu().numpy(), cum)
