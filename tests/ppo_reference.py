@@ -105,24 +105,38 @@ def plain_loss(torch, p, offsets, L, act, x, a, logp_old, advn, ret, clip=0.2, v
     return pg + vf_coef * vl - ent_coef * ent, pg, vl, ent, cf
 
 
+def ext_sample_terms(torch, lpa, v, a, logp_old, advn, ret, v_old, lpa_old, clip=0.2, vf_clip=0.0, ratio_of=None, bounds=None):
+    """The extended loss behind the forward and its log_softmax (lpa [M, A]), per sample [M]: (min(r*A, clamp(r)*A), VL, sum(p*logp), KL,
+    |r - 1| > clip, (v - v_old, (v - ret)^2, clipped (v_c - ret)^2)).  ext_loss takes the means; tests/loss_edges.py reads the samples.
+    ratio_of (a function of log p[act]) replaces exp(log p[act] - logp_old); bounds replaces the clamp's (1 - clip, 1 + clip)."""
+    lp_act = lpa.gather(-1, a.unsqueeze(-1)).squeeze(-1)
+    ratio = torch.exp(lp_act - logp_old) if ratio_of is None else ratio_of(lp_act)
+    lo, hi = (1 - clip, 1 + clip) if bounds is None else bounds
+    smin = torch.min(ratio * advn, torch.clamp(ratio, lo, hi) * advn)
+    l1 = (v - ret).pow(2)
+    l2 = (v_old + torch.clamp(v - v_old, -vf_clip, vf_clip) - ret).pow(2)
+    vls = torch.max(l1, l2) if vf_clip > 0 else l1
+    plp = (lpa.exp() * lpa).sum(-1)
+    kls = (lpa_old.exp() * (lpa_old - lpa)).sum(-1)
+    return smin, vls, plp, kls, (ratio - 1).abs() > clip, (v - v_old, l1, l2)
+
+
 def ext_loss(torch, p, offsets, L, act, x, a, logp_old, advn, ret, v_old, lpa_old, clip=0.2, vf_coef=0.5, ent_coef=0.01, vf_clip=0.0,
              kl_coef=0.0):
     """The extended minibatch loss on packed parameters p (any dtype): returns (loss, pg, mean VL, entropy mean, clip fraction,
     mean KL, (v - v_old, (v - ret)^2, clipped (v_c - ret)^2)).  lpa_old: [M, A] (the acting policy's log-distribution)."""
     logits, v = forward(torch, p, offsets, L, act, x)
-    lpa = torch.log_softmax(logits, -1)
-    ratio = torch.exp(lpa.gather(-1, a.unsqueeze(-1)).squeeze(-1) - logp_old)
-    pg = -torch.min(ratio * advn, torch.clamp(ratio, 1 - clip, 1 + clip) * advn).mean()
-    l1 = (v - ret).pow(2)
-    l2 = (v_old + torch.clamp(v - v_old, -vf_clip, vf_clip) - ret).pow(2)
-    vl = torch.max(l1, l2).mean() if vf_clip > 0 else l1.mean()
-    ent = -(lpa.exp() * lpa).sum(-1).mean()
-    kl = (lpa_old.exp() * (lpa_old - lpa)).sum(-1).mean()
-    cf = ((ratio - 1).abs() > clip).to(x.dtype).mean()
+    smin, vls, plp, kls, clipped, branches = ext_sample_terms(torch, torch.log_softmax(logits, -1), v, a, logp_old, advn, ret, v_old, lpa_old,
+                                                              clip, vf_clip)
+    pg = -smin.mean()
+    vl = vls.mean()
+    ent = -plp.mean()
+    kl = kls.mean()
+    cf = clipped.to(x.dtype).mean()
     loss = pg + vf_coef * vl - ent_coef * ent
     if kl_coef > 0:
         loss = loss + kl_coef * kl
-    return loss, pg, vl, ent, cf, kl, (v - v_old, l1, l2)
+    return loss, pg, vl, ent, cf, kl, branches
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
