@@ -1510,6 +1510,92 @@ int ssg_ppo_apply_shards(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hpa
                          void *dev_workspace, size_t workspace_nbytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The update report (additions to ABI 9): how an update went, reduced on the device
+ * The Stable-Baselines script's PPO2(..., verbose=1, tensorboard_log=tb_dir).learn(..., log_interval=10000)
+ * (train/stable_baselines/ppo.py:88-90) prints and logs, per update, explained_variance, approxkl, clipfrac, policy_entropy,
+ * policy_loss and value_loss; RLlib's PPO (train/rllib/ppo.py:26-41, train/rllib/pbt.py:47-74) reports vf_explained_var, kl, entropy,
+ * policy_loss, vf_loss, cur_kl_coeff and cur_lr per iteration.  ssg_ppo_report / ssg_pop_report reduce a rollout's buffers to one f64
+ * record of SSG_REPORT_COLS per policy, in two launches.
+ *
+ * The walk.  One lane per env, 256-env workgroups counted from the member's first env (ssg_ppo_gae's layout).  Lane e walks
+ * t = 0 .. K-1 in ascending order over its column i = t*N + o_m + e, in f64, every product and sum rounded on its own (no fused
+ * multiply-add), with r = (double)ret[i], v = (double)val[i], a = (double)adv[i], err = r - v:
+ *     S_r += r;  Q_r += r*r;  S_e += err;  Q_e += err*err;  S_v += v;  S_a += a
+ * and, with the post-update group (dev_logp_all_new given), d = logp_all_new[i][act[i] & 3] - logp[i] as ONE f32 subtraction:
+ *     S_d += (double)d;  Q_d += (double)d * (double)d;  C += (d > hi || d < lo) ? 1 : 0
+ * The clip decision is taken in the log domain, so the kernel runs no expf and has an exact restatement: lo = (float)log1p(-clip),
+ * -inf from clip 1 on, hi = (float)log1p(clip), both formed on the host in double (ssg_report_clip_bounds).  This is PPO2's clipfrac
+ * up to the rounding of the gradient kernel's fabsf(expf(d) - 1) > clip at the boundary.  Each workgroup reduces every sum with the
+ * 256-entry halving tree (w = 128 .. 1) and writes one partial row per (member, block) into the scratch.
+ *
+ * The finish.  One workgroup per member: thread j adds the partials of blocks j, j + 256, ... in that order, then one more tree
+ * (the order of ssg_ppo_gae's statistics launch).  The record, all in f64, with n = (double)K * n_m:
+ *     [0]      n
+ *     [1],[2]  mean(ret) = S_r/n;  var(ret) = max(0, (Q_r - S_r*mean) / n): the population variance (np.var)
+ *     [3],[4]  mean(ret - val);  var(ret - val), the same formula
+ *     [5]      explained variance = 1 - [4]/[2]; NaN when [2] == 0 (as Stable-Baselines' explained_variance)
+ *     [6],[7]  mean(val);  mean(adv) (raw, before any normalisation)
+ *     [8]      1.0 when the post-update group was computed, else 0.0 (then [9..11] are 0.0)
+ *     [9]      approximate KL = -(S_d/n)
+ *     [10]     PPO2's approxkl = 0.5 * (Q_d/n)
+ *     [11]     C/n: the clip fraction over the whole batch under the post-update policy
+ *     [12..19] the means of columns 0..7 of the member's stats rows (the f32 rows ssg_ppo_update(_ext) / ssg_pop_update* wrote: pg
+ *              loss, value loss, entropy, clip fraction; with the extended loss KL, gradient norm, KL coefficient, unused): column c
+ *              summed in f64 over its rows in row order by one thread, divided by the row count; 0.0 for columns the rows do not
+ *              have, and for all eight when no rows are given (or the member's count is 0)
+ *     [20]     the number of stats rows used
+ *     [21..23] 0.0
+ * No floating-point atomics, no host synchronisation, constant launch arguments (a capturing stream is fine).
+ *
+ * Contract.  The record depends on the inputs alone, bitwise: not on the stream or on earlier calls.  Member m's record of
+ * ssg_pop_report is bit for bit ssg_ppo_report's on its shard (its columns as a [K][n_m] batch) with its bounds and its rows.  Equal
+ * slices bound with ssg_pop_set_slices give bit for bit what an unbound handle gives.  The calls read their inputs only, and write
+ * only the scratch and dev_out.
+ * ------------------------------------------------------------------------------------------------- */
+#define SSG_REPORT_COLS 24
+#define SSG_REPORT_EXPLAINED_VARIANCE 5
+#define SSG_REPORT_POST 8
+#define SSG_REPORT_STATS 12
+#define SSG_REPORT_ROWS 20
+
+/* Replaces nothing (host helper; the thresholds behind PPO2's clipfrac, train/stable_baselines/ppo.py:88-90, in the log domain).
+ * out_lo_hi = {clip >= 1 ? -inf : (float)log1p(-clip), (float)log1p(clip)}, so that C and Python form the same bits.  Host only.
+ * SSG_ERR_BAD_ARG for clip <= 0 (or NaN) or a NULL pointer. */
+int ssg_report_clip_bounds(double clip, float out_lo_hi[2]);
+
+/* Replaces nothing (sizing helper).  *nbytes = a scratch size that serves ssg_ppo_report over n_envs envs and ssg_pop_report for
+ * n_members members on any slice layout of n_envs envs: n_members * ceil(n_envs / 256) partial rows of 9 doubles, rounded up to 256
+ * bytes.  Host only.  SSG_ERR_BAD_ARG for an argument < 1, n_members > SSG_POP_MAX_MEMBERS or a NULL pointer. */
+int ssg_ppo_report_workspace_nbytes(int n_envs, int n_members, size_t *nbytes);
+
+/* Replaces: the per-update log of PPO2 (train/stable_baselines/ppo.py:88-90: explained_variance, approxkl, clipfrac, policy_entropy,
+ * policy_loss, value_loss) and of RLlib's PPO (train/rllib/ppo.py:26-41: vf_explained_var, kl, entropy, policy_loss, vf_loss) for
+ * one policy: the record above over the K x N batch (rows N apart; N is the batch's, not the handle's), into dev_out24 (f64
+ * [SSG_REPORT_COLS] on the device).  dev_act, dev_logp and dev_logp_all_new (f32 [K*N][4]: an ssg_ppo_dist call made AFTER the
+ * update) are nullable together; dev_stats (nullable) is f32 [n_rows][n_cols], n_cols 4 or 8.  The scratch needs
+ * ceil(N / 256) * 9 doubles.  Two launches on `stream`.  SSG_ERR_BAD_ARG (nothing launched): a NULL handle, value, ret, adv, scratch
+ * or out pointer; K < 1 or N < 1; one of dev_act / dev_logp / dev_logp_all_new given without the others; clip <= 0 with the
+ * post-update group; n_cols not 4 or 8, or n_rows < 1, with dev_stats given; a scratch that is too small or not 256-byte aligned. */
+int ssg_ppo_report(ssg_handle *h, int K, int N, const float *dev_value_KN, const float *dev_ret_KN, const float *dev_adv_KN,
+                   const int32_t *dev_act /* nullable */, const float *dev_logp /* nullable */,
+                   const float *dev_logp_all_new /* nullable */, double clip, const float *dev_stats /* nullable */, int n_rows,
+                   int n_cols, void *dev_scratch, size_t scratch_nbytes, double *dev_out24, void *stream);
+
+/* Replaces: the same for every trial of train/rllib/pbt.py:47-74 in the same two launches: grid (blocks of the widest slice,
+ * members).  The buffers are the [K][n_envs] ones of ssg_pop_gae; member m owns columns [m n, (m + 1) n), n = n_envs / P, or its
+ * slice of ssg_pop_set_slices: unbound, n_envs % P != 0 is refused; slices bound for another P are refused.  dev_bounds (f32 [P][2]:
+ * each member's lo, hi of ssg_report_clip_bounds) is required with the post-update group (dev_logp_all_new: ssg_pop_dist AFTER the
+ * update).  dev_stats (nullable): f32 [P][rows_max][n_cols]; dev_rows (nullable): int32 [P], member m's own row count in
+ * 0..rows_max, NULL meaning rows_max for all.  Rows past a member's count are never read (ssg_pop_update_sched leaves them
+ * unwritten).  dev_out: f64 [P][SSG_REPORT_COLS].  The scratch needs P * ceil(widest slice / 256) * 9 doubles.  Refuses as
+ * ssg_ppo_report, and n_members outside 1..SSG_POP_MAX_MEMBERS, a NULL dev_bounds with the post-update group. */
+int ssg_pop_report(ssg_handle *h, int n_members, int K, const float *dev_value_KN, const float *dev_ret_KN, const float *dev_adv_KN,
+                   const int32_t *dev_act /* nullable */, const float *dev_logp /* nullable */,
+                   const float *dev_logp_all_new /* nullable */, const float *dev_bounds /* [P][2] */,
+                   const float *dev_stats /* nullable */, int rows_max, int n_cols, const int32_t *dev_rows /* nullable */,
+                   void *dev_scratch, size_t scratch_nbytes, double *dev_out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Host-side geometry (what pymunk's cffi exposed at reset time); no GPU needed.
  * ------------------------------------------------------------------------------------------------- */
 /* Replaces cpConvexHull as reached by pm.Poly(...) (models.py:96,180).  out_xy holds >= count pairs. */

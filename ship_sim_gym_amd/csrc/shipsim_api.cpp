@@ -2719,6 +2719,108 @@ int ssg_episode_log_append(ssg_handle *h, const ssg_episode_log *log, int K, int
     return SSG_OK;
 }
 
+// ABI 9 addition: the update report.  Everything the host can judge comes first (BAD_ARG), then the device; nothing is enqueued before.
+int ssg_report_clip_bounds(double clip, float out_lo_hi[2])
+{
+    if (!out_lo_hi || !(clip > 0.0)) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_report_clip_bounds: NULL out_lo_hi or clip <= 0");
+    ssg::report_clip_bounds(clip, out_lo_hi);
+    return SSG_OK;
+}
+
+int ssg_ppo_report_workspace_nbytes(int n_envs, int n_members, size_t *nbytes)
+{
+    if (!nbytes || n_envs < 1 || n_members < 1 || n_members > SSG_POP_MAX_MEMBERS)
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_ppo_report_workspace_nbytes: NULL nbytes, an argument < 1 or n_members above SSG_POP_MAX_MEMBERS");
+    *nbytes = ssg::report_scratch_bytes(n_envs, n_members);
+    return SSG_OK;
+}
+
+// The body of ssg_ppo_report and ssg_pop_report: the launch record is complete but for the checks both calls share.
+static int report(ssg_handle *h, ssg::ReportLaunch &l, bool need_bounds, void *dev_scratch, size_t scratch_nbytes, void *stream, const char *what)
+{
+    const std::string w(what);
+    char buf[200];
+    if (!l.val || !l.ret || !l.adv || !l.out) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL value, ret, adv or out buffer");
+    if (l.K < 1 || l.N < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": K and N must be >= 1");
+    const int given = (l.act != nullptr) + (l.logp != nullptr) + (l.lpa != nullptr);
+    if (given != 0 && given != 3) return fail(h, SSG_ERR_BAD_ARG, w + ": dev_act, dev_logp and dev_logp_all_new go together: all three or none");
+    if (given && need_bounds && !l.bounds) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_bounds with the post-update group");
+    if (l.stats && l.n_cols != 4 && l.n_cols != 8) return fail(h, SSG_ERR_BAD_ARG, w + ": n_cols must be 4 or 8");
+    if (l.stats && l.rows_max < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": fewer than 1 stats row");
+    if (!dev_scratch) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_scratch");
+    if (reinterpret_cast<uintptr_t>(dev_scratch) % 256 != 0) return fail(h, SSG_ERR_BAD_ARG, w + ": the scratch must be 256-byte aligned");
+    const size_t need = (size_t)l.lay.members * (size_t)ssg::ppo_gae_blocks(l.lay.n) * ssg::kReportSums * sizeof(double);
+    if (scratch_nbytes < need) {
+        std::snprintf(buf, sizeof buf, ": scratch of %zu bytes, this call needs %zu (ssg_ppo_report_workspace_nbytes)", scratch_nbytes, need);
+        return fail(h, SSG_ERR_BAD_ARG, w + buf);
+    }
+    const int rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    l.part = static_cast<double *>(dev_scratch);
+    hipError_t e = ssg::launch_report(l, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("report launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+int ssg_ppo_report(ssg_handle *h, int K, int N, const float *dev_value_KN, const float *dev_ret_KN, const float *dev_adv_KN,
+                   const int32_t *dev_act, const float *dev_logp, const float *dev_logp_all_new, double clip, const float *dev_stats,
+                   int n_rows, int n_cols, void *dev_scratch, size_t scratch_nbytes, double *dev_out24, void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc != SSG_OK) return rc;
+    ssg::ReportLaunch l = {};
+    l.K = K;
+    l.N = N;
+    l.lay = ssg::MemberLayout{1, N, nullptr};
+    l.val = dev_value_KN;
+    l.ret = dev_ret_KN;
+    l.adv = dev_adv_KN;
+    l.act = dev_act;
+    l.logp = dev_logp;
+    l.lpa = dev_logp_all_new;
+    if (dev_logp_all_new) {
+        if (!(clip > 0.0)) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_report: clip must be > 0 with the post-update group");
+        float b[2];
+        ssg::report_clip_bounds(clip, b);
+        l.lo = b[0];
+        l.hi = b[1];
+    }
+    l.stats = dev_stats;
+    l.rows_max = n_rows;
+    l.n_cols = n_cols;
+    l.out = dev_out24;
+    return report(h, l, false, dev_scratch, scratch_nbytes, stream, "ssg_ppo_report");
+}
+
+int ssg_pop_report(ssg_handle *h, int n_members, int K, const float *dev_value_KN, const float *dev_ret_KN, const float *dev_adv_KN,
+                   const int32_t *dev_act, const float *dev_logp, const float *dev_logp_all_new, const float *dev_bounds,
+                   const float *dev_stats, int rows_max, int n_cols, const int32_t *dev_rows, void *dev_scratch, size_t scratch_nbytes,
+                   double *dev_out, void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc != SSG_OK) return rc;
+    if (n_members < 1 || n_members > SSG_POP_MAX_MEMBERS)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_pop_report: n_members must be in 1..SSG_POP_MAX_MEMBERS");
+    ssg::ReportLaunch l = {};
+    rc = member_layout(h, n_members, "ssg_pop_report", true, l.lay);
+    if (rc != SSG_OK) return rc;
+    l.K = K;
+    l.N = h->cfg.n_envs;
+    l.val = dev_value_KN;
+    l.ret = dev_ret_KN;
+    l.adv = dev_adv_KN;
+    l.act = dev_act;
+    l.logp = dev_logp;
+    l.lpa = dev_logp_all_new;
+    l.bounds = dev_bounds;
+    l.stats = dev_stats;
+    l.rows = dev_stats ? dev_rows : nullptr;
+    l.rows_max = rows_max;
+    l.n_cols = n_cols;
+    l.out = dev_out;
+    return report(h, l, true, dev_scratch, scratch_nbytes, stream, "ssg_pop_report");
+}
+
 int ssg_eval_account(ssg_handle *h, int episodes_per_env, const double *dev_reward, const uint8_t *dev_done, const uint8_t *dev_flags,
                      double *dev_carry_return, int32_t *dev_carry, int64_t *dev_env_stats, void *stream)
 {

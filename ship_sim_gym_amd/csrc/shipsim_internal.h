@@ -503,6 +503,27 @@ struct EpisodeLogLaunch {
     ssg_episode_record *records; // [capacity]
 };
 hipError_t launch_episode_log(const EpisodeLogLaunch &l, hipStream_t stream);
+// the update report (shipsim_report.hip): the scratch holds the walk's partials, f64 [members][ppo_gae_blocks(widest slice)][kReportSums]
+// = sums of ret, ret^2, ret - val, (ret - val)^2, val, adv, d, d^2 and the clipped count
+constexpr int kReportSums = 9;
+size_t report_scratch_bytes(int n_widest, int members);
+// lo = (float)log1p(-clip), -inf from clip 1 on; hi = (float)log1p(clip): formed in double (ssg_report_clip_bounds)
+void report_clip_bounds(double clip, float out_lo_hi[2]);
+// One call's two launches (walk, finish): member m's columns of the [K] rows (N apart) into its record out[m][SSG_REPORT_COLS].
+struct ReportLaunch {
+    int K, N;
+    MemberLayout lay;
+    const float *val, *ret, *adv;
+    const int32_t *act;          // the post-update group: act, logp and lpa (f32 [K*N][4]) together, or all NULL
+    const float *logp, *lpa;
+    const float *bounds;         // nullable: f32 [members][2]; else lo, hi for every member
+    float lo, hi;
+    const float *stats;          // nullable: f32 [members][rows_max][n_cols]
+    const int32_t *rows;         // nullable: int32 [members], member m's own row count (<= rows_max)
+    int rows_max, n_cols;
+    double *part, *out;
+};
+hipError_t launch_report(const ReportLaunch &l, hipStream_t stream);
 
 #ifdef __HIPCC__
 // One round of Philox4x32-10 (counter ctr, key key).  The counter-based streams of the library — fill_actions_kernel's actions

@@ -144,7 +144,10 @@ def apply_reference(rows, counts, params, adam_mv, step, hp, max_grad_norm=0.0, 
 class DataParallelPPO(NativePPO):
     """NativePPO over this rank's shard of a W-rank job.  group: the process group (None: the default one; with none initialised the
     job is this process alone, W = 1, and every result is NativePPO's bit for bit).  plan=(K, minibatches): check at construction that
-    the shards make the same number of chunks for that rollout length and minibatch count (update() checks what it is given)."""
+    the shards make the same number of chunks for that rollout length and minibatch count (update() checks what it is given).
+    ``report`` / ``report_device`` are NativePPO's: the record is then this rank's OWN shard's (its n, means, variances and post-update
+    group; the stats rows' means are the job's, since every rank holds the same rows).  The sums are mergeable, but merging the ranks'
+    records is out of scope."""
 
     def __init__(self, policy, env, group=None, plan=None, **kw):
         if kw.get("adv_norm", "batch") != "batch":

@@ -207,6 +207,7 @@ class PopulationPPO(DeviceTrainer):
         self.kl_coef = torch.tensor(self.kl_coef, dtype=torch.float32).to(dev)  # (the list set above becomes the device tensor)
         self._last_K = 0  # the rollout length of the last batch gae() or update() saw (minibatches_for_size's default)
         self.return_filter = None  # set_return_filter: the ReturnFilter whose state rows travel with an exploit
+        self._last_taken = None  # the steps each member took in the last update(): the stats rows report() reads (None: all of them)
 
     @property
     def member_envs(self):
@@ -527,7 +528,62 @@ class PopulationPPO(DeviceTrainer):
                                            C.c_void_p(st.data_ptr()) if stats else None, C.c_void_p(self.workspace.data_ptr()),
                                            self.workspace.numel(), self._stream()), h, name)
         self._advance(steps0, taken)
+        self._last_taken = [int(t) for t in taken]  # (report(): the rows of `st` each member wrote)
         return st
+
+    # ------------------------------------------------------------------------------------------------
+    # the update report (ship_sim_gym_amd/report.py)
+    # ------------------------------------------------------------------------------------------------
+    def report_device(self, batch, stats=None, post=False):
+        """ssg_pop_report over a batch gae() has seen: every member's record, f64 [P, 24] on the device (report.REPORT_FIELDS; member m's
+        row is bit for bit NativePPO.report_device's on its shard with its clip and its rows).  Two launches for all members, no
+        synchronisation; on equal slices, per-member schedules and unequal slices alike.  stats: the f32 [P, rows, 4 or 8] tensor
+        update(..., stats=True) returned; member m's means are taken over the steps IT took in the last update() (the rows past them,
+        which a schedule leaves unwritten, are never read).  post=True: the post-update group under every member's parameters as they
+        are NOW and its own clip, which costs one ssg_pop_dist launch into a tensor of its own; batch["logp_all"] is left alone."""
+        torch = _torch()
+        from . import report as R
+        K, n_env = self._KN(batch)
+        P, dev, D = self.n_members, self.population.device, self.population.obs_dim
+        p = [self._flat(batch, k, torch.float32, (K, n_env)) for k in ("val", "ret", "adv")]
+        grp = (None, None, None, None)
+        if post:
+            act, logp = self._flat(batch, "act", torch.int32, (K, n_env)), self._flat(batch, "logp", torch.float32, (K, n_env))
+            self._flat(batch, "obs", torch.float32, (K, n_env, D))
+            new = self.dist({"rew": batch["rew"], "obs": batch["obs"]})  # (a dict of its own: the batch's logp_all stays the acting policy's)
+            bounds = torch.tensor([[float(x) for x in R.clip_bounds(c)] for c in self.clip], dtype=torch.float32).to(dev)
+            grp = (act, logp, C.c_void_p(new.data_ptr()), C.c_void_p(bounds.data_ptr()))
+        sp = rp = None
+        rows_max = cols = 0
+        if stats is not None:
+            if stats.dtype != torch.float32 or stats.device != dev or not stats.is_contiguous() or stats.dim() != 3 or int(stats.shape[0]) != P:
+                raise ValueError("PopulationPPO.report: stats must be a contiguous f32 [%d, rows, 4 or 8] tensor on %s (update(..., stats=True))"
+                                 % (P, dev))
+            rows_max, cols, sp = int(stats.shape[1]), int(stats.shape[2]), C.c_void_p(stats.data_ptr())
+            taken = self._last_taken or [rows_max] * P
+            rows = torch.tensor([min(int(t), rows_max) for t in taken], dtype=torch.int32).to(dev)
+            rp = C.c_void_p(rows.data_ptr())
+        need = R.scratch_nbytes(n_env, P)
+        if getattr(self, "_report_scratch", None) is None or self._report_scratch.numel() < need:
+            self._report_scratch = torch.zeros(need, dtype=torch.uint8, device=dev)
+        out = torch.empty((P, N.REPORT_COLS), dtype=torch.float64, device=dev)
+        h = self.env._h
+        with torch.cuda.device(dev):
+            N.check(N.lib().ssg_pop_report(h, P, K, *p, *grp, sp, rows_max, cols, rp, C.c_void_p(self._report_scratch.data_ptr()),
+                                           self._report_scratch.numel(), C.c_void_p(out.data_ptr()), self._stream()), h, "ssg_pop_report")
+        return out
+
+    def report(self, batch, stats=None, post=False):
+        """report_device's records as a dict of numpy arrays [P] (report.REPORT_FIELDS), plus ``lr``, ``clip``, ``step`` (the members'
+        Adam steps), ``updates`` and ``kl_coef_now`` (the device's coefficients, read with the same copy): ONE device-to-host copy."""
+        torch = _torch()
+        import numpy as np
+        from .report import REPORT_FIELDS
+        out = torch.cat([self.report_device(batch, stats, post), self.kl_coef.to(torch.float64).view(-1, 1)], dim=1).cpu().numpy()
+        rec = {k: out[:, i].copy() for i, k in enumerate(REPORT_FIELDS)}
+        rec.update(lr=np.array(self.lr, dtype=np.float64), clip=np.array(self.clip, dtype=np.float64),
+                   step=np.array(self._steps0(), dtype=np.int64), updates=int(self.updates), kl_coef_now=out[:, N.REPORT_COLS].copy())
+        return rec
 
     def exploit(self, src):
         """PBT's exploit on the device: member m takes the parameters and Adam moments of member src[m] (src[m] == m keeps).  A source

@@ -30,6 +30,10 @@ does per epoch (np.random.shuffle(inds), train/stable_baselines/ppo.py:90), each
 ``updates``, ``member``, epoch) — the object's count of update() calls, kept beside ``step`` and restored by ``load_state_dict``.
 ``draw_perm`` returns such rows, ``host_perm`` is the library's host restatement and ``perm_reference`` the numpy one.  The stream is the
 library's own: it is not seed-compatible with numpy or torch.
+
+``report(batch, stats, post)`` says how an update went — the explained variance of the value network, the means of the update's stats
+rows and, with ``post=True``, how far the policy moved — from two launches over the batch and one copy (ssg_ppo_report;
+ship_sim_gym_amd/report.py holds the record's fields, the numpy restatement and the CSV writer).
 """
 import ctypes as C
 
@@ -514,6 +518,62 @@ class NativePPO(DeviceTrainer):
     def load_into(self, net):
         """Copy the packed parameters into `net` (shaped like the policy: its parameters in torch.cat order)."""
         return load_packed(self.policy.params, net, "NativePPO.load_into: the module has %%d parameters, the policy %d" % self.n_params)
+
+    # ------------------------------------------------------------------------------------------------
+    # the update report (ship_sim_gym_amd/report.py)
+    # ------------------------------------------------------------------------------------------------
+    def _report(self, batch, stats, post):
+        """f64 [25] on the device: ssg_ppo_report's record, then the KL coefficient as it is now.  Enqueued only: no synchronisation."""
+        torch = _torch()
+        from . import report as R
+        dev = self.policy.device
+        val, ret, adv = (self._flat(batch, k, torch.float32) for k in ("val", "ret", "adv"))
+        if val.dim() != 2 or ret.shape != val.shape or adv.shape != val.shape:
+            raise ValueError("NativePPO.report: batch['val'], ['ret'] and ['adv'] must be [K, N] (gae() adds the last two)")
+        K, n_env = int(val.shape[0]), int(val.shape[1])
+        grp = (None, None, None)
+        if post:
+            act, logp = self._flat(batch, "act", torch.int32), self._flat(batch, "logp", torch.float32)
+            if act.numel() != K * n_env or logp.numel() != K * n_env:
+                raise ValueError("NativePPO.report: batch['act'] and ['logp'] must hold K*N entries")
+            # the CURRENT parameters' distribution, in a tensor of its own: batch["logp_all"] is the acting policy's and stays
+            own = {"obs": batch["obs"]}
+            new = self.dist(own)
+            grp = (C.c_void_p(act.data_ptr()), C.c_void_p(logp.data_ptr()), C.c_void_p(new.data_ptr()))
+        rows = cols = 0
+        sp = None
+        if stats is not None:
+            if stats.dtype != torch.float32 or stats.device != dev or not stats.is_contiguous() or stats.dim() != 2:
+                raise ValueError("NativePPO.report: stats must be a contiguous f32 [rows, 4 or 8] tensor on %s (update(..., stats=True))" % (dev,))
+            rows, cols, sp = int(stats.shape[0]), int(stats.shape[1]), C.c_void_p(stats.data_ptr())
+        need = R.scratch_nbytes(n_env, 1)
+        if getattr(self, "_report_scratch", None) is None or self._report_scratch.numel() < need:
+            self._report_scratch = torch.zeros(need, dtype=torch.uint8, device=dev)
+        out = torch.empty(N.REPORT_COLS + 1, dtype=torch.float64, device=dev)
+        h = self.env._h
+        with torch.cuda.device(dev):
+            N.check(N.lib().ssg_ppo_report(h, K, n_env, C.c_void_p(val.data_ptr()), C.c_void_p(ret.data_ptr()), C.c_void_p(adv.data_ptr()),
+                                           *grp, float(self.hp.clip), sp, rows, cols, C.c_void_p(self._report_scratch.data_ptr()),
+                                           self._report_scratch.numel(), C.c_void_p(out.data_ptr()), self._stream()), h, "ssg_ppo_report")
+            out[N.REPORT_COLS:].copy_(self.kl_coef)
+        return out
+
+    def report_device(self, batch, stats=None, post=False):
+        """ssg_ppo_report over a batch gae() has seen: the f64 [24] record on the device (report.REPORT_FIELDS; the layout and the order
+        of operations: include/shipsim.h, restated by report.report_reference).  Two launches, no synchronisation.  stats: the f32
+        [rows, 4 or 8] tensor update(..., stats=True) returned — its column means go into the record.  post=True: the post-update group
+        (approximate KL, PPO2's approxkl, the clip fraction over the whole batch under the parameters as they are NOW), which costs
+        one ssg_ppo_dist launch into a tensor of its own; batch["logp_all"], the acting policy's distribution, is left alone."""
+        return self._report(batch, stats, post)[:N.REPORT_COLS]
+
+    def report(self, batch, stats=None, post=False):
+        """report_device's record as a dict of Python floats (report.REPORT_FIELDS), plus ``lr``, ``clip``, ``step``, ``updates`` and
+        ``kl_coef_now`` (the device's coefficient, read with the same copy): ONE device-to-host copy."""
+        from .report import record_dict
+        row = self._report(batch, stats, post).cpu().tolist()
+        rec = record_dict(row[:N.REPORT_COLS])
+        rec.update(lr=float(self.hp.lr), clip=float(self.hp.clip), step=int(self.step), updates=int(self.updates), kl_coef_now=row[N.REPORT_COLS])
+        return rec
 
     # ------------------------------------------------------------------------------------------------
     # state (ship_sim_gym_amd/checkpoint.py)

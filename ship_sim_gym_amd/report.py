@@ -1,0 +1,185 @@
+"""The update report — how an update went, reduced on the device (ssg_ppo_report / ssg_pop_report), and the CSV the trainers keep of it.
+
+The reference's Stable-Baselines script runs PPO2 with verbose=1 and a tensorboard_log (train/stable_baselines/ppo.py:88-90), which prints
+and logs explained_variance, approxkl, clipfrac, policy_entropy, policy_loss and value_loss per update; RLlib's PPO
+(train/rllib/ppo.py:26-41, train/rllib/pbt.py:47-74) reports vf_explained_var, kl, entropy, policy_loss, vf_loss, cur_kl_coeff and cur_lr.
+``NativePPO.report`` / ``PopulationPPO.report`` return the same quantities from two launches over the rollout batch (plus one
+ssg_ppo_dist / ssg_pop_dist launch with ``post=True``, which measures how far the update moved the policy); ``report_reference`` restates
+the launches in numpy in their order of operations, and the device's record is that restatement bit for bit.  ``ProgressWriter`` is the
+counterpart of Stable-Baselines' progress.csv.
+
+Out of scope: schedules of lr / clip (the columns are there for when they come), merging several ranks' records, the entropy or exact KL
+of the post-update policy over the whole batch (both need exp), a TensorBoard event writer.
+"""
+import ctypes as C
+import os
+import time
+
+import numpy as np
+
+from . import _native as N
+from .ppo import _tree256
+
+# the record's f64 columns (include/shipsim.h); 12..19 are named after the stats rows of the update entry points
+REPORT_FIELDS = (
+    "n", "ret_mean", "ret_var", "err_mean", "err_var", "explained_variance", "value_mean", "adv_mean",
+    "post", "approx_kl", "approxkl_ppo2", "clip_fraction",
+    "policy_loss", "value_loss", "entropy", "clip_fraction_minibatch", "kl", "grad_norm", "kl_coef", "unused19",
+    "stats_rows", "unused21", "unused22", "unused23",
+)
+assert len(REPORT_FIELDS) == N.REPORT_COLS
+REPORT_SUMS = 9  # the walk's sums per lane: ret, ret^2, err, err^2, val, adv, d, d^2, clipped
+PROGRESS_FIELDS = tuple(f for f in REPORT_FIELDS if not f.startswith("unused"))
+PROGRESS_COLUMNS = ("update", "timesteps", "member") + PROGRESS_FIELDS + ("lr", "clip", "t")
+
+
+def clip_bounds(clip):
+    """ssg_report_clip_bounds: (lo, hi) as np.float32 — (float)log1p(-clip), -inf from clip 1 on, and (float)log1p(clip), formed in
+    double by the library, so that the host and the device compare against the same bits."""
+    out = (C.c_float * 2)()
+    N.check(N.lib().ssg_report_clip_bounds(float(clip), out), None, "ssg_report_clip_bounds")
+    return np.float32(out[0]), np.float32(out[1])
+
+
+def report_reference(val, ret, adv, act=None, logp=None, logp_all_new=None, clip=0.2, stats=None, rows=None):
+    """ssg_ppo_report restated in numpy, in the device's order of operations: the f64 [24] record of ONE policy (a population member:
+    its own columns, bounds and rows).  val / ret / adv f32 [K, n]; the post-update group act i32 [K, n], logp f32 [K, n] and
+    logp_all_new f32 [K, n, 4] together or not at all; stats f32 [rows_max, 4 or 8] with rows (None: all of them) used.
+
+    The walk: per env the f64 sums in ascending t, every product and sum separately rounded; the 256-env blocks' halving trees; the
+    blocks' partials added per thread (block b, b + 256, ...) and one more tree; then the record's formulas."""
+    f64 = np.float64
+    val, ret, adv = (np.asarray(x, dtype=np.float32) for x in (val, ret, adv))
+    K, n = val.shape
+    post = logp_all_new is not None
+    if post != (act is not None) or post != (logp is not None):
+        raise ValueError("report_reference: act, logp and logp_all_new go together")
+    nb = -(-n // 256)
+    s = np.zeros((nb * 256, REPORT_SUMS))
+    if post:
+        act, logp = np.asarray(act).astype(np.int64) & 3, np.asarray(logp, dtype=np.float32)
+        lpa = np.asarray(logp_all_new, dtype=np.float32).reshape(K, n, 4)
+        lo, hi = clip_bounds(clip)
+        cols = np.arange(n)
+    for t in range(K):
+        r, v, a = ret[t].astype(f64), val[t].astype(f64), adv[t].astype(f64)
+        err = r - v
+        s[:n, 0] += r
+        s[:n, 1] += r * r
+        s[:n, 2] += err
+        s[:n, 3] += err * err
+        s[:n, 4] += v
+        s[:n, 5] += a
+        if post:
+            d = lpa[t, cols, act[t]] - logp[t]  # one f32 subtraction
+            dd = d.astype(f64)
+            s[:n, 6] += dd
+            s[:n, 7] += dd * dd
+            s[:n, 8] += ((d > hi) | (d < lo)).astype(f64)
+    part = np.zeros((-(-nb // 256) * 256, REPORT_SUMS))
+    for b in range(nb):
+        part[b] = _tree256(s[b * 256: b * 256 + 256].copy())
+    acc = np.zeros((256, REPORT_SUMS))
+    for r in range(part.shape[0] // 256):  # thread j: partials j, j + 256, ... in that order
+        acc += part[r * 256: r * 256 + 256]
+    tot = _tree256(acc)
+    out = np.zeros(N.REPORT_COLS)
+    cnt = f64(K) * f64(n)
+    with np.errstate(all="ignore"):
+        mr = tot[0] / cnt
+        vr = (tot[1] - tot[0] * mr) / cnt
+        vr = f64(0.0) if vr < 0.0 else vr
+        me = tot[2] / cnt
+        ve = (tot[3] - tot[2] * me) / cnt
+        ve = f64(0.0) if ve < 0.0 else ve
+        out[0:5] = cnt, mr, vr, me, ve
+        out[5] = np.nan if vr == 0.0 else f64(1.0) - ve / vr
+        out[6], out[7] = tot[4] / cnt, tot[5] / cnt
+        if post:
+            out[8], out[9], out[10], out[11] = 1.0, -(tot[6] / cnt), f64(0.5) * (tot[7] / cnt), tot[8] / cnt
+        if stats is not None:
+            st = np.asarray(stats, dtype=np.float32)
+            st = st.reshape(-1, st.shape[-1])
+            if st.shape[1] not in (4, 8) or st.shape[0] < 1:
+                raise ValueError("report_reference: stats must be f32 [rows >= 1, 4 or 8]")
+            rows = st.shape[0] if rows is None else max(0, min(int(rows), st.shape[0]))
+            colsum = np.zeros(st.shape[1])
+            for j in range(rows):  # one thread per column, its rows in row order
+                colsum += st[j].astype(f64)
+            if rows > 0:
+                out[N.REPORT_STATS: N.REPORT_STATS + st.shape[1]] = colsum / f64(rows)
+            out[N.REPORT_ROWS] = rows
+    return out
+
+
+def record_dict(row):
+    """A record row (24 numbers) as {field: Python float}."""
+    return {k: float(x) for k, x in zip(REPORT_FIELDS, row)}
+
+
+def scratch_nbytes(n_envs, n_members=1):
+    """ssg_ppo_report_workspace_nbytes."""
+    need = C.c_size_t()
+    N.check(N.lib().ssg_ppo_report_workspace_nbytes(int(n_envs), int(n_members), C.byref(need)), None, "ssg_ppo_report_workspace_nbytes")
+    return need.value
+
+
+class ProgressWriter(object):
+    """The CSV of the update reports: one row per member per update, ``update, timesteps, member``, then the record's fields (without
+    the unused columns), ``lr, clip`` and ``t`` — the host's seconds since the writer was made, the only column that is not
+    reproducible (as in ``MonitorWriter``).  Floats are written with %r, so they read back bit for bit.
+
+    resume=False starts the file anew.  resume=True leaves it; ``cut_back(update)`` then keeps the header and the rows whose ``update``
+    is at most the checkpoint's and cuts the rest (through FILE.tmp and os.replace), so that a run that is saved, killed and resumed
+    leaves the uninterrupted run's file in every column but ``t``."""
+
+    def __init__(self, path, resume=False):
+        self.path = os.fspath(path)
+        self.t_start = time.time()
+        if resume and os.path.exists(self.path):  # (a run resumed with a progress file it did not have before starts one)
+            self._read()
+        else:
+            with open(self.path, "w") as f:
+                f.write(",".join(PROGRESS_COLUMNS) + "\n")
+
+    def _read(self):
+        try:
+            with open(self.path) as f:
+                lines = f.read().splitlines(True)
+            if not lines or lines[0].strip() != ",".join(PROGRESS_COLUMNS):
+                raise ValueError("no progress header")
+            return lines
+        except (OSError, ValueError) as ex:
+            raise ValueError("ProgressWriter: %s is not a progress file of this format (%s)" % (self.path, ex))
+
+    def cut_back(self, update):
+        """Keep the header and the rows with ``update`` <= update; returns how many rows were cut."""
+        lines = self._read()
+        keep = [lines[0]] + [ln for ln in lines[1:] if ln.strip() and int(ln.split(",", 1)[0]) <= int(update)]
+        with open(self.path + ".tmp", "w") as f:
+            f.writelines(ln if ln.endswith("\n") else ln + "\n" for ln in keep)
+        os.replace(self.path + ".tmp", self.path)
+        return len(lines) - len(keep)
+
+    def write(self, update, timesteps, records, lr, clip):
+        """Append one row per member: records is one record (a dict of REPORT_FIELDS, as NativePPO.report returns) or a dict of arrays
+        [P] (PopulationPPO.report); lr / clip are scalars or [P]."""
+        t = round(time.time() - self.t_start, 6)
+        cols = [np.atleast_1d(np.asarray(records[k], dtype=np.float64)) for k in PROGRESS_FIELDS]
+        P = cols[0].shape[0]
+        lr, clip = (np.broadcast_to(np.asarray(x, dtype=np.float64), (P,)) for x in (lr, clip))
+        with open(self.path, "a") as f:
+            for m in range(P):
+                f.write("%d,%d,%d,%s,%r,%r,%r\n" % (int(update), int(timesteps), m, ",".join("%r" % float(c[m]) for c in cols),
+                                                  float(lr[m]), float(clip[m]), t))
+        return P
+
+
+def read_progress(path):
+    """A progress file as {column: numpy array} (int64 for update / timesteps / member, f64 otherwise)."""
+    with open(os.fspath(path)) as f:
+        names = f.readline().strip().split(",")
+        rows = [line.strip().split(",") for line in f if line.strip()]
+    ints = ("update", "timesteps", "member")
+    return {name: np.array([int(r[i]) if name in ints else float(r[i]) for r in rows], dtype=np.int64 if name in ints else np.float64)
+            for i, name in enumerate(names)}

@@ -45,10 +45,16 @@ With ``--perm`` (the minibatch permutations drawn by the library, ssg_pop_perm),
     allocated before it (torch's allocator statistics; the result included); and GAE + update (2 epochs x 4 minibatches, reading the
     first 2 rows) with each draw of all perm_epochs rows INSIDE the timed region, all four alternating.
 
+With ``--report`` (the update report, ssg_pop_report), instead, per configuration:
+
+(i) ``PopulationPPO.report_device`` alone without and with the post-update group (two launches; one ssg_pop_dist launch more), GAE alone
+    (the yardstick) and GAE + update without and with a report (no post group; the update then writes its stats rows) behind it, all
+    alternating; ``update_spread`` is (max - min) / median over the plain GAE + update's repeats.
+
 Each figure: 2 warm-up runs, then the median of ``--repeats`` (5) runs, alternating the two paths, each bracketed by a synchronize and
 timed with HIP events.  One JSON line on stdout.
 
-    python tools/population_timing.py [--configs 16x4096,120x512] [--horizon 32] [--repeats 5] [--sched | --slices | --adv-norm | --perm]
+    python tools/population_timing.py [--configs 16x4096,120x512] [--horizon 32] [--repeats 5] [--sched | --slices | --adv-norm | --perm | --report]
 """
 import argparse
 import importlib.util
@@ -404,6 +410,52 @@ def measure_adv_norm(mod, members, n, horizon, repeats, dev, epochs=2, minibatch
     return out
 
 
+def measure_report(mod, members, n, horizon, repeats, dev, epochs=2, minibatches=4):
+    from ship_sim_gym_amd.population import NativePopulation, PopulationPPO
+    torch.manual_seed(0)
+    P, N = members, members * n
+    env = mod.ShipVecEnv(N, mod.GameConfig, mod.EnvConfig, device=dev, n_maps=64)
+    D, A = env.states_history, env.action_space.n
+    scale = torch.full((D,), float(max(env.bounds)), dtype=torch.float64, device=dev)
+    pop = NativePopulation.from_actor_critics([mod.ActorCritic(D, A).to(dev) for _ in range(P)], scale)
+    p0 = pop.params.clone()
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    env.reset_tensor()
+    b = dict(env.rollout_population(pop, horizon, uniforms=torch.rand((horizon, N), generator=gen, device=dev)))
+    samples = horizon * n
+    perm = torch.rand((P, epochs, samples), generator=gen, device=dev).argsort(dim=-1)
+    ppo = PopulationPPO(pop, env)
+    nb_r = dict(b)
+    ppo.gae(nb_r)
+    st_r = torch.randn((P, epochs * minibatches, 4), device=dev)
+
+    def restore(k):
+        pop.params.copy_(p0)
+        ppo.adam_mv.zero_()
+        ppo.step = 0
+        ppo.member_steps = [0] * P
+
+    def upd(with_report):
+        def run():
+            nb = dict(b)
+            ppo.gae(nb)
+            st = ppo.update(nb, perm, epochs, minibatches, stats=with_report)
+            if with_report:
+                ppo.report_device(nb, stats=st)
+        return run
+
+    t = _alternate([("report", lambda: ppo.report_device(nb_r, stats=st_r)), ("report_post", lambda: ppo.report_device(nb_r, stats=st_r, post=True)),
+                    ("gae", lambda: ppo.gae(dict(b))), ("update", upd(False)), ("update_report", upd(True))], repeats, before=restore)
+    out = {"members": P, "envs_per_member": n, "horizon": horizon, "epochs": epochs, "minibatches": minibatches}
+    for k, v in t.items():
+        out[k + "_ms"] = statistics.median(v)
+        out[k + "_ms_all"] = [round(x, 4) for x in v]
+    out["update_spread"] = (max(t["update"]) - min(t["update"])) / statistics.median(t["update"])
+    env.close()
+    return out
+
+
 def _peak_bytes(fn):
     """Peak device memory during fn() above what was allocated before it (the result included)."""
     torch.cuda.synchronize()
@@ -474,8 +526,13 @@ def main():
     ap.add_argument("--slices", action="store_true", help="time unequal env slices (ssg_pop_set_slices) instead")
     ap.add_argument("--adv-norm", action="store_true", help="time per-minibatch advantage normalisation against batch mode instead")
     ap.add_argument("--perm", action="store_true", help="time the permutation draws (torch's against the library's) and GAE + update with each instead")
+    ap.add_argument("--report", action="store_true", help="time the update report alone, GAE alone and GAE + update with and without a report instead")
     a = ap.parse_args()
     mod = _ppo()
+    if a.report:
+        res = [measure_report(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.horizon, a.repeats, "cuda:0") for c in a.configs.split(",")]
+        print(json.dumps({"population_report_timing": res}))
+        return
     if a.perm:
         res = [measure_perm(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.horizon, a.repeats, "cuda:0") for c in a.configs.split(",")]
         print(json.dumps({"population_perm_timing": res}))

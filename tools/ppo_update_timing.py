@@ -9,7 +9,7 @@ every update from the same parameters' values (their own copies) and draw their 
 line on stdout.  The kernels alone: `rocprofv3 --kernel-trace --stats -- python tools/ppo_update_timing.py --only native` (tools/README.md).
 
     python tools/ppo_update_timing.py [--configs 65536x32,4096x64] [--repeats 7] [--only torch|native] [--ext] [--separate-value] [--ret-filter]
-                                      [--adv-norm] [--perm] [--timeout-bootstrap] [--checkpoint] [--dp] [--episode-log]
+                                      [--adv-norm] [--perm] [--timeout-bootstrap] [--checkpoint] [--dp] [--episode-log] [--report]
 
 --ext adds, in the same run, the extended update (NativePPO with vf_clip 0.2, max_grad_norm 0.5, kl_coef 1.0, kl_target 0.01: GAE, the
 ssg_ppo_dist launch, ssg_ppo_update_ext) as the path "native_ext", and the ssg_ppo_dist launch alone as "dist".
@@ -38,6 +38,10 @@ ssg_ppo_apply_shards alone on 1, 2 and 8 gathered rows (the plain loss: one laun
 --episode-log adds, in the same run and alternating with the others: "eplog_append" (EpisodeLog.append alone: ssg_episode_log_append, three
 launches), "episode_stats" (ssg_pop_episode_stats alone with one member: the closest existing walk, one launch), "gae_alone" (ssg_ppo_gae
 alone) and "native_eplog" (the append, then the whole GAE + update), to set against "native".
+--report adds, in the same run and alternating with the others: "report" (NativePPO.report_device alone without the post-update group:
+ssg_ppo_report, two launches, with the stats rows of an update), "report_post" (the same with the post-update group: one ssg_ppo_dist
+launch more), "gae_only" (ssg_ppo_gae alone, the yardstick) and "native_report" (the whole GAE + update with stats rows, then the report
+without the post group), to set against "native".
 """
 import argparse
 import importlib.util
@@ -92,7 +96,8 @@ def _wall_ms(fn):
 
 
 def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext=False, separate_value=False, ret_filter=False,
-            adv_norm=False, perm=False, timeout_bootstrap=False, checkpoint=False, checkpoint_dir=None, dp=False, episode_log=False):
+            adv_norm=False, perm=False, timeout_bootstrap=False, checkpoint=False, checkpoint_dir=None, dp=False, episode_log=False,
+            report=False):
     from ship_sim_gym_amd.policy import NativePolicy
     from ship_sim_gym_amd.ppo import NativePPO
     torch.manual_seed(0)
@@ -125,7 +130,7 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
         mod.torch_update(net, opt, dict(b, rew=b["rew"].float(), done=b["done"].float(), act=b["act"].long()), b["last_val"], epochs,
                          minibatches, g_t)
 
-    def native_path(trainer, gen, before=None, **gae_kw):
+    def native_path(trainer, gen, before=None, after=None, **gae_kw):
         """The whole GAE + update of `trainer` from the start parameters, its permutations drawn from gen (None: by the library)."""
         def run():
             with torch.no_grad():
@@ -137,7 +142,10 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
             nb = dict(b)
             trainer.gae(nb, **gae_kw)
             rows = None if gen is None else torch.stack([torch.randperm(n, device=dev, generator=gen) for _ in range(epochs)])
-            trainer.update(nb, rows, epochs, minibatches)
+            if after is None:
+                trainer.update(nb, rows, epochs, minibatches)
+            else:
+                after(nb, trainer.update(nb, rows, epochs, minibatches, stats=True))
         return run
 
     from ship_sim_gym_amd.ret_filter import ReturnFilter
@@ -194,6 +202,13 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
                                                   env._stream()), env._h, "ssg_pop_episode_stats")
         paths += [("eplog_append", lambda: eplog.append(b)), ("episode_stats", run_episode_stats), ("gae_alone", lambda: ppo.gae(dict(b))),
                   ("native_eplog", native_path(ppo, seeded(), before=lambda: eplog.append(b)))]
+    if report:  # the report reads a batch GAE has seen and the stats rows of an update; it changes neither
+        nb_r = dict(b)
+        ppo.gae(nb_r)
+        st_r = torch.randn((epochs * minibatches, 4), device=dev)
+        paths += [("report", lambda: ppo.report_device(nb_r, stats=st_r)), ("report_post", lambda: ppo.report_device(nb_r, stats=st_r, post=True)),
+                  ("gae_only", lambda: ppo.gae(dict(b))),
+                  ("native_report", native_path(ppo, seeded(), after=lambda nb, st: ppo.report_device(nb, stats=st)))]
     if checkpoint:
         paths.append(("checkpoint_save", run_checkpoint_save))
     if dp:
@@ -258,11 +273,13 @@ def main():
                                                       "launch alone on 1, 2 and 8 rows")
     ap.add_argument("--episode-log", action="store_true", help="also time the episode log's append alone, ssg_pop_episode_stats alone, GAE "
                                                                "alone, and the whole GAE + update with the append ahead of it")
+    ap.add_argument("--report", action="store_true", help="also time the update report alone (without and with the post-update group), GAE "
+                                                          "alone, and the whole GAE + update with the report behind it")
     a = ap.parse_args()
     mod = _ppo()
     res = [measure(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.repeats, a.only, "cuda:0", ext=a.ext, separate_value=sep, ret_filter=a.ret_filter,
                    adv_norm=a.adv_norm, perm=a.perm, timeout_bootstrap=a.timeout_bootstrap, checkpoint=a.checkpoint,
-                   checkpoint_dir=a.checkpoint_dir, dp=a.dp, episode_log=a.episode_log)
+                   checkpoint_dir=a.checkpoint_dir, dp=a.dp, episode_log=a.episode_log, report=a.report)
            for c in a.configs.split(",") for sep in ([False, True] if a.separate_value else [False])]
     print(json.dumps({"ppo_update_timing": res}))
 

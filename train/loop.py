@@ -121,3 +121,24 @@ def episode_log_section(eplog):
 def load_episode_log(ckpt, eplog):
     if eplog is not None:
         eplog.load_state_dict(ckpt["episode_log"])
+
+
+def add_report_flags(ap):
+    """The flags both command lines share for the update report."""
+    ap.add_argument("--report", action="store_true",
+                    help="after every update print the explained variance of the value network and the means of the policy loss, value "
+                         "loss, entropy and clip fraction over the update's minibatches, reduced on the device (needs --mode native "
+                         "--update native where there is a choice); default: off")
+    ap.add_argument("--report-kl", action="store_true",
+                    help="also measure how far the update moved the policy (approximate KL, PPO2's approxkl, the clip fraction over the "
+                         "whole batch): one more policy forward over the batch per update; implies --report")
+    ap.add_argument("--progress", default=None, metavar="FILE",
+                    help="write the report of every update to FILE as CSV, one row per policy (Stable-Baselines' progress.csv); implies --report")
+
+
+def open_progress(path, resume=False):
+    """The ProgressWriter of a run that asks for one, else None.  A resumed run keeps the file and cuts it back to the checkpoint's update."""
+    if not path:
+        return None
+    from ship_sim_gym_amd.report import ProgressWriter
+    return ProgressWriter(path, resume=bool(resume))

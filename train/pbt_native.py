@@ -60,6 +60,15 @@ member's own gamma): one library call per rollout between the rollout and GAE.  
 as they are; a member's statistics travel with its weights on an exploit, the per-env returns in flight stay with their envs.
 --reward-clip C clamps the normalised rewards to +-C (default 10; 0: none).
 
+--report prints, after every update, one table row per member: the explained variance of its value network over its slice of the
+rollout and the means of its policy loss, value loss, entropy and clip fraction over ITS steps of the update (with an extended term on
+also the KL, the gradient norm and the coefficient) — what RLlib reports per trial and iteration (train/rllib/pbt.py:47-74:
+vf_explained_var, policy_loss, vf_loss, entropy, kl) — from two launches for the whole population and one copy
+(ship_sim_gym_amd/report.py, ssg_pop_report).  --report-kl adds how far the update moved each member's policy (approximate KL, PPO2's
+approxkl, the clip fraction over its whole batch under its own clip) for one more ssg_pop_dist launch; --progress FILE writes the
+records as CSV, one row per member per update, and with --resume cuts the file back to the checkpoint's update first.  The records are
+taken before a perturbation that is due.  Off by default; the three may change between a run and its resumption.
+
 --save FILE writes a checkpoint at the end (ship_sim_gym_amd/checkpoint.py; the reference's checkpoint_at_end, train/rllib/pbt.py:53),
 --save-every U also after every U updates (its checkpoint_freq, :54), --save-best FILE after every update in which the best member's
 episode_reward_mean exceeds the best so far (never after an update in which no episode ended; the file holds the whole population and
@@ -102,7 +111,8 @@ def clamp_schedule(num_sgd_iter, sgd_minibatch_size, samples, max_epochs):
 
 
 # what a resumed run may change: everything else in train()'s arguments is the run's configuration (the checkpoint's "config" section)
-CONFIG_EXEMPT = ("updates", "save", "save_every", "save_best", "resume", "eval_every", "eval_episodes", "log", "return_details")
+CONFIG_EXEMPT = ("updates", "save", "save_every", "save_best", "resume", "eval_every", "eval_episodes", "log", "return_details", "report",
+                 "report_kl", "progress")
 RESUME_SECTIONS = ("population", "trainer", "env", "scheduler", "loop", "config")
 
 
@@ -176,6 +186,7 @@ def make_arg_parser():
                     help="write a checkpoint after every update in which the best member's episode_reward_mean exceeds the best so far "
                          "(the whole population; the file names the member)")
     loop.add_episode_log_flags(ap)
+    loop.add_report_flags(ap)
     ap.add_argument("--resume", default=None, metavar="FILE",
                     help="continue the run a checkpoint was saved from, bit for bit: repeat the original command line; --updates stays "
                          "the TOTAL and may be raised")
@@ -411,11 +422,34 @@ def draw_permutations(run, state):
 def update_population(run, state, batch, perm):
     """The population's PPO update on one rollout: the common schedule, or every member's own, on max(iters) of the drawn rows."""
     if not run.per_member:
-        return run.ppo.update(batch, perm, run.epochs, run.minibatches)
+        return run.ppo.update(batch, perm, run.epochs, run.minibatches, stats=run.report)
     mbs = [run.ppo.minibatches_for_size(s, state.member_samples[m]) for m, s in enumerate(state.sizes)] if run.mutate_schedule else state.counts
     if perm is not None:
         perm = [q[:max(state.iters)].contiguous() for q in perm] if run.sliced else perm[:, :max(state.iters)].contiguous()
-    run.ppo.update(batch, perm, state.iters, mbs)
+    return run.ppo.update(batch, perm, state.iters, mbs, stats=run.report)
+
+
+def report_table(rec, extended):
+    """The update report's table, one row per member (rec: PopulationPPO.report's arrays): explained variance, the update's minibatch
+    means over the member's own steps and, when they were computed, the extended terms and the post-update group."""
+    cols = [("expl.var", "explained_variance", "%+.4f"), ("policy loss", "policy_loss", "%+.5f"), ("value loss", "value_loss", "%.5f"),
+            ("entropy", "entropy", "%.5f"), ("clip frac", "clip_fraction_minibatch", "%.4f")]
+    if extended:
+        cols += [("kl", "kl", "%.6f"), ("grad norm", "grad_norm", "%.4f"), ("kl coef", "kl_coef", "%.4f")]
+    if rec["post"].any():
+        cols += [("approx kl", "approx_kl", "%.6f"), ("approxkl", "approxkl_ppo2", "%.6f"), ("clip frac after", "clip_fraction", "%.4f")]
+    lines = ["%6s  %s" % ("member", "  ".join("%15s" % c[0] for c in cols))]
+    for m in range(len(rec["n"])):
+        lines.append("%6d  %s" % (m, "  ".join("%15s" % (c[2] % rec[c[1]][m]) for c in cols)))
+    return "\n".join(lines)
+
+
+def report_update(run, u, batch, st, log):
+    """--report: one table per update from ssg_pop_report's records (one copy to the host), and the --progress rows."""
+    rec = run.ppo.report(batch, stats=st, post=run.report_kl)
+    log("update %d  report\n%s" % (u, report_table(rec, st.shape[2] == 8)))
+    if run.progress_writer is not None:
+        run.progress_writer.write(u, u * run.horizon * run.n_total, rec, rec["lr"], rec["clip"])
 
 
 def account(state, u, ep, log):
@@ -474,17 +508,21 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
           separate_value=False, mutate_schedule=False, max_epochs=30, eval_every=0, eval_episodes=1, envs=None, mutate_batch=False,
           batch_shares=None, quantum=None, obs_filter=False, norm_reward=False, reward_clip=10.0, adv_norm="batch", perm="torch",
           timeout_bootstrap=False, hidden=64, env_kw=None, save=None, save_every=0, save_best=None, resume=None, episode_log=None,
-          episode_log_capacity=65536):
+          episode_log_capacity=65536, report=False, report_kl=False, progress=None):
     config = run_config(**dict(locals()))  # (first statement: the arguments, nothing else)
     run = argparse.Namespace(**locals())  # the run record: the arguments and the config; plan() and build() add to it
+    run.report = bool(report or report_kl or progress)  # (--report-kl and --progress imply --report)
     import torch
     from ship_sim_gym_amd.ppo import chunk_split
     # check (every refusal on the host, then the file a run resumes from, before any device work), build and bind, resume
     plan(run)
     ckpt = loop.open_resume(resume, config, loop.resume_sections(RESUME_SECTIONS, obs_filter, norm_reward, episode_log), exempt=CONFIG_EXEMPT) if resume else None
     state = build(run, log)
+    run.progress_writer = loop.open_progress(progress, resume)
     if ckpt is not None:
         load_run(run, state, ckpt, log)
+        if run.progress_writer is not None:
+            run.progress_writer.cut_back(state.update)  # (the rows of updates the checkpoint has not seen are written again)
         log("resumed from %s: %d updates done, continuing at update %d of %d" % (resume, state.update, state.update + 1, updates))
     out, evals = None, []
     for u in range(state.update + 1, updates + 1):
@@ -498,7 +536,9 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
         if run.rflt is not None:
             run.rflt.set_gamma(run.ppo.gamma)  # (the members' own discounts, whatever they currently are)
         run.ppo.gae(batch, return_filter=run.rflt)
-        update_population(run, state, batch, draw_permutations(run, state))
+        st_upd = update_population(run, state, batch, draw_permutations(run, state))
+        if run.report:
+            report_update(run, u, batch, st_upd, log)
         ended = account(state, u, ep, log)
         if run.eplog is not None:  # the cycle's one copy of the ring to the host
             log("update %d  episode log: %d rows written, %d in all" % (u, run.epwriter.flush(), run.eplog.rows_written))

@@ -8,6 +8,7 @@ leave the GPU; the policy is a small MLP in fp32.
                               [--eval-every U --eval-episodes E] [--obs-filter [--save-obs-filter FILE]]
                               [--norm-reward [--reward-clip C]]
                               [--save FILE [--save-every U]] [--save-best FILE] [--resume FILE] [--gpus W]
+                              [--report [--report-kl]] [--progress FILE]
 
 Four ways to run the rollout loop (the reference's `model.learn` -> runner.run(): one `env.step(actions)` per policy
 forward, train/stable_baselines/ppo.py:84-100,122-123) — same arithmetic, same results bit for bit:
@@ -57,6 +58,15 @@ history, the best score) and the run's arguments, and ``--resume FILE`` continue
 line and add ``--resume``; ``--updates`` stays the TOTAL and may be raised, the ``--save*`` and ``--eval-*`` options may change, any
 other argument that differs from the file's is refused.  In the other modes ``--save`` writes the policy alone (the torch optimiser's
 state is out of scope), which train/evaluate_native.py ``--checkpoint FILE`` reads and ``--resume`` refuses.
+
+``--report`` (``--mode native --update native`` only; default off): after every update one line with the explained variance of the value
+network over the rollout and the means of the policy loss, value loss, entropy and clip fraction over the update's minibatches —
+what PPO2's verbose=1 prints per update (train/stable_baselines/ppo.py:88-90) — reduced on the device by two launches and read with
+one copy (ship_sim_gym_amd/report.py, ssg_ppo_report).  ``--report-kl`` adds how far the update moved the policy (the approximate KL,
+PPO2's approxkl and the clip fraction over the whole batch under the new parameters) for one more policy forward over the batch;
+``--progress FILE`` writes every update's record as a CSV row (PPO2's progress.csv) and, with ``--resume``, cuts the file back to the
+checkpoint's update first.  The three may change between a run and its resumption; without them nothing is computed or printed.
+More than one rank refuses them.
 
 ``--gpus W`` (``--mode native --update native`` only): ONE policy trained data-parallel on W ranks, one per GPU, as the RLlib scripts
 train one policy from the experience of their workers (train/rllib/ppo.py:34-35, train/rllib/pbt.py:57-58).  The script starts the W
@@ -252,7 +262,7 @@ def rollout(shards, horizon, mode, gen, policy=None, job=None):
 
 # what a resumed run may change: everything else in train()'s arguments is the run's configuration (the checkpoint's "config" section)
 CONFIG_EXEMPT = ("updates", "save", "save_every", "save_best", "save_obs_filter", "resume", "eval_every", "eval_episodes", "eval_envs", "log",
-                 "return_details")
+                 "return_details", "report", "report_kl", "progress")
 RESUME_SECTIONS = ("policy", "trainer", "env", "loop", "config")
 open_resume = loop.open_resume  # (importable from here, as it was)
 
@@ -293,11 +303,18 @@ EPISODE_LOG_REQUIREMENTS = (
 )
 
 
+# The update report's rows, likewise (a: getattr, since callers from before the flags pass argument sets without them).
+REPORT_REQUIREMENTS = tuple(
+    (name, flag, (lambda a, name=name: bool(getattr(a, name, None))), ("mode", "update"), True,
+     "the record is reduced from the device update's buffers and stats rows; a job's ranks would each report their own shard")
+    for name, flag in (("progress", "--progress"), ("report_kl", "--report-kl"), ("report", "--report")))
+
+
 def check_requirements(args, ranks, error=None):
-    """Walk EPISODE_LOG_REQUIREMENTS and REQUIREMENTS over the arguments `args` (a dict) of a run of `ranks` ranks.  The first row that is on and misses a need, or is
+    """Walk EPISODE_LOG_REQUIREMENTS, REPORT_REQUIREMENTS and REQUIREMENTS over the arguments `args` (a dict) of a run of `ranks` ranks.  The first row that is on and misses a need, or is
     refused with more than one rank, goes to the parser's `error` with the flags in the text, or is a ValueError with train()'s names."""
     a = argparse.Namespace(**dict(args, ranks=ranks))
-    for name, flag, on, needs, one_rank_only, why in EPISODE_LOG_REQUIREMENTS + REQUIREMENTS:
+    for name, flag, on, needs, one_rank_only, why in EPISODE_LOG_REQUIREMENTS + REPORT_REQUIREMENTS + REQUIREMENTS:
         text = None
         if on(a) and not all(NEEDS[k][2](a) for k in needs):
             text = ("%s needs %s (%s)" % (flag, " ".join(NEEDS[k][0] for k in needs), why) if error else
@@ -428,8 +445,11 @@ def native_update(run, u, log):
     run.ppo.gae(nb, run.gamma, run.lam, return_filter=run.rflt)
     n = run.horizon * run.n_local  # (a rank shuffles its own samples)
     rows = None if run.perm == "native" else torch.stack([torch.randperm(n, device=run.dev, generator=run.gen) for _ in range(run.epochs)])
-    st_upd = run.ppo.update(nb, rows, run.epochs, run.minibatches, stats=run.flt is not None or run.rflt is not None)
-    if st_upd is not None:
+    filters = run.flt is not None or run.rflt is not None
+    st_upd = run.ppo.update(nb, rows, run.epochs, run.minibatches, stats=filters or run.report)
+    if run.report:
+        report_update(run, u, nb, st_upd, log)
+    if filters:
         pg, vf, ent = (float(v) for v in st_upd[-1, :3])
         notes = []
         if run.flt is not None:
@@ -437,6 +457,26 @@ def native_update(run, u, log):
         if run.rflt is not None:
             notes.append("(return filter: %d returns merged, std %.5f)" % (int(run.rflt.count[0].item()), float(run.rflt.denom[0].item())))
         log("update %3d  last minibatch: policy loss %+.5f  value loss %.5f  entropy %.5f  %s" % (u, pg, vf, ent, "  ".join(notes)))
+
+
+def report_line(rec, extended):
+    """The update report's line (rec: one member's record as floats): explained variance, the update's minibatch means and, when they
+    were computed, the extended terms and the post-update group."""
+    text = "explained variance %+.4f  policy loss %+.5f  value loss %.5f  entropy %.5f  clip fraction %.4f" % (
+        rec["explained_variance"], rec["policy_loss"], rec["value_loss"], rec["entropy"], rec["clip_fraction_minibatch"])
+    if extended:
+        text += "  kl %.6f  grad norm %.4f  kl coef %.4f" % (rec["kl"], rec["grad_norm"], rec["kl_coef"])
+    if rec["post"]:
+        text += "  after the update: approx kl %.6f  approxkl %.6f  clip fraction %.4f" % (rec["approx_kl"], rec["approxkl_ppo2"], rec["clip_fraction"])
+    return text
+
+
+def report_update(run, u, nb, st_upd, log):
+    """--report: one line per update from ssg_ppo_report's record (one copy to the host), and the --progress row."""
+    rec = run.ppo.report(nb, stats=st_upd, post=run.report_kl)
+    log("update %3d  report: %s" % (u, report_line(rec, st_upd.shape[1] == 8)))
+    if run.progress_writer is not None:
+        run.progress_writer.write(u, (u + 1) * run.envs * run.horizon, rec, rec["lr"], rec["clip"])
 
 
 def torch_update(net, opt, b, last_val, epochs, minibatches, gen, gamma=0.99, lam=0.95, clip=0.2, adv_norm="batch"):
@@ -518,9 +558,11 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
           device="cuda:0", seed=0, log=print, mode="eager", return_details=False, env_kw=None, update="torch", separate_value=False,
           eval_every=0, eval_episodes=1, eval_envs=None, obs_filter=False, save_obs_filter=None,
           norm_reward=False, reward_clip=10.0, adv_norm="batch", perm="torch", timeout_bootstrap=False, hidden=64,
-          save=None, save_every=0, save_best=None, resume=None, episode_log=None, episode_log_capacity=65536, best_window=0):
+          save=None, save_every=0, save_best=None, resume=None, episode_log=None, episode_log_capacity=65536, best_window=0,
+          report=False, report_kl=False, progress=None):
     config = run_config(**dict(locals()))  # (first statement: the arguments, nothing else)
     run = argparse.Namespace(**locals())  # the run record: the arguments and the config; build_run() and the bind step add the objects
+    run.report = bool(report or report_kl or progress)  # (--report-kl and --progress imply --report)
     # check: every refusal on the host, then the file a run resumes from, before any device work (a wrong command line costs nothing)
     rank, world = job_ranks()
     check_train_arguments(run, world)
@@ -533,6 +575,7 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
                 if eval_every and rank == 0 else None)
     run.flt, run.rflt, run.evaluator = loop.bind_env(run.env, horizon, 1, obs_filter, norm_reward, gamma, reward_clip, timeout_bootstrap, eval_env)
     run.eplog, run.epwriter = loop.bind_episode_log(run.env, episode_log, episode_log_capacity, 1, resume)
+    run.progress_writer = loop.open_progress(progress, resume)
     if mode in ("graph", "pingpong"):
         capture_graphs(run)
     snapshots, evals, t_roll, t_upd, t_all0 = [], [], 0.0, 0.0, time.perf_counter()
@@ -542,6 +585,8 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
     state = LoopState(st0["episodes"], st0["sum_return"])
     if ckpt is not None:
         load_run(run, state, ckpt)
+        if run.progress_writer is not None:
+            run.progress_writer.cut_back(state.update)  # (the rows of updates the checkpoint has not seen are written again)
         log("resumed from %s: %d updates done, continuing at update %d of %d" % (resume, state.update + 1, state.update + 1, updates))
     start = state.update + 1
     for u in range(start, updates):
@@ -650,6 +695,7 @@ def make_arg_parser():
     ap.add_argument("--best-window", type=int, default=0, metavar="W",
                     help="--save-best compares the mean return of the last W finished episodes (the reference callback's "
                          "np.mean(y[-100:]); needs --episode-log) instead of the mean over the episodes of one update; 0 = off")
+    loop.add_report_flags(ap)
     ap.add_argument("--resume", default=None, metavar="FILE",
                     help="continue the run a checkpoint was saved from, bit for bit (needs --mode native --update native): repeat the "
                          "original command line; --updates stays the TOTAL and may be raised")
