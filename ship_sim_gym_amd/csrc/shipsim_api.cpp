@@ -14,59 +14,200 @@
 #include "shipsim_internal.h"
 #include "shipsim_perm.h"
 
+namespace {
+
+// map_ring mode: the ring's source (fixed by ssg_refill_worlds), the refill's work queue in the blob, and how many more episodes an env
+// may start before the rings must be refilled (an env consumes at most one world per step or reset).
+struct MapRing {
+    bool ready = false;
+    int credit = 0;
+    uint64_t seed = 0;
+    double width_frac = 0.5;
+    unsigned long long *queue = nullptr;
+    unsigned *count = nullptr; // the queue's length
+};
+
+// The state blob's layout: every section's offset and size.  A section the config has no use for has size 0: no bytes, a null pointer.
+struct Span { size_t off = 0, size = 0; };
+struct BlobLayout {
+    int n_pad = 0;
+    size_t nbytes = 0;
+    Span stats, f64, i32, mask;
+    Span obs2, obsH;             // history > 2: the step kernel's two-frame staging rows, then the handle's own [n][H*F] observation rows
+    Span ring_queue, ring_count; // map_ring: work queue of the ring refill, (env, episode) pairs + its length
+    // config 4: columns of the traffic ships, goal bodies and cached arbiters (shipsim_internal.h DC_* / DU_*), the queue of the full step
+    // (one array of n_pad slots per sort bucket, two sets of counters), the memo tables (the narrowphase memo follows the state memo)
+    Span dyn_f64, dyn_live, dyn_u32, dyn_flag, dyn_hash, dyn_count, dyn_row, dyn_bucket, dyn_memo_stats, dyn_memo, dyn_npm, dyn_qmap;
+};
+
+// The one walk over the sections, from the (normalised) config: it builds the record and points the kernel arguments and the ring's queue
+// into `blob` (null while none is bound; the pointer of a section that does not exist is never written and stays null).
+BlobLayout blob_layout(const ssg_config &c, void *blob, ssg::DevCfg &d, MapRing &ring)
+{
+    BlobLayout L;
+    L.n_pad = (c.n_envs + ssg::kPadEnvs - 1) / ssg::kPadEnvs * ssg::kPadEnvs;
+    const size_t np = (size_t)L.n_pad, F = (size_t)(6 + c.n_beams);
+    auto put = [&L, blob](auto *&p, Span &s, size_t bytes, size_t align = 1) {
+        s = {(L.nbytes + align - 1) & ~(align - 1), bytes};
+        L.nbytes = s.off + bytes;
+        p = blob ? reinterpret_cast<std::remove_reference_t<decltype(p)>>(static_cast<char *>(blob) + s.off) : nullptr;
+    };
+    put(d.stats, L.stats, ssg::kStatsDoubles * sizeof(double));
+    put(d.f64cols, L.f64, (size_t)(ssg::COL_LIDAR + c.n_beams) * np * sizeof(double));
+    put(d.i32cols, L.i32, (size_t)ssg::ICOL_COUNT * np * sizeof(int32_t));
+    put(d.mask, L.mask, np);
+    if (c.history > 2) {
+        put(d.obs2, L.obs2, np * 2 * F * sizeof(double), 256);
+        put(d.obsH, L.obsH, np * (size_t)c.history * F * sizeof(double));
+    }
+    if (c.map_ring > 0) {
+        put(ring.queue, L.ring_queue, np * (size_t)c.map_ring * sizeof(unsigned long long), 256);
+        put(ring.count, L.ring_count, 256);
+    }
+    if (c.n_ships > 1) {
+        put(d.dyn_f64, L.dyn_f64, (size_t)ssg::DC_COUNT * np * sizeof(double), 256);
+        put(d.dyn_live, L.dyn_live, np * sizeof(unsigned long long));
+        put(d.dyn_u32, L.dyn_u32, (size_t)ssg::DU_COUNT * np * sizeof(uint32_t));
+        put(d.dyn_flag, L.dyn_flag, np);
+        put(d.dyn_hash, L.dyn_hash, np * sizeof(unsigned long long));
+        put(d.dyn_count, L.dyn_count, (2 * (size_t)ssg::kDynCountWords * sizeof(unsigned) + 255) & ~(size_t)255);
+        put(d.dyn_row, L.dyn_row, np * (size_t)ssg::kDynRow * sizeof(double));
+        put(d.dyn_bucket, L.dyn_bucket, (size_t)ssg::kDynBuckets * np * sizeof(int32_t));
+        put(d.dyn_memo_stats, L.dyn_memo_stats, (size_t)ssg::kMemoStatSlots * ssg::kMemoStatWords * sizeof(unsigned long long), 256);
+        put(d.dyn_memo, L.dyn_memo, (size_t)ssg::kMemoEntries * ssg::kMemoStride * sizeof(unsigned long long));
+        put(d.dyn_npm, L.dyn_npm, (size_t)ssg::kNpmEntries * ssg::kNpmStride * sizeof(unsigned long long));
+        put(d.dyn_qmap, L.dyn_qmap, np * sizeof(int32_t));
+    }
+    return L;
+}
+
+// ssg_state_field's table.  Column j of a field starts (first_column + j) * n_pad elements into its section; a `packed` field is its
+// section as one array, elements side by side.  columns 0: one per beam.  config4: n_ships == 4 only.
+const struct FieldRow { int field, n_fields; Span BlobLayout::*section; int first_column, elem_size, columns; bool packed, config4; } kFields[] = {
+    {SSG_F_X, 7, &BlobLayout::f64, ssg::COL_X, 8, 1, false, false}, // x, y, vx, vy, angle, w, cumulative reward: a column each, in this order
+    {SSG_F_LIDAR, 1, &BlobLayout::f64, ssg::COL_LIDAR, 8, 0, false, false},
+    {SSG_F_RUDDER, 3, &BlobLayout::i32, ssg::ICOL_RUDDER, 4, 1, false, false}, // rudder, step count, map id
+    {SSG_F_GOAL_MASK, 1, &BlobLayout::mask, 0, 1, 1, false, false},
+    // kStatsSlots rows of 4 int64 counters; sum over rows: [0] sum_return*100 [1] sum_length [2] episodes [3] goals
+    {SSG_F_STATS, 1, &BlobLayout::stats, 0, 8, 4 * ssg::kStatsSlots, true, false},
+    {SSG_F_TRAFFIC, 1, &BlobLayout::dyn_f64, ssg::DC_TRAFFIC, 8, 9 * SSG_N_TRAFFIC, false, true},
+    {SSG_F_GOAL_BODIES, 1, &BlobLayout::dyn_f64, ssg::DC_GOALS, 8, ssg::DC_GOAL_COLS * SSG_MAX_GOALS, false, true},
+    {SSG_F_DYN_FLAGS, 1, &BlobLayout::dyn_flag, 0, 1, 1, false, true},
+    {SSG_F_EPISODES, 1, &BlobLayout::i32, ssg::ICOL_EPISODE, 4, 1, false, false},
+    {SSG_F_DYN_MEMO_STATS, 1, &BlobLayout::dyn_memo_stats, 0, 8, ssg::kMemoStatSlots * ssg::kMemoStatWords, true, true},
+    {SSG_F_DYN_LIVE, 1, &BlobLayout::dyn_live, 0, 8, 1, false, true},
+    {SSG_F_DYN_ARB_META, 1, &BlobLayout::dyn_u32, ssg::DU_META, 4, ssg::kDynPairs, false, true},
+    {SSG_F_DYN_ARB_HASH, 1, &BlobLayout::dyn_u32, ssg::DU_HASH, 4, ssg::kPolyPairs, false, true},
+    {SSG_F_DYN_ARB_IMPULSE, 1, &BlobLayout::dyn_f64, ssg::DC_ARB, 8, 4 * ssg::kDynPairs, false, true},
+};
+static_assert(SSG_F_CUM_REWARD - SSG_F_X == ssg::COL_CUM - ssg::COL_X && SSG_F_MAP_ID - SSG_F_RUDDER == ssg::ICOL_MAP - ssg::ICOL_RUDDER, "the two runs of fields are runs of columns");
+
+// The host's half of the config-4 step.  The step kernel's body role leaves, in one of two counter sets, the queue of envs whose bodies the
+// NEXT full cpSpaceStep must visit; the full step consumes it or, when it cannot be trusted, rebuilds it from the per-env flags (a memset
+// of the counters + the classify pass over every env: 12-19 us).  INVARIANT: the queue is trusted only while nothing on the host has
+// touched the envs, the blob, the bank or the kernel arguments since the step kernel left it, except ONE masked reset that joined it.
+// The memo of the full step (shipsim_internal.h, kMemoEntries) lives by GENERATIONS: a new one makes every stored entry count as empty.
+constexpr int kMemoGenSteps = 1 << 15;
+class DynStep {
+    ssg::DevCfg &d; ssg::DynCfg &dyn; // the handle's kernel arguments: dyn_par, dyn_seq, dyn_memo_gen and bank_epoch are written here alone
+    bool queue_valid = false;          // the step kernel's last launch left the next step's queue, and the invariant holds
+    int masked_resets_since_step = 0;  // masked ssg_reset calls that joined the live queue since the last step (at most one may)
+    unsigned memo_gen = 1;             // generation of the memo's entries (1..255; no memset: the generation is part of the tag)
+    int memo_steps = 0;                // launches since it began
+    bool memo_clear_pending = false;   // the tables must be zeroed before the next launch that could read them
+    // A new generation is started whenever the bank changes (entries of the old bank could never match again and would only fill the table) and every
+    // kMemoGenSteps launches (states a caller poked in once, or a long tail of rare ones, do not silt the table up).
+    void new_generation() {
+        if (++memo_gen > 255) { memo_gen = 1; memo_clear_pending = true; } // a wrapped generation could meet its own old tags
+        memo_steps = 0;
+        d.dyn_memo_gen = memo_gen;
+    }
+
+public:
+    DynStep(ssg::DevCfg &dev, ssg::DynCfg &dyn_cfg) : d(dev), dyn(dyn_cfg) {}
+    // (ssg_debug_dyn_counters) launches of the full step so far, and those that rebuilt the queue from the per-env flags first
+    unsigned long long launches = 0, classifies = 0;
+    void args_refreshed() { d.dyn_par = 0; d.dyn_memo_gen = memo_gen; d.dyn_seq = launches; queue_valid = false; }
+    // A blob was bound, or the bound one may have been copied or restored: its memo tables may hold another bank's or handle's results under
+    // this handle's generation (the key names the record, not the bank's contents): zeroed before the next launch that could read them.
+    void blob_rebound() { new_generation(); memo_clear_pending = true; queue_valid = false; }
+    // The blob was zeroed, some envs were edited, or a launch failed (a queue never consumed, or never written): the next step starts over.
+    void queue_lost() { queue_valid = false; }
+    // A new bank, or the bound one regenerated in place: resting traffic must be re-collided against the new banks.
+    void bank_changed() { dyn.bank_epoch++; new_generation(); queue_valid = false; }
+    // A reset arrives; true: it JOINS the queue the step kernel left (the RLlib flow resets its done envs with a masked reset after every
+    // step).  One such reset per step: every env then has at most one entry per sort bucket, which is what a bucket's n_pad slots hold; a
+    // second one, a full reset, or a queue that is not there rebuild it.  And only where the full step runs its one-record-per-wave kernel
+    // (shared banks of at most kDynMapBuckets records): that kernel drops an entry queued under another record than the env now sits on,
+    // and a record IS its map bucket there.  The per-lane-planes kernel (larger banks, map_ring) cannot tell a stale entry from the new
+    // one — both would be stepped, by different waves: an env's bodies could advance twice in one step — so it rebuilds after any reset.
+    bool reset_arrives(bool masked, bool one_record_per_wave) {
+        const bool join = masked && queue_valid && masked_resets_since_step == 0 && one_record_per_wave;
+        if (join) masked_resets_since_step = 1;
+        else queue_valid = false;
+        return join;
+    }
+    // A full step begins: *rebuild says whether its classify pass rebuilds the queue (this step's bucket counters then start from zero);
+    // the memo's generation moves on, and the memsets the launch needs are issued (memo_bytes: both tables, one behind the other).
+    hipError_t step_begins(size_t memo_bytes, hipStream_t st, bool *rebuild) {
+        hipError_t e = hipSuccess;
+        *rebuild = !queue_valid;
+        if (*rebuild) {
+            d.dyn_par = 0;
+            classifies++;
+            e = hipMemsetAsync(d.dyn_count, 0, ssg::kDynCountWords * sizeof(unsigned), st);
+        }
+        if (d.dyn_memo) {
+            if (++memo_steps > kMemoGenSteps) new_generation();
+            if (memo_clear_pending && e == hipSuccess) {
+                e = hipMemsetAsync(d.dyn_memo, 0, memo_bytes, st);
+                memo_clear_pending = false;
+            }
+        }
+        d.dyn_seq = ++launches;
+        return e;
+    }
+    // Both launches of a step went out: the step kernel's body role queues the envs whose bodies must be stepped next, in the other set.
+    void step_issued() { queue_valid = true; masked_resets_since_step = 0; d.dyn_par ^= 1; }
+};
+
+} // namespace
+
 struct ssg_handle {
+    // configuration and the kernel arguments derived from it (refresh_dev)
     ssg_config cfg;
     ssg::DevCfg dev{};
-    int n_pad = 0;
-    size_t off_stats = 0, off_f64 = 0, off_i32 = 0, off_mask = 0, off_obs2 = 0, off_obsH = 0, nbytes = 0;
-    size_t off_dyn_f64 = 0, off_dyn_live = 0, off_dyn_u32 = 0, off_dyn_flag = 0; // config 4 only
-    size_t off_dyn_hash = 0, off_dyn_count = 0, off_dyn_row = 0, off_dyn_bucket = 0;
-    size_t off_dyn_memo = 0, off_dyn_memo_stats = 0, off_dyn_npm = 0, off_dyn_qmap = 0;
-    bool time_kernels = false;        // ssg_debug_kernel_times: HIP events around the two launches of every config-4 step
-    double t_dyn_ms = 0.0, t_step_ms = 0.0;
-    unsigned long long t_steps = 0;
-    unsigned long long n_classify = 0; // launches of the classify pass (the queue of the full step rebuilt from the per-env flags)
-    int masked_resets_since_step = 0; // masked ssg_reset calls that joined the live dyn queue since the last step (at most one may) // the memo of the full dyn step (shipsim_internal.h, kMemoEntries)
-    unsigned long long dyn_seq = 0;   // launches of the full step so far
-    unsigned memo_gen = 1;            // generation of the memo's entries (1..255)
-    bool memo_clear_pending = false;  // the generation counter wrapped: zero the table before the next launch
-    int memo_steps = 0;               // launches since the generation began (a generation ends after kMemoGenSteps of them)
-    bool dyn_queue_valid = false; // the step kernel's last launch left the next step's dyn queue (nothing host-side touched the envs since)
     ssg::DynCfg dyn{};
+    // the bound blob and its layout; the bank
+    BlobLayout layout;
     void *state = nullptr;
+    bool zeroed = false;        // the bound blob is known to have been zeroed by us (ssg_init_state / first full reset)
     const double *bank = nullptr;
     int n_maps = 0;
+    bool remap_pending = false; // the bank shrank: ICOL_MAP must be taken modulo n_maps before the next kernel reads it
+    // launch geometry (ssg_set_map_bank), and which kernels have their dynamic-LDS limit set: the step kernels, the policy kernel
+    // (ssg_policy_act / ssg_rollout_policy), the gradient kernel (ssg_ppo_grad / ssg_ppo_update), the FILTER and the time-out kernels
     int block = 256;
     bool lds = false;
     size_t lds_bytes = 0;
-    bool prepared = false;
-    bool zeroed = false;       // the bound blob is known to have been zeroed by us (ssg_init_state / first full reset)
-    // map_ring mode: the ring's source (fixed by ssg_refill_worlds) and how many more episodes an env may start before the
-    // rings must be refilled (an env consumes at most one world per step or reset)
-    bool ring_ready = false;
-    uint64_t ring_seed = 0;
-    double ring_width_frac = 0.5;
-    int ring_credit = 0;
-    size_t off_ring_queue = 0, off_ring_count = 0;
-    bool remap_pending = false; // the bank shrank: ICOL_MAP must be taken modulo n_maps before the next kernel reads it
+    bool prepared = false, policy_prepared = false, ppo_prepared = false, policy_filter_prepared = false, policy_boot_prepared = false;
+    // config 4: the host's half of the step; ssg_debug_kernel_times (HIP events around the two launches of every config-4 step)
+    DynStep dyn_step{dev, dyn};
+    bool time_kernels = false;
+    double t_dyn_ms = 0.0, t_step_ms = 0.0;
+    unsigned long long t_steps = 0;
+    MapRing ring;
     // ssg_step_host / ssg_wait_host: one completion event per host block slot, created on first use
     static constexpr int kHostSlots = 8;
     hipEvent_t host_ev[kHostSlots] = {};
     bool host_ev_made[kHostSlots] = {};
-    bool policy_prepared = false; // ssg_policy_act / ssg_rollout_policy: the policy kernel's dynamic-LDS limit is set
-    bool ppo_prepared = false;    // ssg_ppo_grad / ssg_ppo_update: the gradient kernel's dynamic-LDS limit is set
-    // ssg_pop_set_slices: the members' env counts (empty: nothing bound), the caller's device table, the largest and smallest slice
+    // bound records.  ssg_pop_set_slices: the members' env counts (empty: nothing bound), the caller's device table, the largest and smallest slice
     std::vector<int32_t> pop_sizes;
     const int32_t *dev_slices = nullptr;
     int slice_max = 0, slice_min = 0;
-    // ssg_set_obs_filter: the bound record (a copy; struct_size 0: nothing bound) and whether the FILTER kernels' LDS limit is set
-    ssg_obs_filter flt{};
-    bool policy_filter_prepared = false;
-    // ssg_set_timeout_boot: the bound record (a copy; struct_size 0: nothing bound) and whether the time-out kernels' LDS limit is set
-    ssg_timeout_boot tob{};
-    bool policy_boot_prepared = false;
-    // ssg_set_eval_recorder: the bound record (a copy; struct_size 0: nothing bound), its env_ids pointing at the copy beside it
-    ssg_eval_recorder rec{};
+    ssg_obs_filter flt{};     // ssg_set_obs_filter (these three: a copy; struct_size 0: nothing bound)
+    ssg_timeout_boot tob{};   // ssg_set_timeout_boot
+    ssg_eval_recorder rec{};  // ssg_set_eval_recorder, its env_ids pointing at the copy beside it
     ssg::EvalRecIds rec_ids{};
     // ssg_ppo_set_adv_norm: the mode (SSG_ADV_NORM_BATCH: nothing bound), the member count the scratch serves and the caller's scratch
     int adv_norm_mode = SSG_ADV_NORM_BATCH, adv_norm_members = 0;
@@ -315,7 +456,6 @@ void refresh_dev(ssg_handle *h)
     const ssg_config &c = h->cfg;
     ssg::DevCfg &d = h->dev;
     d.n_envs = c.n_envs;
-    d.n_pad = h->n_pad;
     d.env_id_base = c.env_id_base;
     d.n_beams = c.n_beams;
     d.history = c.history < 2 ? c.history : 2;
@@ -354,33 +494,12 @@ void refresh_dev(ssg_handle *h)
             d.beam_sin[i] = std::sin(phi);
         }
     }
-    char *base = static_cast<char *>(h->state);
-    d.stats = base ? reinterpret_cast<double *>(base + h->off_stats) : nullptr;
-    d.f64cols = base ? reinterpret_cast<double *>(base + h->off_f64) : nullptr;
-    d.i32cols = base ? reinterpret_cast<int32_t *>(base + h->off_i32) : nullptr;
-    d.mask = base ? reinterpret_cast<uint8_t *>(base + h->off_mask) : nullptr;
-    d.obs2 = (base && c.history > 2) ? reinterpret_cast<double *>(base + h->off_obs2) : nullptr;
-    d.obsH = (base && c.history > 2) ? reinterpret_cast<double *>(base + h->off_obsH) : nullptr;
+    h->layout = blob_layout(c, h->state, d, h->ring);
+    d.n_pad = h->layout.n_pad;
     d.bank = h->bank;
     d.n_ships = c.n_ships;
-    const bool dyn = base && c.n_ships > 1;
-    d.dyn_f64 = dyn ? reinterpret_cast<double *>(base + h->off_dyn_f64) : nullptr;
-    d.dyn_live = dyn ? reinterpret_cast<unsigned long long *>(base + h->off_dyn_live) : nullptr;
-    d.dyn_u32 = dyn ? reinterpret_cast<uint32_t *>(base + h->off_dyn_u32) : nullptr;
-    d.dyn_flag = dyn ? reinterpret_cast<uint8_t *>(base + h->off_dyn_flag) : nullptr;
-    d.dyn_hash = dyn ? reinterpret_cast<unsigned long long *>(base + h->off_dyn_hash) : nullptr;
-    d.dyn_count = dyn ? reinterpret_cast<unsigned *>(base + h->off_dyn_count) : nullptr;
-    d.dyn_bucket = dyn ? reinterpret_cast<int32_t *>(base + h->off_dyn_bucket) : nullptr;
-    d.dyn_qmap = dyn ? reinterpret_cast<int32_t *>(base + h->off_dyn_qmap) : nullptr;
-    d.dyn_par = 0; // (the queue is rebuilt from the flags after every refresh: dyn_queue_valid = false below)
-    d.dyn_row = dyn ? reinterpret_cast<double *>(base + h->off_dyn_row) : nullptr;
     // the memo: shared bank records are what makes states repeat (not per-env worlds; the key holds 16 bits of record index)
-    const bool memo = dyn && !(c.flags & SSG_FLAG_DYN_MEMO_OFF) && c.map_ring == 0 && h->n_maps > 0 && h->n_maps <= 65536;
-    d.dyn_memo = memo ? reinterpret_cast<unsigned long long *>(base + h->off_dyn_memo) : nullptr;
-    d.dyn_memo_stats = dyn ? reinterpret_cast<unsigned long long *>(base + h->off_dyn_memo_stats) : nullptr;
-    d.dyn_npm = memo ? reinterpret_cast<unsigned long long *>(base + h->off_dyn_npm) : nullptr;
-    d.dyn_memo_gen = h->memo_gen;
-    d.dyn_seq = h->dyn_seq;
+    if ((c.flags & SSG_FLAG_DYN_MEMO_OFF) || c.map_ring != 0 || h->n_maps <= 0 || h->n_maps > 65536) d.dyn_memo = d.dyn_npm = nullptr;
     {   // every constant the full step reads, folded into 16 bits of the memo key
         unsigned long long fp = 0xcbf29ce484222325ull;
         auto eat = [&](const void *p, size_t n) { const unsigned char *b = static_cast<const unsigned char *>(p); for (size_t i = 0; i < n; ++i) fp = (fp ^ b[i]) * 0x100000001b3ull; };
@@ -404,20 +523,7 @@ void refresh_dev(ssg_handle *h)
         std::memcpy(d.thull, h->dyn.thull, sizeof(d.thull));
         std::memcpy(d.tnrm, h->dyn.tnrm, sizeof(d.tnrm));
     }
-    h->dyn_queue_valid = false; // (anything that refreshes the kernel arguments may have changed what the queue was built from)
-}
-
-
-// The memo of the full dyn step: a new GENERATION makes every stored entry count as empty (no memset: the generation is part of
-// the tag).  Started whenever the bank changes (entries of the old bank could never match again and would only fill the table)
-// and every kMemoGenSteps launches (states a caller poked in once, or a long tail of rare ones, do not silt the table up).
-constexpr int kMemoGenSteps = 1 << 15;
-static void memo_new_generation(ssg_handle *h)
-{
-    h->memo_gen += 1;
-    if (h->memo_gen > 255) { h->memo_gen = 1; h->memo_clear_pending = true; } // a wrapped generation could meet its own old tags
-    h->memo_steps = 0;
-    h->dev.dyn_memo_gen = h->memo_gen;
+    h->dyn_step.args_refreshed();
 }
 
 int pick_block(int n_envs)
@@ -552,37 +658,8 @@ int ssg_create(const ssg_config *cfg, ssg_handle **out)
     if (!h) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_create: out of host memory");
     h->cfg = *cfg;
     if (h->cfg.n_ships == 0) h->cfg.n_ships = 1;
-    h->n_pad = (cfg->n_envs + ssg::kPadEnvs - 1) / ssg::kPadEnvs * ssg::kPadEnvs;
-    const size_t np = (size_t)h->n_pad;
-    h->off_stats = 0;
-    h->off_f64 = ssg::kStatsDoubles * sizeof(double);
-    h->off_i32 = h->off_f64 + (size_t)(ssg::COL_LIDAR + cfg->n_beams) * np * sizeof(double);
-    h->off_mask = h->off_i32 + (size_t)ssg::ICOL_COUNT * np * sizeof(int32_t);
-    h->off_obs2 = (h->off_mask + np + 255) & ~(size_t)255;
-    // history > 2: the step kernel's two-frame staging rows, then the handle's own [n][H*F] observation rows
-    h->off_obsH = h->off_obs2 + np * (size_t)(2 * (6 + cfg->n_beams)) * sizeof(double);
-    h->nbytes = (cfg->history > 2) ? h->off_obsH + np * (size_t)(cfg->history * (6 + cfg->n_beams)) * sizeof(double) : h->off_mask + np;
-    if (cfg->map_ring > 0) { // work queue of the ring refill: (env, episode) pairs + its length
-        h->off_ring_queue = (h->nbytes + 255) & ~(size_t)255;
-        h->off_ring_count = h->off_ring_queue + np * (size_t)cfg->map_ring * sizeof(unsigned long long);
-        h->nbytes = h->off_ring_count + 256;
-        h->cfg.flags |= SSG_FLAG_BANK_IN_GLOBAL; // n_envs * R records never fit LDS
-    }
+    if (h->cfg.map_ring > 0) h->cfg.flags |= SSG_FLAG_BANK_IN_GLOBAL; // n_envs * R records never fit LDS
     if (h->cfg.n_ships > 1) {
-        // config 4: columns of the traffic ships, goal bodies and cached arbiters (shipsim_internal.h DC_* / DU_*)
-        h->off_dyn_f64 = (h->nbytes + 255) & ~(size_t)255;
-        h->off_dyn_live = h->off_dyn_f64 + (size_t)ssg::DC_COUNT * np * sizeof(double);
-        h->off_dyn_u32 = h->off_dyn_live + np * sizeof(unsigned long long);
-        h->off_dyn_flag = h->off_dyn_u32 + (size_t)ssg::DU_COUNT * np * sizeof(uint32_t);
-        h->off_dyn_hash = h->off_dyn_flag + np;
-        h->off_dyn_count = h->off_dyn_hash + np * sizeof(unsigned long long);
-        h->off_dyn_row = h->off_dyn_count + ((2 * (size_t)ssg::kDynCountWords * sizeof(unsigned) + 255) & ~(size_t)255);
-        h->off_dyn_bucket = h->off_dyn_row + np * (size_t)ssg::kDynRow * sizeof(double);
-        h->off_dyn_memo_stats = (h->off_dyn_bucket + (size_t)ssg::kDynBuckets * np * sizeof(int32_t) + 255) & ~(size_t)255; // one array of n_pad slots per sort bucket
-        h->off_dyn_memo = h->off_dyn_memo_stats + (size_t)ssg::kMemoStatSlots * ssg::kMemoStatWords * sizeof(unsigned long long);
-        h->off_dyn_npm = h->off_dyn_memo + (size_t)ssg::kMemoEntries * ssg::kMemoStride * sizeof(unsigned long long);
-        h->off_dyn_qmap = h->off_dyn_npm + (size_t)ssg::kNpmEntries * ssg::kNpmStride * sizeof(unsigned long long);
-        h->nbytes = h->off_dyn_qmap + np * sizeof(int32_t);
         const int rc = set_traffic(h);
         if (rc != SSG_OK) { delete h; return fail(nullptr, rc, "ssg_create: traffic ship geometry"); }
     }
@@ -605,7 +682,7 @@ int ssg_destroy(ssg_handle *h)
 int ssg_state_nbytes(const ssg_handle *h, size_t *nbytes)
 {
     if (!h || !nbytes) return SSG_ERR_BAD_ARG;
-    *nbytes = h->nbytes;
+    *nbytes = h->layout.nbytes;
     return SSG_OK;
 }
 
@@ -613,47 +690,13 @@ int ssg_state_field(const ssg_handle *h, int field, size_t *offset, int *elem_si
                     size_t *column_stride_bytes)
 {
     if (!h || !offset || !elem_size || !n_columns || !column_stride_bytes) return SSG_ERR_BAD_ARG;
-    const size_t np = (size_t)h->n_pad;
-    size_t off;
-    int es, nc;
-    if (field >= SSG_F_X && field <= SSG_F_CUM_REWARD) {
-        off = h->off_f64 + (size_t)field * np * 8; es = 8; nc = 1;
-    } else if (field == SSG_F_LIDAR) {
-        off = h->off_f64 + (size_t)ssg::COL_LIDAR * np * 8; es = 8; nc = h->cfg.n_beams;
-    } else if (field == SSG_F_RUDDER || field == SSG_F_STEP_COUNT || field == SSG_F_MAP_ID) {
-        off = h->off_i32 + (size_t)(field - SSG_F_RUDDER) * np * 4; es = 4; nc = 1;
-    } else if (field == SSG_F_GOAL_MASK) {
-        off = h->off_mask; es = 1; nc = 1;
-    } else if (field == SSG_F_TRAFFIC || field == SSG_F_GOAL_BODIES) {
-        if (h->cfg.n_ships <= 1) return SSG_ERR_BAD_ARG;
-        const int c0 = field == SSG_F_TRAFFIC ? ssg::DC_TRAFFIC : ssg::DC_GOALS;
-        off = h->off_dyn_f64 + (size_t)c0 * np * 8; es = 8;
-        nc = field == SSG_F_TRAFFIC ? 9 * SSG_N_TRAFFIC : ssg::DC_GOAL_COLS * SSG_MAX_GOALS;
-    } else if (field == SSG_F_EPISODES) {
-        off = h->off_i32 + (size_t)ssg::ICOL_EPISODE * np * 4; es = 4; nc = 1;
-    } else if (field == SSG_F_DYN_FLAGS) {
-        if (h->cfg.n_ships <= 1) return SSG_ERR_BAD_ARG;
-        off = h->off_dyn_flag; es = 1; nc = 1;
-    } else if (field == SSG_F_DYN_MEMO_STATS) {
-        if (h->cfg.n_ships <= 1) return SSG_ERR_BAD_ARG;
-        off = h->off_dyn_memo_stats; es = 8; nc = ssg::kMemoStatSlots * ssg::kMemoStatWords;
-        *offset = off; *elem_size = es; *n_columns = nc; *column_stride_bytes = 8;
-        return SSG_OK;
-    } else if (field == SSG_F_DYN_LIVE || field == SSG_F_DYN_ARB_META || field == SSG_F_DYN_ARB_HASH || field == SSG_F_DYN_ARB_IMPULSE) {
-        if (h->cfg.n_ships <= 1) return SSG_ERR_BAD_ARG;
-        if (field == SSG_F_DYN_LIVE) { off = h->off_dyn_live; es = 8; nc = 1; }
-        else if (field == SSG_F_DYN_ARB_META) { off = h->off_dyn_u32 + (size_t)ssg::DU_META * np * 4; es = 4; nc = ssg::kDynPairs; }
-        else if (field == SSG_F_DYN_ARB_HASH) { off = h->off_dyn_u32 + (size_t)ssg::DU_HASH * np * 4; es = 4; nc = ssg::kPolyPairs; }
-        else { off = h->off_dyn_f64 + (size_t)ssg::DC_ARB * np * 8; es = 8; nc = 4 * ssg::kDynPairs; }
-    } else if (field == SSG_F_STATS) {
-        // kStatsSlots rows of 4 int64 counters; sum over rows: [0] sum_return*100 [1] sum_length [2] episodes [3] goals
-        off = h->off_stats; es = 8; nc = 4 * ssg::kStatsSlots;
-        *offset = off; *elem_size = es; *n_columns = nc; *column_stride_bytes = 8;
-        return SSG_OK;
-    } else {
-        return SSG_ERR_BAD_ARG;
-    }
-    *offset = off; *elem_size = es; *n_columns = nc; *column_stride_bytes = np * (size_t)es;
+    const FieldRow *r = std::find_if(std::begin(kFields), std::end(kFields), [field](const FieldRow &f) { return field >= f.field && field < f.field + f.n_fields; });
+    if (r == std::end(kFields) || (r->config4 && h->cfg.n_ships <= 1)) return SSG_ERR_BAD_ARG;
+    const size_t column = r->packed ? (size_t)r->elem_size : (size_t)h->layout.n_pad * (size_t)r->elem_size;
+    *offset = (h->layout.*r->section).off + (size_t)(r->first_column + field - r->field) * column;
+    *elem_size = r->elem_size;
+    *n_columns = r->columns ? r->columns : h->cfg.n_beams;
+    *column_stride_bytes = column;
     return SSG_OK;
 }
 
@@ -664,28 +707,35 @@ int ssg_bind_state(ssg_handle *h, void *dev_state)
         return fail(h, SSG_ERR_BAD_ARG, "ssg_bind_state: state blob must be 256-byte aligned");
     h->state = dev_state;
     h->zeroed = false;
-    // whatever memo tables the blob carries were not filled by this handle on this bank: they are zeroed before the first launch
-    // that could read them (a blob this handle filled itself — a snapshot copied back IN PLACE — keeps its entries: they are results
-    // of the same pure function)
-    memo_new_generation(h);
-    h->memo_clear_pending = true;
+    h->dyn_step.blob_rebound();
     refresh_dev(h);
     return SSG_OK;
 }
 
-static int ring_refill(ssg_handle *h, double *dev_raw, void *stream);
+// map_ring mode: draw the worlds the rings are missing and restore the credit of R-1 episode starts per env
+static int ring_refill(ssg_handle *h, double *dev_raw, void *stream)
+{
+    MapRing &r = h->ring;
+    hipError_t e = ssg::launch_refill_worlds(h->dev, r.seed, r.width_frac, r.queue, r.count, const_cast<double *>(h->bank), dev_raw,
+                                             static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("ring refill launch: ") + hipGetErrorString(e));
+    r.credit = h->cfg.map_ring - 1;
+    // (A refill draws the worlds of FUTURE episodes, into the R-1 slots an env's current episode does not occupy, so no env's current world changes:
+    // the rest bits and the queue of the next full cpSpaceStep stay valid and DynStep hears nothing of it; dropping the queue cost ~13 us a step.)
+    return SSG_OK;
+}
 
 int ssg_init_state(ssg_handle *h, void *stream)
 {
     int rc = check_ready(h, false);
     if (rc != SSG_OK) return rc;
-    hipError_t e = hipMemsetAsync(h->state, 0, h->nbytes, static_cast<hipStream_t>(stream));
+    hipError_t e = hipMemsetAsync(h->state, 0, h->layout.nbytes, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("ssg_init_state: ") + hipGetErrorString(e));
     h->zeroed = true;
-    h->dyn_queue_valid = false;
+    h->dyn_step.queue_lost();
     // map_ring mode: the episode counters and the rings' "worlds drawn" counters were just zeroed together, so the rings
     // must hold episodes 0 .. R-1 again: redraw them (the bookkeeping and the bank never disagree)
-    if (h->cfg.map_ring > 0 && h->ring_ready) return ring_refill(h, nullptr, stream);
+    if (h->cfg.map_ring > 0 && h->ring.ready) return ring_refill(h, nullptr, stream);
     return SSG_OK;
 }
 
@@ -697,15 +747,14 @@ int ssg_set_map_bank(ssg_handle *h, const double *dev_bank, int n_maps)
         return fail(h, SSG_ERR_BAD_ARG, "ssg_set_map_bank: bank must be 16-byte aligned");
     if (h->cfg.map_ring > 0 && (long long)n_maps != (long long)h->cfg.n_envs * h->cfg.map_ring)
         return fail(h, SSG_ERR_BAD_ARG, "ssg_set_map_bank: map_ring mode needs n_maps == n_envs * map_ring");
-    if (h->cfg.map_ring > 0) h->ring_ready = false; // a new bank: its rings are empty until ssg_refill_worlds
+    if (h->cfg.map_ring > 0) h->ring.ready = false; // a new bank: its rings are empty until ssg_refill_worlds
     // Envs per workgroup, and whether the bank is staged in the CU's LDS or gathered from L2 / HBM.  Staged: the largest size, from
     // the one preferred for this env count down, at which the bank fits the LDS beside the lidar buffers.  Gathered: the largest
     // size at which the record heads fit.  A staged bank wins at EQUAL workgroup size (65 536 envs, 10 beams, 64 records: 6.45
     // against 7.2 us per step), but a workgroup smaller than the preferred one means more workgroups than the chip holds at once
     // — they own their CU's LDS — i.e. launches of several rounds: 65 536 envs x 8 beams on 120 records took 16.1 us per step
     // staged on 64-env workgroups (four rounds) against 6.4 gathered on 256-env ones; 100 records, 128-env workgroups: 8.6
-    // against 6.5.  (Round 5; before, the gathered path was only taken when nothing could be staged, and then on 64-env
-    // workgroups, whose instantiation holds 134 VGPRs = three per CU: two rounds again.)
+    // against 6.5.
     const bool dyn_cfg = h->cfg.n_ships > 1;
     auto fix_dyn = [&](int b) { return (dyn_cfg && b == 128) ? 64 : b; }; // the config-4 step kernel is built for 64 and 256
     const int preferred = fix_dyn(pick_block(h->cfg.n_envs));
@@ -717,8 +766,7 @@ int ssg_set_map_bank(ssg_handle *h, const double *dev_bank, int n_maps)
     if (h->bank && n_maps < h->n_maps) h->remap_pending = true; // stale record indices >= n_maps must not survive
     h->bank = dev_bank;
     h->n_maps = n_maps;
-    h->dyn.bank_epoch++; // resting traffic must be re-collided against the new banks
-    memo_new_generation(h);
+    h->dyn_step.bank_changed();
     h->lds = can_stage && (staged_block == preferred || gathered_block <= staged_block);
     h->block = h->lds ? staged_block : gathered_block;
     h->lds_bytes = ssg::step_lds_bytes(h->cfg.n_beams, h->block, h->lds, n_maps, h->cfg.n_ships > 1);
@@ -727,20 +775,24 @@ int ssg_set_map_bank(ssg_handle *h, const double *dev_bank, int n_maps)
     return SSG_OK;
 }
 
-// map_ring mode: draw the worlds the rings are missing and restore the credit of R-1 episode starts per env
-static int ring_refill(ssg_handle *h, double *dev_raw, void *stream)
+// map_ring mode: the ring was filled by ssg_refill_worlds, or the call is refused (before_reset: ssg_reset's wording)
+static int ring_ready_or_refuse(ssg_handle *h, bool before_reset = false)
 {
-    char *base = static_cast<char *>(h->state);
-    hipError_t e = ssg::launch_refill_worlds(h->dev, h->ring_seed, h->ring_width_frac,
-                                             reinterpret_cast<unsigned long long *>(base + h->off_ring_queue),
-                                             reinterpret_cast<unsigned *>(base + h->off_ring_count),
-                                             const_cast<double *>(h->bank), dev_raw, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("ring refill launch: ") + hipGetErrorString(e));
-    h->ring_credit = h->cfg.map_ring - 1;
-    // (A refill draws the worlds of FUTURE episodes — episodes current+1 .. current+R-1 of every env, into the R-1 slots its current
-    // episode does not occupy — so no env's current world changes: the rest bits (tagged with the bank epoch) and the queue of the
-    // next full cpSpaceStep stay valid.  Until round 6 a refill bumped the epoch and dropped the queue: every env of a config-4
-    // handle was classified and stepped in full once per refill cycle, ~13 us per step on rings of 32.)
+    if (h->cfg.map_ring <= 0 || h->ring.ready) return SSG_OK;
+    return fail(h, SSG_ERR_NOT_BOUND, before_reset ? "map_ring mode: call ssg_refill_worlds before the first ssg_reset"
+                                                   : "map_ring mode: call ssg_refill_worlds first");
+}
+
+// map_ring mode: take up to n episode starts per env (a reset is one, every step may be one) out of the ring's credit, refilling
+// first if none is left, so that every ring still holds an unused world for each of them.  *taken (where asked): 1 .. n.
+static int ring_take(ssg_handle *h, int n, void *stream, int *taken = nullptr)
+{
+    MapRing &r = h->ring;
+    const int rc = r.credit < 1 ? ring_refill(h, nullptr, stream) : SSG_OK;
+    if (rc != SSG_OK) return rc;
+    if (n > r.credit) n = r.credit;
+    r.credit -= n;
+    if (taken) *taken = n;
     return SSG_OK;
 }
 
@@ -756,42 +808,22 @@ static int flush_remap(ssg_handle *h, void *stream)
 int ssg_reset(ssg_handle *h, const uint8_t *dev_mask, const int32_t *dev_map_ids, double *dev_obs, void *stream)
 {
     int rc = check_ready(h, true);
-    if (rc != SSG_OK) return rc;
-    rc = refuse_capture(h, stream, "ssg_reset");
-    if (rc != SSG_OK) return rc;
-    if (!dev_mask && !h->zeroed) { // first full reset on a freshly bound blob: start from zeroed counters / columns
-        rc = ssg_init_state(h, stream);
-        if (rc != SSG_OK) return rc;
-    }
-    rc = flush_remap(h, stream);
+    if (rc == SSG_OK) rc = refuse_capture(h, stream, "ssg_reset");
+    if (rc == SSG_OK && !dev_mask && !h->zeroed) rc = ssg_init_state(h, stream); // first full reset on a freshly bound blob: zeroed counters / columns
+    if (rc == SSG_OK) rc = flush_remap(h, stream);
     if (rc != SSG_OK) return rc;
     if (h->cfg.map_ring > 0) {
         if (dev_map_ids) // episode p of env e lives in record e*R + p mod R: there is no other record to put it on
             return fail(h, SSG_ERR_BAD_ARG, "ssg_reset: dev_map_ids must be NULL in map_ring mode (an env's records are its own ring)");
-        if (!h->ring_ready) return fail(h, SSG_ERR_NOT_BOUND, "map_ring mode: call ssg_refill_worlds before the first ssg_reset");
-        if (h->ring_credit < 1) { // a reset starts an episode: make sure every ring still holds an unused world
-            rc = ring_refill(h, nullptr, stream);
-            if (rc != SSG_OK) return rc;
-        }
-        h->ring_credit -= 1;
+        rc = ring_ready_or_refuse(h, true);
+        if (rc == SSG_OK) rc = ring_take(h, 1, stream);
+        if (rc != SSG_OK) return rc;
     }
-    // Config 4: a MASKED reset between two steps joins the queue the step kernel left for the next full cpSpaceStep (the RLlib flow
-    // resets its done envs this way after every step; rebuilding the queue from the per-env flags instead — memset + the classify
-    // pass over every env — cost the next step 12-19 us).  One such reset per step: every env then has at most one entry per sort
-    // bucket, which is what a bucket's n_pad slots hold; a second one, a full reset, or a queue that is not there rebuild it.
-    // Only where the full step runs its one-record-per-wave kernel (shared banks of at most kDynMapBuckets records): that kernel
-    // drops an entry queued under another record than the env now sits on, and a record IS its map bucket there.  The per-lane-planes
-    // kernel (larger banks, map_ring) cannot tell a stale entry from the new one — both would be stepped, by different waves,
-    // i.e. an env's bodies could advance twice in one step — so those handles rebuild the queue after any reset.
-    const bool dyn_uni = h->cfg.map_ring == 0 && h->n_maps <= ssg::kDynMapBuckets;
-    const bool append = h->cfg.n_ships > 1 && dev_mask && h->dyn_queue_valid && h->masked_resets_since_step == 0 && dyn_uni;
-    if (append) h->masked_resets_since_step = 1;
-    else h->dyn_queue_valid = false;
-    hipError_t e;
-    if (h->cfg.n_ships > 1) // the player, then add_default_traffic + fresh goal bodies of the reset envs: one launch
-        e = ssg::launch_dyn_reset(h->dev, h->dyn, dev_mask, dev_map_ids, dev_obs, append, static_cast<hipStream_t>(stream));
-    else
-        e = ssg::launch_reset(h->dev, dev_mask, dev_map_ids, dev_obs, static_cast<hipStream_t>(stream));
+    const bool one_record_per_wave = h->cfg.map_ring == 0 && h->n_maps <= ssg::kDynMapBuckets;
+    const bool join = h->dyn_step.reset_arrives(dev_mask != nullptr, one_record_per_wave);
+    const hipStream_t st = static_cast<hipStream_t>(stream); // config 4: the player, then add_default_traffic + fresh goal bodies, in one launch
+    hipError_t e = h->cfg.n_ships > 1 ? ssg::launch_dyn_reset(h->dev, h->dyn, dev_mask, dev_map_ids, dev_obs, join, st)
+                                      : ssg::launch_reset(h->dev, dev_mask, dev_map_ids, dev_obs, st);
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("reset launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
@@ -809,8 +841,7 @@ static int prepare(ssg_handle *h)
     return SSG_OK;
 }
 
-int ssg_step(ssg_handle *h, const int32_t *dev_actions, double *dev_obs, double *dev_reward, uint8_t *dev_done,
-             uint8_t *dev_flags, void *stream)
+int ssg_step(ssg_handle *h, const int32_t *dev_actions, double *dev_obs, double *dev_reward, uint8_t *dev_done, uint8_t *dev_flags, void *stream)
 {
     return ssg_rollout_traj(h, dev_actions, 1, dev_obs, dev_reward, dev_done, dev_flags, 0, stream);
 }
@@ -843,10 +874,98 @@ int ssg_wait_host(ssg_handle *h, int slot)
     return SSG_OK;
 }
 
-int ssg_rollout(ssg_handle *h, const int32_t *dev_actions, int K, double *dev_obs, double *dev_reward,
-                uint8_t *dev_done, uint8_t *dev_flags, void *stream)
+int ssg_rollout(ssg_handle *h, const int32_t *dev_actions, int K, double *dev_obs, double *dev_reward, uint8_t *dev_done, uint8_t *dev_flags, void *stream)
 {
     return ssg_rollout_traj(h, dev_actions, K, dev_obs, dev_reward, dev_done, dev_flags, 0, stream);
+}
+
+namespace {
+// One call's K steps: every step's actions, where the outputs go, how many steps one launch may fuse, the stream.
+struct StepCall {
+    const int32_t *actions; // [K][n_envs]
+    int K;
+    double *obs, *reward;
+    uint8_t *done, *flags; // flags may be NULL
+    long long stride; // envs between two steps' output slots; 0: every step writes the same rows
+    int fuse;
+    hipStream_t stream;
+    // the call from step k on: its actions and output slots
+    StepCall from(int k, const ssg_config &cfg) const {
+        const size_t r = (size_t)k * (size_t)stride, D = (size_t)cfg.history * (size_t)(6 + cfg.n_beams);
+        return {actions + (size_t)k * cfg.n_envs, K - k, obs + r * D, reward + r, done + r, flags ? flags + r : nullptr, stride, fuse, stream};
+    }
+};
+
+// ssg_debug_kernel_times, a measurement aid: three events per step (before the full cpSpaceStep, between, after the step kernel); destroyed
+// on every way out of the call, and no timing at all if one of them cannot be created
+struct EventSet {
+    std::vector<hipEvent_t> v;
+    void mark(size_t i, hipStream_t st) const { if (!v.empty()) (void)hipEventRecord(v[i], st); }
+    void create(size_t n) {
+        v.reserve(n);
+        for (size_t i = 0; i < n; ++i) { hipEvent_t ev; if (hipEventCreate(&ev) != hipSuccess) { clear(); return; } v.push_back(ev); }
+    }
+    void clear() { for (auto ev : v) (void)hipEventDestroy(ev); v.clear(); }
+    ~EventSet() { clear(); }
+};
+} // namespace
+
+// history > 2 and config 4: one launch of the step kernel per step.  Non-default history: into the staging rows, then the frame shift (see
+// the kernel).  Config 4: every step is the dyn kernel (traffic ships, goal bodies, contact solver) followed by the step kernel, which
+// reads this step's goal positions and the traffic-contact bit it left in the dyn columns.
+static int steps_one_launch_each(ssg_handle *h, const StepCall &c)
+{
+    const bool dyn = h->cfg.n_ships > 1, shift = h->cfg.history > 2;
+    EventSet evs;
+    if (dyn && h->time_kernels) evs.create(3 * (size_t)c.K);
+    auto failed = [h](const char *what, hipError_t e) { h->dyn_step.queue_lost(); return fail(h, SSG_ERR_HIP, std::string(what) + hipGetErrorString(e)); };
+    for (int k = 0; k < c.K; ++k) {
+        const StepCall s = c.from(k, h->cfg);
+        evs.mark(3 * k, c.stream);
+        const int rc = h->cfg.map_ring > 0 ? ring_take(h, 1, c.stream) : SSG_OK;
+        if (rc != SSG_OK) return rc;
+        if (dyn) {
+            bool rebuild;
+            hipError_t e = h->dyn_step.step_begins(h->layout.dyn_memo.size + h->layout.dyn_npm.size, c.stream, &rebuild);
+            if (e == hipSuccess) e = ssg::launch_dyn_step(h->dev, h->dyn, rebuild, c.stream);
+            if (e != hipSuccess) return failed("dyn step launch: ", e);
+        }
+        evs.mark(3 * k + 1, c.stream);
+        hipError_t e = ssg::launch_step(h->dev, h->block, h->lds, h->lds_bytes, s.actions, 1, shift ? h->dev.obs2 : s.obs, s.reward, s.done,
+                                        s.flags, 0, c.stream);
+        evs.mark(3 * k + 2, c.stream);
+        if (e == hipSuccess && shift) e = ssg::launch_history_shift(h->dev, s.done, s.obs, c.stream);
+        if (e != hipSuccess) return failed("step launch: ", e);
+        if (dyn) h->dyn_step.step_issued();
+    }
+    if (!evs.v.empty()) { // (this call then waits for its own work: a measurement run, not the product path)
+        (void)hipStreamSynchronize(c.stream);
+        for (int k = 0; k < c.K; ++k) {
+            float a = 0.f, b = 0.f;
+            (void)hipEventElapsedTime(&a, evs.v[3 * k], evs.v[3 * k + 1]);
+            (void)hipEventElapsedTime(&b, evs.v[3 * k + 1], evs.v[3 * k + 2]);
+            h->t_dyn_ms += a; h->t_step_ms += b; h->t_steps++;
+        }
+    }
+    return SSG_OK;
+}
+
+// Steps fused into launches (state in registers, bank staged once), at most c.fuse per launch.  map_ring, a brand-new world per episode: an env
+// starts at most one episode per step, so a launch also fuses at most as many steps as the ring has credit — its whole credit, up to 127 steps, in
+// ONE launch (100 + 27 was a launch more per refill cycle) unless SSG_FUSE asks for fewer — then the rings are refilled (two small launches).
+static int steps_fused(ssg_handle *h, const StepCall &c)
+{
+    const bool ring = h->cfg.map_ring > 0;
+    for (int k = 0, n; k < c.K; k += n) {
+        n = c.K - k;
+        if (n > c.fuse && !(ring && c.fuse >= SSG_ROLLOUT_STEPS_PER_LAUNCH)) n = c.fuse;
+        const int rc = ring ? ring_take(h, n, c.stream, &n) : SSG_OK;
+        if (rc != SSG_OK) return rc;
+        const StepCall s = c.from(k, h->cfg);
+        hipError_t e = ssg::launch_step(h->dev, h->block, h->lds, h->lds_bytes, s.actions, n, s.obs, s.reward, s.done, s.flags, c.stride, c.stream);
+        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("step launch: ") + hipGetErrorString(e));
+    }
+    return SSG_OK;
 }
 
 int ssg_rollout_traj(ssg_handle *h, const int32_t *dev_actions, int K, double *dev_obs, double *dev_reward,
@@ -854,137 +973,22 @@ int ssg_rollout_traj(ssg_handle *h, const int32_t *dev_actions, int K, double *d
 {
     int rc = check_ready(h, true);
     if (rc != SSG_OK) return rc;
-    if (!dev_actions || !dev_obs || !dev_reward || !dev_done || K < 1)
-        return fail(h, SSG_ERR_BAD_ARG, "ssg_step/ssg_rollout: NULL buffer or K < 1");
+    if (!dev_actions || !dev_obs || !dev_reward || !dev_done || K < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_step/ssg_rollout: NULL buffer or K < 1");
     if (step_stride_envs != 0 && step_stride_envs < (int64_t)h->cfg.n_envs)
         return fail(h, SSG_ERR_BAD_ARG, "ssg_rollout_traj: step_stride_envs must be 0 or >= n_envs (steps would overlap)");
     rc = refuse_capture(h, stream, "ssg_step/ssg_rollout");
+    if (rc == SSG_OK) rc = prepare(h);
+    if (rc == SSG_OK) rc = flush_remap(h, stream);
+    if (rc == SSG_OK) rc = ring_ready_or_refuse(h);
     if (rc != SSG_OK) return rc;
-    rc = prepare(h);
-    if (rc != SSG_OK) return rc;
-    rc = flush_remap(h, stream);
-    if (rc != SSG_OK) return rc;
-    // One launch runs up to kFuse consecutive steps (state in registers, bank staged once): 100 by default, which
-    // keeps a launch near a millisecond and amortises the fixed launch cost to < 1 %.  SSG_FUSE=1 in the environment
-    // forces one launch per step (the path a policy-in-the-loop caller gets through ssg_step).
+    // One launch runs up to kFuse consecutive steps (state in registers, bank staged once): 100 by default, which keeps a launch near a
+    // millisecond and amortises the fixed launch cost to < 1 %.  SSG_FUSE=1 in the environment forces one launch per step.
     static const int kFuse = [] {
         const char *s = std::getenv("SSG_FUSE");
-        const int v = s ? std::atoi(s) : SSG_ROLLOUT_STEPS_PER_LAUNCH;
-        return v < 1 ? 1 : v;
+        return std::max(1, s ? std::atoi(s) : SSG_ROLLOUT_STEPS_PER_LAUNCH);
     }();
-    const long long traj = (long long)step_stride_envs;
-    const size_t D = (size_t)h->cfg.history * (size_t)(6 + h->cfg.n_beams);
-    // output slots of step k (the same rows for every step when traj == 0)
-    auto obs_at = [&](int k) { return dev_obs + (size_t)k * (size_t)traj * D; };
-    auto rew_at = [&](int k) { return dev_reward + (size_t)k * (size_t)traj; };
-    auto done_at = [&](int k) { return dev_done + (size_t)k * (size_t)traj; };
-    auto flags_at = [&](int k) { return dev_flags ? dev_flags + (size_t)k * (size_t)traj : nullptr; };
-    const bool dyn = h->cfg.n_ships > 1;
-    if (h->cfg.history > 2 || dyn) {
-        // non-default history: one launch per step into the staging rows, then the frame shift (see the kernel).
-        // config 4: every step is the dyn kernel (traffic ships, goal bodies, contact solver) followed by the step
-        // kernel, which reads this step's goal positions and the traffic-contact bit it left in the dyn columns.
-        const bool shift = h->cfg.history > 2;
-        if (h->cfg.map_ring > 0 && !h->ring_ready) return fail(h, SSG_ERR_NOT_BOUND, "map_ring mode: call ssg_refill_worlds first");
-        // measurement aid: three events per step (before the full cpSpaceStep, between, after the step kernel); destroyed on every
-        // way out of this call, and no timing at all if one of them cannot be created
-        struct EventSet {
-            std::vector<hipEvent_t> v;
-            bool empty() const { return v.empty(); }
-            hipEvent_t operator[](size_t i) const { return v[i]; }
-            void create(size_t n) {
-                v.reserve(n);
-                for (size_t i = 0; i < n; ++i) { hipEvent_t ev; if (hipEventCreate(&ev) != hipSuccess) { clear(); return; } v.push_back(ev); }
-            }
-            void clear() { for (auto ev : v) (void)hipEventDestroy(ev); v.clear(); }
-            ~EventSet() { clear(); }
-        } evs;
-        if (dyn && h->time_kernels) evs.create(3 * (size_t)K);
-        for (int k = 0; k < K; ++k) {
-            if (!evs.empty()) (void)hipEventRecord(evs[3 * k], static_cast<hipStream_t>(stream));
-            if (h->cfg.map_ring > 0) { // every step may start one episode per env: keep an unused world in every ring
-                if (h->ring_credit < 1) {
-                    rc = ring_refill(h, nullptr, stream);
-                    if (rc != SSG_OK) return rc;
-                }
-                h->ring_credit -= 1;
-            }
-            if (dyn) {
-                hipError_t e = hipSuccess;
-                if (!h->dyn_queue_valid) { // the classify pass rebuilds the queue: this step's bucket counters start from zero
-                    h->dev.dyn_par = 0;
-                    e = hipMemsetAsync(h->dev.dyn_count, 0, ssg::kDynCountWords * sizeof(unsigned), static_cast<hipStream_t>(stream));
-                }
-                if (h->dev.dyn_memo) {
-                    if (++h->memo_steps > kMemoGenSteps) memo_new_generation(h);
-                    if (h->memo_clear_pending && e == hipSuccess) {
-                        e = hipMemsetAsync(h->dev.dyn_memo, 0, ((size_t)ssg::kMemoEntries * ssg::kMemoStride + (size_t)ssg::kNpmEntries * ssg::kNpmStride) * sizeof(unsigned long long),
-                                           static_cast<hipStream_t>(stream)); // (the narrowphase memo follows the state memo in the blob)
-                        h->memo_clear_pending = false;
-                    }
-                }
-                h->dev.dyn_seq = ++h->dyn_seq;
-                if (!h->dyn_queue_valid) h->n_classify++;
-                if (e == hipSuccess) e = ssg::launch_dyn_step(h->dev, h->dyn, !h->dyn_queue_valid, static_cast<hipStream_t>(stream));
-                if (e != hipSuccess) {
-                    h->dyn_queue_valid = false; // (a queue the full step never consumed must not survive: the next call starts over)
-                    return fail(h, SSG_ERR_HIP, std::string("dyn step launch: ") + hipGetErrorString(e));
-                }
-            }
-            if (!evs.empty()) (void)hipEventRecord(evs[3 * k + 1], static_cast<hipStream_t>(stream));
-            hipError_t e = ssg::launch_step(h->dev, h->block, h->lds, h->lds_bytes, dev_actions + (size_t)k * h->cfg.n_envs, 1,
-                                            shift ? h->dev.obs2 : obs_at(k), rew_at(k), done_at(k), flags_at(k), 0,
-                                            static_cast<hipStream_t>(stream));
-            if (!evs.empty()) (void)hipEventRecord(evs[3 * k + 2], static_cast<hipStream_t>(stream));
-            if (e == hipSuccess && shift) e = ssg::launch_history_shift(h->dev, done_at(k), obs_at(k), static_cast<hipStream_t>(stream));
-            if (e != hipSuccess) {
-                h->dyn_queue_valid = false; // (the next call rebuilds the dyn queue from the flags, counters zeroed)
-                return fail(h, SSG_ERR_HIP, std::string("step launch: ") + hipGetErrorString(e));
-            }
-            if (dyn) { // the step kernel's body role has queued the envs whose bodies must be stepped next, in the other counter set
-                h->dyn_queue_valid = true;
-                h->masked_resets_since_step = 0;
-                h->dev.dyn_par ^= 1;
-            }
-        }
-        if (!evs.empty()) { // (this call then waits for its own work: a measurement run, not the product path)
-            (void)hipStreamSynchronize(static_cast<hipStream_t>(stream));
-            for (int k = 0; k < K; ++k) {
-                float a = 0.f, b = 0.f;
-                (void)hipEventElapsedTime(&a, evs[3 * k], evs[3 * k + 1]);
-                (void)hipEventElapsedTime(&b, evs[3 * k + 1], evs[3 * k + 2]);
-                h->t_dyn_ms += a; h->t_step_ms += b; h->t_steps++;
-            }
-        }
-        return SSG_OK;
-    }
-    if (h->cfg.map_ring > 0) {
-        // a brand-new world per episode: an env starts at most one episode per step, and its ring holds `ring_credit`
-        // unused worlds — fuse at most that many steps, then refill the rings (two small launches on the same stream)
-        if (!h->ring_ready) return fail(h, SSG_ERR_NOT_BOUND, "map_ring mode: call ssg_refill_worlds first");
-        for (int k = 0; k < K;) {
-            if (h->ring_credit < 1) {
-                rc = ring_refill(h, nullptr, stream);
-                if (rc != SSG_OK) return rc;
-            }
-            // (up to the ring's whole credit, at most 127 steps, in ONE launch: 100 + 27 was a launch more per refill cycle)
-            int kk = (K - k < h->ring_credit) ? (K - k) : h->ring_credit;
-            if (kFuse < SSG_ROLLOUT_STEPS_PER_LAUNCH && kk > kFuse) kk = kFuse; // (SSG_FUSE = 1: the one-launch-per-step experiment)
-            hipError_t e = ssg::launch_step(h->dev, h->block, h->lds, h->lds_bytes, dev_actions + (size_t)k * h->cfg.n_envs, kk,
-                                            obs_at(k), rew_at(k), done_at(k), flags_at(k), traj, static_cast<hipStream_t>(stream));
-            if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("step launch: ") + hipGetErrorString(e));
-            h->ring_credit -= kk;
-            k += kk;
-        }
-        return SSG_OK;
-    }
-    for (int k = 0; k < K; k += kFuse) {
-        const int kk = (K - k < kFuse) ? (K - k) : kFuse;
-        hipError_t e = ssg::launch_step(h->dev, h->block, h->lds, h->lds_bytes, dev_actions + (size_t)k * h->cfg.n_envs, kk,
-                                        obs_at(k), rew_at(k), done_at(k), flags_at(k), traj, static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("step launch: ") + hipGetErrorString(e));
-    }
-    return SSG_OK;
+    const StepCall c = {dev_actions, K, dev_obs, dev_reward, dev_done, dev_flags, (long long)step_stride_envs, kFuse, static_cast<hipStream_t>(stream)};
+    return h->cfg.history > 2 || h->cfg.n_ships > 1 ? steps_one_launch_each(h, c) : steps_fused(h, c);
 }
 
 // the activation kind in the low byte, SSG_POLICY_SEPARATE_VALUE or not, and no other bit
@@ -1372,9 +1376,8 @@ static int prepare_steps(ssg_handle *h, const PolicyCall &c, void *stream)
 {
     int rc = check_filter_members(h, c);
     if (rc == SSG_OK) rc = check_ready(h, true);
-    if (rc != SSG_OK) return rc;
-    if (h->cfg.map_ring > 0 && !h->ring_ready) return fail(h, SSG_ERR_NOT_BOUND, "map_ring mode: call ssg_refill_worlds first");
-    rc = refuse_capture(h, stream, c.what);
+    if (rc == SSG_OK) rc = ring_ready_or_refuse(h);
+    if (rc == SSG_OK) rc = refuse_capture(h, stream, c.what);
     if (rc == SSG_OK) rc = prepare(h);
     if (rc == SSG_OK) rc = prepare_policy(h);
     if (rc == SSG_OK) rc = prepare_policy_filter(h);
@@ -2929,7 +2932,7 @@ int ssg_generate_bank(ssg_handle *h, uint64_t seed, double width_frac, double *d
     hipError_t e = ssg::launch_generate_bank(seed, n_maps, h->cfg.n_goals, h->cfg.width, h->cfg.height, width_frac,
                                              h->cfg.spawn_x, h->cfg.spawn_y, dev_bank, dev_raw, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("generate_bank launch: ") + hipGetErrorString(e));
-    if (dev_bank == h->bank) { h->dyn.bank_epoch++; h->dyn_queue_valid = false; memo_new_generation(h); } // regenerated in place
+    if (dev_bank == h->bank) h->dyn_step.bank_changed(); // regenerated in place
     return SSG_OK;
 }
 
@@ -2939,15 +2942,15 @@ int ssg_refill_worlds(ssg_handle *h, uint64_t seed, double width_frac, double *d
     if (rc != SSG_OK) return rc;
     if (h->cfg.map_ring <= 0) return fail(h, SSG_ERR_BAD_ARG, "ssg_refill_worlds: the handle was not created with map_ring");
     if (!(width_frac > 0.0) || !(width_frac <= 1.0)) return fail(h, SSG_ERR_BAD_ARG, "ssg_refill_worlds: bad width_frac");
-    h->ring_seed = seed;
-    h->ring_width_frac = width_frac;
+    h->ring.seed = seed;
+    h->ring.width_frac = width_frac;
     if (!h->zeroed) { // zero a freshly bound blob HERE, before the rings' counters are written (a later full ssg_reset must not wipe them)
-        hipError_t e = hipMemsetAsync(h->state, 0, h->nbytes, static_cast<hipStream_t>(stream));
+        hipError_t e = hipMemsetAsync(h->state, 0, h->layout.nbytes, static_cast<hipStream_t>(stream));
         if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("ssg_refill_worlds: ") + hipGetErrorString(e));
         h->zeroed = true;
     }
     rc = ring_refill(h, dev_raw, stream);
-    if (rc == SSG_OK) h->ring_ready = true;
+    if (rc == SSG_OK) h->ring.ready = true;
     return rc;
 }
 
@@ -2956,11 +2959,8 @@ int ssg_dyn_invalidate(ssg_handle *h, const uint8_t *dev_mask, void *stream)
     int rc = check_ready(h, false);
     if (rc != SSG_OK) return rc;
     if (h->cfg.n_ships <= 1) return SSG_OK; // nothing to wake
-    h->dyn_queue_valid = false;
-    if (!dev_mask) { // "the blob may have been copied or restored": its memo tables may hold another bank's / handle's results under
-        memo_new_generation(h);        // this handle's generation (the key names the record, not the bank's contents), so they are
-        h->memo_clear_pending = true;  // emptied before the next launch that could read them
-    }
+    if (dev_mask) h->dyn_step.queue_lost();
+    else h->dyn_step.blob_rebound(); // "the blob may have been copied or restored"
     hipError_t e = ssg::launch_dyn_invalidate(h->dev, dev_mask, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("dyn_invalidate launch: ") + hipGetErrorString(e));
     return SSG_OK;
@@ -3010,8 +3010,8 @@ int ssg_debug_kernel_times(ssg_handle *h, int enable, double *dyn_step_us, doubl
 int ssg_debug_dyn_counters(const ssg_handle *h, uint64_t *full_steps, uint64_t *queue_rebuilds)
 {
     if (!h) return SSG_ERR_BAD_ARG;
-    if (full_steps) *full_steps = h->dyn_seq;
-    if (queue_rebuilds) *queue_rebuilds = h->n_classify;
+    if (full_steps) *full_steps = h->dyn_step.launches;
+    if (queue_rebuilds) *queue_rebuilds = h->dyn_step.classifies;
     return SSG_OK;
 }
 

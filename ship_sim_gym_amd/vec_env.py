@@ -499,7 +499,7 @@ class ShipVecEnv(*_BASES):
 
         For these handles the blob, the output rows and the bank are all there is.  The host-side fields of ``struct ssg_handle``
         (csrc/shipsim_api.cpp) and why none of them is state here:
-        * cfg, dev, n_pad, the off_* offsets, nbytes, block, lds, lds_bytes: functions of the configuration and of n_maps; ``restore``
+        * cfg, dev, layout (n_pad, nbytes, every section's offset), block, lds, lds_bytes: functions of the configuration and of n_maps; ``restore``
           re-installs the bank through ``set_bank``, which derives them again;
         * state, bank, n_maps: pointers and a count; the tensors behind them are what the snapshot holds;
         * prepared, policy_prepared, ppo_prepared, policy_filter_prepared, policy_boot_prepared: "the kernel's LDS limit is set", set
@@ -507,9 +507,8 @@ class ShipVecEnv(*_BASES):
         * zeroed: "the blob was zeroed by a full reset"; ``restore`` runs the env's first full reset itself when none has happened,
           so that a later ``reset_tensor()`` keeps the restored counters as it keeps the original's;
         * remap_pending: set when a bank shrinks; the remap it asks for takes map ids modulo n_maps, which the restored ids satisfy;
-        * dyn, dyn_queue_valid, dyn_seq, n_classify, masked_resets_since_step, memo_gen, memo_clear_pending, memo_steps, the
-          off_dyn_* offsets: config 4 only (n_ships = 4);
-        * ring_ready, ring_seed, ring_width_frac, ring_credit, off_ring_*: map_ring only (map_mode="fresh_device");
+        * dyn, dyn_step (the queue's validity, the launch counters, the memo's generation): config 4 only (n_ships = 4);
+        * ring (ready, seed, width_frac, credit, the refill queue's pointers): map_ring only (map_mode="fresh_device");
         * time_kernels, t_dyn_ms, t_step_ms, t_steps: a measurement aid's accumulators;
         * host_ev, host_ev_made: completion events of the numpy protocols' copies; no step may be in flight (checked);
         * pop_sizes, dev_slices, slice_max, slice_min, flt, tob, rec, rec_ids, adv_norm_*: bindings (population slices, observation

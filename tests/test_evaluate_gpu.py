@@ -257,11 +257,12 @@ def test_population_evaluation_is_each_member_alone(torch_cuda, split):
     env.close()
 
 
-@pytest.mark.parametrize("kind", ["history3", "n_ships4"])
+@pytest.mark.parametrize("kind", ["history3", "n_ships4", "ring4"])
 def test_other_handle_kinds(torch_cuda, kind):
     torch = torch_cuda
     from ship_sim_gym_amd.evaluate import NativeEvaluator
-    kw = {"history3": dict(history=3), "n_ships4": dict(n_ships=4, n_maps=16)}[kind]
+    # (ring4: a world per episode out of rings of 4 — three episode starts between two refills, episodes of at most 40 steps)
+    kw = {"history3": dict(history=3), "n_ships4": dict(n_ships=4, n_maps=16), "ring4": dict(map_mode="fresh_device", ring=4)}[kind]
     a, b = _vec(128, max_steps=MAX_STEPS, **kw), _vec(128, max_steps=MAX_STEPS, **kw)
     pol = _policy(torch, a.states_history, act="relu", seed=2)
     ev = NativeEvaluator(a)

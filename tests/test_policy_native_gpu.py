@@ -105,16 +105,29 @@ def test_philox_uniforms_are_the_documented_stream(torch_cuda):
         env.close()
 
 
-def test_fused_rollout_equals_stepwise_loop(torch_cuda):
+# config4: every step is the full cpSpaceStep's launch and the step kernel's, the dyn queue handed from step to step; ring4: a world per
+# episode, three episode starts between two refills and episodes of 3 steps, so both 7-step rollouts refill inside the loop
+FUSED_KINDS = {"bank": (1000, 64, {}),
+               "config4": (256, 64, dict(n_ships=4, n_beams=8, n_maps=4, env_config=_env_config(2, 20))),
+               "ring4": (256, 7, dict(map_mode="fresh_device", ring=4, n_beams=8, env_config=_env_config(2, 3)))}
+
+
+@pytest.mark.parametrize("kind", list(FUSED_KINDS))
+def test_fused_rollout_equals_stepwise_loop(torch_cuda, kind):
     torch = torch_cuda
-    n, K = 1000, 64
-    a, b = _vec(n), _vec(n)
+    n, K, kw = FUSED_KINDS[kind]
+    a, b = _vec(n, **kw), _vec(n, **kw)
     a.reset_tensor(); b.reset_tensor()
+
+    def same_state():
+        from ship_sim_gym_amd import _native as N
+        bodies = (N.F_TRAFFIC, N.F_GOAL_BODIES) if kind == "config4" else ()
+        return torch.equal(a.obs, b.obs) and _same_columns(torch, a, b) and all(torch.equal(a.field(f), b.field(f)) for f in bodies)
     net, pol = _policy(torch, a.states_history)
     fused = a.rollout_policy(pol, K, seed=11, step0=500)
     step = _stepwise(b, pol, K, 11, 500)
     _assert_same(torch, fused, step, "philox")
-    assert torch.equal(a.obs, b.obs) and _same_columns(torch, a, b)
+    assert same_state()
     assert int(fused["done"].sum()) > 0 or int(fused["flags"].sum()) > 0
     # caller uniforms and a preallocated `out` (first dimension longer than K)
     u = torch.rand((K, n), device=a.device)
@@ -124,7 +137,7 @@ def test_fused_rollout_equals_stepwise_loop(torch_cuda):
     step2 = _stepwise(b, pol, K, 0, 0, uniforms=u)
     _assert_same(torch, fused2, step2, "uniforms")
     assert fused2["obs"].data_ptr() == out["obs"].data_ptr() and int(out["act"][K:].eq(3).all()) == 1
-    assert torch.equal(a.obs, b.obs) and _same_columns(torch, a, b)
+    assert same_state()
     a.close(); b.close()
 
 
