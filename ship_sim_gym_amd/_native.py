@@ -382,6 +382,11 @@ def check(rc, handle=None, what=""):
         raise ShipSimError("%s failed: %s (%s)" % (what or "libshipsim call", L.ssg_strerror(rc).decode(), msg))
 
 
+def ptr(t):
+    """A tensor's address as a pointer argument of a C call; None stays None (NULL)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
 def default_config():
     c = Config()
     check(lib().ssg_default_config(C.byref(c)), None, "ssg_default_config")

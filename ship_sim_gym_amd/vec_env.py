@@ -65,6 +65,58 @@ def _trainer_bases():
 _BASES = _trainer_bases()
 
 
+def native_config(num_envs, game_config, env_config, device_index, map_mode="bank", env_id_base=0, auto_reset=True, n_beams=None,
+                  fix_collision_reward=False, bank_in_global=False, exact_lidar=False, n_ships=1, rllib=False, ring=32, dyn_memo=True):
+    """(ssg_config, auto_reset, rllib_fused) of a ShipVecEnv, from its constructor's arguments alone.
+
+    rllib_fused: the RLlib flow WITHOUT a reset launch (ssg_set_terminal_obs, history <= 2, worlds that live on the device): the step
+    kernel resets a done env itself — its row of `obs` is then the reset observation reset_at(i) hands out — and also stores the env's
+    TERMINAL observation in `term_obs`, which vector_step reports.  Otherwise (history > 2, host-drawn worlds) the rllib flow runs
+    without in-kernel reset and resets its done envs with ONE masked ssg_reset per step."""
+    if map_mode not in ("bank", "fresh", "fresh_device"):
+        raise ValueError("map_mode must be 'bank', 'fresh' or 'fresh_device'")
+    on_device = map_mode in ("bank", "fresh_device")
+    rllib_fused = bool(rllib) and env_config.HISTORY_SIZE <= 2 and on_device
+    auto_reset = bool(auto_reset) and (not rllib or rllib_fused)
+    bounds = tuple(game_config.BOUNDS)
+    c = N.default_config()
+    c.device_id = int(device_index)
+    c.n_envs = int(num_envs)
+    c.env_id_base = int(env_id_base)
+    if n_beams is None:
+        if getattr(env_config, "USE_LIDAR_CONFIG", False):
+            lc = env_config.LIDAR_CONFIG
+            c.n_beams, c.lidar_spread_deg, c.lidar_dist = lc.N_BEAMS, lc.ANGULAR_SPREAD, lc.DISTANCE
+        else:  # the reference ignores LidarConfig: LiDAR() defaults (models.py:29,150)
+            c.n_beams = cfgmod.LIDAR_DEFAULT_N_BEAMS
+    else:
+        c.n_beams = int(n_beams)
+    c.history = int(env_config.HISTORY_SIZE)
+    c.max_steps = int(env_config.MAX_STEPS)
+    c.n_goals = cfgmod.N_GOALS
+    c.width, c.height = float(bounds[0]), float(bounds[1])
+    c.dt = game_config.SPEED * cfgmod.BASE_DT                 # game.py:194: speed * base_dt
+    c.damping_pow_dt = math.pow(cfgmod.SPACE_DAMPING, c.dt)   # cpSpaceStep: pow(space.damping, dt)
+    c.spawn_x, c.spawn_y = bounds[0] / 2, 25.0                # game.py:274
+    flags = 0
+    if auto_reset and on_device:
+        flags |= N.FLAG_AUTO_RESET
+    if fix_collision_reward:
+        flags |= N.FLAG_FIX_COLLISION_REWARD
+    if bank_in_global or map_mode == "fresh":
+        flags |= N.FLAG_BANK_IN_GLOBAL
+    if exact_lidar:
+        flags |= N.FLAG_EXACT_LIDAR
+    if not dyn_memo:  # config 4 measurement aid: every queued env computes its cpSpaceStep (no memo table look-ups)
+        flags |= N.FLAG_DYN_MEMO_OFF
+    c.flags = flags
+    # n_ships = 4: BASELINE configs[3] — env.game.add_default_traffic() (game.py:279-286) after every reset: three
+    # traffic ships, dynamic goal bodies and Chipmunk's contact solver (csrc/shipsim_dynamics.hip)
+    c.n_ships = int(n_ships)
+    c.map_ring = int(ring) if map_mode == "fresh_device" else 0
+    return c, auto_reset, rllib_fused
+
+
 class EnvHandle(object):
     """One env of a ShipVecEnv, for the per-env calls of the trainers' APIs (`env_method`, `get_attr`, `set_attr`,
     RLlib's `get_unwrapped()`): attribute reads fall through to the batch, `reset()`/`seed()`/`render()` act on
@@ -114,72 +166,55 @@ class ShipVecEnv(*_BASES):
         if env_config.HISTORY_SIZE < 1:  # ship_env.py:46-47
             raise ValueError("history_size must be greater than zero")
         self.num_envs = int(num_envs)
-        self._i32 = torch.int32
-        self.device = torch.device(device)
-        self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self._i32, self._cur_stream = torch.int32, torch.cuda.current_stream
+        dev = torch.device(device)
+        self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
         self.device = torch.device("cuda", self._dev_index)  # (always with its index: tensors report `cuda:N`)
         self.map_mode = map_mode
         self.bounds = tuple(game_config.BOUNDS)
         self.width_frac = float(width_frac)
         # rllib=True: the RLlib VectorEnv flow — vector_step returns the TERMINAL observation of a done env and the
-        # caller's reset_at(i) is the one reset it gets (no in-kernel auto-reset underneath)
+        # caller's reset_at(i) is the one reset it gets (no in-kernel auto-reset underneath, or the fused flow of native_config)
         self.rllib = bool(rllib)
-        # The RLlib flow WITHOUT a reset launch (ssg_set_terminal_obs, history <= 2, worlds that live on the device): the step
-        # kernel resets a done env itself — its row of `obs` is then the reset observation reset_at(i) hands out — and also
-        # stores the env's TERMINAL observation in `term_obs`, which vector_step reports.  Otherwise (history > 2, host-drawn
-        # worlds) the rllib flow runs without in-kernel reset and resets its done envs with ONE masked ssg_reset per step.
-        self._rllib_fused = self.rllib and env_config.HISTORY_SIZE <= 2 and map_mode in ("bank", "fresh_device")
-        self.auto_reset = bool(auto_reset) and (not self.rllib or self._rllib_fused)
-        self.env_id_base = int(env_id_base)
+        self.cfg, self.auto_reset, self._rllib_fused = native_config(
+            num_envs, game_config, env_config, self._dev_index, map_mode=map_mode, env_id_base=env_id_base, auto_reset=auto_reset,
+            n_beams=n_beams, fix_collision_reward=fix_collision_reward, bank_in_global=bank_in_global, exact_lidar=exact_lidar,
+            n_ships=n_ships, rllib=rllib, ring=ring, dyn_memo=dyn_memo)
+        self.env_id_base, self.n_ships, self.ring = int(env_id_base), int(n_ships), int(self.cfg.map_ring)
         self.game_config, self.env_config = game_config, env_config
-
-        c = N.default_config()
-        c.device_id = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        c.n_envs = self.num_envs
-        c.env_id_base = self.env_id_base
-        if n_beams is None:
-            if getattr(env_config, "USE_LIDAR_CONFIG", False):
-                lc = env_config.LIDAR_CONFIG
-                c.n_beams, c.lidar_spread_deg, c.lidar_dist = lc.N_BEAMS, lc.ANGULAR_SPREAD, lc.DISTANCE
-            else:  # the reference ignores LidarConfig: LiDAR() defaults (models.py:29,150)
-                c.n_beams = cfgmod.LIDAR_DEFAULT_N_BEAMS
-        else:
-            c.n_beams = int(n_beams)
-        c.history = int(env_config.HISTORY_SIZE)
-        c.max_steps = int(env_config.MAX_STEPS)
-        c.n_goals = cfgmod.N_GOALS
-        c.width, c.height = float(self.bounds[0]), float(self.bounds[1])
-        c.dt = game_config.SPEED * cfgmod.BASE_DT                 # game.py:194: speed * base_dt
-        c.damping_pow_dt = math.pow(cfgmod.SPACE_DAMPING, c.dt)   # cpSpaceStep: pow(space.damping, dt)
-        c.spawn_x, c.spawn_y = self.bounds[0] / 2, 25.0           # game.py:274
-        flags = 0
-        if self.auto_reset and map_mode in ("bank", "fresh_device"):
-            flags |= N.FLAG_AUTO_RESET
-        if fix_collision_reward:
-            flags |= N.FLAG_FIX_COLLISION_REWARD
-        if bank_in_global or map_mode == "fresh":
-            flags |= N.FLAG_BANK_IN_GLOBAL
-        if exact_lidar:
-            flags |= N.FLAG_EXACT_LIDAR
-        if not dyn_memo:  # config 4 measurement aid: every queued env computes its cpSpaceStep (no memo table look-ups)
-            flags |= N.FLAG_DYN_MEMO_OFF
-        c.flags = flags
-        # n_ships = 4: BASELINE configs[3] — env.game.add_default_traffic() (game.py:279-286) after every reset: three
-        # traffic ships, dynamic goal bodies and Chipmunk's contact solver (csrc/shipsim_dynamics.hip)
-        c.n_ships = int(n_ships)
-        self.n_ships = int(n_ships)
-        self.ring = int(ring) if map_mode == "fresh_device" else 0
-        c.map_ring = self.ring
-        self.cfg = c
-        self.n_states = 6 + c.n_beams                              # ship_env.py:43
-        self.states_history = self.n_states * c.history            # ship_env.py:44
+        self.n_states = 6 + self.cfg.n_beams                       # ship_env.py:43
+        self.states_history = self.n_states * self.cfg.history     # ship_env.py:44
         self.action_space = spaces.Discrete(3)                     # ship_env.py:19
         self.observation_space = spaces.Box(low=0, high=max(self.bounds), shape=(self.states_history,),
                                             dtype=np.uint8)       # ship_env.py:48 (declared uint8; obs are float64)
+        self.host_slots = max(2, min(8, int(host_slots)))  # (ssg_step_host has eight completion-event slots)
+        self.copy_host_outputs = bool(copy_host_outputs)
+        # everything else a ShipVecEnv holds, in its initial state
+        self._host = None  # pinned host side of the numpy protocols, made by the first step_async (the tensor API never needs it)
+        self.term_obs = None            # enable_terminal_obs
+        self._traj_plans = {}           # rollout_tensor(trajectory=True, out=...): launch plans by the obs buffer's address
+        self._pop_slices = None         # set_population_slices: (sizes, device table)
+        self._timeout_boot = None       # set_timeout_bootstrap: {"term_obs", "boot"}
+        self._obs_filter = None         # set_obs_filter
+        self._adv_norm_scratch = None   # set_adv_norm
+        self._full_reset_done = False   # reset_tensor(mask=None) has run (the handle's first full reset zeroes the blob)
+        self._pending = None
+        self._closed = False
+        self._handles = {}
+        self._await_reset = np.zeros(self.num_envs, dtype=bool)  # rllib flow: done envs already re-initialised
+        self._reset_obs_h = None
+        self._create_handle()
+        self._first_bank(bank, n_maps, map_seed)
+        if self._rllib_fused:
+            self.enable_terminal_obs()
+        self._call_base_ctors()
 
-        L = N.lib()
+    def _create_handle(self):
+        """ssg_create, then the two device blocks: the state blob (bound) and the output block, whose addresses `_out` keeps."""
+        torch = _torch()
+        self._lib = L = N.lib()
         self._h = C.c_void_p()
-        N.check(L.ssg_create(C.byref(c), C.byref(self._h)), None, "ssg_create")
+        N.check(L.ssg_create(C.byref(self.cfg), C.byref(self._h)), None, "ssg_create")
         nbytes = C.c_size_t()
         N.check(L.ssg_state_nbytes(self._h, C.byref(nbytes)), self._h, "ssg_state_nbytes")
         # obs | reward | done | flags are views of ONE device block (256-byte aligned sections), so that the numpy protocols
@@ -190,26 +225,25 @@ class ShipVecEnv(*_BASES):
         self._o_done = self._o_rew + up(n_ * 8)
         self._o_flags = self._o_done + up(n_)
         self._out_nbytes = self._o_flags + up(n_)
-        self.host_slots = max(2, min(8, int(host_slots)))  # (ssg_step_host has eight completion-event slots)
-        self.copy_host_outputs = bool(copy_host_outputs)
         with torch.cuda.device(self.device):
             self.state = torch.zeros(nbytes.value, dtype=torch.uint8, device=self.device)
             self._out_blob = torch.zeros(self._out_nbytes, dtype=torch.uint8, device=self.device)
             self.obs, self.reward, self.done, self.flags = self._blob_views(self._out_blob)
             self._actions = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
-        self._host = None  # pinned host side of the numpy protocols, made by the first step_async (the tensor API never needs it)
-        self.term_obs = None
-        N.check(L.ssg_bind_state(self._h, C.c_void_p(self.state.data_ptr())), self._h, "ssg_bind_state")
+        # the four output addresses as plain integers, for the launch path: the block is allocated once and only ever copied into
+        self._out = tuple(t.data_ptr() for t in (self.obs, self.reward, self.done, self.flags))
+        N.check(L.ssg_bind_state(self._h, N.ptr(self.state)), self._h, "ssg_bind_state")
 
-        # ---- map bank ----
-        if map_mode == "bank":
+    def _first_bank(self, bank, n_maps, map_seed):
+        """The constructor's map bank, per map mode."""
+        torch = _torch()
+        self.bank_polys = self.bank_goals = None
+        if self.map_mode == "bank":
             if bank is None:
                 bank, self.bank_polys, self.bank_goals = worldgen.build_bank(
-                    n_maps, self.bounds, n_goals=c.n_goals, width_frac=self.width_frac, seed=map_seed)
-            else:
-                self.bank_polys = self.bank_goals = None
+                    n_maps, self.bounds, n_goals=self.cfg.n_goals, width_frac=self.width_frac, seed=map_seed)
             self.set_bank(bank)
-        elif map_mode == "fresh":
+        elif self.map_mode == "fresh":
             # reference-exact: ShipGame.__init__ ends with self.reset() (game.py:58), so constructing an env already
             # consumes one world's worth of RNG; the user's reset() draws another (App. B-17).
             self.bank_host = np.zeros((self.num_envs, N.MAP_STRIDE), dtype=np.float64)
@@ -217,23 +251,12 @@ class ShipVecEnv(*_BASES):
             for e in range(self.num_envs):
                 self._fresh_world(e)
             self.set_bank(self.bank_host)
-        elif map_mode == "fresh_device":
+        else:
             with torch.cuda.device(self.device):
                 bank = torch.zeros((self.num_envs * self.ring, N.MAP_STRIDE), dtype=torch.float64, device=self.device)
-            self.bank_polys = self.bank_goals = None
             self.map_seed = int(map_seed)
             self.set_bank(bank)
             self.refill_worlds(self.map_seed)  # fills every ring: episodes 0 .. ring-1 of every env
-        else:
-            raise ValueError("map_mode must be 'bank', 'fresh' or 'fresh_device'")
-        if self._rllib_fused:
-            self.enable_terminal_obs()
-        self._pending = None
-        self._closed = False
-        self._handles = {}
-        self._await_reset = np.zeros(self.num_envs, dtype=bool)  # rllib flow: done envs already re-initialised
-        self._reset_obs_h = None
-        self._call_base_ctors()
 
     def _call_base_ctors(self):
         """The trainers' base-class constructors.  stable-baselines declares VecEnv.__init__(num_envs, observation_space,
@@ -273,7 +296,34 @@ class ShipVecEnv(*_BASES):
 
     # ------------------------------------------------------------------------------------------------
     def _stream(self):
-        return C.c_void_p(_torch().cuda.current_stream(self.device).cuda_stream)
+        return C.c_void_p(self._cur_stream(self.device).cuda_stream)
+
+    def _arg(self, t, dtypes, shape, what, more_rows=False, exc=ValueError):
+        """THE check of a tensor argument: `t` is what the C call will read it as — of `dtypes` (one dtype or a tuple of them), of
+        `shape` (an int: that many elements, in any shape; a tuple: exactly that shape, or with more_rows a first dimension of at
+        least shape[0]), contiguous and on this env's device — or `exc` is raised, naming the call and the argument (`what`), what
+        was expected and what was got.  Returns the tensor's address, a plain integer."""
+        if ((t.dtype is dtypes or (type(dtypes) is tuple and t.dtype in dtypes)) and t.device == self.device and t.is_contiguous()
+                and (t.numel() == shape if type(shape) is int else
+                     t.dim() == len(shape) and tuple(t.shape[1:]) == tuple(shape[1:])
+                     and (t.shape[0] >= shape[0] if more_rows else t.shape[0] == shape[0]))):
+            return t.data_ptr()
+        want = "%d elements" % shape if type(shape) is int else "shape [%s]" % ", ".join(
+            [(">= %d" if more_rows else "%d") % shape[0]] + ["%d" % s for s in shape[1:]])
+        names = " / ".join(str(d) for d in (dtypes if type(dtypes) is tuple else (dtypes,)))
+        raise exc("%s must be a contiguous %s tensor of %s on %s (got %s %s on %s, strides %s)"
+                  % (what, names, want, self.device, t.dtype, tuple(t.shape), t.device, tuple(t.stride())))
+
+    def _launch(self, what, fn, *args):
+        """THE launch call: fn(handle, *args); a non-zero status with another device current: switch to this env's and repeat; then
+        N.check.  The arguments are plain integers (addresses, counts, the stream's handle), so the success case is one ctypes call."""
+        rc = fn(self._h, *args)
+        if rc:
+            torch = _torch()
+            if torch.cuda.current_device() != self._dev_index:
+                with torch.cuda.device(self.device):
+                    rc = fn(self._h, *args)
+            N.check(rc, self._h, what)
 
     def _blob_views(self, blob):
         """(obs [N, D] f64, reward [N] f64, done [N] u8, flags [N] u8) views of an output block (device or pinned host)."""
@@ -310,7 +360,7 @@ class ShipVecEnv(*_BASES):
         if on and self.term_obs is None:
             with torch.cuda.device(self.device):
                 self.term_obs = torch.zeros((self.num_envs, self.states_history), dtype=torch.float64, device=self.device)
-        N.check(N.lib().ssg_set_terminal_obs(self._h, C.c_void_p(self.term_obs.data_ptr()) if on else None), self._h, "ssg_set_terminal_obs")
+        N.check(N.lib().ssg_set_terminal_obs(self._h, N.ptr(self.term_obs if on else None)), self._h, "ssg_set_terminal_obs")
         if not on:
             self.term_obs = None
         return self.term_obs
@@ -327,13 +377,11 @@ class ShipVecEnv(*_BASES):
             bank = torch.from_numpy(np.ascontiguousarray(bank, dtype=np.float64)).to(self.device)
         if not bank.is_cuda:
             bank = bank.to(self.device)
-        assert bank.dtype == torch.float64 and bank.dim() == 2 and bank.shape[1] == N.MAP_STRIDE and bank.is_contiguous()
-        assert bank.device == self.device, "set_bank: the bank lives on %s, the env on %s" % (bank.device, self.device)
+        self._arg(bank, torch.float64, (0, N.MAP_STRIDE), "set_bank: bank", more_rows=True, exc=AssertionError)
         self.bank = bank
         self.n_maps = int(bank.shape[0])
         with torch.cuda.device(self.device):
-            N.check(N.lib().ssg_set_map_bank(self._h, C.c_void_p(bank.data_ptr()), self.n_maps), self._h,
-                    "ssg_set_map_bank")
+            N.check(N.lib().ssg_set_map_bank(self._h, N.ptr(bank), self.n_maps), self._h, "ssg_set_map_bank")
 
     def regenerate_bank(self, seed, width_frac=None, n_maps=None, return_raw=False):
         """Refresh the map bank ON THE DEVICE (no host geometry, no upload): n_maps brand-new rivers and goal paths
@@ -347,8 +395,7 @@ class ShipVecEnv(*_BASES):
             bank = self.bank if n_maps == self.n_maps else torch.empty((n_maps, N.MAP_STRIDE), dtype=torch.float64,
                                                                       device=self.device)
             raw = torch.empty((n_maps, 48 + 3 * self.cfg.n_goals), dtype=torch.float64, device=self.device) if return_raw else None
-            N.check(N.lib().ssg_generate_bank(self._h, int(seed), wf, C.c_void_p(bank.data_ptr()), n_maps,
-                                              C.c_void_p(raw.data_ptr()) if raw is not None else None, self._stream()),
+            N.check(N.lib().ssg_generate_bank(self._h, int(seed), wf, N.ptr(bank), n_maps, N.ptr(raw), self._stream()),
                     self._h, "ssg_generate_bank")
         self.bank_polys = self.bank_goals = None  # host copies no longer describe the bank
         if bank is not self.bank:
@@ -372,14 +419,14 @@ class ShipVecEnv(*_BASES):
             if return_raw:
                 raw = torch.full((self.num_envs * self.ring, 48 + 3 * self.cfg.n_goals), float("nan"), dtype=torch.float64,
                                  device=self.device)
-            N.check(N.lib().ssg_refill_worlds(self._h, seed, self.width_frac, C.c_void_p(raw.data_ptr()) if raw is not None else None,
-                                              self._stream()), self._h, "ssg_refill_worlds")
+            N.check(N.lib().ssg_refill_worlds(self._h, seed, self.width_frac, N.ptr(raw), self._stream()), self._h, "ssg_refill_worlds")
         return raw
 
     def launch_geometry(self):
         """(envs per workgroup, bank staged in LDS?, dynamic LDS bytes per workgroup) of the step kernel for this handle."""
         epw, lds, nb = C.c_int(), C.c_int(), C.c_size_t()
-        N.check(N.lib().ssg_debug_launch_geometry(self._h, C.byref(epw), C.byref(lds), C.byref(nb)), self._h, "geometry")
+        N.check(N.lib().ssg_debug_launch_geometry(self._h, C.byref(epw), C.byref(lds), C.byref(nb)), self._h,
+                "ssg_debug_launch_geometry")
         return epw.value, bool(lds.value), nb.value
 
     def field(self, fid):
@@ -401,25 +448,10 @@ class ShipVecEnv(*_BASES):
         v = self.state[off.value: off.value + nc.value * stride.value].view(dt).view(nc.value, n_pad)[:, :self.num_envs]
         return v[0] if nc.value == 1 else v
 
-    def _mask_ptr(self, mask, what):
-        """A per-env byte mask as a C pointer (None = all envs): uint8 or bool, one element per env, on this env's device."""
-        if mask is None:
-            return None
+    def _mask_arg(self, mask, what):
+        """A per-env byte mask (None = all envs), checked: uint8 or bool, one element per env."""
         torch = _torch()
-        if (mask.dtype not in (torch.uint8, torch.bool) or mask.numel() != self.num_envs or not mask.is_cuda or mask.device != self.device
-                or not mask.is_contiguous()):
-            raise ValueError("%s: mask must be a contiguous uint8 / bool tensor of %d elements on %s (got %s %s on %s)"
-                             % (what, self.num_envs, self.device, mask.dtype, tuple(mask.shape), mask.device))
-        return C.c_void_p(mask.data_ptr())
-
-    def _ids_ptr(self, ids, what):
-        if ids is None:
-            return None
-        torch = _torch()
-        if ids.dtype != torch.int32 or ids.numel() != self.num_envs or ids.device != self.device or not ids.is_contiguous():
-            raise ValueError("%s: map_ids must be a contiguous int32 tensor of %d elements on %s (got %s %s on %s)"
-                             % (what, self.num_envs, self.device, ids.dtype, tuple(ids.shape), ids.device))
-        return C.c_void_p(ids.data_ptr())
+        return None if mask is None else self._arg(mask, (torch.uint8, torch.bool), self.num_envs, what + ": mask")
 
     def wake_dynamics(self, mask=None):
         """Config 4: call after writing ANY state column through field() — the traffic / goal-body columns (envs whose
@@ -428,7 +460,7 @@ class ShipVecEnv(*_BASES):
         cpSpaceStep visits was decided from the state the last step ended with): ssg_dyn_invalidate.  Also after restoring or
         copying the state blob.  mask: uint8 device tensor [num_envs]
         (envs whose rest bit is cleared) or None = all; the next step's queue is rebuilt from the columns either way."""
-        mp = self._mask_ptr(mask, "wake_dynamics")
+        mp = self._mask_arg(mask, "wake_dynamics")
         with _torch().cuda.device(self.device):
             N.check(N.lib().ssg_dyn_invalidate(self._h, mp, self._stream()), self._h, "ssg_dyn_invalidate")
 
@@ -539,21 +571,26 @@ class ShipVecEnv(*_BASES):
         mine, theirs = self.fingerprint(), snap["fingerprint"]
         bad = ["%s is %r in the snapshot and %r in this env" % (k, theirs.get(k, "missing"), mine.get(k, "missing"))
                for k in sorted(set(mine) | set(theirs)) if k not in theirs or k not in mine or theirs[k] != mine[k]]
-        state, out, bank, n_maps = snap.get("state"), snap.get("out"), snap.get("bank"), snap.get("n_maps")
-        for name, t, dt, shape in (("state", state, torch.uint8, (self.state.numel(),)), ("out", out, torch.uint8, (self._out_nbytes,))):
-            if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape:
-                bad.append("%s must be a %s tensor %s" % (name, dt, shape))
-        if (not torch.is_tensor(bank) or bank.dtype != torch.float64 or bank.dim() != 2 or int(bank.shape[1]) != N.MAP_STRIDE
-                or isinstance(n_maps, bool) or not isinstance(n_maps, int) or int(bank.shape[0]) != n_maps or n_maps < 1):
-            bad.append("bank must be a float64 tensor [n_maps, %d] with n_maps >= 1" % N.MAP_STRIDE)
+        staged = {}  # the snapshot's tensors on the device, checked as what the copies below will read
+        for name, dt, shape in (("state", torch.uint8, (self.state.numel(),)), ("out", torch.uint8, (self._out_nbytes,)),
+                                ("bank", torch.float64, (1, N.MAP_STRIDE))):
+            try:
+                if not torch.is_tensor(snap.get(name)):
+                    raise ValueError("%s must be a tensor" % name)
+                staged[name] = snap[name].to(self.device).contiguous()
+                self._arg(staged[name], dt, shape, name, more_rows=name == "bank")
+            except ValueError as ex:
+                bad.append(str(ex))
+        if "bank" in staged and (type(snap.get("n_maps")) is not int or snap["n_maps"] != staged["bank"].shape[0]):
+            bad.append("n_maps must be an int, the number of the bank's rows")
         if bad:
             raise ValueError("ShipVecEnv.restore: " + "; ".join(bad))
         with torch.cuda.device(self.device):
-            if not getattr(self, "_full_reset_done", False):
+            if not self._full_reset_done:
                 self.reset_tensor()  # (the handle's first full reset zeroes the blob: let it happen before the blob is written)
-            self.state.copy_(state)
-            self._out_blob.copy_(out)
-            new_bank = bank.contiguous().to(self.device)
+            self.state.copy_(staged["state"])
+            self._out_blob.copy_(staged["out"])
+            new_bank = staged["bank"]
             same_shape = tuple(self.bank.shape) == tuple(new_bank.shape)
             if not (same_shape and torch.equal(self.bank, new_bank)):
                 self.bank_polys = self.bank_goals = None  # (host copies, if any, no longer describe the bank)
@@ -568,53 +605,61 @@ class ShipVecEnv(*_BASES):
     # tensor API (zero-copy; what a GPU-resident policy should use)
     # ------------------------------------------------------------------------------------------------
     def reset_tensor(self, mask=None, map_ids=None):
-        torch = _torch()
-        mp, ip = self._mask_ptr(mask, "reset_tensor"), self._ids_ptr(map_ids, "reset_tensor")
-        if mask is None:
-            self._full_reset_done = True
-        with torch.cuda.device(self.device):
-            if self.map_mode == "fresh" and map_ids is None:
-                ids = torch.arange(self.num_envs, dtype=torch.int32, device=self.device)
-                ip = C.c_void_p(ids.data_ptr())
-            N.check(N.lib().ssg_reset(self._h, mp, ip, C.c_void_p(self.obs.data_ptr()), self._stream()), self._h,
-                    "ssg_reset")
-            if self.map_mode == "fresh" and map_ids is None:
-                torch.cuda.current_stream(self.device).synchronize()  # keep `ids` alive until the kernel ran
+        self._mask_arg(mask, "reset_tensor")
+        if map_ids is not None:
+            self._arg(map_ids, self._i32, self.num_envs, "reset_tensor: map_ids")
+        self._reset_launch(mask, map_ids, self.obs)
         return self.obs
 
-    def _out_ptrs(self):
-        """The four output buffers as C pointers (they are allocated once; cached: these calls sit on the launch path)."""
-        p = self.__dict__.get("_out_ptr_cache")
-        if p is None or p[0] != (self.obs.data_ptr(), self.reward.data_ptr()):
-            p = ((self.obs.data_ptr(), self.reward.data_ptr()),
-                 C.c_void_p(self.obs.data_ptr()), C.c_void_p(self.reward.data_ptr()), C.c_void_p(self.done.data_ptr()),
-                 C.c_void_p(self.flags.data_ptr()))
-            self._out_ptr_cache = p
-        return p[1:]
+    def _reset_launch(self, mask, map_ids, dest):
+        """ssg_reset of the masked envs (None: all of them, a full reset) onto the maps `map_ids` (None: "fresh": env e's own bank
+        slot, e; else the library's rule), writing their rows of `dest`."""
+        torch = _torch()
+        if mask is None:
+            self._full_reset_done = True
+        own_ids = self.map_mode == "fresh" and map_ids is None
+        with torch.cuda.device(self.device):
+            if own_ids:
+                map_ids = torch.arange(self.num_envs, dtype=torch.int32, device=self.device)
+            N.check(N.lib().ssg_reset(self._h, N.ptr(mask), N.ptr(map_ids), N.ptr(dest), self._stream()), self._h, "ssg_reset")
+            if own_ids:
+                torch.cuda.current_stream(self.device).synchronize()  # keep the ids alive until the kernel ran
+
+    def _host_reset(self, envs, dest):
+        """THE host-driven reset: `envs` — a host bool array [N], one env index, or None for a full reset — are re-initialised by
+        ONE ssg_reset that writes their rows of `dest` (self.obs or a side buffer), and the stream is synchronised.  Where each env
+        goes, per map mode: "fresh" draws it a brand-new world on the host (ascending env index, one world per env) and uploads
+        the bank; "bank" moves it to the next map modulo n_maps, exactly the sequence the in-kernel auto-reset follows (a full
+        reset: to its first map); "fresh_device" passes no ids — the reset kernel moves the env to the next world of its ring."""
+        torch = _torch()
+        mask_h = envs
+        if envs is not None and not isinstance(envs, np.ndarray):
+            mask_h = np.arange(self.num_envs) == envs
+        with torch.cuda.device(self.device):
+            mask = None if mask_h is None else torch.from_numpy(mask_h.astype(np.uint8)).to(self.device)
+            ids = None
+            if self.map_mode == "fresh":
+                for e in (range(self.num_envs) if mask_h is None else np.nonzero(mask_h)[0]):
+                    self._fresh_world(int(e))
+                self.bank.copy_(torch.from_numpy(self.bank_host))
+            elif self.map_mode == "bank" and mask is not None:
+                cur = self.field(N.F_MAP_ID)
+                ids = torch.where(mask != 0, (cur + 1) % self.n_maps, cur).to(torch.int32).contiguous()
+            self._reset_launch(mask, ids, dest)
+            torch.cuda.current_stream(self.device).synchronize()
+
+    def _rows_h(self, src, idx):
+        """Rows `idx` (a host index array) of the device tensor `src`, as a numpy array."""
+        return src[_torch().from_numpy(idx).to(self.device)].cpu().numpy()
 
     def step_tensor(self, actions):
         """actions: int32 device tensor [N].  Returns (obs, reward, done, flags) device tensors (reused buffers).
         This is the policy-in-the-loop path: one launch per call, so the host side is kept to one ctypes call with plain
         integers (the cached output pointers, the actions' address, the current stream's handle)."""
         # (a tensor of another dtype / size would be read as int32 [N] all the same: wrong steps, or a read past its end)
-        if (actions.dtype is not self._i32 or actions.numel() != self.num_envs or actions.device != self.device
-                or not actions.is_contiguous()):
-            raise ValueError("step_tensor: actions must be a contiguous int32 device tensor of %d elements (got %s %s on %s)"
-                             % (self.num_envs, actions.dtype, tuple(actions.shape), actions.device))
-        hot = self.__dict__.get("_hot")
-        if hot is None or hot[0] != (self.obs.data_ptr(), self.reward.data_ptr()):
-            torch = _torch()
-            hot = self._hot = ((self.obs.data_ptr(), self.reward.data_ptr()), N.lib().ssg_step, torch.cuda.current_stream,
-                               self.obs.data_ptr(), self.reward.data_ptr(), self.done.data_ptr(), self.flags.data_ptr())
-        _, fn, cur_stream, o, r, d, f = hot
-        rc = fn(self._h, actions.data_ptr(), o, r, d, f, cur_stream(self.device).cuda_stream)
-        if rc:
-            torch = _torch()
-            if torch.cuda.current_device() != self._dev_index:  # called with another device current: switch and retry
-                with torch.cuda.device(self.device):
-                    rc = fn(self._h, actions.data_ptr(), o, r, d, f, cur_stream(self.device).cuda_stream)
-            if rc:
-                N.check(rc, self._h, "ssg_step")
+        a = self._arg(actions, self._i32, self.num_envs, "step_tensor: actions")
+        o, r, d, f = self._out
+        self._launch("ssg_step", self._lib.ssg_step, a, o, r, d, f, self._cur_stream(self.device).cuda_stream)
         return self.obs, self.reward, self.done, self.flags
 
     def rollout_tensor(self, actions_kn, trajectory=False, out=None):
@@ -625,69 +670,48 @@ class ShipVecEnv(*_BASES):
         rollout loop sees them (train/random.py:14-27) — returns (obs [K, N, D], reward [K, N], done [K, N], flags [K, N])
         device tensors; `out` = a tuple of four such preallocated tensors (first dimension >= K, contiguous) to write
         into instead of allocating.  self.obs / reward / done / flags are left untouched in trajectory mode."""
-        if (actions_kn.dtype is not self._i32 or actions_kn.dim() != 2 or actions_kn.shape[1] != self.num_envs
-                or actions_kn.device != self.device or not actions_kn.is_contiguous()):
-            raise ValueError("rollout_tensor: actions must be a contiguous int32 device tensor [K, %d] (got %s %s on %s)"
-                             % (self.num_envs, actions_kn.dtype, tuple(actions_kn.shape), actions_kn.device))
-        if trajectory and out is not None:
+        n, D = self.num_envs, self.states_history
+        a = self._arg(actions_kn, self._i32, (0, n), "rollout_tensor: actions", more_rows=True)
+        K = actions_kn.shape[0]
+        if not trajectory:
+            self._launch("ssg_rollout", self._lib.ssg_rollout, a, K, *self._out, self._cur_stream(self.device).cuda_stream)
+            return self.obs, self.reward, self.done, self.flags
+        if out is not None:
             # a buffer set seen before: one ctypes call with plain integers, like step_tensor — a 20-step launch is ~140 us, and
             # everything the host does before the launch is GPU idle time inside a caller's timed region.  The cache holds
             # POINTERS and shapes only, never the tensors (a caller's `del bufs` really frees them), and a hit needs all four
             # buffers to sit where they sat when the plan was made, with the shapes checked then.
             po = out[0].data_ptr()
-            plan = self.__dict__.setdefault("_traj_plans", {}).get(po)
+            plan = self._traj_plans.get(po)
             if plan is not None:
-                K = actions_kn.shape[0]
-                fn, cur_stream, pr, pd, pf, cap, sig = plan
+                pr, pd, pf, cap, sig = plan
                 # (a hit needs the four buffers to be what was checked when the plan was made: addresses AND dtype / shape /
                 # strides / device of each — the caching allocator readily hands a freed buffer's address to another tensor)
                 if (K <= cap and out[1].data_ptr() == pr and out[2].data_ptr() == pd and out[3].data_ptr() == pf
                         and tuple((t.dtype, tuple(t.shape), t.stride(), t.device.index) for t in out) == sig):
-                    if fn(self._h, actions_kn.data_ptr(), K, po, pr, pd, pf, self.num_envs, cur_stream(self.device).cuda_stream) == 0:
-                        return out[0][:K], out[1][:K], out[2][:K], out[3][:K]  # (sliced after the launch: the GPU is already busy)
-                    # (an error — e.g. another device is current: the checked path below repeats the call and reports)
+                    self._launch("ssg_rollout_traj", self._lib.ssg_rollout_traj, a, K, po, pr, pd, pf, n,
+                                 self._cur_stream(self.device).cuda_stream)
+                    return out[0][:K], out[1][:K], out[2][:K], out[3][:K]  # (sliced after the launch: the GPU is already busy)
         torch = _torch()
-        K = int(actions_kn.shape[0])
-        if not trajectory:
-            o, r, d, f = self._out_ptrs()
-            if torch.cuda.current_device() == self._dev_index:
-                rc = N.lib().ssg_rollout(self._h, C.c_void_p(actions_kn.data_ptr()), K, o, r, d, f, self._stream())
-            else:
-                with torch.cuda.device(self.device):
-                    rc = N.lib().ssg_rollout(self._h, C.c_void_p(actions_kn.data_ptr()), K, o, r, d, f, self._stream())
-            if rc:
-                N.check(rc, self._h, "ssg_rollout")
-            return self.obs, self.reward, self.done, self.flags
-        n, D = self.num_envs, self.states_history
-        with torch.cuda.device(self.device):
-            caller_out = out is not None
-            if out is None:
-                out = (torch.empty((K, n, D), dtype=torch.float64, device=self.device),
-                       torch.empty((K, n), dtype=torch.float64, device=self.device),
-                       torch.empty((K, n), dtype=torch.uint8, device=self.device),
-                       torch.empty((K, n), dtype=torch.uint8, device=self.device))
-            to, tr, td, tf = out
-            assert to.dtype == torch.float64 and tr.dtype == torch.float64 and td.dtype == torch.uint8 and tf.dtype == torch.uint8
-            assert tuple(to.shape[1:]) == (n, D) and all(tuple(t.shape[1:]) == (n,) for t in (tr, td, tf))
-            assert all(t.is_contiguous() and t.shape[0] >= K and t.device == self.device for t in out)
-            rc = N.lib().ssg_rollout_traj(self._h, C.c_void_p(actions_kn.data_ptr()), K, C.c_void_p(to.data_ptr()),
-                                          C.c_void_p(tr.data_ptr()), C.c_void_p(td.data_ptr()), C.c_void_p(tf.data_ptr()),
-                                          n, self._stream())
-        if rc:
-            N.check(rc, self._h, "ssg_rollout_traj")
+        specs = ((torch.float64, (K, n, D)), (torch.float64, (K, n)), (torch.uint8, (K, n)), (torch.uint8, (K, n)))
+        caller_out = out is not None
+        if out is None:
+            out = tuple(torch.empty(shape, dtype=dt, device=self.device) for dt, shape in specs)
+        to, tr, td, tf = out
+        ptrs = [self._arg(t, dt, shape, "rollout_tensor: out[%d]" % j, more_rows=True, exc=AssertionError)
+                for j, (t, (dt, shape)) in enumerate(zip(out, specs))]
+        self._launch("ssg_rollout_traj", self._lib.ssg_rollout_traj, a, K, *ptrs, n, self._cur_stream(self.device).cuda_stream)
         if caller_out:
-            plans = self.__dict__.setdefault("_traj_plans", {})
-            if len(plans) >= 8 and to.data_ptr() not in plans:  # (a handful of rotating buffer sets at most)
-                plans.pop(next(iter(plans)))
-            plans[to.data_ptr()] = (N.lib().ssg_rollout_traj, torch.cuda.current_stream, tr.data_ptr(), td.data_ptr(), tf.data_ptr(),
-                                    min(int(t.shape[0]) for t in out),
-                                    tuple((t.dtype, tuple(t.shape), t.stride(), t.device.index) for t in out))
+            if len(self._traj_plans) >= 8 and ptrs[0] not in self._traj_plans:  # (a handful of rotating buffer sets at most)
+                self._traj_plans.pop(next(iter(self._traj_plans)))
+            self._traj_plans[ptrs[0]] = (*ptrs[1:], min(int(t.shape[0]) for t in out),
+                                         tuple((t.dtype, tuple(t.shape), t.stride(), t.device.index) for t in out))
         return to[:K], tr[:K], td[:K], tf[:K]
 
     def clear_traj_cache(self):
         """Forget the cached launch plans of rollout_tensor(trajectory=True, out=...).  They hold no tensors (pointers and
         shapes only), so this is never needed to free memory; it exists for callers that recycle addresses deliberately."""
-        self.__dict__.pop("_traj_plans", None)
+        self._traj_plans.clear()
 
     # ------------------------------------------------------------------------------------------------
     # the policy in the loop on the device (ABI 9: ssg_policy_act / ssg_rollout_policy; ship_sim_gym_amd/policy.py)
@@ -705,12 +729,8 @@ class ShipVecEnv(*_BASES):
             raise ValueError("%s: the policy lives on %s, the env on %s" % (what, policy.params.device, self.device))
 
     def _f32_rows(self, t, shape, what):
-        torch = _torch()
-        if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous() or t.dim() != len(shape) or t.shape[0] < shape[0] \
-                or tuple(t.shape[1:]) != tuple(shape[1:]):
-            raise ValueError("%s: expected a contiguous float32 tensor %s on %s (got %s %s on %s)"
-                             % (what, tuple(shape), self.device, t.dtype, tuple(t.shape), t.device))
-        return C.c_void_p(t.data_ptr())
+        """A float32 tensor of at least shape[0] rows, checked (None stays None): its address."""
+        return None if t is None else self._arg(t, _torch().float32, shape, what, more_rows=True)
 
     def policy_act(self, policy, seed=0, step=0, uniforms=None, x_out=None, greedy=False):
         """The policy forward + inverse-CDF sampling on the env's current `obs` (ssg_policy_act): returns (act int32 [N], logp [N],
@@ -727,20 +747,20 @@ class ShipVecEnv(*_BASES):
         if greedy and uniforms is not None:
             raise ValueError("%s: greedy=True reads no uniforms (pass one or the other)" % what)
         n, D = self.num_envs, self.states_history
-        up = self._f32_rows(uniforms, (n,), what + " uniforms") if uniforms is not None else None
+        up = self._f32_rows(uniforms, (n,), what + ": uniforms")
         with torch.cuda.device(self.device):
             act = torch.empty(n, dtype=torch.int32, device=self.device)
             logp = torch.empty(n, dtype=torch.float32, device=self.device)
             val = torch.empty(n, dtype=torch.float32, device=self.device)
             x = x_out if x_out is not None else torch.empty((n, D), dtype=torch.float32, device=self.device)
-            xp = self._f32_rows(x, (n, D), what + " x_out")
+            xp = self._f32_rows(x, (n, D), what + ": x_out")
             rec = record.to_native()
             if greedy:
                 c_name, draw = c_name + "_greedy", ()
             else:
                 draw = (up, int(seed), int(step))
-            N.check(getattr(N.lib(), c_name)(self._h, C.byref(rec), C.c_void_p(self.obs.data_ptr()), *draw, C.c_void_p(act.data_ptr()),
-                                             C.c_void_p(logp.data_ptr()), C.c_void_p(val.data_ptr()), xp, self._stream()), self._h, c_name)
+            N.check(getattr(N.lib(), c_name)(self._h, C.byref(rec), N.ptr(self.obs), *draw, N.ptr(act), N.ptr(logp), N.ptr(val), xp,
+                                             self._stream()), self._h, c_name)
         return act, logp, val, x
 
     def rollout_policy(self, policy, K, seed=0, step0=0, uniforms=None, out=None):
@@ -759,12 +779,12 @@ class ShipVecEnv(*_BASES):
         K, n = int(K), self.num_envs
         if K < 1:
             raise ValueError("%s: K must be >= 1" % what)
-        up = self._f32_rows(uniforms, (K, n), what + " uniforms") if uniforms is not None else None
+        up = self._f32_rows(uniforms, (K, n), what + ": uniforms")
         with torch.cuda.device(self.device):
             boot = self._timeout_rows(K, out, what)
             out, p = self._rollout_buffers(K, out, what)
             rec = record.to_native()
-            N.check(getattr(N.lib(), c_name)(self._h, C.byref(rec), K, up, int(seed), int(step0), C.c_void_p(self.obs.data_ptr()),
+            N.check(getattr(N.lib(), c_name)(self._h, C.byref(rec), K, up, int(seed), int(step0), N.ptr(self.obs),
                                              p["act"], p["logp"], p["val"], p["obs"], p["rew"], p["done"], p["flags"], p["last_val"],
                                              n, self._stream()), self._h, c_name)
         res = {k: (v[:K] if k != "last_val" else v) for k, v in out.items() if k != "boot"}
@@ -781,13 +801,7 @@ class ShipVecEnv(*_BASES):
                  "flags": ((K, n), torch.uint8), "last_val": ((n,), torch.float32)}
         if out is None:
             out = {k: torch.empty(s, dtype=dt, device=self.device) for k, (s, dt) in specs.items()}
-        for k, (s, dt) in specs.items():
-            t = out[k]
-            if (t.dtype != dt or t.device != self.device or not t.is_contiguous() or t.dim() != len(s) or t.shape[0] < s[0]
-                    or tuple(t.shape[1:]) != tuple(s[1:])):
-                raise ValueError("%s: out[%r] must be a contiguous %s tensor %s on %s (got %s %s on %s)"
-                                 % (what, k, dt, s, self.device, t.dtype, tuple(t.shape), t.device))
-        return out, {k: C.c_void_p(out[k].data_ptr()) for k in specs}
+        return out, {k: self._arg(out[k], dt, s, "%s: out[%r]" % (what, k), more_rows=True) for k, (s, dt) in specs.items()}
 
     # ------------------------------------------------------------------------------------------------
     # a population of policies on this handle (ssg_pop_act / ssg_pop_rollout; ship_sim_gym_amd/population.py)
@@ -821,7 +835,7 @@ class ShipVecEnv(*_BASES):
         if sum(sizes) != self.num_envs:
             raise ValueError("set_population_slices: the sizes sum to %d, the handle has %d envs" % (sum(sizes), self.num_envs))
         table = torch.tensor(list(buf), dtype=torch.int32).to(self.device)
-        N.check(N.lib().ssg_pop_set_slices(self._h, P, arr, C.c_void_p(table.data_ptr())), self._h, "ssg_pop_set_slices")
+        N.check(N.lib().ssg_pop_set_slices(self._h, P, arr, N.ptr(table)), self._h, "ssg_pop_set_slices")
         # (the device table is the caller's memory; an earlier one stays alive until launches that read it have been enqueued AND run:
         # torch's allocator does not hand a freed block to another stream's work before that)
         self._pop_slices = (sizes, table)
@@ -829,7 +843,7 @@ class ShipVecEnv(*_BASES):
     @property
     def population_slices(self):
         """The bound slice sizes (a list of P ints, as the library holds them: ssg_pop_get_slices), or None."""
-        if getattr(self, "_pop_slices", None) is None:
+        if self._pop_slices is None:
             return None
         P = C.c_int()
         N.check(N.lib().ssg_pop_get_slices(self._h, C.byref(P), None), self._h, "ssg_pop_get_slices")
@@ -880,7 +894,7 @@ class ShipVecEnv(*_BASES):
         """Bind a record of `rows` rows: the kept terminal-observation rows if they serve that many (else new ones), and `boot` (None:
         the kept or a new f32 [rows, N])."""
         torch = _torch()
-        old = getattr(self, "_timeout_boot", None)
+        old = self._timeout_boot
         with torch.cuda.device(self.device):
             if old is not None and old["term_obs"].shape[0] >= rows:
                 term = old["term_obs"]
@@ -906,21 +920,16 @@ class ShipVecEnv(*_BASES):
         what = "timeout_values"
         (self._check_population if pop else self._check_policy)(record, what)
         n, D = self.num_envs, self.states_history
-        if (flags.dtype != torch.uint8 or flags.device != self.device or not flags.is_contiguous() or flags.dim() != 2
-                or int(flags.shape[1]) != n or int(flags.shape[0]) < 1):
-            raise ValueError("%s: flags must be a contiguous uint8 tensor [K, %d] on %s" % (what, n, self.device))
+        fp = self._arg(flags, torch.uint8, (1, n), what + ": flags", more_rows=True)
         K = int(flags.shape[0])
-        if (term_obs.dtype != torch.float64 or term_obs.device != self.device or not term_obs.is_contiguous()
-                or tuple(term_obs.shape) != (K, n, D)):
-            raise ValueError("%s: term_obs must be a contiguous float64 tensor %s on %s" % (what, (K, n, D), self.device))
+        tp = self._arg(term_obs, torch.float64, (K, n, D), what + ": term_obs")
         with torch.cuda.device(self.device):
             if out is None:
                 out = torch.empty((K, n), dtype=torch.float32, device=self.device)
-            op = self._f32_rows(out, (K, n), what + " out")
+            op = self._f32_rows(out, (K, n), what + ": out")
             rec = record.to_native()
             name = "ssg_pop_timeout_values" if pop else "ssg_timeout_values"
-            N.check(getattr(N.lib(), name)(self._h, C.byref(rec), K, C.c_void_p(flags.data_ptr()), C.c_void_p(term_obs.data_ptr()), op, n,
-                                           self._stream()), self._h, name)
+            N.check(getattr(N.lib(), name)(self._h, C.byref(rec), K, fp, tp, op, n, self._stream()), self._h, name)
         return out[:K]
 
     def _timeout_rows(self, K, out, what):
@@ -928,12 +937,12 @@ class ShipVecEnv(*_BASES):
         values into — out["boot"] when the caller's out-dict has one, else a new one per rollout (a batch kept across rollouts keeps
         its values) — bound together with terminal-observation rows that serve K."""
         torch = _torch()
-        if getattr(self, "_timeout_boot", None) is None:
+        if self._timeout_boot is None:
             return None
         boot = out.get("boot") if out is not None else None
         if boot is None:
             boot = torch.empty((K, self.num_envs), dtype=torch.float32, device=self.device)
-        self._f32_rows(boot, (K, self.num_envs), what + " out['boot']")
+        self._f32_rows(boot, (K, self.num_envs), what + ": out['boot']")
         self._bind_timeout_boot(K, boot)
         return boot
 
@@ -946,7 +955,7 @@ class ShipVecEnv(*_BASES):
         of obs / obs_scale, a single policy with a filter of 1 member, a population of P members with one of P; the rollout loops
         merge each step's observations first when the filter is updating.  The library keeps a copy of the record, this env a
         reference to the filter (whose tensors the launches read).  None unbinds; a refused binding leaves the old one in place."""
-        old = getattr(self, "_obs_filter", None)
+        old = self._obs_filter
         if f is None:
             N.check(N.lib().ssg_set_obs_filter(self._h, None), self._h, "ssg_set_obs_filter")
         else:
@@ -963,7 +972,7 @@ class ShipVecEnv(*_BASES):
     @property
     def obs_filter(self):
         """The bound ObsFilter, or None."""
-        return getattr(self, "_obs_filter", None)
+        return self._obs_filter
 
     # ------------------------------------------------------------------------------------------------
     # per-minibatch advantage normalisation (ssg_ppo_set_adv_norm; NativePPO / PopulationPPO bind their own before every call)
@@ -972,8 +981,8 @@ class ShipVecEnv(*_BASES):
         """Bind the advantage-normalisation mode of the device PPO update: N.ADV_NORM_BATCH (the default: once per rollout, nothing
         bound) or N.ADV_NORM_MINIBATCH (PPO2's rule) with `scratch`, a uint8 device tensor of ssg_ppo_adv_norm_nbytes(n_members) bytes
         that the caller keeps alive.  Host only; a refused binding leaves the old one in place."""
-        ptr, nb = (C.c_void_p(scratch.data_ptr()), scratch.numel() * scratch.element_size()) if scratch is not None else (None, 0)
-        N.check(N.lib().ssg_ppo_set_adv_norm(self._h, int(mode), int(n_members), ptr, nb), self._h, "ssg_ppo_set_adv_norm")
+        nb = scratch.numel() * scratch.element_size() if scratch is not None else 0
+        N.check(N.lib().ssg_ppo_set_adv_norm(self._h, int(mode), int(n_members), N.ptr(scratch), nb), self._h, "ssg_ppo_set_adv_norm")
         self._adv_norm_scratch = scratch if int(mode) == N.ADV_NORM_MINIBATCH else None
 
     def adv_norm(self):
@@ -987,19 +996,15 @@ class ShipVecEnv(*_BASES):
         torch = _torch()
         with torch.cuda.device(self.device):
             out = torch.empty((K, self.num_envs), dtype=torch.int32, device=self.device)
-            N.check(N.lib().ssg_fill_actions(self._h, int(seed), int(step0), int(K), C.c_void_p(out.data_ptr()),
-                                             self._stream()), self._h, "ssg_fill_actions")
+            N.check(N.lib().ssg_fill_actions(self._h, int(seed), int(step0), int(K), N.ptr(out), self._stream()), self._h, "ssg_fill_actions")
         return out
 
     # ------------------------------------------------------------------------------------------------
     # stable-baselines VecEnv protocol (numpy in / numpy out)
     # ------------------------------------------------------------------------------------------------
     def reset(self):
-        if self.map_mode == "fresh":
-            for e in range(self.num_envs):
-                self._fresh_world(e)
-            self.bank.copy_(_torch().from_numpy(self.bank_host))
-        return self.reset_tensor().cpu().numpy()
+        self._host_reset(None, self.obs)
+        return self.obs.cpu().numpy()
 
     def step_async(self, actions):
         """VecEnv.step_async: checks the actions, then LAUNCHES the step — actions host -> device from a pinned buffer, ssg_step,
@@ -1015,20 +1020,12 @@ class ShipVecEnv(*_BASES):
         hs = self._host_side()
         np.copyto(hs["acts_np"], self._pending)
         slot = hs["slot"]
-        torch = _torch()
         io = hs["stream"]
-        io.wait_stream(torch.cuda.current_stream(self.device))  # after whatever the tensor API queued (a reset, say)
+        io.wait_stream(self._cur_stream(self.device))  # after whatever the tensor API queued (a reset, say)
         # ONE foreign call: actions host -> device, ssg_step, the packed block device -> host, the slot's completion event
-        rc = hs["step_host"](self._h, hs["acts_ptr"], self._actions.data_ptr(), self.obs.data_ptr(), self.reward.data_ptr(),
-                             self.done.data_ptr(), self.flags.data_ptr(), self._out_blob.data_ptr(), hs["block_ptrs"][slot],
-                             self._out_nbytes, slot, io.cuda_stream)
-        if rc:
-            with torch.cuda.device(self.device):  # (called with another device current: switch and repeat, then report)
-                rc = hs["step_host"](self._h, hs["acts_ptr"], self._actions.data_ptr(), self.obs.data_ptr(), self.reward.data_ptr(),
-                                     self.done.data_ptr(), self.flags.data_ptr(), self._out_blob.data_ptr(), hs["block_ptrs"][slot],
-                                     self._out_nbytes, slot, io.cuda_stream)
-            if rc:
-                N.check(rc, self._h, "ssg_step_host")
+        o, r, d, f = self._out
+        self._launch("ssg_step_host", hs["step_host"], hs["acts_ptr"], self._actions.data_ptr(), o, r, d, f, self._out_blob.data_ptr(),
+                     hs["block_ptrs"][slot], self._out_nbytes, slot, io.cuda_stream)
         hs["inflight"] = slot
         hs["slot"] = (slot + 1) % self.host_slots
 
@@ -1038,7 +1035,6 @@ class ShipVecEnv(*_BASES):
         array is a view of one of `host_slots` rotating blocks: it stays valid until `host_slots - 1` further steps have been
         taken (stable-baselines' runners copy it into their own buffer at once: `self.obs[:] = obs`); rewards and dones are
         fresh small arrays (runners keep them in lists).  `copy_host_outputs=True` returns a fresh observation array too."""
-        torch = _torch()
         hs = self._host_side()
         slot = hs["inflight"]
         if slot is None:
@@ -1050,14 +1046,8 @@ class ShipVecEnv(*_BASES):
         done_h = done_u8.view(np.bool_).copy()
         if self.map_mode == "fresh" and self.auto_reset and done_h.any():
             # host-side auto-reset with brand-new worlds (reference-exact resets)
-            for e in np.nonzero(done_h)[0]:
-                self._fresh_world(int(e))
-            self.bank.copy_(torch.from_numpy(self.bank_host))
-            mask = torch.from_numpy(done_h.astype(np.uint8)).to(self.device)
-            ids = torch.arange(self.num_envs, dtype=torch.int32, device=self.device)
-            self.reset_tensor(mask=mask, map_ids=ids)
-            obs_h[done_h] = self.obs[mask.bool()].cpu().numpy()  # (the reset observations replace the terminal ones)
-            torch.cuda.current_stream(self.device).synchronize()
+            self._host_reset(done_h, self.obs)
+            obs_h[done_h] = self._rows_h(self.obs, np.nonzero(done_h)[0])  # (the reset observations replace the terminal ones)
         return (obs_h.copy() if self.copy_host_outputs else obs_h), rew_h.copy(), done_h, hs["infos"]
 
     def step(self, actions):
@@ -1065,12 +1055,13 @@ class ShipVecEnv(*_BASES):
         return self.step_wait()
 
     def close(self):
-        self.__dict__.pop("_traj_plans", None)
-        self.__dict__.pop("_timeout_boot", None)
-        flt = self.__dict__.pop("_obs_filter", None)
+        self._traj_plans.clear()
+        self._timeout_boot = None
+        flt, self._obs_filter = self._obs_filter, None
         if flt is not None and self in flt._bound:
             flt._bound.remove(self)
-        hs = self.__dict__.get("_host")
+        self._out = (0, 0, 0, 0)  # (no address outlives the handle: a call after close() is refused for its NULL handle)
+        hs = self._host
         if hs is not None:
             try:
                 hs["stream"].synchronize()  # a step_async still in flight reads and writes the buffers about to go
@@ -1095,7 +1086,7 @@ class ShipVecEnv(*_BASES):
         height = int(height or self.bounds[1])
         with torch.cuda.device(self.device):
             img = torch.empty((width, height, 3), dtype=torch.uint8, device=self.device)
-            N.check(N.lib().ssg_render(self._h, int(env), width, height, C.c_void_p(img.data_ptr()), 1 if debug else 0,
+            N.check(N.lib().ssg_render(self._h, int(env), width, height, N.ptr(img), 1 if debug else 0,
                                        self._stream()), self._h, "ssg_render")
         return img
 
@@ -1112,7 +1103,7 @@ class ShipVecEnv(*_BASES):
             else:
                 ids = torch.tensor([int(e) for e in envs], dtype=torch.int32, device=self.device)
             out = torch.empty((ids.numel(), width, height, 3), dtype=torch.uint8, device=self.device)
-            N.check(N.lib().ssg_render_envs(self._h, C.c_void_p(ids.data_ptr()), ids.numel(), width, height, C.c_void_p(out.data_ptr()),
+            N.check(N.lib().ssg_render_envs(self._h, N.ptr(ids), ids.numel(), width, height, N.ptr(out),
                                             1 if debug else 0, self._stream()), self._h, "ssg_render_envs")
         return out
 
@@ -1190,52 +1181,27 @@ class ShipVecEnv(*_BASES):
         """VectorEnv.reset_at: the ONE reset of env `index` (game.py:260-277).  In the rllib flow vector_step has
         already re-initialised every env it reported done, in one masked launch, and cached the reset observations;
         this call hands that observation out instead of resetting (and advancing the map) a second time."""
-        torch = _torch()
         index = int(index)
         if self._await_reset[index]:
             self._await_reset[index] = False
             return self._reset_obs_h[index].copy()
-        mask = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device)
-        mask[index] = 1
-        if self.map_mode == "fresh":
-            self._fresh_world(int(index))
-            self.bank.copy_(torch.from_numpy(self.bank_host))
-            ids = torch.arange(self.num_envs, dtype=torch.int32, device=self.device)
-            self.reset_tensor(mask=mask, map_ids=ids)
-        elif self.map_mode == "fresh_device":
-            self.reset_tensor(mask=mask)  # the reset kernel moves the env to the next world of its ring
-        else:
-            ids = self.field(N.F_MAP_ID).clone()
-            ids[index] = (ids[index] + 1) % self.n_maps
-            self.reset_tensor(mask=mask, map_ids=ids.contiguous())
-        torch.cuda.current_stream(self.device).synchronize()
+        self._host_reset(index, self.obs)
         return self.obs[index].cpu().numpy()
 
-    def _reset_done_envs(self, done_h):
-        """rllib flow: re-initialise all done envs with ONE masked reset launch (next map of the bank, exactly the
-        sequence the in-kernel auto-reset follows) into a side buffer, leaving self.obs = the terminal observations."""
-        torch = _torch()
-        mask = torch.from_numpy(done_h.astype(np.uint8)).to(self.device)
-        if self.map_mode == "fresh":
-            for e in np.nonzero(done_h)[0]:
-                self._fresh_world(int(e))
-            self.bank.copy_(torch.from_numpy(self.bank_host))
-            ids = torch.arange(self.num_envs, dtype=torch.int32, device=self.device)
-        elif self.map_mode == "fresh_device":
-            ids = None  # the reset kernel moves each env to the next world of its ring
-        else:
-            ids = self.field(N.F_MAP_ID).clone()
-            ids = torch.where(mask != 0, (ids + 1) % self.n_maps, ids).to(torch.int32).contiguous()
-        side = torch.empty_like(self.obs)
-        with torch.cuda.device(self.device):
-            N.check(N.lib().ssg_reset(self._h, C.c_void_p(mask.data_ptr()), C.c_void_p(ids.data_ptr()) if ids is not None else None,
-                                      C.c_void_p(side.data_ptr()), self._stream()), self._h, "ssg_reset")
-        torch.cuda.current_stream(self.device).synchronize()
+    def _keep_reset_obs(self, idx, rows):
+        """rllib flow: `rows`, the reset observations of the done envs `idx`, wait for those envs' reset_at."""
         if self._reset_obs_h is None:
             self._reset_obs_h = np.empty((self.num_envs, self.states_history), dtype=np.float64)
+        self._reset_obs_h[idx] = rows
+        self._await_reset[idx] = True
+
+    def _reset_done_envs(self, done_h):
+        """rllib flow without in-kernel reset: re-initialise all done envs with ONE masked reset launch into a side buffer,
+        leaving self.obs = the terminal observations."""
+        side = _torch().empty_like(self.obs)
+        self._host_reset(done_h, side)
         idx = np.nonzero(done_h)[0]
-        self._reset_obs_h[idx] = side[torch.from_numpy(idx).to(self.device)].cpu().numpy()
-        self._await_reset |= done_h
+        self._keep_reset_obs(idx, self._rows_h(side, idx))
 
     def vector_step(self, actions):
         """VectorEnv.vector_step.  Returns (obs, rewards, dones, infos) as SEQUENCES of per-env items: numpy arrays [N, D] /
@@ -1254,13 +1220,9 @@ class ShipVecEnv(*_BASES):
             if self._rllib_fused:
                 # the step kernel has already reset the done envs: their rows of `obs` are the reset observations (kept for
                 # reset_at), their terminal observations are in term_obs — no reset launch
-                torch = _torch()
                 idx = np.nonzero(done)[0]
-                if self._reset_obs_h is None:
-                    self._reset_obs_h = np.empty((self.num_envs, self.states_history), dtype=np.float64)
-                self._reset_obs_h[idx] = obs[idx]
-                obs[idx] = self.term_obs[torch.from_numpy(idx).to(self.device)].cpu().numpy()
-                self._await_reset |= done
+                self._keep_reset_obs(idx, obs[idx])
+                obs[idx] = self._rows_h(self.term_obs, idx)
             else:  # no in-kernel reset underneath: obs rows of done envs are terminal; ONE masked reset for all of them
                 self._reset_done_envs(done)
         return obs, rew, done, infos

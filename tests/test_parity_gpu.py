@@ -275,10 +275,13 @@ def test_trajectory_buffer_set_reused(torch_cuda, native):
     keep = out[1].clone()
     b.rollout_tensor(acts[:3], trajectory=True, out=out2)
     assert torch.equal(out[1], keep) and not bool((out2[1][:3] == 5.0).any())
+    assert b._traj_plans
     b.clear_traj_cache()
-    assert "_traj_plans" not in b.__dict__
+    assert not b._traj_plans
+    b.rollout_tensor(acts[:3], trajectory=True, out=out)
+    assert b._traj_plans
     b.close()
-    assert "_traj_plans" not in b.__dict__
+    assert not b._traj_plans
 
 
 def test_shard_equivalence(torch_cuda, native):
