@@ -1191,6 +1191,60 @@ int ssg_set_obs_filter(ssg_handle *h, const ssg_obs_filter *f /* NULL unbinds */
 int ssg_get_obs_filter(const ssg_handle *h, ssg_obs_filter *out /* struct_size 0: nothing bound */);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Job-wide observation filter (ABI 9 addition): the filter above for W ranks that train one policy (ssg_ppo_apply_shards)
+ * RLlib's trainers normalise on every worker with the worker's own running filter while it samples, and after each training iteration
+ * the driver merges the workers' new statistics and sends the merged filter back (FilterManager.synchronize behind the "PPO" default
+ * of train/rllib/ppo.py:28 and train/rllib/pbt.py:50).  Restated on this library's terms; ssg_obs_filter and ssg_obs_filter_update do
+ * not change, and with nothing below bound every launch is what it was.
+ *
+ * A rank keeps three blocks of the state's layout, f64 [n_members][SSG_FILTER_ROWS][obs_dim]:
+ *   state   what the policy launches apply and the rollout loops update, exactly as above (the record's dev_state);
+ *   buffer  the statistics of this rank's own rows since the last synchronisation: merged from the same per-step batch totals, starting
+ *           from all zeros.  It is a state block: mean, M2, denom and count, bit for bit what an empty filter holds after those batches;
+ *   base    the state every rank held right after the last synchronisation, identical on all ranks.
+ * During a rollout a rank applies its state = base plus its own progress, as an RLlib worker does: the x rows a rollout stores are
+ * normalised with rank-local statistics.  After the rollout, before GAE, the ranks all-gather their buffers in rank order —
+ * rows f64 [W][n_members][SSG_FILTER_ROWS][obs_dim] — and every rank computes, per member and column,
+ *     state = (...((base (+) rows[0]) (+) rows[1]) ...) (+) rows[W - 1]
+ * with (+) the merge formula above in its stated association, an empty side (count 0) leaving the other as it is, and denom by the
+ * rule above (sqrt(M2 / (n - 1)) + eps for n >= 2, else 1.0); then base = state and buffer = 0 (the caller's copies).  Every rank runs
+ * the same arithmetic on the same gathered rows, so the states are bit-identical on all ranks without a broadcast, as
+ * ssg_ppo_apply_shards keeps the parameters.
+ *
+ * No parity with the plain filter is claimed: with one rank, base (+) buffer is not bit for bit the running state of a filter that
+ * merged the same batches one by one, because the association differs ((base (+) (b_1 (+) b_2 ...)) against ((base (+) b_1) (+) b_2 ...)).
+ * Out of scope: the return filter across ranks, statistics merged per step.
+ * ------------------------------------------------------------------------------------------------- */
+
+/* Replaces nothing (memory binding; the reference's counterpart is the per-worker filter buffer RLlib keeps beside the
+ * "observation_filter" of train/rllib/ppo.py:28).  Binds dev_buffer, f64 [n_members][SSG_FILTER_ROWS][obs_dim] of the BOUND record,
+ * caller-owned, to the handle; NULL unbinds.  While it is bound and the record has SSG_FILTER_UPDATE, the per-step update inside
+ * ssg_rollout_policy and ssg_pop_rollout merges each batch total into dev_state and into dev_buffer (the dual finalise kernel: still
+ * two launches per step); with nothing bound the launches are what they were.  Every ssg_set_obs_filter call that succeeds, bind or
+ * unbind, drops this binding.  SSG_ERR_BAD_ARG, the binding left as it was: a NULL handle; no filter bound; a dev_buffer that is not
+ * 8-byte aligned or overlaps the bound record's dev_state. */
+int ssg_set_obs_filter_buffer(ssg_handle *h, double *dev_buffer /* NULL unbinds */);
+
+/* Replaces nothing (introspection).  *out = the bound buffer, NULL: none. */
+int ssg_get_obs_filter_buffer(const ssg_handle *h, double **out);
+
+/* Replaces: a worker's filter update on a batch of observations, which RLlib applies to the filter and to its buffer alike —
+ * MeanStdFilter.__call__(x, update=True) behind the "PPO" default of train/rllib/ppo.py:28.  ssg_obs_filter_update through the dual
+ * finalise kernel, by the launcher the rollout loops use: the batch total, formed exactly as there, is merged into f->dev_state and
+ * into dev_buffer, each with its own count.  For callers that feed explicit rows; neither f nor dev_buffer need be bound.  Refuses
+ * (SSG_ERR_BAD_ARG, nothing launched) what ssg_obs_filter_update refuses, and a dev_buffer that is NULL, not 8-byte aligned or
+ * overlaps f->dev_state. */
+int ssg_obs_filter_update_buffered(ssg_handle *h, const ssg_obs_filter *f, double *dev_buffer, const double *dev_obs, void *stream);
+
+/* Replaces: the driver's merge of the workers' filter buffers and its copy back to them — FilterManager.synchronize after every
+ * training iteration of train/rllib/ppo.py:28 / train/rllib/pbt.py:50 — as one launch on `stream` (one workgroup per member, a thread
+ * per column): f->dev_state = dev_base merged with dev_rows[0 .. n_rows - 1] in index order (section comment above); dev_base is f64
+ * [n_members][SSG_FILTER_ROWS][obs_dim], dev_rows [n_rows] such blocks.  f->flags and the workspace's contents are not read.  Refuses
+ * (SSG_ERR_BAD_ARG, nothing launched) what ssg_set_obs_filter refuses; a NULL or not 8-byte aligned dev_base or dev_rows; n_rows
+ * outside 1..SSG_DP_MAX_SHARDS; a dev_base or dev_rows that overlaps f->dev_state. */
+int ssg_obs_filter_merge_rows(ssg_handle *h, const ssg_obs_filter *f, const double *dev_base, const double *dev_rows, int n_rows, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Return filter (ABI 9 addition): the rewards of a rollout divided by a running standard deviation of the discounted return
  * The other half of the wrapper above: Stable-Baselines users of train/stable_baselines/ppo.py:123 get VecNormalize(norm_reward=True)
  * by default, which keeps a discounted return per env, updates a running variance with every step's returns and divides the step's

@@ -73,6 +73,7 @@ EXPORTS = (
     "ssg_policy_act_greedy", "ssg_pop_act_greedy", "ssg_evaluate", "ssg_pop_evaluate", "ssg_eval_reduce", "ssg_eval_account",
     "ssg_pop_pack_slices", "ssg_pop_set_slices", "ssg_pop_get_slices", "ssg_pop_pack_schedule_samples",
     "ssg_obs_filter_workspace_nbytes", "ssg_obs_filter_update", "ssg_set_obs_filter", "ssg_get_obs_filter",
+    "ssg_set_obs_filter_buffer", "ssg_get_obs_filter_buffer", "ssg_obs_filter_update_buffered", "ssg_obs_filter_merge_rows",
     "ssg_ret_filter_workspace_nbytes", "ssg_ret_filter_apply",
     "ssg_ppo_adv_norm_nbytes", "ssg_ppo_set_adv_norm", "ssg_ppo_get_adv_norm",
     "ssg_host_perm", "ssg_ppo_perm", "ssg_pop_perm",
@@ -331,6 +332,10 @@ def lib():
     L.ssg_obs_filter_update.argtypes = [vp, C.POINTER(ObsFilterRecord), vp, vp]
     L.ssg_set_obs_filter.argtypes = [vp, C.POINTER(ObsFilterRecord)]
     L.ssg_get_obs_filter.argtypes = [vp, C.POINTER(ObsFilterRecord)]
+    L.ssg_set_obs_filter_buffer.argtypes = [vp, vp]
+    L.ssg_get_obs_filter_buffer.argtypes = [vp, C.POINTER(vp)]
+    L.ssg_obs_filter_update_buffered.argtypes = [vp, C.POINTER(ObsFilterRecord), vp, vp, vp]
+    L.ssg_obs_filter_merge_rows.argtypes = [vp, C.POINTER(ObsFilterRecord), vp, vp, C.c_int, vp]
     L.ssg_ret_filter_workspace_nbytes.argtypes = [C.c_int, C.c_int, C.c_int, szp]
     L.ssg_ret_filter_apply.argtypes = [vp, C.POINTER(RetFilterRecord), C.c_int, vp, vp, C.c_int64, vp, vp, vp]
     L.ssg_ppo_adv_norm_nbytes.argtypes = [C.c_int, szp]

@@ -206,6 +206,7 @@ struct ssg_handle {
     const int32_t *dev_slices = nullptr;
     int slice_max = 0, slice_min = 0;
     ssg_obs_filter flt{};     // ssg_set_obs_filter (these three: a copy; struct_size 0: nothing bound)
+    double *flt_buffer = nullptr; // ssg_set_obs_filter_buffer: the bound filter's job buffer (NULL: none; every ssg_set_obs_filter drops it)
     ssg_timeout_boot tob{};   // ssg_set_timeout_boot
     ssg_eval_recorder rec{};  // ssg_set_eval_recorder, its env_ids pointing at the copy beside it
     ssg::EvalRecIds rec_ids{};
@@ -1077,6 +1078,18 @@ static int check_filter(ssg_handle *h, const ssg_obs_filter *f, const char *what
     return SSG_OK;
 }
 
+// a job-wide filter's buffer (non-NULL) against the record f it is updated beside: f64 [n_members][SSG_FILTER_ROWS][obs_dim] like
+// f->dev_state, and apart from it (the dual finalise kernel writes both)
+static int check_filter_buffer(ssg_handle *h, const ssg_obs_filter *f, const double *dev_buffer, const char *what)
+{
+    const std::string w(what);
+    if (reinterpret_cast<uintptr_t>(dev_buffer) % 8 != 0) return fail(h, SSG_ERR_BAD_ARG, w + ": dev_buffer must be 8-byte aligned");
+    const uintptr_t block = (uintptr_t)f->n_members * SSG_FILTER_ROWS * (uintptr_t)f->obs_dim * sizeof(double);
+    const uintptr_t st = reinterpret_cast<uintptr_t>(f->dev_state), bf = reinterpret_cast<uintptr_t>(dev_buffer);
+    if (bf < st + block && st < bf + block) return fail(h, SSG_ERR_BAD_ARG, w + ": dev_buffer overlaps the filter's dev_state");
+    return SSG_OK;
+}
+
 static int prepare_policy_filter(ssg_handle *h)
 {
     if (!h->flt.struct_size || h->policy_filter_prepared) return SSG_OK;
@@ -1367,7 +1380,7 @@ static hipError_t filter_step_update(ssg_handle *h, const PolicyCall &c, const d
 {
     const ssg_obs_filter &f = h->flt;
     if (!f.struct_size || !(f.flags & SSG_FILTER_UPDATE)) return hipSuccess;
-    return ssg::launch_filter_update(obs, f.obs_dim, c.lay, f.eps, f.dev_state, f.dev_workspace, st); // (check_filter_members: the filter's members are the call's)
+    return ssg::launch_filter_update(obs, f.obs_dim, c.lay, f.eps, f.dev_state, h->flt_buffer, f.dev_workspace, st); // (check_filter_members: the filter's members are the call's)
 }
 
 // What a loop of policy launches and steps asks last, once the host has judged the entry point's own arguments: the filter's member
@@ -2453,11 +2466,32 @@ int ssg_set_obs_filter(ssg_handle *h, const ssg_obs_filter *f)
     if (!h) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_set_obs_filter: NULL handle");
     if (!f) { // unbind
         h->flt = ssg_obs_filter{};
+        h->flt_buffer = nullptr;
         return SSG_OK;
     }
     const int rc = check_filter(h, f, "ssg_set_obs_filter");
-    if (rc != SSG_OK) return rc; // (the binding stays as it was)
+    if (rc != SSG_OK) return rc; // (the binding stays as it was, the buffer's too)
     h->flt = *f;
+    h->flt_buffer = nullptr; // (a buffer belongs to the record it was bound beside)
+    return SSG_OK;
+}
+
+int ssg_set_obs_filter_buffer(ssg_handle *h, double *dev_buffer)
+{
+    if (!h) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_set_obs_filter_buffer: NULL handle");
+    if (!h->flt.struct_size) return fail(h, SSG_ERR_BAD_ARG, "ssg_set_obs_filter_buffer: no observation filter is bound (ssg_set_obs_filter)");
+    if (dev_buffer) {
+        const int rc = check_filter_buffer(h, &h->flt, dev_buffer, "ssg_set_obs_filter_buffer");
+        if (rc != SSG_OK) return rc; // (the binding stays as it was)
+    }
+    h->flt_buffer = dev_buffer; // (NULL unbinds)
+    return SSG_OK;
+}
+
+int ssg_get_obs_filter_buffer(const ssg_handle *h, double **out)
+{
+    if (!h || !out) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_get_obs_filter_buffer: NULL handle or out");
+    *out = h->flt_buffer;
     return SSG_OK;
 }
 
@@ -2585,20 +2619,65 @@ int ssg_pop_perm(ssg_handle *h, uint64_t seed, int64_t update, int members, int 
     return run_perm(h, l, stream, "ssg_pop_perm");
 }
 
-int ssg_obs_filter_update(ssg_handle *h, const ssg_obs_filter *f, const double *dev_obs, void *stream)
+// ssg_obs_filter_update (buffered false: dev_buffer is not read) and ssg_obs_filter_update_buffered, through the rollout loop's launcher
+static int filter_update(ssg_handle *h, const ssg_obs_filter *f, bool buffered, double *dev_buffer, const double *dev_obs, void *stream,
+                         const char *what)
 {
+    const std::string w(what);
     int rc = pop_bound(h);
     if (rc != SSG_OK) return rc;
-    if (!f) return fail(h, SSG_ERR_BAD_ARG, "ssg_obs_filter_update: NULL ssg_obs_filter");
-    rc = check_filter(h, f, "ssg_obs_filter_update");
+    if (!f) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL ssg_obs_filter");
+    rc = check_filter(h, f, what);
     if (rc != SSG_OK) return rc;
-    if (!dev_obs) return fail(h, SSG_ERR_BAD_ARG, "ssg_obs_filter_update: NULL dev_obs");
+    if (buffered) {
+        if (!dev_buffer) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_buffer");
+        rc = check_filter_buffer(h, f, dev_buffer, what);
+        if (rc != SSG_OK) return rc;
+    }
+    if (!dev_obs) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_obs");
     ssg::MemberLayout lay = whole_layout(h); // (one member: the whole handle, and the envs' split is not asked)
-    if (f->n_members > 1) rc = member_layout(h, f->n_members, "ssg_obs_filter_update", true, lay);
+    if (f->n_members > 1) rc = member_layout(h, f->n_members, what, true, lay);
     if (rc == SSG_OK) rc = check_ready(h, false);
     if (rc != SSG_OK) return rc;
-    hipError_t e = ssg::launch_filter_update(dev_obs, f->obs_dim, lay, f->eps, f->dev_state, f->dev_workspace, static_cast<hipStream_t>(stream));
+    hipError_t e = ssg::launch_filter_update(dev_obs, f->obs_dim, lay, f->eps, f->dev_state, buffered ? dev_buffer : nullptr, f->dev_workspace,
+                                             static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("observation filter launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+int ssg_obs_filter_update(ssg_handle *h, const ssg_obs_filter *f, const double *dev_obs, void *stream)
+{
+    return filter_update(h, f, false, nullptr, dev_obs, stream, "ssg_obs_filter_update");
+}
+
+int ssg_obs_filter_update_buffered(ssg_handle *h, const ssg_obs_filter *f, double *dev_buffer, const double *dev_obs, void *stream)
+{
+    return filter_update(h, f, true, dev_buffer, dev_obs, stream, "ssg_obs_filter_update_buffered");
+}
+
+int ssg_obs_filter_merge_rows(ssg_handle *h, const ssg_obs_filter *f, const double *dev_base, const double *dev_rows, int n_rows, void *stream)
+{
+    const char *what = "ssg_obs_filter_merge_rows";
+    const std::string w(what);
+    int rc = pop_bound(h);
+    if (rc != SSG_OK) return rc;
+    if (!f) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL ssg_obs_filter");
+    rc = check_filter(h, f, what);
+    if (rc != SSG_OK) return rc;
+    if (!dev_base || !dev_rows) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_base or dev_rows");
+    if (reinterpret_cast<uintptr_t>(dev_base) % 8 != 0 || reinterpret_cast<uintptr_t>(dev_rows) % 8 != 0)
+        return fail(h, SSG_ERR_BAD_ARG, w + ": dev_base and dev_rows must be 8-byte aligned");
+    if (n_rows < 1 || n_rows > SSG_DP_MAX_SHARDS) return fail(h, SSG_ERR_BAD_ARG, w + ": n_rows must be in 1..SSG_DP_MAX_SHARDS");
+    // (the kernel reads base and rows while it writes the state: a block of either that overlaps the state's would be read half merged)
+    const uintptr_t block = (uintptr_t)f->n_members * SSG_FILTER_ROWS * (uintptr_t)f->obs_dim * sizeof(double);
+    const uintptr_t st = reinterpret_cast<uintptr_t>(f->dev_state), b0 = reinterpret_cast<uintptr_t>(dev_base), r0 = reinterpret_cast<uintptr_t>(dev_rows);
+    if (b0 < st + block && st < b0 + block) return fail(h, SSG_ERR_BAD_ARG, w + ": dev_base overlaps the filter's dev_state");
+    if (r0 < st + block && st < r0 + block * (uintptr_t)n_rows) return fail(h, SSG_ERR_BAD_ARG, w + ": dev_rows overlaps the filter's dev_state");
+    rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_filter_merge_rows(dev_base, dev_rows, n_rows, f->obs_dim, f->n_members, f->eps, f->dev_state,
+                                                 static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("observation filter rows merge launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
 

@@ -14,6 +14,10 @@
 // trees and the run its tile falls in depend on the row's index within the member's slice and on the slice's row count only: not on
 // the grid, on which CU ran what, or on the other members.  No atomics, no hand-off between workgroups inside a launch.  The same order
 // operation for operation in numpy: ship_sim_gym_amd/obs_filter.py, merge_reference.
+//
+// A job-wide filter (include/shipsim.h, "Job-wide observation filter") adds two kernels: the finalise launch that merges the batch into
+// the state and into the rank's buffer (filter_finalise_dual_kernel, in place of launch 2 while a buffer is bound), and the merge of
+// the ranks' gathered buffers into the base (filter_merge_rows_kernel; in numpy: merge_rows_reference).
 #include <cstdint>
 
 #include "shipsim_filter_common.h"
@@ -146,6 +150,101 @@ __global__ void __launch_bounds__(kFltTile) filter_finalise_kernel(const double 
     }
 }
 
+// Launch 2 while a job-wide filter's buffer is bound (include/shipsim.h, "Job-wide observation filter"): the member's batch total r[0]
+// is formed exactly as above and merged into two states, the bound one and the buffer — the statistics of this rank's own rows since the
+// last synchronisation — each with its own count, read before the barrier.  The buffer's four rows are written like the state's, so it
+// is a state block: bit for bit what an empty filter holds after the same batches.  A kernel of its own, its first part the text of
+// the one above: with one body shared by both (a template, an inlined helper) the kernel above does not keep its machine code
+// (profiles/obs_filter_job/README.md).
+__global__ void __launch_bounds__(kFltTile) filter_finalise_dual_kernel(const double *__restrict__ part, int tiles_stride, int D, int n,
+                                                                        const int32_t *__restrict__ slices, double eps, double *__restrict__ state,
+                                                                        double *__restrict__ buffer)
+{
+    __shared__ double run_mean[kFltRuns * kFltMaxDim], run_m2[kFltRuns * kFltMaxDim];
+    size_t row0;
+    int n_m;
+    member_rows(slices, blockIdx.x, n, &row0, &n_m);
+    const int T = (n_m + kFltTile - 1) / kFltTile, L = (T + kFltRuns - 1) / kFltRuns;
+    const double *mine = part + (size_t)blockIdx.x * tiles_stride * 2 * (size_t)D;
+    double *st = state + (size_t)blockIdx.x * SSG_FILTER_ROWS * (size_t)D;
+    const int tid = threadIdx.x;
+    const double count = st[3 * D]; // (read by every lane before the barrier below, written after it)
+    double *bf = buffer + (size_t)blockIdx.x * SSG_FILTER_ROWS * (size_t)D;
+    const double bcount = bf[3 * D]; // (likewise)
+    for (int item = tid; item < kFltRuns * D; item += kFltTile) {
+        const int g = item / D, d = item - g * D;
+        const int t1 = (g + 1) * L < T ? (g + 1) * L : T;
+        Stat a = {0.0, 0.0, 0.0};
+        for (int t = g * L; t < t1; t += 8) { // (eight tiles' partials are loaded ahead of their merges, which stay in tile order)
+            double pm[8], pq[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const size_t tt = (size_t)(t + j < t1 ? t + j : t1 - 1);
+                pm[j] = mine[tt * 2 * D + d];
+                pq[j] = mine[tt * 2 * D + D + d];
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                if (t + j >= t1) break;
+                const int left = n_m - (t + j) * kFltTile;
+                const Stat b = {(double)(left < kFltTile ? left : kFltTile), pm[j], pq[j]};
+                merge(a, b);
+            }
+        }
+        run_mean[item] = a.mean;
+        run_m2[item] = a.m2;
+    }
+    __syncthreads();
+    for (int d = tid; d < D; d += kFltTile) {
+        Stat r[kFltRuns];
+#pragma unroll
+        for (int g = 0; g < kFltRuns; ++g) {
+            const long long b0 = (long long)g * L * kFltTile, b1 = b0 + (long long)L * kFltTile; // the run's rows: [b0, b1) within n_m
+            const long long lo = b0 < n_m ? b0 : n_m, hi = b1 < n_m ? b1 : n_m;
+            r[g] = {(double)(hi - lo), run_mean[g * D + d], run_m2[g * D + d]};
+        }
+#pragma unroll
+        for (int h = kFltRuns / 2; h > 0; h >>= 1)
+#pragma unroll
+            for (int g = 0; g < h; ++g) merge(r[g], r[g + h]);
+        Stat s = {count, st[d], st[D + d]};
+        merge(s, r[0]);
+        st[d] = s.mean;
+        st[D + d] = s.m2;
+        st[2 * D + d] = s.n >= 2.0 ? sqrt(s.m2 / (s.n - 1.0)) + eps : 1.0;
+        if (d == 0) st[3 * D] = s.n;
+        Stat b = {bcount, bf[d], bf[D + d]}; // the same total into the buffer
+        merge(b, r[0]);
+        bf[d] = b.mean;
+        bf[D + d] = b.m2;
+        bf[2 * D + d] = b.n >= 2.0 ? sqrt(b.m2 / (b.n - 1.0)) + eps : 1.0;
+        if (d == 0) bf[3 * D] = b.n;
+    }
+}
+
+// The rows merge of a job-wide filter (ssg_obs_filter_merge_rows): one workgroup per member, a thread per column.  state[m] = base[m]
+// merged with rows[0][m], rows[1][m], ..., rows[n_rows - 1][m] in index order, a row of count 0 skipped (merge's empty side); every
+// block is f64 [members][SSG_FILTER_ROWS][D], rows [n_rows] of them.  No atomics, no LDS; state must not alias base or rows.
+__global__ void __launch_bounds__(kFltTile) filter_merge_rows_kernel(const double *__restrict__ base, const double *__restrict__ rows, int n_rows,
+                                                                     int D, double eps, double *__restrict__ state)
+{
+    const size_t block = (size_t)SSG_FILTER_ROWS * (size_t)D, mine = (size_t)blockIdx.x * block, stride = (size_t)gridDim.x * block;
+    const double *b0 = base + mine;
+    double *st = state + mine;
+    for (int d = threadIdx.x; d < D; d += kFltTile) {
+        Stat s = {b0[3 * D], b0[d], b0[D + d]};
+        for (int r = 0; r < n_rows; ++r) {
+            const double *row = rows + (size_t)r * stride + mine;
+            const Stat b = {row[3 * D], row[d], row[D + d]};
+            merge(s, b);
+        }
+        st[d] = s.mean;
+        st[D + d] = s.m2;
+        st[2 * D + d] = s.n >= 2.0 ? sqrt(s.m2 / (s.n - 1.0)) + eps : 1.0;
+        st[3 * D + d] = d == 0 ? s.n : 0.0;
+    }
+}
+
 } // namespace
 
 size_t filter_workspace_bytes(int n_envs, int obs_dim, int members)
@@ -153,15 +252,27 @@ size_t filter_workspace_bytes(int n_envs, int obs_dim, int members)
     return (size_t)members * (size_t)filter_tiles(n_envs) * 2 * (size_t)obs_dim * sizeof(double);
 }
 
-hipError_t launch_filter_update(const double *obs, int D, const MemberLayout &lay, double eps, double *state, void *ws, hipStream_t stream)
+hipError_t launch_filter_update(const double *obs, int D, const MemberLayout &lay, double eps, double *state, double *buffer, void *ws,
+                                hipStream_t stream)
 {
     const int tiles = filter_tiles(lay.n);
     double *part = static_cast<double *>(ws);
     hipLaunchKernelGGL(filter_partials_kernel, dim3((unsigned)tiles, (unsigned)lay.members), dim3(kFltTile), 0, stream, obs, D, lay.n, lay.slices, part);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(filter_finalise_kernel, dim3((unsigned)lay.members), dim3(kFltTile), 0, stream, (const double *)part, tiles, D, lay.n, lay.slices,
-                       eps, state);
+    if (buffer)
+        hipLaunchKernelGGL(filter_finalise_dual_kernel, dim3((unsigned)lay.members), dim3(kFltTile), 0, stream, (const double *)part, tiles, D, lay.n,
+                           lay.slices, eps, state, buffer);
+    else
+        hipLaunchKernelGGL(filter_finalise_kernel, dim3((unsigned)lay.members), dim3(kFltTile), 0, stream, (const double *)part, tiles, D, lay.n,
+                           lay.slices, eps, state);
+    return hipGetLastError();
+}
+
+hipError_t launch_filter_merge_rows(const double *base, const double *rows, int n_rows, int D, int members, double eps, double *state,
+                                    hipStream_t stream)
+{
+    hipLaunchKernelGGL(filter_merge_rows_kernel, dim3((unsigned)members), dim3(kFltTile), 0, stream, base, rows, n_rows, D, eps, state);
     return hipGetLastError();
 }
 

@@ -461,8 +461,13 @@ hipError_t launch_eval_record_frames(const DevCfg &c, const DynCfg &d, const Eva
 constexpr int kFltTile = 256, kFltChunk = 31, kFltMaxDim = SSG_MAX_HISTORY * (6 + SSG_MAX_BEAMS);
 inline int filter_tiles(long long n) { return (int)((n + kFltTile - 1) / kFltTile); }
 size_t filter_workspace_bytes(int n_envs, int obs_dim, int members);
-// the two launches: the rows of member m's envs of obs into its SSG_FILTER_ROWS state rows
-hipError_t launch_filter_update(const double *obs, int D, const MemberLayout &lay, double eps, double *state, void *ws, hipStream_t stream);
+// the two launches: the rows of member m's envs of obs into its SSG_FILTER_ROWS state rows — and, with `buffer` (a job-wide filter's, else
+// NULL), the same batch total into the buffer's rows too, through the dual finalise kernel: still two launches
+hipError_t launch_filter_update(const double *obs, int D, const MemberLayout &lay, double eps, double *state, double *buffer, void *ws,
+                                hipStream_t stream);
+// state[m] = base[m] merged with rows[0][m] .. rows[n_rows - 1][m], every block f64 [members][SSG_FILTER_ROWS][D]: one launch
+hipError_t launch_filter_merge_rows(const double *base, const double *rows, int n_rows, int D, int members, double eps, double *state,
+                                    hipStream_t stream);
 // the return filter (shipsim_retfilter.hip): the workspace holds the walk's tile partials, f64 [members][K][filter_tiles(n_envs)][2], then
 // the chain's denoms, f64 [K][members]
 size_t ret_filter_workspace_bytes(int n_envs, int K, int members);

@@ -15,7 +15,10 @@ The two halves of a minibatch are public so that ONE process can replay a W-rank
 ``set_moments`` and ``local_row`` / ``apply_rows`` with torch.stack as the gather.  ``apply_reference`` and ``moments_reference`` restate
 the two device steps in numpy, operation for operation.
 
-Out of scope: adv_norm="minibatch" across ranks, observation / return filters' statistics across ranks, resuming a multi-rank run,
+The observation filter of such a job is ship_sim_gym_amd/obs_filter.py's ``ObsFilter(job=True)``: rank-local during a rollout,
+synchronised after it by the same pattern (gathered buffers, the same merge on every rank).
+
+Out of scope: adv_norm="minibatch" across ranks, the return filter's statistics across ranks, resuming a multi-rank run,
 populations across ranks, overlapping the gather with the next gradient, running this loop from C.
 """
 import ctypes as C

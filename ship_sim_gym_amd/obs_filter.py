@@ -10,9 +10,11 @@ population when there are several: bound to a ``ShipVecEnv`` (``env.set_obs_filt
 in include/shipsim.h (section "Observation filter") on its own terms; no bit parity with either library is claimed.
 
 ``VecNormalize``'s other half, reward / return normalisation (``norm_reward``), is ship_sim_gym_amd/ret_filter.py's ``ReturnFilter``.
-Not covered: merging the statistics of several handles or GPUs (RLlib synchronises its workers' filters), a per-column clip.
+RLlib synchronises its workers' filters after every training iteration; ``ObsFilter(..., job=True)`` with ``sync()`` is that for the ranks
+of a data-parallel job (ship_sim_gym_amd/dp.py).  Not covered: statistics merged per step, a per-column clip.
 
-``merge_reference`` is a numpy restatement of the device's reduction, the same tiles and trees operation for operation, for tests.
+``merge_reference`` is a numpy restatement of the device's reduction, the same tiles and trees operation for operation, for tests;
+``merge_rows_reference`` restates the synchronisation's merge of the ranks' buffers.
 """
 import ctypes as C
 
@@ -90,6 +92,25 @@ def merge_reference(state_rows, batch_rows, eps=1e-8):
     return out
 
 
+def merge_rows_reference(base_rows, rows, eps=1e-8):
+    """What ssg_obs_filter_merge_rows leaves in one member's state rows: base_rows f64 [4, D] merged with rows f64 [W, 4, D] (the ranks'
+    buffers of that member) in index order, a row of count 0 skipped, in the header's association ("Job-wide observation filter").
+    Returns new state rows; denom's square root is numpy's (the device's may differ in the last bit)."""
+    base = np.array(base_rows, dtype=np.float64)
+    rows = np.array(rows, dtype=np.float64)
+    if base.ndim != 2 or base.shape[0] != N.FILTER_ROWS or rows.ndim != 3 or rows.shape[0] < 1 or rows.shape[1:] != base.shape:
+        raise ValueError("merge_rows_reference: base_rows must be [4, D] and rows [W >= 1, 4, D]")
+    a = (np.float64(base[3, 0]), base[0].copy(), base[1].copy())
+    for r in rows:
+        a = _merge(a, (np.float64(r[3, 0]), r[0].copy(), r[1].copy()))
+    cnt, mean, m2 = a
+    out = np.zeros_like(base)
+    out[0], out[1] = mean, m2
+    out[2] = np.sqrt(m2 / (cnt - 1.0)) + np.float64(eps) if cnt >= 2.0 else 1.0
+    out[3, 0] = cnt
+    return out
+
+
 class ObsFilter(object):
     """The filter of `env` (a ShipVecEnv): owns the state tensor f64 [n_members, 4, D] (mean, M2, denom, {count, 0, ...} per member; zeros
     = empty, which normalises as mean 0, denom 1) and the workspace of the update's partials.  n_members: 1 for a single policy, P for
@@ -98,9 +119,15 @@ class ObsFilter(object):
     (``train(flag)`` changes it later; ``frozen()`` gives a view that never does).
 
     Bind it with ``env.set_obs_filter(f)``; then ``policy_act``, ``rollout_policy``, ``population_act``, ``rollout_population`` and
-    ``NativeEvaluator`` use it without further arguments, and the policy's ``obs_scale`` is not read."""
+    ``NativeEvaluator`` use it without further arguments, and the policy's ``obs_scale`` is not read.
 
-    def __init__(self, env, n_members=1, clip=10.0, eps=1e-8, update=True, _state=None):
+    job=True: the filter of one rank of a data-parallel job (include/shipsim.h, "Job-wide observation filter").  It also owns ``buffer``
+    (this rank's own statistics since the last synchronisation; ``env.set_obs_filter(f)`` binds it too, and every update then merges
+    into both) and ``base`` (the state all ranks held right after it).  ``sync(group)`` after each rollout gathers the ranks' buffers
+    and merges them into every rank's state, bit-identically; ``merge_rows(rows)`` is its second half, so that one process can replay
+    a W-rank job with ``torch.stack`` of the ranks' buffers as the gather."""
+
+    def __init__(self, env, n_members=1, clip=10.0, eps=1e-8, update=True, job=False, _state=None):
         torch = _torch()
         P, D = int(n_members), int(env.states_history)
         clip, eps = float(clip), float(eps)
@@ -114,6 +141,9 @@ class ObsFilter(object):
         N.check(N.lib().ssg_obs_filter_workspace_nbytes(int(env.num_envs), D, P, C.byref(nbytes)), None, "ssg_obs_filter_workspace_nbytes")
         self.state = _state if _state is not None else torch.zeros((P, N.FILTER_ROWS, D), dtype=torch.float64, device=dev)
         self.workspace = torch.zeros(nbytes.value, dtype=torch.uint8, device=dev)
+        self.job = bool(job)
+        self.buffer = torch.zeros_like(self.state) if self.job else None
+        self.base = self.state.clone() if self.job else None
         self._bound = []  # the envs this record is bound to: train() re-binds them (a binding is a copy of the record)
         self._views = []  # the frozen() views of this filter: they follow its clip and eps
 
@@ -151,7 +181,8 @@ class ObsFilter(object):
 
     def update(self, obs=None):
         """Merge a batch of observations into the state (ssg_obs_filter_update, two launches on the current stream), whatever
-        ``updating`` says: obs f64 [N, D] in the env's row layout (default: the env's current ``obs``); member m's rows are its slice."""
+        ``updating`` says: obs f64 [N, D] in the env's row layout (default: the env's current ``obs``); member m's rows are its slice.
+        A job filter merges the batch into its buffer too (ssg_obs_filter_update_buffered: the same two launches)."""
         torch = _torch()
         env = self.env
         obs = env.obs if obs is None else obs
@@ -160,8 +191,40 @@ class ObsFilter(object):
                              % (env.num_envs, self.obs_dim, env.device, obs.dtype, tuple(obs.shape), obs.device))
         rec = self.to_native()
         with torch.cuda.device(env.device):
-            N.check(N.lib().ssg_obs_filter_update(env._h, C.byref(rec), C.c_void_p(obs.data_ptr()), env._stream()), env._h,
-                    "ssg_obs_filter_update")
+            if self.job:
+                N.check(N.lib().ssg_obs_filter_update_buffered(env._h, C.byref(rec), C.c_void_p(self.buffer.data_ptr()),
+                                                               C.c_void_p(obs.data_ptr()), env._stream()), env._h, "ssg_obs_filter_update_buffered")
+            else:
+                N.check(N.lib().ssg_obs_filter_update(env._h, C.byref(rec), C.c_void_p(obs.data_ptr()), env._stream()), env._h,
+                        "ssg_obs_filter_update")
+
+    def merge_rows(self, rows):
+        """The second half of ``sync``: rows f64 [W, n_members, 4, D] on the filter's device (the ranks' buffers in rank order; W in
+        1..64).  state = base merged with rows[0], ..., rows[W - 1] (ssg_obs_filter_merge_rows, one launch on the current stream), then
+        base <- state and buffer <- 0."""
+        torch = _torch()
+        env = self.env
+        if not self.job:
+            raise ValueError("ObsFilter.merge_rows: this filter was not made with job=True (it has no base and no buffer)")
+        want = tuple(self.state.shape)
+        if (rows.dtype != torch.float64 or rows.device != self.state.device or not rows.is_contiguous() or rows.dim() != 4
+                or tuple(rows.shape[1:]) != want or not 1 <= rows.shape[0] <= N.DP_MAX_SHARDS):
+            raise ValueError("ObsFilter.merge_rows: rows must be a contiguous float64 tensor (W in 1..%d, %d, %d, %d) on %s (got %s %s on %s)"
+                             % ((N.DP_MAX_SHARDS,) + want + (self.state.device, rows.dtype, tuple(rows.shape), rows.device)))
+        rec = self.to_native()
+        with torch.cuda.device(env.device):
+            N.check(N.lib().ssg_obs_filter_merge_rows(env._h, C.byref(rec), C.c_void_p(self.base.data_ptr()), C.c_void_p(rows.data_ptr()),
+                                                      int(rows.shape[0]), env._stream()), env._h, "ssg_obs_filter_merge_rows")
+        self.base.copy_(self.state)
+        self.buffer.zero_()
+        return self
+
+    def sync(self, group=None):
+        """After a rollout, before GAE, on every rank of the job: all-gather the ranks' buffers in rank order and merge them into the
+        state (``merge_rows``).  Every rank runs the same arithmetic on the same rows, so the states agree bit for bit without a
+        broadcast.  Without a process group it merges this filter's own buffer."""
+        from .sharding import all_gather_rows
+        return self.merge_rows(all_gather_rows(self.buffer, group))
 
     def train(self, flag=True):
         """Whether the rollout loops update the statistics (``VecNormalize.training``); re-binds the envs this record is bound to."""
@@ -211,15 +274,29 @@ class ObsFilter(object):
         return v.float()
 
     def state_dict(self):
-        return {"state": self.state.detach().cpu().clone(), "clip": self.clip, "eps": self.eps, "n_members": self.n_members,
-                "obs_dim": self.obs_dim}
+        sd = {"state": self.state.detach().cpu().clone(), "clip": self.clip, "eps": self.eps, "n_members": self.n_members,
+              "obs_dim": self.obs_dim}
+        if self.job:  # (a plain filter's dict stays what it was; a plain filter loads a job's dict and reads its state alone)
+            sd.update(base=self.base.detach().cpu().clone(), buffer=self.buffer.detach().cpu().clone())
+        return sd
 
     def load_state_dict(self, sd):
-        """Copy a state_dict's statistics into this filter's state tensor (shape checked), and take its clip and eps."""
+        """Copy a state_dict's statistics into this filter's state tensor (shape checked), and take its clip and eps.  A job filter
+        takes base and buffer too; from a plain filter's dict, which has neither, the state becomes the base and the buffer is empty."""
         st = sd["state"]
-        if tuple(st.shape) != tuple(self.state.shape):
-            raise ValueError("ObsFilter.load_state_dict: state of shape %s, this filter's is %s" % (tuple(st.shape), tuple(self.state.shape)))
+        if self.job and ("base" in sd) != ("buffer" in sd):
+            raise ValueError("ObsFilter.load_state_dict: a job filter's dict holds base and buffer, or neither")
+        base, buffer = (sd.get("base", st), sd.get("buffer")) if self.job else (st, None)
+        for t in (st, base) + (() if buffer is None else (buffer,)):
+            if tuple(t.shape) != tuple(self.state.shape):
+                raise ValueError("ObsFilter.load_state_dict: state of shape %s, this filter's is %s" % (tuple(t.shape), tuple(self.state.shape)))
         self.state.copy_(st.to(self.state.dtype))
+        if self.job:
+            self.base.copy_(base.to(self.state.dtype))
+            if buffer is None:
+                self.buffer.zero_()
+            else:
+                self.buffer.copy_(buffer.to(self.state.dtype))
         self.clip, self.eps = float(sd["clip"]), float(sd["eps"])
         for f in [self] + self._views:  # (training and evaluation must normalise alike)
             f.clip, f.eps = self.clip, self.eps

@@ -953,7 +953,8 @@ class ShipVecEnv(*_BASES):
         """Bind an ObsFilter (or one of its frozen() views) to this env: every policy launch on it — policy_act, rollout_policy,
         population_act, rollout_population, NativeEvaluator — then forms x = clamp((obs - mean) / denom) from the filter's state instead
         of obs / obs_scale, a single policy with a filter of 1 member, a population of P members with one of P; the rollout loops
-        merge each step's observations first when the filter is updating.  The library keeps a copy of the record, this env a
+        merge each step's observations first when the filter is updating — a job filter's (``ObsFilter(job=True)``) into its buffer
+        too, which is bound with it.  The library keeps a copy of the record, this env a
         reference to the filter (whose tensors the launches read).  None unbinds; a refused binding leaves the old one in place."""
         old = self._obs_filter
         if f is None:
@@ -963,6 +964,8 @@ class ShipVecEnv(*_BASES):
                 raise ValueError("set_obs_filter: the filter lives on %s, the env on %s" % (f.state.device, self.device))
             rec = f.to_native()
             N.check(N.lib().ssg_set_obs_filter(self._h, C.byref(rec)), self._h, "ssg_set_obs_filter")
+            if getattr(f, "buffer", None) is not None:  # a job filter: the rollout loops merge into its buffer too (the call above dropped it)
+                N.check(N.lib().ssg_set_obs_filter_buffer(self._h, C.c_void_p(f.buffer.data_ptr())), self._h, "ssg_set_obs_filter_buffer")
         if old is not None and old is not f and self in old._bound:
             old._bound.remove(self)
         if f is not None and self not in f._bound:

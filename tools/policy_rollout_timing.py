@@ -22,6 +22,12 @@ three alternating in every repeat; and the filter's two launches alone (50 back-
 every repeat in us per rollout step; the shader clock as rocm-smi reports it before and after (null when it cannot be read).  The
 unbound figure of two builds of the library is compared by running this mode alternately with SSG_LIB_PATH set to each.
 
+    python tools/policy_rollout_timing.py --obs-filter-job [--beams 8] [--envs 65536,4096] [--horizon 64] [--repeats 7]
+
+--obs-filter-job measures the job-wide filter (``ObsFilter(job=True)``) instead: on ONE native env per env count whole rollouts are
+timed with an updating filter bound and with a job filter bound (its buffer too: the dual finalise kernel), the two alternating in every
+repeat; then, alone and back to back, the update's two launches both ways (50 calls) and the rows-merge launch at W = 1, 2 and 8 rows.
+
     python tools/policy_rollout_timing.py --timeout-bootstrap [--envs 65536,4096] [--horizon 32,64] [--repeats 7]
 
 --timeout-bootstrap measures the time-out bootstrap (ShipVecEnv.set_timeout_bootstrap) instead: on ONE native env per env count (the
@@ -180,6 +186,75 @@ def measure_filter(mod, n, horizon, repeats, dev, beams):
             "sclk_before": clock0, "sclk_after": clock1}
 
 
+def measure_filter_job(mod, n, horizon, repeats, dev, beams):
+    """The job-wide filter's cost: the rollout step with an updating filter bound and its buffer bound too (the dual finalise kernel)
+    against the same filter without a buffer, alternating on ONE env; the update's two launches alone, both ways; and the rows-merge
+    launch alone at W = 1, 2 and 8 rows (ssg_obs_filter_merge_rows without the copies ObsFilter.merge_rows adds)."""
+    from ship_sim_gym_amd.obs_filter import ObsFilter
+    torch.manual_seed(0)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    probe = mod.ShipVecEnv(1, mod.GameConfig, mod.EnvConfig, device=dev, n_maps=1, n_beams=beams)
+    D, A = probe.states_history, probe.action_space.n
+    probe.close()
+    net = mod.ActorCritic(D, A).to(dev)
+    shards = mod.make_shards(n, "native", net, dev, horizon, env_kw={"n_beams": beams})
+    env = shards[0].env
+    env.reset_tensor()
+    policy = mod.NativePolicy.from_actor_critic(net, shards[0].scale)
+    bind = {"unbuffered": ObsFilter(env), "buffered": ObsFilter(env, job=True)}
+    clock0 = _sclk()
+    for m in ("unbuffered", "buffered") * 2:  # warm-up: two rollouts each
+        env.set_obs_filter(bind[m])
+        mod.rollout(shards, horizon, "native", gen, policy)
+    torch.cuda.synchronize()
+    times = {m: [] for m in bind}
+    for _ in range(repeats):
+        for m in bind:
+            env.set_obs_filter(bind[m])
+            times[m].append(_timed(lambda: mod.rollout(shards, horizon, "native", gen, policy)) / horizon)
+    env.set_obs_filter(None)
+    L, h, st, obs = N.lib(), env._h, env._stream(), C.c_void_p(env.obs.data_ptr())
+    job = bind["buffered"]
+    rec, buf = job.to_native(), C.c_void_p(job.buffer.data_ptr())
+
+    def plain(k):
+        for _ in range(k):
+            N.check(L.ssg_obs_filter_update(h, C.byref(rec), obs, st), h, "ssg_obs_filter_update")
+
+    def dual(k):
+        for _ in range(k):
+            N.check(L.ssg_obs_filter_update_buffered(h, C.byref(rec), buf, obs, st), h, "ssg_obs_filter_update_buffered")
+    update_us = {}
+    for name, fn in (("unbuffered", plain), ("buffered", dual)):
+        fn(5)
+        torch.cuda.synchronize()
+        update_us[name] = [_timed(lambda: fn(50)) / 50 for _ in range(repeats)]
+    merge_us = {}
+    base = C.c_void_p(job.base.data_ptr())
+    for W in (1, 2, 8):
+        rows = job.buffer.clone()[None].repeat(W, 1, 1, 1).contiguous()
+
+        def merges(k):
+            for _ in range(k):
+                N.check(L.ssg_obs_filter_merge_rows(h, C.byref(rec), base, C.c_void_p(rows.data_ptr()), W, st), h, "ssg_obs_filter_merge_rows")
+        merges(5)
+        torch.cuda.synchronize()
+        merge_us[W] = [_timed(lambda: merges(50)) / 50 for _ in range(repeats)]
+    clock1 = _sclk()
+    env.close()
+    res = {"envs": n, "obs_dim": D, "hidden": 64, "layers": 2, "n_actions": A, "horizon": horizon,
+           "repeats_us": {k: [round(t, 2) for t in v] for k, v in times.items()}, "sclk_before": clock0, "sclk_after": clock1}
+    for m in bind:
+        res["%s_us_per_step" % m] = round(statistics.median(times[m]), 2)
+        res["update_%s_us" % m] = round(statistics.median(update_us[m]), 2)
+        res["update_%s_repeats_us" % m] = [round(t, 2) for t in update_us[m]]
+    for W, v in merge_us.items():
+        res["merge_rows_%d_us" % W] = round(statistics.median(v), 2)
+        res["merge_rows_%d_repeats_us" % W] = [round(t, 2) for t in v]
+    return res
+
+
 def measure_timeout(mod, n, horizon, repeats, dev):
     torch.manual_seed(0)
     gen = torch.Generator(device=dev)
@@ -253,7 +328,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--separate-value", action="store_true", help="also measure the separate-value-network shape, in the same process")
     ap.add_argument("--obs-filter", action="store_true", help="measure the observation filter instead (unbound / updating / frozen rollouts)")
-    ap.add_argument("--beams", type=int, default=8, help="lidar beams of the --obs-filter env (8 -> D = 28)")
+    ap.add_argument("--obs-filter-job", action="store_true",
+                    help="measure the job-wide filter instead (updating rollouts with and without the buffer bound, the rows merge alone)")
+    ap.add_argument("--beams", type=int, default=8, help="lidar beams of the --obs-filter / --obs-filter-job env (8 -> D = 28)")
     ap.add_argument("--timeout-bootstrap", action="store_true",
                     help="measure the time-out bootstrap instead (unbound / bound rollouts, the one launch alone)")
     a = ap.parse_args()
@@ -269,6 +346,11 @@ def main():
         res = [measure_timeout(mod, n, k, a.repeats, dev) for n, k in zip(envs, horizons)]
         print(json.dumps({"tool": "policy_rollout_timing", "mode": "timeout_bootstrap", "lib": N.LIB_PATH,
                           "device": torch.cuda.get_device_name(0), "results": res}))
+        return
+    if a.obs_filter_job:
+        res = [measure_filter_job(mod, int(n), a.horizon, a.repeats, dev, a.beams) for n in a.envs.split(",")]
+        print(json.dumps({"tool": "policy_rollout_timing", "mode": "obs_filter_job", "lib": N.LIB_PATH, "device": torch.cuda.get_device_name(0),
+                          "results": res}))
         return
     if a.obs_filter:
         res = [measure_filter(mod, int(n), a.horizon, a.repeats, dev, a.beams) for n in a.envs.split(",")]

@@ -61,14 +61,15 @@ def check_flag_values(a, error):
 
 
 def bind_env(env, horizon, n_members=1, obs_filter=False, norm_reward=False, gamma=0.99, reward_clip=10.0, timeout_bootstrap=False,
-             eval_env=None):
+             eval_env=None, job_obs_filter=False):
     """Bind what the configuration asks for to a training env of n_members members; returns (obs filter, return filter, evaluator), None
-    where off.  The obs filter is bound to the env (the rollout merges each step's rows, then normalises) and, frozen, to eval_env; the
+    where off.  The obs filter is bound to the env (the rollout merges each step's rows, then normalises) and, frozen, to eval_env —
+    job_obs_filter: the job-wide one, with its buffer, which the caller synchronises after every rollout; the
     bootstrap makes the rollout return "boot", which gae() reads; the return filter is applied per rollout, between the rollout and GAE."""
     flt = rflt = evaluator = None
-    if obs_filter:
+    if obs_filter or job_obs_filter:
         from ship_sim_gym_amd.obs_filter import ObsFilter
-        flt = ObsFilter(env, n_members=n_members)
+        flt = ObsFilter(env, n_members=n_members, job=bool(job_obs_filter))
         env.set_obs_filter(flt)
     if timeout_bootstrap:
         env.set_timeout_bootstrap(True, rows=horizon)

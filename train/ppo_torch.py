@@ -8,7 +8,7 @@ leave the GPU; the policy is a small MLP in fp32.
                               [--eval-every U --eval-episodes E] [--obs-filter [--save-obs-filter FILE]]
                               [--norm-reward [--reward-clip C]]
                               [--save FILE [--save-every U]] [--save-best FILE] [--resume FILE] [--gpus W]
-                              [--report [--report-kl]] [--progress FILE]
+                              [--report [--report-kl]] [--progress FILE] [--job-obs-filter]
 
 Four ways to run the rollout loop (the reference's `model.learn` -> runner.run(): one `env.step(actions)` per policy
 forward, train/stable_baselines/ppo.py:84-100,122-123) — same arithmetic, same results bit for bit:
@@ -77,6 +77,14 @@ an all-gather of the rows, the same apply on every rank: no parameter broadcast)
 evaluates and writes ``--save`` (the policy and the trainer); every rank prints a checksum of its parameters, and the lines agree.
 ``--resume``, ``--save-every``, ``--obs-filter``, ``--norm-reward`` and ``--adv-norm minibatch`` are refused with more than one rank.
 ``SSG_TRAIN_SHARE_DEVICE=1`` (tests on a one-GPU box) puts every rank on device 0 over gloo.
+
+``--job-obs-filter`` (``--mode native --update native`` only, one rank or more; not together with ``--obs-filter``): the running
+observation filter for a job, synchronised as RLlib synchronises its workers' filters (``ObsFilter(job=True)``,
+ship_sim_gym_amd/obs_filter.py).  During a rollout a rank normalises with its own state, the job's statistics as of the last
+synchronisation plus its own rows since; after every rollout, before GAE, the ranks all-gather what they added and every rank merges
+the rows with the same arithmetic, so the states agree bit for bit.  Rank 0 evaluates through a frozen view, ``--save`` gains the
+``obs_filter`` section, which train/evaluate_native.py ``--checkpoint FILE`` applies, and every rank prints a checksum of the filter's
+state beside the parameters'.  The return filter across ranks stays out of scope.
 
 The sampling noise of a whole rollout is drawn in one call before it (uniforms [horizon, envs], inverse-CDF sampling inside
 the step), so a captured step holds no random-number generator state and replays exactly what the eager loop computes.
@@ -310,13 +318,23 @@ REPORT_REQUIREMENTS = tuple(
     for name, flag in (("progress", "--progress"), ("report_kl", "--report-kl"), ("report", "--report")))
 
 
+# The job-wide observation filter's row, likewise: any number of ranks.  What it cannot be combined with is asked after its needs.
+JOB_OBS_FILTER_REQUIREMENTS = (
+    ("job_obs_filter", "--job-obs-filter", lambda a: bool(getattr(a, "job_obs_filter", None)), ("mode", "update"), False,
+     "the ranks' filters are synchronised between the native rollout and the device's GAE"),
+)
+
+
 def check_requirements(args, ranks, error=None):
-    """Walk EPISODE_LOG_REQUIREMENTS, REPORT_REQUIREMENTS and REQUIREMENTS over the arguments `args` (a dict) of a run of `ranks` ranks.  The first row that is on and misses a need, or is
+    """Walk EPISODE_LOG_REQUIREMENTS, REPORT_REQUIREMENTS, JOB_OBS_FILTER_REQUIREMENTS and REQUIREMENTS over the arguments `args` (a dict) of a run of `ranks` ranks.  The first row that is on and misses a need, or is
     refused with more than one rank, goes to the parser's `error` with the flags in the text, or is a ValueError with train()'s names."""
     a = argparse.Namespace(**dict(args, ranks=ranks))
-    for name, flag, on, needs, one_rank_only, why in EPISODE_LOG_REQUIREMENTS + REPORT_REQUIREMENTS + REQUIREMENTS:
+    for name, flag, on, needs, one_rank_only, why in EPISODE_LOG_REQUIREMENTS + REPORT_REQUIREMENTS + JOB_OBS_FILTER_REQUIREMENTS + REQUIREMENTS:
         text = None
-        if on(a) and not all(NEEDS[k][2](a) for k in needs):
+        if name == "job_obs_filter" and on(a) and a.obs_filter and all(NEEDS[k][2](a) for k in needs):
+            text = ("--job-obs-filter is not supported together with --obs-filter: one filter is bound to the env" if error else
+                    "job_obs_filter (--job-obs-filter): it is not supported together with obs_filter=True: one filter is bound to the env")
+        elif on(a) and not all(NEEDS[k][2](a) for k in needs):
             text = ("%s needs %s (%s)" % (flag, " ".join(NEEDS[k][0] for k in needs), why) if error else
                     "%s: it needs %s (%s; got mode=%r, update=%r)" % (name, " and ".join(NEEDS[k][1] for k in needs), why, a.mode, a.update))
         elif on(a) and one_rank_only and ranks > 1:
@@ -559,7 +577,7 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
           eval_every=0, eval_episodes=1, eval_envs=None, obs_filter=False, save_obs_filter=None,
           norm_reward=False, reward_clip=10.0, adv_norm="batch", perm="torch", timeout_bootstrap=False, hidden=64,
           save=None, save_every=0, save_best=None, resume=None, episode_log=None, episode_log_capacity=65536, best_window=0,
-          report=False, report_kl=False, progress=None):
+          report=False, report_kl=False, progress=None, job_obs_filter=False):
     config = run_config(**dict(locals()))  # (first statement: the arguments, nothing else)
     run = argparse.Namespace(**locals())  # the run record: the arguments and the config; build_run() and the bind step add the objects
     run.report = bool(report or report_kl or progress)  # (--report-kl and --progress imply --report)
@@ -568,12 +586,13 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
     check_train_arguments(run, world)
     if rank != 0:  # (a data-parallel job trains ONE policy, ship_sim_gym_amd/dp.py: only rank 0 logs, evaluates and saves)
         log = lambda *_, **__: None  # noqa: E731
-    ckpt = open_resume(resume, config, loop.resume_sections(RESUME_SECTIONS, obs_filter, norm_reward, episode_log), exempt=CONFIG_EXEMPT) if resume else None
+    ckpt = open_resume(resume, config, loop.resume_sections(RESUME_SECTIONS, obs_filter or job_obs_filter, norm_reward, episode_log), exempt=CONFIG_EXEMPT) if resume else None
     # build, bind, resume
     build_run(run, rank, world)
     eval_env = (ShipVecEnv(int(eval_envs or min(envs, 1024)), GameConfig, EnvConfig, device=device, n_maps=64, **dict(env_kw or {}))
                 if eval_every and rank == 0 else None)
-    run.flt, run.rflt, run.evaluator = loop.bind_env(run.env, horizon, 1, obs_filter, norm_reward, gamma, reward_clip, timeout_bootstrap, eval_env)
+    run.flt, run.rflt, run.evaluator = loop.bind_env(run.env, horizon, 1, obs_filter, norm_reward, gamma, reward_clip, timeout_bootstrap, eval_env,
+                                                     job_obs_filter=job_obs_filter)
     run.eplog, run.epwriter = loop.bind_episode_log(run.env, episode_log, episode_log_capacity, 1, resume)
     run.progress_writer = loop.open_progress(progress, resume)
     if mode in ("graph", "pingpong"):
@@ -596,6 +615,8 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         torch.cuda.synchronize()
         t_roll += time.perf_counter() - t0
         native_last_val = b.pop("last_val", None)
+        if job_obs_filter:  # every rank: gather what the ranks' rollouts added, merge it alike (the x rows were formed rank-locally)
+            run.flt.sync()
         if run.eplog is not None:
             run.eplog.append(run.shards[0].native_out)  # (the rollout's own f64 / u8 rows; no host synchronisation)
         if return_details is True:
@@ -629,6 +650,9 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         import hashlib
         print("parameter checksum after %d Adam steps: %s" % (
             run.ppo.step, hashlib.sha256(run.policy.params.detach().cpu().numpy().tobytes()).hexdigest()), flush=True)
+        if job_obs_filter:
+            print("observation filter checksum after %d rows merged: %s" % (
+                int(run.flt.count[0].item()), hashlib.sha256(run.flt.state.detach().cpu().numpy().tobytes()).hexdigest()), flush=True)
     steps = envs * horizon * max(0, updates - start)  # (this process's own; a resumed run did not step the updates it loaded)
     log("rollout (%s): %.1f M env-steps/s with the policy in the loop; whole training loop (rollout + PPO update): %.1f M env-steps/s" % (
         mode, steps / max(t_roll, 1e-9) / 1e6, steps / max(t_all, 1e-9) / 1e6))
@@ -696,6 +720,10 @@ def make_arg_parser():
                     help="--save-best compares the mean return of the last W finished episodes (the reference callback's "
                          "np.mean(y[-100:]); needs --episode-log) instead of the mean over the episodes of one update; 0 = off")
     loop.add_report_flags(ap)
+    ap.add_argument("--job-obs-filter", action="store_true",
+                    help="the running observation filter for a data-parallel job, one rank or more: every rank normalises with its own "
+                         "statistics during a rollout, and after it the ranks merge what they added, bit-identically (needs --mode native "
+                         "--update native; not together with --obs-filter)")
     ap.add_argument("--resume", default=None, metavar="FILE",
                     help="continue the run a checkpoint was saved from, bit for bit (needs --mode native --update native): repeat the "
                          "original command line; --updates stays the TOTAL and may be raised")
