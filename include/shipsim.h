@@ -1213,7 +1213,7 @@ int ssg_get_obs_filter(const ssg_handle *h, ssg_obs_filter *out /* struct_size 0
  *
  * No parity with the plain filter is claimed: with one rank, base (+) buffer is not bit for bit the running state of a filter that
  * merged the same batches one by one, because the association differs ((base (+) (b_1 (+) b_2 ...)) against ((base (+) b_1) (+) b_2 ...)).
- * Out of scope: the return filter across ranks, statistics merged per step.
+ * The return filter across ranks is exact and needs no base: "Job-wide return filter" below.  Out of scope: statistics merged per step.
  * ------------------------------------------------------------------------------------------------- */
 
 /* Replaces nothing (memory binding; the reference's counterpart is the per-worker filter buffer RLlib keeps beside the
@@ -1314,6 +1314,47 @@ int ssg_ret_filter_workspace_nbytes(int n_envs, int K, int n_members, size_t *nb
  * dev_reward_KN; workspace_nbytes below ssg_ret_filter_workspace_nbytes(n_envs, K, n_members). */
 int ssg_ret_filter_apply(ssg_handle *h, const ssg_ret_filter *f, int K, const double *dev_reward_KN, const uint8_t *dev_done_KN,
                          int64_t step_stride_envs, double *dev_reward_out_KN, double *dev_denom_KP, void *stream);
+
+/* Job-wide return filter (ABI 9 addition): the filter above for W ranks that train one policy (ssg_ppo_apply_shards)
+ * A Stable-Baselines user gets VecNormalize around the WHOLE SubprocVecEnv of train/stable_baselines/ppo.py:122-123: one running
+ * variance over the returns of all envs.  For W ranks, rank r owning n_r of the envs, that is computed exactly, because the walk above
+ * does not read the running state: a rank reduces its shard to one row per step, the ranks exchange the rows once per rollout, and
+ * every rank chains the same rows in the same order.  Job filters have one member (n_members == 1) and update (SSG_RET_FILTER_UPDATE
+ * set; a frozen filter needs no rows and stays ssg_ret_filter_apply).
+ *
+ * For rank r and k = 0 .. K-1, batch_{r,k} is the shard's n_r samples s[k][.] of the walk above, reduced exactly as above (256-row
+ * tiles, eight runs merged in tile order, the halving tree over the runs).  The rank's row k is {mean, M2, 0.0, n_r}: the state's row
+ * order with the denom slot zero.  With rows f64 [W][K][SSG_FILTER_ROWS], the ranks' rows in rank order, every rank computes
+ *     step_k    = rows[0][k] merged with rows[1][k], ..., rows[W-1][k]   (rank order, the merge above in its stated association,
+ *                                                                        starting from rows[0][k]; a row of count 0 is skipped)
+ *     state_k   = merge(state_{k-1}, step_k)
+ *     denom_k   = sqrt(M2_k / (n_k - 1)) + eps for n_k >= 2, else 1.0
+ *     out[k][e] = clamp(rew[k][e] / denom_k, -clip, +clip)               (the division above, on the rank's own envs)
+ * The carry stays with its env on its rank.  Every rank runs the same arithmetic on the same rows, so the states are bit-identical on
+ * all ranks without a broadcast, and what they hold is what one filter over all sum(n_r) envs would hold had it reduced each step's
+ * samples shard by shard.  With W = 1, step_k is the rank's own batch k: the state, carry, denoms and output are ssg_ret_filter_apply's
+ * bit for bit.  Out of scope: populations across ranks, a frozen job call, statistics merged per step over the wire. */
+
+/* Replaces: the return walk and the per-step variance update of VecNormalize.step_wait on this rank's envs (ret = ret * gamma + rews;
+ * the batch moments ret_rms.update forms; ret[news] = 0) as wrapped around the env of train/stable_baselines/ppo.py:123, for K steps: two launches on `stream`, the walk of ssg_ret_filter_apply and a
+ * grid of ceil(K / 32) workgroups that reduces the walk's tile partials to dev_rows_K4, f64 [K][SSG_FILTER_ROWS] = {mean, M2, 0.0,
+ * n_envs} per step — the bits ssg_ret_filter_apply chains.  dev_carry is updated; dev_state is neither read nor written.  The
+ * workspace is ssg_ret_filter_workspace_nbytes(n_envs, K, 1); the rows are the caller's.  Refuses (SSG_ERR_BAD_ARG, nothing launched)
+ * what ssg_ret_filter_apply refuses of the record, K, the stride, the reward and done buffers and the workspace; n_members != 1; a
+ * record without SSG_RET_FILTER_UPDATE; NULL or not 8-byte aligned rows; rows that overlap f->dev_state. */
+int ssg_ret_filter_batches(ssg_handle *h, const ssg_ret_filter *f, int K, const double *dev_reward_KN, const uint8_t *dev_done_KN,
+                           int64_t step_stride_envs, double *dev_rows_K4, void *stream);
+
+/* Replaces: the rest of that reward branch for a job (ret_rms.update's merge into the running moments with every rank's batch, and rews
+ * = clip(rews / sqrt(ret_rms.var + eps)), around the SubprocVecEnv of train/stable_baselines/ppo.py:122-123): two launches on `stream`, one workgroup that merges each step's n_rows rows in rank order
+ * and chains the K steps into f->dev_state, then the division of ssg_ret_filter_apply.  dev_rows_WK4: f64 [n_rows][K][SSG_FILTER_ROWS],
+ * the ranks' ssg_ret_filter_batches rows of these K steps in rank order.  dev_reward_KN, dev_reward_out_KN and step_stride_envs as in
+ * ssg_ret_filter_apply; dev_denom_K (nullable): f64 [K], the divisor of every row.  dev_carry and dev_gamma are not read; the denoms
+ * live in the workspace, as there.  Refuses (SSG_ERR_BAD_ARG, nothing launched) what ssg_ret_filter_apply refuses of the record, K,
+ * the stride, the reward and output buffers and the workspace; n_members != 1; a record without SSG_RET_FILTER_UPDATE; NULL or not
+ * 8-byte aligned rows; n_rows outside 1..SSG_DP_MAX_SHARDS; rows that overlap f->dev_state. */
+int ssg_ret_filter_apply_rows(ssg_handle *h, const ssg_ret_filter *f, int K, const double *dev_rows_WK4, int n_rows, const double *dev_reward_KN,
+                              int64_t step_stride_envs, double *dev_reward_out_KN, double *dev_denom_K, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Per-minibatch advantage normalisation (ABI 9 addition): PPO2's rule in the device update

@@ -74,7 +74,7 @@ EXPORTS = (
     "ssg_pop_pack_slices", "ssg_pop_set_slices", "ssg_pop_get_slices", "ssg_pop_pack_schedule_samples",
     "ssg_obs_filter_workspace_nbytes", "ssg_obs_filter_update", "ssg_set_obs_filter", "ssg_get_obs_filter",
     "ssg_set_obs_filter_buffer", "ssg_get_obs_filter_buffer", "ssg_obs_filter_update_buffered", "ssg_obs_filter_merge_rows",
-    "ssg_ret_filter_workspace_nbytes", "ssg_ret_filter_apply",
+    "ssg_ret_filter_workspace_nbytes", "ssg_ret_filter_apply", "ssg_ret_filter_batches", "ssg_ret_filter_apply_rows",
     "ssg_ppo_adv_norm_nbytes", "ssg_ppo_set_adv_norm", "ssg_ppo_get_adv_norm",
     "ssg_host_perm", "ssg_ppo_perm", "ssg_pop_perm",
     "ssg_set_timeout_boot", "ssg_get_timeout_boot", "ssg_timeout_values", "ssg_pop_timeout_values", "ssg_ppo_gae_boot", "ssg_pop_gae_boot",
@@ -338,6 +338,8 @@ def lib():
     L.ssg_obs_filter_merge_rows.argtypes = [vp, C.POINTER(ObsFilterRecord), vp, vp, C.c_int, vp]
     L.ssg_ret_filter_workspace_nbytes.argtypes = [C.c_int, C.c_int, C.c_int, szp]
     L.ssg_ret_filter_apply.argtypes = [vp, C.POINTER(RetFilterRecord), C.c_int, vp, vp, C.c_int64, vp, vp, vp]
+    L.ssg_ret_filter_batches.argtypes = [vp, C.POINTER(RetFilterRecord), C.c_int, vp, vp, C.c_int64, vp, vp]
+    L.ssg_ret_filter_apply_rows.argtypes = [vp, C.POINTER(RetFilterRecord), C.c_int, vp, C.c_int, vp, C.c_int64, vp, vp, vp]
     L.ssg_ppo_adv_norm_nbytes.argtypes = [C.c_int, szp]
     L.ssg_ppo_set_adv_norm.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
     L.ssg_ppo_get_adv_norm.argtypes = [vp, ip, ip]

@@ -2690,19 +2690,21 @@ int ssg_ret_filter_workspace_nbytes(int n_envs, int K, int n_members, size_t *nb
     return SSG_OK;
 }
 
-int ssg_ret_filter_apply(ssg_handle *h, const ssg_ret_filter *f, int K, const double *dev_reward_KN, const uint8_t *dev_done_KN,
-                         int64_t step_stride_envs, double *dev_reward_out_KN, double *dev_denom_KP, void *stream)
+// What the three launching calls ask of their record, in ssg_ret_filter_apply's order, up to the buffers (which differ): the record, K and
+// the stride.  job: ssg_ret_filter_batches / ssg_ret_filter_apply_rows, which serve one updating member.  lay: the launch's layout.
+static int check_ret_filter(ssg_handle *h, const ssg_ret_filter *f, int K, int64_t step_stride_envs, const std::string &w, bool job,
+                            ssg::MemberLayout &lay)
 {
-    const std::string w("ssg_ret_filter_apply");
-    char buf[200];
     if (!h) return fail(nullptr, SSG_ERR_BAD_ARG, w + ": NULL handle");
     if (!f) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL ssg_ret_filter");
     if (f->struct_size != sizeof(ssg_ret_filter)) return fail(h, SSG_ERR_BAD_ARG, w + ": ssg_ret_filter.struct_size != sizeof(ssg_ret_filter)");
     if (f->flags & ~SSG_RET_FILTER_UPDATE) return fail(h, SSG_ERR_BAD_ARG, w + ": unknown bit in ssg_ret_filter.flags");
     const int P = f->n_members, N = h->cfg.n_envs;
     if (P < 1 || P > SSG_POP_MAX_MEMBERS) return fail(h, SSG_ERR_BAD_ARG, w + ": n_members must be in 1..SSG_POP_MAX_MEMBERS");
-    ssg::MemberLayout lay;
-    int rc = member_layout(h, P, "ssg_ret_filter_apply", true, lay); // (asked for one member too, which then runs on the whole handle)
+    if (job && P != 1) return fail(h, SSG_ERR_BAD_ARG, w + ": a job-wide filter has one member (n_members != 1)");
+    if (job && !(f->flags & SSG_RET_FILTER_UPDATE))
+        return fail(h, SSG_ERR_BAD_ARG, w + ": the record is frozen (SSG_RET_FILTER_UPDATE clear): a frozen filter needs no rows, call ssg_ret_filter_apply");
+    int rc = member_layout(h, P, w.c_str(), true, lay); // (asked for one member too, which then runs on the whole handle)
     if (rc != SSG_OK) return rc;
     if (P == 1) lay = whole_layout(h);
     if (!(f->clip >= 0.0) || !(f->eps >= 0.0)) return fail(h, SSG_ERR_BAD_ARG, w + ": clip and eps must be >= 0 (and not NaN)");
@@ -2710,18 +2712,24 @@ int ssg_ret_filter_apply(ssg_handle *h, const ssg_ret_filter *f, int K, const do
         return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_gamma, dev_state, dev_carry or dev_workspace");
     if (K < 1 || K > SSG_RET_FILTER_MAX_STEPS) return fail(h, SSG_ERR_BAD_ARG, w + ": K must be in 1..SSG_RET_FILTER_MAX_STEPS");
     if (step_stride_envs < N) return fail(h, SSG_ERR_BAD_ARG, w + ": step_stride_envs < n_envs");
-    if (!dev_reward_KN || !dev_done_KN || !dev_reward_out_KN) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL reward, done or output buffer");
-    if (dev_reward_out_KN == dev_reward_KN) return fail(h, SSG_ERR_BAD_ARG, w + ": the output buffer must not be the reward buffer");
-    const size_t need = ssg::ret_filter_workspace_bytes(N, K, P);
+    return SSG_OK;
+}
+
+// ... and after the buffers: the workspace, then the handle's state blob
+static int check_ret_filter_workspace(ssg_handle *h, const ssg_ret_filter *f, int K, const std::string &w)
+{
+    char buf[200];
+    const size_t need = ssg::ret_filter_workspace_bytes(h->cfg.n_envs, K, f->n_members);
     if (f->workspace_nbytes < need) {
         std::snprintf(buf, sizeof buf, ": workspace_nbytes %zu < %zu (ssg_ret_filter_workspace_nbytes)", f->workspace_nbytes, need);
         return fail(h, SSG_ERR_BAD_ARG, w + buf);
     }
-    rc = check_ready(h, false);
-    if (rc != SSG_OK) return rc;
-    ssg::RetFilterLaunch l;
-    l.rew = dev_reward_KN;
-    l.done = dev_done_KN;
+    return check_ready(h, false);
+}
+
+static ssg::RetFilterLaunch ret_filter_launch(const ssg_ret_filter *f, int K, int64_t step_stride_envs, const ssg::MemberLayout &lay)
+{
+    ssg::RetFilterLaunch l{};
     l.K = K;
     l.stride = (size_t)step_stride_envs;
     l.lay = lay;
@@ -2732,10 +2740,79 @@ int ssg_ret_filter_apply(ssg_handle *h, const ssg_ret_filter *f, int K, const do
     l.state = f->dev_state;
     l.carry = f->dev_carry;
     l.workspace = f->dev_workspace;
+    return l;
+}
+
+int ssg_ret_filter_apply(ssg_handle *h, const ssg_ret_filter *f, int K, const double *dev_reward_KN, const uint8_t *dev_done_KN,
+                         int64_t step_stride_envs, double *dev_reward_out_KN, double *dev_denom_KP, void *stream)
+{
+    const std::string w("ssg_ret_filter_apply");
+    ssg::MemberLayout lay;
+    int rc = check_ret_filter(h, f, K, step_stride_envs, w, false, lay);
+    if (rc != SSG_OK) return rc;
+    if (!dev_reward_KN || !dev_done_KN || !dev_reward_out_KN) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL reward, done or output buffer");
+    if (dev_reward_out_KN == dev_reward_KN) return fail(h, SSG_ERR_BAD_ARG, w + ": the output buffer must not be the reward buffer");
+    rc = check_ret_filter_workspace(h, f, K, w);
+    if (rc != SSG_OK) return rc;
+    ssg::RetFilterLaunch l = ret_filter_launch(f, K, step_stride_envs, lay);
+    l.rew = dev_reward_KN;
+    l.done = dev_done_KN;
     l.out = dev_reward_out_KN;
     l.denom_out = dev_denom_KP;
     hipError_t e = ssg::launch_ret_filter(l, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("return filter launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+// the rows of a job-wide call, f64 [n_rows][K][SSG_FILTER_ROWS], against the record's state: the chain reads them while it writes the state
+static int check_ret_filter_rows(ssg_handle *h, const ssg_ret_filter *f, int K, const double *dev_rows, int n_rows, const std::string &w)
+{
+    if (!dev_rows) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL rows");
+    if (reinterpret_cast<uintptr_t>(dev_rows) % 8 != 0) return fail(h, SSG_ERR_BAD_ARG, w + ": the rows must be 8-byte aligned");
+    if (n_rows < 1 || n_rows > SSG_DP_MAX_SHARDS) return fail(h, SSG_ERR_BAD_ARG, w + ": n_rows must be in 1..SSG_DP_MAX_SHARDS");
+    const uintptr_t st = reinterpret_cast<uintptr_t>(f->dev_state), st_bytes = SSG_FILTER_ROWS * sizeof(double);
+    const uintptr_t r0 = reinterpret_cast<uintptr_t>(dev_rows), r_bytes = (uintptr_t)n_rows * (uintptr_t)K * SSG_FILTER_ROWS * sizeof(double);
+    if (r0 < st + st_bytes && st < r0 + r_bytes) return fail(h, SSG_ERR_BAD_ARG, w + ": the rows overlap the filter's dev_state");
+    return SSG_OK;
+}
+
+int ssg_ret_filter_batches(ssg_handle *h, const ssg_ret_filter *f, int K, const double *dev_reward_KN, const uint8_t *dev_done_KN,
+                           int64_t step_stride_envs, double *dev_rows_K4, void *stream)
+{
+    const std::string w("ssg_ret_filter_batches");
+    ssg::MemberLayout lay;
+    int rc = check_ret_filter(h, f, K, step_stride_envs, w, true, lay);
+    if (rc != SSG_OK) return rc;
+    if (!dev_reward_KN || !dev_done_KN) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL reward or done buffer");
+    rc = check_ret_filter_rows(h, f, K, dev_rows_K4, 1, w);
+    if (rc == SSG_OK) rc = check_ret_filter_workspace(h, f, K, w);
+    if (rc != SSG_OK) return rc;
+    ssg::RetFilterLaunch l = ret_filter_launch(f, K, step_stride_envs, lay);
+    l.rew = dev_reward_KN;
+    l.done = dev_done_KN;
+    hipError_t e = ssg::launch_ret_filter_batches(l, dev_rows_K4, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("return filter batches launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+int ssg_ret_filter_apply_rows(ssg_handle *h, const ssg_ret_filter *f, int K, const double *dev_rows_WK4, int n_rows, const double *dev_reward_KN,
+                              int64_t step_stride_envs, double *dev_reward_out_KN, double *dev_denom_K, void *stream)
+{
+    const std::string w("ssg_ret_filter_apply_rows");
+    ssg::MemberLayout lay;
+    int rc = check_ret_filter(h, f, K, step_stride_envs, w, true, lay);
+    if (rc != SSG_OK) return rc;
+    if (!dev_reward_KN || !dev_reward_out_KN) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL reward or output buffer");
+    if (dev_reward_out_KN == dev_reward_KN) return fail(h, SSG_ERR_BAD_ARG, w + ": the output buffer must not be the reward buffer");
+    rc = check_ret_filter_rows(h, f, K, dev_rows_WK4, n_rows, w);
+    if (rc == SSG_OK) rc = check_ret_filter_workspace(h, f, K, w);
+    if (rc != SSG_OK) return rc;
+    ssg::RetFilterLaunch l = ret_filter_launch(f, K, step_stride_envs, lay);
+    l.rew = dev_reward_KN;
+    l.out = dev_reward_out_KN;
+    l.denom_out = dev_denom_K;
+    hipError_t e = ssg::launch_ret_filter_rows(l, dev_rows_WK4, n_rows, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("return filter rows launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
 

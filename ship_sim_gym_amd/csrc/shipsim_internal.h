@@ -489,6 +489,11 @@ struct RetFilterLaunch {
     double *denom_out;   // nullable: f64 [K][members]
 };
 hipError_t launch_ret_filter(const RetFilterLaunch &l, hipStream_t stream);
+// The job-wide filter's two calls, one member (lay: the whole handle).  batches: the walk, then rows f64 [K][SSG_FILTER_ROWS], the shard's
+// {mean, M2, 0, n} per step; state, out and denom_out are not read.  rows: the chain over rows f64 [n_rows][K][SSG_FILTER_ROWS] into the
+// state, then the division; done, gamma and carry are not read.  The workspace is launch_ret_filter's.
+hipError_t launch_ret_filter_batches(const RetFilterLaunch &l, double *rows, hipStream_t stream);
+hipError_t launch_ret_filter_rows(const RetFilterLaunch &l, const double *rows, int n_rows, hipStream_t stream);
 // the episode log (shipsim_eplog.hip): the workspace holds int64 [2] (the head before the call, the call's count), then the counts of
 // every (row, 256-env tile), int32 [K][filter_tiles(n_envs)], scanned in place
 size_t episode_log_workspace_bytes(int n_envs, int K);

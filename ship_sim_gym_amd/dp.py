@@ -18,7 +18,10 @@ the two device steps in numpy, operation for operation.
 The observation filter of such a job is ship_sim_gym_amd/obs_filter.py's ``ObsFilter(job=True)``: rank-local during a rollout,
 synchronised after it by the same pattern (gathered buffers, the same merge on every rank).
 
-Out of scope: adv_norm="minibatch" across ranks, the return filter's statistics across ranks, resuming a multi-rank run,
+The return filter of such a job is ship_sim_gym_amd/ret_filter.py's ``ReturnFilter(job=True)``: ``gae`` hands it the group, the
+ranks gather one [K, 4] block of per-step rows per rollout and chain them alike, which is exact: one filter over all the job's envs.
+
+Out of scope: adv_norm="minibatch" across ranks, resuming a multi-rank run,
 populations across ranks, overlapping the gather with the next gradient, running this loop from C.
 """
 import ctypes as C
@@ -143,6 +146,14 @@ def apply_reference(rows, counts, params, adam_mv, step, hp, max_grad_norm=0.0, 
     return {"g": g, "norm": norm, "coef": f32(coef), "params": p2, "adam_mv": mv2, "stats": stats, "klacc": klacc, "kl_coef": kl_out}
 
 
+def check_return_filter(return_filter, world):
+    """Which return filters serve a job of `world` ranks: a job filter any, a plain one only a job of one rank — with more, the
+    statistics it divides by would be the rank's own (ValueError, on every rank alike)."""
+    if return_filter is not None and int(world) > 1 and not getattr(return_filter, "job", False):
+        raise ValueError("DataParallelPPO.gae: a plain ReturnFilter in a job of %d ranks would normalise by this rank's statistics, not "
+                         "the job's: make it with ReturnFilter(env, job=True)" % int(world))
+
+
 # ------------------------------------------------------------------------------------------------------------------------------------
 class DataParallelPPO(NativePPO):
     """NativePPO over this rank's shard of a W-rank job.  group: the process group (None: the default one; with none initialised the
@@ -212,8 +223,15 @@ class DataParallelPPO(NativePPO):
             N.check(N.lib().ssg_ppo_set_adv_moments(h, int(rows.shape[0]), C.c_void_p(rows.data_ptr()), float(self.hp.adv_eps), ws, nb,
                                                     self._stream()), h, "ssg_ppo_set_adv_moments")
 
+    def _apply_return_filter(self, return_filter, batch):
+        if getattr(return_filter, "job", False):
+            return return_filter.apply(batch, self.group)
+        return return_filter.apply(batch)
+
     def gae(self, batch, gamma=0.99, lam=0.95, return_filter=None):
-        """NativePPO.gae on the shard, then the job-wide advantage statistics: the shards' moments gathered and set."""
+        """NativePPO.gae on the shard, then the job-wide advantage statistics: the shards' moments gathered and set.  return_filter: a
+        job filter (``ReturnFilter(job=True)``) is handed this job's group; a plain one is refused with more than one rank."""
+        check_return_filter(return_filter, self.world)
         out = super(DataParallelPPO, self).gae(batch, gamma, lam, return_filter)
         if int(batch["adv"].shape[0]) * sum(self.shard_envs) < 2:
             raise ValueError("DataParallelPPO.gae: the job has fewer than 2 samples: no unbiased std")

@@ -398,7 +398,7 @@ class NativePPO(DeviceTrainer):
         boot goes in as it is, with a return filter too (the value network already lives in normalised-return units)."""
         torch = _torch()
         if return_filter is not None:
-            return_filter.apply(batch)
+            self._apply_return_filter(return_filter, batch)
         rew, done, val, last = (self._flat(batch, "rew" if return_filter is None else "rew_norm", torch.float64), self._flat(batch, "done", torch.uint8),
                                 self._flat(batch, "val", torch.float32), self._flat(batch, "last_val", torch.float32))
         K, n_env = int(rew.shape[0]), int(rew.shape[1])
@@ -422,6 +422,10 @@ class NativePPO(DeviceTrainer):
                                            C.c_void_p(ret.data_ptr()), ws, nb, self._stream()), h, name)
         batch["adv"], batch["ret"] = adv, ret
         return adv, ret
+
+    def _apply_return_filter(self, return_filter, batch):
+        """gae()'s first step (DataParallelPPO decides which filters serve a job, and hands them its process group)."""
+        return_filter.apply(batch)
 
     def adv_stats(self):
         """f32 [3] device view: the advantage mean, std + adv_eps and its inverse, as the last gae() left them."""

@@ -10,17 +10,23 @@ of a population when there are several, for a whole rollout's [K, N] reward buff
 in include/shipsim.h (section "Return filter") on its own terms; no bit parity with Stable-Baselines is claimed (it uses the
 population variance and sqrt(var + eps)).
 
-Not covered: merging the statistics of several handles or GPUs, and the torch-mode trainers.
+``ReturnFilter(..., job=True)`` is the filter of one rank of a data-parallel job (ship_sim_gym_amd/dp.py): the statistics are the
+job's, those of one ``VecNormalize`` around the envs of all ranks, step by step.  A rank reduces its shard to one (mean, M2, count) row
+per step (``shard_rows``), the ranks gather the rows once per rollout, and every rank chains the same rows in the same order
+(``apply_rows``), so the states agree bit for bit without a broadcast; with one rank the result is the plain filter's bit for bit
+(include/shipsim.h, "Job-wide return filter").
+
+Not covered: the torch-mode trainers, populations across ranks, a frozen job call (a frozen filter needs no rows: ``apply`` serves it).
 
 ``ret_filter_reference`` is a numpy restatement of the device's arithmetic, the same walk and reduction order operation for operation,
-for tests.
+for tests; ``batch_rows_reference`` and ``job_reference`` restate the two halves of the job-wide call.
 """
 import ctypes as C
 
 import numpy as np
 
 from . import _native as N
-from .obs_filter import merge_reference
+from .obs_filter import _merge, merge_reference
 
 
 def _torch():
@@ -62,6 +68,51 @@ def ret_filter_reference(state_rows, carry, rew, done, gamma, clip=10.0, eps=1e-
     return st[:, 0].copy(), c, out, denoms
 
 
+def batch_rows_reference(carry, rew, done, gamma):
+    """What ssg_ret_filter_batches leaves for one rank: carry f64 [n], rew f64 [K, n], done [K, n], gamma a float.  The walk of
+    ``ret_filter_reference``; step k's n samples are reduced in the device's order (``obs_filter.merge_reference`` into an empty state
+    at D = 1) to the row {mean, M2, 0.0, n}.  Returns (rows f64 [K, 4], carry [n])."""
+    c = np.array(carry, dtype=np.float64).reshape(-1)
+    rew = np.asarray(rew, dtype=np.float64)
+    done = np.asarray(done)
+    if rew.ndim != 2 or rew.shape[1] != c.shape[0] or done.shape != rew.shape or rew.shape[1] < 1:
+        raise ValueError("batch_rows_reference: rew and done must be [K, n] and carry [n >= 1]")
+    g = np.float64(gamma)
+    rows = np.zeros((rew.shape[0], N.FILTER_ROWS))
+    empty = np.zeros((N.FILTER_ROWS, 1))
+    for k in range(rew.shape[0]):
+        prod = c * g
+        c = prod + rew[k]
+        st = merge_reference(empty, c[:, None], eps=0.0)
+        rows[k] = st[0, 0], st[1, 0], 0.0, st[3, 0]
+        c = np.where(done[k] != 0, 0.0, c)
+    return rows, c
+
+
+def job_reference(state_rows, rows, eps=1e-8):
+    """What ssg_ret_filter_apply_rows leaves in the state, and its denoms: state_rows f64 [4] (mean, M2, denom, count), rows f64
+    [W, K, 4] (the ranks' rows of ``batch_rows_reference`` in rank order).  For every k: step_k = rows[0][k] merged with rows[1][k],
+    ..., rows[W - 1][k] in the header's association, a row of count 0 skipped; state_k = state_{k-1} merged with step_k; denom_k from
+    state_k, a denom of 0 dividing by 1.  Returns (state [4], denoms [K]); the square roots are numpy's (the device's may differ in
+    the last bit)."""
+    st = np.array(state_rows, dtype=np.float64).reshape(N.FILTER_ROWS)
+    rows = np.array(rows, dtype=np.float64)
+    if rows.ndim != 3 or rows.shape[0] < 1 or rows.shape[1] < 1 or rows.shape[2] != N.FILTER_ROWS:
+        raise ValueError("job_reference: rows must be [W >= 1, K >= 1, 4]")
+    eps = np.float64(eps)
+    s = (np.float64(st[3]), np.float64(st[0]), np.float64(st[1]))
+    denoms = np.empty(rows.shape[1])
+    den = st[2]
+    for k in range(rows.shape[1]):
+        a = (np.float64(rows[0, k, 3]), np.float64(rows[0, k, 0]), np.float64(rows[0, k, 1]))
+        for r in rows[1:, k]:
+            a = _merge(a, (np.float64(r[3]), np.float64(r[0]), np.float64(r[1])))
+        s = _merge(s, a)
+        den = np.sqrt(s[2] / (s[0] - 1.0)) + eps if s[0] >= 2.0 else np.float64(1.0)
+        denoms[k] = 1.0 if den == 0.0 else den
+    return np.array([s[1], s[2], den, s[0]], dtype=np.float64), denoms
+
+
 class ReturnFilter(object):
     """The return filter of `env` (a ShipVecEnv): owns the state tensor f64 [n_members, 4] (mean, M2, denom, count per member; zeros =
     empty, which divides by 1), the per-env carry f64 [N] (the discounted return in flight), the members' discounts on the device and
@@ -71,9 +122,14 @@ class ReturnFilter(object):
     (``train(flag)`` changes it later; ``VecNormalize.training``).
 
     Nothing is bound to the env: call ``apply(batch)`` on a rollout's batch, or hand the filter to ``gae`` of NativePPO /
-    PopulationPPO.  Call ``reset_carry()`` after resetting the envs by hand."""
+    PopulationPPO.  Call ``reset_carry()`` after resetting the envs by hand.
 
-    def __init__(self, env, n_members=1, gamma=0.99, clip=10.0, eps=1e-8, update=True):
+    job=True (one member only): the filter of one rank of a data-parallel job (include/shipsim.h, "Job-wide return filter").  The state
+    is the job's; the carry stays this rank's envs'.  ``apply(batch, group)`` is ``shard_rows`` (the walk and this shard's row per
+    step), one all-gather of the rows, then ``apply_rows`` (the chain over the gathered rows and the division); the two halves are
+    public so that one process can replay a W-rank job with ``torch.stack`` of the shards' rows as the gather."""
+
+    def __init__(self, env, n_members=1, gamma=0.99, clip=10.0, eps=1e-8, update=True, job=False):
         torch = _torch()
         P = int(n_members)
         clip, eps = float(clip), float(eps)
@@ -81,6 +137,9 @@ class ReturnFilter(object):
             raise ValueError("ReturnFilter: n_members must be in 1..%d" % N.POP_MAX_MEMBERS)
         if not clip >= 0.0 or not eps >= 0.0:
             raise ValueError("ReturnFilter: clip and eps must be >= 0")
+        if job and P != 1:
+            raise ValueError("ReturnFilter: a job filter has one member (populations across ranks are out of scope; got n_members=%d)" % P)
+        self.job = bool(job)
         self.env, self.n_members, self.clip, self.eps, self.updating = env, P, clip, eps, bool(update)
         dev = env.device
         self.state = torch.zeros((P, N.FILTER_ROWS), dtype=torch.float64, device=dev)
@@ -182,9 +241,80 @@ class ReturnFilter(object):
                                                      C.c_void_p(denom[k0].data_ptr()), env._stream()), env._h, "ssg_ret_filter_apply")
         return out, denom
 
-    def apply(self, batch):
+    def _job_buffers(self, who, rew, done=None):
+        """(K, row pitch) of a job call's [K, N] buffers, checked as ``normalise`` checks its own."""
+        torch = _torch()
+        env = self.env
+        n_env = int(env.num_envs)
+        if not self.job:
+            raise ValueError("ReturnFilter.%s: this filter was not made with job=True (its statistics are this handle's: use apply)" % who)
+        if not self.updating:
+            raise ValueError("ReturnFilter.%s: a frozen filter needs no rows (apply divides by the state's own denom)" % who)
+        for name, t, dt in (("rew", rew, torch.float64), ("done", done, torch.uint8)):
+            if t is None:
+                continue
+            if t.dtype != dt or t.device != env.device or t.dim() != 2 or int(t.shape[1]) != n_env or int(t.shape[0]) < 1 or \
+                    t.stride(1) != 1 or t.stride(0) < n_env:
+                raise ValueError("ReturnFilter.%s: %s must be a %s tensor [K, %d] on %s with unit-stride rows (got %s %s, strides %s, on %s)"
+                                 % (who, name, dt, n_env, env.device, t.dtype, tuple(t.shape), tuple(t.stride()), t.device))
+        K, pitch = int(rew.shape[0]), int(rew.stride(0))
+        if done is not None and (int(done.shape[0]) != K or int(done.stride(0)) != pitch):
+            raise ValueError("ReturnFilter.%s: rew and done must have the same number of rows and the same row pitch" % who)
+        return K, pitch
+
+    def shard_rows(self, batch):
+        """The first half of a job filter's ``apply`` (ssg_ret_filter_batches): walk batch["rew"] / batch["done"] (the carry is
+        updated) and reduce this rank's envs to one row {mean, M2, 0, n} per step.  Returns the rows, f64 [K, 4] on the device; the
+        state is neither read nor written.  Rollouts longer than the library's cap are served in several calls."""
+        torch = _torch()
+        env = self.env
+        rew, done = batch["rew"], batch["done"]
+        K, pitch = self._job_buffers("shard_rows", rew, done)
+        rows = torch.empty((K, N.FILTER_ROWS), dtype=torch.float64, device=env.device)
+        rec = self.to_native(min(K, N.RET_FILTER_MAX_STEPS))
+        with torch.cuda.device(env.device):
+            for k0 in range(0, K, N.RET_FILTER_MAX_STEPS):
+                k1 = min(K, k0 + N.RET_FILTER_MAX_STEPS)
+                N.check(N.lib().ssg_ret_filter_batches(env._h, C.byref(rec), k1 - k0, C.c_void_p(rew[k0].data_ptr()),
+                                                       C.c_void_p(done[k0].data_ptr()), pitch, C.c_void_p(rows[k0].data_ptr()),
+                                                       env._stream()), env._h, "ssg_ret_filter_batches")
+        return rows
+
+    def apply_rows(self, batch, rows):
+        """The second half (ssg_ret_filter_apply_rows): rows f64 [W, K, 4] on the filter's device, the ranks' ``shard_rows`` of this
+        rollout in rank order (W in 1..64).  Every step's W rows are merged in rank order and chained into the state, and
+        batch["rew"] is divided by the chain's denoms: writes batch["rew_norm"] (f64 [K, N]) and batch["rew_denom"] (f64 [K, 1]).
+        Returns batch["rew_norm"]."""
+        torch = _torch()
+        env = self.env
+        rew = batch["rew"]
+        K, pitch = self._job_buffers("apply_rows", rew)
+        if (rows.dtype != torch.float64 or rows.device != self.state.device or rows.dim() != 3 or not 1 <= int(rows.shape[0]) <= N.DP_MAX_SHARDS
+                or tuple(rows.shape[1:]) != (K, N.FILTER_ROWS)):
+            raise ValueError("ReturnFilter.apply_rows: rows must be a float64 tensor (W in 1..%d, %d, %d) on %s (got %s %s on %s)"
+                             % (N.DP_MAX_SHARDS, K, N.FILTER_ROWS, self.state.device, rows.dtype, tuple(rows.shape), rows.device))
+        W = int(rows.shape[0])
+        n_env = int(env.num_envs)
+        out = torch.empty((K, pitch), dtype=torch.float64, device=env.device)[:, :n_env]
+        denom = torch.empty((K, 1), dtype=torch.float64, device=env.device)
+        rec = self.to_native(min(K, N.RET_FILTER_MAX_STEPS))
+        with torch.cuda.device(env.device):
+            for k0 in range(0, K, N.RET_FILTER_MAX_STEPS):
+                k1 = min(K, k0 + N.RET_FILTER_MAX_STEPS)
+                part = rows[:, k0:k1].contiguous()  # (the ranks' rows of this call's steps, [W, k1 - k0, 4]; the whole tensor when K fits)
+                N.check(N.lib().ssg_ret_filter_apply_rows(env._h, C.byref(rec), k1 - k0, C.c_void_p(part.data_ptr()), W,
+                                                          C.c_void_p(rew[k0].data_ptr()), pitch, C.c_void_p(out[k0].data_ptr()),
+                                                          C.c_void_p(denom[k0].data_ptr()), env._stream()), env._h, "ssg_ret_filter_apply_rows")
+        batch["rew_norm"], batch["rew_denom"] = out, denom
+        return out
+
+    def apply(self, batch, group=None):
         """Normalise a rollout batch's rewards: writes batch["rew_norm"] (f64 [K, N]) and batch["rew_denom"] (f64 [K, n_members]) and
-        leaves batch["rew"] alone.  Returns batch["rew_norm"]."""
+        leaves batch["rew"] alone.  Returns batch["rew_norm"].  An updating job filter: ``shard_rows``, one all-gather of the rows
+        over `group` (None: the default process group; with none initialised the job is this process, W = 1), then ``apply_rows``."""
+        if self.job and self.updating:
+            from .sharding import all_gather_rows
+            return self.apply_rows(batch, all_gather_rows(self.shard_rows(batch), group))
         batch["rew_norm"], batch["rew_denom"] = self.normalise(batch["rew"], batch["done"])
         return batch["rew_norm"]
 

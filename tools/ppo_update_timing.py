@@ -10,6 +10,7 @@ line on stdout.  The kernels alone: `rocprofv3 --kernel-trace --stats -- python 
 
     python tools/ppo_update_timing.py [--configs 65536x32,4096x64] [--repeats 7] [--only torch|native] [--ext] [--separate-value] [--ret-filter]
                                       [--adv-norm] [--perm] [--timeout-bootstrap] [--checkpoint] [--dp] [--episode-log] [--report]
+                                      [--ret-filter-job]
 
 --ext adds, in the same run, the extended update (NativePPO with vf_clip 0.2, max_grad_norm 0.5, kl_coef 1.0, kl_target 0.01: GAE, the
 ssg_ppo_dist launch, ssg_ppo_update_ext) as the path "native_ext", and the ssg_ppo_dist launch alone as "dist".
@@ -42,6 +43,12 @@ alone) and "native_eplog" (the append, then the whole GAE + update), to set agai
 ssg_ppo_report, two launches, with the stats rows of an update), "report_post" (the same with the post-update group: one ssg_ppo_dist
 launch more), "gae_only" (ssg_ppo_gae alone, the yardstick) and "native_report" (the whole GAE + update with stats rows, then the report
 without the post group), to set against "native".
+--ret-filter-job adds, in the same run and alternating with the others, the job-wide return filter (``ReturnFilter(job=True)``) on one
+device: "ret_apply_plain" (ssg_ret_filter_apply updating: three launches) against "ret_apply_split" (the split call at W = 1: shard_rows,
+a gather that is a no-op, apply_rows: four launches); "ret_apply_rows_w1" / "_w2" / "_w8" (apply_rows alone on 1, 2 and 8 stacked
+rows: two launches); and the whole GAE + update with each filter, "native_ret_plain" and "native_ret_job".  With this flag every timed
+path follows one untimed GAE over the batch, so that all have the same predecessor.  The gather over real links is not part of
+any of them.
 """
 import argparse
 import importlib.util
@@ -97,7 +104,7 @@ def _wall_ms(fn):
 
 def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext=False, separate_value=False, ret_filter=False,
             adv_norm=False, perm=False, timeout_bootstrap=False, checkpoint=False, checkpoint_dir=None, dp=False, episode_log=False,
-            report=False):
+            report=False, ret_filter_job=False):
     from ship_sim_gym_amd.policy import NativePolicy
     from ship_sim_gym_amd.ppo import NativePPO
     torch.manual_seed(0)
@@ -228,13 +235,30 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
         rfrozen.state.copy_(rflt.state)  # (whatever it holds: the frozen call's cost does not depend on it)
         paths += [("gae", lambda: ppo.gae(dict(b))), ("ret_gae", lambda: ppo.gae(dict(b), return_filter=rflt)),
                   ("ret_frozen", lambda: rfrozen.apply(dict(b))), ("ret_apply", lambda: rflt.apply(dict(b))), ("native_ret", run_native_ret)]
+    if ret_filter_job:  # (the filters' states keep running from call to call, as in training: the cost does not depend on them)
+        rplain, rjob = ReturnFilter(env), ReturnFilter(env, job=True)
+        own = rjob.shard_rows(dict(b))
+
+        def rows_alone(W):
+            f, rows = ReturnFilter(env, job=True), torch.stack([own] * W)
+            return lambda: f.apply_rows(dict(b), rows)
+        paths += [("ret_apply_plain", lambda: rplain.apply(dict(b))), ("ret_apply_split", lambda: rjob.apply(dict(b)))]
+        paths += [("ret_apply_rows_w%d" % W, rows_alone(W)) for W in (1, 2, 8)]
+        paths += [("native_ret_plain", native_path(ppo, seeded(), return_filter=rplain)), ("native_ret_job", native_path(ppo, seeded(), return_filter=rjob))]
+        # What ran before a path shows in it: the path after a whole update, whichever it is, measured 15 .. 40 us more.  So here every
+        # path follows one untimed GAE over the batch; the two whole updates still differ by their order (profiles/ret_filter_job/).
+        spacer = lambda: ppo.gae(dict(b))  # noqa: E731
+    else:
+        spacer = lambda: None  # noqa: E731
     times = {k: [] for k, _ in paths}
     timer = {"checkpoint_save": _wall_ms}  # (a save is host work: HIP events would bracket only its copies)
     for _ in range(2):
         for k, f in paths:
+            spacer()
             timer.get(k, _timed)(f)
     for _ in range(repeats):
         for k, f in paths:
+            spacer()
             times[k].append(timer.get(k, _timed)(f))
     peaks = {"perm_torch_peak_bytes": _peak_bytes(draw_torch), "perm_native_peak_bytes": _peak_bytes(draw_native)} if perm else {}
     env.close()
@@ -275,11 +299,14 @@ def main():
                                                                "alone, and the whole GAE + update with the append ahead of it")
     ap.add_argument("--report", action="store_true", help="also time the update report alone (without and with the post-update group), GAE "
                                                           "alone, and the whole GAE + update with the report behind it")
+    ap.add_argument("--ret-filter-job", action="store_true", help="also time the job-wide return filter on one device: the split call at "
+                                                                  "W = 1 against ssg_ret_filter_apply, apply_rows alone on 1, 2 and 8 "
+                                                                  "stacked rows, and the whole GAE + update with each")
     a = ap.parse_args()
     mod = _ppo()
     res = [measure(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.repeats, a.only, "cuda:0", ext=a.ext, separate_value=sep, ret_filter=a.ret_filter,
                    adv_norm=a.adv_norm, perm=a.perm, timeout_bootstrap=a.timeout_bootstrap, checkpoint=a.checkpoint,
-                   checkpoint_dir=a.checkpoint_dir, dp=a.dp, episode_log=a.episode_log, report=a.report)
+                   checkpoint_dir=a.checkpoint_dir, dp=a.dp, episode_log=a.episode_log, report=a.report, ret_filter_job=a.ret_filter_job)
            for c in a.configs.split(",") for sep in ([False, True] if a.separate_value else [False])]
     print(json.dumps({"ppo_update_timing": res}))
 

@@ -46,8 +46,8 @@ def check_flag_values(a, error):
     """The value checks both command lines share (a: the parsed arguments; error: the parser's, which exits)."""
     if a.eval_every < 0 or a.eval_episodes < 1:
         error("--eval-every must be >= 0 and --eval-episodes >= 1")
-    if a.reward_clip != 10.0 and not a.norm_reward:
-        error("--reward-clip needs --norm-reward")
+    if a.reward_clip != 10.0 and not (a.norm_reward or getattr(a, "job_norm_reward", False)):
+        error("--reward-clip needs --norm-reward" + (" or --job-norm-reward" if hasattr(a, "job_norm_reward") else ""))
     if not a.reward_clip >= 0.0:
         error("--reward-clip must be >= 0")
     if a.save_every < 0:
@@ -61,11 +61,12 @@ def check_flag_values(a, error):
 
 
 def bind_env(env, horizon, n_members=1, obs_filter=False, norm_reward=False, gamma=0.99, reward_clip=10.0, timeout_bootstrap=False,
-             eval_env=None, job_obs_filter=False):
+             eval_env=None, job_obs_filter=False, job_norm_reward=False):
     """Bind what the configuration asks for to a training env of n_members members; returns (obs filter, return filter, evaluator), None
     where off.  The obs filter is bound to the env (the rollout merges each step's rows, then normalises) and, frozen, to eval_env —
     job_obs_filter: the job-wide one, with its buffer, which the caller synchronises after every rollout; the
-    bootstrap makes the rollout return "boot", which gae() reads; the return filter is applied per rollout, between the rollout and GAE."""
+    bootstrap makes the rollout return "boot", which gae() reads; the return filter is applied per rollout, between the rollout and GAE —
+    job_norm_reward: the job-wide one, whose rows gae() gathers over the ranks."""
     flt = rflt = evaluator = None
     if obs_filter or job_obs_filter:
         from ship_sim_gym_amd.obs_filter import ObsFilter
@@ -73,9 +74,9 @@ def bind_env(env, horizon, n_members=1, obs_filter=False, norm_reward=False, gam
         env.set_obs_filter(flt)
     if timeout_bootstrap:
         env.set_timeout_bootstrap(True, rows=horizon)
-    if norm_reward:
+    if norm_reward or job_norm_reward:
         from ship_sim_gym_amd.ret_filter import ReturnFilter
-        rflt = ReturnFilter(env, n_members=n_members, gamma=gamma, clip=reward_clip)
+        rflt = ReturnFilter(env, n_members=n_members, gamma=gamma, clip=reward_clip, job=bool(job_norm_reward))
     if eval_env is not None:  # an env of its own: evaluation resets and steps it, the training envs keep their episodes
         from ship_sim_gym_amd.evaluate import NativeEvaluator
         evaluator = NativeEvaluator(eval_env)

@@ -8,7 +8,7 @@ leave the GPU; the policy is a small MLP in fp32.
                               [--eval-every U --eval-episodes E] [--obs-filter [--save-obs-filter FILE]]
                               [--norm-reward [--reward-clip C]]
                               [--save FILE [--save-every U]] [--save-best FILE] [--resume FILE] [--gpus W]
-                              [--report [--report-kl]] [--progress FILE] [--job-obs-filter]
+                              [--report [--report-kl]] [--progress FILE] [--job-obs-filter] [--job-norm-reward [--reward-clip C]]
 
 Four ways to run the rollout loop (the reference's `model.learn` -> runner.run(): one `env.step(actions)` per policy
 forward, train/stable_baselines/ppo.py:84-100,122-123) — same arithmetic, same results bit for bit:
@@ -84,7 +84,15 @@ ship_sim_gym_amd/obs_filter.py).  During a rollout a rank normalises with its ow
 synchronisation plus its own rows since; after every rollout, before GAE, the ranks all-gather what they added and every rank merges
 the rows with the same arithmetic, so the states agree bit for bit.  Rank 0 evaluates through a frozen view, ``--save`` gains the
 ``obs_filter`` section, which train/evaluate_native.py ``--checkpoint FILE`` applies, and every rank prints a checksum of the filter's
-state beside the parameters'.  The return filter across ranks stays out of scope.
+state beside the parameters'.
+
+``--job-norm-reward`` (``--mode native --update native`` only, one rank or more; not together with ``--norm-reward``; ``--reward-clip``
+applies): return normalisation for a job, the ``VecNormalize(norm_reward=True)`` a Stable-Baselines user gets around the whole
+SubprocVecEnv (``ReturnFilter(job=True)``, ship_sim_gym_amd/ret_filter.py).  Between the rollout and GAE every rank reduces its shard
+to one statistics row per step, the ranks all-gather the [horizon, 4] rows once, and every rank chains the same rows in the same
+order: the state is that of one filter over all the job's envs, bit-identical on every rank, and with one rank it is ``--norm-reward``'s
+bit for bit.  ``--save`` holds the ``ret_filter`` section (rank 0's: the job's state and rank 0's returns in flight), with one rank
+``--resume`` continues from it, and every rank prints a checksum of the filter's state beside the parameters'.
 
 The sampling noise of a whole rollout is drawn in one call before it (uniforms [horizon, envs], inverse-CDF sampling inside
 the step), so a captured step holds no random-number generator state and replays exactly what the eager loop computes.
@@ -325,15 +333,27 @@ JOB_OBS_FILTER_REQUIREMENTS = (
 )
 
 
+# The job-wide return filter's row, likewise: any number of ranks; not together with the plain one.
+JOB_NORM_REWARD_REQUIREMENTS = (
+    ("job_norm_reward", "--job-norm-reward", lambda a: bool(getattr(a, "job_norm_reward", None)), ("mode", "update"), False,
+     "the ranks' rows are gathered between the native rollout and the device's GAE"),
+)
+# (what a job-wide filter's row is not supported together with, asked after its needs: the argument, its flag, why)
+JOB_FILTER_EXCLUDES = {"job_obs_filter": ("obs_filter", "--obs-filter", "one filter is bound to the env"),
+                       "job_norm_reward": ("norm_reward", "--norm-reward", "one filter normalises the rewards")}
+
+
 def check_requirements(args, ranks, error=None):
-    """Walk EPISODE_LOG_REQUIREMENTS, REPORT_REQUIREMENTS, JOB_OBS_FILTER_REQUIREMENTS and REQUIREMENTS over the arguments `args` (a dict) of a run of `ranks` ranks.  The first row that is on and misses a need, or is
+    """Walk EPISODE_LOG_REQUIREMENTS, REPORT_REQUIREMENTS, JOB_OBS_FILTER_REQUIREMENTS, JOB_NORM_REWARD_REQUIREMENTS and REQUIREMENTS over the arguments `args` (a dict) of a run of `ranks` ranks.  The first row that is on and misses a need, or is
     refused with more than one rank, goes to the parser's `error` with the flags in the text, or is a ValueError with train()'s names."""
     a = argparse.Namespace(**dict(args, ranks=ranks))
-    for name, flag, on, needs, one_rank_only, why in EPISODE_LOG_REQUIREMENTS + REPORT_REQUIREMENTS + JOB_OBS_FILTER_REQUIREMENTS + REQUIREMENTS:
+    rows = EPISODE_LOG_REQUIREMENTS + REPORT_REQUIREMENTS + JOB_OBS_FILTER_REQUIREMENTS + JOB_NORM_REWARD_REQUIREMENTS + REQUIREMENTS
+    for name, flag, on, needs, one_rank_only, why in rows:
         text = None
-        if name == "job_obs_filter" and on(a) and a.obs_filter and all(NEEDS[k][2](a) for k in needs):
-            text = ("--job-obs-filter is not supported together with --obs-filter: one filter is bound to the env" if error else
-                    "job_obs_filter (--job-obs-filter): it is not supported together with obs_filter=True: one filter is bound to the env")
+        other, other_flag, other_why = JOB_FILTER_EXCLUDES.get(name, (None, None, None))
+        if other and on(a) and getattr(a, other) and all(NEEDS[k][2](a) for k in needs):
+            text = ("%s is not supported together with %s: %s" % (flag, other_flag, other_why) if error else
+                    "%s (%s): it is not supported together with %s=True: %s" % (name, flag, other, other_why))
         elif on(a) and not all(NEEDS[k][2](a) for k in needs):
             text = ("%s needs %s (%s)" % (flag, " ".join(NEEDS[k][0] for k in needs), why) if error else
                     "%s: it needs %s (%s; got mode=%r, update=%r)" % (name, " and ".join(NEEDS[k][1] for k in needs), why, a.mode, a.update))
@@ -577,7 +597,7 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
           eval_every=0, eval_episodes=1, eval_envs=None, obs_filter=False, save_obs_filter=None,
           norm_reward=False, reward_clip=10.0, adv_norm="batch", perm="torch", timeout_bootstrap=False, hidden=64,
           save=None, save_every=0, save_best=None, resume=None, episode_log=None, episode_log_capacity=65536, best_window=0,
-          report=False, report_kl=False, progress=None, job_obs_filter=False):
+          report=False, report_kl=False, progress=None, job_obs_filter=False, job_norm_reward=False):
     config = run_config(**dict(locals()))  # (first statement: the arguments, nothing else)
     run = argparse.Namespace(**locals())  # the run record: the arguments and the config; build_run() and the bind step add the objects
     run.report = bool(report or report_kl or progress)  # (--report-kl and --progress imply --report)
@@ -586,13 +606,13 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
     check_train_arguments(run, world)
     if rank != 0:  # (a data-parallel job trains ONE policy, ship_sim_gym_amd/dp.py: only rank 0 logs, evaluates and saves)
         log = lambda *_, **__: None  # noqa: E731
-    ckpt = open_resume(resume, config, loop.resume_sections(RESUME_SECTIONS, obs_filter or job_obs_filter, norm_reward, episode_log), exempt=CONFIG_EXEMPT) if resume else None
+    ckpt = open_resume(resume, config, loop.resume_sections(RESUME_SECTIONS, obs_filter or job_obs_filter, norm_reward or job_norm_reward, episode_log), exempt=CONFIG_EXEMPT) if resume else None
     # build, bind, resume
     build_run(run, rank, world)
     eval_env = (ShipVecEnv(int(eval_envs or min(envs, 1024)), GameConfig, EnvConfig, device=device, n_maps=64, **dict(env_kw or {}))
                 if eval_every and rank == 0 else None)
     run.flt, run.rflt, run.evaluator = loop.bind_env(run.env, horizon, 1, obs_filter, norm_reward, gamma, reward_clip, timeout_bootstrap, eval_env,
-                                                     job_obs_filter=job_obs_filter)
+                                                     job_obs_filter=job_obs_filter, job_norm_reward=job_norm_reward)
     run.eplog, run.epwriter = loop.bind_episode_log(run.env, episode_log, episode_log_capacity, 1, resume)
     run.progress_writer = loop.open_progress(progress, resume)
     if mode in ("graph", "pingpong"):
@@ -653,6 +673,9 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         if job_obs_filter:
             print("observation filter checksum after %d rows merged: %s" % (
                 int(run.flt.count[0].item()), hashlib.sha256(run.flt.state.detach().cpu().numpy().tobytes()).hexdigest()), flush=True)
+        if job_norm_reward:
+            print("return filter checksum after %d returns merged: %s" % (
+                int(run.rflt.count[0].item()), hashlib.sha256(run.rflt.state.detach().cpu().numpy().tobytes()).hexdigest()), flush=True)
     steps = envs * horizon * max(0, updates - start)  # (this process's own; a resumed run did not step the updates it loaded)
     log("rollout (%s): %.1f M env-steps/s with the policy in the loop; whole training loop (rollout + PPO update): %.1f M env-steps/s" % (
         mode, steps / max(t_roll, 1e-9) / 1e6, steps / max(t_all, 1e-9) / 1e6))
@@ -695,7 +718,7 @@ def make_arg_parser():
                     help="divide the rewards GAE sees by a running std of the discounted return, on the device (needs --mode native "
                          "--update native); default: raw rewards")
     ap.add_argument("--reward-clip", type=float, default=10.0, metavar="C",
-                    help="clamp the normalised rewards to +-C (needs --norm-reward; 0: no clamp)")
+                    help="clamp the normalised rewards to +-C (needs --norm-reward or --job-norm-reward; 0: no clamp)")
     ap.add_argument("--adv-norm", choices=("batch", "minibatch"), default="batch",
                     help="normalise the advantages once per rollout, or inside every minibatch as Stable-Baselines' PPO2 does (either --update)")
     ap.add_argument("--perm", choices=("torch", "native"), default="torch",
@@ -724,6 +747,10 @@ def make_arg_parser():
                     help="the running observation filter for a data-parallel job, one rank or more: every rank normalises with its own "
                          "statistics during a rollout, and after it the ranks merge what they added, bit-identically (needs --mode native "
                          "--update native; not together with --obs-filter)")
+    ap.add_argument("--job-norm-reward", action="store_true",
+                    help="--norm-reward for a data-parallel job, one rank or more: the running std is that of the returns of all the "
+                         "job's envs; the ranks gather one row of statistics per step once per rollout and chain them alike, "
+                         "bit-identically (needs --mode native --update native; not together with --norm-reward)")
     ap.add_argument("--resume", default=None, metavar="FILE",
                     help="continue the run a checkpoint was saved from, bit for bit (needs --mode native --update native): repeat the "
                          "original command line; --updates stays the TOTAL and may be raised")
