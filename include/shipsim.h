@@ -1691,6 +1691,51 @@ int ssg_pop_report(ssg_handle *h, int n_members, int K, const float *dev_value_K
                    void *dev_scratch, size_t scratch_nbytes, double *dev_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The update report of a data-parallel job (additions to ABI 9): one record over the experience of all ranks
+ * RLlib's vf_explained_var and kl are taken over the batch gathered from all workers (train/rllib/ppo.py:34-35), PPO2's over the whole
+ * SubprocVecEnv (train/stable_baselines/ppo.py:88-90,122-123).  The walk above reduces a batch to nine raw f64 sums, and the record is
+ * formed from those sums and the count alone; so every rank reduces its shard to one SUM ROW, the rows are all-gathered once per
+ * update, and every rank forms the same record from the same rows in rank order (the pattern of ssg_ppo_adv_moments /
+ * ssg_ppo_set_adv_moments).  A sum row is f64 [SSG_REPORT_ROW_COLS]:
+ *     [0..8]  the walk's sums S_r, Q_r, S_e, Q_e, S_v, S_a, S_d, Q_d, C: bit for bit the totals the finish forms internally
+ *     [9]     n = (double)K * (double)N
+ *     [10]    1.0 when the post-update group was walked, else 0.0 (then [6..8] are 0.0)
+ *     [11]    0.0
+ * ssg_ppo_report_rows accumulates column c of the rows in f64 in row order, starting from row 0's value and adding rows 1 .. W-1; the
+ * count n = sum n_r likewise; the record [0..11] then has the formulas above, and the stats columns [12..20] are formed as the finish
+ * forms them (one thread per column, the stats rows in row order).  The post group is on when every row's [10] is 1.0 and off when
+ * every row's is 0.0; rows that disagree are a caller's error that a launch cannot return, so [8..11] of the job's record are NaN.
+ * One __device__ function turns {totals, n, post, stats sums} into the record for the finish and for ssg_ppo_report_rows alike.
+ *
+ * Contract.  With ONE row, that of ssg_ppo_report_sums on the same inputs, the record is bit for bit ssg_ppo_report's: with and without
+ * the post group, with and without stats, NaN explained variance for constant returns included.  The record depends on the rows and
+ * the stats alone.  No floating-point atomics, no host synchronisation, constant launch arguments.  ssg_ppo_report / ssg_pop_report
+ * give what they gave.
+ * ------------------------------------------------------------------------------------------------- */
+#define SSG_REPORT_ROW_COLS 12
+
+/* Replaces: a worker's share of the per-update log RLlib takes over the experience of all its workers (train/rllib/ppo.py:34-35) and
+ * PPO2 over its SubprocVecEnv (train/stable_baselines/ppo.py:88-90,122-123): this shard's sum row into dev_row12 (f64
+ * [SSG_REPORT_ROW_COLS] on the device).  The walk of ssg_ppo_report (the same kernels, grid and partials in the same scratch,
+ * ssg_ppo_report_workspace_nbytes), then one workgroup: thread j adds the partials of blocks j, j + 256, ... in that order, the
+ * 256-entry tree, plain stores.  Two launches on `stream`.  Refuses what ssg_ppo_report refuses (SSG_ERR_BAD_ARG, nothing launched);
+ * dev_row12 stands for its dev_out24. */
+int ssg_ppo_report_sums(ssg_handle *h, int K, int N, const float *dev_value_KN, const float *dev_ret_KN, const float *dev_adv_KN,
+                        const int32_t *dev_act /* nullable */, const float *dev_logp /* nullable */,
+                        const float *dev_logp_all_new /* nullable */, double clip, void *dev_scratch, size_t scratch_nbytes,
+                        double *dev_row12, void *stream);
+
+/* Replaces: the per-update log over the batch gathered from all workers (train/rllib/ppo.py:34-35;
+ * train/stable_baselines/ppo.py:88-90,122-123): the job's record from the gathered sum rows dev_rows (f64 [n_rows][SSG_REPORT_ROW_COLS],
+ * shard order) into dev_out[0]; with per_shard != 0 also shard r's own view, formed from row r alone with the same stats columns,
+ * into dev_out[1 + r].  dev_out: f64 [1 + (per_shard ? n_rows : 0)][SSG_REPORT_COLS].  dev_stats (nullable): f32
+ * [n_stat_rows][n_cols], n_cols 4 or 8 — in a job the rows ssg_ppo_apply_shards wrote, identical on every rank.  One launch, one
+ * 64-thread workgroup per record.  SSG_ERR_BAD_ARG (nothing launched, dev_out untouched): a NULL handle, rows or out pointer; n_rows
+ * outside 1..SSG_DP_MAX_SHARDS; n_cols not 4 or 8, or n_stat_rows < 1, with dev_stats given. */
+int ssg_ppo_report_rows(ssg_handle *h, int n_rows, const double *dev_rows, const float *dev_stats /* nullable */, int n_stat_rows,
+                        int n_cols, int per_shard, double *dev_out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Host-side geometry (what pymunk's cffi exposed at reset time); no GPU needed.
  * ------------------------------------------------------------------------------------------------- */
 /* Replaces cpConvexHull as reached by pm.Poly(...) (models.py:96,180).  out_xy holds >= count pairs. */

@@ -82,6 +82,7 @@ EXPORTS = (
     "ssg_render_envs", "ssg_set_eval_recorder", "ssg_get_eval_recorder",
     "ssg_episode_log_workspace_nbytes", "ssg_episode_log_append",
     "ssg_report_clip_bounds", "ssg_ppo_report_workspace_nbytes", "ssg_ppo_report", "ssg_pop_report",
+    "ssg_ppo_report_sums", "ssg_ppo_report_rows",
 )
 RENDER_MAX_ENVS = 4096  # frames of one ssg_render_envs launch at most
 EVAL_REC_MAX_ENVS = 64  # tracked envs of an evaluation recorder at most
@@ -90,6 +91,7 @@ EPISODE_LOG_MAX_CELLS = 1 << 22  # K * ceil(n_envs / 256) of one ssg_episode_log
 # the update report's record (include/shipsim.h): its f64 columns, and where the explained variance, the post-update group's flag, the
 # stats rows' means and their row count sit
 REPORT_COLS, REPORT_EXPLAINED_VARIANCE, REPORT_POST, REPORT_STATS, REPORT_ROWS = 24, 5, 8, 12, 20
+REPORT_ROW_COLS = 12  # a shard's sum row (ssg_ppo_report_sums): the walk's nine sums, n, the post flag, 0
 
 
 class ShipSimError(RuntimeError):
@@ -365,6 +367,8 @@ def lib():
     L.ssg_ppo_report_workspace_nbytes.argtypes = [C.c_int, C.c_int, szp]
     L.ssg_ppo_report.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_double, vp, C.c_int, C.c_int, vp, C.c_size_t, vp, vp]
     L.ssg_pop_report.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_size_t, vp, vp]
+    L.ssg_ppo_report_sums.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_double, vp, C.c_size_t, vp, vp]
+    L.ssg_ppo_report_rows.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.ssg_dyn_invalidate.argtypes = [vp, vp, vp]
     L.ssg_host_convex_hull.argtypes = [C.c_int, dp, dp, ip]
     L.ssg_host_moment_for_poly.argtypes = [C.c_double, C.c_int, dp, dp]

@@ -2899,7 +2899,7 @@ static int report(ssg_handle *h, ssg::ReportLaunch &l, bool need_bounds, void *d
 {
     const std::string w(what);
     char buf[200];
-    if (!l.val || !l.ret || !l.adv || !l.out) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL value, ret, adv or out buffer");
+    if (!l.val || !l.ret || !l.adv || (!l.out && !l.row)) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL value, ret, adv or out buffer");
     if (l.K < 1 || l.N < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": K and N must be >= 1");
     const int given = (l.act != nullptr) + (l.logp != nullptr) + (l.lpa != nullptr);
     if (given != 0 && given != 3) return fail(h, SSG_ERR_BAD_ARG, w + ": dev_act, dev_logp and dev_logp_all_new go together: all three or none");
@@ -2949,6 +2949,51 @@ int ssg_ppo_report(ssg_handle *h, int K, int N, const float *dev_value_KN, const
     l.n_cols = n_cols;
     l.out = dev_out24;
     return report(h, l, false, dev_scratch, scratch_nbytes, stream, "ssg_ppo_report");
+}
+
+// The sum row of one rank's shard: ssg_ppo_report's checks and walk, then the launch that stores the totals instead of the record.
+int ssg_ppo_report_sums(ssg_handle *h, int K, int N, const float *dev_value_KN, const float *dev_ret_KN, const float *dev_adv_KN,
+                        const int32_t *dev_act, const float *dev_logp, const float *dev_logp_all_new, double clip, void *dev_scratch,
+                        size_t scratch_nbytes, double *dev_row12, void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc != SSG_OK) return rc;
+    ssg::ReportLaunch l = {};
+    l.K = K;
+    l.N = N;
+    l.lay = ssg::MemberLayout{1, N, nullptr};
+    l.val = dev_value_KN;
+    l.ret = dev_ret_KN;
+    l.adv = dev_adv_KN;
+    l.act = dev_act;
+    l.logp = dev_logp;
+    l.lpa = dev_logp_all_new;
+    if (dev_logp_all_new) {
+        if (!(clip > 0.0)) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_report_sums: clip must be > 0 with the post-update group");
+        float b[2];
+        ssg::report_clip_bounds(clip, b);
+        l.lo = b[0];
+        l.hi = b[1];
+    }
+    l.row = dev_row12;
+    return report(h, l, false, dev_scratch, scratch_nbytes, stream, "ssg_ppo_report_sums");
+}
+
+// The job's record from the gathered rows: host checks, then one launch.
+int ssg_ppo_report_rows(ssg_handle *h, int n_rows, const double *dev_rows, const float *dev_stats, int n_stat_rows, int n_cols, int per_shard,
+                        double *dev_out, void *stream)
+{
+    int rc = pop_bound(h);
+    if (rc != SSG_OK) return rc;
+    if (!dev_rows || !dev_out) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_report_rows: NULL dev_rows or dev_out");
+    if (n_rows < 1 || n_rows > SSG_DP_MAX_SHARDS) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_report_rows: n_rows must be in 1..SSG_DP_MAX_SHARDS");
+    if (dev_stats && n_cols != 4 && n_cols != 8) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_report_rows: n_cols must be 4 or 8");
+    if (dev_stats && n_stat_rows < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_report_rows: fewer than 1 stats row");
+    rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_report_rows(n_rows, dev_rows, dev_stats, n_stat_rows, n_cols, per_shard != 0, dev_out, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("report rows launch: ") + hipGetErrorString(e));
+    return SSG_OK;
 }
 
 int ssg_pop_report(ssg_handle *h, int n_members, int K, const float *dev_value_KN, const float *dev_ret_KN, const float *dev_adv_KN,

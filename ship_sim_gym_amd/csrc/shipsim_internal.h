@@ -532,8 +532,14 @@ struct ReportLaunch {
     const int32_t *rows;         // nullable: int32 [members], member m's own row count (<= rows_max)
     int rows_max, n_cols;
     double *part, *out;
+    double *row;                 // nullable: f64 [SSG_REPORT_ROW_COLS]; given, the second launch writes the sum row instead of the record
+                                 // (one policy, no slices; out, stats and rows are then not read)
 };
 hipError_t launch_report(const ReportLaunch &l, hipStream_t stream);
+// One launch, one small workgroup per record: the job's record from the W sum rows (f64 [W][SSG_REPORT_ROW_COLS], shard order) into
+// out[0], and with per_shard shard r's own, from row r alone, into out[1 + r]; stats (nullable, f32 [n_stat_rows][n_cols]) as the finish.
+hipError_t launch_report_rows(int n_rows, const double *rows, const float *stats, int n_stat_rows, int n_cols, bool per_shard, double *out,
+                              hipStream_t stream);
 
 #ifdef __HIPCC__
 // One round of Philox4x32-10 (counter ctr, key key).  The counter-based streams of the library — fill_actions_kernel's actions

@@ -21,6 +21,10 @@ synchronised after it by the same pattern (gathered buffers, the same merge on e
 The return filter of such a job is ship_sim_gym_amd/ret_filter.py's ``ReturnFilter(job=True)``: ``gae`` hands it the group, the
 ranks gather one [K, 4] block of per-step rows per rollout and chain them alike, which is exact: one filter over all the job's envs.
 
+The update report of such a job is ``job_report`` (ship_sim_gym_amd/report.py): every rank reduces its shard to one f64 sum row, the rows
+are all-gathered once per update, and every rank forms the same record from them in rank order, replayable in one process with
+``report_row`` / ``report_rows`` and torch.stack.  ``report`` stays the rank's own shard's.
+
 Out of scope: adv_norm="minibatch" across ranks, resuming a multi-rank run,
 populations across ranks, overlapping the gather with the next gradient, running this loop from C.
 """
@@ -160,8 +164,8 @@ class DataParallelPPO(NativePPO):
     job is this process alone, W = 1, and every result is NativePPO's bit for bit).  plan=(K, minibatches): check at construction that
     the shards make the same number of chunks for that rollout length and minibatch count (update() checks what it is given).
     ``report`` / ``report_device`` are NativePPO's: the record is then this rank's OWN shard's (its n, means, variances and post-update
-    group; the stats rows' means are the job's, since every rank holds the same rows).  The sums are mergeable, but merging the ranks'
-    records is out of scope."""
+    group; the stats rows' means are the job's, since every rank holds the same rows).  ``job_report`` gives the JOB's record: every
+    rank's sum row gathered once, the same record formed on every rank (ssg_ppo_report_sums / ssg_ppo_report_rows)."""
 
     def __init__(self, policy, env, group=None, plan=None, **kw):
         if kw.get("adv_norm", "batch") != "batch":
@@ -333,6 +337,11 @@ class DataParallelPPO(NativePPO):
                     out.append(st)
         self.updates += 1
         return torch.stack(out) if stats else None
+
+    def job_report(self, batch, stats=None, post=False, group=None, per_shard=False):
+        """NativePPO.job_report over this job's group (group=None: ``self.group``): a collective, every rank calls it and gets the same
+        bits.  stats: what update(..., stats=True) returned — the job's rows, identical on every rank."""
+        return super(DataParallelPPO, self).job_report(batch, stats, post, self.group if group is None else group, per_shard)
 
     # ------------------------------------------------------------------------------------------------
     def state_dict(self):

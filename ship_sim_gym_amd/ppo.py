@@ -33,7 +33,10 @@ library's own: it is not seed-compatible with numpy or torch.
 
 ``report(batch, stats, post)`` says how an update went — the explained variance of the value network, the means of the update's stats
 rows and, with ``post=True``, how far the policy moved — from two launches over the batch and one copy (ssg_ppo_report;
-ship_sim_gym_amd/report.py holds the record's fields, the numpy restatement and the CSV writer).
+ship_sim_gym_amd/report.py holds the record's fields, the numpy restatement and the CSV writer).  ``job_report`` is the same record over
+the experience of every rank of a data-parallel job: ``report_row`` reduces this shard to one f64 sum row (ssg_ppo_report_sums), the
+rows are all-gathered once, and ``report_rows`` forms the record from them alike on every rank (ssg_ppo_report_rows); without a process
+group it is ``report`` bit for bit.
 """
 import ctypes as C
 
@@ -526,8 +529,9 @@ class NativePPO(DeviceTrainer):
     # ------------------------------------------------------------------------------------------------
     # the update report (ship_sim_gym_amd/report.py)
     # ------------------------------------------------------------------------------------------------
-    def _report(self, batch, stats, post):
-        """f64 [25] on the device: ssg_ppo_report's record, then the KL coefficient as it is now.  Enqueued only: no synchronisation."""
+    def _report_inputs(self, batch, post):
+        """What ssg_ppo_report and ssg_ppo_report_sums walk: (K, n_env, the three buffers' pointers, the post-update group's three or
+        Nones, the scratch pointer and size).  post: one ssg_ppo_dist launch into a tensor of its own."""
         torch = _torch()
         from . import report as R
         dev = self.policy.device
@@ -544,21 +548,33 @@ class NativePPO(DeviceTrainer):
             own = {"obs": batch["obs"]}
             new = self.dist(own)
             grp = (C.c_void_p(act.data_ptr()), C.c_void_p(logp.data_ptr()), C.c_void_p(new.data_ptr()))
-        rows = cols = 0
-        sp = None
-        if stats is not None:
-            if stats.dtype != torch.float32 or stats.device != dev or not stats.is_contiguous() or stats.dim() != 2:
-                raise ValueError("NativePPO.report: stats must be a contiguous f32 [rows, 4 or 8] tensor on %s (update(..., stats=True))" % (dev,))
-            rows, cols, sp = int(stats.shape[0]), int(stats.shape[1]), C.c_void_p(stats.data_ptr())
         need = R.scratch_nbytes(n_env, 1)
         if getattr(self, "_report_scratch", None) is None or self._report_scratch.numel() < need:
             self._report_scratch = torch.zeros(need, dtype=torch.uint8, device=dev)
+        bufs = (C.c_void_p(val.data_ptr()), C.c_void_p(ret.data_ptr()), C.c_void_p(adv.data_ptr()))
+        return K, n_env, bufs, grp, (C.c_void_p(self._report_scratch.data_ptr()), self._report_scratch.numel())
+
+    def _report_stats(self, stats, who):
+        """(pointer or None, rows, columns) of the stats rows update(..., stats=True) returned."""
+        torch = _torch()
+        dev = self.policy.device
+        if stats is None:
+            return None, 0, 0
+        if stats.dtype != torch.float32 or stats.device != dev or not stats.is_contiguous() or stats.dim() != 2:
+            raise ValueError("NativePPO.%s: stats must be a contiguous f32 [rows, 4 or 8] tensor on %s (update(..., stats=True))" % (who, dev))
+        return C.c_void_p(stats.data_ptr()), int(stats.shape[0]), int(stats.shape[1])
+
+    def _report(self, batch, stats, post):
+        """f64 [25] on the device: ssg_ppo_report's record, then the KL coefficient as it is now.  Enqueued only: no synchronisation."""
+        torch = _torch()
+        dev = self.policy.device
+        K, n_env, bufs, grp, scratch = self._report_inputs(batch, post)
+        sp, rows, cols = self._report_stats(stats, "report")
         out = torch.empty(N.REPORT_COLS + 1, dtype=torch.float64, device=dev)
         h = self.env._h
         with torch.cuda.device(dev):
-            N.check(N.lib().ssg_ppo_report(h, K, n_env, C.c_void_p(val.data_ptr()), C.c_void_p(ret.data_ptr()), C.c_void_p(adv.data_ptr()),
-                                           *grp, float(self.hp.clip), sp, rows, cols, C.c_void_p(self._report_scratch.data_ptr()),
-                                           self._report_scratch.numel(), C.c_void_p(out.data_ptr()), self._stream()), h, "ssg_ppo_report")
+            N.check(N.lib().ssg_ppo_report(h, K, n_env, *bufs, *grp, float(self.hp.clip), sp, rows, cols, *scratch,
+                                           C.c_void_p(out.data_ptr()), self._stream()), h, "ssg_ppo_report")
             out[N.REPORT_COLS:].copy_(self.kl_coef)
         return out
 
@@ -577,6 +593,60 @@ class NativePPO(DeviceTrainer):
         row = self._report(batch, stats, post).cpu().tolist()
         rec = record_dict(row[:N.REPORT_COLS])
         rec.update(lr=float(self.hp.lr), clip=float(self.hp.clip), step=int(self.step), updates=int(self.updates), kl_coef_now=row[N.REPORT_COLS])
+        return rec
+
+    # the job's report: a sum row per shard, one gather, the same record on every rank
+    def report_row(self, batch, post=False):
+        """ssg_ppo_report_sums over a batch gae() has seen: this shard's sum row, f64 [12] on the device (the walk's nine totals, n, the
+        post flag, 0; report.sums_reference).  Two launches, enqueued only.  post=True: the post-update group, from one ssg_ppo_dist
+        launch into a tensor of its own, as report_device takes it."""
+        torch = _torch()
+        dev = self.policy.device
+        K, n_env, bufs, grp, scratch = self._report_inputs(batch, post)
+        row = torch.empty(N.REPORT_ROW_COLS, dtype=torch.float64, device=dev)
+        h = self.env._h
+        with torch.cuda.device(dev):
+            N.check(N.lib().ssg_ppo_report_sums(h, K, n_env, *bufs, *grp, float(self.hp.clip), *scratch, C.c_void_p(row.data_ptr()),
+                                                self._stream()), h, "ssg_ppo_report_sums")
+        return row
+
+    def report_rows(self, rows, stats=None, per_shard=False):
+        """ssg_ppo_report_rows: the job's record, f64 [24] on the device, from the gathered sum rows (f64 [W, 12], shard order;
+        report.rows_reference); per_shard=True: f64 [1 + W, 24], record 1 + r being shard r's own view.  One launch, enqueued only.
+        stats: the job's stats rows, as report_device takes them."""
+        torch = _torch()
+        dev = self.policy.device
+        rows = rows.to(device=dev, dtype=torch.float64).contiguous()
+        if rows.dim() != 2 or rows.shape[1] != N.REPORT_ROW_COLS:
+            raise ValueError("NativePPO.report_rows: rows must be f64 [W, %d] (got %s)" % (N.REPORT_ROW_COLS, tuple(rows.shape)))
+        W = int(rows.shape[0])
+        sp, n_stat, cols = self._report_stats(stats, "report_rows")
+        out = torch.empty((1 + W if per_shard else 1, N.REPORT_COLS), dtype=torch.float64, device=dev)
+        h = self.env._h
+        with torch.cuda.device(dev):
+            N.check(N.lib().ssg_ppo_report_rows(h, W, C.c_void_p(rows.data_ptr()), sp, n_stat, cols, int(bool(per_shard)),
+                                                C.c_void_p(out.data_ptr()), self._stream()), h, "ssg_ppo_report_rows")
+        return out if per_shard else out[0]
+
+    def job_report(self, batch, stats=None, post=False, group=None, per_shard=False):
+        """report() over the experience of every rank of `group` (a collective: every rank calls it): this shard's report_row, one
+        all-gather of the rows, report_rows on every rank alike, ONE device-to-host copy.  Returns report()'s dict for the job — the
+        same bits on every rank — plus ``shards`` (W) and, with per_shard, ``shard_records`` (W dicts of the record's fields, shard
+        r's own view).  stats: in a job what update(..., stats=True) returned, the job's rows.  Without a process group this is
+        report() bit for bit."""
+        torch = _torch()
+        from .report import record_dict
+        from .sharding import all_gather_rows
+        rows = all_gather_rows(self.report_row(batch, post), group)
+        W = int(rows.shape[0])
+        recs = self.report_rows(rows, stats, per_shard).reshape(-1)
+        with torch.cuda.device(self.policy.device):
+            flat = torch.cat([recs, self.kl_coef.to(torch.float64).reshape(-1)[:1]]).cpu().tolist()
+        rec = record_dict(flat[:N.REPORT_COLS])
+        rec.update(lr=float(self.hp.lr), clip=float(self.hp.clip), step=int(self.step), updates=int(self.updates), kl_coef_now=flat[-1],
+                   shards=W)
+        if per_shard:
+            rec["shard_records"] = [record_dict(flat[(1 + r) * N.REPORT_COLS: (2 + r) * N.REPORT_COLS]) for r in range(W)]
         return rec
 
     # ------------------------------------------------------------------------------------------------

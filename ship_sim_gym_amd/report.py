@@ -8,8 +8,13 @@ ssg_ppo_dist / ssg_pop_dist launch with ``post=True``, which measures how far th
 the launches in numpy in their order of operations, and the device's record is that restatement bit for bit.  ``ProgressWriter`` is the
 counterpart of Stable-Baselines' progress.csv.
 
-Out of scope: schedules of lr / clip (the columns are there for when they come), merging several ranks' records, the entropy or exact KL
-of the post-update policy over the whole batch (both need exp), a TensorBoard event writer.
+A data-parallel job's record is taken over the experience of all its ranks, as RLlib's is over its workers' (train/rllib/ppo.py:34-35):
+every rank reduces its shard to one sum row (ssg_ppo_report_sums: the walk's nine totals, n, the post flag), the rows are all-gathered,
+and every rank forms the same record from the same rows in rank order (ssg_ppo_report_rows).  ``NativePPO.job_report`` does that;
+``sums_reference`` / ``rows_reference`` restate the two calls, and one row gives ``report_reference``'s record bit for bit.
+
+Out of scope: schedules of lr / clip (the columns are there for when they come), the episode log or populations across ranks, the
+entropy or exact KL of the post-update policy over the whole batch (both need exp), a TensorBoard event writer.
 """
 import ctypes as C
 import os
@@ -41,19 +46,16 @@ def clip_bounds(clip):
     return np.float32(out[0]), np.float32(out[1])
 
 
-def report_reference(val, ret, adv, act=None, logp=None, logp_all_new=None, clip=0.2, stats=None, rows=None):
-    """ssg_ppo_report restated in numpy, in the device's order of operations: the f64 [24] record of ONE policy (a population member:
-    its own columns, bounds and rows).  val / ret / adv f32 [K, n]; the post-update group act i32 [K, n], logp f32 [K, n] and
-    logp_all_new f32 [K, n, 4] together or not at all; stats f32 [rows_max, 4 or 8] with rows (None: all of them) used.
-
-    The walk: per env the f64 sums in ascending t, every product and sum separately rounded; the 256-env blocks' halving trees; the
-    blocks' partials added per thread (block b, b + 256, ...) and one more tree; then the record's formulas."""
+def _walk_totals(who, val, ret, adv, act, logp, logp_all_new, clip):
+    """The walk and the two reductions behind it, in the device's order of operations: (K, n, post, the nine totals).  Per env the f64
+    sums in ascending t, every product and sum separately rounded; the 256-env blocks' halving trees; the blocks' partials added per
+    thread (block b, b + 256, ...) and one more tree."""
     f64 = np.float64
     val, ret, adv = (np.asarray(x, dtype=np.float32) for x in (val, ret, adv))
     K, n = val.shape
     post = logp_all_new is not None
     if post != (act is not None) or post != (logp is not None):
-        raise ValueError("report_reference: act, logp and logp_all_new go together")
+        raise ValueError("%s: act, logp and logp_all_new go together" % who)
     nb = -(-n // 256)
     s = np.zeros((nb * 256, REPORT_SUMS))
     if post:
@@ -82,9 +84,35 @@ def report_reference(val, ret, adv, act=None, logp=None, logp_all_new=None, clip
     acc = np.zeros((256, REPORT_SUMS))
     for r in range(part.shape[0] // 256):  # thread j: partials j, j + 256, ... in that order
         acc += part[r * 256: r * 256 + 256]
-    tot = _tree256(acc)
+    return K, n, post, _tree256(acc)
+
+
+def report_reference(val, ret, adv, act=None, logp=None, logp_all_new=None, clip=0.2, stats=None, rows=None):
+    """ssg_ppo_report restated in numpy, in the device's order of operations: the f64 [24] record of ONE policy (a population member:
+    its own columns, bounds and rows).  val / ret / adv f32 [K, n]; the post-update group act i32 [K, n], logp f32 [K, n] and
+    logp_all_new f32 [K, n, 4] together or not at all; stats f32 [rows_max, 4 or 8] with rows (None: all of them) used.
+
+    The walk and its reductions (_walk_totals), then the record's formulas (_record_from_sums): the finish kernel's two halves."""
+    K, n, post, tot = _walk_totals("report_reference", val, ret, adv, act, logp, logp_all_new, clip)
+    return _record_from_sums(tot, np.float64(K) * np.float64(n), int(post), stats, rows, "report_reference")
+
+
+def sums_reference(val, ret, adv, act=None, logp=None, logp_all_new=None, clip=0.2):
+    """ssg_ppo_report_sums restated in numpy, in the device's order of operations: a shard's sum row, f64 [12] = the walk's nine totals
+    (report_reference's walk, partials and tree), n = K * n_envs, the post flag, 0.  Without the post group columns 6..8 are 0."""
+    K, n, post, tot = _walk_totals("sums_reference", val, ret, adv, act, logp, logp_all_new, clip)
+    row = np.zeros(N.REPORT_ROW_COLS)
+    row[:REPORT_SUMS] = tot
+    row[REPORT_SUMS] = np.float64(K) * np.float64(n)
+    row[REPORT_SUMS + 1] = 1.0 if post else 0.0
+    return row
+
+
+def _record_from_sums(tot, cnt, post, stats, rows_used, who="rows_reference"):
+    """The record's formulas (the device's form_record) from the nine totals, the count, the post state (1 on, 0 off, else NaN in
+    [8..11]) and the stats rows."""
+    f64 = np.float64
     out = np.zeros(N.REPORT_COLS)
-    cnt = f64(K) * f64(n)
     with np.errstate(all="ignore"):
         mr = tot[0] / cnt
         vr = (tot[1] - tot[0] * mr) / cnt
@@ -95,21 +123,45 @@ def report_reference(val, ret, adv, act=None, logp=None, logp_all_new=None, clip
         out[0:5] = cnt, mr, vr, me, ve
         out[5] = np.nan if vr == 0.0 else f64(1.0) - ve / vr
         out[6], out[7] = tot[4] / cnt, tot[5] / cnt
-        if post:
+        if post == 1:
             out[8], out[9], out[10], out[11] = 1.0, -(tot[6] / cnt), f64(0.5) * (tot[7] / cnt), tot[8] / cnt
+        elif post != 0:
+            out[8:12] = np.nan
         if stats is not None:
             st = np.asarray(stats, dtype=np.float32)
             st = st.reshape(-1, st.shape[-1])
             if st.shape[1] not in (4, 8) or st.shape[0] < 1:
-                raise ValueError("report_reference: stats must be f32 [rows >= 1, 4 or 8]")
-            rows = st.shape[0] if rows is None else max(0, min(int(rows), st.shape[0]))
+                raise ValueError("%s: stats must be f32 [rows >= 1, 4 or 8]" % who)
+            used = st.shape[0] if rows_used is None else max(0, min(int(rows_used), st.shape[0]))
             colsum = np.zeros(st.shape[1])
-            for j in range(rows):  # one thread per column, its rows in row order
+            for j in range(used):  # one thread per column, its rows in row order
                 colsum += st[j].astype(f64)
-            if rows > 0:
-                out[N.REPORT_STATS: N.REPORT_STATS + st.shape[1]] = colsum / f64(rows)
-            out[N.REPORT_ROWS] = rows
+            if used > 0:
+                out[N.REPORT_STATS: N.REPORT_STATS + st.shape[1]] = colsum / f64(used)
+            out[N.REPORT_ROWS] = used
     return out
+
+
+def rows_reference(rows, stats=None, rows_used=None, per_shard=False):
+    """ssg_ppo_report_rows restated in numpy: the job's record f64 [24] from the sum rows f64 [W, 12] in shard order — column c
+    accumulated in row order from row 0's value on, n likewise, then the record's formulas; the post group on when every row's flag is
+    1.0, off when every row's is 0.0, NaN in [8..11] otherwise.  stats f32 [rows, 4 or 8] with rows_used (None: all; the device call
+    uses all it is given) as in report_reference.  per_shard: [1 + W, 24], record 1 + r formed from row r alone."""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, N.REPORT_ROW_COLS)
+
+    def one(block):
+        tot = block[0, :REPORT_SUMS + 1].copy()
+        for r in block[1:]:
+            tot = tot + r[:REPORT_SUMS + 1]
+        flags = block[:, REPORT_SUMS + 1]
+        post = 1 if np.all(flags == 1.0) else 0 if np.all(flags == 0.0) else -1
+        return _record_from_sums(tot[:REPORT_SUMS], tot[REPORT_SUMS], post, stats, rows_used)
+
+    if rows.shape[0] < 1:
+        raise ValueError("rows_reference: no rows")
+    if not per_shard:
+        return one(rows)
+    return np.stack([one(rows)] + [one(rows[r: r + 1]) for r in range(rows.shape[0])])
 
 
 def record_dict(row):

@@ -10,6 +10,7 @@ line on stdout.  The kernels alone: `rocprofv3 --kernel-trace --stats -- python 
 
     python tools/ppo_update_timing.py [--configs 65536x32,4096x64] [--repeats 7] [--only torch|native] [--ext] [--separate-value] [--ret-filter]
                                       [--adv-norm] [--perm] [--timeout-bootstrap] [--checkpoint] [--dp] [--episode-log] [--report]
+                                      [--ret-filter-job] [--report-job]
                                       [--ret-filter-job]
 
 --ext adds, in the same run, the extended update (NativePPO with vf_clip 0.2, max_grad_norm 0.5, kl_coef 1.0, kl_target 0.01: GAE, the
@@ -49,6 +50,12 @@ a gather that is a no-op, apply_rows: four launches); "ret_apply_rows_w1" / "_w2
 rows: two launches); and the whole GAE + update with each filter, "native_ret_plain" and "native_ret_job".  With this flag every timed
 path follows one untimed GAE over the batch, so that all have the same predecessor.  The gather over real links is not part of
 any of them.
+--report-job adds, in the same run and alternating with the others, the job's update report on one device: "report_device"
+(NativePPO.report_device with the stats rows of an update: ssg_ppo_report, two launches) against "report_split" (the split call at W = 1:
+report_row, then report_rows on its one row: three launches); "report_rows_w1" / "_w2" / "_w8" (report_rows alone on 1, 2 and 8 stacked
+rows: one launch); and the whole GAE + update with each report behind it, one copy to the host included, "native_report_own"
+(NativePPO.report) and "native_report_job" (NativePPO.job_report, whose gather is a no-op here).  Every timed path follows one untimed
+GAE, as with --ret-filter-job.  The gather over real links is not part of any of them.
 """
 import argparse
 import importlib.util
@@ -104,7 +111,7 @@ def _wall_ms(fn):
 
 def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext=False, separate_value=False, ret_filter=False,
             adv_norm=False, perm=False, timeout_bootstrap=False, checkpoint=False, checkpoint_dir=None, dp=False, episode_log=False,
-            report=False, ret_filter_job=False):
+            report=False, ret_filter_job=False, report_job=False):
     from ship_sim_gym_amd.policy import NativePolicy
     from ship_sim_gym_amd.ppo import NativePPO
     torch.manual_seed(0)
@@ -247,6 +254,21 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
         paths += [("native_ret_plain", native_path(ppo, seeded(), return_filter=rplain)), ("native_ret_job", native_path(ppo, seeded(), return_filter=rjob))]
         # What ran before a path shows in it: the path after a whole update, whichever it is, measured 15 .. 40 us more.  So here every
         # path follows one untimed GAE over the batch; the two whole updates still differ by their order (profiles/ret_filter_job/).
+    if report_job:  # the report calls read a batch GAE has seen and the stats rows of an update; they change neither
+        nb_j = dict(b)
+        ppo.gae(nb_j)
+        st_j = torch.randn((epochs * minibatches, 4), device=dev)
+        own_row = ppo.report_row(nb_j)
+
+        def report_rows_alone(W):
+            rows = torch.stack([own_row] * W)
+            return lambda: ppo.report_rows(rows, st_j)
+        paths += [("report_device", lambda: ppo.report_device(nb_j, stats=st_j)),
+                  ("report_split", lambda: ppo.report_rows(ppo.report_row(nb_j)[None], st_j))]
+        paths += [("report_rows_w%d" % W, report_rows_alone(W)) for W in (1, 2, 8)]
+        paths += [("native_report_own", native_path(ppo, seeded(), after=lambda nb, st: ppo.report(nb, stats=st))),
+                  ("native_report_job", native_path(ppo, seeded(), after=lambda nb, st: ppo.job_report(nb, stats=st)))]
+    if ret_filter_job or report_job:
         spacer = lambda: ppo.gae(dict(b))  # noqa: E731
     else:
         spacer = lambda: None  # noqa: E731
@@ -302,11 +324,14 @@ def main():
     ap.add_argument("--ret-filter-job", action="store_true", help="also time the job-wide return filter on one device: the split call at "
                                                                   "W = 1 against ssg_ret_filter_apply, apply_rows alone on 1, 2 and 8 "
                                                                   "stacked rows, and the whole GAE + update with each")
+    ap.add_argument("--report-job", action="store_true", help="also time the job's update report on one device: the split call at W = 1 "
+                                                              "against ssg_ppo_report, report_rows alone on 1, 2 and 8 stacked rows, and "
+                                                              "the whole GAE + update with report() and with job_report() behind it")
     a = ap.parse_args()
     mod = _ppo()
     res = [measure(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.repeats, a.only, "cuda:0", ext=a.ext, separate_value=sep, ret_filter=a.ret_filter,
                    adv_norm=a.adv_norm, perm=a.perm, timeout_bootstrap=a.timeout_bootstrap, checkpoint=a.checkpoint,
-                   checkpoint_dir=a.checkpoint_dir, dp=a.dp, episode_log=a.episode_log, report=a.report, ret_filter_job=a.ret_filter_job)
+                   checkpoint_dir=a.checkpoint_dir, dp=a.dp, episode_log=a.episode_log, report=a.report, ret_filter_job=a.ret_filter_job, report_job=a.report_job)
            for c in a.configs.split(",") for sep in ([False, True] if a.separate_value else [False])]
     print(json.dumps({"ppo_update_timing": res}))
 

@@ -9,6 +9,7 @@ leave the GPU; the policy is a small MLP in fp32.
                               [--norm-reward [--reward-clip C]]
                               [--save FILE [--save-every U]] [--save-best FILE] [--resume FILE] [--gpus W]
                               [--report [--report-kl]] [--progress FILE] [--job-obs-filter] [--job-norm-reward [--reward-clip C]]
+                              [--job-report [--job-report-kl] [--job-report-shards]] [--job-progress FILE]
 
 Four ways to run the rollout loop (the reference's `model.learn` -> runner.run(): one `env.step(actions)` per policy
 forward, train/stable_baselines/ppo.py:84-100,122-123) — same arithmetic, same results bit for bit:
@@ -66,7 +67,7 @@ one copy (ship_sim_gym_amd/report.py, ssg_ppo_report).  ``--report-kl`` adds how
 PPO2's approxkl and the clip fraction over the whole batch under the new parameters) for one more policy forward over the batch;
 ``--progress FILE`` writes every update's record as a CSV row (PPO2's progress.csv) and, with ``--resume``, cuts the file back to the
 checkpoint's update first.  The three may change between a run and its resumption; without them nothing is computed or printed.
-More than one rank refuses them.
+More than one rank refuses them: a job reports through ``--job-report``.
 
 ``--gpus W`` (``--mode native --update native`` only): ONE policy trained data-parallel on W ranks, one per GPU, as the RLlib scripts
 train one policy from the experience of their workers (train/rllib/ppo.py:34-35, train/rllib/pbt.py:57-58).  The script starts the W
@@ -93,6 +94,16 @@ to one statistics row per step, the ranks all-gather the [horizon, 4] rows once,
 order: the state is that of one filter over all the job's envs, bit-identical on every rank, and with one rank it is ``--norm-reward``'s
 bit for bit.  ``--save`` holds the ``ret_filter`` section (rank 0's: the job's state and rank 0's returns in flight), with one rank
 ``--resume`` continues from it, and every rank prints a checksum of the filter's state beside the parameters'.
+
+``--job-report`` (``--mode native --update native`` only, one rank or more; not together with ``--report`` / ``--report-kl`` /
+``--progress``: one report per update): the update report of a job, taken over the experience of all ranks as RLlib takes
+vf_explained_var and kl over its workers' (train/rllib/ppo.py:34-35).  After the update every rank reduces its shard to one row of f64
+sums, the ranks all-gather the rows once, and every rank forms the same record from them in rank order (``job_report``,
+ship_sim_gym_amd/report.py; ssg_ppo_report_sums / ssg_ppo_report_rows); rank 0 prints the line.  ``--job-report-kl`` adds the
+post-update group, ``--job-report-shards`` one line per rank with its shard's samples and explained variance, and ``--job-progress
+FILE`` has rank 0 write the job's record as ``--progress`` writes a rank's (``timesteps`` counts the job's ``--envs``); each implies
+``--job-report``.  With one rank the record is ``--report``'s bit for bit, and ``--resume`` cuts the file back likewise.  The episode
+log and populations across ranks, ``--adv-norm minibatch`` across ranks and multi-rank resume stay out of scope.
 
 The sampling noise of a whole rollout is drawn in one call before it (uniforms [horizon, envs], inverse-CDF sampling inside
 the step), so a captured step holds no random-number generator state and replays exactly what the eager loop computes.
@@ -278,7 +289,7 @@ def rollout(shards, horizon, mode, gen, policy=None, job=None):
 
 # what a resumed run may change: everything else in train()'s arguments is the run's configuration (the checkpoint's "config" section)
 CONFIG_EXEMPT = ("updates", "save", "save_every", "save_best", "save_obs_filter", "resume", "eval_every", "eval_episodes", "eval_envs", "log",
-                 "return_details", "report", "report_kl", "progress")
+                 "return_details", "report", "report_kl", "progress", "job_report", "job_report_kl", "job_progress", "job_report_shards")
 RESUME_SECTIONS = ("policy", "trainer", "env", "loop", "config")
 open_resume = loop.open_resume  # (importable from here, as it was)
 
@@ -343,15 +354,37 @@ JOB_FILTER_EXCLUDES = {"job_obs_filter": ("obs_filter", "--obs-filter", "one fil
                        "job_norm_reward": ("norm_reward", "--norm-reward", "one filter normalises the rewards")}
 
 
+# The job's update report's rows, likewise: any number of ranks; not together with the rank's own report (one report per update).
+JOB_REPORT_REQUIREMENTS = tuple(
+    (name, flag, (lambda a, name=name: bool(getattr(a, name, None))), ("mode", "update"), False,
+     "the ranks' sum rows are reduced from the device update's buffers and gathered once per update")
+    for name, flag in (("job_progress", "--job-progress"), ("job_report_shards", "--job-report-shards"), ("job_report_kl", "--job-report-kl"),
+                       ("job_report", "--job-report")))
+JOB_REPORT_EXCLUDES = tuple((name, flag, "one report per update")  # (the flag that implies another stands before it, as above)
+                            for name, flag in (("progress", "--progress"), ("report_kl", "--report-kl"), ("report", "--report")))
+
+
+def excluded_with(name, a):
+    """What the row `name` is on together with and is not supported with: (the argument, its flag, why), or three Nones."""
+    if name in JOB_FILTER_EXCLUDES:
+        other = JOB_FILTER_EXCLUDES[name]
+        return other if getattr(a, other[0]) else (None, None, None)
+    if name in (row[0] for row in JOB_REPORT_REQUIREMENTS):
+        for other in JOB_REPORT_EXCLUDES:
+            if getattr(a, other[0], None):
+                return other
+    return None, None, None
+
+
 def check_requirements(args, ranks, error=None):
-    """Walk EPISODE_LOG_REQUIREMENTS, REPORT_REQUIREMENTS, JOB_OBS_FILTER_REQUIREMENTS, JOB_NORM_REWARD_REQUIREMENTS and REQUIREMENTS over the arguments `args` (a dict) of a run of `ranks` ranks.  The first row that is on and misses a need, or is
+    """Walk EPISODE_LOG_REQUIREMENTS, JOB_REPORT_REQUIREMENTS, REPORT_REQUIREMENTS, JOB_OBS_FILTER_REQUIREMENTS, JOB_NORM_REWARD_REQUIREMENTS and REQUIREMENTS over the arguments `args` (a dict) of a run of `ranks` ranks.  The first row that is on and misses a need, or is
     refused with more than one rank, goes to the parser's `error` with the flags in the text, or is a ValueError with train()'s names."""
     a = argparse.Namespace(**dict(args, ranks=ranks))
-    rows = EPISODE_LOG_REQUIREMENTS + REPORT_REQUIREMENTS + JOB_OBS_FILTER_REQUIREMENTS + JOB_NORM_REWARD_REQUIREMENTS + REQUIREMENTS
+    rows = EPISODE_LOG_REQUIREMENTS + JOB_REPORT_REQUIREMENTS + REPORT_REQUIREMENTS + JOB_OBS_FILTER_REQUIREMENTS + JOB_NORM_REWARD_REQUIREMENTS + REQUIREMENTS
     for name, flag, on, needs, one_rank_only, why in rows:
         text = None
-        other, other_flag, other_why = JOB_FILTER_EXCLUDES.get(name, (None, None, None))
-        if other and on(a) and getattr(a, other) and all(NEEDS[k][2](a) for k in needs):
+        other, other_flag, other_why = excluded_with(name, a) if on(a) else (None, None, None)
+        if other and all(NEEDS[k][2](a) for k in needs):
             text = ("%s is not supported together with %s: %s" % (flag, other_flag, other_why) if error else
                     "%s (%s): it is not supported together with %s=True: %s" % (name, flag, other, other_why))
         elif on(a) and not all(NEEDS[k][2](a) for k in needs):
@@ -484,9 +517,11 @@ def native_update(run, u, log):
     n = run.horizon * run.n_local  # (a rank shuffles its own samples)
     rows = None if run.perm == "native" else torch.stack([torch.randperm(n, device=run.dev, generator=run.gen) for _ in range(run.epochs)])
     filters = run.flt is not None or run.rflt is not None
-    st_upd = run.ppo.update(nb, rows, run.epochs, run.minibatches, stats=filters or run.report)
+    st_upd = run.ppo.update(nb, rows, run.epochs, run.minibatches, stats=filters or run.report or run.job_report)
     if run.report:
         report_update(run, u, nb, st_upd, log)
+    if run.job_report:  # (every rank: the call gathers the ranks' sum rows)
+        job_report_update(run, u, nb, st_upd, log)
     if filters:
         pg, vf, ent = (float(v) for v in st_upd[-1, :3])
         notes = []
@@ -515,6 +550,17 @@ def report_update(run, u, nb, st_upd, log):
     log("update %3d  report: %s" % (u, report_line(rec, st_upd.shape[1] == 8)))
     if run.progress_writer is not None:
         run.progress_writer.write(u, (u + 1) * run.envs * run.horizon, rec, rec["lr"], rec["clip"])
+
+
+def job_report_update(run, u, nb, st_upd, log):
+    """--job-report: the record over the experience of all ranks (every rank calls it: one all-gather of the sum rows, one copy to the
+    host); rank 0 logs the line, the shards' own lines and the --job-progress row (log and the writer are rank 0's alone)."""
+    rec = run.ppo.job_report(nb, stats=st_upd, post=run.job_report_kl, per_shard=run.job_report_shards)
+    log("update %3d  job report (%d ranks, %d samples): %s" % (u, rec["shards"], int(rec["n"]), report_line(rec, st_upd.shape[1] == 8)))
+    for r, shard in enumerate(rec.get("shard_records", ())):
+        log("update %3d  job report, shard %d: %d samples  explained variance %+.4f" % (u, r, int(shard["n"]), shard["explained_variance"]))
+    if run.job_progress_writer is not None:
+        run.job_progress_writer.write(u, (u + 1) * run.envs * run.horizon, rec, rec["lr"], rec["clip"])
 
 
 def torch_update(net, opt, b, last_val, epochs, minibatches, gen, gamma=0.99, lam=0.95, clip=0.2, adv_norm="batch"):
@@ -597,10 +643,12 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
           eval_every=0, eval_episodes=1, eval_envs=None, obs_filter=False, save_obs_filter=None,
           norm_reward=False, reward_clip=10.0, adv_norm="batch", perm="torch", timeout_bootstrap=False, hidden=64,
           save=None, save_every=0, save_best=None, resume=None, episode_log=None, episode_log_capacity=65536, best_window=0,
-          report=False, report_kl=False, progress=None, job_obs_filter=False, job_norm_reward=False):
+          report=False, report_kl=False, progress=None, job_obs_filter=False, job_norm_reward=False,
+          job_report=False, job_report_kl=False, job_progress=None, job_report_shards=False):
     config = run_config(**dict(locals()))  # (first statement: the arguments, nothing else)
     run = argparse.Namespace(**locals())  # the run record: the arguments and the config; build_run() and the bind step add the objects
     run.report = bool(report or report_kl or progress)  # (--report-kl and --progress imply --report)
+    run.job_report = bool(job_report or job_report_kl or job_progress or job_report_shards)  # (likewise)
     # check: every refusal on the host, then the file a run resumes from, before any device work (a wrong command line costs nothing)
     rank, world = job_ranks()
     check_train_arguments(run, world)
@@ -615,6 +663,7 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
                                                      job_obs_filter=job_obs_filter, job_norm_reward=job_norm_reward)
     run.eplog, run.epwriter = loop.bind_episode_log(run.env, episode_log, episode_log_capacity, 1, resume)
     run.progress_writer = loop.open_progress(progress, resume)
+    run.job_progress_writer = loop.open_progress(job_progress, resume) if rank == 0 else None  # (the job's file is rank 0's)
     if mode in ("graph", "pingpong"):
         capture_graphs(run)
     snapshots, evals, t_roll, t_upd, t_all0 = [], [], 0.0, 0.0, time.perf_counter()
@@ -624,8 +673,9 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
     state = LoopState(st0["episodes"], st0["sum_return"])
     if ckpt is not None:
         load_run(run, state, ckpt)
-        if run.progress_writer is not None:
-            run.progress_writer.cut_back(state.update)  # (the rows of updates the checkpoint has not seen are written again)
+        for writer in (run.progress_writer, run.job_progress_writer):
+            if writer is not None:
+                writer.cut_back(state.update)  # (the rows of updates the checkpoint has not seen are written again)
         log("resumed from %s: %d updates done, continuing at update %d of %d" % (resume, state.update + 1, state.update + 1, updates))
     start = state.update + 1
     for u in range(start, updates):
@@ -751,6 +801,16 @@ def make_arg_parser():
                     help="--norm-reward for a data-parallel job, one rank or more: the running std is that of the returns of all the "
                          "job's envs; the ranks gather one row of statistics per step once per rollout and chain them alike, "
                          "bit-identically (needs --mode native --update native; not together with --norm-reward)")
+    ap.add_argument("--job-report", action="store_true",
+                    help="--report for a data-parallel job, one rank or more: the record over the experience of all ranks, from one "
+                         "gathered row of sums per rank, bit-identical on every rank; rank 0 prints it (needs --mode native --update "
+                         "native; not together with --report / --report-kl / --progress)")
+    ap.add_argument("--job-report-kl", action="store_true",
+                    help="--report-kl for the job's record: one more policy forward over each rank's batch per update; implies --job-report")
+    ap.add_argument("--job-progress", default=None, metavar="FILE",
+                    help="rank 0 writes the job's record of every update to FILE as CSV (--progress's format); implies --job-report")
+    ap.add_argument("--job-report-shards", action="store_true",
+                    help="also print one line per rank: its shard's samples and explained variance; implies --job-report")
     ap.add_argument("--resume", default=None, metavar="FILE",
                     help="continue the run a checkpoint was saved from, bit for bit (needs --mode native --update native): repeat the "
                          "original command line; --updates stays the TOTAL and may be raised")
