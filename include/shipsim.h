@@ -1114,6 +1114,77 @@ int ssg_episode_log_append(ssg_handle *h, const ssg_episode_log *log, int K, int
                            const uint8_t *dev_done_KN, const uint8_t *dev_flags_KN /* nullable */, int64_t step_stride_envs, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Job-wide episode log (addition to ABI 9): the log of a data-parallel job, one gather per rollout
+ * The reference's SubprocVecEnv + Monitor + load_results give the per-episode rows over ALL workers' episodes
+ * (train/stable_baselines/ppo.py:7-8,25-52,122-123).  Rank r of W owns N_r envs, a contiguous range of global env ids in rank order;
+ * the ranks roll out in lockstep, so a call covers the same K rows from the same step0 on every rank.  The job's log is the log ONE
+ * ssg_episode_log_append would keep over the concatenated envs: records ranked by (row t ascending, global env ascending).
+ *
+ * The protocol.  lb_r[t] (t = 0..K) = the episodes that end on shard r in rows before t (lb_r[K] = count_r).  An episode of local rank
+ * q on shard r (its position in np.nonzero(done_r)) that ends in row t has the job rank
+ *     R = (q - lb_r[t]) + sum_{r' < r} lb_r'[t + 1] + sum_{r' >= r} lb_r'[t]
+ * and total = sum_r lb_r[K].  With head = dev_head[0] before the call the record goes to slot (head + R) % capacity unless
+ * R < total - capacity; then dev_head[0] = head + total and dev_head[1] = total.  Integers only, no scan across ranks.
+ *
+ * The shard block: one contiguous, 16-byte aligned buffer per rank and call —
+ *     ssg_episode_log_block_header (32 bytes) | int32 lb[rows + 1], zero past K, padded with zeros to 16 bytes | ssg_episode_record [stage]
+ * `rows` is the largest K of one call, `stage` (S) the record slots; both are the same on every rank and in every call of a log.  The
+ * episode of local rank q lives in slot q % S, and a rank ships its last S records of the call at most (q >= count_r - S).  With
+ * S = min(capacity, rows * ceil(total_envs / W)) nothing that the single log would keep is lost: a shard ends rows * N_r episodes per
+ * call at most, and a record below its shard's last `capacity` cannot survive in the job's ring.  Slots that no episode of the call
+ * owns are unspecified and never read.
+ *
+ * Launches.  ssg_job_episode_log_shard: four on `stream` — ssg_episode_log_append's count, scan and walk kernels as they are, on a staging
+ * ring of capacity S in the block's record region whose head is zero (the order contract already puts rank q at q % S and skips the
+ * ranks below count_r - S; the scanned workspace holds lb_r[t] at counts[t * tiles]), and between scan and walk one small kernel that
+ * packs the header and lb and zeroes the head the walk reads.  ssg_job_episode_log_merge_blocks: two — one lane per (block r, slot i) with
+ * i < min(count_r, S) recovers q (i itself, or the one q in [count_r - S, count_r) congruent to i), takes t = record.step - step0,
+ * forms R from the 2 W lb entries and stores the record with the walk's two 16-byte stores, reading dev_head as it stood; then one
+ * small launch advances dev_head.  No atomics, no host synchronisation.
+ * Memory safety does not rest on the blocks being well-formed: a record with t outside [0, K) or R outside [0, total) is skipped,
+ * lb is never indexed past `rows`, a negative count_r or total counts as 0.  Ranks that disagree on K or step0 are a caller error
+ * with in-bounds behaviour.
+ *
+ * Names.  The three calls are ssg_job_episode_log_*, not ssg_episode_log_*: that prefix belongs to the calls of ONE handle's log,
+ * ssg_episode_log_workspace_nbytes and ssg_episode_log_append, and tests/test_episode_log.py pins the header to exactly those two
+ * under it.  The calls below work on another object — a shard's block, the job's ring — and take the handle's record only for its
+ * carries, workspace, ring and head.  `rows` is at most SSG_EPISODE_LOG_MAX_CELLS in all three (a call's K * tiles is, and K <= rows
+ * needs no more).
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct ssg_episode_log_block_header {
+    int64_t count;    /* count_r: the episodes that end on the shard in the call */
+    int64_t step0;    /* the call's */
+    int32_t K;        /* the call's rows */
+    int32_t stage;    /* S */
+    int64_t reserved; /* 0 */
+} ssg_episode_log_block_header;
+
+/* Replaces nothing (host only).  The size of a shard block for calls of up to `rows` rows with `stage` record slots:
+ * 32 + 16 * ceil((rows + 1) / 4) + 32 * stage bytes.  SSG_ERR_BAD_ARG for NULL nbytes, rows outside 1..SSG_EPISODE_LOG_MAX_CELLS or
+ * stage < 1. */
+int ssg_job_episode_log_block_nbytes(int rows, int stage, size_t *nbytes);
+
+/* Replaces: Monitor's per-episode rows of ONE SubprocVecEnv worker's envs, before load_results merges the workers' files
+ * (train/stable_baselines/ppo.py:7-8,122-123).  Takes what ssg_episode_log_append takes, advances the shard's carries exactly as it
+ * does, and fills dev_block as described above; log->dev_records and log->dev_head (the job's ring) are not touched, the workspace is
+ * ssg_episode_log_append's.  Four launches on `stream`.  Refuses (SSG_ERR_BAD_ARG, nothing launched) everything
+ * ssg_episode_log_append refuses, and: n_members != 1; rows above SSG_EPISODE_LOG_MAX_CELLS; K > rows; stage < 1; a NULL dev_block or one that is not 16-byte aligned;
+ * block_nbytes below ssg_job_episode_log_block_nbytes(rows, stage); a block that overlaps the ring. */
+int ssg_job_episode_log_shard(ssg_handle *h, const ssg_episode_log *log, int K, int64_t step0, const double *dev_reward_KN,
+                              const uint8_t *dev_done_KN, const uint8_t *dev_flags_KN /* nullable */, int64_t step_stride_envs, int rows,
+                              int stage, void *dev_block, size_t block_nbytes, void *stream);
+
+/* Replaces: load_results' merge of the workers' monitor files into one table (train/stable_baselines/ppo.py:7-8,38-40) — for the
+ * n_blocks shard blocks of one call, stacked in rank order (ssg_job_episode_log_block_nbytes(rows, stage) bytes apart), as described
+ * above: two launches on `stream`.  Of the record it uses dev_records, capacity and dev_head alone.  Every rank that merges the same
+ * blocks into the same ring and head holds the same bits.  Refuses (SSG_ERR_BAD_ARG, nothing launched, head and ring untouched): a
+ * NULL handle or record; struct_size mismatch; capacity < 1; n_members != 1; NULL dev_records, dev_head or dev_blocks; a dev_records
+ * or dev_blocks that is not 16-byte aligned, a dev_head that is not 8-byte aligned; n_blocks outside 1..SSG_DP_MAX_SHARDS; K < 1 or
+ * K > rows; rows above SSG_EPISODE_LOG_MAX_CELLS; stage < 1; blocks that overlap the ring or the head. */
+int ssg_job_episode_log_merge_blocks(ssg_handle *h, const ssg_episode_log *log, int K, int64_t step0, int rows, int stage,
+                                     const void *dev_blocks, int n_blocks, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Observation filter (ABI 9 addition): a running mean / std per observation column, kept and applied on the device
  * The reference's RLlib trainers run "PPO" with its defaults (train/rllib/pbt.py:50, train/rllib/ppo.py:28), which in the RLlib
  * generation those scripts are written for include observation_filter = "MeanStdFilter"; Stable-Baselines users wrap the SubprocVecEnv

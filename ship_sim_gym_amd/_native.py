@@ -81,6 +81,7 @@ EXPORTS = (
     "ssg_ppo_adv_moments", "ssg_ppo_set_adv_moments", "ssg_ppo_apply_shards",
     "ssg_render_envs", "ssg_set_eval_recorder", "ssg_get_eval_recorder",
     "ssg_episode_log_workspace_nbytes", "ssg_episode_log_append",
+    "ssg_job_episode_log_block_nbytes", "ssg_job_episode_log_shard", "ssg_job_episode_log_merge_blocks",
     "ssg_report_clip_bounds", "ssg_ppo_report_workspace_nbytes", "ssg_ppo_report", "ssg_pop_report",
     "ssg_ppo_report_sums", "ssg_ppo_report_rows",
 )
@@ -363,6 +364,10 @@ def lib():
     L.ssg_get_eval_recorder.argtypes = [vp, C.POINTER(EvalRecorderRecord)]
     L.ssg_episode_log_workspace_nbytes.argtypes = [C.c_int, C.c_int, szp]
     L.ssg_episode_log_append.argtypes = [vp, C.POINTER(EpisodeLogRecord), C.c_int, C.c_int64, vp, vp, vp, C.c_int64, vp]
+    L.ssg_job_episode_log_block_nbytes.argtypes = [C.c_int, C.c_int, szp]
+    L.ssg_job_episode_log_shard.argtypes = [vp, C.POINTER(EpisodeLogRecord), C.c_int, C.c_int64, vp, vp, vp, C.c_int64, C.c_int, C.c_int, vp,
+                                            C.c_size_t, vp]
+    L.ssg_job_episode_log_merge_blocks.argtypes = [vp, C.POINTER(EpisodeLogRecord), C.c_int, C.c_int64, C.c_int, C.c_int, vp, C.c_int, vp]
     L.ssg_report_clip_bounds.argtypes = [C.c_double, C.POINTER(C.c_float)]
     L.ssg_ppo_report_workspace_nbytes.argtypes = [C.c_int, C.c_int, szp]
     L.ssg_ppo_report.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_double, vp, C.c_int, C.c_int, vp, C.c_size_t, vp, vp]

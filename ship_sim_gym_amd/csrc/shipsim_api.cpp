@@ -2825,10 +2825,11 @@ int ssg_episode_log_workspace_nbytes(int n_envs, int K, size_t *nbytes)
     return SSG_OK;
 }
 
-int ssg_episode_log_append(ssg_handle *h, const ssg_episode_log *log, int K, int64_t step0, const double *dev_reward_KN,
-                           const uint8_t *dev_done_KN, const uint8_t *dev_flags_KN, int64_t step_stride_envs, void *stream)
+// What ssg_episode_log_append asks, in its order, and its launch record; ssg_job_episode_log_shard asks the same first.
+static int check_episode_log(ssg_handle *h, const ssg_episode_log *log, int K, int64_t step0, const double *dev_reward_KN,
+                             const uint8_t *dev_done_KN, const uint8_t *dev_flags_KN, int64_t step_stride_envs, const std::string &w,
+                             ssg::EpisodeLogLaunch &l)
 {
-    const std::string w("ssg_episode_log_append");
     char buf[200];
     if (!h) return fail(nullptr, SSG_ERR_BAD_ARG, w + ": NULL handle");
     if (!log) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL ssg_episode_log");
@@ -2837,7 +2838,7 @@ int ssg_episode_log_append(ssg_handle *h, const ssg_episode_log *log, int K, int
     const int P = log->n_members, N = h->cfg.n_envs;
     if (P < 1 || P > SSG_POP_MAX_MEMBERS) return fail(h, SSG_ERR_BAD_ARG, w + ": n_members must be in 1..SSG_POP_MAX_MEMBERS");
     ssg::MemberLayout lay;
-    int rc = member_layout(h, P, "ssg_episode_log_append", true, lay); // (asked for one member too, which then owns the whole handle)
+    int rc = member_layout(h, P, w.c_str(), true, lay); // (asked for one member too, which then owns the whole handle)
     if (rc != SSG_OK) return rc;
     if (P == 1) lay = whole_layout(h);
     if (!log->dev_records || !log->dev_head || !log->dev_carry_return || !log->dev_carry || !log->dev_workspace)
@@ -2855,9 +2856,6 @@ int ssg_episode_log_append(ssg_handle *h, const ssg_episode_log *log, int K, int
         std::snprintf(buf, sizeof buf, ": workspace_nbytes %zu < %zu (ssg_episode_log_workspace_nbytes)", log->workspace_nbytes, need);
         return fail(h, SSG_ERR_BAD_ARG, w + buf);
     }
-    rc = check_ready(h, false);
-    if (rc != SSG_OK) return rc;
-    ssg::EpisodeLogLaunch l;
     l.K = K;
     l.N = N;
     l.stride = (size_t)step_stride_envs;
@@ -2873,8 +2871,92 @@ int ssg_episode_log_append(ssg_handle *h, const ssg_episode_log *log, int K, int
     l.head = log->dev_head;
     l.workspace = log->dev_workspace;
     l.records = log->dev_records;
+    return SSG_OK;
+}
+
+int ssg_episode_log_append(ssg_handle *h, const ssg_episode_log *log, int K, int64_t step0, const double *dev_reward_KN,
+                           const uint8_t *dev_done_KN, const uint8_t *dev_flags_KN, int64_t step_stride_envs, void *stream)
+{
+    ssg::EpisodeLogLaunch l;
+    int rc = check_episode_log(h, log, K, step0, dev_reward_KN, dev_done_KN, dev_flags_KN, step_stride_envs, "ssg_episode_log_append", l);
+    if (rc != SSG_OK) return rc;
+    rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
     hipError_t e = ssg::launch_episode_log(l, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("episode log launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+// ABI 9 addition: the job-wide episode log.  The same order: the arguments (BAD_ARG), then the handle's state blob and the device.
+int ssg_job_episode_log_block_nbytes(int rows, int stage, size_t *nbytes)
+{
+    if (!nbytes || rows < 1 || rows > SSG_EPISODE_LOG_MAX_CELLS || stage < 1)
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_job_episode_log_block_nbytes: NULL nbytes, rows outside 1..SSG_EPISODE_LOG_MAX_CELLS or stage < 1");
+    *nbytes = ssg::episode_log_block_bytes(rows, stage);
+    return SSG_OK;
+}
+
+// [p, p + n) against the ring and the head of `log`
+static bool overlaps_ring(const ssg_episode_log *log, const void *p, size_t n)
+{
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(p), b1 = b0 + n;
+    const uintptr_t r0 = reinterpret_cast<uintptr_t>(log->dev_records), r1 = r0 + (uintptr_t)log->capacity * sizeof(ssg_episode_record);
+    const uintptr_t h0 = reinterpret_cast<uintptr_t>(log->dev_head), h1 = h0 + 2 * sizeof(int64_t);
+    return (b0 < r1 && r0 < b1) || (b0 < h1 && h0 < b1);
+}
+
+int ssg_job_episode_log_shard(ssg_handle *h, const ssg_episode_log *log, int K, int64_t step0, const double *dev_reward_KN,
+                              const uint8_t *dev_done_KN, const uint8_t *dev_flags_KN, int64_t step_stride_envs, int rows, int stage,
+                              void *dev_block, size_t block_nbytes, void *stream)
+{
+    const std::string w("ssg_job_episode_log_shard");
+    char buf[200];
+    ssg::EpisodeLogLaunch l;
+    int rc = check_episode_log(h, log, K, step0, dev_reward_KN, dev_done_KN, dev_flags_KN, step_stride_envs, w, l);
+    if (rc != SSG_OK) return rc;
+    if (log->n_members != 1) return fail(h, SSG_ERR_BAD_ARG, w + ": a job-wide log has one member (n_members != 1)");
+    if (rows > SSG_EPISODE_LOG_MAX_CELLS) return fail(h, SSG_ERR_BAD_ARG, w + ": rows above SSG_EPISODE_LOG_MAX_CELLS");
+    if (rows < 1 || K > rows) return fail(h, SSG_ERR_BAD_ARG, w + ": K must be in 1..rows");
+    if (stage < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": stage < 1");
+    if (!dev_block) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_block");
+    if (reinterpret_cast<uintptr_t>(dev_block) % 16 != 0) return fail(h, SSG_ERR_BAD_ARG, w + ": dev_block must be 16-byte aligned");
+    const size_t need = ssg::episode_log_block_bytes(rows, stage);
+    if (block_nbytes < need) {
+        std::snprintf(buf, sizeof buf, ": block_nbytes %zu < %zu (ssg_job_episode_log_block_nbytes)", block_nbytes, need);
+        return fail(h, SSG_ERR_BAD_ARG, w + buf);
+    }
+    if (overlaps_ring(log, dev_block, need)) return fail(h, SSG_ERR_BAD_ARG, w + ": the block overlaps the ring or the head");
+    rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_episode_log_shard(l, rows, stage, dev_block, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("episode log shard launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+int ssg_job_episode_log_merge_blocks(ssg_handle *h, const ssg_episode_log *log, int K, int64_t step0, int rows, int stage, const void *dev_blocks,
+                                     int n_blocks, void *stream)
+{
+    const std::string w("ssg_job_episode_log_merge_blocks");
+    if (!h) return fail(nullptr, SSG_ERR_BAD_ARG, w + ": NULL handle");
+    if (!log) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL ssg_episode_log");
+    if (log->struct_size != sizeof(ssg_episode_log)) return fail(h, SSG_ERR_BAD_ARG, w + ": ssg_episode_log.struct_size != sizeof(ssg_episode_log)");
+    if (log->capacity < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": capacity < 1");
+    if (log->n_members != 1) return fail(h, SSG_ERR_BAD_ARG, w + ": a job-wide log has one member (n_members != 1)");
+    if (!log->dev_records || !log->dev_head || !dev_blocks) return fail(h, SSG_ERR_BAD_ARG, w + ": NULL dev_records, dev_head or dev_blocks");
+    if (reinterpret_cast<uintptr_t>(log->dev_records) % 16 != 0 || reinterpret_cast<uintptr_t>(dev_blocks) % 16 != 0 ||
+        reinterpret_cast<uintptr_t>(log->dev_head) % 8 != 0)
+        return fail(h, SSG_ERR_BAD_ARG, w + ": dev_records and dev_blocks must be 16-byte aligned, dev_head 8-byte aligned");
+    if (n_blocks < 1 || n_blocks > SSG_DP_MAX_SHARDS) return fail(h, SSG_ERR_BAD_ARG, w + ": n_blocks must be in 1..SSG_DP_MAX_SHARDS");
+    if (rows > SSG_EPISODE_LOG_MAX_CELLS) return fail(h, SSG_ERR_BAD_ARG, w + ": rows above SSG_EPISODE_LOG_MAX_CELLS");
+    if (rows < 1 || K < 1 || K > rows) return fail(h, SSG_ERR_BAD_ARG, w + ": K must be in 1..rows");
+    if (stage < 1) return fail(h, SSG_ERR_BAD_ARG, w + ": stage < 1");
+    if (overlaps_ring(log, dev_blocks, (size_t)n_blocks * ssg::episode_log_block_bytes(rows, stage)))
+        return fail(h, SSG_ERR_BAD_ARG, w + ": the blocks overlap the ring or the head");
+    const int rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_episode_log_merge(K, step0, rows, stage, dev_blocks, n_blocks, log->dev_records, log->capacity, log->dev_head,
+                                                 static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("episode log merge launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
 

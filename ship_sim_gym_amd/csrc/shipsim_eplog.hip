@@ -1,5 +1,5 @@
-// shipsim_eplog.hip — the episode log: ssg_episode_log_append (include/shipsim.h), in an object of its own so that every other
-// object's device code stays what it is.
+// shipsim_eplog.hip — the episode log: ssg_episode_log_append and the job-wide log's ssg_job_episode_log_shard / ssg_job_episode_log_merge_blocks
+// (include/shipsim.h), in an object of its own so that every other object's device code stays what it is.
 //
 // What Monitor does on the host for one env (train/stable_baselines/ppo.py:7-8,38-40: one (r, l, t) row per finished episode), for the
 // [K][N] reward / done / flags rows of a rollout on the device: every episode that ends in the block becomes one 32-byte record in the
@@ -77,7 +77,8 @@ __global__ void __launch_bounds__(kLogTile) eplog_scan_kernel(int cells, int32_t
         const long long old = head[0];
         hdr[0] = old;
         hdr[1] = total;
-        head[0] = old + total;
+        // (unsigned: the shard call's staging head holds whatever bytes the caller's block did, and the sum may wrap)
+        head[0] = (long long)((unsigned long long)old + (unsigned long long)total);
         head[1] = total;
     }
 }
@@ -190,21 +191,99 @@ __global__ void __launch_bounds__(kLogTile) eplog_walk_kernel(const LogWalk a)
     }
 }
 
-} // namespace
+// ---- the job-wide log (include/shipsim.h, "Job-wide episode log") ----------------------------------------------------------------------
+// A shard block, as the kernels see it: the header, lb and the record slots.
+struct LogBlock {
+    int rows, stage;
+    size_t lb_bytes, bytes; // of lb with its padding; of the whole block
+};
+__device__ __forceinline__ const int32_t *block_lb(const char *b) { return reinterpret_cast<const int32_t *>(b + sizeof(ssg_episode_log_block_header)); }
 
-size_t episode_log_workspace_bytes(int n_envs, int K) { return 16 + 4 * (size_t)K * (size_t)filter_tiles(n_envs); }
-
-hipError_t launch_episode_log(const EpisodeLogLaunch &l, hipStream_t stream)
+// (d) the shard call's pack, between scan and walk, grid (ceil(lb entries / 256)): the scan left lb_r[t] at counts[t * tiles] and the
+// call's count in hdr[1], and used the block's header as the staging ring's head (scratch: it held whatever the caller left there).
+// Lane j writes lb[j] — counts[j * tiles] below K, the count at K, zero past it, padding included —, and lane 0 the header and
+// hdr[0] = 0: the head the walk reads, so that local rank q meets slot q % stage.  Plain vector stores.
+__global__ void __launch_bounds__(kLogTile) eplog_pack_kernel(int K, int tiles, long long step0, int stage, int lb_n, const int32_t *__restrict__ counts,
+                                                              long long *__restrict__ hdr, char *__restrict__ block)
 {
-    const int tiles = filter_tiles(l.N), cells = l.K * tiles;
-    long long *hdr = static_cast<long long *>(l.workspace);
-    int32_t *counts = reinterpret_cast<int32_t *>(hdr + 2);
-    hipLaunchKernelGGL(eplog_count_kernel, dim3(cells), dim3(kLogTile), 0, stream, l.N, tiles, l.stride, l.done, counts);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(eplog_scan_kernel, dim3(1), dim3(kLogTile), 0, stream, cells, counts, hdr, reinterpret_cast<long long *>(l.head));
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    const int j = blockIdx.x * kLogTile + (int)threadIdx.x;
+    const long long count = hdr[1];
+    if (j < lb_n) {
+        int32_t *lb = reinterpret_cast<int32_t *>(block + sizeof(ssg_episode_log_block_header));
+        lb[j] = j < K ? counts[(size_t)j * tiles] : (j == K ? (int32_t)count : 0);
+    }
+    if (j == 0) {
+        long long *bh = reinterpret_cast<long long *>(block);
+        bh[0] = count;
+        bh[1] = step0;
+        bh[2] = (long long)(unsigned)K | ((long long)stage << 32); // int32 K, int32 stage
+        bh[3] = 0;
+        hdr[0] = 0;
+    }
+}
+
+struct LogMerge {
+    int K, n_blocks;
+    long long step0, capacity;
+    LogBlock g;
+    const char *blocks;
+    const long long *head;
+    uint4 *records;
+};
+
+// the call's total, from every block's lb[K] (K <= rows: inside lb); never below 0
+__device__ __forceinline__ long long merge_total(const LogMerge &a)
+{
+    long long total = 0;
+    for (int r = 0; r < a.n_blocks; ++r) total += block_lb(a.blocks + (size_t)r * a.g.bytes)[a.K];
+    return total > 0 ? total : 0;
+}
+
+// (e) grid (ceil(stage / 256), n_blocks): one lane per (block r, slot i).  Everything a lane indexes is bounded by the call's own
+// arguments, never by what a block says: i < stage, t in [0, K) before lb[t + 1] is read (K <= rows), R in [0, total) before the
+// store, the slot taken modulo the capacity from non-negative terms.
+__global__ void __launch_bounds__(kLogTile) eplog_merge_kernel(const LogMerge a)
+{
+    const int r = blockIdx.y, i = blockIdx.x * kLogTile + (int)threadIdx.x;
+    if (i >= a.g.stage) return;
+    const char *b = a.blocks + (size_t)r * a.g.bytes;
+    long long cnt = reinterpret_cast<const long long *>(b)[0];
+    if (cnt < 0) cnt = 0;
+    const long long S = a.g.stage;
+    if ((long long)i >= (cnt < S ? cnt : S)) return;
+    long long q = i;
+    if (cnt > S) { // the one q in [cnt - S, cnt) congruent to i
+        const long long base = cnt - S;
+        q = base + ((long long)i - base % S + S) % S;
+    }
+    const uint4 *slot = reinterpret_cast<const uint4 *>(b + sizeof(ssg_episode_log_block_header) + a.g.lb_bytes) + 2 * (size_t)i;
+    const uint4 q0 = slot[0], q1 = slot[1];
+    const long long step = (long long)(((unsigned long long)q0.w << 32) | (unsigned long long)q0.z);
+    const long long t = step - a.step0;
+    if (t < 0 || t >= (long long)a.K) return;
+    long long R = q - (long long)block_lb(b)[t];
+    for (int v = 0; v < a.n_blocks; ++v) R += (long long)block_lb(a.blocks + (size_t)v * a.g.bytes)[v < r ? t + 1 : t];
+    const long long total = merge_total(a);
+    if (R < 0 || R >= total || R < total - a.capacity) return;
+    long long h0 = a.head[0] % a.capacity;
+    if (h0 < 0) h0 += a.capacity;
+    const long long dst = (h0 + R % a.capacity) % a.capacity;
+    a.records[2 * dst] = q0;
+    a.records[2 * dst + 1] = q1;
+}
+
+// (f) one lane, after (e) on the stream: the head moves once every record has read it.
+__global__ void eplog_merge_head_kernel(const LogMerge a, long long *__restrict__ head)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const long long total = merge_total(a);
+        head[0] += total;
+        head[1] = total;
+    }
+}
+
+LogWalk walk_args(const EpisodeLogLaunch &l, int tiles, const long long *hdr, const int32_t *counts)
+{
     LogWalk a;
     a.K = l.K;
     a.N = l.N;
@@ -224,8 +303,79 @@ hipError_t launch_episode_log(const EpisodeLogLaunch &l, hipStream_t stream)
     a.hdr = hdr;
     a.base = counts;
     a.records = reinterpret_cast<uint4 *>(l.records);
-    if (l.flags) hipLaunchKernelGGL(eplog_walk_kernel<true>, dim3(tiles), dim3(kLogTile), 0, stream, a);
-    else hipLaunchKernelGGL(eplog_walk_kernel<false>, dim3(tiles), dim3(kLogTile), 0, stream, a);
+    return a;
+}
+
+hipError_t launch_walk(const LogWalk &a, hipStream_t stream)
+{
+    if (a.flags) hipLaunchKernelGGL(eplog_walk_kernel<true>, dim3(a.tiles), dim3(kLogTile), 0, stream, a);
+    else hipLaunchKernelGGL(eplog_walk_kernel<false>, dim3(a.tiles), dim3(kLogTile), 0, stream, a);
+    return hipGetLastError();
+}
+
+} // namespace
+
+size_t episode_log_workspace_bytes(int n_envs, int K) { return 16 + 4 * (size_t)K * (size_t)filter_tiles(n_envs); }
+
+hipError_t launch_episode_log(const EpisodeLogLaunch &l, hipStream_t stream)
+{
+    const int tiles = filter_tiles(l.N), cells = l.K * tiles;
+    long long *hdr = static_cast<long long *>(l.workspace);
+    int32_t *counts = reinterpret_cast<int32_t *>(hdr + 2);
+    hipLaunchKernelGGL(eplog_count_kernel, dim3(cells), dim3(kLogTile), 0, stream, l.N, tiles, l.stride, l.done, counts);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(eplog_scan_kernel, dim3(1), dim3(kLogTile), 0, stream, cells, counts, hdr, reinterpret_cast<long long *>(l.head));
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_walk(walk_args(l, tiles, hdr, counts), stream);
+}
+
+hipError_t launch_episode_log_shard(const EpisodeLogLaunch &l, int rows, int stage, void *block, hipStream_t stream)
+{
+    const int tiles = filter_tiles(l.N), cells = l.K * tiles;
+    long long *hdr = static_cast<long long *>(l.workspace);
+    int32_t *counts = reinterpret_cast<int32_t *>(hdr + 2);
+    char *b = static_cast<char *>(block);
+    const size_t lb_bytes = episode_log_block_lb_bytes(rows);
+    const int lb_n = (int)(lb_bytes / 4);
+    hipLaunchKernelGGL(eplog_count_kernel, dim3(cells), dim3(kLogTile), 0, stream, l.N, tiles, l.stride, l.done, counts);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    // (the staging head is the block's header, scratch until the pack: the scan adds the count to whatever bytes it holds, in unsigned
+    // arithmetic, and the pack overwrites both words; a zeroed pair would cost a launch of its own, the workspace has no word to spare)
+    hipLaunchKernelGGL(eplog_scan_kernel, dim3(1), dim3(kLogTile), 0, stream, cells, counts, hdr, reinterpret_cast<long long *>(b));
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(eplog_pack_kernel, dim3((lb_n + kLogTile - 1) / kLogTile), dim3(kLogTile), 0, stream, l.K, tiles, l.step0, stage, lb_n,
+                       counts, hdr, b);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    LogWalk a = walk_args(l, tiles, hdr, counts);
+    a.capacity = stage;
+    a.records = reinterpret_cast<uint4 *>(b + sizeof(ssg_episode_log_block_header) + lb_bytes);
+    return launch_walk(a, stream);
+}
+
+hipError_t launch_episode_log_merge(int K, long long step0, int rows, int stage, const void *blocks, int n_blocks,
+                                    ssg_episode_record *records, long long capacity, int64_t *head, hipStream_t stream)
+{
+    LogMerge a;
+    a.K = K;
+    a.n_blocks = n_blocks;
+    a.step0 = step0;
+    a.capacity = capacity;
+    a.g.rows = rows;
+    a.g.stage = stage;
+    a.g.lb_bytes = episode_log_block_lb_bytes(rows);
+    a.g.bytes = episode_log_block_bytes(rows, stage);
+    a.blocks = static_cast<const char *>(blocks);
+    a.head = reinterpret_cast<const long long *>(head);
+    a.records = reinterpret_cast<uint4 *>(records);
+    hipLaunchKernelGGL(eplog_merge_kernel, dim3((stage + kLogTile - 1) / kLogTile, n_blocks), dim3(kLogTile), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(eplog_merge_head_kernel, dim3(1), dim3(64), 0, stream, a, reinterpret_cast<long long *>(head));
     return hipGetLastError();
 }
 

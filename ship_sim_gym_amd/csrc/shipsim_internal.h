@@ -513,6 +513,18 @@ struct EpisodeLogLaunch {
     ssg_episode_record *records; // [capacity]
 };
 hipError_t launch_episode_log(const EpisodeLogLaunch &l, hipStream_t stream);
+// the job-wide log's shard block: the header, int32 lb[rows + 1] padded to 16 bytes, then `stage` records
+inline size_t episode_log_block_lb_bytes(int rows) { return (((size_t)rows + 1) * 4 + 15) & ~(size_t)15; }
+inline size_t episode_log_block_bytes(int rows, int stage)
+{
+    return sizeof(ssg_episode_log_block_header) + episode_log_block_lb_bytes(rows) + sizeof(ssg_episode_record) * (size_t)stage;
+}
+// One shard call's four launches (count, scan, pack, walk): launch_episode_log's three on a staging ring of `stage` slots with head 0
+// in the block's record region, and the pack of the header and lb.  l.records, l.head and l.capacity are not read.
+hipError_t launch_episode_log_shard(const EpisodeLogLaunch &l, int rows, int stage, void *block, hipStream_t stream);
+// One merge call's two launches: the records of the n_blocks stacked blocks into records[(head + R) % capacity], then the head.
+hipError_t launch_episode_log_merge(int K, long long step0, int rows, int stage, const void *blocks, int n_blocks,
+                                    ssg_episode_record *records, long long capacity, int64_t *head, hipStream_t stream);
 // the update report (shipsim_report.hip): the scratch holds the walk's partials, f64 [members][ppo_gae_blocks(widest slice)][kReportSums]
 // = sums of ret, ret^2, ret - val, (ret - val)^2, val, adv, d, d^2 and the clipped count
 constexpr int kReportSums = 9;

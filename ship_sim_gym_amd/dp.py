@@ -25,6 +25,10 @@ The update report of such a job is ``job_report`` (ship_sim_gym_amd/report.py): 
 are all-gathered once per update, and every rank forms the same record from them in rank order, replayable in one process with
 ``report_row`` / ``report_rows`` and torch.stack.  ``report`` stays the rank's own shard's.
 
+The episode log of such a job is ship_sim_gym_amd/episode_log.py's ``EpisodeLog(job=True)``: every rank packs its shard's finished
+episodes of a rollout into one fixed-size block, the blocks are all-gathered once, and every rank merges them into the same ring in the
+order one log over all the job's envs would keep, replayable in one process with ``shard_block`` / ``merge_blocks`` and torch.stack.
+
 Out of scope: adv_norm="minibatch" across ranks, resuming a multi-rank run,
 populations across ranks, overlapping the gather with the next gradient, running this loop from C.
 """

@@ -7,10 +7,18 @@ The reference's Stable-Baselines script wraps its envs in ``Monitor`` and reads 
 its end.  ``records()`` brings the ring to the host, in append order.  ``MonitorWriter`` writes Stable-Baselines' monitor file from it.
 The order of the records, and everything else about a call, is defined in include/shipsim.h (section "Episode log").
 
-Out of scope: merged logs across ranks or handles, evaluation episodes (``NativeEvaluator`` has its own accounting), per-episode
-wall-clock times, a TensorBoard writer.
+``EpisodeLog(..., job=True, rows=K)`` is the log of one rank of a data-parallel job (ship_sim_gym_amd/dp.py): the ring is the JOB's, the
+one a single ``EpisodeLog`` over the envs of all ranks would keep — what ``SubprocVecEnv`` + ``Monitor`` + ``load_results`` give the
+reference over all its workers (train/stable_baselines/ppo.py:7-8,25-52,122-123).  A rank packs its shard's episodes of a rollout into
+one fixed-size block (``shard_block``), the blocks are all-gathered once, and every rank merges them with the same integer arithmetic
+(``merge_blocks``), so all ranks hold the same bits; ``job_append`` is the two around the gather.  The halves are public so that one
+process can replay a W-rank job with ``torch.stack`` of the shards' blocks as the gather.  The carries stay this rank's envs'.
 
-``episode_log_reference`` is a numpy restatement of the library call, for tests.
+Out of scope: populations or member bits across ranks, evaluation episodes (``NativeEvaluator`` has its own accounting), a
+variable-size gather (it needs a host synchronisation to size), per-episode wall-clock times, a TensorBoard writer.
+
+``episode_log_reference`` is a numpy restatement of the library call, for tests; ``shard_block_reference`` and
+``merge_blocks_reference`` restate the two halves of the job's call.
 """
 import ctypes as C
 import json
@@ -92,15 +100,117 @@ def episode_log_reference(rew, done, flags, carry_ret, carry, head, ring, step0=
     return ring, head, cret, c
 
 
+# the shard block of a job's log (include/shipsim.h, "Job-wide episode log"): a 32-byte header, int32 lb[rows + 1] padded to 16 bytes,
+# then `stage` record slots
+BLOCK_HEADER_DTYPE = np.dtype([("count", "<i8"), ("step0", "<i8"), ("K", "<i4"), ("stage", "<i4"), ("reserved", "<i8")])
+BLOCK_HEADER_BYTES = 32
+assert BLOCK_HEADER_DTYPE.itemsize == BLOCK_HEADER_BYTES
+
+
+def job_stage(capacity, rows, total_envs, world):
+    """S, the record slots of a shard block: min(capacity, rows * ceil(total_envs / world)) — the same on every rank."""
+    return min(int(capacity), int(rows) * ((int(total_envs) + int(world) - 1) // int(world)))
+
+
+def block_layout(rows, stage):
+    """(lb entries with the padding, offset of the records, bytes of the block) — what ssg_job_episode_log_block_nbytes answers."""
+    rows, stage = int(rows), int(stage)
+    if rows < 1 or stage < 1:
+        raise ValueError("block_layout: rows and stage must be >= 1")
+    lb_n = (rows + 1 + 3) // 4 * 4
+    rec_off = BLOCK_HEADER_BYTES + 4 * lb_n
+    return lb_n, rec_off, rec_off + RECORD_BYTES * stage
+
+
+def block_views(block, rows, stage):
+    """(header [1], lb int32 [padded rows + 1], slots RECORD_DTYPE [stage]): numpy views of one block (a uint8 array of its size)."""
+    lb_n, rec_off, nbytes = block_layout(rows, stage)
+    block = np.asarray(block)
+    if block.dtype != np.uint8 or block.ndim != 1 or block.shape[0] != nbytes:
+        raise ValueError("block_views: a block of rows = %d and stage = %d is uint8 [%d] (got %s %s)" % (rows, stage, nbytes, block.dtype, block.shape))
+    return (block[:BLOCK_HEADER_BYTES].view(BLOCK_HEADER_DTYPE), block[BLOCK_HEADER_BYTES:rec_off].view("<i4"),
+            block[rec_off:].view(RECORD_DTYPE))
+
+
+def block_owned_slots(count, stage):
+    """The slots of a block that the call's episodes own: local rank q lives in slot q % stage, for q in [max(0, count - stage), count)."""
+    count, stage = int(count), int(stage)
+    return np.sort(np.arange(max(0, count - stage), count, dtype=np.int64) % stage)
+
+
+def shard_block_reference(rew, done, flags, carry_ret, carry, rows, stage, step0=0, env_base=0):
+    """What ssg_job_episode_log_shard leaves, in numpy: episode_log_reference over a staging ring of `stage` slots with head 0, packed with
+    the header and lb[t] = the episodes that end on the shard in rows before t (lb[K] = count; zero past K).  Slots that no episode of
+    the call owns are zero here and unspecified on the device (block_owned_slots names the others).
+    Returns (block uint8 [nbytes], carry_ret, carry)."""
+    done = np.asarray(done)
+    K = int(done.shape[0])
+    if K < 1 or K > int(rows):
+        raise ValueError("shard_block_reference: K = %d outside 1..rows = %d" % (K, int(rows)))
+    lb_n, rec_off, nbytes = block_layout(rows, stage)
+    ring, head, cret, c = episode_log_reference(rew, done, flags, carry_ret, carry, np.zeros(2, dtype=np.int64),
+                                                np.zeros(int(stage), dtype=RECORD_DTYPE), step0=step0, env_base=env_base)
+    block = np.zeros(nbytes, dtype=np.uint8)
+    hdr, lb, slots = block_views(block, rows, stage)
+    hdr[0] = (int(head[1]), int(step0), K, int(stage), 0)
+    lb[1:K + 1] = np.cumsum(np.count_nonzero(done, axis=1))
+    owned = block_owned_slots(int(head[1]), stage)
+    slots[owned] = ring[owned]
+    return block, cret, c
+
+
+def merge_blocks_reference(blocks, ring, head, K, step0, rows, stage):
+    """What ssg_job_episode_log_merge_blocks leaves, in numpy.  blocks uint8 [W, nbytes], the shards' blocks in rank order; ring a
+    RECORD_DTYPE array [capacity]; head int64 [2].  For block r and slot i < min(count_r, stage): q = i, or the one q in
+    [count_r - stage, count_r) congruent to i; t = step - step0; the job's rank
+        R = (q - lb_r[t]) + sum_{r' < r} lb_r'[t + 1] + sum_{r' >= r} lb_r'[t]
+    and total = sum_r lb_r[K] (not below 0).  The record goes to slot (head[0] + R) % capacity unless t is outside [0, K), R outside
+    [0, total) or R < total - capacity.  Then head[0] += total, head[1] = total.  Returns new (ring, head)."""
+    blocks = np.asarray(blocks)
+    K, step0, rows, stage = int(K), int(step0), int(rows), int(stage)
+    if blocks.ndim != 2 or blocks.shape[0] < 1 or K < 1 or K > rows:
+        raise ValueError("merge_blocks_reference: blocks must be uint8 [W >= 1, nbytes] and K in 1..rows")
+    ring, head = np.array(ring, dtype=RECORD_DTYPE), np.array(head, dtype=np.int64).reshape(2)
+    cap = int(ring.shape[0])
+    views = [block_views(b, rows, stage) for b in blocks]
+    lbs = np.stack([v[1].astype(np.int64) for v in views])  # [W, padded rows + 1]
+    total = max(0, int(lbs[:, K].sum()))
+    head0 = int(head[0])
+    for r, (hdr, _, slots) in enumerate(views):
+        cnt = max(0, int(hdr["count"][0]))
+        for i in range(min(cnt, stage)):
+            q = i
+            if cnt > stage:
+                base = cnt - stage
+                q = base + (i - base % stage) % stage
+            rec = slots[i]
+            t = int(rec["step"]) - step0
+            if t < 0 or t >= K:
+                continue
+            R = (q - int(lbs[r, t])) + int(lbs[:r, t + 1].sum()) + int(lbs[r:, t].sum())
+            if R < 0 or R >= total or R < total - cap:
+                continue
+            ring[(head0 % cap + R) % cap] = rec
+    head[0] = head0 + total
+    head[1] = total
+    return ring, head
+
+
 class EpisodeLog(object):
     """The episode log of `env` (a ShipVecEnv): owns the ring of `capacity` records with its head, the per-env carries (return f64
     [N]; length and goal events int32 [N, 2]) and the workspace, all on the env's device, and counts the steps it has seen (``steps``:
     step0 of the next call, part of its state).  n_members: 1 for a single policy, P for a population — a record then names the member
     that owned the env when the episode ended (the equal split, or the slices bound to the env).
 
-    Nothing is bound to the env: call ``append(batch)`` after every rollout.  Call ``reset_carry()`` after resetting the envs by hand."""
+    Nothing is bound to the env: call ``append(batch)`` after every rollout.  Call ``reset_carry()`` after resetting the envs by hand.
 
-    def __init__(self, env, capacity=65536, n_members=1):
+    job=True (one member only), rows=K: the log of one rank of a data-parallel job (include/shipsim.h, "Job-wide episode log").  The ring
+    and the head are the JOB's, the same bits on every rank; the carries stay this rank's envs'.  rows is the largest K of one call
+    (the rollout length).  The job's size and its total env count come from the process group (`group`; None: the default one; with
+    none initialised the job is this process, W = 1), over which the ranks' env counts are gathered once — or from `world` and
+    `total_envs`, given together, when one process replays a W-rank job.  Call ``job_append(batch)`` after every rollout."""
+
+    def __init__(self, env, capacity=65536, n_members=1, job=False, rows=None, world=None, total_envs=None, group=None):
         torch = _torch()
         cap, P = int(capacity), int(n_members)
         if cap < 1:
@@ -109,6 +219,36 @@ class EpisodeLog(object):
             raise ValueError("EpisodeLog: n_members must be in 1..%d" % N.POP_MAX_MEMBERS)
         self.env, self.capacity, self.n_members = env, cap, P
         dev, n = env.device, int(env.num_envs)
+        self.job, self.group = bool(job), group
+        self.rows = self.world = self.total_envs = self.stage = self.block_nbytes = None
+        self._pending = None    # (K, step0) of a shard_block whose merge_blocks is still to come
+        if not self.job and not (rows is None and world is None and total_envs is None and group is None):
+            raise ValueError("EpisodeLog: rows, world, total_envs and group belong to a job log (job=True)")
+        if self.job:
+            if P != 1:
+                raise ValueError("EpisodeLog: a job log has one member (populations across ranks are out of scope; got n_members=%d)" % P)
+            if rows is None or int(rows) < 1:
+                raise ValueError("EpisodeLog: a job log needs rows >= 1, the largest K of one call (got %r)" % (rows,))
+            if (world is None) != (total_envs is None):
+                raise ValueError("EpisodeLog: world and total_envs go together (both, or neither: then the process group tells)")
+            if world is None:
+                from .sharding import all_gather_rows
+                sizes = all_gather_rows(torch.tensor([n], dtype=torch.int64, device=dev), group).reshape(-1).cpu().tolist()
+                world, total_envs = len(sizes), sum(int(v) for v in sizes)
+            self.rows, self.world, self.total_envs = int(rows), int(world), int(total_envs)
+            if not 1 <= self.world <= N.DP_MAX_SHARDS:
+                raise ValueError("EpisodeLog: %d ranks, ssg_job_episode_log_merge_blocks merges at most %d blocks" % (self.world, N.DP_MAX_SHARDS))
+            if self.total_envs < self.world or n > (self.total_envs + self.world - 1) // self.world:
+                raise ValueError("EpisodeLog: a shard of %d envs is not one of %d envs over %d ranks" % (n, self.total_envs, self.world))
+            if self.rows * ((n + 255) // 256) > N.EPISODE_LOG_MAX_CELLS:
+                raise ValueError("EpisodeLog: rows * ceil(n_envs / 256) = %d above SSG_EPISODE_LOG_MAX_CELLS = %d"
+                                 % (self.rows * ((n + 255) // 256), N.EPISODE_LOG_MAX_CELLS))
+            self.stage = job_stage(cap, self.rows, self.total_envs, self.world)
+            if self.stage > 2 ** 31 - 1:
+                raise ValueError("EpisodeLog: a shard block of %d record slots is more than a call takes" % self.stage)
+            need = C.c_size_t()
+            N.check(N.lib().ssg_job_episode_log_block_nbytes(self.rows, self.stage, C.byref(need)), None, "ssg_job_episode_log_block_nbytes")
+            self.block_nbytes = int(need.value)
         # one buffer, one copy to the host: the head (int64 [2], padded to a record) and then the ring
         self.buffer = torch.zeros((cap + 1) * RECORD_BYTES, dtype=torch.uint8, device=dev)
         self.head = self.buffer[:16].view(torch.int64)
@@ -148,10 +288,8 @@ class EpisodeLog(object):
         rec.dev_workspace, rec.workspace_nbytes = ws.data_ptr(), ws.numel()
         return rec
 
-    def append_rows(self, rew, done, flags=None):
-        """ssg_episode_log_append on a rollout's buffers: rew f64 / done u8 / flags u8 (or None) [K, N] in the env's row layout, rows of
-        unit stride and a common row pitch >= N.  Row t is step ``steps + t``; ``steps`` advances by K.  Blocks beyond the library's
-        cap on K * tiles are served in several calls, which leave what one call would.  No host synchronisation."""
+    def _check_rows(self, rew, done, flags):
+        """(K, row pitch) of a call's [K, N] buffers."""
         torch = _torch()
         env = self.env
         n_env = int(env.num_envs)
@@ -165,6 +303,19 @@ class EpisodeLog(object):
         K, pitch = int(rew.shape[0]), int(rew.stride(0))
         if any(int(t.shape[0]) != K or int(t.stride(0)) != pitch for t in (done, flags) if t is not None):
             raise ValueError("EpisodeLog: rew, done and flags must have the same number of rows and the same row pitch")
+        return K, pitch
+
+    def append_rows(self, rew, done, flags=None):
+        """ssg_episode_log_append on a rollout's buffers: rew f64 / done u8 / flags u8 (or None) [K, N] in the env's row layout, rows of
+        unit stride and a common row pitch >= N.  Row t is step ``steps + t``; ``steps`` advances by K.  Blocks beyond the library's
+        cap on K * tiles are served in several calls, which leave what one call would.  No host synchronisation."""
+        torch = _torch()
+        env = self.env
+        n_env = int(env.num_envs)
+        if self.job:
+            raise ValueError("EpisodeLog.append: a job log's ring holds the episodes of all ranks: call job_append (or shard_block and "
+                             "merge_blocks)")
+        K, pitch = self._check_rows(rew, done, flags)
         per_call = max(1, N.EPISODE_LOG_MAX_CELLS // ((n_env + 255) // 256))
         rec = self.to_native(min(K, per_call))
         with torch.cuda.device(env.device):
@@ -181,6 +332,82 @@ class EpisodeLog(object):
     def append(self, batch):
         """Record the episodes that ended in a rollout batch (``rollout_policy`` / ``rollout_population``: "rew", "done", "flags")."""
         return self.append_rows(batch["rew"], batch["done"], batch.get("flags"))
+
+    # ------------------------------------------------------------------------------------------------
+    # the job's log: the two halves of a call, and the two around the gather
+    # ------------------------------------------------------------------------------------------------
+    def _job_only(self, who):
+        if not self.job:
+            raise ValueError("EpisodeLog.%s: this log was not made with job=True (its ring is this handle's: use append)" % who)
+
+    def shard_block(self, batch, out=None):
+        """The first half of ``job_append`` (ssg_job_episode_log_shard): walk batch["rew"] / batch["done"] / batch.get("flags") — at most
+        `rows` rows — with this rank's carries and pack the shard's episodes into one block.  Returns the block, a uint8 tensor
+        [block_nbytes] on the device (`out` when given: contiguous, 16-byte aligned; what it held does not enter the result); the
+        ring and the head are not touched.  ``merge_blocks`` must follow before the next one."""
+        torch = _torch()
+        self._job_only("shard_block")
+        if self._pending is not None:
+            raise ValueError("EpisodeLog.shard_block: the previous block has not been merged (merge_blocks)")
+        env = self.env
+        rew, done, flags = batch["rew"], batch["done"], batch.get("flags")
+        K, pitch = self._check_rows(rew, done, flags)
+        if K > self.rows:
+            raise ValueError("EpisodeLog.shard_block: %d rows, this log's calls take %d at most (job_append cuts a batch into pieces)" % (K, self.rows))
+        block = torch.empty(self.block_nbytes, dtype=torch.uint8, device=env.device) if out is None else out
+        if block.dtype != torch.uint8 or block.device != self.buffer.device or tuple(block.shape) != (self.block_nbytes,) or not block.is_contiguous():
+            raise ValueError("EpisodeLog.shard_block: out must be a contiguous uint8 tensor (%d,) on %s" % (self.block_nbytes, self.buffer.device))
+        rec = self.to_native(K)
+        with torch.cuda.device(env.device):
+            N.check(N.lib().ssg_job_episode_log_shard(env._h, C.byref(rec), K, self.steps, C.c_void_p(rew.data_ptr()), C.c_void_p(done.data_ptr()),
+                                                      C.c_void_p(flags.data_ptr()) if flags is not None else None, pitch, self.rows,
+                                                      self.stage, C.c_void_p(block.data_ptr()), block.numel(), env._stream()),
+                    env._h, "ssg_job_episode_log_shard")
+        self._pending = (K, self.steps)
+        return block
+
+    def merge_blocks(self, stacked, K=None, step0=None):
+        """The second half (ssg_job_episode_log_merge_blocks): stacked uint8 [W, block_nbytes] on the log's device, the ranks'
+        ``shard_block`` of this call in rank order.  Every record goes to the slot its job rank decides; the head advances by the
+        call's total, and ``steps`` by its rows.  K and step0, given together, merge blocks this log made no ``shard_block`` for
+        (blocks made elsewhere: ``steps`` becomes step0 + K)."""
+        torch = _torch()
+        self._job_only("merge_blocks")
+        if (K is None) != (step0 is None):
+            raise ValueError("EpisodeLog.merge_blocks: K and step0 go together")
+        if K is not None and self._pending is not None:
+            raise ValueError("EpisodeLog.merge_blocks: a shard_block is waiting for its merge: call it without K and step0")
+        if K is not None and not 1 <= int(K) <= self.rows:
+            raise ValueError("EpisodeLog.merge_blocks: K = %d outside 1..rows = %d" % (int(K), self.rows))
+        if K is None and self._pending is None:
+            raise ValueError("EpisodeLog.merge_blocks: no shard_block is waiting for its merge")
+        if (stacked.dtype != torch.uint8 or stacked.device != self.buffer.device or stacked.dim() != 2
+                or tuple(stacked.shape) != (self.world, self.block_nbytes)):
+            raise ValueError("EpisodeLog.merge_blocks: the blocks must be a uint8 tensor (%d, %d) on %s (got %s %s on %s)"
+                             % (self.world, self.block_nbytes, self.buffer.device, stacked.dtype, tuple(stacked.shape), stacked.device))
+        stacked = stacked.contiguous()
+        K, step0 = self._pending if K is None else (int(K), int(step0))
+        env = self.env
+        rec = self.to_native(1)
+        with torch.cuda.device(env.device):
+            N.check(N.lib().ssg_job_episode_log_merge_blocks(env._h, C.byref(rec), K, step0, self.rows, self.stage, C.c_void_p(stacked.data_ptr()),
+                                                             self.world, env._stream()), env._h, "ssg_job_episode_log_merge_blocks")
+        self._pending = None
+        self.steps = step0 + K
+        self._host_copy = None
+        return self
+
+    def job_append(self, batch, group=None):
+        """Record the episodes of ALL ranks that ended in this rollout (a collective: every rank calls it with its own batch of the
+        same rows): ``shard_block``, one all-gather of the blocks over `group` (None: the log's own), then ``merge_blocks``.  A batch
+        of more than `rows` rows goes in pieces of `rows`, which leave what one call would.  No host synchronisation of its own."""
+        from .sharding import all_gather_rows
+        self._job_only("job_append")
+        K = int(batch["rew"].shape[0])
+        for k0 in range(0, K, self.rows):
+            piece = {k: batch[k][k0:k0 + self.rows] for k in ("rew", "done", "flags") if batch.get(k) is not None}
+            self.merge_blocks(all_gather_rows(self.shard_block(piece), self.group if group is None else group))
+        return self
 
     # ------------------------------------------------------------------------------------------------
     # reading (the first read after an append copies the buffer to the host: one device-to-host copy, which waits for the appends before it)
@@ -209,8 +436,9 @@ class EpisodeLog(object):
         return ring[idx].copy(), first - since
 
     def timesteps(self, records):
-        """The x axis of ts2xy(..., 'timesteps'): the env steps the whole batch of envs had taken when each episode ended."""
-        return (np.asarray(records)["step"] + 1) * int(self.env.num_envs)
+        """The x axis of ts2xy(..., 'timesteps'): the env steps the whole batch of envs — a job log: the envs of all ranks — had taken
+        when each episode ended."""
+        return (np.asarray(records)["step"] + 1) * int(self.total_envs if self.job else self.env.num_envs)
 
     def mean_last(self, W, member=None):
         """np.mean of the returns of the last min(W, available) retained records (of `member` alone when given); None when there are
@@ -235,10 +463,19 @@ class EpisodeLog(object):
     # ------------------------------------------------------------------------------------------------
     def state_dict(self):
         """Plain data: the ring and its head, the carries, the step count, and what a MonitorWriter has written and passed."""
-        return {"capacity": self.capacity, "n_members": self.n_members, "num_envs": int(self.env.num_envs),
-                "ring": self.ring.detach().cpu().clone(), "head": self.head.detach().cpu().clone(),
-                "carry_return": self.carry_return.detach().cpu().clone(), "carry": self.carry.detach().cpu().clone(),
-                "steps": int(self.steps), "rows_written": int(self.rows_written), "flushed": int(self.flushed)}
+        if self._pending is not None:
+            raise ValueError("EpisodeLog.state_dict: a shard_block is waiting for its merge_blocks")
+        sd = {"capacity": self.capacity, "n_members": self.n_members, "num_envs": int(self.env.num_envs),
+              "ring": self.ring.detach().cpu().clone(), "head": self.head.detach().cpu().clone(),
+              "carry_return": self.carry_return.detach().cpu().clone(), "carry": self.carry.detach().cpu().clone(),
+              "steps": int(self.steps), "rows_written": int(self.rows_written), "flushed": int(self.flushed)}
+        sd.update(self._job_fields())  # (a job log: the ring is the job's, the carries this rank's)
+        return sd
+
+    def _job_fields(self):
+        if not self.job:
+            return {}
+        return {"job_world": self.world, "job_total_envs": self.total_envs, "job_rows": self.rows, "job_env_base": int(self.env.env_id_base)}
 
     def load_state_dict(self, sd):
         """Become the log the state was taken from.  Checked first, all of it: capacity, member count and env count, every tensor's
@@ -246,7 +483,12 @@ class EpisodeLog(object):
         naming the field and leaves this object, and the files, as they were.  Then the files are cut back to the state's rows."""
         from .checkpoint import check_state, check_values
         who = "EpisodeLog.load_state_dict"
-        check_state(who, sd, fields=(("capacity", self.capacity), ("n_members", self.n_members), ("num_envs", int(self.env.num_envs))),
+        if isinstance(sd, dict) and not self.job and any(k.startswith("job_") for k in sd):
+            raise ValueError("%s: the state is a job log's (job_world = %r), this log is one handle's" % (who, sd.get("job_world")))
+        if self._pending is not None:
+            raise ValueError("%s: a shard_block is waiting for its merge_blocks" % who)
+        check_state(who, sd, fields=(("capacity", self.capacity), ("n_members", self.n_members), ("num_envs", int(self.env.num_envs)))
+                    + tuple(self._job_fields().items()),
                     tensors=(("ring", self.ring), ("head", self.head), ("carry_return", self.carry_return), ("carry", self.carry)))
         check_values(who, sd, (("steps", int), ("rows_written", int), ("flushed", int)))
         if sd["steps"] < 0 or sd["rows_written"] < 0 or sd["flushed"] < sd["rows_written"] or sd["flushed"] > int(sd["head"][0]):

@@ -10,8 +10,7 @@ line on stdout.  The kernels alone: `rocprofv3 --kernel-trace --stats -- python 
 
     python tools/ppo_update_timing.py [--configs 65536x32,4096x64] [--repeats 7] [--only torch|native] [--ext] [--separate-value] [--ret-filter]
                                       [--adv-norm] [--perm] [--timeout-bootstrap] [--checkpoint] [--dp] [--episode-log] [--report]
-                                      [--ret-filter-job] [--report-job]
-                                      [--ret-filter-job]
+                                      [--ret-filter-job] [--report-job] [--episode-log-job]
 
 --ext adds, in the same run, the extended update (NativePPO with vf_clip 0.2, max_grad_norm 0.5, kl_coef 1.0, kl_target 0.01: GAE, the
 ssg_ppo_dist launch, ssg_ppo_update_ext) as the path "native_ext", and the ssg_ppo_dist launch alone as "dist".
@@ -56,6 +55,12 @@ report_row, then report_rows on its one row: three launches); "report_rows_w1" /
 rows: one launch); and the whole GAE + update with each report behind it, one copy to the host included, "native_report_own"
 (NativePPO.report) and "native_report_job" (NativePPO.job_report, whose gather is a no-op here).  Every timed path follows one untimed
 GAE, as with --ret-filter-job.  The gather over real links is not part of any of them.
+--episode-log-job adds, in the same run and alternating with the others, the job-wide episode log (``EpisodeLog(job=True)``) on one
+device, capacity 65 536, rows = the horizon: "eplog_plain" (EpisodeLog.append: ssg_episode_log_append, three launches) against
+"eplog_split" (the split call at W = 1: shard_block, a gather that is a no-op, merge_blocks: six launches); "eplog_merge_w1" / "_w2" /
+"_w8" (merge_blocks alone on 1, 2 and 8 stacked copies of this device's block: two launches); and the whole GAE + update with each log
+ahead of it, "native_eplog_plain" and "native_eplog_job"; and the block's size in bytes.  Every timed path follows one untimed GAE, as
+with --ret-filter-job.  The gather over real links is not part of any of them.
 """
 import argparse
 import importlib.util
@@ -111,7 +116,7 @@ def _wall_ms(fn):
 
 def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext=False, separate_value=False, ret_filter=False,
             adv_norm=False, perm=False, timeout_bootstrap=False, checkpoint=False, checkpoint_dir=None, dp=False, episode_log=False,
-            report=False, ret_filter_job=False, report_job=False):
+            report=False, ret_filter_job=False, report_job=False, episode_log_job=False):
     from ship_sim_gym_amd.policy import NativePolicy
     from ship_sim_gym_amd.ppo import NativePPO
     torch.manual_seed(0)
@@ -268,7 +273,19 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
         paths += [("report_rows_w%d" % W, report_rows_alone(W)) for W in (1, 2, 8)]
         paths += [("native_report_own", native_path(ppo, seeded(), after=lambda nb, st: ppo.report(nb, stats=st))),
                   ("native_report_job", native_path(ppo, seeded(), after=lambda nb, st: ppo.job_report(nb, stats=st)))]
-    if ret_filter_job or report_job:
+    if episode_log_job:  # (the carries and the rings keep running from call to call, as in training: the cost does not depend on them)
+        from ship_sim_gym_amd.episode_log import EpisodeLog
+        ep_plain, ep_job = EpisodeLog(env), EpisodeLog(env, job=True, rows=horizon)
+        own_block = EpisodeLog(env, job=True, rows=horizon).shard_block(b)
+
+        def merge_alone(W):
+            log, stacked = EpisodeLog(env, job=True, rows=horizon, world=W, total_envs=W * envs), torch.stack([own_block] * W)
+            return lambda: log.merge_blocks(stacked, K=horizon, step0=0)
+        paths += [("eplog_plain", lambda: ep_plain.append(b)), ("eplog_split", lambda: ep_job.job_append(b))]
+        paths += [("eplog_merge_w%d" % W, merge_alone(W)) for W in (1, 2, 8)]
+        paths += [("native_eplog_plain", native_path(ppo, seeded(), before=lambda: ep_plain.append(b))),
+                  ("native_eplog_job", native_path(ppo, seeded(), before=lambda: ep_job.job_append(b)))]
+    if ret_filter_job or report_job or episode_log_job:
         spacer = lambda: ppo.gae(dict(b))  # noqa: E731
     else:
         spacer = lambda: None  # noqa: E731
@@ -289,8 +306,10 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
         out[k + "_ms_per_update"] = statistics.median(v)
         out[k + "_ms_all"] = [round(x, 3) for x in v]
     out.update(peaks)
-    if episode_log:
+    if episode_log or episode_log_job:
         out["episodes_per_append"] = int(b["done"].ne(0).sum().item())
+    if episode_log_job:
+        out["eplog_block_bytes"], out["eplog_stage"] = int(ep_job.block_nbytes), int(ep_job.stage)
     if ckpt_path is not None:
         out["checkpoint_file_bytes"] = os.path.getsize(ckpt_path)
         os.remove(ckpt_path)
@@ -327,11 +346,15 @@ def main():
     ap.add_argument("--report-job", action="store_true", help="also time the job's update report on one device: the split call at W = 1 "
                                                               "against ssg_ppo_report, report_rows alone on 1, 2 and 8 stacked rows, and "
                                                               "the whole GAE + update with report() and with job_report() behind it")
+    ap.add_argument("--episode-log-job", action="store_true", help="also time the job-wide episode log on one device: the split call at "
+                                                                   "W = 1 against ssg_episode_log_append, merge_blocks alone on 1, 2 and "
+                                                                   "8 stacked blocks, and the whole GAE + update with each log ahead of it")
     a = ap.parse_args()
     mod = _ppo()
     res = [measure(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.repeats, a.only, "cuda:0", ext=a.ext, separate_value=sep, ret_filter=a.ret_filter,
                    adv_norm=a.adv_norm, perm=a.perm, timeout_bootstrap=a.timeout_bootstrap, checkpoint=a.checkpoint,
-                   checkpoint_dir=a.checkpoint_dir, dp=a.dp, episode_log=a.episode_log, report=a.report, ret_filter_job=a.ret_filter_job, report_job=a.report_job)
+                   checkpoint_dir=a.checkpoint_dir, dp=a.dp, episode_log=a.episode_log, report=a.report, ret_filter_job=a.ret_filter_job, report_job=a.report_job,
+                   episode_log_job=a.episode_log_job)
            for c in a.configs.split(",") for sep in ([False, True] if a.separate_value else [False])]
     print(json.dumps({"ppo_update_timing": res}))
 

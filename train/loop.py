@@ -56,8 +56,8 @@ def check_flag_values(a, error):
         error("--save-every needs --save (the file it rewrites)")
     if a.episode_log_capacity < 1:
         error("--episode-log-capacity must be >= 1")
-    if a.episode_log_capacity != 65536 and not a.episode_log:
-        error("--episode-log-capacity needs --episode-log")
+    if a.episode_log_capacity != 65536 and not (a.episode_log or getattr(a, "job_episode_log", None)):
+        error("--episode-log-capacity needs --episode-log" + (" or --job-episode-log" if hasattr(a, "job_episode_log") else ""))
 
 
 def bind_env(env, horizon, n_members=1, obs_filter=False, norm_reward=False, gamma=0.99, reward_clip=10.0, timeout_bootstrap=False,
@@ -105,14 +105,18 @@ def add_episode_log_flags(ap):
                     help="episodes the device ring holds between two flushes (needs --episode-log); older ones are dropped with a warning")
 
 
-def bind_episode_log(env, path, capacity, n_members=1, resume=False):
+def bind_episode_log(env, path, capacity, n_members=1, resume=False, job_rows=None, writer=True):
     """(EpisodeLog, MonitorWriter) of a run that asks for one, else (None, None).  A resumed run keeps the file: loading the log's
-    state cuts it back to the rows the checkpoint had written."""
+    state cuts it back to the rows the checkpoint had written.  job_rows (the rollout length): the job-wide log of a data-parallel
+    job — every rank calls this (the ranks' env counts are gathered once), and only the rank with `writer` attaches the file."""
     if not path:
         return None, None
     from ship_sim_gym_amd.episode_log import EpisodeLog, MonitorWriter
-    eplog = EpisodeLog(env, capacity=capacity, n_members=n_members)
-    return eplog, MonitorWriter(path, eplog, resume=bool(resume))
+    if job_rows is None:
+        eplog = EpisodeLog(env, capacity=capacity, n_members=n_members)
+    else:
+        eplog = EpisodeLog(env, capacity=capacity, job=True, rows=job_rows)
+    return eplog, (MonitorWriter(path, eplog, resume=bool(resume)) if writer else None)
 
 
 def episode_log_section(eplog):

@@ -102,8 +102,19 @@ sums, the ranks all-gather the rows once, and every rank forms the same record f
 ship_sim_gym_amd/report.py; ssg_ppo_report_sums / ssg_ppo_report_rows); rank 0 prints the line.  ``--job-report-kl`` adds the
 post-update group, ``--job-report-shards`` one line per rank with its shard's samples and explained variance, and ``--job-progress
 FILE`` has rank 0 write the job's record as ``--progress`` writes a rank's (``timesteps`` counts the job's ``--envs``); each implies
-``--job-report``.  With one rank the record is ``--report``'s bit for bit, and ``--resume`` cuts the file back likewise.  The episode
-log and populations across ranks, ``--adv-norm minibatch`` across ranks and multi-rank resume stay out of scope.
+``--job-report``.  With one rank the record is ``--report``'s bit for bit, and ``--resume`` cuts the file back likewise.
+Populations across ranks, ``--adv-norm minibatch`` across ranks and multi-rank resume stay out of scope.
+
+``--job-episode-log FILE`` (``--mode native --update native`` only, one rank or more; not together with ``--episode-log``;
+``--episode-log-capacity`` sizes its ring): the episode log of a job, over the episodes of all ranks as SubprocVecEnv + Monitor +
+load_results give them to the reference (train/stable_baselines/ppo.py:7-8,25-52,122-123).  After every rollout each rank packs its
+shard's finished episodes into one fixed-size block, the ranks all-gather the blocks once, and every rank merges them into the same
+ring in the order one log over all the job's envs would keep (``EpisodeLog(job=True)``, ship_sim_gym_amd/episode_log.py;
+ssg_job_episode_log_shard / ssg_job_episode_log_merge_blocks).  Every rank holds the same ring, so ``--job-best-window W`` scores ``--save-best``
+alike on every rank without a broadcast; rank 0 alone attaches the MonitorWriter, prints the line and writes FILE (``timesteps`` counts
+the job's ``--envs``).  ``--save`` holds rank 0's ``episode_log`` section (the job's ring, rank 0's carries); with one rank the file is
+``--episode-log``'s in every column but ``t`` and ``--resume`` continues from the section.  ``--episode-log`` and ``--best-window`` stay
+refused with more than one rank.
 
 The sampling noise of a whole rollout is drawn in one call before it (uniforms [horizon, envs], inverse-CDF sampling inside
 the step), so a captured step holds no random-number generator state and replays exactly what the eager loop computes.
@@ -305,7 +316,8 @@ NEEDS = {"mode": ("--mode native", "mode='native'", lambda a: a.mode == "native"
          "update": ("--update native", "update='native'", lambda a: a.update == "native"),
          "obs_filter": ("--obs-filter", "obs_filter=True", lambda a: bool(a.obs_filter)),
          "save": ("--save", "save", lambda a: bool(a.save)),
-         "episode_log": ("--episode-log", "episode_log", lambda a: bool(a.episode_log))}
+         "episode_log": ("--episode-log", "episode_log", lambda a: bool(a.episode_log)),
+         "job_episode_log": ("--job-episode-log", "job_episode_log", lambda a: bool(getattr(a, "job_episode_log", None)))}
 REQUIREMENTS = (  # (a row that needs more stands before the row of what it needs: the refusal then names the flag that asks for most)
     ("save_obs_filter", "--save-obs-filter", lambda a: bool(a.save_obs_filter), ("mode", "obs_filter"), True, "it saves that filter's statistics"),
     ("obs_filter", "--obs-filter", lambda a: bool(a.obs_filter), ("mode",), True, "the filter runs inside the native policy launch"),
@@ -326,7 +338,17 @@ REQUIREMENTS = (  # (a row that needs more stands before the row of what it need
 EPISODE_LOG_REQUIREMENTS = (
     ("best_window", "--best-window", lambda a: bool(a.best_window), ("episode_log",), True, "the window is over the log's last episodes"),
     ("episode_log", "--episode-log", lambda a: bool(a.episode_log), ("mode", "update"), True,
-     "it reads the native rollout's reward / done / flags rows; a job's ranks would each hold a log of their own envs"),
+     "it reads the native rollout's reward / done / flags rows; a job's ranks would each hold a log of their own envs (the job's log: "
+     "--job-episode-log)"),
+)
+
+
+# The job-wide episode log's rows, likewise: any number of ranks; not together with the handle's own log (JOB_EXCLUDES below).
+JOB_EPISODE_LOG_REQUIREMENTS = (
+    ("job_best_window", "--job-best-window", lambda a: bool(getattr(a, "job_best_window", 0)), ("job_episode_log",), False,
+     "the window is over the job log's last episodes"),
+    ("job_episode_log", "--job-episode-log", lambda a: bool(getattr(a, "job_episode_log", None)), ("mode", "update"), False,
+     "the ranks' blocks of finished episodes are gathered once per rollout, from the native rollout's reward / done / flags rows"),
 )
 
 
@@ -349,9 +371,11 @@ JOB_NORM_REWARD_REQUIREMENTS = (
     ("job_norm_reward", "--job-norm-reward", lambda a: bool(getattr(a, "job_norm_reward", None)), ("mode", "update"), False,
      "the ranks' rows are gathered between the native rollout and the device's GAE"),
 )
-# (what a job-wide filter's row is not supported together with, asked after its needs: the argument, its flag, why)
-JOB_FILTER_EXCLUDES = {"job_obs_filter": ("obs_filter", "--obs-filter", "one filter is bound to the env"),
-                       "job_norm_reward": ("norm_reward", "--norm-reward", "one filter normalises the rewards")}
+# (what a job-wide filter's or the job-wide episode log's row is not supported together with — the handle's own counterpart —, asked
+# after its needs: the argument, its flag, why)
+JOB_EXCLUDES = {"job_obs_filter": ("obs_filter", "--obs-filter", "one filter is bound to the env"),
+                       "job_norm_reward": ("norm_reward", "--norm-reward", "one filter normalises the rewards"),
+                       "job_episode_log": ("episode_log", "--episode-log", "one log records the run's episodes")}
 
 
 # The job's update report's rows, likewise: any number of ranks; not together with the rank's own report (one report per update).
@@ -366,8 +390,8 @@ JOB_REPORT_EXCLUDES = tuple((name, flag, "one report per update")  # (the flag t
 
 def excluded_with(name, a):
     """What the row `name` is on together with and is not supported with: (the argument, its flag, why), or three Nones."""
-    if name in JOB_FILTER_EXCLUDES:
-        other = JOB_FILTER_EXCLUDES[name]
+    if name in JOB_EXCLUDES:
+        other = JOB_EXCLUDES[name]
         return other if getattr(a, other[0]) else (None, None, None)
     if name in (row[0] for row in JOB_REPORT_REQUIREMENTS):
         for other in JOB_REPORT_EXCLUDES:
@@ -377,10 +401,10 @@ def excluded_with(name, a):
 
 
 def check_requirements(args, ranks, error=None):
-    """Walk EPISODE_LOG_REQUIREMENTS, JOB_REPORT_REQUIREMENTS, REPORT_REQUIREMENTS, JOB_OBS_FILTER_REQUIREMENTS, JOB_NORM_REWARD_REQUIREMENTS and REQUIREMENTS over the arguments `args` (a dict) of a run of `ranks` ranks.  The first row that is on and misses a need, or is
+    """Walk EPISODE_LOG_REQUIREMENTS, JOB_EPISODE_LOG_REQUIREMENTS, JOB_REPORT_REQUIREMENTS, REPORT_REQUIREMENTS, JOB_OBS_FILTER_REQUIREMENTS, JOB_NORM_REWARD_REQUIREMENTS and REQUIREMENTS over the arguments `args` (a dict) of a run of `ranks` ranks.  The first row that is on and misses a need, or is
     refused with more than one rank, goes to the parser's `error` with the flags in the text, or is a ValueError with train()'s names."""
     a = argparse.Namespace(**dict(args, ranks=ranks))
-    rows = EPISODE_LOG_REQUIREMENTS + JOB_REPORT_REQUIREMENTS + REPORT_REQUIREMENTS + JOB_OBS_FILTER_REQUIREMENTS + JOB_NORM_REWARD_REQUIREMENTS + REQUIREMENTS
+    rows = EPISODE_LOG_REQUIREMENTS + JOB_EPISODE_LOG_REQUIREMENTS + JOB_REPORT_REQUIREMENTS + REPORT_REQUIREMENTS + JOB_OBS_FILTER_REQUIREMENTS + JOB_NORM_REWARD_REQUIREMENTS + REQUIREMENTS
     for name, flag, on, needs, one_rank_only, why in rows:
         text = None
         other, other_flag, other_why = excluded_with(name, a) if on(a) else (None, None, None)
@@ -406,8 +430,8 @@ def check_train_arguments(a, ranks):
             raise ValueError("%s must be %r or %r (got %r)" % ((name,) + allowed + (getattr(a, name),)))
     if a.save_every < 0 or a.eval_every < 0 or a.eval_episodes < 1:
         raise ValueError("save_every and eval_every must be >= 0 and eval_episodes >= 1")
-    if a.episode_log_capacity < 1 or a.best_window < 0:
-        raise ValueError("episode_log_capacity must be >= 1 and best_window >= 0")
+    if a.episode_log_capacity < 1 or a.best_window < 0 or getattr(a, "job_best_window", 0) < 0:
+        raise ValueError("episode_log_capacity must be >= 1, best_window and job_best_window >= 0")
     check_requirements(vars(a), ranks)
 
 
@@ -620,7 +644,7 @@ def account(run, state, u, b, log):
     state.scores.append((st["sum_return"] - state.sum_return) / ended if ended > 0 else float("-inf"))
     state.episodes, state.sum_return = st["episodes"], st["sum_return"]
     if run.eplog is not None:  # the cycle's one copy of the ring to the host; then the window's score in place of the update's own
-        written = run.epwriter.flush()
+        written = run.epwriter.flush() if run.epwriter is not None else 0  # (a job's file is rank 0's; the ring is every rank's, the same bits)
         if run.best_window > 0 and ended > 0:
             state.scores[-1] = run.eplog.mean_last(run.best_window)
         log("update %3d  episode log: %d rows written, %d in all%s" % (u, written, run.eplog.rows_written, (
@@ -644,7 +668,7 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
           norm_reward=False, reward_clip=10.0, adv_norm="batch", perm="torch", timeout_bootstrap=False, hidden=64,
           save=None, save_every=0, save_best=None, resume=None, episode_log=None, episode_log_capacity=65536, best_window=0,
           report=False, report_kl=False, progress=None, job_obs_filter=False, job_norm_reward=False,
-          job_report=False, job_report_kl=False, job_progress=None, job_report_shards=False):
+          job_report=False, job_report_kl=False, job_progress=None, job_report_shards=False, job_episode_log=None, job_best_window=0):
     config = run_config(**dict(locals()))  # (first statement: the arguments, nothing else)
     run = argparse.Namespace(**locals())  # the run record: the arguments and the config; build_run() and the bind step add the objects
     run.report = bool(report or report_kl or progress)  # (--report-kl and --progress imply --report)
@@ -652,16 +676,20 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
     # check: every refusal on the host, then the file a run resumes from, before any device work (a wrong command line costs nothing)
     rank, world = job_ranks()
     check_train_arguments(run, world)
+    run.best_window = best_window or job_best_window  # (one window: over the handle's log, or over the job's)
     if rank != 0:  # (a data-parallel job trains ONE policy, ship_sim_gym_amd/dp.py: only rank 0 logs, evaluates and saves)
         log = lambda *_, **__: None  # noqa: E731
-    ckpt = open_resume(resume, config, loop.resume_sections(RESUME_SECTIONS, obs_filter or job_obs_filter, norm_reward or job_norm_reward, episode_log), exempt=CONFIG_EXEMPT) if resume else None
+    ckpt = open_resume(resume, config, loop.resume_sections(RESUME_SECTIONS, obs_filter or job_obs_filter, norm_reward or job_norm_reward, episode_log or job_episode_log), exempt=CONFIG_EXEMPT) if resume else None
     # build, bind, resume
     build_run(run, rank, world)
     eval_env = (ShipVecEnv(int(eval_envs or min(envs, 1024)), GameConfig, EnvConfig, device=device, n_maps=64, **dict(env_kw or {}))
                 if eval_every and rank == 0 else None)
     run.flt, run.rflt, run.evaluator = loop.bind_env(run.env, horizon, 1, obs_filter, norm_reward, gamma, reward_clip, timeout_bootstrap, eval_env,
                                                      job_obs_filter=job_obs_filter, job_norm_reward=job_norm_reward)
-    run.eplog, run.epwriter = loop.bind_episode_log(run.env, episode_log, episode_log_capacity, 1, resume)
+    if job_episode_log:  # every rank: the ring is the job's, the same bits everywhere; the file is rank 0's
+        run.eplog, run.epwriter = loop.bind_episode_log(run.env, job_episode_log, episode_log_capacity, 1, resume, job_rows=horizon, writer=rank == 0)
+    else:
+        run.eplog, run.epwriter = loop.bind_episode_log(run.env, episode_log, episode_log_capacity, 1, resume)
     run.progress_writer = loop.open_progress(progress, resume)
     run.job_progress_writer = loop.open_progress(job_progress, resume) if rank == 0 else None  # (the job's file is rank 0's)
     if mode in ("graph", "pingpong"):
@@ -687,7 +715,9 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         native_last_val = b.pop("last_val", None)
         if job_obs_filter:  # every rank: gather what the ranks' rollouts added, merge it alike (the x rows were formed rank-locally)
             run.flt.sync()
-        if run.eplog is not None:
+        if run.eplog is not None and run.eplog.job:  # every rank: one all-gather of the ranks' blocks, merged alike
+            run.eplog.job_append(run.shards[0].native_out)
+        elif run.eplog is not None:
             run.eplog.append(run.shards[0].native_out)  # (the rollout's own f64 / u8 rows; no host synchronisation)
         if return_details is True:
             snapshots.append({k: v.clone() for k, v in b.items()})
@@ -792,6 +822,13 @@ def make_arg_parser():
     ap.add_argument("--best-window", type=int, default=0, metavar="W",
                     help="--save-best compares the mean return of the last W finished episodes (the reference callback's "
                          "np.mean(y[-100:]); needs --episode-log) instead of the mean over the episodes of one update; 0 = off")
+    ap.add_argument("--job-episode-log", default=None, metavar="FILE",
+                    help="--episode-log for a data-parallel job, one rank or more: the log of the episodes of ALL ranks, in the order one "
+                         "log over all the job's envs would keep; the ranks gather one block of records once per rollout and merge them "
+                         "alike, bit-identically; rank 0 writes FILE (needs --mode native --update native; not together with "
+                         "--episode-log; --episode-log-capacity sizes its ring)")
+    ap.add_argument("--job-best-window", type=int, default=0, metavar="W",
+                    help="--best-window over the job's log (needs --job-episode-log): every rank computes the same score; 0 = off")
     loop.add_report_flags(ap)
     ap.add_argument("--job-obs-filter", action="store_true",
                     help="the running observation filter for a data-parallel job, one rank or more: every rank normalises with its own "
@@ -822,8 +859,8 @@ def parse_args(argv=None):
     ap = make_arg_parser()
     a = ap.parse_args(argv)
     loop.check_flag_values(a, ap.error)
-    if a.best_window < 0:
-        ap.error("--best-window must be >= 0")
+    if a.best_window < 0 or a.job_best_window < 0:
+        ap.error("--best-window and --job-best-window must be >= 0")
     if a.gpus < 1 or a.gpus > 64:
         ap.error("--gpus must be in 1..64")
     check_requirements(vars(a), max(a.gpus, int(os.environ.get("WORLD_SIZE", "1"))), ap.error)
