@@ -1476,6 +1476,75 @@ int ssg_ppo_set_adv_norm(ssg_handle *h, int mode, int n_members, void *dev_scrat
 int ssg_ppo_get_adv_norm(const ssg_handle *h, int *mode, int *n_members);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Job-wide per-minibatch advantage normalisation (ABI 9 addition): PPO2's rule for W ranks that train one policy
+ * The Stable-Baselines script trains PPO2 over a SubprocVecEnv (train/stable_baselines/ppo.py:88-90,122-123): the minibatch PPO2
+ * re-normalises over holds all workers' samples.  In a data-parallel job (ssg_ppo_apply_shards, below) minibatch (e, j) of the job is
+ * the union of the ranks' minibatches (e, j), so its statistics are sums over the ranks.  The advantages are fixed once GAE has run and
+ * a rank's permutations are known before its first gradient, so the sums of EVERY minibatch of an update are formed in one pass:
+ *   1. ssg_ppo_minibatch_adv_sums: this shard's f64 rows {s, q, c, 0}, one per minibatch, two launches per update;
+ *   2. the caller gathers the shards' row blocks (one all-gather per update, or a stack);
+ *   3. ssg_ppo_set_minibatch_adv_rows: every rank adds the blocks in rank order and writes the same table of stats rows, one launch;
+ *   4. ssg_ppo_set_adv_table binds the table; ahead of every local gradient call ssg_ppo_select_adv_row names the minibatch's row.
+ * The per-minibatch loop exchanges nothing beyond the gradient rows it already gathers.
+ *
+ * Minibatch (e, j) of a shard is perm[e][j*chunk : min(n, (j+1)*chunk)], C = ceil(n / chunk) of them per epoch — the slice
+ * ssg_ppo_update cuts — and its row is e*C + j.  s, q and c are the f64 sums of adv, adv^2 and 1 over the minibatch's indices inside
+ * [0, n_samples), in the order ssg_ppo_set_adv_norm's two launches add them for a minibatch of that length M: B = min(64, ceil(M /
+ * 1024)) workgroups, positions b*256 + t stepping by B*256, the 256-entry halving tree, then the tree over the B partials.  The grid of
+ * the first launch is (B of the longest minibatch, epochs*C) x 256 threads, of the second epochs*C workgroups.  No floating-point
+ * atomics, no host synchronisation.  The ranks' M may differ (unequal shards): each sums its own.
+ *
+ * The table's row b, with S, Q and C the sums over r = 0 .. W-1 of rows[r][b][0..2], added in f64 in rank order starting from rank 0's:
+ *   C == 0: {0, 1, 1, 0};  else mean = S/C;  var = C > 1 ? max(0, (Q - S*mean) / (C - 1)) : 0;  std+ = (float)sqrt(var) + adv_eps;
+ *   {(float)mean, std+, 1/std+, 0}
+ * — SSG_ADV_NORM_MINIBATCH's formula, so with W = 1 the row is bit for bit what that mode writes for the minibatch.  The estimator
+ * stays the unbiased one (PPO2's is the population std, as said above).
+ *
+ * A handle has ONE source of per-minibatch statistics: binding a table puts the mode back to SSG_ADV_NORM_BATCH, and a successful
+ * ssg_ppo_set_adv_norm drops a bound table; neither refuses because of the other.  While a table is bound, ssg_ppo_grad and
+ * ssg_ppo_grad_ext launch no statistics kernel and read {mean, std+, 1/std+} from dev_table + 4*row; ssg_ppo_apply_shards runs as ever
+ * (it reads no advantage); ssg_ppo_update, ssg_ppo_update_ext and the ssg_pop_update* entry points are refused (SSG_ERR_BAD_ARG, after
+ * everything else the host judges about the call): a table row is one minibatch's, and those calls run many.
+ * ------------------------------------------------------------------------------------------------- */
+#define SSG_ADV_TABLE_MAX_ROWS 65535 /* minibatches of one ssg_ppo_minibatch_adv_sums call, rows of one table: a grid's second dimension */
+
+/* Replaces nothing (memory binding; PPO2 behind train/stable_baselines/ppo.py:90 keeps its sums on the host): the size of
+ * ssg_ppo_minibatch_adv_sums' partials scratch for n_batches minibatches, f64 [n_batches][64][3] rounded up to 256 bytes.
+ * SSG_ERR_BAD_ARG for NULL nbytes or n_batches outside 1..SSG_ADV_TABLE_MAX_ROWS. */
+int ssg_ppo_minibatch_adv_nbytes(int n_batches, size_t *nbytes);
+
+/* Replaces: a worker's share of advs.mean() and advs.std() of every minibatch of one PPO2 update over a SubprocVecEnv
+ * (train/stable_baselines/ppo.py:88-90,122-123), step 1 above.  dev_adv f32 [n_samples] (GAE's output, rows t*N + e), dev_perm int64
+ * [epochs][n], dev_out f64 [epochs*C][4], dev_scratch 256-byte aligned, of ssg_ppo_minibatch_adv_nbytes(epochs*C) bytes.  An index
+ * outside [0, n_samples) counts for nothing.  Two launches on `stream`.  SSG_ERR_BAD_ARG (nothing launched): NULL pointers; n_samples,
+ * epochs, n or chunk < 1; chunk > n; epochs*C > SSG_ADV_TABLE_MAX_ROWS; a misaligned scratch or one too small.  SSG_ERR_NOT_BOUND
+ * without a state blob. */
+int ssg_ppo_minibatch_adv_sums(ssg_handle *h, int64_t n_samples, const float *dev_adv, const int64_t *dev_perm, int epochs, int64_t n,
+                               int64_t chunk, double *dev_out, void *dev_scratch, size_t scratch_nbytes, void *stream);
+
+/* Replaces: advs.mean() and advs.std() + 1e-8 of every minibatch of that update over all workers' samples
+ * (train/stable_baselines/ppo.py:88-90,122-123), step 3 above.  dev_rows f64 [n_shards][n_batches][4] (the gathered blocks, rank
+ * order), dev_table f32 [n_batches][4].  One lane per minibatch on ceil(n_batches / 256) workgroups of 256; one launch on `stream`.
+ * SSG_ERR_BAD_ARG (nothing launched): NULL pointers, n_shards outside 1..SSG_DP_MAX_SHARDS (64), n_batches outside
+ * 1..SSG_ADV_TABLE_MAX_ROWS, an adv_eps that is not finite.  SSG_ERR_NOT_BOUND without a state blob. */
+int ssg_ppo_set_minibatch_adv_rows(ssg_handle *h, int n_shards, int n_batches, const double *dev_rows, double adv_eps, float *dev_table,
+                                   void *stream);
+
+/* Replaces nothing (memory binding; the minibatch PPO2 normalises behind train/stable_baselines/ppo.py:90 is its own).  Binds the
+ * caller-owned, 16-byte aligned table f32 [n_rows][4] to the handle and selects row 0; a NULL dev_table unbinds (n_rows is not read).
+ * Host only, nothing launched.  SSG_ERR_BAD_ARG, the binding left as it was: a NULL handle, a misaligned table, n_rows < 1. */
+int ssg_ppo_set_adv_table(ssg_handle *h, float *dev_table /* NULL unbinds */, int n_rows);
+
+/* Replaces nothing (the loop index of PPO2's minibatch loop behind train/stable_baselines/ppo.py:90): the row of the bound table the
+ * next ssg_ppo_grad / ssg_ppo_grad_ext reads.  Host only.  SSG_ERR_BAD_ARG, the selection left as it was: a NULL handle, no table
+ * bound, a row outside [0, n_rows). */
+int ssg_ppo_select_adv_row(ssg_handle *h, int row);
+
+/* Replaces nothing (introspection; train/stable_baselines/ppo.py:90 has no such binding).  The bound table (NULL: none), its rows and
+ * the selected row (0 and 0 without a table). */
+int ssg_ppo_get_adv_table(const ssg_handle *h, float **dev_table, int *n_rows, int *row);
+
+/* ---------------------------------------------------------------------------------------------------
  * The minibatch permutations (ABI 9 addition): the shuffle of the update, drawn by the library
  * Both reference trainers shuffle inside their update: PPO2's learn runs np.random.shuffle(inds) once per epoch behind model.learn
  * (train/stable_baselines/ppo.py:90), and RLlib's SGD shuffles its minibatches the same way (train/rllib/pbt.py:50-62).  The update
@@ -1669,8 +1738,8 @@ int ssg_ppo_set_adv_moments(ssg_handle *h, int n_shards, const double *dev_rows 
  * read (the batch pointers are not); one launch, two with max_grad_norm > 0, one more for the adaptation.  dev_stats (nullable):
  * f32[8].  SSG_ERR_BAD_ARG (nothing launched): a bad policy, hparams, ext or shards record (struct_size, n_shards out of range,
  * reserved != 0, n_chunks < 1 where it is read), NULL dev_rows, counts or dev_adam_mv, a count < 1, step < 1, a workspace too small
- * (ssg_ppo_workspace_nbytes covers it), or SSG_ADV_NORM_MINIBATCH bound to the handle: per-minibatch statistics would have to be
- * job-wide too, which is out of scope. */
+ * (ssg_ppo_workspace_nbytes covers it), or SSG_ADV_NORM_MINIBATCH bound to the handle: that mode's statistics are one shard's.  The
+ * job's per-minibatch statistics come from a table (ssg_ppo_set_adv_table, above), with which this call runs as ever. */
 int ssg_ppo_apply_shards(ssg_handle *h, const ssg_policy *pol, const ssg_ppo_hparams *hp, const ssg_ppo_ext *ext /* nullable */,
                          const ssg_ppo_shards *sh, float *dev_adam_mv, int64_t step, float *dev_stats /* nullable */,
                          void *dev_workspace, size_t workspace_nbytes, void *stream);

@@ -31,6 +31,7 @@ RET_FILTER_UPDATE, RET_FILTER_MAX_STEPS = 0x1, 1024  # ssg_ret_filter.flags; the
 ADV_NORM_BATCH, ADV_NORM_MINIBATCH = 0, 1  # ssg_ppo_set_adv_norm's modes: once per rollout (the default), PPO2's per minibatch
 ADV_NORM_BLOCKS, ADV_NORM_SPAN = 64, 1024  # its reduction order: workgroups at most per member, minibatch positions per workgroup below that
 # the minibatch permutations (csrc/shipsim_perm.h): Feistel rounds, the bit-width floor, the cycle walk's cap, the largest row
+ADV_TABLE_MAX_ROWS = 65535  # minibatches of one ssg_ppo_minibatch_adv_sums call, rows of one ssg_ppo_set_adv_table table
 PERM_ROUNDS, PERM_MIN_BITS, PERM_WALK_CAP, PERM_MAX_N = 8, 8, 256, 1 << 32
 
 
@@ -76,6 +77,8 @@ EXPORTS = (
     "ssg_set_obs_filter_buffer", "ssg_get_obs_filter_buffer", "ssg_obs_filter_update_buffered", "ssg_obs_filter_merge_rows",
     "ssg_ret_filter_workspace_nbytes", "ssg_ret_filter_apply", "ssg_ret_filter_batches", "ssg_ret_filter_apply_rows",
     "ssg_ppo_adv_norm_nbytes", "ssg_ppo_set_adv_norm", "ssg_ppo_get_adv_norm",
+    "ssg_ppo_minibatch_adv_nbytes", "ssg_ppo_minibatch_adv_sums", "ssg_ppo_set_minibatch_adv_rows",
+    "ssg_ppo_set_adv_table", "ssg_ppo_select_adv_row", "ssg_ppo_get_adv_table",
     "ssg_host_perm", "ssg_ppo_perm", "ssg_pop_perm",
     "ssg_set_timeout_boot", "ssg_get_timeout_boot", "ssg_timeout_values", "ssg_pop_timeout_values", "ssg_ppo_gae_boot", "ssg_pop_gae_boot",
     "ssg_ppo_adv_moments", "ssg_ppo_set_adv_moments", "ssg_ppo_apply_shards",
@@ -346,6 +349,12 @@ def lib():
     L.ssg_ppo_adv_norm_nbytes.argtypes = [C.c_int, szp]
     L.ssg_ppo_set_adv_norm.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
     L.ssg_ppo_get_adv_norm.argtypes = [vp, ip, ip]
+    L.ssg_ppo_minibatch_adv_nbytes.argtypes = [C.c_int, szp]
+    L.ssg_ppo_minibatch_adv_sums.argtypes = [vp, C.c_int64, vp, vp, C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_size_t, vp]
+    L.ssg_ppo_set_minibatch_adv_rows.argtypes = [vp, C.c_int, C.c_int, vp, C.c_double, vp, vp]
+    L.ssg_ppo_set_adv_table.argtypes = [vp, vp, C.c_int]
+    L.ssg_ppo_select_adv_row.argtypes = [vp, C.c_int]
+    L.ssg_ppo_get_adv_table.argtypes = [vp, C.POINTER(vp), ip, ip]
     L.ssg_host_perm.argtypes = [C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
     L.ssg_ppo_perm.argtypes = [vp, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int64, vp, vp]
     L.ssg_pop_perm.argtypes = [vp, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]

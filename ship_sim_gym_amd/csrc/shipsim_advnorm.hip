@@ -15,6 +15,11 @@
 //   finalise  one workgroup per member: thread b holds partial b (b < B, zeros beyond), the same tree, lane 0 writes the row.
 // No floating-point atomics; plain stores.
 //
+// The job-wide form (ssg_ppo_minibatch_adv_sums / ssg_ppo_set_minibatch_adv_rows; the end of this file) takes the same sums for EVERY
+// minibatch of an update in two launches — minibatch (e, j) of the permutation rows on grid row e*C + j — and leaves them as f64 rows
+// {s, q, c, 0}; the rows of W shards, gathered, are then added in rank order and put through the same formula into a table of stats
+// rows.  The accumulate loop, the trees and the formula are the device functions below, shared with the two kernels above them.
+//
 // Which row of the [K][N] buffers position i of member m's minibatch names is RESTATED from ppo_grad_body (its top and its step 1),
 // for its four shapes: one policy; a population on equal slices; on per-member schedules; on unequal slices.
 #include <cmath>
@@ -93,6 +98,76 @@ __device__ __forceinline__ void tree3(double *rs, double *rq, double *rc)
     }
 }
 
+// thread t of workgroup bx of B: the positions bx*256 + t, then steps of B*256 while below M, added in that order.  pop: the index is
+// member-local, sample t*mem_n + e being row t*N + mem_base + e of the batch.
+__device__ __forceinline__ void adv_accumulate(const float *adv, const int64_t *idx, long long M, long long n_samples, int B, int bx, int pop,
+                                               long long mem_n, long long N, long long mem_base, double &s, double &q, double &c)
+{
+    for (long long i = (long long)bx * 256 + threadIdx.x; i < M; i += (long long)B * 256) {
+        long long j = idx[i];
+        if (j >= n_samples) j = -1;
+        if (j < 0) continue; // a zero, gradient-free sample of the gradient kernel: it counts for nothing
+        if (pop) {
+            const long long t = j / mem_n;
+            j = t * N + mem_base + (j - t * mem_n);
+        }
+        const double v = (double)adv[j];
+        s += v;
+        q += v * v;
+        c += 1.0;
+    }
+}
+
+// the workgroup's tree over its threads' sums; lane 0 stores the (s, q, c) partial
+__device__ __forceinline__ void adv_store_partial(double *rs, double *rq, double *rc, double s, double q, double c, double *p)
+{
+    rs[threadIdx.x] = s;
+    rq[threadIdx.x] = q;
+    rc[threadIdx.x] = c;
+    tree3(rs, rq, rc);
+    if (threadIdx.x == 0) {
+        p[0] = rs[0];
+        p[1] = rq[0];
+        p[2] = rc[0];
+    }
+}
+
+// the finalising workgroup: thread b holds partial b (b < B, zeros beyond), the same tree; entry 0 of each column holds the sum
+__device__ __forceinline__ void adv_sum_partials(double *rs, double *rq, double *rc, const double *part, int B)
+{
+    double s = 0.0, q = 0.0, c = 0.0;
+    for (int b = threadIdx.x; b < B; b += 256) {
+        const double *p = part + b * 3;
+        s += p[0];
+        q += p[1];
+        c += p[2];
+    }
+    rs[threadIdx.x] = s;
+    rq[threadIdx.x] = q;
+    rc[threadIdx.x] = c;
+    tree3(rs, rq, rc);
+}
+
+// the stats row {mean, std+, 1/std+, 0} of the sums S, Q and the count cnt
+__device__ __forceinline__ void adv_stats_row(double S, double Q, double cnt, float adv_eps, float *st)
+{
+    if (cnt == 0.0) {
+        st[0] = 0.0f;
+        st[1] = 1.0f;
+        st[2] = 1.0f;
+        st[3] = 0.0f;
+        return;
+    }
+    const double mean = S / cnt;
+    double var = cnt > 1.0 ? (Q - S * mean) / (cnt - 1.0) : 0.0; // (one sample: PPO2's numpy std is 0; torch.std would be NaN)
+    if (var < 0.0) var = 0.0;
+    const float stdp = (float)sqrt(var) + adv_eps;
+    st[0] = (float)mean;
+    st[1] = stdp;
+    st[2] = 1.0f / stdp;
+    st[3] = 0.0f;
+}
+
 __global__ void __launch_bounds__(256) adv_norm_partial_kernel(const AdvNormArgs a)
 {
     __shared__ double rs[256], rq[256], rc[256];
@@ -102,29 +177,8 @@ __global__ void __launch_bounds__(256) adv_norm_partial_kernel(const AdvNormArgs
     const int B = adv_norm_blocks(mb.M);
     if ((int)blockIdx.x >= B) return;
     double s = 0.0, q = 0.0, c = 0.0;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < mb.M; i += (long long)B * 256) {
-        long long j = mb.idx[i];
-        if (j >= mb.n_samples) j = -1;
-        if (j < 0) continue; // a zero, gradient-free sample of the gradient kernel: it counts for nothing
-        if (a.pop) {
-            const long long t = j / mb.mem_n;
-            j = t * a.N + mb.mem_base + (j - t * mb.mem_n);
-        }
-        const double v = (double)a.adv[j];
-        s += v;
-        q += v * v;
-        c += 1.0;
-    }
-    rs[threadIdx.x] = s;
-    rq[threadIdx.x] = q;
-    rc[threadIdx.x] = c;
-    tree3(rs, rq, rc);
-    if (threadIdx.x == 0) {
-        double *p = a.part + (m * kAdvNormBlocks + blockIdx.x) * 3;
-        p[0] = rs[0];
-        p[1] = rq[0];
-        p[2] = rc[0];
-    }
+    adv_accumulate(a.adv, mb.idx, mb.M, mb.n_samples, B, (int)blockIdx.x, a.pop, mb.mem_n, a.N, mb.mem_base, s, q, c);
+    adv_store_partial(rs, rq, rc, s, q, c, a.part + (m * kAdvNormBlocks + blockIdx.x) * 3);
 }
 
 __global__ void __launch_bounds__(256) adv_norm_final_kernel(const AdvNormArgs a)
@@ -133,38 +187,71 @@ __global__ void __launch_bounds__(256) adv_norm_final_kernel(const AdvNormArgs a
     const size_t m = blockIdx.x;
     MemberBatch mb;
     if (!member_batch(a, m, mb)) return;
-    const int B = adv_norm_blocks(mb.M);
+    adv_sum_partials(rs, rq, rc, a.part + m * kAdvNormBlocks * 3, adv_norm_blocks(mb.M));
+    if (threadIdx.x == 0)
+        adv_stats_row(rs[0], rq[0], rc[0], a.pop ? a.table[m * kPopTableRow + a.adv_eps_col] : a.adv_eps, a.stats + m * 4);
+}
+
+// ---- the job-wide form: every minibatch of an update at once --------------------------------------------------------------------------
+// minibatch y = e*C + j of the permutation rows: perm[e][j*chunk : min(n, (j+1)*chunk)]
+struct MbSumsArgs {
+    const float *adv;
+    const int64_t *perm; // int64 [epochs][n]
+    long long n_samples, n, chunk, C;
+    double *part; // f64 [epochs*C][kAdvNormBlocks][3]
+    double *out;  // f64 [epochs*C][4]
+};
+
+__device__ __forceinline__ long long mb_sums_batch(const MbSumsArgs &a, size_t y, const int64_t *&idx)
+{
+    const long long e = (long long)y / a.C, b0 = ((long long)y - e * a.C) * a.chunk;
+    idx = a.perm + (size_t)e * (size_t)a.n + (size_t)b0;
+    return a.chunk < a.n - b0 ? a.chunk : a.n - b0;
+}
+
+__global__ void __launch_bounds__(256) mb_sums_partial_kernel(const MbSumsArgs a)
+{
+    __shared__ double rs[256], rq[256], rc[256];
+    const size_t y = blockIdx.y;
+    const int64_t *idx;
+    const long long M = mb_sums_batch(a, y, idx);
+    const int B = adv_norm_blocks(M);
+    if ((int)blockIdx.x >= B) return; // (uniform over the workgroup, ahead of every barrier)
     double s = 0.0, q = 0.0, c = 0.0;
-    for (int b = threadIdx.x; b < B; b += 256) {
-        const double *p = a.part + (m * kAdvNormBlocks + b) * 3;
-        s += p[0];
-        q += p[1];
-        c += p[2];
-    }
-    rs[threadIdx.x] = s;
-    rq[threadIdx.x] = q;
-    rc[threadIdx.x] = c;
-    tree3(rs, rq, rc);
+    adv_accumulate(a.adv, idx, M, a.n_samples, B, (int)blockIdx.x, 0, 1, 0, 0, s, q, c);
+    adv_store_partial(rs, rq, rc, s, q, c, a.part + (y * kAdvNormBlocks + blockIdx.x) * 3);
+}
+
+__global__ void __launch_bounds__(256) mb_sums_final_kernel(const MbSumsArgs a)
+{
+    __shared__ double rs[256], rq[256], rc[256];
+    const size_t y = blockIdx.x;
+    const int64_t *idx;
+    const long long M = mb_sums_batch(a, y, idx);
+    adv_sum_partials(rs, rq, rc, a.part + y * kAdvNormBlocks * 3, adv_norm_blocks(M));
     if (threadIdx.x == 0) {
-        float *st = a.stats + m * 4;
-        const double cnt = rc[0];
-        if (cnt == 0.0) {
-            st[0] = 0.0f;
-            st[1] = 1.0f;
-            st[2] = 1.0f;
-            st[3] = 0.0f;
-            return;
-        }
-        const float adv_eps = a.pop ? a.table[m * kPopTableRow + a.adv_eps_col] : a.adv_eps;
-        const double mean = rs[0] / cnt;
-        double var = cnt > 1.0 ? (rq[0] - rs[0] * mean) / (cnt - 1.0) : 0.0; // (one sample: PPO2's numpy std is 0; torch.std would be NaN)
-        if (var < 0.0) var = 0.0;
-        const float stdp = (float)sqrt(var) + adv_eps;
-        st[0] = (float)mean;
-        st[1] = stdp;
-        st[2] = 1.0f / stdp;
-        st[3] = 0.0f;
+        double *o = a.out + y * 4;
+        o[0] = rs[0];
+        o[1] = rq[0];
+        o[2] = rc[0];
+        o[3] = 0.0;
     }
+}
+
+// one lane per minibatch: the W shards' rows added in rank order, then the row
+__global__ void __launch_bounds__(256) mb_rows_kernel(int W, int n_batches, const double *__restrict__ rows, float adv_eps, float *__restrict__ table)
+{
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= n_batches) return;
+    const double *r0 = rows + (size_t)b * 4;
+    double S = r0[0], Q = r0[1], cnt = r0[2];
+    for (int r = 1; r < W; ++r) {
+        const double *p = r0 + (size_t)r * (size_t)n_batches * 4;
+        S += p[0];
+        Q += p[1];
+        cnt += p[2];
+    }
+    adv_stats_row(S, Q, cnt, adv_eps, table + (size_t)b * 4);
 }
 
 } // namespace
@@ -193,6 +280,31 @@ hipError_t launch_adv_norm(const AdvNormLaunch &l, hipStream_t stream)
     a.stats = l.stats;
     hipLaunchKernelGGL(adv_norm_partial_kernel, dim3(kAdvNormBlocks, (unsigned)l.lay.members), dim3(256), 0, stream, a);
     hipLaunchKernelGGL(adv_norm_final_kernel, dim3((unsigned)l.lay.members), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_minibatch_adv_sums(const MinibatchAdvSums &l, hipStream_t stream)
+{
+    MbSumsArgs a;
+    a.adv = l.adv;
+    a.perm = l.perm;
+    a.n_samples = l.n_samples;
+    a.n = l.n;
+    a.chunk = l.chunk;
+    a.C = (l.n + l.chunk - 1) / l.chunk;
+    a.part = l.part;
+    a.out = l.out;
+    const unsigned rows = (unsigned)(l.epochs * a.C);
+    // (the widest minibatch is a full chunk: B is monotone in M, so no workgroup a shorter one needs is missing)
+    const long long bmax = (l.chunk + 1023) / 1024;
+    hipLaunchKernelGGL(mb_sums_partial_kernel, dim3((unsigned)(bmax < kAdvNormBlocks ? bmax : kAdvNormBlocks), rows), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(mb_sums_final_kernel, dim3(rows), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_minibatch_adv_rows(int n_shards, int n_batches, const double *rows, float adv_eps, float *table, hipStream_t stream)
+{
+    hipLaunchKernelGGL(mb_rows_kernel, dim3((unsigned)((n_batches + 255) / 256)), dim3(256), 0, stream, n_shards, n_batches, rows, adv_eps, table);
     return hipGetLastError();
 }
 

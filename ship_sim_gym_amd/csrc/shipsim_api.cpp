@@ -213,6 +213,10 @@ struct ssg_handle {
     // ssg_ppo_set_adv_norm: the mode (SSG_ADV_NORM_BATCH: nothing bound), the member count the scratch serves and the caller's scratch
     int adv_norm_mode = SSG_ADV_NORM_BATCH, adv_norm_members = 0;
     void *adv_norm_scratch = nullptr;
+    // ssg_ppo_set_adv_table: the job's table of per-minibatch stats rows f32 [adv_table_rows][4] (NULL: none) and the selected row;
+    // bound only while the mode above is SSG_ADV_NORM_BATCH — a handle has one source of per-minibatch statistics at a time
+    float *adv_table = nullptr;
+    int adv_table_rows = 0, adv_table_row = 0;
     std::string err;
 };
 
@@ -1219,8 +1223,10 @@ static int check_batch(ssg_handle *h, int64_t n_samples, const ssg::PpoBatch &b,
 
 // Per-minibatch advantage normalisation (ssg_ppo_set_adv_norm): while it is bound, every minibatch of the gradient / update entry points
 // takes its statistics from the handle's scratch (its stats rows, then its partials) instead of the workspace's batch statistics.
+// With a table bound (ssg_ppo_set_adv_table) the gradient call reads the selected row, and nothing is launched ahead of it.
 static void adv_norm_bind(const ssg_handle *h, ssg::PpoMinibatch &mb)
 {
+    if (h->adv_table) mb.adv_stats = h->adv_table + 4 * (size_t)h->adv_table_row;
     if (h->adv_norm_mode != SSG_ADV_NORM_MINIBATCH) return;
     char *base = static_cast<char *>(h->adv_norm_scratch);
     mb.adv_stats = reinterpret_cast<float *>(base);
@@ -2067,6 +2073,9 @@ static int update_call(ssg_handle *h, UpdateCall &c, void *stream)
 {
     const long long M = !c.loop ? c.mb.M : c.sched ? c.sc.Cmax : chunking(c.mb.n_samples, c.minibatches).C;
     int rc = check_workspace(h, c.mb.ws, c.ws_nbytes, need_grad(c.mb.slots_off, c.mb.lay.members, c.pol, M, c.ext), c.what);
+    if (rc == SSG_OK && h->adv_table && (c.loop || c.mb.table)) // (the last thing the host judges: no refusal of a handle without a table moves)
+        rc = fail(h, SSG_ERR_BAD_ARG, std::string(c.what) + ": an advantage table is bound to the handle (ssg_ppo_set_adv_table): a table row is one "
+                                                           "minibatch's and this call runs many, or many members'; only ssg_ppo_grad and ssg_ppo_grad_ext read it");
     if (rc == SSG_OK && !c.device_checked) rc = check_ready(h, false);
     if (rc == SSG_OK) rc = prepare_ppo(h);
     if (rc != SSG_OK) return rc;
@@ -2523,6 +2532,8 @@ int ssg_ppo_set_adv_norm(ssg_handle *h, int mode, int n_members, void *dev_scrat
         h->adv_norm_mode = SSG_ADV_NORM_BATCH;
         h->adv_norm_members = 0;
         h->adv_norm_scratch = nullptr;
+        h->adv_table = nullptr; // (a successful call drops a bound table: the mode named here is the handle's one source)
+        h->adv_table_rows = h->adv_table_row = 0;
         return SSG_OK;
     }
     if (n_members < 1 || n_members > SSG_POP_MAX_MEMBERS)
@@ -2540,6 +2551,8 @@ int ssg_ppo_set_adv_norm(ssg_handle *h, int mode, int n_members, void *dev_scrat
     h->adv_norm_mode = mode;
     h->adv_norm_members = n_members;
     h->adv_norm_scratch = dev_scratch;
+    h->adv_table = nullptr;
+    h->adv_table_rows = h->adv_table_row = 0;
     return SSG_OK;
 }
 
@@ -2548,6 +2561,107 @@ int ssg_ppo_get_adv_norm(const ssg_handle *h, int *mode, int *n_members)
     if (!h || !mode || !n_members) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_ppo_get_adv_norm: NULL handle, mode or n_members");
     *mode = h->adv_norm_mode;
     *n_members = h->adv_norm_members;
+    return SSG_OK;
+}
+
+// ABI 9 additions: the job-wide per-minibatch advantage normalisation.  The table binding is host only; the two launching calls refuse
+// in the order of the data-parallel entry points: the handle, the state blob, what the host can judge, then the device.
+int ssg_ppo_set_adv_table(ssg_handle *h, float *dev_table, int n_rows)
+{
+    if (!h) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_ppo_set_adv_table: NULL handle");
+    if (!dev_table) { // unbind (n_rows is not read; the mode stays as it is)
+        h->adv_table = nullptr;
+        h->adv_table_rows = h->adv_table_row = 0;
+        return SSG_OK;
+    }
+    if (reinterpret_cast<uintptr_t>(dev_table) % 16 != 0)
+        return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_set_adv_table: dev_table must be 16-byte aligned"); // (the binding stays as it was, here and below)
+    if (n_rows < 1) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_set_adv_table: n_rows < 1");
+    h->adv_table = dev_table;
+    h->adv_table_rows = n_rows;
+    h->adv_table_row = 0;
+    h->adv_norm_mode = SSG_ADV_NORM_BATCH; // (the table is now the handle's one source of per-minibatch statistics)
+    h->adv_norm_members = 0;
+    h->adv_norm_scratch = nullptr;
+    return SSG_OK;
+}
+
+int ssg_ppo_select_adv_row(ssg_handle *h, int row)
+{
+    if (!h) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_ppo_select_adv_row: NULL handle");
+    if (!h->adv_table) return fail(h, SSG_ERR_BAD_ARG, "ssg_ppo_select_adv_row: no advantage table is bound (ssg_ppo_set_adv_table)");
+    if (row < 0 || row >= h->adv_table_rows) {
+        char buf[160];
+        std::snprintf(buf, sizeof buf, "ssg_ppo_select_adv_row: row %d is outside [0, %d), the bound table's rows", row, h->adv_table_rows);
+        return fail(h, SSG_ERR_BAD_ARG, buf);
+    }
+    h->adv_table_row = row;
+    return SSG_OK;
+}
+
+int ssg_ppo_get_adv_table(const ssg_handle *h, float **dev_table, int *n_rows, int *row)
+{
+    if (!h || !dev_table || !n_rows || !row) return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_ppo_get_adv_table: NULL handle, dev_table, n_rows or row");
+    *dev_table = h->adv_table;
+    *n_rows = h->adv_table_rows;
+    *row = h->adv_table_row;
+    return SSG_OK;
+}
+
+int ssg_ppo_minibatch_adv_nbytes(int n_batches, size_t *nbytes)
+{
+    if (!nbytes || n_batches < 1 || n_batches > SSG_ADV_TABLE_MAX_ROWS)
+        return fail(nullptr, SSG_ERR_BAD_ARG, "ssg_ppo_minibatch_adv_nbytes: NULL nbytes or n_batches outside 1..SSG_ADV_TABLE_MAX_ROWS");
+    *nbytes = ssg::minibatch_adv_bytes(n_batches);
+    return SSG_OK;
+}
+
+int ssg_ppo_minibatch_adv_sums(ssg_handle *h, int64_t n_samples, const float *dev_adv, const int64_t *dev_perm, int epochs, int64_t n,
+                               int64_t chunk, double *dev_out, void *dev_scratch, size_t scratch_nbytes, void *stream)
+{
+    const char *w = "ssg_ppo_minibatch_adv_sums: ";
+    int rc = pop_bound(h);
+    if (rc != SSG_OK) return rc;
+    if (!dev_adv || !dev_perm || !dev_out || !dev_scratch) return fail(h, SSG_ERR_BAD_ARG, std::string(w) + "NULL dev_adv, dev_perm, dev_out or dev_scratch");
+    if (n_samples < 1 || epochs < 1 || n < 1 || chunk < 1) return fail(h, SSG_ERR_BAD_ARG, std::string(w) + "n_samples, epochs, n or chunk < 1");
+    if (chunk > n) return fail(h, SSG_ERR_BAD_ARG, std::string(w) + "chunk > n");
+    const int64_t chunks = (n + chunk - 1) / chunk;
+    if (chunks > SSG_ADV_TABLE_MAX_ROWS / epochs) { // (epochs * chunks > SSG_ADV_TABLE_MAX_ROWS, without the product)
+        char buf[200];
+        std::snprintf(buf, sizeof buf, "%d epochs x %lld chunks: more than SSG_ADV_TABLE_MAX_ROWS minibatches in one call (the grid's rows)", epochs,
+                      (long long)chunks);
+        return fail(h, SSG_ERR_BAD_ARG, std::string(w) + buf);
+    }
+    if (reinterpret_cast<uintptr_t>(dev_scratch) % 256 != 0) return fail(h, SSG_ERR_BAD_ARG, std::string(w) + "dev_scratch must be 256-byte aligned");
+    const size_t need = ssg::minibatch_adv_bytes((int)(epochs * chunks));
+    if (scratch_nbytes < need) {
+        char buf[200];
+        std::snprintf(buf, sizeof buf, "scratch_nbytes of %zu bytes, %lld minibatches need %zu (ssg_ppo_minibatch_adv_nbytes)", scratch_nbytes,
+                      (long long)(epochs * chunks), need);
+        return fail(h, SSG_ERR_BAD_ARG, std::string(w) + buf);
+    }
+    rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    const ssg::MinibatchAdvSums l = {dev_adv, dev_perm, n_samples, epochs, n, chunk, static_cast<double *>(dev_scratch), dev_out};
+    hipError_t e = ssg::launch_minibatch_adv_sums(l, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("minibatch adv sums launch: ") + hipGetErrorString(e));
+    return SSG_OK;
+}
+
+int ssg_ppo_set_minibatch_adv_rows(ssg_handle *h, int n_shards, int n_batches, const double *dev_rows, double adv_eps, float *dev_table,
+                                   void *stream)
+{
+    const char *w = "ssg_ppo_set_minibatch_adv_rows: ";
+    int rc = pop_bound(h);
+    if (rc != SSG_OK) return rc;
+    if (!dev_rows || !dev_table) return fail(h, SSG_ERR_BAD_ARG, std::string(w) + "NULL dev_rows or dev_table");
+    if (n_shards < 1 || n_shards > SSG_DP_MAX_SHARDS) return fail(h, SSG_ERR_BAD_ARG, std::string(w) + "n_shards must be in 1..SSG_DP_MAX_SHARDS");
+    if (n_batches < 1 || n_batches > SSG_ADV_TABLE_MAX_ROWS) return fail(h, SSG_ERR_BAD_ARG, std::string(w) + "n_batches must be in 1..SSG_ADV_TABLE_MAX_ROWS");
+    if (!std::isfinite(adv_eps)) return fail(h, SSG_ERR_BAD_ARG, std::string(w) + "adv_eps is not finite");
+    rc = check_ready(h, false);
+    if (rc != SSG_OK) return rc;
+    hipError_t e = ssg::launch_minibatch_adv_rows(n_shards, n_batches, dev_rows, (float)adv_eps, dev_table, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(h, SSG_ERR_HIP, std::string("minibatch adv rows launch: ") + hipGetErrorString(e));
     return SSG_OK;
 }
 

@@ -352,6 +352,7 @@ struct PpoMinibatch {
     long long K, perm_epochs;
     // per-minibatch advantage normalisation (ssg_ppo_set_adv_norm; both NULL: the batch statistics in the workspace): the scratch's
     // stats rows and partials.  The two launches of shipsim_advnorm.hip then run ahead of the gradient launch, which reads these rows.
+    // adv_stats alone (ssg_ppo_set_adv_table): a finished row of the job's table, read as it is, nothing launched ahead.
     float *adv_stats;
     double *adv_part;
 };
@@ -380,6 +381,18 @@ struct AdvNormLaunch {
     double *part;
 };
 hipError_t launch_adv_norm(const AdvNormLaunch &l, hipStream_t stream);
+// The job-wide form (ssg_ppo_minibatch_adv_sums / ssg_ppo_set_minibatch_adv_rows): the sums {s, q, c, 0} of every minibatch of an
+// update — minibatch e*C + j is perm[e][j*chunk : min(n, (j+1)*chunk)], C = ceil(n / chunk) — in two launches, with the partials
+// scratch f64 [epochs*C][kAdvNormBlocks][3]; then the table of stats rows from the W shards' gathered sums, one launch.
+inline size_t minibatch_adv_bytes(int n_batches) { return ((size_t)n_batches * kAdvNormBlocks * 3 * sizeof(double) + 255) & ~(size_t)255; }
+struct MinibatchAdvSums {
+    const float *adv;
+    const int64_t *perm;
+    long long n_samples, epochs, n, chunk;
+    double *part, *out;
+};
+hipError_t launch_minibatch_adv_sums(const MinibatchAdvSums &l, hipStream_t stream);
+hipError_t launch_minibatch_adv_rows(int n_shards, int n_batches, const double *rows, float adv_eps, float *table, hipStream_t stream);
 // RLlib's update_kl on every member's coefficient from the last epoch's `chunks` minibatches (sched_hdr, nullable: the schedule
 // table, whose header row m holds member m's own chunk count)
 hipError_t launch_kl_adapt(int members, const PpoExtLaunch &ext, float kl_target, int P, long long chunks, const int32_t *sched_hdr, void *ws,

@@ -1195,8 +1195,9 @@ hipError_t launch_ppo_minibatch(const PpoMinibatch &mb, hipStream_t stream)
     a.M = mb.M;
     a.n_samples = mb.n_samples;
     a.stats = reinterpret_cast<const float *>(base + kPpoStatsOff);
-    if (mb.adv_stats) { // per-minibatch normalisation: this minibatch's own statistics first (two launches), into the scratch's rows
-        if (!mb.adv_part) return hipErrorInvalidValue;
+    if (mb.adv_stats && !mb.adv_part) a.stats = mb.adv_stats; // a finished row of the job's table (ssg_ppo_set_adv_table)
+    if (mb.adv_part) { // per-minibatch normalisation: this minibatch's own statistics first (two launches), into the scratch's rows
+        if (!mb.adv_stats) return hipErrorInvalidValue;
         AdvNormLaunch an = {};
         an.adv = mb.batch.adv;
         an.idx = mb.idx;

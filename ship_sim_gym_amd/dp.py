@@ -29,13 +29,21 @@ The episode log of such a job is ship_sim_gym_amd/episode_log.py's ``EpisodeLog(
 episodes of a rollout into one fixed-size block, the blocks are all-gathered once, and every rank merges them into the same ring in the
 order one log over all the job's envs would keep, replayable in one process with ``shard_block`` / ``merge_blocks`` and torch.stack.
 
-Out of scope: adv_norm="minibatch" across ranks, resuming a multi-rank run,
-populations across ranks, overlapping the gather with the next gradient, running this loop from C.
+PPO2's per-minibatch advantage normalisation of such a job is ``DataParallelPPO(job_adv_norm="minibatch")``: the advantages are fixed
+once GAE has run and a rank's permutations are known before its first gradient, so every rank sums adv, adv^2 and 1 over EACH minibatch
+of the update in one pass (ssg_ppo_minibatch_adv_sums), the [epochs * chunks, 4] blocks are all-gathered once per update, and every rank
+forms the same table of stats rows from them in rank order (ssg_ppo_set_minibatch_adv_rows); the per-minibatch loop then only selects
+its row.  Replayable in one process with ``shard_minibatch_sums`` / ``set_minibatch_rows`` / ``select_minibatch`` and torch.stack;
+``minibatch_sums_reference`` and ``minibatch_rows_reference`` restate the two steps in numpy.  ``adv_norm="minibatch"`` (the
+single-handle mode, whose statistics are one shard's) stays refused.
+
+Out of scope: resuming a multi-rank run, populations across ranks, a gather per minibatch, overlapping the gather with the next
+gradient, running this loop from C.
 """
 import ctypes as C
 
 from . import _native as N
-from .ppo import NativePPO, _torch, _tree256, chunk_split
+from .ppo import NativePPO, _torch, _tree256, adv_stats_row_reference, chunk_split, minibatch_adv_sums_reference
 from .sharding import all_gather_rows
 
 
@@ -75,6 +83,43 @@ def moments_reference(rows, adv_eps):
         var = 0.0
     stdp = np.float32(np.sqrt(var)) + np.float32(adv_eps)
     return np.array([np.float32(mean), stdp, np.float32(1.0) / stdp, 0.0], dtype=np.float32)
+
+
+def minibatch_sums_reference(adv, perm, chunk, n_samples, partials=False):
+    """ssg_ppo_minibatch_adv_sums in numpy, in the device's order of operations: f64 [epochs * C, 4] rows {s, q, c, 0}, C = ceil(n /
+    chunk), row e * C + j for the minibatch perm[e][j * chunk: min(n, (j + 1) * chunk)].  adv: f32, flat; perm: int64 [epochs, n]; an
+    index outside [0, n_samples) counts for nothing.  partials=True: (rows, the list of every minibatch's f64 [B, 3] partials)."""
+    import numpy as np
+    adv = np.asarray(adv, dtype=np.float32).reshape(-1)
+    perm = np.asarray(perm, dtype=np.int64)
+    epochs, n = perm.shape
+    C_ = -(-n // int(chunk))
+    rows, parts = np.zeros((epochs * C_, 4)), []
+    for e in range(epochs):
+        for j in range(C_):
+            idx = perm[e, j * int(chunk): min(n, (j + 1) * int(chunk))]
+            valid = (idx >= 0) & (idx < int(n_samples))
+            s, q, cnt, part = minibatch_adv_sums_reference(adv[np.where(valid, idx, 0)], valid)
+            rows[e * C_ + j, :3] = s, q, cnt
+            parts.append(part)
+    return (rows, parts) if partials else rows
+
+
+def minibatch_rows_reference(rows, adv_eps):
+    """ssg_ppo_set_minibatch_adv_rows in numpy: rows f64 [W, n_batches, 4], per minibatch the shards' S, Q and C added in rank order
+    starting from rank 0's, then ppo.adv_stats_row_reference's formula: the table f32 [n_batches, 4]."""
+    import numpy as np
+    rows = np.asarray(rows, dtype=np.float64)
+    if rows.ndim != 3 or rows.shape[2] != 4:
+        raise ValueError("minibatch_rows_reference: rows must be f64 [W, n_batches, 4] (got %s)" % (rows.shape,))
+    table = np.zeros((rows.shape[1], 4), dtype=np.float32)
+    with np.errstate(all="ignore"):
+        for b in range(rows.shape[1]):
+            S, Q, cnt = rows[0, b, :3]
+            for r in range(1, rows.shape[0]):
+                S, Q, cnt = S + rows[r, b, 0], Q + rows[r, b, 1], cnt + rows[r, b, 2]
+            table[b] = adv_stats_row_reference(S, Q, cnt, adv_eps)
+    return table
 
 
 def shard_weights(counts):
@@ -162,6 +207,9 @@ def check_return_filter(return_filter, world):
                          "the job's: make it with ReturnFilter(env, job=True)" % int(world))
 
 
+JOB_ADV_NORM_MODES = ("batch", "minibatch")
+
+
 # ------------------------------------------------------------------------------------------------------------------------------------
 class DataParallelPPO(NativePPO):
     """NativePPO over this rank's shard of a W-rank job.  group: the process group (None: the default one; with none initialised the
@@ -169,12 +217,21 @@ class DataParallelPPO(NativePPO):
     the shards make the same number of chunks for that rollout length and minibatch count (update() checks what it is given).
     ``report`` / ``report_device`` are NativePPO's: the record is then this rank's OWN shard's (its n, means, variances and post-update
     group; the stats rows' means are the job's, since every rank holds the same rows).  ``job_report`` gives the JOB's record: every
-    rank's sum row gathered once, the same record formed on every rank (ssg_ppo_report_sums / ssg_ppo_report_rows)."""
+    rank's sum row gathered once, the same record formed on every rank (ssg_ppo_report_sums / ssg_ppo_report_rows).
+    job_adv_norm="minibatch": PPO2's rule over the job — the advantages of a minibatch are normalised by the statistics of the JOB's
+    minibatch, from one gather per update (the module's docstring); "batch" (the default): once per rollout, gae()'s job statistics."""
 
-    def __init__(self, policy, env, group=None, plan=None, **kw):
+    def __init__(self, policy, env, group=None, plan=None, job_adv_norm="batch", **kw):
         if kw.get("adv_norm", "batch") != "batch":
             raise ValueError("DataParallelPPO: adv_norm must be 'batch' (per-minibatch statistics across ranks are out of scope; got %r)"
                              % (kw["adv_norm"],))
+        if job_adv_norm not in JOB_ADV_NORM_MODES:
+            raise ValueError("DataParallelPPO: job_adv_norm must be 'batch' or 'minibatch' (got %r)" % (job_adv_norm,))
+        self.job_adv_norm = job_adv_norm
+        self._job_table = None    # f32 [epochs * chunks, 4]: the update's stats rows (set_minibatch_rows)
+        self._job_scratch = None  # ssg_ppo_minibatch_adv_sums' partials
+        self._job_chunks = 0      # chunks per epoch of the sums last taken: select_minibatch's row stride
+        self._job_row = 0
         self.group = group
         self.rank, self.world = _world(group)
         if self.world > N.DP_MAX_SHARDS:
@@ -230,6 +287,90 @@ class DataParallelPPO(NativePPO):
         with torch.cuda.device(self.policy.device):
             N.check(N.lib().ssg_ppo_set_adv_moments(h, int(rows.shape[0]), C.c_void_p(rows.data_ptr()), float(self.hp.adv_eps), ws, nb,
                                                     self._stream()), h, "ssg_ppo_set_adv_moments")
+
+    # ------------------------------------------------------------------------------------------------
+    # per-minibatch advantage statistics over the job (job_adv_norm="minibatch")
+    # ------------------------------------------------------------------------------------------------
+    def _bind_adv_norm(self):
+        """(Re)bind this object's source of statistics on the env (host only): the batch mode, which drops a table another trainer
+        left, or this object's table and the row it selected last."""
+        if self.job_adv_norm != "minibatch":
+            return super(DataParallelPPO, self)._bind_adv_norm()
+        if self._job_table is None:
+            raise ValueError("DataParallelPPO: job_adv_norm='minibatch' and no table yet: call set_minibatch_rows first (update() does)")
+        self.env.set_adv_table(self._job_table)
+        self.env.select_adv_row(self._job_row)
+
+    def _need_job_mode(self, who):
+        if self.job_adv_norm != "minibatch":
+            raise ValueError("DataParallelPPO.%s: job_adv_norm is %r" % (who, self.job_adv_norm))
+
+    def shard_minibatch_sums(self, batch, perm, minibatches, partials=False):
+        """f64 [epochs * C, 4] on the device: {sum adv, sum adv^2, count, 0} of every minibatch update(batch, perm, epochs, minibatches)
+        would cut from THIS shard's samples — row e * C + j for perm[e].chunk(minibatches)[j] (ssg_ppo_minibatch_adv_sums; two launches,
+        enqueued only).  perm: int64 [epochs, n] over the batch's n samples.  partials=True: (rows, the f64 [epochs * C, 64, 3] view of
+        the scratch, of which a minibatch of M indices wrote its first min(64, ceil(M / 1024)))."""
+        torch = _torch()
+        self._need_job_mode("shard_minibatch_sums")
+        dev = self.policy.device
+        adv = self._flat(batch, "adv", torch.float32)
+        n = adv.numel()
+        perm = perm.to(device=dev, dtype=torch.int64).contiguous()
+        if perm.dim() != 2 or int(perm.shape[1]) != n:
+            raise ValueError("DataParallelPPO.shard_minibatch_sums: perm must be int64 [epochs, %d] (got %s)" % (n, tuple(perm.shape)))
+        epochs = int(perm.shape[0])
+        chunk, chunks = chunk_split(n, minibatches)
+        nb = epochs * chunks
+        need = C.c_size_t()
+        N.check(N.lib().ssg_ppo_minibatch_adv_nbytes(nb, C.byref(need)), None, "ssg_ppo_minibatch_adv_nbytes")
+        if self._job_scratch is None or self._job_scratch.numel() < need.value:
+            self._job_scratch = torch.zeros(need.value, dtype=torch.uint8, device=dev)
+        out = torch.empty((nb, 4), dtype=torch.float64, device=dev)
+        h = self.env._h
+        with torch.cuda.device(dev):
+            N.check(N.lib().ssg_ppo_minibatch_adv_sums(h, n, C.c_void_p(adv.data_ptr()), C.c_void_p(perm.data_ptr()), epochs, n, chunk,
+                                                       C.c_void_p(out.data_ptr()), C.c_void_p(self._job_scratch.data_ptr()),
+                                                       self._job_scratch.numel(), self._stream()), h, "ssg_ppo_minibatch_adv_sums")
+        self._job_chunks = chunks
+        if partials:
+            return out, self._job_scratch[:nb * N.ADV_NORM_BLOCKS * 24].view(torch.float64).view(nb, N.ADV_NORM_BLOCKS, 3)
+        return out
+
+    def set_minibatch_rows(self, rows):
+        """The update's table of stats rows from the gathered sums (f64 [W, epochs * C, 4], shard order), bound to the env with row 0
+        selected (ssg_ppo_set_minibatch_adv_rows, one launch; ssg_ppo_set_adv_table).  ``minibatch_table()`` shows it."""
+        torch = _torch()
+        self._need_job_mode("set_minibatch_rows")
+        dev = self.policy.device
+        rows = rows.to(device=dev, dtype=torch.float64).contiguous()
+        if rows.dim() != 3 or rows.shape[2] != 4:
+            raise ValueError("DataParallelPPO.set_minibatch_rows: rows must be f64 [W, epochs * chunks, 4] (got %s)" % (tuple(rows.shape),))
+        W, nb = int(rows.shape[0]), int(rows.shape[1])
+        table = torch.empty((nb, 4), dtype=torch.float32, device=dev)  # (a new one per update: the last one may still be read)
+        h = self.env._h
+        with torch.cuda.device(dev):
+            N.check(N.lib().ssg_ppo_set_minibatch_adv_rows(h, W, nb, C.c_void_p(rows.data_ptr()), float(self.hp.adv_eps),
+                                                           C.c_void_p(table.data_ptr()), self._stream()), h, "ssg_ppo_set_minibatch_adv_rows")
+        self._job_table, self._job_row = table, 0
+        self._bind_adv_norm()
+        return table
+
+    def select_minibatch(self, e, j):
+        """Select the row of minibatch j of epoch e for the next ``local_row`` (host only)."""
+        self._need_job_mode("select_minibatch")
+        if self._job_table is None:
+            raise ValueError("DataParallelPPO.select_minibatch: no table yet: call set_minibatch_rows first")
+        row = int(e) * self._job_chunks + int(j)
+        if not (0 <= int(j) < self._job_chunks and 0 <= row < int(self._job_table.shape[0])):
+            raise ValueError("DataParallelPPO.select_minibatch: (%d, %d) is outside the table's %d rows of %d chunks per epoch"
+                             % (int(e), int(j), int(self._job_table.shape[0]), self._job_chunks))
+        self._job_row = row
+
+    def minibatch_table(self):
+        """f32 [epochs * C, 4] on the device: the table set_minibatch_rows made last, row e * C + j = {mean, std + adv_eps, its
+        inverse, 0} of the job's minibatch (e, j)."""
+        self._need_job_mode("minibatch_table")
+        return self._job_table
 
     def _apply_return_filter(self, return_filter, batch):
         if getattr(return_filter, "job", False):
@@ -330,9 +471,14 @@ class DataParallelPPO(NativePPO):
             self.dist(batch)  # (from the parameters on entry, as NativePPO.update takes it)
         chunk = lens[self.rank]
         self._ws(n, chunk)  # (grown once: the running KL sum lives in it across the minibatches)
+        job_rows = self.job_adv_norm == "minibatch"
+        if job_rows:  # every minibatch's sums in one pass, one gather, the same table on every rank
+            self.set_minibatch_rows(all_gather_rows(self.shard_minibatch_sums(batch, perm, minibatches), self.group))
         out = []
         for e in range(int(epochs)):
             for j in range(n_chunks):
+                if job_rows:
+                    self.select_minibatch(e, j)
                 row = self.local_row(batch, perm[e, j * chunk: min(n, (j + 1) * chunk)])
                 rows = all_gather_rows(row, self.group)
                 st = self.apply_rows(rows, chunk_counts(K, self.shard_envs, minibatches, j), j == 0,
@@ -349,13 +495,18 @@ class DataParallelPPO(NativePPO):
 
     # ------------------------------------------------------------------------------------------------
     def state_dict(self):
-        """NativePPO's state plus ``world`` and ``rank``, which load_state_dict checks."""
+        """NativePPO's state plus ``world`` and ``rank``, which load_state_dict checks, and ``job_adv_norm`` (the mode is made at
+        construction: it must be the state's; a state without the key is a "batch" one).  The table is not state: every update()
+        makes its own before anything reads it."""
         sd = super(DataParallelPPO, self).state_dict()
-        sd["world"], sd["rank"] = int(self.world), int(self.rank)
+        sd["world"], sd["rank"], sd["job_adv_norm"] = int(self.world), int(self.rank), self.job_adv_norm
         return sd
 
     def load_state_dict(self, sd):
         for k, mine in (("world", self.world), ("rank", self.rank)):
             if k not in sd or int(sd[k]) != int(mine):
                 raise ValueError("DataParallelPPO.load_state_dict: %s: the state has %r, this object %r" % (k, sd.get(k, "nothing"), mine))
+        if sd.get("job_adv_norm", "batch") != self.job_adv_norm:
+            raise ValueError("DataParallelPPO.load_state_dict: job_adv_norm: the state has %r, this object %r"
+                             % (sd.get("job_adv_norm", "batch"), self.job_adv_norm))
         return super(DataParallelPPO, self).load_state_dict(sd)

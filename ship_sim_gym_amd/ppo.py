@@ -93,12 +93,10 @@ def _tree256(x):
     return x[0]
 
 
-def minibatch_adv_reference(adv_gathered_f32, valid, adv_eps, partials=False):
-    """The two launches of SSG_ADV_NORM_MINIBATCH restated in numpy, in their order of operations: the stats row f32 [4] = {mean,
-    std + adv_eps, its inverse, 0} of ONE minibatch.  adv_gathered_f32: the advantages at the minibatch's M positions, in the
-    minibatch's order (anything where valid is False); valid: bool [M], the positions whose index lies in [0, n_samples).
-    partials=True: (row, the first launch's f64 [B, 3] partials (s, q, c), B = min(64, ceil(M / 1024))) — the f32 row alone seldom
-    shows a change of the f64 order, the partials do."""
+def minibatch_adv_sums_reference(adv_gathered_f32, valid):
+    """The sums of one minibatch as the kernels of csrc/shipsim_advnorm.hip form them: (s, q, cnt, the first launch's f64 [B, 3] partials
+    (s, q, c), B = min(64, ceil(M / 1024))).  adv_gathered_f32: the advantages at the minibatch's M positions, in the minibatch's order
+    (anything where valid is False); valid: bool [M], the positions whose index lies in [0, n_samples)."""
     import numpy as np
     a = np.where(np.asarray(valid, dtype=bool), np.asarray(adv_gathered_f32, dtype=np.float32), np.float32(0)).astype(np.float64)
     c = np.asarray(valid, dtype=bool).astype(np.float64).reshape(-1)
@@ -117,14 +115,33 @@ def minibatch_adv_reference(adv_gathered_f32, valid, adv_eps, partials=False):
     for b in range(B):  # the workgroup's tree; one (s, q, c) partial
         part[b] = _tree256(acc[b].copy())
     s, q, cnt = _tree256(part.copy())  # the finalising workgroup: partial b in entry b, zeros beyond
+    return s, q, cnt, part[:B].copy()
+
+
+def adv_stats_row_reference(s, q, cnt, adv_eps):
+    """The stats row f32 [4] = {mean, std + adv_eps, its inverse, 0} of the f64 sums s, q and the count cnt, as the device forms it
+    ({0, 1, 1, 0} for no sample, a zero variance for one)."""
+    import numpy as np
     if cnt == 0.0:
-        row = np.array([0.0, 1.0, 1.0, 0.0], dtype=np.float32)
-    else:
+        return np.array([0.0, 1.0, 1.0, 0.0], dtype=np.float32)
+    with np.errstate(all="ignore"):
+        s, q, cnt = np.float64(s), np.float64(q), np.float64(cnt)
         mean = s / cnt
-        var = max(0.0, (q - s * mean) / (cnt - 1.0)) if cnt > 1.0 else 0.0
+        var = (q - s * mean) / (cnt - 1.0) if cnt > 1.0 else np.float64(0.0)
+        if var < 0.0:  # (the device's comparison: a NaN variance stays NaN)
+            var = np.float64(0.0)
         stdp = np.float32(np.sqrt(var)) + np.float32(adv_eps)
-        row = np.array([np.float32(mean), stdp, np.float32(1.0) / stdp, 0.0], dtype=np.float32)
-    return (row, part[:B].copy()) if partials else row
+        return np.array([np.float32(mean), stdp, np.float32(1.0) / stdp, 0.0], dtype=np.float32)
+
+
+def minibatch_adv_reference(adv_gathered_f32, valid, adv_eps, partials=False):
+    """The two launches of SSG_ADV_NORM_MINIBATCH restated in numpy, in their order of operations: the stats row f32 [4] = {mean,
+    std + adv_eps, its inverse, 0} of ONE minibatch (minibatch_adv_sums_reference's sums through adv_stats_row_reference).
+    partials=True: (row, the first launch's f64 [B, 3] partials) — the f32 row alone seldom shows a change of the f64 order, the
+    partials do."""
+    s, q, cnt, part = minibatch_adv_sums_reference(adv_gathered_f32, valid)
+    row = adv_stats_row_reference(s, q, cnt, adv_eps)
+    return (row, part) if partials else row
 
 
 def gae_boot_reference(rew, done, val, last_val, boot, gamma=0.99, lam=0.95, adv_eps=1e-8):

@@ -197,6 +197,7 @@ class ShipVecEnv(*_BASES):
         self._timeout_boot = None       # set_timeout_bootstrap: {"term_obs", "boot"}
         self._obs_filter = None         # set_obs_filter
         self._adv_norm_scratch = None   # set_adv_norm
+        self._adv_table = None          # set_adv_table
         self._full_reset_done = False   # reset_tensor(mask=None) has run (the handle's first full reset zeroes the blob)
         self._pending = None
         self._closed = False
@@ -987,12 +988,36 @@ class ShipVecEnv(*_BASES):
         nb = scratch.numel() * scratch.element_size() if scratch is not None else 0
         N.check(N.lib().ssg_ppo_set_adv_norm(self._h, int(mode), int(n_members), N.ptr(scratch), nb), self._h, "ssg_ppo_set_adv_norm")
         self._adv_norm_scratch = scratch if int(mode) == N.ADV_NORM_MINIBATCH else None
+        self._adv_table = None  # (a successful binding of a mode drops a bound table)
 
     def adv_norm(self):
         """(mode, n_members) as bound (ssg_ppo_get_adv_norm)."""
         mode, members = C.c_int(), C.c_int()
         N.check(N.lib().ssg_ppo_get_adv_norm(self._h, C.byref(mode), C.byref(members)), self._h, "ssg_ppo_get_adv_norm")
         return mode.value, members.value
+
+    def set_adv_table(self, table):
+        """Bind the job's table of per-minibatch advantage statistics (ssg_ppo_set_adv_table): a contiguous f32 [rows, 4] device tensor
+        that the caller keeps alive, row 0 selected; None unbinds.  While it is bound the gradient calls read the selected row and
+        launch no statistics kernel, and the mode is N.ADV_NORM_BATCH.  Host only; a refused binding leaves the old one in place."""
+        if table is not None and (table.dtype != _torch().float32 or table.dim() != 2 or table.shape[1] != 4 or not table.is_contiguous()):
+            raise ValueError("ShipVecEnv.set_adv_table: the table must be a contiguous f32 [rows, 4] tensor (got %s %s)"
+                             % (table.dtype, tuple(table.shape)))
+        N.check(N.lib().ssg_ppo_set_adv_table(self._h, N.ptr(table), 0 if table is None else int(table.shape[0])), self._h,
+                "ssg_ppo_set_adv_table")
+        self._adv_table = table
+        if table is not None:
+            self._adv_norm_scratch = None
+
+    def select_adv_row(self, row):
+        """The row of the bound table the next gradient call reads (ssg_ppo_select_adv_row).  Host only."""
+        N.check(N.lib().ssg_ppo_select_adv_row(self._h, int(row)), self._h, "ssg_ppo_select_adv_row")
+
+    def adv_table(self):
+        """(address or None, rows, selected row) as bound (ssg_ppo_get_adv_table)."""
+        table, rows, row = C.c_void_p(), C.c_int(), C.c_int()
+        N.check(N.lib().ssg_ppo_get_adv_table(self._h, C.byref(table), C.byref(rows), C.byref(row)), self._h, "ssg_ppo_get_adv_table")
+        return table.value, rows.value, row.value
 
     def random_actions(self, seed, step0, K):
         """int32 [K, N] Philox action stream keyed by (seed, step, global env id), generated on the device."""

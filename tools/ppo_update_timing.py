@@ -10,7 +10,7 @@ line on stdout.  The kernels alone: `rocprofv3 --kernel-trace --stats -- python 
 
     python tools/ppo_update_timing.py [--configs 65536x32,4096x64] [--repeats 7] [--only torch|native] [--ext] [--separate-value] [--ret-filter]
                                       [--adv-norm] [--perm] [--timeout-bootstrap] [--checkpoint] [--dp] [--episode-log] [--report]
-                                      [--ret-filter-job] [--report-job] [--episode-log-job]
+                                      [--ret-filter-job] [--report-job] [--episode-log-job] [--adv-norm-job]
 
 --ext adds, in the same run, the extended update (NativePPO with vf_clip 0.2, max_grad_norm 0.5, kl_coef 1.0, kl_target 0.01: GAE, the
 ssg_ppo_dist launch, ssg_ppo_update_ext) as the path "native_ext", and the ssg_ppo_dist launch alone as "dist".
@@ -61,6 +61,13 @@ device, capacity 65 536, rows = the horizon: "eplog_plain" (EpisodeLog.append: s
 "_w8" (merge_blocks alone on 1, 2 and 8 stacked copies of this device's block: two launches); and the whole GAE + update with each log
 ahead of it, "native_eplog_plain" and "native_eplog_job"; and the block's size in bytes.  Every timed path follows one untimed GAE, as
 with --ret-filter-job.  The gather over real links is not part of any of them.
+--adv-norm-job adds, in the same run and alternating with the others, the job-wide per-minibatch advantage normalisation
+(``DataParallelPPO(job_adv_norm="minibatch")``) on one rank: the whole GAE + update of that trainer, "native_dp_mbjob" (the sums' two
+launches, a gather that is a no-op and the rows launch once per update, then a host-side select per minibatch), against the same
+trainer in batch mode, "native_dp_batch", and against "native_mbnorm_single" (NativePPO with adv_norm="minibatch": two launches ahead
+of every minibatch's gradient launch, inside the C loop); "mb_sums" (shard_minibatch_sums alone: ssg_ppo_minibatch_adv_sums, two
+launches) and "mb_rows_w1" / "_w2" / "_w8" (ssg_ppo_set_minibatch_adv_rows and the binding alone on 1, 2 and 8 stacked blocks: one
+launch).  Every timed path follows one untimed GAE, as with --ret-filter-job.  The gather over real links is not part of any of them.
 """
 import argparse
 import importlib.util
@@ -116,7 +123,7 @@ def _wall_ms(fn):
 
 def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext=False, separate_value=False, ret_filter=False,
             adv_norm=False, perm=False, timeout_bootstrap=False, checkpoint=False, checkpoint_dir=None, dp=False, episode_log=False,
-            report=False, ret_filter_job=False, report_job=False, episode_log_job=False):
+            report=False, ret_filter_job=False, report_job=False, episode_log_job=False, adv_norm_job=False):
     from ship_sim_gym_amd.policy import NativePolicy
     from ship_sim_gym_amd.ppo import NativePPO
     torch.manual_seed(0)
@@ -285,7 +292,23 @@ def measure(mod, envs, horizon, repeats, only, dev, epochs=2, minibatches=4, ext
         paths += [("eplog_merge_w%d" % W, merge_alone(W)) for W in (1, 2, 8)]
         paths += [("native_eplog_plain", native_path(ppo, seeded(), before=lambda: ep_plain.append(b))),
                   ("native_eplog_job", native_path(ppo, seeded(), before=lambda: ep_job.job_append(b)))]
-    if ret_filter_job or report_job or episode_log_job:
+    if adv_norm_job:  # (each trainer rebinds its own source of statistics on the env before every call)
+        from ship_sim_gym_amd.dp import DataParallelPPO
+        ppo_jb, ppo_jm = DataParallelPPO(pol, env), DataParallelPPO(pol, env, job_adv_norm="minibatch")
+        ppo_sm = NativePPO(pol, env, adv_norm="minibatch")
+        nb_a = dict(b)
+        ppo.gae(nb_a)
+        perm_a = torch.stack([torch.randperm(n, device=dev, generator=seeded()) for _ in range(epochs)])
+        own_sums = ppo_jm.shard_minibatch_sums(nb_a, perm_a, minibatches)
+
+        def mb_rows_alone(W):
+            stacked = torch.stack([own_sums] * W)
+            return lambda: ppo_jm.set_minibatch_rows(stacked)
+        paths += [("native_dp_batch", native_path(ppo_jb, seeded())), ("native_dp_mbjob", native_path(ppo_jm, seeded())),
+                  ("native_mbnorm_single", native_path(ppo_sm, seeded())),
+                  ("mb_sums", lambda: ppo_jm.shard_minibatch_sums(nb_a, perm_a, minibatches))]
+        paths += [("mb_rows_w%d" % W, mb_rows_alone(W)) for W in (1, 2, 8)]
+    if ret_filter_job or report_job or episode_log_job or adv_norm_job:
         spacer = lambda: ppo.gae(dict(b))  # noqa: E731
     else:
         spacer = lambda: None  # noqa: E731
@@ -349,12 +372,16 @@ def main():
     ap.add_argument("--episode-log-job", action="store_true", help="also time the job-wide episode log on one device: the split call at "
                                                                    "W = 1 against ssg_episode_log_append, merge_blocks alone on 1, 2 and "
                                                                    "8 stacked blocks, and the whole GAE + update with each log ahead of it")
+    ap.add_argument("--adv-norm-job", action="store_true", help="also time the job-wide per-minibatch advantage normalisation on one rank: "
+                                                                "the whole GAE + update of DataParallelPPO in that mode, in batch mode, "
+                                                                "and of NativePPO(adv_norm='minibatch'); the sums call and the rows "
+                                                                "call alone (1, 2 and 8 stacked blocks)")
     a = ap.parse_args()
     mod = _ppo()
     res = [measure(mod, int(c.split("x")[0]), int(c.split("x")[1]), a.repeats, a.only, "cuda:0", ext=a.ext, separate_value=sep, ret_filter=a.ret_filter,
                    adv_norm=a.adv_norm, perm=a.perm, timeout_bootstrap=a.timeout_bootstrap, checkpoint=a.checkpoint,
                    checkpoint_dir=a.checkpoint_dir, dp=a.dp, episode_log=a.episode_log, report=a.report, ret_filter_job=a.ret_filter_job, report_job=a.report_job,
-                   episode_log_job=a.episode_log_job)
+                   episode_log_job=a.episode_log_job, adv_norm_job=a.adv_norm_job)
            for c in a.configs.split(",") for sep in ([False, True] if a.separate_value else [False])]
     print(json.dumps({"ppo_update_timing": res}))
 

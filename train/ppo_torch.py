@@ -76,7 +76,8 @@ rank processes itself and waits for them; under a launcher's environment (``RANK
 seed and draws the whole job's uniforms, and the update goes through ship_sim_gym_amd/dp.py's ``DataParallelPPO`` (local gradients,
 an all-gather of the rows, the same apply on every rank: no parameter broadcast).  Rank 0 logs the job-wide episode statistics,
 evaluates and writes ``--save`` (the policy and the trainer); every rank prints a checksum of its parameters, and the lines agree.
-``--resume``, ``--save-every``, ``--obs-filter``, ``--norm-reward`` and ``--adv-norm minibatch`` are refused with more than one rank.
+``--resume``, ``--save-every``, ``--obs-filter``, ``--norm-reward`` and ``--adv-norm minibatch`` are refused with more than one rank
+(the last three have job-wide forms: ``--job-obs-filter``, ``--job-norm-reward``, ``--job-adv-norm minibatch``).
 ``SSG_TRAIN_SHARE_DEVICE=1`` (tests on a one-GPU box) puts every rank on device 0 over gloo.
 
 ``--job-obs-filter`` (``--mode native --update native`` only, one rank or more; not together with ``--obs-filter``): the running
@@ -103,7 +104,15 @@ ship_sim_gym_amd/report.py; ssg_ppo_report_sums / ssg_ppo_report_rows); rank 0 p
 post-update group, ``--job-report-shards`` one line per rank with its shard's samples and explained variance, and ``--job-progress
 FILE`` has rank 0 write the job's record as ``--progress`` writes a rank's (``timesteps`` counts the job's ``--envs``); each implies
 ``--job-report``.  With one rank the record is ``--report``'s bit for bit, and ``--resume`` cuts the file back likewise.
-Populations across ranks, ``--adv-norm minibatch`` across ranks and multi-rank resume stay out of scope.
+Populations across ranks and multi-rank resume stay out of scope.
+
+``--job-adv-norm minibatch`` (``--mode native --update native`` only, one rank or more; not together with ``--adv-norm minibatch``):
+PPO2's per-minibatch advantage normalisation for a job, over the minibatch of all workers' samples as PPO2 over a SubprocVecEnv takes
+it (train/stable_baselines/ppo.py:88-90,122-123).  Before the first gradient of an update every rank sums adv, adv^2 and 1 over each
+of its epochs x chunks minibatches in one pass, the ranks all-gather the blocks once, and every rank forms the same table of
+{mean, std + eps} rows in rank order (``DataParallelPPO(job_adv_norm="minibatch")``, ship_sim_gym_amd/dp.py;
+ssg_ppo_minibatch_adv_sums / ssg_ppo_set_minibatch_adv_rows); the per-minibatch loop exchanges nothing more than it did.  With one
+rank the parameters are ``--adv-norm minibatch``'s bit for bit; every rank prints the parameter checksum, one rank too.
 
 ``--job-episode-log FILE`` (``--mode native --update native`` only, one rank or more; not together with ``--episode-log``;
 ``--episode-log-capacity`` sizes its ring): the episode log of a job, over the episodes of all ranks as SubprocVecEnv + Monitor +
@@ -371,11 +380,17 @@ JOB_NORM_REWARD_REQUIREMENTS = (
     ("job_norm_reward", "--job-norm-reward", lambda a: bool(getattr(a, "job_norm_reward", None)), ("mode", "update"), False,
      "the ranks' rows are gathered between the native rollout and the device's GAE"),
 )
+# The job-wide per-minibatch advantage normalisation's row, likewise: any number of ranks; not together with the single-handle mode.
+JOB_ADV_NORM_REQUIREMENTS = (
+    ("job_adv_norm", "--job-adv-norm minibatch", lambda a: getattr(a, "job_adv_norm", "batch") == "minibatch", ("mode", "update"), False,
+     "the ranks' sums of every minibatch are gathered once per update, ahead of the device update's gradient calls"),
+)
 # (what a job-wide filter's or the job-wide episode log's row is not supported together with — the handle's own counterpart —, asked
 # after its needs: the argument, its flag, why)
 JOB_EXCLUDES = {"job_obs_filter": ("obs_filter", "--obs-filter", "one filter is bound to the env"),
                        "job_norm_reward": ("norm_reward", "--norm-reward", "one filter normalises the rewards"),
                        "job_episode_log": ("episode_log", "--episode-log", "one log records the run's episodes")}
+JOB_ADV_NORM_EXCLUDES = ("adv_norm", "--adv-norm minibatch", "a handle has one source of per-minibatch statistics")
 
 
 # The job's update report's rows, likewise: any number of ranks; not together with the rank's own report (one report per update).
@@ -390,6 +405,8 @@ JOB_REPORT_EXCLUDES = tuple((name, flag, "one report per update")  # (the flag t
 
 def excluded_with(name, a):
     """What the row `name` is on together with and is not supported with: (the argument, its flag, why), or three Nones."""
+    if name == "job_adv_norm":
+        return JOB_ADV_NORM_EXCLUDES if a.adv_norm == "minibatch" else (None, None, None)
     if name in JOB_EXCLUDES:
         other = JOB_EXCLUDES[name]
         return other if getattr(a, other[0]) else (None, None, None)
@@ -401,16 +418,17 @@ def excluded_with(name, a):
 
 
 def check_requirements(args, ranks, error=None):
-    """Walk EPISODE_LOG_REQUIREMENTS, JOB_EPISODE_LOG_REQUIREMENTS, JOB_REPORT_REQUIREMENTS, REPORT_REQUIREMENTS, JOB_OBS_FILTER_REQUIREMENTS, JOB_NORM_REWARD_REQUIREMENTS and REQUIREMENTS over the arguments `args` (a dict) of a run of `ranks` ranks.  The first row that is on and misses a need, or is
+    """Walk EPISODE_LOG_REQUIREMENTS, JOB_EPISODE_LOG_REQUIREMENTS, JOB_REPORT_REQUIREMENTS, REPORT_REQUIREMENTS, JOB_OBS_FILTER_REQUIREMENTS, JOB_NORM_REWARD_REQUIREMENTS, JOB_ADV_NORM_REQUIREMENTS and REQUIREMENTS over the arguments `args` (a dict) of a run of `ranks` ranks.  The first row that is on and misses a need, or is
     refused with more than one rank, goes to the parser's `error` with the flags in the text, or is a ValueError with train()'s names."""
     a = argparse.Namespace(**dict(args, ranks=ranks))
-    rows = EPISODE_LOG_REQUIREMENTS + JOB_EPISODE_LOG_REQUIREMENTS + JOB_REPORT_REQUIREMENTS + REPORT_REQUIREMENTS + JOB_OBS_FILTER_REQUIREMENTS + JOB_NORM_REWARD_REQUIREMENTS + REQUIREMENTS
+    rows = EPISODE_LOG_REQUIREMENTS + JOB_EPISODE_LOG_REQUIREMENTS + JOB_REPORT_REQUIREMENTS + REPORT_REQUIREMENTS + JOB_OBS_FILTER_REQUIREMENTS + JOB_NORM_REWARD_REQUIREMENTS + JOB_ADV_NORM_REQUIREMENTS + REQUIREMENTS
     for name, flag, on, needs, one_rank_only, why in rows:
         text = None
         other, other_flag, other_why = excluded_with(name, a) if on(a) else (None, None, None)
         if other and all(NEEDS[k][2](a) for k in needs):
             text = ("%s is not supported together with %s: %s" % (flag, other_flag, other_why) if error else
-                    "%s (%s): it is not supported together with %s=True: %s" % (name, flag, other, other_why))
+                    "%s (%s): it is not supported together with %s: %s" % (
+                        name, flag, "adv_norm='minibatch'" if name == "job_adv_norm" else "%s=True" % other, other_why))
         elif on(a) and not all(NEEDS[k][2](a) for k in needs):
             text = ("%s needs %s (%s)" % (flag, " ".join(NEEDS[k][0] for k in needs), why) if error else
                     "%s: it needs %s (%s; got mode=%r, update=%r)" % (name, " and ".join(NEEDS[k][1] for k in needs), why, a.mode, a.update))
@@ -425,7 +443,8 @@ def check_requirements(args, ranks, error=None):
 def check_train_arguments(a, ranks):
     """Every host-side refusal of train(**vars(a)), before the first env is built: the values, then REQUIREMENTS."""
     assert a.mode in ("eager", "graph", "pingpong", "native")
-    for name, allowed in (("perm", ("torch", "native")), ("adv_norm", ("batch", "minibatch")), ("update", ("torch", "native"))):
+    for name, allowed in (("perm", ("torch", "native")), ("adv_norm", ("batch", "minibatch")), ("job_adv_norm", ("batch", "minibatch")),
+                          ("update", ("torch", "native"))):
         if getattr(a, name) not in allowed:
             raise ValueError("%s must be %r or %r (got %r)" % ((name,) + allowed + (getattr(a, name),)))
     if a.save_every < 0 or a.eval_every < 0 or a.eval_episodes < 1:
@@ -481,9 +500,10 @@ def build_run(run, rank, world):
         sh.env.reset_tensor()
     run.policy = NativePolicy.from_actor_critic(run.net, run.shards[0].scale) if run.mode == "native" else None
     perm_seed, run.ppo = run.seed if run.perm == "native" else None, None
-    if world > 1:  # (refuses, on every rank alike, shards that would make different numbers of minibatches)
+    if world > 1 or run.job_adv_norm == "minibatch":  # (refuses, on every rank alike, shards that would make different numbers of minibatches)
         from ship_sim_gym_amd.dp import DataParallelPPO
-        run.ppo = DataParallelPPO(run.policy, run.env, plan=(run.horizon, run.minibatches), lr=run.lr, clip=run.clip, perm_seed=perm_seed)
+        run.ppo = DataParallelPPO(run.policy, run.env, plan=(run.horizon, run.minibatches), lr=run.lr, clip=run.clip, perm_seed=perm_seed,
+                                  job_adv_norm=run.job_adv_norm)
     elif run.update == "native":
         run.ppo = NativePPO(run.policy, run.env, lr=run.lr, clip=run.clip, adv_norm=run.adv_norm, perm_seed=perm_seed)
     run.job = None if world == 1 else (env_range[0], env_range[1], run.envs)
@@ -668,7 +688,8 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
           norm_reward=False, reward_clip=10.0, adv_norm="batch", perm="torch", timeout_bootstrap=False, hidden=64,
           save=None, save_every=0, save_best=None, resume=None, episode_log=None, episode_log_capacity=65536, best_window=0,
           report=False, report_kl=False, progress=None, job_obs_filter=False, job_norm_reward=False,
-          job_report=False, job_report_kl=False, job_progress=None, job_report_shards=False, job_episode_log=None, job_best_window=0):
+          job_report=False, job_report_kl=False, job_progress=None, job_report_shards=False, job_episode_log=None, job_best_window=0,
+          job_adv_norm="batch"):
     config = run_config(**dict(locals()))  # (first statement: the arguments, nothing else)
     run = argparse.Namespace(**locals())  # the run record: the arguments and the config; build_run() and the bind step add the objects
     run.report = bool(report or report_kl or progress)  # (--report-kl and --progress imply --report)
@@ -746,7 +767,7 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
         log("checkpoint after update %d saved to %s" % (state.update, save))
     if run.ppo is not None:
         run.ppo.load_into(run.net)  # the module gets the device-trained parameters (details["params"])
-    if world > 1:  # every rank prints it: the ranks hold the same bits, so the lines are the same
+    if world > 1 or job_adv_norm == "minibatch":  # every rank prints it: the ranks hold the same bits, so the lines are the same
         import hashlib
         print("parameter checksum after %d Adam steps: %s" % (
             run.ppo.step, hashlib.sha256(run.policy.params.detach().cpu().numpy().tobytes()).hexdigest()), flush=True)
@@ -838,6 +859,11 @@ def make_arg_parser():
                     help="--norm-reward for a data-parallel job, one rank or more: the running std is that of the returns of all the "
                          "job's envs; the ranks gather one row of statistics per step once per rollout and chain them alike, "
                          "bit-identically (needs --mode native --update native; not together with --norm-reward)")
+    ap.add_argument("--job-adv-norm", choices=("batch", "minibatch"), default="batch",
+                    help="--adv-norm for a data-parallel job, one rank or more: minibatch normalises the advantages of every minibatch "
+                         "by the mean / std over the whole job's minibatch (PPO2's rule over all workers' samples); the ranks gather "
+                         "one block of sums once per update and form the same statistics, bit-identically (needs --mode native --update "
+                         "native; not together with --adv-norm minibatch)")
     ap.add_argument("--job-report", action="store_true",
                     help="--report for a data-parallel job, one rank or more: the record over the experience of all ranks, from one "
                          "gathered row of sums per rank, bit-identical on every rank; rank 0 prints it (needs --mode native --update "
