@@ -21,13 +21,14 @@ import pytest
 from gpu_support import torch_cuda  # noqa: F401
 
 import event_scenes as ES
+from step_rows import EVENT_ROWS
 
 pytestmark = pytest.mark.gpu
 
-# n_beams x history x fix_collision_reward x n_goals x n_ships, thinned: one beam count from each compiled beam group and both
-# BASELINE counts, history 1 .. 3, both reward rules, n_goals 1, 5 and 6; the last row is config 4 (the DYN instantiation)
-ROWS = ((1, 2, False, 5, 1), (8, 1, True, 6, 1), (8, 3, False, 5, 1), (10, 2, True, 1, 1), (10, 3, False, 6, 1), (16, 1, False, 5, 1),
-        (16, 2, True, 5, 1), (10, 2, False, 5, 4))
+# n_beams x history x fix_collision_reward x n_goals x n_ships (tests/step_rows.py), thinned: one beam count from each compiled beam
+# group and both BASELINE counts, history 1 .. 3, both reward rules, n_goals 1, 5 and 6; the rows with n_ships = 4 are config 4 (the
+# DYN instantiation) at 6, 10, 12 and 16 beams
+ROWS = EVENT_ROWS
 LAYOUTS = (("64", False), ("128", False), ("256", False), ("64", True), ("128", True), ("256", True))
 K = ES.K
 _cache = {}

@@ -16,10 +16,13 @@ hit / miss alternates from lane to lane and from step to step (both arms of the 
 left and rudder right inside every wave in every step.  The designed patterns are asserted on the oracle's run before anything is
 compared with it.
 
-Layouts SSG_BLOCK 64 / 128 / 256, bank staged and bank_in_global; 8 and 10 beams; history 1 and 2; auto-reset on and off.  Per
-layout: a fused K = 4 trajectory launch, and four single-step (K = 1) launches of a second handle.  Reward, done and flags are the
-oracle's (the precedence table on its predicates) bit for bit, observation rows within the suite's 1e-9, and every fused slot is
-bitwise equal to the single-step launch — the pattern of test_every_workgroup_layout_against_the_oracle.
+Layouts SSG_BLOCK 64 / 128 / 256, bank staged and bank_in_global (above 12 beams there are no 256-env workgroups: the layout runs
+at the size the library folds it to); every beam count 1 .. 16 at history 1 and 2, history 3 at 1, 4, 7, 12 and 16 beams
+(tests/step_rows.py: the beam count selects how a row is written — the column tile or the pair writer, their remainders, the
+split and speculative rows); auto-reset on and off.  Per layout: a fused K = 4 trajectory launch, and four single-step (K = 1)
+launches of a second handle.  Reward, done and flags are the oracle's (the precedence table on its predicates) bit for bit,
+observation rows within the suite's 1e-9, and every fused slot is bitwise equal to the single-step launch — the pattern of
+test_every_workgroup_layout_against_the_oracle.
 """
 import math
 import os
@@ -31,6 +34,7 @@ from gpu_support import torch_cuda  # noqa: F401
 
 import event_scenes as ES
 from lidar_scenes import layouts
+from step_rows import LANE_ROWS
 
 pytestmark = pytest.mark.gpu
 
@@ -197,7 +201,7 @@ class Handle:
         return [np.stack([s[i] for s in steps]) for i in range(4)]
 
 
-@pytest.mark.parametrize("nb,hist", ((8, 2), (10, 2), (8, 1), (10, 1)), ids=lambda v: str(v))
+@pytest.mark.parametrize("nb,hist", LANE_ROWS, ids=lambda v: str(v))
 def test_lane_patterns_of_resets_goals_hits_and_thrust(torch_cuda, oracle, native, nb, hist):
     torch, O, N = torch_cuda, oracle, native
     recs = _records()
@@ -213,7 +217,8 @@ def test_lane_patterns_of_resets_goals_hits_and_thrust(torch_cuda, oracle, nativ
                 where = "n=%d beams=%d history=%d SSG_BLOCK=%s global=%d auto_reset=%d" % (n, nb, hist, blk, in_global, auto)
                 a = Handle(torch, N, nb, hist, scenes, recs, blk, in_global, auto)
                 b = Handle(torch, N, nb, hist, scenes, recs, blk, in_global, auto)
-                assert a.vec.launch_geometry()[0] == int(blk), where
+                epw = a.vec.launch_geometry()[0]
+                assert epw == int(blk) or (nb > 12 and epw < int(blk)), where  # (no 256-env workgroups above 12 beams)
                 dacts = torch.tensor(acts, dtype=torch.int32, device=a.vec.device)
                 np.testing.assert_array_equal(a.start(), ref["obs0"], err_msg=where)
                 b.start()
@@ -224,9 +229,11 @@ def test_lane_patterns_of_resets_goals_hits_and_thrust(torch_cuda, oracle, nativ
                     bad = got != want
                     assert not bad.any(), (where, name, [(k, e, scenes[e].tag) for k, e in zip(*np.nonzero(bad))][:8])
                 err = np.abs(fo - ref["obs"])
-                # (the first step's older frame: the kernel rebuilds it from the state columns the scene was written into, the
-                # oracle holds the reset's frame — the scene's own doing; from the second step on every frame is compared)
-                err[0, :, :(6 + nb) * (hist - 1)] = 0.0
+                # (the frames that predate the scene write, hist - 1 - k of them at step k: the kernel rebuilds the newest of them
+                # from the state columns the scene was written into, the oracle holds the reset's frame — the scene's own doing;
+                # every frame of a step taken after the write is compared)
+                for k in range(min(K, hist - 1)):
+                    err[k, :, :(6 + nb) * (hist - 1 - k)] = 0.0
                 assert (err <= 1e-9).all(), (where, "obs", float(err.max()), [(k, e, j) for k, e, j in zip(*np.nonzero(~(err <= 1e-9)))][:8])
                 # every fused slot: bitwise the single-step (K = 1) launch
                 for name, f, s in (("obs", fo, so), ("reward", fr, sr), ("done", fd, sd), ("flags", ff, sf)):
