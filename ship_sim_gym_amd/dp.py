@@ -219,7 +219,9 @@ class DataParallelPPO(NativePPO):
     group; the stats rows' means are the job's, since every rank holds the same rows).  ``job_report`` gives the JOB's record: every
     rank's sum row gathered once, the same record formed on every rank (ssg_ppo_report_sums / ssg_ppo_report_rows).
     job_adv_norm="minibatch": PPO2's rule over the job — the advantages of a minibatch are normalised by the statistics of the JOB's
-    minibatch, from one gather per update (the module's docstring); "batch" (the default): once per rollout, gae()'s job statistics."""
+    minibatch, from one gather per update (the module's docstring); "batch" (the default): once per rollout, gae()'s job statistics.
+    The clock of the hyper-parameter schedules (``set_timesteps``) is the JOB's — the timesteps collected over all ranks, which the
+    caller computes from the job's total env count, the same integer on every rank — so the ranks stay bit-identical with no broadcast."""
 
     def __init__(self, policy, env, group=None, plan=None, job_adv_norm="batch", **kw):
         if kw.get("adv_norm", "batch") != "batch":

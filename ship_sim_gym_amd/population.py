@@ -25,6 +25,7 @@ import random
 from fractions import Fraction
 
 from . import _native as N
+from . import hparam_schedule as HS
 from .policy import ACTIVATIONS, NativePolicy
 from .ppo import DeviceTrainer, adv_norm_mode, adv_norm_scratch, adv_norm_views, chunk_split, load_packed
 
@@ -168,7 +169,14 @@ class PopulationPPO(DeviceTrainer):
     Stable-Baselines' PPO2 does, instead of once per rollout (ssg_ppo_set_adv_norm; ``minibatch_adv_stats()``).
     ``perm_seed``: the library draws the members' minibatch permutations (ssg_pop_perm, one launch): ``update(batch, None, ...)``
     shuffles every member as ``NativePPO(perm_seed=..., member=m)`` shuffles alone, keyed by ``updates``, this object's count of
-    update() calls; ``draw_perm`` returns them in the layout the bound state makes ``update`` expect."""
+    update() calls; ``draw_perm`` returns them in the layout the bound state makes ``update`` expect.
+
+    Hyper-parameter schedules (``HparamSchedule``; not the update schedule of epochs x minibatches): each of ``lr``, ``clip`` and
+    ``ent_coef`` may be a float, an HparamSchedule, or a list of P of either.  ``self.lr`` / ``self.clip`` / ``self.ent_coef`` stay lists
+    of P floats, the CURRENT values; ``set_timesteps`` rewrites a scheduled member's entries from its own clock (members have clocks
+    of their own: under unequal slices their batches differ).  So ``ppo.lr[m] = x`` on a scheduled member lasts until the next
+    ``set_timesteps``; ``clear_schedule(name, m)`` makes the member's value a constant again.  ``exploit`` leaves schedules and clocks
+    where they are: like ``lam``, ``clip`` and ``lr`` themselves they are the scheduler's business, not the weights'."""
 
     def __init__(self, population, env, gamma=0.99, lam=0.95, clip=0.2, vf_coef=0.5, ent_coef=0.01, lr=3e-4, beta1=0.9, beta2=0.999,
                  eps=1e-8, adv_eps=1e-8, vf_clip=0.0, max_grad_norm=0.0, kl_coef=0.0, kl_target=0.0, adv_norm="batch", perm_seed=None):
@@ -188,12 +196,18 @@ class PopulationPPO(DeviceTrainer):
         env._check_population(population, "PopulationPPO")  # (the env's slices for P members, else an equal split)
         given = dict(gamma=gamma, lam=lam, clip=clip, vf_coef=vf_coef, ent_coef=ent_coef, lr=lr, beta1=beta1, beta2=beta2, eps=eps,
                      adv_eps=adv_eps, vf_clip=vf_clip, max_grad_norm=max_grad_norm, kl_target=kl_target, kl_coef=kl_coef)
+        # hyper-parameter schedules (hparam_schedule.py), per member: schedules[name][m] is member m's HparamSchedule or None (a
+        # constant); timesteps[m] its clock.  The lists of floats below then hold the schedules' values at the clocks (0 for now).
+        self.schedules, self.timesteps = {k: [None] * P for k in HS.SCHEDULABLE}, [0] * P
         for k in HPARAM_KEYS + EXT_KEYS + ("kl_coef",):
             v = given[k]
-            v = [float(x) for x in v] if isinstance(v, (list, tuple)) else [float(v)] * P
+            v = list(v) if isinstance(v, (list, tuple)) else [v] * P
             if len(v) != P:
                 raise ValueError("PopulationPPO: %s has %d entries for %d members" % (k, len(v), P))
-            setattr(self, k, v)
+            if k in HS.SCHEDULABLE:
+                pairs = [HS.split("PopulationPPO: member %d" % m, k, x) for m, x in enumerate(v)]
+                v, self.schedules[k] = [p[0] for p in pairs], [p[1] for p in pairs]
+            setattr(self, k, [float(x) for x in v])
         self.n_members, self.n_params = P, population.n_params
         dev = population.device
         self.adam_mv = torch.zeros((P, 2 * self.n_params), dtype=torch.float32, device=dev)  # per member: m, then v
@@ -229,6 +243,28 @@ class PopulationPPO(DeviceTrainer):
         return sizes[0]
 
     # ------------------------------------------------------------------------------------------------
+    def set_timesteps(self, t):
+        """Set the clocks of the hyper-parameter schedules — t: an int >= 0 for every member, or a list of P of them, member m's own
+        timesteps collected before the update that follows — and write every scheduled member's values at its clock into the
+        ``lr`` / ``clip`` / ``ent_coef`` lists.  Host only: nothing is launched.  A member without a schedule keeps its value."""
+        P, who = self.n_members, "PopulationPPO.set_timesteps"
+        ts = list(t) if isinstance(t, (list, tuple)) else [t] * P
+        if len(ts) != P:
+            raise ValueError("%s: %d clocks for %d members" % (who, len(ts), P))
+        self.timesteps = [HS.check_clock(who, x) for x in ts]
+        for name, scheds in self.schedules.items():
+            for m, sched in enumerate(scheds):
+                if sched is not None:
+                    getattr(self, name)[m] = sched.value(self.timesteps[m])
+        return self
+
+    def clear_schedule(self, name, m):
+        """Drop member m's hyper-parameter schedule of `name` ("lr", "clip" or "ent_coef"): its current value stays, as a constant."""
+        if name not in HS.SCHEDULABLE:
+            raise ValueError("PopulationPPO.clear_schedule: %r is not one of %s" % (name, ", ".join(HS.SCHEDULABLE)))
+        self.schedules[name][int(m)] = None
+        return self
+
     def hparams(self):
         """The members' hyper-parameters as a ctypes array of P ssg_ppo_hparams."""
         arr = (N.PpoHparams * self.n_members)()
@@ -643,7 +679,8 @@ class PopulationPPO(DeviceTrainer):
     def state_dict(self):
         """What the next update depends on besides the population and the batch (CPU copies; plain data only): the Adam moments
         [P, 2L], ``step``, ``member_steps``, ``updates``, ``kl_coef`` [P], every per-member hyper-parameter list (HPARAM_KEYS and
-        EXT_KEYS), ``adv_norm``, ``perm_seed`` (with ``has_perm_seed``: the state holds no None), the episode carries and ``last_K``.
+        EXT_KEYS), ``adv_norm``, ``perm_seed`` (with ``has_perm_seed``: the state holds no None), the episode carries, ``last_K``, the
+        hyper-parameter ``schedules`` ({"lr": P entries, ...}: a member's points, an empty list for a constant) and the clocks ``timesteps``.
 
         Not state: the workspace (gae() rewrites the statistics at its head before update() reads them, and a checkpoint is taken
         between an update and the next rollout), the per-minibatch scratch, and the env's slices, which belong to the layout the
@@ -656,12 +693,15 @@ class PopulationPPO(DeviceTrainer):
               "last_K": int(self._last_K)}
         for k in HPARAM_KEYS + EXT_KEYS:
             sd[k] = [float(v) for v in getattr(self, k)]
+        sd["schedules"] = {k: [HS.entry_state(s) for s in self.schedules[k]] for k in HS.SCHEDULABLE}
+        sd["timesteps"] = [int(t) for t in self.timesteps]
         return sd
 
     def load_state_dict(self, sd):
         """Become the trainer the state was taken from.  Checked first, all of it: the member count, ``adv_norm`` (the mode and its
         scratch are made at construction), every tensor's shape and dtype, every list's length.  A mismatch raises ValueError naming
-        the field with both values and leaves this object as it was."""
+        the field with both values and leaves this object as it was.  The hyper-parameter schedules and their clocks are taken over
+        like the hyper-parameters; a state without ``schedules`` and ``timesteps`` is a constant run's."""
         from .checkpoint import check_state, check_values
         who, P = "PopulationPPO.load_state_dict", self.n_members
         check_state(who, sd, [("n_members", P), ("adv_norm", self.adv_norm)],
@@ -674,6 +714,17 @@ class PopulationPPO(DeviceTrainer):
         bad += ["%s holds %r" % (k, v) for k in lists for v in sd[k] if isinstance(v, bool) or not isinstance(v, (int, float))]
         if bad:
             raise ValueError("%s: %s" % (who, "; ".join(bad)))
+        schedules, timesteps = {k: [None] * P for k in HS.SCHEDULABLE}, [0] * P
+        if "schedules" in sd or "timesteps" in sd:
+            check_values(who, sd, [("schedules", dict), ("timesteps", list)])
+            check_values(who + ": schedules", sd["schedules"], [(k, list) for k in HS.SCHEDULABLE])
+            for k in HS.SCHEDULABLE + ("timesteps",):
+                n = len(sd[k] if k == "timesteps" else sd["schedules"][k])
+                if n != P:
+                    raise ValueError("%s: %s lists %d entries in the state, this object has %d members" % (who, k, n, P))
+            schedules = {k: [HS.entry_from_state("%s: member %d" % (who, m), k, e) for m, e in enumerate(sd["schedules"][k])]
+                         for k in HS.SCHEDULABLE}
+            timesteps = [HS.check_clock(who, t) for t in sd["timesteps"]]
         for name in ("adam_mv", "kl_coef", "carry_return", "carry_length"):
             getattr(self, name).copy_(sd[name])
         self.step, self.updates, self._last_K = int(sd["step"]), int(sd["updates"]), int(sd["last_K"])
@@ -681,6 +732,7 @@ class PopulationPPO(DeviceTrainer):
         self.perm_seed = int(sd["perm_seed"]) if sd["has_perm_seed"] else None
         for k in HPARAM_KEYS + EXT_KEYS:
             setattr(self, k, [float(v) for v in sd[k]])
+        self.schedules, self.timesteps = schedules, timesteps
         return self
 
 

@@ -37,10 +37,16 @@ ship_sim_gym_amd/report.py holds the record's fields, the numpy restatement and 
 the experience of every rank of a data-parallel job: ``report_row`` reduces this shard to one f64 sum row (ssg_ppo_report_sums), the
 rows are all-gathered once, and ``report_rows`` forms the record from them alike on every rank (ssg_ppo_report_rows); without a process
 group it is ``report`` bit for bit.
+
+``lr``, ``clip`` and ``ent_coef`` each take a float or a hyper-parameter schedule (``HparamSchedule``, ship_sim_gym_amd/hparam_schedule.py:
+PPO2's ``learning_rate(frac)`` / ``cliprange(frac)``, RLlib's ``lr_schedule`` / ``entropy_coeff_schedule``).  ``set_timesteps(t)``, called
+once before an update, writes the schedules' values at t into ``hp``, on the host; a scheduled run is bit for bit the run whose ``hp``
+fields were set by hand.  (The population's *update schedule* — epochs x minibatches per member — is another thing.)
 """
 import ctypes as C
 
 from . import _native as N
+from . import hparam_schedule as HS
 
 
 def _torch():
@@ -281,6 +287,17 @@ def load_packed(row, net, mismatch):
     return net
 
 
+def _schedules_from_state(who, sd):
+    """(schedules, timesteps) of a NativePPO state: checked, nothing taken over yet; both keys missing: no schedules, clock 0."""
+    from .checkpoint import check_values
+    if "schedules" not in sd and "timesteps" not in sd:
+        return {k: None for k in HS.SCHEDULABLE}, 0
+    check_values(who, sd, [("schedules", dict), ("timesteps", int)])
+    check_values(who + ": schedules", sd["schedules"], [(k, list) for k in HS.SCHEDULABLE])
+    return ({k: HS.entry_from_state(who, k, sd["schedules"][k]) for k in HS.SCHEDULABLE},
+            HS.check_clock(who, sd["timesteps"]))
+
+
 class DeviceTrainer(object):
     """What NativePPO and PopulationPPO share: ``workspace`` on ``_device``, its growth and the current stream."""
 
@@ -317,6 +334,11 @@ class NativePPO(DeviceTrainer):
         self._adv_scratch = adv_norm_scratch(1, policy.device) if self._adv_mode == N.ADV_NORM_MINIBATCH else None
         if env.states_history != policy.obs_dim:
             raise ValueError("NativePPO: the env's observation width %d differs from the policy's obs_dim %d" % (env.states_history, policy.obs_dim))
+        # hyper-parameter schedules (hparam_schedule.py): lr, clip and ent_coef may each be an HparamSchedule; hp then holds its value
+        # at `timesteps`, the clock set_timesteps() sets (0 until it is called).  None: a constant
+        (lr, s_lr), (clip, s_clip), (ent_coef, s_ent) = (HS.split("NativePPO", name, given) for name, given in
+                                                         (("lr", lr), ("clip", clip), ("ent_coef", ent_coef)))
+        self.schedules, self.timesteps = {"lr": s_lr, "clip": s_clip, "ent_coef": s_ent}, 0
         hp = N.PpoHparams()
         hp.struct_size = C.sizeof(N.PpoHparams)
         hp.gamma, hp.lam, hp.clip, hp.vf_coef, hp.ent_coef = 0.99, 0.95, float(clip), float(vf_coef), float(ent_coef)
@@ -333,6 +355,16 @@ class NativePPO(DeviceTrainer):
         self.force_ext = False  # True: the _ext entry points even with every term off (they then compute what the plain ones do)
 
     # ------------------------------------------------------------------------------------------------
+    def set_timesteps(self, t):
+        """Set the clock of the hyper-parameter schedules to t (an int >= 0: the timesteps collected before the update that follows) and
+        write every schedule's value at t into ``hp.lr`` / ``hp.clip`` / ``hp.ent_coef``, the fields every update call passes.  Host
+        only: nothing is launched and the device is not touched.  With no schedule it only records t."""
+        self.timesteps = HS.check_clock("NativePPO.set_timesteps", t)
+        for name, sched in self.schedules.items():
+            if sched is not None:
+                setattr(self.hp, name, sched.value(t))
+        return self
+
     def _ws(self, n_samples, max_minibatch):
         """The workspace, grown to serve n_samples and minibatches of max_minibatch (its first 16 bytes — the advantage
         statistics ssg_ppo_gae left — are kept when it grows)."""
@@ -672,7 +704,8 @@ class NativePPO(DeviceTrainer):
     def state_dict(self):
         """What the next update() depends on besides the policy and the batch (CPU copies; plain data only): the Adam moments, ``step``,
         ``updates``, the KL coefficient and whether the KL term is on, every field of ``hp``, the extended terms' settings, ``adv_norm``,
-        ``perm_seed`` (with ``has_perm_seed``: the state holds no None) and ``member``.
+        ``perm_seed`` (with ``has_perm_seed``: the state holds no None), ``member``, the hyper-parameter ``schedules`` ({"lr": points,
+        "clip": points, "ent_coef": points}, an empty list for a constant) and their clock ``timesteps``.
 
         The workspace is NOT state.  A checkpoint is taken between an update() and the next rollout; the only thing the workspace
         carries from one call to another is the advantage statistics gae() writes into its head for the update() that follows, and the
@@ -682,13 +715,16 @@ class NativePPO(DeviceTrainer):
                 "kl_coef": self.kl_coef.detach().cpu().clone(), "kl_on": bool(self._kl_on),
                 "hp": {k: float(getattr(self.hp, k)) for k in HP_FIELDS},
                 "vf_clip": self.vf_clip, "max_grad_norm": self.max_grad_norm, "kl_target": self.kl_target, "adv_norm": self.adv_norm,
-                "has_perm_seed": self.perm_seed is not None, "perm_seed": int(self.perm_seed or 0), "member": int(self.member)}
+                "has_perm_seed": self.perm_seed is not None, "perm_seed": int(self.perm_seed or 0), "member": int(self.member),
+                "schedules": {k: HS.entry_state(self.schedules[k]) for k in HS.SCHEDULABLE}, "timesteps": int(self.timesteps)}
 
     def load_state_dict(self, sd):
         """Become the trainer the state was taken from.  Checked first, all of it: the moments' and the coefficient's shape and dtype,
         ``adv_norm`` (the mode and its scratch are made at construction: it must be the state's), the types of everything else.  A
         mismatch raises ValueError naming the field with both values and leaves this object as it was.  Then the tensors are copied in
-        place and the counters and settings taken over."""
+        place and the counters and settings taken over — the hyper-parameter schedules and their clock among them, like the other
+        hyper-parameters (``hp`` is the state's, which holds the schedules' values at that clock).  A state without ``schedules`` and
+        ``timesteps`` (a file from before there were any) is a constant run's."""
         from .checkpoint import check_state, check_values
         who = "NativePPO.load_state_dict"
         check_state(who, sd, [("adv_norm", self.adv_norm)], [("adam_mv", self.adam_mv), ("kl_coef", self.kl_coef)])
@@ -696,6 +732,7 @@ class NativePPO(DeviceTrainer):
         check_values(who, sd, [("step", int), ("updates", int), ("kl_on", bool), ("hp", dict), ("vf_clip", num), ("max_grad_norm", num),
                                ("kl_target", num), ("has_perm_seed", bool), ("perm_seed", int), ("member", int)])
         check_values(who + ": hp", sd["hp"], [(k, num) for k in HP_FIELDS])
+        schedules, timesteps = _schedules_from_state(who, sd)
         self.adam_mv.copy_(sd["adam_mv"])
         self.kl_coef.copy_(sd["kl_coef"])
         self.step, self.updates, self._kl_on = int(sd["step"]), int(sd["updates"]), bool(sd["kl_on"])
@@ -704,4 +741,5 @@ class NativePPO(DeviceTrainer):
         self.vf_clip, self.max_grad_norm, self.kl_target = float(sd["vf_clip"]), float(sd["max_grad_norm"]), float(sd["kl_target"])
         self.perm_seed = int(sd["perm_seed"]) if sd["has_perm_seed"] else None
         self.member = int(sd["member"])
+        self.schedules, self.timesteps = schedules, timesteps
         return self

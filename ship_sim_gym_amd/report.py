@@ -13,7 +13,10 @@ every rank reduces its shard to one sum row (ssg_ppo_report_sums: the walk's nin
 and every rank forms the same record from the same rows in rank order (ssg_ppo_report_rows).  ``NativePPO.job_report`` does that;
 ``sums_reference`` / ``rows_reference`` restate the two calls, and one row gives ``report_reference``'s record bit for bit.
 
-Out of scope: schedules of lr / clip (the columns are there for when they come), the episode log or populations across ranks, the
+The ``lr`` and ``clip`` entries of a record are the trainer's current values: under a hyper-parameter schedule
+(ship_sim_gym_amd/hparam_schedule.py) they vary from update to update, and so do ``ProgressWriter``'s two columns.
+
+Out of scope: the episode log or populations across ranks, the
 entropy or exact KL of the post-update policy over the whole batch (both need exp), a TensorBoard event writer.
 """
 import ctypes as C

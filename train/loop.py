@@ -142,6 +142,18 @@ def add_report_flags(ap):
                     help="write the report of every update to FILE as CSV, one row per policy (Stable-Baselines' progress.csv); implies --report")
 
 
+def add_hparam_schedule_flags(ap, starts, span):
+    """The flags both command lines share for the hyper-parameter schedules (ship_sim_gym_amd/hparam_schedule.py); starts / span: what
+    a "linear:" spec starts from and spans by default, in the command line's words."""
+    for flag, what in (("--lr-schedule", "learning rate"), ("--clip-schedule", "clip range"), ("--ent-schedule", "entropy coefficient")):
+        ap.add_argument(flag, default=None, metavar="SPEC",
+                        help="a hyper-parameter schedule of the %s, piecewise linear in the timesteps collected and evaluated once per "
+                             "update: linear:STOP (from %s down to STOP over --total-timesteps) or absolute points T0:V0,T1:V1,... "
+                             "(held at the last value afterwards); default: a constant" % (what, starts))
+    ap.add_argument("--total-timesteps", type=int, default=None, metavar="T",
+                    help="the span of a linear: spec (default: %s, the run's own length); not a stop criterion" % span)
+
+
 def open_progress(path, resume=False):
     """The ProgressWriter of a run that asks for one, else None.  A resumed run keeps the file and cuts it back to the checkpoint's update."""
     if not path:

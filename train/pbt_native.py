@@ -9,6 +9,7 @@ line changed and needs ray; this one needs only the library.
     python train/pbt_native.py --members 3 --epochs 1,2,4 --minibatches 4,4,8 --no-pbt   # a sweep over schedules
     python train/pbt_native.py --members 4 --envs 256 --mutate-batch --mutate-schedule   # train_batch_size per member too (pbt.py:42)
     python train/pbt_native.py --members 3 --batch-shares 1,2,4 --no-pbt                 # a sweep over batch sizes
+    python train/pbt_native.py --lrs 1e-3,1e-4,1e-5 --no-pbt --lr-schedule linear:0      # that sweep with its linear decay to 0 (:111-119)
 
 One ShipVecEnv of members x envs-per-member envs; member m owns the contiguous slice [m*n, (m+1)*n).  Every update is one
 ``rollout_population`` (one policy launch per step for the whole population), then ``PopulationPPO.gae`` and ``.update`` (two launches
@@ -68,6 +69,16 @@ vf_explained_var, policy_loss, vf_loss, entropy, kl) — from two launches for t
 approxkl, the clip fraction over its whole batch under its own clip) for one more ssg_pop_dist launch; --progress FILE writes the
 records as CSV, one row per member per update, and with --resume cuts the file back to the checkpoint's update first.  The records are
 taken before a perturbation that is due.  Off by default; the three may change between a run and its resumption.
+
+--lr-schedule SPEC, --clip-schedule SPEC, --ent-schedule SPEC (default: constants): hyper-parameter schedules of every member's learning
+rate, clip range and entropy coefficient (ship_sim_gym_amd/hparam_schedule.py; not the update schedule of --mutate-schedule), piecewise
+linear in the member's own timesteps.  SPEC is linear:STOP — from the member's OWN constant (its --lrs entry, clip 0.2, entropy
+coefficient 0.01) down to STOP over --total-timesteps T, by default the member's own run, --updates x --horizon x its envs — or absolute
+points T0:V0,T1:V1,..., the same for every member.  Member m's clock before update u (1, 2, ...) is (u - 1) x horizon x n_m, the samples
+it has collected.  --lr-schedule and --clip-schedule need --no-pbt: PBT mutates those two, and a schedule would overwrite the mutation
+at the next update (as RLlib's lr_schedule overrides a mutated lr); --ent-schedule goes with PBT.  None of the three goes with
+--mutate-batch: a member's clock would depend on the history of re-slices.  The specs are part of the run's configuration, and a
+resumed trainer's schedules are the file's.
 
 --save FILE writes a checkpoint at the end (ship_sim_gym_amd/checkpoint.py; the reference's checkpoint_at_end, train/rllib/pbt.py:53),
 --save-every U also after every U updates (its checkpoint_freq, :54), --save-best FILE after every update in which the best member's
@@ -187,6 +198,7 @@ def make_arg_parser():
                          "(the whole population; the file names the member)")
     loop.add_episode_log_flags(ap)
     loop.add_report_flags(ap)
+    loop.add_hparam_schedule_flags(ap, "each member's own constant", "--updates x --horizon x the member's envs")
     ap.add_argument("--resume", default=None, metavar="FILE",
                     help="continue the run a checkpoint was saved from, bit for bit: repeat the original command line; --updates stays "
                          "the TOTAL and may be raised")
@@ -241,6 +253,10 @@ def parse_args(argv=None):
     if a.kl_coeff < 0 or a.kl_target < 0 or a.vf_clip < 0 or a.max_grad_norm < 0:
         ap.error("--kl-coeff, --kl-target, --vf-clip and --max-grad-norm must be >= 0")
     loop.check_flag_values(a, ap.error)
+    try:
+        check_hparam_schedules(a)
+    except ValueError as ex:
+        ap.error(str(ex))
     return a
 
 
@@ -275,6 +291,45 @@ class LoopState(object):
         self.exploits, self.reslices = events_from_plain(sd["exploits"]), [(r[0], r[1]) for r in sd["reslices"]]
 
 
+HPARAM_SCHEDULE_FLAGS = (("lr", "lr_schedule", "--lr-schedule"), ("clip", "clip_schedule", "--clip-schedule"),
+                         ("ent_coef", "ent_schedule", "--ent-schedule"))
+ENT_COEF = 0.01  # PopulationPPO's default entropy coefficient
+
+
+def check_hparam_schedules(a):
+    """The host-side refusals of the hyper-parameter schedule flags (a: train()'s arguments or the parsed command line's): what PBT
+    would overwrite, what re-slicing would make history-dependent, a bad span, a malformed spec or a clip <= 0 (parsed here from the
+    common starts; a learning rate's start, the member's own, does not decide whether its spec is well-formed)."""
+    from ship_sim_gym_amd.hparam_schedule import HparamSchedule, check_schedulable
+    on = [(name, arg, flag) for name, arg, flag in HPARAM_SCHEDULE_FLAGS if getattr(a, arg, None) is not None]
+    for name, arg, flag in on:
+        if a.pbt and name in ("lr", "clip"):
+            raise ValueError("%s (%s) needs --no-pbt (pbt=False): PBT mutates %s, and the schedule would overwrite the mutation at the "
+                             "next update" % (arg, flag, name))
+        if a.mutate_batch:
+            raise ValueError("%s (%s) is not supported together with --mutate-batch (mutate_batch=True): a member's clock would depend on "
+                             "the history of re-slices" % (arg, flag))
+    total = getattr(a, "total_timesteps", None)
+    if total is not None and (isinstance(total, bool) or not isinstance(total, int) or total < 1):
+        raise ValueError("total_timesteps (--total-timesteps) must be an int >= 1 (got %r)" % (total,))
+    start = {"lr": INITIAL["lr"], "clip": INITIAL["clip_param"], "ent_coef": ENT_COEF}
+    for name, arg, flag in on:
+        check_schedulable("%s (%s)" % (arg, flag), name, HparamSchedule.parse(getattr(a, arg), start[name], 1 if total is None else total))
+
+
+def member_hparam_schedules(run, sizes, lrs):
+    """Every member's lr / clip / ent_coef as PopulationPPO takes them: lists of P floats, or of P HparamSchedules where a flag is on —
+    a "linear:" spec from the member's own constant over total_timesteps, by default its own run of updates * horizon * sizes[m]."""
+    from ship_sim_gym_amd.hparam_schedule import HparamSchedule
+    out = {"lr": list(lrs), "clip": [INITIAL["clip_param"]] * run.P, "ent_coef": [ENT_COEF] * run.P}
+    for name, arg, _ in HPARAM_SCHEDULE_FLAGS:
+        spec = getattr(run, arg)
+        if spec is not None:
+            spans = [run.updates * run.horizon * n if run.total_timesteps is None else run.total_timesteps for n in sizes]
+            out[name] = [HparamSchedule.parse(spec, out[name][m], spans[m]) for m in range(run.P)]
+    return out
+
+
 def plan(run):
     """The host side of a run (run: train()'s arguments), before the first env is built: refuse what does not fit, then add what follows
     from the arguments: P members on n_total envs, sliced or n each, the schedule per member or common, the permutation rows drawn."""
@@ -284,6 +339,8 @@ def plan(run):
         raise ValueError("train: episode_log_capacity must be >= 1")
     if run.perm not in ("torch", "native"):
         raise ValueError("train: perm must be 'torch' or 'native' (got %r)" % (run.perm,))
+    check_hparam_schedules(run)
+    run.scheduled = any(getattr(run, arg, None) is not None for _, arg, _ in HPARAM_SCHEDULE_FLAGS)
     P = run.P = int(run.members)
     run.n_total = int(run.envs) if run.envs is not None else P * int(run.envs_per_member)
     run.sliced = bool(run.mutate_batch) or run.batch_shares is not None
@@ -372,7 +429,8 @@ def build(run, log):
         log("schedule: num_sgd_iter %s  sgd_minibatch_size %s" % (state.iters, state.sizes))
     elif run.per_member:
         set_schedule(state, run.max_epochs, iters=run.iters0, counts=run.counts0)
-    run.ppo = PopulationPPO(run.pop, run.env, lam=INITIAL["lambda"], clip=INITIAL["clip_param"], lr=list(run.lrs) if run.lrs is not None else INITIAL["lr"],
+    hparams = member_hparam_schedules(run, state.slices if run.sliced else [run.n] * P, run.lrs if run.lrs is not None else [INITIAL["lr"]] * P)
+    run.ppo = PopulationPPO(run.pop, run.env, lam=INITIAL["lambda"], clip=hparams["clip"], lr=hparams["lr"], ent_coef=hparams["ent_coef"],
                             vf_clip=run.vf_clip, max_grad_norm=run.max_grad_norm, kl_coef=run.kl_coeff, kl_target=run.kl_target if run.kl_coeff > 0 else 0.0,
                             adv_norm=run.adv_norm, perm_seed=run.seed if run.native_perm else None)
     # per-member statistics: a member's rows are its slice, whatever the slices currently are
@@ -508,7 +566,8 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
           separate_value=False, mutate_schedule=False, max_epochs=30, eval_every=0, eval_episodes=1, envs=None, mutate_batch=False,
           batch_shares=None, quantum=None, obs_filter=False, norm_reward=False, reward_clip=10.0, adv_norm="batch", perm="torch",
           timeout_bootstrap=False, hidden=64, env_kw=None, save=None, save_every=0, save_best=None, resume=None, episode_log=None,
-          episode_log_capacity=65536, report=False, report_kl=False, progress=None):
+          episode_log_capacity=65536, report=False, report_kl=False, progress=None, lr_schedule=None, clip_schedule=None, ent_schedule=None,
+          total_timesteps=None):
     config = run_config(**dict(locals()))  # (first statement: the arguments, nothing else)
     run = argparse.Namespace(**locals())  # the run record: the arguments and the config; plan() and build() add to it
     run.report = bool(report or report_kl or progress)  # (--report-kl and --progress imply --report)
@@ -525,7 +584,15 @@ def train(members=16, envs_per_member=512, updates=40, horizon=32, perturb_every
             run.progress_writer.cut_back(state.update)  # (the rows of updates the checkpoint has not seen are written again)
         log("resumed from %s: %d updates done, continuing at update %d of %d" % (resume, state.update, state.update + 1, updates))
     out, evals = None, []
+    for name in sorted(run.ppo.schedules) if run.scheduled else ():  # (once: a resumed trainer's schedules are the file's)
+        log("hyper-parameter schedules of %s: %s" % (name, ["constant" if s is None else s.state() for s in run.ppo.schedules[name]]))
     for u in range(state.update + 1, updates + 1):
+        # the hyper-parameter schedules' clocks: the samples each member has collected before this update (without --mutate-batch the
+        # slices never change, so a clock is a function of u alone)
+        run.ppo.set_timesteps([(u - 1) * s for s in state.member_samples])
+        if run.scheduled:
+            log("update %d  lr %s  clip %s  entropy coefficient %s" % (u, *(" ".join("%d:%.6g" % (m, v) for m, v in enumerate(getattr(run.ppo, k)))
+                                                                            for k in ("lr", "clip", "ent_coef"))))
         uniforms = torch.rand((horizon, run.n_total), generator=run.gen, device=run.dev)
         batch = run.env.rollout_population(run.pop, horizon, uniforms=uniforms, out=out)
         out = {k: v for k, v in batch.items() if k not in ("adv", "ret", "logp_all", "rew_norm", "rew_denom")}

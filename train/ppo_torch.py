@@ -10,6 +10,7 @@ leave the GPU; the policy is a small MLP in fp32.
                               [--save FILE [--save-every U]] [--save-best FILE] [--resume FILE] [--gpus W]
                               [--report [--report-kl]] [--progress FILE] [--job-obs-filter] [--job-norm-reward [--reward-clip C]]
                               [--job-report [--job-report-kl] [--job-report-shards]] [--job-progress FILE]
+                              [--lr-schedule SPEC] [--clip-schedule SPEC] [--ent-schedule SPEC] [--total-timesteps T]
 
 Four ways to run the rollout loop (the reference's `model.learn` -> runner.run(): one `env.step(actions)` per policy
 forward, train/stable_baselines/ppo.py:84-100,122-123) — same arithmetic, same results bit for bit:
@@ -124,6 +125,18 @@ alike on every rank without a broadcast; rank 0 alone attaches the MonitorWriter
 the job's ``--envs``).  ``--save`` holds rank 0's ``episode_log`` section (the job's ring, rank 0's carries); with one rank the file is
 ``--episode-log``'s in every column but ``t`` and ``--resume`` continues from the section.  ``--episode-log`` and ``--best-window`` stay
 refused with more than one rank.
+
+``--lr-schedule SPEC``, ``--clip-schedule SPEC``, ``--ent-schedule SPEC`` (every ``--mode``, either ``--update``, any number of ranks;
+default: constants): hyper-parameter schedules of the learning rate, the clip range and the entropy coefficient, piecewise linear in
+the timesteps collected (ship_sim_gym_amd/hparam_schedule.py).  SPEC is ``linear:STOP`` — from ``--lr`` / ``--clip`` / the entropy
+coefficient's constant 0.01 down to STOP over ``--total-timesteps T``, whose default is ``--updates`` x ``--envs`` x ``--horizon``, the run's
+own length: PPO2's rule, so ``--lr-schedule linear:0`` is train/stable_baselines/ppo.py:111-119's ``make_lr_func(s, 0)`` — or absolute
+points ``T0:V0,T1:V1,...`` as RLlib writes them (``--lr-schedule 0:1e-3,5000000:1e-4,10000000:1e-5`` is train/rllib/ppo.py:39's).  Before
+update u (0-based) the clock is set to u x envs x horizon, envs being the job's total: the timesteps collected before this update's
+rollout, PPO2's ``frac = 1 - (update - 1) / nupdates`` in other words; no step parity with RLlib's own timestep counter is claimed.  Both
+update paths apply the same values, and an update's log line names them.  The specs are part of a run's configuration: ``--resume`` with
+another spec is refused, and the resumed trainer's schedule is the file's, so raising ``--updates`` past a defaulted span continues at the
+stop value instead of stretching the decay.  ``--total-timesteps`` is a span, not a stop criterion: ``--updates`` stays the only one.
 
 The sampling noise of a whole rollout is drawn in one call before it (uniforms [horizon, envs], inverse-CDF sampling inside
 the step), so a captured step holds no random-number generator state and replays exactly what the eager loop computes.
@@ -451,7 +464,30 @@ def check_train_arguments(a, ranks):
         raise ValueError("save_every and eval_every must be >= 0 and eval_episodes >= 1")
     if a.episode_log_capacity < 1 or a.best_window < 0 or getattr(a, "job_best_window", 0) < 0:
         raise ValueError("episode_log_capacity must be >= 1, best_window and job_best_window >= 0")
+    make_hparam_schedules(a)  # (a malformed spec is refused here)
     check_requirements(vars(a), ranks)
+
+
+ENT_COEF = 0.01  # the entropy coefficient's constant: torch_update's and NativePPO's default
+HPARAM_SCHEDULE_FLAGS = (("lr", "lr_schedule", "--lr-schedule"), ("clip", "clip_schedule", "--clip-schedule"),
+                         ("ent_coef", "ent_schedule", "--ent-schedule"))
+
+
+def make_hparam_schedules(a):
+    """(the hyper-parameter schedules of a run, {"lr" | "clip" | "ent_coef": HparamSchedule or None}, their span) from its arguments
+    (train()'s, or the parsed command line's): a "linear:" spec starts from lr / clip / ENT_COEF and spans total_timesteps, by default the
+    run's own length updates * envs * horizon (envs: the job's total).  ValueError for a malformed spec, a span < 1, a clip <= 0."""
+    from ship_sim_gym_amd.hparam_schedule import HparamSchedule, check_schedulable
+    total = getattr(a, "total_timesteps", None)
+    if total is not None and (isinstance(total, bool) or not isinstance(total, int) or total < 1):
+        raise ValueError("total_timesteps (--total-timesteps) must be an int >= 1 (got %r)" % (total,))
+    span = int(a.updates) * int(a.envs) * int(a.horizon) if total is None else total
+    start = {"lr": a.lr, "clip": a.clip, "ent_coef": ENT_COEF}
+    out = {}
+    for name, arg, flag in HPARAM_SCHEDULE_FLAGS:
+        spec = getattr(a, arg, None)
+        out[name] = None if spec is None else check_schedulable("%s (%s)" % (arg, flag), name, HparamSchedule.parse(spec, start[name], span))
+    return out, span
 
 
 class LoopState(object):
@@ -500,12 +536,15 @@ def build_run(run, rank, world):
         sh.env.reset_tensor()
     run.policy = NativePolicy.from_actor_critic(run.net, run.shards[0].scale) if run.mode == "native" else None
     perm_seed, run.ppo = run.seed if run.perm == "native" else None, None
+    run.schedules, run.span = make_hparam_schedules(run)
+    run.now = {"lr": run.lr, "clip": run.clip, "ent_coef": ENT_COEF}  # the current values (the torch update reads them)
+    hparams = {k: run.schedules[k] if run.schedules[k] is not None else run.now[k] for k in run.now}  # a float, or its schedule
     if world > 1 or run.job_adv_norm == "minibatch":  # (refuses, on every rank alike, shards that would make different numbers of minibatches)
         from ship_sim_gym_amd.dp import DataParallelPPO
-        run.ppo = DataParallelPPO(run.policy, run.env, plan=(run.horizon, run.minibatches), lr=run.lr, clip=run.clip, perm_seed=perm_seed,
-                                  job_adv_norm=run.job_adv_norm)
+        run.ppo = DataParallelPPO(run.policy, run.env, plan=(run.horizon, run.minibatches), perm_seed=perm_seed,
+                                  job_adv_norm=run.job_adv_norm, **hparams)
     elif run.update == "native":
-        run.ppo = NativePPO(run.policy, run.env, lr=run.lr, clip=run.clip, adv_norm=run.adv_norm, perm_seed=perm_seed)
+        run.ppo = NativePPO(run.policy, run.env, adv_norm=run.adv_norm, perm_seed=perm_seed, **hparams)
     run.job = None if world == 1 else (env_range[0], env_range[1], run.envs)
     run.n_local = run.envs if world == 1 else env_range[1] - env_range[0]
 
@@ -607,7 +646,7 @@ def job_report_update(run, u, nb, st_upd, log):
         run.job_progress_writer.write(u, (u + 1) * run.envs * run.horizon, rec, rec["lr"], rec["clip"])
 
 
-def torch_update(net, opt, b, last_val, epochs, minibatches, gen, gamma=0.99, lam=0.95, clip=0.2, adv_norm="batch"):
+def torch_update(net, opt, b, last_val, epochs, minibatches, gen, gamma=0.99, lam=0.95, clip=0.2, adv_norm="batch", ent_coef=ENT_COEF):
     """The eager update on a rollout b (obs [horizon, envs, D]; act int64, the rest float32 [horizon, envs]) and the values after its
     last step, on whatever device they are: GAE, then epochs x minibatches of loss, backward, Adam.  One randperm from `gen` per epoch."""
     horizon, envs, D = b["obs"].shape
@@ -637,7 +676,7 @@ def torch_update(net, opt, b, last_val, epochs, minibatches, gen, gamma=0.99, la
                 mb_std = mb_adv.std() if mb_adv.numel() > 1 else mb_adv.new_zeros(())  # (one sample: a std of 0, not NaN)
                 mb_adv = (mb_adv - mb_adv.mean()) / (mb_std + 1e-8)
             pg = -torch.min(ratio * mb_adv, torch.clamp(ratio, 1 - clip, 1 + clip) * mb_adv).mean()
-            loss = pg + 0.5 * (val - b_ret[mb]).pow(2).mean() - 0.01 * dist.entropy().mean()
+            loss = pg + 0.5 * (val - b_ret[mb]).pow(2).mean() - ent_coef * dist.entropy().mean()
             opt.zero_grad(); loss.backward(); opt.step()
 
 
@@ -646,9 +685,38 @@ def eager_update(run, b, last_val):
     if last_val is None:
         with torch.no_grad():
             last_val = torch.cat([run.net(normalise(sh.env.obs, sh.scale))[1] for sh in run.shards])
-    torch_update(run.net, run.opt, b, last_val, run.epochs, run.minibatches, run.gen, run.gamma, run.lam, run.clip, run.adv_norm)
+    for group in run.opt.param_groups:  # (the schedules' current values, set_hparam_clock's; without schedules the constants)
+        group["lr"] = run.now["lr"]
+    torch_update(run.net, run.opt, b, last_val, run.epochs, run.minibatches, run.gen, run.gamma, run.lam, run.now["clip"], run.adv_norm,
+                 ent_coef=run.now["ent_coef"])
     if run.policy is not None:
         run.policy.refresh()
+
+
+def set_hparam_clock(run, u, log):
+    """Before update u (0-based): the hyper-parameter schedules' clock is the timesteps collected so far, u * envs * horizon over the
+    job's envs (the same integer on every rank).  The device trainer evaluates its own schedules (a resumed one's are the file's); the
+    torch update reads run.now.  With a schedule on, one log line names the current values."""
+    t = u * run.envs * run.horizon
+    if run.ppo is not None:
+        run.ppo.set_timesteps(t)
+        run.now = {k: float(getattr(run.ppo.hp, k)) for k in run.now}
+        on = any(s is not None for s in run.ppo.schedules.values())
+    else:
+        run.now = {k: (s.value(t) if s is not None else run.now[k]) for k, s in run.schedules.items()}
+        on = any(s is not None for s in run.schedules.values())
+    if on:
+        log("update %3d  hyper-parameter schedules at %d timesteps: lr %.6g  clip %.6g  entropy coefficient %.6g" % (
+            u, t, run.now["lr"], run.now["clip"], run.now["ent_coef"]))
+
+
+def log_hparam_schedules(run, log):
+    """Once per run: the schedules in use and the span a "linear:" spec was given (a resumed device trainer's are the file's)."""
+    scheds = run.ppo.schedules if run.ppo is not None else run.schedules
+    for name, sched in sorted(scheds.items()):
+        if sched is not None:
+            log("hyper-parameter schedule of %s: points %s (timesteps, value); this run's span for a linear spec: %d timesteps" % (
+                name, sched.state(), run.span))
 
 
 def account(run, state, u, b, log):
@@ -689,7 +757,7 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
           save=None, save_every=0, save_best=None, resume=None, episode_log=None, episode_log_capacity=65536, best_window=0,
           report=False, report_kl=False, progress=None, job_obs_filter=False, job_norm_reward=False,
           job_report=False, job_report_kl=False, job_progress=None, job_report_shards=False, job_episode_log=None, job_best_window=0,
-          job_adv_norm="batch"):
+          job_adv_norm="batch", lr_schedule=None, clip_schedule=None, ent_schedule=None, total_timesteps=None):
     config = run_config(**dict(locals()))  # (first statement: the arguments, nothing else)
     run = argparse.Namespace(**locals())  # the run record: the arguments and the config; build_run() and the bind step add the objects
     run.report = bool(report or report_kl or progress)  # (--report-kl and --progress imply --report)
@@ -727,7 +795,9 @@ def train(envs=4096, updates=20, horizon=64, epochs=2, minibatches=4, lr=3e-4, g
                 writer.cut_back(state.update)  # (the rows of updates the checkpoint has not seen are written again)
         log("resumed from %s: %d updates done, continuing at update %d of %d" % (resume, state.update + 1, state.update + 1, updates))
     start = state.update + 1
+    log_hparam_schedules(run, log)
     for u in range(start, updates):
+        set_hparam_clock(run, u, log)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         b = rollout(run.shards, horizon, mode, run.gen, run.policy, job=run.job)
@@ -874,6 +944,9 @@ def make_arg_parser():
                     help="rank 0 writes the job's record of every update to FILE as CSV (--progress's format); implies --job-report")
     ap.add_argument("--job-report-shards", action="store_true",
                     help="also print one line per rank: its shard's samples and explained variance; implies --job-report")
+    ap.add_argument("--lr", type=float, default=3e-4, help="Adam's learning rate (either --update); the start of --lr-schedule linear:STOP")
+    ap.add_argument("--clip", type=float, default=0.2, help="the PPO clip range (either --update); the start of --clip-schedule linear:STOP")
+    loop.add_hparam_schedule_flags(ap, "--lr / --clip / the entropy coefficient's 0.01", "--updates x --envs x --horizon")
     ap.add_argument("--resume", default=None, metavar="FILE",
                     help="continue the run a checkpoint was saved from, bit for bit (needs --mode native --update native): repeat the "
                          "original command line; --updates stays the TOTAL and may be raised")
@@ -889,6 +962,10 @@ def parse_args(argv=None):
         ap.error("--best-window and --job-best-window must be >= 0")
     if a.gpus < 1 or a.gpus > 64:
         ap.error("--gpus must be in 1..64")
+    try:
+        make_hparam_schedules(a)
+    except ValueError as ex:
+        ap.error(str(ex))
     check_requirements(vars(a), max(a.gpus, int(os.environ.get("WORLD_SIZE", "1"))), ap.error)
     return a
 
