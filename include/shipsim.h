@@ -457,8 +457,10 @@ int ssg_debug_clock_probe(uint64_t *dev_out, int n_blocks, int iters, void *stre
  * Forward, per env e: x[d] = (float)(obs[e][d] / obs_scale[d]) (f64 division, then one rounding to f32); every dense output is an
  * fmaf chain from its bias over k = 0, 1, ... in order, followed by tanh / ReLU on the hidden layers; logits = the pi head, value = the
  * v head.  Sampling (f32): m = max(logits), lse = m + log(sum exp(l - m)), logp_all = l - lse, cdf = cumsum(exp(logp_all)),
- * act = #{j < A-1 : u > cdf[j]}, logp = logp_all[act].  An env's outputs depend on its own observation row, the parameters and its
- * own u only (bitwise: not on n_envs, sharding or the launch that computed them).
+ * act = #{j < A-1 : u > cdf[j]}, logp = logp_all[act]; while that action is j >= 1 with a logit of -inf (a masked action: the f32
+ * cdf in front of it may stop short of 1 - 2^-24) act = j - 1.  So u = 0 gives action 0 whatever its probability, a NaN or +inf
+ * logit gives action 0 with logp NaN, and a -inf logit at j >= 1 is never drawn.  An env's outputs depend on its own observation
+ * row, the parameters and its own u only (bitwise: not on n_envs, sharding or the launch that computed them).
  * ------------------------------------------------------------------------------------------------- */
 #define SSG_POLICY_MAX_HIDDEN 128
 #define SSG_POLICY_TANH 0

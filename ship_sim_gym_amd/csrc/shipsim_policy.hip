@@ -365,6 +365,13 @@ __device__ __forceinline__ void policy_act_body(const ssg_policy &p, const float
             a += u > cdf ? 1 : 0;
         }
     }
+    // A masked action (logit -inf, probability 0) is never drawn.  The f32 sum of the other actions' probabilities can round to
+    // 1 - 2^-23 or less, and a u at the top of Philox's grid then counts past the last of them: step back to the action in front.
+    // (A -inf logit ahead of the last adds 0 to cdf and is passed by both of its thresholds or by neither; action 0 stays the
+    // answer to u = 0 whatever its logit.)
+#pragma unroll
+    for (int j = 3; j >= 1; --j)
+        if (a == j && lg[j] == -INFINITY) a = j - 1;
 #pragma unroll
     for (int j = 1; j < 4; ++j)
         if (a == j) lp = lg[j] - lse;

@@ -64,3 +64,20 @@ def torch_sample(torch, logits, u):
     cdf = logp_all.exp().cumsum(dim=-1)
     act = (u.unsqueeze(-1) > cdf[:, :-1]).sum(dim=-1)
     return act, logp_all.gather(-1, act.unsqueeze(-1)).squeeze(-1), cdf
+
+
+def check_near_rows(torch, near, u, cdf, act, logp, logp_all, tol=None, band=1e-5):
+    """The rows a sampling test keeps out of its exact comparison because u lies within `band` of an entry of the reference's
+    cdf [n, A]: the stored action is still one of the two the boundary separates (the reference's own choice for u - band and for
+    u + band, which are those two unless a second boundary lies in the band too), and logp is the reference log-probability
+    logp_all [n, A] of the action that WAS stored, within `tol` (None: the caller judges).  Returns |logp - reference| of the near rows."""
+    if not bool(near.any()):
+        return torch.zeros(0, dtype=logp_all.dtype, device=logp.device)
+    u, cdf = u[near].double().unsqueeze(-1), cdf[near][:, :-1].double()       # (exact: both are f32 or f64 values)
+    lo, hi = (u - band > cdf).sum(-1), (u + band > cdf).sum(-1)
+    a = act[near].long()
+    assert bool(((lo <= a) & (a <= hi)).all()) and bool((hi > lo).all()), (lo.tolist(), a.tolist(), hi.tolist())
+    ref = logp_all[near].gather(-1, a.unsqueeze(-1)).squeeze(-1)
+    err = (logp[near].to(ref.dtype) - ref).abs()
+    assert tol is None or bool((err <= tol).all()), (err.tolist(), tol)
+    return err

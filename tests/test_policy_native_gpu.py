@@ -7,7 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from gpu_support import env_config as _env_config, load_script, same_columns as _same_columns, torch_sample as _torch_sample
+from gpu_support import check_near_rows as _check_near, env_config as _env_config, load_script, same_columns as _same_columns
+from gpu_support import torch_sample as _torch_sample
 from gpu_support import torch_cuda  # noqa: F401
 from ppo_reference import actor_critic_policy as _policy, assert_same_rollout as _assert_same, stepwise_rollout as _stepwise
 
@@ -48,6 +49,7 @@ def test_forward_matches_torch_on_real_observations(torch_cuda):
                         ok = ~near
                         assert torch.equal(a.long()[ok], ar[ok]), tag
                         assert float((logp - lpr)[ok].abs().max()) <= 1e-4, tag
+                        _check_near(torch, near, u, cdf, a, logp, torch.log_softmax(logits.double(), -1), 1e-4)   # f64: the action's own
                         assert bool(((val - vr).abs() <= 1e-5 * (1 + vr.abs())).all()), (tag, float((val - vr).abs().max()))
                         assert torch.equal(env.obs, obs)  # the forward reads the observation, never writes it
             env.close()

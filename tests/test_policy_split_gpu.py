@@ -7,7 +7,7 @@ import ctypes as C
 
 import pytest
 
-from gpu_support import DEV, torch_cuda, torch_sample as _torch_sample, vec  # noqa: F401
+from gpu_support import DEV, check_near_rows as _check_near, torch_cuda, torch_sample as _torch_sample, vec  # noqa: F401
 from ppo_reference import assert_same_rollout, shared_over_pi_tower, split_policy, stepwise_rollout
 
 pytestmark = pytest.mark.gpu
@@ -80,6 +80,7 @@ def test_independent_towers_follow_the_reference_and_do_not_mix(torch_cuda, n, D
     print("max |logp - ref| %.3e  max |value - ref| %.3e" % (float((logp - lpr)[ok].abs().max()), float((val - vr).abs().max())))
     assert torch.equal(a.long()[ok], ar[ok])
     assert float((logp - lpr)[ok].abs().max()) <= 1e-4
+    _check_near(torch, near, u, cdf, a, logp, torch.log_softmax(logits.double(), -1), 1e-4)   # the f64 logp of the action stored
     assert bool(((val - vr).abs() <= 1e-5 * (1 + vr.abs())).all()), float((val - vr).abs().max())
     assert torch.equal(env.obs, obs)
     # the towers really differ: the value is not the shared policy's over the pi tower

@@ -14,7 +14,7 @@ import itertools
 import numpy as np
 import pytest
 
-from gpu_support import DEV, HIST_BEAMS, env_config as _env_config, torch_cuda  # noqa: F401
+from gpu_support import DEV, HIST_BEAMS, check_near_rows, env_config as _env_config, torch_cuda  # noqa: F401
 from ppo_reference import actor_critic_policy, assert_same_rollout, check_per_tensor, forward, ref_grad, ref_update, stepwise_rollout, \
     synthetic_batch_logp_noise as _synthetic, torch_gae
 
@@ -348,7 +348,7 @@ def test_policy_forward_domain(torch_cuda, history, n_beams):
         _, pol = actor_critic_policy(torch, D, H, L, act, A, seed=j)
         tag = (history, n_beams, H, L, act, A)
         rows = {k: [] for k in ("lp", "v", "lp64", "v64", "lp32", "v32")}
-        near_total = 0
+        near_total, near_err = 0, []
         for env, o, u in zip(hs, obs, us):
             a, logp, val, x = env.policy_act(pol, uniforms=u)
             assert torch.equal(x, (o / pol.obs_scale).float()), tag
@@ -360,6 +360,7 @@ def test_policy_forward_domain(torch_cuda, history, n_beams):
             ok = ~near
             ar = (u.double().unsqueeze(-1) > cdf[:, :-1]).sum(-1)
             assert torch.equal(a.long()[ok], ar[ok]), tag
+            near_err.append(check_near_rows(torch, near, u, cdf, a, logp, lp64_all))   # near rows: an adjacent action, and ITS logp (below)
             al = a.long().unsqueeze(-1)
             rows["lp"].append(logp[ok]); rows["v"].append(val)
             rows["lp64"].append(lp64_all.gather(-1, al).squeeze(-1)[ok]); rows["v64"].append(v64)
@@ -370,6 +371,9 @@ def test_policy_forward_domain(torch_cuda, history, n_beams):
             e_mine = float((cat[q] - cat[q + "64"]).abs().max())
             e_t32 = float((cat[q + "32"] - cat[q + "64"]).abs().max())
             assert e_mine <= 4 * e_t32 + 1e-6 * float(cat[q + "64"].abs().max()), (tag, q, e_mine, e_t32)
+            if q == "lp":                                                       # the same bound, from the other rows, on the near rows
+                e_near = torch.cat(near_err)
+                assert e_near.numel() == near_total and bool((e_near <= 4 * e_t32 + 1e-6 * float(cat["lp64"].abs().max())).all()), (tag, e_near.tolist())
     for e, o in zip(hs, obs):
         assert torch.equal(e.obs, o)
         e.close()
