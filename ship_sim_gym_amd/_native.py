@@ -392,8 +392,6 @@ def lib():
                                          dp, dp, dp]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError here = a declared entry point is not exported
-        if getattr(L, name).restype is C.c_int and name not in ("ssg_abi_version",):
-            pass
     if L.ssg_abi_version() != ABI_VERSION:
         raise ShipSimError("libshipsim.so ABI %d != binding ABI %d" % (L.ssg_abi_version(), ABI_VERSION))
     _lib = L
@@ -407,12 +405,49 @@ def check(rc, handle=None, what=""):
         raise ShipSimError("%s failed: %s (%s)" % (what or "libshipsim call", L.ssg_strerror(rc).decode(), msg))
 
 
+def call(name, *args, handle=None):
+    """THE checked library call: the export `name` on `args`, then check(rc, handle, name).  Every export has its argtypes declared
+    (lib(); tests/test_abi.py), pointers as c_void_p, so an address goes in as a plain integer (``t.data_ptr()``) and None as NULL.
+    As it stands it serves the queries that take no handle; ShipVecEnv.call / ShipVecEnv.enqueue put the handle in front."""
+    check(getattr(lib(), name)(*args), handle, name)
+
+
+def nbytes(name, *args):
+    """A ``*_nbytes`` query: `name` on `args` and a size_t out-parameter, whose value is returned."""
+    need = C.c_size_t()
+    call(name, *args, C.byref(need))
+    return need.value
+
+
 def ptr(t):
     """A tensor's address as a pointer argument of a C call; None stays None (NULL)."""
-    return None if t is None else C.c_void_p(t.data_ptr())
+    return None if t is None else t.data_ptr()
+
+
+def _torch():
+    """THE import point of torch for the host layer: at first use, so that the host-only parts import without it."""
+    import torch
+    return torch
+
+
+def arg(t, dtypes, shape, what, device, more_rows=False, exc=ValueError):
+    """THE check of a tensor argument: `t` is what the C call will read it as — of `dtypes` (one dtype or a tuple of them), of `shape`
+    (an int: that many elements, in any shape; a tuple: exactly that shape, or with more_rows a first dimension of at least shape[0]),
+    contiguous and on `device` — or `exc` is raised, naming the call and the argument (`what`), what was expected and what was got.
+    Returns the tensor's address, a plain integer."""
+    if ((t.dtype is dtypes or (type(dtypes) is tuple and t.dtype in dtypes)) and t.device == device and t.is_contiguous()
+            and (t.numel() == shape if type(shape) is int else
+                 t.dim() == len(shape) and tuple(t.shape[1:]) == tuple(shape[1:])
+                 and (t.shape[0] >= shape[0] if more_rows else t.shape[0] == shape[0]))):
+        return t.data_ptr()
+    want = "%d elements" % shape if type(shape) is int else "shape [%s]" % ", ".join(
+        [(">= %d" if more_rows else "%d") % shape[0]] + ["%d" % s for s in shape[1:]])
+    names = " / ".join(str(d) for d in (dtypes if type(dtypes) is tuple else (dtypes,)))
+    raise exc("%s must be a contiguous %s tensor of %s on %s (got %s %s on %s, strides %s)"
+              % (what, names, want, device, t.dtype, tuple(t.shape), t.device, tuple(t.stride())))
 
 
 def default_config():
     c = Config()
-    check(lib().ssg_default_config(C.byref(c)), None, "ssg_default_config")
+    call("ssg_default_config", C.byref(c))
     return c

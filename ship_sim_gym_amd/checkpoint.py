@@ -20,14 +20,11 @@ section by name.
 """
 import os
 
+from ._native import _torch
+
 FORMAT = "ssg-checkpoint"
 VERSION = 1
 SECTIONS = ("policy", "population", "trainer", "obs_filter", "ret_filter", "episode_log", "env", "scheduler", "loop", "config")
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def check_plain(obj, where="checkpoint"):

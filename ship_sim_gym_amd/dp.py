@@ -43,7 +43,8 @@ gradient, running this loop from C.
 import ctypes as C
 
 from . import _native as N
-from .ppo import NativePPO, _torch, _tree256, adv_stats_row_reference, chunk_split, minibatch_adv_sums_reference
+from ._native import _torch
+from .ppo import NativePPO, _tree256, adv_stats_row_reference, chunk_split, minibatch_adv_sums_reference
 from .sharding import all_gather_rows
 
 
@@ -270,10 +271,7 @@ class DataParallelPPO(NativePPO):
         torch = _torch()
         K, n_env = int(batch["adv"].shape[0]), int(batch["adv"].shape[1])
         out = torch.empty(4, dtype=torch.float64, device=self.policy.device)
-        ws, nb = self._ws_ptr()
-        h = self.env._h
-        with torch.cuda.device(self.policy.device):
-            N.check(N.lib().ssg_ppo_adv_moments(h, K, n_env, ws, nb, C.c_void_p(out.data_ptr()), self._stream()), h, "ssg_ppo_adv_moments")
+        self.env.enqueue("ssg_ppo_adv_moments", K, n_env, *self._ws_ptr(), out.data_ptr())
         return out
 
     def set_moments(self, rows):
@@ -281,14 +279,9 @@ class DataParallelPPO(NativePPO):
         reads them (adv_stats() shows them)."""
         torch = _torch()
         rows = rows.to(device=self.policy.device, dtype=torch.float64).contiguous()
-        if rows.dim() != 2 or rows.shape[1] != 4:
-            raise ValueError("DataParallelPPO.set_moments: rows must be f64 [W, 4] (got %s)" % (tuple(rows.shape),))
+        rp = N.arg(rows, torch.float64, (0, 4), "DataParallelPPO.set_moments: rows", self._device, more_rows=True)
         self._ws(1, 1)
-        ws, nb = self._ws_ptr()
-        h = self.env._h
-        with torch.cuda.device(self.policy.device):
-            N.check(N.lib().ssg_ppo_set_adv_moments(h, int(rows.shape[0]), C.c_void_p(rows.data_ptr()), float(self.hp.adv_eps), ws, nb,
-                                                    self._stream()), h, "ssg_ppo_set_adv_moments")
+        self.env.enqueue("ssg_ppo_set_adv_moments", int(rows.shape[0]), rp, float(self.hp.adv_eps), *self._ws_ptr())
 
     # ------------------------------------------------------------------------------------------------
     # per-minibatch advantage statistics over the job (job_adv_norm="minibatch")
@@ -323,16 +316,12 @@ class DataParallelPPO(NativePPO):
         epochs = int(perm.shape[0])
         chunk, chunks = chunk_split(n, minibatches)
         nb = epochs * chunks
-        need = C.c_size_t()
-        N.check(N.lib().ssg_ppo_minibatch_adv_nbytes(nb, C.byref(need)), None, "ssg_ppo_minibatch_adv_nbytes")
-        if self._job_scratch is None or self._job_scratch.numel() < need.value:
-            self._job_scratch = torch.zeros(need.value, dtype=torch.uint8, device=dev)
+        need = N.nbytes("ssg_ppo_minibatch_adv_nbytes", nb)
+        if self._job_scratch is None or self._job_scratch.numel() < need:
+            self._job_scratch = torch.zeros(need, dtype=torch.uint8, device=dev)
         out = torch.empty((nb, 4), dtype=torch.float64, device=dev)
-        h = self.env._h
-        with torch.cuda.device(dev):
-            N.check(N.lib().ssg_ppo_minibatch_adv_sums(h, n, C.c_void_p(adv.data_ptr()), C.c_void_p(perm.data_ptr()), epochs, n, chunk,
-                                                       C.c_void_p(out.data_ptr()), C.c_void_p(self._job_scratch.data_ptr()),
-                                                       self._job_scratch.numel(), self._stream()), h, "ssg_ppo_minibatch_adv_sums")
+        self.env.enqueue("ssg_ppo_minibatch_adv_sums", n, adv.data_ptr(), perm.data_ptr(), epochs, n, chunk, out.data_ptr(),
+                         self._job_scratch.data_ptr(), self._job_scratch.numel())
         self._job_chunks = chunks
         if partials:
             return out, self._job_scratch[:nb * N.ADV_NORM_BLOCKS * 24].view(torch.float64).view(nb, N.ADV_NORM_BLOCKS, 3)
@@ -345,14 +334,12 @@ class DataParallelPPO(NativePPO):
         self._need_job_mode("set_minibatch_rows")
         dev = self.policy.device
         rows = rows.to(device=dev, dtype=torch.float64).contiguous()
-        if rows.dim() != 3 or rows.shape[2] != 4:
+        if rows.dim() != 3:
             raise ValueError("DataParallelPPO.set_minibatch_rows: rows must be f64 [W, epochs * chunks, 4] (got %s)" % (tuple(rows.shape),))
         W, nb = int(rows.shape[0]), int(rows.shape[1])
+        rp = N.arg(rows, torch.float64, (W, nb, 4), "DataParallelPPO.set_minibatch_rows: rows", dev)
         table = torch.empty((nb, 4), dtype=torch.float32, device=dev)  # (a new one per update: the last one may still be read)
-        h = self.env._h
-        with torch.cuda.device(dev):
-            N.check(N.lib().ssg_ppo_set_minibatch_adv_rows(h, W, nb, C.c_void_p(rows.data_ptr()), float(self.hp.adv_eps),
-                                                           C.c_void_p(table.data_ptr()), self._stream()), h, "ssg_ppo_set_minibatch_adv_rows")
+        self.env.enqueue("ssg_ppo_set_minibatch_adv_rows", W, nb, rp, float(self.hp.adv_eps), table.data_ptr())
         self._job_table, self._job_row = table, 0
         self._bind_adv_norm()
         return table
@@ -401,18 +388,14 @@ class DataParallelPPO(NativePPO):
         M = idx.numel()
         self._ws(n, M)
         row = torch.zeros(self.n_params + N.PPO_EXT_STATS, dtype=torch.float32, device=self.policy.device)
-        ws, nb = self._ws_ptr()
-        pol, h = self.policy.to_native(), self.env._h
         self._bind_adv_norm()
         name, ext = "ssg_ppo_grad", ()
         if self.extended():
             rec = self._ext(batch, n)
             rec.max_grad_norm = 0.0
             name, ext = "ssg_ppo_grad_ext", (C.byref(rec),)
-        with torch.cuda.device(self.policy.device):
-            N.check(getattr(N.lib(), name)(h, C.byref(pol), C.byref(self.hp), *ext, n, *p, C.c_void_p(idx.data_ptr()), M,
-                                           C.c_void_p(row.data_ptr()), C.c_void_p(row[self.n_params:].data_ptr()), ws, nb, self._stream()),
-                    h, name)
+        self.env.enqueue(name, C.byref(self.policy.to_native()), C.byref(self.hp), *ext, n, *p, idx.data_ptr(), M, row.data_ptr(),
+                         row[self.n_params:].data_ptr(), *self._ws_ptr())
         return row
 
     def apply_rows(self, rows, counts, first_chunk, last_chunk, stats=False):
@@ -422,8 +405,7 @@ class DataParallelPPO(NativePPO):
         torch = _torch()
         rows = rows.to(device=self.policy.device, dtype=torch.float32).contiguous()
         W = len(counts)
-        if tuple(rows.shape) != (W, self.n_params + N.PPO_EXT_STATS):
-            raise ValueError("DataParallelPPO.apply_rows: rows must be f32 [%d, %d] (got %s)" % (W, self.n_params + N.PPO_EXT_STATS, tuple(rows.shape)))
+        N.arg(rows, torch.float32, (W, self.n_params + N.PPO_EXT_STATS), "DataParallelPPO.apply_rows: rows", self._device)
         self._since_first = 1 if first_chunk else self._since_first + 1
         cnt = (C.c_int64 * W)(*[int(c) for c in counts])
         sh = N.PpoShards()
@@ -440,13 +422,9 @@ class DataParallelPPO(NativePPO):
             ext = C.byref(rec)
         self._ws(1, 1)
         st = torch.empty(N.PPO_EXT_STATS, dtype=torch.float32, device=self.policy.device) if stats else None
-        ws, nb = self._ws_ptr()
-        pol, h = self.policy.to_native(), self.env._h
         self._bind_adv_norm()
-        with torch.cuda.device(self.policy.device):
-            N.check(N.lib().ssg_ppo_apply_shards(h, C.byref(pol), C.byref(self.hp), ext, C.byref(sh), C.c_void_p(self.adam_mv.data_ptr()),
-                                                 self.step + 1, C.c_void_p(st.data_ptr()) if stats else None, ws, nb, self._stream()),
-                    h, "ssg_ppo_apply_shards")
+        self.env.enqueue("ssg_ppo_apply_shards", C.byref(self.policy.to_native()), C.byref(self.hp), ext, C.byref(sh), self.adam_mv.data_ptr(),
+                         self.step + 1, N.ptr(st), *self._ws_ptr())
         self.step += 1
         if not stats:
             return None

@@ -29,6 +29,7 @@ import warnings
 import numpy as np
 
 from . import _native as N
+from ._native import _torch
 
 RECORD_DTYPE = np.dtype([("ret", "<f8"), ("step", "<i8"), ("env", "<i4"), ("length", "<i4"), ("goals", "<i4"), ("end", "<u4")])
 RECORD_BYTES = 32
@@ -37,11 +38,6 @@ MONITOR_COLUMNS = ("r", "l", "t", "timesteps", "env", "member", "goals", "end")
 # the endings, under evaluate.py's names, and their SSG_EV_* bits
 END_BITS = (("collided", N.EV_COLLIDING), ("out_of_bounds", N.EV_OUT_OF_BOUNDS), ("max_steps", N.EV_MAX_STEPS),
             ("no_goals_left", N.EV_NO_GOALS_LEFT))
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def record_member(records):
@@ -246,9 +242,7 @@ class EpisodeLog(object):
             self.stage = job_stage(cap, self.rows, self.total_envs, self.world)
             if self.stage > 2 ** 31 - 1:
                 raise ValueError("EpisodeLog: a shard block of %d record slots is more than a call takes" % self.stage)
-            need = C.c_size_t()
-            N.check(N.lib().ssg_job_episode_log_block_nbytes(self.rows, self.stage, C.byref(need)), None, "ssg_job_episode_log_block_nbytes")
-            self.block_nbytes = int(need.value)
+            self.block_nbytes = N.nbytes("ssg_job_episode_log_block_nbytes", self.rows, self.stage)
         # one buffer, one copy to the host: the head (int64 [2], padded to a record) and then the ring
         self.buffer = torch.zeros((cap + 1) * RECORD_BYTES, dtype=torch.uint8, device=dev)
         self.head = self.buffer[:16].view(torch.int64)
@@ -269,12 +263,9 @@ class EpisodeLog(object):
         return self
 
     def _ws(self, K):
-        torch = _torch()
-        need = C.c_size_t()
-        N.check(N.lib().ssg_episode_log_workspace_nbytes(int(self.env.num_envs), int(K), C.byref(need)), None,
-                "ssg_episode_log_workspace_nbytes")
-        if self.workspace.numel() < need.value:
-            self.workspace = torch.zeros(need.value, dtype=torch.uint8, device=self.buffer.device)
+        need = N.nbytes("ssg_episode_log_workspace_nbytes", int(self.env.num_envs), int(K))
+        if self.workspace.numel() < need:
+            self.workspace = _torch().zeros(need, dtype=_torch().uint8, device=self.buffer.device)
         return self.workspace
 
     def to_native(self, K=1):
@@ -309,7 +300,6 @@ class EpisodeLog(object):
         """ssg_episode_log_append on a rollout's buffers: rew f64 / done u8 / flags u8 (or None) [K, N] in the env's row layout, rows of
         unit stride and a common row pitch >= N.  Row t is step ``steps + t``; ``steps`` advances by K.  Blocks beyond the library's
         cap on K * tiles are served in several calls, which leave what one call would.  No host synchronisation."""
-        torch = _torch()
         env = self.env
         n_env = int(env.num_envs)
         if self.job:
@@ -318,13 +308,9 @@ class EpisodeLog(object):
         K, pitch = self._check_rows(rew, done, flags)
         per_call = max(1, N.EPISODE_LOG_MAX_CELLS // ((n_env + 255) // 256))
         rec = self.to_native(min(K, per_call))
-        with torch.cuda.device(env.device):
-            for k0 in range(0, K, per_call):
-                k1 = min(K, k0 + per_call)
-                N.check(N.lib().ssg_episode_log_append(env._h, C.byref(rec), k1 - k0, self.steps + k0, C.c_void_p(rew[k0].data_ptr()),
-                                                       C.c_void_p(done[k0].data_ptr()),
-                                                       C.c_void_p(flags[k0].data_ptr()) if flags is not None else None, pitch,
-                                                       env._stream()), env._h, "ssg_episode_log_append")
+        for k0 in range(0, K, per_call):
+            env.enqueue("ssg_episode_log_append", C.byref(rec), min(K, k0 + per_call) - k0, self.steps + k0, rew[k0].data_ptr(),
+                        done[k0].data_ptr(), flags[k0].data_ptr() if flags is not None else None, pitch)
         self.steps += K
         self._host_copy = None
         return self
@@ -355,14 +341,9 @@ class EpisodeLog(object):
         if K > self.rows:
             raise ValueError("EpisodeLog.shard_block: %d rows, this log's calls take %d at most (job_append cuts a batch into pieces)" % (K, self.rows))
         block = torch.empty(self.block_nbytes, dtype=torch.uint8, device=env.device) if out is None else out
-        if block.dtype != torch.uint8 or block.device != self.buffer.device or tuple(block.shape) != (self.block_nbytes,) or not block.is_contiguous():
-            raise ValueError("EpisodeLog.shard_block: out must be a contiguous uint8 tensor (%d,) on %s" % (self.block_nbytes, self.buffer.device))
-        rec = self.to_native(K)
-        with torch.cuda.device(env.device):
-            N.check(N.lib().ssg_job_episode_log_shard(env._h, C.byref(rec), K, self.steps, C.c_void_p(rew.data_ptr()), C.c_void_p(done.data_ptr()),
-                                                      C.c_void_p(flags.data_ptr()) if flags is not None else None, pitch, self.rows,
-                                                      self.stage, C.c_void_p(block.data_ptr()), block.numel(), env._stream()),
-                    env._h, "ssg_job_episode_log_shard")
+        bp = N.arg(block, torch.uint8, (self.block_nbytes,), "EpisodeLog.shard_block: out", self.buffer.device)
+        env.enqueue("ssg_job_episode_log_shard", C.byref(self.to_native(K)), K, self.steps, rew.data_ptr(), done.data_ptr(), N.ptr(flags), pitch,
+                    self.rows, self.stage, bp, block.numel())
         self._pending = (K, self.steps)
         return block
 
@@ -387,11 +368,8 @@ class EpisodeLog(object):
                              % (self.world, self.block_nbytes, self.buffer.device, stacked.dtype, tuple(stacked.shape), stacked.device))
         stacked = stacked.contiguous()
         K, step0 = self._pending if K is None else (int(K), int(step0))
-        env = self.env
-        rec = self.to_native(1)
-        with torch.cuda.device(env.device):
-            N.check(N.lib().ssg_job_episode_log_merge_blocks(env._h, C.byref(rec), K, step0, self.rows, self.stage, C.c_void_p(stacked.data_ptr()),
-                                                             self.world, env._stream()), env._h, "ssg_job_episode_log_merge_blocks")
+        self.env.enqueue("ssg_job_episode_log_merge_blocks", C.byref(self.to_native(1)), K, step0, self.rows, self.stage, stacked.data_ptr(),
+                         self.world)
         self._pending = None
         self.steps = step0 + K
         self._host_copy = None

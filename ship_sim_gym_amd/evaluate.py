@@ -20,13 +20,9 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
+from ._native import _torch
 
 COLUMNS = ("episodes", "return100", "length", "collided", "out_of_bounds", "max_steps", "no_goals_left", "goals")
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def new_carry(n_envs):
@@ -207,10 +203,10 @@ class EvalRecorder(object):
 
     def bind(self):
         rec = self.record()
-        N.check(N.lib().ssg_set_eval_recorder(self.env._h, C.byref(rec)), self.env._h, "ssg_set_eval_recorder")
+        self.env.call("ssg_set_eval_recorder", C.byref(rec))
 
     def unbind(self):
-        N.check(N.lib().ssg_set_eval_recorder(self.env._h, None), self.env._h, "ssg_set_eval_recorder")
+        self.env.call("ssg_set_eval_recorder", None)
 
     def reset(self):
         """Zero the cursors and the overflow counts: the next evaluation records from row 0."""
@@ -301,7 +297,6 @@ class NativeEvaluator(object):
         """One ssg_evaluate / ssg_pop_evaluate call: n_steps iterations enqueued on the current stream, no synchronisation.  uniforms:
         float32 [n_steps, N] rows for the sampled mode.  Continues the carries as they stand.  recorder: an EvalRecorder on this env,
         bound for the duration of the library call (it continues at its cursors) and unbound on every way out."""
-        torch = _torch()
         env, pol = self.env, policy_or_population
         population = hasattr(pol, "member")
         what = "evaluate"
@@ -319,9 +314,7 @@ class NativeEvaluator(object):
                 raise ValueError("evaluate: the recorder belongs to another env")
             recorder.bind()
         try:
-            with torch.cuda.device(env.device):
-                fn = N.lib().ssg_pop_evaluate if population else N.lib().ssg_evaluate
-                N.check(fn(env._h, C.byref(rec), C.byref(ev), env._stream()), env._h, "ssg_pop_evaluate" if population else "ssg_evaluate")
+            env.enqueue("ssg_pop_evaluate" if population else "ssg_evaluate", C.byref(rec), C.byref(ev))
         finally:
             if recorder is not None:
                 recorder.unbind()
@@ -337,28 +330,20 @@ class NativeEvaluator(object):
         reward = env.reward if reward is None else reward
         done = env.done if done is None else done
         flags = env.flags if flags is None else flags
-        for t, dt, what in ((reward, torch.float64, "reward"), (done, torch.uint8, "done"), (flags, torch.uint8, "flags")):
-            if t.dtype != dt or t.device != env.device or not t.is_contiguous() or t.numel() != env.num_envs:
-                raise ValueError("evaluate: %s must be a contiguous %s tensor of %d elements on %s" % (what, dt, env.num_envs, env.device))
-        with torch.cuda.device(env.device):
-            N.check(N.lib().ssg_eval_account(env._h, int(episodes), C.c_void_p(reward.data_ptr()), C.c_void_p(done.data_ptr()),
-                                             C.c_void_p(flags.data_ptr()), C.c_void_p(self.carry_return.data_ptr()),
-                                             C.c_void_p(self.carry.data_ptr()), C.c_void_p(self.env_stats.data_ptr()), env._stream()),
-                    env._h, "ssg_eval_account")
+        p = [env._arg(t, dt, env.num_envs, "evaluate: " + what) for t, dt, what in
+             ((reward, torch.float64, "reward"), (done, torch.uint8, "done"), (flags, torch.uint8, "flags"))]
+        env.enqueue("ssg_eval_account", int(episodes), *p, self.carry_return.data_ptr(), self.carry.data_ptr(), self.env_stats.data_ptr())
         self.steps += 1
 
     def reduce(self, n_members=1):
         """ssg_eval_reduce: int64 [n_members, 8] column sums of each member's rows of env_stats (a view of this object's buffer); a
         member's rows are its slice of the env's set_population_slices when one is bound."""
-        torch = _torch()
         env = self.env
         P = int(n_members)
         sizes = env.population_slices if P > 1 else None  # (one policy's reduce is over the whole handle)
         if P < 1 or P > N.POP_MAX_MEMBERS or (len(sizes) != P if sizes is not None else env.num_envs % P):
             raise ValueError("evaluate: %d envs do not split into %d member slices" % (env.num_envs, P))
-        with torch.cuda.device(env.device):
-            N.check(N.lib().ssg_eval_reduce(env._h, P, C.c_void_p(self.env_stats.data_ptr()), C.c_void_p(self.member_stats.data_ptr()),
-                                            env._stream()), env._h, "ssg_eval_reduce")
+        env.enqueue("ssg_eval_reduce", P, self.env_stats.data_ptr(), self.member_stats.data_ptr())
         return self.member_stats[:P]
 
     def evaluate(self, policy_or_population, episodes, greedy=True, max_steps=None, seed=0, step0=0, uniforms=None, reset=True, chunk=128,

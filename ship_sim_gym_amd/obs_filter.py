@@ -21,11 +21,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
-
-
-def _torch():
-    import torch
-    return torch
+from ._native import _torch
 
 
 def _halving_tree(x):
@@ -137,10 +133,9 @@ class ObsFilter(object):
             raise ValueError("ObsFilter: clip and eps must be >= 0")
         self.env, self.n_members, self.obs_dim, self.clip, self.eps, self.updating = env, P, D, clip, eps, bool(update)
         dev = env.device
-        nbytes = C.c_size_t()
-        N.check(N.lib().ssg_obs_filter_workspace_nbytes(int(env.num_envs), D, P, C.byref(nbytes)), None, "ssg_obs_filter_workspace_nbytes")
+        nbytes = N.nbytes("ssg_obs_filter_workspace_nbytes", int(env.num_envs), D, P)
         self.state = _state if _state is not None else torch.zeros((P, N.FILTER_ROWS, D), dtype=torch.float64, device=dev)
-        self.workspace = torch.zeros(nbytes.value, dtype=torch.uint8, device=dev)
+        self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
         self.job = bool(job)
         self.buffer = torch.zeros_like(self.state) if self.job else None
         self.base = self.state.clone() if self.job else None
@@ -186,17 +181,12 @@ class ObsFilter(object):
         torch = _torch()
         env = self.env
         obs = env.obs if obs is None else obs
-        if obs.dtype != torch.float64 or obs.device != env.device or not obs.is_contiguous() or tuple(obs.shape) != (env.num_envs, self.obs_dim):
-            raise ValueError("ObsFilter.update: obs must be a contiguous float64 tensor (%d, %d) on %s (got %s %s on %s)"
-                             % (env.num_envs, self.obs_dim, env.device, obs.dtype, tuple(obs.shape), obs.device))
+        op = N.arg(obs, torch.float64, (env.num_envs, self.obs_dim), "ObsFilter.update: obs", env.device)
         rec = self.to_native()
-        with torch.cuda.device(env.device):
-            if self.job:
-                N.check(N.lib().ssg_obs_filter_update_buffered(env._h, C.byref(rec), C.c_void_p(self.buffer.data_ptr()),
-                                                               C.c_void_p(obs.data_ptr()), env._stream()), env._h, "ssg_obs_filter_update_buffered")
-            else:
-                N.check(N.lib().ssg_obs_filter_update(env._h, C.byref(rec), C.c_void_p(obs.data_ptr()), env._stream()), env._h,
-                        "ssg_obs_filter_update")
+        if self.job:
+            env.enqueue("ssg_obs_filter_update_buffered", C.byref(rec), self.buffer.data_ptr(), op)
+        else:
+            env.enqueue("ssg_obs_filter_update", C.byref(rec), op)
 
     def merge_rows(self, rows):
         """The second half of ``sync``: rows f64 [W, n_members, 4, D] on the filter's device (the ranks' buffers in rank order; W in
@@ -206,15 +196,10 @@ class ObsFilter(object):
         env = self.env
         if not self.job:
             raise ValueError("ObsFilter.merge_rows: this filter was not made with job=True (it has no base and no buffer)")
-        want = tuple(self.state.shape)
-        if (rows.dtype != torch.float64 or rows.device != self.state.device or not rows.is_contiguous() or rows.dim() != 4
-                or tuple(rows.shape[1:]) != want or not 1 <= rows.shape[0] <= N.DP_MAX_SHARDS):
-            raise ValueError("ObsFilter.merge_rows: rows must be a contiguous float64 tensor (W in 1..%d, %d, %d, %d) on %s (got %s %s on %s)"
-                             % ((N.DP_MAX_SHARDS,) + want + (self.state.device, rows.dtype, tuple(rows.shape), rows.device)))
-        rec = self.to_native()
-        with torch.cuda.device(env.device):
-            N.check(N.lib().ssg_obs_filter_merge_rows(env._h, C.byref(rec), C.c_void_p(self.base.data_ptr()), C.c_void_p(rows.data_ptr()),
-                                                      int(rows.shape[0]), env._stream()), env._h, "ssg_obs_filter_merge_rows")
+        rp = N.arg(rows, torch.float64, (1,) + tuple(self.state.shape), "ObsFilter.merge_rows: rows", self.state.device, more_rows=True)
+        if rows.shape[0] > N.DP_MAX_SHARDS:
+            raise ValueError("ObsFilter.merge_rows: rows holds the buffers of %d ranks, a call merges %d at most" % (rows.shape[0], N.DP_MAX_SHARDS))
+        env.enqueue("ssg_obs_filter_merge_rows", C.byref(self.to_native()), self.base.data_ptr(), rp, int(rows.shape[0]))
         self.base.copy_(self.state)
         self.buffer.zero_()
         return self

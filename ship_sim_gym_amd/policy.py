@@ -16,13 +16,9 @@ on the second, declared in the order ``pi_body, pi, vf_body, v``.  ``value_layer
 import ctypes as C
 
 from . import _native as N
+from ._native import _torch
 
 ACTIVATIONS = {"tanh": N.POLICY_TANH, "relu": N.POLICY_RELU}
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def packed_offsets(obs_dim, hidden, n_hidden_layers, n_actions, separate_value=False):

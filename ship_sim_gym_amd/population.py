@@ -26,13 +26,9 @@ from fractions import Fraction
 
 from . import _native as N
 from . import hparam_schedule as HS
+from ._native import _torch
 from .policy import ACTIVATIONS, NativePolicy
 from .ppo import DeviceTrainer, adv_norm_mode, adv_norm_scratch, adv_norm_views, chunk_split, load_packed
-
-
-def _torch():
-    import torch
-    return torch
 
 
 class NativePopulation(object):
@@ -296,7 +292,7 @@ class PopulationPPO(DeviceTrainer):
         name, step0 = "ssg_pop_pack_hparams", int(self.step)
         if steps0 is not None:
             name, step0 = "ssg_pop_pack_hparams_steps", (C.c_int64 * self.n_members)(*[int(x) for x in steps0])
-        N.check(getattr(N.lib(), name)(self.n_members, self.hparams(), step0, int(n_steps), buf, n), None, name)
+        N.call(name, self.n_members, self.hparams(), step0, int(n_steps), buf, n)
         return torch.tensor(list(buf), dtype=torch.float32).to(self.population.device)
 
     def minibatches_for_size(self, size, samples=None, member=None):
@@ -323,7 +319,7 @@ class PopulationPPO(DeviceTrainer):
             name, sm = "ssg_pop_pack_schedule", int(samples)
 
         def pack(buf, n):
-            N.check(getattr(N.lib(), name)(P, sm, ep, mb, buf, n, steps, C.byref(launches)), None, name)
+            N.call(name, P, sm, ep, mb, buf, n, steps, C.byref(launches))
         pack(None, 0)  # the size query
         n = N.pop_sched_ints(P, launches.value)
         buf = (C.c_int32 * n)()
@@ -334,13 +330,9 @@ class PopulationPPO(DeviceTrainer):
         """The workspace, grown to serve the sizes (its head — the members' advantage statistics — is kept when it grows)."""
         return self._grow("ssg_pop_workspace_nbytes", self.population.to_native(), samples_per_member, max_minibatch, 16 * self.n_members)
 
-    def _flat(self, batch, key, dtype, shape):
-        t = batch[key]
-        dev = self.population.device
-        if t.dtype != dtype or t.device != dev or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-            raise ValueError("PopulationPPO: batch[%r] must be a contiguous %s tensor %s on %s (got %s %s on %s)"
-                             % (key, dtype, tuple(shape), dev, t.dtype, tuple(t.shape), t.device))
-        return C.c_void_p(t.data_ptr())
+    def _flat(self, batch, key, dtype, shape, who="PopulationPPO"):
+        """The address of batch[key], checked (N.arg) as `dtype`, contiguous, on the device and of exactly `shape`."""
+        return N.arg(batch[key], dtype, tuple(shape), "%s: batch[%r]" % (who, key), self._device)
 
     def _KN(self, batch):
         rew = batch["rew"]
@@ -365,25 +357,22 @@ class PopulationPPO(DeviceTrainer):
         target is gamma_m * boot instead of 0; boot goes in as it is, with a return filter too."""
         torch = _torch()
         K, n_env = self._KN(batch)
-        dev = self.population.device
+        dev, who = self.population.device, "PopulationPPO.gae"
         if return_filter is not None:
             return_filter.apply(batch)
-        p = [self._flat(batch, "rew" if return_filter is None else "rew_norm", torch.float64, (K, n_env)), self._flat(batch, "done", torch.uint8, (K, n_env)),
-             self._flat(batch, "val", torch.float32, (K, n_env)), self._flat(batch, "last_val", torch.float32, (n_env,))]
+        p = [self._flat(batch, "rew" if return_filter is None else "rew_norm", torch.float64, (K, n_env), who),
+             self._flat(batch, "done", torch.uint8, (K, n_env), who), self._flat(batch, "val", torch.float32, (K, n_env), who),
+             self._flat(batch, "last_val", torch.float32, (n_env,), who)]
         name = "ssg_pop_gae"
         if "boot" in batch:
-            p.append(self._flat(batch, "boot", torch.float32, (K, n_env)))
+            p.append(self._flat(batch, "boot", torch.float32, (K, n_env), who))
             name = "ssg_pop_gae_boot"
         self._ws(K * max(self.member_envs), 1)
         self._last_K = K
         adv = torch.empty((K, n_env), dtype=torch.float32, device=dev)
         ret = torch.empty_like(adv)
-        pop, h = self.population.to_native(), self.env._h
-        with torch.cuda.device(dev):
-            table = self._table(0)  # (no Adam rows: the step counts do not enter)
-            N.check(getattr(N.lib(), name)(h, C.byref(pop), C.c_void_p(table.data_ptr()), K, *p, C.c_void_p(adv.data_ptr()),
-                                           C.c_void_p(ret.data_ptr()), C.c_void_p(self.workspace.data_ptr()), self.workspace.numel(),
-                                           self._stream()), h, name)
+        table = self._table(0)  # (no Adam rows: the step counts do not enter)
+        self.env.enqueue(name, C.byref(self.population.to_native()), table.data_ptr(), K, *p, adv.data_ptr(), ret.data_ptr(), *self._ws_ptr())
         batch["adv"], batch["ret"] = adv, ret
         return adv, ret
 
@@ -399,9 +388,7 @@ class PopulationPPO(DeviceTrainer):
         dev, D = self.population.device, self.population.obs_dim
         x = self._flat(batch, "obs", torch.float32, (K, n_env, D))
         out = torch.empty((K, n_env, 4), dtype=torch.float32, device=dev)
-        pop, h = self.population.to_native(), self.env._h
-        with torch.cuda.device(dev):
-            N.check(N.lib().ssg_pop_dist(h, C.byref(pop), K, x, C.c_void_p(out.data_ptr()), self._stream()), h, "ssg_pop_dist")
+        self.env.enqueue("ssg_pop_dist", C.byref(self.population.to_native()), K, x, out.data_ptr())
         batch["logp_all"] = out
         return out
 
@@ -418,12 +405,12 @@ class PopulationPPO(DeviceTrainer):
             ext.flags |= N.POP_EXT_GRAD_CLIP
         if any(v > 0.0 for v in self.vf_clip):
             ext.flags |= N.POP_EXT_VF_CLIP
-            ext.dev_value_old = self._flat(batch, "val", torch.float32, (K, n_env)).value
+            ext.dev_value_old = self._flat(batch, "val", torch.float32, (K, n_env))
         if bool((self.kl_coef > 0).any()):
             if "logp_all" not in batch:
                 self.dist(batch)
             ext.dev_kl_coef = self.kl_coef.data_ptr()
-            ext.dev_logp_all = self._flat(batch, "logp_all", torch.float32, (K, n_env, 4)).value
+            ext.dev_logp_all = self._flat(batch, "logp_all", torch.float32, (K, n_env, 4))
         return ext, table
 
     def adv_stats(self):
@@ -459,12 +446,8 @@ class PopulationPPO(DeviceTrainer):
         shape = (E * K * sum(sizes),) if sliced else (P, E, K * sizes[0])
         if out is None:
             out = torch.empty(shape, dtype=torch.int64, device=dev)
-        if out.dtype != torch.int64 or out.device != dev or not out.is_contiguous() or tuple(out.shape) != shape:
-            raise ValueError("PopulationPPO.draw_perm: out must be a contiguous int64 %s tensor on %s" % (shape, dev))
-        h = self.env._h
-        with torch.cuda.device(dev):
-            N.check(N.lib().ssg_pop_perm(h, self.perm_seed, self.updates, P, K, sizes[0], E, C.c_void_p(out.data_ptr()), self._stream()),
-                    h, "ssg_pop_perm")
+        op = N.arg(out, torch.int64, shape, "PopulationPPO.draw_perm: out", dev)
+        self.env.enqueue("ssg_pop_perm", self.perm_seed, self.updates, P, K, sizes[0], E, op)
         return out
 
     def update(self, batch, perm, epochs, minibatches, stats=False):
@@ -511,9 +494,10 @@ class PopulationPPO(DeviceTrainer):
                 raise ValueError("PopulationPPO.update: %d epochs and %d minibatches for %d members" % (len(epochs), len(minibatches), P))
             if min(epochs) < 1 or min(minibatches) < 1:
                 raise ValueError("PopulationPPO.update: every member's epochs and minibatches must be >= 1")
-        p = [self._flat(batch, "obs", torch.float32, (K, n_env, D)), self._flat(batch, "act", torch.int32, (K, n_env)),
-             self._flat(batch, "logp", torch.float32, (K, n_env)), self._flat(batch, "adv", torch.float32, (K, n_env)),
-             self._flat(batch, "ret", torch.float32, (K, n_env))]
+        who = "PopulationPPO.update"
+        p = [self._flat(batch, "obs", torch.float32, (K, n_env, D), who), self._flat(batch, "act", torch.int32, (K, n_env), who),
+             self._flat(batch, "logp", torch.float32, (K, n_env), who), self._flat(batch, "adv", torch.float32, (K, n_env), who),
+             self._flat(batch, "ret", torch.float32, (K, n_env), who)]
         if sliced and isinstance(perm, (list, tuple)):
             if len(perm) != P or any(tuple(q.shape) != (max(epochs), n[m]) for m, q in enumerate(perm)):
                 raise ValueError("PopulationPPO.update: perm must list %d tensors int64 [max(epochs) = %d, K*n_m] with K*n_m = %s"
@@ -545,24 +529,18 @@ class PopulationPPO(DeviceTrainer):
         st = None
         if stats:
             st = (torch.zeros if sched else torch.empty)((P, launches, N.PPO_EXT_STATS if extended else 4), dtype=torch.float32, device=dev)
-        pop, h = self.population.to_native(), self.env._h
         self._bind_adv_norm()
-        with torch.cuda.device(dev):
-            table = self._table(launches, table_steps0)
-            if sched:
-                dev_sched = torch.frombuffer(table_sched, dtype=torch.int32).to(dev)  # (a copy: the host array is free after the call)
-            ext, ext_table = self._ext(batch, K, n_env) if extended else (None, None)
-            if sched:
-                name = "ssg_pop_update_sched"
-                args = (C.byref(ext) if extended else None, C.c_void_p(table.data_ptr()), launches, C.c_void_p(dev_sched.data_ptr()),
-                        (C.c_int32 * P)(*epochs), (C.c_int32 * P)(*minibatches), max(epochs), K, *p, C.c_void_p(perm.data_ptr()))
-            else:
-                name = "ssg_pop_update_ext" if extended else "ssg_pop_update"
-                args = ((C.byref(ext),) if extended else ()) + (C.c_void_p(table.data_ptr()), launches, K, *p, C.c_void_p(perm.data_ptr()),
-                                                                 int(epochs), int(minibatches))
-            N.check(getattr(N.lib(), name)(h, C.byref(pop), *args, C.c_void_p(self.adam_mv.data_ptr()),
-                                           C.c_void_p(st.data_ptr()) if stats else None, C.c_void_p(self.workspace.data_ptr()),
-                                           self.workspace.numel(), self._stream()), h, name)
+        table = self._table(launches, table_steps0)
+        ext, ext_table = self._ext(batch, K, n_env) if extended else (None, None)  # (ext_table: kept alive until the call is enqueued)
+        if sched:
+            dev_sched = torch.frombuffer(table_sched, dtype=torch.int32).to(dev)  # (a copy: the host array is free after the call)
+            name = "ssg_pop_update_sched"
+            args = (C.byref(ext) if extended else None, table.data_ptr(), launches, dev_sched.data_ptr(), (C.c_int32 * P)(*epochs),
+                    (C.c_int32 * P)(*minibatches), max(epochs), K, *p, perm.data_ptr())
+        else:
+            name = "ssg_pop_update_ext" if extended else "ssg_pop_update"
+            args = ((C.byref(ext),) if extended else ()) + (table.data_ptr(), launches, K, *p, perm.data_ptr(), int(epochs), int(minibatches))
+        self.env.enqueue(name, C.byref(self.population.to_native()), *args, self.adam_mv.data_ptr(), N.ptr(st), *self._ws_ptr())
         self._advance(steps0, taken)
         self._last_taken = [int(t) for t in taken]  # (report(): the rows of `st` each member wrote)
         return st
@@ -580,33 +558,26 @@ class PopulationPPO(DeviceTrainer):
         torch = _torch()
         from . import report as R
         K, n_env = self._KN(batch)
-        P, dev, D = self.n_members, self.population.device, self.population.obs_dim
-        p = [self._flat(batch, k, torch.float32, (K, n_env)) for k in ("val", "ret", "adv")]
+        P, dev, D, who = self.n_members, self.population.device, self.population.obs_dim, "PopulationPPO.report"
+        p = [self._flat(batch, k, torch.float32, (K, n_env), who) for k in ("val", "ret", "adv")]
         grp = (None, None, None, None)
         if post:
-            act, logp = self._flat(batch, "act", torch.int32, (K, n_env)), self._flat(batch, "logp", torch.float32, (K, n_env))
-            self._flat(batch, "obs", torch.float32, (K, n_env, D))
+            act, logp = self._flat(batch, "act", torch.int32, (K, n_env), who), self._flat(batch, "logp", torch.float32, (K, n_env), who)
+            self._flat(batch, "obs", torch.float32, (K, n_env, D), who)
             new = self.dist({"rew": batch["rew"], "obs": batch["obs"]})  # (a dict of its own: the batch's logp_all stays the acting policy's)
             bounds = torch.tensor([[float(x) for x in R.clip_bounds(c)] for c in self.clip], dtype=torch.float32).to(dev)
-            grp = (act, logp, C.c_void_p(new.data_ptr()), C.c_void_p(bounds.data_ptr()))
-        sp = rp = None
+            grp = (act, logp, new.data_ptr(), bounds.data_ptr())
+        sp = rows = None
         rows_max = cols = 0
         if stats is not None:
-            if stats.dtype != torch.float32 or stats.device != dev or not stats.is_contiguous() or stats.dim() != 3 or int(stats.shape[0]) != P:
-                raise ValueError("PopulationPPO.report: stats must be a contiguous f32 [%d, rows, 4 or 8] tensor on %s (update(..., stats=True))"
-                                 % (P, dev))
-            rows_max, cols, sp = int(stats.shape[1]), int(stats.shape[2]), C.c_void_p(stats.data_ptr())
+            if stats.dim() != 3:
+                raise ValueError("PopulationPPO.report: stats must be [%d, rows, 4 or 8] (update(..., stats=True); got %s)" % (P, tuple(stats.shape)))
+            sp = N.arg(stats, torch.float32, (P,) + tuple(stats.shape[1:]), "PopulationPPO.report: stats", dev)  # (P is what is judged)
+            rows_max, cols = int(stats.shape[1]), int(stats.shape[2])
             taken = self._last_taken or [rows_max] * P
             rows = torch.tensor([min(int(t), rows_max) for t in taken], dtype=torch.int32).to(dev)
-            rp = C.c_void_p(rows.data_ptr())
-        need = R.scratch_nbytes(n_env, P)
-        if getattr(self, "_report_scratch", None) is None or self._report_scratch.numel() < need:
-            self._report_scratch = torch.zeros(need, dtype=torch.uint8, device=dev)
         out = torch.empty((P, N.REPORT_COLS), dtype=torch.float64, device=dev)
-        h = self.env._h
-        with torch.cuda.device(dev):
-            N.check(N.lib().ssg_pop_report(h, P, K, *p, *grp, sp, rows_max, cols, rp, C.c_void_p(self._report_scratch.data_ptr()),
-                                           self._report_scratch.numel(), C.c_void_p(out.data_ptr()), self._stream()), h, "ssg_pop_report")
+        self.env.enqueue("ssg_pop_report", P, K, *p, *grp, sp, rows_max, cols, N.ptr(rows), *self._report_ws(n_env, P), out.data_ptr())
         return out
 
     def report(self, batch, stats=None, post=False):
@@ -635,14 +606,12 @@ class PopulationPPO(DeviceTrainer):
         if len(src) != self.n_members:
             raise ValueError("PopulationPPO.exploit: src has %d entries for %d members" % (len(src), self.n_members))
         arr = (C.c_int32 * len(src))(*src)
-        pop, h = self.population.to_native(), self.env._h
         flt = getattr(self.env, "obs_filter", None)
         if flt is not None and flt.n_members != self.n_members:  # (judged before anything is copied)
             raise ValueError("PopulationPPO.exploit: the env's observation filter has %d members, the population %d"
                              % (flt.n_members, self.n_members))
+        self.env.enqueue("ssg_pop_exploit", C.byref(self.population.to_native()), arr, self.adam_mv.data_ptr())
         with torch.cuda.device(self.population.device):
-            N.check(N.lib().ssg_pop_exploit(h, C.byref(pop), arr, C.c_void_p(self.adam_mv.data_ptr()), self._stream()), h,
-                    "ssg_pop_exploit")
             self.kl_coef.copy_(self.kl_coef[torch.tensor(src, device=self.population.device)])
             if flt is not None:  # (an indexed copy on the handle's stream; the gather is materialised before the copy writes)
                 flt.state.copy_(flt.state[torch.tensor(src, device=flt.state.device)])
@@ -663,14 +632,11 @@ class PopulationPPO(DeviceTrainer):
         re-slice an episode in flight is credited to whichever member owns the env when it ends."""
         torch = _torch()
         K, n_env = self._KN(batch)
-        dev = self.population.device
-        rew, done = self._flat(batch, "rew", torch.float64, (K, n_env)), self._flat(batch, "done", torch.uint8, (K, n_env))
-        out = torch.zeros((self.n_members, 3), dtype=torch.int64, device=dev)
-        h = self.env._h
-        with torch.cuda.device(dev):
-            N.check(N.lib().ssg_pop_episode_stats(h, self.n_members, K, rew, done, C.c_void_p(self.carry_return.data_ptr()),
-                                                  C.c_void_p(self.carry_length.data_ptr()), C.c_void_p(out.data_ptr()), self._stream()),
-                    h, "ssg_pop_episode_stats")
+        who = "PopulationPPO.episode_stats"
+        rew, done = self._flat(batch, "rew", torch.float64, (K, n_env), who), self._flat(batch, "done", torch.uint8, (K, n_env), who)
+        out = torch.zeros((self.n_members, 3), dtype=torch.int64, device=self.population.device)
+        self.env.enqueue("ssg_pop_episode_stats", self.n_members, K, rew, done, self.carry_return.data_ptr(), self.carry_length.data_ptr(),
+                         out.data_ptr())
         return out
 
     # ------------------------------------------------------------------------------------------------

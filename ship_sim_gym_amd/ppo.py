@@ -47,11 +47,7 @@ import ctypes as C
 
 from . import _native as N
 from . import hparam_schedule as HS
-
-
-def _torch():
-    import torch
-    return torch
+from ._native import _torch
 
 
 def chunk_split(n, minibatches):
@@ -74,9 +70,7 @@ def adv_norm_mode(name, who):
 
 def adv_norm_scratch(n_members, device):
     """A zeroed scratch tensor of ssg_ppo_adv_norm_nbytes(n_members) bytes (torch's allocations are 256-byte aligned)."""
-    need = C.c_size_t()
-    N.check(N.lib().ssg_ppo_adv_norm_nbytes(int(n_members), C.byref(need)), None, "ssg_ppo_adv_norm_nbytes")
-    return _torch().zeros(need.value, dtype=_torch().uint8, device=device)
+    return _torch().zeros(N.nbytes("ssg_ppo_adv_norm_nbytes", int(n_members)), dtype=_torch().uint8, device=device)
 
 
 def adv_norm_views(scratch, n_members):
@@ -269,8 +263,8 @@ def host_perm(seed, update, member, epoch, n, first=0, count=None):
     import numpy as np
     count = int(n) - int(first) if count is None else int(count)
     out = np.empty(max(count, 1), dtype=np.int64)
-    N.check(N.lib().ssg_host_perm(int(seed), int(update), int(member), int(epoch), int(n), int(first), count,
-                                  out.ctypes.data_as(C.POINTER(C.c_int64))), None, "ssg_host_perm")
+    N.call("ssg_host_perm", int(seed), int(update), int(member), int(epoch), int(n), int(first), count,
+           out.ctypes.data_as(C.POINTER(C.c_int64)))
     return out[:count]
 
 
@@ -298,22 +292,43 @@ def _schedules_from_state(who, sd):
             HS.check_clock(who, sd["timesteps"]))
 
 
+def same_device(who, record, env):
+    """ValueError unless the policy's or population's tensors live on the env's device.  The env's calls make the ENV's device current:
+    a record on another card would pass the library's check of the current device and have its pointers read on the wrong one."""
+    if record.params.device != env.device or record.obs_scale.device != env.device:
+        raise ValueError("%s: the policy lives on %s, the env on %s" % (who, record.params.device, env.device))
+
+
 class DeviceTrainer(object):
-    """What NativePPO and PopulationPPO share: ``workspace`` on ``_device``, its growth and the current stream."""
+    """What NativePPO and PopulationPPO share: ``workspace`` and the report's scratch on ``_device`` (the env's: same_device), their
+    growth and the current stream."""
+    _report_scratch = None
 
     def _grow(self, query, record, n_samples, max_minibatch, head):
         """The workspace, grown to what `query` asks for the record and the sizes; its first `head` bytes (gae()'s statistics) are kept."""
-        need = C.c_size_t()
-        N.check(getattr(N.lib(), query)(C.byref(record), int(n_samples), int(max_minibatch), C.byref(need)), None, query)
-        if self.workspace.numel() < need.value:
-            ws = _torch().zeros(need.value + 256, dtype=_torch().uint8, device=self._device)
+        need = N.nbytes(query, C.byref(record), int(n_samples), int(max_minibatch))
+        if self.workspace.numel() < need:
+            ws = _torch().zeros(need + 256, dtype=_torch().uint8, device=self._device)
             if self.workspace.numel():
                 ws[:head].copy_(self.workspace[:head])
             self.workspace = ws
         return self.workspace
 
+    def _ws_ptr(self):
+        # (torch's allocations are 256-byte aligned; the header requires it)
+        return self.workspace.data_ptr(), self.workspace.numel()
+
+    def _report_ws(self, n_env, n_members):
+        """(address, bytes) of the update report's scratch, grown to serve n_env envs and n_members members."""
+        from .report import scratch_nbytes
+        need = scratch_nbytes(n_env, n_members)
+        if self._report_scratch is None or self._report_scratch.numel() < need:
+            self._report_scratch = _torch().zeros(need, dtype=_torch().uint8, device=self._device)
+        return self._report_scratch.data_ptr(), self._report_scratch.numel()
+
     def _stream(self):
-        return C.c_void_p(_torch().cuda.current_stream(self._device).cuda_stream)
+        """The current stream's handle on the trainer's device, a plain integer."""
+        return _torch().cuda.current_stream(self._device).cuda_stream
 
 
 class NativePPO(DeviceTrainer):
@@ -322,6 +337,7 @@ class NativePPO(DeviceTrainer):
     def __init__(self, policy, env, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, clip=0.2, vf_coef=0.5, ent_coef=0.01, adv_eps=1e-8,
                  vf_clip=0.0, max_grad_norm=0.0, kl_coef=0.0, kl_target=0.0, adv_norm="batch", perm_seed=None, member=0):
         torch = _torch()
+        same_device("NativePPO", policy, env)  # (first: a refused construction has touched nothing)
         self.policy, self.env, self._device = policy, env, policy.device
         # the key of the permutations the library draws (draw_perm; update(perm=None)): the seed (None: the caller brings every perm),
         # the member this object stands for (a population member's twin passes its index) and the update() calls so far
@@ -370,26 +386,19 @@ class NativePPO(DeviceTrainer):
         statistics ssg_ppo_gae left — are kept when it grows)."""
         return self._grow("ssg_ppo_workspace_nbytes", self.policy.to_native(), n_samples, max_minibatch, 16)
 
-    def _ws_ptr(self):
-        # (torch's allocations are 256-byte aligned; the header requires it)
-        return C.c_void_p(self.workspace.data_ptr()), self.workspace.numel()
-
-    def _flat(self, batch, key, dtype):
+    def _flat(self, batch, key, dtype, shape=None, who="NativePPO"):
+        """batch[key], checked (N.arg) as `dtype`, contiguous, on the device and of `shape` — an int: that many entries in any shape;
+        a tuple: that shape; None: whatever it holds."""
         t = batch[key]
-        if t.dtype != dtype or t.device != self.policy.device or not t.is_contiguous():
-            raise ValueError("NativePPO: batch[%r] must be a contiguous %s tensor on %s (got %s on %s)" % (key, dtype, self.policy.device, t.dtype, t.device))
+        N.arg(t, dtype, t.numel() if shape is None else shape, "%s: batch[%r]" % (who, key), self._device)
         return t
 
     def _samples(self, batch):
+        """(n, the addresses of obs, act, logp, adv, ret): the batch's n samples, every entry holding n of them in any shape."""
         torch = _torch()
-        x = self._flat(batch, "obs", torch.float32)
-        n = x.numel() // self.policy.obs_dim
-        ptrs = [C.c_void_p(self._flat(batch, k, dt).data_ptr()) for k, dt in
-                (("obs", torch.float32), ("act", torch.int32), ("logp", torch.float32), ("adv", torch.float32), ("ret", torch.float32))]
-        for k in ("act", "logp", "adv", "ret"):
-            if batch[k].numel() != n:
-                raise ValueError("NativePPO: batch[%r] has %d entries, the batch %d samples" % (k, batch[k].numel(), n))
-        return n, ptrs
+        n = self._flat(batch, "obs", torch.float32).numel() // self.policy.obs_dim
+        return n, [batch["obs"].data_ptr()] + [self._flat(batch, k, dt, n).data_ptr() for k, dt in
+                                               (("act", torch.int32), ("logp", torch.float32), ("adv", torch.float32), ("ret", torch.float32))]
 
     def extended(self):
         """True when any of the extended terms is on: grad / update then go through the _ext entry points."""
@@ -402,10 +411,7 @@ class NativePPO(DeviceTrainer):
         x = self._flat(batch, "obs", torch.float32)
         n = x.numel() // self.policy.obs_dim
         out = torch.empty(tuple(x.shape[:-1]) + (4,), dtype=torch.float32, device=self.policy.device)
-        pol, h = self.policy.to_native(), self.env._h
-        with torch.cuda.device(self.policy.device):
-            N.check(N.lib().ssg_ppo_dist(h, C.byref(pol), n, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), self._stream()), h,
-                    "ssg_ppo_dist")
+        self.env.enqueue("ssg_ppo_dist", C.byref(self.policy.to_native()), n, x.data_ptr(), out.data_ptr())
         batch["logp_all"] = out
         return out
 
@@ -418,28 +424,19 @@ class NativePPO(DeviceTrainer):
         if self._kl_on:
             if "logp_all" not in batch:
                 self.dist(batch)
-            la = self._flat(batch, "logp_all", torch.float32)
-            if la.numel() != 4 * n:
-                raise ValueError("NativePPO: batch['logp_all'] has %d entries, the batch %d samples x 4" % (la.numel(), n))
-            ext.dev_kl_coef, ext.dev_logp_all = self.kl_coef.data_ptr(), la.data_ptr()
+            ext.dev_kl_coef, ext.dev_logp_all = self.kl_coef.data_ptr(), self._flat(batch, "logp_all", torch.float32, 4 * n).data_ptr()
         if self.vf_clip > 0.0:
-            val = self._flat(batch, "val", torch.float32)
-            if val.numel() != n:
-                raise ValueError("NativePPO: batch['val'] has %d entries, the batch %d samples" % (val.numel(), n))
-            ext.dev_value_old = val.data_ptr()
+            ext.dev_value_old = self._flat(batch, "val", torch.float32, n).data_ptr()
         return ext
 
     def _call(self, name, batch, n, *args):
         """The gradient / update entry point `name` or, with an extended term on, its _ext form, which takes the ssg_ppo_ext record
         behind the hyper-parameters; args: what the entry point takes between n and the workspace."""
-        ws, nb = self._ws_ptr()
-        pol, h = self.policy.to_native(), self.env._h
         self._bind_adv_norm()
-        with _torch().cuda.device(self.policy.device):
-            ext = ()
-            if self.extended():
-                name, ext = name + "_ext", (C.byref(self._ext(batch, n)),)
-            N.check(getattr(N.lib(), name)(h, C.byref(pol), C.byref(self.hp), *ext, n, *args, ws, nb, self._stream()), h, name)
+        ext = ()
+        if self.extended():
+            name, ext = name + "_ext", (C.byref(self._ext(batch, n)),)
+        self.env.enqueue(name, C.byref(self.policy.to_native()), C.byref(self.hp), *ext, n, *args, *self._ws_ptr())
 
     # ------------------------------------------------------------------------------------------------
     def gae(self, batch, gamma=0.99, lam=0.95, return_filter=None):
@@ -451,27 +448,20 @@ class NativePPO(DeviceTrainer):
         torch = _torch()
         if return_filter is not None:
             self._apply_return_filter(return_filter, batch)
-        rew, done, val, last = (self._flat(batch, "rew" if return_filter is None else "rew_norm", torch.float64), self._flat(batch, "done", torch.uint8),
-                                self._flat(batch, "val", torch.float32), self._flat(batch, "last_val", torch.float32))
+        who = "NativePPO.gae"
+        rew = self._flat(batch, "rew" if return_filter is None else "rew_norm", torch.float64, who=who)  # (its first two dimensions are K and N)
         K, n_env = int(rew.shape[0]), int(rew.shape[1])
-        if tuple(done.shape) != (K, n_env) or tuple(val.shape) != (K, n_env) or tuple(last.shape) != (n_env,):
-            raise ValueError("NativePPO.gae: rew / done / val must be [K, N] and last_val [N]")
+        p = [rew.data_ptr()] + [self._flat(batch, k, dt, shape, who).data_ptr() for k, dt, shape in
+                                (("done", torch.uint8, (K, n_env)), ("val", torch.float32, (K, n_env)), ("last_val", torch.float32, (n_env,)))]
         self.hp.gamma, self.hp.lam = float(gamma), float(lam)
         self._ws(K * n_env, 1)
         adv = torch.empty((K, n_env), dtype=torch.float32, device=self.policy.device)
         ret = torch.empty_like(adv)
-        ws, nb = self._ws_ptr()
-        h = self.env._h
-        name, boot = "ssg_ppo_gae", ()
+        name = "ssg_ppo_gae"
         if "boot" in batch:
-            bt = self._flat(batch, "boot", torch.float32)
-            if tuple(bt.shape) != (K, n_env):
-                raise ValueError("NativePPO.gae: batch['boot'] must be [K, N]")
-            name, boot = "ssg_ppo_gae_boot", (C.c_void_p(bt.data_ptr()),)
-        with torch.cuda.device(self.policy.device):
-            N.check(getattr(N.lib(), name)(h, C.byref(self.hp), K, n_env, C.c_void_p(rew.data_ptr()), C.c_void_p(done.data_ptr()),
-                                           C.c_void_p(val.data_ptr()), C.c_void_p(last.data_ptr()), *boot, C.c_void_p(adv.data_ptr()),
-                                           C.c_void_p(ret.data_ptr()), ws, nb, self._stream()), h, name)
+            p.append(self._flat(batch, "boot", torch.float32, (K, n_env), who).data_ptr())
+            name = "ssg_ppo_gae_boot"
+        self.env.enqueue(name, C.byref(self.hp), K, n_env, *p, adv.data_ptr(), ret.data_ptr(), *self._ws_ptr())
         batch["adv"], batch["ret"] = adv, ret
         return adv, ret
 
@@ -513,8 +503,7 @@ class NativePPO(DeviceTrainer):
         g = torch.empty(self.n_params, dtype=torch.float32, device=self.policy.device)
         ncol = N.PPO_EXT_STATS if self.extended() else 4
         st = torch.empty(ncol, dtype=torch.float32, device=self.policy.device) if stats else None
-        self._call("ssg_ppo_grad", batch, n, *p, C.c_void_p(idx.data_ptr()), M, C.c_void_p(g.data_ptr()),
-                   C.c_void_p(st.data_ptr()) if stats else None)
+        self._call("ssg_ppo_grad", batch, n, *p, idx.data_ptr(), M, g.data_ptr(), N.ptr(st))
         return (g, st) if stats else g
 
     def adam_step(self, grad):
@@ -523,10 +512,7 @@ class NativePPO(DeviceTrainer):
         grad = grad.to(device=self.policy.device, dtype=torch.float32).contiguous()
         if grad.numel() != self.n_params:
             raise ValueError("NativePPO.adam_step: gradient of %d entries, the policy has %d" % (grad.numel(), self.n_params))
-        pol, h = self.policy.to_native(), self.env._h
-        with torch.cuda.device(self.policy.device):
-            N.check(N.lib().ssg_ppo_adam(h, C.byref(pol), C.byref(self.hp), C.c_void_p(grad.data_ptr()), C.c_void_p(self.adam_mv.data_ptr()),
-                                         self.step + 1, self._stream()), h, "ssg_ppo_adam")
+        self.env.enqueue("ssg_ppo_adam", C.byref(self.policy.to_native()), C.byref(self.hp), grad.data_ptr(), self.adam_mv.data_ptr(), self.step + 1)
         self.step += 1
 
     def draw_perm(self, batch_or_n, epochs, out=None):
@@ -539,12 +525,8 @@ class NativePPO(DeviceTrainer):
         n = int(batch_or_n) if not isinstance(batch_or_n, dict) else batch_or_n["obs"].numel() // self.policy.obs_dim
         if out is None:
             out = torch.empty((int(epochs), n), dtype=torch.int64, device=self.policy.device)
-        if out.dtype != torch.int64 or out.device != self.policy.device or not out.is_contiguous() or tuple(out.shape) != (int(epochs), n):
-            raise ValueError("NativePPO.draw_perm: out must be a contiguous int64 [%d, %d] tensor on %s" % (int(epochs), n, self.policy.device))
-        h = self.env._h
-        with torch.cuda.device(self.policy.device):
-            N.check(N.lib().ssg_ppo_perm(h, self.perm_seed, self.updates, self.member, int(epochs), n, C.c_void_p(out.data_ptr()),
-                                         self._stream()), h, "ssg_ppo_perm")
+        op = N.arg(out, torch.int64, (int(epochs), n), "NativePPO.draw_perm: out", self._device)
+        self.env.enqueue("ssg_ppo_perm", self.perm_seed, self.updates, self.member, int(epochs), n, op)
         return out
 
     def update(self, batch, perm, epochs, minibatches, stats=False):
@@ -565,8 +547,7 @@ class NativePPO(DeviceTrainer):
         self._ws(n, chunk)
         ncol = N.PPO_EXT_STATS if self.extended() else 4
         st = torch.empty((int(epochs) * n_chunks, ncol), dtype=torch.float32, device=self.policy.device) if stats else None
-        self._call("ssg_ppo_update", batch, n, *p, C.c_void_p(perm.data_ptr()), int(epochs), int(minibatches),
-                   C.c_void_p(self.adam_mv.data_ptr()), self.step, C.c_void_p(st.data_ptr()) if stats else None)
+        self._call("ssg_ppo_update", batch, n, *p, perm.data_ptr(), int(epochs), int(minibatches), self.adam_mv.data_ptr(), self.step, N.ptr(st))
         self.step += int(epochs) * n_chunks
         self.updates += 1
         return st
@@ -582,36 +563,31 @@ class NativePPO(DeviceTrainer):
         """What ssg_ppo_report and ssg_ppo_report_sums walk: (K, n_env, the three buffers' pointers, the post-update group's three or
         Nones, the scratch pointer and size).  post: one ssg_ppo_dist launch into a tensor of its own."""
         torch = _torch()
-        from . import report as R
-        dev = self.policy.device
-        val, ret, adv = (self._flat(batch, k, torch.float32) for k in ("val", "ret", "adv"))
-        if val.dim() != 2 or ret.shape != val.shape or adv.shape != val.shape:
-            raise ValueError("NativePPO.report: batch['val'], ['ret'] and ['adv'] must be [K, N] (gae() adds the last two)")
+        who = "NativePPO.report"
+        val = self._flat(batch, "val", torch.float32, who=who)
+        if val.dim() != 2:
+            raise ValueError("NativePPO.report: batch['val'] must be [K, N] (got %s)" % (tuple(val.shape),))
         K, n_env = int(val.shape[0]), int(val.shape[1])
+        bufs = (val.data_ptr(), self._flat(batch, "ret", torch.float32, (K, n_env), who).data_ptr(),
+                self._flat(batch, "adv", torch.float32, (K, n_env), who).data_ptr())
         grp = (None, None, None)
         if post:
-            act, logp = self._flat(batch, "act", torch.int32), self._flat(batch, "logp", torch.float32)
-            if act.numel() != K * n_env or logp.numel() != K * n_env:
-                raise ValueError("NativePPO.report: batch['act'] and ['logp'] must hold K*N entries")
+            act, logp = self._flat(batch, "act", torch.int32, K * n_env, who), self._flat(batch, "logp", torch.float32, K * n_env, who)
             # the CURRENT parameters' distribution, in a tensor of its own: batch["logp_all"] is the acting policy's and stays
             own = {"obs": batch["obs"]}
             new = self.dist(own)
-            grp = (C.c_void_p(act.data_ptr()), C.c_void_p(logp.data_ptr()), C.c_void_p(new.data_ptr()))
-        need = R.scratch_nbytes(n_env, 1)
-        if getattr(self, "_report_scratch", None) is None or self._report_scratch.numel() < need:
-            self._report_scratch = torch.zeros(need, dtype=torch.uint8, device=dev)
-        bufs = (C.c_void_p(val.data_ptr()), C.c_void_p(ret.data_ptr()), C.c_void_p(adv.data_ptr()))
-        return K, n_env, bufs, grp, (C.c_void_p(self._report_scratch.data_ptr()), self._report_scratch.numel())
+            grp = (act.data_ptr(), logp.data_ptr(), new.data_ptr())
+        return K, n_env, bufs, grp, self._report_ws(n_env, 1)
 
     def _report_stats(self, stats, who):
-        """(pointer or None, rows, columns) of the stats rows update(..., stats=True) returned."""
-        torch = _torch()
-        dev = self.policy.device
+        """(address or None, rows, columns) of the stats rows update(..., stats=True) returned: f32 [rows, 4 or 8] (the library judges
+        the columns)."""
         if stats is None:
             return None, 0, 0
-        if stats.dtype != torch.float32 or stats.device != dev or not stats.is_contiguous() or stats.dim() != 2:
-            raise ValueError("NativePPO.%s: stats must be a contiguous f32 [rows, 4 or 8] tensor on %s (update(..., stats=True))" % (who, dev))
-        return C.c_void_p(stats.data_ptr()), int(stats.shape[0]), int(stats.shape[1])
+        if stats.dim() != 2:
+            raise ValueError("NativePPO.%s: stats must be [rows, 4 or 8] (update(..., stats=True); got %s)" % (who, tuple(stats.shape)))
+        sp = N.arg(stats, _torch().float32, (0, stats.shape[1]), "NativePPO.%s: stats" % who, self._device, more_rows=True)
+        return sp, int(stats.shape[0]), int(stats.shape[1])
 
     def _report(self, batch, stats, post):
         """f64 [25] on the device: ssg_ppo_report's record, then the KL coefficient as it is now.  Enqueued only: no synchronisation."""
@@ -620,11 +596,8 @@ class NativePPO(DeviceTrainer):
         K, n_env, bufs, grp, scratch = self._report_inputs(batch, post)
         sp, rows, cols = self._report_stats(stats, "report")
         out = torch.empty(N.REPORT_COLS + 1, dtype=torch.float64, device=dev)
-        h = self.env._h
-        with torch.cuda.device(dev):
-            N.check(N.lib().ssg_ppo_report(h, K, n_env, *bufs, *grp, float(self.hp.clip), sp, rows, cols, *scratch,
-                                           C.c_void_p(out.data_ptr()), self._stream()), h, "ssg_ppo_report")
-            out[N.REPORT_COLS:].copy_(self.kl_coef)
+        self.env.enqueue("ssg_ppo_report", K, n_env, *bufs, *grp, float(self.hp.clip), sp, rows, cols, *scratch, out.data_ptr())
+        out[N.REPORT_COLS:].copy_(self.kl_coef)
         return out
 
     def report_device(self, batch, stats=None, post=False):
@@ -653,10 +626,7 @@ class NativePPO(DeviceTrainer):
         dev = self.policy.device
         K, n_env, bufs, grp, scratch = self._report_inputs(batch, post)
         row = torch.empty(N.REPORT_ROW_COLS, dtype=torch.float64, device=dev)
-        h = self.env._h
-        with torch.cuda.device(dev):
-            N.check(N.lib().ssg_ppo_report_sums(h, K, n_env, *bufs, *grp, float(self.hp.clip), *scratch, C.c_void_p(row.data_ptr()),
-                                                self._stream()), h, "ssg_ppo_report_sums")
+        self.env.enqueue("ssg_ppo_report_sums", K, n_env, *bufs, *grp, float(self.hp.clip), *scratch, row.data_ptr())
         return row
 
     def report_rows(self, rows, stats=None, per_shard=False):
@@ -666,15 +636,11 @@ class NativePPO(DeviceTrainer):
         torch = _torch()
         dev = self.policy.device
         rows = rows.to(device=dev, dtype=torch.float64).contiguous()
-        if rows.dim() != 2 or rows.shape[1] != N.REPORT_ROW_COLS:
-            raise ValueError("NativePPO.report_rows: rows must be f64 [W, %d] (got %s)" % (N.REPORT_ROW_COLS, tuple(rows.shape)))
+        rp = N.arg(rows, torch.float64, (0, N.REPORT_ROW_COLS), "NativePPO.report_rows: rows", dev, more_rows=True)
         W = int(rows.shape[0])
         sp, n_stat, cols = self._report_stats(stats, "report_rows")
         out = torch.empty((1 + W if per_shard else 1, N.REPORT_COLS), dtype=torch.float64, device=dev)
-        h = self.env._h
-        with torch.cuda.device(dev):
-            N.check(N.lib().ssg_ppo_report_rows(h, W, C.c_void_p(rows.data_ptr()), sp, n_stat, cols, int(bool(per_shard)),
-                                                C.c_void_p(out.data_ptr()), self._stream()), h, "ssg_ppo_report_rows")
+        self.env.enqueue("ssg_ppo_report_rows", W, rp, sp, n_stat, cols, int(bool(per_shard)), out.data_ptr())
         return out if per_shard else out[0]
 
     def job_report(self, batch, stats=None, post=False, group=None, per_shard=False):

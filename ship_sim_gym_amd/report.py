@@ -45,7 +45,7 @@ def clip_bounds(clip):
     """ssg_report_clip_bounds: (lo, hi) as np.float32 — (float)log1p(-clip), -inf from clip 1 on, and (float)log1p(clip), formed in
     double by the library, so that the host and the device compare against the same bits."""
     out = (C.c_float * 2)()
-    N.check(N.lib().ssg_report_clip_bounds(float(clip), out), None, "ssg_report_clip_bounds")
+    N.call("ssg_report_clip_bounds", float(clip), out)
     return np.float32(out[0]), np.float32(out[1])
 
 
@@ -174,9 +174,7 @@ def record_dict(row):
 
 def scratch_nbytes(n_envs, n_members=1):
     """ssg_ppo_report_workspace_nbytes."""
-    need = C.c_size_t()
-    N.check(N.lib().ssg_ppo_report_workspace_nbytes(int(n_envs), int(n_members), C.byref(need)), None, "ssg_ppo_report_workspace_nbytes")
-    return need.value
+    return N.nbytes("ssg_ppo_report_workspace_nbytes", int(n_envs), int(n_members))
 
 
 class ProgressWriter(object):

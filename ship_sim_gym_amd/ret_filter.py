@@ -26,12 +26,8 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
+from ._native import _torch
 from .obs_filter import _merge, merge_reference
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def _denom(state_rows):
@@ -195,12 +191,9 @@ class ReturnFilter(object):
         return self
 
     def _ws(self, K):
-        torch = _torch()
-        need = C.c_size_t()
-        N.check(N.lib().ssg_ret_filter_workspace_nbytes(int(self.env.num_envs), int(K), self.n_members, C.byref(need)), None,
-                "ssg_ret_filter_workspace_nbytes")
-        if self.workspace.numel() < need.value:
-            self.workspace = torch.zeros(need.value, dtype=torch.uint8, device=self.state.device)
+        need = N.nbytes("ssg_ret_filter_workspace_nbytes", int(self.env.num_envs), int(K), self.n_members)
+        if self.workspace.numel() < need:
+            self.workspace = _torch().zeros(need, dtype=_torch().uint8, device=self.state.device)
         return self.workspace
 
     def to_native(self, K=1):
@@ -214,6 +207,30 @@ class ReturnFilter(object):
         rec.dev_workspace, rec.workspace_nbytes = ws.data_ptr(), ws.numel()
         return rec
 
+    def _rows(self, who, rew, done=None):
+        """THE check of a call's [K, N] buffers, (K, row pitch): rew f64 / done u8 (None: not taken) in the env's row layout, on its
+        device, rows of unit stride and a common row pitch >= N — strided on purpose, so that [:, :N] views of wider buffers serve."""
+        torch = _torch()
+        env = self.env
+        n_env = int(env.num_envs)
+        for name, t, dt in (("rew", rew, torch.float64), ("done", done, torch.uint8)):
+            if t is None:
+                continue
+            if t.dtype != dt or t.device != env.device or t.dim() != 2 or int(t.shape[1]) != n_env or int(t.shape[0]) < 1 or \
+                    t.stride(1) != 1 or t.stride(0) < n_env:
+                raise ValueError("%s: %s must be a %s tensor [K, %d] on %s with unit-stride rows (got %s %s, strides %s, on %s)"
+                                 % (who, name, dt, n_env, env.device, t.dtype, tuple(t.shape), tuple(t.stride()), t.device))
+        K, pitch = int(rew.shape[0]), int(rew.stride(0))
+        if done is not None and (int(done.shape[0]) != K or int(done.stride(0)) != pitch):
+            raise ValueError("%s: rew and done must have the same number of rows and the same row pitch" % who)
+        return K, pitch
+
+    def _pieces(self, K, call):
+        """Serve K steps in pieces of the library's cap: call(record, k0, k1) for each piece [k0, k1); they leave what one call would."""
+        rec = self.to_native(min(K, N.RET_FILTER_MAX_STEPS))
+        for k0 in range(0, K, N.RET_FILTER_MAX_STEPS):
+            call(C.byref(rec), k0, min(K, k0 + N.RET_FILTER_MAX_STEPS))
+
     def normalise(self, rew, done):
         """ssg_ret_filter_apply on a rollout's buffers: rew f64 / done u8 [K, N] in the env's row layout, rows of unit stride and a
         common row pitch >= N (so [:, :N] views of wider buffers serve).  Returns (out, denom): out f64 [K, N] with rew's row pitch,
@@ -221,63 +238,31 @@ class ReturnFilter(object):
         leave what one call would."""
         torch = _torch()
         env = self.env
-        n_env = int(env.num_envs)
-        for name, t, dt in (("rew", rew, torch.float64), ("done", done, torch.uint8)):
-            if t.dtype != dt or t.device != env.device or t.dim() != 2 or int(t.shape[1]) != n_env or int(t.shape[0]) < 1 or \
-                    t.stride(1) != 1 or t.stride(0) < n_env:
-                raise ValueError("ReturnFilter: %s must be a %s tensor [K, %d] on %s with unit-stride rows (got %s %s, strides %s, on %s)"
-                                 % (name, dt, n_env, env.device, t.dtype, tuple(t.shape), tuple(t.stride()), t.device))
-        K, pitch = int(rew.shape[0]), int(rew.stride(0))
-        if int(done.shape[0]) != K or int(done.stride(0)) != pitch:
-            raise ValueError("ReturnFilter: rew and done must have the same number of rows and the same row pitch")
-        out = torch.empty((K, pitch), dtype=torch.float64, device=env.device)[:, :n_env]
+        K, pitch = self._rows("ReturnFilter", rew, done)
+        out = torch.empty((K, pitch), dtype=torch.float64, device=env.device)[:, :int(env.num_envs)]
         denom = torch.empty((K, self.n_members), dtype=torch.float64, device=env.device)
-        rec = self.to_native(min(K, N.RET_FILTER_MAX_STEPS))
-        with torch.cuda.device(env.device):
-            for k0 in range(0, K, N.RET_FILTER_MAX_STEPS):
-                k1 = min(K, k0 + N.RET_FILTER_MAX_STEPS)
-                N.check(N.lib().ssg_ret_filter_apply(env._h, C.byref(rec), k1 - k0, C.c_void_p(rew[k0].data_ptr()),
-                                                     C.c_void_p(done[k0].data_ptr()), pitch, C.c_void_p(out[k0].data_ptr()),
-                                                     C.c_void_p(denom[k0].data_ptr()), env._stream()), env._h, "ssg_ret_filter_apply")
+        self._pieces(K, lambda rec, k0, k1: env.enqueue("ssg_ret_filter_apply", rec, k1 - k0, rew[k0].data_ptr(), done[k0].data_ptr(), pitch,
+                                                        out[k0].data_ptr(), denom[k0].data_ptr()))
         return out, denom
 
-    def _job_buffers(self, who, rew, done=None):
-        """(K, row pitch) of a job call's [K, N] buffers, checked as ``normalise`` checks its own."""
-        torch = _torch()
-        env = self.env
-        n_env = int(env.num_envs)
+    def _job_rows(self, who, rew, done=None):
+        """``_rows`` of a job call's buffers, for an updating job filter only."""
         if not self.job:
             raise ValueError("ReturnFilter.%s: this filter was not made with job=True (its statistics are this handle's: use apply)" % who)
         if not self.updating:
             raise ValueError("ReturnFilter.%s: a frozen filter needs no rows (apply divides by the state's own denom)" % who)
-        for name, t, dt in (("rew", rew, torch.float64), ("done", done, torch.uint8)):
-            if t is None:
-                continue
-            if t.dtype != dt or t.device != env.device or t.dim() != 2 or int(t.shape[1]) != n_env or int(t.shape[0]) < 1 or \
-                    t.stride(1) != 1 or t.stride(0) < n_env:
-                raise ValueError("ReturnFilter.%s: %s must be a %s tensor [K, %d] on %s with unit-stride rows (got %s %s, strides %s, on %s)"
-                                 % (who, name, dt, n_env, env.device, t.dtype, tuple(t.shape), tuple(t.stride()), t.device))
-        K, pitch = int(rew.shape[0]), int(rew.stride(0))
-        if done is not None and (int(done.shape[0]) != K or int(done.stride(0)) != pitch):
-            raise ValueError("ReturnFilter.%s: rew and done must have the same number of rows and the same row pitch" % who)
-        return K, pitch
+        return self._rows("ReturnFilter." + who, rew, done)
 
     def shard_rows(self, batch):
         """The first half of a job filter's ``apply`` (ssg_ret_filter_batches): walk batch["rew"] / batch["done"] (the carry is
         updated) and reduce this rank's envs to one row {mean, M2, 0, n} per step.  Returns the rows, f64 [K, 4] on the device; the
         state is neither read nor written.  Rollouts longer than the library's cap are served in several calls."""
-        torch = _torch()
         env = self.env
         rew, done = batch["rew"], batch["done"]
-        K, pitch = self._job_buffers("shard_rows", rew, done)
-        rows = torch.empty((K, N.FILTER_ROWS), dtype=torch.float64, device=env.device)
-        rec = self.to_native(min(K, N.RET_FILTER_MAX_STEPS))
-        with torch.cuda.device(env.device):
-            for k0 in range(0, K, N.RET_FILTER_MAX_STEPS):
-                k1 = min(K, k0 + N.RET_FILTER_MAX_STEPS)
-                N.check(N.lib().ssg_ret_filter_batches(env._h, C.byref(rec), k1 - k0, C.c_void_p(rew[k0].data_ptr()),
-                                                       C.c_void_p(done[k0].data_ptr()), pitch, C.c_void_p(rows[k0].data_ptr()),
-                                                       env._stream()), env._h, "ssg_ret_filter_batches")
+        K, pitch = self._job_rows("shard_rows", rew, done)
+        rows = _torch().empty((K, N.FILTER_ROWS), dtype=_torch().float64, device=env.device)
+        self._pieces(K, lambda rec, k0, k1: env.enqueue("ssg_ret_filter_batches", rec, k1 - k0, rew[k0].data_ptr(), done[k0].data_ptr(), pitch,
+                                                        rows[k0].data_ptr()))
         return rows
 
     def apply_rows(self, batch, rows):
@@ -288,23 +273,21 @@ class ReturnFilter(object):
         torch = _torch()
         env = self.env
         rew = batch["rew"]
-        K, pitch = self._job_buffers("apply_rows", rew)
+        K, pitch = self._job_rows("apply_rows", rew)
+        # (any strides serve: every piece is made contiguous below)
         if (rows.dtype != torch.float64 or rows.device != self.state.device or rows.dim() != 3 or not 1 <= int(rows.shape[0]) <= N.DP_MAX_SHARDS
                 or tuple(rows.shape[1:]) != (K, N.FILTER_ROWS)):
             raise ValueError("ReturnFilter.apply_rows: rows must be a float64 tensor (W in 1..%d, %d, %d) on %s (got %s %s on %s)"
                              % (N.DP_MAX_SHARDS, K, N.FILTER_ROWS, self.state.device, rows.dtype, tuple(rows.shape), rows.device))
         W = int(rows.shape[0])
-        n_env = int(env.num_envs)
-        out = torch.empty((K, pitch), dtype=torch.float64, device=env.device)[:, :n_env]
+        out = torch.empty((K, pitch), dtype=torch.float64, device=env.device)[:, :int(env.num_envs)]
         denom = torch.empty((K, 1), dtype=torch.float64, device=env.device)
-        rec = self.to_native(min(K, N.RET_FILTER_MAX_STEPS))
-        with torch.cuda.device(env.device):
-            for k0 in range(0, K, N.RET_FILTER_MAX_STEPS):
-                k1 = min(K, k0 + N.RET_FILTER_MAX_STEPS)
-                part = rows[:, k0:k1].contiguous()  # (the ranks' rows of this call's steps, [W, k1 - k0, 4]; the whole tensor when K fits)
-                N.check(N.lib().ssg_ret_filter_apply_rows(env._h, C.byref(rec), k1 - k0, C.c_void_p(part.data_ptr()), W,
-                                                          C.c_void_p(rew[k0].data_ptr()), pitch, C.c_void_p(out[k0].data_ptr()),
-                                                          C.c_void_p(denom[k0].data_ptr()), env._stream()), env._h, "ssg_ret_filter_apply_rows")
+
+        def piece(rec, k0, k1):
+            part = rows[:, k0:k1].contiguous()  # (the ranks' rows of this call's steps, [W, k1 - k0, 4]; the whole tensor when K fits)
+            env.enqueue("ssg_ret_filter_apply_rows", rec, k1 - k0, part.data_ptr(), W, rew[k0].data_ptr(), pitch, out[k0].data_ptr(),
+                        denom[k0].data_ptr())
+        self._pieces(K, piece)
         batch["rew_norm"], batch["rew_denom"] = out, denom
         return out
 

@@ -37,11 +37,7 @@ import numpy as np
 from . import _native as N
 from . import config as cfgmod
 from . import spaces, worldgen
-
-
-def _torch():
-    import torch
-    return torch
+from ._native import _torch
 
 
 def _trainer_bases():
@@ -213,11 +209,11 @@ class ShipVecEnv(*_BASES):
     def _create_handle(self):
         """ssg_create, then the two device blocks: the state blob (bound) and the output block, whose addresses `_out` keeps."""
         torch = _torch()
-        self._lib = L = N.lib()
+        self._lib = N.lib()
         self._h = C.c_void_p()
-        N.check(L.ssg_create(C.byref(self.cfg), C.byref(self._h)), None, "ssg_create")
+        N.call("ssg_create", C.byref(self.cfg), C.byref(self._h))
         nbytes = C.c_size_t()
-        N.check(L.ssg_state_nbytes(self._h, C.byref(nbytes)), self._h, "ssg_state_nbytes")
+        self.call("ssg_state_nbytes", C.byref(nbytes))
         # obs | reward | done | flags are views of ONE device block (256-byte aligned sections), so that the numpy protocols
         # (SB VecEnv / RLlib VectorEnv) bring a whole step to the host with ONE device -> host copy into a pinned block
         n_, D_ = self.num_envs, self.states_history
@@ -226,14 +222,13 @@ class ShipVecEnv(*_BASES):
         self._o_done = self._o_rew + up(n_ * 8)
         self._o_flags = self._o_done + up(n_)
         self._out_nbytes = self._o_flags + up(n_)
-        with torch.cuda.device(self.device):
-            self.state = torch.zeros(nbytes.value, dtype=torch.uint8, device=self.device)
-            self._out_blob = torch.zeros(self._out_nbytes, dtype=torch.uint8, device=self.device)
-            self.obs, self.reward, self.done, self.flags = self._blob_views(self._out_blob)
-            self._actions = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+        self.state = torch.zeros(nbytes.value, dtype=torch.uint8, device=self.device)
+        self._out_blob = torch.zeros(self._out_nbytes, dtype=torch.uint8, device=self.device)
+        self.obs, self.reward, self.done, self.flags = self._blob_views(self._out_blob)
+        self._actions = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
         # the four output addresses as plain integers, for the launch path: the block is allocated once and only ever copied into
         self._out = tuple(t.data_ptr() for t in (self.obs, self.reward, self.done, self.flags))
-        N.check(L.ssg_bind_state(self._h, N.ptr(self.state)), self._h, "ssg_bind_state")
+        self.call("ssg_bind_state", self.state.data_ptr())
 
     def _first_bank(self, bank, n_maps, map_seed):
         """The constructor's map bank, per map mode."""
@@ -253,8 +248,7 @@ class ShipVecEnv(*_BASES):
                 self._fresh_world(e)
             self.set_bank(self.bank_host)
         else:
-            with torch.cuda.device(self.device):
-                bank = torch.zeros((self.num_envs * self.ring, N.MAP_STRIDE), dtype=torch.float64, device=self.device)
+            bank = torch.zeros((self.num_envs * self.ring, N.MAP_STRIDE), dtype=torch.float64, device=self.device)
             self.map_seed = int(map_seed)
             self.set_bank(bank)
             self.refill_worlds(self.map_seed)  # fills every ring: episodes 0 .. ring-1 of every env
@@ -297,27 +291,27 @@ class ShipVecEnv(*_BASES):
 
     # ------------------------------------------------------------------------------------------------
     def _stream(self):
-        return C.c_void_p(self._cur_stream(self.device).cuda_stream)
+        """The current stream's handle on this env's device, a plain integer."""
+        return self._cur_stream(self.device).cuda_stream
 
     def _arg(self, t, dtypes, shape, what, more_rows=False, exc=ValueError):
-        """THE check of a tensor argument: `t` is what the C call will read it as — of `dtypes` (one dtype or a tuple of them), of
-        `shape` (an int: that many elements, in any shape; a tuple: exactly that shape, or with more_rows a first dimension of at
-        least shape[0]), contiguous and on this env's device — or `exc` is raised, naming the call and the argument (`what`), what
-        was expected and what was got.  Returns the tensor's address, a plain integer."""
-        if ((t.dtype is dtypes or (type(dtypes) is tuple and t.dtype in dtypes)) and t.device == self.device and t.is_contiguous()
-                and (t.numel() == shape if type(shape) is int else
-                     t.dim() == len(shape) and tuple(t.shape[1:]) == tuple(shape[1:])
-                     and (t.shape[0] >= shape[0] if more_rows else t.shape[0] == shape[0]))):
-            return t.data_ptr()
-        want = "%d elements" % shape if type(shape) is int else "shape [%s]" % ", ".join(
-            [(">= %d" if more_rows else "%d") % shape[0]] + ["%d" % s for s in shape[1:]])
-        names = " / ".join(str(d) for d in (dtypes if type(dtypes) is tuple else (dtypes,)))
-        raise exc("%s must be a contiguous %s tensor of %s on %s (got %s %s on %s, strides %s)"
-                  % (what, names, want, self.device, t.dtype, tuple(t.shape), t.device, tuple(t.stride())))
+        """N.arg, THE check of a tensor argument, on this env's device: the tensor's address, or `exc`."""
+        return N.arg(t, dtypes, shape, what, self.device, more_rows, exc)
+
+    def call(self, name, *args):
+        """THE checked call of a host-only entry point (a setter, a getter): `name`(handle, *args) with this env's device current."""
+        with _torch().cuda.device(self.device):
+            N.call(name, self._h, *args, handle=self._h)
+
+    def enqueue(self, name, *args):
+        """THE checked call of an entry point that launches: ``call`` with the current stream's handle as the last argument."""
+        with _torch().cuda.device(self.device):
+            N.call(name, self._h, *args, self._cur_stream(self.device).cuda_stream, handle=self._h)
 
     def _launch(self, what, fn, *args):
-        """THE launch call: fn(handle, *args); a non-zero status with another device current: switch to this env's and repeat; then
-        N.check.  The arguments are plain integers (addresses, counts, the stream's handle), so the success case is one ctypes call."""
+        """The step path's form of ``enqueue``: fn, an export bound beforehand, on (handle, *args), the caller appending the stream's
+        handle itself, and NO device context on the success path — a non-zero status with another device current: switch to this
+        env's and repeat; then N.check.  The arguments are plain integers, so the success case is one ctypes call."""
         rc = fn(self._h, *args)
         if rc:
             torch = _torch()
@@ -359,9 +353,8 @@ class ShipVecEnv(*_BASES):
         history <= 2."""
         torch = _torch()
         if on and self.term_obs is None:
-            with torch.cuda.device(self.device):
-                self.term_obs = torch.zeros((self.num_envs, self.states_history), dtype=torch.float64, device=self.device)
-        N.check(N.lib().ssg_set_terminal_obs(self._h, N.ptr(self.term_obs if on else None)), self._h, "ssg_set_terminal_obs")
+            self.term_obs = torch.zeros((self.num_envs, self.states_history), dtype=torch.float64, device=self.device)
+        self.call("ssg_set_terminal_obs", N.ptr(self.term_obs if on else None))
         if not on:
             self.term_obs = None
         return self.term_obs
@@ -381,8 +374,7 @@ class ShipVecEnv(*_BASES):
         self._arg(bank, torch.float64, (0, N.MAP_STRIDE), "set_bank: bank", more_rows=True, exc=AssertionError)
         self.bank = bank
         self.n_maps = int(bank.shape[0])
-        with torch.cuda.device(self.device):
-            N.check(N.lib().ssg_set_map_bank(self._h, N.ptr(bank), self.n_maps), self._h, "ssg_set_map_bank")
+        self.call("ssg_set_map_bank", bank.data_ptr(), self.n_maps)
 
     def regenerate_bank(self, seed, width_frac=None, n_maps=None, return_raw=False):
         """Refresh the map bank ON THE DEVICE (no host geometry, no upload): n_maps brand-new rivers and goal paths
@@ -392,12 +384,9 @@ class ShipVecEnv(*_BASES):
         torch = _torch()
         n_maps = self.n_maps if n_maps is None else int(n_maps)
         wf = self.width_frac if width_frac is None else float(width_frac)
-        with torch.cuda.device(self.device):
-            bank = self.bank if n_maps == self.n_maps else torch.empty((n_maps, N.MAP_STRIDE), dtype=torch.float64,
-                                                                      device=self.device)
-            raw = torch.empty((n_maps, 48 + 3 * self.cfg.n_goals), dtype=torch.float64, device=self.device) if return_raw else None
-            N.check(N.lib().ssg_generate_bank(self._h, int(seed), wf, N.ptr(bank), n_maps, N.ptr(raw), self._stream()),
-                    self._h, "ssg_generate_bank")
+        bank = self.bank if n_maps == self.n_maps else torch.empty((n_maps, N.MAP_STRIDE), dtype=torch.float64, device=self.device)
+        raw = torch.empty((n_maps, 48 + 3 * self.cfg.n_goals), dtype=torch.float64, device=self.device) if return_raw else None
+        self.enqueue("ssg_generate_bank", int(seed), wf, bank.data_ptr(), n_maps, N.ptr(raw))
         self.bank_polys = self.bank_goals = None  # host copies no longer describe the bank
         if bank is not self.bank:
             self.set_bank(bank)
@@ -415,19 +404,16 @@ class ShipVecEnv(*_BASES):
         self.map_seed = seed
         if width_frac is not None:
             self.width_frac = float(width_frac)
-        with torch.cuda.device(self.device):
-            raw = None
-            if return_raw:
-                raw = torch.full((self.num_envs * self.ring, 48 + 3 * self.cfg.n_goals), float("nan"), dtype=torch.float64,
-                                 device=self.device)
-            N.check(N.lib().ssg_refill_worlds(self._h, seed, self.width_frac, N.ptr(raw), self._stream()), self._h, "ssg_refill_worlds")
+        raw = None
+        if return_raw:
+            raw = torch.full((self.num_envs * self.ring, 48 + 3 * self.cfg.n_goals), float("nan"), dtype=torch.float64, device=self.device)
+        self.enqueue("ssg_refill_worlds", seed, self.width_frac, N.ptr(raw))
         return raw
 
     def launch_geometry(self):
         """(envs per workgroup, bank staged in LDS?, dynamic LDS bytes per workgroup) of the step kernel for this handle."""
         epw, lds, nb = C.c_int(), C.c_int(), C.c_size_t()
-        N.check(N.lib().ssg_debug_launch_geometry(self._h, C.byref(epw), C.byref(lds), C.byref(nb)), self._h,
-                "ssg_debug_launch_geometry")
+        self.call("ssg_debug_launch_geometry", C.byref(epw), C.byref(lds), C.byref(nb))
         return epw.value, bool(lds.value), nb.value
 
     def field(self, fid):
@@ -436,8 +422,7 @@ class ShipVecEnv(*_BASES):
         which envs the dyn kernels visit next step was decided from the state the last step ended with (ssg_dyn_invalidate)."""
         torch = _torch()
         off, es, nc, stride = C.c_size_t(), C.c_int(), C.c_int(), C.c_size_t()
-        N.check(N.lib().ssg_state_field(self._h, fid, C.byref(off), C.byref(es), C.byref(nc), C.byref(stride)), self._h,
-                "ssg_state_field")
+        self.call("ssg_state_field", fid, C.byref(off), C.byref(es), C.byref(nc), C.byref(stride))
         dt = {8: torch.float64, 4: torch.int32, 1: torch.uint8}[es.value]
         if fid == N.F_DYN_LIVE:
             dt = torch.int64                  # (a 64-bit mask)
@@ -461,9 +446,7 @@ class ShipVecEnv(*_BASES):
         cpSpaceStep visits was decided from the state the last step ended with): ssg_dyn_invalidate.  Also after restoring or
         copying the state blob.  mask: uint8 device tensor [num_envs]
         (envs whose rest bit is cleared) or None = all; the next step's queue is rebuilt from the columns either way."""
-        mp = self._mask_arg(mask, "wake_dynamics")
-        with _torch().cuda.device(self.device):
-            N.check(N.lib().ssg_dyn_invalidate(self._h, mp, self._stream()), self._h, "ssg_dyn_invalidate")
+        self.enqueue("ssg_dyn_invalidate", self._mask_arg(mask, "wake_dynamics"))
 
     def field_stats_tensor(self):
         """int64 device tensor [4]: sum_return*100, sum_length, episodes, goals_hit of this handle (slots summed)."""
@@ -473,13 +456,13 @@ class ShipVecEnv(*_BASES):
         """Config 4 measurement aid (ssg_debug_kernel_times): returns (full cpSpaceStep us, step kernel us, steps) averaged over
         the steps since the previous call, and switches the per-launch HIP events on or off for the calls that follow."""
         a, b, n = C.c_double(), C.c_double(), C.c_uint64()
-        N.check(N.lib().ssg_debug_kernel_times(self._h, int(bool(enable)), C.byref(a), C.byref(b), C.byref(n)), self._h, "ssg_debug_kernel_times")
+        self.call("ssg_debug_kernel_times", int(bool(enable)), C.byref(a), C.byref(b), C.byref(n))
         return float(a.value), float(b.value), int(n.value)
 
     def dyn_counters(self):
         """Config 4: (launches of the full cpSpaceStep, how many of them rebuilt their queue from the per-env flags first)."""
         a, b = C.c_uint64(), C.c_uint64()
-        N.check(N.lib().ssg_debug_dyn_counters(self._h, C.byref(a), C.byref(b)), self._h, "ssg_debug_dyn_counters")
+        self.call("ssg_debug_dyn_counters", C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
 
     def dyn_memo_stats(self):
@@ -619,12 +602,11 @@ class ShipVecEnv(*_BASES):
         if mask is None:
             self._full_reset_done = True
         own_ids = self.map_mode == "fresh" and map_ids is None
-        with torch.cuda.device(self.device):
-            if own_ids:
-                map_ids = torch.arange(self.num_envs, dtype=torch.int32, device=self.device)
-            N.check(N.lib().ssg_reset(self._h, N.ptr(mask), N.ptr(map_ids), N.ptr(dest), self._stream()), self._h, "ssg_reset")
-            if own_ids:
-                torch.cuda.current_stream(self.device).synchronize()  # keep the ids alive until the kernel ran
+        if own_ids:
+            map_ids = torch.arange(self.num_envs, dtype=torch.int32, device=self.device)
+        self.enqueue("ssg_reset", N.ptr(mask), N.ptr(map_ids), dest.data_ptr())
+        if own_ids:
+            torch.cuda.current_stream(self.device).synchronize()  # keep the ids alive until the kernel ran
 
     def _host_reset(self, envs, dest):
         """THE host-driven reset: `envs` — a host bool array [N], one env index, or None for a full reset — are re-initialised by
@@ -749,19 +731,17 @@ class ShipVecEnv(*_BASES):
             raise ValueError("%s: greedy=True reads no uniforms (pass one or the other)" % what)
         n, D = self.num_envs, self.states_history
         up = self._f32_rows(uniforms, (n,), what + ": uniforms")
-        with torch.cuda.device(self.device):
-            act = torch.empty(n, dtype=torch.int32, device=self.device)
-            logp = torch.empty(n, dtype=torch.float32, device=self.device)
-            val = torch.empty(n, dtype=torch.float32, device=self.device)
-            x = x_out if x_out is not None else torch.empty((n, D), dtype=torch.float32, device=self.device)
-            xp = self._f32_rows(x, (n, D), what + ": x_out")
-            rec = record.to_native()
-            if greedy:
-                c_name, draw = c_name + "_greedy", ()
-            else:
-                draw = (up, int(seed), int(step))
-            N.check(getattr(N.lib(), c_name)(self._h, C.byref(rec), N.ptr(self.obs), *draw, N.ptr(act), N.ptr(logp), N.ptr(val), xp,
-                                             self._stream()), self._h, c_name)
+        act = torch.empty(n, dtype=torch.int32, device=self.device)
+        logp = torch.empty(n, dtype=torch.float32, device=self.device)
+        val = torch.empty(n, dtype=torch.float32, device=self.device)
+        x = x_out if x_out is not None else torch.empty((n, D), dtype=torch.float32, device=self.device)
+        xp = self._f32_rows(x, (n, D), what + ": x_out")
+        rec = record.to_native()
+        if greedy:
+            c_name, draw = c_name + "_greedy", ()
+        else:
+            draw = (up, int(seed), int(step))
+        self.enqueue(c_name, C.byref(rec), self.obs.data_ptr(), *draw, act.data_ptr(), logp.data_ptr(), val.data_ptr(), xp)
         return act, logp, val, x
 
     def rollout_policy(self, policy, K, seed=0, step0=0, uniforms=None, out=None):
@@ -775,19 +755,16 @@ class ShipVecEnv(*_BASES):
 
     def _rollout(self, check, record, c_name, what, K, seed, step0, uniforms, out):
         """rollout_policy / rollout_population: `check` judges the record, c_name is its entry point."""
-        torch = _torch()
         check(record, what)
         K, n = int(K), self.num_envs
         if K < 1:
             raise ValueError("%s: K must be >= 1" % what)
         up = self._f32_rows(uniforms, (K, n), what + ": uniforms")
-        with torch.cuda.device(self.device):
-            boot = self._timeout_rows(K, out, what)
-            out, p = self._rollout_buffers(K, out, what)
-            rec = record.to_native()
-            N.check(getattr(N.lib(), c_name)(self._h, C.byref(rec), K, up, int(seed), int(step0), N.ptr(self.obs),
-                                             p["act"], p["logp"], p["val"], p["obs"], p["rew"], p["done"], p["flags"], p["last_val"],
-                                             n, self._stream()), self._h, c_name)
+        boot = self._timeout_rows(K, out, what)
+        out, p = self._rollout_buffers(K, out, what)
+        rec = record.to_native()
+        self.enqueue(c_name, C.byref(rec), K, up, int(seed), int(step0), self.obs.data_ptr(), p["act"], p["logp"], p["val"], p["obs"],
+                     p["rew"], p["done"], p["flags"], p["last_val"], n)
         res = {k: (v[:K] if k != "last_val" else v) for k, v in out.items() if k != "boot"}
         if boot is not None:  # (with the bootstrap off a caller's out["boot"] is not part of the batch: nothing wrote it)
             res["boot"] = boot[:K]
@@ -824,7 +801,7 @@ class ShipVecEnv(*_BASES):
         members only.  None unbinds.  Env state is not touched: envs are fungible, so a layout may be re-bound between updates."""
         torch = _torch()
         if sizes is None:
-            N.check(N.lib().ssg_pop_set_slices(self._h, 0, None, None), self._h, "ssg_pop_set_slices")
+            self.call("ssg_pop_set_slices", 0, None, None)
             self._pop_slices = None
             return
         sizes = [int(s) for s in sizes]
@@ -832,11 +809,11 @@ class ShipVecEnv(*_BASES):
         arr = (C.c_int32 * max(P, 1))(*sizes)
         n = N.POP_SLICE_ROW * P
         buf = (C.c_int32 * max(n, 1))()
-        N.check(N.lib().ssg_pop_pack_slices(P, arr, buf, n), None, "ssg_pop_pack_slices")
+        N.call("ssg_pop_pack_slices", P, arr, buf, n)
         if sum(sizes) != self.num_envs:
             raise ValueError("set_population_slices: the sizes sum to %d, the handle has %d envs" % (sum(sizes), self.num_envs))
         table = torch.tensor(list(buf), dtype=torch.int32).to(self.device)
-        N.check(N.lib().ssg_pop_set_slices(self._h, P, arr, N.ptr(table)), self._h, "ssg_pop_set_slices")
+        self.call("ssg_pop_set_slices", P, arr, table.data_ptr())
         # (the device table is the caller's memory; an earlier one stays alive until launches that read it have been enqueued AND run:
         # torch's allocator does not hand a freed block to another stream's work before that)
         self._pop_slices = (sizes, table)
@@ -847,9 +824,9 @@ class ShipVecEnv(*_BASES):
         if self._pop_slices is None:
             return None
         P = C.c_int()
-        N.check(N.lib().ssg_pop_get_slices(self._h, C.byref(P), None), self._h, "ssg_pop_get_slices")
+        self.call("ssg_pop_get_slices", C.byref(P), None)
         out = (C.c_int32 * max(P.value, 1))()
-        N.check(N.lib().ssg_pop_get_slices(self._h, C.byref(P), out), self._h, "ssg_pop_get_slices")
+        self.call("ssg_pop_get_slices", C.byref(P), out)
         return [int(out[m]) for m in range(P.value)] or None
 
     def population_act(self, population, seed=0, step=0, uniforms=None, x_out=None, greedy=False):
@@ -879,7 +856,7 @@ class ShipVecEnv(*_BASES):
         history <= 2, like enable_terminal_obs, whose own binding stays in place between rollouts.  A refused call leaves the
         previous state."""
         if not on:
-            N.check(N.lib().ssg_set_timeout_boot(self._h, None), self._h, "ssg_set_timeout_boot")
+            self.call("ssg_set_timeout_boot", None)
             self._timeout_boot = None
             return
         self._bind_timeout_boot(max(1, int(rows or 1)), None)
@@ -888,7 +865,7 @@ class ShipVecEnv(*_BASES):
     def timeout_bootstrap(self):
         """The rows the bound time-out buffers serve (ssg_get_timeout_boot), or 0 with the bootstrap off."""
         rec = N.TimeoutBootRecord()
-        N.check(N.lib().ssg_get_timeout_boot(self._h, C.byref(rec)), self._h, "ssg_get_timeout_boot")
+        self.call("ssg_get_timeout_boot", C.byref(rec))
         return int(rec.rows) if rec.struct_size else 0
 
     def _bind_timeout_boot(self, rows, boot):
@@ -896,18 +873,17 @@ class ShipVecEnv(*_BASES):
         the kept or a new f32 [rows, N])."""
         torch = _torch()
         old = self._timeout_boot
-        with torch.cuda.device(self.device):
-            if old is not None and old["term_obs"].shape[0] >= rows:
-                term = old["term_obs"]
-            else:
-                old = None  # (grown: the kept boot rows are too short as well)
-                term = torch.empty((rows, self.num_envs, self.states_history), dtype=torch.float64, device=self.device)
-            if boot is None:
-                boot = old["boot"] if old is not None else torch.empty((term.shape[0], self.num_envs), dtype=torch.float32, device=self.device)
+        if old is not None and old["term_obs"].shape[0] >= rows:
+            term = old["term_obs"]
+        else:
+            old = None  # (grown: the kept boot rows are too short as well)
+            term = torch.empty((rows, self.num_envs, self.states_history), dtype=torch.float64, device=self.device)
+        if boot is None:
+            boot = old["boot"] if old is not None else torch.empty((term.shape[0], self.num_envs), dtype=torch.float32, device=self.device)
         rec = N.TimeoutBootRecord()
         rec.struct_size, rec.rows = C.sizeof(N.TimeoutBootRecord), min(int(term.shape[0]), int(boot.shape[0]))
         rec.dev_term_obs_KND, rec.dev_boot_KN = term.data_ptr(), boot.data_ptr()
-        N.check(N.lib().ssg_set_timeout_boot(self._h, C.byref(rec)), self._h, "ssg_set_timeout_boot")
+        self.call("ssg_set_timeout_boot", C.byref(rec))
         self._timeout_boot = {"term_obs": term, "boot": boot}
 
     def timeout_values(self, record, flags, term_obs, out=None):
@@ -924,13 +900,11 @@ class ShipVecEnv(*_BASES):
         fp = self._arg(flags, torch.uint8, (1, n), what + ": flags", more_rows=True)
         K = int(flags.shape[0])
         tp = self._arg(term_obs, torch.float64, (K, n, D), what + ": term_obs")
-        with torch.cuda.device(self.device):
-            if out is None:
-                out = torch.empty((K, n), dtype=torch.float32, device=self.device)
-            op = self._f32_rows(out, (K, n), what + ": out")
-            rec = record.to_native()
-            name = "ssg_pop_timeout_values" if pop else "ssg_timeout_values"
-            N.check(getattr(N.lib(), name)(self._h, C.byref(rec), K, fp, tp, op, n, self._stream()), self._h, name)
+        if out is None:
+            out = torch.empty((K, n), dtype=torch.float32, device=self.device)
+        op = self._f32_rows(out, (K, n), what + ": out")
+        rec = record.to_native()
+        self.enqueue("ssg_pop_timeout_values" if pop else "ssg_timeout_values", C.byref(rec), K, fp, tp, op, n)
         return out[:K]
 
     def _timeout_rows(self, K, out, what):
@@ -959,14 +933,14 @@ class ShipVecEnv(*_BASES):
         reference to the filter (whose tensors the launches read).  None unbinds; a refused binding leaves the old one in place."""
         old = self._obs_filter
         if f is None:
-            N.check(N.lib().ssg_set_obs_filter(self._h, None), self._h, "ssg_set_obs_filter")
+            self.call("ssg_set_obs_filter", None)
         else:
             if f.state.device != self.device:
                 raise ValueError("set_obs_filter: the filter lives on %s, the env on %s" % (f.state.device, self.device))
             rec = f.to_native()
-            N.check(N.lib().ssg_set_obs_filter(self._h, C.byref(rec)), self._h, "ssg_set_obs_filter")
+            self.call("ssg_set_obs_filter", C.byref(rec))
             if getattr(f, "buffer", None) is not None:  # a job filter: the rollout loops merge into its buffer too (the call above dropped it)
-                N.check(N.lib().ssg_set_obs_filter_buffer(self._h, C.c_void_p(f.buffer.data_ptr())), self._h, "ssg_set_obs_filter_buffer")
+                self.call("ssg_set_obs_filter_buffer", f.buffer.data_ptr())
         if old is not None and old is not f and self in old._bound:
             old._bound.remove(self)
         if f is not None and self not in f._bound:
@@ -986,45 +960,42 @@ class ShipVecEnv(*_BASES):
         bound) or N.ADV_NORM_MINIBATCH (PPO2's rule) with `scratch`, a uint8 device tensor of ssg_ppo_adv_norm_nbytes(n_members) bytes
         that the caller keeps alive.  Host only; a refused binding leaves the old one in place."""
         nb = scratch.numel() * scratch.element_size() if scratch is not None else 0
-        N.check(N.lib().ssg_ppo_set_adv_norm(self._h, int(mode), int(n_members), N.ptr(scratch), nb), self._h, "ssg_ppo_set_adv_norm")
+        self.call("ssg_ppo_set_adv_norm", int(mode), int(n_members), N.ptr(scratch), nb)
         self._adv_norm_scratch = scratch if int(mode) == N.ADV_NORM_MINIBATCH else None
         self._adv_table = None  # (a successful binding of a mode drops a bound table)
 
     def adv_norm(self):
         """(mode, n_members) as bound (ssg_ppo_get_adv_norm)."""
         mode, members = C.c_int(), C.c_int()
-        N.check(N.lib().ssg_ppo_get_adv_norm(self._h, C.byref(mode), C.byref(members)), self._h, "ssg_ppo_get_adv_norm")
+        self.call("ssg_ppo_get_adv_norm", C.byref(mode), C.byref(members))
         return mode.value, members.value
 
     def set_adv_table(self, table):
         """Bind the job's table of per-minibatch advantage statistics (ssg_ppo_set_adv_table): a contiguous f32 [rows, 4] device tensor
         that the caller keeps alive, row 0 selected; None unbinds.  While it is bound the gradient calls read the selected row and
         launch no statistics kernel, and the mode is N.ADV_NORM_BATCH.  Host only; a refused binding leaves the old one in place."""
-        if table is not None and (table.dtype != _torch().float32 or table.dim() != 2 or table.shape[1] != 4 or not table.is_contiguous()):
-            raise ValueError("ShipVecEnv.set_adv_table: the table must be a contiguous f32 [rows, 4] tensor (got %s %s)"
-                             % (table.dtype, tuple(table.shape)))
-        N.check(N.lib().ssg_ppo_set_adv_table(self._h, N.ptr(table), 0 if table is None else int(table.shape[0])), self._h,
-                "ssg_ppo_set_adv_table")
+        if table is not None:  # (judged on whichever device it lives on: this call has never asked for the env's)
+            N.arg(table, _torch().float32, (0, 4), "ShipVecEnv.set_adv_table: table", table.device, more_rows=True)
+        self.call("ssg_ppo_set_adv_table", N.ptr(table), 0 if table is None else int(table.shape[0]))
         self._adv_table = table
         if table is not None:
             self._adv_norm_scratch = None
 
     def select_adv_row(self, row):
         """The row of the bound table the next gradient call reads (ssg_ppo_select_adv_row).  Host only."""
-        N.check(N.lib().ssg_ppo_select_adv_row(self._h, int(row)), self._h, "ssg_ppo_select_adv_row")
+        self.call("ssg_ppo_select_adv_row", int(row))
 
     def adv_table(self):
         """(address or None, rows, selected row) as bound (ssg_ppo_get_adv_table)."""
         table, rows, row = C.c_void_p(), C.c_int(), C.c_int()
-        N.check(N.lib().ssg_ppo_get_adv_table(self._h, C.byref(table), C.byref(rows), C.byref(row)), self._h, "ssg_ppo_get_adv_table")
+        self.call("ssg_ppo_get_adv_table", C.byref(table), C.byref(rows), C.byref(row))
         return table.value, rows.value, row.value
 
     def random_actions(self, seed, step0, K):
         """int32 [K, N] Philox action stream keyed by (seed, step, global env id), generated on the device."""
         torch = _torch()
-        with torch.cuda.device(self.device):
-            out = torch.empty((K, self.num_envs), dtype=torch.int32, device=self.device)
-            N.check(N.lib().ssg_fill_actions(self._h, int(seed), int(step0), int(K), N.ptr(out), self._stream()), self._h, "ssg_fill_actions")
+        out = torch.empty((K, self.num_envs), dtype=torch.int32, device=self.device)
+        self.enqueue("ssg_fill_actions", int(seed), int(step0), int(K), out.data_ptr())
         return out
 
     # ------------------------------------------------------------------------------------------------
@@ -1112,10 +1083,8 @@ class ShipVecEnv(*_BASES):
         torch = _torch()
         width = int(width or self.bounds[0])
         height = int(height or self.bounds[1])
-        with torch.cuda.device(self.device):
-            img = torch.empty((width, height, 3), dtype=torch.uint8, device=self.device)
-            N.check(N.lib().ssg_render(self._h, int(env), width, height, N.ptr(img), 1 if debug else 0,
-                                       self._stream()), self._h, "ssg_render")
+        img = torch.empty((width, height, 3), dtype=torch.uint8, device=self.device)
+        self.enqueue("ssg_render", int(env), width, height, img.data_ptr(), 1 if debug else 0)
         return img
 
     def get_screens(self, envs, width=None, height=None, debug=True):
@@ -1131,8 +1100,7 @@ class ShipVecEnv(*_BASES):
             else:
                 ids = torch.tensor([int(e) for e in envs], dtype=torch.int32, device=self.device)
             out = torch.empty((ids.numel(), width, height, 3), dtype=torch.uint8, device=self.device)
-            N.check(N.lib().ssg_render_envs(self._h, N.ptr(ids), ids.numel(), width, height, N.ptr(out),
-                                            1 if debug else 0, self._stream()), self._h, "ssg_render_envs")
+        self.enqueue("ssg_render_envs", ids.data_ptr(), ids.numel(), width, height, out.data_ptr(), 1 if debug else 0)
         return out
 
     def render(self, mode='human', close=False, env=0):

@@ -27,15 +27,13 @@ def build_record(left, right, goals, spawn):
     right = np.ascontiguousarray(right, dtype=np.float64).reshape(-1, 2)
     goals = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 2)
     rec = np.zeros(N.MAP_STRIDE, dtype=np.float64)
-    N.check(N.lib().ssg_host_build_map(_dp(left), len(left), _dp(right), len(right), _dp(goals), len(goals),
-                                        float(spawn[0]), float(spawn[1]), _dp(rec)), None, "ssg_host_build_map")
+    N.call("ssg_host_build_map", _dp(left), len(left), _dp(right), len(right), _dp(goals), len(goals), float(spawn[0]), float(spawn[1]), _dp(rec))
     return rec
 
 
 def goal_x_range(rec, width, y):
     lo, hi, hit = C.c_double(), C.c_double(), C.c_int()
-    N.check(N.lib().ssg_host_goal_x_range(_dp(rec), float(width), float(y), C.byref(lo), C.byref(hi), C.byref(hit)),
-            None, "ssg_host_goal_x_range")
+    N.call("ssg_host_goal_x_range", _dp(rec), float(width), float(y), C.byref(lo), C.byref(hi), C.byref(hit))
     return bool(hit.value), lo.value, hi.value
 
 

@@ -27,6 +27,18 @@ def test_library_exports_every_declared_symbol(native):
     assert L.ssg_abi_version() == native.ABI_VERSION
 
 
+def test_every_export_declares_its_argument_types(native):
+    """The host layer passes addresses as plain Python integers (``t.data_ptr()``).  ctypes converts an integer argument of a function
+    WITHOUT argtypes to a C int, which would cut a 64-bit address to 32 bits without a word: every export that takes arguments from
+    the host layer must declare them."""
+    L = native.lib()
+    for name in native.EXPORTS:
+        if name in ("ssg_abi_version", "ssg_strerror", "ssg_last_error"):
+            continue
+        argtypes = getattr(L, name).argtypes
+        assert argtypes is not None and len(argtypes) >= 1, "%s has no argtypes in _native.lib()" % name
+
+
 def test_header_constants_match_binding(native):
     text = open(os.path.join(ROOT, "include", "shipsim.h")).read()
     consts = dict(re.findall(r"#define\s+(SSG_[A-Z_]+)\s+(0x[0-9a-fA-F]+u?|\d+)", text))
